@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — Mvis/s of the w-projection gridder (convgrid2 semantics) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the result line; the
+per-kernel and roofline figures in it come from events recorded during the timed steps.  --full adds what the headline
+figure does not need: the run's checksum self-check, the CPU baseline with its parity check (unless --no-cpu) and, N > 1,
+the collective timed on its own.
 
 One process per GPU.  Started under `python -m torch.distributed.run --nproc-per-node N` the ranks come from
 the environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*); started as a plain command with --gpus N > 1 this
@@ -11,13 +16,15 @@ only), of which rank r grids a contiguous range onto a private N x N complex128 
 summed with ONE RCCL fp64 collective per step, issued on a side stream so that it overlaps the next step's gridding.
 --scaling weak (default): the stream has n_gpus x vis_per_gpu visibilities, every GPU grids vis_per_gpu of them;
 --scaling strong: the stream has the workload's visibilities in total, every GPU grids 1 / n_gpus of them (the
-N-GPU grid then equals the 1-GPU grid of the same stream).  After the timed steps every run certifies itself: the sum
+N-GPU grid then equals the 1-GPU grid of the same stream).  After the timed steps a --full run certifies itself: the sum
 of the (reduced) grid is compared with the analytic checksum sum_k vis_k * sum_ij K[slice_k] of the stream (all taps are
-in range by construction) and the process exits non-zero if they differ by more than 1e-10 or the library counted an
-internal error.
+in range by construction) and the process exits non-zero if they differ by more than 1e-10 (--full) or the library
+counted an internal error (every run).
 
 A "step" = binning pre-pass + tile kernel over the rank's whole shard (+ grid clear and all-reduce when N > 1),
-inputs already resident in HBM.  Rank 0 prints ONE JSON line.
+inputs already resident in HBM.  Rank 0 prints ONE JSON line.  --dump-outputs DIR: rank 0 then writes the grid the
+last timed step produced as float64 .npy files (dump_outputs); the inputs depend on the arguments only, so two builds
+run with the same arguments can be compared output for output.
 
 Workloads (BASELINE.json configs):
   cfg3 (default; configs[2], the configuration the metric is quoted on): 10^8 synthetic visibilities, 4096^2 grid,
@@ -93,7 +100,16 @@ def parse_args(argv=None):
     ap.add_argument("--aw-cache", type=int, default=1, help="cfg4: per-key aw-kernel de-duplication (1 = on)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only (gloo, no GPU): checks the rank spawning / environment plumbing on a CPU box")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the grid the last timed step produced to DIR/*.npy (float64, a fixed "
+                         "sample of its cells and its row / column sums)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the checksum self-check, the CPU baseline and "
+                         "its parity check (unless --no-cpu), N > 1: the collective timed on its own")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -440,6 +456,30 @@ def cpu_baseline_aw(ctx, u, v, wb, a1, a2, vis, wk, ak, N, sample):
                       f"FFT-free restatement of src/Gridding.hs:318-396,761-811), single thread, {dt:.2f} s"}
 
 
+DUMP_SAMPLE_CELLS = 1 << 20
+DUMP_SAMPLE_SEED = 0x6D75D1
+
+
+def dump_outputs(dirname, G):
+    """--dump-outputs: the grid the last timed step produced - what convgrid2 / convgrid4 hands its caller - as float64
+    .npy files, 24 MB in all whatever the grid size: grid_sample.npy [M, 2] (re, im) at the cells grid_sample_cells.npy
+    (flat row-major indices, the same sorted, seeded draw of M distinct cells for every run of a grid size) and
+    grid_row_sums.npy / grid_col_sums.npy [N, 2], which every cell contributes to."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    N = G.shape[0]
+    m = min(DUMP_SAMPLE_CELLS, N * N)
+    cells = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(N * N, size=m, replace=False))
+    sample = G.reshape(-1)[torch.from_numpy(cells).to(G.device)]
+    arrays = {"grid_sample": torch.view_as_real(sample), "grid_sample_cells": cells.astype(np.float64),
+              "grid_row_sums": torch.view_as_real(G.sum(dim=1)), "grid_col_sums": torch.view_as_real(G.sum(dim=0))}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": dirname, "files": sorted(k + ".npy" for k in arrays), "grid": [N, N], "sample_cells": m}
+
+
 # ---------------------------------------------------------------------------------------------------------
 def main():
     args = parse_args()
@@ -621,11 +661,13 @@ def main():
             b_.zero_()
     ctx.set_option("reserve_cus", reserve)
     counter = [0]
+    last = [None]  # the grid the latest step gridded onto (--dump-outputs)
 
     def step():
         i = counter[0]
         counter[0] += 1
         g = red.begin(i) if red else bufs[i % nbuf]
+        last[0] = g
         if red:
             passes[i % 2] = 0
         passes[i % nbuf] += 1
@@ -669,12 +711,13 @@ def main():
         t = torch.tensor([float(errors)], dtype=torch.float64, device=device)
         dist.all_reduce(t)
         errors = int(t.item())
+    dumped = dump_outputs(args.dump_outputs, last[0]) if (args.dump_outputs and rank == 0) else None
 
-    # ---- the run certifies itself (outside the timed region): the sum of every grid the steps produced against the
-    # analytic checksum of the stream.  N > 1: the reduced grids hold the contributions of ALL ranks (rows the
+    # ---- --full: the run certifies itself (outside the timed region): the sum of every grid the steps produced against
+    # the analytic checksum of the stream.  N > 1: the reduced grids hold the contributions of ALL ranks (rows the
     # collective skipped must then be zero on every rank, or the sums disagree), so the expected value is all-reduced.
     check = None
-    if not aw:
+    if not aw and args.full:
         tc0 = time.perf_counter()
         expect, scale = expected_checksum(u, v, wb, vis, gcf, N)
         ex = torch.stack([expect.real, expect.imag, scale])
@@ -702,6 +745,13 @@ def main():
     # N > 1: what the collective costs on its own (outside the timed region; gridding and all-reduce separately)
     multi = None
     if dist is not None:
+        red.close()  # (the communicator's collectives go back to the context's stream = torch's current stream)
+        ctx._use_torch_stream()
+        multi = {"rccl_ranks": dist.get_world_size(), "collective": args.collective, "scaling": args.scaling,
+                 "reduced_rows": list(rows) if rows else [0, N], "reserve_cus": reserve, "yield_cus": yield_cus, "schedule": schedule,
+                 "gridding_ms_per_step": float(np.mean(ker_ms) + np.mean(pre_ms)),
+                 "combined_ms_per_step": elapsed / args.steps * 1e3}
+    if dist is not None and args.full:
         part = G if rows is None else G[rows[0]:rows[1]]
         tg = torch.view_as_real(part)
 
@@ -713,8 +763,6 @@ def main():
             else:
                 comm.allreduce_grid_rows(G, *rows)
 
-        red.close()  # (the communicator's collectives go back to the context's stream = torch's current stream)
-        ctx._use_torch_stream()
         for _ in range(2):
             one()
         torch.cuda.synchronize()
@@ -727,13 +775,9 @@ def main():
         torch.cuda.synchronize()
         ar_ms = e0.elapsed_time(e1) / 5
         nbytes = int(part.numel() * 16)
-        multi = {"rccl_ranks": dist.get_world_size(), "collective": args.collective, "scaling": args.scaling,
-                 "reduced_rows": list(rows) if rows else [0, N], "reserve_cus": reserve, "yield_cus": yield_cus, "schedule": schedule,
-                 "allreduce_bytes": nbytes, "allreduce_ms_alone": ar_ms,
-                 "allreduce_busbw_GBps": nbytes * 2 * (world - 1) / world / (ar_ms * 1e-3) / 1e9 if world > 1 else None,
-                 "gridding_ms_per_step": float(np.mean(ker_ms) + np.mean(pre_ms)),
-                 "combined_ms_per_step": elapsed / args.steps * 1e3,
-                 "check_rel_err": check["rel_err"] if check else None}
+        multi.update(allreduce_bytes=nbytes, allreduce_ms_alone=ar_ms,
+                     allreduce_busbw_GBps=nbytes * 2 * (world - 1) / world / (ar_ms * 1e-3) / 1e9 if world > 1 else None,
+                     check_rel_err=check["rel_err"] if check else None)
 
     failed = []
     if rank == 0:
@@ -832,12 +876,16 @@ def main():
                 "options": opts,
             },
             "errors": errors,
-            "check": check,
+            "full": args.full,
             "roofline": roof,
         }
+        if args.full:
+            out["check"] = check
         if multi:
             out["multi_gpu"] = multi
-        if world == 1 and not args.no_cpu:
+        if dumped:
+            out["outputs"] = dumped
+        if world == 1 and args.full and not args.no_cpu:
             if aw:
                 out["cpu_baseline"] = cpu_baseline_aw(ctx, u, v, wb, a1, a2, vis, gcf, akerns, N, min(args.cpu_sample or 20_000, n))
             else:

@@ -18,6 +18,9 @@ Provenance of each fixture:
   convgrid2_small.npz DERIVED: seeded random case; expected grid from the numpy restatement.
   wkernel_*.npz       DERIVED: parameter sets of test/GridTesting.hs:85-93,139-150 (theta=0.1, Q=2,
                       npixFF=256, S=31, w in {100,1000}); expected kernels from the numpy restatement.
+  h5_reference_shim_testIO.h5  RECORDED by the reference: the file its own HDF5 shim (hdf5/hdf5.cc, built into
+                      oracle/_ref/ by `make -C oracle ref`) writes for test/Hdf5.hs:36-58 with the arrays of :20-28
+                      (/testD, /testC, /test3).  Skipped, with a note, where that build is absent.
 
 Nothing is read from /root/reference at run time; the literals above are restated here.
 Run:  python oracle/make_golden.py
@@ -143,6 +146,27 @@ def wkernels():
                  expected=k)
 
 
+def h5_reference_shim():
+    import shutil
+    import tempfile
+    ref = os.path.join(HERE, "_ref", "libhdf5ref.so")
+    if not os.path.exists(ref):
+        print(f"h5_reference_shim_testIO.h5 not written: {ref} is not built (make -C oracle ref)")
+        return
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "ska-sdp-accelerate-gridding_amd", "python"))
+    from gridhip import h5io
+    lib = h5io.load(ref)
+    d = np.arange(2000, dtype=np.float64).reshape(1000, 2)                           # testData
+    c = (np.arange(1000) * (1 + 1j)).astype(np.complex128)                           # testDataC
+    t3 = (np.arange(12000) * (1 + 1j)).astype(np.complex128).reshape(2, 3, 1000, 2)  # test3
+    with tempfile.TemporaryDirectory() as tmp:
+        name = os.path.join(tmp, "test")  # the shim appends ".h5"
+        h5io.createh5File(name, lib=lib)
+        for ds, a in (("/testD", d), ("/testC", c), ("/test3", t3)):
+            h5io.createDataset(name, ds, a, lib=lib)
+        shutil.copyfile(name + ".h5", os.path.join(OUT, "h5_reference_shim_testIO.h5"))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     brokennumbers()
@@ -152,5 +176,6 @@ if __name__ == "__main__":
     smalltest_aw()
     convgrid2_small()
     wkernels()
+    h5_reference_shim()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

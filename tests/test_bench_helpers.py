@@ -153,3 +153,41 @@ def test_a_failing_rank_ends_the_job():
     out = subprocess.run([sys.executable, bench.__file__, "--gpus", "2", "--steps", "1", "--warmup", "0"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode != 0
+
+
+def test_plain_run_and_full_run_options():
+    """A plain run is the default; --full, --dump-outputs DIR and --steps are parsed as given, and a run without a
+    timed step is refused (ms_per_step is per timed step)."""
+    a = bench.parse_args([])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (10, 3)
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--steps", "7", "--warmup", "0"])
+    assert a.full and a.dump_outputs == "out" and (a.steps, a.warmup) == (7, 0)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_the_grid_it_is_given(tmp_path):
+    """--dump-outputs' files are float64, hold the given grid (sampled cells, row and column sums), draw the same cells
+    every time, and stay within 64 MB for the largest workload grid."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(5)
+    G = rng.normal(size=(96, 96)) + 1j * rng.normal(size=(96, 96))
+    info = bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(G))
+    f = {n: np.load(tmp_path / "a" / n) for n in info["files"]}
+    assert sorted(f) == ["grid_col_sums.npy", "grid_row_sums.npy", "grid_sample.npy", "grid_sample_cells.npy"]
+    assert all(a.dtype == np.float64 for a in f.values())
+    cells = f["grid_sample_cells.npy"].astype(np.int64)
+    assert np.array_equal(cells, np.arange(96 * 96))  # a grid smaller than the sample: every cell
+    s = f["grid_sample.npy"]
+    assert np.array_equal(s[:, 0] + 1j * s[:, 1], G.reshape(-1)[cells])
+    r, c = f["grid_row_sums.npy"], f["grid_col_sums.npy"]
+    assert np.allclose(r[:, 0] + 1j * r[:, 1], G.sum(axis=1), rtol=0, atol=1e-12)
+    assert np.allclose(c[:, 0] + 1j * c[:, 1], G.sum(axis=0), rtol=0, atol=1e-12)
+    G2 = np.zeros((1100, 1100), dtype=np.complex128)  # more cells than the sample takes
+    bench.dump_outputs(str(tmp_path / "b"), torch.from_numpy(G2))
+    bench.dump_outputs(str(tmp_path / "c"), torch.from_numpy(G2))
+    cb, cc = np.load(tmp_path / "b" / "grid_sample_cells.npy"), np.load(tmp_path / "c" / "grid_sample_cells.npy")
+    assert len(cb) == bench.DUMP_SAMPLE_CELLS and np.array_equal(cb, cc) and np.all(np.diff(cb) > 0)
+    N = max(w[1] for w in bench.WORKLOADS.values())
+    assert bench.DUMP_SAMPLE_CELLS * (16 + 8) + 2 * N * 16 <= 64 * 2**20

@@ -188,7 +188,7 @@ def test_bench_multi_gpu_branch_with_one_rank(collective):
     """bench.py's N > 1 branch (process group, reducer / communicator, all-reduce timing, multi_gpu record)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(GRIDHIP_BENCH_FORCE_DIST="1", MASTER_PORT="29535")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--nvis",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--nvis",
                           "3000000", "--no-cpu", "--collective", collective, "--reserve-cus", "16", "--overlap",
                           "auto" if collective == "cabi" else "side"], capture_output=True, text=True,
                          timeout=900, env=env)
@@ -212,7 +212,7 @@ def test_bench_multi_gpu_branch_with_one_rank(collective):
 
 
 def test_bench_default_line_is_bounded():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--nvis",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--nvis",
                           "4000000", "--cpu-sample", "200000"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-4000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -228,7 +228,8 @@ def test_bench_default_line_is_bounded():
 
 
 def _bench(*extra, env=None):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu", *extra],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu",
+                          *extra],
                          capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     return out.returncode, (json.loads(lines[-1]) if lines else None), out.stderr
@@ -327,7 +328,7 @@ def test_bench_with_two_real_ranks_sharing_the_gpu(scaling, overlap):
     twice or cleared late, rows skipped that were not zero: all show there)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GRIDHIP_BENCH_SHARE_GPU="1", GRIDHIP_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                           "--nvis", "3000000", "--scaling", scaling, "--overlap", overlap], capture_output=True, text=True,
                          timeout=900, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
@@ -345,3 +346,38 @@ def test_bench_with_two_real_ranks_sharing_the_gpu(scaling, overlap):
     assert tried is None if overlap == "inline" else len(tried) == (3 if overlap == "side" else 4)
     assert (m["reserve_cus"], m["yield_cus"]) in ((0, 0), (0, 64), (32, 0))
     assert m["schedule"]["collective_runs"].startswith("side") or (m["reserve_cus"], m["yield_cus"]) == (0, 0)
+
+
+def test_bench_plain_line_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the extras (checksum pass, CPU baseline), and
+    --dump-outputs writes the grid of the last timed step: one pass of the stream (its sum is the stream's analytic
+    checksum), the same grid a --full run with the same arguments dumps (the inputs depend on the arguments only)."""
+    import numpy as np
+    import torch
+    import bench
+    args = ["--steps", "3", "--warmup", "1", "--nvis", "2000000"]
+    recs = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, *extra, "--dump-outputs",
+                              str(tmp_path / tag)], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-4000:]
+        recs[tag] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    p = recs["plain"]
+    assert p["unit"] == "Mvis/s" and p["higher_is_better"] is True and p["dtype"] == "f64" and p["value"] > 0
+    assert p["metric"].startswith("Mvis/s gridded") and p["steps"] == 3 and p["ms_per_step"] > 0
+    assert p["value"] == pytest.approx(2000000 / (p["ms_per_step"] * 1e-3) / 1e6, rel=1e-9)
+    assert not p["full"] and "check" not in p and "cpu_baseline" not in p and p["errors"] == 0
+    assert recs["full"]["full"] and recs["full"]["check"]["rel_err"] <= 1e-10
+    d = {tag: {n: np.load(tmp_path / tag / n) for n in recs[tag]["outputs"]["files"]} for tag in recs}
+    assert sum(a.nbytes for a in d["plain"].values()) <= 64 * 2**20
+    assert all(a.dtype == np.float64 for a in d["plain"].values())
+    for n, a in d["plain"].items():
+        b = d["full"][n]
+        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-12 * max(np.abs(b).max(), 1.0), n
+    n, N, W, Q, S = 2000000, *bench.WORKLOADS["cfg3"][1:]
+    dev = torch.device("cuda", 0)
+    u, v, wb, vis = bench.synth_vis(n, N, W, S, 0x5EEDC0DE, dev)
+    expect, scale = bench.expected_checksum(u, v, wb, vis, bench.synth_kernels(W, Q, S, dev), N)
+    for sums in ("grid_row_sums.npy", "grid_col_sums.npy"):
+        got = complex(*d["plain"][sums].sum(axis=0))
+        assert abs(got - complex(expect.item())) <= 1e-10 * scale.item(), sums

@@ -1,7 +1,7 @@
 """Native HDF5 I/O (libgridhip_io.so) — the §8(f) "I/O" row.  CPU tests: the round trip of the
 reference's test/Hdf5.hs:36-58 with the arrays of :20-28, the exported symbols, error reporting,
-and interchange with the reference's own shim built from /root/reference/hdf5/hdf5.cc into
-oracle/_ref/ (skipped where that build is absent, e.g. never required on the GPU box).
+and interchange with the reference's own shim: a file it wrote (tests/golden/) and, where a build of it
+lies in oracle/_ref/, the shim itself.
 GPU test: synthetic HDF5 dataset -> aw_gridding driver (src/ImageDataset.hs:29-86) -> /img,
 checked against the numpy oracle."""
 import ctypes as C
@@ -65,21 +65,65 @@ def test_errors_are_reported_not_swallowed(tmp_path):
         h5io.listGroupMembers(name, "/nogroup")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref (reference hdf5.cc build) not present")
+def _file_types(name, datasets):
+    """{dataset: (stored HDF5 datatype, dims)} of an HDF5 file, read with the HDF5 C library libgridhip_io.so links."""
+    hdf = C.CDLL(h5io.LIB_PATH)  # (symbol lookup through the handle reaches its dependencies: libhdf5)
+    hid = C.c_int64
+    for fn, res, args in (("H5Fopen", hid, [C.c_char_p, C.c_uint, hid]), ("H5Dopen2", hid, [hid, C.c_char_p, hid]),
+                          ("H5Dget_type", hid, [hid]), ("H5Dget_space", hid, [hid]),
+                          ("H5Sget_simple_extent_dims", C.c_int, [hid, C.POINTER(C.c_ulonglong), C.c_void_p]),
+                          ("H5Sclose", C.c_int, [hid]), ("H5Dclose", C.c_int, [hid]), ("H5Fclose", C.c_int, [hid])):
+        getattr(hdf, fn).restype, getattr(hdf, fn).argtypes = res, args
+    f = hdf.H5Fopen(name.encode(), 0, 0)  # H5F_ACC_RDONLY, H5P_DEFAULT
+    assert f >= 0, name
+    out = {}
+    for ds in datasets:
+        d = hdf.H5Dopen2(f, ds.encode(), 0)
+        assert d >= 0, ds
+        sp = hdf.H5Dget_space(d)
+        dims = (C.c_ulonglong * 8)()
+        rank = hdf.H5Sget_simple_extent_dims(sp, dims, None)
+        out[ds] = (hdf.H5Dget_type(d), tuple(dims[:rank]))
+        hdf.H5Sclose(sp)
+        hdf.H5Dclose(d)
+    return hdf, f, out
+
+
 def test_interchange_with_reference_shim(tmp_path):
-    """Files written by either shim are read identically by the other."""
-    ref = h5io.load(REF)
+    """Files written by either shim are read identically by the other.  The reference's side is a file its own shim
+    wrote (tests/golden/h5_reference_shim_testIO.h5, oracle/make_golden.py): libgridhip_io reads it as written, and the
+    file libgridhip_io writes stores every dataset with the very datatype and dataspace of the reference's file - what
+    the reference's reader (H5Dread into a fixed memory type per call) depends on.  Where oracle/_ref holds a build of
+    the reference's shim, that shim also reads the file libgridhip_io writes and writes one for libgridhip_io to read."""
     d, c, t3 = ref_arrays()
-    a, b = str(tmp_path / "mine"), str(tmp_path / "theirs")
+    a = str(tmp_path / "mine")
     h5io.createh5File(a)
     h5io.createDataset(a, "/testD", d)
     h5io.createDataset(a, "/testC", c)
     h5io.createDataset(a, "/test3", t3)
-    h5io.createh5File(b, lib=ref)
-    h5io.createDataset(b, "/testD", d, lib=ref)
-    h5io.createDataset(b, "/testC", c, lib=ref)
-    h5io.createDataset(b, "/test3", t3, lib=ref)
-    for name, lib in ((a, ref), (b, None)):
+    recorded = os.path.join(ROOT, "tests", "golden", "h5_reference_shim_testIO.h5")
+    names = ["/testD", "/testC", "/test3"]
+    hdf, f_mine, mine = _file_types(a + ".h5", names)
+    _, f_theirs, theirs = _file_types(recorded, names)
+    hdf.H5Tequal.restype, hdf.H5Tequal.argtypes = C.c_int, [C.c_int64, C.c_int64]
+    hdf.H5Tclose.argtypes = [C.c_int64]
+    for ds in names:
+        assert mine[ds][1] == theirs[ds][1] == {"/testD": (1000, 2), "/testC": (1000,), "/test3": (2, 3, 1000, 2)}[ds]
+        assert hdf.H5Tequal(mine[ds][0], theirs[ds][0]) > 0, ds
+        hdf.H5Tclose(mine[ds][0])
+        hdf.H5Tclose(theirs[ds][0])
+    hdf.H5Fclose(f_mine)
+    hdf.H5Fclose(f_theirs)
+    pairs = [(a, None), (recorded, None)]
+    if os.path.exists(REF):
+        ref = h5io.load(REF)
+        b = str(tmp_path / "theirs")
+        h5io.createh5File(b, lib=ref)
+        h5io.createDataset(b, "/testD", d, lib=ref)
+        h5io.createDataset(b, "/testC", c, lib=ref)
+        h5io.createDataset(b, "/test3", t3, lib=ref)
+        pairs += [(a, ref), (b, None)]
+    for name, lib in pairs:
         assert h5io.shape(name, "/test3", lib) == (2, 3, 1000, 2)
         assert np.array_equal(h5io.readDataset(name, "/testD", np.float64, lib), d)
         assert np.array_equal(h5io.readDataset(name, "/testC", np.complex128, lib), c)

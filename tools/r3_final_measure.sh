@@ -13,9 +13,9 @@ rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r03_cfg4
 python tools/phase_profile.py --workload=cfg3 > $OUT/phase_cfg3.log 2>&1; echo "phase cfg3 rc=$?"
 python tools/phase_profile.py --workload=cfg5 "" bigtile=2 > $OUT/phase_cfg5.log 2>&1; echo "phase cfg5 rc=$?"
 for WL in cfg3 cfg2 cfg5 cfg4; do
-  python bench.py --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err; echo "bench $WL rc=$?"
+  python bench.py --full --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err; echo "bench $WL rc=$?"
 done
-python bench.py --dist core --no-cpu > $OUT/bench_cfg3_core.json 2> $OUT/bench_cfg3_core.err; echo "bench core rc=$?"
+python bench.py --full --dist core --no-cpu > $OUT/bench_cfg3_core.json 2> $OUT/bench_cfg3_core.err; echo "bench core rc=$?"
 # single-GPU pieces of the multi-GPU prediction: the step with 32 CUs reserved, at each GPU count's share of the stream
 for NV in 100000000 50000000 25000000 12500000; do
   python tools/sweep.py --nvis $NV --reps 3 "" "yield_cus=64" "reserve_cus=32" 2>&1 | grep -v amdgpu.ids | sed "s/^/cfg3 nvis=$NV  /" | tee -a $OUT/multigpu_pieces.txt
