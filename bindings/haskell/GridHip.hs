@@ -26,6 +26,8 @@ module GridHip
   , gridIO, convgridIO, convgrid2IO, degrid2IO, awgridIO
   -- * imaging functions and do_imaging (src/Gridding.hs:76-93, 115-124, 399-449, 452-478, 509-549)
   , simpleImagingIO, convImagingIO, wCacheImagingIO, awImagingIO, doImagingIO, ImagingKind(..)
+  -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
+  , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
   , Node, withNode, convgrid2NodeIO
   ) where
@@ -172,6 +174,21 @@ foreign import ccall unsafe "gridhip_aw_last_stats"
 -- int gridhip_aw_imaging(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, grid)
 foreign import ccall unsafe "gridhip_aw_imaging"
   c_aw_imaging :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_aw_imaging_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, grid)
+foreign import ccall unsafe "gridhip_aw_imaging_dev"
+  c_aw_imaging_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_do_imaging_aw(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, image, psf, pmax)
+foreign import ccall unsafe "gridhip_do_imaging_aw"
+  c_do_imaging_aw :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_do_imaging_aw_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, image, psf, pmax)
+foreign import ccall unsafe "gridhip_do_imaging_aw_dev"
+  c_do_imaging_aw_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_aw_gridding(ctx, theta, lam, f, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, image, imax)
+foreign import ccall unsafe "gridhip_aw_gridding"
+  c_aw_gridding :: Ptr Ctx -> CDouble -> Int64 -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_aw_gridding_dev(ctx, theta, lam, f, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, image, imax)
+foreign import ccall unsafe "gridhip_aw_gridding_dev"
+  c_aw_gridding_dev :: Ptr Ctx -> CDouble -> Int64 -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_do_imaging(ctx, kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, n, u, v, w, uv_stride, vis, image, psf, pmax)
 foreign import ccall unsafe "gridhip_do_imaging"
   c_do_imaging :: Ptr Ctx -> CInt -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
@@ -448,10 +465,14 @@ data ImagingKind
   = SimpleImaging                              -- ^ simple_imaging
   | ConvImaging (A.Array A.DIM4 Visibility)    -- ^ conv_imaging kv
   | WCacheImaging Int Int Int Int              -- ^ w_cache_imaging: wstep qpx npixFF npixKern
+  | AwImaging (A.Array A.DIM5 Visibility) (A.Vector BaseLine) (A.Array A.DIM3 Visibility)
+              (A.Vector Antenna) (A.Vector Antenna)
+                                               -- ^ aw_imaging: wkerns wvals akerns ant1 ant2 (the `src` it reads)
 
 -- | do_imaging theta lam uvw a1 a2 t f vis imgfn  (src/Gridding.hs:509-549): (image, psf, pmax).
 -- uvw is the (n,3) row-major Matrix BaseLine as it comes from HDF5 (src/ImageDataset.hs:94-97): passed with
--- uv_stride = 3, the columns are sliced on the device (:524-526).  a1, a2, t, f are unused by these imaging functions.
+-- uv_stride = 3, the columns are sliced on the device (:524-526).  t, f are unused by these imaging functions; a1, a2
+-- travel inside AwImaging (gridhip_do_imaging_aw: the image and PSF passes share each batch's kernel table).
 doImagingIO :: GridHip -> F -> Int -> A.Matrix BaseLine -> A.Vector Visibility -> ImagingKind
             -> IO (A.Matrix F, A.Matrix F, F)
 doImagingIO h@(GridHip c) theta lam uvw vis kind = do
@@ -471,8 +492,38 @@ doImagingIO h@(GridHip c) theta lam uvw vis kind = do
       let A.Z A.:. q A.:. _ A.:. gh A.:. gw = A.arrayShape kv
       in withCplx kv $ \k -> run 1 (0 :: Int) q (0 :: Int) gh gw k
     WCacheImaging wstep q npixFF s -> run 2 wstep q npixFF s s nullPtr
+    AwImaging wkerns wvals akerns ant1 ant2 ->
+      let A.Z A.:. w A.:. q A.:. _ A.:. s A.:. _ = A.arrayShape wkerns
+          A.Z A.:. na A.:. _ A.:. _ = A.arrayShape akerns
+      in withForeignPtr img $ \pi' -> withForeignPtr psf $ \pp -> withF uvw $ \m -> withCplx vis $ \vs ->
+           withCplx wkerns $ \wk -> withF wvals $ \wv -> withCplx akerns $ \ak -> withI64 ant1 $ \a1 ->
+             withI64 ant2 $ \a2 -> alloca $ \pm -> do
+               c_do_imaging_aw c (realToFrac theta) (fi lam) (fi w) (fi q) (fi s) (fi na) wk wv ak (fi n)
+                               m (m `advancePtr` 1) (m `advancePtr` 2) 3 a1 a2 vs pi' pp pm >>= check h
+               realToFrac <$> peek pm
   let sh = A.Z A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr img), A.fromForeignPtrs sh (castForeignPtr psf), pmax)
+
+-- | aw_gridding after its HDF5 reads (src/ImageDataset.hs:54-77) as one library call: uvw is /vis/uvw in METRES,
+-- the (n,3) Matrix BaseLine, and f the frequency in Hz; uvw_lambda, doweight (on the UN-mirrored uvw, :59),
+-- mirror_uvw, aw_imaging of vis1 * wt, make_grid_hermitian and real . ifft run on the device.  Returns the image
+-- (not normalised, as in the reference) and its maximum, the `max` the reference's driver returns.
+awGriddingIO :: GridHip -> F -> Int -> F -> A.Array A.DIM5 Visibility -> A.Vector BaseLine
+             -> A.Array A.DIM3 Visibility -> A.Matrix BaseLine -> A.Vector Antenna -> A.Vector Antenna
+             -> A.Vector Visibility -> IO (A.Matrix F, F)
+awGriddingIO h@(GridHip c) theta lam f wkerns wvals akerns uvw ant1 ant2 vis = do
+  n' <- imageSize theta lam
+  img <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let A.Z A.:. w A.:. q A.:. _ A.:. s A.:. _ = A.arrayShape wkerns
+      A.Z A.:. na A.:. _ A.:. _ = A.arrayShape akerns
+      A.Z A.:. n = A.arrayShape vis
+  mx <- withForeignPtr img $ \pi' -> withF uvw $ \m -> withCplx vis $ \vs -> withCplx wkerns $ \wk ->
+          withF wvals $ \wv -> withCplx akerns $ \ak -> withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 ->
+            alloca $ \pm -> do
+              c_aw_gridding c (realToFrac theta) (fi lam) (realToFrac f) (fi w) (fi q) (fi s) (fi na) wk wv ak (fi n)
+                            m (m `advancePtr` 1) (m `advancePtr` 2) 3 a1 a2 vs pi' pm >>= check h
+              realToFrac <$> peek pm
+  return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr img), mx)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 110 /* 0.1.1 */
+#define GRIDHIP_VERSION 120 /* 0.1.2 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -123,6 +123,7 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last
  * convgrid / convgrid2 / degrid2 call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
+ * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / imaging call built;
  * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan call used:
  * 1 = the tap-reusing tile kernel (square supports 5..32 with enough visibilities per work item), 2 = the same through
  * sub-footprints (other shapes: one record per spatial part of the kernel), 3 = the general tile kernel (small
@@ -259,6 +260,46 @@ int gridhip_aw_imaging(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, i
                        int64_t n, const double *u, const double *v, const double *w,
                        int64_t uv_stride, const int64_t *a1, const int64_t *a2, const double *vis,
                        double *grid);
+/* aw_imaging with every array argument resident on the device (wkerns, wvals, akerns, u, v, w, a1, a2, vis in; the
+ * N x N grid out, overwritten): replaces the `run` of :452-478 as gridhip_aw_imaging does, but asynchronous on the
+ * context's stream and reading nothing back.  One front-end kernel reads the strided u, v, w once (p = uvw / lam,
+ * findClosest of w in wavelengths), then the aw gridder.  a1 / a2 are taken as given. */
+int gridhip_aw_imaging_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                           const double *wkerns, const double *wvals, const double *akerns, int64_t n,
+                           const double *u, const double *v, const double *w, int64_t uv_stride,
+                           const int64_t *a1, const int64_t *a2, const double *vis, double *grid);
+/* do_imaging, :509-549, with imgfn = aw_imaging (:452-478): uvw in wavelengths; image and psf are N x N doubles
+ * (required), pmax a HOST pointer (may be NULL).  Doweight order: weights from the MIRRORED uvw (:531-535), as for
+ * every do_imaging kind.  The mirror negates u, v, w and conjugates vis; it does not swap a1 / a2 (:551-562).  The
+ * image pass (wt * vis1) and the PSF pass (wt) share each batch's antenna pairs, keys, kernel table and binned
+ * records: the table is built once per batch of 2^20 visibilities (read-only option "aw_tables_built"), where two
+ * aw_imaging calls would build it twice.  Out-of-range antennas or w-bins are dropped and counted
+ * (gridhip_last_dropped) as by gridhip_awgrid_dev.  The _dev form takes device-resident arrays and allocates nothing
+ * after the first call of a shape; both forms synchronise (pmax). */
+int gridhip_do_imaging_aw(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                          const double *wkerns, const double *wvals, const double *akerns, int64_t n,
+                          const double *u, const double *v, const double *w, int64_t uv_stride,
+                          const int64_t *a1, const int64_t *a2, const double *vis, double *image, double *psf,
+                          double *pmax);
+int gridhip_do_imaging_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
+                              int64_t A, const double *wkerns, const double *wvals, const double *akerns,
+                              int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
+                              const int64_t *a1, const int64_t *a2, const double *vis, double *image,
+                              double *psf, double *pmax);
+/* aw_gridding, src/ImageDataset.hs:54-77, as one call: uvw in METRES (uv_stride 3 for the /vis/uvw (n,3) matrix) and
+ * f in Hz -> uvw_lambda (x f / 299792458, :181-187) -> doweight -> mirror_uvw -> aw_imaging of vis1 * wt ->
+ * make_grid_hermitian -> real . ifft.  Doweight order: weights from the UN-mirrored uvw (:59-60), unlike do_imaging.
+ * image (required) is N x N doubles, not normalised; imax (HOST pointer, may be NULL) is its maximum.  No PSF, as in
+ * the reference.  The _dev form's only host round-trip is that scalar. */
+int gridhip_aw_gridding(gridhip_ctx *ctx, double theta, int64_t lam, double f, int64_t W, int64_t Q, int64_t S,
+                        int64_t A, const double *wkerns, const double *wvals, const double *akerns, int64_t n,
+                        const double *u, const double *v, const double *w, int64_t uv_stride,
+                        const int64_t *a1, const int64_t *a2, const double *vis, double *image, double *imax);
+int gridhip_aw_gridding_dev(gridhip_ctx *ctx, double theta, int64_t lam, double f, int64_t W, int64_t Q, int64_t S,
+                            int64_t A, const double *wkerns, const double *wvals, const double *akerns,
+                            int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
+                            const int64_t *a1, const int64_t *a2, const double *vis, double *image,
+                            double *imax);
 /* do_imaging, :509-549: mirror -> weight -> grid(vis*wt), grid(wt) -> hermitian -> ifft -> /max(psf).
  * kind: 0 simple_imaging; 1 conv_imaging (Q, gh, gw, kv); 2 w_cache_imaging (wstep, Q, npixFF, gh = npixKern).
  * image and psf are N x N doubles. */

@@ -470,18 +470,19 @@ int launch_build(gridhip_ctx *ctx, const double2 *wk, const double2 *pairk, cons
 }
 }  // namespace
 
-extern "C" {
+namespace gridhip {
 
-// Device pointers; asynchronous (nothing is read back; scratch grows on first use).
-int gridhip_awgrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t W, int64_t Q,
-                       int64_t S, int64_t A, const double *wkerns, const double *akerns, const double *u,
-                       const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
-                       const int64_t *a2, const double *vis)
+// The aw batch loop over one or two (vis, grid) pairs.  Per batch the antenna pairs, keys, the kernel table and the
+// binned records are made once; the tile kernel then runs once per pair on the same records and table (it reads
+// ctx->recs and the table, and writes neither).  do_imaging grids its baselines twice - image (wt * vis) and PSF (wt) -
+// so its aw form builds the table once where two aw_imaging calls would build it twice.  Arguments are checked by the
+// callers; device pointers; asynchronous.
+int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *const *grids, const double *const *viss,
+                 int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
+                 const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
+                 const int64_t *a2)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
-        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    ctx->aw_tables_built = 0;
     if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
         return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -590,6 +591,7 @@ int gridhip_awgrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, in
             }
         }
         GH_CHECK_HIP(ctx, hipGetLastError());
+        ++ctx->aw_tables_built;
         mark(ctx, 1);
         // gridding: the pre-pass drops the visibilities whose `ok` is -1 (counted), the tile kernel reads the table
         p.g.nvis = (int32_t)m;
@@ -602,17 +604,36 @@ int gridhip_awgrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, in
             hipLaunchKernelGGL(aw_relabel_kernel, dim3((unsigned)rb), dim3(256), 0, ctx->stream, p.g, (RecWord *)ctx->recs.ptr,
                                t.bin_start + p.g.nbins, kid, (int32_t)m);
         }
-        if (p.sorted)
-            GH_CHECK(launch_tile_grid_sorted(ctx, p.g, p.block, p.lds_sorted, p.nkeys, p.batch, m, (const double *)table,
-                                             vis + 2 * lo, grid, false));
-        else
-            GH_CHECK(launch_tile_grid(ctx, p.g, p.block, p.lds, m, (const double *)table, vis + 2 * lo, grid));
+        for (int i = 0; i < npass; ++i) {  // (the tile kernels' errors of every pass land in [2] before the account)
+            if (p.sorted)
+                GH_CHECK(launch_tile_grid_sorted(ctx, p.g, p.block, p.lds_sorted, p.nkeys, p.batch, m, (const double *)table,
+                                                 viss[i] + 2 * lo, grids[i], false));
+            else
+                GH_CHECK(launch_tile_grid(ctx, p.g, p.block, p.lds, m, (const double *)table, viss[i] + 2 * lo, grids[i]));
+        }
         hipLaunchKernelGGL(aw_account_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars, counters, cache, (int32_t)m);
         mark(ctx, 2);
     }
     hipLaunchKernelGGL(aw_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
+}
+
+}  // namespace gridhip
+
+extern "C" {
+
+// Device pointers; asynchronous (nothing is read back; scratch grows on first use).
+int gridhip_awgrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t W, int64_t Q,
+                       int64_t S, int64_t A, const double *wkerns, const double *akerns, const double *u,
+                       const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
+                       const int64_t *a2, const double *vis)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
+        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis)))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    return awgrid_pairs(ctx, H, Wd, 1, &grid, &vis, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2);
 }
 
 // What the last gridhip_awgrid*_dev call did (synchronises): visibilities keyed, distinct kernels built.

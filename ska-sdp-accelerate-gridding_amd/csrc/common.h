@@ -179,6 +179,9 @@ struct gridhip_ctx {
     int last_path = 0;
     // the geometry that call ran with (read-only options "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile")
     int last_geom[4] = {0, 0, 0, 0};
+    // kernel tables the last aw call built, one per batch (read-only option "aw_tables_built"): an aw do_imaging builds
+    // each batch's table once for its image and PSF passes
+    int64_t aw_tables_built = 0;
 };
 
 namespace gridhip {
@@ -293,6 +296,10 @@ void fft_release(gridhip_ctx *ctx);
 int plan_create_borrowed(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t gh, int64_t gw,
                          const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, gridhip_plan **out);
 Tables tables_of(gridhip_ctx *ctx, const Geom &g);
+int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *const *grids, const double *const *viss,
+                 int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
+                 const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
+                 const int64_t *a2);
 size_t tables_bytes(const Geom &g);
 
 }  // namespace gridhip

@@ -465,6 +465,10 @@ int gridhip_get_option(gridhip_ctx *ctx, const char *key, int64_t *value)
                 return GRIDHIP_OK;
             }
     }
+    if (!strcmp(key, "aw_tables_built")) {
+        *value = ctx->aw_tables_built;
+        return GRIDHIP_OK;
+    }
     if (!strcmp(key, "last_path")) {
         *value = ctx->last_path;
         return GRIDHIP_OK;

@@ -68,22 +68,25 @@ __global__ void wbin_finish_kernel(int64_t n, int64_t *__restrict__ rw, int64_t 
 }
 
 // findClosest, src/Gridding.hs:895-907 (hi clamped to len-1 as the host twin does, ImageDataset.hs:150-168)
+__device__ __forceinline__ int64_t closest_index(int64_t nws, const double *__restrict__ ws, double x)
+{
+    int64_t lo = 0, hi = nws;
+    while ((hi - lo) / 2 >= 1) {
+        const int64_t mid = (hi + lo) / 2;
+        if (x > ws[mid])
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int64_t hc = hi > nws - 1 ? nws - 1 : hi;
+    return fabs(x - ws[lo]) < fabs(x - ws[hc]) ? lo : hc;
+}
+
 __global__ void find_closest_kernel(int64_t nws, const double *__restrict__ ws, int64_t n,
                                     const double *__restrict__ w, int64_t stride, int64_t *__restrict__ out)
 {
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
-        const double x = w[k * stride];
-        int64_t lo = 0, hi = nws;
-        while ((hi - lo) / 2 >= 1) {
-            const int64_t mid = (hi + lo) / 2;
-            if (x > ws[mid])
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const int64_t hc = hi > nws - 1 ? nws - 1 : hi;
-        out[k] = fabs(x - ws[lo]) < fabs(x - ws[hc]) ? lo : hc;
-    }
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x)
+        out[k] = closest_index(nws, ws, w[k * stride]);
 }
 
 // mirror_uvw, src/Gridding.hs:551-562
@@ -219,6 +222,60 @@ __global__ void divide_kernel(int64_t cells, double *__restrict__ x, const unsig
     const double m = __longlong_as_double((long long)b);
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (int64_t)gridDim.x * blockDim.x)
         x[c] /= m;
+}
+
+// Front end of the aw entry points, kernel 1 of 2: one read of the strided (u, v, w) and vis per visibility.
+//   uvw_lambda (ImageDataset.hs:181-187: x fc = f / c; fc = 1 for uvw already in wavelengths - an exact product),
+//   mirror_uvw (Gridding.hs:551-562: v < 0 negates u, v, w and conjugates vis; the antennas are NOT swapped),
+//   p = uvw1 / lam and the findClosest w-bin of w1 in wavelengths (aw_imaging, :466-474),
+//   doweight's cell (:564-583) of the mirrored coordinates (weigh 1: do_imaging, :531-535) or of the un-mirrored ones
+//   (weigh 2: aw_gridding, ImageDataset.hs:59-60), counted into the histogram.  The cell is stored, not re-derived
+//   by kernel 2 from p: floor(0.5 + x) is not odd-symmetric, so the two coordinate sets can give different cells.
+// vis1 may be NULL when nothing is mirrored (aw_imaging: the caller's vis is gridded as it is).
+__global__ void aw_front_kernel(int64_t n, const double *__restrict__ u, const double *__restrict__ v,
+                                const double *__restrict__ w, int64_t stride, const double2 *__restrict__ vis, double fc,
+                                double lam, int mirror, int weigh, int64_t N, int64_t nws, const double *__restrict__ ws,
+                                double *__restrict__ pu, double *__restrict__ pv, int64_t *__restrict__ wbin,
+                                double2 *__restrict__ vis1, int64_t *__restrict__ cell, unsigned int *__restrict__ cnt)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const double u0 = u[k * stride] * fc, v0 = v[k * stride] * fc, w0 = w[k * stride] * fc;
+        const bool neg = mirror && v0 < 0;
+        const double u1 = neg ? -u0 : u0, v1 = neg ? -v0 : v0, w1 = neg ? -w0 : w0;
+        const double qu = u1 / lam, qv = v1 / lam;
+        pu[k] = qu;
+        pv[k] = qv;
+        wbin[k] = closest_index(nws, ws, w1);
+        if (vis1) {
+            double2 x = vis[k];
+            if (neg) x.y = -x.y;
+            vis1[k] = x;
+        }
+        if (weigh) {
+            const int64_t c = weigh == 1 ? weight_cell(N, qu, qv) : weight_cell(N, u0 / lam, v0 / lam);
+            cell[k] = c;
+            if (c >= 0) atomicAdd(&cnt[c], 1u);
+        }
+    }
+}
+
+// kernel 2 of 2: wt = doweight's ones / count (the same two divisions as weight_apply_kernel; a visibility outside the
+// grid keeps 1) and, in place, vis1 = wt * vis1 (the product of cmul_real_kernel).  wt may be NULL (aw_gridding).
+__global__ void aw_weight_kernel(int64_t n, const int64_t *__restrict__ cell, const unsigned int *__restrict__ cnt,
+                                 double2 *vis1, double2 *__restrict__ wt)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        double2 a = make_double2(1.0, 0.0);
+        const int64_t c = cell[k];
+        if (c >= 0) {
+            const double wgt = (double)cnt[c];
+            a.x /= wgt;
+            a.y /= wgt;
+        }
+        const double2 y = vis1[k];
+        if (wt) wt[k] = a;
+        vis1[k] = make_double2(a.x * y.x - a.y * y.y, a.x * y.y + a.y * y.x);
+    }
 }
 
 __global__ void cmul_real_kernel(int64_t n, const double2 *__restrict__ a, const double2 *__restrict__ b,
@@ -721,6 +778,212 @@ static int w_cache_grid_dev(gridhip_ctx *ctx, WCache &c, double theta, int64_t l
     return sync(ctx);
 }
 
+// ---- the aw entry points (aw_imaging_dev, do_imaging_aw, aw_gridding): front end -> aw gridder -> imaging tail ----
+
+struct AwArgs {
+    double theta;
+    int64_t lam, W, Q, S, A;
+    const double *wkerns, *wvals, *akerns;
+    int64_t n;
+    const double *u, *v, *w;
+    int64_t stride;
+    const int64_t *a1, *a2;
+    const double *vis;
+};
+
+// Everything is checked before anything is touched (a refused call leaves its outputs as they were).
+static int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N)
+{
+    *N = haskell_round(a.theta * (double)a.lam);
+    if (*N <= 0 || a.n < 0 || a.stride < 1 || a.W <= 0 || a.Q <= 0 || a.S <= 0 || a.A <= 0 || !a.wkerns || !a.wvals ||
+        !a.akerns || (a.n > 0 && (!a.u || !a.v || !a.w || !a.a1 || !a.a2 || !a.vis)))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    return GRIDHIP_OK;
+}
+
+// The inputs on the device: the caller's own (the _dev forms) or uploaded copies (the host forms), in s.d.
+struct AwStage {
+    DevBuf wk, ws, ak, u, v, w, a1, a2, vis;
+    AwArgs d;
+};
+
+static int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s)
+{
+    s.d = a;
+    if (dev) return GRIDHIP_OK;
+    const size_t wel = (size_t)a.W * a.Q * a.Q * a.S * a.S, ael = (size_t)a.A * a.S * a.S;
+    const size_t span = a.n > 0 ? (size_t)(a.n - 1) * a.stride + 1 : 0;
+    GH_CHECK(s.wk.alloc(ctx, wel * 16));
+    GH_CHECK(s.ws.alloc(ctx, a.W * 8));
+    GH_CHECK(s.ak.alloc(ctx, ael * 16));
+    GH_CHECK(s.u.alloc(ctx, span * 8));
+    GH_CHECK(s.v.alloc(ctx, span * 8));
+    GH_CHECK(s.w.alloc(ctx, span * 8));
+    GH_CHECK(s.a1.alloc(ctx, a.n * 8));
+    GH_CHECK(s.a2.alloc(ctx, a.n * 8));
+    GH_CHECK(s.vis.alloc(ctx, a.n * 16));
+    GH_CHECK(h2d(ctx, s.wk.p, a.wkerns, wel * 16));
+    GH_CHECK(h2d(ctx, s.ws.p, a.wvals, a.W * 8));
+    GH_CHECK(h2d(ctx, s.ak.p, a.akerns, ael * 16));
+    GH_CHECK(h2d(ctx, s.u.p, a.u, span * 8));
+    GH_CHECK(h2d(ctx, s.v.p, a.v, span * 8));
+    GH_CHECK(h2d(ctx, s.w.p, a.w, span * 8));
+    GH_CHECK(h2d(ctx, s.a1.p, a.a1, a.n * 8));
+    GH_CHECK(h2d(ctx, s.a2.p, a.a2, a.n * 8));
+    GH_CHECK(h2d(ctx, s.vis.p, a.vis, a.n * 16));
+    s.d.wkerns = s.wk.as<double>(), s.d.wvals = s.ws.as<double>(), s.d.akerns = s.ak.as<double>();
+    s.d.u = s.u.as<double>(), s.d.v = s.v.as<double>(), s.d.w = s.w.as<double>();
+    s.d.a1 = s.a1.as<int64_t>(), s.d.a2 = s.a2.as<int64_t>(), s.d.vis = s.vis.as<double>();
+    return GRIDHIP_OK;
+}
+
+// p = uvw1 / lam, w-bins, and (mirror) vis1, (weigh) wt * vis1 in vis1 and (want_wt) wt: aw_front_kernel +
+// aw_weight_kernel.  weigh: 0 none, 1 on the mirrored coordinates, 2 on the un-mirrored ones.
+struct AwFront {
+    DevBuf pu, pv, wb, vis1, wt, cell, cnt;
+};
+
+static int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt,
+                    AwFront &f)
+{
+    const int64_t n = d.n;
+    GH_CHECK(f.pu.alloc(ctx, n * 8));
+    GH_CHECK(f.pv.alloc(ctx, n * 8));
+    GH_CHECK(f.wb.alloc(ctx, n * 8));
+    if (mirror) GH_CHECK(f.vis1.alloc(ctx, n * 16));
+    if (want_wt) GH_CHECK(f.wt.alloc(ctx, n * 16));
+    if (weigh) {
+        GH_CHECK(f.cell.alloc(ctx, n * 8));
+        GH_CHECK(f.cnt.alloc(ctx, (size_t)N * N * 4));
+        GH_CHECK_HIP(ctx, hipMemsetAsync(f.cnt.p, 0, (size_t)N * N * 4, ctx->stream));
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(aw_front_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, d.u, d.v, d.w, d.stride,
+                           (const double2 *)d.vis, fc, (double)d.lam, mirror ? 1 : 0, weigh, N, d.W, d.wvals,
+                           f.pu.as<double>(), f.pv.as<double>(), f.wb.as<int64_t>(),
+                           mirror ? f.vis1.as<double2>() : (double2 *)nullptr,
+                           weigh ? f.cell.as<int64_t>() : (int64_t *)nullptr,
+                           weigh ? f.cnt.as<unsigned int>() : (unsigned int *)nullptr);
+        if (weigh)
+            hipLaunchKernelGGL(aw_weight_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, f.cell.as<int64_t>(),
+                               f.cnt.as<unsigned int>(), f.vis1.as<double2>(),
+                               want_wt ? f.wt.as<double2>() : (double2 *)nullptr);
+    }
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+// out = real(ifft(make_grid_hermitian(g))) (N x N doubles; the rolls folded in as in do_imaging_impl); its maximum
+// into *maxbits (ordered bits) when given.  h: N x N complex scratch.
+static int aw_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits)
+{
+    static const unsigned long long neg_inf_bits = ~0xfff0000000000000ULL;  // ordered image of -inf
+    const size_t cells = (size_t)N * N;
+    void *plan = nullptr;
+    GH_CHECK(fft_plan_for(ctx, N, &plan));
+    hipLaunchKernelGGL(hermitian_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, g, h, N / 2);
+    if (int rc = g_fft.exec(plan, h, h, 1 /* HIPFFT_BACKWARD */)) return fail(ctx, GRIDHIP_EHIP, "hipfftExecZ2Z: %d", rc);
+    if (maxbits) GH_CHECK(h2d(ctx, maxbits, &neg_inf_bits, 8));
+    hipLaunchKernelGGL(real_max_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells, h, out,
+                       maxbits, N, (N + 1) / 2, 1.0 / ((double)N * (double)N));
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+static double max_of_bits(unsigned long long mb)
+{
+    mb = (mb & 0x8000000000000000ULL) ? (mb & 0x7fffffffffffffffULL) : ~mb;
+    double m;
+    memcpy(&m, &mb, 8);
+    return m;
+}
+
+// do_imaging with imgfn = aw_imaging (src/Gridding.hs:509-549): doweight on the MIRRORED uvw (:531-535); both gridding
+// passes in one aw batch loop (one kernel table per batch), then two tails and the normalisation.
+static int do_imaging_aw_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double *image, double *psf, double *pmax)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N));
+    if (!image || !psf) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)N * N;
+    AwStage s;
+    GH_CHECK(aw_stage(ctx, dev, a, s));
+    const AwArgs &d = s.d;
+    AwFront f;
+    GH_CHECK(aw_front(ctx, N, d, 1.0, true, 1, true, f));
+    // both grids are filled by the one batch loop before either is transformed: two N x N complex blocks
+    DevBuf dg0, dg1, dh, dimg, dpsf, dmax;
+    GH_CHECK(dg0.alloc(ctx, cells * 16));
+    GH_CHECK(dg1.alloc(ctx, cells * 16));
+    GH_CHECK(dh.alloc(ctx, cells * 16));
+    GH_CHECK(dmax.alloc(ctx, 8));
+    if (!dev) {
+        GH_CHECK(dimg.alloc(ctx, cells * 8));
+        GH_CHECK(dpsf.alloc(ctx, cells * 8));
+    }
+    double *rimg = dev ? image : dimg.as<double>(), *rpsf = dev ? psf : dpsf.as<double>();
+    GH_CHECK_HIP(ctx, hipMemsetAsync(dg0.p, 0, cells * 16, ctx->stream));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(dg1.p, 0, cells * 16, ctx->stream));
+    double *grids[2] = {dg0.as<double>(), dg1.as<double>()};
+    const double *viss[2] = {f.vis1.as<double>(), f.wt.as<double>()};  // image from wt * vis1 (:538), PSF from wt (:541)
+    GH_CHECK(awgrid_pairs(ctx, N, N, 2, grids, viss, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, f.pu.as<double>(),
+                          f.pv.as<double>(), 1, f.wb.as<int64_t>(), d.a1, d.a2));
+    GH_CHECK(aw_tail(ctx, N, dg0.as<double2>(), dh.as<double2>(), rimg, nullptr));
+    GH_CHECK(aw_tail(ctx, N, dg1.as<double2>(), dh.as<double2>(), rpsf, dmax.as<unsigned long long>()));
+    // normalise both by max(psf) (:544-548)
+    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells, rimg,
+                       dmax.as<unsigned long long>());
+    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells, rpsf,
+                       dmax.as<unsigned long long>());
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    unsigned long long mb = 0;
+    GH_CHECK(d2h(ctx, &mb, dmax.p, 8));
+    if (!dev) {
+        GH_CHECK(d2h(ctx, image, rimg, cells * 8));
+        GH_CHECK(d2h(ctx, psf, rpsf, cells * 8));
+    }
+    GH_CHECK(sync(ctx));
+    if (pmax) *pmax = max_of_bits(mb);
+    return GRIDHIP_OK;
+}
+
+// aw_gridding, src/ImageDataset.hs:54-77: uvw in metres -> uvw_lambda (x f / c) -> doweight on the UN-mirrored uvw
+// (:59) -> mirror_uvw (:60) -> aw_imaging of vis1 * wt (:72-73) -> make_grid_hermitian -> real . ifft, and its maximum.
+static int aw_gridding_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double f, double *image, double *imax)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N));
+    if (!image || !(f > 0.0) || !(f < INFINITY)) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)N * N;
+    AwStage s;
+    GH_CHECK(aw_stage(ctx, dev, a, s));
+    const AwArgs &d = s.d;
+    AwFront fr;
+    GH_CHECK(aw_front(ctx, N, d, f / 299792458.0, true, 2, false, fr));  // (the constant of uvw_lambda, :187)
+    DevBuf dg, dh, dimg, dmax;
+    GH_CHECK(dg.alloc(ctx, cells * 16));
+    GH_CHECK(dh.alloc(ctx, cells * 16));
+    GH_CHECK(dmax.alloc(ctx, 8));
+    if (!dev) GH_CHECK(dimg.alloc(ctx, cells * 8));
+    double *rimg = dev ? image : dimg.as<double>();
+    GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, cells * 16, ctx->stream));
+    double *grid = dg.as<double>();
+    const double *vis = fr.vis1.as<double>();
+    GH_CHECK(awgrid_pairs(ctx, N, N, 1, &grid, &vis, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, fr.pu.as<double>(),
+                          fr.pv.as<double>(), 1, fr.wb.as<int64_t>(), d.a1, d.a2));
+    GH_CHECK(aw_tail(ctx, N, dg.as<double2>(), dh.as<double2>(), rimg, dmax.as<unsigned long long>()));
+    unsigned long long mb = 0;
+    GH_CHECK(d2h(ctx, &mb, dmax.p, 8));
+    if (!dev) GH_CHECK(d2h(ctx, image, rimg, cells * 8));
+    GH_CHECK(sync(ctx));
+    if (imax) *imax = max_of_bits(mb);
+    return GRIDHIP_OK;
+}
+
 }  // namespace gridhip
 
 using namespace gridhip;
@@ -1138,6 +1401,62 @@ int gridhip_w_cache_imaging_dev(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, in
     GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
     WCache cache;
     return w_cache_grid_dev(ctx, cache, theta, lam, wstep, qpx, npixFF, npixKern, N, n, pu, pv, pw, vis, grid);
+}
+
+// aw_imaging with device-resident arguments: the front end's one kernel (p = uvw / lam, findClosest w-bins), then the
+// aw gridder into the N x N grid (overwritten).  Asynchronous: nothing is read back.
+int gridhip_aw_imaging_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                           const double *wkerns, const double *wvals, const double *akerns, int64_t n, const double *u,
+                           const double *v, const double *w, int64_t uv_stride, const int64_t *a1, const int64_t *a2,
+                           const double *vis, double *grid)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N));
+    if (!grid) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
+    AwFront f;
+    GH_CHECK(aw_front(ctx, N, a, 1.0, false, 0, false, f));
+    return awgrid_pairs(ctx, N, N, 1, &grid, &vis, n, W, Q, S, A, wkerns, akerns, f.pu.as<double>(), f.pv.as<double>(),
+                        1, f.wb.as<int64_t>(), a1, a2);
+}
+
+int gridhip_do_imaging_aw(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                          const double *wkerns, const double *wvals, const double *akerns, int64_t n, const double *u,
+                          const double *v, const double *w, int64_t uv_stride, const int64_t *a1, const int64_t *a2,
+                          const double *vis, double *image, double *psf, double *pmax)
+{
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    return do_imaging_aw_any(ctx, false, a, image, psf, pmax);
+}
+
+int gridhip_do_imaging_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                              const double *wkerns, const double *wvals, const double *akerns, int64_t n, const double *u,
+                              const double *v, const double *w, int64_t uv_stride, const int64_t *a1, const int64_t *a2,
+                              const double *vis, double *image, double *psf, double *pmax)
+{
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    return do_imaging_aw_any(ctx, true, a, image, psf, pmax);
+}
+
+int gridhip_aw_gridding(gridhip_ctx *ctx, double theta, int64_t lam, double f, int64_t W, int64_t Q, int64_t S,
+                        int64_t A, const double *wkerns, const double *wvals, const double *akerns, int64_t n,
+                        const double *u, const double *v, const double *w, int64_t uv_stride, const int64_t *a1,
+                        const int64_t *a2, const double *vis, double *image, double *imax)
+{
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    return aw_gridding_any(ctx, false, a, f, image, imax);
+}
+
+int gridhip_aw_gridding_dev(gridhip_ctx *ctx, double theta, int64_t lam, double f, int64_t W, int64_t Q, int64_t S,
+                            int64_t A, const double *wkerns, const double *wvals, const double *akerns, int64_t n,
+                            const double *u, const double *v, const double *w, int64_t uv_stride, const int64_t *a1,
+                            const int64_t *a2, const double *vis, double *image, double *imax)
+{
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    return aw_gridding_any(ctx, true, a, f, image, imax);
 }
 
 }  // extern "C"

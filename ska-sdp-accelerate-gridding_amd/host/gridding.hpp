@@ -9,7 +9,8 @@
 //   convgrid2 gcf a p wbin v        :199-204
 //   convgrid3/convgrid4 wkerns akerns a p index v   :246-252, :318-324
 //   simple_imaging / conv_imaging / w_cache_imaging / aw_imaging   :84, :115, :399, :452
-//   do_imaging theta lam uvw a1 a2 t f vis imgfn    :509-519
+//   do_imaging theta lam uvw a1 a2 t f vis imgfn    :509-519 (do_imaging_aw: imgfn = aw_imaging)
+//   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
 // Error behaviour: the reference's functions are total on well-formed input and `error` otherwise;
@@ -22,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/gridhip.h"
@@ -182,6 +184,35 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
                                  (Int)vis.size(), uvw.u.data(), uvw.v.data(), uvw.w.data(), 1, cd(vis),
                                  img.data.data(), psf.data.data(), &pmax));
         return {std::move(img), std::move(psf), pmax};
+    }
+    // do_imaging with aw_imaging as the imaging function (:509-549, :452-478) -> (image, psf, pmax); uvw in
+    // wavelengths, weights from the mirrored uvw, one kernel table per batch for both passes
+    std::tuple<Matrix<F>, Matrix<F>, F> do_imaging_aw(F theta, Int lam, const WKernels &wk, const std::vector<F> &wbins,
+                                                      const AKernels &ak, const BaseLines &uvw,
+                                                      const std::vector<Int> &a1, const std::vector<Int> &a2,
+                                                      const std::vector<Visibility> &vis)
+    {
+        const Int N = gridhip_image_size(theta, lam);
+        Matrix<F> img(N, N), psf(N, N);
+        F pmax = 0;
+        check(gridhip_do_imaging_aw(ctx_, theta, lam, wk.W, wk.Q, wk.gh, ak.A, cd(wk.data), wbins.data(), cd(ak.data),
+                                    (Int)vis.size(), uvw.u.data(), uvw.v.data(), uvw.w.data(), 1, a1.data(), a2.data(),
+                                    cd(vis), img.data.data(), psf.data.data(), &pmax));
+        return {std::move(img), std::move(psf), pmax};
+    }
+    // aw_gridding, src/ImageDataset.hs:54-77 -> (image, max pixel): uvw in METRES, f in Hz; weights from the
+    // un-mirrored uvw; image = real . ifft . make_grid_hermitian of the aw grid, not normalised
+    std::pair<Matrix<F>, F> aw_gridding(F theta, Int lam, F f, const WKernels &wk, const std::vector<F> &wbins,
+                                        const AKernels &ak, const BaseLines &uvw_m, const std::vector<Int> &a1,
+                                        const std::vector<Int> &a2, const std::vector<Visibility> &vis)
+    {
+        const Int N = gridhip_image_size(theta, lam);
+        Matrix<F> img(N, N);
+        F mx = 0;
+        check(gridhip_aw_gridding(ctx_, theta, lam, f, wk.W, wk.Q, wk.gh, ak.A, cd(wk.data), wbins.data(), cd(ak.data),
+                                  (Int)vis.size(), uvw_m.u.data(), uvw_m.v.data(), uvw_m.w.data(), 1, a1.data(),
+                                  a2.data(), cd(vis), img.data.data(), &mx));
+        return {std::move(img), mx};
     }
     std::tuple<Matrix<F>, Matrix<F>, F> do_imaging_simple(F theta, Int lam, const BaseLines &uvw,
                                                          const std::vector<Visibility> &vis)

@@ -256,8 +256,33 @@ class Context:
             pass
         return out
 
+    def _aw_dev_args(self, wkernels, wbins, akernels, a1, a2, vis):
+        """torch cuda forms of the aw kernel tables, antenna indices and visibilities"""
+        import torch
+        cv = lambda t, dt: t if (t.dtype == dt and t.is_contiguous()) else t.to(dt).contiguous()
+        return (cv(wkernels, torch.complex128), cv(wbins, torch.float64), cv(akernels, torch.complex128),
+                cv(a1, torch.int64), cv(a2, torch.int64), cv(vis, torch.complex128))
+
+    def _aw_host_args(self, wkernels, wbins, akernels, a1, a2, vis):
+        return (self._np(wkernels, np.complex128), self._np(wbins, np.float64), self._np(akernels, np.complex128),
+                self._np(a1, np.int64), self._np(a2, np.int64), self._np(vis, np.complex128))
+
     def aw_imaging(self, theta, lam, wkernels, wbins, akernels, uvw, src, vis):
-        """src/Gridding.hs:452-478 (aw_imagingOld :480-506 gives the same grid); src = (a1, a2, t, f)"""
+        """src/Gridding.hs:452-478 (aw_imagingOld :480-506 gives the same grid); src = (a1, a2, t, f).
+        torch cuda tensors take the device-resident form (gridhip_aw_imaging_dev) and return a cuda tensor."""
+        if _is_torch(vis):
+            import torch
+            u, v, w, st = self._uvw_dev(uvw)
+            wk, wv, ak, a1, a2, vis = self._aw_dev_args(wkernels, wbins, akernels, src[0], src[1], vis)
+            W, Q, _, S, _ = wk.shape
+            N = self.image_size(theta, lam)
+            g = torch.empty((N, N), dtype=torch.complex128, device=vis.device)
+            self._use_torch_stream()
+            self._check(self._lib.gridhip_aw_imaging_dev(
+                self._h, float(theta), int(lam), W, Q, S, ak.shape[0], self._ptr(wk), self._ptr(wv), self._ptr(ak),
+                int(vis.shape[0]), self._ptr(u), self._ptr(v), self._ptr(w), st, self._ptr(a1), self._ptr(a2),
+                self._ptr(vis), self._ptr(g)))
+            return g
         u, v, w, st = self._uvw(uvw)
         vis = self._np(vis, np.complex128)
         wk, ak = self._np(wkernels, np.complex128), self._np(akernels, np.complex128)
@@ -401,10 +426,14 @@ class Context:
         return g
 
     def do_imaging(self, theta, lam, uvw, a1, a2, t, f, vis, imgfn):
-        """:509-549 -> (image, psf, pmax).  imgfn = ("simple",) | ("conv", kv) | ("w_cache", kernops);
-        a1, a2, t, f (src) are accepted for signature parity and unused by these imaging functions.
-        torch cuda tensors (uvw, vis, and kv for "conv") take the device-resident form (gridhip_do_imaging_dev):
-        nothing crosses PCIe, image and psf come back as cuda tensors."""
+        """:509-549 -> (image, psf, pmax).  imgfn = ("simple",) | ("conv", kv) | ("w_cache", kernops) |
+        ("aw", wkernels, wbins, akernels); a1, a2 feed the antenna indices of "aw" (not swapped by the mirror), t, f
+        (src) are accepted for signature parity and unused by these imaging functions.
+        torch cuda tensors (uvw, vis, and kv / the aw tables and antennas) take the device-resident form
+        (gridhip_do_imaging_dev / gridhip_do_imaging_aw_dev): nothing crosses PCIe, image and psf come back as cuda
+        tensors."""
+        if imgfn[0] == "aw":
+            return self._do_imaging_aw(theta, lam, uvw, a1, a2, vis, imgfn[1], imgfn[2], imgfn[3])
         dev = _is_torch(vis)
         N = self.image_size(theta, lam)
         if dev:
@@ -435,6 +464,41 @@ class Context:
                        self._ptr(u), self._ptr(v), self._ptr(w), st, self._ptr(vis), self._ptr(img), self._ptr(psf),
                        C.byref(pmax)))
         return img, psf, pmax.value
+
+    def _aw_call(self, fn_host, fn_dev, head, theta, lam, wkernels, wbins, akernels, uvw, a1, a2, vis, nout):
+        """shared marshalling of gridhip_do_imaging_aw[_dev] (nout 2) and gridhip_aw_gridding[_dev] (nout 1)"""
+        dev = _is_torch(vis)
+        N = self.image_size(theta, lam)
+        if dev:
+            import torch
+            u, v, w, st = self._uvw_dev(uvw)
+            wk, wv, ak, a1, a2, vis = self._aw_dev_args(wkernels, wbins, akernels, a1, a2, vis)
+            outs = [torch.empty((N, N), dtype=torch.float64, device=vis.device) for _ in range(nout)]
+            self._use_torch_stream()
+        else:
+            u, v, w, st = self._uvw(uvw)
+            wk, wv, ak, a1, a2, vis = self._aw_host_args(wkernels, wbins, akernels, a1, a2, vis)
+            outs = [np.empty((N, N), dtype=np.float64) for _ in range(nout)]
+        W, Q, _, S, _ = wk.shape
+        mx = C.c_double()
+        fn = fn_dev if dev else fn_host
+        self._check(fn(self._h, float(theta), int(lam), *head, W, Q, S, ak.shape[0], self._ptr(wk), self._ptr(wv),
+                       self._ptr(ak), int(vis.shape[0]), self._ptr(u), self._ptr(v), self._ptr(w), st, self._ptr(a1),
+                       self._ptr(a2), self._ptr(vis), *[self._ptr(o) for o in outs], C.byref(mx)))
+        return outs, mx.value
+
+    def _do_imaging_aw(self, theta, lam, uvw, a1, a2, vis, wkernels, wbins, akernels):
+        (img, psf), pmax = self._aw_call(self._lib.gridhip_do_imaging_aw, self._lib.gridhip_do_imaging_aw_dev, (),
+                                         theta, lam, wkernels, wbins, akernels, uvw, a1, a2, vis, 2)
+        return img, psf, pmax
+
+    def aw_gridding(self, theta, lam, f, wkernels, wbins, akernels, uvw_m, a1, a2, vis):
+        """src/ImageDataset.hs:54-77 as one call (gridhip_aw_gridding[_dev]): uvw_m in metres ((n, 3) or a (u, v, w)
+        tuple), f in Hz; doweight on the un-mirrored uvw, mirror, aw_imaging, make_grid_hermitian, real . ifft.
+        Returns (image, max pixel); torch cuda tensors take the device-resident form and return a cuda image."""
+        (img,), mx = self._aw_call(self._lib.gridhip_aw_gridding, self._lib.gridhip_aw_gridding_dev, (float(f),),
+                                   theta, lam, wkernels, wbins, akernels, uvw_m, a1, a2, vis, 1)
+        return img, mx
 
 
 class Plan:

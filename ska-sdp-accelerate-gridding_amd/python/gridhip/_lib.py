@@ -22,6 +22,10 @@ EINVAL, ENOMEM, EHIP, ENODEV, EUNSUPPORTED = -1, -2, -3, -4, -5
 _GRID_DEV = [vp, i64, i64, vp, i64, vp, vp, i64, vp]
 _CONV_DEV = [vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, vp]
 _CONV2_DEV = [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp]
+_AW_IMG = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp,
+           C.POINTER(C.c_double)]
+_AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp,
+                C.POINTER(C.c_double)]
 SIGNATURES = {
     "gridhip_version": (ci, []),
     "gridhip_strerror": (C.c_char_p, [ci]),
@@ -64,6 +68,12 @@ SIGNATURES = {
     "gridhip_aw_last_stats": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "gridhip_aw_imaging": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
                                 vp, vp]),
+    "gridhip_aw_imaging_dev": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp,
+                                    vp, vp, vp]),
+    "gridhip_do_imaging_aw": (ci, _AW_IMG),
+    "gridhip_do_imaging_aw_dev": (ci, _AW_IMG),
+    "gridhip_aw_gridding": (ci, _AW_GRIDDING),
+    "gridhip_aw_gridding_dev": (ci, _AW_GRIDDING),
     "gridhip_do_imaging": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp,
                                 vp, C.POINTER(C.c_double)]),
     "gridhip_do_imaging_dev": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp,

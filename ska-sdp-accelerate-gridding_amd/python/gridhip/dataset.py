@@ -85,7 +85,8 @@ def readSource(file):
 
 def aw_gridding(ctx, wfile, afile, datfile, n=None, outfile=None, theta=0.008, lam=300000):
     """src/ImageDataset.hs:29-86: read -> uvw_lambda -> doweight (on the UN-mirrored uvw, :59) ->
-    mirror_uvw (:60) -> aw_imaging on vis*wt (:72-73) -> make_grid_hermitian -> real . ifft -> /img.
+    mirror_uvw (:60) -> aw_imaging on vis*wt (:72-73) -> make_grid_hermitian -> real . ifft -> /img; everything
+    after the reads is one gridhip_aw_gridding call (Context.aw_gridding).
     Returns (image, max pixel).  theta / lam default to the reference's hard-coded values (:32-33)."""
     vis = readVis(datfile)
     uvw = readBaselines(datfile)
@@ -93,17 +94,12 @@ def aw_gridding(ctx, wfile, afile, datfile, n=None, outfile=None, theta=0.008, l
     akerns = getAKernels(afile, theta, float(ts.reshape(-1)[0]), f)
     wkerns, wbins = getWKernels(wfile, theta)
     n = len(vis) if n is None else min(int(n), len(vis))
-    uvw0 = uvw_lambda(f, uvw[:n])
-    vis0 = vis[:n]
-    cols = (uvw0[:, 0].copy(), uvw0[:, 1].copy(), uvw0[:, 2].copy())
-    wt = ctx.doweight(theta, lam, cols, np.ones(n, dtype=np.complex128))
-    uvw1, vis1 = ctx.mirror_uvw(cols, vis0)
-    uvgrid = ctx.aw_imaging(theta, lam, wkerns, wbins, akerns, uvw1, (a1[:n], a2[:n], ts, f), vis1 * wt)
-    img = np.real(ctx.ifft(ctx.make_grid_hermitian(uvgrid)))
+    # uvw_lambda, doweight, mirror_uvw, aw_imaging, make_grid_hermitian, real . ifft and the maximum: one library call
+    img, mx = ctx.aw_gridding(theta, lam, f, wkerns, wbins, akerns, uvw[:n], a1[:n], a2[:n], vis[:n])
     if outfile is not None:
         h5io.createh5File(outfile)
         h5io.createDataset(outfile, "/img", img)
-    return img, float(img.max())
+    return img, float(mx)
 
 
 def write_synthetic_dataset(prefix, n=400, nant=4, nw=5, Q=2, S=15, theta=0.008, lam=300000, seed=0):

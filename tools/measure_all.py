@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Measure the secondary configurations on one GPU (the headline number comes from bench.py):
 cfg2 grid, cfg3 grid with the 'core' distribution, cfg3 degrid, plans, cfg4 aw-gridding with and without the per-key
-cache, the cfg5 share, a support sweep, do_imaging at N = 2400, the host-pointer ABI.  Prints one JSON line per measurement; timings are HIP-event totals (pre-pass + kernel) or wall time."""
+cache, the cfg5 share, a support sweep, do_imaging at N = 2400, the host-pointer ABI, and (aw_imaging) do_imaging with
+aw_imaging and the one-call aw_gridding at N = 2400 against the composition of single-step calls.  Prints one JSON line per measurement; timings are HIP-event totals (pre-pass + kernel) or wall time."""
 import json
 import os
 import sys
@@ -47,7 +48,7 @@ def report(name, n, t_ms, extra=None):
     print(json.dumps(d), flush=True)
 
 
-which = sys.argv[1:] or ["cfg2", "core", "degrid", "aw", "cfg5", "plan", "supports", "imaging", "host"]
+which = sys.argv[1:] or ["cfg2", "core", "degrid", "aw", "cfg5", "plan", "supports", "imaging", "host", "aw_imaging"]
 if "host" in which:
     # PCIe-inclusive rate of the drop-in host-pointer ABI (pageable numpy arrays in, grid out)
     n, N, W, Q, S = 20_000_000, 4096, 128, 8, 15
@@ -171,3 +172,46 @@ if "imaging" in which:
                     "same_as_host_form": bool(abs(dpmax - pmax) <= 1e-12 * abs(pmax))})
             del duvw, dvis, dimg, dpsf
         del uvw, vis
+if "aw_imaging" in which:
+    # do_imaging with imgfn = aw_imaging (gridhip_do_imaging_aw_dev) and aw_gridding in one call (gridhip_aw_gridding_dev)
+    # at the driver's size, N = theta * lam = 2400 (src/ImageDataset.hs:32-33), on cfg4's aw stream: 15 x 15, Q = 8,
+    # 128 w-planes, 512 antennas; 1.3e5 visibilities (the reference dataset's size) and 1e6.  Every other baseline is
+    # given with v < 0, so that the mirror has work.  Wall times with the stream synchronised; device-resident inputs.
+    theta, lam, f = 0.008, 300000, 1.0e8
+    W, Q, S, A = 128, 8, 15, 512
+    wk = bench.synth_kernels(W, Q, S, dev)
+    ak = bench.synth_akernels(A, S, dev)
+    wv = torch.arange(W, dtype=torch.float64, device=dev) * 100.0 - 6400.0
+    for n in (130_000, 1_000_000):
+        u, v, wb, a1, a2, vis = bench.synth_aw_stream(n, ctx.image_size(theta, lam), W, S, A, 21, dev)
+        sgn = 1.0 - 2.0 * ((torch.arange(n, device=dev) // 8) % 2).to(torch.float64)
+        uvw = torch.stack([u * lam * sgn, v * lam * sgn, wv[wb] * sgn], dim=1).contiguous()
+        vis = torch.where(sgn > 0, vis, vis.conj()).contiguous()
+        imgfn = ("aw", wk, wv, ak)
+        t_do = wall(lambda: ctx.do_imaging(theta, lam, uvw, a1, a2, None, None, vis, imgfn), 3)
+        extra = {"aw_tables_built": ctx.get_option("aw_tables_built"), "kernels_built": ctx.aw_stats(S)["kernels_built"],
+                 "aw_clock_khz": ctx.get_option("aw_clock_khz"), "errors": ctx.get_option("errors")}
+        # the naive composition on the same inputs: mirror + weights (done once, not timed), then two aw_imaging_dev
+        # calls, each building the kernel table, and make_grid_hermitian + ifft of each grid (host-pointer forms)
+        huvw, hvis = uvw.cpu().numpy(), vis.cpu().numpy()
+        m, vis1 = ctx.mirror_uvw((huvw[:, 0], huvw[:, 1], huvw[:, 2]), hvis)
+        wt = ctx.doweight(theta, lam, m, np.ones(n, dtype=np.complex128))
+        duvw1 = torch.from_numpy(np.stack(m, axis=1)).to(dev)
+        dwv, dwt = torch.from_numpy(vis1 * wt).to(dev), torch.from_numpy(wt).to(dev)
+        two = lambda: [ctx.aw_imaging(theta, lam, wk, wv, ak, duvw1, (a1, a2, None, None), x) for x in (dwv, dwt)]
+        t_two = wall(two, 3)
+        t_naive = wall(lambda: [np.real(ctx.ifft(ctx.make_grid_hermitian(g.cpu().numpy()))) for g in two()], 1)
+        hwk, hwv, hak, ha1, ha2 = (x.cpu().numpy() for x in (wk, wv, ak, a1, a2))
+        t0 = time.perf_counter()
+        ctx.do_imaging(theta, lam, huvw, ha1, ha2, None, None, hvis, ("aw", hwk, hwv, hak))
+        t_host = (time.perf_counter() - t0) * 1e3
+        uvw_m = (uvw * (299792458.0 / f)).contiguous()
+        t_grid = wall(lambda: ctx.aw_gridding(theta, lam, f, wk, wv, ak, uvw_m, a1, a2, vis), 3)
+        extra.update({"two_aw_imaging_dev_ms": round(t_two, 3), "naive_composition_ms": round(t_naive, 3),
+                      "ratio_vs_two_aw_imaging_dev": round(t_do / t_two, 3),
+                      "ratio_vs_naive_composition": round(t_do / t_naive, 3), "host_form_ms": round(t_host, 3)})
+        report("do_imaging_aw_dev N=2400, 15x15, Q=8, 128 planes, 512 antennas (image + PSF, one kernel table per batch)",
+               n, t_do, extra)
+        report("aw_gridding_dev N=2400 (uvw in metres -> image, max; src/ImageDataset.hs:54-77 as one call)", n, t_grid,
+               {"aw_tables_built": ctx.get_option("aw_tables_built")})
+        del u, v, wb, a1, a2, vis, uvw, duvw1, dwv, dwt, uvw_m
