@@ -23,7 +23,7 @@
 module GridHip
   ( GridHip, withGridHip, openGridHip, closeGridHip, setOption, getOption
   -- * gridders (IO forms of src/Gridding.hs:95-98, 153-157, 199-204, 246-252, 318-324)
-  , gridIO, convgridIO, convgrid2IO, degrid2IO, awgridIO
+  , gridIO, convgridIO, convgrid2IO, degrid2IO, awgridIO, awdegridIO
   -- * imaging functions and do_imaging (src/Gridding.hs:76-93, 115-124, 399-449, 452-478, 509-549)
   , simpleImagingIO, convImagingIO, wCacheImagingIO, awImagingIO, doImagingIO, ImagingKind(..)
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
@@ -47,6 +47,7 @@ import Types   -- F, Visibility, BaseLine, BaseLines, Antenna (src/Types.hs:7-16
 
 data Ctx
 data Plan
+data AwPlan
 data Comm
 newtype GridHip = GridHip (Ptr Ctx)
 newtype Node    = Node (Ptr Comm)
@@ -171,6 +172,24 @@ foreign import ccall unsafe "gridhip_awgrid_dev"
 -- int gridhip_aw_last_stats(ctx, vis_keyed, kernels_built)
 foreign import ccall unsafe "gridhip_aw_last_stats"
   c_aw_last_stats :: Ptr Ctx -> Ptr Int64 -> Ptr Int64 -> IO CInt
+-- int gridhip_awdegrid(ctx, H, Wd, grid, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2, vis_out)
+foreign import ccall unsafe "gridhip_awdegrid"
+  c_awdegrid :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_awdegrid_dev(ctx, H, Wd, grid, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2, vis_out)
+foreign import ccall unsafe "gridhip_awdegrid_dev"
+  c_awdegrid_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_aw_plan_create_dev(ctx, H, Wd, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2, plan)
+foreign import ccall unsafe "gridhip_aw_plan_create_dev"
+  c_aw_plan_create_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr (Ptr AwPlan) -> IO CInt
+-- int gridhip_aw_plan_grid_dev(plan, vis, grid)
+foreign import ccall unsafe "gridhip_aw_plan_grid_dev"
+  c_aw_plan_grid_dev :: Ptr AwPlan -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_aw_plan_degrid_dev(plan, grid, vis_out)
+foreign import ccall unsafe "gridhip_aw_plan_degrid_dev"
+  c_aw_plan_degrid_dev :: Ptr AwPlan -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_aw_plan_destroy(plan)
+foreign import ccall unsafe "gridhip_aw_plan_destroy"
+  c_aw_plan_destroy :: Ptr AwPlan -> IO CInt
 -- int gridhip_aw_imaging(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis, grid)
 foreign import ccall unsafe "gridhip_aw_imaging"
   c_aw_imaging :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
@@ -402,6 +421,21 @@ awgridIO h@(GridHip c) wkerns akerns a p index v = do
     withIdx3 index $ \wb a1 a2 -> withCplx v $ \vs ->
       c_awgrid c (fi hgt) (fi wid) o (fi n) (fi w) (fi q) (fi s) (fi na) wk ak pu pv 1 wb a1 a2 vs >>= check h
   return (adoptGrid out hgt wid)
+
+-- | the gather twin of convgrid4: wkerns akerns a p index -> one prediction per baseline, with the kernel awgridIO
+-- scatters (conj . aw_kernel_fn2, not conjugated again); out-of-range indices predict 0 (the reference has no degrid)
+awdegridIO :: GridHip -> A.Array A.DIM5 Visibility -> A.Array A.DIM3 Visibility -> A.Matrix Visibility
+           -> A.Vector BaseLines -> A.Vector (Int, Int, Int) -> IO (A.Vector Visibility)
+awdegridIO h@(GridHip c) wkerns akerns a p index = do
+  let A.Z A.:. w A.:. q A.:. _ A.:. s A.:. _ = A.arrayShape wkerns
+      A.Z A.:. na A.:. _ A.:. _ = A.arrayShape akerns
+      A.Z A.:. hgt A.:. wid = A.arrayShape a
+      A.Z A.:. n = A.arrayShape index
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  withForeignPtr out $ \o -> withCplx wkerns $ \wk -> withCplx akerns $ \ak -> withCplx a $ \g ->
+    withUVW p $ \pu pv _ -> withIdx3 index $ \wb a1 a2 ->
+      c_awdegrid c (fi hgt) (fi wid) g (fi n) (fi w) (fi q) (fi s) (fi na) wk ak pu pv 1 wb a1 a2 o >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out))
 
 -- ---------------------------------------------------------------------------------------------------------
 -- ImagingFunctions (src/Gridding.hs:76-81): theta lam uvw src vis -> grid.  uvw in wavelengths; `src` is only used

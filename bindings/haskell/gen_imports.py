@@ -19,6 +19,8 @@ TYPES = [
     (r"^(const )?gridhip_ctx \*$", "Ptr Ctx"),
     (r"^gridhip_plan \*\*$", "Ptr (Ptr Plan)"),
     (r"^gridhip_plan \*$", "Ptr Plan"),
+    (r"^gridhip_aw_plan \*\*$", "Ptr (Ptr AwPlan)"),
+    (r"^gridhip_aw_plan \*$", "Ptr AwPlan"),
     (r"^gridhip_comm \*\*$", "Ptr (Ptr Comm)"),
     (r"^(const )?gridhip_comm \*$", "Ptr Comm"),
     (r"^double \*const \*$", "Ptr (Ptr CDouble)"),

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 120 /* 0.1.2 */
+#define GRIDHIP_VERSION 130 /* 0.1.3 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -123,8 +123,9 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last
  * convgrid / convgrid2 / degrid2 call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
- * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / imaging call built;
- * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan call used:
+ * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or
+ * aw plan creation built (0 after an aw plan pass);
+ * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan / awdegrid / aw plan pass call used:
  * 1 = the tap-reusing tile kernel (square supports 5..32 with enough visibilities per work item), 2 = the same through
  * sub-footprints (other shapes: one record per spatial part of the kernel), 3 = the general tile kernel (small
  * problems, and the sizes listed under "Limits" below: 2 - 3 x slower per visibility at scale), 4 = direct
@@ -251,9 +252,48 @@ int gridhip_awgrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, in
                        int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
                        const double *u, const double *v, int64_t uv_stride, const int64_t *wbin,
                        const int64_t *a1, const int64_t *a2, const double *vis);
-/* What the last gridhip_awgrid / gridhip_awgrid_dev call on this context did (synchronises): visibilities that
- * received a kernel, and distinct (a1, a2, wbin, yf, xf) kernels built for them (equal with "aw_cache" = 0). */
+/* What the last gridhip_awgrid / gridhip_awgrid_dev / gridhip_awdegrid* / gridhip_aw_plan_create_dev call on this
+ * context did (synchronises): visibilities that received a kernel, and distinct (a1, a2, wbin, yf, xf) kernels built
+ * for them (equal with "aw_cache" = 0). */
 int gridhip_aw_last_stats(gridhip_ctx *ctx, int64_t *vis_keyed, int64_t *kernels_built);
+/* awdegrid — the gather that matches convgrid4's scatter (absent from the reference, like degrid2; parity is
+ * unpinned there): the same coordinates (frac_coords, the half-support shift) and the same kernel the gridder scatters,
+ *     awkern_k   = conj(aw_kernel_fn2(yf_k, xf_k, wkerns[wbin_k], akerns[a1_k], akerns[a2_k]))   (:761-775)
+ *     vis_out[k] = sum_ij awkern_k[i,j] * G[y0_k+i, x0_k+j]      (taps outside the grid contribute 0)
+ * i.e. the gridding kernel as given, not conjugated (degrid2's convention).  Adjoint identity:
+ * vdot(g, awgrid(wk, ak, vis)) == vdot(awdegrid(conj wk, conj ak, g), vis).  vis_out is overwritten, not accumulated;
+ * a visibility whose wbin, a1 or a2 is out of range predicts exactly 0 and is counted (gridhip_last_dropped), as the
+ * aw gridder counts it.  Limits and errors are gridhip_awgrid's; a support the LDS tile cannot hold for a gather is
+ * GRIDHIP_EUNSUPPORTED, as for degrid2.  "last_path" = 1 (tap-reusing tile kernel, square supports 5..16) or 3
+ * (general tile kernel).  The host form is synchronous, the _dev form takes device pointers and is asynchronous. */
+int gridhip_awdegrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid, int64_t n, int64_t W,
+                     int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
+                     const double *u, const double *v, int64_t uv_stride, const int64_t *wbin,
+                     const int64_t *a1, const int64_t *a2, double *vis_out);
+int gridhip_awdegrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid, int64_t n, int64_t W,
+                         int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
+                         const double *u, const double *v, int64_t uv_stride, const int64_t *wbin,
+                         const int64_t *a1, const int64_t *a2, double *vis_out);
+/* ---- aw plans: key, build and bin the baselines once, grid / degrid many times (device pointers) --------------
+ * An aw call spends most of its time building its table of distinct kernels from wkerns / akerns (2.7 - 2.8 of 3.1 ms
+ * at 10^6 visibilities, 4096^2, 15 x 15), and a major cycle re-grids and re-predicts the same baselines with the same
+ * kernels.  Unlike gridhip_plan, an aw plan therefore CAPTURES THE KERNEL VALUES: it keeps, per batch of 2^20
+ * visibilities, the binned records, the bin / work tables and the batch's table of distinct kernels (compacted to
+ * the batch's distinct count).  Every input of create may be freed or overwritten once create has returned; create
+ * synchronises the stream (it reads each batch's distinct count to size that batch's table).  Passes are asynchronous,
+ * build nothing ("aw_tables_built" reads 0 after one) and set "last_path" as awdegrid does.  plan_grid_dev ACCUMULATES
+ * into grid (convgrid4); plan_degrid_dev overwrites vis_out (awdegrid).  gridhip_aw_last_stats and
+ * gridhip_last_dropped report the plan's creation.  Limits and errors are gridhip_awgrid's (a support the LDS tile
+ * cannot hold for a gather: GRIDHIP_EUNSUPPORTED).  A plan belongs to its context (same device, same stream, not
+ * thread-safe) and must be destroyed before it. */
+typedef struct gridhip_aw_plan gridhip_aw_plan;
+int gridhip_aw_plan_create_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q,
+                               int64_t S, int64_t A, const double *wkerns, const double *akerns,
+                               const double *u, const double *v, int64_t uv_stride, const int64_t *wbin,
+                               const int64_t *a1, const int64_t *a2, gridhip_aw_plan **plan);
+int gridhip_aw_plan_grid_dev(gridhip_aw_plan *plan, const double *vis, double *grid);
+int gridhip_aw_plan_degrid_dev(gridhip_aw_plan *plan, const double *grid, double *vis_out);
+int gridhip_aw_plan_destroy(gridhip_aw_plan *plan);
 /* aw_imaging / aw_imagingOld, :452-506: wvals are the W plane w-values searched by findClosest. */
 int gridhip_aw_imaging(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
                        int64_t A, const double *wkerns, const double *wvals, const double *akerns,

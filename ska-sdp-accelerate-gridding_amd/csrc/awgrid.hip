@@ -12,6 +12,8 @@
 //   3. the table of distinct kernels feeds the tap-reusing tile gridder (tile_sorted.hip, AW mode): a record's
 //      slice is its key's index, runs of equal key reuse their taps from registers.
 // Work is done in batches so the kernel table stays bounded; nothing is read back inside a call.
+// The same per-batch preparation feeds the gather (awdegrid: the tile kernel's degrid form reads the same table) and
+// aw plans, which keep each batch's records, tables and compacted kernel table for many passes.
 #include "tile_common.h"
 
 namespace gridhip {
@@ -472,15 +474,181 @@ int launch_build(gridhip_ctx *ctx, const double2 *wk, const double2 *pairk, cons
 
 namespace gridhip {
 
-// The aw batch loop over one or two (vis, grid) pairs.  Per batch the antenna pairs, keys, the kernel table and the
-// binned records are made once; the tile kernel then runs once per pair on the same records and table (it reads
-// ctx->recs and the table, and writes neither).  do_imaging grids its baselines twice - image (wt * vis) and PSF (wt) -
-// so its aw form builds the table once where two aw_imaging calls would build it twice.  Arguments are checked by the
-// callers; device pointers; asynchronous.
-int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *const *grids, const double *const *viss,
-                 int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
-                 const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
-                 const int64_t *a2)
+// What an aw call decides before its batch loop, and where its scratch lies (ctx->aw).
+struct AwCall {
+    int64_t W = 0, Q = 0, S = 0, A = 0, batch = 0;
+    int32_t pair_cap = 0;
+    int cache = 0;
+    uint32_t hslots = 0;
+    int32_t *slot = nullptr, *pairlist = nullptr, *counters = nullptr, *hid = nullptr, *kid = nullptr;
+    double2 *pairk = nullptr, *table = nullptr;  // table: the call scratch's, of batch capacity (null for a plan)
+    unsigned long long *htab = nullptr, *ukey = nullptr;
+    int64_t *ok = nullptr;
+    Prep p;  // geometry of the tile step (one plane: `ok` stands in for wbin; every slice is private to its key)
+};
+
+// Limits, then scratch and geometry for n visibilities.  with_table: the call scratch holds a kernel table of batch
+// capacity (a plan builds each batch's table in a block of its own, of the batch's distinct count).
+static int aw_setup(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A,
+                    bool with_table, AwCall *c)
+{
+    const size_t S2 = (size_t)S * S, pairs = (size_t)A * A;
+    c->W = W;
+    c->Q = Q;
+    c->S = S;
+    c->A = A;
+    c->cache = ctx->opt.aw_cache != 0;
+    // The table of kernels is sized for the batch whatever the de-duplication finds (nothing is read back inside a
+    // call): 2^20 visibilities per batch with the cache (3.8 GB of table at 15 x 15; the 10^6-visibility benchmark is
+    // one batch), 2^22 without it, where every visibility has a kernel of its own anyway (15 GB).
+    const int64_t bcap = cache_on(ctx) ? ((int64_t)1 << 20) : ((int64_t)1 << 22);
+    c->batch = n < bcap ? n : bcap;
+    c->pair_cap = (int32_t)(pairs < (size_t)n ? pairs : (size_t)n);
+    c->hslots = 1024;
+    while (c->hslots < 2 * (uint64_t)c->batch) c->hslots <<= 1;
+    const int64_t batch = c->batch;
+
+    // ---- scratch (grows on first use; laid out in one workspace)
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_slot = 0, o_plist = o_slot + al(pairs * 4), o_cnt = o_plist + al((size_t)c->pair_cap * 4),
+                 o_pairk = o_cnt + al(64), o_htab = o_pairk + al((size_t)c->pair_cap * S2 * 16),
+                 o_hid = o_htab + al((size_t)c->hslots * 8), o_kid = o_hid + al((size_t)c->hslots * 4),
+                 o_ok = o_kid + al((size_t)batch * 4), o_ukey = o_ok + al((size_t)batch * 8),
+                 o_table = o_ukey + al((size_t)batch * 8), total = o_table + (with_table ? al((size_t)batch * S2 * 16) : 0);
+    GH_CHECK(ws_reserve(ctx, ctx->aw, total));
+    char *base = (char *)ctx->aw.ptr;
+    c->slot = (int32_t *)(base + o_slot);
+    c->pairlist = (int32_t *)(base + o_plist);
+    c->counters = (int32_t *)(base + o_cnt);
+    c->pairk = (double2 *)(base + o_pairk);
+    c->table = with_table ? (double2 *)(base + o_table) : nullptr;
+    c->htab = (unsigned long long *)(base + o_htab);
+    c->ukey = (unsigned long long *)(base + o_ukey);
+    c->hid = (int32_t *)(base + o_hid);
+    c->kid = (int32_t *)(base + o_kid);
+    c->ok = (int64_t *)(base + o_ok);
+
+    Prep &p = c->p;
+    const int64_t keep_w = ctx->opt.wgroups;
+    ctx->opt.wgroups = 1;  // the table is read once per run: nothing for an L2 to keep
+    Geom g;
+    int block;
+    size_t lds;
+    int rc = make_geom(ctx, H, Wd, 1, Q, S, S, batch, &g, &block, &lds, 0);  // (no big-tile form of the aw tile kernel)
+    ctx->opt.wgroups = keep_w;
+    GH_CHECK(rc);
+    g.per_vis = 1;
+    g.nslices = (int32_t)batch;  // table capacity: a record's kslice is brought below it
+    set_rec_bits(&g);
+    p.g = g;
+    p.block = block;
+    p.lds = lds;
+    p.nrec = batch;
+    p.sorted = ctx->opt.sort != 2 && sorted_plan(ctx, p.g, p.block, &p.nkeys, &p.batch, &p.lds_sorted);
+    if (p.sorted) p.g.chunk = p.batch;
+    return GRIDHIP_OK;
+}
+
+// ---- antenna-pair kernels (once per call)
+static int aw_pairs(gridhip_ctx *ctx, const AwCall &c, int64_t n, const double *akerns, const int64_t *a1,
+                    const int64_t *a2)
+{
+    const int64_t A = c.A, S = c.S;
+    GH_CHECK_HIP(ctx, hipMemsetAsync(c.slot, 0xff, (size_t)A * A * 4, ctx->stream));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(c.counters, 0, 64, ctx->stream));
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > ctx->num_cu * 8) blocks = ctx->num_cu * 8;
+    hipLaunchKernelGGL(aw_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n, A, a1, a2, c.slot, c.pairlist,
+                       c.counters, c.pair_cap);
+    switch (S) {
+#define AW_CASE(S_) \
+    case S_: GH_CHECK((launch_build<S_, true>(ctx, (const double2 *)akerns, (const double2 *)akerns, nullptr, c.pairlist, A, c.counters, 0, 0, c.pair_cap, c.pairk, (int64_t)c.pair_cap, (int64_t)A))); break;
+        AW_CASE(5) AW_CASE(7) AW_CASE(9) AW_CASE(11) AW_CASE(13) AW_CASE(15)
+#undef AW_CASE
+        default: {
+            int pb = c.pair_cap < ctx->num_cu * 8 ? c.pair_cap : ctx->num_cu * 8;
+            hipLaunchKernelGGL(aw_pair_kernel, dim3((unsigned)(pb > 0 ? pb : 1)), dim3(256), 2 * S * S * sizeof(double2), ctx->stream,
+                               A, (int)S, (const double2 *)akerns, c.pairlist, c.counters, c.pair_cap, c.pairk, ctx->d_scalars + 31);
+        }
+    }
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+// ---- per batch: keys (the batch's visibilities [lo, lo + m); pointers are the call's)
+static int aw_keys(gridhip_ctx *ctx, const AwCall &c, int64_t H, int64_t Wd, int64_t lo, int64_t m, const double *u,
+                   const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1, const int64_t *a2)
+{
+    if (c.cache) {
+        GH_CHECK_HIP(ctx, hipMemsetAsync(c.htab, 0xff, (size_t)c.hslots * 8, ctx->stream));
+        GH_CHECK_HIP(ctx, hipMemsetAsync(c.counters + 1, 0, 4, ctx->stream));
+    }
+    int64_t kb = (m + 255) / 256;
+    if (kb > ctx->num_cu * 8) kb = ctx->num_cu * 8;
+    hipLaunchKernelGGL(aw_keys_kernel, dim3((unsigned)kb), dim3(256), 0, ctx->stream, H, Wd, m, c.W, (int32_t)c.Q, c.A,
+                       u + lo * uv_stride, v + lo * uv_stride, uv_stride, wbin + lo, a1 + lo, a2 + lo, c.slot, c.cache,
+                       c.htab, c.hid, c.hslots - 1, c.kid, c.ok, c.ukey, c.counters, (int32_t)c.batch);
+    if (c.cache) hipLaunchKernelGGL(aw_kid_kernel, dim3((unsigned)kb), dim3(256), 0, ctx->stream, m, c.hid, c.kid, c.ok);
+    return GRIDHIP_OK;
+}
+
+// ---- per batch: the distinct kernels into `table` (entries below the batch's distinct count and `cap` are written)
+static int aw_build(gridhip_ctx *ctx, const AwCall &c, int64_t m, const double *wkerns, double2 *table, int64_t cap)
+{
+    const int which = c.cache ? 1 : -1;
+    const int64_t nslice = c.W * c.Q * c.Q;
+    switch (c.S) {
+#define AW_CASE(S_) \
+    case S_: GH_CHECK((launch_build<S_, false>(ctx, (const double2 *)wkerns, c.pairk, c.ukey, nullptr, c.A, c.counters, which, (int32_t)m, (int32_t)cap, table, (int64_t)c.pair_cap, nslice))); break;
+        AW_CASE(5) AW_CASE(7) AW_CASE(9) AW_CASE(11) AW_CASE(13) AW_CASE(15)
+#undef AW_CASE
+        default: {
+            int gb = (int)(m < ctx->num_cu * 8 ? m : ctx->num_cu * 8);
+            hipLaunchKernelGGL(aw_build_generic_kernel, dim3((unsigned)gb), dim3(256), 2 * c.S * c.S * sizeof(double2), ctx->stream,
+                               (int)c.S, (const double2 *)wkerns, c.pairk, c.ukey, c.counters, which, (int32_t)m, (int32_t)cap,
+                               table, (int64_t)c.pair_cap, nslice, ctx->d_scalars + 31);
+        }
+    }
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+// ---- per batch: binning into ctx->recs / ctx->tables, then each record's kslice becomes its kernel's index.  The
+// pre-pass drops the visibilities whose `ok` is -1 (counted); zero_out (degrid): it writes their predictions' zeros.
+static int aw_bin(gridhip_ctx *ctx, const AwCall &c, const Geom &g, int64_t lo, int64_t m, const double *u, const double *v,
+                  int64_t uv_stride, double *zero_out)
+{
+    GH_CHECK(launch_bin(ctx, g, m, u + lo * uv_stride, v + lo * uv_stride, uv_stride, c.ok,
+                        zero_out ? reinterpret_cast<double2 *>(zero_out + 2 * lo) : nullptr));
+    Tables t = tables_of(ctx, g);
+    int rb = (int)((m + 255) / 256);
+    if (rb > ctx->num_cu * 8) rb = ctx->num_cu * 8;
+    hipLaunchKernelGGL(aw_relabel_kernel, dim3((unsigned)rb), dim3(256), 0, ctx->stream, g, (RecWord *)ctx->recs.ptr,
+                       t.bin_start + g.nbins, c.kid, (int32_t)m);
+    return GRIDHIP_OK;
+}
+
+// ---- a pass over one batch's binned records (ctx->recs / ctx->tables) and kernel table: gridding adds vis x kernels
+// onto grid; degridding writes the batch's predictions (vis = vis_out, grid read)
+static int aw_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t m, const double2 *table, const double *vis,
+                   double *grid, bool degrid)
+{
+    if (p.sorted)
+        return launch_tile_grid_sorted(ctx, g, p.block, p.lds_sorted, p.nkeys, p.batch, m, (const double *)table, vis, grid,
+                                       degrid);
+    if (degrid) return launch_tile_degrid(ctx, g, p.block, p.lds, m, (const double *)table, grid, const_cast<double *>(vis));
+    return launch_tile_grid(ctx, g, p.block, p.lds, m, (const double *)table, vis, grid);
+}
+
+// The aw batch loop over one or two (vis, grid) pairs, or (vis_out != null) the gather of one grid into vis_out.  Per
+// batch the antenna pairs, keys, the kernel table and the binned records are made once; the tile kernel then runs once
+// per pair on the same records and table (it reads ctx->recs and the table, and writes neither).  do_imaging grids its
+// baselines twice - image (wt * vis) and PSF (wt) - so its aw form builds the table once where two aw_imaging calls
+// would build it twice.  Arguments are checked by the callers; device pointers; asynchronous.
+static int aw_batches(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *const *grids, const double *const *viss,
+                      const double *dgrid, double *vis_out, int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A,
+                      const double *wkerns, const double *akerns, const double *u, const double *v, int64_t uv_stride,
+                      const int64_t *wbin, const int64_t *a1, const int64_t *a2)
 {
     ctx->aw_tables_built = 0;
     if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
@@ -491,127 +659,32 @@ int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *con
     GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
     GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 28, 0, 4 * sizeof(int32_t), ctx->stream));
     if (n == 0) return GRIDHIP_OK;
-    const size_t S2 = (size_t)S * S, pairs = (size_t)A * A;
-    const int cache = ctx->opt.aw_cache != 0;
-    // The table of kernels is sized for the batch whatever the de-duplication finds (nothing is read back inside a
-    // call): 2^20 visibilities per batch with the cache (3.8 GB of table at 15 x 15; the 10^6-visibility benchmark is
-    // one batch), 2^22 without it, where every visibility has a kernel of its own anyway (15 GB).
-    const int64_t bcap = cache_on(ctx) ? ((int64_t)1 << 20) : ((int64_t)1 << 22);
-    const int64_t batch = n < bcap ? n : bcap;
-    const int32_t pair_cap = (int32_t)(pairs < (size_t)n ? pairs : (size_t)n);
-    uint32_t hslots = 1024;
-    while (hslots < 2 * (uint64_t)batch) hslots <<= 1;
-
-    // ---- scratch (grows on first use; laid out in one workspace)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_slot = 0, o_plist = o_slot + al(pairs * 4), o_cnt = o_plist + al((size_t)pair_cap * 4),
-                 o_pairk = o_cnt + al(64), o_htab = o_pairk + al((size_t)pair_cap * S2 * 16),
-                 o_hid = o_htab + al((size_t)hslots * 8), o_kid = o_hid + al((size_t)hslots * 4),
-                 o_ok = o_kid + al((size_t)batch * 4), o_ukey = o_ok + al((size_t)batch * 8),
-                 o_table = o_ukey + al((size_t)batch * 8), total = o_table + al((size_t)batch * S2 * 16);
-    GH_CHECK(ws_reserve(ctx, ctx->aw, total));
-    char *base = (char *)ctx->aw.ptr;
-    int32_t *slot = (int32_t *)(base + o_slot), *pairlist = (int32_t *)(base + o_plist), *counters = (int32_t *)(base + o_cnt);
-    double2 *pairk = (double2 *)(base + o_pairk), *table = (double2 *)(base + o_table);
-    unsigned long long *htab = (unsigned long long *)(base + o_htab), *ukey = (unsigned long long *)(base + o_ukey);
-    int32_t *hid = (int32_t *)(base + o_hid), *kid = (int32_t *)(base + o_kid);
-    int64_t *ok = (int64_t *)(base + o_ok);
-
-    // geometry of the gridding step (one plane: `ok` stands in for wbin; every slice is private to its key)
-    Prep p;
-    {
-        const int64_t keep_w = ctx->opt.wgroups;
-        ctx->opt.wgroups = 1;  // the table is read once per run: nothing for an L2 to keep
-        Geom g;
-        int block;
-        size_t lds;
-        int rc = make_geom(ctx, H, Wd, 1, Q, S, S, batch, &g, &block, &lds, 0);  // (no big-tile form of the aw tile kernel)
-        ctx->opt.wgroups = keep_w;
-        GH_CHECK(rc);
-        g.per_vis = 1;
-        g.nslices = (int32_t)batch;  // table capacity: a record's kslice is brought below it
-        set_rec_bits(&g);
-        p.g = g;
-        p.block = block;
-        p.lds = lds;
-        p.nrec = batch;
-        p.sorted = ctx->opt.sort != 2 && sorted_plan(ctx, p.g, p.block, &p.nkeys, &p.batch, &p.lds_sorted);
-        if (p.sorted) p.g.chunk = p.batch;
-    }
+    const bool degrid = vis_out != nullptr;
+    AwCall c;
+    GH_CHECK(aw_setup(ctx, H, Wd, n, W, Q, S, A, true, &c));
+    Prep &p = c.p;
+    if (degrid) ctx->last_path = p.sorted ? 1 : 3;
     GH_CHECK(ws_reserve(ctx, ctx->tables, tables_bytes(p.g)));
-    GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)batch * sizeof(RecWord)));
+    GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)c.batch * sizeof(RecWord)));
 
     mark(ctx, 0);
-    // ---- antenna-pair kernels
-    GH_CHECK_HIP(ctx, hipMemsetAsync(slot, 0xff, pairs * 4, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(counters, 0, 64, ctx->stream));
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > ctx->num_cu * 8) blocks = ctx->num_cu * 8;
-    hipLaunchKernelGGL(aw_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n, A, a1, a2, slot, pairlist,
-                       counters, pair_cap);
-    switch (S) {
-#define AW_CASE(S_) \
-    case S_: GH_CHECK((launch_build<S_, true>(ctx, (const double2 *)akerns, (const double2 *)akerns, nullptr, pairlist, A, counters, 0, 0, pair_cap, pairk, (int64_t)pair_cap, (int64_t)A))); break;
-        AW_CASE(5) AW_CASE(7) AW_CASE(9) AW_CASE(11) AW_CASE(13) AW_CASE(15)
-#undef AW_CASE
-        default: {
-            int pb = pair_cap < ctx->num_cu * 8 ? pair_cap : ctx->num_cu * 8;
-            hipLaunchKernelGGL(aw_pair_kernel, dim3((unsigned)(pb > 0 ? pb : 1)), dim3(256), 2 * S2 * sizeof(double2), ctx->stream,
-                               A, (int)S, (const double2 *)akerns, pairlist, counters, pair_cap, pairk, ctx->d_scalars + 31);
-        }
-    }
-    GH_CHECK_HIP(ctx, hipGetLastError());
+    GH_CHECK(aw_pairs(ctx, c, n, akerns, a1, a2));
 
     // ---- per batch: keys -> distinct kernels -> binning -> tile gridder
-    for (int64_t lo = 0; lo < n; lo += batch) {
-        const int64_t m = n - lo < batch ? n - lo : batch;
-        const double *bu = u + lo * uv_stride, *bv = v + lo * uv_stride;
-        if (cache) {
-            GH_CHECK_HIP(ctx, hipMemsetAsync(htab, 0xff, (size_t)hslots * 8, ctx->stream));
-            GH_CHECK_HIP(ctx, hipMemsetAsync(counters + 1, 0, 4, ctx->stream));
-        }
-        int64_t kb = (m + 255) / 256;
-        if (kb > ctx->num_cu * 8) kb = ctx->num_cu * 8;
-        hipLaunchKernelGGL(aw_keys_kernel, dim3((unsigned)kb), dim3(256), 0, ctx->stream, H, Wd, m, W, (int32_t)Q, A, bu, bv,
-                           uv_stride, wbin + lo, a1 + lo, a2 + lo, slot, cache, htab, hid, hslots - 1, kid, ok, ukey,
-                           counters, (int32_t)batch);
-        if (cache)
-            hipLaunchKernelGGL(aw_kid_kernel, dim3((unsigned)kb), dim3(256), 0, ctx->stream, m, hid, kid, ok);
-        const int which = cache ? 1 : -1;
-        switch (S) {
-#define AW_CASE(S_) \
-    case S_: GH_CHECK((launch_build<S_, false>(ctx, (const double2 *)wkerns, pairk, ukey, nullptr, A, counters, which, (int32_t)m, (int32_t)batch, table, (int64_t)pair_cap, (int64_t)(W * Q * Q)))); break;
-            AW_CASE(5) AW_CASE(7) AW_CASE(9) AW_CASE(11) AW_CASE(13) AW_CASE(15)
-#undef AW_CASE
-            default: {
-                int gb = (int)(m < ctx->num_cu * 8 ? m : ctx->num_cu * 8);
-                hipLaunchKernelGGL(aw_build_generic_kernel, dim3((unsigned)gb), dim3(256), 2 * S2 * sizeof(double2), ctx->stream,
-                                   (int)S, (const double2 *)wkerns, pairk, ukey, counters, which, (int32_t)m, (int32_t)batch,
-                                   table, (int64_t)pair_cap, (int64_t)(W * Q * Q), ctx->d_scalars + 31);
-            }
-        }
-        GH_CHECK_HIP(ctx, hipGetLastError());
+    for (int64_t lo = 0; lo < n; lo += c.batch) {
+        const int64_t m = n - lo < c.batch ? n - lo : c.batch;
+        GH_CHECK(aw_keys(ctx, c, H, Wd, lo, m, u, v, uv_stride, wbin, a1, a2));
+        GH_CHECK(aw_build(ctx, c, m, wkerns, c.table, c.batch));
         ++ctx->aw_tables_built;
         mark(ctx, 1);
-        // gridding: the pre-pass drops the visibilities whose `ok` is -1 (counted), the tile kernel reads the table
         p.g.nvis = (int32_t)m;
         p.g.nrec = (int32_t)m;
-        GH_CHECK(launch_bin(ctx, p.g, m, bu, bv, uv_stride, ok));
-        Tables t = tables_of(ctx, p.g);
-        {
-            int rb = (int)((m + 255) / 256);
-            if (rb > ctx->num_cu * 8) rb = ctx->num_cu * 8;
-            hipLaunchKernelGGL(aw_relabel_kernel, dim3((unsigned)rb), dim3(256), 0, ctx->stream, p.g, (RecWord *)ctx->recs.ptr,
-                               t.bin_start + p.g.nbins, kid, (int32_t)m);
-        }
-        for (int i = 0; i < npass; ++i) {  // (the tile kernels' errors of every pass land in [2] before the account)
-            if (p.sorted)
-                GH_CHECK(launch_tile_grid_sorted(ctx, p.g, p.block, p.lds_sorted, p.nkeys, p.batch, m, (const double *)table,
-                                                 viss[i] + 2 * lo, grids[i], false));
-            else
-                GH_CHECK(launch_tile_grid(ctx, p.g, p.block, p.lds, m, (const double *)table, viss[i] + 2 * lo, grids[i]));
-        }
-        hipLaunchKernelGGL(aw_account_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars, counters, cache, (int32_t)m);
+        GH_CHECK(aw_bin(ctx, c, p.g, lo, m, u, v, uv_stride, vis_out));
+        if (degrid)
+            GH_CHECK(aw_pass(ctx, p, p.g, m, c.table, vis_out + 2 * lo, const_cast<double *>(dgrid), true));
+        for (int i = 0; i < npass && !degrid; ++i)  // (the tile kernels' errors of every pass land in [2] before the account)
+            GH_CHECK(aw_pass(ctx, p, p.g, m, c.table, viss[i] + 2 * lo, grids[i], false));
+        hipLaunchKernelGGL(aw_account_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars, c.counters, c.cache, (int32_t)m);
         mark(ctx, 2);
     }
     hipLaunchKernelGGL(aw_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars);
@@ -619,7 +692,84 @@ int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *con
     return GRIDHIP_OK;
 }
 
+int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *const *grids, const double *const *viss,
+                 int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
+                 const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
+                 const int64_t *a2)
+{
+    return aw_batches(ctx, H, Wd, npass, grids, viss, nullptr, nullptr, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride,
+                      wbin, a1, a2);
+}
+
 }  // namespace gridhip
+
+// An aw plan: per batch of visibilities its binned records, bin / work tables and the table of its distinct kernels,
+// built once; passes lend them to the tile kernels one batch at a time (plan.hip's Lend).
+struct gridhip_aw_plan {
+    gridhip_ctx *ctx = nullptr;
+    int64_t n = 0;
+    gridhip::Prep p;
+    struct Batch {
+        int64_t lo = 0, m = 0, nkern = 0;
+        gridhip::Workspace recs, tables;
+        double2 *table = nullptr;  // nkern distinct kernels
+        bool all_binned = false;   // no visibility of the batch was dropped: degrid writes all of its predictions
+    };
+    std::vector<Batch> b;
+};
+
+namespace {
+// the launchers read the binned data from the context's scratch slots: lend them a batch's
+struct AwLend {
+    gridhip_ctx *ctx;
+    gridhip_aw_plan::Batch &b;
+    AwLend(gridhip_ctx *c, gridhip_aw_plan::Batch &bb) : ctx(c), b(bb)
+    {
+        std::swap(ctx->recs, b.recs);
+        std::swap(ctx->tables, b.tables);
+    }
+    ~AwLend()
+    {
+        std::swap(ctx->recs, b.recs);
+        std::swap(ctx->tables, b.tables);
+    }
+};
+
+// the geometry a pass over batch b runs with: its visibilities, and its table's distinct kernels as the slices a
+// record's kslice is brought below
+gridhip::Geom batch_geom(const gridhip_aw_plan *pl, const gridhip_aw_plan::Batch &b)
+{
+    gridhip::Geom g = pl->p.g;
+    g.nvis = (int32_t)b.m;
+    g.nrec = (int32_t)b.m;
+    g.nslices = (int32_t)(b.nkern > 0 ? b.nkern : 1);
+    return g;
+}
+
+// gridding: vis in, grid accumulated; degridding (vis_out != null): grid in, vis_out written
+int aw_plan_pass(gridhip_aw_plan *pl, const double *vis, double *grid, double *vis_out)
+{
+    if (!pl) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = pl->ctx;
+    const bool degrid = vis_out != nullptr;
+    if (!grid || (pl->n > 0 && !vis && !vis_out)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->aw_tables_built = 0;
+    ctx->last_path = pl->p.sorted ? 1 : 3;
+    for (auto &b : pl->b) {
+        const gridhip::Geom g = batch_geom(pl, b);
+        if (degrid) {
+            if (!b.all_binned) GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out + 2 * b.lo, 0, (size_t)b.m * 16, ctx->stream));
+            AwLend lend(ctx, b);
+            GH_CHECK(gridhip::aw_pass(ctx, pl->p, g, b.m, b.table, vis_out + 2 * b.lo, grid, true));
+        } else {
+            AwLend lend(ctx, b);
+            GH_CHECK(gridhip::aw_pass(ctx, pl->p, g, b.m, b.table, vis + 2 * b.lo, grid, false));
+        }
+    }
+    return GRIDHIP_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -695,6 +845,170 @@ int gridhip_awgrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_
     GH_CHECK_HIP(ctx, hipMemcpyAsync(grid, dg.p, cells * 16, hipMemcpyDeviceToHost, ctx->stream));
     GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return GRIDHIP_OK;
+}
+
+// The gather with convgrid4's coordinates and kernels (include/gridhip.h); device pointers, asynchronous.
+int gridhip_awdegrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid, int64_t n, int64_t W, int64_t Q,
+                         int64_t S, int64_t A, const double *wkerns, const double *akerns, const double *u,
+                         const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
+                         const int64_t *a2, double *vis_out)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
+        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis_out)))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    return aw_batches(ctx, H, Wd, 0, nullptr, nullptr, grid, n > 0 ? vis_out : nullptr, n, W, Q, S, A, wkerns, akerns, u,
+                      v, uv_stride, wbin, a1, a2);
+}
+
+// Host pointers: stages everything through device blocks of the call's own, synchronous.
+int gridhip_awdegrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid, int64_t n, int64_t W, int64_t Q,
+                     int64_t S, int64_t A, const double *wkerns, const double *akerns, const double *u, const double *v,
+                     int64_t uv_stride, const int64_t *wbin, const int64_t *a1, const int64_t *a2, double *vis_out)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
+        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis_out)))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)H * Wd, span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 1;
+    const size_t wel = (size_t)W * Q * Q * S * S, ael = (size_t)A * S * S;
+    struct Buf {
+        void *p = nullptr;
+        ~Buf()
+        {
+            if (p) (void)hipFree(p);
+        }
+    } dg, du, dv, dwb, da1, da2, dvis, dwk, dak;
+    GH_CHECK_HIP(ctx, hipMalloc(&dg.p, cells * 16));
+    GH_CHECK_HIP(ctx, hipMalloc(&du.p, span * 8));
+    GH_CHECK_HIP(ctx, hipMalloc(&dv.p, span * 8));
+    GH_CHECK_HIP(ctx, hipMalloc(&dwb.p, (size_t)n * 8 + 8));
+    GH_CHECK_HIP(ctx, hipMalloc(&da1.p, (size_t)n * 8 + 8));
+    GH_CHECK_HIP(ctx, hipMalloc(&da2.p, (size_t)n * 8 + 8));
+    GH_CHECK_HIP(ctx, hipMalloc(&dvis.p, (size_t)n * 16 + 16));
+    GH_CHECK_HIP(ctx, hipMalloc(&dwk.p, wel * 16));
+    GH_CHECK_HIP(ctx, hipMalloc(&dak.p, ael * 16));
+    GH_CHECK_HIP(ctx, hipMemcpyAsync(dg.p, grid, cells * 16, hipMemcpyHostToDevice, ctx->stream));
+    GH_CHECK_HIP(ctx, hipMemcpyAsync(dwk.p, wkerns, wel * 16, hipMemcpyHostToDevice, ctx->stream));
+    GH_CHECK_HIP(ctx, hipMemcpyAsync(dak.p, akerns, ael * 16, hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0) {
+        GH_CHECK_HIP(ctx, hipMemcpyAsync(du.p, u, span * 8, hipMemcpyHostToDevice, ctx->stream));
+        GH_CHECK_HIP(ctx, hipMemcpyAsync(dv.p, v, span * 8, hipMemcpyHostToDevice, ctx->stream));
+        GH_CHECK_HIP(ctx, hipMemcpyAsync(dwb.p, wbin, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        GH_CHECK_HIP(ctx, hipMemcpyAsync(da1.p, a1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        GH_CHECK_HIP(ctx, hipMemcpyAsync(da2.p, a2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    GH_CHECK(gridhip_awdegrid_dev(ctx, H, Wd, (const double *)dg.p, n, W, Q, S, A, (const double *)dwk.p,
+                                  (const double *)dak.p, (const double *)du.p, (const double *)dv.p, uv_stride,
+                                  (const int64_t *)dwb.p, (const int64_t *)da1.p, (const int64_t *)da2.p,
+                                  (double *)dvis.p));
+    if (n > 0) GH_CHECK_HIP(ctx, hipMemcpyAsync(vis_out, dvis.p, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GRIDHIP_OK;
+}
+
+int gridhip_aw_plan_destroy(gridhip_aw_plan *pl)
+{
+    if (!pl) return GRIDHIP_OK;
+    (void)hipSetDevice(pl->ctx->device);
+    (void)hipDeviceSynchronize();
+    for (auto &b : pl->b) {
+        if (b.recs.ptr) (void)hipFree(b.recs.ptr);
+        if (b.tables.ptr) (void)hipFree(b.tables.ptr);
+        if (b.table) (void)hipFree(b.table);
+    }
+    delete pl;
+    return GRIDHIP_OK;
+}
+
+// Per batch: keys, then (synchronising) its distinct count sizes a table of the plan's own, which the builder fills;
+// then the binning into blocks of the plan's own.  The inputs are not read after this returns.
+int gridhip_aw_plan_create_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t S,
+                               int64_t A, const double *wkerns, const double *akerns, const double *u, const double *v,
+                               int64_t uv_stride, const int64_t *wbin, const int64_t *a1, const int64_t *a2,
+                               gridhip_aw_plan **out)
+{
+    if (!ctx || !out) return GRIDHIP_EINVAL;
+    *out = nullptr;
+    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !wkerns || !akerns ||
+        (n > 0 && (!u || !v || !wbin || !a1 || !a2)))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    ctx->aw_tables_built = 0;
+    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
+        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 28, 0, 4 * sizeof(int32_t), ctx->stream));
+    gridhip_aw_plan *pl = new (std::nothrow) gridhip_aw_plan();
+    if (!pl) return GRIDHIP_ENOMEM;
+    pl->ctx = ctx;
+    pl->n = n;
+    auto make = [&]() -> int {
+        if (n == 0) return GRIDHIP_OK;
+        AwCall c;
+        GH_CHECK(aw_setup(ctx, H, Wd, n, W, Q, S, A, false, &c));
+        pl->p = c.p;
+        GH_CHECK(aw_pairs(ctx, c, n, akerns, a1, a2));
+        const size_t S2 = (size_t)S * S;
+        for (int64_t lo = 0; lo < n; lo += c.batch) {
+            const int64_t m = n - lo < c.batch ? n - lo : c.batch;
+            pl->b.emplace_back();
+            gridhip_aw_plan::Batch &b = pl->b.back();
+            b.lo = lo;
+            b.m = m;
+            GH_CHECK(aw_keys(ctx, c, H, Wd, lo, m, u, v, uv_stride, wbin, a1, a2));
+            int32_t nk = (int32_t)m;
+            if (c.cache) {
+                GH_CHECK_HIP(ctx, hipMemcpyAsync(&nk, c.counters + 1, sizeof nk, hipMemcpyDeviceToHost, ctx->stream));
+                GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            b.nkern = nk < 0 ? 0 : nk > m ? m : nk;
+            GH_CHECK_HIP(ctx, hipMalloc((void **)&b.table, (size_t)(b.nkern > 0 ? b.nkern : 1) * S2 * 16));
+            GH_CHECK(aw_build(ctx, c, m, wkerns, b.table, b.nkern));
+            ++ctx->aw_tables_built;
+            Geom g = c.p.g;
+            g.nvis = (int32_t)m;
+            g.nrec = (int32_t)m;
+            int32_t binned = 0;
+            {
+                AwLend lend(ctx, b);
+                GH_CHECK(ws_reserve(ctx, ctx->tables, tables_bytes(g)));
+                GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)m * sizeof(RecWord)));
+                GH_CHECK(aw_bin(ctx, c, g, lo, m, u, v, uv_stride, nullptr));
+                const Tables t = tables_of(ctx, g);
+                GH_CHECK_HIP(ctx, hipMemcpyAsync(&binned, t.bin_start + g.nbins, sizeof binned, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            hipLaunchKernelGGL(aw_account_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars, c.counters, c.cache, (int32_t)m);
+            GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the batch's binned count)
+            b.all_binned = binned == (int32_t)m && ctx->opt.fault_inject == 0;
+        }
+        hipLaunchKernelGGL(aw_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars);
+        GH_CHECK_HIP(ctx, hipGetLastError());
+        // the inputs may be freed or overwritten once this returns
+        GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return GRIDHIP_OK;
+    };
+    const int rc = make();
+    if (rc != GRIDHIP_OK) {
+        gridhip_aw_plan_destroy(pl);
+        return rc;
+    }
+    *out = pl;
+    return GRIDHIP_OK;
+}
+
+int gridhip_aw_plan_grid_dev(gridhip_aw_plan *plan, const double *vis, double *grid)
+{
+    return aw_plan_pass(plan, vis, grid, nullptr);
+}
+
+int gridhip_aw_plan_degrid_dev(gridhip_aw_plan *plan, const double *grid, double *vis_out)
+{
+    if (!plan) return GRIDHIP_EINVAL;
+    if (plan->n > 0 && !vis_out) return fail(plan->ctx, GRIDHIP_EINVAL, "null pointer");
+    if (plan->n == 0) return grid ? GRIDHIP_OK : fail(plan->ctx, GRIDHIP_EINVAL, "null pointer");
+    return aw_plan_pass(plan, nullptr, const_cast<double *>(grid), vis_out);
 }
 
 }  // extern "C"

@@ -59,8 +59,10 @@ struct SortedItem {
 // AW (aw gridders, awgrid.hip): a record's kslice is the index of its de-duplicated (a1, a2, wbin, yf, xf) kernel in a
 // table built for this call - arbitrary 31-bit numbers, far more of them than a histogram holds.  The counting sort
 // then orders by kslice mod nkeys (equal kernels still end up next to each other unless two of them share a
-// residue) and the sorted list carries the kslice itself in place of `orig`, which gridding does not need; a run
-// is a stretch of equal kslice.
+// residue) and the sorted list carries the kslice itself in place of `orig`; a run is a stretch of equal kslice.
+// Gridding needs no `orig` there (the sorter stages the values next to the list); the gather (aw degrid) has no
+// values to stage, and the sorter stages each record's `orig` in that slot instead (4 bytes per record), which the
+// walkers read with the list to know where a prediction goes.
 // BT ("big tile"): the im plane follows the re plane at Geom.imoff bytes, a run-time distance that may exceed what a DS
 // instruction's offset field holds - the tile may then use all of the LDS (65 x 110 cells instead of 65 x 89 at
 // 15 x 15: a quarter more visibilities per slice and item, what counts where the walk waits for taps) at the price of
@@ -121,12 +123,14 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
     // this work-group's two halves of the sorted-list scratch
     double2 *svals_wg = sorted_vals + (size_t)blockIdx.x * 2 * batch;
     uint2 *smo_wg = sorted_mo + (size_t)blockIdx.x * 2 * batch;
+    int32_t *sorig_wg = reinterpret_cast<int32_t *>(sorted_vals) + (size_t)blockIdx.x * 2 * batch;  // (STAGE_ORIG)
 
     // Where a record's visibility value comes from.  w-projection gridding: the walkers gather it themselves from the
     // caller's array, a block of 64 records ahead of its use - the sorted list then carries 8 bytes per record and the
     // values cross the memory system once.  aw gridding: the list's second word is the kernel's index, so the sorter
     // gathers the values and stages them next to the list (16 bytes more per record, written and read back).
     constexpr bool STAGE_VALS = !DEGRID && AW;
+    constexpr bool STAGE_ORIG = DEGRID && AW;  // (the aw gather: orig travels next to the list)
     const bool solo = nw == 1;
     const bool is_sorter = wave == nw - 1;
     // the sorter is the youngest wave of its SIMD, i.e. last at the arbiter, and its work is a chain of latencies:
@@ -188,6 +192,7 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
         const int first_slice = first_plane * g.Q * g.Q * g.P;
         double2 *svals = svals_wg + (size_t)slot * batch;
         uint2 *smo = smo_wg + (size_t)slot * batch;
+        int32_t *sorig = sorig_wg + (size_t)slot * batch;
         const int b_lo = w.v_lo;
         const int cnt = min(batch, w.v_hi - b_lo);  // a work item never holds more than `batch` records
         // counting sort by kernel slice, one wave: LDS operations of a wave execute in program order; the
@@ -263,6 +268,7 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
                     smo[pos] = make_uint2(((uint32_t)key << 16) | (uint32_t)((rec[q].lxy >> 16) * g.ldw + (rec[q].lxy & 0xffff)),
                                           (uint32_t)(AW ? rec[q].kslice : rec[q].orig));
                     if (STAGE_VALS) svals[pos] = val[q];
+                    if (STAGE_ORIG) sorig[pos] = rec[q].orig;
                 } else
                     ++bad;
             }
@@ -304,6 +310,7 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
     auto walk = [&](int slot, int staged, int first_slice) {
         const double2 *svals = svals_wg + (size_t)slot * batch;
         const uint2 *smo = smo_wg + (size_t)slot * batch;
+        const int32_t *sorig = sorig_wg + (size_t)slot * batch;
         // With 15 walkers the pieces are weighted: the SIMD arbiter favours its oldest wave, so with equal pieces
         // walkers 0..3 finish at 0.55 of the walk and the last three run on for the rest with the LDS unit half idle.
         // cut[w] / 1024 = share of the list in front of walker w (option dbg = 256: equal pieces, for comparison).
@@ -316,10 +323,11 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
             seg_hi = (int)(((int64_t)staged * (wave + 1)) / nwalk);
         }
         if (seg_lo >= seg_hi) return;
-        auto load_list = [&](int b0, uint2 &mo, double2 &v) {
+        auto load_list = [&](int b0, uint2 &mo, double2 &v, int32_t &o) {
             const int idx = max(min(b0 + lane, seg_hi - 1), seg_lo);  // past the end: the piece's last record
             mo = smo[idx];
             if (STAGE_VALS) v = svals[idx];
+            if (STAGE_ORIG) o = sorig[idx];
         };
         auto load_value = [&](const uint2 &mo, double2 &v) {  // (mo.y = orig, brought below nvis by the sorter)
             if (!DEGRID && !STAGE_VALS) v = (ABL & 8) ? make_double2(1.0, 2.0) : load_nt(vis + mo.y);
@@ -359,16 +367,19 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
         // two blocks of the list and one block of values are in flight ahead of the block being accumulated
         uint2 moN, moNN;
         double2 vN = make_double2(0.0, 0.0), vNN = make_double2(0.0, 0.0);
-        load_list(seg_lo, moN, vN);
-        load_list(seg_lo + 64, moNN, vNN);
+        int32_t oN = 0, oNN = 0;  // (STAGE_ORIG) the records' `orig`
+        load_list(seg_lo, moN, vN, oN);
+        load_list(seg_lo + 64, moNN, vNN, oNN);
         load_value(moN, vN);
         for (int b0 = seg_lo; b0 < seg_hi; b0 += 64) {
             const uint2 mo = moN;
             const double2 vB = vN;
+            const int32_t oB = oN;
             moN = moNN;
             vN = vNN;
+            oN = oNN;
             load_value(moN, vN);                      // the next block's values (its list entries arrived a block ago) ...
-            load_list(b0 + 128, moNN, vNN);           // ... and the list entries of the one after travel meanwhile
+            load_list(b0 + 128, moNN, vNN, oNN);      // ... and the list entries of the one after travel meanwhile
             const int bcnt = min(64, seg_hi - b0);
             const uint32_t mykey = AW ? mo.y : mo.x >> 16;
             const uint32_t prevkey = (uint32_t)__shfl_up((int)mykey, 1, 64);
@@ -531,7 +542,7 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
                                 const int j = start + i + q;
                                 const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)mo.x, j);
                                 const int lbase = (int)(m & 0xffff);
-                                oo[q] = __builtin_amdgcn_readlane((int)mo.y, j);
+                                oo[q] = __builtin_amdgcn_readlane(STAGE_ORIG ? (int)oB : (int)mo.y, j);
                                 // all of the visibility's tile cells first (2 x NSTEP LDS reads in flight), then the
                                 // products: the reads' latency is paid once per visibility, not once per step.  The
                                 // lanes without a tap in the tail step read a valid cell and multiply by a zero tap
@@ -744,7 +755,6 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
     Tables t = tables_of(ctx, g);
     const RecWord *recs = (const RecWord *)ctx->recs.ptr;
     if (g.chunk > batch) return fail(ctx, GRIDHIP_EINVAL, "sorted kernel: chunk %d exceeds its work-item capacity %d", g.chunk, batch);
-    if (g.per_vis && degrid) return fail(ctx, GRIDHIP_EUNSUPPORTED, "no degrid form of the aw tile kernel");
     if (g.per_vis && g.imoff > 0) return fail(ctx, GRIDHIP_EUNSUPPORTED, "no big-tile form of the aw tile kernel");
     // persistent work-groups: as many as can be resident (LDS-limited), pulling items from per-group queues
     int per_cu = (int)((size_t)ctx->max_lds / lds_bytes);
@@ -777,7 +787,7 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
     }
     const dim3 gr(nblk), bl(block);
     // two sorted lists (current item, next item) per resident work-group: 8 B (meta, orig) per record, and for the aw
-    // gridders, whose sorter stages the values, 16 B more
+    // gridders, whose sorter stages the values (gridding) or each record's orig (degrid), 16 B more
     const size_t nlist = (size_t)nblk * 2 * batch, nvals = g.per_vis ? nlist : 0;
     GH_CHECK(ws_reserve(ctx, ctx->sorted, nvals * 16 + nlist * 8));
     double2 *svals = (double2 *)ctx->sorted.ptr;  // (not dereferenced when nothing is staged)
@@ -797,12 +807,19 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
         else                             \
             GH_LAUNCH_(S_, D_, false);   \
     } while (0)
-#define GH_LAUNCH_AW(S_)                                                                                         \
+#define GH_LAUNCH_AW_(S_, D_)                                                                                    \
     do {                                                                                                         \
-        GH_CHECK(raise_lds(ctx, tile_grid_sorted_kernel<S_, false, 0, true>));                                   \
-        hipLaunchKernelGGL((tile_grid_sorted_kernel<S_, false, 0, true>), gr, bl, lds_bytes, ctx->stream, g, recs, \
+        GH_CHECK(raise_lds(ctx, tile_grid_sorted_kernel<S_, D_, 0, true>));                                      \
+        hipLaunchKernelGGL((tile_grid_sorted_kernel<S_, D_, 0, true>), gr, bl, lds_bytes, ctx->stream, g, recs,  \
                            t.bin_start, t.work_start, (const double2 *)gcf, (double2 *)vis, grid, nkeys, batch, \
                            t.scalars, svals, smo);                                                               \
+    } while (0)
+#define GH_LAUNCH_AW(S_)                 \
+    do {                                 \
+        if (degrid)                      \
+            GH_LAUNCH_AW_(S_, true);     \
+        else                             \
+            GH_LAUNCH_AW_(S_, false);    \
     } while (0)
 #define GH_CASE(S_)             \
     case S_:                    \
@@ -856,6 +873,7 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
 #undef GH_LAUNCH
 #undef GH_LAUNCH_
 #undef GH_LAUNCH_AW
+#undef GH_LAUNCH_AW_
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }

@@ -126,6 +126,16 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
                              cd(ak.data), p.u.data(), p.v.data(), 1, wbin.data(), a1.data(), a2.data(), cd(v)));
         return a;
     }
+    // the gather twin of convgrid4 (the kernel it scatters, not conjugated again); index = (wbin, a1, a2)
+    std::vector<Visibility> awdegrid(const WKernels &wk, const AKernels &ak, const Matrix<Visibility> &a,
+                                     const BaseLines &p, const std::vector<Int> &wbin, const std::vector<Int> &a1,
+                                     const std::vector<Int> &a2)
+    {
+        std::vector<Visibility> out(p.size());
+        check(gridhip_awdegrid(ctx_, a.h, a.w, cd(a.data), (Int)p.size(), wk.W, wk.Q, wk.gh, ak.A, cd(wk.data),
+                               cd(ak.data), p.u.data(), p.v.data(), 1, wbin.data(), a1.data(), a2.data(), cd(out)));
+        return out;
+    }
     Matrix<Visibility> convgrid3(const WKernels &wk, const AKernels &ak, Matrix<Visibility> a, const BaseLines &p,
                                  const std::vector<Int> &wbin, const std::vector<Int> &a1,
                                  const std::vector<Int> &a2, const std::vector<Visibility> &v)

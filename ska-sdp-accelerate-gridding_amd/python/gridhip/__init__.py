@@ -7,6 +7,8 @@ argument order and meaning:
     convgrid  gcf a p v        (src/Gridding.hs:153-157)
     convgrid2 gcf a p wbin v   (src/Gridding.hs:199-204)
     degrid2   gcf a p wbin     (the gather twin; absent from the reference)
+    convgrid4 wkerns akerns a p index v   (src/Gridding.hs:318-324; convgrid3 gives the same grid)
+    degrid4   wkerns akerns a p index     (the gather twin of convgrid4; absent from the reference)
 
 `a` is the destination grid (complex128, [H, W], ACCUMULATED INTO and returned), `p` the
 baselines already scaled to (-.5, .5) — a (u, v, w) tuple of float64 arrays or an (n, 3)
@@ -238,6 +240,57 @@ class Context:
         return a
 
     convgrid3 = convgrid4
+
+    def _aw_index(self, dev, akerns, index):
+        wbin, a1, a2 = index
+        if dev:
+            import torch
+            cv = lambda t, dt: t if (t.dtype == dt and t.is_contiguous()) else t.to(dt).contiguous()
+            return cv(akerns, torch.complex128), cv(wbin, torch.int64), cv(a1, torch.int64), cv(a2, torch.int64)
+        return (self._np(akerns, np.complex128), self._np(wbin, np.int64), self._np(a1, np.int64),
+                self._np(a2, np.int64))
+
+    def degrid4(self, wkerns, akerns, a, p, index, out=None):
+        """The gather twin of convgrid4 (gridhip_awdegrid): out[k] = sum_ij awkern_k[i,j] * a[y0+i, x0+j] with the
+        kernel convgrid4 scatters, awkern_k = conj(aw_kernel_fn2(yf, xf, wkerns[wbin], akerns[a1], akerns[a2])).
+        index = (wbin, a1, a2); out of range indices predict 0 (counted in last_dropped).  Returns out (overwritten)."""
+        dev, a, pu, pv, stride, _, _, wkerns = self._prep(a, p, None, None, wkerns)
+        akerns, wbin, a1, a2 = self._aw_index(dev, akerns, index)
+        W, Q, _, S, _ = wkerns.shape
+        n = int(pu.shape[0])
+        if dev:
+            import torch
+            if out is None:
+                out = torch.empty(n, dtype=torch.complex128, device=a.device)
+            fn = self._lib.gridhip_awdegrid_dev
+        else:
+            if out is None:
+                out = np.empty(n, dtype=np.complex128)
+            fn = self._lib.gridhip_awdegrid
+        self._check(fn(self._h, a.shape[0], a.shape[1], self._ptr(a), n, W, Q, S, akerns.shape[0], self._ptr(wkerns),
+                       self._ptr(akerns), self._ptr(pu), self._ptr(pv), stride, self._ptr(wbin), self._ptr(a1),
+                       self._ptr(a2), self._ptr(out)))
+        return out
+
+    def aw_plan(self, grid_shape, wkerns, akerns, p, index):
+        """Key, build and bin the baselines `p` (torch cuda tensors) once for an [H, W] grid (gridhip_aw_plan).  The plan
+        keeps the kernels built from wkerns / akerns: the arguments may be freed or changed afterwards.  Returns an
+        AwPlan whose grid() / degrid() run the tile kernel only."""
+        import torch
+        u, v, stride = _split_p(p)
+        if stride == 1:
+            u, v = u.to(torch.float64).contiguous(), v.to(torch.float64).contiguous()
+        wkerns = wkerns if (wkerns.dtype == torch.complex128 and wkerns.is_contiguous()) else wkerns.to(torch.complex128).contiguous()
+        akerns, wbin, a1, a2 = self._aw_index(True, akerns, index)
+        self._use_torch_stream()
+        W, Q, _, S, _ = wkerns.shape
+        n = int(u.shape[0])
+        h = C.c_void_p()
+        self._check(self._lib.gridhip_aw_plan_create_dev(self._h, grid_shape[0], grid_shape[1], n, W, Q, S,
+                                                         akerns.shape[0], self._ptr(wkerns), self._ptr(akerns),
+                                                         self._ptr(u), self._ptr(v), stride, self._ptr(wbin),
+                                                         self._ptr(a1), self._ptr(a2), C.byref(h)))
+        return AwPlan(self, h, n, tuple(grid_shape))
 
     def aw_stats(self, S=15):
         """What the last convgrid4 did: visibilities keyed, distinct kernels built, the hit rate of the per-key
@@ -532,6 +585,46 @@ class Plan:
     def close(self):
         if self._h:
             self.ctx._lib.gridhip_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AwPlan:
+    """aw baselines keyed, their kernels built and binned once (gridhip_aw_plan); grid() / degrid() run the tile kernel
+    only, with the kernel values captured at creation."""
+
+    def __init__(self, ctx, handle, n, grid_shape):
+        self.ctx, self._h, self.n, self.grid_shape = ctx, handle, n, grid_shape
+
+    def _chk(self, a):
+        assert self._h, "plan is closed"
+        assert tuple(a.shape) == self.grid_shape and a.is_cuda and a.is_contiguous()
+        self.ctx._use_torch_stream()
+
+    def grid(self, a, v):
+        """a += convgrid4 contributions of visibilities v (cuda complex128, length n)"""
+        self._chk(a)
+        assert v.shape[0] == self.n and v.is_contiguous()
+        self.ctx._check(self.ctx._lib.gridhip_aw_plan_grid_dev(self._h, Context._ptr(v), Context._ptr(a)))
+        return a
+
+    def degrid(self, a, out=None):
+        """degrid4 of the grid a over the plan's baselines (out is overwritten)"""
+        import torch
+        self._chk(a)
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.complex128, device=a.device)
+        self.ctx._check(self.ctx._lib.gridhip_aw_plan_degrid_dev(self._h, Context._ptr(a), Context._ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            self.ctx._lib.gridhip_aw_plan_destroy(self._h)
             self._h = None
 
     def __del__(self):

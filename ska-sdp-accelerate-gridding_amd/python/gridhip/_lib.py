@@ -66,6 +66,13 @@ SIGNATURES = {
     "gridhip_awgrid": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     "gridhip_awgrid_dev": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     "gridhip_aw_last_stats": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "gridhip_awdegrid": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "gridhip_awdegrid_dev": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "gridhip_aw_plan_create_dev": (ci, [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp,
+                                        C.POINTER(vp)]),
+    "gridhip_aw_plan_grid_dev": (ci, [vp, vp, vp]),
+    "gridhip_aw_plan_degrid_dev": (ci, [vp, vp, vp]),
+    "gridhip_aw_plan_destroy": (ci, [vp]),
     "gridhip_aw_imaging": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
                                 vp, vp]),
     "gridhip_aw_imaging_dev": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp,

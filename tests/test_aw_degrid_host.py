@@ -1,0 +1,69 @@
+"""CPU checks of the aw degridder and aw plans: the library and the ctypes table carry the six new entry points, the
+version says so, the Python binding has its methods, and host/aw_degrid_check.cpp (gridding.hpp's awdegrid) compiles
+and links against include/gridhip.h and libgridhip.so.  The GPU half runs aw_degrid_check."""
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+HOST = os.path.join(ROOT, "ska-sdp-accelerate-gridding_amd", "host")
+LIBDIR = os.path.join(ROOT, "ska-sdp-accelerate-gridding_amd", "lib")
+NEW = ("gridhip_awdegrid", "gridhip_awdegrid_dev", "gridhip_aw_plan_create_dev", "gridhip_aw_plan_grid_dev",
+       "gridhip_aw_plan_degrid_dev", "gridhip_aw_plan_destroy")
+
+
+def build(tmp_path):
+    exe = str(tmp_path / "aw_degrid_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(HOST, "aw_degrid_check.cpp"),
+                           "-L" + LIBDIR, "-lgridhip", "-Wl,-rpath," + LIBDIR])
+    return exe
+
+
+def test_new_symbols_are_exported_and_bound():
+    from gridhip import _lib
+    lib = _lib.load()
+    for name in NEW:
+        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+
+
+def test_version():
+    from gridhip import _lib
+    assert _lib.load().gridhip_version() >= 130
+
+
+def test_python_binding_has_the_aw_gather_and_plans():
+    import gridhip
+    for name in ("degrid4", "aw_plan"):
+        assert callable(getattr(gridhip.Context, name))
+    for name in ("grid", "degrid", "close"):
+        assert callable(getattr(gridhip.AwPlan, name))
+
+
+def test_null_arguments_are_refused_without_a_device():
+    import ctypes as C
+    from gridhip import _lib
+    lib = _lib.load()
+    assert lib.gridhip_aw_plan_grid_dev(None, None, None) == _lib.EINVAL
+    assert lib.gridhip_aw_plan_degrid_dev(None, None, None) == _lib.EINVAL
+    assert lib.gridhip_aw_plan_destroy(None) == _lib.OK
+    pl = C.c_void_p()
+    assert lib.gridhip_aw_plan_create_dev(None, 8, 8, 0, 1, 1, 5, 1, None, None, None, None, 1, None, None, None,
+                                          C.byref(pl)) == _lib.EINVAL
+    assert lib.gridhip_awdegrid_dev(None, 8, 8, None, 0, 1, 1, 5, 1, None, None, None, None, 1, None, None, None,
+                                    None) == _lib.EINVAL
+
+
+def test_cpp_aw_degrid_check_compiles_and_links(tmp_path):
+    assert os.path.exists(build(tmp_path))
+
+
+@pytest.mark.gpu
+def test_cpp_aw_degrid_check_runs(tmp_path):
+    out = subprocess.run([build(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    lines = dict((l.split()[0], l.split()[1:]) for l in out.stdout.strip().splitlines())
+    assert float(lines["adjoint"][0]) < 1e-11
+    assert lines["dropped"] == ["1", "1"]
+    assert lines["error"] == ["-1"]
