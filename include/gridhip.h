@@ -25,7 +25,9 @@
  * reports nothing; this is the one deliberate departure)
  *
  * Two flavours per operation:
- *   gridhip_<op>      host pointers, synchronous — the drop-in form;
+ *   gridhip_<op>      host pointers, synchronous — the drop-in form.  It stages its arrays through device blocks
+ *                     from a pool the context keeps: a repeated call of a shape allocates nothing, and the blocks
+ *                     stay allocated until gridhip_destroy;
  *   gridhip_<op>_dev  device pointers, asynchronous on the context's stream — what the
  *                     benchmark and multi-GPU drivers use so that H2D is outside the timing.
  *                     `grid` and `vis_out` must be ordinary device allocations (hipMalloc: coarse-grained
@@ -265,7 +267,9 @@ int gridhip_aw_last_stats(gridhip_ctx *ctx, int64_t *vis_keyed, int64_t *kernels
  * a visibility whose wbin, a1 or a2 is out of range predicts exactly 0 and is counted (gridhip_last_dropped), as the
  * aw gridder counts it.  Limits and errors are gridhip_awgrid's; a support the LDS tile cannot hold for a gather is
  * GRIDHIP_EUNSUPPORTED, as for degrid2.  "last_path" = 1 (tap-reusing tile kernel, square supports 5..16) or 3
- * (general tile kernel).  The host form is synchronous, the _dev form takes device pointers and is asynchronous. */
+ * (general tile kernel).  The host form is synchronous, the _dev form takes device pointers and is asynchronous.
+ * The host forms of awgrid and awdegrid keep their staging blocks in the context's pool between calls, as every
+ * other host form does (gridhip_destroy frees them). */
 int gridhip_awdegrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid, int64_t n, int64_t W,
                      int64_t Q, int64_t S, int64_t A, const double *wkerns, const double *akerns,
                      const double *u, const double *v, int64_t uv_stride, const int64_t *wbin,

@@ -1,5 +1,5 @@
 // C-ABI entry points of the gridders (include/gridhip.h): argument checks, the device-pointer
-// forms that enqueue the kernels, and the host-pointer drop-in forms that stage through HBM.
+// forms that enqueue the kernels, and the host-pointer drop-in forms that stage through pooled device blocks.
 
 #include "common.h"
 
@@ -18,21 +18,6 @@ int check_common(gridhip_ctx *ctx, int64_t H, int64_t Wd, const void *grid, int6
     if (n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per call");
     return GRIDHIP_OK;
 }
-
-// bump allocator over the staging workspace
-struct Stage {
-    char *base;
-    size_t off = 0;
-    template <typename T>
-    T *take(size_t count)
-    {
-        T *p = reinterpret_cast<T *>(base + off);
-        off += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
-size_t aligned(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the host-pointer forms are synchronous: an internal consistency failure of the call (a record that did not fit
 // the record array, a slice index outside the kernel table - the caller's arrays changed during the call, or a
@@ -169,6 +154,25 @@ int tile_kernels(gridhip_ctx *ctx, const Prep &p, const double *gcf, const doubl
     return GRIDHIP_OK;
 }
 
+int upload_inputs(gridhip_ctx *ctx, GridInputs &d, size_t cells, const double *grid, int64_t n, int64_t uv_stride,
+                  const double *u, const double *v, const double *vis, const int64_t *wbin, const double *gcf,
+                  size_t gcf_elems)
+{
+    if (grid) {
+        GH_CHECK(d.grid.upload(ctx, grid, cells * 16));
+    } else {
+        GH_CHECK(d.grid.alloc(ctx, cells * 16));
+        GH_CHECK_HIP(ctx, hipMemsetAsync(d.grid.p, 0, cells * 16, ctx->stream));
+    }
+    const size_t span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 0;
+    GH_CHECK(d.u.upload(ctx, u, span * 8));
+    GH_CHECK(d.v.upload(ctx, v, span * 8));
+    GH_CHECK(vis ? d.vis.upload(ctx, vis, (size_t)n * 16) : d.vis.alloc(ctx, (size_t)n * 16));
+    if (wbin) GH_CHECK(d.wbin.upload(ctx, wbin, (size_t)n * 8));
+    if (gcf) GH_CHECK(d.gcf.upload(ctx, gcf, gcf_elems * 16));
+    return GRIDHIP_OK;
+}
+
 }  // namespace gridhip
 
 extern "C" {
@@ -299,20 +303,8 @@ int gridhip_degrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *g
 extern "C" {
 
 // ---------------------------------------------------------------------------------------------
-// host-pointer forms
-
-static int stage_uv(gridhip_ctx *ctx, Stage &st, int64_t n, int64_t stride, const double *u, const double *v,
-                    double **du, double **dv)
-{
-    const size_t span = n > 0 ? (size_t)(n - 1) * stride + 1 : 0;
-    *du = st.take<double>(span ? span : 1);
-    *dv = st.take<double>(span ? span : 1);
-    if (span) {
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(*du, u, span * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(*dv, v, span * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return GRIDHIP_OK;
-}
+// host-pointer forms: the inputs go up into blocks of the context's pool (DevBuf), the _dev form runs on them, the
+// result comes back
 
 int gridhip_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, const double *u,
                  const double *v, int64_t uv_stride, const double *vis)
@@ -320,18 +312,13 @@ int gridhip_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t 
     GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
     if (n > 0 && !vis) return fail(ctx, GRIDHIP_EINVAL, "null vis");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd, span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 1;
-    GH_CHECK(ws_reserve(ctx, ctx->stage, aligned(cells * 16) + 2 * aligned(span * 8) + aligned((size_t)n * 16 + 16)));
-    Stage st{(char *)ctx->stage.ptr};
-    double *dg = st.take<double>(cells * 2), *du, *dv;
-    GH_CHECK(stage_uv(ctx, st, n, uv_stride, u, v, &du, &dv));
-    double *dvis = st.take<double>((size_t)n * 2 + 2);
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dg, grid, cells * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n) GH_CHECK_HIP(ctx, hipMemcpyAsync(dvis, vis, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK(gridhip_grid_dev(ctx, H, Wd, dg, n, du, dv, uv_stride, dvis));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(grid, dg, cells * 16, hipMemcpyDeviceToHost, ctx->stream));
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
+    const size_t cells = (size_t)H * Wd;
+    GridInputs d;
+    GH_CHECK(upload_inputs(ctx, d, cells, grid, n, uv_stride, u, v, vis, nullptr, nullptr, 0));
+    GH_CHECK(gridhip_grid_dev(ctx, H, Wd, d.grid.as<double>(), n, d.u.as<double>(), d.v.as<double>(), uv_stride,
+                              d.vis.as<double>()));
+    GH_CHECK(d2h(ctx, grid, d.grid.p, cells * 16));
+    return sync(ctx);
 }
 
 int gridhip_convgrid2(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t W, int64_t Q,
@@ -342,25 +329,14 @@ int gridhip_convgrid2(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int
     if (!gcf || (n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
     if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd, span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 1;
-    const size_t kel = (size_t)W * Q * Q * gh * gw;
-    GH_CHECK(ws_reserve(ctx, ctx->stage, aligned(cells * 16) + 2 * aligned(span * 8) + aligned((size_t)n * 16 + 16) +
-                                             aligned((size_t)n * 8 + 8) + aligned(kel * 16)));
-    Stage st{(char *)ctx->stage.ptr};
-    double *dg = st.take<double>(cells * 2), *du, *dv;
-    GH_CHECK(stage_uv(ctx, st, n, uv_stride, u, v, &du, &dv));
-    double *dvis = st.take<double>((size_t)n * 2 + 2);
-    int64_t *dwb = st.take<int64_t>((size_t)n + 1);
-    double *dk = st.take<double>(kel * 2);
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dg, grid, cells * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dk, gcf, kel * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n) GH_CHECK_HIP(ctx, hipMemcpyAsync(dvis, vis, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n && wbin) GH_CHECK_HIP(ctx, hipMemcpyAsync(dwb, wbin, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK(gridhip_convgrid2_dev(ctx, H, Wd, dg, n, W, Q, gh, gw, dk, du, dv, uv_stride, wbin ? dwb : nullptr, dvis));
+    const size_t cells = (size_t)H * Wd;
+    GridInputs d;
+    GH_CHECK(upload_inputs(ctx, d, cells, grid, n, uv_stride, u, v, vis, wbin, gcf, (size_t)W * Q * Q * gh * gw));
+    GH_CHECK(gridhip_convgrid2_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, gh, gw, d.gcf.as<double>(), d.u.as<double>(),
+                                   d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), d.vis.as<double>()));
     if (ctx->opt.variant != 1) GH_CHECK(check_errors(ctx));  // (before the grid is handed back)
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(grid, dg, cells * 16, hipMemcpyDeviceToHost, ctx->stream));
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
+    GH_CHECK(d2h(ctx, grid, d.grid.p, cells * 16));
+    return sync(ctx);
 }
 
 int gridhip_convgrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t Q, int64_t gh,
@@ -378,24 +354,13 @@ int gridhip_degrid2(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid,
     if (!gcf || (n > 0 && !vis_out)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
     if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd, span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 1;
-    const size_t kel = (size_t)W * Q * Q * gh * gw;
-    GH_CHECK(ws_reserve(ctx, ctx->stage, aligned(cells * 16) + 2 * aligned(span * 8) + aligned((size_t)n * 16 + 16) +
-                                             aligned((size_t)n * 8 + 8) + aligned(kel * 16)));
-    Stage st{(char *)ctx->stage.ptr};
-    double *dg = st.take<double>(cells * 2), *du, *dv;
-    GH_CHECK(stage_uv(ctx, st, n, uv_stride, u, v, &du, &dv));
-    double *dvis = st.take<double>((size_t)n * 2 + 2);
-    int64_t *dwb = st.take<int64_t>((size_t)n + 1);
-    double *dk = st.take<double>(kel * 2);
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dg, grid, cells * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dk, gcf, kel * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n && wbin) GH_CHECK_HIP(ctx, hipMemcpyAsync(dwb, wbin, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK(gridhip_degrid2_dev(ctx, H, Wd, dg, n, W, Q, gh, gw, dk, du, dv, uv_stride, wbin ? dwb : nullptr, dvis));
+    GridInputs d;
+    GH_CHECK(upload_inputs(ctx, d, (size_t)H * Wd, grid, n, uv_stride, u, v, nullptr, wbin, gcf, (size_t)W * Q * Q * gh * gw));
+    GH_CHECK(gridhip_degrid2_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, gh, gw, d.gcf.as<double>(), d.u.as<double>(),
+                                 d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), d.vis.as<double>()));
     GH_CHECK(check_errors(ctx));
-    if (n) GH_CHECK_HIP(ctx, hipMemcpyAsync(vis_out, dvis, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
+    GH_CHECK(d2h(ctx, vis_out, d.vis.p, (size_t)n * 16));
+    return sync(ctx);
 }
 
 }  // extern "C"

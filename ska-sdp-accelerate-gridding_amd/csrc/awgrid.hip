@@ -640,6 +640,32 @@ static int aw_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t m, co
     return launch_tile_grid(ctx, g, p.block, p.lds, m, (const double *)table, vis, grid);
 }
 
+// The argument check of the aw entry points: sizes, and the arrays given (has_grid / has_vis: the entry point's grid
+// and vis, where it takes them).  A refused call touches nothing.
+static int aw_args_ok(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A,
+                      int64_t uv_stride, const double *wkerns, const double *akerns, const double *u, const double *v,
+                      const int64_t *wbin, const int64_t *a1, const int64_t *a2, bool has_grid, bool has_vis)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !has_grid || !wkerns ||
+        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !has_vis)))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    return GRIDHIP_OK;
+}
+
+// Start of an aw batch loop or plan: the shapes it takes, then the counters it reports zeroed - [0] dropped, [2] errors,
+// [28] distinct kernels built, [29] visibilities keyed, [30] dropped so far (batches), [31] errors so far
+static int aw_begin(gridhip_ctx *ctx, int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A)
+{
+    ctx->aw_tables_built = 0;
+    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
+        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 28, 0, 4 * sizeof(int32_t), ctx->stream));
+    return GRIDHIP_OK;
+}
+
 // The aw batch loop over one or two (vis, grid) pairs, or (vis_out != null) the gather of one grid into vis_out.  Per
 // batch the antenna pairs, keys, the kernel table and the binned records are made once; the tile kernel then runs once
 // per pair on the same records and table (it reads ctx->recs and the table, and writes neither).  do_imaging grids its
@@ -650,14 +676,7 @@ static int aw_batches(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double
                       const double *wkerns, const double *akerns, const double *u, const double *v, int64_t uv_stride,
                       const int64_t *wbin, const int64_t *a1, const int64_t *a2)
 {
-    ctx->aw_tables_built = 0;
-    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
-        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    // [0] dropped, [2] errors, [28] distinct kernels built, [29] visibilities keyed, [30] dropped so far (batches),
-    // [31] errors so far
-    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 28, 0, 4 * sizeof(int32_t), ctx->stream));
+    GH_CHECK(aw_begin(ctx, n, W, Q, S, A));
     if (n == 0) return GRIDHIP_OK;
     const bool degrid = vis_out != nullptr;
     AwCall c;
@@ -779,10 +798,7 @@ int gridhip_awgrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, in
                        const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
                        const int64_t *a2, const double *vis)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
-        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, grid, vis));
     return awgrid_pairs(ctx, H, Wd, 1, &grid, &vis, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2);
 }
 
@@ -799,52 +815,24 @@ int gridhip_aw_last_stats(gridhip_ctx *ctx, int64_t *vis_keyed, int64_t *kernels
     return GRIDHIP_OK;
 }
 
-// Host pointers: convgrid3 / convgrid4 of src/Gridding.hs:246-396 (same result).
+// Host pointers: convgrid3 / convgrid4 of src/Gridding.hs:246-396 (same result).  Synchronous.
 int gridhip_awgrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t W, int64_t Q, int64_t S,
                    int64_t A, const double *wkerns, const double *akerns, const double *u, const double *v,
                    int64_t uv_stride, const int64_t *wbin, const int64_t *a1, const int64_t *a2, const double *vis)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
-        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, grid, vis));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd, span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 1;
-    const size_t wel = (size_t)W * Q * Q * S * S, ael = (size_t)A * S * S;
-    struct Buf {
-        void *p = nullptr;
-        ~Buf()
-        {
-            if (p) (void)hipFree(p);
-        }
-    } dg, du, dv, dwb, da1, da2, dvis, dwk, dak;
-    GH_CHECK_HIP(ctx, hipMalloc(&dg.p, cells * 16));
-    GH_CHECK_HIP(ctx, hipMalloc(&du.p, span * 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&dv.p, span * 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&dwb.p, (size_t)n * 8 + 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&da1.p, (size_t)n * 8 + 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&da2.p, (size_t)n * 8 + 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&dvis.p, (size_t)n * 16 + 16));
-    GH_CHECK_HIP(ctx, hipMalloc(&dwk.p, wel * 16));
-    GH_CHECK_HIP(ctx, hipMalloc(&dak.p, ael * 16));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dg.p, grid, cells * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dwk.p, wkerns, wel * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dak.p, akerns, ael * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n > 0) {
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(du.p, u, span * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(dv.p, v, span * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(dwb.p, wbin, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(da1.p, a1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(da2.p, a2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(dvis.p, vis, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    }
-    GH_CHECK(gridhip_awgrid_dev(ctx, H, Wd, (double *)dg.p, n, W, Q, S, A, (const double *)dwk.p,
-                                (const double *)dak.p, (const double *)du.p, (const double *)dv.p, uv_stride,
-                                (const int64_t *)dwb.p, (const int64_t *)da1.p, (const int64_t *)da2.p,
-                                (const double *)dvis.p));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(grid, dg.p, cells * 16, hipMemcpyDeviceToHost, ctx->stream));
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
+    GridInputs d;  // (the w-kernels as its gcf)
+    DevBuf ak, da1, da2;
+    GH_CHECK(upload_inputs(ctx, d, (size_t)H * Wd, grid, n, uv_stride, u, v, vis, wbin, wkerns, (size_t)W * Q * Q * S * S));
+    GH_CHECK(ak.upload(ctx, akerns, (size_t)A * S * S * 16));
+    GH_CHECK(da1.upload(ctx, a1, (size_t)n * 8));
+    GH_CHECK(da2.upload(ctx, a2, (size_t)n * 8));
+    GH_CHECK(gridhip_awgrid_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, S, A, d.gcf.as<double>(), ak.as<double>(),
+                                d.u.as<double>(), d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), da1.as<int64_t>(),
+                                da2.as<int64_t>(), d.vis.as<double>()));
+    GH_CHECK(d2h(ctx, grid, d.grid.p, (size_t)H * Wd * 16));
+    return sync(ctx);
 }
 
 // The gather with convgrid4's coordinates and kernels (include/gridhip.h); device pointers, asynchronous.
@@ -853,59 +841,29 @@ int gridhip_awdegrid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *
                          const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
                          const int64_t *a2, double *vis_out)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
-        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis_out)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, grid, vis_out));
     return aw_batches(ctx, H, Wd, 0, nullptr, nullptr, grid, n > 0 ? vis_out : nullptr, n, W, Q, S, A, wkerns, akerns, u,
                       v, uv_stride, wbin, a1, a2);
 }
 
-// Host pointers: stages everything through device blocks of the call's own, synchronous.
+// Host pointers; synchronous.
 int gridhip_awdegrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid, int64_t n, int64_t W, int64_t Q,
                      int64_t S, int64_t A, const double *wkerns, const double *akerns, const double *u, const double *v,
                      int64_t uv_stride, const int64_t *wbin, const int64_t *a1, const int64_t *a2, double *vis_out)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !grid || !wkerns ||
-        !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !vis_out)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, grid, vis_out));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd, span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 1;
-    const size_t wel = (size_t)W * Q * Q * S * S, ael = (size_t)A * S * S;
-    struct Buf {
-        void *p = nullptr;
-        ~Buf()
-        {
-            if (p) (void)hipFree(p);
-        }
-    } dg, du, dv, dwb, da1, da2, dvis, dwk, dak;
-    GH_CHECK_HIP(ctx, hipMalloc(&dg.p, cells * 16));
-    GH_CHECK_HIP(ctx, hipMalloc(&du.p, span * 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&dv.p, span * 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&dwb.p, (size_t)n * 8 + 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&da1.p, (size_t)n * 8 + 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&da2.p, (size_t)n * 8 + 8));
-    GH_CHECK_HIP(ctx, hipMalloc(&dvis.p, (size_t)n * 16 + 16));
-    GH_CHECK_HIP(ctx, hipMalloc(&dwk.p, wel * 16));
-    GH_CHECK_HIP(ctx, hipMalloc(&dak.p, ael * 16));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dg.p, grid, cells * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dwk.p, wkerns, wel * 16, hipMemcpyHostToDevice, ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemcpyAsync(dak.p, akerns, ael * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n > 0) {
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(du.p, u, span * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(dv.p, v, span * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(dwb.p, wbin, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(da1.p, a1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        GH_CHECK_HIP(ctx, hipMemcpyAsync(da2.p, a2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    GH_CHECK(gridhip_awdegrid_dev(ctx, H, Wd, (const double *)dg.p, n, W, Q, S, A, (const double *)dwk.p,
-                                  (const double *)dak.p, (const double *)du.p, (const double *)dv.p, uv_stride,
-                                  (const int64_t *)dwb.p, (const int64_t *)da1.p, (const int64_t *)da2.p,
-                                  (double *)dvis.p));
-    if (n > 0) GH_CHECK_HIP(ctx, hipMemcpyAsync(vis_out, dvis.p, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
+    GridInputs d;  // (the w-kernels as its gcf; vis: the predictions)
+    DevBuf ak, da1, da2;
+    GH_CHECK(upload_inputs(ctx, d, (size_t)H * Wd, grid, n, uv_stride, u, v, nullptr, wbin, wkerns, (size_t)W * Q * Q * S * S));
+    GH_CHECK(ak.upload(ctx, akerns, (size_t)A * S * S * 16));
+    GH_CHECK(da1.upload(ctx, a1, (size_t)n * 8));
+    GH_CHECK(da2.upload(ctx, a2, (size_t)n * 8));
+    GH_CHECK(gridhip_awdegrid_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, S, A, d.gcf.as<double>(), ak.as<double>(),
+                                  d.u.as<double>(), d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), da1.as<int64_t>(),
+                                  da2.as<int64_t>(), d.vis.as<double>()));
+    GH_CHECK(d2h(ctx, vis_out, d.vis.p, (size_t)n * 16));
+    return sync(ctx);
 }
 
 int gridhip_aw_plan_destroy(gridhip_aw_plan *pl)
@@ -931,15 +889,8 @@ int gridhip_aw_plan_create_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t 
 {
     if (!ctx || !out) return GRIDHIP_EINVAL;
     *out = nullptr;
-    if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !wkerns || !akerns ||
-        (n > 0 && (!u || !v || !wbin || !a1 || !a2)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
-    ctx->aw_tables_built = 0;
-    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
-        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 28, 0, 4 * sizeof(int32_t), ctx->stream));
+    GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, true, true));
+    GH_CHECK(aw_begin(ctx, n, W, Q, S, A));
     gridhip_aw_plan *pl = new (std::nothrow) gridhip_aw_plan();
     if (!pl) return GRIDHIP_ENOMEM;
     pl->ctx = ctx;

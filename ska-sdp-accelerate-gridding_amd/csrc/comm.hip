@@ -374,6 +374,7 @@ int gridhip_comm_convgrid2(gridhip_comm *c, int64_t H, int64_t Wd, double *grid,
     const size_t cells = (size_t)H * Wd, kel = (size_t)W * Q * Q * gh * gw;
     std::vector<double *> dgrid(nd, nullptr);
     std::vector<int> rcs(nd, GRIDHIP_OK);
+    std::vector<GridInputs> in(nd);  // (each device's blocks outlive the all-reduce and the final copy)
     auto work = [&](int i) {
         gridhip_ctx *x = c->ctx[i];
         // contiguous, balanced shard of the stream (the rank form grids everything it was given)
@@ -381,38 +382,13 @@ int gridhip_comm_convgrid2(gridhip_comm *c, int64_t H, int64_t Wd, double *grid,
         const int64_t lo = i * base + (i < rem ? i : rem), cnt = base + (i < rem ? 1 : 0);
         auto run = [&]() -> int {
             GH_CHECK_HIP(x, hipSetDevice(x->device));
-            const size_t span = cnt > 0 ? (size_t)(cnt - 1) * uv_stride + 1 : 1;
-            auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-            GH_CHECK(ws_reserve(x, x->stage, al(cells * 16) + 2 * al(span * 8) + al((size_t)cnt * 16 + 16) +
-                                                 al((size_t)cnt * 8 + 8) + al(kel * 16)));
-            char *p = (char *)x->stage.ptr;
-            double *dg = (double *)p;
-            p += al(cells * 16);
-            double *du = (double *)p;
-            p += al(span * 8);
-            double *dv = (double *)p;
-            p += al(span * 8);
-            double *dvis = (double *)p;
-            p += al((size_t)cnt * 16 + 16);
-            int64_t *dwb = (int64_t *)p;
-            p += al((size_t)cnt * 8 + 8);
-            double *dk = (double *)p;
-            dgrid[i] = dg;
-            if (i == 0)
-                GH_CHECK_HIP(x, hipMemcpyAsync(dg, grid, cells * 16, hipMemcpyHostToDevice, x->stream));
-            else
-                GH_CHECK_HIP(x, hipMemsetAsync(dg, 0, cells * 16, x->stream));
-            GH_CHECK_HIP(x, hipMemcpyAsync(dk, gcf, kel * 16, hipMemcpyHostToDevice, x->stream));
-            if (cnt > 0) {
-                GH_CHECK_HIP(x, hipMemcpyAsync(du, u + lo * uv_stride, span * 8, hipMemcpyHostToDevice, x->stream));
-                GH_CHECK_HIP(x, hipMemcpyAsync(dv, v + lo * uv_stride, span * 8, hipMemcpyHostToDevice, x->stream));
-                GH_CHECK_HIP(x, hipMemcpyAsync(dvis, vis + 2 * lo, (size_t)cnt * 16, hipMemcpyHostToDevice, x->stream));
-                if (wbin)
-                    GH_CHECK_HIP(x, hipMemcpyAsync(dwb, wbin + lo, (size_t)cnt * 8, hipMemcpyHostToDevice, x->stream));
-            }
-            GH_CHECK(gridhip_convgrid2_dev(x, H, Wd, dg, cnt, W, Q, gh, gw, dk, du, dv, uv_stride, wbin ? dwb : nullptr,
-                                           dvis));
-            return GRIDHIP_OK;
+            GridInputs &d = in[i];
+            const int rc = upload_inputs(x, d, cells, i == 0 ? grid : nullptr, cnt, uv_stride, u + lo * uv_stride,
+                                         v + lo * uv_stride, vis + 2 * lo, wbin ? wbin + lo : nullptr, gcf, kel);
+            dgrid[i] = d.grid.as<double>();  // (set once the grid block exists, whatever failed after it)
+            GH_CHECK(rc);
+            return gridhip_convgrid2_dev(x, H, Wd, dgrid[i], cnt, W, Q, gh, gw, d.gcf.as<double>(), d.u.as<double>(),
+                                         d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), d.vis.as<double>());
         };
         rcs[i] = run();
     };

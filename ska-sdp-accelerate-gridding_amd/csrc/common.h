@@ -133,7 +133,6 @@ struct gridhip_ctx {
     // device scratch, grown on demand (never inside a timed/captured region after warm-up)
     gridhip::Workspace recs;    // RecWord[n]
     gridhip::Workspace tables;  // bin_count / bin_start / work_start / cursors / scalars
-    gridhip::Workspace stage;   // staging for the host-pointer entry points
     gridhip::Workspace sorted;  // sorted-list scratch of the tap-reusing tile kernel (tile_sorted.hip)
     gridhip::Workspace recs_raw;   // 8-byte pre-records the counting sweep leaves for the scatter (bin.hip)
     gridhip::Workspace recs_tmp;   // coarse-binned records between the two scatter levels of the pre-pass (bin.hip)
@@ -158,10 +157,10 @@ struct gridhip_ctx {
     void *fft_plan[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t fft_n[4] = {0, 0, 0, 0};
     int fft_next = 0;  // the slot the next new size replaces
-    // device blocks of the imaging entry points (imaging.hip: DevBuf), kept between calls: a resident imaging call
-    // (gridhip_do_imaging_dev) then neither allocates nor frees - hipFree synchronises the whole device.  All of a
-    // context's work is ordered on one stream (gridhip_set_stream orders a new one after the old), so a block handed
-    // back by one call may be handed out to the next without waiting.
+    // device blocks of the host-pointer forms and the imaging entry points (DevBuf), kept between calls: a repeated
+    // call then neither allocates nor frees - hipFree synchronises the whole device.  All of a context's work is
+    // ordered on one stream (gridhip_set_stream orders a new one after the old), so a block handed back by one call
+    // may be handed out to the next without waiting.
     std::vector<std::pair<void *, size_t>> pool_free;
     // the last w-kernel table w_cache_imaging built (imaging.hip): the table depends on the field of view, the w-planes
     // and the kernel's shape only, and an imaging run calls with the same ones again and again (image and PSF, every
@@ -206,6 +205,59 @@ int fail(gridhip_ctx *ctx, int code, const char *fmt, ...);
     } while (0)
 
 int ws_reserve(gridhip_ctx *ctx, Workspace &ws, size_t bytes);
+
+// Device block of one call, drawn from and returned to the context's pool (gridhip_ctx::pool_free): the smallest pooled
+// block of at least the size asked for and at most twice it, else a new one.  Nothing is freed before gridhip_destroy,
+// so the second call of a given shape allocates nothing.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    gridhip_ctx *owner = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;  // (one owner hands the block back)
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf()
+    {
+        if (p && owner) owner->pool_free.emplace_back(p, cap);
+    }
+    int alloc(gridhip_ctx *ctx, size_t bytes);
+    int upload(gridhip_ctx *ctx, const void *host, size_t bytes);  // alloc, then an async copy of `bytes` from the host
+    template <typename T>
+    T *as()
+    {
+        return reinterpret_cast<T *>(p);
+    }
+};
+
+// copies on ctx->stream (none for 0 bytes); copy_in / copy_out take host arrays (the drop-in forms) or device-resident
+// ones (dev: the _dev forms)
+static inline int copy_in(gridhip_ctx *ctx, void *d, const void *src, size_t bytes, bool dev)
+{
+    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(d, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    return GRIDHIP_OK;
+}
+static inline int copy_out(gridhip_ctx *ctx, void *dst, const void *d, size_t bytes, bool dev)
+{
+    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(dst, d, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    return GRIDHIP_OK;
+}
+static inline int h2d(gridhip_ctx *ctx, void *d, const void *h, size_t bytes) { return copy_in(ctx, d, h, bytes, false); }
+static inline int d2h(gridhip_ctx *ctx, void *h, const void *d, size_t bytes) { return copy_out(ctx, h, d, bytes, false); }
+static inline int sync(gridhip_ctx *ctx)
+{
+    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GRIDHIP_OK;
+}
+
+// The device copies of a host-pointer gridding call's inputs (api.hip): the grid (uploaded, or zeroed when `grid` is
+// null), the u / v spans, vis (uploaded, or left for the call to write when `vis` is null), wbin and gcf when given
+// (else their blocks stay null).
+struct GridInputs {
+    DevBuf grid, u, v, vis, wbin, gcf;
+};
+int upload_inputs(gridhip_ctx *ctx, GridInputs &d, size_t cells, const double *grid, int64_t n, int64_t uv_stride,
+                  const double *u, const double *v, const double *vis, const int64_t *wbin, const double *gcf,
+                  size_t gcf_elems);
 
 // HIP events of a timed call: i = 0: it starts, 1: its pre-pass is enqueued, 2: its dominant kernel is enqueued (the
 // call is then readable with gridhip_timing)

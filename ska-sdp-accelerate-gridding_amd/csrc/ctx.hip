@@ -33,6 +33,44 @@ int ws_reserve(gridhip_ctx *ctx, Workspace &ws, size_t bytes)
     return GRIDHIP_OK;
 }
 
+int DevBuf::alloc(gridhip_ctx *ctx, size_t bytes)
+{
+    if (bytes < 256) bytes = 256;
+    owner = ctx;
+    int best = -1;
+    for (int i = 0; i < (int)ctx->pool_free.size(); ++i) {
+        const size_t c = ctx->pool_free[i].second;
+        if (c >= bytes && c <= 2 * bytes && (best < 0 || c < ctx->pool_free[best].second)) best = i;
+    }
+    if (best >= 0) {
+        p = ctx->pool_free[best].first;
+        cap = ctx->pool_free[best].second;
+        ctx->pool_free.erase(ctx->pool_free.begin() + best);
+        return GRIDHIP_OK;
+    }
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipErrorOutOfMemory && !ctx->pool_free.empty()) {  // give the pooled blocks back and try once more
+        (void)hipGetLastError();
+        (void)hipDeviceSynchronize();
+        for (auto &b : ctx->pool_free) (void)hipFree(b.first);
+        ctx->pool_free.clear();
+        e = hipMalloc(&p, bytes);
+    }
+    if (e != hipSuccess) {
+        p = nullptr;
+        return fail(ctx, e == hipErrorOutOfMemory ? GRIDHIP_ENOMEM : GRIDHIP_EHIP, "hipMalloc(%zu) failed: %s", bytes,
+                    hipGetErrorString(e));
+    }
+    cap = bytes;
+    return GRIDHIP_OK;
+}
+
+int DevBuf::upload(gridhip_ctx *ctx, const void *host, size_t bytes)
+{
+    GH_CHECK(alloc(ctx, bytes));
+    return h2d(ctx, p, host, bytes);
+}
+
 static int ilog2(int x)
 {
     int l = 0;
@@ -348,7 +386,7 @@ int gridhip_destroy(gridhip_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     fft_release(ctx);
-    Workspace *all[] = {&ctx->recs, &ctx->tables, &ctx->stage, &ctx->blockhist, &ctx->sorted, &ctx->recs_tmp, &ctx->recs_raw, &ctx->ktab, &ctx->aw};
+    Workspace *all[] = {&ctx->recs, &ctx->tables, &ctx->blockhist, &ctx->sorted, &ctx->recs_tmp, &ctx->recs_raw, &ctx->ktab, &ctx->aw};
     for (Workspace *w : all)
         if (w->ptr) (void)hipFree(w->ptr);
     for (auto &b : ctx->pool_free) (void)hipFree(b.first);

@@ -481,83 +481,6 @@ int dev_w_kernel(gridhip_ctx *ctx, double theta, double w, int64_t npixFF, int64
     return GRIDHIP_OK;
 }
 
-// Device buffer of one imaging call, drawn from and returned to the context's pool (gridhip_ctx::pool_free): the
-// smallest pooled block of at least the size asked for and at most twice it, else a new one.  Nothing is freed
-// before gridhip_destroy, so the second call of a given shape allocates nothing.
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    gridhip_ctx *owner = nullptr;
-    ~DevBuf()
-    {
-        if (p && owner) owner->pool_free.emplace_back(p, cap);
-    }
-    int alloc(gridhip_ctx *ctx, size_t bytes)
-    {
-        if (bytes < 256) bytes = 256;
-        owner = ctx;
-        int best = -1;
-        for (int i = 0; i < (int)ctx->pool_free.size(); ++i) {
-            const size_t c = ctx->pool_free[i].second;
-            if (c >= bytes && c <= 2 * bytes && (best < 0 || c < ctx->pool_free[best].second)) best = i;
-        }
-        if (best >= 0) {
-            p = ctx->pool_free[best].first;
-            cap = ctx->pool_free[best].second;
-            ctx->pool_free.erase(ctx->pool_free.begin() + best);
-            return GRIDHIP_OK;
-        }
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipErrorOutOfMemory && !ctx->pool_free.empty()) {  // give the pooled blocks back and try once more
-            (void)hipGetLastError();
-            (void)hipDeviceSynchronize();
-            for (auto &b : ctx->pool_free) (void)hipFree(b.first);
-            ctx->pool_free.clear();
-            e = hipMalloc(&p, bytes);
-        }
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(ctx, e == hipErrorOutOfMemory ? GRIDHIP_ENOMEM : GRIDHIP_EHIP, "hipMalloc(%zu) failed: %s", bytes,
-                        hipGetErrorString(e));
-        }
-        cap = bytes;
-        return GRIDHIP_OK;
-    }
-    template <typename T>
-    T *as()
-    {
-        return reinterpret_cast<T *>(p);
-    }
-};
-
-// inputs / outputs of an imaging call: host arrays (the drop-in forms) or device-resident ones (the _dev forms)
-static int copy_in(gridhip_ctx *ctx, void *d, const void *src, size_t bytes, bool dev)
-{
-    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(d, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    return GRIDHIP_OK;
-}
-static int copy_out(gridhip_ctx *ctx, void *dst, const void *d, size_t bytes, bool dev)
-{
-    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(dst, d, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    return GRIDHIP_OK;
-}
-
-static int h2d(gridhip_ctx *ctx, void *d, const void *h, size_t bytes)
-{
-    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return GRIDHIP_OK;
-}
-static int d2h(gridhip_ctx *ctx, void *h, const void *d, size_t bytes)
-{
-    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return GRIDHIP_OK;
-}
-static int sync(gridhip_ctx *ctx)
-{
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
-}
-
 // Prelude `round` on the host (N = round (theta * lam), src/Gridding.hs:87,118,416): half to even
 static int64_t haskell_round(double x) { return (int64_t)nearbyint(x); }
 
@@ -567,9 +490,8 @@ static int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t strid
                      int64_t *wmin, int64_t *nplanes)
 {
     DevBuf mm;
-    GH_CHECK(mm.alloc(ctx, 16));
     const long long init[2] = {0x7fffffffffffffffLL, -0x7fffffffffffffffLL - 1};
-    GH_CHECK(h2d(ctx, mm.p, init, 16));
+    GH_CHECK(mm.upload(ctx, init, 16));
     if (n > 0) {
         hipLaunchKernelGGL(wround_kernel, dim3(grid_for(ctx, n).x > (unsigned)ctx->num_cu * 4 ? (unsigned)ctx->num_cu * 4 : grid_for(ctx, n).x), dim3(256), 0, ctx->stream, n, w, stride, wstep, wbin,
                            mm.as<long long>());
@@ -582,6 +504,47 @@ static int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t strid
     GH_CHECK_HIP(ctx, hipGetLastError());
     *wmin = n > 0 ? res[0] : 0;
     *nplanes = n > 0 ? (res[1] - res[0]) / wstep + 1 : 0;
+    return GRIDHIP_OK;
+}
+
+// out = real(ifft(make_grid_hermitian(g))) (N x N doubles), its maximum into *maxbits (ordered bits) when given: the
+// imaging tail (src/Gridding.hs:539,542).  The centred inverse transform (shift2D . ifft2D . ishift2D, dev_fft2c) has its
+// two rolls folded into the Hermitian fill's stores and the real part's loads: four passes over the N^2 grid fewer per
+// call.  h: N x N complex scratch.
+static int image_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits)
+{
+    static const unsigned long long neg_inf_bits = ~0xfff0000000000000ULL;  // ordered image of -inf
+    const size_t cells = (size_t)N * N;
+    void *plan = nullptr;
+    GH_CHECK(fft_plan_for(ctx, N, &plan));
+    hipLaunchKernelGGL(hermitian_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, g, h, N / 2);
+    if (int rc = g_fft.exec(plan, h, h, 1 /* HIPFFT_BACKWARD */)) return fail(ctx, GRIDHIP_EHIP, "hipfftExecZ2Z: %d", rc);
+    if (maxbits) GH_CHECK(h2d(ctx, maxbits, &neg_inf_bits, 8));
+    hipLaunchKernelGGL(real_max_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells, h, out,
+                       maxbits, N, (N + 1) / 2, 1.0 / ((double)N * (double)N));
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+static double max_of_bits(unsigned long long mb)
+{
+    mb = (mb & 0x8000000000000000ULL) ? (mb & 0x7fffffffffffffffULL) : ~mb;
+    double m;
+    memcpy(&m, &mb, 8);
+    return m;
+}
+
+// normalise image and PSF by the PSF's maximum (src/Gridding.hs:544-548): maxbits holds it (image_tail), *pmax gets it
+static int normalise(gridhip_ctx *ctx, size_t cells, double *image, double *psf, const unsigned long long *maxbits,
+                     double *pmax)
+{
+    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells, image, maxbits);
+    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells, psf, maxbits);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    unsigned long long mb = 0;
+    GH_CHECK(d2h(ctx, &mb, maxbits, 8));
+    GH_CHECK(sync(ctx));
+    if (pmax) *pmax = max_of_bits(mb);
     return GRIDHIP_OK;
 }
 
@@ -614,12 +577,9 @@ static int do_imaging_impl(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
         DevBuf s0, s1, s2;
         const double *su = u, *sv = v, *sw = w;
         if (!dev) {
-            GH_CHECK(s0.alloc(ctx, span * 8));
-            GH_CHECK(s1.alloc(ctx, span * 8));
-            GH_CHECK(s2.alloc(ctx, span * 8));
-            GH_CHECK(h2d(ctx, s0.p, u, span * 8));
-            GH_CHECK(h2d(ctx, s1.p, v, span * 8));
-            GH_CHECK(h2d(ctx, s2.p, w, span * 8));
+            GH_CHECK(s0.upload(ctx, u, span * 8));
+            GH_CHECK(s1.upload(ctx, v, span * 8));
+            GH_CHECK(s2.upload(ctx, w, span * 8));
             su = s0.as<double>(), sv = s1.as<double>(), sw = s2.as<double>();
         }
         if (n > 0) {
@@ -649,42 +609,18 @@ static int do_imaging_impl(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
         hipLaunchKernelGGL(cmul_real_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, dwt.as<double2>(),
                            dvis.as<double2>(), dvis.as<double2>());
     }
-    const unsigned long long neg_inf_bits = ~0xfff0000000000000ULL;  // ordered image of -inf
     for (int pass = 0; pass < 2; ++pass) {
-        // pass 0: image from wt*vis (:538-539); pass 1: PSF from wt (:541-542)
+        // pass 0: image from wt*vis (:538-539) into dreal; pass 1: PSF from wt (:541-542) into dtmp, and its maximum
         GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, cells * 16, ctx->stream));
         GH_CHECK(imgfn(N, du.as<double>(), dv.as<double>(), dw.as<double>(),
                        pass == 0 ? dvis.as<double>() : dwt.as<double>(), dg.as<double>()));
-        // centred inverse transform (shift2D . ifft2D . ishift2D, dev_fft2c) with its two rolls folded into the Hermitian
-        // fill's stores and the real part's loads: four passes over the N^2 grid fewer per call
-        void *plan = nullptr;
-        GH_CHECK(fft_plan_for(ctx, N, &plan));
-        hipLaunchKernelGGL(hermitian_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, dg.as<double2>(),
-                           dh.as<double2>(), N / 2);
-        if (int rc = g_fft.exec(plan, dh.p, dh.p, 1 /* HIPFFT_BACKWARD */)) return fail(ctx, GRIDHIP_EHIP, "hipfftExecZ2Z: %d", rc);
-        if (pass == 1) GH_CHECK(h2d(ctx, dmax.p, &neg_inf_bits, 8));
-        hipLaunchKernelGGL(real_max_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells,
-                           dh.as<double2>(), pass == 0 ? dreal.as<double>() : dtmp.as<double>(),
-                           pass == 1 ? dmax.as<unsigned long long>() : (unsigned long long *)nullptr, N, (N + 1) / 2,
-                           1.0 / ((double)N * (double)N));
+        GH_CHECK(image_tail(ctx, N, dg.as<double2>(), dh.as<double2>(), pass == 0 ? dreal.as<double>() : dtmp.as<double>(),
+                            pass == 1 ? dmax.as<unsigned long long>() : nullptr));
     }
-    // normalise both by max(psf) (:544-548); dtmp holds the real PSF, dreal the real image
-    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells,
-                       dreal.as<double>(), dmax.as<unsigned long long>());
-    unsigned long long mb = 0;
-    GH_CHECK(d2h(ctx, &mb, dmax.p, 8));
-    GH_CHECK(sync(ctx));
-    mb = (mb & 0x8000000000000000ULL) ? (mb & 0x7fffffffffffffffULL) : ~mb;
-    double m;
-    memcpy(&m, &mb, 8);
-    if (pmax) *pmax = m;
-    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells,
-                       dtmp.as<double>(), dmax.as<unsigned long long>());
-    GH_CHECK_HIP(ctx, hipGetLastError());
+    GH_CHECK(normalise(ctx, cells, dreal.as<double>(), dtmp.as<double>(), dmax.as<unsigned long long>(), pmax));
     if (image) GH_CHECK(copy_out(ctx, image, dreal.p, cells * 8, dev));
     if (psf) GH_CHECK(copy_out(ctx, psf, dtmp.p, cells * 8, dev));
-    GH_CHECK(sync(ctx));
-    return GRIDHIP_OK;
+    return sync(ctx);
 }
 
 // builds [W][Q][Q][S][S] conjugated w-kernels for planes w = i*wstep + wmin (:434-448)
@@ -813,24 +749,15 @@ static int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s)
     if (dev) return GRIDHIP_OK;
     const size_t wel = (size_t)a.W * a.Q * a.Q * a.S * a.S, ael = (size_t)a.A * a.S * a.S;
     const size_t span = a.n > 0 ? (size_t)(a.n - 1) * a.stride + 1 : 0;
-    GH_CHECK(s.wk.alloc(ctx, wel * 16));
-    GH_CHECK(s.ws.alloc(ctx, a.W * 8));
-    GH_CHECK(s.ak.alloc(ctx, ael * 16));
-    GH_CHECK(s.u.alloc(ctx, span * 8));
-    GH_CHECK(s.v.alloc(ctx, span * 8));
-    GH_CHECK(s.w.alloc(ctx, span * 8));
-    GH_CHECK(s.a1.alloc(ctx, a.n * 8));
-    GH_CHECK(s.a2.alloc(ctx, a.n * 8));
-    GH_CHECK(s.vis.alloc(ctx, a.n * 16));
-    GH_CHECK(h2d(ctx, s.wk.p, a.wkerns, wel * 16));
-    GH_CHECK(h2d(ctx, s.ws.p, a.wvals, a.W * 8));
-    GH_CHECK(h2d(ctx, s.ak.p, a.akerns, ael * 16));
-    GH_CHECK(h2d(ctx, s.u.p, a.u, span * 8));
-    GH_CHECK(h2d(ctx, s.v.p, a.v, span * 8));
-    GH_CHECK(h2d(ctx, s.w.p, a.w, span * 8));
-    GH_CHECK(h2d(ctx, s.a1.p, a.a1, a.n * 8));
-    GH_CHECK(h2d(ctx, s.a2.p, a.a2, a.n * 8));
-    GH_CHECK(h2d(ctx, s.vis.p, a.vis, a.n * 16));
+    GH_CHECK(s.wk.upload(ctx, a.wkerns, wel * 16));
+    GH_CHECK(s.ws.upload(ctx, a.wvals, a.W * 8));
+    GH_CHECK(s.ak.upload(ctx, a.akerns, ael * 16));
+    GH_CHECK(s.u.upload(ctx, a.u, span * 8));
+    GH_CHECK(s.v.upload(ctx, a.v, span * 8));
+    GH_CHECK(s.w.upload(ctx, a.w, span * 8));
+    GH_CHECK(s.a1.upload(ctx, a.a1, a.n * 8));
+    GH_CHECK(s.a2.upload(ctx, a.a2, a.n * 8));
+    GH_CHECK(s.vis.upload(ctx, a.vis, a.n * 16));
     s.d.wkerns = s.wk.as<double>(), s.d.wvals = s.ws.as<double>(), s.d.akerns = s.ak.as<double>();
     s.d.u = s.u.as<double>(), s.d.v = s.v.as<double>(), s.d.w = s.w.as<double>();
     s.d.a1 = s.a1.as<int64_t>(), s.d.a2 = s.a2.as<int64_t>(), s.d.vis = s.vis.as<double>();
@@ -873,29 +800,16 @@ static int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, boo
     return GRIDHIP_OK;
 }
 
-// out = real(ifft(make_grid_hermitian(g))) (N x N doubles; the rolls folded in as in do_imaging_impl); its maximum
-// into *maxbits (ordered bits) when given.  h: N x N complex scratch.
-static int aw_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits)
+// aw_imaging on device-resident arguments d: the front end's one kernel (p = uvw / lam, findClosest w-bins; NB the
+// reference searches with w in wavelengths, not w / lam, :473-474), then the aw gridder into the N x N grid (zeroed
+// first).  Asynchronous.
+static int aw_imaging_to(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double *grid)
 {
-    static const unsigned long long neg_inf_bits = ~0xfff0000000000000ULL;  // ordered image of -inf
-    const size_t cells = (size_t)N * N;
-    void *plan = nullptr;
-    GH_CHECK(fft_plan_for(ctx, N, &plan));
-    hipLaunchKernelGGL(hermitian_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, g, h, N / 2);
-    if (int rc = g_fft.exec(plan, h, h, 1 /* HIPFFT_BACKWARD */)) return fail(ctx, GRIDHIP_EHIP, "hipfftExecZ2Z: %d", rc);
-    if (maxbits) GH_CHECK(h2d(ctx, maxbits, &neg_inf_bits, 8));
-    hipLaunchKernelGGL(real_max_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells, h, out,
-                       maxbits, N, (N + 1) / 2, 1.0 / ((double)N * (double)N));
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    return GRIDHIP_OK;
-}
-
-static double max_of_bits(unsigned long long mb)
-{
-    mb = (mb & 0x8000000000000000ULL) ? (mb & 0x7fffffffffffffffULL) : ~mb;
-    double m;
-    memcpy(&m, &mb, 8);
-    return m;
+    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
+    AwFront f;
+    GH_CHECK(aw_front(ctx, N, d, 1.0, false, 0, false, f));
+    return awgrid_pairs(ctx, N, N, 1, &grid, &d.vis, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, f.pu.as<double>(),
+                        f.pv.as<double>(), 1, f.wb.as<int64_t>(), d.a1, d.a2);
 }
 
 // do_imaging with imgfn = aw_imaging (src/Gridding.hs:509-549): doweight on the MIRRORED uvw (:531-535); both gridding
@@ -930,23 +844,13 @@ static int do_imaging_aw_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double
     const double *viss[2] = {f.vis1.as<double>(), f.wt.as<double>()};  // image from wt * vis1 (:538), PSF from wt (:541)
     GH_CHECK(awgrid_pairs(ctx, N, N, 2, grids, viss, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, f.pu.as<double>(),
                           f.pv.as<double>(), 1, f.wb.as<int64_t>(), d.a1, d.a2));
-    GH_CHECK(aw_tail(ctx, N, dg0.as<double2>(), dh.as<double2>(), rimg, nullptr));
-    GH_CHECK(aw_tail(ctx, N, dg1.as<double2>(), dh.as<double2>(), rpsf, dmax.as<unsigned long long>()));
-    // normalise both by max(psf) (:544-548)
-    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells, rimg,
-                       dmax.as<unsigned long long>());
-    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, (int64_t)cells, rpsf,
-                       dmax.as<unsigned long long>());
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    unsigned long long mb = 0;
-    GH_CHECK(d2h(ctx, &mb, dmax.p, 8));
-    if (!dev) {
-        GH_CHECK(d2h(ctx, image, rimg, cells * 8));
-        GH_CHECK(d2h(ctx, psf, rpsf, cells * 8));
-    }
-    GH_CHECK(sync(ctx));
-    if (pmax) *pmax = max_of_bits(mb);
-    return GRIDHIP_OK;
+    GH_CHECK(image_tail(ctx, N, dg0.as<double2>(), dh.as<double2>(), rimg, nullptr));
+    GH_CHECK(image_tail(ctx, N, dg1.as<double2>(), dh.as<double2>(), rpsf, dmax.as<unsigned long long>()));
+    GH_CHECK(normalise(ctx, cells, rimg, rpsf, dmax.as<unsigned long long>(), pmax));
+    if (dev) return GRIDHIP_OK;
+    GH_CHECK(d2h(ctx, image, rimg, cells * 8));
+    GH_CHECK(d2h(ctx, psf, rpsf, cells * 8));
+    return sync(ctx);
 }
 
 // aw_gridding, src/ImageDataset.hs:54-77: uvw in metres -> uvw_lambda (x f / c) -> doweight on the UN-mirrored uvw
@@ -975,7 +879,7 @@ static int aw_gridding_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double f
     const double *vis = fr.vis1.as<double>();
     GH_CHECK(awgrid_pairs(ctx, N, N, 1, &grid, &vis, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, fr.pu.as<double>(),
                           fr.pv.as<double>(), 1, fr.wb.as<int64_t>(), d.a1, d.a2));
-    GH_CHECK(aw_tail(ctx, N, dg.as<double2>(), dh.as<double2>(), rimg, dmax.as<unsigned long long>()));
+    GH_CHECK(image_tail(ctx, N, dg.as<double2>(), dh.as<double2>(), rimg, dmax.as<unsigned long long>()));
     unsigned long long mb = 0;
     GH_CHECK(d2h(ctx, &mb, dmax.p, 8));
     if (!dev) GH_CHECK(d2h(ctx, image, rimg, cells * 8));
@@ -1000,9 +904,8 @@ int gridhip_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t wstep, i
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf dw, db;
-    GH_CHECK(dw.alloc(ctx, n * 8));
+    GH_CHECK(dw.upload(ctx, w, n * 8));
     GH_CHECK(db.alloc(ctx, n * 8));
-    GH_CHECK(h2d(ctx, dw.p, w, n * 8));
     GH_CHECK(dev_wbins(ctx, n, dw.as<double>(), 1, wstep, db.as<int64_t>(), wmin, nplanes));
     GH_CHECK(d2h(ctx, wbin, db.p, n * 8));
     return sync(ctx);
@@ -1014,11 +917,9 @@ int gridhip_find_closest(gridhip_ctx *ctx, int64_t nws, const double *ws, int64_
     if (nws <= 0 || n < 0 || !ws || (n > 0 && (!w || !out))) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf dws, dw, dout;
-    GH_CHECK(dws.alloc(ctx, nws * 8));
-    GH_CHECK(dw.alloc(ctx, n * 8));
+    GH_CHECK(dws.upload(ctx, ws, nws * 8));
+    GH_CHECK(dw.upload(ctx, w, n * 8));
     GH_CHECK(dout.alloc(ctx, n * 8));
-    GH_CHECK(h2d(ctx, dws.p, ws, nws * 8));
-    GH_CHECK(h2d(ctx, dw.p, w, n * 8));
     if (n > 0)
         hipLaunchKernelGGL(find_closest_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, nws, dws.as<double>(), n,
                            dw.as<double>(), (int64_t)1, dout.as<int64_t>());
@@ -1033,14 +934,10 @@ int gridhip_mirror_uvw(gridhip_ctx *ctx, int64_t n, double *u, double *v, double
     if (n < 0 || (n > 0 && (!u || !v))) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf du, dv, dw, dvis;
-    GH_CHECK(du.alloc(ctx, n * 8));
-    GH_CHECK(dv.alloc(ctx, n * 8));
-    GH_CHECK(dw.alloc(ctx, n * 8));
-    GH_CHECK(dvis.alloc(ctx, n * 16));
-    GH_CHECK(h2d(ctx, du.p, u, n * 8));
-    GH_CHECK(h2d(ctx, dv.p, v, n * 8));
-    if (w) GH_CHECK(h2d(ctx, dw.p, w, n * 8));
-    if (vis) GH_CHECK(h2d(ctx, dvis.p, vis, n * 16));
+    GH_CHECK(du.upload(ctx, u, n * 8));
+    GH_CHECK(dv.upload(ctx, v, n * 8));
+    GH_CHECK(dw.upload(ctx, w, w ? n * 8 : 0));
+    GH_CHECK(dvis.upload(ctx, vis, vis ? n * 16 : 0));
     if (n > 0)
         hipLaunchKernelGGL(mirror_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, du.as<double>(),
                            dv.as<double>(), w ? dw.as<double>() : nullptr, vis ? dvis.as<double2>() : nullptr);
@@ -1060,15 +957,12 @@ int gridhip_doweight(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, con
     if (N <= 0 || n < 0 || (n > 0 && (!u || !v || !vis))) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf du, dv, dpu, dpv, dvis, cnt;
-    GH_CHECK(du.alloc(ctx, n * 8));
-    GH_CHECK(dv.alloc(ctx, n * 8));
+    GH_CHECK(du.upload(ctx, u, n * 8));
+    GH_CHECK(dv.upload(ctx, v, n * 8));
     GH_CHECK(dpu.alloc(ctx, n * 8));
     GH_CHECK(dpv.alloc(ctx, n * 8));
-    GH_CHECK(dvis.alloc(ctx, n * 16));
+    GH_CHECK(dvis.upload(ctx, vis, n * 16));
     GH_CHECK(cnt.alloc(ctx, (size_t)N * N * 4));
-    GH_CHECK(h2d(ctx, du.p, u, n * 8));
-    GH_CHECK(h2d(ctx, dv.p, v, n * 8));
-    GH_CHECK(h2d(ctx, dvis.p, vis, n * 16));
     GH_CHECK_HIP(ctx, hipMemsetAsync(cnt.p, 0, (size_t)N * N * 4, ctx->stream));
     if (n > 0) {
         hipLaunchKernelGGL(scale_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, du.as<double>(), (int64_t)1,
@@ -1092,9 +986,8 @@ int gridhip_make_grid_hermitian(gridhip_ctx *ctx, int64_t N, double *grid)
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cells = (size_t)N * N;
     DevBuf a, b;
-    GH_CHECK(a.alloc(ctx, cells * 16));
+    GH_CHECK(a.upload(ctx, grid, cells * 16));
     GH_CHECK(b.alloc(ctx, cells * 16));
-    GH_CHECK(h2d(ctx, a.p, grid, cells * 16));
     hipLaunchKernelGGL(hermitian_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, a.as<double2>(),
                        b.as<double2>(), (int64_t)0);
     GH_CHECK_HIP(ctx, hipGetLastError());
@@ -1109,10 +1002,9 @@ int gridhip_fft2_centered(gridhip_ctx *ctx, int64_t N, const double *in, double 
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cells = (size_t)N * N;
     DevBuf a, b, t;
-    GH_CHECK(a.alloc(ctx, cells * 16));
+    GH_CHECK(a.upload(ctx, in, cells * 16));
     GH_CHECK(b.alloc(ctx, cells * 16));
     GH_CHECK(t.alloc(ctx, cells * 16));
-    GH_CHECK(h2d(ctx, a.p, in, cells * 16));
     GH_CHECK(dev_fft2c(ctx, N, a.as<double2>(), b.as<double2>(), t.as<double2>(), inverse != 0));
     GH_CHECK(d2h(ctx, out, b.p, cells * 16));
     return sync(ctx);
@@ -1145,17 +1037,13 @@ static int stage3(gridhip_ctx *ctx, int64_t n, const double *u, const double *v,
 {
     const size_t span = n > 0 ? (size_t)(n - 1) * stride + 1 : 0;
     DevBuf s0, s1, s2;
-    GH_CHECK(s0.alloc(ctx, span * 8));
-    GH_CHECK(s1.alloc(ctx, span * 8));
-    GH_CHECK(s2.alloc(ctx, span * 8));
+    GH_CHECK(s0.upload(ctx, u, span * 8));
+    GH_CHECK(s1.upload(ctx, v, span * 8));
+    GH_CHECK(s2.upload(ctx, w, w ? span * 8 : 0));
     GH_CHECK(du.alloc(ctx, n * 8));
     GH_CHECK(dv.alloc(ctx, n * 8));
     GH_CHECK(dw.alloc(ctx, n * 8));
-    GH_CHECK(dvis.alloc(ctx, n * 16));
-    GH_CHECK(h2d(ctx, s0.p, u, span * 8));
-    GH_CHECK(h2d(ctx, s1.p, v, span * 8));
-    if (w) GH_CHECK(h2d(ctx, s2.p, w, span * 8));
-    GH_CHECK(h2d(ctx, dvis.p, vis, n * 16));
+    GH_CHECK(dvis.upload(ctx, vis, n * 16));
     if (n > 0) {
         hipLaunchKernelGGL(scale_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, s0.as<double>(), stride, 1.0,
                            du.as<double>());
@@ -1234,8 +1122,7 @@ int gridhip_conv_imaging(gridhip_ctx *ctx, int64_t Q, int64_t gh, int64_t gw, co
     DevBuf du, dv, dw, dvis, dg, dk;
     GH_CHECK(stage3(ctx, n, u, v, nullptr, uv_stride, vis, du, dv, dw, dvis));
     GH_CHECK(dg.alloc(ctx, (size_t)N * N * 16));
-    GH_CHECK(dk.alloc(ctx, (size_t)Q * Q * gh * gw * 16));
-    GH_CHECK(h2d(ctx, dk.p, kv, (size_t)Q * Q * gh * gw * 16));
+    GH_CHECK(dk.upload(ctx, kv, (size_t)Q * Q * gh * gw * 16));
     GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, (size_t)N * N * 16, ctx->stream));
     GH_CHECK(conv_grid_dev(ctx, lam, N, Q, gh, gw, dk.as<double>(), n, du.as<double>(), dv.as<double>(),
                            dvis.as<double>(), dg.as<double>()));
@@ -1274,42 +1161,16 @@ int gridhip_aw_imaging(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, i
                        const double *vis, double *grid)
 {
     if (!ctx) return GRIDHIP_EINVAL;
-    const int64_t N = haskell_round(theta * (double)lam);
-    if (N <= 0 || n < 0 || uv_stride < 1 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || !grid || !wkerns || !wvals ||
-        !akerns || (n > 0 && (!u || !v || !w || !a1 || !a2 || !vis)))
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N));
+    if (!grid) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf du, dv, dw, dvis, dg, dpu, dpv, dwb, dws, da1, da2, dwk, dak;
-    GH_CHECK(stage3(ctx, n, u, v, w, uv_stride, vis, du, dv, dw, dvis));
-    const size_t wel = (size_t)W * Q * Q * S * S, ael = (size_t)A * S * S;
+    AwStage s;
+    GH_CHECK(aw_stage(ctx, false, a, s));
+    DevBuf dg;
     GH_CHECK(dg.alloc(ctx, (size_t)N * N * 16));
-    GH_CHECK(dpu.alloc(ctx, n * 8));
-    GH_CHECK(dpv.alloc(ctx, n * 8));
-    GH_CHECK(dwb.alloc(ctx, n * 8));
-    GH_CHECK(dws.alloc(ctx, W * 8));
-    GH_CHECK(da1.alloc(ctx, n * 8));
-    GH_CHECK(da2.alloc(ctx, n * 8));
-    GH_CHECK(dwk.alloc(ctx, wel * 16));
-    GH_CHECK(dak.alloc(ctx, ael * 16));
-    GH_CHECK(h2d(ctx, dws.p, wvals, W * 8));
-    GH_CHECK(h2d(ctx, da1.p, a1, n * 8));
-    GH_CHECK(h2d(ctx, da2.p, a2, n * 8));
-    GH_CHECK(h2d(ctx, dwk.p, wkerns, wel * 16));
-    GH_CHECK(h2d(ctx, dak.p, akerns, ael * 16));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, (size_t)N * N * 16, ctx->stream));
-    if (n > 0) {
-        hipLaunchKernelGGL(scale_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, du.as<double>(), (int64_t)1,
-                           (double)lam, dpu.as<double>());
-        hipLaunchKernelGGL(scale_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, dv.as<double>(), (int64_t)1,
-                           (double)lam, dpv.as<double>());
-        // NB the reference searches with w in wavelengths, not w/lam (:473-474)
-        hipLaunchKernelGGL(find_closest_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, W, dws.as<double>(), n,
-                           dw.as<double>(), (int64_t)1, dwb.as<int64_t>());
-    }
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    GH_CHECK(gridhip_awgrid_dev(ctx, N, N, dg.as<double>(), n, W, Q, S, A, dwk.as<double>(), dak.as<double>(),
-                                dpu.as<double>(), dpv.as<double>(), 1, dwb.as<int64_t>(), da1.as<int64_t>(),
-                                da2.as<int64_t>(), dvis.as<double>()));
+    GH_CHECK(aw_imaging_to(ctx, N, s.d, dg.as<double>()));
     GH_CHECK(d2h(ctx, grid, dg.p, (size_t)N * N * 16));
     return sync(ctx);
 }
@@ -1334,8 +1195,7 @@ static int do_imaging_any(gridhip_ctx *ctx, bool dev, int kind, int64_t wstep, i
         DevBuf dk;
         const double *k = kv;
         if (!dev) {
-            GH_CHECK(dk.alloc(ctx, (size_t)Q * Q * gh * gw * 16));
-            GH_CHECK(h2d(ctx, dk.p, kv, (size_t)Q * Q * gh * gw * 16));
+            GH_CHECK(dk.upload(ctx, kv, (size_t)Q * Q * gh * gw * 16));
             k = dk.as<double>();
         }
         return do_imaging_impl(ctx, theta, lam, n, u, v, w, uv_stride, vis, image, psf, pmax, dev,
@@ -1416,11 +1276,7 @@ int gridhip_aw_imaging_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
     GH_CHECK(aw_check(ctx, a, &N));
     if (!grid) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
-    AwFront f;
-    GH_CHECK(aw_front(ctx, N, a, 1.0, false, 0, false, f));
-    return awgrid_pairs(ctx, N, N, 1, &grid, &vis, n, W, Q, S, A, wkerns, akerns, f.pu.as<double>(), f.pv.as<double>(),
-                        1, f.wb.as<int64_t>(), a1, a2);
+    return aw_imaging_to(ctx, N, a, grid);
 }
 
 int gridhip_do_imaging_aw(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
