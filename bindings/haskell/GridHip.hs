@@ -26,6 +26,8 @@ module GridHip
   , gridIO, convgridIO, convgrid2IO, degrid2IO, awgridIO, awdegridIO
   -- * imaging functions and do_imaging (src/Gridding.hs:76-93, 115-124, 399-449, 452-478, 509-549)
   , simpleImagingIO, convImagingIO, wCacheImagingIO, awImagingIO, doImagingIO, ImagingKind(..)
+  -- * prediction: a model image -> visibilities, the other half of a major cycle (absent from the reference)
+  , predictIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -217,6 +219,18 @@ foreign import ccall unsafe "gridhip_do_imaging_dev"
 -- int gridhip_w_cache_imaging_dev(ctx, wstep, qpx, npixFF, npixKern, theta, lam, n, u, v, w, uv_stride, vis, grid)
 foreign import ccall unsafe "gridhip_w_cache_imaging_dev"
   c_w_cache_imaging_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_predict(ctx, kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, model, n, u, v, w, uv_stride, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_predict"
+  c_predict :: Ptr Ctx -> CInt -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_predict_dev(ctx, kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, model, n, u, v, w, uv_stride, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_predict_dev"
+  c_predict_dev :: Ptr Ctx -> CInt -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_predict_aw(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, model, n, u, v, w, uv_stride, a1, a2, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_predict_aw"
+  c_predict_aw :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_predict_aw_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, model, n, u, v, w, uv_stride, a1, a2, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_predict_aw_dev"
+  c_predict_aw_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -537,6 +551,37 @@ doImagingIO h@(GridHip c) theta lam uvw vis kind = do
                realToFrac <$> peek pm
   let sh = A.Z A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr img), A.fromForeignPtrs sh (castForeignPtr psf), pmax)
+
+-- | predict theta lam uvw model kind vis_sub: the visibilities of a real N x N model image (N = round (theta * lam)),
+-- the exact adjoint of the imaging function `kind` applied to the centred forward transform of the model
+-- (include/gridhip.h, gridhip_predict / gridhip_predict_aw); with Just vis_sub, vis_sub minus that (the residual of a
+-- major cycle: doImagingIO -> model -> predictIO (Just vis) -> residual).  uvw as doImagingIO takes it (the (n,3)
+-- Matrix BaseLine in wavelengths, uv_stride 3), not mirrored.
+predictIO :: GridHip -> F -> Int -> A.Matrix BaseLine -> A.Matrix F -> ImagingKind -> Maybe (A.Vector Visibility)
+          -> IO (A.Vector Visibility)
+predictIO h@(GridHip c) theta lam uvw model kind visSub = do
+  let A.Z A.:. n A.:. _ = A.arrayShape uvw
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  let withSub k = maybe (k nullPtr) (\s -> withCplx s k) visSub
+      run k wstep q npixFF gh gw kv =
+        withForeignPtr out $ \o -> withF uvw $ \m -> withF model $ \md -> withSub $ \sb ->
+          c_predict c k (fi wstep) (fi q) (fi npixFF) (fi gh) (fi gw) kv (realToFrac theta) (fi lam) md (fi n)
+                    m (m `advancePtr` 1) (m `advancePtr` 2) 3 sb o >>= check h
+  case kind of
+    SimpleImaging -> run 0 (0 :: Int) (0 :: Int) (0 :: Int) (0 :: Int) (0 :: Int) nullPtr
+    ConvImaging kv ->
+      let A.Z A.:. q A.:. _ A.:. gh A.:. gw = A.arrayShape kv
+      in withCplx kv $ \k -> run 1 (0 :: Int) q (0 :: Int) gh gw k
+    WCacheImaging wstep q npixFF s -> run 2 wstep q npixFF s s nullPtr
+    AwImaging wkerns wvals akerns ant1 ant2 ->
+      let A.Z A.:. w A.:. q A.:. _ A.:. s A.:. _ = A.arrayShape wkerns
+          A.Z A.:. na A.:. _ A.:. _ = A.arrayShape akerns
+      in withForeignPtr out $ \o -> withF uvw $ \m -> withF model $ \md -> withSub $ \sb ->
+           withCplx wkerns $ \wk -> withF wvals $ \wv -> withCplx akerns $ \ak -> withI64 ant1 $ \a1 ->
+             withI64 ant2 $ \a2 ->
+               c_predict_aw c (realToFrac theta) (fi lam) (fi w) (fi q) (fi s) (fi na) wk wv ak md (fi n)
+                            m (m `advancePtr` 1) (m `advancePtr` 2) 3 a1 a2 sb o >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out))
 
 -- | aw_gridding after its HDF5 reads (src/ImageDataset.hs:54-77) as one library call: uvw is /vis/uvw in METRES,
 -- the (n,3) Matrix BaseLine, and f the frequency in Hz; uvw_lambda, doweight (on the UN-mirrored uvw, :59),

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 130 /* 0.1.3 */
+#define GRIDHIP_VERSION 140 /* 0.1.4 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -363,6 +363,55 @@ int gridhip_do_imaging_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q,
 int gridhip_w_cache_imaging_dev(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_t npixFF, int64_t npixKern,
                                 double theta, int64_t lam, int64_t n, const double *u, const double *v,
                                 const double *w, int64_t uv_stride, const double *vis, double *grid);
+
+/* ---- prediction: a model image -> visibilities, the other half of a major cycle -------------------------------------
+ * The model is a real N x N image, N = gridhip_image_size(theta, lam), row-major [y][x] and laid out as the `image` that
+ * do_imaging returns.  u, v and w are taken exactly as the imaging function of that kind takes them: same units (uvw in
+ * wavelengths), same uv_stride, no mirroring.  For each kind let A be the imaging function's linear map from visibilities
+ * to the N x N grid.  Then
+ *     F       = fft_c(model)   the centred forward transform, unnormalised (= gridhip_fft2_centered(.., inverse = 0) of
+ *                              the model as complex)
+ *     pred    = A^H F          the exact adjoint of the imaging function's scatter:
+ *       simple   pred[k] = F[y_k, x_k], the nearest-cell rule of gridhip_grid (n is the grid HEIGHT for both axes); NaN
+ *                or out-of-grid coordinates predict exactly 0
+ *       conv     degrid2 with conj(kv), W = 1                        (conv_imaging grids with kv)
+ *       w_cache  degrid2 with the UNconjugated w_kernel planes      (w_cache_imaging grids with their conjugates), on
+ *                the w-bins of w_cache_imaging (the wstep rule)
+ *       aw       awdegrid with conj(wkerns), conj(akerns)           (the identity stated at gridhip_awdegrid)
+ *     vis_out = pred, or vis_sub - pred (the residual) when vis_sub != NULL.
+ * The centred inverse transform's adjoint is N^-2 fft_c (odd N too), so for every kind, any vis and any real model
+ *     sum(model * Re(ifft_c(imgfn(vis)))) == N^-2 Re(vdot(vis, predict(model)))
+ * and this is the physically right prediction: a real sky's visibilities are its unnormalised DFT seen through the
+ * unconjugated w / A kernels.
+ * kind: 0 simple, 1 conv (Q, gh, gw, kv), 2 w_cache (wstep (<= 0: 2000), Q = qpx, npixFF, gh = npixKern; gw unused):
+ * do_imaging's layout.  The host forms are synchronous; the _dev forms take device pointers (model, u, v, w, kv,
+ * wkerns, wvals, akerns, a1, a2, vis_sub, vis_out) and are asynchronous on the context's stream, except kind 2, which
+ * reads the w-bins' min and max back as gridhip_do_imaging_dev does.  vis_out is overwritten, never accumulated;
+ * vis_out == vis_sub (an in-place residual) is allowed.  All arguments are checked before anything is touched: a refused
+ * call (bad kind, NULL model, NULL vis_out with n > 0, bad shapes) returns GRIDHIP_EINVAL and leaves vis_out unchanged.
+ * A support the gather cannot hold is GRIDHIP_EUNSUPPORTED, as for degrid2 and awdegrid.  Out-of-range antennas or aw
+ * w-bins predict exactly 0 (vis_sub[k] in the residual form) and are counted by gridhip_last_dropped as the gather counts
+ * them.  Scratch comes from the context's pool: after the first call of a shape a _dev call allocates nothing.  The
+ * w_cache kind takes w_cache_imaging's cached kernel table as it is; that cache is keyed on the w range, so predicting
+ * on un-mirrored w after a do_imaging (which mirrors) may rebuild it.  With timing enabled (gridhip_timing) ms_prepass
+ * is the transform (head kernel + FFT) and ms_kernel the gather and the epilogue. */
+int gridhip_predict(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh, int64_t gw,
+                    const double *kv, double theta, int64_t lam, const double *model, int64_t n,
+                    const double *u, const double *v, const double *w, int64_t uv_stride,
+                    const double *vis_sub, double *vis_out);
+int gridhip_predict_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh, int64_t gw,
+                        const double *kv, double theta, int64_t lam, const double *model, int64_t n,
+                        const double *u, const double *v, const double *w, int64_t uv_stride,
+                        const double *vis_sub, double *vis_out);
+/* aw: wkerns [W][Q][Q][S][S], wvals the W plane w-values searched by findClosest, akerns [A][S][S], as aw_imaging. */
+int gridhip_predict_aw(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                       const double *wkerns, const double *wvals, const double *akerns, const double *model,
+                       int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
+                       const int64_t *a1, const int64_t *a2, const double *vis_sub, double *vis_out);
+int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                           const double *wkerns, const double *wvals, const double *akerns, const double *model,
+                           int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
+                           const int64_t *a1, const int64_t *a2, const double *vis_sub, double *vis_out);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

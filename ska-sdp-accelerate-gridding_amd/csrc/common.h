@@ -354,4 +354,63 @@ int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *con
                  const int64_t *a2);
 size_t tables_bytes(const Geom &g);
 
+// ---- shared with predict.hip: the imaging functions' front ends and the centred transform (imaging.hip) -------------
+// work-groups of 256 threads for a grid-stride loop over n items (at most 16 per CU)
+static inline dim3 grid_for(gridhip_ctx *ctx, int64_t n, int block = 256)
+{
+    int64_t b = (n + block - 1) / block;
+    if (b < 1) b = 1;
+    if (b > (int64_t)ctx->num_cu * 16) b = (int64_t)ctx->num_cu * 16;
+    return dim3((unsigned)b);
+}
+// out[k] = x[k * stride] / lam (scale_kernel: div3, src/Gridding.hs:838-839)
+int launch_scale(gridhip_ctx *ctx, int64_t n, const double *x, int64_t stride, double lam, double *out);
+// out[y][x] = in[(y+s) mod N][(x+s) mod N] * scale (roll_kernel)
+int launch_roll(gridhip_ctx *ctx, int64_t N, const double2 *in, double2 *out, int64_t s, double scale);
+// the context's cached N x N Z2Z hipFFT plan, bound to its stream; an in-place transform with it
+int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan);
+int fft_exec(gridhip_ctx *ctx, void *plan, double2 *data, bool inverse);
+
+// What w_cache_imaging (src/Gridding.hs:399-449) derives from the baselines alone: scaled u, v, the
+// w-bins and one conjugated w-kernel per plane.  do_imaging calls the imaging function twice with the
+// same baselines (image and PSF, :538,541); the reference rebuilds everything both times ("no cache
+// despite the name", :405-411) — here the second call reuses it.
+struct WCache {
+    DevBuf pu, pv, wb;
+    double2 *table = nullptr;  // the context's cached table (gridhip_ctx::wk_cache): not owned
+    int64_t nplanes = 0;
+    bool ready = false;
+    gridhip_plan *plan = nullptr;  // the baselines binned once for both passes
+    ~WCache() { gridhip_plan_destroy(plan); }
+};
+// u, v, w: n contiguous doubles each (wavelengths); synchronises (the w-bin rule reads min / max back)
+int w_cache_prepare(gridhip_ctx *ctx, WCache &c, double theta, int64_t lam, int64_t wstep, int64_t Q, int64_t npixFF,
+                    int64_t S, int64_t n, const double *u, const double *v, const double *w);
+
+// the arguments of the aw entry points (aw_imaging_dev, do_imaging_aw, aw_gridding, predict_aw)
+struct AwArgs {
+    double theta;
+    int64_t lam, W, Q, S, A;
+    const double *wkerns, *wvals, *akerns;
+    int64_t n;
+    const double *u, *v, *w;
+    int64_t stride;
+    const int64_t *a1, *a2;
+    const double *vis;
+};
+// N = image size; vis_needed: whether the call reads vis (the gridding entry points do, predict_aw does not)
+int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed = true);
+// The inputs on the device: the caller's own (the _dev forms) or uploaded copies (the host forms), in s.d.
+struct AwStage {
+    DevBuf wk, ws, ak, u, v, w, a1, a2, vis;
+    AwArgs d;
+};
+int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s);
+// p = uvw1 / lam, w-bins, and (mirror) vis1, (weigh) wt * vis1 in vis1 and (want_wt) wt: aw_front_kernel +
+// aw_weight_kernel.  weigh: 0 none, 1 on the mirrored coordinates, 2 on the un-mirrored ones.
+struct AwFront {
+    DevBuf pu, pv, wb, vis1, wt, cell, cnt;
+};
+int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt, AwFront &f);
+
 }  // namespace gridhip

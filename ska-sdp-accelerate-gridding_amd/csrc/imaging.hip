@@ -357,14 +357,6 @@ __global__ void wkern_extract_kernel(int64_t na, int64_t Q, int64_t S, const dou
     }
 }
 
-static inline dim3 grid_for(gridhip_ctx *ctx, int64_t n, int block = 256)
-{
-    int64_t b = (n + block - 1) / block;
-    if (b < 1) b = 1;
-    if (b > (int64_t)ctx->num_cu * 16) b = (int64_t)ctx->num_cu * 16;
-    return dim3((unsigned)b);
-}
-
 // ---------------------------------------------------------------------------------------------
 // hipFFT, loaded on first use so the gridder itself has no dependency on it
 
@@ -410,7 +402,7 @@ static int load_hipfft(gridhip_ctx *ctx)
 // accelerate-fft: Forward = exp(-i..) unnormalised, Inverse = exp(+i..) scaled by 1/N^2.
 // `in` is preserved, `tmp` and `out` are N*N scratch/output (out may not alias in).
 // the context's cached N x N Z2Z plan, bound to its stream
-static int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan)
+int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan)
 {
     GH_CHECK(load_hipfft(ctx));
     if (N > 0x7fffffff) return fail(ctx, GRIDHIP_EUNSUPPORTED, "fft size");
@@ -433,6 +425,27 @@ static int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan)
     }
     if (int rc = g_fft.setstream(plan, ctx->stream)) return fail(ctx, GRIDHIP_EHIP, "hipfftSetStream: %d", rc);
     *out_plan = plan;
+    return GRIDHIP_OK;
+}
+
+int fft_exec(gridhip_ctx *ctx, void *plan, double2 *data, bool inverse)
+{
+    if (int rc = g_fft.exec(plan, data, data, inverse ? 1 /* HIPFFT_BACKWARD */ : -1 /* HIPFFT_FORWARD */))
+        return fail(ctx, GRIDHIP_EHIP, "hipfftExecZ2Z: %d", rc);
+    return GRIDHIP_OK;
+}
+
+int launch_scale(gridhip_ctx *ctx, int64_t n, const double *x, int64_t stride, double lam, double *out)
+{
+    if (n > 0) hipLaunchKernelGGL(scale_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, x, stride, lam, out);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int launch_roll(gridhip_ctx *ctx, int64_t N, const double2 *in, double2 *out, int64_t s, double scale)
+{
+    hipLaunchKernelGGL(roll_kernel, grid_for(ctx, N * N), dim3(256), 0, ctx->stream, N, in, out, s, scale);
+    GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }
 
@@ -639,20 +652,8 @@ static int build_wkernels(gridhip_ctx *ctx, double theta, int64_t wstep, int64_t
     return GRIDHIP_OK;
 }
 
-// What w_cache_imaging (src/Gridding.hs:399-449) derives from the baselines alone: scaled u, v, the
-// w-bins and one conjugated w-kernel per plane.  do_imaging calls the imaging function twice with the
-// same baselines (image and PSF, :538,541); the reference rebuilds everything both times ("no cache
-// despite the name", :405-411) — here the second call reuses it.
-struct WCache {
-    DevBuf pu, pv, wb;
-    double2 *table = nullptr;  // the context's cached table (gridhip_ctx::wk_cache): not owned
-    int64_t nplanes = 0;
-    bool ready = false;
-    gridhip_plan *plan = nullptr;  // the baselines binned once for both passes
-    ~WCache() { gridhip_plan_destroy(plan); }
-};
-
-static int w_cache_prepare(gridhip_ctx *ctx, WCache &c, double theta, int64_t lam, int64_t wstep, int64_t Q,
+// (WCache: common.h)
+int w_cache_prepare(gridhip_ctx *ctx, WCache &c, double theta, int64_t lam, int64_t wstep, int64_t Q,
                            int64_t npixFF, int64_t S, int64_t n, const double *u, const double *v, const double *w)
 {
     GH_CHECK(c.pu.alloc(ctx, n * 8));
@@ -716,34 +717,18 @@ static int w_cache_grid_dev(gridhip_ctx *ctx, WCache &c, double theta, int64_t l
 
 // ---- the aw entry points (aw_imaging_dev, do_imaging_aw, aw_gridding): front end -> aw gridder -> imaging tail ----
 
-struct AwArgs {
-    double theta;
-    int64_t lam, W, Q, S, A;
-    const double *wkerns, *wvals, *akerns;
-    int64_t n;
-    const double *u, *v, *w;
-    int64_t stride;
-    const int64_t *a1, *a2;
-    const double *vis;
-};
-
+// (AwArgs, AwStage: common.h)
 // Everything is checked before anything is touched (a refused call leaves its outputs as they were).
-static int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N)
+int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed)
 {
     *N = haskell_round(a.theta * (double)a.lam);
     if (*N <= 0 || a.n < 0 || a.stride < 1 || a.W <= 0 || a.Q <= 0 || a.S <= 0 || a.A <= 0 || !a.wkerns || !a.wvals ||
-        !a.akerns || (a.n > 0 && (!a.u || !a.v || !a.w || !a.a1 || !a.a2 || !a.vis)))
+        !a.akerns || (a.n > 0 && (!a.u || !a.v || !a.w || !a.a1 || !a.a2 || (vis_needed && !a.vis))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     return GRIDHIP_OK;
 }
 
-// The inputs on the device: the caller's own (the _dev forms) or uploaded copies (the host forms), in s.d.
-struct AwStage {
-    DevBuf wk, ws, ak, u, v, w, a1, a2, vis;
-    AwArgs d;
-};
-
-static int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s)
+int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s)
 {
     s.d = a;
     if (dev) return GRIDHIP_OK;
@@ -757,20 +742,15 @@ static int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s)
     GH_CHECK(s.w.upload(ctx, a.w, span * 8));
     GH_CHECK(s.a1.upload(ctx, a.a1, a.n * 8));
     GH_CHECK(s.a2.upload(ctx, a.a2, a.n * 8));
-    GH_CHECK(s.vis.upload(ctx, a.vis, a.n * 16));
+    GH_CHECK(s.vis.upload(ctx, a.vis, a.vis ? a.n * 16 : 0));  // (predict_aw reads no vis)
     s.d.wkerns = s.wk.as<double>(), s.d.wvals = s.ws.as<double>(), s.d.akerns = s.ak.as<double>();
     s.d.u = s.u.as<double>(), s.d.v = s.v.as<double>(), s.d.w = s.w.as<double>();
     s.d.a1 = s.a1.as<int64_t>(), s.d.a2 = s.a2.as<int64_t>(), s.d.vis = s.vis.as<double>();
     return GRIDHIP_OK;
 }
 
-// p = uvw1 / lam, w-bins, and (mirror) vis1, (weigh) wt * vis1 in vis1 and (want_wt) wt: aw_front_kernel +
-// aw_weight_kernel.  weigh: 0 none, 1 on the mirrored coordinates, 2 on the un-mirrored ones.
-struct AwFront {
-    DevBuf pu, pv, wb, vis1, wt, cell, cnt;
-};
-
-static int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt,
+// (AwFront: common.h)
+int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt,
                     AwFront &f)
 {
     const int64_t n = d.n;

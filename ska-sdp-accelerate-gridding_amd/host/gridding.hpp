@@ -10,6 +10,7 @@
 //   convgrid3/convgrid4 wkerns akerns a p index v   :246-252, :318-324
 //   simple_imaging / conv_imaging / w_cache_imaging / aw_imaging   :84, :115, :399, :452
 //   do_imaging theta lam uvw a1 a2 t f vis imgfn    :509-519 (do_imaging_aw: imgfn = aw_imaging)
+//   predict / predict_aw: the way back, model image -> visibilities (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -235,6 +236,37 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         return {std::move(img), std::move(psf), pmax};
     }
 
+    // ---- prediction: the adjoint of an imaging function applied to fft_c(model) (gridhip_predict) ----
+    // model: the real N x N image (N = gridhip_image_size(theta, lam)); uvw in wavelengths, not mirrored.  kind 0
+    // simple, 1 conv (kv), 2 w_cache (ko).  vis_sub given: vis_sub - prediction (the residual).
+    std::vector<Visibility> predict(int kind, F theta, Int lam, const Matrix<F> &model, const BaseLines &uvw,
+                                    const Kernel *kv = nullptr, const KernelOptions *ko = nullptr,
+                                    const std::vector<Visibility> *vis_sub = nullptr)
+    {
+        check_model(theta, lam, model);
+        std::vector<Visibility> out(uvw.size());
+        Int wstep = 0, Q = 0, npixFF = 0, gh = 0, gw = 0;
+        if (kv) Q = kv->Q, gh = kv->gh, gw = kv->gw;
+        if (ko) wstep = ko->wstep, Q = ko->qpx, npixFF = ko->npixFF, gh = gw = ko->npixKern;
+        check(gridhip_predict(ctx_, kind, wstep, Q, npixFF, gh, gw, kv ? cd(kv->data) : nullptr, theta, lam,
+                              model.data.data(), (Int)uvw.size(), uvw.u.data(), uvw.v.data(),
+                              uvw.w.empty() ? nullptr : uvw.w.data(), 1, vis_sub ? cd(*vis_sub) : nullptr, cd(out)));
+        return out;
+    }
+    // the same for aw_imaging (:452-478): the gather twin of awdegrid with conj(wk), conj(ak)
+    std::vector<Visibility> predict_aw(F theta, Int lam, const WKernels &wk, const std::vector<F> &wbins,
+                                       const AKernels &ak, const Matrix<F> &model, const BaseLines &uvw,
+                                       const std::vector<Int> &a1, const std::vector<Int> &a2,
+                                       const std::vector<Visibility> *vis_sub = nullptr)
+    {
+        check_model(theta, lam, model);
+        std::vector<Visibility> out(uvw.size());
+        check(gridhip_predict_aw(ctx_, theta, lam, wk.W, wk.Q, wk.gh, ak.A, cd(wk.data), wbins.data(), cd(ak.data),
+                                 model.data.data(), (Int)uvw.size(), uvw.u.data(), uvw.v.data(), uvw.w.data(), 1,
+                                 a1.data(), a2.data(), vis_sub ? cd(*vis_sub) : nullptr, cd(out)));
+        return out;
+    }
+
     // ---- helpers ----
     Matrix<Visibility> make_grid_hermitian(Matrix<Visibility> g)
     {
@@ -265,6 +297,11 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
 
    private:
     gridhip_ctx *ctx_ = nullptr;
+    static void check_model(F theta, Int lam, const Matrix<F> &model)
+    {
+        const Int N = gridhip_image_size(theta, lam);
+        if (model.h != N || model.w != N) throw Error(GRIDHIP_EINVAL, "model must be N x N, N = gridhip_image_size(theta, lam)");
+    }
 };
 
 

@@ -553,6 +553,67 @@ class Context:
                                    theta, lam, wkernels, wbins, akernels, uvw_m, a1, a2, vis, 1)
         return img, mx
 
+    def predict(self, theta, lam, uvw, model, imgfn, a1=None, a2=None, vis_sub=None, out=None):
+        """Visibilities of a real N x N model image (gridhip_predict[_aw][_dev]): the adjoint of the imaging function
+        `imgfn` applied to fft_c(model), or vis_sub minus that (the residual) when vis_sub is given.  imgfn takes
+        do_imaging's tuples: ("simple",) | ("conv", kv) | ("w_cache", kernops) | ("aw", wkernels, wbins, akernels), the
+        last with the antenna indices a1, a2.  uvw (wavelengths, not mirrored) as the imaging function takes it.
+        numpy in gives numpy out; torch cuda tensors take the device form on torch's stream and return a cuda tensor.
+        out: the array to write (may be vis_sub itself: an in-place residual); a new one when None."""
+        dev = _is_torch(model)
+        N = self.image_size(theta, lam)
+        if tuple(model.shape) != (N, N):
+            raise ValueError(f"model must be {N} x {N} (image_size(theta, lam)), not {tuple(model.shape)}")
+        if dev:
+            import torch
+            cv = lambda t, dt: None if t is None else (t if (t.dtype == dt and t.is_contiguous()) else t.to(dt).contiguous())
+            u, v, w, st = self._uvw_dev(uvw)
+            model = cv(model, torch.float64)
+            n = int(u.shape[0])
+            sub = cv(vis_sub, torch.complex128)
+            if out is None:
+                out = torch.empty(n, dtype=torch.complex128, device=model.device)
+            elif not (out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous()):
+                raise ValueError("out must be a contiguous cuda complex128 tensor")
+            self._use_torch_stream()
+        else:
+            cv = lambda t, dt: None if t is None else self._np(t, dt)
+            u, v, w, st = self._uvw(uvw)
+            model = self._np(model, np.float64)
+            n = len(u)
+            sub = cv(vis_sub, np.complex128)
+            if out is None:
+                out = np.empty(n, dtype=np.complex128)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.complex128 and out.flags.c_contiguous):
+                raise ValueError("out must be a C-contiguous complex128 ndarray")
+        if len(out) != n or (sub is not None and len(sub) != n):
+            raise ValueError("vis_sub and out must hold one value per visibility")
+        if imgfn[0] == "aw":
+            cplx, real, idx = ((lambda t: cv(t, torch.complex128)), (lambda t: cv(t, torch.float64)),
+                               (lambda t: cv(t, torch.int64))) if dev else \
+                ((lambda t: cv(t, np.complex128)), (lambda t: cv(t, np.float64)), (lambda t: cv(t, np.int64)))
+            wk, wv, ak, a1, a2 = cplx(imgfn[1]), real(imgfn[2]), cplx(imgfn[3]), idx(a1), idx(a2)
+            W, Q, _, S, _ = wk.shape
+            fn = self._lib.gridhip_predict_aw_dev if dev else self._lib.gridhip_predict_aw
+            self._check(fn(self._h, float(theta), int(lam), W, Q, S, ak.shape[0], self._ptr(wk), self._ptr(wv),
+                           self._ptr(ak), self._ptr(model), n, self._ptr(u), self._ptr(v), self._ptr(w), st,
+                           self._ptr(a1), self._ptr(a2), self._ptr(sub), self._ptr(out)))
+            return out
+        kind, wstep, Q, npixFF, gh, gw, kv = 0, 0, 0, 0, 0, 0, None
+        if imgfn[0] == "conv":
+            kv = cv(imgfn[1], torch.complex128 if dev else np.complex128)
+            kind, (Q, _, gh, gw) = 1, kv.shape
+        elif imgfn[0] == "w_cache":
+            ko = imgfn[1]
+            kind, wstep, Q, npixFF, gh = 2, int(ko.get("wstep") or 2000), int(ko["qpx"]), int(ko["npixFF"]), int(ko["npixKern"])
+            gw = gh
+        elif imgfn[0] != "simple":
+            raise ValueError("unknown imaging function")
+        fn = self._lib.gridhip_predict_dev if dev else self._lib.gridhip_predict
+        self._check(fn(self._h, kind, wstep, Q, npixFF, gh, gw, self._ptr(kv), float(theta), int(lam), self._ptr(model),
+                       n, self._ptr(u), self._ptr(v), self._ptr(w), st, self._ptr(sub), self._ptr(out)))
+        return out
+
 
 class Plan:
     """Baselines binned once (gridhip_plan); grid()/degrid() run the tile kernel only."""

@@ -26,6 +26,8 @@ _AW_IMG = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp,
            C.POINTER(C.c_double)]
 _AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp,
                 C.POINTER(C.c_double)]
+_PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, vp, vp, i64, vp, vp]
+_PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
     "gridhip_strerror": (C.c_char_p, [ci]),
@@ -86,6 +88,10 @@ SIGNATURES = {
     "gridhip_do_imaging_dev": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp,
                                     vp, C.POINTER(C.c_double)]),
     "gridhip_w_cache_imaging_dev": (ci, [vp, i64, i64, i64, i64, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp]),
+    "gridhip_predict": (ci, _PREDICT),
+    "gridhip_predict_dev": (ci, _PREDICT),
+    "gridhip_predict_aw": (ci, _PREDICT_AW),
+    "gridhip_predict_aw_dev": (ci, _PREDICT_AW),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),
