@@ -28,6 +28,8 @@ module GridHip
   , simpleImagingIO, convImagingIO, wCacheImagingIO, awImagingIO, doImagingIO, ImagingKind(..)
   -- * prediction: a model image -> visibilities, the other half of a major cycle (absent from the reference)
   , predictIO
+  -- * imagers: the baselines of a major cycle bound once, one call per cycle (include/gridhip.h, gridhip_imager_*)
+  , ImagerH, withImager, imagerCycleIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -50,6 +52,7 @@ import Types   -- F, Visibility, BaseLine, BaseLines, Antenna (src/Types.hs:7-16
 data Ctx
 data Plan
 data AwPlan
+data Imager
 data Comm
 newtype GridHip = GridHip (Ptr Ctx)
 newtype Node    = Node (Ptr Comm)
@@ -231,6 +234,24 @@ foreign import ccall unsafe "gridhip_predict_aw"
 -- int gridhip_predict_aw_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, model, n, u, v, w, uv_stride, a1, a2, vis_sub, vis_out)
 foreign import ccall unsafe "gridhip_predict_aw_dev"
   c_predict_aw_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_create_dev(ctx, kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, n, u, v, w, uv_stride, imager)
+foreign import ccall unsafe "gridhip_imager_create_dev"
+  c_imager_create_dev :: Ptr Ctx -> CInt -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr (Ptr Imager) -> IO CInt
+-- int gridhip_imager_create_aw_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, imager)
+foreign import ccall unsafe "gridhip_imager_create_aw_dev"
+  c_imager_create_aw_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr (Ptr Imager) -> IO CInt
+-- int gridhip_imager_psf_dev(imager, psf, pmax)
+foreign import ccall unsafe "gridhip_imager_psf_dev"
+  c_imager_psf_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_cycle_dev(imager, model, vis, image, vis_res)
+foreign import ccall unsafe "gridhip_imager_cycle_dev"
+  c_imager_cycle_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_predict_dev(imager, model, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_imager_predict_dev"
+  c_imager_predict_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_destroy(imager)
+foreign import ccall unsafe "gridhip_imager_destroy"
+  c_imager_destroy :: Ptr Imager -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -603,6 +624,63 @@ awGriddingIO h@(GridHip c) theta lam f wkerns wvals akerns uvw ant1 ant2 vis = d
                             m (m `advancePtr` 1) (m `advancePtr` 2) 3 a1 a2 vs pi' pm >>= check h
               realToFrac <$> peek pm
   return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr img), mx)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Imagers (include/gridhip.h, gridhip_imager_*): device pointers only, like the plans, so the host arrays are staged
+-- through gridhip_malloc / gridhip_memcpy_h2d here.
+
+-- | an imager, its context, the visibilities it was created for and its image size
+data ImagerH = ImagerH GridHip (Ptr Imager) Int Int
+
+-- a device copy of `bytes` bytes at `src` for the duration of `k`
+withDev :: GridHip -> Ptr a -> Int -> (Ptr b -> IO c) -> IO c
+withDev h@(GridHip c) src bytes k = bracket open (\d -> () <$ c_free c d) $ \d -> do
+  c_memcpy_h2d c d (castPtr src) (fi bytes) >>= check h
+  k (castPtr d)
+  where open = alloca $ \pp -> c_malloc c pp (fi (max 16 bytes)) >>= check h >> peek pp
+
+-- | withImager h theta lam uvw kind k: bind the baselines `uvw` (the (n,3) Matrix BaseLine in wavelengths, not
+-- mirrored, as doImagingIO and predictIO take it) and the imaging function `kind` once - mirror, weights, w-bins, kernel
+-- tables, both binnings, the PSF - and run `k` with the imager; the loop of a major cycle is then imagerCycleIO alone.
+withImager :: GridHip -> F -> Int -> A.Matrix BaseLine -> ImagingKind -> (ImagerH -> IO a) -> IO a
+withImager h@(GridHip c) theta lam uvw kind k = do
+  n' <- imageSize theta lam
+  let A.Z A.:. n A.:. _ = A.arrayShape uvw
+      make f = alloca $ \pp -> f pp >>= check h >> peek pp
+      plain kd wstep q npixFF gh gw kv = withF uvw $ \m -> withDev h m (24 * n) $ \d ->
+        make $ c_imager_create_dev c kd (fi wstep) (fi q) (fi npixFF) (fi gh) (fi gw) kv (realToFrac theta) (fi lam)
+                                   (fi n) d (d `advancePtr` 1) (d `advancePtr` 2) 3
+      open = case kind of
+        SimpleImaging -> plain 0 (0 :: Int) (0 :: Int) (0 :: Int) (0 :: Int) (0 :: Int) nullPtr
+        ConvImaging kv ->
+          let A.Z A.:. q A.:. _ A.:. gh A.:. gw = A.arrayShape kv
+          in withCplx kv $ \kp -> withDev h kp (16 * q * q * gh * gw) $ \dk -> plain 1 (0 :: Int) q (0 :: Int) gh gw dk
+        WCacheImaging wstep q npixFF s -> plain 2 wstep q npixFF s s nullPtr
+        AwImaging wkerns wvals akerns ant1 ant2 ->
+          let A.Z A.:. w A.:. q A.:. _ A.:. s A.:. _ = A.arrayShape wkerns
+              A.Z A.:. na A.:. _ A.:. _ = A.arrayShape akerns
+          in withF uvw $ \m -> withDev h m (24 * n) $ \d -> withCplx wkerns $ \wk ->
+               withDev h wk (16 * w * q * q * s * s) $ \dwk -> withF wvals $ \wv -> withDev h wv (8 * w) $ \dwv ->
+                 withCplx akerns $ \ak -> withDev h ak (16 * na * s * s) $ \dak -> withI64 ant1 $ \a1 ->
+                   withDev h a1 (8 * n) $ \d1 -> withI64 ant2 $ \a2 -> withDev h a2 (8 * n) $ \d2 ->
+                     make $ c_imager_create_aw_dev c (realToFrac theta) (fi lam) (fi w) (fi q) (fi s) (fi na) dwk dwv dak
+                                                   (fi n) d (d `advancePtr` 1) (d `advancePtr` 2) 3 d1 d2
+  bracket open (\p -> () <$ c_imager_destroy p) $ \p -> k (ImagerH h p n n')
+
+-- | imagerCycleIO im model vis: the image of doImagingIO (predictIO (Just vis) model) for the imager's baselines
+-- (of doImagingIO vis with Nothing), and the residual visibilities vis - predict model.
+imagerCycleIO :: ImagerH -> Maybe (A.Matrix F) -> A.Vector Visibility -> IO (A.Matrix F, A.Vector Visibility)
+imagerCycleIO (ImagerH h@(GridHip c) p n n') model vis = do
+  img <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  res <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  let withModel k = maybe (k nullPtr) (\m -> withF m $ \mp -> withDev h mp (8 * n' * n') k) model
+  withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withModel $ \dm ->
+    withForeignPtr img $ \pi' -> withDev h pi' (8 * n' * n') $ \di -> withForeignPtr res $ \pr -> do
+      c_imager_cycle_dev p dm dv di dv >>= check h   -- (the residual in place, in the device copy of vis)
+      c_memcpy_d2h c (castPtr pi') (castPtr di) (fi (8 * n' * n')) >>= check h
+      c_memcpy_d2h c (castPtr pr) (castPtr dv) (fi (16 * n)) >>= check h
+      c_synchronize c >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr img), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr res))
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

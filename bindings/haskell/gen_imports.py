@@ -21,6 +21,8 @@ TYPES = [
     (r"^gridhip_plan \*$", "Ptr Plan"),
     (r"^gridhip_aw_plan \*\*$", "Ptr (Ptr AwPlan)"),
     (r"^gridhip_aw_plan \*$", "Ptr AwPlan"),
+    (r"^gridhip_imager \*\*$", "Ptr (Ptr Imager)"),
+    (r"^gridhip_imager \*$", "Ptr Imager"),
     (r"^gridhip_comm \*\*$", "Ptr (Ptr Comm)"),
     (r"^(const )?gridhip_comm \*$", "Ptr Comm"),
     (r"^double \*const \*$", "Ptr (Ptr CDouble)"),

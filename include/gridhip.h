@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 140 /* 0.1.4 */
+#define GRIDHIP_VERSION 150 /* 0.1.5 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -126,7 +126,7 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  * Read-only (gridhip_get_option): "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last
  * convgrid / convgrid2 / degrid2 call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
  * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or
- * aw plan creation built (0 after an aw plan pass);
+ * aw plan or aw imager creation built (0 after an aw plan pass or an imager's cycle);
  * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan / awdegrid / aw plan pass call used:
  * 1 = the tap-reusing tile kernel (square supports 5..32 with enough visibilities per work item), 2 = the same through
  * sub-footprints (other shapes: one record per spatial part of the kernel), 3 = the general tile kernel (small
@@ -412,6 +412,71 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
                            const double *wkerns, const double *wvals, const double *akerns, const double *model,
                            int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
                            const int64_t *a1, const int64_t *a2, const double *vis_sub, double *vis_out);
+
+/* ---- imagers: bind the baselines once, one asynchronous call per major cycle (device pointers) ----------------------
+ * A major cycle is
+ *     residual = predict(model, vis_sub = vis);  image, psf, pmax = do_imaging(residual)
+ * and in it uvw, the antenna pairs, the kernels, theta and lam never change: only model and, at most, vis do.  An imager
+ * is created once from those and is DEFINED BY THE TWO CALLS IT REPLACES.  For the arguments given at creation, with
+ * predict* / do_imaging* the _dev entry points of the imager's kind:
+ *   cycle(model, vis)   image = the `image` output of do_imaging*(vis - predict*(model)); vis_res, when given,
+ *                       = vis - predict*(model), un-mirrored and un-weighted as predict returns it (vis_res == vis: in place)
+ *   cycle(NULL, vis)    image = the `image` output of do_imaging*(vis); vis_res, when given, receives vis
+ *   psf, pmax           the `psf` / `pmax` outputs of do_imaging* for these baselines (they do not depend on vis)
+ *   predict(model, vis_sub, vis_out)   gridhip_predict*_dev with the same arguments
+ * which fixes every convention: weights from the mirrored uvw, a1 / a2 not swapped by the mirror, the image normalised by
+ * pmax, prediction on the UN-mirrored baselines with the conjugated tables, dropped baselines predicting exactly 0 and
+ * gridding nothing, NaN coordinates as the simple kind treats them.  Results agree with the two calls to the tolerance
+ * the fp64 atomics of either side allow (1e-10 of the largest magnitude), not bit for bit.
+ * Creation (may synchronise; the one place the w_cache kind reads a min / max back) slices and scales the strided uvw,
+ * mirrors, histograms and applies the uniform weights, computes the w-bins of both streams, builds or copies the kernel
+ * tables into memory of the imager's own, bins both record sets, grids the PSF and runs its tail.  Every creation input
+ * may be freed or overwritten once it returns.  gridhip_last_dropped and gridhip_aw_last_stats then report the mirrored
+ * stream's binning, "aw_tables_built" both streams' tables.  Everything is checked at creation by gridhip_predict's /
+ * gridhip_aw_imaging's rules (GRIDHIP_EINVAL); a support the gather cannot hold, more than 65536 w-planes or a shape
+ * outside the aw limits is GRIDHIP_EUNSUPPORTED.  A refused creation leaves *imager NULL and nothing allocated.
+ * A cycle is: head kernel + forward FFT of the model, the gather over the un-mirrored records, ONE pass over the
+ * visibilities (subtract, store vis_res, conjugate where mirrored, times the weight), the scatter over the mirrored
+ * records, Hermitian fill + inverse FFT + real part divided by the stored pmax.  No PSF pass, no pre-pass, no table
+ * build, no histogram.  cycle and predict enqueue on the context's stream and return: after the first cycle (which may
+ * grow the context's launcher scratch) they allocate nothing, never synchronise, read nothing back and enqueue kernels
+ * only - no memset node - so a cycle can be captured into a graph.  With timing enabled ms_prepass is the prediction
+ * side (transform, gather, the pass over the visibilities) and ms_kernel the scatter and the tail.
+ * The prediction gathers on the un-mirrored baselines and do_imaging scatters on the mirrored ones, and the two
+ * binnings are not mirror images of each other bit for bit (floor(.5 + x), the w-bin rule and findClosest are not odd
+ * functions): an imager keeps BOTH record sets, and for the aw kind both kernel tables ((wk, ak) keyed on the mirrored
+ * stream, (conj wk, conj ak) on the un-mirrored one, per batch of 2^20 visibilities as gridhip_aw_plan holds them); for
+ * w_cache one table per stream's w range (the gather's planes are the w_kernels, the scatter's their conjugates: two
+ * tables even where the ranges agree).  Supports the tap-reusing kernel has no instantiation for go through
+ * sub-footprints as they do for plans (their zero-padded table is rebuilt in the context's scratch by each pass).
+ * Memory an imager holds: per visibility 8 B (the weight, its sign the mirror flag) + 16 B (the prediction, which the
+ * pass over the visibilities turns into the gridder's input in place) + 2 x 8 B records (x P for sub-footprints), or
+ * 4 x 8 B coordinates instead of records for the simple kind; per N^2 cell 16 B (grid) + 16 B (transform) + 8 B (psf),
+ * and 16 B more for odd N; the kernel tables (conv: 2 tables; w_cache: one plane per w-bin of each stream; aw: each
+ * batch's distinct kernels, twice) and one hipFFT plan.
+ * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
+ * and 1).  n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
+ * touches nothing.  An imager belongs to its context (same device, same stream, not thread-safe) and must be destroyed
+ * before it; any other call on the context between two imager calls - do_imaging or predict of another shape, another
+ * imager, a rebuild of the w-kernel cache - leaves its results unchanged. */
+typedef struct gridhip_imager gridhip_imager;
+int gridhip_imager_create_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
+                              int64_t gw, const double *kv, double theta, int64_t lam, int64_t n, const double *u,
+                              const double *v, const double *w, int64_t uv_stride, gridhip_imager **imager);
+/* aw: gridhip_do_imaging_aw's / gridhip_predict_aw's argument layout */
+int gridhip_imager_create_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
+                                 int64_t A, const double *wkerns, const double *wvals, const double *akerns,
+                                 int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
+                                 const int64_t *a1, const int64_t *a2, gridhip_imager **imager);
+/* the PSF (N x N doubles on the device, copied on the stream) and its maximum (a HOST pointer), both computed at
+ * creation; either may be NULL */
+int gridhip_imager_psf_dev(gridhip_imager *imager, double *psf, double *pmax);
+/* one major-cycle step.  model NULL: no prediction.  vis_res NULL: the residual visibilities are not returned */
+int gridhip_imager_cycle_dev(gridhip_imager *imager, const double *model, const double *vis, double *image,
+                             double *vis_res);
+/* the prediction alone, gridhip_predict's vis_sub / vis_out rules */
+int gridhip_imager_predict_dev(gridhip_imager *imager, const double *model, const double *vis_sub, double *vis_out);
+int gridhip_imager_destroy(gridhip_imager *imager);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

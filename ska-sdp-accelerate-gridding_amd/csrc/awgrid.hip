@@ -735,7 +735,18 @@ struct gridhip_aw_plan {
         bool all_binned = false;   // no visibility of the batch was dropped: degrid writes all of its predictions
     };
     std::vector<Batch> b;
+    bool caller_clears = false;  // degrid leaves the clearing of its output to the caller (aw_plan_caller_clears)
 };
+
+namespace gridhip {
+bool aw_plan_caller_clears(gridhip_aw_plan *plan)
+{
+    plan->caller_clears = true;
+    for (const auto &b : plan->b)
+        if (!b.all_binned) return true;
+    return false;
+}
+}  // namespace gridhip
 
 namespace {
 // the launchers read the binned data from the context's scratch slots: lend them a batch's
@@ -778,7 +789,8 @@ int aw_plan_pass(gridhip_aw_plan *pl, const double *vis, double *grid, double *v
     for (auto &b : pl->b) {
         const gridhip::Geom g = batch_geom(pl, b);
         if (degrid) {
-            if (!b.all_binned) GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out + 2 * b.lo, 0, (size_t)b.m * 16, ctx->stream));
+            if (!b.all_binned && !pl->caller_clears)
+                GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out + 2 * b.lo, 0, (size_t)b.m * 16, ctx->stream));
             AwLend lend(ctx, b);
             GH_CHECK(gridhip::aw_pass(ctx, pl->p, g, b.m, b.table, vis_out + 2 * b.lo, grid, true));
         } else {

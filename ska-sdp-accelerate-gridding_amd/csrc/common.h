@@ -303,6 +303,32 @@ __device__ __forceinline__ void frac_coord_dev(int64_t n, int32_t qpx, double p,
     *fr = r;
 }
 
+// findClosest, src/Gridding.hs:895-907 (hi clamped to len-1 as the host twin does, ImageDataset.hs:150-168)
+__device__ __forceinline__ int64_t closest_index(int64_t nws, const double *__restrict__ ws, double x)
+{
+    int64_t lo = 0, hi = nws;
+    while ((hi - lo) / 2 >= 1) {
+        const int64_t mid = (hi + lo) / 2;
+        if (x > ws[mid])
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int64_t hc = hi > nws - 1 ? nws - 1 : hi;
+    return fabs(x - ws[lo]) < fabs(x - ws[hc]) ? lo : hc;
+}
+
+// doweight's cell, src/Gridding.hs:564-583: frac_coords (N,N) 1 p; -1: outside the grid or NaN (the weight stays 1)
+__device__ __forceinline__ int64_t weight_cell(int64_t N, double pu, double pv)
+{
+    int64_t x, y;
+    int32_t f;
+    frac_coord_dev(N, 1, pu, &x, &f);
+    frac_coord_dev(N, 1, pv, &y, &f);
+    if (!(pu == pu) || !(pv == pv) || x < 0 || y < 0 || x >= N || y >= N) return -1;
+    return y * N + x;
+}
+
 // kernel launchers (each enqueues on ctx->stream)
 // zero_out (degrid2): the counting sweep writes a zero prediction for every visibility it drops (no tap inside the
 // grid, wbin out of range), so that the caller's array needs no clearing pass
@@ -370,6 +396,34 @@ int launch_roll(gridhip_ctx *ctx, int64_t N, const double2 *in, double2 *out, in
 // the context's cached N x N Z2Z hipFFT plan, bound to its stream; an in-place transform with it
 int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan);
 int fft_exec(gridhip_ctx *ctx, void *plan, double2 *data, bool inverse);
+
+// a transform the caller owns (hipfftPlan2d Z2Z, N x N), binding it to the context's stream, releasing it
+int fft_plan_own(gridhip_ctx *ctx, int64_t N, void **out_plan);
+int fft_plan_bind(gridhip_ctx *ctx, void *plan);
+void fft_plan_drop(void *plan);
+// x[c] /= the maximum kept in maxbits in ordered-bits form (divide_kernel)
+int launch_divide(gridhip_ctx *ctx, int64_t cells, double *x, const unsigned long long *maxbits);
+// the imaging tail (imaging.hip): out = real(ifft_c(make_grid_hermitian(g))), its maximum into *maxbits when given, or
+// (divbits) stored divided by the maximum kept there; h: N x N complex scratch; plan: fft_plan_own's, or the context's
+int image_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits,
+               const unsigned long long *divbits = nullptr, void *plan = nullptr);
+// the w-bin rule on the device (synchronises: min and plane count come back to the host)
+int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t stride, int64_t wstep, int64_t *wbin, int64_t *wmin,
+              int64_t *nplanes);
+// one plane of a w-kernel table, out[Q][Q][S][S]; pad: (npixFF * Q)^2 complex scratch (af, tmp: unused)
+int dev_w_kernel(gridhip_ctx *ctx, double theta, double w, int64_t npixFF, int64_t S, int64_t Q, double2 *out, bool conj,
+                 double2 *pad, double2 *af, double2 *tmp);
+// ---- shared with imager.hip: pieces of predict.hip ---------------------------------------------------------------------
+// f = fft_c(model) (N x N complex); t: N x N complex scratch, used for odd N only; plan as image_tail's
+int model_transform_to(gridhip_ctx *ctx, int64_t N, const double *model, double2 *f, double2 *t, void *plan);
+int launch_simple_degrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double2 *grid, int64_t n, const double *u,
+                         const double *v, int64_t stride, double lam, double2 *out);
+int launch_conj_copy(gridhip_ctx *ctx, int64_t n, const double2 *in, double2 *out);
+int launch_residual(gridhip_ctx *ctx, int64_t n, const double2 *pred, const double2 *sub, double2 *out);
+// A plan that an imager gathers with: the caller clears the predictions itself (in a kernel, so that a cycle can be
+// captured) where the plan would clear them with a memset.  Returns whether they need clearing at all.
+bool plan_caller_clears(gridhip_plan *plan);
+bool aw_plan_caller_clears(gridhip_aw_plan *plan);
 
 // What w_cache_imaging (src/Gridding.hs:399-449) derives from the baselines alone: scaled u, v, the
 // w-bins and one conjugated w-kernel per plane.  do_imaging calls the imaging function twice with the

@@ -1,0 +1,479 @@
+// Imagers: what a major cycle holds (include/gridhip.h, "imagers").  An imager is created once from the baselines and
+// the imaging function and turns (model, vis) into the residual image in one asynchronous call:
+//     image = do_imaging(vis - predict(model)).image
+// Everything that depends on the baselines alone is done at creation: the slice / scale of the strided uvw, the mirror,
+// the uniform weights, the w-bins, the kernel tables (in memory of the imager's own), the binning of BOTH record sets -
+// the un-mirrored one the prediction gathers on and the mirrored one do_imaging scatters on; the two are not mirror
+// images of each other bit for bit (floor(.5 + x), the w-bin rule and findClosest are not odd functions), so neither is
+// derived from the other - and the PSF with its maximum.  A cycle is then
+//     head kernel + forward FFT of the model -> gather (un-mirrored records) -> imager_middle_kernel ->
+//     scatter (mirrored records) -> Hermitian fill + inverse FFT + real part / pmax
+// with no pre-pass, no table build, no histogram, no PSF pass, no allocation, no synchronisation and no memset node.
+// The gather and the scatter are the tile kernels of the plans (plan.hip, awgrid.hip), which lend their records to the
+// launchers; the simple kind has no records and keeps its two coordinate sets instead.
+#include <string.h>
+
+#include <new>
+
+#include "common.h"
+
+namespace gridhip {
+
+// Creation front end: one read of the strided (u, v, w) per visibility.  Writes
+//   p = uvw / lam of the un-mirrored baseline (pu, pv: what predict's gathers bin) and of the mirrored one (mu, mv: what
+//   do_imaging's scatters bin; mirror_uvw, src/Gridding.hs:551-562: v < 0 negates u, v, w) - true divisions, as
+//   scale_kernel's; -(u / lam) and (-u) / lam are the same double, so one division serves both;
+//   the mirror flag as the sign of sw (+-1 here; imager_weight_kernel puts the weight's magnitude on it);
+//   doweight's cell of the mirrored p (:531-535), counted into the histogram;
+//   w of both streams (w_cache: the w-bin rule needs the whole stream's min and max first) or their findClosest bins (aw:
+//   the reference searches with w in wavelengths, :473-474).
+// There is no product or sum here for the compiler to contract; frac_coord_dev switches contraction off itself.
+__global__ void __launch_bounds__(256)
+    imager_front_kernel(int64_t n, const double *__restrict__ u, const double *__restrict__ v, const double *__restrict__ w,
+                        int64_t stride, double lam, int64_t N, int64_t nws, const double *__restrict__ ws,
+                        double *__restrict__ pu, double *__restrict__ pv, double *__restrict__ mu, double *__restrict__ mv,
+                        double *__restrict__ w0, double *__restrict__ w1, int64_t *__restrict__ wb0,
+                        int64_t *__restrict__ wb1, double *__restrict__ sw, int64_t *__restrict__ cell,
+                        unsigned int *__restrict__ cnt)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const double u0 = u[k * stride], v0 = v[k * stride];
+        const bool neg = v0 < 0;
+        const double qu = u0 / lam, qv = v0 / lam;
+        const double ru = neg ? -qu : qu, rv = neg ? -qv : qv;
+        pu[k] = qu;
+        pv[k] = qv;
+        mu[k] = ru;
+        mv[k] = rv;
+        sw[k] = neg ? -1.0 : 1.0;
+        if (w) {
+            const double x0 = w[k * stride], x1 = neg ? -x0 : x0;
+            if (w0) {
+                w0[k] = x0;
+                w1[k] = x1;
+            }
+            if (wb0) {
+                wb0[k] = closest_index(nws, ws, x0);
+                wb1[k] = closest_index(nws, ws, x1);
+            }
+        }
+        const int64_t c = weight_cell(N, ru, rv);
+        cell[k] = c;
+        if (c >= 0) atomicAdd(&cnt[c], 1u);
+    }
+}
+
+// |sw| = doweight's ones / count (weight_apply_kernel's division; a visibility outside the grid keeps 1), the sign stays
+__global__ void __launch_bounds__(256)
+    imager_weight_kernel(int64_t n, const int64_t *__restrict__ cell, const unsigned int *__restrict__ cnt,
+                         double *__restrict__ sw)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        double a = 1.0;
+        const int64_t c = cell[k];
+        if (c >= 0) a /= (double)cnt[c];
+        sw[k] = copysign(a, sw[k]);
+    }
+}
+
+// the PSF pass's input (src/Gridding.hs:541): the weights as complex numbers
+__global__ void __launch_bounds__(256)
+    imager_wt_kernel(int64_t n, const double *__restrict__ sw, double2 *__restrict__ out)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x)
+        out[k] = make_double2(fabs(sw[k]), 0.0);
+}
+
+// nd doubles of zeros, 16 bytes per lane (a is 16-byte aligned; an odd last double goes alone): the grid before the
+// scatter, the predictions where the gather does not write them all, the image of an imager without visibilities
+__global__ void __launch_bounds__(256) imager_zero_kernel(int64_t nd, double *__restrict__ a)
+{
+    const int64_t pairs = nd / 2, k0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t k = k0; k < pairs; k += (int64_t)gridDim.x * blockDim.x)
+        reinterpret_cast<double2 *>(a)[k] = make_double2(0.0, 0.0);
+    if (k0 == 0 && (nd & 1)) a[nd - 1] = 0.0;
+}
+
+// Cycle middle, the one pass over the visibilities between the gather and the scatter (residual_kernel, a copy,
+// mirror_kernel and cmul_real_kernel in the two calls an imager replaces, in their order): r = vis - pred (SUB) or vis;
+// vis_res = r when asked; then conj where mirrored, then re and im times the real weight, into the gridder's input -
+// which is the prediction's own block: element k is read before it is written, by the same lane.
+// vis_res may be vis (an in-place residual): no __restrict__ on either.
+template <bool SUB>
+__global__ void __launch_bounds__(256)
+    imager_middle_kernel(int64_t n, const double2 *vis, double2 *pred, const double *__restrict__ sw, double2 *vis_res)
+{
+#pragma clang fp contract(off)
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        double2 r = vis[k];
+        if (SUB) {
+            const double2 p = pred[k];
+            r = make_double2(r.x - p.x, r.y - p.y);
+        }
+        if (vis_res) vis_res[k] = r;
+        const double s = sw[k];
+        const double a = fabs(s);
+        if (signbit(s)) r.y = -r.y;
+        pred[k] = make_double2(a * r.x, a * r.y);
+    }
+}
+
+}  // namespace gridhip
+
+using namespace gridhip;
+
+struct gridhip_imager {
+    gridhip_ctx *ctx = nullptr;
+    int kind = 0;  // 0 simple, 1 conv, 2 w_cache, 3 aw
+    int64_t N = 0, n = 0;
+    std::vector<void *> owned;  // every device block below
+    double *sw = nullptr;       // [n] weight, negative where the baseline is mirrored
+    double2 *pred = nullptr;    // [n] the prediction, then the gridder's input
+    double2 *g = nullptr, *f = nullptr, *t = nullptr;  // N x N complex: the scatter's grid; fft_c(model), then the tail's
+                                                       // Hermitian grid; the forward transform's scratch (odd N only)
+    double *psf = nullptr;                             // N x N, normalised
+    unsigned long long *pmaxbits = nullptr;            // the PSF's maximum as divide_kernel reads it
+    double pmax = 0.0;
+    void *fft = nullptr;  // the imager's own N x N transform
+    // simple: p of the un-mirrored and the mirrored stream
+    double *pu = nullptr, *pv = nullptr, *mu = nullptr, *mv = nullptr;
+    // conv, w_cache: the two record sets and their kernel tables (gather: conj kv / the w_kernels; scatter: kv / their
+    // conjugates, on the mirrored stream's planes)
+    gridhip_plan *gather = nullptr, *scatter = nullptr;
+    double2 *ktab_g = nullptr, *ktab_s = nullptr;
+    // aw: the same as aw plans, which hold their batches' kernel tables themselves
+    gridhip_aw_plan *aw_gather = nullptr, *aw_scatter = nullptr;
+    bool clear_pred = false;  // the gather does not write every prediction: they start from zero
+};
+
+namespace {
+
+template <typename T>
+int own(gridhip_imager *im, T **p, size_t bytes)
+{
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return fail(im->ctx, GRIDHIP_ENOMEM, "imager: %zu bytes", bytes);
+    im->owned.push_back(q);
+    *p = (T *)q;
+    return GRIDHIP_OK;
+}
+
+// n complex numbers (2 n doubles) of zeros
+int zero(gridhip_ctx *ctx, int64_t n, double2 *a)
+{
+    hipLaunchKernelGGL(imager_zero_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, 2 * n, (double *)a);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+// pred = the prediction of `model` on the un-mirrored baselines
+int gather(gridhip_imager *im, const double *model)
+{
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(model_transform_to(ctx, im->N, model, im->f, im->t, im->fft));
+    if (im->clear_pred) GH_CHECK(zero(ctx, im->n, im->pred));
+    switch (im->kind) {
+        case 0:  // (the kept p is u / lam already: a division by 1 is exact)
+            return launch_simple_degrid(ctx, im->N, im->N, im->f, im->n, im->pu, im->pv, 1, 1.0, im->pred);
+        case 3: return gridhip_aw_plan_degrid_dev(im->aw_gather, (const double *)im->f, (double *)im->pred);
+        default:
+            return gridhip_plan_degrid_dev(im->gather, (const double *)im->ktab_g, (const double *)im->f,
+                                           (double *)im->pred);
+    }
+}
+
+// g = the imaging function's grid of the values in pred, on the mirrored baselines
+int scatter(gridhip_imager *im)
+{
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(zero(ctx, im->N * im->N, im->g));
+    switch (im->kind) {
+        case 0:
+            return launch_simple_grid(ctx, im->N, im->N, (double *)im->g, im->n, im->mu, im->mv, 1,
+                                      (const double *)im->pred);
+        case 3: return gridhip_aw_plan_grid_dev(im->aw_scatter, (const double *)im->pred, (double *)im->g);
+        default:
+            return gridhip_plan_grid_dev(im->scatter, (const double *)im->ktab_s, (const double *)im->pred,
+                                         (double *)im->g);
+    }
+}
+
+struct Kernels {  // conv: kv; w_cache: the generator's options; aw: the tables and the antennas
+    int64_t wstep = 0, Q = 0, npixFF = 0, gh = 0, gw = 0;
+    const double *kv = nullptr;
+    double theta = 0.0;
+    int64_t W = 0, S = 0, A = 0;
+    const double *wkerns = nullptr, *wvals = nullptr, *akerns = nullptr;
+    const int64_t *a1 = nullptr, *a2 = nullptr;
+};
+
+// [nplanes][Q][Q][S][S] w_kernels of the planes w = i * wstep + wmin (src/Gridding.hs:434-448), conjugated or not
+int build_planes(gridhip_ctx *ctx, const Kernels &k, int64_t wmin, int64_t nplanes, double2 *table, bool conj)
+{
+    const int64_t na = k.npixFF * k.Q;
+    DevBuf pad;
+    GH_CHECK(pad.alloc(ctx, (size_t)na * na * 16));
+    for (int64_t i = 0; i < nplanes; ++i)
+        GH_CHECK(dev_w_kernel(ctx, k.theta, (double)(i * k.wstep + wmin), k.npixFF, k.gh, k.Q,
+                              table + i * k.Q * k.Q * k.gh * k.gh, conj, pad.as<double2>(), nullptr, nullptr));
+    return GRIDHIP_OK;
+}
+
+double max_of_bits(unsigned long long mb)
+{
+    mb = (mb & 0x8000000000000000ULL) ? (mb & 0x7fffffffffffffffULL) : ~mb;
+    double m;
+    memcpy(&m, &mb, 8);
+    return m;
+}
+
+// Everything creation does, into *im (the caller destroys it on failure).  Arguments are checked by the callers.
+int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, const double *v, const double *w,
+         int64_t stride)
+{
+    gridhip_ctx *ctx = im->ctx;
+    const int64_t N = im->N, n = im->n;
+    const size_t cells = (size_t)N * N;
+    GH_CHECK(own(im, &im->psf, cells * 8));
+    GH_CHECK(own(im, &im->pmaxbits, 8));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));  // nothing dropped so far
+    if (n == 0) {  // a valid imager: no PSF, and every image is zero
+        GH_CHECK_HIP(ctx, hipMemsetAsync(im->psf, 0, cells * 8, ctx->stream));
+        GH_CHECK_HIP(ctx, hipMemsetAsync(im->pmaxbits, 0, 8, ctx->stream));
+        return sync(ctx);
+    }
+    GH_CHECK(own(im, &im->sw, (size_t)n * 8));
+    GH_CHECK(own(im, &im->pred, (size_t)n * 16));
+    GH_CHECK(own(im, &im->g, cells * 16));
+    GH_CHECK(own(im, &im->f, cells * 16));
+    if (N % 2 != 0) GH_CHECK(own(im, &im->t, cells * 16));
+    GH_CHECK(fft_plan_own(ctx, N, &im->fft));
+
+    // ---- front end: both coordinate sets, the mirror flags, the weights
+    DevBuf tp[4], tw[2], tb[2], cell, cnt;
+    double *p[4];
+    for (int i = 0; i < 4; ++i) {
+        if (im->kind == 0) {
+            GH_CHECK(own(im, &p[i], (size_t)n * 8));
+        } else {
+            GH_CHECK(tp[i].alloc(ctx, (size_t)n * 8));
+            p[i] = tp[i].as<double>();
+        }
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (im->kind == 2) GH_CHECK(tw[i].alloc(ctx, (size_t)n * 8));
+        if (im->kind >= 2) GH_CHECK(tb[i].alloc(ctx, (size_t)n * 8));
+    }
+    GH_CHECK(cell.alloc(ctx, (size_t)n * 8));
+    GH_CHECK(cnt.alloc(ctx, cells * 4));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(cnt.p, 0, cells * 4, ctx->stream));
+    hipLaunchKernelGGL(imager_front_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, u, v,
+                       im->kind >= 2 ? w : (const double *)nullptr, stride, lam, N, k.W, k.wvals, p[0], p[1], p[2], p[3],
+                       tw[0].as<double>(), tw[1].as<double>(), im->kind == 3 ? tb[0].as<int64_t>() : (int64_t *)nullptr,
+                       im->kind == 3 ? tb[1].as<int64_t>() : (int64_t *)nullptr, im->sw, cell.as<int64_t>(),
+                       cnt.as<unsigned int>());
+    hipLaunchKernelGGL(imager_weight_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, cell.as<int64_t>(),
+                       cnt.as<unsigned int>(), im->sw);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+
+    // ---- kernel tables and the two record sets: the gather's first, so that gridhip_last_dropped and
+    // gridhip_aw_last_stats report the mirrored stream, as do_imaging does
+    if (im->kind == 0) {
+        im->pu = p[0], im->pv = p[1], im->mu = p[2], im->mv = p[3];
+    } else if (im->kind == 1) {
+        const size_t el = (size_t)k.Q * k.Q * k.gh * k.gw;
+        GH_CHECK(own(im, &im->ktab_g, el * 16));
+        GH_CHECK(own(im, &im->ktab_s, el * 16));
+        GH_CHECK(launch_conj_copy(ctx, (int64_t)el, (const double2 *)k.kv, im->ktab_g));
+        GH_CHECK(copy_in(ctx, im->ktab_s, k.kv, el * 16, true));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, 1, k.Q, k.gh, k.gw, p[0], p[1], 1, nullptr, &im->gather));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, 1, k.Q, k.gh, k.gw, p[2], p[3], 1, nullptr, &im->scatter));
+    } else if (im->kind == 2) {
+        // the w-bin rule on each stream: its own minimum and plane count, hence a table of its own.  (The gather's
+        // planes are the w_kernels, the scatter's their conjugates, :441: two tables even where the ranges agree.)
+        int64_t wmin[2] = {0, 0}, np[2] = {0, 0};
+        for (int i = 0; i < 2; ++i) {
+            GH_CHECK(dev_wbins(ctx, n, tw[i].as<double>(), 1, k.wstep, tb[i].as<int64_t>(), &wmin[i], &np[i]));
+            if (np[i] < 1 || np[i] > 65536) return fail(ctx, GRIDHIP_EUNSUPPORTED, "%lld w-planes", (long long)np[i]);
+        }
+        const size_t pl = (size_t)k.Q * k.Q * k.gh * k.gh;
+        GH_CHECK(own(im, &im->ktab_g, np[0] * pl * 16));
+        GH_CHECK(own(im, &im->ktab_s, np[1] * pl * 16));
+        GH_CHECK(build_planes(ctx, k, wmin[0], np[0], im->ktab_g, false));
+        GH_CHECK(build_planes(ctx, k, wmin[1], np[1], im->ktab_s, true));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[0], k.Q, k.gh, k.gh, p[0], p[1], 1, tb[0].as<int64_t>(),
+                                         &im->gather));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[1], k.Q, k.gh, k.gh, p[2], p[3], 1, tb[1].as<int64_t>(),
+                                         &im->scatter));
+    } else {
+        // the gather's kernels are conj(aw_kernel_fn2(conj wk, conj ak)) (predict_aw); the aw plans keep what they build
+        const size_t wel = (size_t)k.W * k.Q * k.Q * k.S * k.S, ael = (size_t)k.A * k.S * k.S;
+        DevBuf cwk, cak;
+        GH_CHECK(cwk.alloc(ctx, wel * 16));
+        GH_CHECK(cak.alloc(ctx, ael * 16));
+        GH_CHECK(launch_conj_copy(ctx, (int64_t)wel, (const double2 *)k.wkerns, cwk.as<double2>()));
+        GH_CHECK(launch_conj_copy(ctx, (int64_t)ael, (const double2 *)k.akerns, cak.as<double2>()));
+        GH_CHECK(gridhip_aw_plan_create_dev(ctx, N, N, n, k.W, k.Q, k.S, k.A, cwk.as<double>(), cak.as<double>(), p[0],
+                                            p[1], 1, tb[0].as<int64_t>(), k.a1, k.a2, &im->aw_gather));
+        int64_t tables = ctx->aw_tables_built;
+        GH_CHECK(gridhip_aw_plan_create_dev(ctx, N, N, n, k.W, k.Q, k.S, k.A, k.wkerns, k.akerns, p[2], p[3], 1,
+                                            tb[1].as<int64_t>(), k.a1, k.a2, &im->aw_scatter));
+        ctx->aw_tables_built += tables;
+    }
+    if (im->gather) im->clear_pred = plan_caller_clears(im->gather);
+    if (im->aw_gather) im->clear_pred = aw_plan_caller_clears(im->aw_gather);
+    const int64_t tables = ctx->aw_tables_built;
+
+    // ---- the PSF (src/Gridding.hs:541-548) and its maximum
+    hipLaunchKernelGGL(imager_wt_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, im->sw, im->pred);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    GH_CHECK(scatter(im));
+    GH_CHECK(image_tail(ctx, N, im->g, im->f, im->psf, im->pmaxbits, nullptr, im->fft));
+    GH_CHECK(launch_divide(ctx, (int64_t)cells, im->psf, im->pmaxbits));
+    // one gather of an empty grid: a support the gather cannot hold is refused here, not in the first cycle, and the
+    // launchers' scratch has its size before a cycle is captured
+    GH_CHECK(zero(ctx, (int64_t)cells, im->f));
+    if (im->clear_pred) GH_CHECK(zero(ctx, n, im->pred));
+    if (im->kind == 0)
+        GH_CHECK(launch_simple_degrid(ctx, N, N, im->f, n, im->pu, im->pv, 1, 1.0, im->pred));
+    else if (im->kind == 3)
+        GH_CHECK(gridhip_aw_plan_degrid_dev(im->aw_gather, (const double *)im->f, (double *)im->pred));
+    else
+        GH_CHECK(gridhip_plan_degrid_dev(im->gather, (const double *)im->ktab_g, (const double *)im->f, (double *)im->pred));
+    ctx->aw_tables_built = tables;  // (the passes above reset it: it reports the creation)
+    unsigned long long mb = 0;
+    GH_CHECK(d2h(ctx, &mb, im->pmaxbits, 8));
+    GH_CHECK(sync(ctx));  // the inputs may be freed or overwritten once this returns
+    im->pmax = max_of_bits(mb);
+    return GRIDHIP_OK;
+}
+
+int create(gridhip_ctx *ctx, int kind, int64_t N, int64_t n, const Kernels &k, double lam, const double *u,
+           const double *v, const double *w, int64_t stride, gridhip_imager **out)
+{
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    gridhip_imager *im = new (std::nothrow) gridhip_imager();
+    if (!im) return GRIDHIP_ENOMEM;
+    im->ctx = ctx;
+    im->kind = kind;
+    im->N = N;
+    im->n = n;
+    const int rc = make(im, k, lam, u, v, w, stride);
+    if (rc != GRIDHIP_OK) {
+        const std::string why = ctx->err;  // (destroy synchronises: keep the message of the failure)
+        gridhip_imager_destroy(im);
+        ctx->err = why;
+        return rc;
+    }
+    *out = im;
+    return GRIDHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gridhip_imager_create_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
+                              int64_t gw, const double *kv, double theta, int64_t lam, int64_t n, const double *u,
+                              const double *v, const double *w, int64_t uv_stride, gridhip_imager **imager)
+{
+    if (imager) *imager = nullptr;
+    if (!ctx) return GRIDHIP_EINVAL;
+    // predict_check's rules (predict.hip), without a model or an output
+    const int64_t N = gridhip_image_size(theta, lam);
+    if (kind == 2 && wstep <= 0) wstep = 2000;  // (w_cache_imaging's default, :412)
+    const bool kinds = kind == 0 || (kind == 1 && kv && Q > 0 && gh > 0 && gw > 0) ||
+                       (kind == 2 && Q > 0 && npixFF > 0 && gh > 0 && gh <= npixFF);
+    if (!imager || N <= 0 || !kinds || n < 0 || uv_stride < 1 || (n > 0 && (!u || !v || (kind == 2 && !w))))
+        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    if (n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per imager");
+    Kernels k;
+    k.wstep = wstep, k.Q = Q, k.npixFF = npixFF, k.gh = gh, k.gw = kind == 2 ? gh : gw, k.kv = kv, k.theta = theta;
+    return create(ctx, kind, N, n, k, (double)lam, u, v, w, uv_stride, imager);
+}
+
+int gridhip_imager_create_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
+                                 int64_t A, const double *wkerns, const double *wvals, const double *akerns,
+                                 int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
+                                 const int64_t *a1, const int64_t *a2, gridhip_imager **imager)
+{
+    if (imager) *imager = nullptr;
+    if (!ctx) return GRIDHIP_EINVAL;
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, nullptr};
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N, false));
+    if (!imager) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    // (the aw plans' limits, checked before anything is allocated)
+    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
+        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
+    Kernels k;
+    k.Q = Q, k.W = W, k.S = S, k.A = A, k.wkerns = wkerns, k.wvals = wvals, k.akerns = akerns, k.a1 = a1, k.a2 = a2;
+    k.theta = theta;
+    return create(ctx, 3, N, n, k, (double)lam, u, v, w, uv_stride, imager);
+}
+
+int gridhip_imager_psf_dev(gridhip_imager *im, double *psf, double *pmax)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (psf) GH_CHECK(copy_out(ctx, psf, im->psf, (size_t)im->N * im->N * 8, true));
+    if (pmax) *pmax = im->pmax;
+    return GRIDHIP_OK;
+}
+
+int gridhip_imager_cycle_dev(gridhip_imager *im, const double *model, const double *vis, double *image, double *vis_res)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    const int64_t n = im->n, cells = im->N * im->N;
+    if (!image || (n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (n == 0) {
+        hipLaunchKernelGGL(imager_zero_kernel, grid_for(ctx, cells / 2), dim3(256), 0, ctx->stream, cells, image);
+        GH_CHECK_HIP(ctx, hipGetLastError());
+        return GRIDHIP_OK;
+    }
+    mark(ctx, 0);
+    if (model) GH_CHECK(gather(im, model));
+    if (model)
+        hipLaunchKernelGGL(imager_middle_kernel<true>, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, (const double2 *)vis,
+                           im->pred, im->sw, (double2 *)vis_res);
+    else
+        hipLaunchKernelGGL(imager_middle_kernel<false>, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, (const double2 *)vis,
+                           im->pred, im->sw, (double2 *)vis_res);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    mark(ctx, 1);
+    GH_CHECK(scatter(im));
+    GH_CHECK(image_tail(ctx, im->N, im->g, im->f, image, nullptr, im->pmaxbits, im->fft));
+    mark(ctx, 2);
+    return GRIDHIP_OK;
+}
+
+int gridhip_imager_predict_dev(gridhip_imager *im, const double *model, const double *vis_sub, double *vis_out)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (!model || (im->n > 0 && !vis_out)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (im->n == 0) return GRIDHIP_OK;
+    GH_CHECK(gather(im, model));
+    return launch_residual(ctx, im->n, im->pred, (const double2 *)vis_sub, (double2 *)vis_out);
+}
+
+int gridhip_imager_destroy(gridhip_imager *im)
+{
+    if (!im) return GRIDHIP_OK;
+    (void)hipSetDevice(im->ctx->device);
+    (void)hipDeviceSynchronize();
+    gridhip_plan_destroy(im->gather);
+    gridhip_plan_destroy(im->scatter);
+    gridhip_aw_plan_destroy(im->aw_gather);
+    gridhip_aw_plan_destroy(im->aw_scatter);
+    fft_plan_drop(im->fft);
+    for (void *p : im->owned) (void)hipFree(p);
+    delete im;
+    return GRIDHIP_OK;
+}
+
+}  // extern "C"

@@ -67,21 +67,7 @@ __global__ void wbin_finish_kernel(int64_t n, int64_t *__restrict__ rw, int64_t 
         rw[k] = (rw[k] - mn) / wstep;  // non-negative: `div` and C division agree
 }
 
-// findClosest, src/Gridding.hs:895-907 (hi clamped to len-1 as the host twin does, ImageDataset.hs:150-168)
-__device__ __forceinline__ int64_t closest_index(int64_t nws, const double *__restrict__ ws, double x)
-{
-    int64_t lo = 0, hi = nws;
-    while ((hi - lo) / 2 >= 1) {
-        const int64_t mid = (hi + lo) / 2;
-        if (x > ws[mid])
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const int64_t hc = hi > nws - 1 ? nws - 1 : hi;
-    return fabs(x - ws[lo]) < fabs(x - ws[hc]) ? lo : hc;
-}
-
+// (closest_index: common.h)
 __global__ void find_closest_kernel(int64_t nws, const double *__restrict__ ws, int64_t n,
                                     const double *__restrict__ w, int64_t stride, int64_t *__restrict__ out)
 {
@@ -103,17 +89,7 @@ __global__ void mirror_kernel(int64_t n, double *__restrict__ u, double *__restr
     }
 }
 
-// doweight, src/Gridding.hs:564-583: frac_coords (N,N) 1 p -> cell histogram -> v / count
-__device__ __forceinline__ int64_t weight_cell(int64_t N, double pu, double pv)
-{
-    int64_t x, y;
-    int32_t f;
-    frac_coord_dev(N, 1, pu, &x, &f);
-    frac_coord_dev(N, 1, pv, &y, &f);
-    if (!(pu == pu) || !(pv == pv) || x < 0 || y < 0 || x >= N || y >= N) return -1;
-    return y * N + x;
-}
-
+// doweight, src/Gridding.hs:564-583: frac_coords (N,N) 1 p -> cell histogram -> v / count  (weight_cell: common.h)
 __global__ void weight_hist_kernel(int64_t N, int64_t n, const double *__restrict__ pu, const double *__restrict__ pv,
                                    unsigned int *__restrict__ cnt)
 {
@@ -178,10 +154,20 @@ __global__ void roll_kernel(int64_t N, const double2 *__restrict__ in, double2 *
 // N > 0: `in` is a transform's raw N x N output and the cell read for c = (y, x) is in[(y+s) mod N][(x+s) mod N] * scale -
 // the shift2D and the 1 / N^2 the centred inverse transform ends with, applied while the real part is taken instead
 // of in a pass of their own (the same multiplication: bit-identical).
+// DIV (an imager's cycle: the PSF's maximum is known beforehand): the real part is stored divided by the maximum that
+// divbits holds in divide_kernel's form - that kernel's division, without its pass - and no maximum is taken.
+template <bool DIV>
 __global__ void real_max_kernel(int64_t cells, const double2 *__restrict__ in, double *__restrict__ real_out,
-                                unsigned long long *__restrict__ maxbits, int64_t N, int64_t s, double scale)
+                                unsigned long long *__restrict__ maxbits, int64_t N, int64_t s, double scale,
+                                const unsigned long long *__restrict__ divbits)
 {
     double m = -INFINITY;
+    double dm = 1.0;
+    if (DIV) {
+        unsigned long long b = *divbits;
+        b = (b & 0x8000000000000000ULL) ? (b & 0x7fffffffffffffffULL) : ~b;
+        dm = __longlong_as_double((long long)b);
+    }
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (int64_t)gridDim.x * blockDim.x) {
         double r;
         if (N > 0) {
@@ -193,9 +179,14 @@ __global__ void real_max_kernel(int64_t cells, const double2 *__restrict__ in, d
             r = in[y * N + x].x * scale;
         } else
             r = in[c].x;
+        if (DIV) {
+            real_out[c] = r / dm;
+            continue;
+        }
         if (real_out) real_out[c] = r;
         m = r > m ? r : m;
     }
+    if (DIV) return;
     for (int off = 32; off > 0; off >>= 1) {
         const double o = __shfl_xor(m, off, 64);
         m = o > m ? o : m;
@@ -428,6 +419,30 @@ int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan)
     return GRIDHIP_OK;
 }
 
+// a transform of the caller's own (an imager keeps one: the context's four cached sizes come and go with other calls)
+int fft_plan_own(gridhip_ctx *ctx, int64_t N, void **out_plan)
+{
+    GH_CHECK(load_hipfft(ctx));
+    if (N > 0x7fffffff) return fail(ctx, GRIDHIP_EUNSUPPORTED, "fft size");
+    *out_plan = nullptr;
+    if (int rc = g_fft.plan2d(out_plan, (int)N, (int)N, 0x69 /* HIPFFT_Z2Z */)) {
+        *out_plan = nullptr;
+        return fail(ctx, GRIDHIP_EHIP, "hipfftPlan2d(%lld) failed: %d", (long long)N, rc);
+    }
+    return GRIDHIP_OK;
+}
+
+int fft_plan_bind(gridhip_ctx *ctx, void *plan)
+{
+    if (int rc = g_fft.setstream(plan, ctx->stream)) return fail(ctx, GRIDHIP_EHIP, "hipfftSetStream: %d", rc);
+    return GRIDHIP_OK;
+}
+
+void fft_plan_drop(void *plan)
+{
+    if (plan && g_fft.h) g_fft.destroy(plan);
+}
+
 int fft_exec(gridhip_ctx *ctx, void *plan, double2 *data, bool inverse)
 {
     if (int rc = g_fft.exec(plan, data, data, inverse ? 1 /* HIPFFT_BACKWARD */ : -1 /* HIPFFT_FORWARD */))
@@ -438,6 +453,13 @@ int fft_exec(gridhip_ctx *ctx, void *plan, double2 *data, bool inverse)
 int launch_scale(gridhip_ctx *ctx, int64_t n, const double *x, int64_t stride, double lam, double *out)
 {
     if (n > 0) hipLaunchKernelGGL(scale_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, x, stride, lam, out);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int launch_divide(gridhip_ctx *ctx, int64_t cells, double *x, const unsigned long long *maxbits)
+{
+    hipLaunchKernelGGL(divide_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, cells, x, maxbits);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }
@@ -499,7 +521,7 @@ static int64_t haskell_round(double x) { return (int64_t)nearbyint(x); }
 
 // w-bins on the device; returns min and plane count to the host (the reference does the same
 // round-trip with a nested CPU.run, :430)
-static int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t stride, int64_t wstep, int64_t *wbin,
+int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t stride, int64_t wstep, int64_t *wbin,
                      int64_t *wmin, int64_t *nplanes)
 {
     DevBuf mm;
@@ -523,18 +545,27 @@ static int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t strid
 // out = real(ifft(make_grid_hermitian(g))) (N x N doubles), its maximum into *maxbits (ordered bits) when given: the
 // imaging tail (src/Gridding.hs:539,542).  The centred inverse transform (shift2D . ifft2D . ishift2D, dev_fft2c) has its
 // two rolls folded into the Hermitian fill's stores and the real part's loads: four passes over the N^2 grid fewer per
-// call.  h: N x N complex scratch.
-static int image_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits)
+// call.  h: N x N complex scratch.  divbits (an imager's cycle; maxbits is then null): out is stored divided by the
+// maximum kept there.  plan: the caller's own transform (fft_plan_own) instead of the context's cached one.
+int image_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits,
+               const unsigned long long *divbits, void *plan)
 {
     static const unsigned long long neg_inf_bits = ~0xfff0000000000000ULL;  // ordered image of -inf
     const size_t cells = (size_t)N * N;
-    void *plan = nullptr;
-    GH_CHECK(fft_plan_for(ctx, N, &plan));
+    if (plan)
+        GH_CHECK(fft_plan_bind(ctx, plan));
+    else
+        GH_CHECK(fft_plan_for(ctx, N, &plan));
     hipLaunchKernelGGL(hermitian_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, g, h, N / 2);
     if (int rc = g_fft.exec(plan, h, h, 1 /* HIPFFT_BACKWARD */)) return fail(ctx, GRIDHIP_EHIP, "hipfftExecZ2Z: %d", rc);
     if (maxbits) GH_CHECK(h2d(ctx, maxbits, &neg_inf_bits, 8));
-    hipLaunchKernelGGL(real_max_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells, h, out,
-                       maxbits, N, (N + 1) / 2, 1.0 / ((double)N * (double)N));
+    if (divbits)
+        hipLaunchKernelGGL(real_max_kernel<true>, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells,
+                           h, out, (unsigned long long *)nullptr, N, (N + 1) / 2, 1.0 / ((double)N * (double)N), divbits);
+    else
+        hipLaunchKernelGGL(real_max_kernel<false>, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, (int64_t)cells,
+                           h, out, maxbits, N, (N + 1) / 2, 1.0 / ((double)N * (double)N),
+                           (const unsigned long long *)nullptr);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }

@@ -19,6 +19,8 @@ struct gridhip_plan {
     // passes of one call - no hipMalloc, no hipFree with its device-wide synchronisation); valid until the context's
     // next gridding call that is not this plan's
     bool borrowed = false;
+    // degrid leaves the clearing of its output to the caller (plan_caller_clears: an imager clears in a kernel)
+    bool caller_clears = false;
 };
 
 using namespace gridhip;
@@ -51,6 +53,12 @@ int plan_create_borrowed(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int
                          const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, gridhip_plan **out)
 {
     return plan_create(ctx, H, Wd, n, W, Q, gh, gw, u, v, uv_stride, wbin, out, true);
+}
+
+bool plan_caller_clears(gridhip_plan *plan)
+{
+    plan->caller_clears = true;
+    return plan->n > 0 && !plan->all_binned;
 }
 }  // namespace gridhip
 
@@ -153,7 +161,7 @@ int gridhip_plan_degrid_dev(gridhip_plan *p, const double *gcf, const double *gr
     if (!gcf || !grid || (p->n > 0 && !vis_out)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (p->n == 0) return GRIDHIP_OK;
-    if (!p->all_binned) GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out, 0, (size_t)p->n * 16, ctx->stream));
+    if (!p->all_binned && !p->caller_clears) GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out, 0, (size_t)p->n * 16, ctx->stream));
     const double *tk = gcf;
     GH_CHECK(tile_kernels(ctx, p->p, gcf, &tk));
     Lend lend(p);

@@ -77,6 +77,47 @@ __global__ void __launch_bounds__(256) residual_kernel(int64_t n, const double2 
     }
 }
 
+// F = fft_c(model) into f; t: scratch for odd N (unused for even N); plan: the caller's own transform, or the context's
+int model_transform_to(gridhip_ctx *ctx, int64_t N, const double *model, double2 *f, double2 *t, void *plan)
+{
+    const size_t cells = (size_t)N * N;
+    const bool even = N % 2 == 0;
+    if (plan)
+        GH_CHECK(fft_plan_bind(ctx, plan));
+    else
+        GH_CHECK(fft_plan_for(ctx, N, &plan));
+    double2 *in = even ? f : t;
+    hipLaunchKernelGGL(predict_head_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, model, in, N / 2,
+                       even ? 1 : 0);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    GH_CHECK(fft_exec(ctx, plan, in, false));
+    if (!even) GH_CHECK(launch_roll(ctx, N, in, f, (N + 1) / 2, 1.0));
+    return GRIDHIP_OK;
+}
+
+int launch_simple_degrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double2 *grid, int64_t n, const double *u,
+                         const double *v, int64_t stride, double lam, double2 *out)
+{
+    hipLaunchKernelGGL(simple_degrid_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, H, Wd, grid, n, u, v, stride, lam,
+                       out);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int launch_conj_copy(gridhip_ctx *ctx, int64_t n, const double2 *in, double2 *out)
+{
+    hipLaunchKernelGGL(conj_copy_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, in, out);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int launch_residual(gridhip_ctx *ctx, int64_t n, const double2 *pred, const double2 *sub, double2 *out)
+{
+    hipLaunchKernelGGL(residual_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, pred, sub, out);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
 namespace {
 
 // the conjugate of an n-element complex table, in a block of the pool
@@ -94,18 +135,9 @@ int conj_copy(gridhip_ctx *ctx, DevBuf &b, int64_t n, const double *in, const do
 int model_transform(gridhip_ctx *ctx, int64_t N, const double *model, DevBuf &f, DevBuf &t)
 {
     const size_t cells = (size_t)N * N;
-    const bool even = N % 2 == 0;
-    void *plan = nullptr;
-    GH_CHECK(fft_plan_for(ctx, N, &plan));
     GH_CHECK(f.alloc(ctx, cells * 16));
-    if (!even) GH_CHECK(t.alloc(ctx, cells * 16));
-    double2 *in = even ? f.as<double2>() : t.as<double2>();
-    hipLaunchKernelGGL(predict_head_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, model, in, N / 2,
-                       even ? 1 : 0);
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    GH_CHECK(fft_exec(ctx, plan, in, false));
-    if (!even) GH_CHECK(launch_roll(ctx, N, in, f.as<double2>(), (N + 1) / 2, 1.0));
-    return GRIDHIP_OK;
+    if (N % 2 != 0) GH_CHECK(t.alloc(ctx, cells * 16));
+    return model_transform_to(ctx, N, model, f.as<double2>(), t.as<double2>(), nullptr);
 }
 
 struct PredictArgs {

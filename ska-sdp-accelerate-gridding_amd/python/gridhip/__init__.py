@@ -615,6 +615,43 @@ class Context:
         return out
 
 
+    def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None):
+        """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
+        and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
+        (gridhip_imager): mirror, weights, w-bins, kernel tables, both binnings and the PSF are made here.  Returns an
+        Imager whose cycle(vis, model) is do_imaging(predict(model, vis_sub=vis))'s image in one asynchronous call.  Every
+        argument may be freed or changed afterwards."""
+        import torch
+        cv = lambda t, dt: t if (t.dtype == dt and t.is_contiguous()) else t.to(dt).contiguous()
+        u, v, w, st = self._uvw_dev(uvw)
+        n = int(u.shape[0])
+        N = self.image_size(theta, lam)
+        self._use_torch_stream()
+        h = C.c_void_p()
+        if imgfn[0] == "aw":
+            wk, wv, ak = cv(imgfn[1], torch.complex128), cv(imgfn[2], torch.float64), cv(imgfn[3], torch.complex128)
+            a1, a2 = cv(a1, torch.int64), cv(a2, torch.int64)
+            W, Q, _, S, _ = wk.shape
+            self._check(self._lib.gridhip_imager_create_aw_dev(
+                self._h, float(theta), int(lam), W, Q, S, ak.shape[0], self._ptr(wk), self._ptr(wv), self._ptr(ak), n,
+                self._ptr(u), self._ptr(v), self._ptr(w), st, self._ptr(a1), self._ptr(a2), C.byref(h)))
+        else:
+            kind, wstep, Q, npixFF, gh, gw, kv = 0, 0, 0, 0, 0, 0, None
+            if imgfn[0] == "conv":
+                kv = cv(imgfn[1], torch.complex128)
+                kind, (Q, _, gh, gw) = 1, kv.shape
+            elif imgfn[0] == "w_cache":
+                ko = imgfn[1]
+                kind, wstep, Q, npixFF, gh = 2, int(ko.get("wstep") or 2000), int(ko["qpx"]), int(ko["npixFF"]), int(ko["npixKern"])
+                gw = gh
+            elif imgfn[0] != "simple":
+                raise ValueError("unknown imaging function")
+            self._check(self._lib.gridhip_imager_create_dev(
+                self._h, kind, wstep, Q, npixFF, gh, gw, self._ptr(kv), float(theta), int(lam), n, self._ptr(u),
+                self._ptr(v), self._ptr(w), st, C.byref(h)))
+        return Imager(self, h, n, N, u.device)
+
+
 class Plan:
     """Baselines binned once (gridhip_plan); grid()/degrid() run the tile kernel only."""
 
@@ -686,6 +723,90 @@ class AwPlan:
     def close(self):
         if self._h:
             self.ctx._lib.gridhip_aw_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Imager:
+    """The baselines of a major cycle bound once (gridhip_imager): cycle() is predict + do_imaging without anything that
+    depends on the baselines alone; psf and pmax were computed at creation."""
+
+    def __init__(self, ctx, handle, n, N, device):
+        self.ctx, self._h, self.n, self.N, self.device = ctx, handle, n, N, device
+        self._psf = None
+
+    def _use(self):
+        assert self._h, "imager is closed"
+        self.ctx._use_torch_stream()
+
+    @staticmethod
+    def _ok(t, dt, shape, what):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{what} must be a contiguous cuda {dt} tensor of shape {shape}")
+        return t
+
+    def _pmax(self, psf):
+        pm = C.c_double()
+        self.ctx._check(self.ctx._lib.gridhip_imager_psf_dev(self._h, Context._ptr(psf), C.byref(pm)))
+        return pm.value
+
+    @property
+    def psf(self):
+        """do_imaging's psf for these baselines (N x N cuda float64, normalised by pmax)"""
+        import torch
+        if self._psf is None:
+            self._use()
+            self._psf = torch.empty((self.N, self.N), dtype=torch.float64, device=self.device)
+            self._pmax(self._psf)
+        return self._psf
+
+    @property
+    def pmax(self):
+        assert self._h, "imager is closed"
+        return self._pmax(None)
+
+    def cycle(self, vis, model=None, out=None, vis_res=None):
+        """The image of do_imaging(vis - predict(model)) (of do_imaging(vis) without a model), asynchronous on torch's
+        stream.  out: the N x N cuda float64 tensor to write (a new one when None).  vis_res: a length-n cuda complex128
+        tensor that receives vis - predict(model); it may be vis itself."""
+        import torch
+        self._use()
+        vis = self._ok(vis, torch.complex128, (self.n,), "vis")
+        if model is not None:
+            model = self._ok(model, torch.float64, (self.N, self.N), "model")
+        if vis_res is not None:
+            self._ok(vis_res, torch.complex128, (self.n,), "vis_res")
+        if out is None:
+            out = torch.empty((self.N, self.N), dtype=torch.float64, device=self.device)
+        else:
+            self._ok(out, torch.float64, (self.N, self.N), "out")
+        self.ctx._check(self.ctx._lib.gridhip_imager_cycle_dev(self._h, Context._ptr(model), Context._ptr(vis),
+                                                               Context._ptr(out), Context._ptr(vis_res)))
+        return out
+
+    def predict(self, model, vis_sub=None, out=None):
+        """Context.predict for the imager's baselines: the prediction of `model`, or vis_sub minus it; out may be vis_sub."""
+        import torch
+        self._use()
+        model = self._ok(model, torch.float64, (self.N, self.N), "model")
+        if vis_sub is not None:
+            self._ok(vis_sub, torch.complex128, (self.n,), "vis_sub")
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.complex128, device=self.device)
+        else:
+            self._ok(out, torch.complex128, (self.n,), "out")
+        self.ctx._check(self.ctx._lib.gridhip_imager_predict_dev(self._h, Context._ptr(model), Context._ptr(vis_sub),
+                                                                 Context._ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            self.ctx._lib.gridhip_imager_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -92,6 +92,14 @@ SIGNATURES = {
     "gridhip_predict_dev": (ci, _PREDICT),
     "gridhip_predict_aw": (ci, _PREDICT_AW),
     "gridhip_predict_aw_dev": (ci, _PREDICT_AW),
+    "gridhip_imager_create_dev": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64,
+                                       C.POINTER(vp)]),
+    "gridhip_imager_create_aw_dev": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp,
+                                          vp, C.POINTER(vp)]),
+    "gridhip_imager_psf_dev": (ci, [vp, vp, C.POINTER(C.c_double)]),
+    "gridhip_imager_cycle_dev": (ci, [vp, vp, vp, vp, vp]),
+    "gridhip_imager_predict_dev": (ci, [vp, vp, vp, vp]),
+    "gridhip_imager_destroy": (ci, [vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),
