@@ -2,6 +2,7 @@
 // forms that enqueue the kernels, and the host-pointer drop-in forms that stage through pooled device blocks.
 
 #include "common.h"
+#include "imaging.h"
 
 using namespace gridhip;
 

@@ -14,6 +14,7 @@
 // Work is done in batches so the kernel table stays bounded; nothing is read back inside a call.
 // The same per-batch preparation feeds the gather (awdegrid: the tile kernel's degrid form reads the same table) and
 // aw plans, which keep each batch's records, tables and compacted kernel table for many passes.
+#include "imaging.h"
 #include "tile_common.h"
 
 namespace gridhip {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "imaging.h"
 
 using namespace gridhip;
 

@@ -5,8 +5,6 @@
 #include <stdio.h>
 #include <string>
 #include <unordered_set>
-#include <utility>
-#include <vector>
 
 #include "../../include/gridhip.h"
 
@@ -121,6 +119,8 @@ struct Workspace {
     size_t bytes = 0;
 };
 
+struct ImagingState;  // the imaging layer's share of a context (imaging.h)
+
 }  // namespace gridhip
 
 struct gridhip_ctx {
@@ -152,25 +152,7 @@ struct gridhip_ctx {
     bool ev_open = false;  // a call has recorded its first event and not yet its last
     uint32_t attr_mask = 0;  // pre-pass kernels whose dynamic-LDS limit has been raised
     std::unordered_set<const void *> lds_raised;  // tile kernels whose dynamic-LDS limit has been raised
-    // cached hipFFT Z2Z plans (imaging.hip): do_imaging with w_cache_imaging alternates between the kernel generator's
-    // size and the image's, and creating a plan costs milliseconds
-    void *fft_plan[4] = {nullptr, nullptr, nullptr, nullptr};
-    int64_t fft_n[4] = {0, 0, 0, 0};
-    int fft_next = 0;  // the slot the next new size replaces
-    // device blocks of the host-pointer forms and the imaging entry points (DevBuf), kept between calls: a repeated
-    // call then neither allocates nor frees - hipFree synchronises the whole device.  All of a context's work is
-    // ordered on one stream (gridhip_set_stream orders a new one after the old), so a block handed back by one call
-    // may be handed out to the next without waiting.
-    std::vector<std::pair<void *, size_t>> pool_free;
-    // the last w-kernel table w_cache_imaging built (imaging.hip): the table depends on the field of view, the w-planes
-    // and the kernel's shape only, and an imaging run calls with the same ones again and again (image and PSF, every
-    // major cycle) - a call whose planes match takes the table as it is (21 planes: 1.6 ms of small kernels saved)
-    struct {
-        double theta = 0.0;
-        int64_t wstep = 0, wmin = 0, nplanes = 0, npixFF = 0, S = 0, Q = 0;
-        void *ptr = nullptr;
-        size_t bytes = 0;
-    } wk_cache;
+    gridhip::ImagingState *img = nullptr;  // what the layer around the gridder keeps between calls (imaging.h)
     // which gridder the last convgrid / convgrid2 / degrid2 / plan call used (read-only option "last_path"):
     // 1 = tap-reusing tile kernel, 2 = the same through sub-footprints (one record per spatial part of the kernel),
     // 3 = general tile kernel (small problems; shapes or sizes the tap-reusing kernel does not take),
@@ -205,59 +187,6 @@ int fail(gridhip_ctx *ctx, int code, const char *fmt, ...);
     } while (0)
 
 int ws_reserve(gridhip_ctx *ctx, Workspace &ws, size_t bytes);
-
-// Device block of one call, drawn from and returned to the context's pool (gridhip_ctx::pool_free): the smallest pooled
-// block of at least the size asked for and at most twice it, else a new one.  Nothing is freed before gridhip_destroy,
-// so the second call of a given shape allocates nothing.
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    gridhip_ctx *owner = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;  // (one owner hands the block back)
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf()
-    {
-        if (p && owner) owner->pool_free.emplace_back(p, cap);
-    }
-    int alloc(gridhip_ctx *ctx, size_t bytes);
-    int upload(gridhip_ctx *ctx, const void *host, size_t bytes);  // alloc, then an async copy of `bytes` from the host
-    template <typename T>
-    T *as()
-    {
-        return reinterpret_cast<T *>(p);
-    }
-};
-
-// copies on ctx->stream (none for 0 bytes); copy_in / copy_out take host arrays (the drop-in forms) or device-resident
-// ones (dev: the _dev forms)
-static inline int copy_in(gridhip_ctx *ctx, void *d, const void *src, size_t bytes, bool dev)
-{
-    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(d, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    return GRIDHIP_OK;
-}
-static inline int copy_out(gridhip_ctx *ctx, void *dst, const void *d, size_t bytes, bool dev)
-{
-    if (bytes) GH_CHECK_HIP(ctx, hipMemcpyAsync(dst, d, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    return GRIDHIP_OK;
-}
-static inline int h2d(gridhip_ctx *ctx, void *d, const void *h, size_t bytes) { return copy_in(ctx, d, h, bytes, false); }
-static inline int d2h(gridhip_ctx *ctx, void *h, const void *d, size_t bytes) { return copy_out(ctx, h, d, bytes, false); }
-static inline int sync(gridhip_ctx *ctx)
-{
-    GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GRIDHIP_OK;
-}
-
-// The device copies of a host-pointer gridding call's inputs (api.hip): the grid (uploaded, or zeroed when `grid` is
-// null), the u / v spans, vis (uploaded, or left for the call to write when `vis` is null), wbin and gcf when given
-// (else their blocks stay null).
-struct GridInputs {
-    DevBuf grid, u, v, vis, wbin, gcf;
-};
-int upload_inputs(gridhip_ctx *ctx, GridInputs &d, size_t cells, const double *grid, int64_t n, int64_t uv_stride,
-                  const double *u, const double *v, const double *vis, const int64_t *wbin, const double *gcf,
-                  size_t gcf_elems);
 
 // HIP events of a timed call: i = 0: it starts, 1: its pre-pass is enqueued, 2: its dominant kernel is enqueued (the
 // call is then readable with gridhip_timing)
@@ -303,32 +232,6 @@ __device__ __forceinline__ void frac_coord_dev(int64_t n, int32_t qpx, double p,
     *fr = r;
 }
 
-// findClosest, src/Gridding.hs:895-907 (hi clamped to len-1 as the host twin does, ImageDataset.hs:150-168)
-__device__ __forceinline__ int64_t closest_index(int64_t nws, const double *__restrict__ ws, double x)
-{
-    int64_t lo = 0, hi = nws;
-    while ((hi - lo) / 2 >= 1) {
-        const int64_t mid = (hi + lo) / 2;
-        if (x > ws[mid])
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const int64_t hc = hi > nws - 1 ? nws - 1 : hi;
-    return fabs(x - ws[lo]) < fabs(x - ws[hc]) ? lo : hc;
-}
-
-// doweight's cell, src/Gridding.hs:564-583: frac_coords (N,N) 1 p; -1: outside the grid or NaN (the weight stays 1)
-__device__ __forceinline__ int64_t weight_cell(int64_t N, double pu, double pv)
-{
-    int64_t x, y;
-    int32_t f;
-    frac_coord_dev(N, 1, pu, &x, &f);
-    frac_coord_dev(N, 1, pv, &y, &f);
-    if (!(pu == pu) || !(pv == pv) || x < 0 || y < 0 || x >= N || y >= N) return -1;
-    return y * N + x;
-}
-
 // kernel launchers (each enqueues on ctx->stream)
 // zero_out (degrid2): the counting sweep writes a zero prediction for every visibility it drops (no tap inside the
 // grid, wbin out of range), so that the caller's array needs no clearing pass
@@ -369,7 +272,6 @@ struct Tables {
     int32_t *cursor;      // [nbins] scatter cursors
     int32_t *scalars;     // = ctx->d_scalars
 };
-void fft_release(gridhip_ctx *ctx);
 // a plan whose records live in the context's own scratch (plan.hip): for callers that keep it for one call's passes
 int plan_create_borrowed(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t gh, int64_t gw,
                          const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, gridhip_plan **out);
@@ -379,92 +281,5 @@ int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *con
                  const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, const int64_t *a1,
                  const int64_t *a2);
 size_t tables_bytes(const Geom &g);
-
-// ---- shared with predict.hip: the imaging functions' front ends and the centred transform (imaging.hip) -------------
-// work-groups of 256 threads for a grid-stride loop over n items (at most 16 per CU)
-static inline dim3 grid_for(gridhip_ctx *ctx, int64_t n, int block = 256)
-{
-    int64_t b = (n + block - 1) / block;
-    if (b < 1) b = 1;
-    if (b > (int64_t)ctx->num_cu * 16) b = (int64_t)ctx->num_cu * 16;
-    return dim3((unsigned)b);
-}
-// out[k] = x[k * stride] / lam (scale_kernel: div3, src/Gridding.hs:838-839)
-int launch_scale(gridhip_ctx *ctx, int64_t n, const double *x, int64_t stride, double lam, double *out);
-// out[y][x] = in[(y+s) mod N][(x+s) mod N] * scale (roll_kernel)
-int launch_roll(gridhip_ctx *ctx, int64_t N, const double2 *in, double2 *out, int64_t s, double scale);
-// the context's cached N x N Z2Z hipFFT plan, bound to its stream; an in-place transform with it
-int fft_plan_for(gridhip_ctx *ctx, int64_t N, void **out_plan);
-int fft_exec(gridhip_ctx *ctx, void *plan, double2 *data, bool inverse);
-
-// a transform the caller owns (hipfftPlan2d Z2Z, N x N), binding it to the context's stream, releasing it
-int fft_plan_own(gridhip_ctx *ctx, int64_t N, void **out_plan);
-int fft_plan_bind(gridhip_ctx *ctx, void *plan);
-void fft_plan_drop(void *plan);
-// x[c] /= the maximum kept in maxbits in ordered-bits form (divide_kernel)
-int launch_divide(gridhip_ctx *ctx, int64_t cells, double *x, const unsigned long long *maxbits);
-// the imaging tail (imaging.hip): out = real(ifft_c(make_grid_hermitian(g))), its maximum into *maxbits when given, or
-// (divbits) stored divided by the maximum kept there; h: N x N complex scratch; plan: fft_plan_own's, or the context's
-int image_tail(gridhip_ctx *ctx, int64_t N, const double2 *g, double2 *h, double *out, unsigned long long *maxbits,
-               const unsigned long long *divbits = nullptr, void *plan = nullptr);
-// the w-bin rule on the device (synchronises: min and plane count come back to the host)
-int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t stride, int64_t wstep, int64_t *wbin, int64_t *wmin,
-              int64_t *nplanes);
-// one plane of a w-kernel table, out[Q][Q][S][S]; pad: (npixFF * Q)^2 complex scratch (af, tmp: unused)
-int dev_w_kernel(gridhip_ctx *ctx, double theta, double w, int64_t npixFF, int64_t S, int64_t Q, double2 *out, bool conj,
-                 double2 *pad, double2 *af, double2 *tmp);
-// ---- shared with imager.hip: pieces of predict.hip ---------------------------------------------------------------------
-// f = fft_c(model) (N x N complex); t: N x N complex scratch, used for odd N only; plan as image_tail's
-int model_transform_to(gridhip_ctx *ctx, int64_t N, const double *model, double2 *f, double2 *t, void *plan);
-int launch_simple_degrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double2 *grid, int64_t n, const double *u,
-                         const double *v, int64_t stride, double lam, double2 *out);
-int launch_conj_copy(gridhip_ctx *ctx, int64_t n, const double2 *in, double2 *out);
-int launch_residual(gridhip_ctx *ctx, int64_t n, const double2 *pred, const double2 *sub, double2 *out);
-// A plan that an imager gathers with: the caller clears the predictions itself (in a kernel, so that a cycle can be
-// captured) where the plan would clear them with a memset.  Returns whether they need clearing at all.
-bool plan_caller_clears(gridhip_plan *plan);
-bool aw_plan_caller_clears(gridhip_aw_plan *plan);
-
-// What w_cache_imaging (src/Gridding.hs:399-449) derives from the baselines alone: scaled u, v, the
-// w-bins and one conjugated w-kernel per plane.  do_imaging calls the imaging function twice with the
-// same baselines (image and PSF, :538,541); the reference rebuilds everything both times ("no cache
-// despite the name", :405-411) — here the second call reuses it.
-struct WCache {
-    DevBuf pu, pv, wb;
-    double2 *table = nullptr;  // the context's cached table (gridhip_ctx::wk_cache): not owned
-    int64_t nplanes = 0;
-    bool ready = false;
-    gridhip_plan *plan = nullptr;  // the baselines binned once for both passes
-    ~WCache() { gridhip_plan_destroy(plan); }
-};
-// u, v, w: n contiguous doubles each (wavelengths); synchronises (the w-bin rule reads min / max back)
-int w_cache_prepare(gridhip_ctx *ctx, WCache &c, double theta, int64_t lam, int64_t wstep, int64_t Q, int64_t npixFF,
-                    int64_t S, int64_t n, const double *u, const double *v, const double *w);
-
-// the arguments of the aw entry points (aw_imaging_dev, do_imaging_aw, aw_gridding, predict_aw)
-struct AwArgs {
-    double theta;
-    int64_t lam, W, Q, S, A;
-    const double *wkerns, *wvals, *akerns;
-    int64_t n;
-    const double *u, *v, *w;
-    int64_t stride;
-    const int64_t *a1, *a2;
-    const double *vis;
-};
-// N = image size; vis_needed: whether the call reads vis (the gridding entry points do, predict_aw does not)
-int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed = true);
-// The inputs on the device: the caller's own (the _dev forms) or uploaded copies (the host forms), in s.d.
-struct AwStage {
-    DevBuf wk, ws, ak, u, v, w, a1, a2, vis;
-    AwArgs d;
-};
-int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s);
-// p = uvw1 / lam, w-bins, and (mirror) vis1, (weigh) wt * vis1 in vis1 and (want_wt) wt: aw_front_kernel +
-// aw_weight_kernel.  weigh: 0 none, 1 on the mirrored coordinates, 2 on the un-mirrored ones.
-struct AwFront {
-    DevBuf pu, pv, wb, vis1, wt, cell, cnt;
-};
-int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt, AwFront &f);
 
 }  // namespace gridhip

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "imaging.h"
 
 namespace gridhip {
 
@@ -37,23 +38,24 @@ int DevBuf::alloc(gridhip_ctx *ctx, size_t bytes)
 {
     if (bytes < 256) bytes = 256;
     owner = ctx;
+    auto &pool = ctx->img->pool_free;
     int best = -1;
-    for (int i = 0; i < (int)ctx->pool_free.size(); ++i) {
-        const size_t c = ctx->pool_free[i].second;
-        if (c >= bytes && c <= 2 * bytes && (best < 0 || c < ctx->pool_free[best].second)) best = i;
+    for (int i = 0; i < (int)pool.size(); ++i) {
+        const size_t c = pool[i].second;
+        if (c >= bytes && c <= 2 * bytes && (best < 0 || c < pool[best].second)) best = i;
     }
     if (best >= 0) {
-        p = ctx->pool_free[best].first;
-        cap = ctx->pool_free[best].second;
-        ctx->pool_free.erase(ctx->pool_free.begin() + best);
+        p = pool[best].first;
+        cap = pool[best].second;
+        pool.erase(pool.begin() + best);
         return GRIDHIP_OK;
     }
     hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipErrorOutOfMemory && !ctx->pool_free.empty()) {  // give the pooled blocks back and try once more
+    if (e == hipErrorOutOfMemory && !pool.empty()) {  // give the pooled blocks back and try once more
         (void)hipGetLastError();
         (void)hipDeviceSynchronize();
-        for (auto &b : ctx->pool_free) (void)hipFree(b.first);
-        ctx->pool_free.clear();
+        for (auto &b : pool) (void)hipFree(b.first);
+        pool.clear();
         e = hipMalloc(&p, bytes);
     }
     if (e != hipSuccess) {
@@ -346,7 +348,11 @@ int gridhip_create(int device, gridhip_ctx **out)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return GRIDHIP_ENODEV;
     gridhip_ctx *ctx = new (std::nothrow) gridhip_ctx();
-    if (!ctx) return GRIDHIP_ENOMEM;
+    if (ctx) ctx->img = new (std::nothrow) ImagingState();
+    if (!ctx || !ctx->img) {
+        delete ctx;
+        return GRIDHIP_ENOMEM;
+    }
     ctx->device = device;
     ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     int maxlds = 0;
@@ -358,6 +364,7 @@ int gridhip_create(int device, gridhip_ctx **out)
     // CDNA4: 160 KiB of LDS per CU, all of it available to one work-group
     if (strstr(prop.gcnArchName, "gfx950") && ctx->max_lds < 160 * 1024) ctx->max_lds = 160 * 1024;
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) {
+        delete ctx->img;
         delete ctx;
         return GRIDHIP_EHIP;
     }
@@ -389,13 +396,14 @@ int gridhip_destroy(gridhip_ctx *ctx)
     Workspace *all[] = {&ctx->recs, &ctx->tables, &ctx->blockhist, &ctx->sorted, &ctx->recs_tmp, &ctx->recs_raw, &ctx->ktab, &ctx->aw};
     for (Workspace *w : all)
         if (w->ptr) (void)hipFree(w->ptr);
-    for (auto &b : ctx->pool_free) (void)hipFree(b.first);
-    ctx->pool_free.clear();
+    for (auto &b : ctx->img->pool_free) (void)hipFree(b.first);
+    ctx->img->pool_free.clear();
     if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
     for (int i = 0; i < gridhip_ctx::EV_RING * 3; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+    delete ctx->img;
     delete ctx;
     return GRIDHIP_OK;
 }

@@ -16,6 +16,7 @@
 #include <new>
 
 #include "common.h"
+#include "imaging.h"
 
 namespace gridhip {
 
@@ -198,40 +199,19 @@ int scatter(gridhip_imager *im)
     }
 }
 
-struct Kernels {  // conv: kv; w_cache: the generator's options; aw: the tables and the antennas
-    int64_t wstep = 0, Q = 0, npixFF = 0, gh = 0, gw = 0;
-    const double *kv = nullptr;
-    double theta = 0.0;
+struct Kernels {  // conv, w_cache: the imaging function; aw: its Q, the tables and the antennas
+    ImagingFn fn = {};
     int64_t W = 0, S = 0, A = 0;
     const double *wkerns = nullptr, *wvals = nullptr, *akerns = nullptr;
     const int64_t *a1 = nullptr, *a2 = nullptr;
 };
-
-// [nplanes][Q][Q][S][S] w_kernels of the planes w = i * wstep + wmin (src/Gridding.hs:434-448), conjugated or not
-int build_planes(gridhip_ctx *ctx, const Kernels &k, int64_t wmin, int64_t nplanes, double2 *table, bool conj)
-{
-    const int64_t na = k.npixFF * k.Q;
-    DevBuf pad;
-    GH_CHECK(pad.alloc(ctx, (size_t)na * na * 16));
-    for (int64_t i = 0; i < nplanes; ++i)
-        GH_CHECK(dev_w_kernel(ctx, k.theta, (double)(i * k.wstep + wmin), k.npixFF, k.gh, k.Q,
-                              table + i * k.Q * k.Q * k.gh * k.gh, conj, pad.as<double2>(), nullptr, nullptr));
-    return GRIDHIP_OK;
-}
-
-double max_of_bits(unsigned long long mb)
-{
-    mb = (mb & 0x8000000000000000ULL) ? (mb & 0x7fffffffffffffffULL) : ~mb;
-    double m;
-    memcpy(&m, &mb, 8);
-    return m;
-}
 
 // Everything creation does, into *im (the caller destroys it on failure).  Arguments are checked by the callers.
 int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, const double *v, const double *w,
          int64_t stride)
 {
     gridhip_ctx *ctx = im->ctx;
+    const ImagingFn &fn = k.fn;
     const int64_t N = im->N, n = im->n;
     const size_t cells = (size_t)N * N;
     GH_CHECK(own(im, &im->psf, cells * 8));
@@ -281,42 +261,42 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
     if (im->kind == 0) {
         im->pu = p[0], im->pv = p[1], im->mu = p[2], im->mv = p[3];
     } else if (im->kind == 1) {
-        const size_t el = (size_t)k.Q * k.Q * k.gh * k.gw;
+        const size_t el = (size_t)fn.Q * fn.Q * fn.gh * fn.gw;
         GH_CHECK(own(im, &im->ktab_g, el * 16));
         GH_CHECK(own(im, &im->ktab_s, el * 16));
-        GH_CHECK(launch_conj_copy(ctx, (int64_t)el, (const double2 *)k.kv, im->ktab_g));
-        GH_CHECK(copy_in(ctx, im->ktab_s, k.kv, el * 16, true));
-        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, 1, k.Q, k.gh, k.gw, p[0], p[1], 1, nullptr, &im->gather));
-        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, 1, k.Q, k.gh, k.gw, p[2], p[3], 1, nullptr, &im->scatter));
+        GH_CHECK(launch_conj_copy(ctx, (int64_t)el, (const double2 *)fn.kv, im->ktab_g));
+        GH_CHECK(copy_in(ctx, im->ktab_s, fn.kv, el * 16, true));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, 1, fn.Q, fn.gh, fn.gw, p[0], p[1], 1, nullptr, &im->gather));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, 1, fn.Q, fn.gh, fn.gw, p[2], p[3], 1, nullptr, &im->scatter));
     } else if (im->kind == 2) {
         // the w-bin rule on each stream: its own minimum and plane count, hence a table of its own.  (The gather's
         // planes are the w_kernels, the scatter's their conjugates, :441: two tables even where the ranges agree.)
         int64_t wmin[2] = {0, 0}, np[2] = {0, 0};
         for (int i = 0; i < 2; ++i) {
-            GH_CHECK(dev_wbins(ctx, n, tw[i].as<double>(), 1, k.wstep, tb[i].as<int64_t>(), &wmin[i], &np[i]));
+            GH_CHECK(dev_wbins(ctx, n, tw[i].as<double>(), 1, fn.wstep, tb[i].as<int64_t>(), &wmin[i], &np[i]));
             if (np[i] < 1 || np[i] > 65536) return fail(ctx, GRIDHIP_EUNSUPPORTED, "%lld w-planes", (long long)np[i]);
         }
-        const size_t pl = (size_t)k.Q * k.Q * k.gh * k.gh;
+        const size_t pl = (size_t)fn.Q * fn.Q * fn.gh * fn.gh;
         GH_CHECK(own(im, &im->ktab_g, np[0] * pl * 16));
         GH_CHECK(own(im, &im->ktab_s, np[1] * pl * 16));
-        GH_CHECK(build_planes(ctx, k, wmin[0], np[0], im->ktab_g, false));
-        GH_CHECK(build_planes(ctx, k, wmin[1], np[1], im->ktab_s, true));
-        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[0], k.Q, k.gh, k.gh, p[0], p[1], 1, tb[0].as<int64_t>(),
+        GH_CHECK(build_w_planes(ctx, fn.theta, fn.wstep, wmin[0], np[0], fn.npixFF, fn.gh, fn.Q, im->ktab_g, false));
+        GH_CHECK(build_w_planes(ctx, fn.theta, fn.wstep, wmin[1], np[1], fn.npixFF, fn.gh, fn.Q, im->ktab_s, true));
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[0], fn.Q, fn.gh, fn.gh, p[0], p[1], 1, tb[0].as<int64_t>(),
                                          &im->gather));
-        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[1], k.Q, k.gh, k.gh, p[2], p[3], 1, tb[1].as<int64_t>(),
+        GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[1], fn.Q, fn.gh, fn.gh, p[2], p[3], 1, tb[1].as<int64_t>(),
                                          &im->scatter));
     } else {
         // the gather's kernels are conj(aw_kernel_fn2(conj wk, conj ak)) (predict_aw); the aw plans keep what they build
-        const size_t wel = (size_t)k.W * k.Q * k.Q * k.S * k.S, ael = (size_t)k.A * k.S * k.S;
+        const size_t wel = (size_t)k.W * fn.Q * fn.Q * k.S * k.S, ael = (size_t)k.A * k.S * k.S;
         DevBuf cwk, cak;
         GH_CHECK(cwk.alloc(ctx, wel * 16));
         GH_CHECK(cak.alloc(ctx, ael * 16));
         GH_CHECK(launch_conj_copy(ctx, (int64_t)wel, (const double2 *)k.wkerns, cwk.as<double2>()));
         GH_CHECK(launch_conj_copy(ctx, (int64_t)ael, (const double2 *)k.akerns, cak.as<double2>()));
-        GH_CHECK(gridhip_aw_plan_create_dev(ctx, N, N, n, k.W, k.Q, k.S, k.A, cwk.as<double>(), cak.as<double>(), p[0],
+        GH_CHECK(gridhip_aw_plan_create_dev(ctx, N, N, n, k.W, fn.Q, k.S, k.A, cwk.as<double>(), cak.as<double>(), p[0],
                                             p[1], 1, tb[0].as<int64_t>(), k.a1, k.a2, &im->aw_gather));
         int64_t tables = ctx->aw_tables_built;
-        GH_CHECK(gridhip_aw_plan_create_dev(ctx, N, N, n, k.W, k.Q, k.S, k.A, k.wkerns, k.akerns, p[2], p[3], 1,
+        GH_CHECK(gridhip_aw_plan_create_dev(ctx, N, N, n, k.W, fn.Q, k.S, k.A, k.wkerns, k.akerns, p[2], p[3], 1,
                                             tb[1].as<int64_t>(), k.a1, k.a2, &im->aw_scatter));
         ctx->aw_tables_built += tables;
     }
@@ -344,7 +324,7 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
     unsigned long long mb = 0;
     GH_CHECK(d2h(ctx, &mb, im->pmaxbits, 8));
     GH_CHECK(sync(ctx));  // the inputs may be freed or overwritten once this returns
-    im->pmax = max_of_bits(mb);
+    im->pmax = ordered_value(mb);
     return GRIDHIP_OK;
 }
 
@@ -379,16 +359,13 @@ int gridhip_imager_create_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t
 {
     if (imager) *imager = nullptr;
     if (!ctx) return GRIDHIP_EINVAL;
-    // predict_check's rules (predict.hip), without a model or an output
-    const int64_t N = gridhip_image_size(theta, lam);
-    if (kind == 2 && wstep <= 0) wstep = 2000;  // (w_cache_imaging's default, :412)
-    const bool kinds = kind == 0 || (kind == 1 && kv && Q > 0 && gh > 0 && gw > 0) ||
-                       (kind == 2 && Q > 0 && npixFF > 0 && gh > 0 && gh <= npixFF);
-    if (!imager || N <= 0 || !kinds || n < 0 || uv_stride < 1 || (n > 0 && (!u || !v || (kind == 2 && !w))))
+    Kernels k;
+    k.fn = {kind, wstep, Q, npixFF, gh, kind == 2 ? gh : gw, kv, theta, lam};
+    int64_t N = 0;
+    GH_CHECK(imaging_fn_check(ctx, k.fn, &N));
+    if (!imager || n < 0 || uv_stride < 1 || (n > 0 && (!u || !v || (kind == 2 && !w))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     if (n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per imager");
-    Kernels k;
-    k.wstep = wstep, k.Q = Q, k.npixFF = npixFF, k.gh = gh, k.gw = kind == 2 ? gh : gw, k.kv = kv, k.theta = theta;
     return create(ctx, kind, N, n, k, (double)lam, u, v, w, uv_stride, imager);
 }
 
@@ -407,8 +384,7 @@ int gridhip_imager_create_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, in
     if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
         return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
     Kernels k;
-    k.Q = Q, k.W = W, k.S = S, k.A = A, k.wkerns = wkerns, k.wvals = wvals, k.akerns = akerns, k.a1 = a1, k.a2 = a2;
-    k.theta = theta;
+    k.fn.Q = Q, k.W = W, k.S = S, k.A = A, k.wkerns = wkerns, k.wvals = wvals, k.akerns = akerns, k.a1 = a1, k.a2 = a2;
     return create(ctx, 3, N, n, k, (double)lam, u, v, w, uv_stride, imager);
 }
 

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "common.h"
+#include "imaging.h"
 
 struct gridhip_plan {
     gridhip_ctx *ctx = nullptr;

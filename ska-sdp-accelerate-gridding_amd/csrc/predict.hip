@@ -12,6 +12,7 @@
 // which by the shift theorem is the shift2D after the transform, so the gathers read the FFT's output directly.
 // For odd N that phase is not +-1, and the shift stays a roll after the transform.
 #include "common.h"
+#include "imaging.h"
 
 namespace gridhip {
 
@@ -141,11 +142,7 @@ int model_transform(gridhip_ctx *ctx, int64_t N, const double *model, DevBuf &f,
 }
 
 struct PredictArgs {
-    int kind;
-    int64_t wstep, Q, npixFF, gh, gw;
-    const double *kv;
-    double theta;
-    int64_t lam;
+    ImagingFn fn;
     const double *model;
     int64_t n;
     const double *u, *v, *w;
@@ -157,12 +154,8 @@ struct PredictArgs {
 // Everything is checked before anything is touched: a refused call leaves vis_out as it was.
 int predict_check(gridhip_ctx *ctx, PredictArgs &a, int64_t *N)
 {
-    *N = gridhip_image_size(a.theta, a.lam);
-    if (a.kind == 2 && a.wstep <= 0) a.wstep = 2000;  // (w_cache_imaging's default, :412)
-    const bool kinds = a.kind == 0 || (a.kind == 1 && a.kv && a.Q > 0 && a.gh > 0 && a.gw > 0) ||
-                       (a.kind == 2 && a.Q > 0 && a.npixFF > 0 && a.gh > 0 && a.gh <= a.npixFF);
-    if (*N <= 0 || !kinds || !a.model || a.n < 0 || a.stride < 1 ||
-        (a.n > 0 && (!a.u || !a.v || !a.vis_out || (a.kind == 2 && !a.w))))
+    GH_CHECK(imaging_fn_check(ctx, a.fn, N));
+    if (!a.model || a.n < 0 || a.stride < 1 || (a.n > 0 && (!a.u || !a.v || !a.vis_out || (a.fn.kind == 2 && !a.w))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     if (a.n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per call");
     return GRIDHIP_OK;
@@ -192,6 +185,7 @@ int predict_any(gridhip_ctx *ctx, bool dev, PredictArgs a)
     if (!ctx) return GRIDHIP_EINVAL;
     int64_t N = 0;
     GH_CHECK(predict_check(ctx, a, &N));
+    const ImagingFn &fn = a.fn;
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n = a.n;
     // nothing is dropped until a gather says otherwise (the simple gather counts nothing, as `grid` does not)
@@ -201,14 +195,14 @@ int predict_any(gridhip_ctx *ctx, bool dev, PredictArgs a)
     const size_t span = (size_t)(n - 1) * a.stride + 1;
     // the inputs on the device
     DevBuf sm, su, sv, sw, skv, ssub, sout;
-    const double *model = a.model, *u = a.u, *v = a.v, *w = a.w, *kv = a.kv, *vis_sub = a.vis_sub;
+    const double *model = a.model, *u = a.u, *v = a.v, *w = a.w, *kv = fn.kv, *vis_sub = a.vis_sub;
     double *out = a.vis_out;
     if (!dev) {
         GH_CHECK(sm.upload(ctx, a.model, cells * 8));
         GH_CHECK(su.upload(ctx, a.u, span * 8));
         GH_CHECK(sv.upload(ctx, a.v, span * 8));
-        if (a.kind == 2) GH_CHECK(sw.upload(ctx, a.w, span * 8));
-        if (a.kind == 1) GH_CHECK(skv.upload(ctx, a.kv, (size_t)a.Q * a.Q * a.gh * a.gw * 16));
+        if (fn.kind == 2) GH_CHECK(sw.upload(ctx, a.w, span * 8));
+        if (fn.kind == 1) GH_CHECK(skv.upload(ctx, fn.kv, (size_t)fn.Q * fn.Q * fn.gh * fn.gw * 16));
         if (a.vis_sub) GH_CHECK(ssub.upload(ctx, a.vis_sub, (size_t)n * 16));
         GH_CHECK(sout.alloc(ctx, (size_t)n * 16));
         model = sm.as<double>(), u = su.as<double>(), v = sv.as<double>(), w = sw.as<double>(), kv = skv.as<double>();
@@ -218,22 +212,14 @@ int predict_any(gridhip_ctx *ctx, bool dev, PredictArgs a)
     // front end: the imaging function's coordinates (p = uvw / lam; w_cache: the w-bins and its kernel table)
     DevBuf pu, pv, pw;
     WCache wc;
-    if (a.kind == 1) {
-        GH_CHECK(pu.alloc(ctx, (size_t)n * 8));
-        GH_CHECK(pv.alloc(ctx, (size_t)n * 8));
-        GH_CHECK(launch_scale(ctx, n, u, a.stride, (double)a.lam, pu.as<double>()));
-        GH_CHECK(launch_scale(ctx, n, v, a.stride, (double)a.lam, pv.as<double>()));
-    } else if (a.kind == 2) {
+    if (fn.kind == 1) {
+        GH_CHECK(scaled_uv(ctx, n, u, v, a.stride, (double)fn.lam, pu, pv));
+    } else if (fn.kind == 2) {
         if (a.stride != 1) {  // (w_cache_prepare takes contiguous columns: slice the (n, 3) matrix)
-            GH_CHECK(pu.alloc(ctx, (size_t)n * 8));
-            GH_CHECK(pv.alloc(ctx, (size_t)n * 8));
-            GH_CHECK(pw.alloc(ctx, (size_t)n * 8));
-            GH_CHECK(launch_scale(ctx, n, u, a.stride, 1.0, pu.as<double>()));
-            GH_CHECK(launch_scale(ctx, n, v, a.stride, 1.0, pv.as<double>()));
-            GH_CHECK(launch_scale(ctx, n, w, a.stride, 1.0, pw.as<double>()));
+            GH_CHECK(slice_uvw(ctx, n, u, v, w, a.stride, pu, pv, pw));
             u = pu.as<double>(), v = pv.as<double>(), w = pw.as<double>();
         }
-        GH_CHECK(w_cache_prepare(ctx, wc, a.theta, a.lam, a.wstep, a.Q, a.npixFF, a.gh, n, u, v, w));
+        GH_CHECK(w_cache_prepare(ctx, wc, fn.theta, fn.lam, fn.wstep, fn.Q, fn.npixFF, fn.gh, n, u, v, w));
     }
     DevBuf f, t, pred, ctab;
     GH_CHECK(pred.alloc(ctx, (size_t)n * 16));
@@ -242,20 +228,19 @@ int predict_any(gridhip_ctx *ctx, bool dev, PredictArgs a)
     mark(ctx, 1);
     {
         NoTiming quiet(ctx);
-        if (a.kind == 0) {
-            hipLaunchKernelGGL(simple_degrid_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, N, N,
-                               f.as<const double2>(), n, u, v, a.stride, (double)a.lam, pred.as<double2>());
-            GH_CHECK_HIP(ctx, hipGetLastError());
-        } else if (a.kind == 1) {
+        if (fn.kind == 0) {
+            GH_CHECK(launch_simple_degrid(ctx, N, N, f.as<const double2>(), n, u, v, a.stride, (double)fn.lam,
+                                          pred.as<double2>()));
+        } else if (fn.kind == 1) {
             const double *k = nullptr;
-            GH_CHECK(conj_copy(ctx, ctab, a.Q * a.Q * a.gh * a.gw, kv, &k));
-            GH_CHECK(gridhip_degrid2_dev(ctx, N, N, f.as<double>(), n, 1, a.Q, a.gh, a.gw, k, pu.as<double>(),
+            GH_CHECK(conj_copy(ctx, ctab, fn.Q * fn.Q * fn.gh * fn.gw, kv, &k));
+            GH_CHECK(gridhip_degrid2_dev(ctx, N, N, f.as<double>(), n, 1, fn.Q, fn.gh, fn.gw, k, pu.as<double>(),
                                          pv.as<double>(), 1, nullptr, pred.as<double>()));
         } else {
             // the cached table holds conj(w_kernel) per plane (w_cache_imaging's); the gather wants w_kernel
             const double *k = nullptr;
-            GH_CHECK(conj_copy(ctx, ctab, wc.nplanes * a.Q * a.Q * a.gh * a.gh, (const double *)wc.table, &k));
-            GH_CHECK(gridhip_degrid2_dev(ctx, N, N, f.as<double>(), n, wc.nplanes, a.Q, a.gh, a.gh, k,
+            GH_CHECK(conj_copy(ctx, ctab, wc.nplanes * fn.Q * fn.Q * fn.gh * fn.gh, (const double *)wc.table, &k));
+            GH_CHECK(gridhip_degrid2_dev(ctx, N, N, f.as<double>(), n, wc.nplanes, fn.Q, fn.gh, fn.gh, k,
                                          wc.pu.as<double>(), wc.pv.as<double>(), 1, wc.wb.as<int64_t>(),
                                          pred.as<double>()));
         }
@@ -325,7 +310,7 @@ int gridhip_predict(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_
                     const double *kv, double theta, int64_t lam, const double *model, int64_t n, const double *u,
                     const double *v, const double *w, int64_t uv_stride, const double *vis_sub, double *vis_out)
 {
-    return predict_any(ctx, false, {kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, model, n, u, v, w, uv_stride, vis_sub,
+    return predict_any(ctx, false, {{kind, wstep, Q, npixFF, gh, gw, kv, theta, lam}, model, n, u, v, w, uv_stride, vis_sub,
                                     vis_out});
 }
 
@@ -333,7 +318,7 @@ int gridhip_predict_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, in
                         const double *kv, double theta, int64_t lam, const double *model, int64_t n, const double *u,
                         const double *v, const double *w, int64_t uv_stride, const double *vis_sub, double *vis_out)
 {
-    return predict_any(ctx, true, {kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, model, n, u, v, w, uv_stride, vis_sub,
+    return predict_any(ctx, true, {{kind, wstep, Q, npixFF, gh, gw, kv, theta, lam}, model, n, u, v, w, uv_stride, vis_sub,
                                    vis_out});
 }
 

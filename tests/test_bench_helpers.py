@@ -191,3 +191,44 @@ def test_dump_outputs_writes_the_grid_it_is_given(tmp_path):
     assert len(cb) == bench.DUMP_SAMPLE_CELLS and np.array_equal(cb, cc) and np.all(np.diff(cb) > 0)
     N = max(w[1] for w in bench.WORKLOADS.values())
     assert bench.DUMP_SAMPLE_CELLS * (16 + 8) + 2 * N * 16 <= 64 * 2**20
+
+
+def test_imaging_declarations_are_outside_the_fingerprint(tmp_path, monkeypatch):
+    """The layer around the gridder (csrc/imaging.h: staging, transform, imaging functions, imagers) is not part of the
+    sources the traffic measurement is tied to: the fingerprint reads neither imaging.h nor a file that includes it,
+    and does not move when imaging.h changes."""
+    import builtins
+    import os
+    import re
+    import shutil
+    csrc = os.path.join(bench.ROOT, "ska-sdp-accelerate-gridding_amd", "csrc")
+    assert os.path.isfile(os.path.join(csrc, "imaging.h"))
+    read = []
+
+    def recording_open(path, *a, **k):
+        read.append(str(path))
+        return builtins.open(path, *a, **k)
+
+    monkeypatch.setattr(bench, "open", recording_open, raising=False)
+    real = bench.csrc_fingerprint()
+    monkeypatch.delattr(bench, "open")
+    names = sorted(os.path.basename(p) for p in read)
+    assert "common.h" in names and "bin.hip" in names and any(n.startswith("tile_") for n in names)
+    assert all(os.path.dirname(p) == csrc for p in read)
+    assert "imaging.h" not in names
+    for p in read:
+        includes = re.findall(r'#\s*include\s*[<"]([^>"]+)[>"]', open(p, encoding="utf-8").read())
+        assert not any(os.path.basename(i) == "imaging.h" for i in includes), p
+        # (what they do include from this directory is fingerprinted, and so checked, itself)
+        assert all(i in names for i in includes if os.sep not in i and os.path.exists(os.path.join(csrc, i))), p
+    # the same tree with a changed imaging.h
+    dst = tmp_path / "ska-sdp-accelerate-gridding_amd" / "csrc"
+    shutil.copytree(csrc, dst, ignore=shutil.ignore_patterns("build*"))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    assert bench.csrc_fingerprint() == real
+    with open(dst / "imaging.h", "a") as f:
+        f.write("int one_more_imaging_declaration(int);\n")
+    assert bench.csrc_fingerprint() == real
+    with open(dst / "common.h", "a") as f:
+        f.write("int one_more_gridder_declaration(int);\n")
+    assert bench.csrc_fingerprint() != real
