@@ -18,11 +18,17 @@ ci = C.c_int
 OK = 0
 EINVAL, ENOMEM, EHIP, ENODEV, EUNSUPPORTED = -1, -2, -3, -4, -5
 
-# name -> (restype, argtypes); mirrors include/gridhip.h one to one
+# name -> (restype, argtypes); mirrors include/gridhip.h one to one (tests/test_abi.py compares the two); a host form and
+# its _dev twin share one list
 _GRID_DEV = [vp, i64, i64, vp, i64, vp, vp, i64, vp]
 _CONV_DEV = [vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, vp]
 _CONV2_DEV = [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp]
-_AW_IMG = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp,
+_W_CACHE = [vp, i64, i64, i64, i64, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp]
+_AWGRID = [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+_AW_IMAGING = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+_DO_IMAGING = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp, vp,
+               C.POINTER(C.c_double)]
+_DO_IMAGING_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp,
            C.POINTER(C.c_double)]
 _AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp,
                 C.POINTER(C.c_double)]
@@ -64,30 +70,26 @@ SIGNATURES = {
     "gridhip_w_kernel": (ci, [vp, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_simple_imaging": (ci, [vp, C.c_double, i64, i64, vp, vp, i64, vp, vp]),
     "gridhip_conv_imaging": (ci, [vp, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, i64, vp, vp]),
-    "gridhip_w_cache_imaging": (ci, [vp, i64, i64, i64, i64, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp]),
-    "gridhip_awgrid": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
-    "gridhip_awgrid_dev": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "gridhip_w_cache_imaging": (ci, _W_CACHE),
+    "gridhip_awgrid": (ci, _AWGRID),
+    "gridhip_awgrid_dev": (ci, _AWGRID),
     "gridhip_aw_last_stats": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
-    "gridhip_awdegrid": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
-    "gridhip_awdegrid_dev": (ci, [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "gridhip_awdegrid": (ci, _AWGRID),
+    "gridhip_awdegrid_dev": (ci, _AWGRID),
     "gridhip_aw_plan_create_dev": (ci, [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp,
                                         C.POINTER(vp)]),
     "gridhip_aw_plan_grid_dev": (ci, [vp, vp, vp]),
     "gridhip_aw_plan_degrid_dev": (ci, [vp, vp, vp]),
     "gridhip_aw_plan_destroy": (ci, [vp]),
-    "gridhip_aw_imaging": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
-                                vp, vp]),
-    "gridhip_aw_imaging_dev": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp,
-                                    vp, vp, vp]),
-    "gridhip_do_imaging_aw": (ci, _AW_IMG),
-    "gridhip_do_imaging_aw_dev": (ci, _AW_IMG),
+    "gridhip_aw_imaging": (ci, _AW_IMAGING),
+    "gridhip_aw_imaging_dev": (ci, _AW_IMAGING),
+    "gridhip_do_imaging_aw": (ci, _DO_IMAGING_AW),
+    "gridhip_do_imaging_aw_dev": (ci, _DO_IMAGING_AW),
     "gridhip_aw_gridding": (ci, _AW_GRIDDING),
     "gridhip_aw_gridding_dev": (ci, _AW_GRIDDING),
-    "gridhip_do_imaging": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp,
-                                vp, C.POINTER(C.c_double)]),
-    "gridhip_do_imaging_dev": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp,
-                                    vp, C.POINTER(C.c_double)]),
-    "gridhip_w_cache_imaging_dev": (ci, [vp, i64, i64, i64, i64, C.c_double, i64, i64, vp, vp, vp, i64, vp, vp]),
+    "gridhip_do_imaging": (ci, _DO_IMAGING),
+    "gridhip_do_imaging_dev": (ci, _DO_IMAGING),
+    "gridhip_w_cache_imaging_dev": (ci, _W_CACHE),
     "gridhip_predict": (ci, _PREDICT),
     "gridhip_predict_dev": (ci, _PREDICT),
     "gridhip_predict_aw": (ci, _PREDICT_AW),
@@ -126,6 +128,9 @@ SIGNATURES = {
     "gridhip_timing": (ci, [vp, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gridhip_enable_timing": (ci, [vp, ci]),
 }
+
+# per entry point, which arguments after the handle it takes by address (arrays; NULL allowed where the header says so)
+POINTERS = {name: tuple(i - 1 for i, t in enumerate(args) if t is vp and i > 0) for name, (_, args) in SIGNATURES.items()}
 
 _lib = None
 

@@ -1,0 +1,175 @@
+"""The one marshalling path of the binding: every entry point turns its arguments into what include/gridhip.h takes
+through the helpers here, whichever library the arguments come from.
+
+A call picks its back end once, by its leading array (`backend`): HOST for numpy arrays - the synchronous
+gridhip_<op> - or the torch one for cuda tensors - the asynchronous gridhip_<op>_dev on torch's current stream.  A
+back end knows how to make an argument "contiguous, of dtype complex128 / float64 / int64, or None" without copying
+one that already is, how to allocate an output like it and how to take an address; `Handle._call` does the rest,
+guided by the prototype table of _lib.py."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import POINTERS, GridHipError
+
+
+class _Host:
+    """numpy arrays -> host pointers"""
+    suffix = ""
+    c128, f64, i64 = np.complex128, np.float64, np.int64
+    form, bad_grid = "a C-contiguous complex128 ndarray", ValueError
+
+    @staticmethod
+    def cv(x, dt):
+        return None if x is None else np.ascontiguousarray(x, dtype=dt)
+
+    @staticmethod
+    def empty(shape, dt, like):
+        return np.empty(shape, dtype=dt)
+
+    @staticmethod
+    def ok(x, dt):
+        return isinstance(x, np.ndarray) and x.dtype == dt and x.flags.c_contiguous
+
+    @staticmethod
+    def ptr(x):
+        return C.c_void_p(x.ctypes.data)
+
+    @staticmethod
+    def bind(owner):
+        pass
+
+
+class _Device:
+    """torch cuda tensors -> device pointers; the context is first bound to torch's current stream"""
+    suffix = "_dev"
+    form, bad_grid = "a contiguous cuda complex128 tensor", AssertionError
+
+    def __init__(self):
+        import torch
+        self.torch = torch
+        self.c128, self.f64, self.i64 = torch.complex128, torch.float64, torch.int64
+
+    @staticmethod
+    def cv(x, dt):
+        return None if x is None else x.to(dt).contiguous()  # (both return x itself when there is nothing to do)
+
+    def empty(self, shape, dt, like):
+        """like: a tensor on the device wanted, or the torch.device itself"""
+        return self.torch.empty(shape, dtype=dt, device=getattr(like, "device", like))
+
+    @staticmethod
+    def ok(x, dt):
+        return x.is_cuda and x.dtype == dt and x.is_contiguous()
+
+    @staticmethod
+    def ptr(x):
+        return C.c_void_p(x.data_ptr())
+
+    @staticmethod
+    def bind(owner):
+        owner._ctx._use_torch_stream()
+
+
+HOST = _Host()
+_device = None
+
+
+def device():
+    """the torch back end (torch is imported when the first tensor arrives)"""
+    global _device
+    if _device is None:
+        _device = _Device()
+    return _device
+
+
+def is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def backend(x):
+    """the back end of a call, chosen once by its leading array"""
+    return device() if type(x).__module__.startswith("torch") else HOST
+
+
+def baselines(be, p, k):
+    """The first k components (u, v[, w]) of a baseline argument and their element stride (include/gridhip.h,
+    uv_stride): a (u, v, w) tuple gives k contiguous float64 vectors at stride 1 - components past k are not touched,
+    the gridders take (u, v, None) - and an (n, 3) array gives views of its columns at stride 3."""
+    cv, f64 = be.cv, be.f64
+    if isinstance(p, (tuple, list)):
+        return (cv(p[0], f64), cv(p[1], f64), 1) if k == 2 else (cv(p[0], f64), cv(p[1], f64), cv(p[2], f64), 1)
+    if p.ndim == 2 and p.shape[1] == 3:
+        m = cv(p, f64)
+        return (m[:, 0], m[:, 1], 3) if k == 2 else (m[:, 0], m[:, 1], m[:, 2], 3)
+    raise ValueError("p must be a (u, v, w) tuple or an (n, 3) array")
+
+
+def imaging_function(be, imgfn):
+    """("simple",) | ("conv", kv) | ("w_cache", kernops) -> (kind, wstep, Q, npixFF, gh, gw, kv), the leading arguments
+    of gridhip_do_imaging, gridhip_predict and gridhip_imager_create_dev.  kernops = dict(wstep=, qpx=, npixFF=,
+    npixKern=) as KernelOptions (src/Gridding.hs:30-38); no wstep, or 0: 2000."""
+    if imgfn[0] == "simple":
+        return 0, 0, 0, 0, 0, 0, None
+    if imgfn[0] == "conv":
+        kv = be.cv(imgfn[1], be.c128)
+        Q, _, gh, gw = kv.shape
+        return 1, 0, Q, 0, gh, gw, kv
+    if imgfn[0] == "w_cache":
+        ko = imgfn[1]
+        side = int(ko["npixKern"])
+        return 2, int(ko.get("wstep") or 2000), int(ko["qpx"]), int(ko["npixFF"]), side, side, None
+    raise ValueError("unknown imaging function")
+
+
+def aw_tables(be, wkernels, wbins, akernels, a1, a2):
+    """-> (W, Q, S, A, wkerns, wvals, akerns), a1, a2 as gridhip_aw_imaging and every entry point with its layout take them"""
+    wk, wv, ak = be.cv(wkernels, be.c128), be.cv(wbins, be.f64), be.cv(akernels, be.c128)
+    W, Q, _, S, _ = wk.shape
+    return (W, Q, S, ak.shape[0], wk, wv, ak), be.cv(a1, be.i64), be.cv(a2, be.i64)
+
+
+def aw_kernels(be, wkerns, akerns, index):
+    """-> (W, Q, S, A, wkerns, akerns), (wbin, a1, a2) as gridhip_awgrid, gridhip_awdegrid and gridhip_aw_plan_create_dev
+    take the tables and the index triple of convgrid4"""
+    wk, ak = be.cv(wkerns, be.c128), be.cv(akerns, be.c128)
+    W, Q, _, S, _ = wk.shape
+    wbin, a1, a2 = index
+    return (W, Q, S, ak.shape[0], wk, ak), (be.cv(wbin, be.i64), be.cv(a1, be.i64), be.cv(a2, be.i64))
+
+
+class Handle:
+    """Owner of one library handle `_h` (a context, plan, imager or communicator): destroyed once, by close() or by the
+    collector; _call passes it to an entry point and raises GridHipError with the owner's last-error text."""
+    _destroy = _what = None  # gridhip_*_destroy; the name _open() refuses by
+    _ctx = None              # the Context whose stream a device call runs on
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self):
+        assert self._h, f"{self._what} is closed"
+
+    def _check(self, rc):
+        if rc != 0:
+            raise GridHipError(rc, self._error(rc))
+
+    def _call(self, be, name, *args):
+        """gridhip_<name>(handle, args...) for host arguments, gridhip_<name>_dev on torch's current stream for device
+        arguments.  The arguments the prototype takes as `void *` are arrays (or None) and go by address, everything
+        else as it is."""
+        be.bind(self)
+        name = "gridhip_" + name + be.suffix
+        args, ptr = list(args), be.ptr
+        for i in POINTERS[name]:
+            if args[i] is not None:
+                args[i] = ptr(args[i])
+        self._check(getattr(self._lib, name)(self._h, *args))

@@ -6,7 +6,12 @@ stream onto a private N x N complex128 grid and ONE fp64 sum all-reduce of the 2
 combines the partial grids (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU
 tests).  The reference itself is single-process; this is new surface.
 """
+import ctypes as C
+
 import numpy as np
+
+from . import _lib
+from ._marshal import HOST, Handle
 
 
 def shard_bounds(n, world, rank):
@@ -185,54 +190,41 @@ def sharded_convgrid2(gridder, gcf, a, p, wbin, v, rank, world, group=None, redu
     return a
 
 
-class Comm:
+class Comm(Handle):
     """libgridhip's own RCCL communicator (include/gridhip.h, gridhip_comm_*): the multi-GPU surface a
     non-Python host binds.  Comm.single_process(ndev) drives ndev devices from this process
     (ncclCommInitAll); Comm.from_torch(ctx) is the one-process-per-GPU form, the 128-byte id travelling
     over the already initialised torch.distributed group."""
+    _destroy = "gridhip_comm_destroy"
 
     def __init__(self, handle, lib, ctxs=None):
         self._h, self._lib, self.ctxs = handle, lib, ctxs or []
 
-    @staticmethod
-    def _err(lib, rc, h=None):
-        from ._lib import GridHipError
-        return GridHipError(rc, (lib.gridhip_comm_last_error(h) or b"").decode())
+    def _error(self, rc):
+        return (self._lib.gridhip_comm_last_error(self._h) or b"").decode()  # (no handle yet: the last failed creation)
 
     @classmethod
     def single_process(cls, ndev, dev_ids=None):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        h = C.c_void_p()
+        self = cls(C.c_void_p(), _lib.load())
         ids = (C.c_int * ndev)(*dev_ids) if dev_ids is not None else None
-        rc = lib.gridhip_comm_create(int(ndev), ids, C.byref(h))
-        if rc != 0:
-            raise cls._err(lib, rc)
-        return cls(h, lib)
+        self._check(self._lib.gridhip_comm_create(int(ndev), ids, C.byref(self._h)))
+        return self
 
     @classmethod
     def from_torch(cls, ctx, group=None):
-        import ctypes as C
         import torch
         import torch.distributed as dist
-        from . import _lib
-        lib = _lib.load()
+        self = cls(C.c_void_p(), _lib.load(), [ctx])
         rank, world = dist.get_rank(group), dist.get_world_size(group)
         buf = (C.c_char * 128)()
         if rank == 0:
-            rc = lib.gridhip_comm_unique_id(buf)
-            if rc != 0:
-                raise cls._err(lib, rc)
+            self._check(self._lib.gridhip_comm_unique_id(buf))
         dev = torch.device("cuda", ctx.device) if dist.get_backend(group) == "nccl" else torch.device("cpu")
         t = torch.frombuffer(bytearray(buf.raw), dtype=torch.uint8).to(dev)
         dist.broadcast(t, src=0, group=group)
         ident = (C.c_char * 128).from_buffer_copy(bytes(t.cpu().numpy().tobytes()))
-        h = C.c_void_p()
-        rc = lib.gridhip_comm_create_rank(ctx._h, world, rank, ident, C.byref(h))
-        if rc != 0:
-            raise cls._err(lib, rc)
-        return cls(h, lib, [ctx])
+        self._check(self._lib.gridhip_comm_create_rank(ctx._h, world, rank, ident, C.byref(self._h)))
+        return self
 
     @property
     def ndev(self):
@@ -245,69 +237,36 @@ class Comm:
     def allreduce_grid(self, grid):
         """In-place fp64 sum over the communicator of a cuda complex128 tensor (rank form), enqueued on the
         context's stream."""
-        import ctypes as C
-        rc = self._lib.gridhip_comm_allreduce_grid(self._h, grid.numel(), C.c_void_p(grid.data_ptr()))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._check(self._lib.gridhip_comm_allreduce_grid(self._h, grid.numel(), C.c_void_p(grid.data_ptr())))
         return grid
 
     def allreduce_grid_rows(self, grid, y0, y1):
         """The same for rows [y0, y1) only (gridhip_comm_allreduce_grid_rows)."""
-        import ctypes as C
         assert grid.dim() == 2 and grid.is_contiguous() and 0 <= y0 <= y1 <= grid.shape[0]
-        rc = self._lib.gridhip_comm_allreduce_grid_rows(self._h, grid.shape[1], int(y0), int(y1), C.c_void_p(grid.data_ptr()))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._check(self._lib.gridhip_comm_allreduce_grid_rows(self._h, grid.shape[1], int(y0), int(y1),
+                                                               C.c_void_p(grid.data_ptr())))
         return grid
 
     def set_option(self, key, value):
-        rc = self._lib.gridhip_comm_set_option(self._h, key.encode(), int(value))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._check(self._lib.gridhip_comm_set_option(self._h, key.encode(), int(value)))
 
     def get_option(self, key):
-        import ctypes as C
         v = C.c_int64()
-        rc = self._lib.gridhip_comm_get_option(self._h, key.encode(), C.byref(v))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._check(self._lib.gridhip_comm_get_option(self._h, key.encode(), C.byref(v)))
         return v.value
 
     def set_stream(self, stream_ptr, i=0):
         """Enqueue device i's collectives on this hipStream_t instead of its context's stream."""
-        import ctypes as C
-        rc = self._lib.gridhip_comm_set_stream(self._h, int(i), C.c_void_p(stream_ptr or 0))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._check(self._lib.gridhip_comm_set_stream(self._h, int(i), C.c_void_p(stream_ptr or 0)))
 
     def reset_stream(self, i=0):
-        rc = self._lib.gridhip_comm_reset_stream(self._h, int(i))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._check(self._lib.gridhip_comm_reset_stream(self._h, int(i)))
 
     def convgrid2(self, gcf, a, p, wbin, v):
         """convgrid2 over all devices of the communicator, numpy host arrays (gridhip_comm_convgrid2)."""
-        import ctypes as C
-        gcf = np.ascontiguousarray(gcf, dtype=np.complex128)
-        u, vv = np.ascontiguousarray(p[0], dtype=np.float64), np.ascontiguousarray(p[1], dtype=np.float64)
-        vis = np.ascontiguousarray(v, dtype=np.complex128)
-        wb = None if wbin is None else np.ascontiguousarray(wbin, dtype=np.int64)
+        gcf, vis, wb = HOST.cv(gcf, HOST.c128), HOST.cv(v, HOST.c128), HOST.cv(wbin, HOST.i64)
+        u, vv = HOST.cv(p[0], HOST.f64), HOST.cv(p[1], HOST.f64)
         assert a.dtype == np.complex128 and a.flags.c_contiguous
         W, Q, _, gh, gw = gcf.shape
-        ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)
-        rc = self._lib.gridhip_comm_convgrid2(self._h, a.shape[0], a.shape[1], ptr(a), len(u), W, Q, gh, gw, ptr(gcf),
-                                              ptr(u), ptr(vv), 1, ptr(wb), ptr(vis))
-        if rc != 0:
-            raise self._err(self._lib, rc, self._h)
+        self._call(HOST, "comm_convgrid2", a.shape[0], a.shape[1], a, len(u), W, Q, gh, gw, gcf, u, vv, 1, wb, vis)
         return a
-
-    def close(self):
-        if self._h:
-            self._lib.gridhip_comm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

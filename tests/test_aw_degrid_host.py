@@ -41,6 +41,18 @@ def test_python_binding_has_the_aw_gather_and_plans():
         assert callable(getattr(gridhip.AwPlan, name))
 
 
+def test_closed_plans_refuse_a_pass_before_the_library():
+    """Plan and AwPlan alike: no null handle reaches gridhip_plan_grid_dev / gridhip_aw_plan_grid_dev"""
+    import gridhip
+    for plan, tables in ((gridhip.Plan(None, None, 0, (8, 8), (1, 1, 1, 5, 5)), (None,)),
+                         (gridhip.AwPlan(None, None, 0, (8, 8)), ())):
+        with pytest.raises(AssertionError, match="plan is closed"):
+            plan.grid(*tables, None, None)
+        with pytest.raises(AssertionError, match="plan is closed"):
+            plan.degrid(*tables, None)
+        plan.close()
+
+
 def test_null_arguments_are_refused_without_a_device():
     import ctypes as C
     from gridhip import _lib

@@ -236,3 +236,13 @@ def test_plan_edge_cases(ctx):
     a64[6], a64[8], a64[9] = 64, p(big), p(big)
     assert lib.gridhip_aw_plan_create_dev(*a64, C.byref(pl)) == _lib.EUNSUPPORTED
     assert dv(p(g), 100, 2, 2, 64, 3, p(big), p(big), p(u), p(v), 1, p(wb), p(a1), p(a2), p(vis)) == _lib.EUNSUPPORTED
+    # a closed plan of either kind refuses a pass before it reaches the library
+    gcf = torch.zeros((2, 2, 2, 7, 7), dtype=torch.complex128, device="cuda:0")
+    aw = ctx.aw_plan(g.shape, wk, ak, (u, v, None), (wb, a1, a2))
+    w2 = ctx.plan(g.shape, gcf.shape, (u, v, None), wb)
+    aw.grid(g, vis), w2.grid(gcf, g, vis)
+    aw.close(), w2.close()
+    aw.close(), w2.close()  # (closing twice is harmless)
+    for call in (lambda: aw.grid(g, vis), lambda: aw.degrid(g), lambda: w2.grid(gcf, g, vis), lambda: w2.degrid(gcf, g)):
+        with pytest.raises(AssertionError, match="plan is closed"):
+            call()
