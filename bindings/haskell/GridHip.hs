@@ -30,6 +30,8 @@ module GridHip
   , predictIO
   -- * imagers: the baselines of a major cycle bound once, one call per cycle (include/gridhip.h, gridhip_imager_*)
   , ImagerH, withImager, imagerCycleIO
+  -- * deconvolution: Hogbom CLEAN, alone or inside an imager's major-cycle loop (absent from the reference)
+  , CleanOptions(..), cleanIO, imagerCleanIO, imagerDeconvolveIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -252,6 +254,18 @@ foreign import ccall unsafe "gridhip_imager_predict_dev"
 -- int gridhip_imager_destroy(imager)
 foreign import ccall unsafe "gridhip_imager_destroy"
   c_imager_destroy :: Ptr Imager -> IO CInt
+-- int gridhip_clean(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_clean"
+  c_clean :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_clean_dev(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_clean_dev"
+  c_clean_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_clean_dev(imager, residual, model, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_imager_clean_dev"
+  c_imager_clean_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_deconvolve_dev(imager, vis, model, image, nmajor, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_imager_deconvolve_dev"
+  c_imager_deconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -681,6 +695,73 @@ imagerCycleIO (ImagerH h@(GridHip c) p n n') model vis = do
       c_memcpy_d2h c (castPtr pr) (castPtr dv) (fi (16 * n)) >>= check h
       c_synchronize c >>= check h
   return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr img), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr res))
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Deconvolution (include/gridhip.h, "deconvolution"): Hogbom CLEAN of a real N x N image.
+
+-- | gain, threshold, niter, border, patch as gridhip_clean takes them
+data CleanOptions = CleanOptions { cleanGain :: F, cleanThreshold :: F, cleanNiter :: Int, cleanBorder :: Int
+                                 , cleanPatch :: Int }
+
+-- [iterations, final peak, its flat index, flux added] per row of a stats block
+statsRows :: Int -> Ptr CDouble -> IO [[F]]
+statsRows rows p = mapM (\r -> map realToFrac <$> peekArray 4 (p `advancePtr` (4 * r))) [0 .. rows - 1]
+
+-- | cleanIO h opts image psf model: (model + the components found, the residual, the stats) - the host form, synchronous
+cleanIO :: GridHip -> CleanOptions -> A.Matrix F -> A.Matrix F -> A.Matrix F -> IO (A.Matrix F, A.Matrix F, [F])
+cleanIO h@(GridHip c) (CleanOptions g t ni b pa) image psf model = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape image
+      copyOf m = do o <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+                    withF m $ \s -> withForeignPtr o $ \d -> copyArray d s (n' * n')
+                    return o
+  res <- copyOf image
+  mdl <- copyOf model
+  st <- withF psf $ \pp -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pm -> allocaArray 4 $ \ps -> do
+          c_clean c (fi n') pp pr pm (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ps >>= check h
+          head <$> statsRows 1 ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
+
+-- | imagerCleanIO im opts image model: cleanIO with the imager's own PSF (gridhip_imager_clean_dev; the host arrays are
+-- staged as imagerCycleIO stages them)
+imagerCleanIO :: ImagerH -> CleanOptions -> A.Matrix F -> A.Matrix F -> IO (A.Matrix F, A.Matrix F, [F])
+imagerCleanIO (ImagerH h@(GridHip c) p _ n') (CleanOptions g t ni b pa) image model = do
+  res <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+  st <- withF image $ \pi' -> withDev h pi' bytes $ \di -> withF model $ \pm -> withDev h pm bytes $ \dm ->
+          allocaArray 4 $ \ps -> withDev h ps 32 $ \ds -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pq -> do
+            c_imager_clean_dev p di dm (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ds >>= check h
+            c_memcpy_d2h c (castPtr pr) (castPtr di) (fi bytes) >>= check h
+            c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+            c_memcpy_d2h c (castPtr ps) (castPtr ds) 32 >>= check h
+            c_synchronize c >>= check h
+            head <$> statsRows 1 ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
+
+-- | imagerDeconvolveIO im opts nmajor vis model: nmajor times (imagerCycleIO, imagerCleanIO) and one closing cycle in
+-- one call on the device (gridhip_imager_deconvolve_dev): (the model, the closing residual image, one stats row per
+-- major cycle)
+imagerDeconvolveIO :: ImagerH -> CleanOptions -> Int -> A.Vector Visibility -> A.Matrix F
+                   -> IO (A.Matrix F, A.Matrix F, [[F]])
+imagerDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) nmajor vis model = do
+  img <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+      rows = max 0 nmajor
+  st <- withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withF model $ \pm -> withDev h pm bytes $ \dm ->
+          withForeignPtr img $ \pi' -> withDev h pi' bytes $ \di -> allocaArray (4 * rows) $ \ps ->
+            withDev h ps (32 * rows) $ \ds -> withForeignPtr mdl $ \pq -> do
+              c_imager_deconvolve_dev p dv dm di (fi nmajor) (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ds
+                >>= check h
+              c_memcpy_d2h c (castPtr pi') (castPtr di) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr ps) (castPtr ds) (fi (32 * rows)) >>= check h
+              c_synchronize c >>= check h
+              statsRows rows ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

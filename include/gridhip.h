@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 150 /* 0.1.5 */
+#define GRIDHIP_VERSION 160 /* 0.1.6 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -453,7 +453,8 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
  * pass over the visibilities turns into the gridder's input in place) + 2 x 8 B records (x P for sub-footprints), or
  * 4 x 8 B coordinates instead of records for the simple kind; per N^2 cell 16 B (grid) + 16 B (transform) + 8 B (psf),
  * and 16 B more for odd N; the kernel tables (conv: 2 tables; w_cache: one plane per w-bin of each stream; aw: each
- * batch's distinct kernels, twice) and one hipFFT plan.
+ * batch's distinct kernels, twice) and one hipFFT plan; after its first clean or deconvolve also clean's state block and
+ * tile table, 64 B + 16 B per 16 x 128 cells (released at destroy).
  * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
  * and 1).  n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
  * touches nothing.  An imager belongs to its context (same device, same stream, not thread-safe) and must be destroyed
@@ -477,6 +478,60 @@ int gridhip_imager_cycle_dev(gridhip_imager *imager, const double *model, const 
 /* the prediction alone, gridhip_predict's vis_sub / vis_out rules */
 int gridhip_imager_predict_dev(gridhip_imager *imager, const double *model, const double *vis_sub, double *vis_out);
 int gridhip_imager_destroy(gridhip_imager *imager);
+
+/* ---- deconvolution: Hogbom CLEAN on the device, the minor cycle between two major cycles ------------------------------
+ * The reference has no deconvolution: the semantics are defined here.  psf, residual and model are real N x N images,
+ * row-major [y][x], laid out as do_imaging's `image` and `psf`.  The PSF's zero-lag cell is c = (N / 2, N / 2) in integer
+ * division, for even and odd N: where gridhip_fft2_centered(inverse = 1) puts it, and where an imager's PSF has its
+ * maximum.
+ *     repeat at most niter times:
+ *         k = the flat index y * N + x with the largest |residual[k]| over the cells border <= y, x < N - border;
+ *             ties go to the lowest flat index; a NaN cell is never selected
+ *         p = residual[k]
+ *         if |p| <= threshold: stop                            (tested before anything is subtracted)
+ *         f = gain * p                                         (rounded once)
+ *         model[k] += f
+ *         residual[y', x'] -= f * psf[y' - y + c, x' - x + c]  for every cell whose PSF index lies in the grid and, when
+ *                                                              patch > 0, within |y' - y| <= patch and |x' - x| <= patch
+ *     stats = { iterations performed, residual[k*] (signed), k* as a double, sum of all f added }
+ *             where k* is the peak of the final residual under the same search rule
+ * The product f * psf is rounded before it is subtracted (no fused multiply-add), every comparison is (|value|, lower
+ * index wins) and nothing is accumulated with atomics: a call is deterministic, bit for bit, whatever the scheduling,
+ * and the host, _dev and imager forms give the same bits.  residual is updated in place.  model is accumulated into,
+ * never zeroed (model = model + clean(...) is one call on the same model).  stats is four doubles, written on the
+ * device (a host array for gridhip_clean); it may be NULL.  niter = 0 is valid: it changes nothing and reports the
+ * current peak.  If no cell can be selected (every searched cell is NaN) the loop stops and stats reports a NaN peak at
+ * index -1.  All arguments are checked before anything is touched, GRIDHIP_EINVAL: N >= 1, 0 < gain <= 1,
+ * threshold >= 0, niter >= 0, 0 <= border, 2 * border < N, patch >= 0, non-NULL psf, residual and model, no two of the
+ * three arrays overlapping (nmajor >= 0 and, for an imager with visibilities, non-NULL vis for deconvolve).  N above
+ * 1048560 is GRIDHIP_EUNSUPPORTED.
+ * The image is cut into tiles of 16 rows x 128 columns and a device table keeps each tile's peak; it is built by one pass
+ * over the residual per call.  An iteration is two kernels: one subtracts the shifted, scaled PSF from the tiles the PSF
+ * (or the patch) overlaps - it is launched over those tiles only - and recomputes their table entries in the same pass;
+ * a one-work-group kernel reduces the table to the next peak, tests the stop rule and takes the next component.  With
+ * patch > 0 an iteration costs the patch area plus the table, not N^2.  The stop condition lives on the device: niter
+ * iterations are enqueued unconditionally, and a launch whose state is stopped or out of iterations returns at its first
+ * instruction.  gridhip_clean is synchronous and stages host arrays through the context's pool.  The _dev forms take
+ * device pointers, enqueue kernels only on the context's stream (2 + 2 * niter launches; no memset or copy node),
+ * allocate nothing after the first call of a shape, never synchronise and read nothing back, so they can be captured
+ * into a graph like an imager's cycle.  Scratch (64 B + 16 B per tile) comes from the context's pool, or for the imager
+ * forms from memory the imager owns. */
+int gridhip_clean(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                  double threshold, int64_t niter, int64_t border, int64_t patch, double *stats);
+int gridhip_clean_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                      double threshold, int64_t niter, int64_t border, int64_t patch, double *stats);
+/* gridhip_clean_dev with the imager's own PSF (nothing is copied) and N */
+int gridhip_imager_clean_dev(gridhip_imager *imager, double *residual, double *model, double gain, double threshold,
+                             int64_t niter, int64_t border, int64_t patch, double *stats);
+/* visibilities -> model image in one call, DEFINED BY THE CALLS IT REPLACES:
+ *     repeat nmajor times: image = cycle(model, vis); clean(image, model) with stats + 4 * i (when stats != NULL)
+ *     image = cycle(model, vis)
+ * so that on return image is do_imaging(vis - predict(model))'s image for the returned model.  model is the caller's
+ * and must be initialised (zeros for a fresh start); stats is nmajor x 4 doubles on the device, or NULL.  Asynchronous,
+ * allocation-free after the first call and capturable, as cycle and clean are. */
+int gridhip_imager_deconvolve_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
+                                  int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
+                                  int64_t patch, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -145,6 +145,7 @@ struct gridhip_imager {
     // aw: the same as aw plans, which hold their batches' kernel tables themselves
     gridhip_aw_plan *aw_gather = nullptr, *aw_scatter = nullptr;
     bool clear_pred = false;  // the gather does not write every prediction: they start from zero
+    void *clean_scratch = nullptr;  // clean's state block and tile table (clean.hip), made by the first clean
 };
 
 namespace {
@@ -435,6 +436,34 @@ int gridhip_imager_predict_dev(gridhip_imager *im, const double *model, const do
     if (im->n == 0) return GRIDHIP_OK;
     GH_CHECK(gather(im, model));
     return launch_residual(ctx, im->n, im->pred, (const double2 *)vis_sub, (double2 *)vis_out);
+}
+
+int gridhip_imager_clean_dev(gridhip_imager *im, double *residual, double *model, double gain, double threshold,
+                             int64_t niter, int64_t border, int64_t patch, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(clean_check(ctx, im->N, im->psf, residual, model, gain, threshold, niter, border, patch));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!im->clean_scratch) GH_CHECK(own(im, &im->clean_scratch, clean_scratch_bytes(im->N)));
+    return clean_run(ctx, im->N, im->psf, residual, model, gain, threshold, niter, border, patch, stats,
+                     im->clean_scratch);
+}
+
+int gridhip_imager_deconvolve_dev(gridhip_imager *im, const double *vis, double *model, double *image, int64_t nmajor,
+                                  double gain, double threshold, int64_t niter, int64_t border, int64_t patch,
+                                  double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "deconvolve: bad argument");
+    GH_CHECK(clean_check(ctx, im->N, im->psf, image, model, gain, threshold, niter, border, patch));
+    for (int64_t c = 0; c < nmajor; ++c) {
+        GH_CHECK(gridhip_imager_cycle_dev(im, model, vis, image, nullptr));
+        GH_CHECK(gridhip_imager_clean_dev(im, image, model, gain, threshold, niter, border, patch,
+                                          stats ? stats + 4 * c : nullptr));
+    }
+    return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
 }
 
 int gridhip_imager_destroy(gridhip_imager *im)

@@ -1,6 +1,6 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
-// streaming image operations, the imaging functions, prediction and imagers (api.hip, comm.hip, awgrid.hip's entry
-// points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip).
+// streaming image operations, the imaging functions, prediction, imagers and deconvolution (api.hip, comm.hip, awgrid.hip's entry
+// points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -249,5 +249,15 @@ struct AwFront {
     DevBuf pu, pv, wb, vis1, wt, cell, cnt;
 };
 int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt, AwFront &f);
+
+// ---- deconvolution (clean.hip) -------------------------------------------------------------------------------------------
+// gridhip_clean's argument rules (GRIDHIP_EINVAL; an N the tile grid cannot hold is GRIDHIP_EUNSUPPORTED)
+int clean_check(gridhip_ctx *ctx, int64_t N, const double *psf, const double *residual, const double *model, double gain,
+                double threshold, int64_t niter, int64_t border, int64_t patch);
+// the state block and the tile table of an N x N clean
+size_t clean_scratch_bytes(int64_t N);
+// gridhip_clean_dev on checked arguments: kernels only, on ctx->stream; scratch: clean_scratch_bytes(N) of device memory
+int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
 
 }  // namespace gridhip

@@ -11,6 +11,7 @@
 //   simple_imaging / conv_imaging / w_cache_imaging / aw_imaging   :84, :115, :399, :452
 //   do_imaging theta lam uvw a1 a2 t f vis imgfn    :509-519 (do_imaging_aw: imgfn = aw_imaging)
 //   predict / predict_aw: the way back, model image -> visibilities (absent from the reference)
+//   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -265,6 +266,23 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
                                  model.data.data(), (Int)uvw.size(), uvw.u.data(), uvw.v.data(), uvw.w.data(), 1,
                                  a1.data(), a2.data(), vis_sub ? cd(*vis_sub) : nullptr, cd(out)));
         return out;
+    }
+
+    // ---- deconvolution: Hogbom CLEAN (gridhip_clean; include/gridhip.h, "deconvolution") ----
+    // image and psf as do_imaging returns them; `model` is accumulated into (model = model + clean(...)) and `image`
+    // becomes the residual, both in place.  Returns {iterations, final peak, its flat index, flux added}.
+    struct CleanStats {
+        F iterations, peak, index, flux;
+    };
+    CleanStats clean(Matrix<F> &image, const Matrix<F> &psf, Matrix<F> &model, F gain = 0.1, F threshold = 0.0,
+                     Int niter = 100, Int border = 0, Int patch = 0)
+    {
+        if (image.h != image.w || psf.h != image.h || psf.w != image.w || model.h != image.h || model.w != image.w)
+            throw Error(GRIDHIP_EINVAL, "clean: image, psf and model must be N x N");
+        F st[4] = {0, 0, 0, 0};
+        check(gridhip_clean(ctx_, image.h, psf.data.data(), image.data.data(), model.data.data(), gain, threshold, niter,
+                            border, patch, st));
+        return {st[0], st[1], st[2], st[3]};
     }
 
     // ---- helpers ----

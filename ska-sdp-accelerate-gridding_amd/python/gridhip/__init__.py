@@ -23,7 +23,8 @@ import ctypes as C
 
 from . import _lib
 from ._lib import GridHipError, LIB_PATH  # noqa: F401
-from ._marshal import HOST, Handle, aw_kernels, aw_tables, backend, baselines, device, imaging_function, is_torch
+from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, clean_scalars, device, imaging_function,
+                       in_place, is_torch)
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
 
@@ -358,6 +359,27 @@ class Context(Handle):
             self._call(be, "predict", *imaging_function(be, imgfn), *tl, model, n, u, v, w, st, sub, out)
         return out
 
+    def clean(self, image, psf, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None):
+        """Hogbom CLEAN of the N x N float64 `image` with `psf` (gridhip_clean[_dev]; include/gridhip.h,
+        "deconvolution"): at most niter components of gain * peak, searched inside `border`, stopping at |peak| <=
+        threshold, the PSF subtracted over its whole overlap or (patch > 0) within +-patch cells of the peak.
+        `image` is UPDATED IN PLACE and returned as the residual; `model` (zeros when None) is accumulated into and
+        returned, so `model, residual, stats = ctx.clean(image, psf, model=model)` is model = model + clean(image, psf).
+        stats = [iterations, final peak, its flat index, flux added].  numpy arrays take the synchronous host form;
+        torch cuda tensors the asynchronous one on torch's stream, with stats a cuda tensor: nothing is read back."""
+        be = backend(image)
+        shape = tuple(getattr(image, "shape", ()))
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("image must be N x N")
+        image = in_place(be, image, shape, "image")
+        psf = be.cv(psf, be.f64)
+        if tuple(psf.shape) != shape:
+            raise ValueError(f"psf must be {shape}, as the image")
+        model = in_place(be, model, shape, "model", image)
+        stats = be.empty(4, be.f64, image)
+        self._call(be, "clean", shape[0], psf, image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return model, image, stats
+
     def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None):
         """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
         and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
@@ -516,6 +538,36 @@ class Imager(_Bound):
             self._ok(out, be.c128, (self.n,), "out")
         self._call(be, "imager_predict", model, vis_sub, out)
         return out
+
+
+    def clean(self, image, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+        """Context.clean with the imager's own PSF (gridhip_imager_clean_dev): `image` (N x N cuda float64, a cycle's
+        output) is updated in place and returned as the residual, `model` (zeros when None) is accumulated into.
+        Returns (model, residual, stats); asynchronous, and capturable after a first call."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        image = in_place(be, image, NN, "image")
+        model = in_place(be, model, NN, "model", self.device)
+        stats = be.empty(4, be.f64, self.device)
+        self._call(be, "imager_clean", image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return model, image, stats
+
+    def deconvolve(self, vis, nmajor, model=None, out=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+        """Visibilities to a model image in one asynchronous call (gridhip_imager_deconvolve_dev): nmajor times
+        image = cycle(vis, model) then clean(image, model), and one closing cycle, so that the returned image is
+        do_imaging(vis - predict(model))'s for the returned model.  model (zeros when None) is accumulated into, out
+        (a new image when None) receives the closing residual image.  Returns (model, image, stats[nmajor, 4])."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        self._ok(vis, be.c128, (self.n,), "vis")
+        model = in_place(be, model, NN, "model", self.device)
+        out = be.empty(NN, be.f64, self.device) if out is None else in_place(be, out, NN, "out")
+        if int(nmajor) < 0:
+            raise ValueError("nmajor must be >= 0")
+        stats = be.empty((int(nmajor), 4), be.f64, self.device)
+        self._call(be, "imager_deconvolve", vis, model, out, int(nmajor),
+                   *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return model, out, stats
 
 
 _default = {}

@@ -33,6 +33,7 @@ _DO_IMAGING_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, 
 _AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp,
                 C.POINTER(C.c_double)]
 _PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, vp, vp, i64, vp, vp]
+_CLEAN = [vp, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -102,6 +103,10 @@ SIGNATURES = {
     "gridhip_imager_cycle_dev": (ci, [vp, vp, vp, vp, vp]),
     "gridhip_imager_predict_dev": (ci, [vp, vp, vp, vp]),
     "gridhip_imager_destroy": (ci, [vp]),
+    "gridhip_clean": (ci, _CLEAN),
+    "gridhip_clean_dev": (ci, _CLEAN),
+    "gridhip_imager_clean_dev": (ci, [vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]),
+    "gridhip_imager_deconvolve_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

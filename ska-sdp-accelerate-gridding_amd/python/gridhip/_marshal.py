@@ -28,6 +28,10 @@ class _Host:
         return np.empty(shape, dtype=dt)
 
     @staticmethod
+    def zeros(shape, dt, like):
+        return np.zeros(shape, dtype=dt)
+
+    @staticmethod
     def ok(x, dt):
         return isinstance(x, np.ndarray) and x.dtype == dt and x.flags.c_contiguous
 
@@ -57,6 +61,9 @@ class _Device:
     def empty(self, shape, dt, like):
         """like: a tensor on the device wanted, or the torch.device itself"""
         return self.torch.empty(shape, dtype=dt, device=getattr(like, "device", like))
+
+    def zeros(self, shape, dt, like):
+        return self.torch.zeros(shape, dtype=dt, device=getattr(like, "device", like))
 
     @staticmethod
     def ok(x, dt):
@@ -136,6 +143,23 @@ def aw_kernels(be, wkerns, akerns, index):
     W, Q, _, S, _ = wk.shape
     wbin, a1, a2 = index
     return (W, Q, S, ak.shape[0], wk, ak), (be.cv(wbin, be.i64), be.cv(a1, be.i64), be.cv(a2, be.i64))
+
+
+def in_place(be, x, shape, what, like=None):
+    """An N x N float64 image an entry point updates in place (clean's residual and model, deconvolve's image): the
+    caller's own array, which must be in the form the ABI takes - a converted copy would take the update with it - or,
+    for None, a new one of zeros on `like`'s device."""
+    if x is None and like is not None:
+        return be.zeros(shape, be.f64, like)
+    if not (be is backend(x) and be.ok(x, be.f64) and tuple(x.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be {be.form.replace('complex128', 'float64')} of shape {tuple(shape)}"
+                         " (it is updated in place)")
+    return x
+
+
+def clean_scalars(gain, threshold, niter, border, patch):
+    """gain, threshold, niter, border, patch as every clean entry point takes them"""
+    return float(gain), float(threshold), int(niter), int(border), int(patch)
 
 
 class Handle:
