@@ -32,6 +32,8 @@ module GridHip
   , ImagerH, withImager, imagerCycleIO
   -- * deconvolution: Hogbom CLEAN, alone or inside an imager's major-cycle loop (absent from the reference)
   , CleanOptions(..), cleanIO, imagerCleanIO, imagerDeconvolveIO
+  -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
+  , fitBeamIO, restoreIO, imagerBeamIO, imagerRestoreIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -266,6 +268,24 @@ foreign import ccall unsafe "gridhip_imager_clean_dev"
 -- int gridhip_imager_deconvolve_dev(imager, vis, model, image, nmajor, gain, threshold, niter, border, patch, stats)
 foreign import ccall unsafe "gridhip_imager_deconvolve_dev"
   c_imager_deconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_fit_beam(ctx, N, psf, window, cut, beam)
+foreign import ccall unsafe "gridhip_fit_beam"
+  c_fit_beam :: Ptr Ctx -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fit_beam_dev(ctx, N, psf, window, cut, beam)
+foreign import ccall unsafe "gridhip_fit_beam_dev"
+  c_fit_beam_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_restore(ctx, N, model, residual, beam, support, restored)
+foreign import ccall unsafe "gridhip_restore"
+  c_restore :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_restore_dev(ctx, N, model, residual, beam, support, restored)
+foreign import ccall unsafe "gridhip_restore_dev"
+  c_restore_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_beam_dev(imager, window, cut, beam)
+foreign import ccall unsafe "gridhip_imager_beam_dev"
+  c_imager_beam_dev :: Ptr Imager -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_restore_dev(imager, model, residual, window, cut, support, restored, beam)
+foreign import ccall unsafe "gridhip_imager_restore_dev"
+  c_imager_restore_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -762,6 +782,53 @@ imagerDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) nma
               statsRows rows ps
   let sh = A.Z A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Restoring beam and restore (include/gridhip.h, "restoring beam and restore").  A beam is the 8 values
+-- [A, B, C, bmaj, bmin, bpa, ncells, ok] of the fit: FWHMs in cells, bpa in radians, ok = 0 and NaNs when it failed.
+
+-- | fitBeamIO h window cut psf: the elliptical Gaussian fitted to the PSF's main lobe - the host form, synchronous
+fitBeamIO :: GridHip -> Int -> F -> A.Matrix F -> IO [F]
+fitBeamIO h@(GridHip c) window cut psf = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape psf
+  withF psf $ \pp -> allocaArray 8 $ \pb -> do
+    c_fit_beam c (fi n') pp (fi window) (realToFrac cut) pb >>= check h
+    map realToFrac <$> peekArray 8 pb
+
+-- | restoreIO h support beam model residual: model convolved with the beam over +-support cells (1 to 32) + residual,
+-- in units per beam - the host form, synchronous; a failed beam is refused
+restoreIO :: GridHip -> Int -> [F] -> A.Matrix F -> A.Matrix F -> IO (A.Matrix F)
+restoreIO h@(GridHip c) support beam model residual = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape model
+  out <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  withF model $ \pm -> withF residual $ \pr -> withArray (map realToFrac beam) $ \pb -> withForeignPtr out $ \po ->
+    c_restore c (fi n') pm pr pb (fi support) po >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr out))
+
+-- | imagerBeamIO im window cut: fitBeamIO on the imager's own PSF (gridhip_imager_beam_dev)
+imagerBeamIO :: ImagerH -> Int -> F -> IO [F]
+imagerBeamIO (ImagerH h@(GridHip c) p _ _) window cut =
+  allocaArray 8 $ \pb -> withDev h pb 64 $ \db -> do
+    c_imager_beam_dev p (fi window) (realToFrac cut) db >>= check h
+    c_memcpy_d2h c (castPtr pb) (castPtr db) 64 >>= check h
+    c_synchronize c >>= check h
+    map realToFrac <$> peekArray 8 pb
+
+-- | imagerRestoreIO im window cut support model residual: (the restored image, the beam fitted to the imager's own
+-- PSF) in one call on the device (gridhip_imager_restore_dev; the host arrays are staged as imagerCycleIO stages them).
+-- A failed fit gives an image of NaNs and a beam whose ok is 0.
+imagerRestoreIO :: ImagerH -> Int -> F -> Int -> A.Matrix F -> A.Matrix F -> IO (A.Matrix F, [F])
+imagerRestoreIO (ImagerH h@(GridHip c) p _ n') window cut support model residual = do
+  out <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+  beam <- withF model $ \pm -> withDev h pm bytes $ \dm -> withF residual $ \pr -> withDev h pr bytes $ \dr ->
+            allocaArray 8 $ \pb -> withDev h pb 64 $ \db -> withForeignPtr out $ \po -> do
+              c_imager_restore_dev p dm dr (fi window) (realToFrac cut) (fi support) dr db >>= check h
+              c_memcpy_d2h c (castPtr po) (castPtr dr) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr pb) (castPtr db) 64 >>= check h
+              c_synchronize c >>= check h
+              map realToFrac <$> peekArray 8 pb
+  return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr out), beam)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

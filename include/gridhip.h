@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 160 /* 0.1.6 */
+#define GRIDHIP_VERSION 170 /* 0.1.7 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -454,7 +454,8 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
  * 4 x 8 B coordinates instead of records for the simple kind; per N^2 cell 16 B (grid) + 16 B (transform) + 8 B (psf),
  * and 16 B more for odd N; the kernel tables (conv: 2 tables; w_cache: one plane per w-bin of each stream; aw: each
  * batch's distinct kernels, twice) and one hipFFT plan; after its first clean or deconvolve also clean's state block and
- * tile table, 64 B + 16 B per 16 x 128 cells (released at destroy).
+ * tile table, 64 B + 16 B per 16 x 128 cells, and after its first restore without a `beam` output 64 B for the fitted beam
+ * (all released at destroy).
  * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
  * and 1).  n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
  * touches nothing.  An imager belongs to its context (same device, same stream, not thread-safe) and must be destroyed
@@ -532,6 +533,65 @@ int gridhip_imager_clean_dev(gridhip_imager *imager, double *residual, double *m
 int gridhip_imager_deconvolve_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
                                   int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
                                   int64_t patch, double *stats);
+
+/* ---- restoring beam and restore: from clean's model and residual to a map, on the device -----------------------------
+ * The reference stops at the dirty image: the semantics are defined here.  All images are real N x N, row-major [y][x];
+ * the PSF's zero-lag cell is c = (N / 2, N / 2) in integer division, as for clean.
+ * BEAM FIT: an elliptical Gaussian fitted to the main lobe of the PSF.  window >= 1 and 0 < cut < 1 are the caller's.
+ *     R = min(window, c, N - 1 - c)
+ *     p(dy, dx) = psf[c + dy, c + dx] / psf[c, c]
+ *     a cell (dy, dx) != (0, 0) with |dy|, |dx| <= R takes part if and only if p <= 1 and
+ *         p >= cut, or max(|dy|, |dx|) == 1 and p > 0
+ *     (the second case lets the eight neighbours of the centre take part whenever their logarithm exists, so that a beam
+ *     narrower than a couple of cells - what a uniformly weighted imager makes - is still fitted; a NaN cell never
+ *     takes part)
+ *     minimise  sum p^2 (A dx^2 + 2 B dx dy + C dy^2 + ln p)^2  over the participating cells
+ * With w = p^2, a = dx^2, b = 2 dx dy, c = dy^2 (exact integers) and l = ln p, the nine sums of the normal equations
+ *     M = [[sum (w a) a, sum (w a) b, sum (w a) c], [., sum (w b) b, sum (w b) c], [., ., sum (w c) c]] (symmetric),
+ *     g = [sum (w a) l, sum (w b) l, sum (w c) l]
+ * are accumulated in fp64 without fused multiply-adds and without atomics: each row dy in dx order from +0.0, then the rows
+ * in dy order from +0.0.  M (A, B, C)^T = -g is solved by Cramer's rule (cofactor expansion along the first row).
+ *     beam(dy, dx) = exp(-(A dx^2 + 2 B dx dy + C dy^2)), peak 1
+ *     result = 8 doubles { A, B, C, bmaj, bmin, bpa, ncells, ok }
+ * bmaj >= bmin are the FWHMs in cells, 2 sqrt(ln 2 / lambda) for the two eigenvalues (A + C) / 2 -+ sqrt(((A - C) / 2)^2
+ * + B^2) of [[A, B], [B, C]] (a cell is theta / N radians); bpa is the direction of the major axis, the angle from +x
+ * towards +y in radians, in (-pi/2, pi/2], 0 when A == C and B == 0; ncells is the number of participating cells.  The
+ * fit FAILS when fewer than 3 cells take part, when det M is not positive, when psf[c, c] is not positive or not finite,
+ * or when the fitted form is not positive definite (A > 0, C > 0, A C - B^2 > 0): it then writes ok = 0, the true
+ * ncells and NaN in the other six.  A call is deterministic bit for bit.
+ * RESTORE: 1 <= support <= 32 is a host argument (it fixes the launch shape, so that the call can be captured).
+ *     restored[y, x] = residual[y, x] + sum over |dy|, |dx| <= support of model[y - dy, x - dx] * beam(dy, dx)
+ * Model cells outside the image count as zero.  The taps are summed dy ascending, then dx ascending, one fused multiply-add
+ * each, starting from +0.0, and the residual is added last; nothing is accumulated with atomics, so the host, _dev and
+ * imager forms give the same bits, and so do two runs.  The restored image is in units per beam (the beam's peak is 1).
+ * restored may be residual itself (an in-place restore); otherwise it may overlap neither residual nor model nor beam.
+ * The _dev forms read the beam from 8 doubles on the device - the fit's output, or { A, B, C, -, -, -, -, ok != 0 } of
+ * the caller's own: a beam whose ok is 0 or NaN, or whose A, B, C are not finite and positive definite, writes NaN to
+ * every cell of restored; nothing is read back and nothing is silently replaced by a delta beam.  gridhip_restore takes
+ * the 8 doubles from the host and refuses such a beam with GRIDHIP_EINVAL before anything is touched.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL handle or array (the imager form's beam
+ * output may be NULL), N < 1, window < 1, cut outside (0, 1) or NaN, support < 1, a forbidden overlap.  support > 32 or
+ * N above 1048560 is GRIDHIP_EUNSUPPORTED.
+ * The fit is one work-group: each thread owns whole rows of the window (any window; 128 rows per pass), one thread adds the
+ * rows, solves and writes the result.  The restore is an LDS-tiled direct convolution: a work-group makes 32 x 64 cells,
+ * stages the model tile and its halo of `support` cells and, unless that window holds no non-zero cell - then the tile is
+ * residual + 0.0, with the same bits as the full sum (a -0.0 residual becomes +0.0 either way) - the (2 support + 1)^2
+ * weights, evaluated once per work-group.  gridhip_fit_beam and gridhip_restore are synchronous and stage host arrays
+ * through the context's pool.  The _dev and imager forms take device pointers, enqueue one kernel each on the context's
+ * stream (no memset or copy node), allocate nothing after the first call, never synchronise and read nothing back, so
+ * visibilities -> deconvolve -> restore can be captured into one graph.  They need no scratch. */
+int gridhip_fit_beam(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, double *beam);
+int gridhip_fit_beam_dev(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, double *beam);
+int gridhip_restore(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
+                    int64_t support, double *restored);
+int gridhip_restore_dev(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
+                        int64_t support, double *restored);
+/* gridhip_fit_beam_dev on the imager's own PSF (nothing is copied) and N */
+int gridhip_imager_beam_dev(gridhip_imager *imager, int64_t window, double cut, double *beam);
+/* the fit on the imager's own PSF, then gridhip_restore_dev with that beam; beam (8 doubles on the device) receives it,
+ * or is NULL */
+int gridhip_imager_restore_dev(gridhip_imager *imager, const double *model, const double *residual, int64_t window,
+                               double cut, int64_t support, double *restored, double *beam);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

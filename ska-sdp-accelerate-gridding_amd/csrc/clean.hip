@@ -25,6 +25,7 @@ namespace gridhip {
 namespace {
 
 constexpr int CLEAN_TH = 16, CLEAN_TW = 128;  // one wave takes one row of a tile, 16 bytes per lane
+static_assert(CLEAN_MAX_N == (int64_t)CLEAN_TH * 65535, "imaging.h states the tile grid's limit");
 
 struct CleanEntry {  // a tile's peak: the signed value and its flat index; k < 0: no cell of the tile can be selected
     double v;
@@ -218,7 +219,7 @@ int clean_check(gridhip_ctx *ctx, int64_t N, const double *psf, const double *re
     if (N < 1 || !(gain > 0.0 && gain <= 1.0) || !(threshold >= 0.0) || niter < 0 || border < 0 || 2 * border >= N ||
         patch < 0 || !psf || !residual || !model)
         return fail(ctx, GRIDHIP_EINVAL, "clean: bad argument");
-    if (N > (int64_t)CLEAN_TH * 65535) return fail(ctx, GRIDHIP_EUNSUPPORTED, "clean: N above %d", CLEAN_TH * 65535);
+    if (N > CLEAN_MAX_N) return fail(ctx, GRIDHIP_EUNSUPPORTED, "clean: N above %d", CLEAN_TH * 65535);
     const size_t bytes = (size_t)N * N * 8;
     if (overlap(psf, residual, bytes) || overlap(psf, model, bytes) || overlap(residual, model, bytes))
         return fail(ctx, GRIDHIP_EINVAL, "clean: psf, residual and model must not overlap");

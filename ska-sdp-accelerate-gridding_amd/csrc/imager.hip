@@ -146,6 +146,7 @@ struct gridhip_imager {
     gridhip_aw_plan *aw_gather = nullptr, *aw_scatter = nullptr;
     bool clear_pred = false;  // the gather does not write every prediction: they start from zero
     void *clean_scratch = nullptr;  // clean's state block and tile table (clean.hip), made by the first clean
+    double *beam = nullptr;         // the fitted beam of a restore that does not return it (8 doubles), made by the first
 };
 
 namespace {
@@ -464,6 +465,32 @@ int gridhip_imager_deconvolve_dev(gridhip_imager *im, const double *vis, double 
                                           stats ? stats + 4 * c : nullptr));
     }
     return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
+}
+
+int gridhip_imager_beam_dev(gridhip_imager *im, int64_t window, double cut, double *beam)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(fit_beam_check(ctx, im->N, im->psf, window, cut, beam));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return fit_beam_run(ctx, im->N, im->psf, window, cut, beam);
+}
+
+int gridhip_imager_restore_dev(gridhip_imager *im, const double *model, const double *residual, int64_t window, double cut,
+                               int64_t support, double *restored, double *beam)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    double placeholder = 0.0;  // (stands for the imager's own block in the checks: it overlaps nothing of the caller's)
+    GH_CHECK(fit_beam_check(ctx, im->N, im->psf, window, cut, beam ? beam : &placeholder));
+    GH_CHECK(restore_check(ctx, im->N, model, residual, beam ? beam : &placeholder, support, restored));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!beam) {
+        if (!im->beam) GH_CHECK(own(im, &im->beam, 64));
+        beam = im->beam;
+    }
+    GH_CHECK(fit_beam_run(ctx, im->N, im->psf, window, cut, beam));
+    return restore_run(ctx, im->N, model, residual, beam, support, restored);
 }
 
 int gridhip_imager_destroy(gridhip_imager *im)

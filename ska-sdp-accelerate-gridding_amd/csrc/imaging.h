@@ -1,6 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
-// streaming image operations, the imaging functions, prediction, imagers and deconvolution (api.hip, comm.hip, awgrid.hip's entry
-// points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip).
+// streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
+// awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
+// restore.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -34,6 +35,7 @@ struct ImagingState {
         void *ptr = nullptr;
         size_t bytes = 0;
     } wk_cache;
+    bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
 };
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled
@@ -251,6 +253,8 @@ struct AwFront {
 int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt, AwFront &f);
 
 // ---- deconvolution (clean.hip) -------------------------------------------------------------------------------------------
+// the largest N clean's tile grid holds (65535 rows of 16-row tiles); the restore takes the same limit
+constexpr int64_t CLEAN_MAX_N = 16 * 65535;
 // gridhip_clean's argument rules (GRIDHIP_EINVAL; an N the tile grid cannot hold is GRIDHIP_EUNSUPPORTED)
 int clean_check(gridhip_ctx *ctx, int64_t N, const double *psf, const double *residual, const double *model, double gain,
                 double threshold, int64_t niter, int64_t border, int64_t patch);
@@ -259,5 +263,16 @@ size_t clean_scratch_bytes(int64_t N);
 // gridhip_clean_dev on checked arguments: kernels only, on ctx->stream; scratch: clean_scratch_bytes(N) of device memory
 int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
               double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
+
+// ---- the restoring beam and the restore (restore.hip) --------------------------------------------------------------------
+// gridhip_fit_beam's and gridhip_restore's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); the beam's values are
+// not looked at (they may live on the device)
+int fit_beam_check(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, const double *beam);
+int restore_check(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
+                  int64_t support, const double *restored);
+// the _dev forms on checked arguments: one kernel each on ctx->stream, no scratch
+int fit_beam_run(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, double *beam);
+int restore_run(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
+                int64_t support, double *restored);
 
 }  // namespace gridhip

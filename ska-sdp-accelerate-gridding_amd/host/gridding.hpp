@@ -12,6 +12,7 @@
 //   do_imaging theta lam uvw a1 a2 t f vis imgfn    :509-519 (do_imaging_aw: imgfn = aw_imaging)
 //   predict / predict_aw: the way back, model image -> visibilities (absent from the reference)
 //   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
+//   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -283,6 +284,30 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_clean(ctx_, image.h, psf.data.data(), image.data.data(), model.data.data(), gain, threshold, niter,
                             border, patch, st));
         return {st[0], st[1], st[2], st[3]};
+    }
+
+    // ---- restoring beam and restore (gridhip_fit_beam, gridhip_restore; include/gridhip.h, "restoring beam and restore") ----
+    // The elliptical Gaussian exp(-(A dx^2 + 2 B dx dy + C dy^2)) fitted to the PSF's main lobe: FWHMs in cells (a cell
+    // is theta / N radians), bpa in radians from +x towards +y.  ok is false, and the rest NaN, when the fit failed.
+    struct Beam {
+        F A, B, C, bmaj, bmin, bpa, ncells, ok;
+    };
+    Beam fit_beam(const Matrix<F> &psf, Int window = 8, F cut = 0.5)
+    {
+        if (psf.h != psf.w) throw Error(GRIDHIP_EINVAL, "fit_beam: psf must be N x N");
+        F b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_fit_beam(ctx_, psf.h, psf.data.data(), window, cut, b));
+        return {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7]};
+    }
+    // model convolved with the beam over +-support cells (1 to 32) + residual, in units per beam
+    Matrix<F> restore(const Matrix<F> &model, const Matrix<F> &residual, const Beam &beam, Int support)
+    {
+        if (model.h != model.w || residual.h != model.h || residual.w != model.w)
+            throw Error(GRIDHIP_EINVAL, "restore: model and residual must be N x N");
+        const F b[8] = {beam.A, beam.B, beam.C, beam.bmaj, beam.bmin, beam.bpa, beam.ncells, beam.ok};
+        Matrix<F> out = residual;
+        check(gridhip_restore(ctx_, model.h, model.data.data(), residual.data.data(), b, support, out.data.data()));
+        return out;
     }
 
     // ---- helpers ----

@@ -23,8 +23,8 @@ import ctypes as C
 
 from . import _lib
 from ._lib import GridHipError, LIB_PATH  # noqa: F401
-from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, clean_scalars, device, imaging_function,
-                       in_place, is_torch)
+from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
+                       image_of, imaging_function, in_place, is_torch)
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
 
@@ -380,6 +380,44 @@ class Context(Handle):
         self._call(be, "clean", shape[0], psf, image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
         return model, image, stats
 
+    def fit_beam(self, psf, window=8, cut=0.5):
+        """The restoring beam of the N x N `psf` (gridhip_fit_beam[_dev]; include/gridhip.h, "restoring beam and
+        restore"): an elliptical Gaussian fitted to the main lobe over the cells within `window` of the centre that
+        reach `cut` of the peak (and the centre's eight neighbours).  Returns the 8 values [A, B, C, bmaj, bmin, bpa,
+        ncells, ok] - FWHMs in cells (a cell is theta / N radians), bpa in radians from +x towards +y; ok = 0 and NaNs
+        when the fit failed.  A numpy psf takes the synchronous host form; a torch cuda tensor the asynchronous one,
+        and the result is a cuda tensor: nothing is read back."""
+        be = backend(psf)
+        psf = be.cv(psf, be.f64)
+        shape = tuple(psf.shape)
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("psf must be N x N")
+        beam = be.empty(8, be.f64, psf)
+        self._call(be, "fit_beam", shape[0], psf, int(window), float(cut), beam)
+        return beam
+
+    def restore(self, model, residual, beam, support=None, out=None):
+        """restored = model convolved with the beam + residual (gridhip_restore[_dev]), in units per beam: `model` and
+        `residual` are N x N float64 as clean returns them, `beam` the 8 values of fit_beam (or [A, B, C, 0, 0, 0, 0, 1]
+        of your own), `support` the half-width of the convolution in cells, 1 to 32.  support=None derives it from the
+        beam - the smallest R with exp(-lambda_min R^2) <= 1e-9 - which READS THE BEAM BACK: one synchronisation for
+        cuda tensors, and a ValueError when the fit failed or R exceeds 32; an explicit support keeps the call
+        asynchronous (a failed beam then gives an all-NaN image from the device form).  out: the array to write (a new
+        one when None); it may be `residual` itself.  Returns it."""
+        be = backend(model)
+        shape = tuple(getattr(model, "shape", ()))
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("model must be N x N")
+        model, residual = image_of(be, model, shape, "model"), image_of(be, residual, shape, "residual")
+        beam = be.cv(beam, be.f64)
+        if tuple(beam.shape) != (8,):
+            raise ValueError("beam must be the 8 values of fit_beam")
+        out = be.empty(shape, be.f64, model) if out is None else in_place(be, out, shape, "out")
+        if support is None:
+            support = beam_support(beam.tolist())
+        self._call(be, "restore", shape[0], model, residual, beam, int(support), out)
+        return out
+
     def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None):
         """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
         and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
@@ -568,6 +606,33 @@ class Imager(_Bound):
         self._call(be, "imager_deconvolve", vis, model, out, int(nmajor),
                    *clean_scalars(gain, threshold, niter, border, patch), stats)
         return model, out, stats
+
+    def beam(self, window=8, cut=0.5):
+        """Context.fit_beam on the imager's own PSF (gridhip_imager_beam_dev): the 8 values as a cuda tensor,
+        asynchronous."""
+        self._open()
+        be = device()
+        beam = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_beam", int(window), float(cut), beam)
+        return beam
+
+    def restore(self, model, residual, support=None, window=8, cut=0.5, out=None):
+        """The restored image of a deconvolve's or a clean's (model, residual) with the beam fitted to the imager's own
+        PSF (gridhip_imager_restore_dev): returns (restored, beam), the image in units per beam and the 8 values of the
+        fit, both on the device.  With an explicit `support` (1 to 32) the call is asynchronous and, after a first
+        call, capturable together with deconvolve.  support=None fits the beam first and READS IT BACK to derive the
+        support (Context.restore): one synchronisation, and a ValueError when the fit failed or the beam needs more
+        than 32 cells.  out may be `residual` itself."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        self._ok(model, be.f64, NN, "model")
+        self._ok(residual, be.f64, NN, "residual")
+        out = be.empty(NN, be.f64, self.device) if out is None else in_place(be, out, NN, "out")
+        if support is None:
+            support = beam_support(self.beam(window, cut).tolist())
+        beam = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_restore", model, residual, int(window), float(cut), int(support), out, beam)
+        return out, beam
 
 
 _default = {}

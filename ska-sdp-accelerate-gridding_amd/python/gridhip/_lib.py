@@ -34,6 +34,8 @@ _AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp,
                 C.POINTER(C.c_double)]
 _PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, vp, vp, i64, vp, vp]
 _CLEAN = [vp, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
+_FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
+_RESTORE = [vp, i64, vp, vp, vp, i64, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -107,6 +109,12 @@ SIGNATURES = {
     "gridhip_clean_dev": (ci, _CLEAN),
     "gridhip_imager_clean_dev": (ci, [vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_imager_deconvolve_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64, vp]),
+    "gridhip_fit_beam": (ci, _FIT_BEAM),
+    "gridhip_fit_beam_dev": (ci, _FIT_BEAM),
+    "gridhip_restore": (ci, _RESTORE),
+    "gridhip_restore_dev": (ci, _RESTORE),
+    "gridhip_imager_beam_dev": (ci, [vp, i64, C.c_double, vp]),
+    "gridhip_imager_restore_dev": (ci, [vp, vp, vp, i64, C.c_double, i64, vp, vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

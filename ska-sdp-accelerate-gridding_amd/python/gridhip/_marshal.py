@@ -162,6 +162,32 @@ def clean_scalars(gain, threshold, niter, border, patch):
     return float(gain), float(threshold), int(niter), int(border), int(patch)
 
 
+def image_of(be, x, shape, what):
+    """An N x N float64 image an entry point only reads (restore's model and residual), converted where it must be"""
+    x = be.cv(x, be.f64)
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{what} must be of shape {tuple(shape)}")
+    return x
+
+
+def beam_support(beam):
+    """The support a restore needs for the fitted beam `beam` (the 8 values, read back when they are on the device:
+    one synchronisation): the smallest R with exp(-lambda_min R^2) <= 1e-9, lambda_min the smaller eigenvalue of
+    [[A, B], [B, C]].  Raises when the fit failed or when R exceeds the 32 cells gridhip_restore takes."""
+    import math
+    A, B, C_, ok = (float(beam[i]) for i in (0, 1, 2, 7))
+    lam = 0.5 * (A + C_) - math.hypot(0.5 * (A - C_), B)
+    if not (ok != 0.0 and ok == ok and lam > 0.0 and math.isfinite(A + C_)):
+        raise ValueError("the beam's fit failed: there is no support to derive (pass support= and a beam of your own)")
+    R = max(1, math.ceil(math.sqrt(math.log(1e9) / lam)))
+    while R > 1 and math.exp(-lam * (R - 1) ** 2) <= 1e-9:  # (the square root's rounding)
+        R -= 1
+    if R > 32:
+        raise ValueError(f"the beam needs a support of {R} cells, above the 32 gridhip_restore takes: pass support=32 to"
+                         " truncate it")
+    return R
+
+
 class Handle:
     """Owner of one library handle `_h` (a context, plan, imager or communicator): destroyed once, by close() or by the
     collector; _call passes it to an entry point and raises GridHipError with the owner's last-error text."""
