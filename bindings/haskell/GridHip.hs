@@ -34,6 +34,9 @@ module GridHip
   , CleanOptions(..), cleanIO, imagerCleanIO, imagerDeconvolveIO
   -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
   , fitBeamIO, restoreIO, imagerBeamIO, imagerRestoreIO
+  -- * imaging weights: natural, uniform, Briggs, taper and data weights, alone or as what an imager is created with
+  , Weighting(..), WeightMode(..), weightsIO, imagerCreateWeightedIO, imagerCreateAwWeightedIO, imagerDestroyIO
+  , imagerWeightStatsIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -286,6 +289,21 @@ foreign import ccall unsafe "gridhip_imager_beam_dev"
 -- int gridhip_imager_restore_dev(imager, model, residual, window, cut, support, restored, beam)
 foreign import ccall unsafe "gridhip_imager_restore_dev"
   c_imager_restore_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_weights(ctx, theta, lam, n, u, v, uv_stride, wt_in, mode, robust, taper_sigma, wt_out, stats)
+foreign import ccall unsafe "gridhip_weights"
+  c_weights :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> CInt -> CDouble -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_weights_dev(ctx, theta, lam, n, u, v, uv_stride, wt_in, mode, robust, taper_sigma, wt_out, stats)
+foreign import ccall unsafe "gridhip_weights_dev"
+  c_weights_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> CInt -> CDouble -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_create_weighted_dev(ctx, kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, n, u, v, w, uv_stride, mode, robust, taper_sigma, wt_in, imager)
+foreign import ccall unsafe "gridhip_imager_create_weighted_dev"
+  c_imager_create_weighted_dev :: Ptr Ctx -> CInt -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CInt -> CDouble -> CDouble -> Ptr CDouble -> Ptr (Ptr Imager) -> IO CInt
+-- int gridhip_imager_create_aw_weighted_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, mode, robust, taper_sigma, wt_in, imager)
+foreign import ccall unsafe "gridhip_imager_create_aw_weighted_dev"
+  c_imager_create_aw_weighted_dev :: Ptr Ctx -> CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr Int64 -> CInt -> CDouble -> CDouble -> Ptr CDouble -> Ptr (Ptr Imager) -> IO CInt
+-- int gridhip_imager_weight_stats_dev(imager, stats)
+foreign import ccall unsafe "gridhip_imager_weight_stats_dev"
+  c_imager_weight_stats_dev :: Ptr Imager -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -829,6 +847,95 @@ imagerRestoreIO (ImagerH h@(GridHip c) p _ n') window cut support model residual
               c_synchronize c >>= check h
               map realToFrac <$> peekArray 8 pb
   return (A.fromForeignPtrs (A.Z A.:. n' A.:. n') (castForeignPtr out), beam)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Imaging weights (include/gridhip.h, "imaging weights").  stats are the 8 values
+-- [sum w, sum w^2 / s, sum s, noise, f^2, n_used, n_flagged, n_outside].
+
+data WeightMode = NaturalWeighting | UniformWeighting | BriggsWeighting
+
+-- | the mode, Briggs' robust and the taper's sigma in wavelengths (0: no taper)
+data Weighting = Weighting { weightMode :: WeightMode, weightRobust :: F, weightTaper :: F }
+
+modeCode :: WeightMode -> CInt
+modeCode NaturalWeighting = 0
+modeCode UniformWeighting = 1
+modeCode BriggsWeighting  = 2
+
+-- | weightsIO h theta lam weighting uvw wt: the imaging weights of the baselines `uvw` (the (n,3) Matrix BaseLine in
+-- wavelengths, taken as given) with the data weights `wt` (Nothing: ones; a value that is not > 0 flags its visibility)
+-- and the stats - the host form, synchronous
+weightsIO :: GridHip -> F -> Int -> Weighting -> A.Matrix BaseLine -> Maybe (A.Vector F) -> IO (A.Vector F, [F])
+weightsIO h@(GridHip c) theta lam (Weighting m r t) uvw wt = do
+  let A.Z A.:. n A.:. _ = A.arrayShape uvw
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+  out <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
+  st <- withF uvw $ \p -> withWt $ \ps -> withForeignPtr out $ \po -> allocaArray 8 $ \pst -> do
+          c_weights c (realToFrac theta) (fi lam) (fi n) p (p `advancePtr` 1) 3 ps (modeCode m) (realToFrac r)
+                    (realToFrac t) po pst >>= check h
+          map realToFrac <$> peekArray 8 pst
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out), st)
+
+-- the data weights on the device for the duration of `k` (NULL for Nothing)
+withDevWeights :: GridHip -> Int -> Maybe (A.Vector F) -> (Ptr CDouble -> IO a) -> IO a
+withDevWeights h n wt k = maybe (k nullPtr) (\s -> withF s $ \ps -> withDev h ps (8 * n) k) wt
+
+-- | imagerCreateWeightedIO h theta lam weighting wt uvw kind: withImager's creation for SimpleImaging, ConvImaging and
+-- WCacheImaging with a weighting (gridhip_imager_create_weighted_dev); the density is taken on the mirrored baselines
+-- and a flagged visibility contributes nothing to any image.  The caller ends with imagerDestroyIO.
+imagerCreateWeightedIO :: GridHip -> F -> Int -> Weighting -> Maybe (A.Vector F) -> A.Matrix BaseLine -> ImagingKind
+                       -> IO ImagerH
+imagerCreateWeightedIO h@(GridHip c) theta lam (Weighting m r t) wt uvw kind = do
+  n' <- imageSize theta lam
+  let A.Z A.:. n A.:. _ = A.arrayShape uvw
+      plain kd wstep q npixFF gh gw kv = withF uvw $ \mp -> withDev h mp (24 * n) $ \d -> withDevWeights h n wt $ \dw ->
+        alloca $ \pp -> do
+          c_imager_create_weighted_dev c kd (fi wstep) (fi q) (fi npixFF) (fi gh) (fi gw) kv (realToFrac theta) (fi lam)
+                                       (fi n) d (d `advancePtr` 1) (d `advancePtr` 2) 3 (modeCode m) (realToFrac r)
+                                       (realToFrac t) dw pp >>= check h
+          peek pp
+  p <- case kind of
+    SimpleImaging -> plain 0 (0 :: Int) (0 :: Int) (0 :: Int) (0 :: Int) (0 :: Int) nullPtr
+    ConvImaging kv ->
+      let A.Z A.:. q A.:. _ A.:. gh A.:. gw = A.arrayShape kv
+      in withCplx kv $ \kp -> withDev h kp (16 * q * q * gh * gw) $ \dk -> plain 1 (0 :: Int) q (0 :: Int) gh gw dk
+    WCacheImaging wstep q npixFF s -> plain 2 wstep q npixFF s s nullPtr
+    AwImaging {} -> error "imagerCreateWeightedIO: AwImaging is imagerCreateAwWeightedIO's"
+  return (ImagerH h p n n')
+
+-- | imagerCreateAwWeightedIO h theta lam weighting wt uvw wkerns wvals akerns ant1 ant2: the same for aw_imaging
+-- (gridhip_imager_create_aw_weighted_dev)
+imagerCreateAwWeightedIO :: GridHip -> F -> Int -> Weighting -> Maybe (A.Vector F) -> A.Matrix BaseLine
+                         -> A.Array A.DIM5 Visibility -> A.Vector BaseLine -> A.Array A.DIM3 Visibility
+                         -> A.Vector Antenna -> A.Vector Antenna -> IO ImagerH
+imagerCreateAwWeightedIO h@(GridHip c) theta lam (Weighting m r t) wt uvw wkerns wvals akerns ant1 ant2 = do
+  n' <- imageSize theta lam
+  let A.Z A.:. n A.:. _ = A.arrayShape uvw
+      A.Z A.:. w A.:. q A.:. _ A.:. s A.:. _ = A.arrayShape wkerns
+      A.Z A.:. na A.:. _ A.:. _ = A.arrayShape akerns
+  p <- withF uvw $ \mp -> withDev h mp (24 * n) $ \d -> withCplx wkerns $ \wk ->
+         withDev h wk (16 * w * q * q * s * s) $ \dwk -> withF wvals $ \wv -> withDev h wv (8 * w) $ \dwv ->
+           withCplx akerns $ \ak -> withDev h ak (16 * na * s * s) $ \dak -> withI64 ant1 $ \a1 ->
+             withDev h a1 (8 * n) $ \d1 -> withI64 ant2 $ \a2 -> withDev h a2 (8 * n) $ \d2 ->
+               withDevWeights h n wt $ \dw -> alloca $ \pp -> do
+                 c_imager_create_aw_weighted_dev c (realToFrac theta) (fi lam) (fi w) (fi q) (fi s) (fi na) dwk dwv dak
+                                                 (fi n) d (d `advancePtr` 1) (d `advancePtr` 2) 3 d1 d2 (modeCode m)
+                                                 (realToFrac r) (realToFrac t) dw pp >>= check h
+                 peek pp
+  return (ImagerH h p n n')
+
+-- | release an imager made by imagerCreateWeightedIO / imagerCreateAwWeightedIO
+imagerDestroyIO :: ImagerH -> IO ()
+imagerDestroyIO (ImagerH _ p _ _) = () <$ c_imager_destroy p
+
+-- | imagerWeightStatsIO im: the stats of the weighting the imager was created with (gridhip_imager_weight_stats_dev)
+imagerWeightStatsIO :: ImagerH -> IO [F]
+imagerWeightStatsIO (ImagerH h@(GridHip c) p _ _) =
+  allocaArray 8 $ \ps -> withDev h ps 64 $ \ds -> do
+    c_imager_weight_stats_dev p ds >>= check h
+    c_memcpy_d2h c (castPtr ps) (castPtr ds) 64 >>= check h
+    c_synchronize c >>= check h
+    map realToFrac <$> peekArray 8 ps
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 170 /* 0.1.7 */
+#define GRIDHIP_VERSION 180 /* 0.1.8 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -592,6 +592,69 @@ int gridhip_imager_beam_dev(gridhip_imager *imager, int64_t window, double cut, 
  * or is NULL */
 int gridhip_imager_restore_dev(gridhip_imager *imager, const double *model, const double *residual, int64_t window,
                                double cut, int64_t support, double *restored, double *beam);
+
+/* ---- imaging weights: natural, uniform, Briggs, taper and data weights, on the device -----------------------------------
+ * The reference weights one way only, doweight (src/Gridding.hs:564-583: every visibility divided by the number of
+ * visibilities in its cell); everything beyond that is defined here.  For n visibilities at (u_k, v_k) in wavelengths
+ * (uv_stride as everywhere; taken as given - nothing is mirrored here, a caller that wants Hermitian cells merged mirrors
+ * first, as do_imaging does), N = gridhip_image_size(theta, lam), data weights s_k (wt_in: n doubles, or NULL for all
+ * ones), mode, robust R and taper_sigma sigma (wavelengths; 0: no taper):
+ *     FLAGGED   a visibility whose s_k is not > 0 (zero, negative, NaN): w_k is exactly +0.0 and it takes part in nothing else
+ *     c_k       doweight's cell of (u_k / lam, v_k / lam); -1 outside the grid or for NaN coordinates
+ *     D[c]      the sum of s_k over the unflagged visibilities with c_k = c
+ *     t_k       exp(-(u_k^2 + v_k^2) / (2 sigma^2)), or 1 when sigma = 0
+ *     mode 0    natural   w_k = s_k t_k
+ *     mode 1    uniform   w_k = (s_k / D[c_k]) t_k
+ *     mode 2    Briggs    f^2 = (5 * 10^-R)^2 / (sum_c D[c]^2 / sum_c D[c]) ;  w_k = s_k / (1 + D[c_k] f^2) t_k
+ *                         (1 + D f^2 is a rounded product followed by an add: no fused multiply-add; f^2 is 0 when no
+ *                         visibility lies in the grid)
+ *     OUTSIDE   an unflagged visibility with c_k = -1 keeps w_k = s_k t_k in every mode, as doweight keeps 1, and is left
+ *               out of D, of f^2 and of the sums below
+ *     stats     8 doubles { sum w, sum w^2 / s, sum s, noise, f^2, n_used, n_flagged, n_outside }, the sums over the
+ *               unflagged visibilities in the grid; noise = sqrt(sum(w^2 / s) sum(s)) / sum(w), NaN when sum w is 0: the
+ *               thermal noise relative to natural weighting (>= 1, and 1 for natural weighting without a taper); f^2 is 0
+ *               outside mode 2.  stats may be NULL.
+ * With wt_in NULL, D is an integer count and sum D, sum D^2 are 64-bit integer sums: the weights do not depend on the
+ * schedule (two calls give the same bits), and mode 1 without a taper gives the bits of doweight applied to ones,
+ * 1.0 / count.  With data weights D is accumulated with fp64 atomics and the weights agree to the order of those sums
+ * (1e-10 relative at up to 1000 visibilities per cell).  The six sums of stats are added in a fixed order either way.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL context; NULL u, v or wt_out with n > 0;
+ * n < 0; uv_stride < 1; N < 1; a mode outside 0..2; a robust that is not finite; taper_sigma < 0 or NaN; wt_out
+ * overlapping u or v.  wt_out may be wt_in itself (in place).
+ * gridhip_weights is synchronous and stages host arrays through the context's pool (stats: 8 doubles on the host).
+ * gridhip_weights_dev takes device pointers (stats: 8 doubles on the device) and enqueues kernels only on the context's
+ * stream - no memset node, no copy node: a kernel zeroes the density; pass 1 over the visibilities takes the cell and
+ * accumulates the density (uint32 counts, or fp64 atomics with data weights) and leaves the 8-byte cell code; for Briggs
+ * one reduction over the N^2 cells; pass 2 writes w with the sums of stats fused into it (it reads u, v again only for
+ * a taper); a one-work-group kernel writes stats.  Natural weighting is pass 2 alone.  f^2 never leaves the device.  The
+ * scratch (the density, 8 B per visibility of cell codes, 200 KB of partial sums) comes from the context's pool: nothing
+ * is allocated after the first call of a shape, nothing is read back and nothing synchronises, so a call can be captured
+ * into a graph like clean and restore. */
+int gridhip_weights(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, const double *u, const double *v,
+                    int64_t uv_stride, const double *wt_in, int mode, double robust, double taper_sigma, double *wt_out,
+                    double *stats);
+int gridhip_weights_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, const double *u, const double *v,
+                        int64_t uv_stride, const double *wt_in, int mode, double robust, double taper_sigma,
+                        double *wt_out, double *stats);
+/* Imagers with a weighting: the creation calls above plus (mode, robust, taper_sigma, wt_in).  wt_in is n doubles on the
+ * device in the un-mirrored order of vis, or NULL; the density is taken on the MIRRORED coordinates, where the imager takes
+ * doweight's.  gridhip_imager_create_dev / _aw_dev are these with (1, 0, 0, NULL), bit for bit.  Everything after
+ * creation - cycle, predict, psf, clean, deconvolve, beam, restore - is unchanged and sees the new weights; prediction
+ * stays un-weighted.  A visibility of weight 0 (flagged) contributes EXACTLY NOTHING to the image and the PSF even when its
+ * vis is NaN or Inf: its contribution is selected out, not multiplied by zero (vis_res is still vis - pred for it).
+ * Memory held per visibility is unchanged: the mirror flag stays the sign bit of the stored weight, of a zero too. */
+int gridhip_imager_create_weighted_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
+                                       int64_t gw, const double *kv, double theta, int64_t lam, int64_t n,
+                                       const double *u, const double *v, const double *w, int64_t uv_stride, int mode,
+                                       double robust, double taper_sigma, const double *wt_in, gridhip_imager **imager);
+int gridhip_imager_create_aw_weighted_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
+                                          int64_t A, const double *wkerns, const double *wvals, const double *akerns,
+                                          int64_t n, const double *u, const double *v, const double *w,
+                                          int64_t uv_stride, const int64_t *a1, const int64_t *a2, int mode,
+                                          double robust, double taper_sigma, const double *wt_in,
+                                          gridhip_imager **imager);
+/* the stats of the creation's weighting, copied on the stream into 8 doubles on the device */
+int gridhip_imager_weight_stats_dev(gridhip_imager *imager, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -24,8 +24,10 @@ namespace gridhip {
 //   p = uvw / lam of the un-mirrored baseline (pu, pv: what predict's gathers bin) and of the mirrored one (mu, mv: what
 //   do_imaging's scatters bin; mirror_uvw, src/Gridding.hs:551-562: v < 0 negates u, v, w) - true divisions, as
 //   scale_kernel's; -(u / lam) and (-u) / lam are the same double, so one division serves both;
-//   the mirror flag as the sign of sw (+-1 here; imager_weight_kernel puts the weight's magnitude on it);
-//   doweight's cell of the mirrored p (:531-535), counted into the histogram;
+//   the mirror flag as the sign of sw (+-1 here; the weighting's second pass, weights.hip, puts the weight's magnitude on
+//   it - the default, uniform weighting without data weights, is doweight's ones / count, and a weight of zero keeps its
+//   sign bit);
+//   doweight's cell of the mirrored p (:531-535) or the code of a flagged visibility, and the density (weight_note);
 //   w of both streams (w_cache: the w-bin rule needs the whole stream's min and max first) or their findClosest bins (aw:
 //   the reference searches with w in wavelengths, :473-474).
 // There is no product or sum here for the compiler to contract; frac_coord_dev switches contraction off itself.
@@ -35,7 +37,7 @@ __global__ void __launch_bounds__(256)
                         double *__restrict__ pu, double *__restrict__ pv, double *__restrict__ mu, double *__restrict__ mv,
                         double *__restrict__ w0, double *__restrict__ w1, int64_t *__restrict__ wb0,
                         int64_t *__restrict__ wb1, double *__restrict__ sw, int64_t *__restrict__ cell,
-                        unsigned int *__restrict__ cnt)
+                        const double *__restrict__ wt_in, unsigned int *__restrict__ cnt, double *__restrict__ dens)
 {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
         const double u0 = u[k * stride], v0 = v[k * stride];
@@ -58,22 +60,7 @@ __global__ void __launch_bounds__(256)
                 wb1[k] = closest_index(nws, ws, x1);
             }
         }
-        const int64_t c = weight_cell(N, ru, rv);
-        cell[k] = c;
-        if (c >= 0) atomicAdd(&cnt[c], 1u);
-    }
-}
-
-// |sw| = doweight's ones / count (weight_apply_kernel's division; a visibility outside the grid keeps 1), the sign stays
-__global__ void __launch_bounds__(256)
-    imager_weight_kernel(int64_t n, const int64_t *__restrict__ cell, const unsigned int *__restrict__ cnt,
-                         double *__restrict__ sw)
-{
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
-        double a = 1.0;
-        const int64_t c = cell[k];
-        if (c >= 0) a /= (double)cnt[c];
-        sw[k] = copysign(a, sw[k]);
+        cell[k] = weight_note(weight_cell(N, ru, rv), wt_in, k, cnt, dens);
     }
 }
 
@@ -115,7 +102,7 @@ __global__ void __launch_bounds__(256)
         const double s = sw[k];
         const double a = fabs(s);
         if (signbit(s)) r.y = -r.y;
-        pred[k] = make_double2(a * r.x, a * r.y);
+        pred[k] = a == 0.0 ? make_double2(0.0, 0.0) : make_double2(a * r.x, a * r.y);  // (selected out: vis may be NaN)
     }
 }
 
@@ -147,6 +134,7 @@ struct gridhip_imager {
     bool clear_pred = false;  // the gather does not write every prediction: they start from zero
     void *clean_scratch = nullptr;  // clean's state block and tile table (clean.hip), made by the first clean
     double *beam = nullptr;         // the fitted beam of a restore that does not return it (8 doubles), made by the first
+    double *wstats = nullptr;       // the weighting's stats (8 doubles), written at creation
 };
 
 namespace {
@@ -201,8 +189,11 @@ int scatter(gridhip_imager *im)
     }
 }
 
-struct Kernels {  // conv, w_cache: the imaging function; aw: its Q, the tables and the antennas
+struct Kernels {  // conv, w_cache: the imaging function; aw: its Q, the tables and the antennas; the weighting
     ImagingFn fn = {};
+    int mode = 1;
+    double robust = 0.0, sigma = 0.0;
+    const double *wt_in = nullptr;
     int64_t W = 0, S = 0, A = 0;
     const double *wkerns = nullptr, *wvals = nullptr, *akerns = nullptr;
     const int64_t *a1 = nullptr, *a2 = nullptr;
@@ -219,7 +210,12 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
     GH_CHECK(own(im, &im->psf, cells * 8));
     GH_CHECK(own(im, &im->pmaxbits, 8));
     GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));  // nothing dropped so far
+    GH_CHECK(own(im, &im->wstats, 64));
+    WeightScratch wts;
+    GH_CHECK(weights_begin(ctx, N, k.mode, k.wt_in != nullptr, wts));
     if (n == 0) {  // a valid imager: no PSF, and every image is zero
+        GH_CHECK(weights_finish(ctx, N, 0, k.mode, k.robust, k.sigma, nullptr, wts, nullptr, u, v, stride, lam, nullptr,
+                                true, im->wstats));
         GH_CHECK_HIP(ctx, hipMemsetAsync(im->psf, 0, cells * 8, ctx->stream));
         GH_CHECK_HIP(ctx, hipMemsetAsync(im->pmaxbits, 0, 8, ctx->stream));
         return sync(ctx);
@@ -232,7 +228,7 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
     GH_CHECK(fft_plan_own(ctx, N, &im->fft));
 
     // ---- front end: both coordinate sets, the mirror flags, the weights
-    DevBuf tp[4], tw[2], tb[2], cell, cnt;
+    DevBuf tp[4], tw[2], tb[2], cell;
     double *p[4];
     for (int i = 0; i < 4; ++i) {
         if (im->kind == 0) {
@@ -247,16 +243,15 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
         if (im->kind >= 2) GH_CHECK(tb[i].alloc(ctx, (size_t)n * 8));
     }
     GH_CHECK(cell.alloc(ctx, (size_t)n * 8));
-    GH_CHECK(cnt.alloc(ctx, cells * 4));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(cnt.p, 0, cells * 4, ctx->stream));
     hipLaunchKernelGGL(imager_front_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, u, v,
                        im->kind >= 2 ? w : (const double *)nullptr, stride, lam, N, k.W, k.wvals, p[0], p[1], p[2], p[3],
                        tw[0].as<double>(), tw[1].as<double>(), im->kind == 3 ? tb[0].as<int64_t>() : (int64_t *)nullptr,
-                       im->kind == 3 ? tb[1].as<int64_t>() : (int64_t *)nullptr, im->sw, cell.as<int64_t>(),
-                       cnt.as<unsigned int>());
-    hipLaunchKernelGGL(imager_weight_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, cell.as<int64_t>(),
-                       cnt.as<unsigned int>(), im->sw);
+                       im->kind == 3 ? tb[1].as<int64_t>() : (int64_t *)nullptr, im->sw, cell.as<int64_t>(), k.wt_in,
+                       wts.cnt, wts.den);
     GH_CHECK_HIP(ctx, hipGetLastError());
+    // |sw| = the weight (the sign stays); u^2 + v^2 of the taper is the same on either side of the mirror
+    GH_CHECK(weights_finish(ctx, N, n, k.mode, k.robust, k.sigma, cell.as<int64_t>(), wts, k.wt_in, u, v, stride, lam,
+                            im->sw, true, im->wstats));
 
     // ---- kernel tables and the two record sets: the gather's first, so that gridhip_last_dropped and
     // gridhip_aw_last_stats report the mirrored stream, as do_imaging does
@@ -355,20 +350,53 @@ int create(gridhip_ctx *ctx, int kind, int64_t N, int64_t n, const Kernels &k, d
 
 extern "C" {
 
-int gridhip_imager_create_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
-                              int64_t gw, const double *kv, double theta, int64_t lam, int64_t n, const double *u,
-                              const double *v, const double *w, int64_t uv_stride, gridhip_imager **imager)
+int gridhip_imager_create_weighted_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
+                                       int64_t gw, const double *kv, double theta, int64_t lam, int64_t n, const double *u,
+                                       const double *v, const double *w, int64_t uv_stride, int mode, double robust,
+                                       double taper_sigma, const double *wt_in, gridhip_imager **imager)
 {
     if (imager) *imager = nullptr;
     if (!ctx) return GRIDHIP_EINVAL;
     Kernels k;
     k.fn = {kind, wstep, Q, npixFF, gh, kind == 2 ? gh : gw, kv, theta, lam};
+    k.mode = mode, k.robust = robust, k.sigma = taper_sigma, k.wt_in = wt_in;
     int64_t N = 0;
     GH_CHECK(imaging_fn_check(ctx, k.fn, &N));
+    GH_CHECK(weights_mode_check(ctx, mode, robust, taper_sigma));
     if (!imager || n < 0 || uv_stride < 1 || (n > 0 && (!u || !v || (kind == 2 && !w))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     if (n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per imager");
     return create(ctx, kind, N, n, k, (double)lam, u, v, w, uv_stride, imager);
+}
+
+int gridhip_imager_create_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
+                              int64_t gw, const double *kv, double theta, int64_t lam, int64_t n, const double *u,
+                              const double *v, const double *w, int64_t uv_stride, gridhip_imager **imager)
+{
+    return gridhip_imager_create_weighted_dev(ctx, kind, wstep, Q, npixFF, gh, gw, kv, theta, lam, n, u, v, w, uv_stride, 1,
+                                              0.0, 0.0, nullptr, imager);
+}
+
+int gridhip_imager_create_aw_weighted_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
+                                          int64_t A, const double *wkerns, const double *wvals, const double *akerns,
+                                          int64_t n, const double *u, const double *v, const double *w,
+                                          int64_t uv_stride, const int64_t *a1, const int64_t *a2, int mode, double robust,
+                                          double taper_sigma, const double *wt_in, gridhip_imager **imager)
+{
+    if (imager) *imager = nullptr;
+    if (!ctx) return GRIDHIP_EINVAL;
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, nullptr};
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N, false));
+    GH_CHECK(weights_mode_check(ctx, mode, robust, taper_sigma));
+    if (!imager) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    // (the aw plans' limits, checked before anything is allocated)
+    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
+        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
+    Kernels k;
+    k.fn.Q = Q, k.W = W, k.S = S, k.A = A, k.wkerns = wkerns, k.wvals = wvals, k.akerns = akerns, k.a1 = a1, k.a2 = a2;
+    k.mode = mode, k.robust = robust, k.sigma = taper_sigma, k.wt_in = wt_in;
+    return create(ctx, 3, N, n, k, (double)lam, u, v, w, uv_stride, imager);
 }
 
 int gridhip_imager_create_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
@@ -376,18 +404,17 @@ int gridhip_imager_create_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, in
                                  int64_t n, const double *u, const double *v, const double *w, int64_t uv_stride,
                                  const int64_t *a1, const int64_t *a2, gridhip_imager **imager)
 {
-    if (imager) *imager = nullptr;
-    if (!ctx) return GRIDHIP_EINVAL;
-    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, nullptr};
-    int64_t N = 0;
-    GH_CHECK(aw_check(ctx, a, &N, false));
-    if (!imager) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
-    // (the aw plans' limits, checked before anything is allocated)
-    if (S > 63 || A > 46340 || n > (int64_t)0x7fffff00 || W * Q * Q >= ((int64_t)1 << 30))
-        return fail(ctx, GRIDHIP_EUNSUPPORTED, "shape outside aw limits");
-    Kernels k;
-    k.fn.Q = Q, k.W = W, k.S = S, k.A = A, k.wkerns = wkerns, k.wvals = wvals, k.akerns = akerns, k.a1 = a1, k.a2 = a2;
-    return create(ctx, 3, N, n, k, (double)lam, u, v, w, uv_stride, imager);
+    return gridhip_imager_create_aw_weighted_dev(ctx, theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride,
+                                                 a1, a2, 1, 0.0, 0.0, nullptr, imager);
+}
+
+int gridhip_imager_weight_stats_dev(gridhip_imager *im, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (!stats) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return copy_out(ctx, stats, im->wstats, 64, true);
 }
 
 int gridhip_imager_psf_dev(gridhip_imager *im, double *psf, double *pmax)

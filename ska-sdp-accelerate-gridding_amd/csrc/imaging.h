@@ -275,4 +275,41 @@ int fit_beam_run(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window,
 int restore_run(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
                 int64_t support, double *restored);
 
+// ---- imaging weights (weights.hip) ---------------------------------------------------------------------------------------
+// The cell code of a flagged visibility (a data weight that is not > 0); -1 stays "outside the grid".
+constexpr int64_t WEIGHT_FLAGGED = -2;
+// What the density pass does with one visibility whose doweight cell is c: a flagged one takes part in nothing, an
+// unflagged one in the grid adds its data weight to the density (dens, fp64) or, without data weights, 1 to the count
+// (cnt); whichever the mode does not need is null.  Returns the cell code the second pass reads.
+__device__ __forceinline__ int64_t weight_note(int64_t c, const double *__restrict__ wt_in, int64_t k,
+                                               unsigned int *__restrict__ cnt, double *__restrict__ dens)
+{
+    if (wt_in) {
+        const double s = wt_in[k];
+        if (!(s > 0.0)) return WEIGHT_FLAGGED;
+        if (c >= 0 && dens) atomicAdd(&dens[c], s);
+    } else if (c >= 0 && cnt) {
+        atomicAdd(&cnt[c], 1u);
+    }
+    return c;
+}
+// gridhip_weights' rules for mode, robust and taper_sigma (GRIDHIP_EINVAL)
+int weights_mode_check(gridhip_ctx *ctx, int mode, double robust, double sigma);
+// The scratch of one weighting: the N x N density (counts without data weights; absent for natural weighting) and the
+// accumulators (the two sums over the cells, then one row of partial sums per work-group of the second pass).
+struct WeightScratch {
+    DevBuf dens, acc;
+    unsigned int *cnt = nullptr;  // one of the two views of dens, or neither
+    double *den = nullptr;
+};
+// takes the scratch from the pool and zeroes it with a kernel (no memset node)
+int weights_begin(gridhip_ctx *ctx, int64_t N, int mode, bool data_weights, WeightScratch &s);
+// Everything after the density pass, kernels only: the sums over the cells (Briggs), the pass that writes the weights and
+// the partial sums, and (stats != null) the 8 doubles.  cell: the codes the density pass left, or null - the pass then
+// takes the cell of (u / lam, v / lam) itself (natural weighting needs no density pass).  u, v are read for the taper and
+// for a null cell only.  keep_sign: out holds +-1 and keeps its sign (an imager's mirror flag).  out may be wt_in.
+int weights_finish(gridhip_ctx *ctx, int64_t N, int64_t n, int mode, double robust, double sigma, const int64_t *cell,
+                   WeightScratch &s, const double *wt_in, const double *u, const double *v, int64_t stride, double lam,
+                   double *out, bool keep_sign, double *stats);
+
 }  // namespace gridhip

@@ -13,6 +13,7 @@
 //   predict / predict_aw: the way back, model image -> visibilities (absent from the reference)
 //   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
+//   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -307,6 +308,28 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         const F b[8] = {beam.A, beam.B, beam.C, beam.bmaj, beam.bmin, beam.bpa, beam.ncells, beam.ok};
         Matrix<F> out = residual;
         check(gridhip_restore(ctx_, model.h, model.data.data(), residual.data.data(), b, support, out.data.data()));
+        return out;
+    }
+
+    // ---- imaging weights (gridhip_weights; include/gridhip.h, "imaging weights") ----
+    enum class Weighting : int { natural = 0, uniform = 1, briggs = 2 };
+    struct WeightStats {
+        F sum_w, sum_w2_over_s, sum_s, noise, f2, n_used, n_flagged, n_outside;
+    };
+    // The weights of the baselines `uvw` (wavelengths, taken as given: mirror first for Hermitian cells) on the grid of
+    // gridhip_image_size(theta, lam): robust is Briggs', taper_sigma a Gaussian taper in wavelengths (0: none), data the
+    // data weights (empty: ones; a value that is not > 0 flags its visibility, whose weight is exactly 0).
+    std::vector<F> weights(F theta, Int lam, const BaseLines &uvw, Weighting mode = Weighting::uniform, F robust = 0,
+                           F taper_sigma = 0, const std::vector<F> &data = {}, WeightStats *stats = nullptr)
+    {
+        const Int n = (Int)uvw.u.size();
+        if ((Int)uvw.v.size() != n || (!data.empty() && (Int)data.size() != n))
+            throw Error(GRIDHIP_EINVAL, "weights: u, v and the data weights must hold one value per visibility");
+        std::vector<F> out((size_t)n);
+        F st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_weights(ctx_, theta, lam, n, uvw.u.data(), uvw.v.data(), 1, data.empty() ? nullptr : data.data(),
+                              (int)mode, robust, taper_sigma, out.data(), st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
         return out;
     }
 

@@ -25,6 +25,7 @@ from . import _lib
 from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
                        image_of, imaging_function, in_place, is_torch)
+from ._marshal import weighting as _weighting
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
 
@@ -418,20 +419,50 @@ class Context(Handle):
         self._call(be, "restore", shape[0], model, residual, beam, int(support), out)
         return out
 
-    def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None):
+    def weights(self, theta, lam, p, mode="uniform", robust=0.0, taper=0.0, weights=None, out=None):
+        """Imaging weights of the baselines `p` (wavelengths, taken as given: mirror first for Hermitian cells; a (u, v[, w])
+        tuple or an (n, 3) array) on the N x N grid of image_size(theta, lam) (gridhip_weights[_dev]; include/gridhip.h,
+        "imaging weights"): mode "natural" | "uniform" | "briggs" with `robust`, a Gaussian taper of sigma `taper`
+        wavelengths (0: none) and the data weights `weights` (None: ones; a value that is not > 0 flags its visibility,
+        whose weight is exactly 0).  Returns (w, stats): n float64 weights and the 8 values [sum w, sum w^2 / s, sum s,
+        noise, f^2, n_used, n_flagged, n_outside].  out: the array to write (a new one when None); it may be `weights`
+        itself.  numpy arrays take the synchronous host form; torch cuda tensors the asynchronous one on torch's stream,
+        and both results are cuda tensors: nothing is read back."""
+        be = backend(p[0] if isinstance(p, (tuple, list)) else p)
+        u, v, st = baselines(be, p, 2)
+        n = int(u.shape[0])
+        m, robust, taper, wt = _weighting(be, mode, robust, taper, weights, n)
+        if out is None:
+            out = be.empty(n, be.f64, u)
+        elif not (be is backend(out) and be.ok(out, be.f64) and tuple(out.shape) == (n,)):
+            raise ValueError(f"out must be {be.form.replace('complex128', 'float64')} of shape ({n},)")
+        stats = be.empty(8, be.f64, u)
+        self._call(be, "weights", float(theta), int(lam), n, u, v, st, wt, m, robust, taper, out, stats)
+        return out, stats
+
+    def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None, weighting="uniform", robust=0.0, taper=0.0, weights=None):
         """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
         and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
         (gridhip_imager): mirror, weights, w-bins, kernel tables, both binnings and the PSF are made here.  Returns an
         Imager whose cycle(vis, model) is do_imaging(predict(model, vis_sub=vis))'s image in one asynchronous call.  Every
-        argument may be freed or changed afterwards."""
+        argument may be freed or changed afterwards.
+        weighting "natural" | "uniform" | "briggs", robust, taper and weights (n cuda float64 data weights in the order of
+        vis, or None) are Context.weights' (gridhip_imager_create[_aw]_weighted_dev): the density is taken on the mirrored
+        baselines, a visibility whose data weight is not > 0 contributes nothing to any image even where its vis is NaN,
+        and the default is the uniform weighting of do_imaging."""
         be = device()
         u, v, w, st = baselines(be, uvw, 3)
         tl, n, h = (float(theta), int(lam)), int(u.shape[0]), C.c_void_p()
+        wargs = _weighting(be, weighting, robust, taper, weights, n)
+        if wargs == (1, 0.0, 0.0, None):
+            name, wargs = "imager_create", ()
+        else:
+            name = "imager_create_weighted"
         if imgfn[0] == "aw":
             tables, a1, a2 = aw_tables(be, imgfn[1], imgfn[2], imgfn[3], a1, a2)
-            self._call(be, "imager_create_aw", *tl, *tables, n, u, v, w, st, a1, a2, C.byref(h))
+            self._call(be, name.replace("create", "create_aw"), *tl, *tables, n, u, v, w, st, a1, a2, *wargs, C.byref(h))
         else:
-            self._call(be, "imager_create", *imaging_function(be, imgfn), *tl, n, u, v, w, st, C.byref(h))
+            self._call(be, name, *imaging_function(be, imgfn), *tl, n, u, v, w, st, *wargs, C.byref(h))
         return Imager(self, h, n, self.image_size(theta, lam), u.device)
 
 
@@ -606,6 +637,15 @@ class Imager(_Bound):
         self._call(be, "imager_deconvolve", vis, model, out, int(nmajor),
                    *clean_scalars(gain, threshold, niter, border, patch), stats)
         return model, out, stats
+
+    def weight_stats(self):
+        """The stats of the weighting the imager was created with (gridhip_imager_weight_stats_dev): Context.weights'
+        8 values as a cuda tensor, copied on torch's stream."""
+        self._open()
+        be = device()
+        stats = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_weight_stats", stats)
+        return stats
 
     def beam(self, window=8, cut=0.5):
         """Context.fit_beam on the imager's own PSF (gridhip_imager_beam_dev): the 8 values as a cuda tensor,

@@ -36,6 +36,8 @@ _PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, v
 _CLEAN = [vp, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
 _FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
 _RESTORE = [vp, i64, vp, vp, vp, i64, vp]
+_WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_double, vp, vp]
+_WEIGHTING = [ci, C.c_double, C.c_double, vp]  # mode, robust, taper_sigma, wt_in
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -115,6 +117,13 @@ SIGNATURES = {
     "gridhip_restore_dev": (ci, _RESTORE),
     "gridhip_imager_beam_dev": (ci, [vp, i64, C.c_double, vp]),
     "gridhip_imager_restore_dev": (ci, [vp, vp, vp, i64, C.c_double, i64, vp, vp]),
+    "gridhip_weights": (ci, _WEIGHTS),
+    "gridhip_weights_dev": (ci, _WEIGHTS),
+    "gridhip_imager_create_weighted_dev": (ci, [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, i64, vp, vp, vp, i64,
+                                                *_WEIGHTING, C.POINTER(vp)]),
+    "gridhip_imager_create_aw_weighted_dev": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp,
+                                                   i64, vp, vp, *_WEIGHTING, C.POINTER(vp)]),
+    "gridhip_imager_weight_stats_dev": (ci, [vp, vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

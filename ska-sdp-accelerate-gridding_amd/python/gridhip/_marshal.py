@@ -188,6 +188,30 @@ def beam_support(beam):
     return R
 
 
+WEIGHTINGS = {"natural": 0, "uniform": 1, "briggs": 2}
+
+
+def weighting(be, mode, robust, taper, weights, n):
+    """mode, robust, taper_sigma, wt_in as gridhip_weights and the weighted imager creations take them: the mode by name,
+    a finite robust, a taper sigma >= 0 in wavelengths (0: none) and the data weights - n float64 values (converted
+    where they must be; an array already in the ABI's form goes as it is, so that it can be the output too) or None."""
+    import math
+    if mode not in WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, not {mode!r}")
+    robust, taper = float(robust), float(taper)
+    if not math.isfinite(robust):
+        raise ValueError("robust must be finite")
+    if not taper >= 0.0:
+        raise ValueError("taper must be >= 0 (the sigma in wavelengths; 0: no taper)")
+    if weights is not None:
+        if be is not backend(weights) and be is not HOST:
+            raise ValueError(f"weights must be {be.form.replace('complex128', 'float64')}")
+        weights = be.cv(weights, be.f64)
+        if tuple(weights.shape) != (n,):
+            raise ValueError(f"weights must hold one value per visibility ({n}), not {tuple(weights.shape)}")
+    return WEIGHTINGS[mode], robust, taper, weights
+
+
 class Handle:
     """Owner of one library handle `_h` (a context, plan, imager or communicator): destroyed once, by close() or by the
     collector; _call passes it to an entry point and raises GridHipError with the owner's last-error text."""
