@@ -32,6 +32,8 @@ module GridHip
   , ImagerH, withImager, imagerCycleIO
   -- * deconvolution: Hogbom CLEAN, alone or inside an imager's major-cycle loop (absent from the reference)
   , CleanOptions(..), cleanIO, imagerCleanIO, imagerDeconvolveIO
+  -- * multi-scale CLEAN: the same with components of several scales (absent from the reference)
+  , mscleanIO, imagerMscleanIO, imagerMsDeconvolveIO, msDefaultBias
   -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
   , fitBeamIO, restoreIO, imagerBeamIO, imagerRestoreIO
   -- * imaging weights: natural, uniform, Briggs, taper and data weights, alone or as what an imager is created with
@@ -271,6 +273,18 @@ foreign import ccall unsafe "gridhip_imager_clean_dev"
 -- int gridhip_imager_deconvolve_dev(imager, vis, model, image, nmajor, gain, threshold, niter, border, patch, stats)
 foreign import ccall unsafe "gridhip_imager_deconvolve_dev"
   c_imager_deconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_msclean(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_msclean"
+  c_msclean :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_msclean_dev(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_msclean_dev"
+  c_msclean_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_msclean_dev(imager, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_imager_msclean_dev"
+  c_imager_msclean_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_msdeconvolve_dev(imager, vis, model, image, nmajor, S, scales, bias, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_imager_msdeconvolve_dev"
+  c_imager_msdeconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
 -- int gridhip_fit_beam(ctx, N, psf, window, cut, beam)
 foreign import ccall unsafe "gridhip_fit_beam"
   c_fit_beam :: Ptr Ctx -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
@@ -798,6 +812,79 @@ imagerDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) nma
               c_memcpy_d2h c (castPtr ps) (castPtr ds) (fi (32 * rows)) >>= check h
               c_synchronize c >>= check h
               statsRows rows ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Multi-scale deconvolution (include/gridhip.h, "multi-scale deconvolution"): scales in cells increasing from 0, one
+-- bias per scale; both are host arrays for every form.  A stats row is [iterations, final peak, its flat index, the
+-- last component's scale, flux added, 0, components per scale x 6].
+
+msStatsRows :: Int -> Ptr CDouble -> IO [[F]]
+msStatsRows rows p = mapM (\r -> map realToFrac <$> peekArray 12 (p `advancePtr` (12 * r))) [0 .. rows - 1]
+
+-- the default bias of a scale list: 1 - 0.6 a_s / a_max
+msDefaultBias :: [F] -> [F]
+msDefaultBias scales = let amax = maximum scales in [if amax > 0 then 1 - 0.6 * a / amax else 1 | a <- scales]
+
+-- | mscleanIO h opts scales bias image psf model: cleanIO with multi-scale components - the host form, synchronous
+mscleanIO :: GridHip -> CleanOptions -> [F] -> [F] -> A.Matrix F -> A.Matrix F -> A.Matrix F
+          -> IO (A.Matrix F, A.Matrix F, [F])
+mscleanIO h@(GridHip c) (CleanOptions g t ni b pa) scales bias image psf model = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape image
+      copyOf m = do o <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+                    withF m $ \s -> withForeignPtr o $ \d -> copyArray d s (n' * n')
+                    return o
+  res <- copyOf image
+  mdl <- copyOf model
+  st <- withF psf $ \pp -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pm -> allocaArray 12 $ \ps ->
+          withArray (map realToFrac scales) $ \psc -> withArray (map realToFrac bias) $ \pbi -> do
+            c_msclean c (fi n') pp pr pm (fi (length scales)) psc pbi (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ps
+              >>= check h
+            head <$> msStatsRows 1 ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
+
+-- | imagerMscleanIO im opts scales bias image model: mscleanIO with the imager's own PSF (gridhip_imager_msclean_dev);
+-- the imager keeps the cross-PSFs of the scale list between calls
+imagerMscleanIO :: ImagerH -> CleanOptions -> [F] -> [F] -> A.Matrix F -> A.Matrix F -> IO (A.Matrix F, A.Matrix F, [F])
+imagerMscleanIO (ImagerH h@(GridHip c) p _ n') (CleanOptions g t ni b pa) scales bias image model = do
+  res <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+  st <- withF image $ \pi' -> withDev h pi' bytes $ \di -> withF model $ \pm -> withDev h pm bytes $ \dm ->
+          allocaArray 12 $ \ps -> withDev h ps 96 $ \ds -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pq ->
+            withArray (map realToFrac scales) $ \psc -> withArray (map realToFrac bias) $ \pbi -> do
+              c_imager_msclean_dev p di dm (fi (length scales)) psc pbi (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ds
+                >>= check h
+              c_memcpy_d2h c (castPtr pr) (castPtr di) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr ps) (castPtr ds) 96 >>= check h
+              c_synchronize c >>= check h
+              head <$> msStatsRows 1 ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
+
+-- | imagerMsDeconvolveIO im opts scales bias nmajor vis model: imagerDeconvolveIO with the multi-scale minor cycle
+-- (gridhip_imager_msdeconvolve_dev): (the model, the closing residual image, one stats row per major cycle)
+imagerMsDeconvolveIO :: ImagerH -> CleanOptions -> [F] -> [F] -> Int -> A.Vector Visibility -> A.Matrix F
+                     -> IO (A.Matrix F, A.Matrix F, [[F]])
+imagerMsDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) scales bias nmajor vis model = do
+  img <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+      rows = max 0 nmajor
+  st <- withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withF model $ \pm -> withDev h pm bytes $ \dm ->
+          withForeignPtr img $ \pi' -> withDev h pi' bytes $ \di -> allocaArray (12 * rows) $ \ps ->
+            withDev h ps (96 * rows) $ \ds -> withForeignPtr mdl $ \pq ->
+              withArray (map realToFrac scales) $ \psc -> withArray (map realToFrac bias) $ \pbi -> do
+                c_imager_msdeconvolve_dev p dv dm di (fi nmajor) (fi (length scales)) psc pbi (realToFrac g) (realToFrac t)
+                  (fi ni) (fi b) (fi pa) ds >>= check h
+                c_memcpy_d2h c (castPtr pi') (castPtr di) (fi bytes) >>= check h
+                c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+                c_memcpy_d2h c (castPtr ps) (castPtr ds) (fi (96 * rows)) >>= check h
+                c_synchronize c >>= check h
+                msStatsRows rows ps
   let sh = A.Z A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
 

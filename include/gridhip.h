@@ -454,7 +454,7 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
  * 4 x 8 B coordinates instead of records for the simple kind; per N^2 cell 16 B (grid) + 16 B (transform) + 8 B (psf),
  * and 16 B more for odd N; the kernel tables (conv: 2 tables; w_cache: one plane per w-bin of each stream; aw: each
  * batch's distinct kernels, twice) and one hipFFT plan; after its first clean or deconvolve also clean's state block and
- * tile table, 64 B + 16 B per 16 x 128 cells, and after its first restore without a `beam` output 64 B for the fitted beam
+ * tile table, 64 B + 16 B per 16 x 128 cells, after its first msclean that call's scratch (see there), and after its first restore without a `beam` output 64 B for the fitted beam
  * (all released at destroy).
  * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
  * and 1).  n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
@@ -533,6 +533,73 @@ int gridhip_imager_clean_dev(gridhip_imager *imager, double *residual, double *m
 int gridhip_imager_deconvolve_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
                                   int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
                                   int64_t patch, double *stats);
+
+/* ---- multi-scale deconvolution: multi-scale CLEAN (Cornwell 2008) on the device, beside the Hogbom one -------------------
+ * Hogbom CLEAN takes one cell per component, so extended emission costs thousands of components and leaves a pedestal.
+ * Here a component is a tapered paraboloid of one of S scales.  The reference has neither form: the semantics are defined
+ * here.  psf, residual and model are as for gridhip_clean, c = N / 2.  scales a_0 < a_1 < ... < a_{S-1} are in cells
+ * (doubles), 1 <= S <= 6, a_0 == 0, a_{S-1} <= 32; bias b_s is finite and > 0, one per scale.  scales and bias are HOST
+ * arrays for every form: they fix launch shapes and kernel arguments and are read at call time.
+ * SCALE KERNEL: m_0 is the delta.  For s >= 1, R_s = ceil(a_s) - 1 and
+ *     t(dy, dx) = max(0, 1 - (dx^2 + dy^2) / a_s^2)   over |dy|, |dx| <= R_s
+ * in fp64, the quotient rounded, no fused multiply-add; sum = its taps added from +0.0, each row in dx order, then the rows
+ * in dy order; m_s = t / sum.  m_s is made on the device by a kernel (nothing is uploaded).
+ * CONVOLUTION: (m (*) X)[y, x] = sum of X[y - dy, x - dx] * m(dy, dx), cells outside the image counting as zero, the taps
+ * dy ascending, then dx ascending, one fused multiply-add each from +0.0 (the restore's rule).  Convolving with the delta
+ * is the identity and is not computed: P_00 is psf itself and R_0 is residual itself, in place.
+ * SET-UP:  P_s = m_s (*) psf;  P_st = m_t (*) P_s for s <= t (P_ts means P_st);  R_t = m_t (*) residual for t >= 1;
+ *          q_s = P_ss[c, c].
+ *     repeat at most niter times:
+ *         for each scale: k_s = the peak of |R_s| under clean's search rule (border, ties to the lowest flat index, NaN
+ *                         never), p_s = R_s[k_s]
+ *         stop if no cell of R_0 can be selected or |p_0| <= threshold   (before anything is subtracted; the threshold is
+ *                                                                         in units of the plain residual)
+ *         s* = the scale with the largest |b_s * (p_s / q_s)|  (the quotient rounded, then the product; ties to the lowest
+ *              s; a scale whose q_s is not positive and finite, or which has no selectable cell, never wins - if none
+ *              can, the loop stops)
+ *         f = gain * (p_s* / q_s*),  k = k_s* = (y, x)
+ *         model[y', x'] += f * m_s*(y' - y, x' - x)         over the kernel's support, clipped to the image; the product
+ *                                                           is rounded, then added (the delta's one cell receives
+ *                                                           gain * (p / q) in one fused step, as gridhip_clean's does)
+ *         R_t[y', x'] -= f * P_{s* t}[y' - y + c, x' - x + c]   for every t; the clipping and the patch rule are exactly
+ *                                                           gridhip_clean's; the product is rounded, then subtracted
+ *     stats = 12 doubles { iterations, final p_0, final k_0, the s* of the last component taken (-1 if none), sum of f, 0,
+ *                          n_0 .. n_5 }, n_s the number of components taken at scale s
+ * No atomics anywhere: a call is deterministic bit for bit, and the host, _dev and imager forms give the same bits.  With
+ * S = 1, scales = {0}, bias = {1} and psf[c, c] == 1.0, residual and model come out with the bits of gridhip_clean.
+ * Only residual (R_0) and model are returned; the smoothed residuals are scratch.
+ * Arguments: gridhip_clean's rules, and GRIDHIP_EINVAL for S out of range, NULL scales or bias, scales not strictly
+ * increasing or a_0 != 0, a bias not finite and positive - all checked before anything is touched; a_{S-1} > 32 is
+ * GRIDHIP_EUNSUPPORTED (it would need an FFT-based set-up).
+ * The set-up convolutions are LDS-tiled direct convolutions (the restore's tile and halo staging, the taps staged once per
+ * work-group; a work-group whose staged window holds no non-zero cell stores +0.0, the sum's own bits).  An iteration is
+ * two launches as gridhip_clean's: one covers the tiles the update region overlaps times S - slice t subtracts
+ * f * P_{s* t} from R_t and recomputes the entries of table t in the same pass - and a one-work-group kernel reduces the S
+ * tables, applies the stop test and the scale choice and adds the model blob (at most 63 x 63 cells).  The stop condition
+ * lives on the device; a launch that finds the state stopped returns at its first instruction.
+ * gridhip_msclean is synchronous and stages host arrays through the context's pool.  The _dev forms enqueue kernels only on
+ * the context's stream (no memset or copy node), allocate nothing after the first call of a shape, read nothing back and
+ * never synchronise.  Scratch is S - 1 smoothed residuals, S (S + 1) / 2 - 1 cross-PSFs (N x N doubles each), the taps,
+ * the state block and S tile tables: from the context's pool, or, for the imager forms, memory the imager owns (grown -
+ * one hipFree - by a call with a longer scale list).  An imager keeps the taps and the cross-PSFs between calls, keyed by
+ * the scale list: its PSF never changes, so they are built by the first call with a given list only. */
+int gridhip_msclean(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                    const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                    int64_t patch, double *stats);
+int gridhip_msclean_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                        const double *scales, const double *bias, double gain, double threshold, int64_t niter,
+                        int64_t border, int64_t patch, double *stats);
+/* gridhip_msclean_dev with the imager's own PSF (nothing is copied) and N */
+int gridhip_imager_msclean_dev(gridhip_imager *imager, double *residual, double *model, int64_t S, const double *scales,
+                               const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                               int64_t patch, double *stats);
+/* gridhip_imager_deconvolve_dev with the multi-scale minor cycle, DEFINED BY THE CALLS IT REPLACES:
+ *     repeat nmajor times: image = cycle(model, vis); msclean(image, model) with stats + 12 * i (when stats != NULL)
+ *     image = cycle(model, vis)
+ * stats is nmajor x 12 doubles on the device, or NULL.  The cross-PSFs are built by the first of the nmajor cleans. */
+int gridhip_imager_msdeconvolve_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
+                                    int64_t nmajor, int64_t S, const double *scales, const double *bias, double gain,
+                                    double threshold, int64_t niter, int64_t border, int64_t patch, double *stats);
 
 /* ---- restoring beam and restore: from clean's model and residual to a map, on the device -----------------------------
  * The reference stops at the dirty image: the semantics are defined here.  All images are real N x N, row-major [y][x];

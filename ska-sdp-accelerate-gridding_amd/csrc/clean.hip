@@ -24,14 +24,7 @@ namespace gridhip {
 
 namespace {
 
-constexpr int CLEAN_TH = 16, CLEAN_TW = 128;  // one wave takes one row of a tile, 16 bytes per lane
-static_assert(CLEAN_MAX_N == (int64_t)CLEAN_TH * 65535, "imaging.h states the tile grid's limit");
-
-struct CleanEntry {  // a tile's peak: the signed value and its flat index; k < 0: no cell of the tile can be selected
-    double v;
-    long long k;
-};
-
+// (the tile, CleanEntry, consider and group_best are in imaging.h: msclean.hip shares them)
 struct CleanState {  // 64 bytes at the head of the scratch block
     double peak;          // the residual's current peak (signed); NaN when no cell can be selected
     long long k;          // its flat index, -1 when none
@@ -41,34 +34,6 @@ struct CleanState {  // 64 bytes at the head of the scratch block
     long long stopped;    // threshold reached, out of iterations or nothing to select: every later launch returns
     long long pad[2];
 };
-
-__device__ __forceinline__ int64_t lo64(int64_t a, int64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ int64_t hi64(int64_t a, int64_t b) { return a > b ? a : b; }
-
-// does (v, k) beat the best so far?  NaN never does; a larger magnitude does, and the lower index among equals
-__device__ __forceinline__ void consider(double v, long long k, double &bv, long long &bk)
-{
-    const double a = fabs(v), b = fabs(bv);
-    if (v == v && k >= 0 && (bk < 0 || a > b || (a == b && k < bk))) {
-        bv = v;
-        bk = k;
-    }
-}
-
-// the best of a work-group in thread 0 (sh: one entry per wave)
-__device__ __forceinline__ void group_best(double &bv, long long &bk, CleanEntry *sh)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_down(bv, off);
-        const long long ok = __shfl_down(bk, off);
-        consider(ov, ok, bv, bk);
-    }
-    const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[wave] = {bv, bk};
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < nwaves; ++w) consider(sh[w].v, sh[w].k, bv, bk);
-}
 
 // One tile per work-group.  SUB = false: grid (ntx, nty), the tile's entry from the residual as it is.  SUB = true: the
 // grid covers the most tiles the update region can overlap, counted from the region's first tile; work-groups past its
@@ -196,13 +161,6 @@ __global__ void __launch_bounds__(1024)
         stats[2] = (double)bk;
         stats[3] = flux;
     }
-}
-
-// the most tiles of side T an interval of L cells overlaps, wherever it starts (at most all `have` of them)
-int64_t tiles_spanned(int64_t L, int64_t T, int64_t have)
-{
-    const int64_t t = (L + T - 2) / T + 1;
-    return t < have ? t : have;
 }
 
 bool overlap(const double *a, const double *b, size_t bytes)

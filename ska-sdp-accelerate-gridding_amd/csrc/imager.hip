@@ -133,6 +133,11 @@ struct gridhip_imager {
     gridhip_aw_plan *aw_gather = nullptr, *aw_scatter = nullptr;
     bool clear_pred = false;  // the gather does not write every prediction: they start from zero
     void *clean_scratch = nullptr;  // clean's state block and tile table (clean.hip), made by the first clean
+    // msclean's scratch (msclean.hip), made by the first msclean and grown by one that needs more; it keeps the taps and
+    // the cross-PSFs of the scale list ms_scales between calls (the PSF never changes)
+    void *ms_scratch = nullptr;
+    size_t ms_bytes = 0;
+    std::vector<double> ms_scales;
     double *beam = nullptr;         // the fitted beam of a restore that does not return it (8 doubles), made by the first
     double *wstats = nullptr;       // the weighting's stats (8 doubles), written at creation
 };
@@ -494,6 +499,52 @@ int gridhip_imager_deconvolve_dev(gridhip_imager *im, const double *vis, double 
     return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
 }
 
+int gridhip_imager_msclean_dev(gridhip_imager *im, double *residual, double *model, int64_t S, const double *scales,
+                               const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                               int64_t patch, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(msclean_check(ctx, im->N, im->psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t need = msclean_scratch_bytes(im->N, S);
+    if (need > im->ms_bytes) {  // (the first call, or a longer scale list: hipFree waits for the work that uses the old block)
+        if (im->ms_scratch) {
+            for (void *&p : im->owned)
+                if (p == im->ms_scratch) p = nullptr;
+            (void)hipFree(im->ms_scratch);
+            im->ms_scratch = nullptr;
+        }
+        im->ms_bytes = 0;
+        im->ms_scales.clear();
+        GH_CHECK(own(im, &im->ms_scratch, need));
+        im->ms_bytes = need;
+    }
+    const std::vector<double> key(scales, scales + S);
+    const bool setup = key != im->ms_scales;
+    im->ms_scales.clear();  // (a set-up that fails half way leaves no key behind)
+    GH_CHECK(msclean_run(ctx, im->N, im->psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
+                         im->ms_scratch, setup));
+    im->ms_scales = key;
+    return GRIDHIP_OK;
+}
+
+int gridhip_imager_msdeconvolve_dev(gridhip_imager *im, const double *vis, double *model, double *image, int64_t nmajor,
+                                    int64_t S, const double *scales, const double *bias, double gain, double threshold,
+                                    int64_t niter, int64_t border, int64_t patch, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "msdeconvolve: bad argument");
+    GH_CHECK(msclean_check(ctx, im->N, im->psf, image, model, S, scales, bias, gain, threshold, niter, border, patch));
+    for (int64_t c = 0; c < nmajor; ++c) {
+        GH_CHECK(gridhip_imager_cycle_dev(im, model, vis, image, nullptr));
+        GH_CHECK(gridhip_imager_msclean_dev(im, image, model, S, scales, bias, gain, threshold, niter, border, patch,
+                                            stats ? stats + 12 * c : nullptr));
+    }
+    return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
+}
+
 int gridhip_imager_beam_dev(gridhip_imager *im, int64_t window, double cut, double *beam)
 {
     if (!im) return GRIDHIP_EINVAL;
@@ -530,7 +581,8 @@ int gridhip_imager_destroy(gridhip_imager *im)
     gridhip_aw_plan_destroy(im->aw_gather);
     gridhip_aw_plan_destroy(im->aw_scatter);
     fft_plan_drop(im->fft);
-    for (void *p : im->owned) (void)hipFree(p);
+    for (void *p : im->owned)
+        if (p) (void)hipFree(p);
     delete im;
     return GRIDHIP_OK;
 }

@@ -36,6 +36,7 @@ struct ImagingState {
         size_t bytes = 0;
     } wk_cache;
     bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
+    bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
 };
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled
@@ -264,6 +265,66 @@ size_t clean_scratch_bytes(int64_t N);
 int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
               double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
 
+// What clean.hip and msclean.hip share: the tile, a tile's table entry, the search rule and its reductions.
+constexpr int CLEAN_TH = 16, CLEAN_TW = 128;  // one wave takes one row of a tile, 16 bytes per lane
+static_assert(CLEAN_MAX_N == (int64_t)CLEAN_TH * 65535, "the tile grid's limit");
+
+struct CleanEntry {  // a tile's peak: the signed value and its flat index; k < 0: no cell of the tile can be selected
+    double v;
+    long long k;
+};
+
+__device__ __forceinline__ int64_t lo64(int64_t a, int64_t b) { return a < b ? a : b; }
+__device__ __forceinline__ int64_t hi64(int64_t a, int64_t b) { return a > b ? a : b; }
+
+// does (v, k) beat the best so far?  NaN never does; a larger magnitude does, and the lower index among equals
+__device__ __forceinline__ void consider(double v, long long k, double &bv, long long &bk)
+{
+    const double a = fabs(v), b = fabs(bv);
+    if (v == v && k >= 0 && (bk < 0 || a > b || (a == b && k < bk))) {
+        bv = v;
+        bk = k;
+    }
+}
+
+// the best of a work-group in thread 0 (sh: one entry per wave)
+__device__ __forceinline__ void group_best(double &bv, long long &bk, CleanEntry *sh)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_down(bv, off);
+        const long long ok = __shfl_down(bk, off);
+        consider(ov, ok, bv, bk);
+    }
+    const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[wave] = {bv, bk};
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < nwaves; ++w) consider(sh[w].v, sh[w].k, bv, bk);
+}
+
+// the most tiles of side T an interval of L cells overlaps, wherever it starts (at most all `have` of them)
+static inline int64_t tiles_spanned(int64_t L, int64_t T, int64_t have)
+{
+    const int64_t t = (L + T - 2) / T + 1;
+    return t < have ? t : have;
+}
+
+// ---- multi-scale CLEAN (msclean.hip) ---------------------------------------------------------------------------------------
+constexpr int MS_MAX_SCALES = 6;
+constexpr double MS_MAX_SCALE = 32.0;
+// gridhip_msclean's argument rules: clean's, then the scale list's (GRIDHIP_EINVAL; a scale above 32 cells is
+// GRIDHIP_EUNSUPPORTED)
+int msclean_check(gridhip_ctx *ctx, int64_t N, const double *psf, const double *residual, const double *model, int64_t S,
+                  const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                  int64_t patch);
+// the state block, the S tile tables, the taps, the S - 1 smoothed residuals and the S (S + 1) / 2 - 1 cross-PSFs
+size_t msclean_scratch_bytes(int64_t N, int64_t S);
+// gridhip_msclean_dev on checked arguments: kernels only, on ctx->stream.  setup: make the taps, the pointer table and the
+// cross-PSFs of `psf` in scratch; a caller whose scratch holds them for this psf and these scales passes false.
+int msclean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                int64_t patch, double *stats, void *scratch, bool setup);
+
 // ---- the restoring beam and the restore (restore.hip) --------------------------------------------------------------------
 // gridhip_fit_beam's and gridhip_restore's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); the beam's values are
 // not looked at (they may live on the device)
@@ -274,6 +335,20 @@ int restore_check(gridhip_ctx *ctx, int64_t N, const double *model, const double
 int fit_beam_run(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, double *beam);
 int restore_run(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
                 int64_t support, double *restored);
+// What restore.hip and msclean.hip's set-up convolution share: the tile and the staged LDS layout (restore.hip's head).
+constexpr int RS_TH = 32, RS_TW = 64, RS_LX = RS_TW / 8;  // the tile; lanes along x
+// the staged width of `cols` cells (cell u lies at u + u / 8) and the row stride: the next count that is 8 modulo 32
+__host__ __device__ inline int staged_pos(int u) { return u + (u >> 3); }
+inline int staged_stride(int s)
+{
+    const int w = staged_pos(RS_TW + 2 * s - 1) + 1;
+    return w + ((8 - w % 32) + 32) % 32;
+}
+inline size_t restore_lds_bytes(int s)
+{
+    const int K = 2 * s + 1;
+    return ((size_t)(RS_TH + 2 * s) * staged_stride(s) + (size_t)K * K) * sizeof(double);
+}
 
 // ---- imaging weights (weights.hip) ---------------------------------------------------------------------------------------
 // The cell code of a flagged visibility (a data weight that is not > 0); -1 stays "outside the grid".

@@ -31,8 +31,9 @@ namespace gridhip {
 
 namespace {
 
-constexpr int RS_TH = 32, RS_TW = 64, RS_LX = RS_TW / 8;  // the tile; lanes along x
-constexpr int FIT_T = 128;                                // rows of the window one pass of the fit takes
+// (the tile RS_TH x RS_TW and the staged layout - staged_pos, staged_stride, restore_lds_bytes - are in imaging.h:
+// msclean.hip's set-up convolution shares them)
+constexpr int FIT_T = 128;                              // rows of the window one pass of the fit takes
 
 // ---- the fit -----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FIT_T)
@@ -113,19 +114,6 @@ __host__ __device__ inline bool beam_usable(double A, double B, double C, double
 {
     const double inf = __builtin_inf();
     return ok != 0.0 && ok == ok && A > 0.0 && A < inf && C > 0.0 && C < inf && B > -inf && B < inf && A * C - B * B > 0.0;
-}
-
-// the staged width of `cols` cells (cell u lies at u + u / 8) and the row stride: the next count that is 8 modulo 32
-__host__ __device__ inline int staged_pos(int u) { return u + (u >> 3); }
-inline int staged_stride(int s)
-{
-    const int w = staged_pos(RS_TW + 2 * s - 1) + 1;
-    return w + ((8 - w % 32) + 32) % 32;
-}
-inline size_t restore_lds_bytes(int s)
-{
-    const int K = 2 * s + 1;
-    return ((size_t)(RS_TH + 2 * s) * staged_stride(s) + (size_t)K * K) * sizeof(double);
 }
 
 // grid (ceil(N / RS_TW), ceil(N / RS_TH)); dynamic LDS: restore_lds_bytes(s); stride = staged_stride(s).

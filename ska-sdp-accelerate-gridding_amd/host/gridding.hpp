@@ -12,6 +12,7 @@
 //   do_imaging theta lam uvw a1 a2 t f vis imgfn    :509-519 (do_imaging_aw: imgfn = aw_imaging)
 //   predict / predict_aw: the way back, model image -> visibilities (absent from the reference)
 //   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
+//   msclean: multi-scale CLEAN, clean with components of several scales (absent from the reference)
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
@@ -285,6 +286,32 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_clean(ctx_, image.h, psf.data.data(), image.data.data(), model.data.data(), gain, threshold, niter,
                             border, patch, st));
         return {st[0], st[1], st[2], st[3]};
+    }
+
+    // ---- multi-scale CLEAN (gridhip_msclean; include/gridhip.h, "multi-scale deconvolution") ----
+    // clean with components of the given scales (cells, increasing from the delta scale 0, at most 6 and at most 32).
+    // An empty bias is the default 1 - 0.6 a_s / a_max.
+    struct MsCleanStats {
+        F iterations, peak, index, last_scale, flux;
+        F per_scale[6];
+    };
+    MsCleanStats msclean(Matrix<F> &image, const Matrix<F> &psf, Matrix<F> &model, const std::vector<F> &scales,
+                         std::vector<F> bias = {}, F gain = 0.1, F threshold = 0.0, Int niter = 100, Int border = 0,
+                         Int patch = 0)
+    {
+        if (image.h != image.w || psf.h != image.h || psf.w != image.w || model.h != image.h || model.w != image.w)
+            throw Error(GRIDHIP_EINVAL, "msclean: image, psf and model must be N x N");
+        if (bias.empty() && !scales.empty()) {
+            F amax = scales[0];
+            for (F a : scales) amax = a > amax ? a : amax;
+            for (F a : scales) bias.push_back(amax > 0 ? 1 - 0.6 * a / amax : 1);
+        }
+        if (bias.size() != scales.size()) throw Error(GRIDHIP_EINVAL, "msclean: one bias per scale");
+        F st[12] = {0};
+        check(gridhip_msclean(ctx_, image.h, psf.data.data(), image.data.data(), model.data.data(), (Int)scales.size(),
+                              scales.data(), bias.data(), gain, threshold, niter, border, patch, st));
+        MsCleanStats out = {st[0], st[1], st[2], st[3], st[4], {st[6], st[7], st[8], st[9], st[10], st[11]}};
+        return out;
     }
 
     // ---- restoring beam and restore (gridhip_fit_beam, gridhip_restore; include/gridhip.h, "restoring beam and restore") ----

@@ -24,7 +24,7 @@ import ctypes as C
 from . import _lib
 from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
-                       image_of, imaging_function, in_place, is_torch)
+                       image_of, imaging_function, in_place, is_torch, scale_list)
 from ._marshal import weighting as _weighting
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
@@ -381,6 +381,30 @@ class Context(Handle):
         self._call(be, "clean", shape[0], psf, image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
         return model, image, stats
 
+    def msclean(self, image, psf, scales, bias=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None):
+        """Multi-scale CLEAN of the N x N float64 `image` with `psf` (gridhip_msclean[_dev]; include/gridhip.h,
+        "multi-scale deconvolution"): clean() whose components are tapered paraboloids of the `scales` (in cells,
+        increasing from the delta scale 0, at most 6 of them and at most 32 cells), chosen by the largest bias-weighted
+        peak.  `scales` and `bias` are host sequences for numpy and torch images alike; bias=None is
+        1 - 0.6 a_s / a_max.  `image` is UPDATED IN PLACE and returned as the residual, `model` (zeros when None) is
+        accumulated into.  Returns (model, residual, stats); stats = [iterations, final peak, its flat index, the scale
+        of the last component (-1: none), flux added, 0, components per scale x 6]."""
+        be = backend(image)
+        shape = tuple(getattr(image, "shape", ()))
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("image must be N x N")
+        image = in_place(be, image, shape, "image")
+        psf = be.cv(psf, be.f64)
+        if tuple(psf.shape) != shape:
+            raise ValueError(f"psf must be {shape}, as the image")
+        sc, keep = scale_list(scales, bias)
+        model = in_place(be, model, shape, "model", image)
+        stats = be.empty(12, be.f64, image)
+        self._call(be, "msclean", shape[0], psf, image, model, *sc,
+                   *clean_scalars(gain, threshold, niter, border, patch), stats)
+        del keep
+        return model, image, stats
+
     def fit_beam(self, psf, window=8, cut=0.5):
         """The restoring beam of the N x N `psf` (gridhip_fit_beam[_dev]; include/gridhip.h, "restoring beam and
         restore"): an elliptical Gaussian fitted to the main lobe over the cells within `window` of the centre that
@@ -621,11 +645,28 @@ class Imager(_Bound):
         self._call(be, "imager_clean", image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
         return model, image, stats
 
-    def deconvolve(self, vis, nmajor, model=None, out=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+    def msclean(self, image, scales, bias=None, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+        """Context.msclean with the imager's own PSF (gridhip_imager_msclean_dev).  The imager keeps the cross-PSFs of
+        the scale list between calls: a second call with the same `scales` builds and allocates nothing.  Returns
+        (model, residual, stats[12]); asynchronous, and capturable after a first call with these scales."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        image = in_place(be, image, NN, "image")
+        sc, keep = scale_list(scales, bias)
+        model = in_place(be, model, NN, "model", self.device)
+        stats = be.empty(12, be.f64, self.device)
+        self._call(be, "imager_msclean", image, model, *sc, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        del keep
+        return model, image, stats
+
+    def deconvolve(self, vis, nmajor, model=None, out=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0,
+                   scales=None, bias=None):
         """Visibilities to a model image in one asynchronous call (gridhip_imager_deconvolve_dev): nmajor times
         image = cycle(vis, model) then clean(image, model), and one closing cycle, so that the returned image is
         do_imaging(vis - predict(model))'s for the returned model.  model (zeros when None) is accumulated into, out
-        (a new image when None) receives the closing residual image.  Returns (model, image, stats[nmajor, 4])."""
+        (a new image when None) receives the closing residual image.  Returns (model, image, stats[nmajor, 4]).
+        With `scales` (and optionally `bias`) the minor cycle is msclean (gridhip_imager_msdeconvolve_dev) and stats is
+        [nmajor, 12]."""
         self._open()
         be, NN = device(), (self.N, self.N)
         self._ok(vis, be.c128, (self.n,), "vis")
@@ -633,9 +674,18 @@ class Imager(_Bound):
         out = be.empty(NN, be.f64, self.device) if out is None else in_place(be, out, NN, "out")
         if int(nmajor) < 0:
             raise ValueError("nmajor must be >= 0")
-        stats = be.empty((int(nmajor), 4), be.f64, self.device)
-        self._call(be, "imager_deconvolve", vis, model, out, int(nmajor),
+        if scales is None:
+            if bias is not None:
+                raise ValueError("bias goes with scales")
+            stats = be.empty((int(nmajor), 4), be.f64, self.device)
+            self._call(be, "imager_deconvolve", vis, model, out, int(nmajor),
+                       *clean_scalars(gain, threshold, niter, border, patch), stats)
+            return model, out, stats
+        sc, keep = scale_list(scales, bias)
+        stats = be.empty((int(nmajor), 12), be.f64, self.device)
+        self._call(be, "imager_msdeconvolve", vis, model, out, int(nmajor), *sc,
                    *clean_scalars(gain, threshold, niter, border, patch), stats)
+        del keep
         return model, out, stats
 
     def weight_stats(self):

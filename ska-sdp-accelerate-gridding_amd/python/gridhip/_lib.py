@@ -34,6 +34,8 @@ _AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp,
                 C.POINTER(C.c_double)]
 _PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, vp, vp, i64, vp, vp]
 _CLEAN = [vp, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
+_HOST_F64 = C.POINTER(C.c_double)  # an array that is the host's in every form (msclean's scales and bias)
+_MSCLEAN = [vp, i64, vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64, i64, i64, vp]
 _FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
 _RESTORE = [vp, i64, vp, vp, vp, i64, vp]
 _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_double, vp, vp]
@@ -111,6 +113,11 @@ SIGNATURES = {
     "gridhip_clean_dev": (ci, _CLEAN),
     "gridhip_imager_clean_dev": (ci, [vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_imager_deconvolve_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64, vp]),
+    "gridhip_msclean": (ci, _MSCLEAN),
+    "gridhip_msclean_dev": (ci, _MSCLEAN),
+    "gridhip_imager_msclean_dev": (ci, [vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64, i64, i64, vp]),
+    "gridhip_imager_msdeconvolve_dev": (ci, [vp, vp, vp, vp, i64, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64,
+                                             i64, i64, vp]),
     "gridhip_fit_beam": (ci, _FIT_BEAM),
     "gridhip_fit_beam_dev": (ci, _FIT_BEAM),
     "gridhip_restore": (ci, _RESTORE),

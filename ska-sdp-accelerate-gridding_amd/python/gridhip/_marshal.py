@@ -162,6 +162,23 @@ def clean_scalars(gain, threshold, niter, border, patch):
     return float(gain), float(threshold), int(niter), int(border), int(patch)
 
 
+def scale_list(scales, bias):
+    """S, scales, bias as every msclean entry point takes them: host float64 arrays whichever back end the images come
+    from (they fix launch shapes and kernel arguments), passed by address - the caller keeps the returned arrays alive
+    for the call.  bias=None: 1 - 0.6 a_s / a_max (1 for the delta alone)."""
+    sc = np.ascontiguousarray(scales, dtype=np.float64).ravel()
+    if sc.size < 1:
+        raise ValueError("scales must hold at least the delta scale 0")
+    if bias is None:
+        amax = float(sc.max())
+        bias = 1.0 - 0.6 * sc / amax if amax > 0.0 else np.ones_like(sc)
+    bs = np.ascontiguousarray(bias, dtype=np.float64).ravel()
+    if bs.size != sc.size:
+        raise ValueError(f"bias must hold one value per scale ({sc.size}), not {bs.size}")
+    f64p = C.POINTER(C.c_double)
+    return (int(sc.size), sc.ctypes.data_as(f64p), bs.ctypes.data_as(f64p)), (sc, bs)
+
+
 def image_of(be, x, shape, what):
     """An N x N float64 image an entry point only reads (restore's model and residual), converted where it must be"""
     x = be.cv(x, be.f64)
