@@ -34,6 +34,8 @@ module GridHip
   , CleanOptions(..), cleanIO, imagerCleanIO, imagerDeconvolveIO
   -- * multi-scale CLEAN: the same with components of several scales (absent from the reference)
   , mscleanIO, imagerMscleanIO, imagerMsDeconvolveIO, msDefaultBias
+  -- * clean masks and noise-based stop levels: robust image statistics and the _auto forms (absent from the reference)
+  , AutoOptions(..), imageStatsIO, cleanAutoIO, imagerDeconvolveAutoIO
   -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
   , fitBeamIO, restoreIO, imagerBeamIO, imagerRestoreIO
   -- * imaging weights: natural, uniform, Briggs, taper and data weights, alone or as what an imager is created with
@@ -285,6 +287,39 @@ foreign import ccall unsafe "gridhip_imager_msclean_dev"
 -- int gridhip_imager_msdeconvolve_dev(imager, vis, model, image, nmajor, S, scales, bias, gain, threshold, niter, border, patch, stats)
 foreign import ccall unsafe "gridhip_imager_msdeconvolve_dev"
   c_imager_msdeconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_image_stats(ctx, N, image, mask, border, stats)
+foreign import ccall unsafe "gridhip_image_stats"
+  c_image_stats :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Word8 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_image_stats_dev(ctx, N, image, mask, border, stats)
+foreign import ccall unsafe "gridhip_image_stats_dev"
+  c_image_stats_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Word8 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_image_stats_dev(imager, image, mask, border, stats)
+foreign import ccall unsafe "gridhip_imager_image_stats_dev"
+  c_imager_image_stats_dev :: Ptr Imager -> Ptr CDouble -> Ptr Word8 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_clean_auto(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_clean_auto"
+  c_clean_auto :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_clean_auto_dev(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_clean_auto_dev"
+  c_clean_auto_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_msclean_auto(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_msclean_auto"
+  c_msclean_auto :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_msclean_auto_dev(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_msclean_auto_dev"
+  c_msclean_auto_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_clean_auto_dev(imager, residual, model, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_imager_clean_auto_dev"
+  c_imager_clean_auto_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_msclean_auto_dev(imager, residual, model, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_imager_msclean_auto_dev"
+  c_imager_msclean_auto_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_deconvolve_auto_dev(imager, vis, model, image, nmajor, gain, threshold, niter, border, patch, mask, nsigma, peak_frac, stats, istats)
+foreign import ccall unsafe "gridhip_imager_deconvolve_auto_dev"
+  c_imager_deconvolve_auto_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_msdeconvolve_auto_dev(imager, vis, model, image, nmajor, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, peak_frac, stats, istats)
+foreign import ccall unsafe "gridhip_imager_msdeconvolve_auto_dev"
+  c_imager_msdeconvolve_auto_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_fit_beam(ctx, N, psf, window, cut, beam)
 foreign import ccall unsafe "gridhip_fit_beam"
   c_fit_beam :: Ptr Ctx -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
@@ -814,6 +849,75 @@ imagerDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) nma
               statsRows rows ps
   let sh = A.Z A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Clean masks and noise-based stop levels (include/gridhip.h, "image statistics", "masks and noise-based stop levels").
+-- A mask is one byte per cell, row-major, non-zero where a component may be centred.
+
+-- | the clean mask (Nothing: none), nsigma and peak_frac of the stop level T = max(threshold, nsigma * sigma,
+-- peak_frac * |first peak|)
+data AutoOptions = AutoOptions { autoMask :: Maybe [Word8], autoNsigma :: F, autoPeakFrac :: F }
+
+withMask :: Maybe [Word8] -> (Ptr Word8 -> IO a) -> IO a
+withMask Nothing k = k nullPtr
+withMask (Just m) k = withArray m k
+
+-- | imageStatsIO h image mask border: [n, median, MAD, sigma = 1.4826 MAD, min, max, non-finite cells skipped, 0] of
+-- the cells inside the border and the mask (gridhip_image_stats, the host form, synchronous)
+imageStatsIO :: GridHip -> A.Matrix F -> Maybe [Word8] -> Int -> IO [F]
+imageStatsIO h@(GridHip c) image mask border = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape image
+  withF image $ \pi' -> withMask mask $ \pk -> allocaArray 8 $ \ps -> do
+    c_image_stats c (fi n') pi' pk (fi border) ps >>= check h
+    map realToFrac <$> peekArray 8 ps
+
+-- | cleanAutoIO h opts auto sigma image psf model: cleanIO under a mask, stopping at T; sigma is the noise the nsigma
+-- term multiplies (element 3 of imageStatsIO).  The stats are gridhip_clean's four, then [T, reason, first peak, 0].
+cleanAutoIO :: GridHip -> CleanOptions -> AutoOptions -> F -> A.Matrix F -> A.Matrix F -> A.Matrix F
+            -> IO (A.Matrix F, A.Matrix F, [F])
+cleanAutoIO h@(GridHip c) (CleanOptions g t ni b pa) (AutoOptions mask ns pf) sigma image psf model = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape image
+      copyOf m = do o <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+                    withF m $ \s -> withForeignPtr o $ \d -> copyArray d s (n' * n')
+                    return o
+  res <- copyOf image
+  mdl <- copyOf model
+  st <- withF psf $ \pp -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pm -> withMask mask $ \pk ->
+          with (realToFrac sigma :: CDouble) $ \pn -> allocaArray 8 $ \ps -> do
+            c_clean_auto c (fi n') pp pr pm (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) pk (realToFrac ns) pn
+              (realToFrac pf) ps >>= check h
+            map realToFrac <$> peekArray 8 ps
+  let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
+
+-- | imagerDeconvolveAutoIO im opts auto nmajor vis model: imagerDeconvolveIO whose minor cycles stop at nsigma times
+-- the sigma of the map they clean (gridhip_imager_deconvolve_auto_dev): (the model, the closing residual image, one
+-- row of 8 clean stats and one row of 8 image stats per major cycle)
+imagerDeconvolveAutoIO :: ImagerH -> CleanOptions -> AutoOptions -> Int -> A.Vector Visibility -> A.Matrix F
+                       -> IO (A.Matrix F, A.Matrix F, [[F]], [[F]])
+imagerDeconvolveAutoIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) (AutoOptions mask ns pf) nmajor vis model = do
+  img <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+      rows = max 0 nmajor
+      rows8 q = mapM (\r -> map realToFrac <$> peekArray 8 (q `advancePtr` (8 * r))) [0 .. rows - 1]
+      withDevMask Nothing k = k nullPtr
+      withDevMask (Just m) k = withArray m $ \pk -> withDev h pk (n' * n') k
+  withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withF model $ \pm -> withDev h pm bytes $ \dm ->
+    withForeignPtr img $ \pi' -> withDev h pi' bytes $ \di -> allocaArray (8 * rows) $ \ps ->
+      withDev h ps (64 * rows) $ \ds -> allocaArray (8 * rows) $ \pis -> withDev h pis (64 * rows) $ \dis ->
+        withDevMask mask $ \dk -> withForeignPtr mdl $ \pq -> do
+          c_imager_deconvolve_auto_dev p dv dm di (fi nmajor) (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) dk
+            (realToFrac ns) (realToFrac pf) ds dis >>= check h
+          c_memcpy_d2h c (castPtr pi') (castPtr di) (fi bytes) >>= check h
+          c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+          c_memcpy_d2h c (castPtr ps) (castPtr ds) (fi (64 * rows)) >>= check h
+          c_memcpy_d2h c (castPtr pis) (castPtr dis) (fi (64 * rows)) >>= check h
+          c_synchronize c >>= check h
+          st <- rows8 ps
+          ist <- rows8 pis
+          let sh = A.Z A.:. n' A.:. n'
+          return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st, ist)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- Multi-scale deconvolution (include/gridhip.h, "multi-scale deconvolution"): scales in cells increasing from 0, one

@@ -28,6 +28,7 @@ TYPES = [
     (r"^double \*const \*$", "Ptr (Ptr CDouble)"),
     (r"^(const )?double \*$", "Ptr CDouble"),
     (r"^(const )?int64_t \*$", "Ptr Int64"),
+    (r"^(const )?uint8_t \*$", "Ptr Word8"),
     (r"^(const )?int \*$", "Ptr CInt"),
     (r"^const char \*$", "CString"),
     (r"^void \*\*$", "Ptr (Ptr ())"),

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 180 /* 0.1.8 */
+#define GRIDHIP_VERSION 190 /* 0.1.9 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -600,6 +600,110 @@ int gridhip_imager_msclean_dev(gridhip_imager *imager, double *residual, double 
 int gridhip_imager_msdeconvolve_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
                                     int64_t nmajor, int64_t S, const double *scales, const double *bias, double gain,
                                     double threshold, int64_t niter, int64_t border, int64_t patch, double *stats);
+
+/* ---- image statistics: a robust noise estimate of a map, on the device -----------------------------------------------
+ * The reference has none of this: the semantics are defined here.  image is a real N x N image, row-major; mask is
+ * N x N bytes, or NULL for none; border follows clean's rule.  A cell k = y * N + x TAKES PART when
+ *     border <= y, x < N - border,   mask == NULL or mask[k] != 0,   and image[k] is finite (NaN and +-Inf never).
+ * Let n be the number of such cells.  They are ORDERED by the usual order-preserving 64-bit key of a double: all bits
+ * of a negative value flipped, the sign bit of a non-negative value flipped, the keys compared as unsigned integers.
+ * This puts -0.0 before +0.0 and needs no comparison of doubles.
+ *     median = the element of rank (n - 1) / 2 (integer division: the LOWER median; an element of the image, never an
+ *              average)
+ *     d_k    = |image[k] - median|, the difference rounded once, over the same cells
+ *     MAD    = the lower median of the d_k
+ *     sigma  = 1.4826 * MAD, rounded once
+ *     stats  = 8 doubles { n, median, MAD, sigma, min, max, the number of non-finite cells inside border and mask, 0 }
+ *              (min and max under the key order; n = 0: median, MAD, sigma, min and max are NaN)
+ * Every value is an order statistic or a count: the result is the same bits for the host, _dev and imager forms, for
+ * two runs, and for a sort of the keys on the host.
+ * Arguments, checked before anything is touched: GRIDHIP_EINVAL for N < 1, border < 0 or 2 * border >= N, NULL image
+ * or stats, mask overlapping image, stats overlapping image or mask; N above 1048560 is GRIDHIP_EUNSUPPORTED.
+ * The implementation is a radix select on the key, never a sort: one pass over the image builds the histogram of one
+ * 13-bit digit over the cells whose higher digits equal the prefix chosen so far (each work-group into LDS with 32-bit
+ * integer atomics, then its non-zero bins into a 64-bit table with integer atomics), a one-work-group kernel takes
+ * the digit that holds the wanted rank; 5 passes give the median, 5 more over d_k the MAD.  The first pass also
+ * takes n, min, max and the skipped count.  There is no floating-point atomic and no sum of doubles.  21 launches
+ * whatever the image holds.  (Context option "noise_bits" = 8 selects 8-bit digits, 8 + 8 passes, for comparison.)
+ * gridhip_image_stats is synchronous and stages host arrays through the context's pool.  The _dev and imager forms
+ * enqueue kernels only on the context's stream (the tables are zeroed by a kernel: no memset or copy node), allocate
+ * nothing after the first call, read nothing back and never synchronise: they can be captured.  Scratch (about 80 KB)
+ * comes from the context's pool, or for the imager form from memory the imager owns; stats is on the device. */
+int gridhip_image_stats(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border,
+                        double *stats);
+int gridhip_image_stats_dev(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border,
+                            double *stats);
+/* gridhip_image_stats_dev with the imager's N and its own scratch */
+int gridhip_imager_image_stats_dev(gridhip_imager *imager, const double *image, const uint8_t *mask, int64_t border,
+                                   double *stats);
+
+/* ---- masks and noise-based stop levels: the _auto forms of clean and msclean --------------------------------------------
+ * Everything is gridhip_clean's / gridhip_msclean's, with two additions.
+ * MASK: N x N bytes, or NULL for none.  A cell with mask[k] == 0 is never selected: it is skipped in the search exactly
+ * as a NaN cell is - for msclean in the search of every scale, so the mask constrains component CENTRES.  Nothing else
+ * changes: the PSF is subtracted over the whole update region, masked or not, a multi-scale blob may extend over
+ * masked-out cells, and the final peak and index of stats are the peak UNDER THE MASK.  The mask must not overlap
+ * residual or model (GRIDHIP_EINVAL).
+ * STOP LEVEL: noise points to ONE double, sigma - on the device for the _dev and imager forms, on the host for the host
+ * forms - so that element 3 of a gridhip_image_stats result can be passed as it is.  p1 is the first peak the call
+ * finds, before anything is subtracted (for msclean p_0, the plain residual's peak).
+ *     T = max(threshold, nsigma * sigma, peak_frac * |p1|)     each product rounded once
+ * computed once per call, on the device, and the loop's test is |p| <= T where it was |p| <= threshold.  nsigma == 0
+ * leaves its term out, and noise may then be NULL; peak_frac == 0 leaves its term out; so does a p1 that does not exist
+ * (nothing selectable).  If nsigma > 0 and sigma is NaN the call stops at once and touches nothing but stats (reason 3):
+ * it does not fall back to a threshold the caller did not ask for.  GRIDHIP_EINVAL before anything is touched: nsigma
+ * not finite or < 0, peak_frac outside [0, 1) or NaN, nsigma > 0 with NULL noise.
+ * STATS: clean writes 8 doubles, the 4 of gridhip_clean then { T, reason, p1, 0 }; msclean 16, the 12 of gridhip_msclean
+ * then the same four.  reason, the first of these that holds when the loop stops:
+ *     3  no usable sigma            2  nothing selectable (for msclean also: no scale can be chosen)
+ *     1  |peak| <= T                0  niter components taken
+ * (Rounding, for a restatement that wants the bits: gridhip_clean's model cell and its flux receive gain * p in one fused
+ * multiply-add each; f itself, which scales the PSF, is the rounded product.  gridhip_msclean fuses the delta's cell only.)
+ * IDENTITY: with mask == NULL, nsigma == 0 and peak_frac == 0, residual, model and the first 4 (12) stats have the bits
+ * of gridhip_clean (gridhip_msclean).  Launch counts, scratch and capturability are those of the plain forms; a lane of
+ * the tile kernel reads the two mask bytes of its two-cell slot, and the kernels without a mask are the code they were. */
+int gridhip_clean_auto(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                       double threshold, int64_t niter, int64_t border, int64_t patch, const uint8_t *mask, double nsigma,
+                       const double *noise, double peak_frac, double *stats);
+int gridhip_clean_auto_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                           double threshold, int64_t niter, int64_t border, int64_t patch, const uint8_t *mask,
+                           double nsigma, const double *noise, double peak_frac, double *stats);
+int gridhip_msclean_auto(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                         const double *scales, const double *bias, double gain, double threshold, int64_t niter,
+                         int64_t border, int64_t patch, const uint8_t *mask, double nsigma, const double *noise,
+                         double peak_frac, double *stats);
+int gridhip_msclean_auto_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                             const double *scales, const double *bias, double gain, double threshold, int64_t niter,
+                             int64_t border, int64_t patch, const uint8_t *mask, double nsigma, const double *noise,
+                             double peak_frac, double *stats);
+/* the _auto_dev forms with the imager's own PSF and N */
+int gridhip_imager_clean_auto_dev(gridhip_imager *imager, double *residual, double *model, double gain, double threshold,
+                                  int64_t niter, int64_t border, int64_t patch, const uint8_t *mask, double nsigma,
+                                  const double *noise, double peak_frac, double *stats);
+int gridhip_imager_msclean_auto_dev(gridhip_imager *imager, double *residual, double *model, int64_t S,
+                                    const double *scales, const double *bias, double gain, double threshold,
+                                    int64_t niter, int64_t border, int64_t patch, const uint8_t *mask, double nsigma,
+                                    const double *noise, double peak_frac, double *stats);
+/* visibilities -> model image with minor cycles that know the noise, DEFINED BY THE CALLS IT REPLACES:
+ *     repeat nmajor times (i = 0 ..):
+ *         image = cycle(model, vis)
+ *         image_stats(image, NULL, border) -> istats + 8 i     (the whole search region; the clean mask is NOT applied:
+ *                                                               sigma of the map)
+ *         clean_auto | msclean_auto(image, model, ..., mask, nsigma, noise = &istats[8 i + 3], peak_frac)
+ *                                                            -> stats + 8 i | stats + 16 i   (when stats != NULL)
+ *     image = cycle(model, vis)
+ * istats is nmajor x 8 doubles on the device; when it is NULL the imager keeps the 8 doubles itself.  Asynchronous,
+ * allocation-free after the first call and capturable.  All nmajor cycles are enqueued and run: a major cycle whose
+ * clean stops at once still images and measures; nothing on the device skips a cycle. */
+int gridhip_imager_deconvolve_auto_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
+                                       int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
+                                       int64_t patch, const uint8_t *mask, double nsigma, double peak_frac,
+                                       double *stats, double *istats);
+int gridhip_imager_msdeconvolve_auto_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
+                                         int64_t nmajor, int64_t S, const double *scales, const double *bias, double gain,
+                                         double threshold, int64_t niter, int64_t border, int64_t patch,
+                                         const uint8_t *mask, double nsigma, double peak_frac, double *stats,
+                                         double *istats);
 
 /* ---- restoring beam and restore: from clean's model and residual to a map, on the device -----------------------------
  * The reference stops at the dirty image: the semantics are defined here.  All images are real N x N, row-major [y][x];

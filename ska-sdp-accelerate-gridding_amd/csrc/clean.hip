@@ -32,7 +32,8 @@ struct CleanState {  // 64 bytes at the head of the scratch block
     double flux;          // sum of the f added to the model
     double f;             // gain * peak of the component the next tile kernel subtracts
     long long stopped;    // threshold reached, out of iterations or nothing to select: every later launch returns
-    long long pad[2];
+    double T;             // the stop level (the _auto forms: the first pick computes it; else the threshold)
+    long long reason;     // why the loop stopped (the _auto forms' codes)
 };
 
 // One tile per work-group.  SUB = false: grid (ntx, nty), the tile's entry from the residual as it is.  SUB = true: the
@@ -42,10 +43,12 @@ struct CleanState {  // 64 bytes at the head of the scratch block
 // A lane takes the two cells of one 16-byte aligned slot of the row; a row whose first or last cell shares its slot with
 // the neighbouring tile (odd N, or a base address that is 8 bytes off) takes that cell alone.  The PSF is read at a
 // shifted offset: 16 bytes at once where that address happens to be aligned (the same for a whole wave), two loads if not.
-template <bool SUB>
+// MASK: a cell whose mask byte is 0 is not searched (a lane reads the two bytes of its slot, in searched rows only);
+// the subtraction does not look at the mask.  Without MASK the kernel is the code it was before there were masks.
+template <bool SUB, bool MASK>
 __global__ void __launch_bounds__(256)
     clean_tile_kernel(int64_t N, int64_t border, int64_t patch, int ntx, const double *__restrict__ psf, double *res,
-                      CleanEntry *__restrict__ table, const CleanState *st)
+                      CleanEntry *__restrict__ table, const CleanState *st, const uint8_t *__restrict__ mask)
 {
 #pragma clang fp contract(off)
     __shared__ CleanEntry sh[4];
@@ -114,8 +117,8 @@ __global__ void __launch_bounds__(256)
                 }
             }
             if (ysearch) {
-                if (v0 && x >= border && x < N - border) consider(r0, a, bv, bk);
-                if (v1 && x + 1 >= border && x + 1 < N - border) consider(r1, a + 1, bv, bk);
+                if (v0 && x >= border && x < N - border && (!MASK || mask[a] != 0)) consider(r0, a, bv, bk);
+                if (v1 && x + 1 >= border && x + 1 < N - border && (!MASK || mask[a + 1] != 0)) consider(r1, a + 1, bv, bk);
             }
         }
     }
@@ -127,10 +130,13 @@ __global__ void __launch_bounds__(256)
 // nothing can be selected, when niter components are taken or when |peak| <= threshold - before anything is
 // subtracted - else take the component: f = gain * peak into the model, the flux and the state, where the next tile
 // kernel finds it.  INIT: the first pick of a call, which starts the state from zero whatever the block held.
-template <bool INIT>
+// AUTO (the _auto forms): the first pick computes the stop level T from the first peak and the noise and keeps it in the
+// state, every pick tests |peak| <= T and records why it stopped - 3: no usable sigma, 2: nothing selectable,
+// 1: |peak| <= T, 0: niter components taken, the first that holds - and stats has 8 doubles.
+template <bool INIT, bool AUTO>
 __global__ void __launch_bounds__(1024)
     clean_pick_kernel(int ntiles, const CleanEntry *__restrict__ table, CleanState *st, double *model, double gain,
-                      double threshold, int64_t niter, double *stats)
+                      double threshold, int64_t niter, double *stats, double nsigma, const double *noise, double peak_frac)
 {
     __shared__ CleanEntry sh[16];
     if (!INIT && st->stopped) return;
@@ -142,11 +148,15 @@ __global__ void __launch_bounds__(1024)
     long long iters = INIT ? 0 : st->iters;
     double flux = INIT ? 0.0 : st->flux;
     const double peak = bk < 0 ? __builtin_nan("") : bv;
-    const bool stop = bk < 0 || iters >= niter || !(fabs(bv) > threshold);
+    bool bad = false;
+    if (AUTO) threshold = INIT ? stop_level(threshold, nsigma, noise, peak_frac, peak, &bad) : st->T;
+    const bool stop = bad || bk < 0 || iters >= niter || !(fabs(bv) > threshold);
     if (!stop) {
+        // the model cell and the flux receive gain * peak in one fused step each (what contraction made of the two
+        // sums from the start, and what the header promises); f, which scales the PSF, is the rounded product
         const double f = gain * bv;
-        model[bk] += f;
-        flux += f;
+        model[bk] = fma(gain, bv, model[bk]);
+        flux = fma(gain, bv, flux);
         iters += 1;
         st->f = f;
     }
@@ -161,12 +171,46 @@ __global__ void __launch_bounds__(1024)
         stats[2] = (double)bk;
         stats[3] = flux;
     }
+    if (AUTO) {
+        const long long reason = !stop ? 0 : bad ? 3 : bk < 0 ? 2 : !(fabs(bv) > threshold) ? 1 : 0;
+        st->T = threshold;
+        st->reason = reason;
+        if (stats) {
+            if (INIT) stats[4] = threshold, stats[6] = peak, stats[7] = 0.0;
+            stats[5] = (double)reason;
+        }
+    }
 }
 
 bool overlap(const double *a, const double *b, size_t bytes)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + bytes && y < x + bytes;
+}
+
+template <bool MASK, bool AUTO>
+void clean_launch(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                  double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch,
+                  const CleanAuto &au)
+{
+    const int64_t ntx = (N + CLEAN_TW - 1) / CLEAN_TW, nty = (N + CLEAN_TH - 1) / CLEAN_TH;
+    CleanState *st = reinterpret_cast<CleanState *>(scratch);
+    CleanEntry *table = reinterpret_cast<CleanEntry *>(st + 1);
+    const int ntiles = (int)(ntx * nty);
+    const int64_t span = patch > 0 && 2 * patch + 1 < N ? 2 * patch + 1 : N;
+    const dim3 all((unsigned)ntx, (unsigned)nty);
+    const dim3 part((unsigned)tiles_spanned(span, CLEAN_TW, ntx), (unsigned)tiles_spanned(span, CLEAN_TH, nty));
+    hipLaunchKernelGGL((clean_tile_kernel<false, MASK>), all, dim3(256), 0, ctx->stream, N, border, patch, (int)ntx, psf,
+                       residual, table, (const CleanState *)st, au.mask);
+    hipLaunchKernelGGL((clean_pick_kernel<true, AUTO>), dim3(1), dim3(1024), 0, ctx->stream, ntiles,
+                       (const CleanEntry *)table, st, model, gain, threshold, niter, stats, au.nsigma, au.noise, au.peak_frac);
+    for (int64_t i = 0; i < niter; ++i) {
+        hipLaunchKernelGGL((clean_tile_kernel<true, MASK>), part, dim3(256), 0, ctx->stream, N, border, patch, (int)ntx, psf,
+                           residual, table, (const CleanState *)st, au.mask);
+        hipLaunchKernelGGL((clean_pick_kernel<false, AUTO>), dim3(1), dim3(1024), 0, ctx->stream, ntiles,
+                           (const CleanEntry *)table, st, model, gain, threshold, niter, stats, au.nsigma, au.noise,
+                           au.peak_frac);
+    }
 }
 
 }  // namespace
@@ -190,26 +234,30 @@ size_t clean_scratch_bytes(int64_t N)
     return sizeof(CleanState) + (size_t)ntx * nty * sizeof(CleanEntry);
 }
 
-int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
-              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch)
+int clean_auto_check(gridhip_ctx *ctx, int64_t N, const double *residual, const double *model, const uint8_t *mask,
+                     double nsigma, const double *noise, double peak_frac)
 {
-    const int64_t ntx = (N + CLEAN_TW - 1) / CLEAN_TW, nty = (N + CLEAN_TH - 1) / CLEAN_TH;
-    CleanState *st = reinterpret_cast<CleanState *>(scratch);
-    CleanEntry *table = reinterpret_cast<CleanEntry *>(st + 1);
-    const int ntiles = (int)(ntx * nty);
-    const int64_t span = patch > 0 && 2 * patch + 1 < N ? 2 * patch + 1 : N;
-    const dim3 all((unsigned)ntx, (unsigned)nty);
-    const dim3 part((unsigned)tiles_spanned(span, CLEAN_TW, ntx), (unsigned)tiles_spanned(span, CLEAN_TH, nty));
-    hipLaunchKernelGGL(clean_tile_kernel<false>, all, dim3(256), 0, ctx->stream, N, border, patch, (int)ntx, psf, residual,
-                       table, (const CleanState *)st);
-    hipLaunchKernelGGL(clean_pick_kernel<true>, dim3(1), dim3(1024), 0, ctx->stream, ntiles, (const CleanEntry *)table, st,
-                       model, gain, threshold, niter, stats);
-    for (int64_t i = 0; i < niter; ++i) {
-        hipLaunchKernelGGL(clean_tile_kernel<true>, part, dim3(256), 0, ctx->stream, N, border, patch, (int)ntx, psf,
-                           residual, table, (const CleanState *)st);
-        hipLaunchKernelGGL(clean_pick_kernel<false>, dim3(1), dim3(1024), 0, ctx->stream, ntiles,
-                           (const CleanEntry *)table, st, model, gain, threshold, niter, stats);
+    if (!(nsigma >= 0.0 && nsigma < __builtin_inf()) || !(peak_frac >= 0.0 && peak_frac < 1.0) || (nsigma > 0.0 && !noise))
+        return fail(ctx, GRIDHIP_EINVAL, "clean_auto: bad nsigma, noise or peak_frac");
+    if (mask) {
+        const uintptr_t m = (uintptr_t)mask, cells = (uintptr_t)N * N;
+        for (const double *a : {residual, model})
+            if (m < (uintptr_t)a + cells * 8 && (uintptr_t)a < m + cells)
+                return fail(ctx, GRIDHIP_EINVAL, "clean_auto: the mask must not overlap residual or model");
     }
+    return GRIDHIP_OK;
+}
+
+int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch,
+              const CleanAuto &au)
+{
+    if (!au.on)
+        clean_launch<false, false>(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats, scratch, au);
+    else if (au.mask)
+        clean_launch<true, true>(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats, scratch, au);
+    else
+        clean_launch<false, true>(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats, scratch, au);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }
@@ -221,26 +269,35 @@ using namespace gridhip;
 namespace {
 
 int clean_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *psf, double *residual, double *model, double gain,
-              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats)
+              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, CleanAuto au = CleanAuto{})
 {
     if (!ctx) return GRIDHIP_EINVAL;
     GH_CHECK(clean_check(ctx, N, psf, residual, model, gain, threshold, niter, border, patch));
+    if (au.on) GH_CHECK(clean_auto_check(ctx, N, residual, model, au.mask, au.nsigma, au.noise, au.peak_frac));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, clean_scratch_bytes(N)));
     if (dev)
-        return clean_run(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats, scratch.p);
-    const size_t bytes = (size_t)N * N * 8;
-    DevBuf p, r, m, s;
+        return clean_run(ctx, N, psf, residual, model, gain, threshold, niter, border, patch, stats, scratch.p, au);
+    const size_t bytes = (size_t)N * N * 8, sbytes = au.on ? 64 : 32;
+    DevBuf p, r, m, s, mk, nz;
     GH_CHECK(p.upload(ctx, psf, bytes));
     GH_CHECK(r.upload(ctx, residual, bytes));
     GH_CHECK(m.upload(ctx, model, bytes));
-    GH_CHECK(s.alloc(ctx, 32));
+    GH_CHECK(s.alloc(ctx, sbytes));
+    if (au.mask) {
+        GH_CHECK(mk.upload(ctx, au.mask, bytes / 8));
+        au.mask = mk.as<uint8_t>();
+    }
+    if (au.nsigma > 0.0) {
+        GH_CHECK(nz.upload(ctx, au.noise, 8));
+        au.noise = nz.as<double>();
+    }
     GH_CHECK(clean_run(ctx, N, p.as<double>(), r.as<double>(), m.as<double>(), gain, threshold, niter, border, patch,
-                       s.as<double>(), scratch.p));
+                       s.as<double>(), scratch.p, au));
     GH_CHECK(d2h(ctx, residual, r.p, bytes));
     GH_CHECK(d2h(ctx, model, m.p, bytes));
-    if (stats) GH_CHECK(d2h(ctx, stats, s.p, 32));
+    if (stats) GH_CHECK(d2h(ctx, stats, s.p, sbytes));
     return sync(ctx);
 }
 
@@ -258,6 +315,22 @@ int gridhip_clean_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *re
                       double threshold, int64_t niter, int64_t border, int64_t patch, double *stats)
 {
     return clean_any(ctx, true, N, psf, residual, model, gain, threshold, niter, border, patch, stats);
+}
+
+int gridhip_clean_auto(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                       double threshold, int64_t niter, int64_t border, int64_t patch, const uint8_t *mask, double nsigma,
+                       const double *noise, double peak_frac, double *stats)
+{
+    return clean_any(ctx, false, N, psf, residual, model, gain, threshold, niter, border, patch, stats,
+                     CleanAuto{mask, nsigma, noise, peak_frac, true});
+}
+
+int gridhip_clean_auto_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
+                           double threshold, int64_t niter, int64_t border, int64_t patch, const uint8_t *mask,
+                           double nsigma, const double *noise, double peak_frac, double *stats)
+{
+    return clean_any(ctx, true, N, psf, residual, model, gain, threshold, niter, border, patch, stats,
+                     CleanAuto{mask, nsigma, noise, peak_frac, true});
 }
 
 }  // extern "C"

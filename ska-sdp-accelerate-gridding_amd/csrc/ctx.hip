@@ -478,6 +478,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "subfoot")) return &ctx->opt.subfoot;
     if (!strcmp(key, "bigtile")) return &ctx->opt.bigtile;
     if (!strcmp(key, "yield_cus")) return &ctx->opt.yield_cus;
+    if (!strcmp(key, "noise_bits")) return &ctx->img->noise_bits;  // image_stats' digit: 8, or anything else for 13
     return nullptr;
 }
 

@@ -140,6 +140,8 @@ struct gridhip_imager {
     std::vector<double> ms_scales;
     double *beam = nullptr;         // the fitted beam of a restore that does not return it (8 doubles), made by the first
     double *wstats = nullptr;       // the weighting's stats (8 doubles), written at creation
+    void *noise_scratch = nullptr;  // image_stats' state block and tables (noise.hip), made by the first image_stats
+    double *istats = nullptr;       // the image stats of a deconvolve_auto that does not return them (8 doubles)
 };
 
 namespace {
@@ -471,16 +473,81 @@ int gridhip_imager_predict_dev(gridhip_imager *im, const double *model, const do
     return launch_residual(ctx, im->n, im->pred, (const double2 *)vis_sub, (double2 *)vis_out);
 }
 
-int gridhip_imager_clean_dev(gridhip_imager *im, double *residual, double *model, double gain, double threshold,
-                             int64_t niter, int64_t border, int64_t patch, double *stats)
+static int imager_clean(gridhip_imager *im, double *residual, double *model, double gain, double threshold,
+                        int64_t niter, int64_t border, int64_t patch, double *stats, const CleanAuto &au)
 {
     if (!im) return GRIDHIP_EINVAL;
     gridhip_ctx *ctx = im->ctx;
     GH_CHECK(clean_check(ctx, im->N, im->psf, residual, model, gain, threshold, niter, border, patch));
+    if (au.on) GH_CHECK(clean_auto_check(ctx, im->N, residual, model, au.mask, au.nsigma, au.noise, au.peak_frac));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (!im->clean_scratch) GH_CHECK(own(im, &im->clean_scratch, clean_scratch_bytes(im->N)));
     return clean_run(ctx, im->N, im->psf, residual, model, gain, threshold, niter, border, patch, stats,
-                     im->clean_scratch);
+                     im->clean_scratch, au);
+}
+
+int gridhip_imager_clean_dev(gridhip_imager *im, double *residual, double *model, double gain, double threshold,
+                             int64_t niter, int64_t border, int64_t patch, double *stats)
+{
+    return imager_clean(im, residual, model, gain, threshold, niter, border, patch, stats, CleanAuto{});
+}
+
+int gridhip_imager_clean_auto_dev(gridhip_imager *im, double *residual, double *model, double gain, double threshold,
+                                  int64_t niter, int64_t border, int64_t patch, const uint8_t *mask, double nsigma,
+                                  const double *noise, double peak_frac, double *stats)
+{
+    return imager_clean(im, residual, model, gain, threshold, niter, border, patch, stats,
+                        CleanAuto{mask, nsigma, noise, peak_frac, true});
+}
+
+int gridhip_imager_image_stats_dev(gridhip_imager *im, const double *image, const uint8_t *mask, int64_t border,
+                                   double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(image_stats_check(ctx, im->N, image, mask, border, stats));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!im->noise_scratch) GH_CHECK(own(im, &im->noise_scratch, image_stats_scratch_bytes(ctx)));
+    return image_stats_run(ctx, im->N, image, mask, border, stats, im->noise_scratch);
+}
+
+// the checks and the loop the two _auto deconvolves share; minor(c, noise): the c-th minor cycle with sigma at `noise`
+extern "C++" template <typename Minor>
+static int deconvolve_auto(gridhip_imager *im, const double *vis, double *model, double *image, int64_t nmajor,
+                           int64_t border, const uint8_t *mask, double nsigma, double peak_frac, double *istats,
+                           Minor minor)
+{
+    gridhip_ctx *ctx = im->ctx;
+    double placeholder = 0.0;  // (stands for sigma's cell in the checks: the loop passes its own)
+    GH_CHECK(clean_auto_check(ctx, im->N, image, model, mask, nsigma, &placeholder, peak_frac));
+    if (!istats) {
+        GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+        if (!im->istats) GH_CHECK(own(im, &im->istats, 64));
+    }
+    for (int64_t c = 0; c < nmajor; ++c) {
+        double *ist = istats ? istats + 8 * c : im->istats;
+        GH_CHECK(gridhip_imager_cycle_dev(im, model, vis, image, nullptr));
+        GH_CHECK(gridhip_imager_image_stats_dev(im, image, nullptr, border, ist));
+        GH_CHECK(minor(c, (const double *)(ist + 3)));
+    }
+    return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
+}
+
+int gridhip_imager_deconvolve_auto_dev(gridhip_imager *im, const double *vis, double *model, double *image,
+                                       int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
+                                       int64_t patch, const uint8_t *mask, double nsigma, double peak_frac,
+                                       double *stats, double *istats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "deconvolve: bad argument");
+    GH_CHECK(clean_check(ctx, im->N, im->psf, image, model, gain, threshold, niter, border, patch));
+    return deconvolve_auto(im, vis, model, image, nmajor, border, mask, nsigma, peak_frac, istats,
+                           [&](int64_t c, const double *noise) {
+                               return gridhip_imager_clean_auto_dev(im, image, model, gain, threshold, niter, border, patch,
+                                                                    mask, nsigma, noise, peak_frac,
+                                                                    stats ? stats + 8 * c : nullptr);
+                           });
 }
 
 int gridhip_imager_deconvolve_dev(gridhip_imager *im, const double *vis, double *model, double *image, int64_t nmajor,
@@ -499,13 +566,14 @@ int gridhip_imager_deconvolve_dev(gridhip_imager *im, const double *vis, double 
     return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
 }
 
-int gridhip_imager_msclean_dev(gridhip_imager *im, double *residual, double *model, int64_t S, const double *scales,
-                               const double *bias, double gain, double threshold, int64_t niter, int64_t border,
-                               int64_t patch, double *stats)
+static int imager_msclean(gridhip_imager *im, double *residual, double *model, int64_t S, const double *scales,
+                          const double *bias, double gain, double threshold, int64_t niter, int64_t border, int64_t patch,
+                          double *stats, const CleanAuto &au)
 {
     if (!im) return GRIDHIP_EINVAL;
     gridhip_ctx *ctx = im->ctx;
     GH_CHECK(msclean_check(ctx, im->N, im->psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch));
+    if (au.on) GH_CHECK(clean_auto_check(ctx, im->N, residual, model, au.mask, au.nsigma, au.noise, au.peak_frac));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t need = msclean_scratch_bytes(im->N, S);
     if (need > im->ms_bytes) {  // (the first call, or a longer scale list: hipFree waits for the work that uses the old block)
@@ -524,9 +592,43 @@ int gridhip_imager_msclean_dev(gridhip_imager *im, double *residual, double *mod
     const bool setup = key != im->ms_scales;
     im->ms_scales.clear();  // (a set-up that fails half way leaves no key behind)
     GH_CHECK(msclean_run(ctx, im->N, im->psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
-                         im->ms_scratch, setup));
+                         im->ms_scratch, setup, au));
     im->ms_scales = key;
     return GRIDHIP_OK;
+}
+
+int gridhip_imager_msclean_dev(gridhip_imager *im, double *residual, double *model, int64_t S, const double *scales,
+                               const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                               int64_t patch, double *stats)
+{
+    return imager_msclean(im, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats, CleanAuto{});
+}
+
+int gridhip_imager_msclean_auto_dev(gridhip_imager *im, double *residual, double *model, int64_t S, const double *scales,
+                                    const double *bias, double gain, double threshold, int64_t niter, int64_t border,
+                                    int64_t patch, const uint8_t *mask, double nsigma, const double *noise,
+                                    double peak_frac, double *stats)
+{
+    return imager_msclean(im, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
+                          CleanAuto{mask, nsigma, noise, peak_frac, true});
+}
+
+int gridhip_imager_msdeconvolve_auto_dev(gridhip_imager *im, const double *vis, double *model, double *image,
+                                         int64_t nmajor, int64_t S, const double *scales, const double *bias, double gain,
+                                         double threshold, int64_t niter, int64_t border, int64_t patch,
+                                         const uint8_t *mask, double nsigma, double peak_frac, double *stats,
+                                         double *istats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "msdeconvolve: bad argument");
+    GH_CHECK(msclean_check(ctx, im->N, im->psf, image, model, S, scales, bias, gain, threshold, niter, border, patch));
+    return deconvolve_auto(im, vis, model, image, nmajor, border, mask, nsigma, peak_frac, istats,
+                           [&](int64_t c, const double *noise) {
+                               return gridhip_imager_msclean_auto_dev(im, image, model, S, scales, bias, gain, threshold,
+                                                                      niter, border, patch, mask, nsigma, noise, peak_frac,
+                                                                      stats ? stats + 16 * c : nullptr);
+                           });
 }
 
 int gridhip_imager_msdeconvolve_dev(gridhip_imager *im, const double *vis, double *model, double *image, int64_t nmajor,

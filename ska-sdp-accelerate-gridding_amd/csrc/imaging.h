@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// restore.hip).
+// msclean.hip, noise.hip, restore.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -37,6 +37,7 @@ struct ImagingState {
     } wk_cache;
     bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
     bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
+    int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
 };
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled
@@ -261,9 +262,24 @@ int clean_check(gridhip_ctx *ctx, int64_t N, const double *psf, const double *re
                 double threshold, int64_t niter, int64_t border, int64_t patch);
 // the state block and the tile table of an N x N clean
 size_t clean_scratch_bytes(int64_t N);
-// gridhip_clean_dev on checked arguments: kernels only, on ctx->stream; scratch: clean_scratch_bytes(N) of device memory
+// What the _auto forms add to a clean (include/gridhip.h, "masks and noise-based stop levels"): the clean mask, or null;
+// T = max(threshold, nsigma * *noise, peak_frac * |first peak|), noise a device pointer; on: stats has the four further
+// doubles { T, reason, first peak, 0 }.  The neutral value - what the plain entry points pass - is CleanAuto{}.
+struct CleanAuto {
+    const uint8_t *mask = nullptr;
+    double nsigma = 0.0;
+    const double *noise = nullptr;
+    double peak_frac = 0.0;
+    bool on = false;
+};
+// the _auto forms' own argument rules (GRIDHIP_EINVAL), after clean_check's
+int clean_auto_check(gridhip_ctx *ctx, int64_t N, const double *residual, const double *model, const uint8_t *mask,
+                     double nsigma, const double *noise, double peak_frac);
+// gridhip_clean_dev / gridhip_clean_auto_dev on checked arguments: kernels only, on ctx->stream; scratch:
+// clean_scratch_bytes(N) of device memory
 int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
-              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
+              double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch,
+              const CleanAuto &au = CleanAuto{});
 
 // What clean.hip and msclean.hip share: the tile, a tile's table entry, the search rule and its reductions.
 constexpr int CLEAN_TH = 16, CLEAN_TW = 128;  // one wave takes one row of a tile, 16 bytes per lane
@@ -323,7 +339,41 @@ size_t msclean_scratch_bytes(int64_t N, int64_t S);
 // cross-PSFs of `psf` in scratch; a caller whose scratch holds them for this psf and these scales passes false.
 int msclean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
                 const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
-                int64_t patch, double *stats, void *scratch, bool setup);
+                int64_t patch, double *stats, void *scratch, bool setup, const CleanAuto &au = CleanAuto{});
+
+// The stop level of an _auto call, by the first pick kernel: T = max(threshold, nsigma * sigma, peak_frac * |p1|), each
+// product rounded once, a term whose factor is 0 left out (noise is then not read); p1 is NaN when nothing can be
+// selected and its term is then left out.  *bad: nsigma > 0 and sigma is NaN - T is NaN and the call stops at once.
+__device__ __forceinline__ double stop_level(double threshold, double nsigma, const double *noise, double peak_frac,
+                                             double p1, bool *bad)
+{
+    double T = threshold;
+    *bad = false;
+    if (nsigma > 0.0) {
+        const double sigma = *noise;
+        if (sigma != sigma) {
+            *bad = true;
+            return sigma;
+        }
+        const double a = nsigma * sigma;
+        T = a > T ? a : T;
+    }
+    if (peak_frac > 0.0 && p1 == p1) {
+        const double b = peak_frac * fabs(p1);
+        T = b > T ? b : T;
+    }
+    return T;
+}
+
+// ---- robust image statistics (noise.hip) -----------------------------------------------------------------------------------
+// gridhip_image_stats' argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED)
+int image_stats_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border,
+                      const double *stats);
+// the state block, the bin table and one row per work-group; the same for every N
+size_t image_stats_scratch_bytes(gridhip_ctx *ctx);
+// gridhip_image_stats_dev on checked arguments: kernels only, on ctx->stream
+int image_stats_run(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border, double *stats,
+                    void *scratch);
 
 // ---- the restoring beam and the restore (restore.hip) --------------------------------------------------------------------
 // gridhip_fit_beam's and gridhip_restore's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); the beam's values are

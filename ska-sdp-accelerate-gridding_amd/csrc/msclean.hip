@@ -42,6 +42,8 @@ struct MsState {  // the head of the scratch block
     long long n[MS_MAX_SCALES];     // components taken per scale
     const double *P[MS_PAIRS];      // P[pair_index(s, t)]; P[0] is the psf
     double *R[MS_MAX_SCALES];       // the smoothed residuals; R[0] is not used (the residual is a kernel argument)
+    double T;                       // the stop level (the _auto forms: the first pick computes it)
+    long long reason;               // why the loop stopped (the _auto forms' codes)
 };
 
 struct MsScales {  // by value to the kernels: read from the host arrays at call time
@@ -166,11 +168,12 @@ __global__ void __launch_bounds__(256)
 // S); slice t subtracts f * P_{s* t}, shifted to the component's centre, over Hogbom's update region - the cells whose
 // PSF index lies in the grid, cut to the patch - and recomputes the entries of the tiles it touched in the same pass.
 // The access shape is clean_tile_kernel's: a lane takes the two cells of one 16-byte aligned slot, the shifted cross-PSF
-// is read 16 bytes at once where that address is aligned.  s*, k and f come from the state block.
-template <bool SUB>
+// is read 16 bytes at once where that address is aligned.  s*, k and f come from the state block.  MASK: a cell whose mask
+// byte is 0 is not searched, in any slice - the mask constrains component centres; the subtraction does not look at it.
+template <bool SUB, bool MASK>
 __global__ void __launch_bounds__(256)
     ms_tile_kernel(int64_t N, int64_t border, int64_t patch, int ntx, int ntiles, double *residual,
-                   CleanEntry *__restrict__ tables, const MsState *st)
+                   CleanEntry *__restrict__ tables, const MsState *st, const uint8_t *__restrict__ mask)
 {
 #pragma clang fp contract(off)
     __shared__ CleanEntry sh[4];
@@ -244,8 +247,8 @@ __global__ void __launch_bounds__(256)
                 }
             }
             if (ysearch) {
-                if (v0 && x >= border && x < N - border) consider(r0, a, bv, bk);
-                if (v1 && x + 1 >= border && x + 1 < N - border) consider(r1, a + 1, bv, bk);
+                if (v0 && x >= border && x < N - border && (!MASK || mask[a] != 0)) consider(r0, a, bv, bk);
+                if (v1 && x + 1 >= border && x + 1 < N - border && (!MASK || mask[a + 1] != 0)) consider(r1, a + 1, bv, bk);
             }
         }
     }
@@ -259,12 +262,13 @@ __global__ void __launch_bounds__(256)
 // selectable cell or whose q_s is not positive and finite never; no scale left stops the loop too.  The component
 // f = gain * (p / q) at k goes into the state for the next tile kernel, and the whole work-group adds its blob
 // f * m_s* to the model (for the delta the one cell, as gridhip_clean adds it).  INIT: the first pick of a call, which starts the
-// counters from zero whatever the block held (the pointer table stays).
-template <bool INIT>
+// counters from zero whatever the block held (the pointer table stays).  AUTO: clean_pick_kernel's - the stop level T
+// from p_0 of the first pick, the reason codes (no scale left counts as nothing selectable), 16 stats.
+template <bool INIT, bool AUTO>
 __global__ void __launch_bounds__(1024)
     ms_pick_kernel(int64_t N, int ntiles, const CleanEntry *__restrict__ tables, MsState *st, MsScales sc,
                    const double *__restrict__ taps, double *model, double gain, double threshold, int64_t niter,
-                   double *stats)
+                   double *stats, double nsigma, const double *noise, double peak_frac)
 {
 #pragma clang fp contract(off)
     __shared__ CleanEntry sh[16];
@@ -289,7 +293,10 @@ __global__ void __launch_bounds__(1024)
         for (int s = 0; s < MS_MAX_SCALES; ++s) n[s] = INIT ? 0 : st->n[s];
         const long long k0 = best[0].k;
         const double peak = k0 < 0 ? __builtin_nan("") : best[0].v;
-        bool stop = k0 < 0 || iters >= niter || !(fabs(best[0].v) > threshold);
+        bool bad = false;
+        if (AUTO) threshold = INIT ? stop_level(threshold, nsigma, noise, peak_frac, peak, &bad) : st->T;
+        bool stop = bad || k0 < 0 || iters >= niter || !(fabs(best[0].v) > threshold);
+        long long reason = !stop ? 0 : bad ? 3 : k0 < 0 ? 2 : !(fabs(best[0].v) > threshold) ? 1 : 0;
         int pick = -1;
         if (!stop) {
             const int64_t c = N / 2;
@@ -304,6 +311,7 @@ __global__ void __launch_bounds__(1024)
             }
             if (pick < 0) {
                 stop = true;
+                reason = 2;
             } else {
                 const double r = best[pick].v / q_pick;
                 const double f = gain * r;
@@ -335,6 +343,14 @@ __global__ void __launch_bounds__(1024)
             stats[4] = flux;
             stats[5] = 0.0;
             for (int s = 0; s < MS_MAX_SCALES; ++s) stats[6 + s] = (double)n[s];
+        }
+        if (AUTO) {
+            st->T = threshold;
+            st->reason = reason;
+            if (stats) {
+                if (INIT) stats[12] = threshold, stats[14] = peak, stats[15] = 0.0;
+                stats[13] = (double)reason;
+            }
         }
     }
     __syncthreads();
@@ -379,6 +395,41 @@ MsLayout layout(int64_t N, int64_t S)
     return l;
 }
 
+struct MsLaunch {  // what the tile and pick launches of one call take
+    gridhip_ctx *ctx;
+    int64_t N, border, patch;
+    int ntx, ntiles;
+    double *residual;
+    CleanEntry *tables;
+    MsState *st;
+    MsScales sc;
+    const double *taps;
+    double *model;
+    double gain, threshold;
+    int64_t niter;
+    double *stats;
+    dim3 all, part;
+    CleanAuto au;
+};
+
+template <bool MASK, bool AUTO>
+void ms_launch(const MsLaunch &a)
+{
+    hipStream_t q = a.ctx->stream;
+    hipLaunchKernelGGL((ms_tile_kernel<false, MASK>), a.all, dim3(256), 0, q, a.N, a.border, a.patch, a.ntx, a.ntiles,
+                       a.residual, a.tables, (const MsState *)a.st, a.au.mask);
+    hipLaunchKernelGGL((ms_pick_kernel<true, AUTO>), dim3(1), dim3(1024), 0, q, a.N, a.ntiles, (const CleanEntry *)a.tables,
+                       a.st, a.sc, a.taps, a.model, a.gain, a.threshold, a.niter, a.stats, a.au.nsigma, a.au.noise,
+                       a.au.peak_frac);
+    for (int64_t i = 0; i < a.niter; ++i) {
+        hipLaunchKernelGGL((ms_tile_kernel<true, MASK>), a.part, dim3(256), 0, q, a.N, a.border, a.patch, a.ntx, a.ntiles,
+                           a.residual, a.tables, (const MsState *)a.st, a.au.mask);
+        hipLaunchKernelGGL((ms_pick_kernel<false, AUTO>), dim3(1), dim3(1024), 0, q, a.N, a.ntiles,
+                           (const CleanEntry *)a.tables, a.st, a.sc, a.taps, a.model, a.gain, a.threshold, a.niter, a.stats,
+                           a.au.nsigma, a.au.noise, a.au.peak_frac);
+    }
+}
+
 int conv(gridhip_ctx *ctx, int64_t N, const double *in, const double *taps, int s, double *out)
 {
     const dim3 grid((unsigned)((N + RS_TW - 1) / RS_TW), (unsigned)((N + RS_TH - 1) / RS_TH));
@@ -411,7 +462,7 @@ size_t msclean_scratch_bytes(int64_t N, int64_t S) { return layout(N, S).total; 
 
 int msclean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
                 const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
-                int64_t patch, double *stats, void *scratch, bool setup)
+                int64_t patch, double *stats, void *scratch, bool setup, const CleanAuto &au)
 {
     const MsLayout l = layout(N, S);
     char *base = reinterpret_cast<char *>(scratch);
@@ -456,16 +507,14 @@ int msclean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual
     const dim3 all((unsigned)l.ntx, (unsigned)l.nty, (unsigned)S);
     const dim3 part((unsigned)tiles_spanned(span, CLEAN_TW, l.ntx), (unsigned)tiles_spanned(span, CLEAN_TH, l.nty),
                     (unsigned)S);
-    hipLaunchKernelGGL(ms_tile_kernel<false>, all, dim3(256), 0, ctx->stream, N, border, patch, (int)l.ntx, ntiles, residual,
-                       tables, (const MsState *)st);
-    hipLaunchKernelGGL(ms_pick_kernel<true>, dim3(1), dim3(1024), 0, ctx->stream, N, ntiles, (const CleanEntry *)tables, st,
-                       sc, (const double *)taps, model, gain, threshold, niter, stats);
-    for (int64_t i = 0; i < niter; ++i) {
-        hipLaunchKernelGGL(ms_tile_kernel<true>, part, dim3(256), 0, ctx->stream, N, border, patch, (int)l.ntx, ntiles,
-                           residual, tables, (const MsState *)st);
-        hipLaunchKernelGGL(ms_pick_kernel<false>, dim3(1), dim3(1024), 0, ctx->stream, N, ntiles,
-                           (const CleanEntry *)tables, st, sc, (const double *)taps, model, gain, threshold, niter, stats);
-    }
+    const MsLaunch go = {ctx, N, border, patch, (int)l.ntx, ntiles, residual, tables, st, sc, taps, model, gain, threshold,
+                         niter, stats, all, part, au};
+    if (!au.on)
+        ms_launch<false, false>(go);
+    else if (au.mask)
+        ms_launch<true, true>(go);
+    else
+        ms_launch<false, true>(go);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }
@@ -478,27 +527,36 @@ namespace {
 
 int msclean_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *psf, double *residual, double *model, int64_t S,
                 const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
-                int64_t patch, double *stats)
+                int64_t patch, double *stats, CleanAuto au = CleanAuto{})
 {
     if (!ctx) return GRIDHIP_EINVAL;
     GH_CHECK(msclean_check(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch));
+    if (au.on) GH_CHECK(clean_auto_check(ctx, N, residual, model, au.mask, au.nsigma, au.noise, au.peak_frac));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, msclean_scratch_bytes(N, S)));
     if (dev)
         return msclean_run(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
-                           scratch.p, true);
-    const size_t bytes = (size_t)N * N * 8;
-    DevBuf p, r, m, s;
+                           scratch.p, true, au);
+    const size_t bytes = (size_t)N * N * 8, sbytes = au.on ? 128 : 96;
+    DevBuf p, r, m, s, mk, nz;
     GH_CHECK(p.upload(ctx, psf, bytes));
     GH_CHECK(r.upload(ctx, residual, bytes));
     GH_CHECK(m.upload(ctx, model, bytes));
-    GH_CHECK(s.alloc(ctx, 96));
+    GH_CHECK(s.alloc(ctx, sbytes));
+    if (au.mask) {
+        GH_CHECK(mk.upload(ctx, au.mask, bytes / 8));
+        au.mask = mk.as<uint8_t>();
+    }
+    if (au.nsigma > 0.0) {
+        GH_CHECK(nz.upload(ctx, au.noise, 8));
+        au.noise = nz.as<double>();
+    }
     GH_CHECK(msclean_run(ctx, N, p.as<double>(), r.as<double>(), m.as<double>(), S, scales, bias, gain, threshold, niter,
-                         border, patch, s.as<double>(), scratch.p, true));
+                         border, patch, s.as<double>(), scratch.p, true, au));
     GH_CHECK(d2h(ctx, residual, r.p, bytes));
     GH_CHECK(d2h(ctx, model, m.p, bytes));
-    if (stats) GH_CHECK(d2h(ctx, stats, s.p, 96));
+    if (stats) GH_CHECK(d2h(ctx, stats, s.p, sbytes));
     return sync(ctx);
 }
 
@@ -518,6 +576,24 @@ int gridhip_msclean_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *
                         int64_t border, int64_t patch, double *stats)
 {
     return msclean_any(ctx, true, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats);
+}
+
+int gridhip_msclean_auto(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                         const double *scales, const double *bias, double gain, double threshold, int64_t niter,
+                         int64_t border, int64_t patch, const uint8_t *mask, double nsigma, const double *noise,
+                         double peak_frac, double *stats)
+{
+    return msclean_any(ctx, false, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
+                       CleanAuto{mask, nsigma, noise, peak_frac, true});
+}
+
+int gridhip_msclean_auto_dev(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
+                             const double *scales, const double *bias, double gain, double threshold, int64_t niter,
+                             int64_t border, int64_t patch, const uint8_t *mask, double nsigma, const double *noise,
+                             double peak_frac, double *stats)
+{
+    return msclean_any(ctx, true, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
+                       CleanAuto{mask, nsigma, noise, peak_frac, true});
 }
 
 }  // extern "C"

@@ -314,6 +314,63 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         return out;
     }
 
+    // ---- image statistics, masks and noise-based stop levels (gridhip_image_stats, gridhip_clean_auto,
+    // gridhip_msclean_auto; include/gridhip.h, "image statistics", "masks and noise-based stop levels") ----
+    // The lower median, the MAD and sigma = 1.4826 MAD of the finite cells inside `border` and `mask` (one byte per
+    // cell, empty: every cell): exact order statistics.
+    struct ImageStats {
+        F n, median, mad, sigma, min, max, skipped;
+    };
+    ImageStats image_stats(const Matrix<F> &image, const std::vector<uint8_t> &mask = {}, Int border = 0)
+    {
+        if (image.h != image.w || (!mask.empty() && (Int)mask.size() != image.h * image.w))
+            throw Error(GRIDHIP_EINVAL, "image_stats: image must be N x N and the mask N x N bytes");
+        F st[8] = {0};
+        check(gridhip_image_stats(ctx_, image.h, image.data.data(), mask.empty() ? nullptr : mask.data(), border, st));
+        return {st[0], st[1], st[2], st[3], st[4], st[5], st[6]};
+    }
+    // clean / msclean under a mask (cells whose byte is 0 are never selected; empty: none), stopping at
+    // T = max(threshold, nsigma * sigma, peak_frac * |first peak|).  reason: 0 niter components taken, 1 |peak| <= T,
+    // 2 nothing selectable, 3 no usable sigma.
+    struct AutoStop {
+        F T, reason, first_peak;
+    };
+    CleanStats clean_auto(Matrix<F> &image, const Matrix<F> &psf, Matrix<F> &model, const std::vector<uint8_t> &mask,
+                          F nsigma, F sigma, F peak_frac, AutoStop *why = nullptr, F gain = 0.1, F threshold = 0.0,
+                          Int niter = 100, Int border = 0, Int patch = 0)
+    {
+        if (image.h != image.w || psf.h != image.h || psf.w != image.w || model.h != image.h || model.w != image.w ||
+            (!mask.empty() && (Int)mask.size() != image.h * image.w))
+            throw Error(GRIDHIP_EINVAL, "clean_auto: image, psf, model and mask must be N x N");
+        F st[8] = {0};
+        check(gridhip_clean_auto(ctx_, image.h, psf.data.data(), image.data.data(), model.data.data(), gain, threshold,
+                                 niter, border, patch, mask.empty() ? nullptr : mask.data(), nsigma, &sigma, peak_frac, st));
+        if (why) *why = {st[4], st[5], st[6]};
+        return {st[0], st[1], st[2], st[3]};
+    }
+    MsCleanStats msclean_auto(Matrix<F> &image, const Matrix<F> &psf, Matrix<F> &model, const std::vector<F> &scales,
+                              std::vector<F> bias, const std::vector<uint8_t> &mask, F nsigma, F sigma, F peak_frac,
+                              AutoStop *why = nullptr, F gain = 0.1, F threshold = 0.0, Int niter = 100, Int border = 0,
+                              Int patch = 0)
+    {
+        if (image.h != image.w || psf.h != image.h || psf.w != image.w || model.h != image.h || model.w != image.w ||
+            (!mask.empty() && (Int)mask.size() != image.h * image.w))
+            throw Error(GRIDHIP_EINVAL, "msclean_auto: image, psf, model and mask must be N x N");
+        if (bias.empty() && !scales.empty()) {
+            F amax = scales[0];
+            for (F a : scales) amax = a > amax ? a : amax;
+            for (F a : scales) bias.push_back(amax > 0 ? 1 - 0.6 * a / amax : 1);
+        }
+        if (bias.size() != scales.size()) throw Error(GRIDHIP_EINVAL, "msclean_auto: one bias per scale");
+        F st[16] = {0};
+        check(gridhip_msclean_auto(ctx_, image.h, psf.data.data(), image.data.data(), model.data.data(), (Int)scales.size(),
+                                   scales.data(), bias.data(), gain, threshold, niter, border, patch,
+                                   mask.empty() ? nullptr : mask.data(), nsigma, &sigma, peak_frac, st));
+        if (why) *why = {st[12], st[13], st[14]};
+        MsCleanStats out = {st[0], st[1], st[2], st[3], st[4], {st[6], st[7], st[8], st[9], st[10], st[11]}};
+        return out;
+    }
+
     // ---- restoring beam and restore (gridhip_fit_beam, gridhip_restore; include/gridhip.h, "restoring beam and restore") ----
     // The elliptical Gaussian exp(-(A dx^2 + 2 B dx dy + C dy^2)) fitted to the PSF's main lobe: FWHMs in cells (a cell
     // is theta / N radians), bpa in radians from +x towards +y.  ok is false, and the rest NaN, when the fit failed.

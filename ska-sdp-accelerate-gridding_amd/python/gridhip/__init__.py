@@ -24,7 +24,7 @@ import ctypes as C
 from . import _lib
 from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
-                       image_of, imaging_function, in_place, is_torch, scale_list)
+                       auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
 from ._marshal import weighting as _weighting
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
@@ -360,14 +360,37 @@ class Context(Handle):
             self._call(be, "predict", *imaging_function(be, imgfn), *tl, model, n, u, v, w, st, sub, out)
         return out
 
-    def clean(self, image, psf, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None):
+    def image_stats(self, image, mask=None, border=0):
+        """Robust statistics of the N x N float64 `image` (gridhip_image_stats[_dev]; include/gridhip.h, "image
+        statistics") over the finite cells inside `border` and `mask` (bool or uint8, N x N, None: every cell):
+        [n, median, MAD, sigma = 1.4826 MAD, min, max, non-finite cells skipped, 0] - exact order statistics, the same
+        bits on every run.  A numpy image takes the synchronous host form; a torch cuda tensor the asynchronous one, and
+        the result is a cuda tensor: nothing is read back (stats[3:4] is the `noise` of clean)."""
+        be = backend(image)
+        shape = tuple(getattr(image, "shape", ()))
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("image must be N x N")
+        image = image_of(be, image, shape, "image")
+        mask = mask_of(be, mask, shape)
+        stats = be.empty(8, be.f64, image)
+        self._call(be, "image_stats", shape[0], image, mask, int(border), stats)
+        return stats
+
+    def clean(self, image, psf, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None, mask=None,
+              nsigma=0.0, noise=None, peak_frac=0.0):
         """Hogbom CLEAN of the N x N float64 `image` with `psf` (gridhip_clean[_dev]; include/gridhip.h,
         "deconvolution"): at most niter components of gain * peak, searched inside `border`, stopping at |peak| <=
         threshold, the PSF subtracted over its whole overlap or (patch > 0) within +-patch cells of the peak.
         `image` is UPDATED IN PLACE and returned as the residual; `model` (zeros when None) is accumulated into and
         returned, so `model, residual, stats = ctx.clean(image, psf, model=model)` is model = model + clean(image, psf).
         stats = [iterations, final peak, its flat index, flux added].  numpy arrays take the synchronous host form;
-        torch cuda tensors the asynchronous one on torch's stream, with stats a cuda tensor: nothing is read back."""
+        torch cuda tensors the asynchronous one on torch's stream, with stats a cuda tensor: nothing is read back.
+        With any of `mask` (bool or uint8, N x N: cells that are 0 are never selected), `nsigma` and `noise` (sigma: a
+        number, or one element like image_stats(...)[3:4]) or `peak_frac` the call is gridhip_clean_auto[_dev]
+        ("masks and noise-based stop levels"): the loop stops at T = max(threshold, nsigma * sigma, peak_frac * |first
+        peak|) and stats has four more values, [T, reason, first peak, 0].  With cuda tensors pass `noise` as a device
+        element (stats[3:4]): a Python number is uploaded by a host-to-device copy, so the call is then neither
+        asynchronous nor capturable into a graph."""
         be = backend(image)
         shape = tuple(getattr(image, "shape", ()))
         if len(shape) != 2 or shape[0] != shape[1]:
@@ -377,18 +400,27 @@ class Context(Handle):
         if tuple(psf.shape) != shape:
             raise ValueError(f"psf must be {shape}, as the image")
         model = in_place(be, model, shape, "model", image)
-        stats = be.empty(4, be.f64, image)
-        self._call(be, "clean", shape[0], psf, image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        auto = auto_args(be, mask, nsigma, noise, peak_frac, shape, image)
+        stats = be.empty(8 if auto else 4, be.f64, image)
+        if auto:
+            self._call(be, "clean_auto", shape[0], psf, image, model, *clean_scalars(gain, threshold, niter, border, patch),
+                       *auto, stats)
+        else:
+            self._call(be, "clean", shape[0], psf, image, model, *clean_scalars(gain, threshold, niter, border, patch),
+                       stats)
         return model, image, stats
 
-    def msclean(self, image, psf, scales, bias=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None):
+    def msclean(self, image, psf, scales, bias=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None,
+                mask=None, nsigma=0.0, noise=None, peak_frac=0.0):
         """Multi-scale CLEAN of the N x N float64 `image` with `psf` (gridhip_msclean[_dev]; include/gridhip.h,
         "multi-scale deconvolution"): clean() whose components are tapered paraboloids of the `scales` (in cells,
         increasing from the delta scale 0, at most 6 of them and at most 32 cells), chosen by the largest bias-weighted
         peak.  `scales` and `bias` are host sequences for numpy and torch images alike; bias=None is
         1 - 0.6 a_s / a_max.  `image` is UPDATED IN PLACE and returned as the residual, `model` (zeros when None) is
         accumulated into.  Returns (model, residual, stats); stats = [iterations, final peak, its flat index, the scale
-        of the last component (-1: none), flux added, 0, components per scale x 6]."""
+        of the last component (-1: none), flux added, 0, components per scale x 6].  mask, nsigma, noise, peak_frac: as
+        for clean (gridhip_msclean_auto[_dev]); the mask constrains component centres, and stats has 16 values.  As
+        for clean, a numeric `noise` with cuda tensors is a host-to-device copy and cannot be captured: pass stats[3:4]."""
         be = backend(image)
         shape = tuple(getattr(image, "shape", ()))
         if len(shape) != 2 or shape[0] != shape[1]:
@@ -399,9 +431,14 @@ class Context(Handle):
             raise ValueError(f"psf must be {shape}, as the image")
         sc, keep = scale_list(scales, bias)
         model = in_place(be, model, shape, "model", image)
-        stats = be.empty(12, be.f64, image)
-        self._call(be, "msclean", shape[0], psf, image, model, *sc,
-                   *clean_scalars(gain, threshold, niter, border, patch), stats)
+        auto = auto_args(be, mask, nsigma, noise, peak_frac, shape, image)
+        stats = be.empty(16 if auto else 12, be.f64, image)
+        if auto:
+            self._call(be, "msclean_auto", shape[0], psf, image, model, *sc,
+                       *clean_scalars(gain, threshold, niter, border, patch), *auto, stats)
+        else:
+            self._call(be, "msclean", shape[0], psf, image, model, *sc,
+                       *clean_scalars(gain, threshold, niter, border, patch), stats)
         del keep
         return model, image, stats
 
@@ -633,40 +670,72 @@ class Imager(_Bound):
         return out
 
 
-    def clean(self, image, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+    def image_stats(self, image, mask=None, border=0):
+        """Context.image_stats of an N x N cuda float64 image with the imager's own scratch
+        (gridhip_imager_image_stats_dev): asynchronous, and capturable after a first call."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        self._ok(image, be.f64, NN, "image")
+        mask = mask_of(be, mask, NN)
+        stats = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_image_stats", image, mask, int(border), stats)
+        return stats
+
+    def clean(self, image, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, mask=None, nsigma=0.0,
+              noise=None, peak_frac=0.0):
         """Context.clean with the imager's own PSF (gridhip_imager_clean_dev): `image` (N x N cuda float64, a cycle's
         output) is updated in place and returned as the residual, `model` (zeros when None) is accumulated into.
-        Returns (model, residual, stats); asynchronous, and capturable after a first call."""
+        Returns (model, residual, stats); asynchronous, and capturable after a first call.  mask, nsigma, noise,
+        peak_frac: as for Context.clean (gridhip_imager_clean_auto_dev, 8 stats); to stay capturable `noise` must be a
+        device element such as image_stats(...)[3:4], not a Python number."""
         self._open()
         be, NN = device(), (self.N, self.N)
         image = in_place(be, image, NN, "image")
         model = in_place(be, model, NN, "model", self.device)
-        stats = be.empty(4, be.f64, self.device)
-        self._call(be, "imager_clean", image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        auto = auto_args(be, mask, nsigma, noise, peak_frac, NN, self.device)
+        stats = be.empty(8 if auto else 4, be.f64, self.device)
+        if auto:
+            self._call(be, "imager_clean_auto", image, model, *clean_scalars(gain, threshold, niter, border, patch), *auto,
+                       stats)
+        else:
+            self._call(be, "imager_clean", image, model, *clean_scalars(gain, threshold, niter, border, patch), stats)
         return model, image, stats
 
-    def msclean(self, image, scales, bias=None, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+    def msclean(self, image, scales, bias=None, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0,
+                mask=None, nsigma=0.0, noise=None, peak_frac=0.0):
         """Context.msclean with the imager's own PSF (gridhip_imager_msclean_dev).  The imager keeps the cross-PSFs of
         the scale list between calls: a second call with the same `scales` builds and allocates nothing.  Returns
-        (model, residual, stats[12]); asynchronous, and capturable after a first call with these scales."""
+        (model, residual, stats[12]); asynchronous, and capturable after a first call with these scales.  mask, nsigma,
+        noise, peak_frac: as for Context.msclean (gridhip_imager_msclean_auto_dev, 16 stats); `noise` as a device element
+        to stay capturable."""
         self._open()
         be, NN = device(), (self.N, self.N)
         image = in_place(be, image, NN, "image")
         sc, keep = scale_list(scales, bias)
         model = in_place(be, model, NN, "model", self.device)
-        stats = be.empty(12, be.f64, self.device)
-        self._call(be, "imager_msclean", image, model, *sc, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        auto = auto_args(be, mask, nsigma, noise, peak_frac, NN, self.device)
+        stats = be.empty(16 if auto else 12, be.f64, self.device)
+        if auto:
+            self._call(be, "imager_msclean_auto", image, model, *sc, *clean_scalars(gain, threshold, niter, border, patch),
+                       *auto, stats)
+        else:
+            self._call(be, "imager_msclean", image, model, *sc, *clean_scalars(gain, threshold, niter, border, patch),
+                       stats)
         del keep
         return model, image, stats
 
     def deconvolve(self, vis, nmajor, model=None, out=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0,
-                   scales=None, bias=None):
+                   scales=None, bias=None, mask=None, nsigma=0.0, peak_frac=0.0):
         """Visibilities to a model image in one asynchronous call (gridhip_imager_deconvolve_dev): nmajor times
         image = cycle(vis, model) then clean(image, model), and one closing cycle, so that the returned image is
         do_imaging(vis - predict(model))'s for the returned model.  model (zeros when None) is accumulated into, out
         (a new image when None) receives the closing residual image.  Returns (model, image, stats[nmajor, 4]).
         With `scales` (and optionally `bias`) the minor cycle is msclean (gridhip_imager_msdeconvolve_dev) and stats is
-        [nmajor, 12]."""
+        [nmajor, 12].
+        With any of `mask`, `nsigma`, `peak_frac` every major cycle measures its image (image_stats over the whole
+        search region) and its minor cycle is clean / msclean under the mask, stopping at max(threshold, nsigma * that
+        cycle's sigma, peak_frac * its first peak) (gridhip_imager_[ms]deconvolve_auto_dev): returns (model, image,
+        stats[nmajor, 8 | 16], istats[nmajor, 8])."""
         self._open()
         be, NN = device(), (self.N, self.N)
         self._ok(vis, be.c128, (self.n,), "vis")
@@ -674,6 +743,17 @@ class Imager(_Bound):
         out = be.empty(NN, be.f64, self.device) if out is None else in_place(be, out, NN, "out")
         if int(nmajor) < 0:
             raise ValueError("nmajor must be >= 0")
+        if mask is not None or nsigma or peak_frac:
+            if scales is None and bias is not None:
+                raise ValueError("bias goes with scales")
+            mask, nsigma, _, peak_frac = auto_args(be, mask, nsigma, None, peak_frac, NN, self.device, own_noise=True)
+            istats = be.empty((int(nmajor), 8), be.f64, self.device)
+            sc, keep = scale_list(scales, bias) if scales is not None else ((), None)
+            stats = be.empty((int(nmajor), 16 if sc else 8), be.f64, self.device)
+            self._call(be, "imager_msdeconvolve_auto" if sc else "imager_deconvolve_auto", vis, model, out, int(nmajor), *sc,
+                       *clean_scalars(gain, threshold, niter, border, patch), mask, nsigma, peak_frac, stats, istats)
+            del keep
+            return model, out, stats, istats
         if scales is None:
             if bias is not None:
                 raise ValueError("bias goes with scales")

@@ -36,6 +36,10 @@ _PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, v
 _CLEAN = [vp, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
 _HOST_F64 = C.POINTER(C.c_double)  # an array that is the host's in every form (msclean's scales and bias)
 _MSCLEAN = [vp, i64, vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64, i64, i64, vp]
+_AUTO = [vp, C.c_double, vp, C.c_double]  # mask, nsigma, noise, peak_frac (the _auto forms, before stats)
+_CLEAN_AUTO = _CLEAN[:-1] + _AUTO + [vp]
+_MSCLEAN_AUTO = _MSCLEAN[:-1] + _AUTO + [vp]
+_IMAGE_STATS = [vp, i64, vp, vp, i64, vp]
 _FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
 _RESTORE = [vp, i64, vp, vp, vp, i64, vp]
 _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_double, vp, vp]
@@ -118,6 +122,20 @@ SIGNATURES = {
     "gridhip_imager_msclean_dev": (ci, [vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_imager_msdeconvolve_dev": (ci, [vp, vp, vp, vp, i64, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64,
                                              i64, i64, vp]),
+    "gridhip_image_stats": (ci, _IMAGE_STATS),
+    "gridhip_image_stats_dev": (ci, _IMAGE_STATS),
+    "gridhip_imager_image_stats_dev": (ci, [vp, vp, vp, i64, vp]),
+    "gridhip_clean_auto": (ci, _CLEAN_AUTO),
+    "gridhip_clean_auto_dev": (ci, _CLEAN_AUTO),
+    "gridhip_msclean_auto": (ci, _MSCLEAN_AUTO),
+    "gridhip_msclean_auto_dev": (ci, _MSCLEAN_AUTO),
+    "gridhip_imager_clean_auto_dev": (ci, [vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, *_AUTO, vp]),
+    "gridhip_imager_msclean_auto_dev": (ci, [vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64, i64, i64,
+                                             *_AUTO, vp]),
+    "gridhip_imager_deconvolve_auto_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64, vp, C.c_double,
+                                                C.c_double, vp, vp]),
+    "gridhip_imager_msdeconvolve_auto_dev": (ci, [vp, vp, vp, vp, i64, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double,
+                                                  i64, i64, i64, vp, C.c_double, C.c_double, vp, vp]),
     "gridhip_fit_beam": (ci, _FIT_BEAM),
     "gridhip_fit_beam_dev": (ci, _FIT_BEAM),
     "gridhip_restore": (ci, _RESTORE),

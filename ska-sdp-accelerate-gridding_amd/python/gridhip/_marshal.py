@@ -18,6 +18,7 @@ class _Host:
     suffix = ""
     c128, f64, i64 = np.complex128, np.float64, np.int64
     form, bad_grid = "a C-contiguous complex128 ndarray", ValueError
+    array = "C-contiguous ndarray"  # the kind of array this back end takes, for messages about other dtypes
 
     @staticmethod
     def cv(x, dt):
@@ -48,6 +49,7 @@ class _Device:
     """torch cuda tensors -> device pointers; the context is first bound to torch's current stream"""
     suffix = "_dev"
     form, bad_grid = "a contiguous cuda complex128 tensor", AssertionError
+    array = "contiguous cuda tensor"
 
     def __init__(self):
         import torch
@@ -160,6 +162,51 @@ def in_place(be, x, shape, what, like=None):
 def clean_scalars(gain, threshold, niter, border, patch):
     """gain, threshold, niter, border, patch as every clean entry point takes them"""
     return float(gain), float(threshold), int(niter), int(border), int(patch)
+
+
+def mask_of(be, mask, shape):
+    """A clean mask as the ABI takes it - N x N bytes, non-zero where a component may be centred - or None: a bool or
+    uint8 array of `be`'s own kind and of the image's shape; a bool one is reinterpreted, nothing is converted."""
+    if mask is None:
+        return None
+    if be is not backend(mask) or not hasattr(mask, "dtype"):
+        raise ValueError(f"mask must be a {be.array} of dtype bool or uint8")
+    u8, b1 = (np.uint8, np.bool_) if be is HOST else (be.torch.uint8, be.torch.bool)
+    if mask.dtype not in (u8, b1):
+        raise ValueError(f"mask must be of dtype bool or uint8, not {mask.dtype}")
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"mask must be of shape {tuple(shape)}, as the image")
+    mask = be.cv(mask, mask.dtype)
+    return mask.view(u8) if mask.dtype == b1 else mask
+
+
+def auto_args(be, mask, nsigma, noise, peak_frac, shape, like, own_noise=False):
+    """mask, nsigma, noise, peak_frac as the _auto entry points take them, or None when all four are at their defaults
+    (the caller then takes the plain entry point).  noise: sigma as a number, or one float64 element of `be`'s own kind
+    (element 3 of an image_stats result: stats[3:4]) - on the device nothing is read back.  A NUMBER with device
+    images is uploaded from pageable host memory by this call: a copy that cannot be captured into a graph and that
+    makes the call wait for the host - inside a graph, or to stay asynchronous, pass a device element.  own_noise: the entry point
+    measures sigma itself (deconvolve)."""
+    import math
+    if mask is None and not nsigma and noise is None and not peak_frac:
+        return None
+    nsigma, peak_frac = float(nsigma), float(peak_frac)
+    if not (math.isfinite(nsigma) and nsigma >= 0.0):
+        raise ValueError("nsigma must be finite and >= 0")
+    if not 0.0 <= peak_frac < 1.0:
+        raise ValueError("peak_frac must be in [0, 1)")
+    mask = mask_of(be, mask, shape)
+    if noise is None:
+        if nsigma > 0.0 and not own_noise:
+            raise ValueError("nsigma > 0 needs noise (sigma, e.g. image_stats(...)[3:4])")
+    elif isinstance(noise, (int, float)):
+        noise = np.array([noise], dtype=np.float64)
+        if be is not HOST:
+            noise = be.torch.from_numpy(noise).to(getattr(like, "device", like))
+    else:
+        if be is not backend(noise) or not be.ok(noise, be.f64) or int(np.prod(tuple(noise.shape))) != 1:
+            raise ValueError(f"noise must be a number or a {be.array} of one float64 element")
+    return mask, nsigma, noise, peak_frac
 
 
 def scale_list(scales, bias):
