@@ -36,6 +36,8 @@ module GridHip
   , mscleanIO, imagerMscleanIO, imagerMsDeconvolveIO, msDefaultBias
   -- * clean masks and noise-based stop levels: robust image statistics and the _auto forms (absent from the reference)
   , AutoOptions(..), imageStatsIO, cleanAutoIO, imagerDeconvolveAutoIO
+  -- * wide-band imaging: Taylor-term major cycles and the multi-term CLEAN (absent from the reference)
+  , mfcleanIO, imagerSetSpectralIO, imagerMfsCycleIO, imagerMfDeconvolveIO
   -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
   , fitBeamIO, restoreIO, imagerBeamIO, imagerRestoreIO
   -- * imaging weights: natural, uniform, Briggs, taper and data weights, alone or as what an imager is created with
@@ -353,6 +355,27 @@ foreign import ccall unsafe "gridhip_imager_create_aw_weighted_dev"
 -- int gridhip_imager_weight_stats_dev(imager, stats)
 foreign import ccall unsafe "gridhip_imager_weight_stats_dev"
   c_imager_weight_stats_dev :: Ptr Imager -> Ptr CDouble -> IO CInt
+-- int gridhip_mfclean(ctx, N, T, psfs, residuals, models, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_mfclean"
+  c_mfclean :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_mfclean_dev(ctx, N, T, psfs, residuals, models, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_mfclean_dev"
+  c_mfclean_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_set_spectral_dev(imager, T, x)
+foreign import ccall unsafe "gridhip_imager_set_spectral_dev"
+  c_imager_set_spectral_dev :: Ptr Imager -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_spectral_psfs_dev(imager, psfs)
+foreign import ccall unsafe "gridhip_imager_spectral_psfs_dev"
+  c_imager_spectral_psfs_dev :: Ptr Imager -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_mfs_cycle_dev(imager, models, vis, images, vis_res)
+foreign import ccall unsafe "gridhip_imager_mfs_cycle_dev"
+  c_imager_mfs_cycle_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_mfclean_dev(imager, residuals, models, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_imager_mfclean_dev"
+  c_imager_mfclean_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_mfdeconvolve_dev(imager, vis, models, images, nmajor, gain, threshold, niter, border, patch, stats)
+foreign import ccall unsafe "gridhip_imager_mfdeconvolve_dev"
+  c_imager_mfdeconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -990,6 +1013,78 @@ imagerMsDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) s
                 c_synchronize c >>= check h
                 msStatsRows rows ps
   let sh = A.Z A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Wide-band imaging (include/gridhip.h, "wide-band imaging"): T Taylor terms of the sky, as [T][N][N] arrays.
+
+-- [iterations, a_0 at the final peak, its flat index, flux_0 .. flux_3, reason] per row of a stats block
+mfStatsRows :: Int -> Ptr CDouble -> IO [[F]]
+mfStatsRows rows p = mapM (\r -> map realToFrac <$> peekArray 8 (p `advancePtr` (8 * r))) [0 .. rows - 1]
+
+-- | mfcleanIO h opts images psfs models: the multi-term CLEAN of the T residual images with the 2T - 1 spectral PSFs:
+-- (models + the components found, the residuals, the stats) - the host form, synchronous
+mfcleanIO :: GridHip -> CleanOptions -> A.Array A.DIM3 F -> A.Array A.DIM3 F -> A.Array A.DIM3 F
+          -> IO (A.Array A.DIM3 F, A.Array A.DIM3 F, [F])
+mfcleanIO h@(GridHip c) (CleanOptions g t ni b pa) images psfs models = do
+  let A.Z A.:. nt A.:. n' A.:. _ = A.arrayShape images
+      copyOf m = do o <- mallocForeignPtrArray (nt * n' * n') :: IO (ForeignPtr CDouble)
+                    withF m $ \s -> withForeignPtr o $ \d -> copyArray d s (nt * n' * n')
+                    return o
+  res <- copyOf images
+  mdl <- copyOf models
+  st <- withF psfs $ \pp -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pm -> allocaArray 8 $ \ps -> do
+          c_mfclean c (fi n') (fi nt) pp pr pm (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ps >>= check h
+          head <$> mfStatsRows 1 ps
+  let sh = A.Z A.:. nt A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
+
+-- | imagerSetSpectralIO im nterms x: give the imager nterms Taylor terms, x_k = (nu_k - nu_0) / nu_0 per visibility
+-- (gridhip_imager_set_spectral_dev: it builds and keeps the 2 nterms - 1 spectral PSFs)
+imagerSetSpectralIO :: ImagerH -> Int -> A.Vector F -> IO ()
+imagerSetSpectralIO (ImagerH h p n _) nterms x = withF x $ \px -> withDev h px (8 * n) $ \dx ->
+  c_imager_set_spectral_dev p (fi nterms) dx >>= check h
+
+-- | imagerMfsCycleIO im nterms models vis: one wide-band major-cycle step (gridhip_imager_mfs_cycle_dev) of an imager
+-- that has had imagerSetSpectralIO with nterms: the nterms residual images of vis minus the prediction of the nterms
+-- models (of vis with Nothing), and the residual visibilities
+imagerMfsCycleIO :: ImagerH -> Int -> Maybe (A.Array A.DIM3 F) -> A.Vector Visibility
+                 -> IO (A.Array A.DIM3 F, A.Vector Visibility)
+imagerMfsCycleIO (ImagerH h@(GridHip c) p n n') nterms models vis = do
+  let bytes = 8 * nterms * n' * n'
+  img <- mallocForeignPtrArray (nterms * n' * n') :: IO (ForeignPtr CDouble)
+  res <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  let withModels k = maybe (k nullPtr) (\m -> withF m $ \mp -> withDev h mp bytes k) models
+  withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withModels $ \dm ->
+    withForeignPtr img $ \pi' -> withDev h pi' bytes $ \di -> withForeignPtr res $ \pr -> do
+      c_imager_mfs_cycle_dev p dm dv di dv >>= check h   -- (the residual in place, in the device copy of vis)
+      c_memcpy_d2h c (castPtr pi') (castPtr di) (fi bytes) >>= check h
+      c_memcpy_d2h c (castPtr pr) (castPtr dv) (fi (16 * n)) >>= check h
+      c_synchronize c >>= check h
+  return ( A.fromForeignPtrs (A.Z A.:. nterms A.:. n' A.:. n') (castForeignPtr img)
+         , A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr res) )
+
+-- | imagerMfDeconvolveIO im opts nterms nmajor vis models: nmajor times (imagerMfsCycleIO, the multi-term CLEAN) and
+-- one closing cycle in one call on the device (gridhip_imager_mfdeconvolve_dev): (the models, the closing residual
+-- images, one row of 8 stats per major cycle)
+imagerMfDeconvolveIO :: ImagerH -> CleanOptions -> Int -> Int -> A.Vector Visibility -> A.Array A.DIM3 F
+                     -> IO (A.Array A.DIM3 F, A.Array A.DIM3 F, [[F]])
+imagerMfDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) nterms nmajor vis models = do
+  img <- mallocForeignPtrArray (nterms * n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (nterms * n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * nterms * n' * n'
+      rows = max 0 nmajor
+  st <- withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withF models $ \pm -> withDev h pm bytes $ \dm ->
+          withForeignPtr img $ \pi' -> withDev h pi' bytes $ \di -> allocaArray (8 * rows) $ \ps ->
+            withDev h ps (64 * rows) $ \ds -> withForeignPtr mdl $ \pq -> do
+              c_imager_mfdeconvolve_dev p dv dm di (fi nmajor) (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) ds
+                >>= check h
+              c_memcpy_d2h c (castPtr pi') (castPtr di) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+              c_memcpy_d2h c (castPtr ps) (castPtr ds) (fi (64 * rows)) >>= check h
+              c_synchronize c >>= check h
+              mfStatsRows rows ps
+  let sh = A.Z A.:. nterms A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
 
 -- ---------------------------------------------------------------------------------------------------------

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 190 /* 0.1.9 */
+#define GRIDHIP_VERSION 200 /* 0.2.0 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -454,7 +454,8 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
  * 4 x 8 B coordinates instead of records for the simple kind; per N^2 cell 16 B (grid) + 16 B (transform) + 8 B (psf),
  * and 16 B more for odd N; the kernel tables (conv: 2 tables; w_cache: one plane per w-bin of each stream; aw: each
  * batch's distinct kernels, twice) and one hipFFT plan; after its first clean or deconvolve also clean's state block and
- * tile table, 64 B + 16 B per 16 x 128 cells, after its first msclean that call's scratch (see there), and after its first restore without a `beam` output 64 B for the fitted beam
+ * tile table, 64 B + 16 B per 16 x 128 cells, after its first msclean that call's scratch (see there), and after its first restore without a `beam` output 64 B for the fitted beam;
+ * with spectral terms (see "wide-band imaging") 8 B + 16 B more per visibility, 2T - 1 images and mfclean's scratch
  * (all released at destroy).
  * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
  * and 1).  n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
@@ -826,6 +827,92 @@ int gridhip_imager_create_aw_weighted_dev(gridhip_ctx *ctx, double theta, int64_
                                           gridhip_imager **imager);
 /* the stats of the creation's weighting, copied on the stream into 8 doubles on the device */
 int gridhip_imager_weight_stats_dev(gridhip_imager *imager, double *stats);
+
+/* ---- wide-band imaging: Taylor-term major cycles and a multi-term CLEAN, on the device ---------------------------------
+ * Multi-term multi-frequency synthesis (Sault & Wieringa 1994; Rau & Cornwell 2011, one scale): the sky is modelled as
+ * I(nu) = sum_t I_t x^t with x = (nu - nu_0) / nu_0, T Taylor terms, 1 <= T <= 4.  The reference has nothing of the kind:
+ * the semantics are defined here.
+ * THE MINOR CYCLE.  All images are real N x N, laid out as gridhip_clean's, c = (N / 2, N / 2):
+ *     psfs       [2T - 1][N][N], the spectral PSFs P_s
+ *     residuals  [T][N][N], updated in place
+ *     models     [T][N][N], accumulated into, never zeroed
+ *     H[t][q] = P_{t+q}[c, c]
+ *     Hinv    = the inverse of H by Gauss-Jordan WITHOUT pivoting, rows in order: the pivot row is divided by the pivot
+ *               (true divisions), then m * (pivot row) is taken from every other row, m that row's entry in the pivot's
+ *               column, the product rounded, then subtracted (no fused multiply-add).  A pivot that is not > 0, NaN
+ *               included, makes H singular: nothing is done, reason 3, stats = { 0, NaN, -1, 0, 0, 0, 0, 3 }
+ *     repeat at most niter times:
+ *         for every cell:  a_t = sum_q Hinv[t][q] * R_q   (q ascending from the first product, each product rounded,
+ *                                                          then added)
+ *                          s   = sum_t a_t * R_t          (t ascending, likewise)
+ *         k = the flat index of the largest s over border <= y, x < N - border; ties go to the lowest flat index; a NaN
+ *             s is never selected.  (Hinv is positive definite when the elimination succeeds, so s is negative only by
+ *             the rounding of a cell at zero: the comparison is clean's own, on the magnitude.)
+ *         p = a_0[k]
+ *         if |p| <= threshold: stop                                (before anything is subtracted)
+ *         f_t = gain * a_t[k] (rounded once);  models[t][k] += f_t;  flux_t += f_t
+ *         R_t[y', x'] = (...((R_t - f_0 * P_t) - f_1 * P_{t+1}) ... - f_{T-1} * P_{t+T-1})  at the PSF index
+ *                       [y' - y + c, x' - x + c], q ascending, each product rounded before it is subtracted; the region
+ *                       and the patch rule are exactly gridhip_clean's
+ *     stats (8 doubles) = { iterations, a_0 at the final k*, k*, flux_0, flux_1, flux_2, flux_3, reason }, k* the peak of
+ *                         the final residuals under the same rule (NaN at -1 when nothing can be selected); reason
+ *                         0: niter components taken, 1: |p| <= threshold, 2: nothing selectable, 3: singular H - the
+ *                         first of 3, 2, 1 that holds; unused flux slots are 0
+ * (Rounding, for a restatement that wants the bits: as in gridhip_clean, models[t][k] and flux_t receive gain * a_t in one
+ * fused multiply-add each; f_t itself, which scales the PSFs, is the rounded product.)
+ * With T = 1 and P_0[c, c] == 1 this is Hogbom CLEAN: residual and model come out with gridhip_clean's bits wherever no
+ * two cells tie in the square of their value.  No atomics anywhere, contraction is off: a call is deterministic bit for
+ * bit, and the host, _dev and imager forms give the same bits.
+ * Arguments: gridhip_clean's rules for N, gain, threshold, niter, border, patch and NULL pointers, its NaN rule and its
+ * GRIDHIP_EUNSUPPORTED limit on N; T in 1 .. 4; no two of the 4T - 1 planes overlapping - GRIDHIP_EINVAL, refused before
+ * anything is touched.
+ * The shape is gridhip_clean's: tiles of 16 x 128 cells, a device table of one (score, index) entry per tile.  The first
+ * launch builds the table in one pass over the T residuals, the second inverts H into the state block and takes the first
+ * component; an iteration is two launches: a tile kernel over the overlapped tiles only, which reads T residuals and
+ * 2T - 1 PSFs and writes T residuals - (4T - 1) * 8 B per cell, (4T - 1) / 3 of Hogbom's - and recomputes the tiles'
+ * scores in the same pass, and a one-work-group kernel that reduces the table, recomputes a_t at k from the T residual
+ * cells, tests the stop rule and takes the component.  gridhip_mfclean is synchronous and stages host arrays through the
+ * context's pool.  The _dev forms enqueue kernels only on the context's stream (2 + 2 * niter launches; no memset or copy
+ * node), allocate nothing after the first call of a shape, never synchronise and read nothing back: they can be
+ * captured into a graph.  Scratch (256 B + 16 B per tile) comes from the context's pool, or for the imager form from
+ * memory the imager owns.  Masks, noise-based stop levels and a multi-scale variant are not part of this form. */
+int gridhip_mfclean(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, double *residuals, double *models,
+                    double gain, double threshold, int64_t niter, int64_t border, int64_t patch, double *stats);
+int gridhip_mfclean_dev(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, double *residuals, double *models,
+                        double gain, double threshold, int64_t niter, int64_t border, int64_t patch, double *stats);
+/* WIDE-BAND IMAGERS.  set_spectral gives an imager T Taylor terms: x is n doubles on the device, x_k = (nu_k - nu_0) /
+ * nu_0 of visibility k in the order of vis; it is copied, and the caller may free it.  The powers are pw_0 = 1,
+ * pw_t = pw_{t-1} * x.  A visibility whose x_k is not finite is treated as flagged: it grids nothing and predicts 0 in
+ * every term.  The call builds and keeps the 2T - 1 spectral PSFs, DEFINED BY EXISTING CALLS:
+ *     P_s = the image of cycle(NULL, vis_k = (pw_s(x_k), 0))
+ * - the weighted PSF pass with x^s, divided by the imager's stored pmax - so that P_0 agrees with the imager's own PSF
+ * to the tolerance of the fp64 atomics (1e-10).  It may synchronise, as creation does; calling it again replaces the
+ * terms.  T outside 1 .. 4 or (n > 0) a NULL x is GRIDHIP_EINVAL.  No other entry point changes: an imager without
+ * spectral terms is what it was, and one with them still cycles, cleans and restores as before.
+ * Memory: an imager with spectral terms also holds 8 B (x) + 16 B (the residual visibilities of an mfs_cycle) per
+ * visibility, 2T - 1 images of N^2 doubles and, after its first mfclean, 256 B + 16 B per 16 x 128 cells. */
+int gridhip_imager_set_spectral_dev(gridhip_imager *imager, int64_t T, const double *x);
+/* the 2T - 1 spectral PSFs, [2T - 1][N][N] doubles on the device, copied on the stream */
+int gridhip_imager_spectral_psfs_dev(gridhip_imager *imager, double *psfs);
+/* one wide-band major-cycle step, DEFINED BY THE CALLS IT REPLACES (models [T][N][N] or NULL, images [T][N][N]):
+ *     r         = vis - sum_q pw_q(x) * predict(models[q])     (q ascending; models NULL: r = vis)
+ *     images[t] = cycle(NULL, pw_t(x) * r).image               vis_res, when given, = r (it may be vis itself)
+ * One forward transform and one gather per model term, accumulated into the residual-visibility block; then per term one
+ * pass over that block (times pw_t, conjugate where mirrored, times the weight), the scatter and the tail.
+ * Asynchronous, allocation-free after the first call, kernels only, capturable, like cycle. */
+int gridhip_imager_mfs_cycle_dev(gridhip_imager *imager, const double *models, const double *vis, double *images,
+                                 double *vis_res);
+/* gridhip_mfclean_dev with the imager's spectral PSFs (nothing is copied), its T and N */
+int gridhip_imager_mfclean_dev(gridhip_imager *imager, double *residuals, double *models, double gain, double threshold,
+                               int64_t niter, int64_t border, int64_t patch, double *stats);
+/* visibilities -> T model images in one call, DEFINED BY THE CALLS IT REPLACES:
+ *     repeat nmajor times: images = mfs_cycle(models, vis); mfclean(images, models) with stats + 8 * i (when stats != NULL)
+ *     images = mfs_cycle(models, vis)
+ * models is the caller's and must be initialised; stats is nmajor x 8 doubles on the device, or NULL.
+ * spectral_psfs, mfs_cycle, mfclean and mfdeconvolve on an imager without spectral terms are GRIDHIP_EINVAL. */
+int gridhip_imager_mfdeconvolve_dev(gridhip_imager *imager, const double *vis, double *models, double *images,
+                                    int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
+                                    int64_t patch, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

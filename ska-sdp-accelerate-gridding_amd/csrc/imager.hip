@@ -11,6 +11,10 @@
 // with no pre-pass, no table build, no histogram, no PSF pass, no allocation, no synchronisation and no memset node.
 // The gather and the scatter are the tile kernels of the plans (plan.hip, awgrid.hip), which lend their records to the
 // launchers; the simple kind has no records and keeps its two coordinate sets instead.
+// Wide-band imaging ("wide-band imaging" in the header) adds to an imager x = (nu - nu_0) / nu_0 per visibility, the
+// 2T - 1 spectral PSFs - each the image of a plain cycle of (x^s, 0) - and a residual-visibility block: an mfs_cycle is one
+// transform and gather per model term accumulated into that block, then per term one pass over it (times x^t, conjugate
+// where mirrored, times the weight), the scatter and the tail.  An imager without spectral terms runs none of this.
 #include <string.h>
 
 #include <new>
@@ -106,6 +110,64 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// ---- wide-band imaging (include/gridhip.h, "wide-band imaging"): x_k = (nu_k - nu_0) / nu_0 per visibility, the powers
+// pw_0 = 1, pw_t = pw_{t-1} * x, and a visibility whose x is not finite taking part in nothing
+__device__ __forceinline__ double spectral_power(double x, int t)
+{
+    double pw = 1.0;
+    for (int i = 0; i < t; ++i) pw = pw * x;
+    return pw;
+}
+
+// the visibilities whose cycle image is the spectral PSF P_s: (pw_s(x), 0), and 0 where x is not finite
+__global__ void __launch_bounds__(256)
+    imager_spectral_vis_kernel(int64_t n, const double *__restrict__ x, int s, double2 *__restrict__ out)
+{
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const double xk = x[k];
+        out[k] = make_double2(isfinite(xk) ? spectral_power(xk, s) : 0.0, 0.0);
+    }
+}
+
+// r = vis - sum_q pw_q(x) * predict(models[q]), one prediction at a time, q ascending: FIRST starts r from vis, the later
+// ones take their term from r.  A visibility whose x is not finite predicts 0 (selected out: pred may be anything).
+template <bool FIRST>
+__global__ void __launch_bounds__(256)
+    imager_mfs_sub_kernel(int64_t n, const double2 *__restrict__ vis, const double2 *__restrict__ pred,
+                          const double *__restrict__ x, int q, double2 *__restrict__ r)
+{
+#pragma clang fp contract(off)
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        double2 v = FIRST ? vis[k] : r[k];
+        const double xk = x[k];
+        if (isfinite(xk)) {
+            const double pw = spectral_power(xk, q);
+            const double2 p = pred[k];
+            v = make_double2(v.x - pw * p.x, v.y - pw * p.y);
+        }
+        r[k] = v;
+    }
+}
+
+// The pass of term t over the residual visibilities r (imager_middle_kernel's, with the power in front): vis_res = r
+// when asked; pw_t(x) * r, conjugated where mirrored, times the weight, into the gridder's input; 0 where the weight is 0
+// or x is not finite.  vis_res may be r's own block (the caller's vis): no __restrict__ on either.
+__global__ void __launch_bounds__(256)
+    imager_mfs_term_kernel(int64_t n, const double2 *r, const double *__restrict__ x, const double *__restrict__ sw, int t,
+                           double2 *__restrict__ pred, double2 *vis_res)
+{
+#pragma clang fp contract(off)
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        double2 v = r[k];
+        if (vis_res) vis_res[k] = v;
+        const double xk = x[k], s = sw[k];
+        const double a = fabs(s), pw = spectral_power(xk, t);
+        v = make_double2(pw * v.x, pw * v.y);
+        if (signbit(s)) v.y = -v.y;
+        pred[k] = (a == 0.0 || !isfinite(xk)) ? make_double2(0.0, 0.0) : make_double2(a * v.x, a * v.y);
+    }
+}
+
 }  // namespace gridhip
 
 using namespace gridhip;
@@ -142,6 +204,13 @@ struct gridhip_imager {
     double *wstats = nullptr;       // the weighting's stats (8 doubles), written at creation
     void *noise_scratch = nullptr;  // image_stats' state block and tables (noise.hip), made by the first image_stats
     double *istats = nullptr;       // the image stats of a deconvolve_auto that does not return them (8 doubles)
+    // wide-band imaging, made by set_spectral: the number of Taylor terms (0: none), x per visibility, the residual
+    // visibilities of an mfs_cycle, the 2T - 1 spectral PSFs, and mfclean's state block and tile table (mfclean.hip)
+    int64_t sp_T = 0;
+    double *sp_x = nullptr;
+    double2 *sp_r = nullptr;
+    double *sp_psfs = nullptr;
+    void *mf_scratch = nullptr;
 };
 
 namespace {
@@ -564,6 +633,128 @@ int gridhip_imager_deconvolve_dev(gridhip_imager *im, const double *vis, double 
                                           stats ? stats + 4 * c : nullptr));
     }
     return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
+}
+
+// ---- wide-band imaging ---------------------------------------------------------------------------------------------------
+// hands a block of the imager's back (hipFree waits for the work that uses it)
+static void disown(gridhip_imager *im, void *q)
+{
+    if (!q) return;
+    for (void *&p : im->owned)
+        if (p == q) p = nullptr;
+    (void)hipFree(q);
+}
+
+int gridhip_imager_set_spectral_dev(gridhip_imager *im, int64_t T, const double *x)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (T < 1 || T > MF_MAX_TERMS || (im->n > 0 && !x)) return fail(ctx, GRIDHIP_EINVAL, "set_spectral: bad argument");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const int64_t n = im->n, cells = im->N * im->N;
+    if (T > im->sp_T) {  // (the first call, or more terms than before)
+        disown(im, im->sp_psfs);
+        im->sp_psfs = nullptr;
+        im->sp_T = 0;
+        GH_CHECK(own(im, &im->sp_psfs, (size_t)(2 * T - 1) * cells * 8));
+    }
+    im->sp_T = 0;  // (a call that fails half way leaves an imager without terms)
+    if (!im->sp_x) GH_CHECK(own(im, &im->sp_x, (size_t)n * 8));
+    if (!im->sp_r) GH_CHECK(own(im, &im->sp_r, (size_t)n * 16));
+    GH_CHECK(copy_in(ctx, im->sp_x, x, (size_t)n * 8, true));
+    // P_s = the image of cycle(NULL, (pw_s(x), 0)): the weighted PSF pass with x^s, divided by the stored pmax
+    for (int64_t s = 0; s < 2 * T - 1; ++s) {
+        if (n > 0) {
+            hipLaunchKernelGGL(imager_spectral_vis_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, im->sp_x, (int)s,
+                               im->sp_r);
+            GH_CHECK_HIP(ctx, hipGetLastError());
+        }
+        GH_CHECK(gridhip_imager_cycle_dev(im, nullptr, (const double *)im->sp_r, im->sp_psfs + s * cells, nullptr));
+    }
+    GH_CHECK(sync(ctx));  // x may be freed or overwritten once this returns
+    im->sp_T = T;
+    return GRIDHIP_OK;
+}
+
+int gridhip_imager_spectral_psfs_dev(gridhip_imager *im, double *psfs)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (!im->sp_T || !psfs) return fail(ctx, GRIDHIP_EINVAL, "spectral_psfs: no spectral terms, or a null pointer");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return copy_out(ctx, psfs, im->sp_psfs, (size_t)(2 * im->sp_T - 1) * im->N * im->N * 8, true);
+}
+
+int gridhip_imager_mfs_cycle_dev(gridhip_imager *im, const double *models, const double *vis, double *images,
+                                 double *vis_res)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    const int64_t n = im->n, cells = im->N * im->N, T = im->sp_T;
+    if (!T) return fail(ctx, GRIDHIP_EINVAL, "mfs_cycle: the imager has no spectral terms (set_spectral)");
+    if (!images || (n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (n == 0) {
+        hipLaunchKernelGGL(imager_zero_kernel, grid_for(ctx, T * cells / 2), dim3(256), 0, ctx->stream, T * cells, images);
+        GH_CHECK_HIP(ctx, hipGetLastError());
+        return GRIDHIP_OK;
+    }
+    mark(ctx, 0);
+    const double2 *r = (const double2 *)vis;
+    if (models) {
+        for (int64_t q = 0; q < T; ++q) {
+            GH_CHECK(gather(im, models + q * cells));
+            if (q == 0)
+                hipLaunchKernelGGL(imager_mfs_sub_kernel<true>, grid_for(ctx, n), dim3(256), 0, ctx->stream, n,
+                                   (const double2 *)vis, (const double2 *)im->pred, (const double *)im->sp_x, (int)q, im->sp_r);
+            else
+                hipLaunchKernelGGL(imager_mfs_sub_kernel<false>, grid_for(ctx, n), dim3(256), 0, ctx->stream, n,
+                                   (const double2 *)vis, (const double2 *)im->pred, (const double *)im->sp_x, (int)q, im->sp_r);
+            GH_CHECK_HIP(ctx, hipGetLastError());
+        }
+        r = im->sp_r;
+    }
+    mark(ctx, 1);
+    for (int64_t t = 0; t < T; ++t) {
+        hipLaunchKernelGGL(imager_mfs_term_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, r,
+                           (const double *)im->sp_x, (const double *)im->sw, (int)t, im->pred,
+                           t == 0 ? (double2 *)vis_res : (double2 *)nullptr);
+        GH_CHECK_HIP(ctx, hipGetLastError());
+        GH_CHECK(scatter(im));
+        GH_CHECK(image_tail(ctx, im->N, im->g, im->f, images + t * cells, nullptr, im->pmaxbits, im->fft));
+    }
+    mark(ctx, 2);
+    return GRIDHIP_OK;
+}
+
+int gridhip_imager_mfclean_dev(gridhip_imager *im, double *residuals, double *models, double gain, double threshold,
+                               int64_t niter, int64_t border, int64_t patch, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (!im->sp_T) return fail(ctx, GRIDHIP_EINVAL, "mfclean: the imager has no spectral terms (set_spectral)");
+    GH_CHECK(mfclean_check(ctx, im->N, im->sp_T, im->sp_psfs, residuals, models, gain, threshold, niter, border, patch));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!im->mf_scratch) GH_CHECK(own(im, &im->mf_scratch, mfclean_scratch_bytes(im->N)));
+    return mfclean_run(ctx, im->N, im->sp_T, im->sp_psfs, residuals, models, gain, threshold, niter, border, patch, stats,
+                       im->mf_scratch);
+}
+
+int gridhip_imager_mfdeconvolve_dev(gridhip_imager *im, const double *vis, double *models, double *images, int64_t nmajor,
+                                    double gain, double threshold, int64_t niter, int64_t border, int64_t patch,
+                                    double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (!im->sp_T) return fail(ctx, GRIDHIP_EINVAL, "mfdeconvolve: the imager has no spectral terms (set_spectral)");
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "mfdeconvolve: bad argument");
+    GH_CHECK(mfclean_check(ctx, im->N, im->sp_T, im->sp_psfs, images, models, gain, threshold, niter, border, patch));
+    for (int64_t c = 0; c < nmajor; ++c) {
+        GH_CHECK(gridhip_imager_mfs_cycle_dev(im, models, vis, images, nullptr));
+        GH_CHECK(gridhip_imager_mfclean_dev(im, images, models, gain, threshold, niter, border, patch,
+                                            stats ? stats + 8 * c : nullptr));
+    }
+    return gridhip_imager_mfs_cycle_dev(im, models, vis, images, nullptr);
 }
 
 static int imager_msclean(gridhip_imager *im, double *residual, double *model, int64_t S, const double *scales,

@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, noise.hip, restore.hip).
+// msclean.hip, mfclean.hip, noise.hip, restore.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -340,6 +340,17 @@ size_t msclean_scratch_bytes(int64_t N, int64_t S);
 int msclean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, int64_t S,
                 const double *scales, const double *bias, double gain, double threshold, int64_t niter, int64_t border,
                 int64_t patch, double *stats, void *scratch, bool setup, const CleanAuto &au = CleanAuto{});
+
+// ---- multi-term CLEAN (mfclean.hip) -----------------------------------------------------------------------------------------
+constexpr int MF_MAX_TERMS = 4;
+// gridhip_mfclean's argument rules: T in 1 .. 4, then clean's, then no two of the 4T - 1 planes overlapping (GRIDHIP_EINVAL)
+int mfclean_check(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, const double *residuals,
+                  const double *models, double gain, double threshold, int64_t niter, int64_t border, int64_t patch);
+// the state block and the tile table of an N x N multi-term clean, the same for every T
+size_t mfclean_scratch_bytes(int64_t N);
+// gridhip_mfclean_dev on checked arguments: kernels only, on ctx->stream; scratch: mfclean_scratch_bytes(N)
+int mfclean_run(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, double *residuals, double *models,
+                double gain, double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
 
 // The stop level of an _auto call, by the first pick kernel: T = max(threshold, nsigma * sigma, peak_frac * |p1|), each
 // product rounded once, a term whose factor is 0 left out (noise is then not read); p1 is NaN when nothing can be

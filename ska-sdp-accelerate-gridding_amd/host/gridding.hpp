@@ -13,6 +13,7 @@
 //   predict / predict_aw: the way back, model image -> visibilities (absent from the reference)
 //   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
 //   msclean: multi-scale CLEAN, clean with components of several scales (absent from the reference)
+//   mfclean: multi-term CLEAN, the minor cycle of wide-band imaging over T Taylor terms (absent from the reference)
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
@@ -312,6 +313,27 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
                               scales.data(), bias.data(), gain, threshold, niter, border, patch, st));
         MsCleanStats out = {st[0], st[1], st[2], st[3], st[4], {st[6], st[7], st[8], st[9], st[10], st[11]}};
         return out;
+    }
+
+    // ---- multi-term CLEAN (gridhip_mfclean; include/gridhip.h, "wide-band imaging") ----
+    // T Taylor terms, 1 <= T <= 4, as stacks of N x N planes: images [T][N][N] become the residuals and models [T][N][N]
+    // are accumulated into, both in place; psfs holds the 2T - 1 spectral PSFs.  reason: 0 niter components taken,
+    // 1 |peak| <= threshold, 2 nothing selectable, 3 singular Hessian.
+    struct MfCleanStats {
+        F iterations, peak, index;
+        F flux[4];
+        F reason;
+    };
+    MfCleanStats mfclean(Int N, Int T, std::vector<F> &images, const std::vector<F> &psfs, std::vector<F> &models,
+                         F gain = 0.1, F threshold = 0.0, Int niter = 100, Int border = 0, Int patch = 0)
+    {
+        if (N < 1 || T < 1 || T > 4 || (Int)images.size() != T * N * N || (Int)models.size() != T * N * N ||
+            (Int)psfs.size() != (2 * T - 1) * N * N)
+            throw Error(GRIDHIP_EINVAL, "mfclean: images and models must be T x N x N, psfs (2T - 1) x N x N, T in 1 .. 4");
+        F st[8] = {0};
+        check(gridhip_mfclean(ctx_, N, T, psfs.data(), images.data(), models.data(), gain, threshold, niter, border, patch,
+                              st));
+        return {st[0], st[1], st[2], {st[3], st[4], st[5], st[6]}, st[7]};
     }
 
     // ---- image statistics, masks and noise-based stop levels (gridhip_image_stats, gridhip_clean_auto,

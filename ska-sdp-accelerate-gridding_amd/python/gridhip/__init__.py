@@ -442,6 +442,29 @@ class Context(Handle):
         del keep
         return model, image, stats
 
+    def mfclean(self, images, psfs, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, models=None):
+        """Multi-term CLEAN of the T residual images `images` ([T, N, N] float64, 1 <= T <= 4) with the 2T - 1 spectral
+        PSFs `psfs` ([2T - 1, N, N]) (gridhip_mfclean[_dev]; include/gridhip.h, "wide-band imaging"): at most niter
+        components, each the T Taylor coefficients at the cell with the largest Hessian-weighted score, searched inside
+        `border`, stopping at |a_0| <= threshold; region and patch as for clean.  `images` is UPDATED IN PLACE and
+        returned as the residuals; `models` ([T, N, N], zeros when None) is accumulated into.  Returns (models,
+        residuals, stats); stats = [iterations, a_0 at the final peak, its flat index, flux_0 .. flux_3, reason] with
+        reason 0 niter taken, 1 threshold, 2 nothing selectable, 3 singular Hessian.  numpy arrays take the synchronous
+        host form; torch cuda tensors the asynchronous one on torch's stream, with stats a cuda tensor."""
+        be = backend(images)
+        shape = tuple(getattr(images, "shape", ()))
+        if len(shape) != 3 or shape[1] != shape[2] or not 1 <= shape[0] <= 4:
+            raise ValueError("images must be T x N x N with T in 1 .. 4")
+        T, N = shape[0], shape[1]
+        images = in_place(be, images, shape, "images")
+        psfs = be.cv(psfs, be.f64)
+        if tuple(psfs.shape) != (2 * T - 1, N, N):
+            raise ValueError(f"psfs must be {(2 * T - 1, N, N)}: the 2T - 1 spectral PSFs")
+        models = in_place(be, models, shape, "models", images)
+        stats = be.empty(8, be.f64, images)
+        self._call(be, "mfclean", N, T, psfs, images, models, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return models, images, stats
+
     def fit_beam(self, psf, window=8, cut=0.5):
         """The restoring beam of the N x N `psf` (gridhip_fit_beam[_dev]; include/gridhip.h, "restoring beam and
         restore"): an elliptical Gaussian fitted to the main lobe over the cells within `window` of the centre that
@@ -609,6 +632,7 @@ class Imager(_Bound):
         super().__init__(ctx, handle, n)
         self.N, self.device = N, device
         self._psf = None
+        self.nterms = 0  # the Taylor terms of set_spectral (0: none)
 
     @staticmethod
     def _ok(t, dt, shape, what):
@@ -767,6 +791,90 @@ class Imager(_Bound):
                    *clean_scalars(gain, threshold, niter, border, patch), stats)
         del keep
         return model, out, stats
+
+    # -- wide-band imaging (include/gridhip.h, "wide-band imaging") -------------------------------------------------------
+    def _terms(self, *stacks):
+        """T of the stacks a wide-band call takes: set_spectral's, or - on an imager without terms, which the library
+        then refuses - that of the first stack given (1 when there is none)"""
+        for t in stacks:
+            if self.nterms == 0 and t is not None and len(getattr(t, "shape", ())) == 3:
+                return int(t.shape[0])
+        return self.nterms or 1
+
+    def set_spectral(self, x, nterms=2):
+        """Give the imager `nterms` Taylor terms (1 to 4; gridhip_imager_set_spectral_dev): x holds (nu_k - nu_0) / nu_0
+        per visibility (n cuda float64 values in the order of vis; copied).  A visibility whose x is not finite is
+        treated as flagged.  Builds and keeps the 2 nterms - 1 spectral PSFs; may synchronise, as creation does."""
+        self._open()
+        be = device()
+        if not 1 <= int(nterms) <= 4:
+            raise ValueError("nterms must be 1 to 4")
+        if not is_torch(x):
+            raise ValueError("x must be a cuda tensor")
+        x = be.cv(x, be.f64)
+        if tuple(x.shape) != (self.n,):
+            raise ValueError(f"x must hold one value per visibility ({self.n}), not {tuple(x.shape)}")
+        self.nterms = 0
+        self._call(be, "imager_set_spectral", int(nterms), x)
+        self.nterms = int(nterms)
+
+    def spectral_psfs(self):
+        """The 2T - 1 spectral PSFs set_spectral built ([2T - 1, N, N] cuda float64; [0] is the imager's own PSF)"""
+        self._open()
+        be = device()
+        out = be.empty((2 * self._terms() - 1, self.N, self.N), be.f64, self.device)
+        self._call(be, "imager_spectral_psfs", out)
+        return out
+
+    def mfs_cycle(self, vis, models=None, out=None, vis_res=None):
+        """One wide-band major-cycle step (gridhip_imager_mfs_cycle_dev): with r = vis - sum_q x^q predict(models[q])
+        (r = vis without models), out[t] = cycle(x^t r) for the T terms.  models and out are [T, N, N] cuda float64 (out:
+        a new one when None); vis_res (length n, may be vis itself) receives r.  Asynchronous on torch's stream."""
+        self._open()
+        be = device()
+        TNN = (self._terms(models, out), self.N, self.N)
+        self._ok(vis, be.c128, (self.n,), "vis")
+        if models is not None:
+            self._ok(models, be.f64, TNN, "models")
+        if vis_res is not None:
+            self._ok(vis_res, be.c128, (self.n,), "vis_res")
+        if out is None:
+            out = be.empty(TNN, be.f64, self.device)
+        else:
+            self._ok(out, be.f64, TNN, "out")
+        self._call(be, "imager_mfs_cycle", models, vis, out, vis_res)
+        return out
+
+    def mfclean(self, images, models=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+        """Context.mfclean with the imager's own spectral PSFs (gridhip_imager_mfclean_dev): `images` ([T, N, N] cuda
+        float64, an mfs_cycle's output) is updated in place and returned as the residuals, `models` (zeros when None) is
+        accumulated into.  Returns (models, residuals, stats[8]); asynchronous, and capturable after a first call."""
+        self._open()
+        be = device()
+        TNN = (self._terms(images, models), self.N, self.N)
+        images = in_place(be, images, TNN, "images")
+        models = in_place(be, models, TNN, "models", self.device)
+        stats = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_mfclean", images, models, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return models, images, stats
+
+    def mfdeconvolve(self, vis, nmajor, models=None, out=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0):
+        """Visibilities to T model images in one asynchronous call (gridhip_imager_mfdeconvolve_dev): nmajor times
+        images = mfs_cycle(vis, models) then mfclean(images, models), and one closing mfs_cycle.  models (zeros when
+        None) is accumulated into, out (new when None) receives the closing residual images.  Returns (models, images,
+        stats[nmajor, 8])."""
+        self._open()
+        be = device()
+        TNN = (self._terms(models, out), self.N, self.N)
+        self._ok(vis, be.c128, (self.n,), "vis")
+        models = in_place(be, models, TNN, "models", self.device)
+        out = be.empty(TNN, be.f64, self.device) if out is None else in_place(be, out, TNN, "out")
+        if int(nmajor) < 0:
+            raise ValueError("nmajor must be >= 0")
+        stats = be.empty((int(nmajor), 8), be.f64, self.device)
+        self._call(be, "imager_mfdeconvolve", vis, models, out, int(nmajor),
+                   *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return models, out, stats
 
     def weight_stats(self):
         """The stats of the weighting the imager was created with (gridhip_imager_weight_stats_dev): Context.weights'

@@ -34,6 +34,7 @@ _AW_GRIDDING = [vp, C.c_double, i64, C.c_double, i64, i64, i64, i64, vp, vp, vp,
                 C.POINTER(C.c_double)]
 _PREDICT = [vp, ci, i64, i64, i64, i64, i64, vp, C.c_double, i64, vp, i64, vp, vp, vp, i64, vp, vp]
 _CLEAN = [vp, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
+_MFCLEAN = [vp, i64, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]
 _HOST_F64 = C.POINTER(C.c_double)  # an array that is the host's in every form (msclean's scales and bias)
 _MSCLEAN = [vp, i64, vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double, i64, i64, i64, vp]
 _AUTO = [vp, C.c_double, vp, C.c_double]  # mask, nsigma, noise, peak_frac (the _auto forms, before stats)
@@ -149,6 +150,13 @@ SIGNATURES = {
     "gridhip_imager_create_aw_weighted_dev": (ci, [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp,
                                                    i64, vp, vp, *_WEIGHTING, C.POINTER(vp)]),
     "gridhip_imager_weight_stats_dev": (ci, [vp, vp]),
+    "gridhip_mfclean": (ci, _MFCLEAN),
+    "gridhip_mfclean_dev": (ci, _MFCLEAN),
+    "gridhip_imager_set_spectral_dev": (ci, [vp, i64, vp]),
+    "gridhip_imager_spectral_psfs_dev": (ci, [vp, vp]),
+    "gridhip_imager_mfs_cycle_dev": (ci, [vp, vp, vp, vp, vp]),
+    "gridhip_imager_mfclean_dev": (ci, [vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]),
+    "gridhip_imager_mfdeconvolve_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),
