@@ -95,6 +95,14 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               coarse bin = 2^coarse_shift (0 = balanced); scatter_chunk = 4096: half-size chunks, two work-groups
  *               per CU; count_unroll = 4: four visibilities per thread and trip in the counting sweep, 1: one, and
  *               no 16-byte grid-stride form either (0 = auto)
+ *   "bin_reuse" 0 = auto: a convgrid2 / degrid2 call whose geometry, n, stride, u / v / wbin pointers and pre-pass options
+ *               equal the previous call's, with no other pre-pass on the context in between, first verifies in one
+ *               read-only sweep that every visibility still falls into the same bin, cell and kernel slice, and if so
+ *               keeps the previous call's binned records instead of running the two scatter levels (the values may
+ *               change freely; results are those of a full pre-pass either way; after a failed attempt the next 4
+ *               calls do not try); 1 = never.  A call made while the stream is being captured into a graph neither
+ *               verifies nor leaves anything to reuse, and a replay of such a graph marks the device so that the
+ *               next call after it runs its pre-pass in full
  *   "aw_cache"  aw gridders: 1 (default) = build each distinct (a1, a2, wbin, yf, xf) kernel once per call and let
  *               the visibilities that share it reuse it; 0 = one kernel per visibility (as the reference evaluates)
  *   "fault_inject"  TEST HOOK: hides the last k slots of the record array from the pre-pass's scatter so that its
@@ -123,8 +131,10 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               100 + t: widen the record's kernel-slice field until its fields take t <= 64 bits
  *   ("dbg", the ablation / profiling switch of tuning runs, exists only in the tuning build of the library,
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
- * Read-only (gridhip_get_option): "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last
- * convgrid / convgrid2 / degrid2 call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
+ * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
+ * "prepass_reused" = those of them that kept their records (counted on the device: reading it synchronises the stream);
+ * "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last convgrid / convgrid2 / degrid2
+ * call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
  * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or
  * aw plan or aw imager creation built (0 after an aw plan pass or an imager's cycle);
  * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan / awdegrid / aw plan pass call used:

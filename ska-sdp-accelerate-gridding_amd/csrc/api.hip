@@ -238,7 +238,7 @@ int gridhip_convgrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid,
     mark(ctx, 0);
     const double *tk = gcf;
     GH_CHECK(tile_kernels(ctx, p, gcf, &tk));
-    GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin));
+    GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, nullptr, true));
     mark(ctx, 1);
     if (n > 0) {
         if (p.sorted)
@@ -286,7 +286,7 @@ int gridhip_degrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *g
     if (n > 0 && parts) GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out, 0, (size_t)n * 16, ctx->stream));
     const double *tk = gcf;
     GH_CHECK(tile_kernels(ctx, p, gcf, &tk));
-    GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, parts ? nullptr : reinterpret_cast<double2 *>(vis_out)));
+    GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, parts ? nullptr : reinterpret_cast<double2 *>(vis_out), true));
     mark(ctx, 1);
     if (n > 0) {
         if (p.sorted)  // the sorted kernel's degrid mode reads `grid` and writes the vis array

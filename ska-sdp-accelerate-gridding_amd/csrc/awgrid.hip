@@ -626,6 +626,7 @@ static int aw_bin(gridhip_ctx *ctx, const AwCall &c, const Geom &g, int64_t lo, 
     if (rb > ctx->num_cu * 8) rb = ctx->num_cu * 8;
     hipLaunchKernelGGL(aw_relabel_kernel, dim3((unsigned)rb), dim3(256), 0, ctx->stream, g, (RecWord *)ctx->recs.ptr,
                        t.bin_start + g.nbins, c.kid, (int32_t)m);
+    ++ctx->bin_gen;  // (the records are rewritten after their pre-pass)
     return GRIDHIP_OK;
 }
 

@@ -29,9 +29,28 @@
 // changes which records are produced, never where they are written); every record store is bounds-checked
 // against the array all the same and violations are counted (option "errors").
 //
+// Reuse.  Everything the gridder takes from (u, v, wbin) is in the pre-records, and in real use the coordinates stay
+// the same from call to call while the values change (image then PSF, degrid then grid, every major cycle).  A plain
+// convgrid2 / degrid2 call whose key - geometry, n, stride, the three pointers, the pre-pass options, the scratch
+// blocks and the generation of the tables (gridhip_ctx::bin_gen: every pre-pass and every other writer of the records
+// counts there) - equals the one the pre-records in recs_raw were written under first runs
+//   clear       : every pre-pass's first kernel, captured or not, one-level or two-level, stamps its generation into
+//                 d_scalars[SC_GEN]; before it does, it arms the device word `match` to 1 only if the stamp it finds
+//                 is the kept generation.  A replay of a graph captured earlier never enters the library, but it
+//                 stamps its capture-time generation, which no kept state carries: the call after it runs in full
+//   bin_verify  : one read-only sweep that derives every pre-record again and compares it with the kept one; a
+//                 work-group that meets a difference clears `match`
+// and then enqueues the usual kernels, each of which returns at once while `match` is 1: the records, bin_start and
+// work_start in the context are then the ones a fresh pre-pass would write.  The host never waits for the verdict; the
+// last kernel copies it into a mapped host word that the NEXT call reads, unsynchronised, to stop verifying a stream
+// whose contents change under the same pointers (4 calls' pause after a failure).
+//
 // Coordinates follow frac_coords / convgrid2 of src/Gridding.hs:126-151,212-218: the footprint origin is
 // (x - gw/2, y - gh/2); a visibility none of whose taps can land inside the grid is dropped here (fixoutofbounds
 // would drop every one of its taps, :883-891).
+#include <stddef.h>
+#include <string.h>
+
 #include "tile_common.h"
 
 namespace gridhip {
@@ -144,6 +163,30 @@ __device__ __forceinline__ BinOut pre_unpack(const PreFmt f, unsigned long long 
     return b;
 }
 
+// Two consecutive visibilities of a unit-stride stream in 16-byte accesses (k0 even, arrays 16-byte aligned; `two`:
+// k0 + 1 exists) and their bins: the counting sweep's and the verify sweep's one way from coordinates to BinOut.
+__device__ __forceinline__ void vis_bin_pair(const Geom &g, const double *__restrict__ u, const double *__restrict__ v,
+                                             const int64_t *__restrict__ wbin, int64_t k0, bool two, BinOut *b0, BinOut *b1)
+{
+    double2 pu, pv;
+    longlong2 wb = make_longlong2(0, 0);
+    if (two) {
+        pu = *reinterpret_cast<const double2 *>(u + k0);
+        pv = *reinterpret_cast<const double2 *>(v + k0);
+        if (wbin) wb = *reinterpret_cast<const longlong2 *>(wbin + k0);
+    } else {
+        pu = make_double2(u[k0], 0.0);
+        pv = make_double2(v[k0], 0.0);
+        if (wbin) wb.x = wbin[k0];
+    }
+    *b0 = vis_bin(g, pu.x, pv.x, wb.x, k0, 0);
+    *b1 = vis_bin(g, pu.y, pv.y, wb.y, k0 + 1, 0);
+    if (!two) b1->bin = -1;
+}
+
+// `match` of the kernels below: null, or the verify sweep's verdict - 1: the kept records stand, return at once
+__device__ __forceinline__ bool records_stand(const int32_t *match) { return match && *match == 1; }
+
 // ---- records between the two scatter levels -------------------------------------------------------
 // FMT 8: the final 8-byte word with, in the bits above its fields (from bit ob + kb + 14), the bin's index inside its
 // coarse bin (bin & (2^shift - 1)); which coarse bin follows from where the record lies in the coarse-ordered array.
@@ -201,8 +244,9 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
                                                          int32_t *__restrict__ block_hist,
                                                          int32_t *__restrict__ scalars, int bin_lo, int bin_hi,
                                                          PreFmt pf, unsigned long long *__restrict__ pre,
-                                                         double2 *__restrict__ zero_out)
+                                                         double2 *__restrict__ zero_out, const int32_t *match)
 {
+    if (records_stand(match)) return;
     // LDS_HIST: this launch handles the bins [bin_lo, bin_hi) only (a window that fits in LDS); grids
     // with more bins than that are covered by several launches.  pre != null: the first window's launch leaves
     // the pre-record of every visibility, the others (pf.bin_bits < 0) count from those.
@@ -235,20 +279,8 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
         hi = n;
         for (int64_t k0 = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); k0 < hi; k0 += 2 * (int64_t)gridDim.x * blockDim.x) {
             const bool two = k0 + 1 < hi;
-            double2 pu, pv;
-            longlong2 wb = make_longlong2(0, 0);
-            if (two) {
-                pu = *reinterpret_cast<const double2 *>(u + k0);
-                pv = *reinterpret_cast<const double2 *>(v + k0);
-                if (wbin) wb = *reinterpret_cast<const longlong2 *>(wbin + k0);
-            } else {
-                pu = make_double2(u[k0], 0.0);
-                pv = make_double2(v[k0], 0.0);
-                if (wbin) wb.x = wbin[k0];
-            }
-            const BinOut b0 = vis_bin(g, pu.x, pv.x, wb.x, k0, 0);
-            BinOut b1 = vis_bin(g, pu.y, pv.y, wb.y, k0 + 1, 0);
-            if (!two) b1.bin = -1;
+            BinOut b0, b1;
+            vis_bin_pair(g, u, v, wbin, k0, two, &b0, &b1);
             if (pre) {
                 if (two)
                     *reinterpret_cast<ulonglong2 *>(pre + k0) = make_ulonglong2(pre_pack(rf, b0), pre_pack(rf, b1));
@@ -325,6 +357,68 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
     }
 }
 
+// The verify sweep ("Reuse" at the top): the counting sweep without histogram and without stores - every pre-record
+// derived again (vis_bin, pre_pack: the same code) and compared with the kept one.  Grid-stride like the V2 counting
+// sweep; every POLL trips a wave that met a difference clears `flags[0]` (one lane's store) and leaves, and the
+// others leave once they see it cleared.  What the skipped counting sweep would have done besides is done here: the
+// dropped visibilities are counted (flags[1]; the last pre-pass kernel makes it the call's count if the records
+// stand) and a degrid's zero predictions for them are written (rare stores, outside the common path).
+template <bool V2>
+__global__ void __launch_bounds__(1024) bin_verify_kernel(Geom g, int64_t n, const double *__restrict__ u,
+                                                          const double *__restrict__ v, int64_t stride,
+                                                          const int64_t *__restrict__ wbin, PreFmt pf,
+                                                          const unsigned long long *__restrict__ pre,
+                                                          double2 *__restrict__ zero_out, int32_t *flags)
+{
+    constexpr int POLL = 8;
+    bool diff = false;
+    int dropped = 0, trip = 0;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, tstep = (int64_t)gridDim.x * blockDim.x;
+    // (the clear kernel disarms the verdict itself when the device's stamp is not the kept generation)
+    if (__hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+    // true: this wave is done (a difference, here or elsewhere)
+    auto settled = [&]() {
+        if (__ballot(diff)) {
+            if ((threadIdx.x & 63) == 0) __hip_atomic_store(flags, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return true;
+        }
+        return __hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+    };
+    if (V2) {
+        for (int64_t k0 = 2 * t0; k0 < n; k0 += 2 * tstep) {
+            const bool two = k0 + 1 < n;
+            ulonglong2 kept;
+            if (two)
+                kept = *reinterpret_cast<const ulonglong2 *>(pre + k0);
+            else
+                kept = make_ulonglong2(pre[k0], ~0ull);
+            BinOut b0, b1;
+            vis_bin_pair(g, u, v, wbin, k0, two, &b0, &b1);
+            diff |= pre_pack(pf, b0) != kept.x || pre_pack(pf, b1) != kept.y;
+            dropped += (b0.bin == -2) + (b1.bin == -2);
+            if (zero_out) {
+                if (b0.bin < 0) zero_out[k0] = make_double2(0.0, 0.0);
+                if (two && b1.bin < 0) zero_out[k0 + 1] = make_double2(0.0, 0.0);
+            }
+            if (++trip % POLL == 0 && settled()) return;
+        }
+    } else {
+        for (int64_t e = t0; e < n; e += tstep) {
+            int64_t k;
+            int part;
+            elem_of(g, e, &k, &part);
+            const unsigned long long kept = pre[e];
+            const BinOut b = vis_bin(g, u[k * stride], v[k * stride], wbin ? wbin[k] : 0, k, part);
+            diff |= pre_pack(pf, b) != kept;
+            dropped += b.bin == -2;
+            if (zero_out && b.bin < 0) zero_out[k] = make_double2(0.0, 0.0);
+            if (++trip % POLL == 0 && settled()) return;
+        }
+    }
+    if (settled()) return;
+    if (dropped) atomicAdd(&flags[1], dropped);
+}
+
 // block_hist[b][bin] (count) -> first slot of block b inside bin: bin_start[bin] + counts of the
 // blocks before it.  One thread per bin, coalesced across bins.
 __global__ void __launch_bounds__(256) bin_offsets_kernel(int nbins, int nblocks, const int32_t *__restrict__ bin_start,
@@ -385,9 +479,10 @@ template <int NT>
 __global__ void __launch_bounds__(NT) bin_scan_kernel(Geom g, const int32_t *__restrict__ bin_count,
                                                         int32_t *__restrict__ bin_start,
                                                         int32_t *__restrict__ work_start,
-                                                        int32_t *__restrict__ cursor)
+                                                        int32_t *__restrict__ cursor, const int32_t *match)
 {
     __shared__ int32_t wtot[16];
+    if (records_stand(match)) return;
     const int tid = threadIdx.x;
     const bool starts = (int)blockIdx.x < SCAN_SEGS;  // (uniform per work-group)
     const int grp = (int)blockIdx.x - SCAN_SEGS;
@@ -542,8 +637,10 @@ __global__ void __launch_bounds__(NT, 4) coarse_scatter_kernel(Geom g, int64_t n
                                                                int32_t *__restrict__ ccur, int shift, int ncoarse,
                                                                void *__restrict__ tmp_,
                                                                const unsigned long long *__restrict__ pre, PreFmt pf,
-                                                               int32_t cap, int32_t *__restrict__ scalars)
+                                                               int32_t cap, int32_t *__restrict__ scalars,
+                                                               const int32_t *match)
 {
+    if (records_stand(match)) return;
     using Tmp = TmpRec<FMT != 16>;
     constexpr int RW = FMT == 8 ? 2 : (int)sizeof(Tmp) / 4;  // 32-bit words per staged record
     extern __shared__ int32_t smem[];
@@ -671,8 +768,22 @@ __global__ void __launch_bounds__(NT, 4) fine_scatter_kernel(Geom g, const int32
                                                              int32_t *__restrict__ cursor, int shift, int ncoarse,
                                                              const void *__restrict__ tmp_,
                                                              RecWord *__restrict__ out, int32_t cap,
-                                                             int32_t *__restrict__ scalars)
+                                                             int32_t *__restrict__ scalars, const int32_t *match,
+                                                             int32_t *host_flag)
 {
+    // the pre-pass's last kernel: after a verify sweep it hands the verdict to the host (a mapped word the next call
+    // reads without waiting) and, where the records stand, makes the sweep's count of dropped visibilities the call's
+    if (match) {
+        const bool stand = *match == 1;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            *host_flag = stand ? 1 : 0;
+            if (stand) {
+                scalars[0] = scalars[SC_VDROPPED];
+                scalars[SC_REUSED] += 1;
+            }
+        }
+        if (stand) return;
+    }
     using Rec = FineRec<FMT>;
     constexpr int RW = (int)sizeof(Rec) / 4;
     extern __shared__ int32_t smem[];
@@ -844,7 +955,7 @@ __global__ void __launch_bounds__(NT, 4) fine_scatter_kernel(Geom g, const int32
 template <bool FROM_PRE, int FMT, int NT, int CHUNK>
 static int launch_two_level(gridhip_ctx *ctx, const Geom &g, const Tables &t, int64_t n, const double *u, const double *v,
                             int64_t uv_stride, const int64_t *wbin, int shift, int ncoarse, int cblocks,
-                            const unsigned long long *pre, PreFmt pf, int32_t cap)
+                            const unsigned long long *pre, PreFmt pf, int32_t cap, const int32_t *match)
 {
     const size_t rec_bytes = FMT;
     const size_t coarse_lds = (size_t)CHUNK * (rec_bytes + (FMT == 8 ? 2 : 0)) + (size_t)(2 * ncoarse + 32) * sizeof(int32_t);
@@ -860,15 +971,16 @@ static int launch_two_level(gridhip_ctx *ctx, const Geom &g, const Tables &t, in
     int32_t *ccur = (int32_t *)ctx->blockhist.ptr;
     void *tmp = ctx->recs_tmp.ptr;
     hipLaunchKernelGGL(coarse, dim3(cblocks), dim3(NT), coarse_lds, ctx->stream, g, n, u, v, uv_stride, wbin, t.bin_start,
-                       ccur, shift, ncoarse, tmp, pre, pf, cap, t.scalars);
+                       ccur, shift, ncoarse, tmp, pre, pf, cap, t.scalars, match);
     hipLaunchKernelGGL(fine, dim3(cblocks), dim3(NT), fine_lds, ctx->stream, g, t.bin_start, t.cursor, shift, ncoarse,
-                       (const void *)tmp, (RecWord *)ctx->recs.ptr, cap, t.scalars);
+                       (const void *)tmp, (RecWord *)ctx->recs.ptr, cap, t.scalars, match, ctx->keep.host_flag_dev);
     return GRIDHIP_OK;
 }
 
 int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, const double *v,
-               int64_t uv_stride, const int64_t *wbin, double2 *zero_out)
+               int64_t uv_stride, const int64_t *wbin, double2 *zero_out, bool may_reuse)
 {
+    const uint64_t gen_in = ctx->bin_gen++;  // (whatever this call does to the records and tables, it is a writer)
     GH_CHECK(ws_reserve(ctx, ctx->tables, tables_bytes(g)));
     if (!rec_fits(g)) return fail(ctx, GRIDHIP_EUNSUPPORTED, "record fields need %d bits", g.ob + g.kb + 14);  // (api.hip cuts such calls)
     GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)(n > 0 ? n : 1) * sizeof(RecWord)));
@@ -928,7 +1040,6 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
         const int fmt = (p != 5 && p != 6 && g.ob + g.kb <= 40) ? 8 : (g.nbins <= TMP12_MAX_BINS && p != 5) ? 12 : 16;
         GH_CHECK(ws_reserve(ctx, ctx->recs_tmp, (size_t)(n > 0 ? n : 1) * fmt));
         GH_CHECK(ws_reserve(ctx, ctx->blockhist, (size_t)ncoarse * sizeof(int32_t)));  // coarse cursors
-        launch_clear(ctx, t.bin_count, g.nbins, t.scalars, 3, (int32_t *)ctx->blockhist.ptr, ncoarse);
         // chunk size: 8192 records, one work-group per CU (option scatter_chunk = 4096: two per CU; measured no faster)
         const bool small_chunk = ctx->opt.scatter_chunk == 4096;
         const int chunk = small_chunk ? 4096 : 8192;
@@ -944,6 +1055,76 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             GH_CHECK(ws_reserve(ctx, ctx->recs_raw, (size_t)(n > 0 ? n : 1) * sizeof(unsigned long long)));
             pre = (unsigned long long *)ctx->recs_raw.ptr;
         }
+        // ---- reuse (see the top): verify when the pre-records in recs_raw were written by the previous pre-pass of this
+        // context under an equal key.  Not while the stream is captured (or its state cannot be told): nothing runs
+        // then, so a captured call neither verifies nor leaves state behind.  What its replays write later the host
+        // does not see; the stamp the clear kernel leaves on the device is there for them.
+        BinKeep &keep = ctx->keep;
+        BinKey key;
+        memset(&key, 0, sizeof key);
+        bool keeps = false, verify = false;
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx->stream, &capturing) != hipSuccess) {
+            (void)hipGetLastError();
+            capturing = hipStreamCaptureStatusInvalidated;
+        }
+        if (may_reuse && use_pre && n > 0 && ctx->opt.fault_inject == 0 && capturing == hipStreamCaptureStatusNone) {
+            keeps = true;
+            key.g = g;
+            key.n = n;
+            key.stride = uv_stride;
+            key.u = u;
+            key.v = v;
+            key.wbin = wbin;
+            key.opt[0] = p;
+            key.opt[1] = ctx->opt.coarse_shift;
+            key.opt[2] = ctx->opt.scatter_chunk;
+            key.opt[3] = ctx->opt.count_unroll;
+            key.opt[4] = ctx->opt.fault_inject;
+            key.recs = ctx->recs.ptr;
+            key.tables = ctx->tables.ptr;
+            key.pre = pre;
+            key.gen = gen_in + 1;
+            constexpr size_t geom_bytes = offsetof(Geom, sPx) + sizeof(int32_t);  // (no padding before the last field)
+            const bool same = keep.valid && keep.key.gen == gen_in && !memcmp(&keep.key.g, &key.g, geom_bytes) &&
+                              !memcmp(&keep.key.n, &key.n, offsetof(BinKey, gen) - offsetof(BinKey, n));
+            if (same && ctx->opt.bin_reuse != 1) {
+                if (keep.pending && keep.host_flag && *(volatile int32_t *)keep.host_flag == 0) keep.backoff = 4;  // (possibly stale: a guess)
+                if (keep.backoff > 0)
+                    --keep.backoff;
+                else
+                    verify = true;
+            } else
+                keep.backoff = 0;
+            keep.pending = false;
+        }
+        keep.valid = false;
+        if (verify && !keep.host_flag) {
+            GH_CHECK_HIP(ctx, hipHostMalloc((void **)&keep.host_flag, 64, hipHostMallocMapped));
+            GH_CHECK_HIP(ctx, hipHostGetDevicePointer((void **)&keep.host_flag_dev, keep.host_flag, 0));
+            *keep.host_flag = 1;
+        }
+        int32_t *const match = verify ? t.scalars + SC_MATCH : nullptr;
+        // (the clear kernel arms `match` only if the device's stamp is the kept generation: a replayed graph has stamped its own)
+        launch_clear(ctx, t.bin_count, g.nbins, t.scalars, 3, (int32_t *)ctx->blockhist.ptr, ncoarse, match, t.scalars + SC_GEN,
+                     gen_in + 1, gen_in);
+        if (verify) {
+            const bool v2 = uv_stride == 1 && g.P == 1 && (((uintptr_t)u | (uintptr_t)v | (uintptr_t)wbin | (uintptr_t)pre) & 15) == 0;
+            // no LDS and 72 registers: three work-groups of 512 threads share a CU (24 waves against the counting sweep's 16)
+            // (measured on the headline case: 0.545 ms; 1 or 2 x 1024 threads 0.54, 4 x 512 0.61, 6 x 256 0.58, 8 x 256 0.65)
+            const int vthreads = 512, vper = 3;
+            int64_t vneed = (n + 16383) / 16384;
+            const int vblocks = (int)(vneed < ctx->num_cu * vper ? vneed : ctx->num_cu * vper);
+            if (v2)
+                hipLaunchKernelGGL(bin_verify_kernel<true>, dim3(vblocks), dim3(vthreads), 0, ctx->stream, g, n, u, v, uv_stride, wbin,
+                                   PreFmt{bb}, (const unsigned long long *)pre, zero_out, match);
+            else
+                hipLaunchKernelGGL(bin_verify_kernel<false>, dim3(vblocks), dim3(vthreads), 0, ctx->stream, g, n, u, v, uv_stride, wbin,
+                                   PreFmt{bb}, (const unsigned long long *)pre, zero_out, match);
+            ++keep.verified;
+            keep.pending = true;
+            *(volatile int32_t *)keep.host_flag = 1;  // (until this sweep's verdict arrives: assume the best)
+        }
         for (int wdw = 0; wdw < windows; ++wdw) {
             const int b_lo = wdw * win, b_hi = b_lo + win < g.nbins ? b_lo + win : g.nbins;
             // four visibilities per thread and trip when the bins take several windows: the windows after the first
@@ -954,24 +1135,24 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             if (v2)
                 hipLaunchKernelGGL((bin_count_kernel<true, 1, true>), dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u, v,
                                    uv_stride, wbin, t.bin_count, (int32_t *)nullptr, t.scalars, b_lo, b_hi,
-                                   PreFmt{bb}, pre, zero_out);
+                                   PreFmt{bb}, pre, zero_out, match);
             else if (ctx->opt.count_unroll == 4 || (ctx->opt.count_unroll == 0 && windows > 1))
                 hipLaunchKernelGGL((bin_count_kernel<true, 4>), dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u, v,
                                    uv_stride, wbin, t.bin_count, (int32_t *)nullptr, t.scalars, b_lo, b_hi,
-                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out);
+                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out, match);
             else
                 hipLaunchKernelGGL((bin_count_kernel<true, 1>), dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u, v,
                                    uv_stride, wbin, t.bin_count, (int32_t *)nullptr, t.scalars, b_lo, b_hi,
-                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out);
+                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out, match);
         }
         hipLaunchKernelGGL(bin_scan_kernel<1024>, dim3(SCAN_SEGS + g.ngroups), dim3(1024), 0, ctx->stream, g, t.bin_count, t.bin_start,
-                           t.work_start, t.cursor);
+                           t.work_start, t.cursor, match);
         const PreFmt pf{bb};
 #define GH_TWO(P_, T_)                                                                                                  \
     (small_chunk ? launch_two_level<P_, T_, 512, 4096>(ctx, g, t, n, u, v, uv_stride, wbin, shift, ncoarse, cblocks, pre, \
-                                                        pf, cap)                                                          \
+                                                        pf, cap, match)                                                        \
                  : launch_two_level<P_, T_, 1024, 8192>(ctx, g, t, n, u, v, uv_stride, wbin, shift, ncoarse, cblocks,   \
-                                                         pre, pf, cap))
+                                                         pre, pf, cap, match))
         if (use_pre && fmt == 8)
             GH_CHECK(GH_TWO(true, 8));
         else if (use_pre && fmt == 12)
@@ -986,10 +1167,15 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             GH_CHECK(GH_TWO(false, 16));
 #undef GH_TWO
         GH_CHECK_HIP(ctx, hipGetLastError());
+        if (keeps) {  // whichever way the verdict goes, recs_raw now holds this call's pre-records
+            keep.key = key;
+            keep.valid = true;
+        }
         return GRIDHIP_OK;
     }
 
-    launch_clear(ctx, t.bin_count, g.nbins, t.scalars, 3);
+    ctx->keep.valid = false;
+    launch_clear(ctx, t.bin_count, g.nbins, t.scalars, 3, nullptr, 0, nullptr, t.scalars + SC_GEN, gen_in + 1);
     if (lds_hist) {
         GH_CHECK(ws_reserve(ctx, ctx->blockhist, (size_t)blocks * g.nbins * sizeof(int32_t)));
         block_hist = (int32_t *)ctx->blockhist.ptr;
@@ -997,15 +1183,15 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             const int b_lo = wdw * win, b_hi = b_lo + win < g.nbins ? b_lo + win : g.nbins;
             hipLaunchKernelGGL(bin_count_kernel<true>, dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u,
                                v, uv_stride, wbin, t.bin_count, block_hist, t.scalars, b_lo, b_hi, PreFmt{0},
-                               (unsigned long long *)nullptr, zero_out);
+                               (unsigned long long *)nullptr, zero_out, (const int32_t *)nullptr);
         }
     } else {
         hipLaunchKernelGGL(bin_count_kernel<false>, dim3(blocks), dim3(threads), 0, ctx->stream, g, n, u, v,
                            uv_stride, wbin, t.bin_count, block_hist, t.scalars, 0, g.nbins, PreFmt{0},
-                           (unsigned long long *)nullptr, zero_out);
+                           (unsigned long long *)nullptr, zero_out, (const int32_t *)nullptr);
     }
     hipLaunchKernelGGL(bin_scan_kernel<1024>, dim3(SCAN_SEGS + g.ngroups), dim3(1024), 0, ctx->stream, g, t.bin_count, t.bin_start,
-                       t.work_start, t.cursor);
+                       t.work_start, t.cursor, (const int32_t *)nullptr);
     if (lds_hist) {
         hipLaunchKernelGGL(bin_offsets_kernel, dim3((g.nbins + 255) / 256), dim3(256), 0, ctx->stream, g.nbins, blocks,
                            t.bin_start, block_hist);

@@ -111,13 +111,38 @@ __host__ __device__ __forceinline__ RecWord rec_pack(const Geom &g, int32_t lxy,
 }
 
 struct Options {
-    int64_t tile = 0, block = 0, chunk = 0, wgroups = 0, variant = 0, sort = 0, dbg = 0, prepass = 0, fault_inject = 0, aw_cache = 1, tile_x = 0, tile_y = 0, coarse_shift = 0, scatter_chunk = 0, count_unroll = 0, rec_bits = 0, wtable = 0, reserve_cus = 0, subfoot = 0, bigtile = 0, yield_cus = 0;
+    int64_t tile = 0, block = 0, chunk = 0, wgroups = 0, variant = 0, sort = 0, dbg = 0, prepass = 0, fault_inject = 0, aw_cache = 1, tile_x = 0, tile_y = 0, coarse_shift = 0, scatter_chunk = 0, count_unroll = 0, rec_bits = 0, wtable = 0, reserve_cus = 0, subfoot = 0, bigtile = 0, yield_cus = 0, bin_reuse = 0;
 };
 
 struct Workspace {
     void *ptr = nullptr;
     size_t bytes = 0;
 };
+
+// What the last two-level pre-pass of a plain gridding call (convgrid2 / degrid2) left behind, so that the next call
+// over the same coordinates can keep its records (bin.hip, "Reuse").  The pre-records themselves stay in recs_raw.
+struct BinKey {
+    Geom g;                  // compared up to its last named field
+    int64_t n, stride;
+    const void *u, *v, *wbin;
+    int64_t opt[5];          // prepass, coarse_shift, scatter_chunk, count_unroll, fault_inject
+    const void *recs, *tables, *pre;  // the scratch blocks the state lives in (a re-allocation moves them)
+    uint64_t gen;            // gridhip_ctx::bin_gen when the state was written
+};
+struct BinKeep {
+    bool valid = false;
+    BinKey key;
+    bool pending = false;    // the previous call verified: its outcome is (or will be) in *host_flag
+    int backoff = 0;         // calls that do not verify after a failed attempt
+    int32_t *host_flag = nullptr;  // mapped host word: 1 = the last verifying pre-pass kept its records, 0 = it did not
+    int32_t *host_flag_dev = nullptr;
+    int64_t verified = 0;    // calls that ran the verify sweep (read-only option "prepass_verified")
+};
+// slots of d_scalars the reuse uses: the verify sweep's verdict (1 = every pre-record equal), its count of dropped
+// visibilities, the calls that kept their records so far (read-only option "prepass_reused"), and - two words - the
+// generation of the pre-pass that last ran on the device: written by the kernels themselves, so that a replayed graph,
+// which the host never sees, leaves its mark
+constexpr int SC_MATCH = 104, SC_VDROPPED = 105, SC_REUSED = 106, SC_GEN = 108;
 
 struct ImagingState;  // the imaging layer's share of a context (imaging.h)
 
@@ -140,7 +165,12 @@ struct gridhip_ctx {
     gridhip::Workspace ktab;       // kernel table cut into zero-padded square parts (sub-footprints, api.hip)
     gridhip::Workspace aw;         // aw gridders: pair slots, pair kernels, key hash table, table of distinct kernels
     int32_t *d_scalars = nullptr;  // [0]=dropped (wbin out of range), [2]=errors, [4..19] work queues,
-                                   // [20..27] clock stamps of the last sorted tile kernel, [28..30] aw gridders, [32..] profile
+                                   // [20..27] clock stamps of the last sorted tile kernel, [28..30] aw gridders, [32..] profile,
+                                   // [104..109] pre-pass reuse (SC_MATCH ...)
+    // every pre-pass, and whatever else writes the records or the bin tables, counts here: kept state is only as
+    // good as the generation it was written under
+    uint64_t bin_gen = 0;
+    gridhip::BinKeep keep;
     int num_cu = 256;
     int max_lds = 160 * 1024;
     bool timing = false;
@@ -235,8 +265,10 @@ __device__ __forceinline__ void frac_coord_dev(int64_t n, int32_t qpx, double p,
 // kernel launchers (each enqueues on ctx->stream)
 // zero_out (degrid2): the counting sweep writes a zero prediction for every visibility it drops (no tap inside the
 // grid, wbin out of range), so that the caller's array needs no clearing pass
+// may_reuse: the caller's records and tables are the context's own and stay as the pre-pass leaves them until the
+// next pre-pass, so a later call with equal coordinates may keep them (convgrid2 / degrid2; see "Reuse" in bin.hip)
 int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, const double *v,
-               int64_t uv_stride, const int64_t *wbin, double2 *zero_out = nullptr);
+               int64_t uv_stride, const int64_t *wbin, double2 *zero_out = nullptr, bool may_reuse = false);
 int launch_tile_grid(gridhip_ctx *ctx, const Geom &g, int block, size_t lds_bytes, int64_t n,
                      const double *gcf, const double *vis, double *grid);
 bool sorted_plan(const gridhip_ctx *ctx, const Geom &g, int block, int *nkeys, int *maxchunk, size_t *lds_bytes);

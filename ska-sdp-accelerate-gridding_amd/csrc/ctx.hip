@@ -399,6 +399,7 @@ int gridhip_destroy(gridhip_ctx *ctx)
     for (auto &b : ctx->img->pool_free) (void)hipFree(b.first);
     ctx->img->pool_free.clear();
     if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
+    if (ctx->keep.host_flag) (void)hipHostFree(ctx->keep.host_flag);
     for (int i = 0; i < gridhip_ctx::EV_RING * 3; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
@@ -478,6 +479,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "subfoot")) return &ctx->opt.subfoot;
     if (!strcmp(key, "bigtile")) return &ctx->opt.bigtile;
     if (!strcmp(key, "yield_cus")) return &ctx->opt.yield_cus;
+    if (!strcmp(key, "bin_reuse")) return &ctx->opt.bin_reuse;
     if (!strcmp(key, "noise_bits")) return &ctx->img->noise_bits;  // image_stats' digit: 8, or anything else for 13
     return nullptr;
 }
@@ -514,6 +516,21 @@ int gridhip_get_option(gridhip_ctx *ctx, const char *key, int64_t *value)
     }
     if (!strcmp(key, "aw_tables_built")) {
         *value = ctx->aw_tables_built;
+        return GRIDHIP_OK;
+    }
+    if (!strcmp(key, "prepass_verified")) {
+        // read-only: convgrid2 / degrid2 calls so far whose pre-pass ran the verify sweep (bin.hip, "Reuse") ...
+        *value = ctx->keep.verified;
+        return GRIDHIP_OK;
+    }
+    if (!strcmp(key, "prepass_reused")) {
+        // ... and those of them that kept the previous call's records (counted on the device: the host never waits
+        // for a verdict)
+        GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+        int32_t h = 0;
+        GH_CHECK_HIP(ctx, hipMemcpyAsync(&h, ctx->d_scalars + SC_REUSED, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *value = h;
         return GRIDHIP_OK;
     }
     if (!strcmp(key, "last_path")) {

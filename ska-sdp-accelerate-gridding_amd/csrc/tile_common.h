@@ -163,14 +163,19 @@ static inline int work_blocks(const Geom &g, int64_t n)
 
 // Zeroes up to three int32 ranges in one launch.  Kernels, not hipMemsetAsync: what a gridding call enqueues is then
 // nothing but kernel launches, which a caller may capture into a HIP graph and replay.
-__global__ void __launch_bounds__(256) clear_ints_kernel(int32_t *a, int na, int32_t *b, int nb, int32_t *c, int nc);
+// `stamp` (every pre-pass's first kernel, bin.hip "Reuse"): the two words of d_scalars that hold the generation of the
+// pre-pass that last ran on the device, set to `gen`.  `arm` (before a verify sweep): arm[0] = 1 if the stamp found
+// there was `gen_kept`, else 0, and arm[1] = 0 - the sweep's verdict and its dropped count.
+__global__ void __launch_bounds__(256) clear_ints_kernel(int32_t *a, int na, int32_t *b, int nb, int32_t *c, int nc, int32_t *arm,
+                                                         int32_t *stamp, uint64_t gen, uint64_t gen_kept);
 static inline void launch_clear(gridhip_ctx *ctx, int32_t *a, int na, int32_t *b = nullptr, int nb = 0, int32_t *c = nullptr,
-                                int nc = 0)
+                                int nc = 0, int32_t *arm = nullptr, int32_t *stamp = nullptr, uint64_t gen = 0,
+                                uint64_t gen_kept = 0)
 {
     const int most = na > nb ? (na > nc ? na : nc) : (nb > nc ? nb : nc);
     int blocks = (most + 255) / 256;
     blocks = blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks;
-    hipLaunchKernelGGL(clear_ints_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a, na, b, nb, c, nc);
+    hipLaunchKernelGGL(clear_ints_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a, na, b, nb, c, nc, arm, stamp, gen, gen_kept);
 }
 
 template <typename K>

@@ -18,8 +18,17 @@
 
 namespace gridhip {
 
-__global__ void __launch_bounds__(256) clear_ints_kernel(int32_t *a, int na, int32_t *b, int nb, int32_t *c, int nc)
+__global__ void __launch_bounds__(256) clear_ints_kernel(int32_t *a, int na, int32_t *b, int nb, int32_t *c, int nc, int32_t *arm,
+                                                         int32_t *stamp, uint64_t gen, uint64_t gen_kept)
 {
+    if (stamp && blockIdx.x == 0 && threadIdx.x == 0) {
+        if (arm) {
+            arm[0] = stamp[0] == (int32_t)(uint32_t)gen_kept && stamp[1] == (int32_t)(uint32_t)(gen_kept >> 32);
+            arm[1] = 0;
+        }
+        stamp[0] = (int32_t)(uint32_t)gen;
+        stamp[1] = (int32_t)(uint32_t)(gen >> 32);
+    }
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < na || i < nb || i < nc; i += gridDim.x * blockDim.x) {
         if (i < na) a[i] = 0;
         if (i < nb) b[i] = 0;

@@ -69,10 +69,18 @@ if tile:
         rec["fetch_bytes"] = fetch * 2048.0
         rec["write_bytes"] = write * 1024.0
         rec["hbm_bytes_per_launch"] = fetch * 2048.0 + write * 1024.0
-    cal = [kk for kk in set(x for (x, _) in per) if kk.startswith("bin_count")]
-    if cal and mean(cal[0], "FETCH_SIZE") is not None:
-        rec["calibration_bin_count_fetch_bytes_x2"] = mean(cal[0], "FETCH_SIZE") * 2048.0
+    # calibration: the dispatches that swept the stream (after a verify sweep that kept the records the counting sweep
+    # returns at once and fetches nothing: those dispatches are left out)
+    def swept(prefix):
+        v = [x for (kk, c), xs in per.items() if kk.startswith(prefix) and c == "FETCH_SIZE" for x in xs]
+        v = [x for x in v if x > 0.5 * max(v)]
+        return sum(v) / len(v) if v else None
+    if swept("bin_count") is not None:
+        rec["calibration_bin_count_fetch_bytes_x2"] = swept("bin_count") * 2048.0
         rec["calibration_note"] = "bin_count_kernel reads u, v, wbin once: 24 B per visibility"
+    if swept("bin_verify") is not None:
+        rec["calibration_bin_verify_fetch_bytes_x2"] = swept("bin_verify") * 2048.0
+        rec["calibration_verify_note"] = "bin_verify_kernel reads u, v, wbin and the kept pre-record once: 32 B per visibility"
     h, m = mean(k, "TCC_HIT_sum"), mean(k, "TCC_MISS_sum")
     if h is not None and m is not None:
         rec["tcc_hit_rate"] = h / (h + m)
