@@ -237,7 +237,15 @@ int gridhip_make_grid_hermitian(gridhip_ctx *ctx, int64_t N, double *grid);
 /* fft / ifft, :815-829: shift2D . fft2D . ishift2D on an N x N complex array (hipFFT);
  * inverse != 0 is scaled by 1/N^2 as accelerate-fft's Inverse mode. */
 int gridhip_fft2_centered(gridhip_ctx *ctx, int64_t N, const double *in, double *out, int inverse);
-/* w_kernel, :610-728: out is [qpx][qpx][npixKern][npixKern]. */
+/* w_kernel, :610-728: out is [qpx][qpx][npixKern][npixKern].
+ * The w-kernel shape rule, GRIDHIP_EINVAL before anything is touched (out is left as it was): npixFF, npixKern, qpx >= 1,
+ * npixKern <= npixFF, and with na = npixFF * qpx
+ *     na / 2 - qpx * (npixKern / 2) >= qpx - 1        (integer divisions)
+ * extract_oversampled (:709-728) reads the transformed na x na far field from row and column
+ * na / 2 - qpx * (npixKern / 2) - (qpx - 1) on; the reference indexes outside its array where that is negative, e.g.
+ * (npixFF, npixKern, qpx) = (8, 8, 2) or (16, 16, 2); (9, 9, 2) and every qpx = 1 shape are legal.  The rule holds for
+ * every entry point that takes (npixFF, npixKern, qpx): this one and the w_cache kind (kind 2) of w_cache_imaging,
+ * do_imaging, predict and the imagers, host and _dev forms alike. */
 int gridhip_w_kernel(gridhip_ctx *ctx, double theta, double w, int64_t npixFF, int64_t npixKern,
                      int64_t qpx, double *out);
 /* ImagingFunctions (:76-81): grid is N x N with N = gridhip_image_size(theta, lam), overwritten. */
@@ -246,7 +254,8 @@ int gridhip_simple_imaging(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
 int gridhip_conv_imaging(gridhip_ctx *ctx, int64_t Q, int64_t gh, int64_t gw, const double *kv,
                          double theta, int64_t lam, int64_t n, const double *u, const double *v,
                          int64_t uv_stride, const double *vis, double *grid);
-/* w_cache_imaging, :399-449: builds one conjugated w_kernel per plane, then convgrid2. */
+/* w_cache_imaging, :399-449: builds one conjugated w_kernel per plane, then convgrid2.  (qpx, npixFF, npixKern):
+ * the w-kernel shape rule stated at gridhip_w_kernel. */
 int gridhip_w_cache_imaging(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_t npixFF,
                             int64_t npixKern, double theta, int64_t lam, int64_t n, const double *u,
                             const double *v, const double *w, int64_t uv_stride, const double *vis,

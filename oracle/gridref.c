@@ -655,11 +655,14 @@ void gridref_awgrid(int64_t H, int64_t Wd, double *G, int64_t n, int64_t W, int6
  *   w_kernel_function (:651-667): exp(i*2*pi*w*(1 - sqrt(1 - l^2 - m^2)))
  *   kernel_oversample (:669-680): pad_mid ff (n*qpx) -> ifft -> extract_oversampled
  *   extract_oversampled (:709-728): K[yf,xf,y,x] = af[c - yf + qpx*y, c - xf + qpx*x] * qpx^2,
- *                                   c = na/2 - qpx*(s/2) */
+ *                                   c = na/2 - qpx*(s/2)
+ * The rows and columns read are c - (qpx-1) ... c + qpx*(s-1): inside af for s <= n (the last is below na then) and
+ * c >= qpx - 1.  The reference indexes outside its array otherwise; such a shape is refused here (-2, out untouched). */
 int gridref_w_kernel(double theta, double w, int64_t npixFF, int64_t npixKern, int64_t qpx,
                      double *out)
 {
     int64_t n = npixFF, s = npixKern, na = n * qpx;
+    if (n <= 0 || s <= 0 || qpx <= 0 || s > n || na / 2 - qpx * (s / 2) < qpx - 1) return -2;
     double *ff = (double *)malloc(sizeof(double) * 2 * (size_t)n * (size_t)n);
     double *pad = (double *)malloc(sizeof(double) * 2 * (size_t)na * (size_t)na);
     double *af = (double *)malloc(sizeof(double) * 2 * (size_t)na * (size_t)na);

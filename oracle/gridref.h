@@ -78,7 +78,9 @@ void gridref_awgrid(int64_t H, int64_t Wd, double *G, int64_t n, int64_t W, int6
                     const double *u, const double *v, const int64_t *wbin,
                     const int64_t *a1, const int64_t *a2, const double *vis, int direct);
 
-/* src/Gridding.hs:610-728: out is [Q][Q][S][S] */
+/* src/Gridding.hs:610-728: out is [Q][Q][S][S].  0 on success, -1 out of memory, -2 (out untouched) for a shape that
+ * is not positive, has npixKern > npixFF, or extracts outside the transformed far field:
+ * (npixFF*qpx)/2 - qpx*(npixKern/2) < qpx - 1. */
 int gridref_w_kernel(double theta, double w, int64_t npixFF, int64_t npixKern, int64_t qpx,
                      double *out);
 /* centred 2-D transforms, src/Gridding.hs:815-829 (inverse is 1/N^2 normalised) */

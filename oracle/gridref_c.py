@@ -165,6 +165,8 @@ def w_kernel(theta, w, npixFF, npixKern, qpx):
     out = np.empty((qpx, qpx, npixKern, npixKern), dtype=np.complex128)
     rc = lib().gridref_w_kernel(C.c_double(theta), C.c_double(w), i64(npixFF), i64(npixKern), i64(qpx),
                                 _d(out))
+    if rc == -2:
+        raise ValueError(f"w_kernel: npixFF={npixFF}, npixKern={npixKern}, qpx={qpx} refused (gridref.h)")
     assert rc == 0
     return out
 

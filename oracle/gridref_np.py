@@ -17,9 +17,14 @@ def haskell_round(x):
 
 
 def acc_round(x):
-    """Accelerate `round` as lowered by the LLVM backends = libm round (half away from zero)."""
+    """Accelerate `round` as lowered by the LLVM backends = libm round (half away from zero).
+
+    By truncation and a compare of the fractional part, both exact for every finite double: x - trunc(x) is
+    representable, and above 2^52 every double is its own truncation.  (floor(|x| + 0.5) is not libm round: the sum
+    rounds up to 1 for x = 0.49999999999999994, and to the even neighbour for odd integers above 2^52.)"""
     x = np.asarray(x, dtype=np.float64)
-    return (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64)
+    t = np.trunc(x)
+    return (t + np.where(np.abs(x - t) >= 0.5, np.copysign(1.0, x), 0.0)).astype(np.int64)
 
 
 def frac_coord(n, qpx, p):
@@ -231,7 +236,13 @@ def awgrid(wkerns, akerns, G, u, v, wbin, a1, a2, vis):
 
 
 def w_kernel(theta, w, npixFF, npixKern, qpx):
-    """:610-728 — returns [Q,Q,S,S]"""
+    """:610-728 — returns [Q,Q,S,S].  ValueError for a shape whose extraction (:709-728) would index outside the
+    transformed far field: the first row read is na/2 - qpx*(npixKern/2) - (qpx-1).  (gridref_w_kernel's rule.)"""
+    if npixFF <= 0 or npixKern <= 0 or qpx <= 0 or npixKern > npixFF:
+        raise ValueError(f"w_kernel: bad shape npixFF={npixFF}, npixKern={npixKern}, qpx={qpx}")
+    if (npixFF * qpx) // 2 - qpx * (npixKern // 2) < qpx - 1:
+        raise ValueError(f"w_kernel: npixFF={npixFF}, npixKern={npixKern}, qpx={qpx} extracts outside the far field "
+                         f"(na/2 - qpx*(npixKern/2) < qpx - 1)")
     n = npixFF
     step = 1.0 / n
     base = (-(n // 2)) * step + np.arange(n, dtype=np.float64) * step

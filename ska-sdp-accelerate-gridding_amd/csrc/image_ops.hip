@@ -121,14 +121,15 @@ __global__ void hermitian_kernel(int64_t N, const double2 *__restrict__ in, doub
         x += s;
         y -= y >= N ? N : 0;
         x -= x >= N ? N : 0;
+        // the conjugate is ADDED (zipWith (+), :605), and on an even grid's first row and column what is added is 0 :+ 0:
+        // an imaginary part of -0.0 becomes +0.0 there (g.y - 0.0 would keep -0.0)
         double2 a = make_double2(0.0, 0.0);
-        if (even) {
-            if (x != 0 && y != 0) a = in[(N - y) * N + (N - x)];
-        } else {
-            a = in[(N - 1 - y) * N + (N - 1 - x)];
+        if (!even || (x != 0 && y != 0)) {
+            a = even ? in[(N - y) * N + (N - x)] : in[(N - 1 - y) * N + (N - 1 - x)];
+            a.y = -a.y;
         }
         const double2 g = in[y * N + x];
-        out[c] = make_double2(g.x + a.x, g.y - a.y);
+        out[c] = make_double2(g.x + a.x, g.y + a.y);
     }
 }
 
@@ -531,8 +532,10 @@ int gridhip_w_kernel(gridhip_ctx *ctx, double theta, double w, int64_t npixFF, i
                      double *out)
 {
     if (!ctx) return GRIDHIP_EINVAL;
-    if (npixFF <= 0 || npixKern <= 0 || qpx <= 0 || !out || npixKern > npixFF)
-        return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    if (!out) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    if (!w_kernel_shape_ok(npixFF, npixKern, qpx))
+        return fail(ctx, GRIDHIP_EINVAL, "w-kernel shape npixFF %lld, npixKern %lld, qpx %lld: not positive, npixKern > npixFF, "
+                    "or extracting outside the far field", (long long)npixFF, (long long)npixKern, (long long)qpx);
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t na = npixFF * qpx;
     const size_t kel = (size_t)qpx * qpx * npixKern * npixKern;

@@ -179,6 +179,13 @@ int normalise(gridhip_ctx *ctx, size_t cells, double *image, double *psf, const 
 // the w-bin rule on the device (synchronises: min and plane count come back to the host)
 int dev_wbins(gridhip_ctx *ctx, int64_t n, const double *w, int64_t stride, int64_t wstep, int64_t *wbin, int64_t *wmin,
               int64_t *nplanes);
+// The w-kernel shape rule (include/gridhip.h, at gridhip_w_kernel): wkern_extract_kernel reads the na x na transform from
+// row and column na / 2 - Q * (S / 2) - (Q - 1) to na / 2 - Q * (S / 2) + Q * (S - 1); the first is negative unless
+// na / 2 - Q * (S / 2) >= Q - 1, the last is below na for S <= npixFF.  Every caller-given shape passes through here.
+static inline bool w_kernel_shape_ok(int64_t npixFF, int64_t S, int64_t Q)
+{
+    return npixFF > 0 && S > 0 && Q > 0 && S <= npixFF && (npixFF * Q) / 2 - Q * (S / 2) >= Q - 1;
+}
 // one plane of a w-kernel table, out[Q][Q][S][S]; pad: (npixFF * Q)^2 complex scratch
 int dev_w_kernel(gridhip_ctx *ctx, double theta, double w, int64_t npixFF, int64_t S, int64_t Q, double2 *out, bool conj,
                  double2 *pad);

@@ -10,9 +10,10 @@ int imaging_fn_check(gridhip_ctx *ctx, ImagingFn &fn, int64_t *N)
     *N = gridhip_image_size(fn.theta, fn.lam);
     if (fn.kind == 2 && fn.wstep <= 0) fn.wstep = 2000;  // (w_cache_imaging's default, :412)
     const bool ok = fn.kind == 0 || (fn.kind == 1 && fn.kv && fn.Q > 0 && fn.gh > 0 && fn.gw > 0) ||
-                    (fn.kind == 2 && fn.Q > 0 && fn.npixFF > 0 && fn.gh > 0 && fn.gh <= fn.npixFF);
+                    (fn.kind == 2 && w_kernel_shape_ok(fn.npixFF, fn.gh, fn.Q));
     if (*N <= 0 || !ok)
-        return fail(ctx, GRIDHIP_EINVAL, "bad imaging function %d, its options, or image size %lld", fn.kind, (long long)*N);
+        return fail(ctx, GRIDHIP_EINVAL, "bad imaging function %d, its options (kind 2: the w-kernel shape rule), or image size %lld",
+                    fn.kind, (long long)*N);
     return GRIDHIP_OK;
 }
 

@@ -168,6 +168,61 @@ def test_c_vs_numpy_fft_and_kernels(oracle):
         assert rel(oracle.w_kernel(0.1, 750.0, nff, s, q), P.w_kernel(0.1, 750.0, nff, s, q)) < 1e-12
 
 
+def test_acc_round_is_libm_round(oracle):
+    """The numpy oracle's `round` against the C oracle's (libm round, reached through wbins with wstep = 1 and through
+    frac_coord): half away from zero at every tie, the largest double below one half, signed zeros, odd integers above
+    2^52 and 10^4 random values; and the two oracles' w-bins on the tie vectors the GPU test uses."""
+    from image_ops_cases import BELOW_HALF, WSTEPS, tie_vector
+    rng = np.random.default_rng(23)
+    edge = np.array([BELOW_HALF, -BELOW_HALF, 0.5, -0.5, 1.5, -1.5, 2.5, -2.5, 0.0, -0.0, 2.0 ** 52 + 1, 2.0 ** 53 - 1])
+    x = np.concatenate([edge, rng.uniform(-1.0e6, 1.0e6, 8000), rng.uniform(-4.0, 4.0, 1000),
+                        np.floor(rng.uniform(2.0 ** 52, 2.0 ** 53, 1000))])
+    assert len(x) == 12 + 10 ** 4
+    wb, mn, _ = oracle.wbins(x, 1)  # wbin = round(w) - min round(w)
+    got = P.acc_round(x)
+    assert got.dtype == np.int64 and np.array_equal(got, wb + mn)
+    assert list(got[:12]) == [0, 0, 1, -1, 2, -2, 3, -3, 0, 0, 2 ** 52 + 1, 2 ** 53 - 1]
+    # the sub-pixel index: x = p, flx = floor(p + 0.25) = 0, fracx = round(2 p) with 2 p the largest double below 0.5
+    p = np.array([BELOW_HALF / 2, 0.25, 0.1])
+    for a, b in zip(oracle.frac_coord(1, 2, p), P.frac_coord(1, 2, p)):
+        assert np.array_equal(a, b)
+    assert list(P.frac_coord(1, 2, p)[0]) == [0, 0, 0] and list(P.frac_coord(1, 2, p)[1]) == [0, 1, 0]
+    for wstep in WSTEPS:
+        w = np.concatenate([tie_vector(wstep), rng.uniform(-5.0 * wstep, 5.0 * wstep, 200)])
+        a, amn, anp = oracle.wbins(w, wstep)
+        b, bmn, bnp = P.wbins(w, wstep)
+        assert np.array_equal(a, b) and (amn, anp) == (bmn, bnp), wstep
+        assert amn == -5 * wstep and anp == 11  # (k = +-9: 4.5 rounds away from zero)
+    w = np.array([-8000.0, 999.9999999999999, 4000.0])
+    assert list(P.wbins(w, 2000)[0]) == list(oracle.wbins(w, 2000)[0]) == [0, 4, 6]
+
+
+def test_w_kernel_refuses_shapes_that_extract_outside_the_far_field(oracle):
+    """extract_oversampled reads rows from na/2 - qpx*(npixKern/2) - (qpx-1): negative for (8, 8, 2) and (16, 16, 2).
+    Both oracles refuse those (the C one without touching its output) and still agree on the legal shapes next to
+    them, (9, 9, 2) being the last legal one (first row read: 0)."""
+    import ctypes as C
+    from image_ops_cases import WKERNEL_REFUSED
+    for nff, s, q in WKERNEL_REFUSED:
+        with pytest.raises(ValueError, match="w_kernel"):
+            P.w_kernel(0.1, 50.0, nff, s, q)
+        with pytest.raises(ValueError, match="w_kernel"):
+            oracle.w_kernel(0.1, 50.0, nff, s, q)
+        out = np.full((q, q, s, s), 7 - 3j)
+        rc = oracle.lib().gridref_w_kernel(C.c_double(0.1), C.c_double(50.0), C.c_int64(nff), C.c_int64(s), C.c_int64(q),
+                                           out.ctypes.data_as(C.POINTER(C.c_double)))
+        assert rc != 0 and np.all(out == 7 - 3j)
+    with pytest.raises(ValueError):
+        P.w_kernel(0.1, 50.0, 8, 9, 1)  # npixKern > npixFF reads past the other end
+    with pytest.raises(ValueError):
+        oracle.w_kernel(0.1, 50.0, 8, 9, 1)
+    # 1e-13: two restatements of one (na <= 34)^2 transform, a few eps each (they agree to 5e-16)
+    for nff, s, q in [(16, 16, 1), (17, 17, 1), (9, 9, 2), (16, 15, 2)]:
+        a, b = oracle.w_kernel(0.1, 50.0, nff, s, q), P.w_kernel(0.1, 50.0, nff, s, q)
+        assert a.shape == (q, q, s, s) and np.abs(b).max() > 0
+        assert rel(a, b) < 1e-13, (nff, s, q)
+
+
 # ---- properties -----------------------------------------------------------------------------------
 def test_properties(oracle):
     rng = np.random.default_rng(17)
