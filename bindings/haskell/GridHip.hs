@@ -43,6 +43,7 @@ module GridHip
   -- * imaging weights: natural, uniform, Briggs, taper and data weights, alone or as what an imager is created with
   , Weighting(..), WeightMode(..), weightsIO, imagerCreateWeightedIO, imagerCreateAwWeightedIO, imagerDestroyIO
   , imagerWeightStatsIO
+  , GainSolve(..), gaincalIO, applyGainsIO, imagerSelfcalIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -376,6 +377,21 @@ foreign import ccall unsafe "gridhip_imager_mfclean_dev"
 -- int gridhip_imager_mfdeconvolve_dev(imager, vis, models, images, nmajor, gain, threshold, niter, border, patch, stats)
 foreign import ccall unsafe "gridhip_imager_mfdeconvolve_dev"
   c_imager_mfdeconvolve_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_gaincal(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+foreign import ccall unsafe "gridhip_gaincal"
+  c_gaincal :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_gaincal_dev(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+foreign import ccall unsafe "gridhip_gaincal_dev"
+  c_gaincal_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_gains(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_gains"
+  c_apply_gains :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_gains_dev(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_gains_dev"
+  c_apply_gains_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_selfcal_dev(imager, model, vis, A, T, a1, a2, slot, wt, mode, refant, warm, niter, tol, gains, vis_cal, wt_cal, stats)
+foreign import ccall unsafe "gridhip_imager_selfcal_dev"
+  c_imager_selfcal_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -1222,6 +1238,81 @@ imagerWeightStatsIO (ImagerH h@(GridHip c) p _ _) =
     c_memcpy_d2h c (castPtr ps) (castPtr ds) 64 >>= check h
     c_synchronize c >>= check h
     map realToFrac <$> peekArray 8 ps
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Gain calibration (include/gridhip.h, "gain calibration"): per-antenna gains by StEFCal, their application, and the
+-- selfcal step of an imager.
+
+-- | how a solve runs: phase only or amplitude and phase; the reference antenna (Nothing: no rotation); the most
+-- iterations and the relative change that stops them on the device (0: never early)
+data GainSolve = GainSolve { gainPhaseOnly :: Bool, gainRefant :: Maybe Int, gainNiter :: Int, gainTol :: F }
+
+solveCodes :: GainSolve -> (CInt, Int64, Int64, CDouble)
+solveCodes (GainSolve po ref niter tol) = (if po then 1 else 0, maybe (-1) fi ref, fi niter, realToFrac tol)
+
+-- | gaincalIO h solve nant nslots ant1 ant2 slot wt vis model: the [nslots][nant] gains of vis ~ g_p model conj(g_q)
+-- starting from 1, and the 8 stats - the host form, synchronous.  slot Nothing: one interval; wt Nothing: ones.
+gaincalIO :: GridHip -> GainSolve -> Int -> Int -> A.Vector Antenna -> A.Vector Antenna -> Maybe (A.Vector Antenna)
+          -> Maybe (A.Vector F) -> A.Vector Visibility -> A.Vector Visibility -> IO (A.Matrix Visibility, [F])
+gaincalIO h@(GridHip c) solve nant nslots ant1 ant2 slot wt vis model = do
+  let A.Z A.:. n = A.arrayShape vis
+      (mode, ref, niter, tol) = solveCodes solve
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s k) slot
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+  out <- mallocForeignPtrArray (2 * nslots * nant) :: IO (ForeignPtr CDouble)
+  st <- withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 -> withSlot $ \sl -> withWt $ \ps -> withCplx vis $ \vs ->
+          withCplx model $ \ms -> withForeignPtr out $ \po -> allocaArray 8 $ \pst -> do
+            c_gaincal c (fi n) (fi nant) (fi nslots) a1 a2 sl vs ms ps mode ref 0 niter tol po pst >>= check h
+            map realToFrac <$> peekArray 8 pst
+  return (A.fromForeignPtrs (A.Z A.:. nslots A.:. nant) (castForeignPtr out), st)
+
+-- | applyGainsIO h inverse gains ant1 ant2 slot wt vis: (the visibilities, the weights) after the gains - True: data
+-- corrected, vis / (g_p conj(g_q)) with weights |g_p|^2 |g_q|^2 wt and weight 0 where there is no usable gain; False: a
+-- model corrupted, g_p vis conj(g_q) - the host form, synchronous
+applyGainsIO :: GridHip -> Bool -> A.Matrix Visibility -> A.Vector Antenna -> A.Vector Antenna
+             -> Maybe (A.Vector Antenna) -> Maybe (A.Vector F) -> A.Vector Visibility
+             -> IO (A.Vector Visibility, A.Vector F)
+applyGainsIO h@(GridHip c) inverse gains ant1 ant2 slot wt vis = do
+  let A.Z A.:. n = A.arrayShape vis
+      A.Z A.:. nslots A.:. nant = A.arrayShape gains
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s k) slot
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  wout <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
+  withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 -> withSlot $ \sl -> withWt $ \ps -> withCplx gains $ \g ->
+    withCplx vis $ \vs -> withForeignPtr out $ \po -> withForeignPtr wout $ \pw ->
+      c_apply_gains c (fi n) (fi nant) (fi nslots) a1 a2 sl g (if inverse then 1 else 0) vs ps po pw >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout))
+
+-- | imagerSelfcalIO im solve nant nslots ant1 ant2 slot wt model vis: one self-calibration step
+-- (gridhip_imager_selfcal_dev: predict, solve, correct as one chain on the device) -> (gains, the corrected
+-- visibilities, their weights, the 8 stats)
+imagerSelfcalIO :: ImagerH -> GainSolve -> Int -> Int -> A.Vector Antenna -> A.Vector Antenna
+                -> Maybe (A.Vector Antenna) -> Maybe (A.Vector F) -> A.Matrix F -> A.Vector Visibility
+                -> IO (A.Matrix Visibility, A.Vector Visibility, A.Vector F, [F])
+imagerSelfcalIO (ImagerH h@(GridHip c) p n n') solve nant nslots ant1 ant2 slot wt model vis = do
+  let (mode, ref, niter, tol) = solveCodes solve
+      cells = nslots * nant
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s $ \sp -> withDev h sp (8 * n) k) slot
+  g <- mallocForeignPtrArray (2 * cells) :: IO (ForeignPtr CDouble)
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  wout <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
+  st <- withI64 ant1 $ \a1 -> withDev h a1 (8 * n) $ \d1 -> withI64 ant2 $ \a2 -> withDev h a2 (8 * n) $ \d2 ->
+          withSlot $ \ds -> withDevWeights h n wt $ \dw -> withF model $ \mp -> withDev h mp (8 * n' * n') $ \dm ->
+            withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withForeignPtr g $ \pg ->
+              withDev h pg (16 * cells) $ \dg -> withForeignPtr wout $ \pw -> withDev h pw (8 * n) $ \dwo ->
+                withForeignPtr out $ \po -> allocaArray 8 $ \pst -> withDev h pst 64 $ \dst -> do
+                  -- (the corrected visibilities in place, in the device copy of vis)
+                  c_imager_selfcal_dev p dm dv (fi nant) (fi nslots) d1 d2 ds dw mode ref 0 niter tol dg dv dwo dst
+                    >>= check h
+                  c_memcpy_d2h c (castPtr pg) (castPtr dg) (fi (16 * cells)) >>= check h
+                  c_memcpy_d2h c (castPtr po) (castPtr dv) (fi (16 * n)) >>= check h
+                  c_memcpy_d2h c (castPtr pw) (castPtr dwo) (fi (8 * n)) >>= check h
+                  c_memcpy_d2h c (castPtr pst) (castPtr dst) 64 >>= check h
+                  c_synchronize c >>= check h
+                  map realToFrac <$> peekArray 8 pst
+  return (A.fromForeignPtrs (A.Z A.:. nslots A.:. nant) (castForeignPtr g), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out),
+          A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout), st)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

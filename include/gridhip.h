@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 200 /* 0.2.0 */
+#define GRIDHIP_VERSION 210 /* 0.2.1 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -932,6 +932,92 @@ int gridhip_imager_mfclean_dev(gridhip_imager *imager, double *residuals, double
 int gridhip_imager_mfdeconvolve_dev(gridhip_imager *imager, const double *vis, double *models, double *images,
                                     int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
                                     int64_t patch, double *stats);
+
+/* ---- gain calibration: per-antenna gains by StEFCal, their application, and a selfcal step, on the device ----------------
+ * The reference has no calibration: the semantics are defined here.  Scalar, single-polarisation, direction-independent
+ * antenna gains (StEFCal: Salvini & Wijnholds 2014) with solution intervals.  Inputs: n visibilities V_k (vis) and model
+ * visibilities M_k (model_vis), complex as interleaved doubles; the antenna pairs p_k = a1[k], q_k = a2[k], each in
+ * [0, A); the solution interval t_k = slot[k] in [0, T), or slot == NULL with T == 1; data weights s_k (wt: n doubles, or
+ * NULL for all ones).  The measurement equation is V_k ~ g[t,p] M_k conj(g[t,q]); gains is [T][A] complex.
+ *     FLAGGED   a visibility whose s_k is not > 0 (zero, negative, NaN) - gridhip_weights' rule, looked at first: it
+ *               contributes exactly nothing even when V_k or M_k is NaN or Inf (selected out, not multiplied by zero)
+ *     DROPPED   an unflagged visibility whose p, q or t is out of range: it contributes nothing and is counted
+ *     AUTO      an unflagged one in range with p == q: it contributes nothing and is counted with the dropped
+ *     X_k = (s_k V_k) conj(M_k),  Y_k = s_k |M_k|^2      once per solve, every product rounded (no fused multiply-add):
+ *               (a + bi) conj(c + di) = (a c + b d) + (b c - a d) i with a + bi = (s re V, s im V);  |M|^2 = c c + d d
+ *     start     g = 1 everywhere, or the caller's gains when warm != 0
+ *     iteration i = 0, 1, ... with the current g, for every (t, a):
+ *               num[t,a] = sum_{t_k = t, p_k = a} X_k g[t,q_k]      + sum_{t_k = t, q_k = a} conj(X_k) g[t,p_k]
+ *               den[t,a] = sum_{t_k = t, p_k = a} Y_k |g[t,q_k]|^2  + sum_{t_k = t, q_k = a} Y_k |g[t,p_k]|^2
+ *               g'[t,a]  = num / den where den > 0; else g'[t,a] = g[t,a], the very bits, and none of the next two
+ *                          rules touches it (UNSOLVED in this iteration)
+ *               mode 1 (phase only): g' <- g' / |g'| where |g'| > 0, else g
+ *               on odd i: g' <- (g' + g) / 2
+ *               rel = sqrt(sum |g' - g|^2 / sum |g'|^2) over all (t, a);  then g <- g'
+ *               stop when tol > 0 and rel <= tol: rel is tested after the update, and tol = 0 never stops early
+ *     after the loop (t, a) is UNSOLVED when its den was never > 0: its gain is exactly 1 + 0i (or the warm value), and
+ *               it is counted.  If refant >= 0 every solved gain of an interval is multiplied by conj(g[t,refant]) /
+ *               |g[t,refant]|, and g[t,refant] itself becomes (|g[t,refant]|, 0): real and non-negative.  The rotation
+ *               leaves an unsolved gain the very bits it started from, and an interval whose reference antenna is
+ *               unsolved (or zero, or not finite) is left unrotated.  refant < 0: no rotation.
+ *     stats     8 doubles { iterations performed, the last rel (NaN when there was none), chi^2 = sum s_k |V_k - g_p M_k
+ *               conj(g_q)|^2 over the used k with the final gains, chi^2 at g = 1, n_used, n_flagged, n_dropped (autos
+ *               included), the number of unsolved (t, a) }.  stats may be NULL.
+ * APPLY takes gains [T][A], vis_in, a1, a2, slot and optionally wt_in (NULL: ones) and wt_out (NULL: not written):
+ *     inverse 1 (correct data)     vis_out = vis_in / (g_p conj(g_q)),  wt_out = wt_in |g_p|^2 |g_q|^2.  A visibility whose
+ *               p, q or t is out of range, or that touches a gain that is zero or not finite, gets vis_out = vis_in and
+ *               wt_out = +0.0: gridhip_weights' flag, so that a corrected stream leaves out the baselines to an
+ *               antenna without a gain.  "Zero or not finite" is judged on |g|^2 as fp64 computes it, so a gain whose
+ *               square underflows to 0 or overflows (|g| below about 1e-154 or above about 1e154) counts as such.
+ *     inverse 0 (corrupt a model)  vis_out = g_p vis_in conj(g_q), weights copied; out of range: vis_out = vis_in.
+ *     Autocorrelations and flagged visibilities are applied like any other.  In place (vis_out == vis_in, wt_out ==
+ *     wt_in) is allowed; any other overlap of an output with an input or with the other output is refused.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL context; n < 0; A < 2; T < 1; slot ==
+ * NULL with T != 1; a NULL a1, a2, vis, model_vis (gaincal), vis_in, vis_out (apply) with n > 0; a NULL gains; niter < 0;
+ * tol < 0 or NaN; a mode or an inverse outside 0..1; refant >= A; gains overlapping any input (gaincal) or any output
+ * (apply).  n = 0 is valid: the gains are all 1 (or the warm values) and everything is unsolved.  A * T above 2^21
+ * (2097152; A = 512 with T = 4096) is GRIDHIP_EUNSUPPORTED: a solve keeps 28 B of scratch per (t, a) and its two
+ * one-work-group kernels pass over all of them in every iteration.
+ * gridhip_gaincal and gridhip_apply_gains are synchronous and stage host arrays through the context's pool.  The _dev
+ * and imager forms take device pointers and enqueue kernels only on the context's stream - no memset node, no copy node;
+ * they allocate nothing after the first call of a shape (the scratch - 32 B per visibility, 28 B per (t, a) - comes from
+ * the context's pool), never synchronise and read nothing back.  The stop condition lives on the device as in
+ * gridhip_clean: niter iterations are enqueued unconditionally and a launch that finds the state stopped returns at its
+ * first instruction, so a solve or a whole selfcal can be captured into a graph like clean and restore.
+ * A solve is: one pass that reads V, M, s, a1, a2, slot and leaves X (16 B), Y (8 B) and a packed 8-byte key (t, p, q,
+ * used) per visibility; per iteration a kernel that streams those 32 B - a work-group takes a contiguous range of whole
+ * chunks of 4096 visibilities, keeps the gains and the (num, den) sums of one interval in LDS (A <= 512; more antennas
+ * add to global memory directly) and flushes to a global [T][A][3] table when the interval changes, so a time-major
+ * stream is the fast case and an unordered slot is merely slower - and a one-work-group kernel that forms g', rel and the
+ * stop test and zeroes the table; then the rotation, and one more pass for chi^2.
+ * DETERMINISM.  The sums over the visibilities meet in fp64 atomics: gains are reproducible to the order of those sums
+ * (1e-10 of the largest |g| at a few thousand visibilities per antenna), as gridhip_weights with data weights - NOT bit
+ * for bit.  Given the gains, rel, chi^2 and the counts are added in a fixed order. */
+int gridhip_gaincal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                    const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                    int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats);
+int gridhip_gaincal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                        const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                        int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats);
+int gridhip_apply_gains(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                        const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
+                        double *vis_out, double *wt_out);
+int gridhip_apply_gains_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                            const int64_t *slot, const double *gains, int inverse, const double *vis_in,
+                            const double *wt_in, double *vis_out, double *wt_out);
+/* One self-calibration step of an imager of any kind, DEFINED BY THE CALLS IT REPLACES:
+ *     pred = gridhip_imager_predict_dev(imager, model, NULL)
+ *     gridhip_gaincal_dev(vis against pred)                         -> gains, stats
+ *     gridhip_apply_gains_dev(inverse = 1, vis, wt)                 -> vis_cal, wt_cal (wt_cal may be NULL)
+ * n is the imager's; a1, a2 (for the aw kind too: the imager does not keep them in the order of vis), slot, wt, vis,
+ * gains [T][A], vis_cal and wt_cal are on the device.  The solver reads the imager's own prediction where the gather left
+ * it - nothing is copied - and the solve's last pass writes the corrected stream.  vis_cal may be vis and wt_cal may be
+ * wt.  vis_cal can go straight into cycle or deconvolve; wt_cal is what a re-weighted imager would be created with.  A
+ * NULL imager or model is GRIDHIP_EINVAL; the other rules are those of the two calls. */
+int gridhip_imager_selfcal_dev(gridhip_imager *imager, const double *model, const double *vis, int64_t A, int64_t T,
+                               const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
+                               int64_t refant, int warm, int64_t niter, double tol, double *gains, double *vis_cal,
+                               double *wt_cal, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

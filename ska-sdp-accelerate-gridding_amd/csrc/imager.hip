@@ -542,6 +542,25 @@ int gridhip_imager_predict_dev(gridhip_imager *im, const double *model, const do
     return launch_residual(ctx, im->n, im->pred, (const double2 *)vis_sub, (double2 *)vis_out);
 }
 
+// predict -> gaincal -> apply_gains(inverse = 1) as one enqueued chain (gaincal.hip): the solver reads the prediction where
+// the gather left it, and the solve's final pass writes the corrected stream
+int gridhip_imager_selfcal_dev(gridhip_imager *im, const double *model, const double *vis, int64_t A, int64_t T,
+                               const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
+                               int64_t refant, int warm, int64_t niter, double tol, double *gains, double *vis_cal,
+                               double *wt_cal, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    const int64_t n = im->n;
+    if (!model) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK(gaincal_check(ctx, n, A, T, a1, a2, slot, vis, (const double *)im->pred, wt, mode, refant, niter, tol, gains));
+    GH_CHECK(apply_gains_check(ctx, n, A, T, a1, a2, slot, gains, 1, vis, wt, vis_cal, wt_cal));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (n > 0) GH_CHECK(gather(im, model));
+    return gaincal_run(ctx, n, A, T, a1, a2, slot, vis, (const double *)im->pred, wt, mode, refant, warm, niter, tol, gains,
+                       stats, vis_cal, wt_cal);
+}
+
 static int imager_clean(gridhip_imager *im, double *residual, double *model, double gain, double threshold,
                         int64_t niter, int64_t border, int64_t patch, double *stats, const CleanAuto &au)
 {

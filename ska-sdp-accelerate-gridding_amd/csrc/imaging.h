@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, restore.hip).
+// msclean.hip, mfclean.hip, noise.hip, restore.hip, weights.hip, gaincal.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -454,5 +454,28 @@ int weights_begin(gridhip_ctx *ctx, int64_t N, int mode, bool data_weights, Weig
 int weights_finish(gridhip_ctx *ctx, int64_t N, int64_t n, int mode, double robust, double sigma, const int64_t *cell,
                    WeightScratch &s, const double *wt_in, const double *u, const double *v, int64_t stride, double lam,
                    double *out, bool keep_sign, double *stats);
+
+// ---- gain calibration (gaincal.hip) --------------------------------------------------------------------------------------
+// the visibilities of one chunk of the iteration kernel (a work-group takes whole chunks); the most antennas whose gains
+// and sums of one interval the kernel keeps in LDS (above it the sums go straight to global memory); the most (interval,
+// antenna) cells of a solve - and so of A and of T alone, which the packed key's 21-bit fields rely on
+constexpr int64_t GC_CHUNK = 4096;
+constexpr int GC_LDS_A = 512;
+constexpr int64_t GC_MAX_TABLE = (int64_t)1 << 21;
+// gridhip_gaincal's and gridhip_apply_gains' argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED)
+int gaincal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                  const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                  int64_t refant, int64_t niter, double tol, const double *gains);
+int apply_gains_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                      const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
+                      const double *vis_out, const double *wt_out);
+// the _dev forms on checked arguments: kernels only, on ctx->stream; scratch from the context's pool.  vis_cal != null:
+// the final pass also writes apply_gains(inverse = 1) of vis, wt into vis_cal and (when given) wt_cal - a selfcal
+int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
+                int warm, int64_t niter, double tol, double *gains, double *stats, double *vis_cal, double *wt_cal);
+int apply_gains_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                    const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
+                    double *vis_out, double *wt_out);
 
 }  // namespace gridhip

@@ -16,6 +16,7 @@
 //   mfclean: multi-term CLEAN, the minor cycle of wide-band imaging over T Taylor terms (absent from the reference)
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
+//   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -436,6 +437,52 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_weights(ctx_, theta, lam, n, uvw.u.data(), uvw.v.data(), 1, data.empty() ? nullptr : data.data(),
                               (int)mode, robust, taper_sigma, out.data(), st));
         if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+        return out;
+    }
+
+    // ---- gain calibration (gridhip_gaincal, gridhip_apply_gains; include/gridhip.h, "gain calibration") ----
+    // (Host forms, as everything in this class; the device-pointer forms gridhip_gaincal_dev, gridhip_apply_gains_dev and
+    // the imager's gridhip_imager_selfcal_dev are the C header's, like every other _dev and imager entry point.)
+    struct GainStats {
+        F iterations, rel, chi2, chi2_unit, n_used, n_flagged, n_dropped, n_unsolved;
+    };
+    // The [T][A] antenna gains of vis ~ g[slot, a1] model conj(g[slot, a2]) by StEFCal, starting from 1 (or, warm, from
+    // `gains`).  slot empty: one interval (T must be 1); data empty: ones, a value that is not > 0 flags its
+    // visibility.  refant < 0: no rotation.  At most niter iterations, stopped once the relative change is <= tol.
+    std::vector<Visibility> gaincal(const std::vector<Visibility> &vis, const std::vector<Visibility> &model,
+                                    const std::vector<Int> &a1, const std::vector<Int> &a2, Int A,
+                                    const std::vector<Int> &slot = {}, Int T = 1, const std::vector<F> &data = {},
+                                    bool phase_only = false, Int refant = 0, Int niter = 50, F tol = 1e-8,
+                                    GainStats *stats = nullptr, const std::vector<Visibility> *warm = nullptr)
+    {
+        const Int n = (Int)vis.size();
+        if ((Int)model.size() != n || (Int)a1.size() != n || (Int)a2.size() != n || (!slot.empty() && (Int)slot.size() != n) ||
+            (!data.empty() && (Int)data.size() != n) || A < 2 || T < 1 || (warm && (Int)warm->size() != A * T))
+            throw Error(GRIDHIP_EINVAL, "gaincal: one value per visibility, A >= 2, T >= 1, gains of T x A");
+        std::vector<Visibility> g = warm ? *warm : std::vector<Visibility>((size_t)(A * T));
+        F st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_gaincal(ctx_, n, A, T, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(vis), cd(model),
+                              data.empty() ? nullptr : data.data(), phase_only ? 1 : 0, refant, warm ? 1 : 0, niter, tol,
+                              cd(g), st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+        return g;
+    }
+    // vis after the [T][A] gains: inverse - data corrected, vis / (g_p conj(g_q)), *wt_out = data |g_p|^2 |g_q|^2 and 0 where
+    // there is no usable gain; else a model corrupted, g_p vis conj(g_q), weights copied
+    std::vector<Visibility> apply_gains(const std::vector<Visibility> &gains, Int A, Int T, const std::vector<Visibility> &vis,
+                                        const std::vector<Int> &a1, const std::vector<Int> &a2,
+                                        const std::vector<Int> &slot = {}, bool inverse = true,
+                                        const std::vector<F> &data = {}, std::vector<F> *wt_out = nullptr)
+    {
+        const Int n = (Int)vis.size();
+        if ((Int)a1.size() != n || (Int)a2.size() != n || (!slot.empty() && (Int)slot.size() != n) ||
+            (!data.empty() && (Int)data.size() != n) || A < 2 || T < 1 || (Int)gains.size() != A * T)
+            throw Error(GRIDHIP_EINVAL, "apply_gains: one value per visibility, gains of T x A");
+        std::vector<Visibility> out((size_t)n);
+        if (wt_out) wt_out->assign((size_t)n, 0);
+        check(gridhip_apply_gains(ctx_, n, A, T, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(gains),
+                                  inverse ? 1 : 0, cd(vis), data.empty() ? nullptr : data.data(), cd(out),
+                                  wt_out ? wt_out->data() : nullptr));
         return out;
     }
 

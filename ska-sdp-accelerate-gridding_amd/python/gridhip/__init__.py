@@ -25,6 +25,7 @@ from . import _lib
 from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
                        auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
+from ._marshal import gain_stream, result_array, solve_args, stream_array
 from ._marshal import weighting as _weighting
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
@@ -524,6 +525,44 @@ class Context(Handle):
         self._call(be, "weights", float(theta), int(lam), n, u, v, st, wt, m, robust, taper, out, stats)
         return out, stats
 
+    def gaincal(self, vis, model_vis, a1, a2, nant, *, slot=None, nslots=1, weights=None, phase_only=False, refant=0,
+                niter=50, tol=1e-8, gains=None):
+        """Antenna gains of `vis` against `model_vis` by StEFCal (gridhip_gaincal[_dev]; include/gridhip.h, "gain
+        calibration"): vis ~ g[slot, a1] model_vis conj(g[slot, a2]) for n visibilities, `nant` antennas and `nslots`
+        solution intervals (slot None: one interval).  weights: n data weights (None: ones; a value that is not > 0 flags
+        its visibility, which then contributes nothing even where it is NaN).  phase_only keeps |g| = 1; refant: the
+        antenna whose gain is made real and non-negative in every interval (None: no rotation); at most niter iterations,
+        stopped on the device once the relative change is <= tol (tol = 0: never early).  gains: an (nslots, nant)
+        complex128 array in the ABI's form to start from (a warm start) - it is updated in place and returned - or None to
+        start from 1.  Returns (gains, stats), stats the 8 values [iterations, last rel, chi^2, chi^2 at g = 1, n_used,
+        n_flagged, n_dropped, n_unsolved].  numpy arrays take the synchronous host form; torch cuda tensors the
+        asynchronous one on torch's stream, and both results are cuda tensors: nothing is read back."""
+        be = backend(vis)
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, nant, slot, nslots, weights)
+        model_vis = stream_array(be, model_vis, be.c128, n, "model_vis")
+        mode, refant, warm, niter, tol, gains = solve_args(be, phase_only, refant, niter, tol, gains, A, T, vis)
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "gaincal", n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+        return gains, stats
+
+    def apply_gains(self, gains, vis, a1, a2, *, slot=None, inverse=True, weights=None, out=None, weights_out=None):
+        """Apply the (nslots, nant) gains to a visibility stream (gridhip_apply_gains[_dev]).  inverse=True corrects data:
+        vis / (g[slot, a1] conj(g[slot, a2])) and weights |g[a1]|^2 |g[a2]|^2 times `weights` (None: ones); a visibility
+        whose indices are out of range or whose gains are zero or not finite keeps its value and gets the weight +0.0,
+        the flag of Context.weights.  inverse=False corrupts a model: g[a1] vis conj(g[a2]), weights copied.  out and
+        weights_out: the arrays to write (new ones when None); they may be `vis` and `weights` themselves.  Returns
+        (vis_out, weights_out)."""
+        be = backend(vis)
+        if not hasattr(gains, "shape") or len(gains.shape) != 2:
+            raise ValueError("gains must be of shape (nslots, nant)")
+        T, A = int(gains.shape[0]), int(gains.shape[1])
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, A, slot, T, weights)
+        gains = stream_array(be, gains.reshape(-1), be.c128, T * A, "gains")
+        out = result_array(be, out, be.c128, (n,), "out", vis)
+        weights_out = result_array(be, weights_out, be.f64, (n,), "weights_out", vis)
+        self._call(be, "apply_gains", n, A, T, a1, a2, slot, gains, int(bool(inverse)), vis, wt, out, weights_out)
+        return out, weights_out
+
     def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None, weighting="uniform", robust=0.0, taper=0.0, weights=None):
         """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
         and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
@@ -875,6 +914,27 @@ class Imager(_Bound):
         self._call(be, "imager_mfdeconvolve", vis, models, out, int(nmajor),
                    *clean_scalars(gain, threshold, niter, border, patch), stats)
         return models, out, stats
+
+    def selfcal(self, model, vis, a1, a2, nant, *, slot=None, nslots=1, weights=None, phase_only=False, refant=0,
+                niter=50, tol=1e-8, gains=None, out=None, weights_out=None):
+        """One self-calibration step (gridhip_imager_selfcal_dev): predict(model), Context.gaincal of `vis` against it
+        and Context.apply_gains(inverse=True) of vis and weights, as one asynchronous chain that copies nothing and,
+        after a first call, can be captured into a graph.  a1, a2 (for an aw imager too), slot, weights, gains, out and
+        weights_out are cuda tensors as in those calls; out may be vis and weights_out may be weights.  Returns (gains,
+        vis_cal, wt_cal, stats): vis_cal goes into cycle or deconvolve, wt_cal is what a re-weighted imager is created
+        with."""
+        self._open()
+        be = device()
+        self._ok(model, be.f64, (self.N, self.N), "model")
+        self._ok(vis, be.c128, (self.n,), "vis")
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, nant, slot, nslots, weights)
+        mode, refant, warm, niter, tol, gains = solve_args(be, phase_only, refant, niter, tol, gains, A, T, self.device)
+        out = result_array(be, out, be.c128, (n,), "out", self.device)
+        weights_out = result_array(be, weights_out, be.f64, (n,), "weights_out", self.device)
+        stats = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_selfcal", model, vis, A, T, a1, a2, slot, wt, mode, refant, warm, niter, tol, gains, out,
+                   weights_out, stats)
+        return gains, out, weights_out, stats
 
     def weight_stats(self):
         """The stats of the weighting the imager was created with (gridhip_imager_weight_stats_dev): Context.weights'

@@ -45,6 +45,8 @@ _FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
 _RESTORE = [vp, i64, vp, vp, vp, i64, vp]
 _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_double, vp, vp]
 _WEIGHTING = [ci, C.c_double, C.c_double, vp]  # mode, robust, taper_sigma, wt_in
+_GAINCAL = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]
+_APPLY_GAINS = [vp, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -157,6 +159,11 @@ SIGNATURES = {
     "gridhip_imager_mfs_cycle_dev": (ci, [vp, vp, vp, vp, vp]),
     "gridhip_imager_mfclean_dev": (ci, [vp, vp, vp, C.c_double, C.c_double, i64, i64, i64, vp]),
     "gridhip_imager_mfdeconvolve_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64, vp]),
+    "gridhip_gaincal": (ci, _GAINCAL),
+    "gridhip_gaincal_dev": (ci, _GAINCAL),
+    "gridhip_apply_gains": (ci, _APPLY_GAINS),
+    "gridhip_apply_gains_dev": (ci, _APPLY_GAINS),
+    "gridhip_imager_selfcal_dev": (ci, [vp, vp, vp, i64, i64, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp, vp, vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

@@ -276,6 +276,76 @@ def weighting(be, mode, robust, taper, weights, n):
     return WEIGHTINGS[mode], robust, taper, weights
 
 
+def _integers(be, x, n, what):
+    """an index array as the ABI takes it: n int64 values of `be`'s own kind; other integer widths are converted, any
+    other dtype (a float index is a mistake, not a format) and any other length are refused"""
+    if be is HOST:
+        x = np.asarray(x)
+        integral = x.dtype.kind in "iu"
+    else:
+        integral = is_torch(x) and not (x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == be.torch.bool)
+    if not integral:
+        raise ValueError(f"{what} must be an integer {be.array}, not {getattr(x, 'dtype', type(x))}")
+    if tuple(x.shape) != (n,):
+        raise ValueError(f"{what} must hold one index per visibility ({n}), not {tuple(x.shape)}")
+    return be.cv(x, be.i64)
+
+
+def stream_array(be, x, dt, n, what):
+    """a per-visibility input: n values converted to dt where they must be, or None"""
+    if x is None:
+        return None
+    if be is not backend(x) and be is not HOST:
+        raise ValueError(f"{what} must be a {be.array}")
+    if be is HOST:
+        x = np.asarray(x)
+    if dt is be.f64 and (x.dtype.kind == "c" if be is HOST else x.dtype.is_complex):
+        raise ValueError(f"{what} must be real, not {x.dtype}")
+    if n < 0:
+        n = int(x.shape[0]) if len(x.shape) == 1 else -1
+    if tuple(x.shape) != (n,):
+        raise ValueError(f"{what} must be one-dimensional with one value per visibility, not of shape {tuple(x.shape)}")
+    return be.cv(x, dt)
+
+
+def result_array(be, x, dt, shape, what, like):
+    """an output: the caller's own array in the ABI's form (it is written in place), or a new one"""
+    if x is None:
+        return be.empty(shape, dt, like)
+    if not (be is backend(x) and be.ok(x, dt) and tuple(x.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be a {be.array} of shape {tuple(shape)} and the output's dtype (it is written in place)")
+    return x
+
+
+def gain_stream(be, vis, a1, a2, nant, slot, nslots, weights):
+    """n, A, T, a1, a2, slot, vis, wt as gridhip_gaincal, gridhip_apply_gains and gridhip_imager_selfcal_dev take the
+    visibility stream: slot None goes as NULL and needs nslots == 1."""
+    vis = stream_array(be, vis, be.c128, -1, "vis")  # (its length is the stream's: any one-dimensional array)
+    n, A, T = int(vis.shape[0]), int(nant), int(nslots)
+    if A < 2 or T < 1:
+        raise ValueError("nant must be >= 2 and nslots >= 1")
+    if slot is None and T != 1:
+        raise ValueError("nslots > 1 needs slot, the solution interval of every visibility")
+    a1, a2 = _integers(be, a1, n, "a1"), _integers(be, a2, n, "a2")
+    slot = None if slot is None else _integers(be, slot, n, "slot")
+    return n, A, T, a1, a2, slot, vis, stream_array(be, weights, be.f64, n, "weights")
+
+
+def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like):
+    """mode, refant, warm, niter, tol, gains as the solving entry points take them: refant None is -1 (no rotation); gains
+    None starts from 1 in a new [T][A] array, a given one - in the ABI's form: it is updated in place - is the warm start."""
+    import math
+    refant = -1 if refant is None else int(refant)
+    niter, tol = int(niter), float(tol)
+    if refant >= A:
+        raise ValueError(f"refant must be below nant ({A}), or None")
+    if niter < 0 or not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError("niter must be >= 0 and tol finite and >= 0")
+    warm = int(gains is not None)
+    gains = result_array(be, gains, be.c128, (T, A), "gains", like)
+    return int(bool(phase_only)), refant, warm, niter, tol, gains
+
+
 class Handle:
     """Owner of one library handle `_h` (a context, plan, imager or communicator): destroyed once, by close() or by the
     collector; _call passes it to an entry point and raises GridHipError with the owner's last-error text."""
