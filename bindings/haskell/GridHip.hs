@@ -44,6 +44,7 @@ module GridHip
   , Weighting(..), WeightMode(..), weightsIO, imagerCreateWeightedIO, imagerCreateAwWeightedIO, imagerDestroyIO
   , imagerWeightStatsIO
   , GainSolve(..), gaincalIO, applyGainsIO, imagerSelfcalIO
+  , dftPredictIO, componentsFromImageIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -392,6 +393,18 @@ foreign import ccall unsafe "gridhip_apply_gains_dev"
 -- int gridhip_imager_selfcal_dev(imager, model, vis, A, T, a1, a2, slot, wt, mode, refant, warm, niter, tol, gains, vis_cal, wt_cal, stats)
 foreign import ccall unsafe "gridhip_imager_selfcal_dev"
   c_imager_selfcal_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
+foreign import ccall unsafe "gridhip_dft_predict"
+  c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_dft_predict_dev(ctx, C, comps, count_dev, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
+foreign import ccall unsafe "gridhip_dft_predict_dev"
+  c_dft_predict_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_components_from_image(ctx, theta, lam, T, model, max_c, comps, count)
+foreign import ccall unsafe "gridhip_components_from_image"
+  c_components_from_image :: Ptr Ctx -> CDouble -> Int64 -> CInt -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr Int64 -> IO CInt
+-- int gridhip_components_from_image_dev(ctx, theta, lam, T, model, max_c, comps, count)
+foreign import ccall unsafe "gridhip_components_from_image_dev"
+  c_components_from_image_dev :: Ptr Ctx -> CDouble -> Int64 -> CInt -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr Int64 -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -1313,6 +1326,38 @@ imagerSelfcalIO (ImagerH h@(GridHip c) p n n') solve nant nslots ant1 ant2 slot 
                   map realToFrac <$> peekArray 8 pst
   return (A.fromForeignPtrs (A.Z A.:. nslots A.:. nant) (castForeignPtr g), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out),
           A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Direct-Fourier prediction (include/gridhip.h, "direct-Fourier prediction"): the exact visibilities of a component
+-- list, and a model image as such a list.
+
+-- | dftPredictIO h terms comps p x sub: sum_c S_c(x) E_c exp(-2 pi i (u l + v m + w (n - 1))) for the [C][10] component
+-- rows {l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0} at the baselines p (wavelengths, not mirrored), or sub minus it, and the
+-- 4 stats [used, skipped, non-finite visibilities, slices] - the host form, synchronous.  x Nothing: x = 0.
+dftPredictIO :: GridHip -> Int -> A.Matrix F -> A.Vector BaseLines -> Maybe (A.Vector F) -> Maybe (A.Vector Visibility)
+             -> IO (A.Vector Visibility, [F])
+dftPredictIO h@(GridHip c) terms comps p x sub = do
+  let A.Z A.:. n = A.arrayShape p
+      A.Z A.:. ncomp A.:. _ = A.arrayShape comps
+      withX k = maybe (k nullPtr) (\s -> withF s k) x
+      withSub k = maybe (k nullPtr) (\s -> withCplx s k) sub
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  st <- withF comps $ \pc -> withUVW p $ \pu pv pw -> withX $ \px -> withSub $ \ps -> withForeignPtr out $ \po ->
+          allocaArray 4 $ \pst -> do
+            c_dft_predict c (fi ncomp) pc nullPtr (fi terms) (fi n) pu pv pw 1 px ps po pst >>= check h
+            map realToFrac <$> peekArray 4 pst
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out), st)
+
+-- | componentsFromImageIO h theta lam terms maxc model: the non-zero cells of the [terms][N][N] model as point components
+-- in row-major order -> (the [maxc][10] rows, of which the first min found maxc are written, the number found)
+componentsFromImageIO :: GridHip -> F -> Int -> Int -> Int -> A.Array A.DIM3 F -> IO (A.Matrix F, Int)
+componentsFromImageIO h@(GridHip c) theta lam terms maxc model = do
+  out <- mallocForeignPtrArray (10 * maxc) :: IO (ForeignPtr CDouble)
+  found <- withF model $ \pm -> withForeignPtr out $ \po -> alloca $ \pn -> do
+             mapM_ (\i -> pokeElemOff po i 0) [0 .. 10 * maxc - 1]
+             c_components_from_image c (realToFrac theta) (fi lam) (fi terms) pm (fi maxc) po pn >>= check h
+             fromIntegral <$> peek pn
+  return (A.fromForeignPtrs (A.Z A.:. maxc A.:. 10) (castForeignPtr out), found)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 210 /* 0.2.1 */
+#define GRIDHIP_VERSION 220 /* 0.2.2 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -129,6 +129,8 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *   "rec_bits"  TEST HOOK: pretend the 64-bit record word has this many bits (16..63), so that small calls take the
  *               path that grids a call in several parts (taken for real above 2^50 slices x visibilities);
  *               100 + t: widen the record's kernel-slice field until its fields take t <= 64 bits
+ *   "dft_slices"  gridhip_dft_predict: the slices S the component list is cut into; 0 = auto (a function of n and C
+ *               alone), 1..64 = that many (values above 64 count as 64)
  *   ("dbg", the ablation / profiling switch of tuning runs, exists only in the tuning build of the library,
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
@@ -1018,6 +1020,80 @@ int gridhip_imager_selfcal_dev(gridhip_imager *imager, const double *model, cons
                                const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
                                int64_t refant, int warm, int64_t niter, double tol, double *gains, double *vis_cal,
                                double *wt_cal, double *stats);
+
+/* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
+ * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image
+ * and a degridder; this one evaluates the measurement equation itself,
+ *     V(u,v,w) = sum_c S_c(x) E_c(u,v) exp(-2 pi i (u l_c + v m_c + w (n_c - 1))),
+ * for a catalogue, for a source outside the imaged field, or as the exact model a calibration solves against.
+ * COMPONENTS  comps is [C][GRIDHIP_COMP_DOUBLES = 10] doubles, one row per component:
+ *                 { l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0 }
+ *     l, m      direction cosines relative to the phase centre.  The pixel [y][x] of an N x N image, N =
+ *               gridhip_image_size(theta, lam), lies at l = theta (x - N/2) / N, m = theta (y - N/2) / N with the integer
+ *               N/2 (the product first, then the quotient); with this the DFT at an integer cell (u, v) = (i, j) / theta
+ *               equals fft_c(model)[N/2 + j][N/2 + i], gridhip_predict's simple kind, for even and odd N
+ *     flux      S(x) = f0 + x (f1 + x (f2 + x f3)) by Horner with every product rounded; x is per visibility, (nu - nu_0) /
+ *               nu_0 as gridhip_imager_set_spectral_dev takes it.  T in 1..4 says how many f are read: f_T .. f3 are
+ *               ignored (taken as 0).  x == NULL means x = 0: only f0 counts, though f0 .. f_{T-1} are still read and must
+ *               be finite.
+ *     shape     bmaj == 0 && bmin == 0: a point, E = 1 and no exp is evaluated.  Otherwise an elliptical Gaussian with
+ *               FWHM axes bmaj >= bmin >= 0 in direction-cosine units and position angle bpa in radians from +m towards +l:
+ *                   E = exp(-(pi^2 / (4 ln 2)) (bmaj^2 up^2 + bmin^2 vp^2)),  up = u sin bpa + v cos bpa,
+ *                                                                           vp = u cos bpa - v sin bpa
+ *               (evaluated as a quadratic form quu u^2 + quv u v + qvv v^2 whose coefficients are formed once per call).
+ *               The tenth double is reserved and not read.
+ *     n - 1     = -r2 / (1 + sqrt(1 - r2)), r2 = l^2 + m^2: the subtraction form cancels.
+ *     SIGN      the phase is -2 pi (u l + v m + w (n - 1)): the minus sign of the forward transform, and w (n - 1) as the
+ *               far field of gridhip_w_kernel, exp(+2 pi i w (1 - n)), which a prediction sees unconjugated.
+ *     phase     formed in turns: p = u l + v m + w (n - 1) in fp64, r = p - rint(p), which is exact, then the sine and
+ *               cosine of 2 pi r with |r| <= 1/2.  fp64 throughout.  With |p| <= 1e4 turns the error of a visibility is
+ *               below 1e-10 sum_c |S_c|.
+ *     SKIPPED   a component contributes exactly nothing and is counted when any of l, m, f0 .. f_{T-1}, bmaj, bmin, bpa is
+ *               not finite, r2 > 1, bmaj < bmin or bmin < 0, or when the quadratic form of its Gaussian is not finite
+ *               in fp64: an axis whose square overflows, bmaj above about 1e154.
+ * VISIBILITIES  u, v, w in wavelengths with uv_stride as everywhere else, un-mirrored; w == NULL means w = 0; x: n doubles
+ *     or NULL.  A visibility with a non-finite u, v or w, or a non-finite x when x is given, predicts exactly 0 and is
+ *     counted.  vis_out = pred, or vis_sub - pred (the residual) when vis_sub != NULL - vis_sub[k] itself for such a
+ *     visibility.  vis_out == vis_sub is allowed.  vis_out is overwritten, never accumulated.
+ * count_dev   a device int64 (the host form: a host int64), or NULL.  When given, the call uses min(max(*count_dev, 0), C)
+ *     components and reads no row after them, so a list built on the device - gridhip_components_from_image_dev's - is
+ *     predicted with nothing read back.
+ * stats       optional, 4 doubles { components used, components skipped, visibilities with non-finite coordinates, the
+ *     slices S }.
+ * DETERMINISM.  For a given (n, C, options) the result has the same bits on every run: each visibility's sum runs over the
+ *     components in list order in one thread, with no atomics in the sum.  When n is too small to fill the device the list
+ *     is cut into S slices of ceil(C / S) components (S a function of n and C alone, or the option "dft_slices"), whose
+ *     partial sums are added in slice order; S changes the rounding of the sum, not its reproducibility.
+ * FROM A MODEL IMAGE.  gridhip_components_from_image turns model[T][N][N] (T Taylor-term planes as gridhip_mfclean leaves
+ *     them; T = 1: the model of clean or msclean) into a list: every cell where some term is not zero (a NaN is not zero)
+ *     becomes a point component - its l, m by the rule above, f_t the cell's terms, the unused f and the shape fields 0 -
+ *     in row-major order, by an ordered compaction (per-segment counts, an exclusive scan, a scatter): the same list on
+ *     every run.  *count receives the number found even when it exceeds max_c; only the first max_c rows are written, and
+ *     the rows after the last one written are left as they were.  In the _dev form count is a device int64.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL context; n < 0; C < 0; T outside 1..4; a
+ * NULL comps with C > 0 (max_c > 0); a NULL u, v or vis_out with n > 0; uv_stride < 1; vis_out overlapping anything but
+ * vis_sub (and then only as vis_sub itself); stats overlapping any other argument; max_c < 0; a NULL model or count; an image size below 1; comps, count and
+ * model overlapping.  n of 2^31 - 256 or more and N above 2^20 are GRIDHIP_EUNSUPPORTED.  A refused call leaves its outputs
+ * unchanged.  n = 0 and C = 0 are valid: with C = 0 vis_out is 0, or vis_sub.
+ * The host forms are synchronous and stage through the context's pool.  The _dev forms take device pointers and enqueue
+ * kernels only on the context's stream - no memset node, no copy node; they allocate nothing after the first call of a
+ * shape (80 B of scratch per component, 16 S B per visibility when S > 1), never synchronise and read nothing back, so
+ * they can be captured into a graph.
+ * A prediction is: a pass that validates the components and converts each to { l, m, n - 1, f0 .. f3, quu, quv, qvv }; the
+ * main kernel, whose work-groups of 256 threads take 512 visibilities each - two per thread, in registers with their two
+ * complex sums - and stage the converted components through LDS in chunks of 256 (20 KB), every lane of a wave reading the
+ * same component; with S > 1 an epilogue that adds the partial sums and applies vis_sub. */
+#define GRIDHIP_COMP_DOUBLES 10
+int gridhip_dft_predict(gridhip_ctx *ctx, int64_t C, const double *comps, const int64_t *count, int T, int64_t n,
+                        const double *u, const double *v, const double *w, int64_t uv_stride, const double *x,
+                        const double *vis_sub, double *vis_out, double *stats);
+int gridhip_dft_predict_dev(gridhip_ctx *ctx, int64_t C, const double *comps, const int64_t *count_dev, int T, int64_t n,
+                            const double *u, const double *v, const double *w, int64_t uv_stride, const double *x,
+                            const double *vis_sub, double *vis_out, double *stats);
+int gridhip_components_from_image(gridhip_ctx *ctx, double theta, int64_t lam, int T, const double *model, int64_t max_c,
+                                  double *comps, int64_t *count);
+int gridhip_components_from_image_dev(gridhip_ctx *ctx, double theta, int64_t lam, int T, const double *model,
+                                      int64_t max_c, double *comps, int64_t *count);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

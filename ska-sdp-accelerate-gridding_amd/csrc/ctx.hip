@@ -481,6 +481,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "yield_cus")) return &ctx->opt.yield_cus;
     if (!strcmp(key, "bin_reuse")) return &ctx->opt.bin_reuse;
     if (!strcmp(key, "noise_bits")) return &ctx->img->noise_bits;  // image_stats' digit: 8, or anything else for 13
+    if (!strcmp(key, "dft_slices")) return &ctx->img->dft_slices;  // dft_predict's component slices: 0 = auto, 1..64
     return nullptr;
 }
 

@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, restore.hip, weights.hip, gaincal.hip).
+// msclean.hip, mfclean.hip, noise.hip, restore.hip, weights.hip, gaincal.hip, dft.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -38,6 +38,7 @@ struct ImagingState {
     bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
     bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
+    int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
 };
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled
@@ -477,5 +478,23 @@ int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t
 int apply_gains_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
                     double *vis_out, double *wt_out);
+
+// ---- direct-Fourier prediction of a component list (dft.hip) ---------------------------------------------------------------
+// gridhip_dft_predict's and gridhip_components_from_image's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); *N: the
+// image size
+int dft_predict_check(gridhip_ctx *ctx, int64_t C, const double *comps, const int64_t *count, int T, int64_t n,
+                      const double *u, const double *v, const double *w, int64_t stride, const double *x,
+                      const double *vis_sub, const double *vis_out, const double *stats);
+int components_check(gridhip_ctx *ctx, double theta, int64_t lam, int T, const double *model, int64_t max_c,
+                     const double *comps, const int64_t *count, int64_t *N);
+// the component slices S of a call: the option "dft_slices" when it is set, else a function of (n, C) alone
+int dft_slices(gridhip_ctx *ctx, int64_t n, int64_t C);
+// the _dev forms on checked arguments: kernels only, on ctx->stream; scratch (80 B per component, 16 S B per visibility
+// when S > 1, one row per work-group) from the context's pool
+int dft_predict_run(gridhip_ctx *ctx, int64_t C, const double *comps, const int64_t *count_dev, int T, int64_t n,
+                    const double *u, const double *v, const double *w, int64_t stride, const double *x,
+                    const double *vis_sub, double *vis_out, double *stats);
+int components_run(gridhip_ctx *ctx, int64_t N, double theta, int T, const double *model, int64_t max_c, double *comps,
+                   int64_t *count_dev);
 
 }  // namespace gridhip

@@ -17,6 +17,7 @@
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
+//   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -484,6 +485,45 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
                                   inverse ? 1 : 0, cd(vis), data.empty() ? nullptr : data.data(), cd(out),
                                   wt_out ? wt_out->data() : nullptr));
         return out;
+    }
+
+    // ---- direct-Fourier prediction (gridhip_dft_predict, gridhip_components_from_image; include/gridhip.h) ----
+    // (Host forms; the device-pointer forms are the C header's.)
+    struct DftStats {
+        F used, skipped, bad_vis, slices;
+    };
+    // The exact visibilities of the component rows {l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0} (comps: 10 doubles each) at
+    // the baselines uvw (wavelengths, not mirrored; w empty: 0), or sub minus them.  x empty: x = 0; terms: how many of f0..f3 count.
+    std::vector<Visibility> dft_predict(const std::vector<F> &comps, const BaseLines &uvw, Int terms = 1,
+                                        const std::vector<F> &x = {}, const std::vector<Visibility> &sub = {},
+                                        DftStats *stats = nullptr)
+    {
+        const Int n = (Int)uvw.size(), C = (Int)comps.size() / GRIDHIP_COMP_DOUBLES;
+        if ((Int)comps.size() != C * GRIDHIP_COMP_DOUBLES || (Int)uvw.v.size() != n || (!uvw.w.empty() && (Int)uvw.w.size() != n) ||
+            (!x.empty() && (Int)x.size() != n) || (!sub.empty() && (Int)sub.size() != n))
+            throw Error(GRIDHIP_EINVAL, "dft_predict: 10 doubles per component, one v, w, x and sub per visibility");
+        std::vector<Visibility> out((size_t)n);
+        F st[4] = {0, 0, 0, 0};
+        check(gridhip_dft_predict(ctx_, C, comps.data(), nullptr, (int)terms, n, uvw.u.data(), uvw.v.data(),
+                                  uvw.w.empty() ? nullptr : uvw.w.data(), 1, x.empty() ? nullptr : x.data(),
+                                  sub.empty() ? nullptr : cd(sub), cd(out), st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3]};
+        return out;
+    }
+    // The non-zero cells of model[terms][N][N] as point components in row-major order: at most max_c rows; *found gets the
+    // number of non-zero cells, which may exceed max_c
+    std::vector<F> components_from_image(F theta, Int lam, Int terms, const std::vector<F> &model, Int max_c,
+                                         Int *found = nullptr)
+    {
+        const Int N = gridhip_image_size(theta, lam);
+        if (max_c < 0 || (Int)model.size() != terms * N * N)
+            throw Error(GRIDHIP_EINVAL, "components_from_image: a model of terms x N x N, max_c >= 0");
+        std::vector<F> comps((size_t)max_c * GRIDHIP_COMP_DOUBLES, 0);
+        int64_t count = 0;
+        check(gridhip_components_from_image(ctx_, theta, lam, (int)terms, model.data(), max_c, comps.data(), &count));
+        comps.resize((size_t)(count < max_c ? count : max_c) * GRIDHIP_COMP_DOUBLES);
+        if (found) *found = count;
+        return comps;
     }
 
     // ---- helpers ----

@@ -26,9 +26,10 @@ from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
                        auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
 from ._marshal import gain_stream, result_array, solve_args, stream_array
+from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
 from ._marshal import weighting as _weighting
 
-__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError"]
+__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components"]
 
 
 class Context(Handle):
@@ -563,6 +564,52 @@ class Context(Handle):
         self._call(be, "apply_gains", n, A, T, a1, a2, slot, gains, int(bool(inverse)), vis, wt, out, weights_out)
         return out, weights_out
 
+    def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
+        """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
+        prediction"): sum_c S_c(x) E_c(u, v) exp(-2 pi i (u l_c + v m_c + w (n_c - 1))), or vis_sub minus that.  uvw
+        (wavelengths, not mirrored): a (u, v, w) tuple - w may be None: 0 - or an (n, 3) array; comps: a (C, 10) array of
+        rows {l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0} (gridhip.components, Context.components_from_image); x: the n
+        fractional frequency offsets the spectral terms are evaluated at (None: 0), terms: how many of f0..f3 are read;
+        count: one int64 element (for numpy also an int) - only the first min(max(count, 0), C) rows are used, which
+        takes a list built on the device without reading its length back.  out: the array to write (may be vis_sub
+        itself); a new one when None.  numpy in gives numpy out; torch cuda tensors take the device form on torch's
+        stream.  Returns out, or with stats=True (out, stats), stats the 4 values [components used, components skipped,
+        visibilities with non-finite coordinates, slices].  The same bits on every run."""
+        be = backend(comps)
+        C_, comps = component_list(be, comps)
+        u, v, w, st = baselines(be, uvw, 3)
+        n, T = int(u.shape[0]), int(terms)
+        if not 1 <= T <= 4:
+            raise ValueError("terms must be in 1..4")
+        x = stream_array(be, x, be.f64, n, "x")
+        sub = stream_array(be, vis_sub, be.c128, n, "vis_sub")
+        count = component_count(be, count, comps)
+        out = result_array(be, out, be.c128, (n,), "out", comps)
+        st4 = be.empty(4, be.f64, comps) if stats else None
+        self._call(be, "dft_predict", C_, comps, count, T, n, u, v, w, st, x, sub, out, st4)
+        return (out, st4) if stats else out
+
+    def components_from_image(self, theta, lam, model, max_components, out=None):
+        """The non-zero cells of a model image as a component list (gridhip_components_from_image[_dev]): model is N x N,
+        N = image_size(theta, lam), or (T, N, N) Taylor-term planes as mfclean leaves them; every cell where some term is
+        not zero becomes a point component at l = theta (x - N/2) / N, m = theta (y - N/2) / N, in row-major order, the
+        same list on every run.  Returns (comps, count): comps a (max_components, 10) array whose first min(count,
+        max_components) rows are written (out: the array to write; a new one of zeros when None), count the number
+        found - an int for numpy, one int64 cuda element for torch tensors, which dft_predict takes as `count` with
+        nothing read back."""
+        be = backend(model)
+        N, max_c = self.image_size(theta, lam), int(max_components)
+        T, model = model_planes(be, model, N)
+        if max_c < 0:
+            raise ValueError("max_components must be >= 0")
+        if out is None:
+            out = be.zeros((max_c, COMP_DOUBLES), be.f64, model)
+        else:
+            out = result_array(be, out, be.f64, (max_c, COMP_DOUBLES), "out", model)
+        count = be.zeros(1, be.i64, model)
+        self._call(be, "components_from_image", float(theta), int(lam), T, model, max_c, out, count)
+        return out, (int(count[0]) if be is HOST else count)
+
     def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None, weighting="uniform", robust=0.0, taper=0.0, weights=None):
         """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
         and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
@@ -974,6 +1021,28 @@ class Imager(_Bound):
 
 
 _default = {}
+
+
+def components(l, m, flux, spectral=None, fwhm=None, pa=None):
+    """Pack a component list for Context.dft_predict: l, m (direction cosines) and flux are C values each; spectral: a
+    (C, k) array, k <= 3, of the further polynomial coefficients f1..fk of S(x) = f0 + x (f1 + x (f2 + x f3)); fwhm: a
+    (C, 2) array of the Gaussian FWHM axes (bmaj, bmin) in direction cosines, None or 0: points; pa: C position angles in
+    radians from +m towards +l.  numpy in gives a (C, 10) float64 ndarray, torch tensors a tensor on l's device."""
+    be = backend(l)
+    l = be.cv(l, be.f64).reshape(-1)
+    n = int(l.shape[0])
+    out = be.zeros((n, COMP_DOUBLES), be.f64, l)
+    out[:, 0], out[:, 1], out[:, 2] = l, be.cv(m, be.f64).reshape(-1), be.cv(flux, be.f64).reshape(-1)
+    if spectral is not None:
+        sp = be.cv(spectral, be.f64).reshape(n, -1)
+        if sp.shape[1] > 3:
+            raise ValueError("spectral holds at most the three coefficients f1, f2, f3 per component")
+        out[:, 3:3 + sp.shape[1]] = sp
+    if fwhm is not None:
+        out[:, 6:8] = be.cv(fwhm, be.f64).reshape(n, 2)
+    if pa is not None:
+        out[:, 8] = be.cv(pa, be.f64).reshape(-1)
+    return out
 
 
 def default_context(device=0):

@@ -47,6 +47,8 @@ _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_doubl
 _WEIGHTING = [ci, C.c_double, C.c_double, vp]  # mode, robust, taper_sigma, wt_in
 _GAINCAL = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]
 _APPLY_GAINS = [vp, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+_DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+_COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -164,6 +166,10 @@ SIGNATURES = {
     "gridhip_apply_gains": (ci, _APPLY_GAINS),
     "gridhip_apply_gains_dev": (ci, _APPLY_GAINS),
     "gridhip_imager_selfcal_dev": (ci, [vp, vp, vp, i64, i64, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp, vp, vp]),
+    "gridhip_dft_predict": (ci, _DFT_PREDICT),
+    "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
+    "gridhip_components_from_image": (ci, _COMPONENTS),
+    "gridhip_components_from_image_dev": (ci, _COMPONENTS),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

@@ -346,6 +346,43 @@ def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like):
     return int(bool(phase_only)), refant, warm, niter, tol, gains
 
 
+COMP_DOUBLES = 10  # GRIDHIP_COMP_DOUBLES: { l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0 }
+
+
+def component_list(be, comps):
+    """C, comps as gridhip_dft_predict takes a component list: a (C, 10) float64 array of `be`'s own kind (the rows of
+    gridhip.components or of Context.components_from_image), converted where it must be"""
+    if be is not backend(comps) or not hasattr(comps, "shape"):
+        raise ValueError(f"comps must be a {be.array} of shape (C, {COMP_DOUBLES})")
+    if len(comps.shape) != 2 or int(comps.shape[1]) != COMP_DOUBLES:
+        raise ValueError(f"comps must be of shape (C, {COMP_DOUBLES}), not {tuple(comps.shape)}")
+    if comps.dtype.kind == "c" if be is HOST else comps.dtype.is_complex:
+        raise ValueError(f"comps must be real, not {comps.dtype}")
+    return int(comps.shape[0]), be.cv(comps, be.f64)
+
+
+def component_count(be, count, like):
+    """count as gridhip_dft_predict takes it, or None: one int64 element of `be`'s own kind - on the device nothing is read
+    back - or, for host arrays, a number"""
+    if count is None:
+        return None
+    if be is HOST and isinstance(count, (int, np.integer)):
+        return np.array([count], dtype=np.int64)
+    if be is not backend(count) or not be.ok(count, be.i64) or int(np.prod(tuple(count.shape))) != 1:
+        raise ValueError(f"count must be a {be.array} of one int64 element" + (" or an int" if be is HOST else ""))
+    return count
+
+
+def model_planes(be, model, N):
+    """T, model as gridhip_components_from_image takes a model: (N, N), or (T, N, N) with T in 1..4, float64"""
+    shape = tuple(getattr(model, "shape", ()))
+    if shape == (N, N):
+        shape = (1, N, N)
+    if len(shape) != 3 or shape[1:] != (N, N) or not 1 <= shape[0] <= 4:
+        raise ValueError(f"model must be {N} x {N} (image_size(theta, lam)) or T of them, T in 1..4, not {shape}")
+    return shape[0], be.cv(model, be.f64)
+
+
 class Handle:
     """Owner of one library handle `_h` (a context, plan, imager or communicator): destroyed once, by close() or by the
     collector; _call passes it to an entry point and raises GridHipError with the owner's last-error text."""
