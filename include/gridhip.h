@@ -105,6 +105,10 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               next call after it runs its pre-pass in full
  *   "aw_cache"  aw gridders: 1 (default) = build each distinct (a1, a2, wbin, yf, xf) kernel once per call and let
  *               the visibilities that share it reuse it; 0 = one kernel per visibility (as the reference evaluates)
+ *   "aw_batch"  aw gridders, degridders and plans: visibilities per batch of the kernel table.  0 (default) = 2^20 with
+ *               "aw_cache", 2^22 without; k > 0 = min(k, that).  For tests of the batch loop and for bounding the scratch
+ *               memory (one S x S kernel per visibility of a batch).  The one option that can be set negative: every aw
+ *               entry point then returns GRIDHIP_EINVAL before it touches anything.  A plan keeps the batches it was made with
  *   "fault_inject"  TEST HOOK: hides the last k slots of the record array from the pre-pass's scatter so that its
  *               bounds checks have something to reject (counted in "errors"; results are then incomplete)
  *   "reserve_cus"  compute units the persistent tile kernel leaves free (0 = none): it launches one work-group per

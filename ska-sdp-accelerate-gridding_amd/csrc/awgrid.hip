@@ -502,7 +502,10 @@ static int aw_setup(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t 
     // The table of kernels is sized for the batch whatever the de-duplication finds (nothing is read back inside a
     // call): 2^20 visibilities per batch with the cache (3.8 GB of table at 15 x 15; the 10^6-visibility benchmark is
     // one batch), 2^22 without it, where every visibility has a kernel of its own anyway (15 GB).
-    const int64_t bcap = cache_on(ctx) ? ((int64_t)1 << 20) : ((int64_t)1 << 22);
+    // Option "aw_batch" (> 0) lowers that: fewer visibilities per batch bound the scratch, and let a test run the batch
+    // loop at sizes an oracle can follow.
+    int64_t bcap = cache_on(ctx) ? ((int64_t)1 << 20) : ((int64_t)1 << 22);
+    if (ctx->opt.aw_batch > 0 && ctx->opt.aw_batch < bcap) bcap = ctx->opt.aw_batch;
     c->batch = n < bcap ? n : bcap;
     c->pair_cap = (int32_t)(pairs < (size_t)n ? pairs : (size_t)n);
     c->hslots = 1024;
@@ -652,6 +655,7 @@ static int aw_args_ok(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_
     if (H <= 0 || Wd <= 0 || n < 0 || W <= 0 || Q <= 0 || S <= 0 || A <= 0 || uv_stride < 1 || !has_grid || !wkerns ||
         !akerns || (n > 0 && (!u || !v || !wbin || !a1 || !a2 || !has_vis)))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    if (ctx->opt.aw_batch < 0) return fail(ctx, GRIDHIP_EINVAL, "option 'aw_batch' must be >= 0");
     return GRIDHIP_OK;
 }
 

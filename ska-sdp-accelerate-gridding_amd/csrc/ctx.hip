@@ -470,6 +470,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "prepass")) return &ctx->opt.prepass;
     if (!strcmp(key, "fault_inject")) return &ctx->opt.fault_inject;
     if (!strcmp(key, "aw_cache")) return &ctx->opt.aw_cache;
+    if (!strcmp(key, "aw_batch")) return &ctx->opt.aw_batch;
     if (!strcmp(key, "coarse_shift")) return &ctx->opt.coarse_shift;
     if (!strcmp(key, "scatter_chunk")) return &ctx->opt.scatter_chunk;
     if (!strcmp(key, "count_unroll")) return &ctx->opt.count_unroll;
@@ -490,7 +491,8 @@ int gridhip_set_option(gridhip_ctx *ctx, const char *key, int64_t value)
     if (!ctx || !key) return GRIDHIP_EINVAL;
     int64_t *s = opt_slot(ctx, key);
     if (!s) return fail(ctx, GRIDHIP_EINVAL, "unknown option '%s'", key);
-    if (value < 0) return fail(ctx, GRIDHIP_EINVAL, "option '%s' must be >= 0", key);
+    // ("aw_batch" keeps a negative value as given: the aw entry points refuse it, before they touch anything)
+    if (value < 0 && s != &ctx->opt.aw_batch) return fail(ctx, GRIDHIP_EINVAL, "option '%s' must be >= 0", key);
     *s = value;
     return GRIDHIP_OK;
 }

@@ -210,6 +210,7 @@ int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed)
     if (*N <= 0 || a.n < 0 || a.stride < 1 || a.W <= 0 || a.Q <= 0 || a.S <= 0 || a.A <= 0 || !a.wkerns || !a.wvals ||
         !a.akerns || (a.n > 0 && (!a.u || !a.v || !a.w || !a.a1 || !a.a2 || (vis_needed && !a.vis))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    if (ctx->opt.aw_batch < 0) return fail(ctx, GRIDHIP_EINVAL, "option 'aw_batch' must be >= 0");
     return GRIDHIP_OK;
 }
 
