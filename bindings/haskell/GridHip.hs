@@ -36,6 +36,8 @@ module GridHip
   , mscleanIO, imagerMscleanIO, imagerMsDeconvolveIO, msDefaultBias
   -- * clean masks and noise-based stop levels: robust image statistics and the _auto forms (absent from the reference)
   , AutoOptions(..), imageStatsIO, cleanAutoIO, imagerDeconvolveAutoIO
+  -- * auto-masking: the clean mask from the map itself, alone or inside the major-cycle loop (absent from the reference)
+  , AutomaskOptions(..), automaskIO, imagerDeconvolveAutomaskIO
   -- * wide-band imaging: Taylor-term major cycles and the multi-term CLEAN (absent from the reference)
   , mfcleanIO, imagerSetSpectralIO, imagerMfsCycleIO, imagerMfDeconvolveIO
   -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
@@ -324,6 +326,21 @@ foreign import ccall unsafe "gridhip_imager_deconvolve_auto_dev"
 -- int gridhip_imager_msdeconvolve_auto_dev(imager, vis, model, image, nmajor, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, peak_frac, stats, istats)
 foreign import ccall unsafe "gridhip_imager_msdeconvolve_auto_dev"
   c_imager_msdeconvolve_auto_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_automask(ctx, N, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, grow, stats)
+foreign import ccall unsafe "gridhip_automask"
+  c_automask :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Word8 -> Int64 -> CInt -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_automask_dev(ctx, N, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, grow, stats)
+foreign import ccall unsafe "gridhip_automask_dev"
+  c_automask_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Word8 -> Int64 -> CInt -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_automask_dev(imager, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, grow, stats)
+foreign import ccall unsafe "gridhip_imager_automask_dev"
+  c_imager_automask_dev :: Ptr Imager -> Ptr CDouble -> Ptr Word8 -> Int64 -> CInt -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_deconvolve_automask_dev(imager, vis, model, image, nmajor, gain, threshold, niter, border, patch, mask, nsigma, peak_frac_clean, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, peak_frac, min_cells, grow, stats, istats, astats)
+foreign import ccall unsafe "gridhip_imager_deconvolve_automask_dev"
+  c_imager_deconvolve_automask_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> CDouble -> CInt -> CDouble -> CDouble -> CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_msdeconvolve_automask_dev(imager, vis, model, image, nmajor, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, peak_frac_clean, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, peak_frac, min_cells, grow, stats, istats, astats)
+foreign import ccall unsafe "gridhip_imager_msdeconvolve_automask_dev"
+  c_imager_msdeconvolve_automask_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> CDouble -> CInt -> CDouble -> CDouble -> CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_fit_beam(ctx, N, psf, window, cut, beam)
 foreign import ccall unsafe "gridhip_fit_beam"
   c_fit_beam :: Ptr Ctx -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
@@ -970,6 +987,63 @@ imagerDeconvolveAutoIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa)
           ist <- rows8 pis
           let sh = A.Z A.:. n' A.:. n'
           return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st, ist)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Auto-masking (include/gridhip.h, "auto-masking"): two levels, islands above the higher one pruned by size, kept with
+-- the whole island above the lower level they lie in, grown, and OR-ed into the mask.
+
+-- | absolute, (thr_hi, thr_lo), (nsigma_hi, nsigma_lo), peak_frac, min_cells, grow of gridhip_automask
+data AutomaskOptions = AutomaskOptions { amAbsolute :: Bool, amThr :: (F, F), amNsigma :: (F, F), amPeakFrac :: F
+                                       , amMinCells :: Int, amGrow :: Int }
+
+-- | automaskIO h opts sigma border image mask: (the updated mask, [T_hi, T_lo, P, components of H, surviving the prune,
+-- components of L kept, cells newly set, reason]); sigma is the noise the nsigma terms multiply (element 3 of
+-- imageStatsIO) - gridhip_automask, the host form, synchronous
+automaskIO :: GridHip -> AutomaskOptions -> F -> Int -> A.Matrix F -> [Word8] -> IO ([Word8], [F])
+automaskIO h@(GridHip c) (AutomaskOptions ab (th, tl) (nh, nl) pf mc gr) sigma border image mask = do
+  let A.Z A.:. n' A.:. _ = A.arrayShape image
+  withF image $ \pi' -> withArray mask $ \pk -> with (realToFrac sigma :: CDouble) $ \pn -> allocaArray 8 $ \ps -> do
+    c_automask c (fi n') pi' pk (fi border) (if ab then 1 else 0) (realToFrac th) (realToFrac tl) (realToFrac nh)
+      (realToFrac nl) pn (realToFrac pf) (fi mc) (fi gr) ps >>= check h
+    m <- peekArray (n' * n') pk
+    st <- map realToFrac <$> peekArray 8 ps
+    return (m, st)
+
+-- | imagerDeconvolveAutomaskIO im opts auto am nmajor vis model: imagerDeconvolveAutoIO whose mask every major cycle
+-- extends from the map it is about to clean (gridhip_imager_deconvolve_automask_dev); autoMask is the starting mask
+-- (Nothing: zeros).  Returns (the model, the closing residual image, the accumulated mask, and per major cycle one row of
+-- 8 clean stats, one of 8 image stats and one of 8 automask stats)
+imagerDeconvolveAutomaskIO :: ImagerH -> CleanOptions -> AutoOptions -> AutomaskOptions -> Int -> A.Vector Visibility
+                           -> A.Matrix F -> IO (A.Matrix F, A.Matrix F, [Word8], [[F]], [[F]], [[F]])
+imagerDeconvolveAutomaskIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) (AutoOptions mask ns pf)
+                           (AutomaskOptions ab (th, tl) (nh, nl) apf mc gr) nmajor vis model = do
+  img <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  mdl <- mallocForeignPtrArray (n' * n') :: IO (ForeignPtr CDouble)
+  let bytes = 8 * n' * n'
+      rows = max 0 nmajor
+      rows8 q = mapM (\r -> map realToFrac <$> peekArray 8 (q `advancePtr` (8 * r))) [0 .. rows - 1]
+      start = maybe (replicate (n' * n') 0) id mask
+  withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withF model $ \pm -> withDev h pm bytes $ \dm ->
+    withForeignPtr img $ \pi' -> withDev h pi' bytes $ \di -> allocaArray (8 * rows) $ \ps ->
+      withDev h ps (64 * rows) $ \ds -> allocaArray (8 * rows) $ \pis -> withDev h pis (64 * rows) $ \dis ->
+        allocaArray (8 * rows) $ \pas -> withDev h pas (64 * rows) $ \das ->
+          withArray start $ \pk -> withDev h pk (n' * n') $ \dk -> withForeignPtr mdl $ \pq -> do
+            c_imager_deconvolve_automask_dev p dv dm di (fi nmajor) (realToFrac g) (realToFrac t) (fi ni) (fi b) (fi pa) dk
+              (realToFrac ns) (realToFrac pf) (if ab then 1 else 0) (realToFrac th) (realToFrac tl) (realToFrac nh)
+              (realToFrac nl) (realToFrac apf) (fi mc) (fi gr) ds dis das >>= check h
+            c_memcpy_d2h c (castPtr pi') (castPtr di) (fi bytes) >>= check h
+            c_memcpy_d2h c (castPtr pq) (castPtr dm) (fi bytes) >>= check h
+            c_memcpy_d2h c (castPtr pk) (castPtr dk) (fi (n' * n')) >>= check h
+            c_memcpy_d2h c (castPtr ps) (castPtr ds) (fi (64 * rows)) >>= check h
+            c_memcpy_d2h c (castPtr pis) (castPtr dis) (fi (64 * rows)) >>= check h
+            c_memcpy_d2h c (castPtr pas) (castPtr das) (fi (64 * rows)) >>= check h
+            c_synchronize c >>= check h
+            st <- rows8 ps
+            ist <- rows8 pis
+            ast <- rows8 pas
+            m <- peekArray (n' * n') pk
+            let sh = A.Z A.:. n' A.:. n'
+            return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), m, st, ist, ast)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- Multi-scale deconvolution (include/gridhip.h, "multi-scale deconvolution"): scales in cells increasing from 0, one

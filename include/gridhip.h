@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 220 /* 0.2.2 */
+#define GRIDHIP_VERSION 230 /* 0.2.3 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -730,6 +730,90 @@ int gridhip_imager_msdeconvolve_auto_dev(gridhip_imager *imager, const double *v
                                          double threshold, int64_t niter, int64_t border, int64_t patch,
                                          const uint8_t *mask, double nsigma, double peak_frac, double *stats,
                                          double *istats);
+
+/* ---- auto-masking: the clean mask of a major cycle from the map it is about to clean, on the device ------------------------
+ * The reference has no masks at all: the semantics are defined here.  image is a real N x N image, row-major, k = y * N +
+ * x; mask is N x N bytes, UPDATED IN PLACE; border follows clean's rule.  A cell TAKES PART when
+ *     border <= y, x < N - border   and image[k] is finite (NaN and +-Inf never):
+ * gridhip_image_stats' rule without a mask.  v(k) = image[k], or |image[k]| when absolute != 0.
+ * LEVELS.  noise points to ONE double, sigma - on the device for the _dev and imager forms, on the host for the host form -
+ * so that element 3 of a gridhip_image_stats result can be passed as it is.  P is the maximum of v over the cells that
+ * take part (under image_stats' key order: +0.0 above -0.0).
+ *     T_hi = max(thr_hi, nsigma_hi * sigma, peak_frac * P)     each product rounded once
+ *     T_lo = max(thr_lo, nsigma_lo * sigma, peak_frac * P)
+ * A zero nsigma leaves its term out, and noise may be NULL when both are zero; a zero peak_frac leaves its term out.
+ * STEPS.  Connectivity is 8 everywhere.
+ *     1  H = { k takes part : v(k) > T_hi },  L = { k takes part : v(k) > T_lo }.  The comparison is strict: these are the
+ *        cells clean's |p| <= T test would not stop at.  H is a subset of L.
+ *     2  PRUNE.  The components of H are labelled; one with fewer than min_cells cells is dropped.  The seeds S are the
+ *        cells of the components that survive.
+ *     3  HYSTERESIS.  The components of L are labelled; one is kept if and only if it holds at least one cell of S.  K is
+ *        the union of the kept components.
+ *     4  GROW.  G = { k inside the border region : some cell of K lies within Chebyshev distance grow }.  grow is a host
+ *        argument (it fixes the launch shape).  A non-finite cell inside the region may be in G; nothing outside the border
+ *        region is ever set.
+ *     5  ACCUMULATE.  A cell with mask[k] != 0 keeps its byte; a cell of G with mask[k] == 0 becomes 1.  No bit is ever
+ *        cleared: a mask of zeros starts a run, and a caller's own regions are kept.
+ * A component's label is the smallest k in it, which makes every intermediate result unique: the whole result is a
+ * function of the input alone - the same bytes for the host, _dev and imager forms, for two runs, and for a flood fill on
+ * the host.
+ * stats is 8 doubles { T_hi, T_lo, P, components of H, of them surviving the prune, components of L kept, cells newly set,
+ * reason }, all exact counts or once-rounded products.  reason is 0 when the steps ran.  Otherwise the mask is left exactly
+ * as it was and the four counts are 0 - the first of these that holds:
+ *     3  an nsigma term is wanted and sigma is NaN: T_hi and T_lo are NaN, P is the maximum (NaN without one)
+ *     2  no cell takes part: P is NaN, and T_hi, T_lo are the levels without the peak_frac term
+ * Arguments, checked before anything is touched.  GRIDHIP_EINVAL: thr_lo > thr_hi or nsigma_lo > nsigma_hi; thr or nsigma
+ * negative or not finite; peak_frac outside [0, 1) or NaN; nsigma_hi > 0 with NULL noise; min_cells < 1; grow < 0; a NULL
+ * image, mask or stats; mask or stats overlapping image, or each other; N < 1; border < 0 or 2 * border >= N.  Then
+ * GRIDHIP_EUNSUPPORTED: grow > 32, or N > 46340 (labels are 32-bit cell indices).
+ * The labelling is a union-find with a fixed pass structure, never a propagation repeated until nothing changes: a
+ * work-group labels one 32 x 32 tile in LDS (each cell starts at the first cell of its horizontal run, runs are united
+ * with the row above by 32-bit atomicMin on roots); a second kernel unites cells across tile edges and across the corners
+ * where four tiles meet, in global memory; a third flattens.  label[k] <= k holds at every instant - a link always goes
+ * from the larger root to the smaller - which bounds every loop by the index it starts from, whatever other threads do.
+ * Component sizes are integer counts, taken per tile in LDS and added to the root once per (tile, component).  Growing is
+ * one LDS-tiled kernel with a halo of grow cells.  There is no floating-point atomic: levels are compared, never summed.
+ * gridhip_automask is synchronous and stages host arrays through the context's pool.  The _dev and imager forms enqueue
+ * kernels only on the context's stream - 13 launches whatever the image holds, no memset or copy node - allocate nothing
+ * after the first call, read nothing back and never synchronise: they can be captured.  Scratch (two int32 planes and a
+ * byte plane, 9 bytes per cell) comes from the context's pool, or for the imager forms from memory the imager owns; stats
+ * is on the device. */
+int gridhip_automask(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask, int64_t border, int absolute,
+                     double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise,
+                     double peak_frac, int64_t min_cells, int64_t grow, double *stats);
+int gridhip_automask_dev(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask, int64_t border, int absolute,
+                         double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise,
+                         double peak_frac, int64_t min_cells, int64_t grow, double *stats);
+/* gridhip_automask_dev with the imager's N and its own scratch */
+int gridhip_imager_automask_dev(gridhip_imager *imager, const double *image, uint8_t *mask, int64_t border, int absolute,
+                                double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise,
+                                double peak_frac, int64_t min_cells, int64_t grow, double *stats);
+/* visibilities -> model image under a mask that every major cycle extends itself, DEFINED BY THE CALLS IT REPLACES:
+ *     repeat nmajor times (i = 0 ..):
+ *         image = cycle(model, vis)
+ *         image_stats(image, NULL, border)                                -> istats + 8 i
+ *         automask(image, mask, border, absolute .. grow, noise = &istats[8 i + 3])   -> astats + 8 i
+ *         clean_auto | msclean_auto(image, model, ..., mask, nsigma, noise = &istats[8 i + 3], peak_frac_clean)
+ *                                                                         -> stats + 8 i | stats + 16 i   (when stats != NULL)
+ *     image = cycle(model, vis)
+ * mask is the caller's device buffer and may not be NULL: its content on entry is the starting mask, on return it holds
+ * the accumulated mask.  A cycle whose mask is still empty cleans nothing (clean_auto's reason 2) and still images and
+ * measures; nothing on the device skips a cycle.  istats and astats are nmajor x 8 doubles on the device; where one is NULL
+ * the imager keeps the 8 doubles itself.  Every argument rule of the calls replaced is checked before anything is
+ * enqueued.  Asynchronous, allocation-free after the first call and capturable. */
+int gridhip_imager_deconvolve_automask_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
+                                           int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
+                                           int64_t patch, uint8_t *mask, double nsigma, double peak_frac_clean,
+                                           int absolute, double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo,
+                                           double peak_frac, int64_t min_cells, int64_t grow, double *stats,
+                                           double *istats, double *astats);
+int gridhip_imager_msdeconvolve_automask_dev(gridhip_imager *imager, const double *vis, double *model, double *image,
+                                             int64_t nmajor, int64_t S, const double *scales, const double *bias,
+                                             double gain, double threshold, int64_t niter, int64_t border, int64_t patch,
+                                             uint8_t *mask, double nsigma, double peak_frac_clean, int absolute,
+                                             double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo,
+                                             double peak_frac, int64_t min_cells, int64_t grow, double *stats,
+                                             double *istats, double *astats);
 
 /* ---- restoring beam and restore: from clean's model and residual to a map, on the device -----------------------------
  * The reference stops at the dirty image: the semantics are defined here.  All images are real N x N, row-major [y][x];

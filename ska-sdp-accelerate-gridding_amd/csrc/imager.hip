@@ -204,6 +204,8 @@ struct gridhip_imager {
     double *wstats = nullptr;       // the weighting's stats (8 doubles), written at creation
     void *noise_scratch = nullptr;  // image_stats' state block and tables (noise.hip), made by the first image_stats
     double *istats = nullptr;       // the image stats of a deconvolve_auto that does not return them (8 doubles)
+    void *am_scratch = nullptr;     // automask's state block and planes (automask.hip), made by the first automask
+    double *astats = nullptr;       // the automask stats of a deconvolve_automask that does not return them (8 doubles)
     // wide-band imaging, made by set_spectral: the number of Taylor terms (0: none), x per visibility, the residual
     // visibilities of an mfs_cycle, the 2T - 1 spectral PSFs, and mfclean's state block and tile table (mfclean.hip)
     int64_t sp_T = 0;
@@ -897,6 +899,98 @@ int gridhip_imager_destroy(gridhip_imager *im)
         if (p) (void)hipFree(p);
     delete im;
     return GRIDHIP_OK;
+}
+
+int gridhip_imager_automask_dev(gridhip_imager *im, const double *image, uint8_t *mask, int64_t border, int absolute,
+                                double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise,
+                                double peak_frac, int64_t min_cells, int64_t grow, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    GH_CHECK(automask_check(ctx, im->N, image, mask, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                            min_cells, grow, stats));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!im->am_scratch) GH_CHECK(own(im, &im->am_scratch, automask_scratch_bytes(ctx, im->N)));
+    return automask_run(ctx, im->N, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                        min_cells, grow, stats, im->am_scratch);
+}
+
+// the automask of a deconvolve_automask: what every cycle's mask update takes besides the image, the mask and sigma
+struct AutomaskArgs {
+    int absolute;
+    double thr_hi, thr_lo, nsigma_hi, nsigma_lo, peak_frac;
+    int64_t min_cells, grow;
+};
+
+// the checks and the loop the two _automask deconvolves share; minor(c, noise): the c-th minor cycle with sigma at `noise`
+extern "C++" template <typename Minor>
+static int deconvolve_automask(gridhip_imager *im, const double *vis, double *model, double *image, int64_t nmajor,
+                               int64_t border, uint8_t *mask, double nsigma, double peak_frac, const AutomaskArgs &am,
+                               double *istats, double *astats, Minor minor)
+{
+    gridhip_ctx *ctx = im->ctx;
+    double placeholder = 0.0, none[8];  // (stand for sigma's cell and a stats row in the checks: the loop passes its own)
+    if (!mask) return fail(ctx, GRIDHIP_EINVAL, "deconvolve_automask: the mask is the call's state and cannot be NULL");
+    GH_CHECK(clean_auto_check(ctx, im->N, image, model, mask, nsigma, &placeholder, peak_frac));
+    GH_CHECK(automask_check(ctx, im->N, image, mask, border, am.thr_hi, am.thr_lo, am.nsigma_hi, am.nsigma_lo, &placeholder,
+                            am.peak_frac, am.min_cells, am.grow, none));
+    if (!istats || !astats) {
+        GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+        if (!istats && !im->istats) GH_CHECK(own(im, &im->istats, 64));
+        if (!astats && !im->astats) GH_CHECK(own(im, &im->astats, 64));
+    }
+    for (int64_t c = 0; c < nmajor; ++c) {
+        double *ist = istats ? istats + 8 * c : im->istats;
+        double *ast = astats ? astats + 8 * c : im->astats;
+        GH_CHECK(gridhip_imager_cycle_dev(im, model, vis, image, nullptr));
+        GH_CHECK(gridhip_imager_image_stats_dev(im, image, nullptr, border, ist));
+        GH_CHECK(gridhip_imager_automask_dev(im, image, mask, border, am.absolute, am.thr_hi, am.thr_lo, am.nsigma_hi,
+                                             am.nsigma_lo, (const double *)(ist + 3), am.peak_frac, am.min_cells, am.grow,
+                                             ast));
+        GH_CHECK(minor(c, (const double *)(ist + 3)));
+    }
+    return gridhip_imager_cycle_dev(im, model, vis, image, nullptr);
+}
+
+int gridhip_imager_deconvolve_automask_dev(gridhip_imager *im, const double *vis, double *model, double *image,
+                                           int64_t nmajor, double gain, double threshold, int64_t niter, int64_t border,
+                                           int64_t patch, uint8_t *mask, double nsigma, double peak_frac_clean,
+                                           int absolute, double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo,
+                                           double peak_frac, int64_t min_cells, int64_t grow, double *stats,
+                                           double *istats, double *astats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "deconvolve: bad argument");
+    GH_CHECK(clean_check(ctx, im->N, im->psf, image, model, gain, threshold, niter, border, patch));
+    return deconvolve_automask(im, vis, model, image, nmajor, border, mask, nsigma, peak_frac_clean,
+                               AutomaskArgs{absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, peak_frac, min_cells, grow},
+                               istats, astats, [&](int64_t c, const double *noise) {
+                                   return gridhip_imager_clean_auto_dev(im, image, model, gain, threshold, niter, border,
+                                                                        patch, mask, nsigma, noise, peak_frac_clean,
+                                                                        stats ? stats + 8 * c : nullptr);
+                               });
+}
+
+int gridhip_imager_msdeconvolve_automask_dev(gridhip_imager *im, const double *vis, double *model, double *image,
+                                             int64_t nmajor, int64_t S, const double *scales, const double *bias,
+                                             double gain, double threshold, int64_t niter, int64_t border, int64_t patch,
+                                             uint8_t *mask, double nsigma, double peak_frac_clean, int absolute,
+                                             double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo,
+                                             double peak_frac, int64_t min_cells, int64_t grow, double *stats,
+                                             double *istats, double *astats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    if (nmajor < 0 || (im->n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "msdeconvolve: bad argument");
+    GH_CHECK(msclean_check(ctx, im->N, im->psf, image, model, S, scales, bias, gain, threshold, niter, border, patch));
+    return deconvolve_automask(im, vis, model, image, nmajor, border, mask, nsigma, peak_frac_clean,
+                               AutomaskArgs{absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, peak_frac, min_cells, grow},
+                               istats, astats, [&](int64_t c, const double *noise) {
+                                   return gridhip_imager_msclean_auto_dev(im, image, model, S, scales, bias, gain, threshold,
+                                                                          niter, border, patch, mask, nsigma, noise,
+                                                                          peak_frac_clean, stats ? stats + 16 * c : nullptr);
+                               });
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, restore.hip, weights.hip, gaincal.hip, dft.hip).
+// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, dft.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -393,6 +393,18 @@ size_t image_stats_scratch_bytes(gridhip_ctx *ctx);
 // gridhip_image_stats_dev on checked arguments: kernels only, on ctx->stream
 int image_stats_run(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border, double *stats,
                     void *scratch);
+
+// ---- auto-masking (automask.hip) ---------------------------------------------------------------------------------------------
+// gridhip_automask's argument rules (GRIDHIP_EINVAL, then GRIDHIP_EUNSUPPORTED); noise is not read (it may live on the device)
+int automask_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border, double thr_hi,
+                   double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                   int64_t min_cells, int64_t grow, const double *stats);
+// the state block, one row per work-group, two int32 label planes and a byte plane
+size_t automask_scratch_bytes(gridhip_ctx *ctx, int64_t N);
+// gridhip_automask_dev on checked arguments: 13 kernels on ctx->stream, nothing else
+int automask_run(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask, int64_t border, int absolute,
+                 double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                 int64_t min_cells, int64_t grow, double *stats, void *scratch);
 
 // ---- the restoring beam and the restore (restore.hip) --------------------------------------------------------------------
 // gridhip_fit_beam's and gridhip_restore's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); the beam's values are

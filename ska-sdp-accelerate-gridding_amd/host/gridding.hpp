@@ -14,6 +14,7 @@
 //   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
 //   msclean: multi-scale CLEAN, clean with components of several scales (absent from the reference)
 //   mfclean: multi-term CLEAN, the minor cycle of wide-band imaging over T Taylor terms (absent from the reference)
+//   automask: the clean mask from the map itself - two levels, pruned, grown, accumulated (absent from the reference)
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
@@ -393,6 +394,26 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         if (why) *why = {st[12], st[13], st[14]};
         MsCleanStats out = {st[0], st[1], st[2], st[3], st[4], {st[6], st[7], st[8], st[9], st[10], st[11]}};
         return out;
+    }
+
+    // ---- auto-masking (gridhip_automask; include/gridhip.h, "auto-masking") ----
+    // The mask of the islands of `image` above T_hi = max(thr_hi, nsigma_hi * sigma, peak_frac * peak) with at least
+    // min_cells cells, each extended to the whole island above T_lo it lies in and grown by `grow` cells, OR-ed into
+    // `mask` (N x N bytes, updated in place; bytes that are not 0 stay as they are).  reason: 0 the steps ran, 2 no cell
+    // takes part, 3 no usable sigma (the mask is then untouched).
+    struct AutomaskStats {
+        F T_hi, T_lo, peak, components, surviving, kept, cells_set, reason;
+    };
+    AutomaskStats automask(const Matrix<F> &image, std::vector<uint8_t> &mask, F sigma, F nsigma_hi = 5, F nsigma_lo = 2.5,
+                           F thr_hi = 0, F thr_lo = 0, F peak_frac = 0, Int min_cells = 1, Int grow = 0, Int border = 0,
+                           bool absolute = false)
+    {
+        if (image.h != image.w || (Int)mask.size() != image.h * image.w)
+            throw Error(GRIDHIP_EINVAL, "automask: image must be N x N and the mask N x N bytes");
+        F st[8] = {0};
+        check(gridhip_automask(ctx_, image.h, image.data.data(), mask.data(), border, absolute ? 1 : 0, thr_hi, thr_lo,
+                               nsigma_hi, nsigma_lo, &sigma, peak_frac, min_cells, grow, st));
+        return {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
     }
 
     // ---- restoring beam and restore (gridhip_fit_beam, gridhip_restore; include/gridhip.h, "restoring beam and restore") ----

@@ -27,6 +27,7 @@ from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, 
                        auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
 from ._marshal import gain_stream, result_array, solve_args, stream_array
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
+from ._marshal import automask_args, mask_in_place
 from ._marshal import weighting as _weighting
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components"]
@@ -377,6 +378,29 @@ class Context(Handle):
         stats = be.empty(8, be.f64, image)
         self._call(be, "image_stats", shape[0], image, mask, int(border), stats)
         return stats
+
+    def automask(self, image, mask=None, noise=None, border=0, absolute=False, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0,
+                 min_cells=1, grow=0):
+        """The clean mask of the N x N float64 `image` (gridhip_automask[_dev]; include/gridhip.h, "auto-masking"): the
+        islands above T_hi = max(thr[0], nsigma[0] * sigma, peak_frac * peak) with at least `min_cells` cells
+        (8-connected), each extended to the whole island above T_lo = max(thr[1], nsigma[1] * sigma, peak_frac * peak) it
+        lies in, grown by `grow` cells, OR-ed into `mask`.  `mask` (uint8 or bool, N x N; zeros when None) is UPDATED IN
+        PLACE and returned; bytes that are not 0 stay as they are.  `noise` is sigma: a number, or one element like
+        image_stats(...)[3:4]; nsigma=0 takes fixed levels and needs none.  absolute: |image| is thresholded.  Returns
+        (mask, stats); stats = [T_hi, T_lo, peak, components above T_hi, of them surviving the prune, components above
+        T_lo kept, cells newly set, reason (0; 2: no cell takes part, 3: sigma is NaN - the mask is then untouched)].
+        numpy arrays take the synchronous host form; torch cuda tensors the asynchronous one, with stats a cuda tensor:
+        nothing is read back.  With cuda tensors pass `noise` as a device element to stay capturable."""
+        be = backend(image)
+        shape = tuple(getattr(image, "shape", ()))
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("image must be N x N")
+        image = image_of(be, image, shape, "image")
+        args = automask_args(be, absolute, thr, nsigma, noise, peak_frac, min_cells, grow, image)
+        mask, m8 = mask_in_place(be, mask, shape, image)
+        stats = be.empty(8, be.f64, image)
+        self._call(be, "automask", shape[0], image, m8, int(border), *args, stats)
+        return mask, stats
 
     def clean(self, image, psf, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, model=None, mask=None,
               nsigma=0.0, noise=None, peak_frac=0.0):
@@ -791,6 +815,19 @@ class Imager(_Bound):
         self._call(be, "imager_image_stats", image, mask, int(border), stats)
         return stats
 
+    def automask(self, image, mask=None, noise=None, border=0, absolute=False, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0,
+                 min_cells=1, grow=0):
+        """Context.automask of an N x N cuda float64 image with the imager's own scratch (gridhip_imager_automask_dev):
+        asynchronous, and capturable after a first call.  Returns (mask, stats)."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        self._ok(image, be.f64, NN, "image")
+        args = automask_args(be, absolute, thr, nsigma, noise, peak_frac, min_cells, grow, self.device)
+        mask, m8 = mask_in_place(be, mask, NN, self.device)
+        stats = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_automask", image, m8, int(border), *args, stats)
+        return mask, stats
+
     def clean(self, image, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, mask=None, nsigma=0.0,
               noise=None, peak_frac=0.0):
         """Context.clean with the imager's own PSF (gridhip_imager_clean_dev): `image` (N x N cuda float64, a cycle's
@@ -835,7 +872,7 @@ class Imager(_Bound):
         return model, image, stats
 
     def deconvolve(self, vis, nmajor, model=None, out=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0,
-                   scales=None, bias=None, mask=None, nsigma=0.0, peak_frac=0.0):
+                   scales=None, bias=None, mask=None, nsigma=0.0, peak_frac=0.0, automask=None):
         """Visibilities to a model image in one asynchronous call (gridhip_imager_deconvolve_dev): nmajor times
         image = cycle(vis, model) then clean(image, model), and one closing cycle, so that the returned image is
         do_imaging(vis - predict(model))'s for the returned model.  model (zeros when None) is accumulated into, out
@@ -845,7 +882,12 @@ class Imager(_Bound):
         With any of `mask`, `nsigma`, `peak_frac` every major cycle measures its image (image_stats over the whole
         search region) and its minor cycle is clean / msclean under the mask, stopping at max(threshold, nsigma * that
         cycle's sigma, peak_frac * its first peak) (gridhip_imager_[ms]deconvolve_auto_dev): returns (model, image,
-        stats[nmajor, 8 | 16], istats[nmajor, 8])."""
+        stats[nmajor, 8 | 16], istats[nmajor, 8]).
+        With `automask` = dict(absolute=, thr=, nsigma=, peak_frac=, min_cells=, grow=) (Context.automask's keywords and
+        defaults; {} takes them all) every major cycle also extends the mask from the image it is about to clean, at that
+        cycle's sigma, before its minor cycle (gridhip_imager_[ms]deconvolve_automask_dev): `mask` (zeros when None) is
+        the starting mask, UPDATED IN PLACE, and the call returns (model, image, stats[nmajor, 8 | 16], istats[nmajor,
+        8], mask, astats[nmajor, 8])."""
         self._open()
         be, NN = device(), (self.N, self.N)
         self._ok(vis, be.c128, (self.n,), "vis")
@@ -853,6 +895,28 @@ class Imager(_Bound):
         out = be.empty(NN, be.f64, self.device) if out is None else in_place(be, out, NN, "out")
         if int(nmajor) < 0:
             raise ValueError("nmajor must be >= 0")
+        if automask is not None:
+            if scales is None and bias is not None:
+                raise ValueError("bias goes with scales")
+            unknown = set(automask) - {"absolute", "thr", "nsigma", "peak_frac", "min_cells", "grow"}
+            if unknown:
+                raise ValueError(f"automask has no option {sorted(unknown)}")
+            am = automask_args(be, automask.get("absolute", False), automask.get("thr", (0, 0)),
+                               automask.get("nsigma", (5, 2.5)), None, automask.get("peak_frac", 0),
+                               automask.get("min_cells", 1), automask.get("grow", 0), self.device, own_noise=True)
+            nsigma, peak_frac = float(nsigma), float(peak_frac)
+            if not (nsigma >= 0.0 and nsigma < float("inf")) or not 0.0 <= peak_frac < 1.0:
+                raise ValueError("nsigma must be finite and >= 0 and peak_frac in [0, 1)")
+            mask, m8 = mask_in_place(be, mask, NN, self.device)
+            rows = int(nmajor)
+            istats, astats = be.empty((rows, 8), be.f64, self.device), be.empty((rows, 8), be.f64, self.device)
+            sc, keep = scale_list(scales, bias) if scales is not None else ((), None)
+            stats = be.empty((rows, 16 if sc else 8), be.f64, self.device)
+            self._call(be, "imager_msdeconvolve_automask" if sc else "imager_deconvolve_automask", vis, model, out, rows, *sc,
+                       *clean_scalars(gain, threshold, niter, border, patch), m8, nsigma, peak_frac, *am, stats, istats,
+                       astats)
+            del keep
+            return model, out, stats, istats, mask, astats
         if mask is not None or nsigma or peak_frac:
             if scales is None and bias is not None:
                 raise ValueError("bias goes with scales")

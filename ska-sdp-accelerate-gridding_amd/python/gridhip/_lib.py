@@ -41,6 +41,13 @@ _AUTO = [vp, C.c_double, vp, C.c_double]  # mask, nsigma, noise, peak_frac (the 
 _CLEAN_AUTO = _CLEAN[:-1] + _AUTO + [vp]
 _MSCLEAN_AUTO = _MSCLEAN[:-1] + _AUTO + [vp]
 _IMAGE_STATS = [vp, i64, vp, vp, i64, vp]
+# border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, grow (automask, after image and mask)
+_AUTOMASK_ARGS = [i64, ci, C.c_double, C.c_double, C.c_double, C.c_double, vp, C.c_double, i64, i64]
+_AUTOMASK = [vp, i64, vp, vp, *_AUTOMASK_ARGS, vp]
+# what the _automask deconvolves take after patch: mask, nsigma, peak_frac_clean, then automask's own from absolute on
+# (no border, no noise), then stats, istats, astats
+_AUTOMASK_LOOP = [vp, C.c_double, C.c_double, ci, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i64, i64,
+                  vp, vp, vp]
 _FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
 _RESTORE = [vp, i64, vp, vp, vp, i64, vp]
 _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_double, vp, vp]
@@ -141,6 +148,13 @@ SIGNATURES = {
                                                 C.c_double, vp, vp]),
     "gridhip_imager_msdeconvolve_auto_dev": (ci, [vp, vp, vp, vp, i64, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_double,
                                                   i64, i64, i64, vp, C.c_double, C.c_double, vp, vp]),
+    "gridhip_automask": (ci, _AUTOMASK),
+    "gridhip_automask_dev": (ci, _AUTOMASK),
+    "gridhip_imager_automask_dev": (ci, [vp, vp, vp, *_AUTOMASK_ARGS, vp]),
+    "gridhip_imager_deconvolve_automask_dev": (ci, [vp, vp, vp, vp, i64, C.c_double, C.c_double, i64, i64, i64,
+                                                    *_AUTOMASK_LOOP]),
+    "gridhip_imager_msdeconvolve_automask_dev": (ci, [vp, vp, vp, vp, i64, i64, _HOST_F64, _HOST_F64, C.c_double,
+                                                      C.c_double, i64, i64, i64, *_AUTOMASK_LOOP]),
     "gridhip_fit_beam": (ci, _FIT_BEAM),
     "gridhip_fit_beam_dev": (ci, _FIT_BEAM),
     "gridhip_restore": (ci, _RESTORE),

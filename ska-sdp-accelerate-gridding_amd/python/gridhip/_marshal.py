@@ -209,6 +209,54 @@ def auto_args(be, mask, nsigma, noise, peak_frac, shape, like, own_noise=False):
     return mask, nsigma, noise, peak_frac
 
 
+def automask_args(be, absolute, thr, nsigma, noise, peak_frac, min_cells, grow, like, own_noise=False):
+    """absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, grow as the automask entry points take
+    them (include/gridhip.h, "auto-masking").  thr and nsigma are (hi, lo) pairs; a single number stands for both.  noise:
+    as for auto_args - a number, or one float64 element of `be`'s own kind such as image_stats(...)[3:4]; a NUMBER with
+    device images is uploaded by this call and cannot be captured.  own_noise: the entry point measures sigma itself
+    (deconvolve), and noise is left out of the result."""
+    import math
+
+    def pair(x, what):
+        hi, lo = (x, x) if isinstance(x, (int, float)) else x
+        hi, lo = float(hi), float(lo)
+        if not (math.isfinite(hi) and math.isfinite(lo) and 0.0 <= lo <= hi):
+            raise ValueError(f"{what} must be (hi, lo), finite, with 0 <= lo <= hi")
+        return hi, lo
+    thr, nsigma, peak_frac = pair(thr, "thr"), pair(nsigma, "nsigma"), float(peak_frac)
+    min_cells, grow = int(min_cells), int(grow)
+    if not 0.0 <= peak_frac < 1.0:
+        raise ValueError("peak_frac must be in [0, 1)")
+    if min_cells < 1 or not 0 <= grow <= 32:
+        raise ValueError("min_cells must be >= 1 and grow in 0 .. 32")
+    head, tail = (int(bool(absolute)), *thr, *nsigma), (peak_frac, min_cells, grow)
+    if own_noise:
+        return head + tail
+    if noise is None:
+        if nsigma[0] > 0.0:
+            raise ValueError("nsigma > 0 needs noise (sigma, e.g. image_stats(...)[3:4]); pass nsigma=0 for fixed levels")
+    elif isinstance(noise, (int, float)):
+        noise = np.array([noise], dtype=np.float64)
+        if be is not HOST:
+            noise = be.torch.from_numpy(noise).to(getattr(like, "device", like))
+    elif be is not backend(noise) or not be.ok(noise, be.f64) or int(np.prod(tuple(noise.shape))) != 1:
+        raise ValueError(f"noise must be a number or a {be.array} of one float64 element")
+    return head + (noise,) + tail
+
+
+def mask_in_place(be, mask, shape, like):
+    """The mask an automask updates in place: the caller's own N x N uint8 or bool array of `be`'s kind in the ABI's form
+    (a converted copy would take the update with it), or, for None, a new uint8 one of zeros.  -> (the array the caller
+    gets back, its uint8 view for the ABI)"""
+    if mask is None:
+        u8 = np.uint8 if be is HOST else be.torch.uint8
+        mask = be.zeros(shape, u8, like)
+        return mask, mask
+    if be is backend(mask) and hasattr(mask, "dtype") and not be.ok(mask, mask.dtype):
+        raise ValueError(f"mask must be a {be.array} (it is updated in place)")
+    return mask, mask_of(be, mask, shape)
+
+
 def scale_list(scales, bias):
     """S, scales, bias as every msclean entry point takes them: host float64 arrays whichever back end the images come
     from (they fix launch shapes and kernel arguments), passed by address - the caller keeps the returned arrays alive
