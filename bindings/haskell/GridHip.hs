@@ -46,6 +46,7 @@ module GridHip
   , Weighting(..), WeightMode(..), weightsIO, imagerCreateWeightedIO, imagerCreateAwWeightedIO, imagerDestroyIO
   , imagerWeightStatsIO
   , GainSolve(..), gaincalIO, applyGainsIO, imagerSelfcalIO
+  , FlagOptions(..), flagResidualsIO
   , dftPredictIO, componentsFromImageIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
@@ -410,6 +411,15 @@ foreign import ccall unsafe "gridhip_apply_gains_dev"
 -- int gridhip_imager_selfcal_dev(imager, model, vis, A, T, a1, a2, slot, wt, mode, refant, warm, niter, tol, gains, vis_cal, wt_cal, stats)
 foreign import ccall unsafe "gridhip_imager_selfcal_dev"
   c_imager_selfcal_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_flag_residuals(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats, stats)
+foreign import ccall unsafe "gridhip_flag_residuals"
+  c_flag_residuals :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_flag_residuals_dev(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats, stats)
+foreign import ccall unsafe "gridhip_flag_residuals_dev"
+  c_flag_residuals_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_flag_dev(imager, model, vis, G, group, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats, stats)
+foreign import ccall unsafe "gridhip_imager_flag_dev"
+  c_imager_flag_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
 foreign import ccall unsafe "gridhip_dft_predict"
   c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
@@ -1400,6 +1410,35 @@ imagerSelfcalIO (ImagerH h@(GridHip c) p n n') solve nant nslots ant1 ant2 slot 
                   map realToFrac <$> peekArray 8 pst
   return (A.fromForeignPtrs (A.Z A.:. nslots A.:. nant) (castForeignPtr g), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out),
           A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Residual flagging (include/gridhip.h, "residual flagging"): robust per-group clipping of |vis - model|.
+
+-- | how a flagging runs: nsigma of T = median + nsigma * 1.4826 MAD; amax (0: no limit); the fewest samples of a group
+-- that is clipped; the most rounds (0 .. 16)
+data FlagOptions = FlagOptions { flagNsigma :: F, flagAmax :: F, flagMinCount :: Int, flagNiter :: Int }
+
+-- | flagResidualsIO h opts ngroups group wt vis model: (the weights with 0 where a sample is flagged, the class of every
+-- sample, [n, median, MAD, T] per group, the 8 stats) - gridhip_flag_residuals, the host form, synchronous.  group
+-- Nothing: one group (ngroups must be 1); wt Nothing: ones; model Nothing: zero.
+flagResidualsIO :: GridHip -> FlagOptions -> Int -> Maybe (A.Vector Antenna) -> Maybe (A.Vector F) -> A.Vector Visibility
+                -> Maybe (A.Vector Visibility) -> IO (A.Vector F, [Word8], [[F]], [F])
+flagResidualsIO h@(GridHip c) (FlagOptions ns am mc ni) ngroups group wt vis model = do
+  let A.Z A.:. n = A.arrayShape vis
+      withGroup k = maybe (k nullPtr) (\s -> withI64 s k) group
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+      withModel k = maybe (k nullPtr) (\s -> withCplx s k) model
+      rows xs = if null xs then [] else take 4 xs : rows (drop 4 xs)
+  wout <- mallocForeignPtrArray (max 1 n) :: IO (ForeignPtr CDouble)
+  (fl, gs, st) <- withGroup $ \pg -> withWt $ \ps -> withCplx vis $ \vs -> withModel $ \ms ->
+    withForeignPtr wout $ \pw -> allocaArray (max 1 n) $ \pf -> allocaArray (4 * ngroups) $ \pgs -> allocaArray 8 $ \pst -> do
+      c_flag_residuals c (fi n) (fi ngroups) pg vs ms ps (realToFrac ns) (realToFrac am) (fi mc) (fi ni) pw pf pgs pst
+        >>= check h
+      fl <- peekArray n pf
+      gs <- map realToFrac <$> peekArray (4 * ngroups) pgs
+      st <- map realToFrac <$> peekArray 8 pst
+      return (fl, rows gs, st)
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout), fl, gs, st)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- Direct-Fourier prediction (include/gridhip.h, "direct-Fourier prediction"): the exact visibilities of a component

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 230 /* 0.2.3 */
+#define GRIDHIP_VERSION 240 /* 0.2.4 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1108,6 +1108,79 @@ int gridhip_imager_selfcal_dev(gridhip_imager *imager, const double *model, cons
                                const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
                                int64_t refant, int warm, int64_t niter, double tol, double *gains, double *vis_cal,
                                double *wt_cal, double *stats);
+
+/* ---- residual flagging: robust per-group clipping of visibility residuals, on the device -----------------------------------
+ * The reference has no flagging: the semantics are defined here.  Every other step treats a visibility whose weight is not
+ * > 0 as absent; this is the step that decides that a sample is bad and produces such weights.  Inputs: n visibilities
+ * V_k (vis) and model visibilities M_k (model_vis, or NULL: zero), complex as interleaved doubles; data weights s_k (wt_in:
+ * n doubles, or NULL for all ones); the group g_k = group[k] (n int64: a baseline, a solution interval, ...), or group ==
+ * NULL with G == 1; G groups; nsigma, amax, min_count, niter.
+ * CLASSES.  Each visibility falls into the FIRST class that applies; its code goes to flags_out (n bytes, may be NULL):
+ *     1       FLAGGED ON INPUT  s_k is not > 0 (zero, negative, NaN) - gridhip_weights' rule, looked at first: it takes
+ *             part in nothing, whatever V_k, M_k or g_k hold
+ *     2       LEFT ALONE        g_k < 0 or g_k >= G: not tested, not counted in any group, its weight passes through
+ *             unchanged - how a caller exempts samples
+ *     3       NOT FINITE        a_k (below) is NaN or Inf.  As in gridhip_apply_gains this is judged on the value fp64
+ *             computes: a component of the residual above about 1e154 squares to Inf and counts
+ *     4       ABOVE AMAX        amax > 0 and a_k > amax
+ *     16 + r  CLIPPED in round r (below)
+ *     0       KEPT
+ * AMPLITUDE.  r_k = V_k - M_k, each component one rounded subtraction;  a_k = sqrt(re * re + im * im): both products
+ *     rounded, the sum rounded, no fused multiply-add, a correctly rounded square root - numpy's np.sqrt(re * re + im * im)
+ *     to the bit (NOT np.abs, which is hypot).  a_k >= +0.0, so the unsigned bit pattern of a_k is its order-preserving
+ *     key; the same holds for d_k = |a_k - med|.
+ * ROUNDS r = 0 .. niter - 1 over the PARTICIPANTS, the visibilities still of class 0.  For every group g:
+ *     n_g     the number of participants of the group
+ *     med_g   the LOWER median of their a_k, the element of rank (n_g - 1) / 2: an element, never an average
+ *     MAD_g   the lower median of d_k = |a_k - med_g|, each rounded once
+ *     sigma_g = 1.4826 * MAD_g;   T_g = med_g + nsigma * sigma_g, the product rounded, then the sum
+ *     T_g = +Inf when n_g < min_count or sigma_g == 0: a group of ties, or one too small, is not clipped
+ *     a participant with a_k > T_g gets the code 16 + r and is no participant any more
+ *     A round that clips nothing stops the loop.  niter = 0 is valid: the classes 1 to 4 only, no statistics.
+ * OUTPUTS.  wt_out (n doubles; may be wt_in itself) holds s_k (1 without data weights) for the classes 0 and 2 and exactly
+ *     +0.0 otherwise; vis is never written.  group_stats ([G][4] doubles, may be NULL) holds { n_g, med_g, MAD_g, T_g } of
+ *     the last round that ran, as that round saw them; an empty group gives { 0, NaN, NaN, +Inf }, and with niter = 0
+ *     every group has that form with its count.  stats (8 doubles, may be NULL): { rounds run (the one that clipped
+ *     nothing included), participants at the start of round 0, clipped in all rounds, not finite, above amax, left alone,
+ *     flagged on input, kept }.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL context; n < 0; G < 1; group == NULL with
+ * G != 1; a NULL vis or wt_out with n > 0; nsigma not finite or <= 0; amax NaN or < 0; min_count < 1; niter < 0 or > 16;
+ * any output overlapping an input or another output, other than wt_out == wt_in.  G above 2^18 (262144; A = 512 antennas
+ * give 130816 baselines) is GRIDHIP_EUNSUPPORTED - the bin table is 1 KB per group - and so is n above 2^32 - 1 (the bins
+ * and ranks are 32-bit counts).  n = 0 is valid.
+ * gridhip_flag_residuals is synchronous and stages host arrays through the context's pool.  The _dev and imager forms take
+ * device pointers and enqueue kernels only on the context's stream - no memset node, no copy node (the tables are zeroed
+ * by kernels); they allocate nothing after the first call of a shape (the scratch - 12 B per visibility, 1 KB of bins and
+ * 40 B of state per group - comes from the context's pool, or is the imager's own), never synchronise and read nothing
+ * back.  The stop test lives on the device as in gridhip_clean and gridhip_gaincal: all niter rounds are enqueued, a round
+ * counts what it clips, and every launch of the next round reads that count first and returns at once when it is zero -
+ * so a call can be captured into a graph.  The launch count, 3 + 33 niter (5 for niter = 0), does not depend on the data.
+ * A call is: one pass that reads V, M, s and g (40 B) and leaves the 8-byte key of a_k and a 4-byte group code per
+ * visibility; per round a segmented most-significant-digit radix select with 8-bit digits over those 12 B - 8 passes for
+ * the medians of all groups at once, then 8 over d_k for the MADs, each followed by a kernel that takes, one wave per
+ * group, the digit that holds the group's rank - and a pass that clips; then a pass that writes wt_out.  The histogram
+ * has two paths, chosen by G alone: for G <= 64 a work-group keeps G x 256 32-bit bins in LDS (1 KB per group) and adds
+ * its non-zero bins to the global table; above 64 the lanes add to the global [G][256] table directly.
+ * DETERMINISM.  Every output is an order statistic, a count, or one rounded expression of those: integer atomics only, no
+ * floating-point atomic, no sum of doubles.  The result is the same bits for the host, _dev and imager forms, for two
+ * runs, on either histogram path, and for a numpy restatement that sorts. */
+int gridhip_flag_residuals(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis,
+                           const double *model_vis, const double *wt_in, double nsigma, double amax, int64_t min_count,
+                           int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats);
+int gridhip_flag_residuals_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis,
+                               const double *model_vis, const double *wt_in, double nsigma, double amax,
+                               int64_t min_count, int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats,
+                               double *stats);
+/* Flagging against an imager's own prediction, for an imager of any kind, DEFINED BY THE CALLS IT REPLACES:
+ *     pred = gridhip_imager_predict_dev(imager, model, NULL)
+ *     gridhip_flag_residuals_dev(vis against pred)                  -> wt_out, flags_out, group_stats, stats
+ * n is the imager's; vis, group, wt_in and the outputs are on the device.  The front pass reads the imager's own
+ * prediction where the gather left it, as selfcal does - nothing is copied - and the scratch is the imager's.  wt_out is
+ * what a re-weighted imager is created with, or what gridhip_imager_selfcal_dev takes as wt.  A NULL imager or model is
+ * GRIDHIP_EINVAL; the other rules are those of gridhip_flag_residuals_dev. */
+int gridhip_imager_flag_dev(gridhip_imager *imager, const double *model, const double *vis, int64_t G,
+                            const int64_t *group, const double *wt_in, double nsigma, double amax, int64_t min_count,
+                            int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats);
 
 /* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
  * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image

@@ -203,6 +203,8 @@ struct gridhip_imager {
     double *beam = nullptr;         // the fitted beam of a restore that does not return it (8 doubles), made by the first
     double *wstats = nullptr;       // the weighting's stats (8 doubles), written at creation
     void *noise_scratch = nullptr;  // image_stats' state block and tables (noise.hip), made by the first image_stats
+    void *flag_scratch = nullptr;   // flag's state block, tables and keys (flag.hip), made by the first flag and replaced
+    size_t flag_bytes = 0;          // by one with more groups
     double *istats = nullptr;       // the image stats of a deconvolve_auto that does not return them (8 doubles)
     void *am_scratch = nullptr;     // automask's state block and planes (automask.hip), made by the first automask
     double *astats = nullptr;       // the automask stats of a deconvolve_automask that does not return them (8 doubles)
@@ -561,6 +563,28 @@ int gridhip_imager_selfcal_dev(gridhip_imager *im, const double *model, const do
     if (n > 0) GH_CHECK(gather(im, model));
     return gaincal_run(ctx, n, A, T, a1, a2, slot, vis, (const double *)im->pred, wt, mode, refant, warm, niter, tol, gains,
                        stats, vis_cal, wt_cal);
+}
+
+// predict -> flag_residuals as one enqueued chain (flag.hip): the front pass reads the prediction where the gather left it
+int gridhip_imager_flag_dev(gridhip_imager *im, const double *model, const double *vis, int64_t G, const int64_t *group,
+                            const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter,
+                            double *wt_out, uint8_t *flags_out, double *group_stats, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    const int64_t n = im->n;
+    if (!model) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK(flag_check(ctx, n, G, group, vis, (const double *)im->pred, wt_in, nsigma, amax, min_count, niter, wt_out,
+                        flags_out, group_stats, stats));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t need = flag_scratch_bytes(n, G);
+    if (need > im->flag_bytes) {
+        GH_CHECK(own(im, &im->flag_scratch, need));
+        im->flag_bytes = need;
+    }
+    if (n > 0) GH_CHECK(gather(im, model));
+    return flag_run(ctx, n, G, group, vis, (const double *)im->pred, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out,
+                    group_stats, stats, im->flag_scratch);
 }
 
 static int imager_clean(gridhip_imager *im, double *residual, double *model, double gain, double threshold,

@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, dft.hip).
+// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, dft.hip, flag.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -37,6 +37,7 @@ struct ImagingState {
     } wk_cache;
     bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
     bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
+    bool flag_lds_raised = false;     // and flag_hist_kernel's LDS path its 64 KB (flag.hip)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
 };
@@ -490,6 +491,23 @@ int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t
 int apply_gains_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
                     double *vis_out, double *wt_out);
+
+// ---- residual flagging (flag.hip) ------------------------------------------------------------------------------------------
+// the most groups of one call (the bin table is 1 KB per group); the most groups whose bins a work-group of the histogram
+// keeps in LDS (above it the lanes add to the global table directly); the most clipping rounds
+constexpr int64_t FLAG_MAX_GROUPS = (int64_t)1 << 18;
+constexpr int FLAG_LDS_GROUPS = 64;
+constexpr int FLAG_MAX_ROUNDS = 16;
+// gridhip_flag_residuals' argument rules (GRIDHIP_EINVAL, then GRIDHIP_EUNSUPPORTED); nothing is read
+int flag_check(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis, const double *model_vis,
+               const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter, const double *wt_out,
+               const uint8_t *flags_out, const double *group_stats, const double *stats);
+// the state block, 40 B and the 1 KB of bins per group, 12 B per visibility
+size_t flag_scratch_bytes(int64_t n, int64_t G);
+// gridhip_flag_residuals_dev on checked arguments: kernels only, on ctx->stream; scratch: flag_scratch_bytes(n, G)
+int flag_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis, const double *model_vis,
+             const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter, double *wt_out,
+             uint8_t *flags_out, double *group_stats, double *stats, void *scratch);
 
 // ---- direct-Fourier prediction of a component list (dft.hip) ---------------------------------------------------------------
 // gridhip_dft_predict's and gridhip_components_from_image's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); *N: the

@@ -18,6 +18,7 @@
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
+//   flag_residuals: robust per-group clipping of visibility residuals (absent from the reference)
 //   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
@@ -505,6 +506,38 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_apply_gains(ctx_, n, A, T, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(gains),
                                   inverse ? 1 : 0, cd(vis), data.empty() ? nullptr : data.data(), cd(out),
                                   wt_out ? wt_out->data() : nullptr));
+        return out;
+    }
+
+    // ---- residual flagging (gridhip_flag_residuals; include/gridhip.h, "residual flagging") ----
+    // (Host form; the device-pointer forms gridhip_flag_residuals_dev and the imager's gridhip_imager_flag_dev are the C
+    // header's.)
+    struct FlagStats {
+        F rounds, participants, clipped, not_finite, above_amax, left_alone, flagged_in, kept;
+    };
+    // The data weights of vis after clipping |vis - model| per group: the weight (1 where data is empty) of a sample that
+    // is kept or left alone, +0.0 of one that is flagged.  model empty: zero; group empty: one group (G must be 1), else
+    // group[k] in [0, G) and a sample outside is left alone.  T_g = median + nsigma * 1.4826 MAD per group and round; amax
+    // > 0 also flags amplitudes above it.  flags: the class of every sample; group_stats: { n, median, MAD, T } per group.
+    std::vector<F> flag_residuals(const std::vector<Visibility> &vis, const std::vector<Visibility> &model = {},
+                                  const std::vector<Int> &group = {}, Int G = 1, const std::vector<F> &data = {},
+                                  F nsigma = 5.0, F amax = 0.0, Int min_count = 8, Int niter = 3,
+                                  std::vector<uint8_t> *flags = nullptr, std::vector<F> *group_stats = nullptr,
+                                  FlagStats *stats = nullptr)
+    {
+        const Int n = (Int)vis.size();
+        if ((!model.empty() && (Int)model.size() != n) || (!group.empty() && (Int)group.size() != n) ||
+            (!data.empty() && (Int)data.size() != n) || G < 1 || (group.empty() && G != 1))
+            throw Error(GRIDHIP_EINVAL, "flag_residuals: one value per visibility, G >= 1, a group array unless G == 1");
+        std::vector<F> out((size_t)n);
+        if (flags) flags->assign((size_t)n, 0);
+        if (group_stats) group_stats->assign((size_t)(4 * G), 0);
+        F st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_flag_residuals(ctx_, n, G, group.empty() ? nullptr : group.data(), cd(vis),
+                                     model.empty() ? nullptr : cd(model), data.empty() ? nullptr : data.data(), nsigma, amax,
+                                     min_count, niter, out.data(), flags ? flags->data() : nullptr,
+                                     group_stats ? group_stats->data() : nullptr, st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
         return out;
     }
 

@@ -26,11 +26,12 @@ from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
                        auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
 from ._marshal import gain_stream, result_array, solve_args, stream_array
+from ._marshal import flag_outputs, flag_scalars, flag_stream
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
 from ._marshal import automask_args, mask_in_place
 from ._marshal import weighting as _weighting
 
-__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components"]
+__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups"]
 
 
 class Context(Handle):
@@ -588,6 +589,28 @@ class Context(Handle):
         self._call(be, "apply_gains", n, A, T, a1, a2, slot, gains, int(bool(inverse)), vis, wt, out, weights_out)
         return out, weights_out
 
+    def flag_residuals(self, vis, model_vis=None, group=None, G=None, weights=None, nsigma=5.0, amax=0.0, min_count=8,
+                       niter=3, out=None):
+        """Robust per-group flagging of the residuals vis - model_vis (gridhip_flag_residuals[_dev]; include/gridhip.h,
+        "residual flagging"): per group the lower median and the MAD of the amplitudes a = sqrt(re^2 + im^2), and in each
+        of at most niter rounds a sample with a > med + nsigma * 1.4826 * MAD is clipped (a group of fewer than min_count
+        samples or with MAD = 0 is not).  model_vis None: zero.  group: the group of every visibility in [0, G) (a sample
+        whose group is outside is left alone), as flag_groups returns it with G; None: one group.  weights: n data
+        weights (None: ones; a value that is not > 0 flags its visibility on input).  amax > 0 also flags a > amax.
+        Returns (weights, flags, group_stats, stats): the weights with +0.0 where a sample was flagged (out: the array to
+        write, which may be `weights` itself), the class of every sample (uint8: 0 kept, 1 flagged on input, 2 left alone,
+        3 not finite, 4 above amax, 16 + r clipped in round r), the (G, 4) values [n, median, MAD, T] per group of the last
+        round that ran, and the 8 values [rounds, participants, clipped, not finite, above amax, left alone, flagged on
+        input, kept].  The result is an order statistic throughout: the same bits on every run.  numpy arrays take the
+        synchronous host form; torch cuda tensors the asynchronous one on torch's stream, and every result is a cuda
+        tensor: nothing is read back."""
+        be = backend(vis)
+        n, G, group, vis, model_vis, wt = flag_stream(be, vis, model_vis, group, G, weights)
+        scalars = flag_scalars(nsigma, amax, min_count, niter)
+        out, flags, gstats, stats = flag_outputs(be, n, G, out, vis)
+        self._call(be, "flag_residuals", n, G, group, vis, model_vis, wt, *scalars, out, flags, gstats, stats)
+        return out, flags, gstats, stats
+
     def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
         """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
         prediction"): sum_c S_c(x) E_c(u, v) exp(-2 pi i (u l_c + v m_c + w (n_c - 1))), or vis_sub minus that.  uvw
@@ -1047,6 +1070,21 @@ class Imager(_Bound):
                    weights_out, stats)
         return gains, out, weights_out, stats
 
+    def flag(self, model, vis, group=None, G=None, weights=None, nsigma=5.0, amax=0.0, min_count=8, niter=3, out=None):
+        """Context.flag_residuals of `vis` against the imager's own prediction of `model` (gridhip_imager_flag_dev):
+        predict(model) and the flagging as one asynchronous chain that copies nothing and, after a first call of a
+        shape, can be captured into a graph.  group, weights and out are cuda tensors as in that call; out may be weights.
+        Returns (weights, flags, group_stats, stats): the weights go into Context.imager(weights=...) or selfcal."""
+        self._open()
+        be = device()
+        self._ok(model, be.f64, (self.N, self.N), "model")
+        self._ok(vis, be.c128, (self.n,), "vis")
+        n, G, group, vis, _, wt = flag_stream(be, vis, None, group, G, weights, self.n)
+        scalars = flag_scalars(nsigma, amax, min_count, niter)
+        out, flags, gstats, stats = flag_outputs(be, n, G, out, self.device)
+        self._call(be, "imager_flag", model, vis, G, group, wt, *scalars, out, flags, gstats, stats)
+        return out, flags, gstats, stats
+
     def weight_stats(self):
         """The stats of the weighting the imager was created with (gridhip_imager_weight_stats_dev): Context.weights'
         8 values as a cuda tensor, copied on torch's stream."""
@@ -1107,6 +1145,32 @@ def components(l, m, flux, spectral=None, fwhm=None, pa=None):
     if pa is not None:
         out[:, 8] = be.cv(pa, be.f64).reshape(-1)
     return out
+
+
+def flag_groups(a1, a2, slot=None, by="baseline"):
+    """The groups Context.flag_residuals clips within, from the antenna pair (and the solution interval) of every
+    visibility: by "baseline" - one group per unordered antenna pair; "slot" - per interval; "baseline_slot" - per pair
+    and interval; "all" - one group.  Returns (group, G): compact int64 ids in [0, G), numbered in the order of the
+    sorted (pair, slot) keys, and their number.  torch tensors (any device) or anything numpy converts; plumbing - torch
+    operations only, no kernel of the library - and G is read back: one synchronisation where the tensors are on a device."""
+    import torch
+    if by not in ("baseline", "slot", "baseline_slot", "all"):
+        raise ValueError(f'by must be "baseline", "slot", "baseline_slot" or "all", not {by!r}')
+    a1, a2 = (torch.as_tensor(x).to(torch.int64).reshape(-1) for x in (a1, a2))
+    if a1.shape != a2.shape:
+        raise ValueError("a1 and a2 must hold one antenna per visibility each")
+    if by in ("slot", "baseline_slot"):
+        if slot is None:
+            raise ValueError(f'by="{by}" needs slot')
+        slot = torch.as_tensor(slot).to(torch.int64).reshape(-1).to(a1.device)
+        if slot.shape != a1.shape:
+            raise ValueError("slot must hold one interval per visibility")
+    if by == "all" or a1.numel() == 0:
+        return torch.zeros_like(a1), 1
+    lo, hi = torch.minimum(a1, a2), torch.maximum(a1, a2)
+    cols = {"baseline": (lo, hi), "slot": (slot,), "baseline_slot": (lo, hi, slot)}[by]
+    _, group = torch.unique(torch.stack(cols, dim=1), dim=0, sorted=True, return_inverse=True)
+    return group.to(torch.int64), int(group.max()) + 1
 
 
 def default_context(device=0):

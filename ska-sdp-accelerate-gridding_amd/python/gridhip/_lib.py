@@ -54,6 +54,8 @@ _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_doubl
 _WEIGHTING = [ci, C.c_double, C.c_double, vp]  # mode, robust, taper_sigma, wt_in
 _GAINCAL = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]
 _APPLY_GAINS = [vp, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+_FLAG_ARGS = [C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]  # nsigma, amax, min_count, niter, then the four outputs
+_FLAG = [vp, i64, i64, vp, vp, vp, vp, *_FLAG_ARGS]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
@@ -180,6 +182,9 @@ SIGNATURES = {
     "gridhip_apply_gains": (ci, _APPLY_GAINS),
     "gridhip_apply_gains_dev": (ci, _APPLY_GAINS),
     "gridhip_imager_selfcal_dev": (ci, [vp, vp, vp, i64, i64, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp, vp, vp]),
+    "gridhip_flag_residuals": (ci, _FLAG),
+    "gridhip_flag_residuals_dev": (ci, _FLAG),
+    "gridhip_imager_flag_dev": (ci, [vp, vp, vp, i64, vp, vp, *_FLAG_ARGS]),
     "gridhip_dft_predict": (ci, _DFT_PREDICT),
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),

@@ -394,6 +394,49 @@ def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like):
     return int(bool(phase_only)), refant, warm, niter, tol, gains
 
 
+FLAG_MAX_ROUNDS = 16  # the most clipping rounds of gridhip_flag_residuals
+
+
+def flag_stream(be, vis, model_vis, group, G, weights, n=-1):
+    """n, G, group, vis, model_vis, wt_in as gridhip_flag_residuals and gridhip_imager_flag_dev take the stream: group None
+    goes as NULL and needs G in (None, 1); a given group needs G, the number of groups (gridhip.flag_groups returns both)."""
+    vis = stream_array(be, vis, be.c128, n, "vis")
+    n = int(vis.shape[0])
+    if group is None:
+        if G not in (None, 1):
+            raise ValueError("G > 1 needs group, the group of every visibility")
+        G = 1
+    else:
+        if G is None:
+            raise ValueError("group needs G, the number of groups (flag_groups returns both)")
+        group = _integers(be, group, n, "group")
+    G = int(G)
+    if G < 1:
+        raise ValueError("G must be >= 1")
+    return (n, G, group, vis, stream_array(be, model_vis, be.c128, n, "model_vis"),
+            stream_array(be, weights, be.f64, n, "weights"))
+
+
+def flag_scalars(nsigma, amax, min_count, niter):
+    """nsigma, amax, min_count, niter as the flagging entry points take them"""
+    import math
+    nsigma, amax, min_count, niter = float(nsigma), float(amax), int(min_count), int(niter)
+    if not (math.isfinite(nsigma) and nsigma > 0.0):
+        raise ValueError("nsigma must be finite and > 0")
+    if not amax >= 0.0:
+        raise ValueError("amax must be >= 0 (0: no limit)")
+    if min_count < 1 or not 0 <= niter <= FLAG_MAX_ROUNDS:
+        raise ValueError(f"min_count must be >= 1 and niter in 0 .. {FLAG_MAX_ROUNDS}")
+    return nsigma, amax, min_count, niter
+
+
+def flag_outputs(be, n, G, out, like):
+    """wt_out, flags_out, group_stats, stats: new arrays, or for wt_out the caller's own (it may be `weights` itself)"""
+    u8 = np.uint8 if be is HOST else be.torch.uint8
+    return (result_array(be, out, be.f64, (n,), "out", like), be.empty((n,), u8, like), be.empty((G, 4), be.f64, like),
+            be.empty((8,), be.f64, like))
+
+
 COMP_DOUBLES = 10  # GRIDHIP_COMP_DOUBLES: { l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0 }
 
 
