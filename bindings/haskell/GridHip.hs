@@ -48,6 +48,7 @@ module GridHip
   , GainSolve(..), gaincalIO, applyGainsIO, imagerSelfcalIO
   , FlagOptions(..), flagResidualsIO
   , dftPredictIO, componentsFromImageIO
+  , findSourcesIO
   -- * the reference's one wired-up program after its HDF5 reads (src/ImageDataset.hs:54-77) as one call
   , awGriddingIO
   -- * a whole node (single process, all devices; RCCL all-reduce of the partial grids)
@@ -432,6 +433,15 @@ foreign import ccall unsafe "gridhip_components_from_image"
 -- int gridhip_components_from_image_dev(ctx, theta, lam, T, model, max_c, comps, count)
 foreign import ccall unsafe "gridhip_components_from_image_dev"
   c_components_from_image_dev :: Ptr Ctx -> CDouble -> Int64 -> CInt -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr Int64 -> IO CInt
+-- int gridhip_find_sources(ctx, theta, lam, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats)
+foreign import ccall unsafe "gridhip_find_sources"
+  c_find_sources :: Ptr Ctx -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_find_sources_dev(ctx, theta, lam, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats)
+foreign import ccall unsafe "gridhip_find_sources_dev"
+  c_find_sources_dev :: Ptr Ctx -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_find_sources_dev(imager, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats)
+foreign import ccall unsafe "gridhip_imager_find_sources_dev"
+  c_imager_find_sources_dev :: Ptr Imager -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -1471,6 +1481,32 @@ componentsFromImageIO h@(GridHip c) theta lam terms maxc model = do
              c_components_from_image c (realToFrac theta) (fi lam) (fi terms) pm (fi maxc) po pn >>= check h
              fromIntegral <$> peek pn
   return (A.fromForeignPtrs (A.Z A.:. maxc A.:. 10) (castForeignPtr out), found)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Source finding (include/gridhip.h, "source finding"): a map as a list of Gaussian components.
+
+-- | findSourcesIO h theta lam opts sigma border beam correct maxc image: the islands of the N x N map under the levels of
+-- opts (amAbsolute and amGrow are not used), each measured by its moments -> (the [maxc][10] component rows that
+-- dftPredictIO takes, of which the first min found maxc are written, the [maxc][16] measurements, the number found, the 8
+-- stats [T_hi, T_lo, P, found, written, points, summed flux, reason]).  beam: the 8 values of fitBeamIO, or Nothing -
+-- gridhip_find_sources, the host form, synchronous
+findSourcesIO :: GridHip -> F -> Int -> AutomaskOptions -> F -> Int -> Maybe [F] -> Bool -> Int -> A.Matrix F
+              -> IO (A.Matrix F, A.Matrix F, Int, [F])
+findSourcesIO h@(GridHip c) theta lam (AutomaskOptions _ (th, tl) (nh, nl) pf mc _) sigma border beam correct maxc image = do
+  out <- mallocForeignPtrArray (10 * maxc) :: IO (ForeignPtr CDouble)
+  inf <- mallocForeignPtrArray (16 * maxc) :: IO (ForeignPtr CDouble)
+  let withBeam k = maybe (k nullPtr) (\b -> withArray (map realToFrac b :: [CDouble]) k) beam
+  (found, st) <- withF image $ \pi' -> withForeignPtr out $ \po -> withForeignPtr inf $ \pq ->
+    with (realToFrac sigma :: CDouble) $ \pn -> withBeam $ \pb -> alloca $ \pc -> allocaArray 8 $ \ps -> do
+      mapM_ (\i -> pokeElemOff po i 0) [0 .. 10 * maxc - 1]
+      mapM_ (\i -> pokeElemOff pq i 0) [0 .. 16 * maxc - 1]
+      c_find_sources c (realToFrac theta) (fi lam) pi' (fi border) (realToFrac th) (realToFrac tl) (realToFrac nh)
+        (realToFrac nl) pn (realToFrac pf) (fi mc) pb (if correct then 1 else 0) (fi maxc) po pq pc ps >>= check h
+      n <- fromIntegral <$> peek pc
+      s <- map realToFrac <$> peekArray 8 ps
+      return (n, s)
+  return ( A.fromForeignPtrs (A.Z A.:. maxc A.:. 10) (castForeignPtr out)
+         , A.fromForeignPtrs (A.Z A.:. maxc A.:. 16) (castForeignPtr inf), found, st )
 
 -- ---------------------------------------------------------------------------------------------------------
 -- A whole node from one Haskell process: ndev devices, visibilities cut into contiguous shards, partial grids

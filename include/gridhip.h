@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 240 /* 0.2.4 */
+#define GRIDHIP_VERSION 250 /* 0.2.5 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1255,6 +1255,91 @@ int gridhip_components_from_image(gridhip_ctx *ctx, double theta, int64_t lam, i
                                   double *comps, int64_t *count);
 int gridhip_components_from_image_dev(gridhip_ctx *ctx, double theta, int64_t lam, int T, const double *model,
                                       int64_t max_c, double *comps, int64_t *count);
+
+/* ---- source finding: from a restored map to a list of Gaussian components, on the device -----------------------------------
+ * The reference has no such function: the semantics are defined here.  gridhip_components_from_image turns every non-zero
+ * model cell into a point; this turns a MAP - restored, or any real N x N image, N = gridhip_image_size(theta, lam) - into a
+ * catalogue: one row per island of emission with its position, integrated flux and deconvolved shape, in the row format of
+ * gridhip_dft_predict, so that the list can be predicted, or solved against, as it is.
+ * ISLANDS.  border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac and min_cells are auto-masking's, with the same
+ * meaning, the same rounding of the levels T_hi and T_lo, the same rule for the noise pointer (one double; on the device for
+ * the _dev and imager forms) and the same reasons 2 and 3.  There is no `absolute`: a catalogue is of positive emission.
+ * The islands are the components of K of auto-masking's steps 1-3, before any growing: the components of L = { v > T_lo }
+ * that hold a cell of a component of H = { v > T_hi } with at least min_cells cells.  An island's label is its smallest
+ * cell index; the islands are listed in ascending label order, so the list is a function of the image alone.  Since the
+ * levels are >= 0 every cell of an island is > 0 and all weights below are positive.  An island with several peaks (a
+ * blend) is ONE component: nothing here splits islands.
+ * PER ISLAND, over its cells I(y, x):
+ *     exact     ncells; the bounding box y0, y1, x0, x1; the peak P_i and its cell (yp, xp) - the maximum under
+ *               image_stats' key order, the smallest cell index among equals; edge = the box touches row or column `border`
+ *               or N - 1 - border
+ *     sums      with dx = x - xp, dy = y - yp (exact small integers, so that nothing cancels):
+ *               S = sum I, Sx = sum I dx, Sy = sum I dy, Sxx = sum I dx^2, Sxy = sum I (dx dy), Syy = sum I dy^2,
+ *               each term ONE rounded product of I and an exact integer, added in fp64 in an order that depends on the
+ *               island's box and the launch constants only - no floating-point atomics: two runs and all three forms give
+ *               the same bits
+ *     derived, in this order, every operation rounded (no fused multiply-add):
+ *     1  cx = xp + Sx / S, cy = yp + Sy / S; mxx = Sxx / S - (Sx / S)^2, mxy = Sxy / S - (Sx / S)(Sy / S), myy = Syy / S -
+ *        (Sy / S)^2; F = S
+ *     2  correct != 0: the truncation of a Gaussian cut at an isophote.  t = T_lo / P_i; t == 0 leaves everything as it is;
+ *        else F <- F / (1 - t) and m.. <- m.. (1 - t) / (1 - t (1 - ln t)).  (In the coordinates where the Gaussian is
+ *        round, P exp(-r^2 / 2) is above t P for r^2 / 2 < -ln t: the flux inside is (1 - t) of the whole and the second
+ *        moment inside is 1 - t (1 - ln t) of the whole, so the normalised moment is low by their quotient - for any
+ *        axis ratio and angle, for a continuous Gaussian.)
+ *     3  beam != NULL (the 8 doubles of gridhip_fit_beam, exp(-(A dx^2 + 2 B dx dy + C dy^2))): det = A C - B^2, the beam's
+ *        covariance is bxx = C / (2 det), bxy = -B / (2 det), byy = A / (2 det); F <- F sqrt(det) / pi turns units per beam
+ *        into integrated flux; i.. = m.. - b...  Without a beam i.. = m...  A beam that gridhip_restore could not use (ok 0
+ *        or NaN, or A, B, C not finite and positive definite) gives NaN in F, bmaj, bmin, bpa of every row and sets flag
+ *        bit 2; nothing is silently replaced.  gridhip_find_sources, which has the beam on the host, refuses it instead
+ *        (GRIDHIP_EINVAL), as gridhip_restore does.
+ *     4  ixx > 0, iyy > 0 and D = ixx iyy - ixy^2 > 0: a Gaussian.  lambda+ = (ixx + iyy) / 2 + sqrt(((ixx - iyy) / 2)^2 +
+ *        ixy^2), lambda- = D / lambda+ (the other eigenvalue without its cancellation); FWHM+- = sqrt(8 ln 2 lambda+-)
+ *        cells; bmaj, bmin = FWHM+- theta / N; phi = atan2(2 ixy, ixx - iyy) / 2, bpa = pi / 2 - phi folded into (-pi/2,
+ *        pi/2]: gridhip_dft_predict's angle, from +m towards +l.  Otherwise a point: bmaj = bmin = bpa = 0, flag bit 0.
+ *        This atan2(y, x) is formed from rounded +, -, *, / alone, so that the angle has the same bits wherever it is
+ *        computed (a libm's is not correctly rounded): 0 for y = x = 0; t = min(|x|, |y|) / max(|x|, |y|); if t > tan(pi/8)
+ *        = 0.4142135623730950488, t <- (t - 1) / (t + 1) and base = pi / 4, else base = 0; s = 1 - z / 3 + z^2 / 5 - ... +
+ *        z^22 / 45 with z = t t, by Horner from the last term, each coefficient the quotient 1 / (2 k + 1); r = base + t s;
+ *        r <- pi / 2 - r if |y| > |x|; r <- pi - r if x < 0; the sign of y.  Within 1e-15 relative of the true value.
+ *     5  l = theta (cx - N/2) / N, m = theta (cy - N/2) / N with the integer N/2, the product before the quotient, as for
+ *        gridhip_components_from_image.
+ * OUTPUTS
+ *     comps   [max_c][GRIDHIP_COMP_DOUBLES] rows { l, m, F, 0, 0, 0, bmaj, bmin, bpa, 0 }
+ *     info    [max_c][GRIDHIP_SRC_DOUBLES = 16] rows { label, ncells, yp, xp, P_i, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1,
+ *             flags }, or NULL.  flags: bit 0 a point, bit 1 edge, bit 2 the beam is unusable
+ *     count   one int64 (on the device for the _dev and imager forms): the islands found, even above max_c.  Only the
+ *             first max_c rows are written; the rows after the last one written are left as they were
+ *     stats   8 doubles { T_hi, T_lo, P, islands found, rows written, of them points, the sum of F over the rows written
+ *             (added in row order by one thread), reason }.  reason 2 and 3 as for auto-masking: count is 0, the counts
+ *             are 0 and no row is written
+ * Arguments, checked before anything is touched.  GRIDHIP_EINVAL: auto-masking's rules for N, border, image, the levels,
+ * noise and min_cells; max_c < 0; a NULL comps with max_c > 0; a NULL count or stats; correct outside {0, 1}; comps, info,
+ * count or stats overlapping each other, the image, the beam or the noise.  Then GRIDHIP_EUNSUPPORTED: N > 46340.
+ * gridhip_find_sources is synchronous and stages host arrays through the context's pool.  The _dev and imager forms
+ * enqueue kernels only on the context's stream - 17 launches whatever the image holds (12 with max_c = 0), no memset or
+ * copy node - allocate nothing after the first call of a shape, read nothing back and never synchronise: image ->
+ * image_stats -> find_sources -> dft_predict can be captured into one graph.  Scratch is auto-masking's (9 bytes per cell)
+ * and 12 B per 1024 cells and 20 B per row; the imager form keeps its own.
+ * The labelling is auto-masking's own kernels.  Then: the roots of the islands are compacted in order (per-segment counts,
+ * an exclusive scan, a scatter - components_from_image's pattern), which numbers the rows; one flat pass takes the boxes by
+ * 32-bit integer atomicMin / atomicMax per row; one work-group of 256 threads per row walks the row's box in row-major
+ * order, thread t the cells t, t + 256, ..., keeping the cells that carry the island's label - first for the peak, then for
+ * the count and the six sums - each reduced by a wave shuffle tree and a fixed tree over the four waves; one thread derives
+ * the fields and writes both rows. */
+#define GRIDHIP_SRC_DOUBLES 16
+int gridhip_find_sources(gridhip_ctx *ctx, double theta, int64_t lam, const double *image, int64_t border, double thr_hi,
+                         double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                         int64_t min_cells, const double *beam, int correct, int64_t max_c, double *comps, double *info,
+                         int64_t *count, double *stats);
+int gridhip_find_sources_dev(gridhip_ctx *ctx, double theta, int64_t lam, const double *image, int64_t border, double thr_hi,
+                             double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                             int64_t min_cells, const double *beam, int correct, int64_t max_c, double *comps, double *info,
+                             int64_t *count, double *stats);
+/* gridhip_find_sources_dev with the imager's theta, lam and N and its own scratch */
+int gridhip_imager_find_sources_dev(gridhip_imager *imager, const double *image, int64_t border, double thr_hi, double thr_lo,
+                                    double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                                    int64_t min_cells, const double *beam, int correct, int64_t max_c, double *comps,
+                                    double *info, int64_t *count, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -26,7 +26,7 @@
 // Loads of labels that other work-groups change within a launch (the border and flatten kernels) are relaxed agent-scope
 // atomic loads: they are served past the CU's L1, which other CUs' stores never refresh.
 //
-// One call is 13 launches whatever the image holds:
+// One call is 13 launches whatever the image holds (the first 11 are automask_label_run, which sources.hip shares):
 //     am_peak_kernel, am_levels_kernel                P = max v over the cells that take part; T_hi, T_lo; the counters zeroed
 //     local, border, flatten  at T_hi                 components of H and their sizes (plane A: labels, plane B: sizes)
 //     am_seeds_kernel                                 bytes: 1 on the cells of components with >= min_cells cells
@@ -53,12 +53,7 @@ constexpr int64_t AM_MAX_N = 46340, AM_MAX_GROW = 32;
 constexpr u64 AM_EXP = 0x7ff0000000000000ULL;
 static_assert(AM_TW == 32 && AM_TH % 8 == 0, "a wave's ballot holds two rows of a tile");
 
-struct AmState {  // at the head of the scratch block
-    double T_hi, T_lo, P;
-    int reason, pad;
-    unsigned int nH, nSurv, nKept, nNew;
-};
-
+// (AmState, the head of the scratch block, is in imaging.h: sources.hip reads the levels and the reason from it)
 struct AmLayout {
     size_t state, rows, planeA, planeB, bytes, total;
     int nwg;
@@ -480,11 +475,9 @@ int automask_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8
                    double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
                    int64_t min_cells, int64_t grow, const double *stats)
 {
-    if (N < 1 || border < 0 || 2 * border >= N || !image || !mask || !stats || min_cells < 1 || grow < 0)
-        return fail(ctx, GRIDHIP_EINVAL, "automask: bad argument");
-    if (!level_ok(thr_hi) || !level_ok(thr_lo) || !level_ok(nsigma_hi) || !level_ok(nsigma_lo) || thr_lo > thr_hi ||
-        nsigma_lo > nsigma_hi || !(peak_frac >= 0.0 && peak_frac < 1.0) || (nsigma_hi > 0.0 && !noise))
-        return fail(ctx, GRIDHIP_EINVAL, "automask: bad thr, nsigma, noise or peak_frac");
+    if (!mask || !stats || grow < 0) return fail(ctx, GRIDHIP_EINVAL, "automask: bad argument");
+    GH_CHECK(automask_levels_check(ctx, "automask", N, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                                   min_cells));
     if (N <= AM_MAX_N) {  // (above it the call is refused below, and the byte counts are not needed)
         const size_t cells = (size_t)N * N;
         if (overlap_bytes(mask, cells, image, cells * 8) || overlap_bytes(stats, 64, image, cells * 8) ||
@@ -498,9 +491,29 @@ int automask_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8
 
 size_t automask_scratch_bytes(gridhip_ctx *ctx, int64_t N) { return layout(ctx, N).total; }
 
-int automask_run(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask, int64_t border, int absolute,
-                 double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
-                 int64_t min_cells, int64_t grow, double *stats, void *scratch)
+int automask_levels_check(gridhip_ctx *ctx, const char *who, int64_t N, const double *image, int64_t border, double thr_hi,
+                          double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                          int64_t min_cells)
+{
+    if (N < 1 || border < 0 || 2 * border >= N || !image || min_cells < 1)
+        return fail(ctx, GRIDHIP_EINVAL, "%s: bad argument", who);
+    if (!level_ok(thr_hi) || !level_ok(thr_lo) || !level_ok(nsigma_hi) || !level_ok(nsigma_lo) || thr_lo > thr_hi ||
+        nsigma_lo > nsigma_hi || !(peak_frac >= 0.0 && peak_frac < 1.0) || (nsigma_hi > 0.0 && !noise))
+        return fail(ctx, GRIDHIP_EINVAL, "%s: bad thr, nsigma, noise or peak_frac", who);
+    return GRIDHIP_OK;
+}
+
+AmPlanes automask_planes(gridhip_ctx *ctx, int64_t N, void *scratch)
+{
+    const AmLayout l = layout(ctx, N);
+    char *base = reinterpret_cast<char *>(scratch);
+    return AmPlanes{reinterpret_cast<AmState *>(base + l.state), reinterpret_cast<int *>(base + l.planeB),
+                    reinterpret_cast<int *>(base + l.planeA), reinterpret_cast<uint8_t *>(base + l.bytes)};
+}
+
+int automask_label_run(gridhip_ctx *ctx, int64_t N, const double *image, int64_t border, int absolute, double thr_hi,
+                       double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                       int64_t min_cells, double *stats, void *scratch)
 {
     const AmLayout l = layout(ctx, N);
     char *base = reinterpret_cast<char *>(scratch);
@@ -530,10 +543,23 @@ int automask_run(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask
     hipLaunchKernelGGL(am_mark_kernel, flat, dim3(256), 0, s, cells, (const AmState *)st, (const int *)B,
                        (const uint8_t *)bytes, A);
     hipLaunchKernelGGL(am_keep_kernel, flat, dim3(256), 0, s, cells, st, (const int *)B, (const int *)A, bytes);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int automask_run(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask, int64_t border, int absolute,
+                 double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                 int64_t min_cells, int64_t grow, double *stats, void *scratch)
+{
+    GH_CHECK(automask_label_run(ctx, N, image, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                                min_cells, stats, scratch));
+    const AmPlanes p = automask_planes(ctx, N, scratch);
+    const dim3 tiles((unsigned)((N + AM_TW - 1) / AM_TW), (unsigned)((N + AM_TH - 1) / AM_TH));
+    hipStream_t s = ctx->stream;
     const int g = (int)grow;
     const size_t lds = (size_t)(AM_TH + 2 * g) * (AM_TW + 2 * g) + (size_t)(AM_TH + 2 * g) * AM_TW;  // at most 12 KB
-    hipLaunchKernelGGL(am_grow_kernel, tiles, dim3(256), lds, s, N, border, g, st, (const uint8_t *)bytes, mask);
-    hipLaunchKernelGGL(am_stats_kernel, dim3(1), dim3(1), 0, s, (const AmState *)st, stats);
+    hipLaunchKernelGGL(am_grow_kernel, tiles, dim3(256), lds, s, N, border, g, p.state, (const uint8_t *)p.kbyte, mask);
+    hipLaunchKernelGGL(am_stats_kernel, dim3(1), dim3(1), 0, s, (const AmState *)p.state, stats);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }

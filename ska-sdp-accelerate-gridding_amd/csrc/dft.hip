@@ -40,7 +40,6 @@ constexpr int DFT_CHUNK = 256;             // prepared components staged in LDS 
 constexpr int DFT_PREP = 10;               // doubles of a prepared component
 constexpr int DFT_MAX_SLICES = 64;
 constexpr int DFT_FILL = 512;              // work-groups that fill the chip (2 per CU of 256): below it, slices
-constexpr int CFI_SEG = 1024;              // cells of a segment of the compaction: 4 per thread
 static_assert(DFT_PREP == GRIDHIP_COMP_DOUBLES, "a prepared component takes the room of a given one");
 
 __device__ __forceinline__ bool is_fin(double x) { return x - x == 0.0; }
@@ -274,27 +273,7 @@ __device__ __forceinline__ bool cell_set(const double *__restrict__ model, int64
     return nz;
 }
 
-// the counts of the threads before this one (exclusive) and of all the work-group (*total); lds: 4 values
-__device__ __forceinline__ unsigned int block_rank(unsigned int mine, unsigned int *lds, unsigned int *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned int before = 0, all = 0;
-    for (int wv = 0; wv < 4; ++wv) {
-        if (wv < wave) before += lds[wv];
-        all += lds[wv];
-    }
-    *total = all;
-    return before + inc - mine;
-}
-
+// (block_rank and CFI_SEG are in imaging.h: sources.hip compacts the island roots the same way)
 __global__ void __launch_bounds__(256)
     cfi_count_kernel(int64_t cells, int T, const double *__restrict__ model, int64_t nseg, unsigned int *__restrict__ segcount)
 {
@@ -483,6 +462,13 @@ int components_check(gridhip_ctx *ctx, double theta, int64_t lam, int T, const d
     return GRIDHIP_OK;
 }
 
+int segment_scan(gridhip_ctx *ctx, int64_t nseg, const unsigned int *segcount, int64_t *offs, int64_t *count)
+{
+    hipLaunchKernelGGL(cfi_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, nseg, segcount, offs, count);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
 int components_run(gridhip_ctx *ctx, int64_t N, double theta, int T, const double *model, int64_t max_c, double *comps,
                    int64_t *count_dev)
 {
@@ -492,8 +478,7 @@ int components_run(gridhip_ctx *ctx, int64_t N, double theta, int T, const doubl
     GH_CHECK(offs.alloc(ctx, (size_t)nseg * 8));
     const dim3 grid = grid_for(ctx, nseg, 1);
     hipLaunchKernelGGL(cfi_count_kernel, grid, dim3(256), 0, ctx->stream, cells, T, model, nseg, segcount.as<unsigned int>());
-    hipLaunchKernelGGL(cfi_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, nseg,
-                       (const unsigned int *)segcount.as<unsigned int>(), offs.as<int64_t>(), count_dev);
+    GH_CHECK(segment_scan(ctx, nseg, segcount.as<unsigned int>(), offs.as<int64_t>(), count_dev));
     if (max_c > 0)
         hipLaunchKernelGGL(cfi_scatter_kernel, grid, dim3(256), 0, ctx->stream, N, T, theta, model, nseg,
                            (const int64_t *)offs.as<int64_t>(), max_c, comps);

@@ -208,6 +208,10 @@ struct gridhip_imager {
     double *istats = nullptr;       // the image stats of a deconvolve_auto that does not return them (8 doubles)
     void *am_scratch = nullptr;     // automask's state block and planes (automask.hip), made by the first automask
     double *astats = nullptr;       // the automask stats of a deconvolve_automask that does not return them (8 doubles)
+    double theta = 0.0;             // the field of view and the wavelength scale of creation: find_sources' l, m
+    int64_t lam = 0;
+    void *src_scratch = nullptr;    // find_sources' segment table, roots and boxes (sources.hip), made by the first
+    int64_t src_rows = -1;          // find_sources and replaced by one with more rows
     // wide-band imaging, made by set_spectral: the number of Taylor terms (0: none), x per visibility, the residual
     // visibilities of an mfs_cycle, the 2T - 1 spectral PSFs, and mfclean's state block and tile table (mfclean.hip)
     int64_t sp_T = 0;
@@ -446,7 +450,9 @@ int gridhip_imager_create_weighted_dev(gridhip_ctx *ctx, int kind, int64_t wstep
     if (!imager || n < 0 || uv_stride < 1 || (n > 0 && (!u || !v || (kind == 2 && !w))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     if (n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per imager");
-    return create(ctx, kind, N, n, k, (double)lam, u, v, w, uv_stride, imager);
+    GH_CHECK(create(ctx, kind, N, n, k, (double)lam, u, v, w, uv_stride, imager));
+    (*imager)->theta = theta, (*imager)->lam = lam;
+    return GRIDHIP_OK;
 }
 
 int gridhip_imager_create_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q, int64_t npixFF, int64_t gh,
@@ -476,7 +482,9 @@ int gridhip_imager_create_aw_weighted_dev(gridhip_ctx *ctx, double theta, int64_
     Kernels k;
     k.fn.Q = Q, k.W = W, k.S = S, k.A = A, k.wkerns = wkerns, k.wvals = wvals, k.akerns = akerns, k.a1 = a1, k.a2 = a2;
     k.mode = mode, k.robust = robust, k.sigma = taper_sigma, k.wt_in = wt_in;
-    return create(ctx, 3, N, n, k, (double)lam, u, v, w, uv_stride, imager);
+    GH_CHECK(create(ctx, 3, N, n, k, (double)lam, u, v, w, uv_stride, imager));
+    (*imager)->theta = theta, (*imager)->lam = lam;
+    return GRIDHIP_OK;
 }
 
 int gridhip_imager_create_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S,
@@ -937,6 +945,26 @@ int gridhip_imager_automask_dev(gridhip_imager *im, const double *image, uint8_t
     if (!im->am_scratch) GH_CHECK(own(im, &im->am_scratch, automask_scratch_bytes(ctx, im->N)));
     return automask_run(ctx, im->N, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
                         min_cells, grow, stats, im->am_scratch);
+}
+
+int gridhip_imager_find_sources_dev(gridhip_imager *im, const double *image, int64_t border, double thr_hi, double thr_lo,
+                                    double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                                    int64_t min_cells, const double *beam, int correct, int64_t max_c, double *comps,
+                                    double *info, int64_t *count, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    int64_t N = 0;
+    GH_CHECK(sources_check(ctx, im->theta, im->lam, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                           min_cells, beam, correct, max_c, comps, info, count, stats, &N));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!im->am_scratch) GH_CHECK(own(im, &im->am_scratch, automask_scratch_bytes(ctx, im->N)));
+    if (max_c > im->src_rows) {  // (the block it replaces stays the imager's until destruction: earlier calls may be in flight)
+        GH_CHECK(own(im, &im->src_scratch, sources_scratch_bytes(im->N, max_c)));
+        im->src_rows = max_c;
+    }
+    return sources_run(ctx, im->N, im->theta, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                       min_cells, beam, correct, max_c, comps, info, count, stats, im->am_scratch, im->src_scratch);
 }
 
 // the automask of a deconvolve_automask: what every cycle's mask update takes besides the image, the mask and sigma

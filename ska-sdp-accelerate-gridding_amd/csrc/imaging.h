@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, dft.hip, flag.hip).
+// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, dft.hip, flag.hip, sources.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -402,6 +402,30 @@ int automask_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8
                    int64_t min_cells, int64_t grow, const double *stats);
 // the state block, one row per work-group, two int32 label planes and a byte plane
 size_t automask_scratch_bytes(gridhip_ctx *ctx, int64_t N);
+// The head of the scratch block: the levels, the reason (0: the steps run; 2, 3: every kernel after the levels leaves at
+// once) and the four counts of the stats.
+struct AmState {
+    double T_hi, T_lo, P;
+    int reason, pad;
+    unsigned int nH, nSurv, nKept, nNew;
+};
+// What steps 1-3 leave in the scratch block: the labels of L (a cell's label is the smallest index of its component, -1
+// outside L), a second int32 plane that is free again (0, or 1 at the roots of the kept components) and the bytes of K.
+struct AmPlanes {
+    AmState *state;
+    int *label, *spare;
+    uint8_t *kbyte;
+};
+AmPlanes automask_planes(gridhip_ctx *ctx, int64_t N, void *scratch);
+// the rules of N, border, image, min_cells and the levels alone (GRIDHIP_EINVAL), for automask and find_sources (`who`)
+int automask_levels_check(gridhip_ctx *ctx, const char *who, int64_t N, const double *image, int64_t border, double thr_hi,
+                          double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                          int64_t min_cells);
+// steps 1-3 on checked arguments: the first 11 kernels of an automask.  An early end (reason 2, 3) writes the 8 stats
+// { T_hi, T_lo, P, 0, 0, 0, 0, reason } and leaves the planes as they were: whoever reads them reads the reason first.
+int automask_label_run(gridhip_ctx *ctx, int64_t N, const double *image, int64_t border, int absolute, double thr_hi,
+                       double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                       int64_t min_cells, double *stats, void *scratch);
 // gridhip_automask_dev on checked arguments: 13 kernels on ctx->stream, nothing else
 int automask_run(gridhip_ctx *ctx, int64_t N, const double *image, uint8_t *mask, int64_t border, int absolute,
                  double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
@@ -417,6 +441,12 @@ int restore_check(gridhip_ctx *ctx, int64_t N, const double *model, const double
 int fit_beam_run(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, double *beam);
 int restore_run(gridhip_ctx *ctx, int64_t N, const double *model, const double *residual, const double *beam,
                 int64_t support, double *restored);
+// a beam restore and find_sources may use: ok set, A, B, C finite and positive definite
+__host__ __device__ inline bool beam_usable(double A, double B, double C, double ok)
+{
+    const double inf = __builtin_inf();
+    return ok != 0.0 && ok == ok && A > 0.0 && A < inf && C > 0.0 && C < inf && B > -inf && B < inf && A * C - B * B > 0.0;
+}
 // What restore.hip and msclean.hip's set-up convolution share: the tile and the staged LDS layout (restore.hip's head).
 constexpr int RS_TH = 32, RS_TW = 64, RS_LX = RS_TW / 8;  // the tile; lanes along x
 // the staged width of `cols` cells (cell u lies at u + u / 8) and the row stride: the next count that is 8 modulo 32
@@ -526,5 +556,46 @@ int dft_predict_run(gridhip_ctx *ctx, int64_t C, const double *comps, const int6
                     const double *vis_sub, double *vis_out, double *stats);
 int components_run(gridhip_ctx *ctx, int64_t N, double theta, int T, const double *model, int64_t max_c, double *comps,
                    int64_t *count_dev);
+
+// What the two ordered compactions (dft.hip's non-zero cells, sources.hip's island roots) share: the counts of the threads
+// before this one (exclusive) and of all the work-group of 256 (*total); lds: 4 values
+__device__ __forceinline__ unsigned int block_rank(unsigned int mine, unsigned int *lds, unsigned int *total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned int inc = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    unsigned int before = 0, all = 0;
+    for (int wv = 0; wv < 4; ++wv) {
+        if (wv < wave) before += lds[wv];
+        all += lds[wv];
+    }
+    *total = all;
+    return before + inc - mine;
+}
+constexpr int CFI_SEG = 1024;  // cells of a segment of a compaction: 4 per thread
+// offs = the exclusive scan of the nseg segment counts, *count = their sum: one work-group (cfi_scan_kernel, dft.hip)
+int segment_scan(gridhip_ctx *ctx, int64_t nseg, const unsigned int *segcount, int64_t *offs, int64_t *count);
+
+// ---- source finding (sources.hip) ---------------------------------------------------------------------------------------------
+constexpr int64_t SRC_MAX_N = 46340;  // automask's limit: labels are 32-bit cell indices
+// gridhip_find_sources' argument rules (GRIDHIP_EINVAL, then GRIDHIP_EUNSUPPORTED); nothing is read; *N: the image size
+int sources_check(gridhip_ctx *ctx, double theta, int64_t lam, const double *image, int64_t border, double thr_hi,
+                  double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
+                  int64_t min_cells, const double *beam, int correct, int64_t max_c, const double *comps, const double *info,
+                  const int64_t *count, const double *stats, int64_t *N);
+// the segment counts and offsets of the compaction, and a root and a box per row that can be written
+size_t sources_scratch_bytes(int64_t N, int64_t max_c);
+// gridhip_find_sources_dev on checked arguments: kernels only, on ctx->stream; am_scratch: automask_scratch_bytes(N),
+// scratch: sources_scratch_bytes(N, max_c)
+int sources_run(gridhip_ctx *ctx, int64_t N, double theta, const double *image, int64_t border, double thr_hi,
+                double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac, int64_t min_cells,
+                const double *beam, int correct, int64_t max_c, double *comps, double *info, int64_t *count, double *stats,
+                void *am_scratch, void *scratch);
 
 }  // namespace gridhip

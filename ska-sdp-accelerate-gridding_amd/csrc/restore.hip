@@ -109,13 +109,7 @@ __global__ void __launch_bounds__(FIT_T)
 }
 
 // ---- the restore -------------------------------------------------------------------------------------------------------
-// a beam restore may use: ok set, A, B, C finite and positive definite
-__host__ __device__ inline bool beam_usable(double A, double B, double C, double ok)
-{
-    const double inf = __builtin_inf();
-    return ok != 0.0 && ok == ok && A > 0.0 && A < inf && C > 0.0 && C < inf && B > -inf && B < inf && A * C - B * B > 0.0;
-}
-
+// (beam_usable - ok set, A, B, C finite and positive definite - is in imaging.h: sources.hip shares it)
 // grid (ceil(N / RS_TW), ceil(N / RS_TH)); dynamic LDS: restore_lds_bytes(s); stride = staged_stride(s).
 // restored may be residual itself: a cell is read and written by the same thread.
 __global__ void __launch_bounds__(256)

@@ -20,6 +20,7 @@
 //   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
 //   flag_residuals: robust per-group clipping of visibility residuals (absent from the reference)
 //   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
+//   find_sources: a map as a list of Gaussian components - islands, moments, the beam deconvolved (absent from the reference)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //
@@ -577,6 +578,42 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_components_from_image(ctx_, theta, lam, (int)terms, model.data(), max_c, comps.data(), &count));
         comps.resize((size_t)(count < max_c ? count : max_c) * GRIDHIP_COMP_DOUBLES);
         if (found) *found = count;
+        return comps;
+    }
+
+    // ---- source finding (gridhip_find_sources; include/gridhip.h, "source finding") ----
+    // The islands of `image` (N x N, N = gridhip_image_size(theta, lam)) under automask's levels, without growing, each
+    // measured by its moments and written as one component row {l, m, flux, 0, 0, 0, bmaj, bmin, bpa, 0} for dft_predict,
+    // in ascending order of the island's first cell.  beam (fit_beam's; NULL: none) turns units per beam into integrated
+    // flux and is deconvolved from the shape; correct undoes the cut of a Gaussian at T_lo.  At most max_c rows; info
+    // (when given) receives GRIDHIP_SRC_DOUBLES doubles per row.  reason: 0 the steps ran, 2 no cell takes part, 3 no
+    // usable sigma.
+    struct SourceStats {
+        F T_hi, T_lo, peak, found, written, points, flux, reason;
+    };
+    std::vector<F> find_sources(F theta, Int lam, const Matrix<F> &image, F sigma, Int max_c, const Beam *beam = nullptr,
+                                bool correct = true, F nsigma_hi = 5, F nsigma_lo = 2.5, F thr_hi = 0, F thr_lo = 0,
+                                F peak_frac = 0, Int min_cells = 1, Int border = 0, SourceStats *stats = nullptr,
+                                std::vector<F> *info = nullptr)
+    {
+        const Int N = gridhip_image_size(theta, lam);
+        if (max_c < 0 || image.h != N || image.w != N)
+            throw Error(GRIDHIP_EINVAL, "find_sources: an image of N x N, N = image_size(theta, lam), max_c >= 0");
+        std::vector<F> comps((size_t)max_c * GRIDHIP_COMP_DOUBLES, 0);
+        if (info) info->assign((size_t)max_c * GRIDHIP_SRC_DOUBLES, 0);
+        F b[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (beam) {
+            const F v[8] = {beam->A, beam->B, beam->C, beam->bmaj, beam->bmin, beam->bpa, beam->ncells, beam->ok};
+            for (int i = 0; i < 8; ++i) b[i] = v[i];
+        }
+        int64_t count = 0;
+        check(gridhip_find_sources(ctx_, theta, lam, image.data.data(), border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, &sigma,
+                                   peak_frac, min_cells, beam ? b : nullptr, correct ? 1 : 0, max_c, comps.data(),
+                                   info ? info->data() : nullptr, &count, st));
+        const size_t rows = (size_t)(count < max_c ? count : max_c);
+        comps.resize(rows * GRIDHIP_COMP_DOUBLES);
+        if (info) info->resize(rows * GRIDHIP_SRC_DOUBLES);
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
         return comps;
     }
 

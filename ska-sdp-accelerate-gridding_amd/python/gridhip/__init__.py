@@ -28,7 +28,7 @@ from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, 
 from ._marshal import gain_stream, result_array, solve_args, stream_array
 from ._marshal import flag_outputs, flag_scalars, flag_stream
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
-from ._marshal import automask_args, mask_in_place
+from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import weighting as _weighting
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups"]
@@ -657,6 +657,30 @@ class Context(Handle):
         self._call(be, "components_from_image", float(theta), int(lam), T, model, max_c, out, count)
         return out, (int(count[0]) if be is HOST else count)
 
+    def find_sources(self, theta, lam, image, beam=None, noise=None, border=0, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0,
+                     min_cells=1, correct=True, max_sources=1024, out=None, info=True):
+        """A catalogue of the N x N float64 map `image`, N = image_size(theta, lam) (gridhip_find_sources[_dev];
+        include/gridhip.h, "source finding"): the islands of automask's levels - above T_lo = max(thr[1], nsigma[1] * sigma,
+        peak_frac * peak) around at least `min_cells` connected cells above T_hi, no growing - each measured by its moments
+        about its peak and written as one component row {l, m, flux, 0, 0, 0, bmaj, bmin, bpa, 0} that dft_predict takes as
+        it is, in ascending order of the island's first cell.  `beam` (the 8 values of fit_beam, or None) turns units per
+        beam into integrated flux and is deconvolved from the shape; `correct` undoes the cut of a Gaussian at T_lo; an
+        island whose deconvolved shape is not positive definite is a point.  `noise` is sigma as for automask.  Returns
+        (comps, count, info, stats): comps a (max_sources, 10) array whose first min(count, max_sources) rows are written
+        (out: the array to write; a new one of zeros when None); count the islands found - an int for numpy, one int64 cuda
+        element for torch tensors, which dft_predict takes as `count`; info (None with info=False) the (max_sources, 16) rows
+        [label, ncells, yp, xp, peak, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1, flags (1 point, 2 at the edge, 4 beam
+        unusable)]; stats = [T_hi, T_lo, peak, islands found, rows written, of them points, their summed flux, reason].
+        numpy arrays take the synchronous host form; torch cuda tensors the asynchronous one: nothing is read back, and
+        with `noise` a device element the call can be captured."""
+        be = backend(image)
+        N = self.image_size(theta, lam)
+        image = image_of(be, image, (N, N), "image")
+        args = source_args(be, thr, nsigma, noise, peak_frac, min_cells, beam, correct, max_sources, out, info, image)
+        self._call(be, "find_sources", float(theta), int(lam), image, int(border), *args)
+        comps, table, count, stats = args[-4:]
+        return comps, (int(count[0]) if be is HOST else count), table, stats
+
     def imager(self, theta, lam, uvw, imgfn, a1=None, a2=None, weighting="uniform", robust=0.0, taper=0.0, weights=None):
         """Bind the baselines `uvw` (torch cuda tensors, wavelengths, not mirrored: a (u, v, w) tuple or an (n, 3) tensor)
         and the imaging function `imgfn` (predict's tuples; "aw" with the antenna indices a1, a2) once
@@ -850,6 +874,18 @@ class Imager(_Bound):
         stats = be.empty(8, be.f64, self.device)
         self._call(be, "imager_automask", image, m8, int(border), *args, stats)
         return mask, stats
+
+    def find_sources(self, image, beam=None, noise=None, border=0, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0, min_cells=1,
+                     correct=True, max_sources=1024, out=None, info=True):
+        """Context.find_sources of an N x N cuda float64 map with the imager's theta, lam and its own scratch
+        (gridhip_imager_find_sources_dev): asynchronous, and capturable after a first call with as many rows.  Returns
+        (comps, count, info, stats)."""
+        self._open()
+        be, NN = device(), (self.N, self.N)
+        self._ok(image, be.f64, NN, "image")
+        args = source_args(be, thr, nsigma, noise, peak_frac, min_cells, beam, correct, max_sources, out, info, self.device)
+        self._call(be, "imager_find_sources", image, int(border), *args)
+        return args[-4], args[-2], args[-3], args[-1]
 
     def clean(self, image, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, mask=None, nsigma=0.0,
               noise=None, peak_frac=0.0):

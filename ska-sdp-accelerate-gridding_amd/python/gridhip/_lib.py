@@ -58,6 +58,10 @@ _FLAG_ARGS = [C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]  # nsigma, amax,
 _FLAG = [vp, i64, i64, vp, vp, vp, vp, *_FLAG_ARGS]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
+# border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats
+# (find_sources, after the image)
+_FIND_SOURCES_ARGS = [i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, C.c_double, i64, vp, ci, i64, vp, vp, vp, vp]
+_FIND_SOURCES = [vp, C.c_double, i64, vp, *_FIND_SOURCES_ARGS]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -189,6 +193,9 @@ SIGNATURES = {
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),
     "gridhip_components_from_image_dev": (ci, _COMPONENTS),
+    "gridhip_find_sources": (ci, _FIND_SOURCES),
+    "gridhip_find_sources_dev": (ci, _FIND_SOURCES),
+    "gridhip_imager_find_sources_dev": (ci, [vp, vp, *_FIND_SOURCES_ARGS]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

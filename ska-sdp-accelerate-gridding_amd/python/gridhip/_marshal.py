@@ -464,6 +464,30 @@ def component_count(be, count, like):
     return count
 
 
+SRC_DOUBLES = 16  # GRIDHIP_SRC_DOUBLES: { label, ncells, yp, xp, peak, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1, flags }
+
+
+def source_args(be, thr, nsigma, noise, peak_frac, min_cells, beam, correct, max_sources, out, info, like):
+    """thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats as
+    the find_sources entry points take them (include/gridhip.h, "source finding"): the levels as for automask_args; beam:
+    the 8 values of fit_beam as an array of `be`'s own kind, or None; out: the (max_sources, 10) array to write, or None
+    for a new one of zeros; info: whether the (max_sources, 16) table of measurements is wanted."""
+    levels = automask_args(be, False, thr, nsigma, noise, peak_frac, min_cells, 0, like)[1:8]
+    max_c = int(max_sources)
+    if max_c < 0:
+        raise ValueError("max_sources must be >= 0")
+    if beam is not None:
+        if be is not backend(beam) or not hasattr(beam, "shape") or tuple(beam.shape) != (8,):
+            raise ValueError(f"beam must be the 8 values of fit_beam as a {be.array}, or None")
+        beam = be.cv(beam, be.f64)
+    if out is None:
+        out = be.zeros((max_c, COMP_DOUBLES), be.f64, like)
+    else:
+        out = result_array(be, out, be.f64, (max_c, COMP_DOUBLES), "out", like)
+    table = be.zeros((max_c, SRC_DOUBLES), be.f64, like) if info else None
+    return (*levels, beam, int(bool(correct)), max_c, out, table, be.zeros(1, be.i64, like), be.empty(8, be.f64, like))
+
+
 def model_planes(be, model, N):
     """T, model as gridhip_components_from_image takes a model: (N, N), or (T, N, N) with T in 1..4, float64"""
     shape = tuple(getattr(model, "shape", ()))
