@@ -143,7 +143,8 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  * call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
  * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or
  * aw plan or aw imager creation built (0 after an aw plan pass or an imager's cycle);
- * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan / awdegrid / aw plan pass call used:
+ * "last_path" = which gridder the last convgrid / convgrid2 / degrid2 / plan / aw gridding (convgrid4, aw_imaging and the
+ * other calls that run the aw batch loop) / awdegrid / aw plan pass call used:
  * 1 = the tap-reusing tile kernel (square supports 5..32 with enough visibilities per work item), 2 = the same through
  * sub-footprints (other shapes: one record per spatial part of the kernel), 3 = the general tile kernel (small
  * problems, and the sizes listed under "Limits" below: 2 - 3 x slower per visibility at scale), 4 = direct

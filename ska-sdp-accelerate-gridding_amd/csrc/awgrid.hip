@@ -688,7 +688,7 @@ static int aw_batches(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double
     AwCall c;
     GH_CHECK(aw_setup(ctx, H, Wd, n, W, Q, S, A, true, &c));
     Prep &p = c.p;
-    if (degrid) ctx->last_path = p.sorted ? 1 : 3;
+    ctx->last_path = p.sorted ? 1 : 3;  // (gridding and the gather alike)
     GH_CHECK(ws_reserve(ctx, ctx->tables, tables_bytes(p.g)));
     GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)c.batch * sizeof(RecWord)));
 

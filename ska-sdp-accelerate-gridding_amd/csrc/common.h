@@ -183,7 +183,7 @@ struct gridhip_ctx {
     uint32_t attr_mask = 0;  // pre-pass kernels whose dynamic-LDS limit has been raised
     std::unordered_set<const void *> lds_raised;  // tile kernels whose dynamic-LDS limit has been raised
     gridhip::ImagingState *img = nullptr;  // what the layer around the gridder keeps between calls (imaging.h)
-    // which gridder the last convgrid / convgrid2 / degrid2 / plan call used (read-only option "last_path"):
+    // which gridder the last convgrid / convgrid2 / degrid2 / plan / aw call used (read-only option "last_path"):
     // 1 = tap-reusing tile kernel, 2 = the same through sub-footprints (one record per spatial part of the kernel),
     // 3 = general tile kernel (small problems; shapes or sizes the tap-reusing kernel does not take),
     // 4 = direct global-atomic scatter (option variant = 1, supports too large for an LDS tile)

@@ -81,10 +81,13 @@ def test_tuning_knobs_do_not_change_results(ctx, oracle, tile, block, wgroups, c
         for k, val in (("tile", tile), ("block", block), ("wgroups", wgroups), ("chunk", chunk), ("sort", sort)):
             ctx.set_option(k, val)
         got = ctx.convgrid2(gcf, np.zeros((N, N), dtype=np.complex128), (u, v, None), wb, vis)
+        path = ctx.get_option("last_path")
     finally:
         for k in ("tile", "block", "wgroups", "chunk", "sort"):
             ctx.set_option(k, 0)
     assert rel(got, ref) < TOL
+    assert sort != 1 or path == 1      # the rows that force the tap-reusing kernel on really ran it
+    assert sort != 2 or path == 3
 
 
 @pytest.mark.parametrize("dist", ["uniform", "core"])
@@ -98,9 +101,11 @@ def test_sorted_variant_matches_oracle(ctx, oracle, dist):
         ctx.set_option("sort", 1)
         try:
             got = ctx.convgrid2(gcf, np.zeros((N, N), dtype=np.complex128), (u, v, None), wb, vis)
+            path = ctx.get_option("last_path")
         finally:
             ctx.set_option("sort", 0)
         assert rel(got, ref) < TOL
+        assert path == 1, (N, W, Q, S, n)
 
 
 @pytest.mark.parametrize("shape", [(256, 256, 8, 8, 15, 15, 20000, {}), (128, 96, 2, 2, 5, 9, 5000, {}),
@@ -483,20 +488,28 @@ def test_subfootprints_large_and_nonsquare_supports(ctx, oracle, N, M, W, Q, gh,
         ctx.set_option("subfoot", subfoot)
         for k, val in opts.items():
             ctx.set_option(k, val)
+        paths = []
         got = ctx.convgrid2(gcf, np.zeros((N, M), dtype=np.complex128), (u, v, None), wb, vis)
         e1 = ctx.get_option("errors")
+        paths.append(ctx.get_option("last_path"))
         d = ctx.degrid2(gcf, G, (u, v, None), wb)
         e2 = ctx.get_option("errors")
+        paths.append(ctx.get_option("last_path"))
         plan = ctx.plan((N, M), gcf.shape, (t(u), t(v), None), t(wb))
         pg = plan.grid(t(gcf), torch.zeros((N, M), dtype=torch.complex128, device=dev), t(vis)).cpu().numpy()
+        paths.append(ctx.get_option("last_path"))
         pd = plan.degrid(t(gcf), t(G)).cpu().numpy()
+        paths.append(ctx.get_option("last_path"))
         plan.close()
         ctx.set_option("prepass", 2)   # the two-level scatter with pre-records, one record per part
         got2 = ctx.convgrid2(gcf, np.zeros((N, M), dtype=np.complex128), (u, v, None), wb, vis)
+        paths.append(ctx.get_option("last_path"))
     finally:
         for k in ("sort", "tile", "block", "wgroups", "prepass", "subfoot"):
             ctx.set_option(k, 0)
     assert e1 == 0 and e2 == 0
+    # 1 = one record per visibility (square supports 17..32 unless "subfoot" = 1), 2 = one record per spatial part
+    assert paths == [1 if gh == gw and 17 <= gh <= 32 and subfoot == 0 else 2] * 5
     assert rel(got, ref) < TOL and rel(got2, ref) < TOL and rel(pg, ref) < TOL
     assert rel(d, dref) < TOL and rel(pd, dref) < TOL
 
@@ -518,20 +531,26 @@ def test_every_support_17_to_32_in_parts_of_the_tap_list(ctx, oracle, S):
     t = lambda a: torch.from_numpy(a).to(dev)
     try:
         ctx.set_option("sort", 1)
+        paths = []
         got = ctx.convgrid2(gcf, np.zeros((N, M), dtype=np.complex128), (u, v, None), wb, vis)
+        paths.append(ctx.get_option("last_path"))
         d = ctx.degrid2(gcf, G, (u, v, None), wb)
         errors = ctx.get_option("errors")
+        paths.append(ctx.get_option("last_path"))
         plan = ctx.plan((N, M), gcf.shape, (t(u), t(v), None), t(wb))
         pd = plan.degrid(t(gcf), t(G)).cpu().numpy()
+        paths.append(ctx.get_option("last_path"))
         pd2 = plan.degrid(t(gcf), t(G), out=torch.full((n,), 7.0 + 1j, dtype=torch.complex128, device=dev)).cpu().numpy()
         plan.close()
         ctx.set_option("wgroups", 1)
         ctx.set_option("tile", 24)
         got_small = ctx.convgrid2(gcf, np.zeros((N, M), dtype=np.complex128), (u, v, None), wb, vis)
+        paths.append(ctx.get_option("last_path"))
     finally:
         for k in ("sort", "wgroups", "tile"):
             ctx.set_option(k, 0)
     assert errors == 0
+    assert paths == [1, 1, 1, 1]       # the tap-reusing kernel, one record per visibility, in every call
     assert rel(got, ref) < TOL and rel(got_small, ref) < TOL
     assert rel(d, dref) < TOL and rel(pd, dref) < TOL and rel(pd2, dref) < TOL
 
@@ -551,10 +570,12 @@ def test_degrid2_sorted_variant(ctx, oracle, N, W, Q, S, n, opts):
         for k, val in opts.items():
             ctx.set_option(k, val)
         got = ctx.degrid2(gcf, G, (u, v, None), wb)
+        path = ctx.get_option("last_path")
     finally:
         for k in ("sort", "tile", "block", "wgroups"):
             ctx.set_option(k, 0)
     assert ctx.get_option("errors") == 0
+    assert path == 1
     assert rel(got, ref) < TOL
 
 
