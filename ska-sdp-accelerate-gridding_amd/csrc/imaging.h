@@ -264,6 +264,8 @@ struct AwFront {
 int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt, AwFront &f);
 
 // ---- deconvolution (clean.hip) -------------------------------------------------------------------------------------------
+// (what the three CLEANs share on the device and in their launchers - the tile, the table entry, the search rule, the
+// walk over a tile - is in clean_walk.h, which only they include; here are the host declarations)
 // the largest N clean's tile grid holds (65535 rows of 16-row tiles); the restore takes the same limit
 constexpr int64_t CLEAN_MAX_N = 16 * 65535;
 // gridhip_clean's argument rules (GRIDHIP_EINVAL; an N the tile grid cannot hold is GRIDHIP_EUNSUPPORTED)
@@ -289,50 +291,6 @@ int clean_auto_check(gridhip_ctx *ctx, int64_t N, const double *residual, const 
 int clean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual, double *model, double gain,
               double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch,
               const CleanAuto &au = CleanAuto{});
-
-// What clean.hip and msclean.hip share: the tile, a tile's table entry, the search rule and its reductions.
-constexpr int CLEAN_TH = 16, CLEAN_TW = 128;  // one wave takes one row of a tile, 16 bytes per lane
-static_assert(CLEAN_MAX_N == (int64_t)CLEAN_TH * 65535, "the tile grid's limit");
-
-struct CleanEntry {  // a tile's peak: the signed value and its flat index; k < 0: no cell of the tile can be selected
-    double v;
-    long long k;
-};
-
-__device__ __forceinline__ int64_t lo64(int64_t a, int64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ int64_t hi64(int64_t a, int64_t b) { return a > b ? a : b; }
-
-// does (v, k) beat the best so far?  NaN never does; a larger magnitude does, and the lower index among equals
-__device__ __forceinline__ void consider(double v, long long k, double &bv, long long &bk)
-{
-    const double a = fabs(v), b = fabs(bv);
-    if (v == v && k >= 0 && (bk < 0 || a > b || (a == b && k < bk))) {
-        bv = v;
-        bk = k;
-    }
-}
-
-// the best of a work-group in thread 0 (sh: one entry per wave)
-__device__ __forceinline__ void group_best(double &bv, long long &bk, CleanEntry *sh)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_down(bv, off);
-        const long long ok = __shfl_down(bk, off);
-        consider(ov, ok, bv, bk);
-    }
-    const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[wave] = {bv, bk};
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < nwaves; ++w) consider(sh[w].v, sh[w].k, bv, bk);
-}
-
-// the most tiles of side T an interval of L cells overlaps, wherever it starts (at most all `have` of them)
-static inline int64_t tiles_spanned(int64_t L, int64_t T, int64_t have)
-{
-    const int64_t t = (L + T - 2) / T + 1;
-    return t < have ? t : have;
-}
 
 // ---- multi-scale CLEAN (msclean.hip) ---------------------------------------------------------------------------------------
 constexpr int MS_MAX_SCALES = 6;
@@ -360,30 +318,6 @@ size_t mfclean_scratch_bytes(int64_t N);
 // gridhip_mfclean_dev on checked arguments: kernels only, on ctx->stream; scratch: mfclean_scratch_bytes(N)
 int mfclean_run(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, double *residuals, double *models,
                 double gain, double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
-
-// The stop level of an _auto call, by the first pick kernel: T = max(threshold, nsigma * sigma, peak_frac * |p1|), each
-// product rounded once, a term whose factor is 0 left out (noise is then not read); p1 is NaN when nothing can be
-// selected and its term is then left out.  *bad: nsigma > 0 and sigma is NaN - T is NaN and the call stops at once.
-__device__ __forceinline__ double stop_level(double threshold, double nsigma, const double *noise, double peak_frac,
-                                             double p1, bool *bad)
-{
-    double T = threshold;
-    *bad = false;
-    if (nsigma > 0.0) {
-        const double sigma = *noise;
-        if (sigma != sigma) {
-            *bad = true;
-            return sigma;
-        }
-        const double a = nsigma * sigma;
-        T = a > T ? a : T;
-    }
-    if (peak_frac > 0.0 && p1 == p1) {
-        const double b = peak_frac * fabs(p1);
-        T = b > T ? b : T;
-    }
-    return T;
-}
 
 // ---- robust image statistics (noise.hip) -----------------------------------------------------------------------------------
 // gridhip_image_stats' argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED)

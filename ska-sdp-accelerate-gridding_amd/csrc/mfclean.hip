@@ -1,7 +1,8 @@
 // Multi-term CLEAN, the minor cycle of wide-band imaging (include/gridhip.h, "wide-band imaging"): T Taylor terms of the
 // residual are cleaned together with the 2T - 1 spectral PSFs (Sault & Wieringa 1994; Rau & Cornwell 2011, one scale).
 // The shape is clean.hip's: tiles of CLEAN_TH x CLEAN_TW, a device table of one (score, index) entry per tile, a state
-// block that holds the stop condition, niter iterations enqueued unconditionally.  One call is
+// block that holds the stop condition, niter iterations enqueued unconditionally - and the code is: the walk over a tile,
+// the table's reduction and the launch loop are clean_walk.h's; this file has what T terms add to them.  One call is
 //     mf_tile_kernel<T, false>   builds the table: one pass over the T residuals; each work-group inverts the T x T
 //                                Hessian for itself (at most 7 doubles read, a few dozen operations)
 //     mf_pick_kernel<T, true>    inverts it once more into the state block, starts the state, takes the first component
@@ -13,7 +14,7 @@
 // against Hogbom's 24.  The kernels are templated on T so that the T x T products and the 3T - 1 values of a cell live in
 // registers.  No atomics; contraction is off: a plain restatement in numpy gives the same bits.
 #include "common.h"
-#include "imaging.h"
+#include "clean_walk.h"
 
 namespace gridhip {
 
@@ -89,109 +90,45 @@ __device__ __forceinline__ double mf_score(const double *Hinv, const double *R)
     return s;
 }
 
+// What clean_tile_walk (clean_walk.h) does with T terms: T residual planes and 2T - 1 PSF planes, N * N cells apart;
+// R_t loses the products f_q P_{t+q}, q ascending, each rounded, then subtracted; the score of a cell from its T values.
+template <int TT>
+struct MfWalk {
+    static constexpr int T = TT, NP = 2 * TT - 1;
+    double *res;
+    const double *psf;
+    int64_t cells;
+    double f[TT], Hinv[TT * TT];
+    __device__ __forceinline__ double product(int t, int q, const double (&p)[NP]) const
+    {
+#pragma clang fp contract(off)
+        return f[q] * p[t + q];
+    }
+    __device__ __forceinline__ double score(const double (&r)[T]) const { return mf_score<T>(Hinv, r); }
+    __device__ __forceinline__ bool searched(int64_t) const { return true; }
+};
+
 // One tile per work-group, clean_tile_kernel's geometry: SUB = false over all tiles, SUB = true over the tiles the update
-// region can overlap, counted from its first tile.  A lane takes the two cells of one 16-byte slot of the row, in all T
-// residual planes and - inside the region - all 2T - 1 PSF planes; the slots are those of plane 0.  For odd N the planes
-// are 8 bytes apart in alignment, so a plane (or a shifted PSF address) that is not aligned where plane 0 is takes its
-// two cells by two 8-byte accesses.
+// region can overlap, counted from its first tile.  The slots a lane takes are those of plane 0; for odd N the planes
+// are 8 bytes apart in alignment, and the walk takes a plane (or a shifted PSF address) that is not aligned where plane 0
+// is by two 8-byte accesses.
 template <int T, bool SUB>
 __global__ void __launch_bounds__(256)
     mf_tile_kernel(int64_t N, int64_t border, int64_t patch, int ntx, const double *__restrict__ psfs, double *res,
                    CleanEntry *__restrict__ table, const MfState *st)
 {
-#pragma clang fp contract(off)
     __shared__ CleanEntry sh[4];
-    int64_t tx = blockIdx.x, ty = blockIdx.y;
-    int64_t ylo = 0, yhi = -1, xlo = 0, xhi = -1, py = 0, px = 0;
-    const int64_t c = N / 2, cells = N * N;
-    double f[T], Hinv[T * T];
+    if (SUB && st->stopped) return;
+    MfWalk<T> w;
+    w.res = res, w.psf = psfs, w.cells = N * N;
     if (SUB) {
-        if (st->stopped) return;
-        const int64_t k = st->k;
-        for (int t = 0; t < T; ++t) f[t] = st->f[t];
-        for (int i = 0; i < T * T; ++i) Hinv[i] = st->Hinv[i];
-        py = k / N, px = k % N;
-        ylo = py - c, yhi = py - c + N - 1, xlo = px - c, xhi = px - c + N - 1;
-        if (patch > 0) {
-            ylo = hi64(ylo, py - patch), yhi = lo64(yhi, py + patch);
-            xlo = hi64(xlo, px - patch), xhi = lo64(xhi, px + patch);
-        }
-        ylo = hi64(ylo, 0), yhi = lo64(yhi, N - 1), xlo = hi64(xlo, 0), xhi = lo64(xhi, N - 1);
-        ty += ylo / CLEAN_TH, tx += xlo / CLEAN_TW;
-        if (ty > yhi / CLEAN_TH || tx > xhi / CLEAN_TW) return;
+        for (int t = 0; t < T; ++t) w.f[t] = st->f[t];
+        for (int i = 0; i < T * T; ++i) w.Hinv[i] = st->Hinv[i];
     } else {
-        for (int t = 0; t < T; ++t) f[t] = 0.0;
-        (void)mf_invert<T>(psfs, cells, c * N + c, Hinv);  // (a singular one: the first pick stops the call)
+        for (int t = 0; t < T; ++t) w.f[t] = 0.0;
+        (void)mf_invert<T>(psfs, w.cells, (N / 2) * N + N / 2, w.Hinv);  // (a singular one: the first pick stops the call)
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t x0 = tx * CLEAN_TW, x1 = lo64(x0 + CLEAN_TW, N);
-    const int64_t mis = (int64_t)(((uintptr_t)res >> 3) & 1);  // res + a is 16-byte aligned where a + mis is even
-    double bv = 0.0;
-    long long bk = -1;
-    for (int r = wave; r < CLEAN_TH; r += 4) {
-        const int64_t y = ty * CLEAN_TH + r;
-        if (y >= N) break;
-        const int64_t base = y * N;
-        const bool yin = SUB && y >= ylo && y <= yhi, ysearch = y >= border && y < N - border;
-        const int64_t poff = (y - py + c) * N + (c - px) - base;  // psf index of the cell at flat index a: a + poff
-        const int64_t a0 = ((base + x0 + mis) & ~(int64_t)1) - mis, a1 = base + x1;
-        for (int64_t a = a0 + 2 * lane; a < a1; a += 128) {
-            const int64_t x = a - base;
-            const bool v0 = x >= x0, v1 = x + 1 < x1;  // (at least one holds: a slot has a cell of this tile's row)
-            double r0[T], r1[T];
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const double *q = res + t * cells + a;
-                r0[t] = 0.0, r1[t] = 0.0;
-                if (v0 && v1 && ((uintptr_t)q & 15) == 0) {
-                    const double2 w = *reinterpret_cast<const double2 *>(q);
-                    r0[t] = w.x, r1[t] = w.y;
-                } else {
-                    if (v0) r0[t] = q[0];
-                    if (v1) r1[t] = q[1];
-                }
-            }
-            if (yin) {
-                const bool u0 = v0 && x >= xlo && x <= xhi, u1 = v1 && x + 1 >= xlo && x + 1 <= xhi;
-                if (u0 || u1) {
-                    double p0[2 * T - 1], p1[2 * T - 1];
-#pragma unroll
-                    for (int s = 0; s < 2 * T - 1; ++s) {
-                        const double *q = psfs + s * cells + (a + poff);
-                        p0[s] = 0.0, p1[s] = 0.0;
-                        if (u0 && u1 && ((uintptr_t)q & 15) == 0) {
-                            const double2 w = *reinterpret_cast<const double2 *>(q);
-                            p0[s] = w.x, p1[s] = w.y;
-                        } else {
-                            if (u0) p0[s] = q[0];
-                            if (u1) p1[s] = q[1];
-                        }
-                    }
-#pragma unroll
-                    for (int t = 0; t < T; ++t) {
-#pragma unroll
-                        for (int q = 0; q < T; ++q) {
-                            if (u0) r0[t] = r0[t] - f[q] * p0[t + q];
-                            if (u1) r1[t] = r1[t] - f[q] * p1[t + q];
-                        }
-                        double *o = res + t * cells + a;
-                        if (u0 && u1 && ((uintptr_t)o & 15) == 0) {
-                            *reinterpret_cast<double2 *>(o) = make_double2(r0[t], r1[t]);
-                        } else {
-                            if (u0) o[0] = r0[t];
-                            if (u1) o[1] = r1[t];
-                        }
-                    }
-                }
-            }
-            if (ysearch) {
-                if (v0 && x >= border && x < N - border) consider(mf_score<T>(Hinv, r0), a, bv, bk);
-                if (v1 && x + 1 >= border && x + 1 < N - border) consider(mf_score<T>(Hinv, r1), a + 1, bv, bk);
-            }
-        }
-    }
-    group_best(bv, bk, sh);
-    if (threadIdx.x == 0) table[ty * ntx + tx] = {bv, bk};
+    clean_tile_walk<SUB>(N, border, patch, ntx, SUB ? st->k : 0, table, sh, w);
 }
 
 // One work-group: the table's best is the cell with the largest score.  Then, by thread 0, the head of the next
@@ -208,10 +145,9 @@ __global__ void __launch_bounds__(1024)
 #pragma clang fp contract(off)
     __shared__ CleanEntry sh[16];
     if (!INIT && st->stopped) return;
-    double bv = 0.0;
-    long long bk = -1;
-    for (int t = threadIdx.x; t < ntiles; t += blockDim.x) consider(table[t].v, table[t].k, bv, bk);
-    group_best(bv, bk, sh);
+    double bv;
+    long long bk;
+    table_best(table, ntiles, bv, bk, sh);
     if (threadIdx.x != 0) return;
     const int64_t cells = N * N;
     double Hinv[T * T], flux[4] = {0.0, 0.0, 0.0, 0.0};
@@ -258,33 +194,24 @@ __global__ void __launch_bounds__(1024)
     }
 }
 
-bool overlap(const double *a, size_t abytes, const double *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bbytes && y < x + abytes;
-}
-
 template <int T>
 void mf_launch(gridhip_ctx *ctx, int64_t N, const double *psfs, double *res, double *models, double gain,
                double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch)
 {
-    const int64_t ntx = (N + CLEAN_TW - 1) / CLEAN_TW, nty = (N + CLEAN_TH - 1) / CLEAN_TH;
+    const CleanTiles g = clean_tiles(N, patch);
     MfState *st = reinterpret_cast<MfState *>(scratch);
     CleanEntry *table = reinterpret_cast<CleanEntry *>(st + 1);
-    const int ntiles = (int)(ntx * nty);
-    const int64_t span = patch > 0 && 2 * patch + 1 < N ? 2 * patch + 1 : N;
-    const dim3 all((unsigned)ntx, (unsigned)nty);
-    const dim3 part((unsigned)tiles_spanned(span, CLEAN_TW, ntx), (unsigned)tiles_spanned(span, CLEAN_TH, nty));
-    hipLaunchKernelGGL((mf_tile_kernel<T, false>), all, dim3(256), 0, ctx->stream, N, border, patch, (int)ntx, psfs, res,
-                       table, (const MfState *)st);
-    hipLaunchKernelGGL((mf_pick_kernel<T, true>), dim3(1), dim3(1024), 0, ctx->stream, N, ntiles,
-                       (const CleanEntry *)table, st, psfs, (const double *)res, models, gain, threshold, niter, stats);
-    for (int64_t i = 0; i < niter; ++i) {
-        hipLaunchKernelGGL((mf_tile_kernel<T, true>), part, dim3(256), 0, ctx->stream, N, border, patch, (int)ntx, psfs, res,
-                           table, (const MfState *)st);
-        hipLaunchKernelGGL((mf_pick_kernel<T, false>), dim3(1), dim3(1024), 0, ctx->stream, N, ntiles,
+    const auto tile = [&](auto sub, const dim3 &grid) {
+        hipLaunchKernelGGL((mf_tile_kernel<T, decltype(sub)::value>), grid, dim3(256), 0, ctx->stream, N, border, patch,
+                           g.ntx, psfs, res, table, (const MfState *)st);
+    };
+    const auto pick = [&](auto init) {
+        hipLaunchKernelGGL((mf_pick_kernel<T, decltype(init)::value>), dim3(1), dim3(1024), 0, ctx->stream, N, g.ntiles,
                            (const CleanEntry *)table, st, psfs, (const double *)res, models, gain, threshold, niter, stats);
-    }
+    };
+    clean_launch_loop(
+        niter, [&] { tile(std::false_type{}, g.all); }, [&] { pick(std::true_type{}); },
+        [&] { tile(std::true_type{}, g.part); }, [&] { pick(std::false_type{}); });
 }
 
 }  // namespace
@@ -302,8 +229,7 @@ int mfclean_check(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, co
 
 size_t mfclean_scratch_bytes(int64_t N)
 {
-    const int64_t ntx = (N + CLEAN_TW - 1) / CLEAN_TW, nty = (N + CLEAN_TH - 1) / CLEAN_TH;
-    return sizeof(MfState) + (size_t)ntx * nty * sizeof(CleanEntry);
+    return sizeof(MfState) + (size_t)clean_tiles(N).ntiles * sizeof(CleanEntry);
 }
 
 int mfclean_run(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, double *residuals, double *models,

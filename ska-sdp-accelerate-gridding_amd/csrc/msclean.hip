@@ -1,5 +1,6 @@
 // Multi-scale CLEAN (include/gridhip.h, "multi-scale deconvolution"): clean.hip's tile-peak table, on-device stop state
-// and two-launch iteration, widened to S scales, and restore.hip's LDS-tiled direct convolution for the set-up.
+// and two-launch iteration, widened to S scales, and restore.hip's LDS-tiled direct convolution for the set-up.  The walk
+// over a tile, the table's reduction and the launch loop are clean_walk.h's, the same code as clean.hip runs.
 //
 // A component of scale s is the tapered paraboloid m_s (the delta for s = 0) instead of one cell.  The loop keeps one
 // residual per scale, R_t = m_t (*) residual (R_0 is the caller's residual itself), and subtracts from each the cross-PSF
@@ -18,7 +19,7 @@
 // k, f, the pointers - lives in the state block on the device; the host reads nothing back, and a launch that finds the
 // state stopped returns at its first instruction.  No atomics; contraction is off wherever the header orders a rounding.
 #include "common.h"
-#include "imaging.h"
+#include "clean_walk.h"
 
 namespace gridhip {
 
@@ -163,97 +164,26 @@ __global__ void __launch_bounds__(256)
             if (xf + j < N) out[y * N + xf + j] = acc[j];
 }
 
-// clean_tile_kernel with a third grid dimension: slice t = blockIdx.z works on R_t and table t.  SUB = false: grid
-// (ntx, nty, S), the entry of every tile from R_t as it is.  SUB = true: grid (the most tiles the update region overlaps,
-// S); slice t subtracts f * P_{s* t}, shifted to the component's centre, over Hogbom's update region - the cells whose
-// PSF index lies in the grid, cut to the patch - and recomputes the entries of the tiles it touched in the same pass.
-// The access shape is clean_tile_kernel's: a lane takes the two cells of one 16-byte aligned slot, the shifted cross-PSF
-// is read 16 bytes at once where that address is aligned.  s*, k and f come from the state block.  MASK: a cell whose mask
-// byte is 0 is not searched, in any slice - the mask constrains component centres; the subtraction does not look at it.
+// clean_tile_kernel with a third grid dimension: slice t = blockIdx.z walks R_t and table t (clean_tile_walk,
+// clean_walk.h).  SUB = false: grid (ntx, nty, S), the entry of every tile from R_t as it is.  SUB = true: grid (the most
+// tiles the update region overlaps, S); slice t subtracts f * P_{s* t}, shifted to the component's centre, over Hogbom's
+// update region and recomputes the entries of the tiles it touched in the same pass.  s*, k and f come from the state
+// block.  MASK: a cell whose mask byte is 0 is not searched, in any slice - the mask constrains component centres; the
+// subtraction does not look at it.
 template <bool SUB, bool MASK>
 __global__ void __launch_bounds__(256)
     ms_tile_kernel(int64_t N, int64_t border, int64_t patch, int ntx, int ntiles, double *residual,
                    CleanEntry *__restrict__ tables, const MsState *st, const uint8_t *__restrict__ mask)
 {
-#pragma clang fp contract(off)
     __shared__ CleanEntry sh[4];
     if (SUB && st->stopped) return;
     const int slice = blockIdx.z;
     double *res = slice == 0 ? residual : st->R[slice];
-    CleanEntry *table = tables + (size_t)slice * ntiles;
-    const double *psf = nullptr;
-    int64_t tx = blockIdx.x, ty = blockIdx.y;
-    int64_t ylo = 0, yhi = -1, xlo = 0, xhi = -1, py = 0, px = 0;
-    const int64_t c = N / 2;
-    double f = 0.0;
-    if (SUB) {
-        const int64_t k = st->k;
-        f = st->f;
-        psf = st->P[pair_index((int)st->s, slice)];
-        py = k / N, px = k % N;
-        ylo = py - c, yhi = py - c + N - 1, xlo = px - c, xhi = px - c + N - 1;
-        if (patch > 0) {
-            ylo = hi64(ylo, py - patch), yhi = lo64(yhi, py + patch);
-            xlo = hi64(xlo, px - patch), xhi = lo64(xhi, px + patch);
-        }
-        ylo = hi64(ylo, 0), yhi = lo64(yhi, N - 1), xlo = hi64(xlo, 0), xhi = lo64(xhi, N - 1);
-        ty += ylo / CLEAN_TH, tx += xlo / CLEAN_TW;
-        if (ty > yhi / CLEAN_TH || tx > xhi / CLEAN_TW) return;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t x0 = tx * CLEAN_TW, x1 = lo64(x0 + CLEAN_TW, N);
-    const int64_t mis = (int64_t)(((uintptr_t)res >> 3) & 1);  // res + a is 16-byte aligned where a + mis is even
-    double bv = 0.0;
-    long long bk = -1;
-    for (int r = wave; r < CLEAN_TH; r += 4) {
-        const int64_t y = ty * CLEAN_TH + r;
-        if (y >= N) break;
-        const int64_t base = y * N;
-        const bool yin = SUB && y >= ylo && y <= yhi, ysearch = y >= border && y < N - border;
-        const int64_t poff = (y - py + c) * N + (c - px) - base;  // psf index of the cell at flat index a: a + poff
-        const int64_t a0 = ((base + x0 + mis) & ~(int64_t)1) - mis, a1 = base + x1;
-        for (int64_t a = a0 + 2 * lane; a < a1; a += 128) {
-            const int64_t x = a - base;
-            const bool v0 = x >= x0, v1 = x + 1 < x1;  // (at least one holds: a slot has a cell of this tile's row)
-            double r0 = 0.0, r1 = 0.0;
-            if (v0 && v1) {
-                const double2 t = *reinterpret_cast<const double2 *>(res + a);
-                r0 = t.x, r1 = t.y;
-            } else if (v0) {
-                r0 = res[a];
-            } else {
-                r1 = res[a + 1];
-            }
-            if (yin) {
-                const bool u0 = v0 && x >= xlo && x <= xhi, u1 = v1 && x + 1 >= xlo && x + 1 <= xhi;
-                if (u0 || u1) {
-                    const double *q = psf + (a + poff);
-                    double p0 = 0.0, p1 = 0.0;
-                    if (u0 && u1 && ((uintptr_t)q & 15) == 0) {
-                        const double2 t = *reinterpret_cast<const double2 *>(q);
-                        p0 = t.x, p1 = t.y;
-                    } else {
-                        if (u0) p0 = q[0];
-                        if (u1) p1 = q[1];
-                    }
-                    if (u0) r0 = r0 - f * p0;
-                    if (u1) r1 = r1 - f * p1;
-                    if (u0 && u1)
-                        *reinterpret_cast<double2 *>(res + a) = make_double2(r0, r1);
-                    else if (u0)
-                        res[a] = r0;
-                    else
-                        res[a + 1] = r1;
-                }
-            }
-            if (ysearch) {
-                if (v0 && x >= border && x < N - border && (!MASK || mask[a] != 0)) consider(r0, a, bv, bk);
-                if (v1 && x + 1 >= border && x + 1 < N - border && (!MASK || mask[a + 1] != 0)) consider(r1, a + 1, bv, bk);
-            }
-        }
-    }
-    group_best(bv, bk, sh);
-    if (threadIdx.x == 0) table[ty * ntx + tx] = {bv, bk};
+    const long long k = SUB ? st->k : 0;
+    const double f = SUB ? st->f : 0.0;
+    const double *psf = SUB ? st->P[pair_index((int)st->s, slice)] : nullptr;
+    clean_tile_walk<SUB>(N, border, patch, ntx, k, tables + (size_t)slice * ntiles, sh,
+                         OneTermWalk<MASK>{res, psf, 0, f, mask});
 }
 
 // One work-group.  Each table's best is that scale's peak p_s at k_s.  Then the head of the next iteration, by thread 0:
@@ -278,11 +208,9 @@ __global__ void __launch_bounds__(1024)
     __shared__ int sh_s;
     if (!INIT && st->stopped) return;
     for (int s = 0; s < sc.S; ++s) {
-        const CleanEntry *table = tables + (size_t)s * ntiles;
-        double bv = 0.0;
-        long long bk = -1;
-        for (int t = threadIdx.x; t < ntiles; t += blockDim.x) consider(table[t].v, table[t].k, bv, bk);
-        group_best(bv, bk, sh);
+        double bv;
+        long long bk;
+        table_best(tables + (size_t)s * ntiles, ntiles, bv, bk, sh);
         if (threadIdx.x == 0) best[s] = {bv, bk};
         __syncthreads();  // (sh is free for the next scale)
     }
@@ -379,15 +307,13 @@ __global__ void __launch_bounds__(1024)
 // the sizes of the scratch block's parts, in bytes
 struct MsLayout {
     size_t state, tables, taps, image, total;
-    int64_t ntx, nty;
     int nimages;
 };
 MsLayout layout(int64_t N, int64_t S)
 {
     MsLayout l;
-    l.ntx = (N + CLEAN_TW - 1) / CLEAN_TW, l.nty = (N + CLEAN_TH - 1) / CLEAN_TH;
     l.state = (sizeof(MsState) + 255) & ~(size_t)255;
-    l.tables = ((size_t)S * l.ntx * l.nty * sizeof(CleanEntry) + 255) & ~(size_t)255;
+    l.tables = ((size_t)S * clean_tiles(N).ntiles * sizeof(CleanEntry) + 255) & ~(size_t)255;
     l.taps = ((size_t)(S - 1) * MS_TAPS * sizeof(double) + 255) & ~(size_t)255;
     l.image = ((size_t)N * N * sizeof(double) + 255) & ~(size_t)255;
     l.nimages = (int)((S - 1) + S * (S + 1) / 2 - 1);
@@ -398,7 +324,7 @@ MsLayout layout(int64_t N, int64_t S)
 struct MsLaunch {  // what the tile and pick launches of one call take
     gridhip_ctx *ctx;
     int64_t N, border, patch;
-    int ntx, ntiles;
+    CleanTiles t;  // (all and part with S slices)
     double *residual;
     CleanEntry *tables;
     MsState *st;
@@ -408,7 +334,6 @@ struct MsLaunch {  // what the tile and pick launches of one call take
     double gain, threshold;
     int64_t niter;
     double *stats;
-    dim3 all, part;
     CleanAuto au;
 };
 
@@ -416,18 +341,18 @@ template <bool MASK, bool AUTO>
 void ms_launch(const MsLaunch &a)
 {
     hipStream_t q = a.ctx->stream;
-    hipLaunchKernelGGL((ms_tile_kernel<false, MASK>), a.all, dim3(256), 0, q, a.N, a.border, a.patch, a.ntx, a.ntiles,
-                       a.residual, a.tables, (const MsState *)a.st, a.au.mask);
-    hipLaunchKernelGGL((ms_pick_kernel<true, AUTO>), dim3(1), dim3(1024), 0, q, a.N, a.ntiles, (const CleanEntry *)a.tables,
-                       a.st, a.sc, a.taps, a.model, a.gain, a.threshold, a.niter, a.stats, a.au.nsigma, a.au.noise,
-                       a.au.peak_frac);
-    for (int64_t i = 0; i < a.niter; ++i) {
-        hipLaunchKernelGGL((ms_tile_kernel<true, MASK>), a.part, dim3(256), 0, q, a.N, a.border, a.patch, a.ntx, a.ntiles,
-                           a.residual, a.tables, (const MsState *)a.st, a.au.mask);
-        hipLaunchKernelGGL((ms_pick_kernel<false, AUTO>), dim3(1), dim3(1024), 0, q, a.N, a.ntiles,
-                           (const CleanEntry *)a.tables, a.st, a.sc, a.taps, a.model, a.gain, a.threshold, a.niter, a.stats,
-                           a.au.nsigma, a.au.noise, a.au.peak_frac);
-    }
+    const auto tile = [&](auto sub, const dim3 &grid) {
+        hipLaunchKernelGGL((ms_tile_kernel<decltype(sub)::value, MASK>), grid, dim3(256), 0, q, a.N, a.border, a.patch,
+                           a.t.ntx, a.t.ntiles, a.residual, a.tables, (const MsState *)a.st, a.au.mask);
+    };
+    const auto pick = [&](auto init) {
+        hipLaunchKernelGGL((ms_pick_kernel<decltype(init)::value, AUTO>), dim3(1), dim3(1024), 0, q, a.N, a.t.ntiles,
+                           (const CleanEntry *)a.tables, a.st, a.sc, a.taps, a.model, a.gain, a.threshold, a.niter,
+                           a.stats, a.au.nsigma, a.au.noise, a.au.peak_frac);
+    };
+    clean_launch_loop(
+        a.niter, [&] { tile(std::false_type{}, a.t.all); }, [&] { pick(std::true_type{}); },
+        [&] { tile(std::true_type{}, a.t.part); }, [&] { pick(std::false_type{}); });
 }
 
 int conv(gridhip_ctx *ctx, int64_t N, const double *in, const double *taps, int s, double *out)
@@ -502,13 +427,9 @@ int msclean_run(gridhip_ctx *ctx, int64_t N, const double *psf, double *residual
     }
     for (int t = 1; t < (int)S; ++t) GH_CHECK(conv(ctx, N, residual, taps + (size_t)(t - 1) * MS_TAPS, sc.R[t], ptr.R[t]));
 
-    const int ntiles = (int)(l.ntx * l.nty);
-    const int64_t span = patch > 0 && 2 * patch + 1 < N ? 2 * patch + 1 : N;
-    const dim3 all((unsigned)l.ntx, (unsigned)l.nty, (unsigned)S);
-    const dim3 part((unsigned)tiles_spanned(span, CLEAN_TW, l.ntx), (unsigned)tiles_spanned(span, CLEAN_TH, l.nty),
-                    (unsigned)S);
-    const MsLaunch go = {ctx, N, border, patch, (int)l.ntx, ntiles, residual, tables, st, sc, taps, model, gain, threshold,
-                         niter, stats, all, part, au};
+    CleanTiles t = clean_tiles(N, patch);
+    t.all.z = t.part.z = (unsigned)S;
+    const MsLaunch go = {ctx, N, border, patch, t, residual, tables, st, sc, taps, model, gain, threshold, niter, stats, au};
     if (!au.on)
         ms_launch<false, false>(go);
     else if (au.mask)

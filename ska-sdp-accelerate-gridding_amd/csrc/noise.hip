@@ -257,7 +257,7 @@ int image_stats_check(gridhip_ctx *ctx, int64_t N, const double *image, const ui
                       const double *stats)
 {
     if (N < 1 || border < 0 || 2 * border >= N || !image || !stats) return fail(ctx, GRIDHIP_EINVAL, "image_stats: bad argument");
-    if (N > CLEAN_MAX_N) return fail(ctx, GRIDHIP_EUNSUPPORTED, "image_stats: N above %d", CLEAN_TH * 65535);
+    if (N > CLEAN_MAX_N) return fail(ctx, GRIDHIP_EUNSUPPORTED, "image_stats: N above %lld", (long long)CLEAN_MAX_N);
     const size_t cells = (size_t)N * N;
     if ((mask && (overlap_bytes(mask, cells, image, cells * 8) || overlap_bytes(stats, 64, mask, cells))) ||
         overlap_bytes(stats, 64, image, cells * 8))

@@ -91,6 +91,13 @@ def mfclean(psfs, residuals, models, gain, threshold, niter, border=0, patch=0, 
         iters += 1
 
 
+def midway_threshold(psfs, img, border=0, patch=0):
+    """A threshold that a clean of img reaches after some components and before many: half of |a_0| at the first peak,
+    which is what a run with niter = 0 reports.  (Half of the image's peak serves for up to three terms; with four the
+    coefficient a_0 at the first peak is already below it.)"""
+    return 0.5 * abs(mfclean(psfs, img.copy(), np.zeros_like(img), 1.0, 0.0, 0, border, patch)[1])
+
+
 def make_psfs(N, seed, T, fill=0.04):
     """The 2T - 1 spectral PSFs of clean_ref.make_psf's coverage: every occupied uv cell gets a random x in [-0.25, 0.25],
     term s has the point-symmetrised weights occ * x^s, and all terms are divided by P_0[c, c].  make_psfs(N, seed, 1)[0]

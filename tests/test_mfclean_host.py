@@ -146,6 +146,26 @@ def test_one_term_is_hogbom_bit_for_bit(border, patch):
     assert np.array_equal(s2, [s1[0], s1[1], s1[2], s1[3], 0.0, 0.0, 0.0, 0.0])
 
 
+@pytest.mark.parametrize("patch", [0, 32])
+@pytest.mark.parametrize("wide_border", [False, True])
+@pytest.mark.parametrize("N", [256, 255])
+def test_four_terms_meet_the_gpu_tests_preconditions(N, wide_border, patch):
+    """tests/test_gpu_mfclean.py's T = 4 cases, the restatement alone: the midway threshold stops the loop after some
+    components and before niter, threshold 0 is never reached, and the two largest scores never come closer than 1e-8."""
+    T, niter, border = 4, 200, N // 8 if wide_border else 0
+    psfs = mfclean_ref.make_psfs(N, 100, T)
+    img, _ = mfclean_ref.make_sky(psfs, 101)
+    mid = mfclean_ref.midway_threshold(psfs, img, border, patch)
+    assert mid > 0.0
+    for threshold in (mid, 0.0):
+        trace = []
+        st = mfclean_ref.mfclean(psfs, img.copy(), np.zeros_like(img), 0.2, threshold, niter, border, patch, trace)
+        print(f"N {N} border {border} patch {patch} threshold {threshold:.3e}: {st[0]:.0f} components, reason {st[7]:.0f}, "
+              f"smallest gap {min(g for _, g in trace):.2e}")
+        assert (0 < st[0] < niter and st[7] == 1) if threshold > 0.0 else (st[0] == niter and st[7] == 0), st
+        assert len(trace) == st[0] and min(g for _, g in trace) > 1e-8
+
+
 # ---- what the Python methods hand to the ABI ------------------------------------------------------------------------------
 def test_context_mfclean_host_form(rig):  # noqa: F811
     ctx, rec, run = rig
