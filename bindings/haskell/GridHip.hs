@@ -46,6 +46,7 @@ module GridHip
   , Weighting(..), WeightMode(..), weightsIO, imagerCreateWeightedIO, imagerCreateAwWeightedIO, imagerDestroyIO
   , imagerWeightStatsIO
   , GainSolve(..), gaincalIO, applyGainsIO, imagerSelfcalIO
+  , ddcalIO, ddSubtractIO, imagerPeelIO
   , FlagOptions(..), flagResidualsIO
   , dftPredictIO, componentsFromImageIO
   , findSourcesIO
@@ -412,6 +413,24 @@ foreign import ccall unsafe "gridhip_apply_gains_dev"
 -- int gridhip_imager_selfcal_dev(imager, model, vis, A, T, a1, a2, slot, wt, mode, refant, warm, niter, tol, gains, vis_cal, wt_cal, stats)
 foreign import ccall unsafe "gridhip_imager_selfcal_dev"
   c_imager_selfcal_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_ddcal(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+foreign import ccall unsafe "gridhip_ddcal"
+  c_ddcal :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_ddcal_dev(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+foreign import ccall unsafe "gridhip_ddcal_dev"
+  c_ddcal_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int64_t gridhip_ddcal_lds_antennas(D)
+foreign import ccall unsafe "gridhip_ddcal_lds_antennas"
+  c_ddcal_lds_antennas :: Int64 -> IO Int64
+-- int gridhip_dd_subtract(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out)
+foreign import ccall unsafe "gridhip_dd_subtract"
+  c_dd_subtract :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_dd_subtract_dev(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out)
+foreign import ccall unsafe "gridhip_dd_subtract_dev"
+  c_dd_subtract_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_imager_peel_dev(imager, model, vis, A, T, D, a1, a2, slot, wt, mode, refant, warm, niter, tol, model_vis, gains, vis_cal, wt_cal, stats)
+foreign import ccall unsafe "gridhip_imager_peel_dev"
+  c_imager_peel_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_flag_residuals(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats, stats)
 foreign import ccall unsafe "gridhip_flag_residuals"
   c_flag_residuals :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
@@ -1420,6 +1439,76 @@ imagerSelfcalIO (ImagerH h@(GridHip c) p n n') solve nant nslots ant1 ant2 slot 
                   map realToFrac <$> peekArray 8 pst
   return (A.fromForeignPtrs (A.Z A.:. nslots A.:. nant) (castForeignPtr g), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out),
           A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Direction-dependent calibration (include/gridhip.h, "direction-dependent calibration"): D gain sets per antenna at
+-- once, the subtraction of corrupted directions, and the peel step of an imager.
+
+-- | ddcalIO h solve nant nslots ant1 ant2 slot wt vis models: the [D][nslots][nant] gains of
+-- vis ~ sum_d g_dp models_d conj(g_dq), models [D][n], starting from 1, and the 8 stats - the host form, synchronous
+ddcalIO :: GridHip -> GainSolve -> Int -> Int -> A.Vector Antenna -> A.Vector Antenna -> Maybe (A.Vector Antenna)
+        -> Maybe (A.Vector F) -> A.Vector Visibility -> A.Matrix Visibility -> IO (A.Array A.DIM3 Visibility, [F])
+ddcalIO h@(GridHip c) solve nant nslots ant1 ant2 slot wt vis models = do
+  let A.Z A.:. n = A.arrayShape vis
+      A.Z A.:. nd A.:. _ = A.arrayShape models
+      (mode, ref, niter, tol) = solveCodes solve
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s k) slot
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+  out <- mallocForeignPtrArray (2 * nd * nslots * nant) :: IO (ForeignPtr CDouble)
+  st <- withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 -> withSlot $ \sl -> withWt $ \ps -> withCplx vis $ \vs ->
+          withCplx models $ \ms -> withForeignPtr out $ \po -> allocaArray 8 $ \pst -> do
+            c_ddcal c (fi n) (fi nant) (fi nslots) (fi nd) a1 a2 sl vs ms ps mode ref 0 niter tol po pst >>= check h
+            map realToFrac <$> peekArray 8 pst
+  return (A.fromForeignPtrs (A.Z A.:. nd A.:. nslots A.:. nant) (castForeignPtr out), st)
+
+-- | ddSubtractIO h gains models directions ant1 ant2 slot vis: vis minus the corrupted models of the directions
+-- (Nothing: all of them); vis Nothing: plus them, the corrupted model itself - the host form, synchronous
+ddSubtractIO :: GridHip -> A.Array A.DIM3 Visibility -> A.Matrix Visibility -> Maybe [Int] -> A.Vector Antenna
+             -> A.Vector Antenna -> Maybe (A.Vector Antenna) -> Maybe (A.Vector Visibility) -> IO (A.Vector Visibility)
+ddSubtractIO h@(GridHip c) gains models directions ant1 ant2 slot vis = do
+  let A.Z A.:. nd A.:. nslots A.:. nant = A.arrayShape gains
+      A.Z A.:. _ A.:. n = A.arrayShape models
+      dirs = maybe (2 ^ nd - 1) (sum . map (2 ^)) directions :: Int
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s k) slot
+      withVis k = maybe (k nullPtr) (\s -> withCplx s k) vis
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 -> withSlot $ \sl -> withCplx gains $ \g -> withCplx models $ \ms ->
+    withVis $ \vs -> withForeignPtr out $ \po ->
+      c_dd_subtract c (fi n) (fi nant) (fi nslots) (fi nd) a1 a2 sl g ms (fi dirs) vs po >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out))
+
+-- | imagerPeelIO im solve nant nslots ant1 ant2 slot wt model vis models: one peel step (gridhip_imager_peel_dev:
+-- predict into row 0 of models, the direction-dependent solve, the subtraction of the directions 1 .. D - 1 and the
+-- correction toward direction 0 as one chain on the device) -> (gains, the corrected visibilities, their weights, the
+-- 8 stats)
+imagerPeelIO :: ImagerH -> GainSolve -> Int -> Int -> A.Vector Antenna -> A.Vector Antenna
+             -> Maybe (A.Vector Antenna) -> Maybe (A.Vector F) -> A.Matrix F -> A.Vector Visibility
+             -> A.Matrix Visibility -> IO (A.Array A.DIM3 Visibility, A.Vector Visibility, A.Vector F, [F])
+imagerPeelIO (ImagerH h@(GridHip c) p n n') solve nant nslots ant1 ant2 slot wt model vis models = do
+  let (mode, ref, niter, tol) = solveCodes solve
+      A.Z A.:. nd A.:. _ = A.arrayShape models
+      cells = nd * nslots * nant
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s $ \sp -> withDev h sp (8 * n) k) slot
+  g <- mallocForeignPtrArray (2 * cells) :: IO (ForeignPtr CDouble)
+  out <- mallocForeignPtrArray (2 * n) :: IO (ForeignPtr CDouble)
+  wout <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
+  st <- withI64 ant1 $ \a1 -> withDev h a1 (8 * n) $ \d1 -> withI64 ant2 $ \a2 -> withDev h a2 (8 * n) $ \d2 ->
+          withSlot $ \ds -> withDevWeights h n wt $ \dw -> withF model $ \mp -> withDev h mp (8 * n' * n') $ \dm ->
+            withCplx vis $ \vs -> withDev h vs (16 * n) $ \dv -> withCplx models $ \ms ->
+              withDev h ms (16 * nd * n) $ \dms -> withForeignPtr g $ \pg -> withDev h pg (16 * cells) $ \dg ->
+                withForeignPtr wout $ \pw -> withDev h pw (8 * n) $ \dwo ->
+                  withForeignPtr out $ \po -> allocaArray 8 $ \pst -> withDev h pst 64 $ \dst -> do
+                    -- (the corrected visibilities in place, in the device copy of vis)
+                    c_imager_peel_dev p dm dv (fi nant) (fi nslots) (fi nd) d1 d2 ds dw mode ref 0 niter tol dms dg dv dwo
+                      dst >>= check h
+                    c_memcpy_d2h c (castPtr pg) (castPtr dg) (fi (16 * cells)) >>= check h
+                    c_memcpy_d2h c (castPtr po) (castPtr dv) (fi (16 * n)) >>= check h
+                    c_memcpy_d2h c (castPtr pw) (castPtr dwo) (fi (8 * n)) >>= check h
+                    c_memcpy_d2h c (castPtr pst) (castPtr dst) 64 >>= check h
+                    c_synchronize c >>= check h
+                    map realToFrac <$> peekArray 8 pst
+  return (A.fromForeignPtrs (A.Z A.:. nd A.:. nslots A.:. nant) (castForeignPtr g),
+          A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout), st)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- Residual flagging (include/gridhip.h, "residual flagging"): robust per-group clipping of |vis - model|.

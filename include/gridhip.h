@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 250 /* 0.2.5 */
+#define GRIDHIP_VERSION 260 /* 0.2.6 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1109,6 +1109,103 @@ int gridhip_imager_selfcal_dev(gridhip_imager *imager, const double *model, cons
                                const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
                                int64_t refant, int warm, int64_t niter, double tol, double *gains, double *vis_cal,
                                double *wt_cal, double *stats);
+
+/* ---- direction-dependent calibration: D gain sets per antenna at once, the subtraction of directions, a peel step ----------
+ * The reference has no calibration: the semantics are defined here, on top of "gain calibration" above.  The sky is split
+ * into D directions, 1 <= D <= 8, each with its own model visibilities and its own gains: model_vis is [D][n] complex,
+ * contiguous (row d: the model of direction d), gains is [D][T][A] complex, and the measurement equation is
+ *     V_k ~ sum_d g[d,t_k,p_k] M[d,k] conj(g[d,t_k,q_k])
+ * n, A, T, a1, a2, slot, vis, wt, mode, refant, warm, niter, tol and stats are gridhip_gaincal's.  The classes FLAGGED,
+ * DROPPED and AUTO are exactly those of gridhip_gaincal (a flagged visibility contributes exactly nothing even when V_k
+ * or any M[d,k] is NaN or Inf), and so are the start (g = 1 everywhere, or the caller's gains when warm != 0) and the stop
+ * test on the device.  The solver is the multi-direction StEFCal (the "direction solve" of Smirnov & Tasse 2015, as in
+ * DP3): iteration i = 0, 1, ... with the current g, for every (t, a), over the used k with t_k = t:
+ *     for each k with p_k = a:  z_d = M[d,k] conj(g[d,t,q_k]),        y = V_k
+ *     for each k with q_k = a:  z_d = conj(M[d,k]) conj(g[d,t,p_k]),  y = conj(V_k)
+ *     H[d,e] = sum s_k conj(z_d) z_e   Hermitian; the upper triangle is kept: D real diagonals, D (D - 1) / 2 complex entries
+ *     b[d]   = sum s_k conj(z_d) y
+ *     g'[.,t,a] solves H g' = b by LDL^H without pivoting, in direction order: H = L diag(d_j) L^H, L unit lower
+ *               triangular, d_j = H[j,j] - sum_{k<j} |L[j,k]|^2 d_k.
+ *     SOLVED    (t, a) is solved in this iteration iff every pivot d_j > 1e-12 * H[j,j], the product as fp64 computes it
+ *               (a NaN fails the test).  Otherwise ALL D gains of (t, a) keep their bits and none of the next rules
+ *               touches them (UNSOLVED in this iteration, as in gridhip_gaincal): a direction without a model on the
+ *               baselines of an antenna, two equal directions, or fewer independent visibilities than directions.
+ *     mode 1 (phase only): each g'[d] <- g'[d] / |g'[d]| where |g'[d]| > 0, else g[d] - every direction separately
+ *     on odd i: g' <- (g' + g) / 2
+ *     rel = sqrt(sum |g' - g|^2 / sum |g'|^2) over all (d, t, a);  then g <- g';  stop when tol > 0 and rel <= tol
+ *     after the loop (t, a) is UNSOLVED when it was solved in no iteration: its D gains are exactly 1 + 0i (or the warm
+ *               values), and it is counted once.  If refant >= 0 the rotation of gridhip_gaincal is done per direction
+ *               and per interval: every gain g[d,t,.] of a solved (t, a) is multiplied by conj(g[d,t,refant]) /
+ *               |g[d,t,refant]| and g[d,t,refant] becomes real and non-negative; where (t, refant) is unsolved, or
+ *               g[d,t,refant] is zero or not finite, that direction of that interval is left unrotated.
+ *     stats     8 doubles in gridhip_gaincal's layout; chi^2 = sum s_k |V_k - sum_d g[d,t,p] M[d,k] conj(g[d,t,q])|^2 over
+ *               the used k, at the final gains and at g = 1; "unsolved" counts the (t, a) that were never solved.
+ * With D = 1 the iteration is gridhip_gaincal's formula, g' = sum X g_q / sum Y |g_q|^2, up to the order of the products.
+ * Products: s_k V_k is formed once per solve; per iteration z_d, s_k z_d, conj(z_d) (s_k z_e) and conj(z_d) (s_k y), every
+ * product rounded (no fused multiply-add).
+ * All arguments are checked before anything is touched.  GRIDHIP_EINVAL: every refusal of gridhip_gaincal (with gains and
+ * model_vis at their larger sizes in the overlap test), and D outside 1..8.  D * A * T above 2^21 is
+ * GRIDHIP_EUNSUPPORTED.  n = 0 is valid.
+ * gridhip_ddcal is synchronous and stages host arrays through the context's pool.  gridhip_ddcal_dev takes device
+ * pointers and enqueues kernels only on the context's stream - no memset node, no copy node; it allocates nothing after
+ * the first call of a shape (the scratch - 32 B per visibility, (D^2 + 2 D) * 8 + 4 B per (t, a) - comes from the
+ * context's pool), never synchronises and reads nothing back: niter iterations are enqueued unconditionally and a launch
+ * that finds the state stopped returns at its first instruction, so a solve can be captured into a graph.
+ * A solve is: one pass that leaves s V (16 B), s (8 B) and the packed 8-byte key per visibility; per iteration a kernel,
+ * one instantiation per D, that streams those 32 B and the D model values (48 B per visibility at D = 1, where gaincal
+ * streams 32 B) - a work-group takes a contiguous range of whole chunks of 4096 visibilities, keeps the gains (2 D doubles)
+ * and the sums (D^2 + 2 D doubles) of one interval in LDS, (D^2 + 4 D) * 8 bytes per antenna, adds with LDS fp64 atomics
+ * and flushes to a global [T][A][D^2 + 2 D] table when the interval changes - and a one-work-group kernel with one thread
+ * per (t, a) that does the LDL^H, the mode, the averaging, rel and the stop test and zeroes the table; then the rotation,
+ * and one more pass for chi^2.
+ * LDS BUDGET.  The LDS path serves A <= gridhip_ddcal_lds_antennas(D) = floor(131072 / ((D^2 + 4 D) * 8)): 3276, 1365,
+ * 780, 512, 364, 273, 212, 170 for D = 1 .. 8; more antennas add to the global table directly.  The budget is 128 KiB of
+ * the 160 KiB a gfx950 CU has: a table above 80 KiB leaves room for one work-group per CU anyway, so the budget is set by
+ * what that one work-group still needs beside it (nothing but a word), rounded down to the power of two that admits
+ * A = 512 at D = 4; the kernel then runs as ONE work-group of 1024 threads per CU, two of 512 from 40 KiB, four of 256
+ * below, so that a CU holds 1024 threads whatever the table takes.  gridhip_ddcal_lds_antennas is a pure host function;
+ * it returns 0 for D outside 1..8.
+ * DETERMINISM.  The sums over the visibilities meet in fp64 atomics: gains are reproducible to the order of those sums
+ * (1e-10 of the largest |g| at a few thousand visibilities per antenna, for an H whose pivots are far from the threshold)
+ * - NOT bit for bit.  Given the gains, rel, chi^2 and the counts are added in a fixed order. */
+int gridhip_ddcal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+                  const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                  int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats);
+int gridhip_ddcal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+                      const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                      int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats);
+int64_t gridhip_ddcal_lds_antennas(int64_t D);
+/* SUBTRACT takes gains [D][T][A], model_vis [D][n], a1, a2, slot, a set of directions dirs (bit d: direction d; a 64-bit
+ * mask passed as int64_t) and vis_in:
+ *     vis_out = vis_in - sum_{d in dirs, ascending} g[d,t,p] M[d,k] conj(g[d,t,q])
+ * the terms subtracted one after the other, each (g_p M) conj(g_q) with every product rounded (no fused multiply-add).
+ * vis_in == NULL means zeros with the sign flipped: vis_out = + the same sum, started from +0 - the corrupted model itself,
+ * the counterpart of gridhip_apply_gains(inverse = 0).  A visibility whose p, q or t is out of range gets vis_out = vis_in
+ * (or 0); autocorrelations and flagged visibilities are treated like any other.  In place (vis_out == vis_in) is allowed;
+ * any other overlap of vis_out with an input is refused.  GRIDHIP_EINVAL: a NULL context; n < 0; A < 2; T < 1; D outside
+ * 1..8; slot == NULL with T != 1; a NULL a1, a2, model_vis or vis_out with n > 0; a NULL gains; a bit of dirs at or above
+ * D (a negative dirs has bit 63).  D * A * T above 2^21 is GRIDHIP_EUNSUPPORTED.  dirs == 0 copies.  Correction TOWARD a
+ * direction stays gridhip_apply_gains on the contiguous slice gains + d * T * A * 2: there is no other apply call. */
+int gridhip_dd_subtract(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+                        const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs,
+                        const double *vis_in, double *vis_out);
+int gridhip_dd_subtract_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1,
+                            const int64_t *a2, const int64_t *slot, const double *gains, const double *model_vis,
+                            int64_t dirs, const double *vis_in, double *vis_out);
+/* One peel step of an imager of any kind, DEFINED BY THE CALLS IT REPLACES:
+ *     gridhip_imager_predict_dev(imager, model, NULL, model_vis)           -> row 0 of model_vis; rows 1 .. D - 1 are the
+ *                                                                           caller's (gridhip_dft_predict of bright components)
+ *     gridhip_ddcal_dev(vis against the D rows)                            -> gains [D][T][A], stats
+ *     gridhip_dd_subtract_dev(dirs = directions 1 .. D - 1, vis)           -> vis_cal
+ *     gridhip_apply_gains_dev(gains[0], inverse = 1, vis_cal, wt)          -> vis_cal, wt_cal (wt_cal may be NULL)
+ * n is the imager's; everything is on the device, nothing is copied, the call is asynchronous and can be captured after
+ * a first call.  vis_cal may be vis and wt_cal may be wt; row 0 of model_vis is written and may overlap nothing else.
+ * vis_cal goes straight into cycle or deconvolve.  With D = 1 this is gridhip_imager_selfcal_dev.  A NULL imager or model
+ * is GRIDHIP_EINVAL; the other rules are those of the calls. */
+int gridhip_imager_peel_dev(gridhip_imager *imager, const double *model, const double *vis, int64_t A, int64_t T, int64_t D,
+                            const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
+                            int64_t refant, int warm, int64_t niter, double tol, double *model_vis, double *gains,
+                            double *vis_cal, double *wt_cal, double *stats);
 
 /* ---- residual flagging: robust per-group clipping of visibility residuals, on the device -----------------------------------
  * The reference has no flagging: the semantics are defined here.  Every other step treats a visibility whose weight is not

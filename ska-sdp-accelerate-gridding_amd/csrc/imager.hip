@@ -573,6 +573,32 @@ int gridhip_imager_selfcal_dev(gridhip_imager *im, const double *model, const do
                        stats, vis_cal, wt_cal);
 }
 
+// predict -> ddcal -> dd_subtract(directions 1 .. D - 1) -> apply_gains(gains[0], inverse = 1) as one enqueued chain
+// (ddcal.hip): the prediction goes to row 0 of the caller's model_vis, and the stream is corrected in place in vis_cal
+int gridhip_imager_peel_dev(gridhip_imager *im, const double *model, const double *vis, int64_t A, int64_t T, int64_t D,
+                            const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
+                            int64_t refant, int warm, int64_t niter, double tol, double *model_vis, double *gains,
+                            double *vis_cal, double *wt_cal, double *stats)
+{
+    if (!im) return GRIDHIP_EINVAL;
+    gridhip_ctx *ctx = im->ctx;
+    const int64_t n = im->n;
+    if (!model) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    GH_CHECK(ddcal_check(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
+    const int64_t others = ((int64_t)1 << D) - 2;  // every direction but 0
+    GH_CHECK(dd_subtract_check(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, others, vis, vis_cal));
+    GH_CHECK(apply_gains_check(ctx, n, A, T, a1, a2, slot, gains, 1, vis, wt, vis_cal, wt_cal));
+    GH_CHECK(peel_check(ctx, n, D * A * T, model_vis, gains, a1, a2, slot, vis, wt, wt_cal, stats));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (n > 0) {
+        GH_CHECK(gather(im, model));
+        GH_CHECK(launch_residual(ctx, n, im->pred, nullptr, (double2 *)model_vis));
+    }
+    GH_CHECK(ddcal_run(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats));
+    GH_CHECK(dd_subtract_run(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, others, vis, vis_cal));
+    return apply_gains_run(ctx, n, A, T, a1, a2, slot, gains, 1, vis_cal, wt, vis_cal, wt_cal);
+}
+
 // predict -> flag_residuals as one enqueued chain (flag.hip): the front pass reads the prediction where the gather left it
 int gridhip_imager_flag_dev(gridhip_imager *im, const double *model, const double *vis, int64_t G, const int64_t *group,
                             const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter,

@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, dft.hip, flag.hip, sources.hip).
+// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip, sources.hip).
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -38,6 +38,7 @@ struct ImagingState {
     bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
     bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
     bool flag_lds_raised = false;     // and flag_hist_kernel's LDS path its 64 KB (flag.hip)
+    unsigned int ddcal_lds_raised = 0;  // and ddcal_iter_kernel<D> its DD_LDS_BUDGET: bit D (ddcal.hip)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
 };
@@ -455,6 +456,32 @@ int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t
 int apply_gains_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
                     double *vis_out, double *wt_out);
+
+// ---- direction-dependent calibration (ddcal.hip) -----------------------------------------------------------------------------
+// the most directions of a solve; the LDS a work-group of the iteration kernel may take for the gains and sums of one
+// interval ((D^2 + 4 D) * 8 bytes per antenna: gridhip_ddcal_lds_antennas, include/gridhip.h)
+constexpr int DD_MAX_D = 8;
+constexpr int64_t DD_LDS_BUDGET = 128 * 1024;
+// gridhip_ddcal's and gridhip_dd_subtract's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED)
+int ddcal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+                const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
+                int64_t niter, double tol, const double *gains);
+int dd_subtract_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+                      const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs, const double *vis_in,
+                      const double *vis_out);
+// what the checks of the calls a peel replaces leave open: row 0 of model_vis is written and may overlap no input and no
+// other output (gains and vis_cal are covered by the two checks above), and wt_cal may overlap none of the D x T x A
+// (cells) gains, where apply_gains_check sees direction 0 alone
+int peel_check(gridhip_ctx *ctx, int64_t n, int64_t cells, const double *model_vis, const double *gains, const int64_t *a1,
+               const int64_t *a2, const int64_t *slot, const double *vis, const double *wt, const double *wt_cal,
+               const double *stats);
+// the _dev forms on checked arguments: kernels only, on ctx->stream; scratch from the context's pool
+int ddcal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+              const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
+              int warm, int64_t niter, double tol, double *gains, double *stats);
+int dd_subtract_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+                    const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs, const double *vis_in,
+                    double *vis_out);
 
 // ---- residual flagging (flag.hip) ------------------------------------------------------------------------------------------
 // the most groups of one call (the bin table is 1 KB per group); the most groups whose bins a work-group of the histogram

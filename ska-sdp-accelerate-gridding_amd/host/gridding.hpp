@@ -18,6 +18,7 @@
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
+//   ddcal, dd_subtract: direction-dependent gains of D directions at once and the subtraction of directions
 //   flag_residuals: robust per-group clipping of visibility residuals (absent from the reference)
 //   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
 //   find_sources: a map as a list of Gaussian components - islands, moments, the beam deconvolved (absent from the reference)
@@ -507,6 +508,47 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_apply_gains(ctx_, n, A, T, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(gains),
                                   inverse ? 1 : 0, cd(vis), data.empty() ? nullptr : data.data(), cd(out),
                                   wt_out ? wt_out->data() : nullptr));
+        return out;
+    }
+
+    // ---- direction-dependent calibration (gridhip_ddcal, gridhip_dd_subtract; include/gridhip.h, "direction-dependent
+    // calibration") ----
+    // (Host forms; the device-pointer forms gridhip_ddcal_dev, gridhip_dd_subtract_dev and the imager's
+    // gridhip_imager_peel_dev and the pure gridhip_ddcal_lds_antennas are the C header's.)
+    // The [D][T][A] gains of vis ~ sum_d g[d, slot, a1] models[d] conj(g[d, slot, a2]), models [D][n] row after row, by the
+    // multi-direction StEFCal.  The other arguments are gaincal's.
+    std::vector<Visibility> ddcal(const std::vector<Visibility> &vis, const std::vector<Visibility> &models, Int D,
+                                  const std::vector<Int> &a1, const std::vector<Int> &a2, Int A,
+                                  const std::vector<Int> &slot = {}, Int T = 1, const std::vector<F> &data = {},
+                                  bool phase_only = false, Int refant = 0, Int niter = 50, F tol = 1e-8,
+                                  GainStats *stats = nullptr, const std::vector<Visibility> *warm = nullptr)
+    {
+        const Int n = (Int)vis.size();
+        if (D < 1 || (Int)models.size() != D * n || (Int)a1.size() != n || (Int)a2.size() != n ||
+            (!slot.empty() && (Int)slot.size() != n) || (!data.empty() && (Int)data.size() != n) || A < 2 || T < 1 ||
+            (warm && (Int)warm->size() != D * A * T))
+            throw Error(GRIDHIP_EINVAL, "ddcal: one value per visibility, D rows of models, A >= 2, T >= 1, gains of D x T x A");
+        std::vector<Visibility> g = warm ? *warm : std::vector<Visibility>((size_t)(D * A * T));
+        F st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_ddcal(ctx_, n, A, T, D, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(vis), cd(models),
+                            data.empty() ? nullptr : data.data(), phase_only ? 1 : 0, refant, warm ? 1 : 0, niter, tol, cd(g),
+                            st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+        return g;
+    }
+    // vis (empty: zero, and the sign flips) minus the corrupted models of the directions in the bit set dirs
+    std::vector<Visibility> dd_subtract(const std::vector<Visibility> &gains, Int D, Int A, Int T,
+                                        const std::vector<Visibility> &models, const std::vector<Int> &a1,
+                                        const std::vector<Int> &a2, const std::vector<Int> &slot, Int dirs,
+                                        const std::vector<Visibility> &vis = {})
+    {
+        const Int n = (Int)a1.size();
+        if (D < 1 || (Int)models.size() != D * n || (Int)a2.size() != n || (!slot.empty() && (Int)slot.size() != n) ||
+            (!vis.empty() && (Int)vis.size() != n) || A < 2 || T < 1 || (Int)gains.size() != D * A * T)
+            throw Error(GRIDHIP_EINVAL, "dd_subtract: one value per visibility, D rows of models, gains of D x T x A");
+        std::vector<Visibility> out((size_t)n);
+        check(gridhip_dd_subtract(ctx_, n, A, T, D, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(gains),
+                                  cd(models), dirs, vis.empty() ? nullptr : cd(vis), cd(out)));
         return out;
     }
 

@@ -26,12 +26,13 @@ from ._lib import GridHipError, LIB_PATH  # noqa: F401
 from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, beam_support, clean_scalars, device,
                        auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
 from ._marshal import gain_stream, result_array, solve_args, stream_array
+from ._marshal import direction_mask, model_rows
 from ._marshal import flag_outputs, flag_scalars, flag_stream
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
 from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import weighting as _weighting
 
-__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups"]
+__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas"]
 
 
 class Context(Handle):
@@ -571,6 +572,43 @@ class Context(Handle):
         self._call(be, "gaincal", n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
         return gains, stats
 
+    def ddcal(self, vis, model_vis, a1, a2, nant, *, slot=None, nslots=1, weights=None, phase_only=False, refant=0,
+              niter=50, tol=1e-8, gains=None):
+        """Direction-dependent gains of `vis` against the D rows of `model_vis` (D, n) by the multi-direction StEFCal
+        (gridhip_ddcal[_dev]; include/gridhip.h, "direction-dependent calibration"): vis ~ sum over d of g[d, slot, a1]
+        model_vis[d] conj(g[d, slot, a2]).  Everything else is Context.gaincal's; an (slot, antenna) whose D x D normal
+        matrix has a pivot at or below 1e-12 of its diagonal keeps all its gains.  gains: a (D, nslots, nant) complex128
+        array in the ABI's form to start from, updated in place, or None.  Returns (gains (D, nslots, nant), stats)."""
+        be = backend(vis)
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, nant, slot, nslots, weights)
+        D, model_vis = model_rows(be, model_vis, n)
+        mode, refant, warm, niter, tol, gains = solve_args(be, phase_only, refant, niter, tol, gains, A, T, vis, D)
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "ddcal", n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+        return gains, stats
+
+    def dd_subtract(self, gains, model_vis, a1, a2, *, slot=None, directions=None, vis=None, out=None):
+        """vis minus the corrupted models of `directions` (an iterable of direction numbers; None: all):
+        vis - sum over d of g[d, slot, a1] model_vis[d] conj(g[d, slot, a2]) with the (D, nslots, nant) gains
+        (gridhip_dd_subtract[_dev]).  vis None: plus that sum - the corrupted model itself.  A visibility whose indices
+        are out of range keeps its value.  out: the array to write (a new one when None); it may be `vis`.  Correcting
+        toward direction d afterwards is Context.apply_gains(gains[d], ...)."""
+        be = backend(model_vis)
+        if not hasattr(gains, "shape") or len(gains.shape) != 3:
+            raise ValueError("gains must be of shape (D, nslots, nant)")
+        D, T, A = (int(v) for v in gains.shape)
+        Dm, model_vis = model_rows(be, model_vis, -1)
+        if Dm != D:
+            raise ValueError(f"gains has {D} directions and model_vis {Dm}")
+        n, A, T, a1, a2, slot, first, _ = gain_stream(be, model_vis[0] if vis is None else vis, a1, a2, A, slot, T, None)
+        if int(model_vis.shape[1]) != n:
+            raise ValueError("model_vis must have one column per visibility")
+        gains = stream_array(be, gains.reshape(-1), be.c128, D * T * A, "gains")
+        out = result_array(be, out, be.c128, (n,), "out", model_vis)
+        self._call(be, "dd_subtract", n, A, T, D, a1, a2, slot, gains, model_vis, direction_mask(directions, D),
+                   None if vis is None else first, out)
+        return out
+
     def apply_gains(self, gains, vis, a1, a2, *, slot=None, inverse=True, weights=None, out=None, weights_out=None):
         """Apply the (nslots, nant) gains to a visibility stream (gridhip_apply_gains[_dev]).  inverse=True corrects data:
         vis / (g[slot, a1] conj(g[slot, a2])) and weights |g[a1]|^2 |g[a2]|^2 times `weights` (None: ones); a visibility
@@ -1106,6 +1144,30 @@ class Imager(_Bound):
                    weights_out, stats)
         return gains, out, weights_out, stats
 
+    def peel(self, model, vis, model_vis, a1, a2, nant, *, slot=None, nslots=1, weights=None, phase_only=False, refant=0,
+             niter=50, tol=1e-8, gains=None, out=None, weights_out=None):
+        """One peel step (gridhip_imager_peel_dev): predict(model) into row 0 of `model_vis` - a contiguous (D, n)
+        complex128 cuda tensor whose rows 1 .. D - 1 hold the caller's models of the bright directions, for instance
+        Context.dft_predict of their components - then Context.ddcal of `vis` against all D rows, Context.dd_subtract of
+        the directions 1 .. D - 1 and Context.apply_gains(gains[0], inverse=True) of the result and the weights, as one
+        asynchronous chain that copies nothing and, after a first call, can be captured into a graph.  The other
+        arguments are selfcal's; gains is (D, nslots, nant).  Returns (gains, vis_cal, wt_cal, stats)."""
+        self._open()
+        be = device()
+        self._ok(model, be.f64, (self.N, self.N), "model")
+        self._ok(vis, be.c128, (self.n,), "vis")
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, nant, slot, nslots, weights)
+        if not (is_torch(model_vis) and len(model_vis.shape) == 2 and be.ok(model_vis, be.c128)):
+            raise ValueError("model_vis must be a contiguous cuda complex128 tensor of shape (D, n): its row 0 is written")
+        D, model_vis = model_rows(be, model_vis, n)
+        mode, refant, warm, niter, tol, gains = solve_args(be, phase_only, refant, niter, tol, gains, A, T, self.device, D)
+        out = result_array(be, out, be.c128, (n,), "out", self.device)
+        weights_out = result_array(be, weights_out, be.f64, (n,), "weights_out", self.device)
+        stats = be.empty(8, be.f64, self.device)
+        self._call(be, "imager_peel", model, vis, A, T, D, a1, a2, slot, wt, mode, refant, warm, niter, tol, model_vis,
+                   gains, out, weights_out, stats)
+        return gains, out, weights_out, stats
+
     def flag(self, model, vis, group=None, G=None, weights=None, nsigma=5.0, amax=0.0, min_count=8, niter=3, out=None):
         """Context.flag_residuals of `vis` against the imager's own prediction of `model` (gridhip_imager_flag_dev):
         predict(model) and the flagging as one asynchronous chain that copies nothing and, after a first call of a
@@ -1181,6 +1243,12 @@ def components(l, m, flux, spectral=None, fwhm=None, pa=None):
     if pa is not None:
         out[:, 8] = be.cv(pa, be.f64).reshape(-1)
     return out
+
+
+def ddcal_lds_antennas(D):
+    """The most antennas whose gains and sums of one interval Context.ddcal's iteration kernel keeps in LDS for D
+    directions (gridhip_ddcal_lds_antennas): more antennas add to global memory directly.  0 for D outside 1..8."""
+    return int(_lib.load().gridhip_ddcal_lds_antennas(int(D)))
 
 
 def flag_groups(a1, a2, slot=None, by="baseline"):

@@ -54,6 +54,8 @@ _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_doubl
 _WEIGHTING = [ci, C.c_double, C.c_double, vp]  # mode, robust, taper_sigma, wt_in
 _GAINCAL = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]
 _APPLY_GAINS = [vp, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+_DDCAL = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]  # gaincal's, D after T
+_DD_SUBTRACT = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp]
 _FLAG_ARGS = [C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]  # nsigma, amax, min_count, niter, then the four outputs
 _FLAG = [vp, i64, i64, vp, vp, vp, vp, *_FLAG_ARGS]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
@@ -186,6 +188,13 @@ SIGNATURES = {
     "gridhip_apply_gains": (ci, _APPLY_GAINS),
     "gridhip_apply_gains_dev": (ci, _APPLY_GAINS),
     "gridhip_imager_selfcal_dev": (ci, [vp, vp, vp, i64, i64, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp, vp, vp]),
+    "gridhip_ddcal": (ci, _DDCAL),
+    "gridhip_ddcal_dev": (ci, _DDCAL),
+    "gridhip_ddcal_lds_antennas": (i64, [i64]),
+    "gridhip_dd_subtract": (ci, _DD_SUBTRACT),
+    "gridhip_dd_subtract_dev": (ci, _DD_SUBTRACT),
+    "gridhip_imager_peel_dev": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp, vp, vp,
+                                     vp]),
     "gridhip_flag_residuals": (ci, _FLAG),
     "gridhip_flag_residuals_dev": (ci, _FLAG),
     "gridhip_imager_flag_dev": (ci, [vp, vp, vp, i64, vp, vp, *_FLAG_ARGS]),

@@ -379,9 +379,10 @@ def gain_stream(be, vis, a1, a2, nant, slot, nslots, weights):
     return n, A, T, a1, a2, slot, vis, stream_array(be, weights, be.f64, n, "weights")
 
 
-def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like):
+def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like, D=None):
     """mode, refant, warm, niter, tol, gains as the solving entry points take them: refant None is -1 (no rotation); gains
-    None starts from 1 in a new [T][A] array, a given one - in the ABI's form: it is updated in place - is the warm start."""
+    None starts from 1 in a new [T][A] array ([D][T][A] with D, the direction-dependent solves), a given one - in the
+    ABI's form: it is updated in place - is the warm start."""
     import math
     refant = -1 if refant is None else int(refant)
     niter, tol = int(niter), float(tol)
@@ -390,8 +391,39 @@ def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like):
     if niter < 0 or not (tol >= 0.0 and math.isfinite(tol)):
         raise ValueError("niter must be >= 0 and tol finite and >= 0")
     warm = int(gains is not None)
-    gains = result_array(be, gains, be.c128, (T, A), "gains", like)
+    gains = result_array(be, gains, be.c128, (T, A) if D is None else (D, T, A), "gains", like)
     return int(bool(phase_only)), refant, warm, niter, tol, gains
+
+
+DD_MAX_DIRECTIONS = 8  # the most directions of gridhip_ddcal
+
+
+def model_rows(be, x, n):
+    """D, model_vis as gridhip_ddcal and gridhip_dd_subtract take the models of the directions: a (D, n) array, or (n,)
+    for one direction, converted to contiguous complex128 where it must be"""
+    if x is None or (be is not backend(x) and be is not HOST):
+        raise ValueError(f"model_vis must be a {be.array}")
+    if be is HOST:
+        x = np.asarray(x)
+    shape = tuple(int(v) for v in x.shape)
+    shape = (1,) + shape if len(shape) == 1 else shape
+    if len(shape) != 2 or (n >= 0 and shape[1] != n) or not 1 <= shape[0] <= DD_MAX_DIRECTIONS:
+        raise ValueError(f"model_vis must be of shape (D, n) with D in 1..{DD_MAX_DIRECTIONS} and one column per "
+                         f"visibility, not {tuple(x.shape)}")
+    return shape[0], be.cv(x, be.c128)
+
+
+def direction_mask(directions, D):
+    """dirs as gridhip_dd_subtract takes a set of directions: None is all D of them"""
+    if directions is None:
+        return (1 << D) - 1
+    mask = 0
+    for d in directions:
+        d = int(d)
+        if not 0 <= d < D:
+            raise ValueError(f"a direction must be in 0..{D - 1}, not {d}")
+        mask |= 1 << d
+    return mask
 
 
 FLAG_MAX_ROUNDS = 16  # the most clipping rounds of gridhip_flag_residuals
