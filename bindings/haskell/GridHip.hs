@@ -461,6 +461,18 @@ foreign import ccall unsafe "gridhip_find_sources_dev"
 -- int gridhip_imager_find_sources_dev(imager, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats)
 foreign import ccall unsafe "gridhip_imager_find_sources_dev"
   c_imager_find_sources_dev :: Ptr Imager -> Ptr CDouble -> Int64 -> CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_phase_shift(ctx, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats)
+foreign import ccall unsafe "gridhip_phase_shift"
+  c_phase_shift :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_phase_shift_dev(ctx, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats)
+foreign import ccall unsafe "gridhip_phase_shift_dev"
+  c_phase_shift_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_average(ctx, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out, wt_out, count_out, stats)
+foreign import ccall unsafe "gridhip_average"
+  c_average :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_average_dev(ctx, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out, wt_out, count_out, stats)
+foreign import ccall unsafe "gridhip_average_dev"
+  c_average_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 260 /* 0.2.6 */
+#define GRIDHIP_VERSION 270 /* 0.2.7 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1438,6 +1438,98 @@ int gridhip_imager_find_sources_dev(gridhip_imager *imager, const double *image,
                                     double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
                                     int64_t min_cells, const double *beam, int correct, int64_t max_c, double *comps,
                                     double *info, int64_t *count, double *stats);
+
+/* ---- phase shift and averaging: a stream rotated to another phase centre, groups of samples collapsed into one each ----------
+ * The reference has neither: the semantics are defined here.  Every other step runs on the stream at its recorded
+ * resolution and about its recorded phase centre; these are the two data-reduction steps a pipeline puts in front of them.
+ * PHASE SHIFT.  gridhip_phase_shift rotates n visibilities and their (u, v, w) - wavelengths, un-mirrored, uv_stride as
+ *     everywhere else, w == NULL meaning w = 0 - to another phase centre.  R is 9 HOST doubles in both forms, row-major, read
+ *     at the call: the rotation from the old (u, v, w) frame to the new one.  Its third row is the new centre (l0, m0, n0) in
+ *     the old frame.
+ *     PHASE RULE       vis_out = vis_in * exp(+2 pi i p),  p = u l0 + v m0 + w (n0 - 1),
+ *                      n0 - 1 = -r2 / (1 + sqrt(1 - r2)), r2 = l0^2 + m0^2 (formed once per call; the subtraction form
+ *                      cancels).  The sign, the reduction to turns r = p - rint(p) (exact) and fp64 are exactly those of
+ *                      gridhip_dft_predict, with the opposite sign of the exponent: a point of flux S at (l0, m0) therefore
+ *                      becomes the constant S.  The product is (re c - im s, re s + im c) with c, s the cosine and sine of
+ *                      2 pi r, every product rounded, no fused multiply-add.  With |p| <= 1e4 turns the error of a
+ *                      visibility is below 1e-10 |vis|.
+ *     COORDINATE RULE  with the coordinate outputs given (all three or none)
+ *                          u' = (R00 u + R01 v) + R02 w,  v' = (R10 u + R11 v) + R12 w,  w' = (R20 u + R21 v) + R22 w:
+ *                      every product is rounded, the sums go left to right, contraction is off - numpy reproduces them to
+ *                      the bit.  They are written at out_stride.
+ *     ALIASING         vis_out == vis_in is allowed, and so are u_out == u, v_out == v and w_out == w at out_stride ==
+ *                      uv_stride (element k is read before it is written, by the same lane).  Any other overlap of an
+ *                      output with an input or with another output is GRIDHIP_EINVAL; the columns of one interleaved (n, 3)
+ *                      array do not overlap each other.
+ *     NOT FINITE       a visibility with a non-finite u, v or w passes vis_in through unchanged and is counted; its
+ *                      coordinate outputs are what the coordinate rule gives (not finite).
+ *     stats            optional, 4 doubles { visibilities shifted, visibilities with non-finite coordinates, 0, 0 }.
+ *     Refused before anything is touched, GRIDHIP_EINVAL: a NULL context or R; R not finite; R22 <= 0 (a centre behind the
+ *     sky); |R R^T - I| above 1e-9 in any entry; n < 0; a NULL u, v, vis_in or vis_out with n > 0; a stride < 1; one or two of
+ *     the three coordinate outputs.  n of 2^31 - 256 or more is GRIDHIP_EUNSUPPORTED.  n = 0 is valid.
+ * AVERAGING.  gridhip_average collapses the n samples into G, one per group: group is n int64 as gridhip_flag_residuals
+ *     takes it (NULL with G == 1: one group); x (n doubles or NULL: 0) is any further per-sample column - gridhip_dft_predict's
+ *     fractional frequency, a time; wt the data weights s_k (n doubles, or NULL for all ones).
+ *     CLASSES.  Each visibility falls into the FIRST class that applies:
+ *         FLAGGED       s_k is not > 0 (zero, negative, NaN) - gridhip_weights' rule
+ *         LEFT OUT      g_k outside [0, G)
+ *         NOT FINITE    any of s re, s im, s u, s v, s w, s x is not finite: each is one rounded product, judged on the
+ *                       value fp64 computes (1e300 with the weight 1e10 counts)
+ *         PARTICIPANT   everything else
+ *     SUMS.  They are EXACT INTEGER SUMS, so that the result does not depend on the arrival order.  For each group: n_g is
+ *         the number of participants and L = ceil(log2 n_g) as an integer (0 for n_g = 1).  For each class of columns -
+ *         vis: re and im; uvw: u, v and w; x; the weight - b is the largest biased exponent field (0 .. 2046) of the
+ *         class's weighted values over the group's participants, and s = 1084 - L - b.  Every weighted value y enters as
+ *             q = (int64) rint(ldexp(y, s)),   so |q| <= 2^(62 - L)
+ *         and the group's sum Q cannot overflow int64.  The column's sum is ldexp((double) Q, -s): one rounding in the
+ *         conversion (and the rounding of ldexp where that result is subnormal).
+ *         ERROR BOUND against the exact sum:  |sum - exact| <= n_g 2^(L-62) M + 2^-53 |sum|,  M = max(max|y|, 2^-1022)
+ *         with max|y| over the class - at most n_g roundings of half the quantum 2^-s, which is <= 2^(L-61) max|y| while the
+ *         largest value is normal and stays 2^(L-1084) below that; and the conversion, half an ulp of the sum.  For sums of
+ *         mixed sign in the normal range this is within (n_g 2^(L-62) + 2^-52) max|y|.  A class of subnormals with n_g <=
+ *         1024 is summed exactly.
+ *     OUTPUTS per group: wt_out = W, the weight sum; vis_out = sum / W, and u_out, v_out, w_out (at out_stride) and x_out
+ *         the same way, each one rounded division; count_out (int64, may be NULL) = n_g.  A group without participants
+ *         gives vis = u = v = w = x = 0, wt = +0.0 and count = 0: a sample every other step already ignores.  x_out may be
+ *         NULL when x is.
+ *     stats  optional, 8 doubles { groups with a participant, participants, flagged, left out, not finite, largest n_g,
+ *         non-finite coordinates seen by the fused shift, 0 }.
+ *     FUSED SHIFT.  R != NULL is DEFINED BY THE CALLS IT REPLACES,
+ *             gridhip_phase_shift_dev(R: vis, u, v, w -> vis', u', v', w')
+ *             gridhip_average_dev(NULL: vis', u', v', w')
+ *         with the same bits, and no shifted stream is written.  The shift sees all n visibilities: its count of non-finite
+ *         coordinates does not depend on the classes.
+ *     Refused before anything is touched, GRIDHIP_EINVAL: a NULL context; n < 0; G < 1; with n > 0 a NULL group unless G == 1 and a NULL
+ *     u, v or vis; a stride < 1; a NULL u_out, v_out, w_out, vis_out or wt_out; x without x_out; R as above; any
+ *     output overlapping an input or another output.  n of 2^31 - 256 or more and G above 2^31 - 256 are
+ *     GRIDHIP_EUNSUPPORTED (the counts are 32-bit).  n = 0 is valid: every group is empty.
+ * The host forms are synchronous and stage through the context's pool.  The _dev forms take device pointers (R excepted) and
+ * enqueue kernels only on the context's stream - no memset node, no copy node (the tables are zeroed by a kernel); they
+ * allocate nothing after the first call of a shape (the scratch - 76 B per group: a 32-bit count, four 32-bit exponents,
+ * seven 64-bit sums - comes from the context's pool), never synchronise and read nothing back, so they can be captured
+ * into a graph.  An averaging is a fixed number of launches whatever the data hold, 5 (4 without stats): a kernel that
+ * zeroes the tables; pass A over the stream - the classes, n_g by 32-bit atomicAdd and b by 32-bit atomicMax; pass B over
+ * the stream again - the 64-bit integer atomicAdd of every q; a pass over the groups that finalises; the stats.  The fused
+ * shift is evaluated in both passes.  The tables are column-major, so a stream whose neighbours lie in neighbouring groups
+ * adds to contiguous memory; where neighbours share a group, the lanes of a wave that form a run of one group are summed by
+ * shuffles first and one lane goes to memory.
+ * DETERMINISM.  integer atomics only: no floating-point atomic and no sum of doubles.  Integer adds commute, so neither the
+ * arrival order nor the pre-aggregation changes a bit: the same bits for the host and _dev forms, for two runs, for any
+ * permutation of the stream, and for a numpy restatement with Python's exact integers. */
+int gridhip_phase_shift(gridhip_ctx *ctx, int64_t n, const double *R, const double *u, const double *v, const double *w,
+                        int64_t uv_stride, const double *vis_in, double *vis_out, double *u_out, double *v_out, double *w_out,
+                        int64_t out_stride, double *stats);
+int gridhip_phase_shift_dev(gridhip_ctx *ctx, int64_t n, const double *R, const double *u, const double *v, const double *w,
+                            int64_t uv_stride, const double *vis_in, double *vis_out, double *u_out, double *v_out,
+                            double *w_out, int64_t out_stride, double *stats);
+int gridhip_average(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *R, const double *u,
+                    const double *v, const double *w, int64_t uv_stride, const double *x, const double *vis, const double *wt,
+                    double *u_out, double *v_out, double *w_out, int64_t out_stride, double *x_out, double *vis_out,
+                    double *wt_out, int64_t *count_out, double *stats);
+int gridhip_average_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *R, const double *u,
+                        const double *v, const double *w, int64_t uv_stride, const double *x, const double *vis,
+                        const double *wt, double *u_out, double *v_out, double *w_out, int64_t out_stride, double *x_out,
+                        double *vis_out, double *wt_out, int64_t *count_out, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -22,6 +22,7 @@
 //   flag_residuals: robust per-group clipping of visibility residuals (absent from the reference)
 //   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
 //   find_sources: a map as a list of Gaussian components - islands, moments, the beam deconvolved (absent from the reference)
+//   (phase shift and averaging, gridhip_phase_shift / gridhip_average, have no mirror here: the C ABI and the Python binding carry them)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
 //

@@ -30,9 +30,11 @@ from ._marshal import direction_mask, model_rows
 from ._marshal import flag_outputs, flag_scalars, flag_stream
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
 from ._marshal import automask_args, mask_in_place, source_args
+from ._marshal import group_ids, rotation as _rotation
 from ._marshal import weighting as _weighting
 
-__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas"]
+__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas",
+           "rotation_to", "rotation_radec", "average_groups"]
 
 
 class Context(Handle):
@@ -674,6 +676,61 @@ class Context(Handle):
         self._call(be, "dft_predict", C_, comps, count, T, n, u, v, w, st, x, sub, out, st4)
         return (out, st4) if stats else out
 
+    def phase_shift(self, uvw, vis, R, coords=True, out=None, stats=False):
+        """`vis` and its baselines rotated to another phase centre (gridhip_phase_shift[_dev]; include/gridhip.h, "phase
+        shift and averaging"): vis * exp(+2 pi i (u l0 + v m0 + w (n0 - 1))) with (l0, m0, n0) the third row of the 3 x 3
+        rotation R (rotation_to, rotation_radec; host values whichever back end), and (u', v', w') = R (u, v, w).  uvw
+        (wavelengths, not mirrored): a (u, v, w) tuple - w may be None: 0 - or an (n, 3) array.  out: the array to write,
+        which may be `vis` itself; a new one when None.  Returns (out, uvw_out) - uvw_out a new (n, 3) array - or with
+        coords=False out alone; with stats=True the 4 values [shifted, visibilities with non-finite coordinates (they
+        pass through unchanged), 0, 0] are appended.  numpy in gives numpy out; torch cuda tensors take the device form on
+        torch's stream and stay on the device."""
+        be = backend(vis)
+        u, v, w, st = baselines(be, uvw, 3)
+        n = int(u.shape[0])
+        vis = stream_array(be, vis, be.c128, n, "vis")
+        Rp, keep = _rotation(R)
+        if Rp is None:
+            raise ValueError("R must be a 3 x 3 rotation")
+        out = result_array(be, out, be.c128, (n,), "out", vis)
+        new = be.empty((n, 3), be.f64, vis) if coords else None
+        cols = (new[:, 0], new[:, 1], new[:, 2]) if coords else (None, None, None)
+        st4 = be.empty(4, be.f64, vis) if stats else None
+        self._call(be, "phase_shift", n, Rp, u, v, w, st, vis, out, *cols, 3, st4)
+        res = (out, new) if coords else (out,)
+        res = res + (st4,) if stats else res
+        return res if len(res) > 1 else res[0]
+
+    def average(self, uvw, vis, group, G, weights=None, x=None, R=None, counts=False, stats=False):
+        """The stream collapsed into G weighted samples, one per group (gridhip_average[_dev]; include/gridhip.h, "phase
+        shift and averaging").  uvw as for phase_shift; group: the group of every visibility in [0, G) (a sample whose
+        group is outside is left out), as average_groups or flag_groups return it with G; None: one group.  weights: n data
+        weights (None: ones; a value that is not > 0 flags its sample); x: a further per-sample column averaged the same
+        way (dft_predict's fractional frequency, a time), or None.  R: a rotation as for phase_shift - the stream is
+        shifted first, with the bits of phase_shift followed by average and without writing the shifted stream.
+        Returns (uvw_g (G, 3), vis_g, weights_g, x_g) - x_g None without x - then, with counts=True, the participants of
+        every group (int64) and, with stats=True, the 8 values [groups with a participant, participants, flagged, left
+        out, not finite, largest group, non-finite coordinates seen by the shift, 0].  A group without participants is
+        all zeros with the weight +0.0.  The sums are exact integer sums: the same bits on every run and for any order of
+        the stream.  numpy in gives numpy out; torch cuda tensors take the device form on torch's stream: nothing is read
+        back."""
+        be = backend(vis)
+        u, v, w, st = baselines(be, uvw, 3)
+        n = int(u.shape[0])
+        vis = stream_array(be, vis, be.c128, n, "vis")
+        G, group = group_ids(be, group, G, n)
+        wt = stream_array(be, weights, be.f64, n, "weights")
+        x = stream_array(be, x, be.f64, n, "x")
+        Rp, keep = _rotation(R)
+        uvw_g = be.empty((G, 3), be.f64, vis)
+        vis_g, wt_g = be.empty((G,), be.c128, vis), be.empty((G,), be.f64, vis)
+        x_g = None if x is None else be.empty((G,), be.f64, vis)
+        cnt = be.empty((G,), be.i64, vis) if counts else None
+        st8 = be.empty(8, be.f64, vis) if stats else None
+        self._call(be, "average", n, G, group, Rp, u, v, w, st, x, vis, wt, uvw_g[:, 0], uvw_g[:, 1], uvw_g[:, 2], 3, x_g,
+                   vis_g, wt_g, cnt, st8)
+        return (uvw_g, vis_g, wt_g, x_g) + ((cnt,) if counts else ()) + ((st8,) if stats else ())
+
     def components_from_image(self, theta, lam, model, max_components, out=None):
         """The non-zero cells of a model image as a component list (gridhip_components_from_image[_dev]): model is N x N,
         N = image_size(theta, lam), or (T, N, N) Taylor-term planes as mfclean leaves them; every cell where some term is
@@ -1275,6 +1332,87 @@ def flag_groups(a1, a2, slot=None, by="baseline"):
     cols = {"baseline": (lo, hi), "slot": (slot,), "baseline_slot": (lo, hi, slot)}[by]
     _, group = torch.unique(torch.stack(cols, dim=1), dim=0, sorted=True, return_inverse=True)
     return group.to(torch.int64), int(group.max()) + 1
+
+
+def rotation_to(l0, m0):
+    """The minimal rotation that takes the w-axis to the direction cosines (l0, m0) - what Context.phase_shift and
+    Context.average take as R: a (3, 3) float64 ndarray whose third row is (l0, m0, n0), n0 = sqrt(1 - l0^2 - m0^2), and
+    which turns about the axis perpendicular to the old and the new centre (no field rotation).  Plumbing: numpy only."""
+    import math
+    import numpy as np
+    l0, m0 = float(l0), float(m0)
+    r2 = l0 * l0 + m0 * m0
+    if not r2 < 1.0:
+        raise ValueError("l0^2 + m0^2 must be below 1: the new centre lies in front of the old one")
+    n0 = math.sqrt(1.0 - r2)
+    k = 1.0 / (1.0 + n0)
+    return np.array([[1.0 - k * l0 * l0, -k * l0 * m0, -l0], [-k * l0 * m0, 1.0 - k * m0 * m0, -m0], [l0, m0, n0]])
+
+
+def rotation_radec(ra0, dec0, ra1, dec1):
+    """The rotation from the (u, v, w) frame of the phase centre (ra0, dec0) to that of (ra1, dec1), radians:
+    M(ra1, dec1) M(ra0, dec0)^T, M having the rows e_u = (-sin ra, cos ra, 0), e_v = (-sin dec cos ra, -sin dec sin ra,
+    cos dec), e_w = (cos dec cos ra, cos dec sin ra, sin dec).  Its third row is the new centre in the old frame:
+    l0 = cos dec1 sin(ra1 - ra0).  A (3, 3) float64 ndarray.  Plumbing: numpy only."""
+    import numpy as np
+
+    def M(ra, dec):
+        sr, cr, sd, cd = np.sin(ra), np.cos(ra), np.sin(dec), np.cos(dec)
+        return np.array([[-sr, cr, 0.0], [-sd * cr, -sd * sr, cd], [cd * cr, cd * sr, sd]])
+    return M(float(ra1), float(dec1)) @ M(float(ra0), float(dec0)).T
+
+
+def average_groups(a1, a2, time, ntime=1, chan=None, nchan=1, uvw=None, bda=None):
+    """The groups Context.average collapses: one per unordered antenna pair, per window `time // f` of the integer time
+    index and per block `chan // nchan` of the integer channel index (chan None: one block).  f = ntime, or with
+    bda=max_factor the baseline-dependent f_b = clamp(floor(ntime * Lmax / L_b), ntime, max_factor), L_b the largest
+    sqrt(u^2 + v^2) of baseline b in `uvw` (a (u, v, w) tuple or an (n, 3) array) and Lmax the largest L_b: the longest
+    baseline keeps ntime, shorter ones average longer.  Returns (group, G, a1_g, a2_g): compact int64 ids in [0, G),
+    numbered in the order of the sorted (pair, window, block) keys as in flag_groups, their number, and the antenna pair
+    of every group.  torch tensors (any device) or anything numpy converts; plumbing - torch operations only, no kernel of
+    the library - and G is read back: one synchronisation where the tensors are on a device."""
+    import torch
+    a1, a2, time = (torch.as_tensor(x).to(torch.int64).reshape(-1) for x in (a1, a2, time))
+    dev = a1.device
+    a2, time = a2.to(dev), time.to(dev)
+    ntime, nchan = int(ntime), int(nchan)
+    if a1.shape != a2.shape or a1.shape != time.shape:
+        raise ValueError("a1, a2 and time must hold one value per visibility each")
+    if ntime < 1 or nchan < 1:
+        raise ValueError("ntime and nchan must be >= 1")
+    if chan is None:
+        chan = torch.zeros_like(a1)
+    else:
+        chan = torch.as_tensor(chan).to(torch.int64).reshape(-1).to(dev)
+        if chan.shape != a1.shape:
+            raise ValueError("chan must hold one channel per visibility")
+    if a1.numel() == 0:
+        return torch.zeros_like(a1), 1, torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    lo, hi = torch.minimum(a1, a2), torch.maximum(a1, a2)
+    if bda is None:
+        window = torch.div(time, ntime, rounding_mode="floor")
+    else:
+        most = int(bda)
+        if most < ntime:
+            raise ValueError("bda, the largest factor, must be >= ntime")
+        if uvw is None:
+            raise ValueError("bda needs uvw")
+        if isinstance(uvw, (tuple, list)):
+            u, v = (torch.as_tensor(c).to(torch.float64).reshape(-1).to(dev) for c in uvw[:2])
+        else:
+            uvw = torch.as_tensor(uvw).to(torch.float64).to(dev)
+            u, v = uvw[:, 0], uvw[:, 1]
+        if u.shape != a1.shape or v.shape != a1.shape:
+            raise ValueError("uvw must hold one baseline per visibility")
+        _, bl = torch.unique(torch.stack((lo, hi), dim=1), dim=0, sorted=True, return_inverse=True)
+        length = torch.zeros(int(bl.max()) + 1, dtype=torch.float64, device=dev)
+        length = length.scatter_reduce(0, bl, torch.sqrt(u * u + v * v), reduce="amax")
+        factor = torch.floor(ntime * length.max() / length)
+        factor = torch.where(length > 0, factor, torch.full_like(factor, float(most))).clamp(ntime, most).to(torch.int64)
+        window = torch.div(time, factor[bl], rounding_mode="floor")
+    block = torch.div(chan, nchan, rounding_mode="floor")
+    keys, group = torch.unique(torch.stack((lo, hi, window, block), dim=1), dim=0, sorted=True, return_inverse=True)
+    return group.to(torch.int64), int(keys.shape[0]), keys[:, 0].contiguous(), keys[:, 1].contiguous()
 
 
 def default_context(device=0):

@@ -64,6 +64,9 @@ _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 # (find_sources, after the image)
 _FIND_SOURCES_ARGS = [i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, C.c_double, i64, vp, ci, i64, vp, vp, vp, vp]
 _FIND_SOURCES = [vp, C.c_double, i64, vp, *_FIND_SOURCES_ARGS]
+# R is the host's in both forms (9 doubles, read at the call)
+_PHASE_SHIFT = [vp, i64, _HOST_F64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+_AVERAGE = [vp, i64, i64, vp, _HOST_F64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -205,6 +208,10 @@ SIGNATURES = {
     "gridhip_find_sources": (ci, _FIND_SOURCES),
     "gridhip_find_sources_dev": (ci, _FIND_SOURCES),
     "gridhip_imager_find_sources_dev": (ci, [vp, vp, *_FIND_SOURCES_ARGS]),
+    "gridhip_phase_shift": (ci, _PHASE_SHIFT),
+    "gridhip_phase_shift_dev": (ci, _PHASE_SHIFT),
+    "gridhip_average": (ci, _AVERAGE),
+    "gridhip_average_dev": (ci, _AVERAGE),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

@@ -496,6 +496,34 @@ def component_count(be, count, like):
     return count
 
 
+def group_ids(be, group, G, n):
+    """G, group as gridhip_average takes them: group None goes as NULL and needs G in (None, 1); a given group needs G, the
+    number of groups (gridhip.average_groups and gridhip.flag_groups return both)"""
+    if group is None:
+        if G not in (None, 1):
+            raise ValueError("G > 1 needs group, the group of every visibility")
+        return 1, None
+    if G is None:
+        raise ValueError("group needs G, the number of groups (average_groups returns both)")
+    if int(G) < 1:
+        raise ValueError("G must be >= 1")
+    return int(G), _integers(be, group, n, "group")
+
+
+def rotation(R):
+    """R as gridhip_phase_shift and gridhip_average take it: 9 host float64 values whichever back end the stream comes from,
+    passed by address - the caller keeps the returned array alive for the call; None goes as NULL.  The values are checked by
+    the library (finite, R22 > 0, orthonormal to 1e-9)."""
+    if R is None:
+        return None, None
+    if is_torch(R):
+        R = R.detach().cpu().numpy()
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if R.shape not in ((3, 3), (9,)):
+        raise ValueError(f"R must be a 3 x 3 rotation, not of shape {R.shape}")
+    return R.ctypes.data_as(C.POINTER(C.c_double)), R
+
+
 SRC_DOUBLES = 16  # GRIDHIP_SRC_DOUBLES: { label, ncells, yp, xp, peak, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1, flags }
 
 
