@@ -461,12 +461,6 @@ __global__ void am_stats_kernel(const AmState *st, double *stats)
     stats[7] = 0.0;
 }
 
-bool overlap_bytes(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 bool level_ok(double x) { return x >= 0.0 && x < __builtin_inf(); }
 
 }  // namespace
@@ -480,8 +474,8 @@ int automask_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8
                                    min_cells));
     if (N <= AM_MAX_N) {  // (above it the call is refused below, and the byte counts are not needed)
         const size_t cells = (size_t)N * N;
-        if (overlap_bytes(mask, cells, image, cells * 8) || overlap_bytes(stats, 64, image, cells * 8) ||
-            overlap_bytes(stats, 64, mask, cells))
+        if (overlap(mask, cells, image, cells * 8) || overlap(stats, 64, image, cells * 8) ||
+            overlap(stats, 64, mask, cells))
             return fail(ctx, GRIDHIP_EINVAL, "automask: image, mask and stats must not overlap");
     }
     if (grow > AM_MAX_GROW) return fail(ctx, GRIDHIP_EUNSUPPORTED, "automask: grow above %d", (int)AM_MAX_GROW);
@@ -580,20 +574,13 @@ int automask_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *image, uin
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, automask_scratch_bytes(ctx, N)));
-    if (dev)
-        return automask_run(ctx, N, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
-                            min_cells, grow, stats, scratch.p);
     const size_t cells = (size_t)N * N;
-    DevBuf im, mk, nz, s;
-    GH_CHECK(im.upload(ctx, image, cells * 8));
-    GH_CHECK(mk.upload(ctx, mask, cells));
-    if (noise) GH_CHECK(nz.upload(ctx, noise, 8));
-    GH_CHECK(s.alloc(ctx, 64));
-    GH_CHECK(automask_run(ctx, N, im.as<double>(), mk.as<uint8_t>(), border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo,
-                          noise ? nz.as<double>() : nullptr, peak_frac, min_cells, grow, s.as<double>(), scratch.p));
-    GH_CHECK(d2h(ctx, mask, mk.p, cells));
-    GH_CHECK(d2h(ctx, stats, s.p, 64));
-    return sync(ctx);
+    Staged st(ctx, dev);
+    image = st.in(image, cells * 8), mask = st.inout(mask, mask, cells), noise = st.in(noise, 8), stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(automask_run(ctx, N, image, mask, border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac,
+                          min_cells, grow, stats, scratch.p));
+    return st.finish();
 }
 
 }  // namespace

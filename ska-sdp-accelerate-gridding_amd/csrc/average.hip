@@ -24,8 +24,6 @@
 // Integer atomics only; no floating-point atomic and no sum of doubles anywhere in this file.
 #include <math.h>
 
-#include <vector>
-
 #include "common.h"
 #include "imaging.h"
 
@@ -360,16 +358,14 @@ struct Span {  // n elements of 8 * width bytes, `stride` doubles apart
     int64_t n, stride, width;
 };
 
-size_t span_bytes(const Span &a) { return a.p && a.n > 0 ? ((size_t)(a.n - 1) * a.stride + a.width) * 8 : 0; }
+size_t span_bytes(const Span &a) { return gridhip::span_bytes(a.n, a.stride, a.width); }
 
 // do two arrays share an element?  Columns of one interleaved array (equal strides, bases a whole number of doubles
 // apart that is no multiple of the stride) do not; everything else is judged by the byte ranges.
 bool collide(const Span &a, const Span &b)
 {
-    const size_t ab = span_bytes(a), bb = span_bytes(b);
-    if (!ab || !bb) return false;
+    if (!overlap(a.p, span_bytes(a), b.p, span_bytes(b))) return false;
     const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
-    if (!(x < y + bb && y < x + ab)) return false;
     if (a.stride == b.stride && a.width == 1 && b.width == 1 && a.stride > 1) {
         const uintptr_t d = x > y ? x - y : y - x;
         if (d % 8 == 0 && (d / 8) % (uintptr_t)a.stride != 0) return false;
@@ -501,22 +497,73 @@ int average_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, co
     return GRIDHIP_OK;
 }
 
-// the host forms' strided coordinate outputs: n contiguous doubles from the device into out[k * stride]
-int download_strided(gridhip_ctx *ctx, double *out, int64_t stride, const void *dev, int64_t n)
-{
-    if (stride == 1) return d2h(ctx, out, dev, (size_t)n * 8);
-    std::vector<double> tmp((size_t)n);
-    GH_CHECK(d2h(ctx, tmp.data(), dev, (size_t)n * 8));
-    GH_CHECK(sync(ctx));
-    for (int64_t k = 0; k < n; ++k) out[k * stride] = tmp[(size_t)k];
-    return GRIDHIP_OK;
-}
-
 }  // namespace
 
 }  // namespace gridhip
 
 using namespace gridhip;
+
+namespace {
+
+int phase_shift_any(gridhip_ctx *ctx, bool dev, int64_t n, const double *R, const double *u, const double *v, const double *w,
+                    int64_t uv_stride, const double *vis_in, double *vis_out, double *u_out, double *v_out, double *w_out,
+                    int64_t out_stride, double *stats)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    Shift S;
+    GH_CHECK(shift_check(ctx, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats, &S));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t sb = span_bytes(n, uv_stride), n8 = (size_t)n * 8;
+    Staged st(ctx, dev);
+    u = st.in(u, sb), v = st.in(v, sb), w = st.in(w, sb);
+    double *dvis = st.inout(vis_in, vis_out, 2 * n8);
+    if (!dev) vis_in = dvis;  // (the device copy of vis is shifted in place)
+    // (the coordinate outputs are contiguous in their staged blocks and strided at the caller's)
+    double *du = st.raw(u_out, n8), *dv = st.raw(v_out, n8), *dw = st.raw(w_out, n8);
+    double *dst = st.out(stats, 32);
+    GH_CHECK(st.status());
+    GH_CHECK(shift_run(ctx, n, S, u, v, w, uv_stride, vis_in, dvis, du, dv, dw, dev ? out_stride : 1, dst));
+    if (!dev && u_out) {
+        GH_CHECK(download_strided(ctx, u_out, out_stride, du, n));
+        GH_CHECK(download_strided(ctx, v_out, out_stride, dv, n));
+        GH_CHECK(download_strided(ctx, w_out, out_stride, dw, n));
+    }
+    return st.finish();
+}
+
+int average_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t G, const int64_t *group, const double *R, const double *u,
+                const double *v, const double *w, int64_t uv_stride, const double *x, const double *vis, const double *wt,
+                double *u_out, double *v_out, double *w_out, int64_t out_stride, double *x_out, double *vis_out,
+                double *wt_out, int64_t *count_out, double *stats)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    Shift S;
+    GH_CHECK(average_check(ctx, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out,
+                           wt_out, count_out, stats, &S));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t sb = span_bytes(n, uv_stride), n8 = (size_t)n * 8, g8 = (size_t)G * 8;
+    DevBuf scratch;
+    GH_CHECK(scratch.alloc(ctx, average_scratch_bytes(G)));
+    Staged st(ctx, dev);
+    group = st.in(group, n8), u = st.in(u, sb), v = st.in(v, sb), w = st.in(w, sb), x = st.in(x, n8);
+    vis = st.in(vis, 2 * n8), wt = st.in(wt, n8);
+    // (the coordinate outputs are contiguous in their staged blocks and strided at the caller's)
+    double *du = st.raw(u_out, g8), *dv = st.raw(v_out, g8), *dw = st.raw(w_out, g8);
+    double *dx = st.out(x_out, g8), *dvis = st.out(vis_out, 2 * g8), *dwt = st.out(wt_out, g8);
+    int64_t *dcnt = st.out(count_out, g8);
+    double *dst = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(average_run(ctx, n, G, group, R ? &S : nullptr, u, v, w, uv_stride, x, vis, wt, du, dv, dw, dev ? out_stride : 1, dx,
+                         dvis, dwt, dcnt, dst, scratch.p));
+    if (!dev) {
+        GH_CHECK(download_strided(ctx, u_out, out_stride, du, G));
+        GH_CHECK(download_strided(ctx, v_out, out_stride, dv, G));
+        GH_CHECK(download_strided(ctx, w_out, out_stride, dw, G));
+    }
+    return st.finish();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -524,45 +571,14 @@ int gridhip_phase_shift_dev(gridhip_ctx *ctx, int64_t n, const double *R, const 
                             int64_t uv_stride, const double *vis_in, double *vis_out, double *u_out, double *v_out,
                             double *w_out, int64_t out_stride, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    Shift S;
-    GH_CHECK(shift_check(ctx, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats, &S));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return shift_run(ctx, n, S, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats);
+    return phase_shift_any(ctx, true, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats);
 }
 
 int gridhip_phase_shift(gridhip_ctx *ctx, int64_t n, const double *R, const double *u, const double *v, const double *w,
                         int64_t uv_stride, const double *vis_in, double *vis_out, double *u_out, double *v_out, double *w_out,
                         int64_t out_stride, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    Shift S;
-    GH_CHECK(shift_check(ctx, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats, &S));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t sb = n > 0 ? ((size_t)(n - 1) * uv_stride + 1) * 8 : 0, n8 = (size_t)n * 8;
-    DevBuf du, dv, dw, dvis, dou, dov, dow, dst;
-    GH_CHECK(du.upload(ctx, u, sb));
-    GH_CHECK(dv.upload(ctx, v, sb));
-    if (w) GH_CHECK(dw.upload(ctx, w, sb));
-    GH_CHECK(dvis.upload(ctx, vis_in, 2 * n8));
-    if (u_out) {
-        GH_CHECK(dou.alloc(ctx, n8));
-        GH_CHECK(dov.alloc(ctx, n8));
-        GH_CHECK(dow.alloc(ctx, n8));
-    }
-    if (stats) GH_CHECK(dst.alloc(ctx, 32));
-    // (the device copy of vis is shifted in place; the coordinate outputs are contiguous there and strided here)
-    GH_CHECK(shift_run(ctx, n, S, du.as<double>(), dv.as<double>(), w ? dw.as<double>() : nullptr, uv_stride, dvis.as<double>(),
-                       dvis.as<double>(), u_out ? dou.as<double>() : nullptr, u_out ? dov.as<double>() : nullptr,
-                       u_out ? dow.as<double>() : nullptr, 1, stats ? dst.as<double>() : nullptr));
-    GH_CHECK(d2h(ctx, vis_out, dvis.p, 2 * n8));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 32));
-    if (u_out) {
-        GH_CHECK(download_strided(ctx, u_out, out_stride, dou.p, n));
-        GH_CHECK(download_strided(ctx, v_out, out_stride, dov.p, n));
-        GH_CHECK(download_strided(ctx, w_out, out_stride, dow.p, n));
-    }
-    return sync(ctx);
+    return phase_shift_any(ctx, false, n, R, u, v, w, uv_stride, vis_in, vis_out, u_out, v_out, w_out, out_stride, stats);
 }
 
 int gridhip_average_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *R, const double *u,
@@ -570,15 +586,8 @@ int gridhip_average_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *g
                         const double *wt, double *u_out, double *v_out, double *w_out, int64_t out_stride, double *x_out,
                         double *vis_out, double *wt_out, int64_t *count_out, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    Shift S;
-    GH_CHECK(average_check(ctx, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out,
-                           wt_out, count_out, stats, &S));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf scratch;
-    GH_CHECK(scratch.alloc(ctx, average_scratch_bytes(G)));
-    return average_run(ctx, n, G, group, R ? &S : nullptr, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out,
-                       vis_out, wt_out, count_out, stats, scratch.p);
+    return average_any(ctx, true, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out,
+                       wt_out, count_out, stats);
 }
 
 int gridhip_average(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *R, const double *u,
@@ -586,43 +595,8 @@ int gridhip_average(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group
                     double *u_out, double *v_out, double *w_out, int64_t out_stride, double *x_out, double *vis_out,
                     double *wt_out, int64_t *count_out, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    Shift S;
-    GH_CHECK(average_check(ctx, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out,
-                           wt_out, count_out, stats, &S));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t sb = n > 0 ? ((size_t)(n - 1) * uv_stride + 1) * 8 : 0, n8 = (size_t)n * 8, g8 = (size_t)G * 8;
-    DevBuf scratch, dg, du, dv, dw, dx, dvis, dwt, dou, dov, dow, dox, dovis, dowt, docnt, dst;
-    GH_CHECK(scratch.alloc(ctx, average_scratch_bytes(G)));
-    if (group) GH_CHECK(dg.upload(ctx, group, n8));
-    GH_CHECK(du.upload(ctx, u, sb));
-    GH_CHECK(dv.upload(ctx, v, sb));
-    if (w) GH_CHECK(dw.upload(ctx, w, sb));
-    if (x) GH_CHECK(dx.upload(ctx, x, n8));
-    GH_CHECK(dvis.upload(ctx, vis, 2 * n8));
-    if (wt) GH_CHECK(dwt.upload(ctx, wt, n8));
-    GH_CHECK(dou.alloc(ctx, g8));
-    GH_CHECK(dov.alloc(ctx, g8));
-    GH_CHECK(dow.alloc(ctx, g8));
-    if (x_out) GH_CHECK(dox.alloc(ctx, g8));
-    GH_CHECK(dovis.alloc(ctx, 2 * g8));
-    GH_CHECK(dowt.alloc(ctx, g8));
-    if (count_out) GH_CHECK(docnt.alloc(ctx, g8));
-    if (stats) GH_CHECK(dst.alloc(ctx, 64));
-    GH_CHECK(average_run(ctx, n, G, group ? dg.as<int64_t>() : nullptr, R ? &S : nullptr, du.as<double>(), dv.as<double>(),
-                         w ? dw.as<double>() : nullptr, uv_stride, x ? dx.as<double>() : nullptr, dvis.as<double>(),
-                         wt ? dwt.as<double>() : nullptr, dou.as<double>(), dov.as<double>(), dow.as<double>(), 1,
-                         x_out ? dox.as<double>() : nullptr, dovis.as<double>(), dowt.as<double>(),
-                         count_out ? docnt.as<int64_t>() : nullptr, stats ? dst.as<double>() : nullptr, scratch.p));
-    GH_CHECK(download_strided(ctx, u_out, out_stride, dou.p, G));
-    GH_CHECK(download_strided(ctx, v_out, out_stride, dov.p, G));
-    GH_CHECK(download_strided(ctx, w_out, out_stride, dow.p, G));
-    if (x_out) GH_CHECK(d2h(ctx, x_out, dox.p, g8));
-    GH_CHECK(d2h(ctx, vis_out, dovis.p, 2 * g8));
-    GH_CHECK(d2h(ctx, wt_out, dowt.p, g8));
-    if (count_out) GH_CHECK(d2h(ctx, count_out, docnt.p, g8));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 64));
-    return sync(ctx);
+    return average_any(ctx, false, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out,
+                       wt_out, count_out, stats);
 }
 
 }  // extern "C"

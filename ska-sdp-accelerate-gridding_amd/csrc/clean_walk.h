@@ -1,6 +1,6 @@
 // What the three CLEANs (clean.hip, msclean.hip, mfclean.hip) share and nothing else includes: the tile, a tile's table
 // entry, the search rule and its reductions, the stop level of the _auto forms, the one walk over a tile that all three
-// tile kernels are, and on the host the tile grids, the overlap test and the launch loop of a call.
+// tile kernels are, and on the host the tile grids and the launch loop of a call.
 #pragma once
 #include <type_traits>
 
@@ -250,13 +250,6 @@ static inline CleanTiles clean_tiles(int64_t N, int64_t patch = 0)
     const int64_t span = patch > 0 && 2 * patch + 1 < N ? 2 * patch + 1 : N;
     return {(int)ntx, (int)nty, (int)(ntx * nty), dim3((unsigned)ntx, (unsigned)nty),
             dim3((unsigned)tiles_spanned(span, CLEAN_TW, ntx), (unsigned)tiles_spanned(span, CLEAN_TH, nty))};
-}
-
-// do the abytes at a and the bbytes at b share a byte?
-static inline bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bbytes && y < x + abytes;
 }
 
 // The launches of one call, in stream order: the tile pass over all tiles and the first pick, then niter times the tile

@@ -73,6 +73,39 @@ int DevBuf::upload(gridhip_ctx *ctx, const void *host, size_t bytes)
     return h2d(ctx, p, host, bytes);
 }
 
+void *Staged::block(const void *own, const void *src, void *dst, size_t bytes)
+{
+    if (!own || dev_) return const_cast<void *>(own);
+    if (err_ != GRIDHIP_OK) return nullptr;
+    if (nbufs_ == MAX) {
+        err_ = fail(ctx_, GRIDHIP_EINVAL, "a call stages at most %d arguments", MAX);
+        return nullptr;
+    }
+    DevBuf &b = bufs_[nbufs_++];
+    err_ = src ? b.upload(ctx_, src, bytes) : b.alloc(ctx_, bytes);
+    if (err_ != GRIDHIP_OK) return nullptr;
+    if (dst) outs_[nouts_++] = {dst, b.p, bytes};
+    return b.p;
+}
+
+int Staged::finish()
+{
+    GH_CHECK(err_);
+    if (dev_) return GRIDHIP_OK;
+    for (int i = 0; i < nouts_; ++i) GH_CHECK(d2h(ctx_, outs_[i].host, outs_[i].d, outs_[i].bytes));
+    return sync(ctx_);
+}
+
+int download_strided(gridhip_ctx *ctx, double *out, int64_t stride, const void *dev, int64_t n)
+{
+    if (stride == 1) return d2h(ctx, out, dev, (size_t)n * 8);
+    std::vector<double> tmp((size_t)n);
+    GH_CHECK(d2h(ctx, tmp.data(), dev, (size_t)n * 8));
+    GH_CHECK(sync(ctx));
+    for (int64_t k = 0; k < n; ++k) out[k * stride] = tmp[(size_t)k];
+    return GRIDHIP_OK;
+}
+
 static int ilog2(int x)
 {
     int l = 0;

@@ -475,8 +475,7 @@ int ddcal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, co
         return fail(ctx, GRIDHIP_EINVAL, "ddcal: bad argument");
     GH_CHECK(dd_shape_check(ctx, "ddcal", n, A, T, D, a1, a2, slot));
     const size_t gb = (size_t)D * A * T * 16, n8 = (size_t)n * 8;
-    if (overlap(gains, gb, a1, n8) || overlap(gains, gb, a2, n8) || overlap(gains, gb, slot, n8) ||
-        overlap(gains, gb, vis, 2 * n8) || overlap(gains, gb, model_vis, 2 * n8 * D) || overlap(gains, gb, wt, n8))
+    if (overlaps_any({gains, gb}, {{a1, n8}, {a2, n8}, {slot, n8}, {vis, 2 * n8}, {model_vis, 2 * n8 * D}, {wt, n8}}))
         return fail(ctx, GRIDHIP_EINVAL, "ddcal: gains must not overlap an input");
     return GRIDHIP_OK;
 }
@@ -490,8 +489,7 @@ int dd_subtract_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t
         return fail(ctx, GRIDHIP_EINVAL, "dd_subtract: bad argument");
     GH_CHECK(dd_shape_check(ctx, "dd_subtract", n, A, T, D, a1, a2, slot));
     const size_t gb = (size_t)D * A * T * 16, n8 = (size_t)n * 8;
-    if (overlap(vis_out, 2 * n8, gains, gb) || overlap(vis_out, 2 * n8, a1, n8) || overlap(vis_out, 2 * n8, a2, n8) ||
-        overlap(vis_out, 2 * n8, slot, n8) || overlap(vis_out, 2 * n8, model_vis, 2 * n8 * D))
+    if (overlaps_any({vis_out, 2 * n8}, {{gains, gb}, {a1, n8}, {a2, n8}, {slot, n8}, {model_vis, 2 * n8 * D}}))
         return fail(ctx, GRIDHIP_EINVAL, "dd_subtract: vis_out overlaps gains, model_vis, a1, a2 or slot");
     if (vis_out != vis_in && overlap(vis_out, 2 * n8, vis_in, 2 * n8))
         return fail(ctx, GRIDHIP_EINVAL, "dd_subtract: vis_out may be vis_in itself, and overlap it in no other way");
@@ -505,9 +503,7 @@ int peel_check(gridhip_ctx *ctx, int64_t n, int64_t cells, const double *model_v
     const size_t n8 = (size_t)n * 8;
     if (overlap(wt_cal, n8, gains, (size_t)cells * 16))
         return fail(ctx, GRIDHIP_EINVAL, "peel: wt_cal overlaps gains");
-    if (overlap(model_vis, 2 * n8, a1, n8) || overlap(model_vis, 2 * n8, a2, n8) || overlap(model_vis, 2 * n8, slot, n8) ||
-        overlap(model_vis, 2 * n8, vis, 2 * n8) || overlap(model_vis, 2 * n8, wt, n8) ||
-        overlap(model_vis, 2 * n8, wt_cal, n8) || overlap(model_vis, 2 * n8, stats, 64))
+    if (overlaps_any({model_vis, 2 * n8}, {{a1, n8}, {a2, n8}, {slot, n8}, {vis, 2 * n8}, {wt, n8}, {wt_cal, n8}, {stats, 64}}))
         return fail(ctx, GRIDHIP_EINVAL, "peel: row 0 of model_vis is written and may overlap nothing else");
     return GRIDHIP_OK;
 }
@@ -578,6 +574,45 @@ int ddcal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, cons
 
 using namespace gridhip;
 
+namespace {
+
+int ddcal_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
+              const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
+              int warm, int64_t niter, double tol, double *gains, double *stats)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    GH_CHECK(ddcal_check(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n8 = (size_t)n * 8, gb = (size_t)D * A * T * 16;
+    Staged st(ctx, dev);
+    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), vis = st.in(vis, 2 * n8);
+    model_vis = st.in(model_vis, 2 * n8 * D), wt = st.in(wt, n8);
+    gains = warm ? st.inout(gains, gains, gb) : st.out(gains, gb);  // (a cold start reads no gains)
+    stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(ddcal_run(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats));
+    return st.finish();
+}
+
+int dd_subtract_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1,
+                    const int64_t *a2, const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs,
+                    const double *vis_in, double *vis_out)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    GH_CHECK(dd_subtract_check(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n8 = (size_t)n * 8;
+    Staged st(ctx, dev);
+    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), gains = st.in(gains, (size_t)D * A * T * 16);
+    model_vis = st.in(model_vis, 2 * n8 * D), vis_out = st.inout(vis_in, vis_out, 2 * n8);
+    if (!dev && vis_in) vis_in = vis_out;  // (the staged visibilities are subtracted from in place)
+    GH_CHECK(st.status());
+    GH_CHECK(dd_subtract_run(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out));
+    return st.finish();
+}
+
+}  // namespace
+
 extern "C" {
 
 int64_t gridhip_ddcal_lds_antennas(int64_t D)
@@ -589,73 +624,28 @@ int gridhip_ddcal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t
                       const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                       int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(ddcal_check(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return ddcal_run(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return ddcal_any(ctx, true, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
 }
 
 int gridhip_ddcal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
                   const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                   int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(ddcal_check(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8, gb = (size_t)D * A * T * 16;
-    DevBuf d1, d2, ds, dv, dm, dw, dg, dst;
-    GH_CHECK(d1.upload(ctx, a1, n8));
-    GH_CHECK(d2.upload(ctx, a2, n8));
-    if (slot) GH_CHECK(ds.upload(ctx, slot, n8));
-    GH_CHECK(dv.upload(ctx, vis, 2 * n8));
-    GH_CHECK(dm.upload(ctx, model_vis, 2 * n8 * D));
-    if (wt) GH_CHECK(dw.upload(ctx, wt, n8));
-    if (warm)
-        GH_CHECK(dg.upload(ctx, gains, gb));
-    else
-        GH_CHECK(dg.alloc(ctx, gb));
-    GH_CHECK(dst.alloc(ctx, 64));
-    GH_CHECK(ddcal_run(ctx, n, A, T, D, d1.as<int64_t>(), d2.as<int64_t>(), slot ? ds.as<int64_t>() : nullptr,
-                       dv.as<double>(), dm.as<double>(), wt ? dw.as<double>() : nullptr, mode, refant, warm, niter, tol,
-                       dg.as<double>(), dst.as<double>()));
-    GH_CHECK(d2h(ctx, gains, dg.p, gb));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 64));
-    return sync(ctx);
+    return ddcal_any(ctx, false, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
 }
 
 int gridhip_dd_subtract_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1,
                             const int64_t *a2, const int64_t *slot, const double *gains, const double *model_vis,
                             int64_t dirs, const double *vis_in, double *vis_out)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(dd_subtract_check(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return dd_subtract_run(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out);
+    return dd_subtract_any(ctx, true, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out);
 }
 
 int gridhip_dd_subtract(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
                         const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs,
                         const double *vis_in, double *vis_out)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(dd_subtract_check(ctx, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8;
-    DevBuf d1, d2, ds, dg, dm, dv;
-    GH_CHECK(d1.upload(ctx, a1, n8));
-    GH_CHECK(d2.upload(ctx, a2, n8));
-    if (slot) GH_CHECK(ds.upload(ctx, slot, n8));
-    GH_CHECK(dg.upload(ctx, gains, (size_t)D * A * T * 16));
-    GH_CHECK(dm.upload(ctx, model_vis, 2 * n8 * D));
-    if (vis_in)
-        GH_CHECK(dv.upload(ctx, vis_in, 2 * n8));
-    else
-        GH_CHECK(dv.alloc(ctx, 2 * n8));
-    // (the staged visibilities are subtracted from in place)
-    GH_CHECK(dd_subtract_run(ctx, n, A, T, D, d1.as<int64_t>(), d2.as<int64_t>(), slot ? ds.as<int64_t>() : nullptr,
-                             dg.as<double>(), dm.as<double>(), dirs, vis_in ? dv.as<double>() : nullptr, dv.as<double>()));
-    GH_CHECK(d2h(ctx, vis_out, dv.p, 2 * n8));
-    return sync(ctx);
+    return dd_subtract_any(ctx, false, n, A, T, D, a1, a2, slot, gains, model_vis, dirs, vis_in, vis_out);
 }
 
 }  // extern "C"

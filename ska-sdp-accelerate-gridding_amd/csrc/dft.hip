@@ -350,14 +350,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-
-size_t span_bytes(int64_t n, int64_t stride) { return n > 0 ? ((size_t)(n - 1) * stride + 1) * 8 : 0; }
-
 template <int TT>
 void launch_main(gridhip_ctx *ctx, dim3 grid, bool sliced, int64_t n, const double *u, const double *v, const double *w,
                  int64_t stride, const double *x, const double *prep, const int64_t *head, int64_t per,
@@ -392,19 +384,13 @@ int dft_predict_check(gridhip_ctx *ctx, int64_t C, const double *comps, const in
     if (n < 0 || C < 0 || T < 1 || T > 4 || (C > 0 && !comps) || (n > 0 && (!u || !v || !vis_out)) || stride < 1)
         return fail(ctx, GRIDHIP_EINVAL, "dft_predict: n >= 0, C >= 0, T in 1..4, comps, u, v, vis_out, uv_stride >= 1");
     if (n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "dft_predict: n must be < 2^31 per call");
-    const size_t ob = (size_t)n * 16, sb = span_bytes(n, stride);
-    if (overlap(vis_out, ob, comps, (size_t)C * GRIDHIP_COMP_DOUBLES * 8) || overlap(vis_out, ob, count, 8) ||
-        overlap(vis_out, ob, u, sb) || overlap(vis_out, ob, v, sb) || overlap(vis_out, ob, w, sb) ||
-        overlap(vis_out, ob, x, (size_t)n * 8) || (vis_out != vis_sub && overlap(vis_out, ob, vis_sub, ob)))
+    const size_t ob = (size_t)n * 16, sb = span_bytes(n, stride), cb = (size_t)C * GRIDHIP_COMP_DOUBLES * 8;
+    if (overlaps_any({vis_out, ob}, {{comps, cb}, {count, 8}, {u, sb}, {v, sb}, {w, sb}, {x, (size_t)n * 8}}) ||
+        (vis_out != vis_sub && overlap(vis_out, ob, vis_sub, ob)))
         return fail(ctx, GRIDHIP_EINVAL, "dft_predict: vis_out may be vis_sub itself, and overlap nothing else");
-    const struct {
-        const void *p;
-        size_t bytes;
-    } others[8] = {{vis_out, ob}, {vis_sub, ob}, {comps, (size_t)C * GRIDHIP_COMP_DOUBLES * 8}, {count, 8}, {u, sb}, {v, sb},
-                   {w, sb}, {x, (size_t)n * 8}};
-    for (const auto &o : others)
-        if (overlap(stats, 32, o.p, o.bytes))
-            return fail(ctx, GRIDHIP_EINVAL, "dft_predict: stats overlaps another argument");
+    if (overlaps_any({stats, 32}, {{vis_out, ob}, {vis_sub, ob}, {comps, cb}, {count, 8}, {u, sb}, {v, sb}, {w, sb},
+                                   {x, (size_t)n * 8}}))
+        return fail(ctx, GRIDHIP_EINVAL, "dft_predict: stats overlaps another argument");
     return GRIDHIP_OK;
 }
 
@@ -490,74 +476,77 @@ int components_run(gridhip_ctx *ctx, int64_t N, double theta, int T, const doubl
 
 using namespace gridhip;
 
+namespace {
+
+int dft_predict_any(gridhip_ctx *ctx, bool dev, int64_t C, const double *comps, const int64_t *count, int T, int64_t n,
+                    const double *u, const double *v, const double *w, int64_t uv_stride, const double *x,
+                    const double *vis_sub, double *vis_out, double *stats)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    GH_CHECK(dft_predict_check(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t sb = span_bytes(n, uv_stride), ob = (size_t)n * 16;
+    Staged st(ctx, dev);
+    comps = st.in(comps, (size_t)C * GRIDHIP_COMP_DOUBLES * 8), count = st.in(count, 8), u = st.in(u, sb), v = st.in(v, sb);
+    w = st.in(w, sb), x = st.in(x, (size_t)n * 8), vis_sub = st.in(vis_sub, ob), vis_out = st.out(vis_out, ob);
+    stats = st.out(stats, 32);
+    GH_CHECK(st.status());
+    GH_CHECK(dft_predict_run(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats));
+    return st.finish();
+}
+
+int components_any(gridhip_ctx *ctx, bool dev, double theta, int64_t lam, int T, const double *model, int64_t max_c,
+                   double *comps, int64_t *count)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    int64_t N = 0;
+    GH_CHECK(components_check(ctx, theta, lam, T, model, max_c, comps, count, &N));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    Staged st(ctx, dev);
+    model = st.in(model, (size_t)T * N * N * 8);
+    double *dc = st.raw(comps, (size_t)max_c * GRIDHIP_COMP_DOUBLES * 8);
+    int64_t *dn = st.raw(count, 8);
+    GH_CHECK(st.status());
+    GH_CHECK(components_run(ctx, N, theta, T, model, max_c, dc, dn));
+    if (dev) return GRIDHIP_OK;
+    // only the rows written come back: the caller's rows after them stay as they were
+    int64_t found = 0;
+    GH_CHECK(d2h(ctx, &found, dn, 8));
+    GH_CHECK(sync(ctx));
+    GH_CHECK(d2h(ctx, comps, dc, (size_t)(found < max_c ? found : max_c) * GRIDHIP_COMP_DOUBLES * 8));
+    GH_CHECK(st.finish());
+    *count = found;
+    return GRIDHIP_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int gridhip_dft_predict_dev(gridhip_ctx *ctx, int64_t C, const double *comps, const int64_t *count_dev, int T, int64_t n,
                             const double *u, const double *v, const double *w, int64_t uv_stride, const double *x,
                             const double *vis_sub, double *vis_out, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(dft_predict_check(ctx, C, comps, count_dev, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return dft_predict_run(ctx, C, comps, count_dev, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats);
+    return dft_predict_any(ctx, true, C, comps, count_dev, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats);
 }
 
 int gridhip_dft_predict(gridhip_ctx *ctx, int64_t C, const double *comps, const int64_t *count, int T, int64_t n,
                         const double *u, const double *v, const double *w, int64_t uv_stride, const double *x,
                         const double *vis_sub, double *vis_out, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(dft_predict_check(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t sb = span_bytes(n, uv_stride), ob = (size_t)n * 16;
-    DevBuf dc, dn, du, dv, dw, dx, dsub, dout, dst;
-    GH_CHECK(dc.upload(ctx, comps, (size_t)C * GRIDHIP_COMP_DOUBLES * 8));
-    if (count) GH_CHECK(dn.upload(ctx, count, 8));
-    GH_CHECK(du.upload(ctx, u, sb));
-    GH_CHECK(dv.upload(ctx, v, sb));
-    if (w) GH_CHECK(dw.upload(ctx, w, sb));
-    if (x) GH_CHECK(dx.upload(ctx, x, (size_t)n * 8));
-    if (vis_sub) GH_CHECK(dsub.upload(ctx, vis_sub, ob));
-    GH_CHECK(dout.alloc(ctx, ob));
-    GH_CHECK(dst.alloc(ctx, 32));
-    GH_CHECK(dft_predict_run(ctx, C, dc.as<double>(), count ? dn.as<int64_t>() : nullptr, T, n, du.as<double>(),
-                             dv.as<double>(), w ? dw.as<double>() : nullptr, uv_stride, x ? dx.as<double>() : nullptr,
-                             vis_sub ? dsub.as<double>() : nullptr, dout.as<double>(), stats ? dst.as<double>() : nullptr));
-    GH_CHECK(d2h(ctx, vis_out, dout.p, ob));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 32));
-    return sync(ctx);
+    return dft_predict_any(ctx, false, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats);
 }
 
 int gridhip_components_from_image_dev(gridhip_ctx *ctx, double theta, int64_t lam, int T, const double *model,
                                       int64_t max_c, double *comps, int64_t *count)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    int64_t N = 0;
-    GH_CHECK(components_check(ctx, theta, lam, T, model, max_c, comps, count, &N));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return components_run(ctx, N, theta, T, model, max_c, comps, count);
+    return components_any(ctx, true, theta, lam, T, model, max_c, comps, count);
 }
 
 int gridhip_components_from_image(gridhip_ctx *ctx, double theta, int64_t lam, int T, const double *model, int64_t max_c,
                                   double *comps, int64_t *count)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    int64_t N = 0;
-    GH_CHECK(components_check(ctx, theta, lam, T, model, max_c, comps, count, &N));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf dm, dc, dn;
-    GH_CHECK(dm.upload(ctx, model, (size_t)T * N * N * 8));
-    GH_CHECK(dc.alloc(ctx, (size_t)max_c * GRIDHIP_COMP_DOUBLES * 8));
-    GH_CHECK(dn.alloc(ctx, 8));
-    GH_CHECK(components_run(ctx, N, theta, T, dm.as<double>(), max_c, dc.as<double>(), dn.as<int64_t>()));
-    int64_t found = 0;
-    GH_CHECK(d2h(ctx, &found, dn.p, 8));
-    GH_CHECK(sync(ctx));
-    // only the rows written come back: the caller's rows after them stay as they were
-    GH_CHECK(d2h(ctx, comps, dc.p, (size_t)(found < max_c ? found : max_c) * GRIDHIP_COMP_DOUBLES * 8));
-    GH_CHECK(sync(ctx));
-    *count = found;
-    return GRIDHIP_OK;
+    return components_any(ctx, false, theta, lam, T, model, max_c, comps, count);
 }
 
 }  // extern "C"

@@ -316,12 +316,6 @@ __global__ void __launch_bounds__(256)
     stats[7] = (double)((u64)st->cls[0] - clipped);
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-
 template <bool LDS>
 void launch_hist(gridhip_ctx *ctx, dim3 grid, size_t lds, bool mad, int64_t pairs, int G, int shift, int round,
                  const u64 *keys, const u32 *codes, const FlagGroup *gs, const FlagState *st, u32 *bins)
@@ -345,19 +339,11 @@ int flag_check(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, con
         return fail(ctx, GRIDHIP_EINVAL, "flag_residuals: bad argument");
     if (G <= FLAG_MAX_GROUPS && n <= (int64_t)0xffffffffLL) {  // (sizes that overflow nothing)
         const size_t n8 = (size_t)n * 8;
-        const struct {
-            const void *p;
-            size_t bytes;
-        } outs[4] = {{wt_out, n8}, {flags_out, (size_t)n}, {group_stats, (size_t)G * 32}, {stats, 64}},
-          ins[4] = {{group, n8}, {vis, 2 * n8}, {model_vis, 2 * n8}, {wt_in, n8}};
-        for (int o = 0; o < 4; ++o) {
-            for (int i = 0; i < 4; ++i)
-                if (!(o == 0 && i == 3 && wt_out == wt_in) && overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
-                    return fail(ctx, GRIDHIP_EINVAL, "flag_residuals: an output overlaps an input (only wt_out may be wt_in)");
-            for (int q = o + 1; q < 4; ++q)
-                if (overlap(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes))
-                    return fail(ctx, GRIDHIP_EINVAL, "flag_residuals: two outputs overlap");
-        }
+        const int clash = outputs_clash({{wt_out, n8}, {flags_out, (size_t)n}, {group_stats, (size_t)G * 32}, {stats, 64}},
+                                        {{group, n8}, {vis, 2 * n8}, {model_vis, 2 * n8}, {wt_in, n8}}, {{0, 3}});
+        if (clash == 1)
+            return fail(ctx, GRIDHIP_EINVAL, "flag_residuals: an output overlaps an input (only wt_out may be wt_in)");
+        if (clash == 2) return fail(ctx, GRIDHIP_EINVAL, "flag_residuals: two outputs overlap");
     }
     if (G > FLAG_MAX_GROUPS) return fail(ctx, GRIDHIP_EUNSUPPORTED, "flag_residuals: G above %lld", (long long)FLAG_MAX_GROUPS);
     if (n > (int64_t)0xffffffffLL) return fail(ctx, GRIDHIP_EUNSUPPORTED, "flag_residuals: n above 2^32 - 1");
@@ -428,50 +414,47 @@ int flag_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const
 
 using namespace gridhip;
 
-extern "C" {
+namespace {
 
-int gridhip_flag_residuals_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis,
-                               const double *model_vis, const double *wt_in, double nsigma, double amax, int64_t min_count,
-                               int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats)
-{
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(flag_check(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out,
-                        group_stats, stats));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf scratch;
-    GH_CHECK(scratch.alloc(ctx, flag_scratch_bytes(n, G)));
-    return flag_run(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats,
-                    stats, scratch.p);
-}
-
-int gridhip_flag_residuals(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis,
-                           const double *model_vis, const double *wt_in, double nsigma, double amax, int64_t min_count,
-                           int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats)
+int flag_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t G, const int64_t *group, const double *vis,
+             const double *model_vis, const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter,
+             double *wt_out, uint8_t *flags_out, double *group_stats, double *stats)
 {
     if (!ctx) return GRIDHIP_EINVAL;
     GH_CHECK(flag_check(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out,
                         group_stats, stats));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n8 = (size_t)n * 8;
-    DevBuf scratch, dg, dv, dm, dw, dwo, df, dgs, dst;
+    DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, flag_scratch_bytes(n, G)));
-    if (group) GH_CHECK(dg.upload(ctx, group, n8));
-    GH_CHECK(dv.upload(ctx, vis, 2 * n8));
-    if (model_vis) GH_CHECK(dm.upload(ctx, model_vis, 2 * n8));
-    if (wt_in) GH_CHECK(dw.upload(ctx, wt_in, n8));
-    GH_CHECK(dwo.alloc(ctx, n8));
-    if (flags_out) GH_CHECK(df.alloc(ctx, (size_t)n));
-    if (group_stats) GH_CHECK(dgs.alloc(ctx, (size_t)G * 32));
-    if (stats) GH_CHECK(dst.alloc(ctx, 64));
-    GH_CHECK(flag_run(ctx, n, G, group ? dg.as<int64_t>() : nullptr, dv.as<double>(), model_vis ? dm.as<double>() : nullptr,
-                      wt_in ? dw.as<double>() : nullptr, nsigma, amax, min_count, niter, dwo.as<double>(),
-                      flags_out ? df.as<uint8_t>() : nullptr, group_stats ? dgs.as<double>() : nullptr,
-                      stats ? dst.as<double>() : nullptr, scratch.p));
-    GH_CHECK(d2h(ctx, wt_out, dwo.p, n8));
-    if (flags_out) GH_CHECK(d2h(ctx, flags_out, df.p, (size_t)n));
-    if (group_stats) GH_CHECK(d2h(ctx, group_stats, dgs.p, (size_t)G * 32));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 64));
-    return sync(ctx);
+    Staged st(ctx, dev);
+    group = st.in(group, n8), vis = st.in(vis, 2 * n8), model_vis = st.in(model_vis, 2 * n8), wt_in = st.in(wt_in, n8);
+    wt_out = st.out(wt_out, n8), flags_out = st.out(flags_out, (size_t)n), group_stats = st.out(group_stats, (size_t)G * 32);
+    stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(flag_run(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats,
+                      stats, scratch.p));
+    return st.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int gridhip_flag_residuals_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis,
+                               const double *model_vis, const double *wt_in, double nsigma, double amax, int64_t min_count,
+                               int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats)
+{
+    return flag_any(ctx, true, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out,
+                    group_stats, stats);
+}
+
+int gridhip_flag_residuals(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis,
+                           const double *model_vis, const double *wt_in, double nsigma, double amax, int64_t min_count,
+                           int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats)
+{
+    return flag_any(ctx, false, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out,
+                    group_stats, stats);
 }
 
 }  // extern "C"

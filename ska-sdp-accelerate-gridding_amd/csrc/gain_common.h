@@ -100,12 +100,6 @@ __global__ void __launch_bounds__(256)
     stats[7] = (double)st->unsolved;
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-
 }  // namespace
 
 }  // namespace gridhip

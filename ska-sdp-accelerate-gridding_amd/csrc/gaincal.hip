@@ -344,8 +344,7 @@ int gaincal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64
         return fail(ctx, GRIDHIP_EINVAL, "gaincal: bad argument");
     GH_CHECK(shape_check(ctx, "gaincal", n, A, T, a1, a2, slot));
     const size_t gb = (size_t)A * T * 16, n8 = (size_t)n * 8;
-    if (overlap(gains, gb, a1, n8) || overlap(gains, gb, a2, n8) || overlap(gains, gb, slot, n8) ||
-        overlap(gains, gb, vis, 2 * n8) || overlap(gains, gb, model_vis, 2 * n8) || overlap(gains, gb, wt, n8))
+    if (overlaps_any({gains, gb}, {{a1, n8}, {a2, n8}, {slot, n8}, {vis, 2 * n8}, {model_vis, 2 * n8}, {wt, n8}}))
         return fail(ctx, GRIDHIP_EINVAL, "gaincal: gains must not overlap an input");
     return GRIDHIP_OK;
 }
@@ -359,19 +358,16 @@ int apply_gains_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const i
         return fail(ctx, GRIDHIP_EINVAL, "apply_gains: bad argument");
     GH_CHECK(shape_check(ctx, "apply_gains", n, A, T, a1, a2, slot));
     const size_t gb = (size_t)A * T * 16, n8 = (size_t)n * 8;
-    const struct {
-        const void *p;
-        size_t bytes;
-    } outs[2] = {{vis_out, 2 * n8}, {wt_out, n8}}, ins[4] = {{gains, gb}, {a1, n8}, {a2, n8}, {slot, n8}};
-    for (const auto &o : outs)
-        for (const auto &i : ins)
-            if (overlap(o.p, o.bytes, i.p, i.bytes))
-                return fail(ctx, GRIDHIP_EINVAL, "apply_gains: an output overlaps gains, a1, a2 or slot");
+    const Range vo = {vis_out, 2 * n8}, wo = {wt_out, n8};
+    if (overlaps_any(vo, {{gains, gb}, {a1, n8}, {a2, n8}, {slot, n8}}) ||
+        overlaps_any(wo, {{gains, gb}, {a1, n8}, {a2, n8}, {slot, n8}}))
+        return fail(ctx, GRIDHIP_EINVAL, "apply_gains: an output overlaps gains, a1, a2 or slot");
     // in place: vis_out may be vis_in itself and wt_out may be wt_in itself, nothing else
-    if ((vis_out != vis_in && overlap(vis_out, 2 * n8, vis_in, 2 * n8)) || overlap(vis_out, 2 * n8, wt_in, n8) ||
-        overlap(wt_out, n8, vis_in, 2 * n8) || (wt_out != wt_in && overlap(wt_out, n8, wt_in, n8)))
+    // (both outputs against the inputs before one against the other: which message a doubly wrong call gets)
+    if (outputs_clash({vo}, {{vis_in, 2 * n8}, {wt_in, n8}}, {{0, 0}}) ||
+        outputs_clash({wo}, {{vis_in, 2 * n8}, {wt_in, n8}}, {{0, 1}}))
         return fail(ctx, GRIDHIP_EINVAL, "apply_gains: an output may be its own input, and overlap no other");
-    if (overlap(vis_out, 2 * n8, wt_out, n8)) return fail(ctx, GRIDHIP_EINVAL, "apply_gains: vis_out overlaps wt_out");
+    if (overlap(vo.p, vo.bytes, wo.p, wo.bytes)) return fail(ctx, GRIDHIP_EINVAL, "apply_gains: vis_out overlaps wt_out");
     return GRIDHIP_OK;
 }
 
@@ -456,80 +452,75 @@ int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t
 
 using namespace gridhip;
 
+namespace {
+
+int gaincal_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
+                int warm, int64_t niter, double tol, double *gains, double *stats)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    GH_CHECK(gaincal_check(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n8 = (size_t)n * 8, gb = (size_t)A * T * 16;
+    Staged st(ctx, dev);
+    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), vis = st.in(vis, 2 * n8);
+    model_vis = st.in(model_vis, 2 * n8), wt = st.in(wt, n8);
+    gains = warm ? st.inout(gains, gains, gb) : st.out(gains, gb);  // (a cold start reads no gains)
+    stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(gaincal_run(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats, nullptr,
+                         nullptr));
+    return st.finish();
+}
+
+int apply_gains_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                    const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
+                    double *vis_out, double *wt_out)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    GH_CHECK(apply_gains_check(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n8 = (size_t)n * 8;
+    Staged st(ctx, dev);
+    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), gains = st.in(gains, (size_t)A * T * 16);
+    vis_out = st.inout(vis_in, vis_out, 2 * n8);
+    if (!dev) vis_in = vis_out;  // (the staged visibilities are corrected in place)
+    wt_in = st.in(wt_in, n8), wt_out = st.out(wt_out, n8);
+    GH_CHECK(st.status());
+    GH_CHECK(apply_gains_run(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out));
+    return st.finish();
+}
+
+}  // namespace
+
 extern "C" {
 
 int gridhip_gaincal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                         const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                         int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(gaincal_check(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return gaincal_run(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats, nullptr,
-                       nullptr);
+    return gaincal_any(ctx, true, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
 }
 
 int gridhip_gaincal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                     int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(gaincal_check(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8, gb = (size_t)A * T * 16;
-    DevBuf d1, d2, ds, dv, dm, dw, dg, dst;
-    GH_CHECK(d1.upload(ctx, a1, n8));
-    GH_CHECK(d2.upload(ctx, a2, n8));
-    if (slot) GH_CHECK(ds.upload(ctx, slot, n8));
-    GH_CHECK(dv.upload(ctx, vis, 2 * n8));
-    GH_CHECK(dm.upload(ctx, model_vis, 2 * n8));
-    if (wt) GH_CHECK(dw.upload(ctx, wt, n8));
-    if (warm)
-        GH_CHECK(dg.upload(ctx, gains, gb));
-    else
-        GH_CHECK(dg.alloc(ctx, gb));
-    GH_CHECK(dst.alloc(ctx, 64));
-    GH_CHECK(gaincal_run(ctx, n, A, T, d1.as<int64_t>(), d2.as<int64_t>(), slot ? ds.as<int64_t>() : nullptr,
-                         dv.as<double>(), dm.as<double>(), wt ? dw.as<double>() : nullptr, mode, refant, warm, niter, tol,
-                         dg.as<double>(), dst.as<double>(), nullptr, nullptr));
-    GH_CHECK(d2h(ctx, gains, dg.p, gb));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 64));
-    return sync(ctx);
+    return gaincal_any(ctx, false, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
 }
 
 int gridhip_apply_gains_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                             const int64_t *slot, const double *gains, int inverse, const double *vis_in,
                             const double *wt_in, double *vis_out, double *wt_out)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(apply_gains_check(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return apply_gains_run(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out);
+    return apply_gains_any(ctx, true, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out);
 }
 
 int gridhip_apply_gains(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                         const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
                         double *vis_out, double *wt_out)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(apply_gains_check(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8;
-    DevBuf d1, d2, ds, dg, dv, dw, dwo;
-    GH_CHECK(d1.upload(ctx, a1, n8));
-    GH_CHECK(d2.upload(ctx, a2, n8));
-    if (slot) GH_CHECK(ds.upload(ctx, slot, n8));
-    GH_CHECK(dg.upload(ctx, gains, (size_t)A * T * 16));
-    GH_CHECK(dv.upload(ctx, vis_in, 2 * n8));
-    if (wt_in) GH_CHECK(dw.upload(ctx, wt_in, n8));
-    if (wt_out) GH_CHECK(dwo.alloc(ctx, n8));
-    // (the staged visibilities are corrected in place)
-    GH_CHECK(apply_gains_run(ctx, n, A, T, d1.as<int64_t>(), d2.as<int64_t>(), slot ? ds.as<int64_t>() : nullptr,
-                             dg.as<double>(), inverse, dv.as<double>(), wt_in ? dw.as<double>() : nullptr, dv.as<double>(),
-                             wt_out ? dwo.as<double>() : nullptr));
-    GH_CHECK(d2h(ctx, vis_out, dv.p, 2 * n8));
-    if (wt_out) GH_CHECK(d2h(ctx, wt_out, dwo.p, n8));
-    return sync(ctx);
+    return apply_gains_any(ctx, false, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip, sources.hip, average.hip).
+// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
+// sources.hip, average.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -10,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "argrules.h"
 #include "common.h"
 
 namespace gridhip {
@@ -85,6 +87,49 @@ static inline int sync(gridhip_ctx *ctx)
     GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return GRIDHIP_OK;
 }
+
+// the host forms' strided coordinate outputs: n contiguous doubles from the device into out[k * stride]; synchronises
+// unless stride == 1
+int download_strided(gridhip_ctx *ctx, double *out, int64_t stride, const void *dev, int64_t n);
+
+// The pointer arguments of one call as its kernels see them, for both forms of an entry point from one body.  dev: the
+// caller's pointers are device pointers and pass through as they are; nothing is allocated, copied or waited for.  Else
+// every non-null pointer gets a pooled block (in the order of the calls), inputs are uploaded at once and finish()
+// downloads the outputs in that order and synchronises the stream once.  A null pointer stays null either way, also
+// where its length is 0 (a null required argument of an empty call gets no block, as in the _dev form).  A block
+// that cannot be had makes every later call return null and status() / finish() return its code: a body checks status()
+// once, after its last argument and before it launches anything.
+class Staged {
+  public:
+    Staged(gridhip_ctx *ctx, bool dev) : ctx_(ctx), dev_(dev) {}
+    template <typename T>
+    const T *in(const T *p, size_t bytes) { return static_cast<const T *>(block(p, p, nullptr, bytes)); }
+    template <typename T>
+    T *out(T *p, size_t bytes) { return static_cast<T *>(block(p, nullptr, p, bytes)); }
+    // uploaded from src, downloaded to dst (dev: dst itself - a kernel that reads src is given src by the body)
+    template <typename T>
+    T *inout(const T *src, T *dst, size_t bytes) { return static_cast<T *>(block(dst, src, dst, bytes)); }
+    // a block that finish() leaves alone: the body downloads what it wants of it itself
+    template <typename T>
+    T *raw(T *p, size_t bytes) { return static_cast<T *>(block(p, nullptr, nullptr, bytes)); }
+    int status() const { return err_; }
+    int finish();
+
+  private:
+    void *block(const void *own, const void *src, void *dst, size_t bytes);
+    struct Out {
+        void *host;
+        const void *d;
+        size_t bytes;
+    };
+    static constexpr int MAX = 16;  // pointer arguments of one call (gridhip_average has 15)
+    gridhip_ctx *ctx_;
+    bool dev_;
+    int err_ = GRIDHIP_OK;
+    int nbufs_ = 0, nouts_ = 0;
+    DevBuf bufs_[MAX];
+    Out outs_[MAX];
+};
 
 // The device copies of a host-pointer gridding call's inputs (api.hip): the grid (uploaded, or zeroed when `grid` is
 // null), the u / v spans, vis (uploaded, or left for the call to write when `vis` is null), wbin and gcf when given

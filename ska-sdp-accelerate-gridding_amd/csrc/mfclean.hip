@@ -259,20 +259,13 @@ int mfclean_any(gridhip_ctx *ctx, bool dev, int64_t N, int64_t T, const double *
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, mfclean_scratch_bytes(N)));
-    if (dev)
-        return mfclean_run(ctx, N, T, psfs, residuals, models, gain, threshold, niter, border, patch, stats, scratch.p);
     const size_t plane = (size_t)N * N * 8, pb = (size_t)(2 * T - 1) * plane, rb = (size_t)T * plane;
-    DevBuf p, r, m, s;
-    GH_CHECK(p.upload(ctx, psfs, pb));
-    GH_CHECK(r.upload(ctx, residuals, rb));
-    GH_CHECK(m.upload(ctx, models, rb));
-    GH_CHECK(s.alloc(ctx, 64));
-    GH_CHECK(mfclean_run(ctx, N, T, p.as<double>(), r.as<double>(), m.as<double>(), gain, threshold, niter, border, patch,
-                         s.as<double>(), scratch.p));
-    GH_CHECK(d2h(ctx, residuals, r.p, rb));
-    GH_CHECK(d2h(ctx, models, m.p, rb));
-    if (stats) GH_CHECK(d2h(ctx, stats, s.p, 64));
-    return sync(ctx);
+    Staged st(ctx, dev);
+    psfs = st.in(psfs, pb), residuals = st.inout(residuals, residuals, rb), models = st.inout(models, models, rb);
+    stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(mfclean_run(ctx, N, T, psfs, residuals, models, gain, threshold, niter, border, patch, stats, scratch.p));
+    return st.finish();
 }
 
 }  // namespace

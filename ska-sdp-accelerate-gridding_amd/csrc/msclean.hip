@@ -456,29 +456,15 @@ int msclean_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *psf, double
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, msclean_scratch_bytes(N, S)));
-    if (dev)
-        return msclean_run(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
-                           scratch.p, true, au);
-    const size_t bytes = (size_t)N * N * 8, sbytes = au.on ? 128 : 96;
-    DevBuf p, r, m, s, mk, nz;
-    GH_CHECK(p.upload(ctx, psf, bytes));
-    GH_CHECK(r.upload(ctx, residual, bytes));
-    GH_CHECK(m.upload(ctx, model, bytes));
-    GH_CHECK(s.alloc(ctx, sbytes));
-    if (au.mask) {
-        GH_CHECK(mk.upload(ctx, au.mask, bytes / 8));
-        au.mask = mk.as<uint8_t>();
-    }
-    if (au.nsigma > 0.0) {
-        GH_CHECK(nz.upload(ctx, au.noise, 8));
-        au.noise = nz.as<double>();
-    }
-    GH_CHECK(msclean_run(ctx, N, p.as<double>(), r.as<double>(), m.as<double>(), S, scales, bias, gain, threshold, niter,
-                         border, patch, s.as<double>(), scratch.p, true, au));
-    GH_CHECK(d2h(ctx, residual, r.p, bytes));
-    GH_CHECK(d2h(ctx, model, m.p, bytes));
-    if (stats) GH_CHECK(d2h(ctx, stats, s.p, sbytes));
-    return sync(ctx);
+    const size_t bytes = (size_t)N * N * 8;
+    Staged st(ctx, dev);
+    psf = st.in(psf, bytes), residual = st.inout(residual, residual, bytes), model = st.inout(model, model, bytes);
+    stats = st.out(stats, au.on ? 128 : 96), au.mask = st.in(au.mask, bytes / 8);
+    if (au.nsigma > 0.0) au.noise = st.in(au.noise, 8);
+    GH_CHECK(st.status());
+    GH_CHECK(msclean_run(ctx, N, psf, residual, model, S, scales, bias, gain, threshold, niter, border, patch, stats,
+                         scratch.p, true, au));
+    return st.finish();
 }
 
 }  // namespace

@@ -245,12 +245,6 @@ __global__ void __launch_bounds__(1024)
     }
 }
 
-bool overlap_bytes(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 int image_stats_check(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int64_t border,
@@ -259,8 +253,7 @@ int image_stats_check(gridhip_ctx *ctx, int64_t N, const double *image, const ui
     if (N < 1 || border < 0 || 2 * border >= N || !image || !stats) return fail(ctx, GRIDHIP_EINVAL, "image_stats: bad argument");
     if (N > CLEAN_MAX_N) return fail(ctx, GRIDHIP_EUNSUPPORTED, "image_stats: N above %lld", (long long)CLEAN_MAX_N);
     const size_t cells = (size_t)N * N;
-    if ((mask && (overlap_bytes(mask, cells, image, cells * 8) || overlap_bytes(stats, 64, mask, cells))) ||
-        overlap_bytes(stats, 64, image, cells * 8))
+    if (overlap(mask, cells, image, cells * 8) || overlap(stats, 64, mask, cells) || overlap(stats, 64, image, cells * 8))
         return fail(ctx, GRIDHIP_EINVAL, "image_stats: image, mask and stats must not overlap");
     return GRIDHIP_OK;
 }
@@ -317,15 +310,12 @@ int image_stats_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *image, 
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf scratch;
     GH_CHECK(scratch.alloc(ctx, image_stats_scratch_bytes(ctx)));
-    if (dev) return image_stats_run(ctx, N, image, mask, border, stats, scratch.p);
     const size_t cells = (size_t)N * N;
-    DevBuf im, mk, s;
-    GH_CHECK(im.upload(ctx, image, cells * 8));
-    if (mask) GH_CHECK(mk.upload(ctx, mask, cells));
-    GH_CHECK(s.alloc(ctx, 64));
-    GH_CHECK(image_stats_run(ctx, N, im.as<double>(), mask ? mk.as<uint8_t>() : nullptr, border, s.as<double>(), scratch.p));
-    GH_CHECK(d2h(ctx, stats, s.p, 64));
-    return sync(ctx);
+    Staged st(ctx, dev);
+    image = st.in(image, cells * 8), mask = st.in(mask, cells), stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(image_stats_run(ctx, N, image, mask, border, stats, scratch.p));
+    return st.finish();
 }
 
 }  // namespace

@@ -186,12 +186,6 @@ __global__ void __launch_bounds__(256)
             if (xf + j < N) restored[y * N + xf + j] = residual[y * N + xf + j] + acc[j];
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bbytes && y < x + abytes;
-}
-
 }  // namespace
 
 int fit_beam_check(gridhip_ctx *ctx, int64_t N, const double *psf, int64_t window, double cut, const double *beam)
@@ -251,13 +245,11 @@ int fit_beam_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *psf, int64
     if (!ctx) return GRIDHIP_EINVAL;
     GH_CHECK(fit_beam_check(ctx, N, psf, window, cut, beam));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (dev) return fit_beam_run(ctx, N, psf, window, cut, beam);
-    DevBuf p, b;
-    GH_CHECK(p.upload(ctx, psf, (size_t)N * N * 8));
-    GH_CHECK(b.alloc(ctx, 64));
-    GH_CHECK(fit_beam_run(ctx, N, p.as<double>(), window, cut, b.as<double>()));
-    GH_CHECK(d2h(ctx, beam, b.p, 64));
-    return sync(ctx);
+    Staged st(ctx, dev);
+    psf = st.in(psf, (size_t)N * N * 8), beam = st.out(beam, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(fit_beam_run(ctx, N, psf, window, cut, beam));
+    return st.finish();
 }
 
 int restore_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *model, const double *residual, const double *beam,
@@ -268,15 +260,14 @@ int restore_any(gridhip_ctx *ctx, bool dev, int64_t N, const double *model, cons
     if (!dev && !beam_usable(beam[0], beam[1], beam[2], beam[7]))
         return fail(ctx, GRIDHIP_EINVAL, "restore: the beam's fit failed, or A, B, C are not finite and positive definite");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (dev) return restore_run(ctx, N, model, residual, beam, support, restored);
     const size_t bytes = (size_t)N * N * 8;
-    DevBuf m, r, b;
-    GH_CHECK(m.upload(ctx, model, bytes));
-    GH_CHECK(r.upload(ctx, residual, bytes));
-    GH_CHECK(b.upload(ctx, beam, 64));
-    GH_CHECK(restore_run(ctx, N, m.as<double>(), r.as<double>(), b.as<double>(), support, r.as<double>()));
-    GH_CHECK(d2h(ctx, restored, r.p, bytes));
-    return sync(ctx);
+    Staged st(ctx, dev);
+    model = st.in(model, bytes), restored = st.inout(residual, restored, bytes);
+    if (!dev) residual = restored;  // (the staged residual is restored in place)
+    beam = st.in(beam, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(restore_run(ctx, N, model, residual, beam, support, restored));
+    return st.finish();
 }
 
 }  // namespace

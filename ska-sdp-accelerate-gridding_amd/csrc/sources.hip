@@ -345,12 +345,6 @@ __global__ void src_stats_kernel(const AmState *st, const int64_t *__restrict__ 
     stats[7] = 0.0;
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-
 }  // namespace
 
 int sources_check(gridhip_ctx *ctx, double theta, int64_t lam, const double *image, int64_t border, double thr_hi,
@@ -365,14 +359,9 @@ int sources_check(gridhip_ctx *ctx, double theta, int64_t lam, const double *ima
                                    peak_frac, min_cells));
     if (*N <= SRC_MAX_N) {  // (above it the call is refused below, and the byte counts are not needed)
         const size_t cb = (size_t)max_c * GRIDHIP_COMP_DOUBLES * 8, ib = (size_t)max_c * SRC_INFO * 8;
-        const struct {
-            const void *p;
-            size_t bytes;
-        } args[7] = {{comps, cb}, {info, ib}, {count, 8}, {stats, 64}, {image, (size_t)*N * *N * 8}, {beam, 64}, {noise, 8}};
-        for (int i = 0; i < 4; ++i)  // every output against every other argument
-            for (int j = i + 1; j < 7; ++j)
-                if (overlap(args[i].p, args[i].bytes, args[j].p, args[j].bytes))
-                    return fail(ctx, GRIDHIP_EINVAL, "find_sources: comps, info, count and stats may overlap nothing");
+        if (outputs_clash({{comps, cb}, {info, ib}, {count, 8}, {stats, 64}},
+                          {{image, (size_t)*N * *N * 8}, {beam, 64}, {noise, 8}}))
+            return fail(ctx, GRIDHIP_EINVAL, "find_sources: comps, info, count and stats may overlap nothing");
     }
     if (*N > SRC_MAX_N) return fail(ctx, GRIDHIP_EUNSUPPORTED, "find_sources: N above %d", (int)SRC_MAX_N);
     return GRIDHIP_OK;
@@ -436,31 +425,23 @@ int find_sources_any(gridhip_ctx *ctx, bool dev, double theta, int64_t lam, cons
     DevBuf am, scratch;
     GH_CHECK(am.alloc(ctx, automask_scratch_bytes(ctx, N)));
     GH_CHECK(scratch.alloc(ctx, sources_scratch_bytes(N, max_c)));
-    if (dev)
-        return sources_run(ctx, N, theta, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells,
-                           beam, correct, max_c, comps, info, count, stats, am.p, scratch.p);
-    const size_t cb = (size_t)max_c * GRIDHIP_COMP_DOUBLES * 8, ib = (size_t)max_c * SRC_INFO * 8;
-    DevBuf im, nz, bm, dc, di, dn, ds;
-    GH_CHECK(im.upload(ctx, image, (size_t)N * N * 8));
-    if (noise) GH_CHECK(nz.upload(ctx, noise, 8));
-    if (beam) GH_CHECK(bm.upload(ctx, beam, 64));
-    GH_CHECK(dc.alloc(ctx, cb));
-    if (info) GH_CHECK(di.alloc(ctx, ib));
-    GH_CHECK(dn.alloc(ctx, 8));
-    GH_CHECK(ds.alloc(ctx, 64));
-    GH_CHECK(sources_run(ctx, N, theta, im.as<double>(), border, thr_hi, thr_lo, nsigma_hi, nsigma_lo,
-                         noise ? nz.as<double>() : nullptr, peak_frac, min_cells, beam ? bm.as<double>() : nullptr, correct,
-                         max_c, dc.as<double>(), info ? di.as<double>() : nullptr, dn.as<int64_t>(), ds.as<double>(), am.p,
-                         scratch.p));
-    int64_t found = 0;
-    GH_CHECK(d2h(ctx, &found, dn.p, 8));
-    GH_CHECK(d2h(ctx, stats, ds.p, 64));
-    GH_CHECK(sync(ctx));
+    Staged st(ctx, dev);
+    image = st.in(image, (size_t)N * N * 8), noise = st.in(noise, 8), beam = st.in(beam, 64);
+    double *dc = st.raw(comps, (size_t)max_c * GRIDHIP_COMP_DOUBLES * 8), *di = st.raw(info, (size_t)max_c * SRC_INFO * 8);
+    int64_t *dn = st.raw(count, 8);
+    double *ds = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(sources_run(ctx, N, theta, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam,
+                         correct, max_c, dc, di, dn, ds, am.p, scratch.p));
+    if (dev) return GRIDHIP_OK;
     // only the rows written come back: the caller's rows after them stay as they were
-    const size_t rows = (size_t)(found < max_c ? found : max_c);
-    GH_CHECK(d2h(ctx, comps, dc.p, rows * GRIDHIP_COMP_DOUBLES * 8));
-    if (info) GH_CHECK(d2h(ctx, info, di.p, rows * SRC_INFO * 8));
+    int64_t found = 0;
+    GH_CHECK(d2h(ctx, &found, dn, 8));
     GH_CHECK(sync(ctx));
+    const size_t rows = (size_t)(found < max_c ? found : max_c);
+    GH_CHECK(d2h(ctx, comps, dc, rows * GRIDHIP_COMP_DOUBLES * 8));
+    if (info) GH_CHECK(d2h(ctx, info, di, rows * SRC_INFO * 8));
+    GH_CHECK(st.finish());
     *count = found;
     return GRIDHIP_OK;
 }

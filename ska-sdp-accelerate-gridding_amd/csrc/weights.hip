@@ -249,12 +249,6 @@ __global__ void __launch_bounds__(256)
     stats[7] = tot[5];
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
@@ -318,9 +312,6 @@ using namespace gridhip;
 
 namespace {
 
-// the bytes a strided column of n doubles spans
-size_t span(int64_t n, int64_t stride) { return n > 0 ? ((size_t)(n - 1) * stride + 1) * 8 : 0; }
-
 // gridhip_weights' argument rules; *N = the image size
 int weights_check(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, const double *u, const double *v, int64_t stride,
                   int mode, double robust, double sigma, const double *wt_out, int64_t *N)
@@ -329,7 +320,7 @@ int weights_check(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, const 
     if (*N < 1 || n < 0 || stride < 1 || (n > 0 && (!u || !v || !wt_out)))
         return fail(ctx, GRIDHIP_EINVAL, "weights: bad argument");
     GH_CHECK(weights_mode_check(ctx, mode, robust, sigma));
-    if (overlap(wt_out, (size_t)n * 8, u, span(n, stride)) || overlap(wt_out, (size_t)n * 8, v, span(n, stride)))
+    if (overlaps_any({wt_out, (size_t)n * 8}, {{u, span_bytes(n, stride)}, {v, span_bytes(n, stride)}}))
         return fail(ctx, GRIDHIP_EINVAL, "weights: wt_out may be wt_in itself, and overlap neither u nor v");
     return GRIDHIP_OK;
 }
@@ -357,6 +348,22 @@ int weights_run(gridhip_ctx *ctx, int64_t N, double lam, int64_t n, const double
                           stats);
 }
 
+int weights_any(gridhip_ctx *ctx, bool dev, double theta, int64_t lam, int64_t n, const double *u, const double *v,
+                int64_t uv_stride, const double *wt_in, int mode, double robust, double taper_sigma, double *wt_out,
+                double *stats)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    int64_t N = 0;
+    GH_CHECK(weights_check(ctx, theta, lam, n, u, v, uv_stride, mode, robust, taper_sigma, wt_out, &N));
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    Staged st(ctx, dev);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), wt_in = st.in(wt_in, (size_t)n * 8);
+    wt_out = st.out(wt_out, (size_t)n * 8), stats = st.out(stats, 64);
+    GH_CHECK(st.status());
+    GH_CHECK(weights_run(ctx, N, (double)lam, n, u, v, uv_stride, wt_in, mode, robust, taper_sigma, wt_out, stats));
+    return st.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -365,32 +372,14 @@ int gridhip_weights_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, 
                         int64_t uv_stride, const double *wt_in, int mode, double robust, double taper_sigma, double *wt_out,
                         double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    int64_t N = 0;
-    GH_CHECK(weights_check(ctx, theta, lam, n, u, v, uv_stride, mode, robust, taper_sigma, wt_out, &N));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return weights_run(ctx, N, (double)lam, n, u, v, uv_stride, wt_in, mode, robust, taper_sigma, wt_out, stats);
+    return weights_any(ctx, true, theta, lam, n, u, v, uv_stride, wt_in, mode, robust, taper_sigma, wt_out, stats);
 }
 
 int gridhip_weights(gridhip_ctx *ctx, double theta, int64_t lam, int64_t n, const double *u, const double *v,
                     int64_t uv_stride, const double *wt_in, int mode, double robust, double taper_sigma, double *wt_out,
                     double *stats)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
-    int64_t N = 0;
-    GH_CHECK(weights_check(ctx, theta, lam, n, u, v, uv_stride, mode, robust, taper_sigma, wt_out, &N));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf du, dv, ds, dw, dst;
-    GH_CHECK(du.upload(ctx, u, span(n, uv_stride)));
-    GH_CHECK(dv.upload(ctx, v, span(n, uv_stride)));
-    if (wt_in) GH_CHECK(ds.upload(ctx, wt_in, (size_t)n * 8));
-    GH_CHECK(dw.alloc(ctx, (size_t)n * 8));
-    GH_CHECK(dst.alloc(ctx, 64));
-    GH_CHECK(weights_run(ctx, N, (double)lam, n, du.as<double>(), dv.as<double>(), uv_stride,
-                         wt_in ? ds.as<double>() : nullptr, mode, robust, taper_sigma, dw.as<double>(), dst.as<double>()));
-    GH_CHECK(d2h(ctx, wt_out, dw.p, (size_t)n * 8));
-    if (stats) GH_CHECK(d2h(ctx, stats, dst.p, 64));
-    return sync(ctx);
+    return weights_any(ctx, false, theta, lam, n, u, v, uv_stride, wt_in, mode, robust, taper_sigma, wt_out, stats);
 }
 
 }  // extern "C"

@@ -116,6 +116,65 @@ def test_phase_shift_of_coordinates_in_place_and_a_nan_coordinate(ctx):
     check_shift("all in place", (host(dv), host(m)), want, vis)
 
 
+@pytest.mark.parametrize("stride", [1, 3])
+@pytest.mark.parametrize("n", [0, 1, 257])  # none, one, one work-group and one
+def test_phase_shift_host_and_device_forms_give_the_same_bits(ctx, n, stride):
+    """Every staging branch of gridhip_phase_shift: w, the coordinate outputs and stats present and null, the outputs at
+    stride 1 and 3, vis and the coordinates out of place and in place.  One rounded sequence per visibility: the two forms
+    give the same bits, and both agree with the reference as in the tests above."""
+    rng = np.random.default_rng(500 + 10 * n + stride)
+    R = np.ascontiguousarray(rot(0.03, -0.02), dtype=f64)
+    u, v, w = coords(rng, n)
+    vis = noise(rng, n)
+    Rp = R.ctypes.data_as(C.POINTER(C.c_double))
+    for with_w in (True, False):
+        want = A.phase_shift(R, u, v, w if with_w else None, vis)
+        for outs in ("none", "new", "in place"):
+            for in_place in (False, True):
+                for with_stats in (True, False):
+                    # the three columns in one array: interleaved (stride 3) or one after the other (stride 1)
+                    m = np.stack([u, v, w], axis=1 if stride == 3 else 0)
+                    flat, off = m.reshape(-1).copy(), [0, 1, 2] if stride == 3 else [0, n, 2 * n]
+                    vin = vis.copy()
+                    vout = vin if in_place else np.full(n, 7 - 7j)
+                    os_ = stride if outs == "in place" else 3
+                    o = None if outs == "none" else flat if outs == "in place" else np.full(3 * max(n, 1), 7.0)
+                    ooff = off if outs == "in place" else [0, 1, 2]
+                    st = np.full(4, 7.0) if with_stats else None
+                    hst, dvc = _shift_both(ctx, n, Rp, flat, off, with_w, stride, vin, vout, o, ooff, os_, st)
+                    what = (n, stride, with_w, outs, in_place, with_stats)
+                    for k in hst:
+                        assert hst[k].tobytes() == dvc[k].tobytes(), what
+                    uvw = None
+                    if o is not None:
+                        got = hst[id(o)]
+                        uvw = np.stack([got[ooff[j]:ooff[j] + (n - 1) * os_ + 1:os_] if n else got[:0] for j in range(3)], axis=1)
+                    check_shift(str(what), (hst[id(vout)], uvw), want, vis)
+                    if st is not None:
+                        assert hst[id(st)].tolist() == [n, 0, 0, 0], what
+
+
+def _shift_both(ctx, n, Rp, flat, off, with_w, stride, vin, vout, o, ooff, os_, st):
+    """gridhip_phase_shift and its _dev form on pointers into `flat` (and into `o`) at the given offsets in doubles"""
+    import torch
+    from gridhip._marshal import device
+    lib, h = ctx._lib, ctx._h
+    arrays = {id(a): a for a in (flat, vin, vout, o, st) if a is not None}
+    hst = {k: a.copy() for k, a in arrays.items()}
+    dvc = {k: to_dev(a if a.size else np.zeros(4, a.dtype)) for k, a in arrays.items()}  # (an empty tensor has no address)
+    for base, ptr in ((hst, lambda a: a.ctypes.data), (dvc, lambda t: t.data_ptr())):
+        at = lambda a, k=0: None if a is None else C.c_void_p(ptr(base[id(a)]) + 8 * k)  # noqa: E731
+        args = [n, Rp, at(flat, off[0]), at(flat, off[1]), at(flat, off[2]) if with_w else None, stride, at(vin), at(vout),
+                at(o, ooff[0]), at(o, ooff[1]), at(o, ooff[2]), os_, at(st)]
+        if base is hst:
+            assert lib.gridhip_phase_shift(h, *args) == 0
+        else:
+            device().bind(ctx)
+            assert lib.gridhip_phase_shift_dev(h, *args) == 0
+            torch.cuda.synchronize()
+    return hst, {k: host(t)[:arrays[k].size] for k, t in dvc.items()}
+
+
 def test_refusals(ctx):
     """every rule of the header that needs a context; nothing is touched by a refused call"""
     import torch

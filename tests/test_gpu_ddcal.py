@@ -340,6 +340,37 @@ def test_subtract_every_subset_in_place_no_input_and_rows_out_of_range(ctx):
     assert one.shape == (n,)
 
 
+@pytest.mark.parametrize("n", [0, 1, 257])  # none, one, one work-group and one
+def test_subtract_host_and_device_forms_give_the_same_bits(ctx, n):
+    """Every staging branch of gridhip_dd_subtract: slot and vis_in present and null, out of place and in place.  The
+    subtraction is a fixed sequence of rounded operations per visibility, so the two forms give the same bits; the
+    restatement holds within the 1e-12 of the largest visibility of the test above."""
+    from test_gpu_gaincal import both_forms
+    rng = np.random.default_rng(400 + n)
+    A, T, D = 3, 2, 2
+    a1, a2, sl, V, M, _ = stream(rng, n, A, T, D)
+    M = np.ascontiguousarray(M)
+    g = (1 + 0.3 * rng.normal(size=(D, T, A))) * np.exp(1j * rng.uniform(-2, 2, (D, T, A)))
+    for slot in (sl, None):
+        gg = g if slot is not None else np.ascontiguousarray(g[:, :1])
+        for given in (True, False):
+            for in_place in ((False, True) if given else (False,)):
+                for dirs in ([0, 1], [1]):
+                    vin = V.copy() if given else None
+                    vout = vin if in_place else np.full(n, 7 - 7j)
+                    bits = sum(1 << d for d in dirs)
+                    hst, dvc = both_forms(ctx, "dd_subtract", [n, A, gg.shape[1], D, a1, a2, slot, gg, M, bits, vin, vout])
+                    what = (n, slot is not None, given, in_place, dirs)
+                    for k in hst:
+                        assert hst[k].tobytes() == dvc[k].tobytes(), what
+                    for x in (a1, a2, gg, M) + ((vin,) if given and not in_place else ()):
+                        assert hst[id(x)].tobytes() == x.tobytes(), what  # inputs as they were
+                    want = R.dd_subtract(gg, M, a1, a2, slot=slot, directions=dirs, vis=vin if given else None)
+                    if n:
+                        scale = np.abs(V).max() if given else np.abs(want).max()
+                        assert np.abs(hst[id(vout)] - want).max() <= 1e-12 * scale, what
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------------
 def test_refusals(ctx):
     """Every rule of the header, through the C ABI on device memory: GRIDHIP_EINVAL and the outputs as they were given."""

@@ -289,6 +289,57 @@ def test_apply_both_directions_in_place_and_unusable_gains(ctx):
     assert np.allclose(w1, R.apply_gains(good, V, a1, a2, slot=sl)[1], rtol=1e-14, atol=0)
 
 
+def both_forms(ctx, name, scalars_and_arrays):
+    """gridhip_<name> on numpy arrays and gridhip_<name>_dev on device copies of them, through the C ABI.  An argument is a
+    scalar, None, or a numpy array; an array that occurs twice (an output that is its own input) is one array on the
+    device too.  -> ({id: the host array after the call}, {id: the device copy after the call, brought back})"""
+    import torch
+    from gridhip._marshal import device
+    lib, h = ctx._lib, ctx._h
+    arrays = {id(a): a for a in scalars_and_arrays if isinstance(a, np.ndarray)}
+    hst = {k: a.copy() for k, a in arrays.items()}
+    dvc = {k: to_dev(a if a.size else np.zeros(1, a.dtype)) for k, a in arrays.items()}  # (an empty tensor has no address)
+    hp = lambda a: C.c_void_p(hst[id(a)].ctypes.data) if isinstance(a, np.ndarray) else a  # noqa: E731
+    dp = lambda a: C.c_void_p(dvc[id(a)].data_ptr()) if isinstance(a, np.ndarray) else a  # noqa: E731
+    assert getattr(lib, "gridhip_" + name)(h, *[hp(a) for a in scalars_and_arrays]) == 0
+    device().bind(ctx)
+    assert getattr(lib, "gridhip_" + name + "_dev")(h, *[dp(a) for a in scalars_and_arrays]) == 0
+    torch.cuda.synchronize()
+    return hst, {k: host(t).reshape(-1)[:arrays[k].size].reshape(arrays[k].shape) for k, t in dvc.items()}
+
+
+@pytest.mark.parametrize("n", [0, 1, 257])  # none, one, one work-group and one
+def test_apply_host_and_device_forms_give_the_same_bits(ctx, n):
+    """Every staging branch of gridhip_apply_gains: slot, wt_in and wt_out present and null, out of place and in place.
+    The correction is one rounded expression per visibility, so the two forms give the same bits; the restatement rounds
+    its products in another order, so it holds within the bounds of the test above (1e-12 of the largest, 1e-14 relative)."""
+    rng = np.random.default_rng(300 + n)
+    A, T = 3, 2
+    a1, a2, sl, V, _, w = stream(rng, n, A, T)
+    g = (1 + 0.3 * rng.normal(size=(T, A))) * np.exp(1j * rng.uniform(-2, 2, (T, A)))
+    for slot in (sl, None):
+        gg = g if slot is not None else g[:1].copy()
+        for wt in (w, None):
+            for want_wo in (True, False):
+                for in_place in (False, True):
+                    for inverse in (1, 0):
+                        vin = V.copy()
+                        vout = vin if in_place else np.full(n, 7 - 7j)
+                        wi = None if wt is None else wt.copy()
+                        wo = None if not want_wo else wi if in_place and wi is not None else np.full(n, 7.0)
+                        hst, dvc = both_forms(ctx, "apply_gains", [n, A, len(gg), a1, a2, slot, gg, inverse, vin, wi, vout, wo])
+                        what = (n, slot is not None, wt is not None, want_wo, in_place, inverse)
+                        for k in hst:
+                            assert hst[k].tobytes() == dvc[k].tobytes(), what
+                        for x in (a1, a2, gg) + (() if in_place else (vin,)):
+                            assert hst[id(x)].tobytes() == x.tobytes(), what  # inputs as they were
+                        vr, wr = R.apply_gains(gg, V, a1, a2, slot=slot, wt=wt, inverse=bool(inverse))
+                        if n:
+                            assert np.abs(hst[id(vout)] - vr).max() <= 1e-12 * np.abs(vr).max(), what
+                        if wo is not None:
+                            assert np.allclose(hst[id(wo)], wr, rtol=1e-14, atol=0), what
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------
 def test_refusals(ctx):
     """Every rule of the header, through the C ABI on device memory: GRIDHIP_EINVAL and the outputs as they were given."""
