@@ -1,5 +1,6 @@
-// C-ABI entry points of the gridders (include/gridhip.h): argument checks, the device-pointer
-// forms that enqueue the kernels, and the host-pointer drop-in forms that stage through pooled device blocks.
+// C-ABI entry points of the gridders (include/gridhip.h): argument checks, the device-pointer forms that enqueue the
+// kernels - one pass of the tile kernels is tile_pass, for plans and the aw gridders too - and the host-pointer drop-in
+// forms, which stage their arguments (Staged, imaging.h) and run the device-pointer form on them.
 
 #include "common.h"
 #include "imaging.h"
@@ -20,6 +21,16 @@ int check_common(gridhip_ctx *ctx, int64_t H, int64_t Wd, const void *grid, int6
     return GRIDHIP_OK;
 }
 
+// the check of a convolutional call, both directions and both forms (vis: the visibilities or the predictions)
+int check_conv2(gridhip_ctx *ctx, int64_t H, int64_t Wd, const void *grid, int64_t n, const void *u, const void *v,
+                int64_t uv_stride, const void *gcf, const void *vis, int64_t W, int64_t Q, int64_t gh, int64_t gw)
+{
+    GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
+    if (!gcf || (n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
+    if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
+    return GRIDHIP_OK;
+}
+
 // the host-pointer forms are synchronous: an internal consistency failure of the call (a record that did not fit
 // the record array, a slice index outside the kernel table - the caller's arrays changed during the call, or a
 // bug) is reported instead of a silently incomplete grid
@@ -32,6 +43,26 @@ int check_errors(gridhip_ctx *ctx)
     return GRIDHIP_OK;
 }
 
+// A record is one 64-bit word: 14 bits of footprint origin, the kernel slice, the visibility's index.  A call whose
+// slices x visibilities exceed 2^50 (no realistic one does: 10^8 visibilities leave room for 8 x 10^6 slices) is
+// gridded in several parts - gridding and degridding are both sums / maps over visibilities.  Returns the
+// visibilities per part, 0 when the call fits, < 0 when no part size does.  Option "rec_bits" (test hook) lowers the
+// word's width so that small cases take this path.  (gridhip_last_dropped and "errors" then report the last part's.)
+int64_t part_size(gridhip_ctx *ctx, const Prep &p)
+{
+    const int limit = ctx->opt.rec_bits >= 16 && ctx->opt.rec_bits < 64 ? (int)ctx->opt.rec_bits : 64;
+    if (p.direct || rec_fits(p.g, limit)) return 0;
+    const int room = limit - 14 - p.g.kb;
+    return room >= 1 ? (int64_t)1 << room : -1;
+}
+// the parts of such a call: one(lo, m) on the visibilities [lo, lo + m) of [0, n), m <= part (part_size's, not 0)
+template <typename One>
+int in_parts(gridhip_ctx *ctx, int64_t n, int64_t part, One one)
+{
+    if (part < 0) return fail(ctx, GRIDHIP_EUNSUPPORTED, "kernel table with too many slices");
+    for (int64_t lo = 0; lo < n; lo += part) GH_CHECK(one(lo, part < n - lo ? part : n - lo));
+    return GRIDHIP_OK;
+}
 
 // kernel table -> zero-padded square parts: out[(slice * P + part)][sub][sub] (Geom, "Sub-footprints")
 __global__ void __launch_bounds__(256) pad_kernels_kernel(Geom g, int64_t nslices, const double2 *__restrict__ in,
@@ -155,23 +186,15 @@ int tile_kernels(gridhip_ctx *ctx, const Prep &p, const double *gcf, const doubl
     return GRIDHIP_OK;
 }
 
-int upload_inputs(gridhip_ctx *ctx, GridInputs &d, size_t cells, const double *grid, int64_t n, int64_t uv_stride,
-                  const double *u, const double *v, const double *vis, const int64_t *wbin, const double *gcf,
-                  size_t gcf_elems)
+// (gridding reads vis and writes grid, degridding the other way round: the const of the one it writes is cast away here)
+int tile_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t nrec, const double *table, const double *vis,
+              const double *grid, bool degrid)
 {
-    if (grid) {
-        GH_CHECK(d.grid.upload(ctx, grid, cells * 16));
-    } else {
-        GH_CHECK(d.grid.alloc(ctx, cells * 16));
-        GH_CHECK_HIP(ctx, hipMemsetAsync(d.grid.p, 0, cells * 16, ctx->stream));
-    }
-    const size_t span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 0;
-    GH_CHECK(d.u.upload(ctx, u, span * 8));
-    GH_CHECK(d.v.upload(ctx, v, span * 8));
-    GH_CHECK(vis ? d.vis.upload(ctx, vis, (size_t)n * 16) : d.vis.alloc(ctx, (size_t)n * 16));
-    if (wbin) GH_CHECK(d.wbin.upload(ctx, wbin, (size_t)n * 8));
-    if (gcf) GH_CHECK(d.gcf.upload(ctx, gcf, gcf_elems * 16));
-    return GRIDHIP_OK;
+    if (p.sorted)  // the sorted kernel's degrid mode reads `grid` and writes the vis array
+        return launch_tile_grid_sorted(ctx, g, p.block, p.lds_sorted, p.nkeys, p.batch, nrec, table, vis,
+                                       const_cast<double *>(grid), degrid);
+    if (degrid) return launch_tile_degrid(ctx, g, p.block, p.lds, nrec, table, grid, const_cast<double *>(vis));
+    return launch_tile_grid(ctx, g, p.block, p.lds, nrec, table, vis, const_cast<double *>(grid));
 }
 
 }  // namespace gridhip
@@ -191,39 +214,22 @@ int gridhip_grid_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int6
     return GRIDHIP_OK;
 }
 
-// A record is one 64-bit word: 14 bits of footprint origin, the kernel slice, the visibility's index.  A call whose
-// slices x visibilities exceed 2^50 (no realistic one does: 10^8 visibilities leave room for 8 x 10^6 slices) is
-// gridded in several parts - gridding and degridding are both sums / maps over visibilities.  Returns the
-// visibilities per part, 0 when the call fits, < 0 when no part size does.  Option "rec_bits" (test hook) lowers the
-// word's width so that small cases take this path.  (gridhip_last_dropped and "errors" then report the last part's.)
-static int64_t part_size(gridhip_ctx *ctx, const Prep &p)
-{
-    const int limit = ctx->opt.rec_bits >= 16 && ctx->opt.rec_bits < 64 ? (int)ctx->opt.rec_bits : 64;
-    if (p.direct || rec_fits(p.g, limit)) return 0;
-    const int room = limit - 14 - p.g.kb;
-    return room >= 1 ? (int64_t)1 << room : -1;
-}
-
 int gridhip_convgrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t W, int64_t Q,
                           int64_t gh, int64_t gw, const double *gcf, const double *u, const double *v,
                           int64_t uv_stride, const int64_t *wbin, const double *vis)
 {
-    GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
-    if (!gcf || (n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
-    if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
+    GH_CHECK(check_conv2(ctx, H, Wd, grid, n, u, v, uv_stride, gcf, vis, W, Q, gh, gw));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     Prep p;
     if (ctx->opt.variant == 1)
         p.direct = true;
     else
         GH_CHECK(prepare(ctx, H, Wd, W, Q, gh, gw, n, &p));
-    if (const int64_t part = part_size(ctx, p)) {
-        if (part < 0) return fail(ctx, GRIDHIP_EUNSUPPORTED, "kernel table with too many slices");
-        for (int64_t lo = 0; lo < n; lo += part)
-            GH_CHECK(gridhip_convgrid2_dev(ctx, H, Wd, grid, part < n - lo ? part : n - lo, W, Q, gh, gw, gcf, u + lo * uv_stride,
-                                           v + lo * uv_stride, uv_stride, wbin ? wbin + lo : nullptr, vis + 2 * lo));
-        return GRIDHIP_OK;
-    }
+    if (const int64_t part = part_size(ctx, p))
+        return in_parts(ctx, n, part, [&](int64_t lo, int64_t m) {
+            return gridhip_convgrid2_dev(ctx, H, Wd, grid, m, W, Q, gh, gw, gcf, u + lo * uv_stride, v + lo * uv_stride,
+                                         uv_stride, wbin ? wbin + lo : nullptr, vis + 2 * lo);
+        });
     if (p.direct) {
         ctx->last_path = 4;
         mark(ctx, 0);
@@ -240,12 +246,7 @@ int gridhip_convgrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid,
     GH_CHECK(tile_kernels(ctx, p, gcf, &tk));
     GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, nullptr, true));
     mark(ctx, 1);
-    if (n > 0) {
-        if (p.sorted)
-            GH_CHECK(launch_tile_grid_sorted(ctx, p.g, p.block, p.lds_sorted, p.nkeys, p.batch, p.nrec, tk, vis, grid, false));
-        else
-            GH_CHECK(launch_tile_grid(ctx, p.g, p.block, p.lds, p.nrec, tk, vis, grid));
-    }
+    if (n > 0) GH_CHECK(tile_pass(ctx, p, p.g, p.nrec, tk, vis, grid, false));
     mark(ctx, 2);
     return GRIDHIP_OK;
 }
@@ -262,20 +263,16 @@ int gridhip_degrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *g
                         int64_t Q, int64_t gh, int64_t gw, const double *gcf, const double *u, const double *v,
                         int64_t uv_stride, const int64_t *wbin, double *vis_out)
 {
-    GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
-    if (!gcf || (n > 0 && !vis_out)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
-    if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
+    GH_CHECK(check_conv2(ctx, H, Wd, grid, n, u, v, uv_stride, gcf, vis_out, W, Q, gh, gw));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     Prep p;
     GH_CHECK(prepare(ctx, H, Wd, W, Q, gh, gw, n, &p));
     if (p.direct) return fail(ctx, GRIDHIP_EUNSUPPORTED, "degrid2: support %lldx%lld too large for an LDS tile", (long long)gh, (long long)gw);
-    if (const int64_t part = part_size(ctx, p)) {
-        if (part < 0) return fail(ctx, GRIDHIP_EUNSUPPORTED, "kernel table with too many slices");
-        for (int64_t lo = 0; lo < n; lo += part)
-            GH_CHECK(gridhip_degrid2_dev(ctx, H, Wd, grid, part < n - lo ? part : n - lo, W, Q, gh, gw, gcf, u + lo * uv_stride,
-                                         v + lo * uv_stride, uv_stride, wbin ? wbin + lo : nullptr, vis_out + 2 * lo));
-        return GRIDHIP_OK;
-    }
+    if (const int64_t part = part_size(ctx, p))
+        return in_parts(ctx, n, part, [&](int64_t lo, int64_t m) {
+            return gridhip_degrid2_dev(ctx, H, Wd, grid, m, W, Q, gh, gw, gcf, u + lo * uv_stride, v + lo * uv_stride,
+                                       uv_stride, wbin ? wbin + lo : nullptr, vis_out + 2 * lo);
+        });
     GH_CHECK(ws_reserve(ctx, ctx->tables, tables_bytes(p.g)));
     GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)(p.nrec > 0 ? p.nrec : 1) * sizeof(RecWord)));
     mark(ctx, 0);
@@ -288,13 +285,7 @@ int gridhip_degrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *g
     GH_CHECK(tile_kernels(ctx, p, gcf, &tk));
     GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, parts ? nullptr : reinterpret_cast<double2 *>(vis_out), true));
     mark(ctx, 1);
-    if (n > 0) {
-        if (p.sorted)  // the sorted kernel's degrid mode reads `grid` and writes the vis array
-            GH_CHECK(launch_tile_grid_sorted(ctx, p.g, p.block, p.lds_sorted, p.nkeys, p.batch, p.nrec, tk, vis_out,
-                                             const_cast<double *>(grid), true));
-        else
-            GH_CHECK(launch_tile_degrid(ctx, p.g, p.block, p.lds, p.nrec, tk, grid, vis_out));
-    }
+    if (n > 0) GH_CHECK(tile_pass(ctx, p, p.g, p.nrec, tk, vis_out, grid, true));
     mark(ctx, 2);
     return GRIDHIP_OK;
 }
@@ -304,7 +295,7 @@ int gridhip_degrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *g
 extern "C" {
 
 // ---------------------------------------------------------------------------------------------
-// host-pointer forms: the inputs go up into blocks of the context's pool (DevBuf), the _dev form runs on them, the
+// host-pointer forms: the arguments go up into blocks of the context's pool (Staged), the _dev form runs on them, the
 // result comes back
 
 int gridhip_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, const double *u,
@@ -313,31 +304,28 @@ int gridhip_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t 
     GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
     if (n > 0 && !vis) return fail(ctx, GRIDHIP_EINVAL, "null vis");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd;
-    GridInputs d;
-    GH_CHECK(upload_inputs(ctx, d, cells, grid, n, uv_stride, u, v, vis, nullptr, nullptr, 0));
-    GH_CHECK(gridhip_grid_dev(ctx, H, Wd, d.grid.as<double>(), n, d.u.as<double>(), d.v.as<double>(), uv_stride,
-                              d.vis.as<double>()));
-    GH_CHECK(d2h(ctx, grid, d.grid.p, cells * 16));
-    return sync(ctx);
+    Staged st(ctx, false);
+    grid = st.inout(grid, grid, (size_t)H * Wd * 16);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis = st.in(vis, (size_t)n * 16);
+    GH_CHECK(st.status());
+    GH_CHECK(gridhip_grid_dev(ctx, H, Wd, grid, n, u, v, uv_stride, vis));
+    return st.finish();
 }
 
 int gridhip_convgrid2(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t W, int64_t Q,
                       int64_t gh, int64_t gw, const double *gcf, const double *u, const double *v,
                       int64_t uv_stride, const int64_t *wbin, const double *vis)
 {
-    GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
-    if (!gcf || (n > 0 && !vis)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
-    if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
+    GH_CHECK(check_conv2(ctx, H, Wd, grid, n, u, v, uv_stride, gcf, vis, W, Q, gh, gw));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)H * Wd;
-    GridInputs d;
-    GH_CHECK(upload_inputs(ctx, d, cells, grid, n, uv_stride, u, v, vis, wbin, gcf, (size_t)W * Q * Q * gh * gw));
-    GH_CHECK(gridhip_convgrid2_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, gh, gw, d.gcf.as<double>(), d.u.as<double>(),
-                                   d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), d.vis.as<double>()));
+    Staged st(ctx, false);
+    grid = st.inout(grid, grid, (size_t)H * Wd * 16);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis = st.in(vis, (size_t)n * 16);
+    wbin = st.in(wbin, (size_t)n * 8), gcf = st.in(gcf, (size_t)W * Q * Q * gh * gw * 16);
+    GH_CHECK(st.status());
+    GH_CHECK(gridhip_convgrid2_dev(ctx, H, Wd, grid, n, W, Q, gh, gw, gcf, u, v, uv_stride, wbin, vis));
     if (ctx->opt.variant != 1) GH_CHECK(check_errors(ctx));  // (before the grid is handed back)
-    GH_CHECK(d2h(ctx, grid, d.grid.p, cells * 16));
-    return sync(ctx);
+    return st.finish();
 }
 
 int gridhip_convgrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n, int64_t Q, int64_t gh,
@@ -351,17 +339,16 @@ int gridhip_degrid2(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid,
                     int64_t gh, int64_t gw, const double *gcf, const double *u, const double *v, int64_t uv_stride,
                     const int64_t *wbin, double *vis_out)
 {
-    GH_CHECK(check_common(ctx, H, Wd, grid, n, u, v, uv_stride));
-    if (!gcf || (n > 0 && !vis_out)) return fail(ctx, GRIDHIP_EINVAL, "null pointer");
-    if (W <= 0 || Q <= 0 || gh <= 0 || gw <= 0) return fail(ctx, GRIDHIP_EINVAL, "bad kernel shape");
+    GH_CHECK(check_conv2(ctx, H, Wd, grid, n, u, v, uv_stride, gcf, vis_out, W, Q, gh, gw));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    GridInputs d;
-    GH_CHECK(upload_inputs(ctx, d, (size_t)H * Wd, grid, n, uv_stride, u, v, nullptr, wbin, gcf, (size_t)W * Q * Q * gh * gw));
-    GH_CHECK(gridhip_degrid2_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, gh, gw, d.gcf.as<double>(), d.u.as<double>(),
-                                 d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), d.vis.as<double>()));
+    Staged st(ctx, false);
+    grid = st.in(grid, (size_t)H * Wd * 16);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis_out = st.out(vis_out, (size_t)n * 16);
+    wbin = st.in(wbin, (size_t)n * 8), gcf = st.in(gcf, (size_t)W * Q * Q * gh * gw * 16);
+    GH_CHECK(st.status());
+    GH_CHECK(gridhip_degrid2_dev(ctx, H, Wd, grid, n, W, Q, gh, gw, gcf, u, v, uv_stride, wbin, vis_out));
     GH_CHECK(check_errors(ctx));
-    GH_CHECK(d2h(ctx, vis_out, d.vis.p, (size_t)n * 16));
-    return sync(ctx);
+    return st.finish();
 }
 
 }  // extern "C"

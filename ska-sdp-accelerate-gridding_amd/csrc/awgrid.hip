@@ -633,18 +633,6 @@ static int aw_bin(gridhip_ctx *ctx, const AwCall &c, const Geom &g, int64_t lo, 
     return GRIDHIP_OK;
 }
 
-// ---- a pass over one batch's binned records (ctx->recs / ctx->tables) and kernel table: gridding adds vis x kernels
-// onto grid; degridding writes the batch's predictions (vis = vis_out, grid read)
-static int aw_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t m, const double2 *table, const double *vis,
-                   double *grid, bool degrid)
-{
-    if (p.sorted)
-        return launch_tile_grid_sorted(ctx, g, p.block, p.lds_sorted, p.nkeys, p.batch, m, (const double *)table, vis, grid,
-                                       degrid);
-    if (degrid) return launch_tile_degrid(ctx, g, p.block, p.lds, m, (const double *)table, grid, const_cast<double *>(vis));
-    return launch_tile_grid(ctx, g, p.block, p.lds, m, (const double *)table, vis, grid);
-}
-
 // The argument check of the aw entry points: sizes, and the arrays given (has_grid / has_vis: the entry point's grid
 // and vis, where it takes them).  A refused call touches nothing.
 static int aw_args_ok(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t S, int64_t A,
@@ -705,10 +693,11 @@ static int aw_batches(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double
         p.g.nvis = (int32_t)m;
         p.g.nrec = (int32_t)m;
         GH_CHECK(aw_bin(ctx, c, p.g, lo, m, u, v, uv_stride, vis_out));
-        if (degrid)
-            GH_CHECK(aw_pass(ctx, p, p.g, m, c.table, vis_out + 2 * lo, const_cast<double *>(dgrid), true));
-        for (int i = 0; i < npass && !degrid; ++i)  // (the tile kernels' errors of every pass land in [2] before the account)
-            GH_CHECK(aw_pass(ctx, p, p.g, m, c.table, viss[i] + 2 * lo, grids[i], false));
+        // a pass over the batch's binned records and kernel table: the gather writes the batch's predictions, gridding
+        // adds each pair's vis x kernels onto its grid (the tile kernels' errors of every pass land in [2] before the account)
+        const double *table = (const double *)c.table;
+        if (degrid) GH_CHECK(tile_pass(ctx, p, p.g, m, table, vis_out + 2 * lo, dgrid, true));
+        for (int i = 0; i < npass && !degrid; ++i) GH_CHECK(tile_pass(ctx, p, p.g, m, table, viss[i] + 2 * lo, grids[i], false));
         hipLaunchKernelGGL(aw_account_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scalars, c.counters, c.cache, (int32_t)m);
         mark(ctx, 2);
     }
@@ -729,7 +718,7 @@ int awgrid_pairs(gridhip_ctx *ctx, int64_t H, int64_t Wd, int npass, double *con
 }  // namespace gridhip
 
 // An aw plan: per batch of visibilities its binned records, bin / work tables and the table of its distinct kernels,
-// built once; passes lend them to the tile kernels one batch at a time (plan.hip's Lend).
+// built once; passes lend them to the tile kernels one batch at a time (LendScratch).
 struct gridhip_aw_plan {
     gridhip_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -755,22 +744,6 @@ bool aw_plan_caller_clears(gridhip_aw_plan *plan)
 }  // namespace gridhip
 
 namespace {
-// the launchers read the binned data from the context's scratch slots: lend them a batch's
-struct AwLend {
-    gridhip_ctx *ctx;
-    gridhip_aw_plan::Batch &b;
-    AwLend(gridhip_ctx *c, gridhip_aw_plan::Batch &bb) : ctx(c), b(bb)
-    {
-        std::swap(ctx->recs, b.recs);
-        std::swap(ctx->tables, b.tables);
-    }
-    ~AwLend()
-    {
-        std::swap(ctx->recs, b.recs);
-        std::swap(ctx->tables, b.tables);
-    }
-};
-
 // the geometry a pass over batch b runs with: its visibilities, and its table's distinct kernels as the slices a
 // record's kslice is brought below
 gridhip::Geom batch_geom(const gridhip_aw_plan *pl, const gridhip_aw_plan::Batch &b)
@@ -794,15 +767,11 @@ int aw_plan_pass(gridhip_aw_plan *pl, const double *vis, double *grid, double *v
     ctx->last_path = pl->p.sorted ? 1 : 3;
     for (auto &b : pl->b) {
         const gridhip::Geom g = batch_geom(pl, b);
-        if (degrid) {
-            if (!b.all_binned && !pl->caller_clears)
-                GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out + 2 * b.lo, 0, (size_t)b.m * 16, ctx->stream));
-            AwLend lend(ctx, b);
-            GH_CHECK(gridhip::aw_pass(ctx, pl->p, g, b.m, b.table, vis_out + 2 * b.lo, grid, true));
-        } else {
-            AwLend lend(ctx, b);
-            GH_CHECK(gridhip::aw_pass(ctx, pl->p, g, b.m, b.table, vis + 2 * b.lo, grid, false));
-        }
+        if (degrid && !b.all_binned && !pl->caller_clears)
+            GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out + 2 * b.lo, 0, (size_t)b.m * 16, ctx->stream));
+        gridhip::LendScratch lend(ctx, b.recs, b.tables);
+        GH_CHECK(gridhip::tile_pass(ctx, pl->p, g, b.m, (const double *)b.table, (degrid ? vis_out : vis) + 2 * b.lo, grid,
+                                    degrid));
     }
     return GRIDHIP_OK;
 }
@@ -840,17 +809,14 @@ int gridhip_awgrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_
 {
     GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, grid, vis));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    GridInputs d;  // (the w-kernels as its gcf)
-    DevBuf ak, da1, da2;
-    GH_CHECK(upload_inputs(ctx, d, (size_t)H * Wd, grid, n, uv_stride, u, v, vis, wbin, wkerns, (size_t)W * Q * Q * S * S));
-    GH_CHECK(ak.upload(ctx, akerns, (size_t)A * S * S * 16));
-    GH_CHECK(da1.upload(ctx, a1, (size_t)n * 8));
-    GH_CHECK(da2.upload(ctx, a2, (size_t)n * 8));
-    GH_CHECK(gridhip_awgrid_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, S, A, d.gcf.as<double>(), ak.as<double>(),
-                                d.u.as<double>(), d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), da1.as<int64_t>(),
-                                da2.as<int64_t>(), d.vis.as<double>()));
-    GH_CHECK(d2h(ctx, grid, d.grid.p, (size_t)H * Wd * 16));
-    return sync(ctx);
+    Staged st(ctx, false);
+    grid = st.inout(grid, grid, (size_t)H * Wd * 16);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis = st.in(vis, (size_t)n * 16);
+    wbin = st.in(wbin, (size_t)n * 8), wkerns = st.in(wkerns, (size_t)W * Q * Q * S * S * 16);
+    akerns = st.in(akerns, (size_t)A * S * S * 16), a1 = st.in(a1, (size_t)n * 8), a2 = st.in(a2, (size_t)n * 8);
+    GH_CHECK(st.status());
+    GH_CHECK(gridhip_awgrid_dev(ctx, H, Wd, grid, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2, vis));
+    return st.finish();
 }
 
 // The gather with convgrid4's coordinates and kernels (include/gridhip.h); device pointers, asynchronous.
@@ -871,17 +837,14 @@ int gridhip_awdegrid(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *grid
 {
     GH_CHECK(aw_args_ok(ctx, H, Wd, n, W, Q, S, A, uv_stride, wkerns, akerns, u, v, wbin, a1, a2, grid, vis_out));
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    GridInputs d;  // (the w-kernels as its gcf; vis: the predictions)
-    DevBuf ak, da1, da2;
-    GH_CHECK(upload_inputs(ctx, d, (size_t)H * Wd, grid, n, uv_stride, u, v, nullptr, wbin, wkerns, (size_t)W * Q * Q * S * S));
-    GH_CHECK(ak.upload(ctx, akerns, (size_t)A * S * S * 16));
-    GH_CHECK(da1.upload(ctx, a1, (size_t)n * 8));
-    GH_CHECK(da2.upload(ctx, a2, (size_t)n * 8));
-    GH_CHECK(gridhip_awdegrid_dev(ctx, H, Wd, d.grid.as<double>(), n, W, Q, S, A, d.gcf.as<double>(), ak.as<double>(),
-                                  d.u.as<double>(), d.v.as<double>(), uv_stride, d.wbin.as<int64_t>(), da1.as<int64_t>(),
-                                  da2.as<int64_t>(), d.vis.as<double>()));
-    GH_CHECK(d2h(ctx, vis_out, d.vis.p, (size_t)n * 16));
-    return sync(ctx);
+    Staged st(ctx, false);
+    grid = st.in(grid, (size_t)H * Wd * 16);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis_out = st.out(vis_out, (size_t)n * 16);
+    wbin = st.in(wbin, (size_t)n * 8), wkerns = st.in(wkerns, (size_t)W * Q * Q * S * S * 16);
+    akerns = st.in(akerns, (size_t)A * S * S * 16), a1 = st.in(a1, (size_t)n * 8), a2 = st.in(a2, (size_t)n * 8);
+    GH_CHECK(st.status());
+    GH_CHECK(gridhip_awdegrid_dev(ctx, H, Wd, grid, n, W, Q, S, A, wkerns, akerns, u, v, uv_stride, wbin, a1, a2, vis_out));
+    return st.finish();
 }
 
 int gridhip_aw_plan_destroy(gridhip_aw_plan *pl)
@@ -941,7 +904,7 @@ int gridhip_aw_plan_create_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t 
             g.nrec = (int32_t)m;
             int32_t binned = 0;
             {
-                AwLend lend(ctx, b);
+                LendScratch lend(ctx, b.recs, b.tables);
                 GH_CHECK(ws_reserve(ctx, ctx->tables, tables_bytes(g)));
                 GH_CHECK(ws_reserve(ctx, ctx->recs, (size_t)m * sizeof(RecWord)));
                 GH_CHECK(aw_bin(ctx, c, g, lo, m, u, v, uv_stride, nullptr));

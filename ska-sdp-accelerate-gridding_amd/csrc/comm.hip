@@ -104,6 +104,32 @@ bool load_rccl()
     return g_rccl.h != nullptr;
 }
 
+// The device copies of one device's share of gridhip_comm_convgrid2's inputs, which outlive the call that staged them
+// (the all-reduce reads the grids afterwards): the grid (uploaded, or zeroed when `grid` is null - every device but the
+// first starts from an empty grid), the u / v spans, vis (uploaded, or left for the call to write when `vis` is null),
+// wbin and gcf when given (else their blocks stay null).
+struct GridInputs {
+    DevBuf grid, u, v, vis, wbin, gcf;
+};
+int upload_inputs(gridhip_ctx *ctx, GridInputs &d, size_t cells, const double *grid, int64_t n, int64_t uv_stride,
+                  const double *u, const double *v, const double *vis, const int64_t *wbin, const double *gcf,
+                  size_t gcf_elems)
+{
+    if (grid) {
+        GH_CHECK(d.grid.upload(ctx, grid, cells * 16));
+    } else {
+        GH_CHECK(d.grid.alloc(ctx, cells * 16));
+        GH_CHECK_HIP(ctx, hipMemsetAsync(d.grid.p, 0, cells * 16, ctx->stream));
+    }
+    const size_t span = n > 0 ? (size_t)(n - 1) * uv_stride + 1 : 0;
+    GH_CHECK(d.u.upload(ctx, u, span * 8));
+    GH_CHECK(d.v.upload(ctx, v, span * 8));
+    GH_CHECK(vis ? d.vis.upload(ctx, vis, (size_t)n * 16) : d.vis.alloc(ctx, (size_t)n * 16));
+    if (wbin) GH_CHECK(d.wbin.upload(ctx, wbin, (size_t)n * 8));
+    if (gcf) GH_CHECK(d.gcf.upload(ctx, gcf, gcf_elems * 16));
+    return GRIDHIP_OK;
+}
+
 int comm_fail(gridhip_comm *c, int code, const std::string &msg)
 {
     if (c)

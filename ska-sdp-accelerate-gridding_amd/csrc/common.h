@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string>
 #include <unordered_set>
+#include <utility>
 
 #include "../../include/gridhip.h"
 
@@ -218,6 +219,32 @@ int fail(gridhip_ctx *ctx, int code, const char *fmt, ...);
 
 int ws_reserve(gridhip_ctx *ctx, Workspace &ws, size_t bytes);
 
+// The launchers read the binned data from the context's scratch slots (ctx->recs, ctx->tables): a plan lends them its
+// own pair for the length of a scope.  lend = false is the no-op form, for a borrowed plan (plan.hip), whose records
+// live in the context's slots already.
+class LendScratch {
+  public:
+    LendScratch(gridhip_ctx *ctx, Workspace &recs, Workspace &tables, bool lend = true)
+        : ctx_(ctx), recs_(recs), tables_(tables), lend_(lend)
+    {
+        swap();
+    }
+    ~LendScratch() { swap(); }
+    LendScratch(const LendScratch &) = delete;
+    LendScratch &operator=(const LendScratch &) = delete;
+
+  private:
+    void swap()
+    {
+        if (!lend_) return;
+        std::swap(ctx_->recs, recs_);
+        std::swap(ctx_->tables, tables_);
+    }
+    gridhip_ctx *ctx_;
+    Workspace &recs_, &tables_;
+    bool lend_;
+};
+
 // HIP events of a timed call: i = 0: it starts, 1: its pre-pass is enqueued, 2: its dominant kernel is enqueued (the
 // call is then readable with gridhip_timing)
 static inline void mark(gridhip_ctx *ctx, int i)
@@ -293,6 +320,12 @@ struct Prep {
 int prepare(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t W, int64_t Q, int64_t gh, int64_t gw, int64_t n, Prep *p);
 // the kernel table the tile kernels read: gcf itself, or (sub-footprints) its zero-padded parts in ctx->ktab
 int tile_kernels(gridhip_ctx *ctx, const Prep &p, const double *gcf, const double **out);
+// One pass of the tile kernels over nrec binned records (ctx->recs / ctx->tables) and the kernel table `table`: the
+// one caller of launch_tile_grid, launch_tile_grid_sorted and launch_tile_degrid (api.hip).  Gridding adds
+// vis x kernels onto grid; degridding reads grid and writes the predictions to vis.  p says which kernel (the
+// tap-reusing one, or the general one of the direction) and its launch shape; g is p.g, or a batch's copy of it (aw).
+int tile_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t nrec, const double *table, const double *vis,
+              const double *grid, bool degrid);
 int launch_simple_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n,
                        const double *u, const double *v, int64_t uv_stride, const double *vis);
 

@@ -98,7 +98,9 @@ int download_strided(gridhip_ctx *ctx, double *out, int64_t stride, const void *
 // downloads the outputs in that order and synchronises the stream once.  A null pointer stays null either way, also
 // where its length is 0 (a null required argument of an empty call gets no block, as in the _dev form).  A block
 // that cannot be had makes every later call return null and status() / finish() return its code: a body checks status()
-// once, after its last argument and before it launches anything.
+// once, after its last argument and before it launches anything.  Every host-pointer form goes through it - the
+// gridders' (api.hip, awgrid.hip: stage, then the _dev form) as the imaging layer's (one X_any body per pair) - but
+// gridhip_comm_convgrid2, whose blocks per device outlive the call that stages them (comm.hip).
 class Staged {
   public:
     Staged(gridhip_ctx *ctx, bool dev) : ctx_(ctx), dev_(dev) {}
@@ -130,16 +132,6 @@ class Staged {
     DevBuf bufs_[MAX];
     Out outs_[MAX];
 };
-
-// The device copies of a host-pointer gridding call's inputs (api.hip): the grid (uploaded, or zeroed when `grid` is
-// null), the u / v spans, vis (uploaded, or left for the call to write when `vis` is null), wbin and gcf when given
-// (else their blocks stay null).
-struct GridInputs {
-    DevBuf grid, u, v, vis, wbin, gcf;
-};
-int upload_inputs(gridhip_ctx *ctx, GridInputs &d, size_t cells, const double *grid, int64_t n, int64_t uv_stride,
-                  const double *u, const double *v, const double *vis, const int64_t *wbin, const double *gcf,
-                  size_t gcf_elems);
 
 // findClosest, src/Gridding.hs:895-907 (hi clamped to len-1 as the host twin does, ImageDataset.hs:150-168)
 __device__ __forceinline__ int64_t closest_index(int64_t nws, const double *__restrict__ ws, double x)
@@ -296,12 +288,9 @@ struct AwArgs {
 };
 // N = image size; vis_needed: whether the call reads vis (the gridding entry points do, predict_aw does not)
 int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed = true);
-// The inputs on the device: the caller's own (the _dev forms) or uploaded copies (the host forms), in s.d.
-struct AwStage {
-    DevBuf wk, ws, ak, u, v, w, a1, a2, vis;
-    AwArgs d;
-};
-int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s);
+// The arguments as the kernels see them: a's nine pointers taken through st.in (vis stays null where the entry point
+// reads none).  The caller checks st.status() after its own last argument.
+AwArgs stage_aw(Staged &st, const AwArgs &a);
 // p = uvw1 / lam, w-bins, and (mirror) vis1, (weigh) wt * vis1 in vis1 and (want_wt) wt: aw_front_kernel +
 // aw_weight_kernel.  weigh: 0 none, 1 on the mirrored coordinates, 2 on the un-mirrored ones.
 struct AwFront {

@@ -87,13 +87,17 @@ __global__ void fill_ones_kernel(int64_t n, double2 *__restrict__ a)
 }
 
 // mirror + weights + the two gridding passes + hermitian + iFFT + normalise, all on the device.
-// `imgfn` grids (u1, v1, w1, vis) -> zeroed N x N grid.
+// `imgfn` grids (u1, v1, w1, vis) -> zeroed N x N grid.  st: the call's staging, which may hold arguments of the
+// caller's already (conv_imaging's kv); the array arguments here are the caller's own, taken through it.
 template <typename ImgFn>
-static int do_imaging_impl(gridhip_ctx *ctx, int64_t N, int64_t lam, int64_t n, const double *u, const double *v,
-                           const double *w, int64_t stride, const double *vis, double *image, double *psf,
-                           double *pmax, bool dev, ImgFn imgfn)
+static int do_imaging_impl(gridhip_ctx *ctx, Staged &st, int64_t N, int64_t lam, int64_t n, const double *u,
+                           const double *v, const double *w, int64_t stride, const double *vis, double *image,
+                           double *psf, double *pmax, ImgFn imgfn)
 {
-    const size_t cells = (size_t)N * N;
+    const size_t cells = (size_t)N * N, span = span_bytes(n, stride);
+    u = st.in(u, span), v = st.in(v, span), w = st.in(w, span), vis = st.in(vis, n * 16);
+    image = st.out(image, cells * 8), psf = st.out(psf, cells * 8);
+    GH_CHECK(st.status());
     DevBuf du, dv, dw, dvis, dwt, dpu, dpv, dg, dh, dtmp, dreal, dmax;
     GH_CHECK(dvis.alloc(ctx, n * 16));
     GH_CHECK(dwt.alloc(ctx, n * 16));
@@ -102,22 +106,10 @@ static int do_imaging_impl(gridhip_ctx *ctx, int64_t N, int64_t lam, int64_t n, 
     GH_CHECK(dtmp.alloc(ctx, cells * 16));
     GH_CHECK(dreal.alloc(ctx, cells * 8));
     GH_CHECK(dmax.alloc(ctx, 8));
-    // slice the columns (src/Gridding.hs:524-526) while uploading (device-resident inputs: straight from them)
-    {
-        const size_t span = n > 0 ? (size_t)(n - 1) * stride + 1 : 0;
-        DevBuf s0, s1, s2;
-        const double *su = u, *sv = v, *sw = w;
-        if (!dev) {
-            GH_CHECK(s0.upload(ctx, u, span * 8));
-            GH_CHECK(s1.upload(ctx, v, span * 8));
-            GH_CHECK(s2.upload(ctx, w, span * 8));
-            su = s0.as<double>(), sv = s1.as<double>(), sw = s2.as<double>();
-        }
-        GH_CHECK(slice_uvw(ctx, n, su, sv, sw, stride, du, dv, dw));
-        if (!dev) GH_CHECK(sync(ctx));  // (the staging blocks go back to the pool; all later work is stream-ordered after this)
-    }
-    GH_CHECK(copy_in(ctx, dvis.p, vis, n * 16, dev));
-    // mirror baselines such that v >= 0 (:531)
+    // slice the columns (src/Gridding.hs:524-526)
+    GH_CHECK(slice_uvw(ctx, n, u, v, w, stride, du, dv, dw));
+    // mirror baselines such that v >= 0 (:531): in place, so on a copy of vis
+    GH_CHECK(copy_in(ctx, dvis.p, vis, n * 16, true));
     GH_CHECK(launch_mirror(ctx, n, du.as<double>(), dv.as<double>(), dw.as<double>(), dvis.as<double2>()));
     // weights (:534-535): doweight theta lam uvw1 ones
     GH_CHECK(scaled_uv(ctx, n, du.as<double>(), dv.as<double>(), 1, (double)lam, dpu, dpv));
@@ -138,9 +130,10 @@ static int do_imaging_impl(gridhip_ctx *ctx, int64_t N, int64_t lam, int64_t n, 
                             pass == 1 ? dmax.as<unsigned long long>() : nullptr));
     }
     GH_CHECK(normalise(ctx, cells, dreal.as<double>(), dtmp.as<double>(), dmax.as<unsigned long long>(), pmax));
-    if (image) GH_CHECK(copy_out(ctx, image, dreal.p, cells * 8, dev));
-    if (psf) GH_CHECK(copy_out(ctx, psf, dtmp.p, cells * 8, dev));
-    return sync(ctx);
+    if (image) GH_CHECK(copy_out(ctx, image, dreal.p, cells * 8, true));
+    if (psf) GH_CHECK(copy_out(ctx, psf, dtmp.p, cells * 8, true));
+    GH_CHECK(st.finish());
+    return sync(ctx);  // (the device-resident form, too, returns with image and psf written)
 }
 
 // (WCache: imaging.h)
@@ -202,7 +195,7 @@ static int w_cache_grid_dev(gridhip_ctx *ctx, WCache &c, double theta, int64_t l
 
 // ---- the aw entry points (aw_imaging_dev, do_imaging_aw, aw_gridding): front end -> aw gridder -> imaging tail ----
 
-// (AwArgs, AwStage: imaging.h)
+// (AwArgs: imaging.h)
 // Everything is checked before anything is touched (a refused call leaves its outputs as they were).
 int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed)
 {
@@ -214,25 +207,17 @@ int aw_check(gridhip_ctx *ctx, const AwArgs &a, int64_t *N, bool vis_needed)
     return GRIDHIP_OK;
 }
 
-int aw_stage(gridhip_ctx *ctx, bool dev, const AwArgs &a, AwStage &s)
+AwArgs stage_aw(Staged &st, const AwArgs &a)
 {
-    s.d = a;
-    if (dev) return GRIDHIP_OK;
-    const size_t wel = (size_t)a.W * a.Q * a.Q * a.S * a.S, ael = (size_t)a.A * a.S * a.S;
-    const size_t span = a.n > 0 ? (size_t)(a.n - 1) * a.stride + 1 : 0;
-    GH_CHECK(s.wk.upload(ctx, a.wkerns, wel * 16));
-    GH_CHECK(s.ws.upload(ctx, a.wvals, a.W * 8));
-    GH_CHECK(s.ak.upload(ctx, a.akerns, ael * 16));
-    GH_CHECK(s.u.upload(ctx, a.u, span * 8));
-    GH_CHECK(s.v.upload(ctx, a.v, span * 8));
-    GH_CHECK(s.w.upload(ctx, a.w, span * 8));
-    GH_CHECK(s.a1.upload(ctx, a.a1, a.n * 8));
-    GH_CHECK(s.a2.upload(ctx, a.a2, a.n * 8));
-    GH_CHECK(s.vis.upload(ctx, a.vis, a.vis ? a.n * 16 : 0));  // (predict_aw reads no vis)
-    s.d.wkerns = s.wk.as<double>(), s.d.wvals = s.ws.as<double>(), s.d.akerns = s.ak.as<double>();
-    s.d.u = s.u.as<double>(), s.d.v = s.v.as<double>(), s.d.w = s.w.as<double>();
-    s.d.a1 = s.a1.as<int64_t>(), s.d.a2 = s.a2.as<int64_t>(), s.d.vis = s.vis.as<double>();
-    return GRIDHIP_OK;
+    const size_t span = span_bytes(a.n, a.stride);
+    AwArgs d = a;
+    d.wkerns = st.in(a.wkerns, (size_t)a.W * a.Q * a.Q * a.S * a.S * 16);
+    d.wvals = st.in(a.wvals, (size_t)a.W * 8);
+    d.akerns = st.in(a.akerns, (size_t)a.A * a.S * a.S * 16);
+    d.u = st.in(a.u, span), d.v = st.in(a.v, span), d.w = st.in(a.w, span);
+    d.a1 = st.in(a.a1, (size_t)a.n * 8), d.a2 = st.in(a.a2, (size_t)a.n * 8);
+    d.vis = st.in(a.vis, (size_t)a.n * 16);  // (predict_aw reads no vis: null)
+    return d;
 }
 
 // (AwFront: imaging.h)
@@ -288,35 +273,28 @@ static int do_imaging_aw_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double
     if (!image || !psf) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cells = (size_t)N * N;
-    AwStage s;
-    GH_CHECK(aw_stage(ctx, dev, a, s));
-    const AwArgs &d = s.d;
+    Staged st(ctx, dev);
+    const AwArgs d = stage_aw(st, a);
+    image = st.out(image, cells * 8), psf = st.out(psf, cells * 8);
+    GH_CHECK(st.status());
     AwFront f;
     GH_CHECK(aw_front(ctx, N, d, 1.0, true, 1, true, f));
     // both grids are filled by the one batch loop before either is transformed: two N x N complex blocks
-    DevBuf dg0, dg1, dh, dimg, dpsf, dmax;
+    DevBuf dg0, dg1, dh, dmax;
     GH_CHECK(dg0.alloc(ctx, cells * 16));
     GH_CHECK(dg1.alloc(ctx, cells * 16));
     GH_CHECK(dh.alloc(ctx, cells * 16));
     GH_CHECK(dmax.alloc(ctx, 8));
-    if (!dev) {
-        GH_CHECK(dimg.alloc(ctx, cells * 8));
-        GH_CHECK(dpsf.alloc(ctx, cells * 8));
-    }
-    double *rimg = dev ? image : dimg.as<double>(), *rpsf = dev ? psf : dpsf.as<double>();
     GH_CHECK_HIP(ctx, hipMemsetAsync(dg0.p, 0, cells * 16, ctx->stream));
     GH_CHECK_HIP(ctx, hipMemsetAsync(dg1.p, 0, cells * 16, ctx->stream));
     double *grids[2] = {dg0.as<double>(), dg1.as<double>()};
     const double *viss[2] = {f.vis1.as<double>(), f.wt.as<double>()};  // image from wt * vis1 (:538), PSF from wt (:541)
     GH_CHECK(awgrid_pairs(ctx, N, N, 2, grids, viss, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, f.pu.as<double>(),
                           f.pv.as<double>(), 1, f.wb.as<int64_t>(), d.a1, d.a2));
-    GH_CHECK(image_tail(ctx, N, dg0.as<double2>(), dh.as<double2>(), rimg, nullptr));
-    GH_CHECK(image_tail(ctx, N, dg1.as<double2>(), dh.as<double2>(), rpsf, dmax.as<unsigned long long>()));
-    GH_CHECK(normalise(ctx, cells, rimg, rpsf, dmax.as<unsigned long long>(), pmax));
-    if (dev) return GRIDHIP_OK;
-    GH_CHECK(d2h(ctx, image, rimg, cells * 8));
-    GH_CHECK(d2h(ctx, psf, rpsf, cells * 8));
-    return sync(ctx);
+    GH_CHECK(image_tail(ctx, N, dg0.as<double2>(), dh.as<double2>(), image, nullptr));
+    GH_CHECK(image_tail(ctx, N, dg1.as<double2>(), dh.as<double2>(), psf, dmax.as<unsigned long long>()));
+    GH_CHECK(normalise(ctx, cells, image, psf, dmax.as<unsigned long long>(), pmax));
+    return st.finish();
 }
 
 // aw_gridding, src/ImageDataset.hs:54-77: uvw in metres -> uvw_lambda (x f / c) -> doweight on the UN-mirrored uvw
@@ -329,29 +307,27 @@ static int aw_gridding_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double f
     if (!image || !(f > 0.0) || !(f < INFINITY)) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cells = (size_t)N * N;
-    AwStage s;
-    GH_CHECK(aw_stage(ctx, dev, a, s));
-    const AwArgs &d = s.d;
+    Staged st(ctx, dev);
+    const AwArgs d = stage_aw(st, a);
+    image = st.out(image, cells * 8);
+    GH_CHECK(st.status());
     AwFront fr;
     GH_CHECK(aw_front(ctx, N, d, f / 299792458.0, true, 2, false, fr));  // (the constant of uvw_lambda, :187)
-    DevBuf dg, dh, dimg, dmax;
+    DevBuf dg, dh, dmax;
     GH_CHECK(dg.alloc(ctx, cells * 16));
     GH_CHECK(dh.alloc(ctx, cells * 16));
     GH_CHECK(dmax.alloc(ctx, 8));
-    if (!dev) GH_CHECK(dimg.alloc(ctx, cells * 8));
-    double *rimg = dev ? image : dimg.as<double>();
     GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, cells * 16, ctx->stream));
     double *grid = dg.as<double>();
     const double *vis = fr.vis1.as<double>();
     GH_CHECK(awgrid_pairs(ctx, N, N, 1, &grid, &vis, d.n, d.W, d.Q, d.S, d.A, d.wkerns, d.akerns, fr.pu.as<double>(),
                           fr.pv.as<double>(), 1, fr.wb.as<int64_t>(), d.a1, d.a2));
-    GH_CHECK(image_tail(ctx, N, dg.as<double2>(), dh.as<double2>(), rimg, dmax.as<unsigned long long>()));
+    GH_CHECK(image_tail(ctx, N, dg.as<double2>(), dh.as<double2>(), image, dmax.as<unsigned long long>()));
     unsigned long long mb = 0;
     GH_CHECK(d2h(ctx, &mb, dmax.p, 8));
-    if (!dev) GH_CHECK(d2h(ctx, image, rimg, cells * 8));
     GH_CHECK(sync(ctx));
     if (imax) *imax = ordered_value(mb);
-    return GRIDHIP_OK;
+    return st.finish();
 }
 
 }  // namespace gridhip
@@ -361,19 +337,6 @@ using namespace gridhip;
 extern "C" {
 
 // ---- imaging functions (ImagingFunction, src/Gridding.hs:76-81): uvw in wavelengths, returns the N x N grid ----
-
-static int stage3(gridhip_ctx *ctx, int64_t n, const double *u, const double *v, const double *w, int64_t stride,
-                  const double *vis, DevBuf &du, DevBuf &dv, DevBuf &dw, DevBuf &dvis)
-{
-    const size_t span = n > 0 ? (size_t)(n - 1) * stride + 1 : 0;
-    DevBuf s0, s1, s2;
-    GH_CHECK(s0.upload(ctx, u, span * 8));
-    GH_CHECK(s1.upload(ctx, v, span * 8));
-    GH_CHECK(s2.upload(ctx, w, w ? span * 8 : 0));
-    GH_CHECK(dvis.upload(ctx, vis, n * 16));
-    GH_CHECK(slice_uvw(ctx, n, s0.as<double>(), s1.as<double>(), w ? s2.as<double>() : nullptr, stride, du, dv, dw));
-    return sync(ctx);
-}
 
 static int simple_grid_dev(gridhip_ctx *ctx, int64_t lam, int64_t N, int64_t n, const double *u, const double *v,
                            const double *vis, double *grid)
@@ -403,13 +366,15 @@ int gridhip_simple_imaging(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
     if (N <= 0 || n < 0 || uv_stride < 1 || !grid || (n > 0 && (!u || !v || !vis)))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf du, dv, dw, dvis, dg;
-    GH_CHECK(stage3(ctx, n, u, v, nullptr, uv_stride, vis, du, dv, dw, dvis));
-    GH_CHECK(dg.alloc(ctx, (size_t)N * N * 16));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, (size_t)N * N * 16, ctx->stream));
-    GH_CHECK(simple_grid_dev(ctx, lam, N, n, du.as<double>(), dv.as<double>(), dvis.as<double>(), dg.as<double>()));
-    GH_CHECK(d2h(ctx, grid, dg.p, (size_t)N * N * 16));
-    return sync(ctx);
+    Staged st(ctx, false);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis = st.in(vis, (size_t)n * 16);
+    grid = st.out(grid, (size_t)N * N * 16);
+    GH_CHECK(st.status());
+    DevBuf du, dv, dw;
+    GH_CHECK(slice_uvw(ctx, n, u, v, nullptr, uv_stride, du, dv, dw));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
+    GH_CHECK(simple_grid_dev(ctx, lam, N, n, du.as<double>(), dv.as<double>(), vis, grid));
+    return st.finish();
 }
 
 // conv_imaging kv, src/Gridding.hs:115-124 ; kv is [Q][Q][gh][gw]
@@ -423,21 +388,21 @@ int gridhip_conv_imaging(gridhip_ctx *ctx, int64_t Q, int64_t gh, int64_t gw, co
         (n > 0 && (!u || !v || !vis)))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf du, dv, dw, dvis, dg, dk;
-    GH_CHECK(stage3(ctx, n, u, v, nullptr, uv_stride, vis, du, dv, dw, dvis));
-    GH_CHECK(dg.alloc(ctx, (size_t)N * N * 16));
-    GH_CHECK(dk.upload(ctx, kv, (size_t)Q * Q * gh * gw * 16));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, (size_t)N * N * 16, ctx->stream));
-    GH_CHECK(conv_grid_dev(ctx, lam, N, Q, gh, gw, dk.as<double>(), n, du.as<double>(), dv.as<double>(),
-                           dvis.as<double>(), dg.as<double>()));
-    GH_CHECK(d2h(ctx, grid, dg.p, (size_t)N * N * 16));
-    return sync(ctx);
+    Staged st(ctx, false);
+    u = st.in(u, span_bytes(n, uv_stride)), v = st.in(v, span_bytes(n, uv_stride)), vis = st.in(vis, (size_t)n * 16);
+    kv = st.in(kv, (size_t)Q * Q * gh * gw * 16), grid = st.out(grid, (size_t)N * N * 16);
+    GH_CHECK(st.status());
+    DevBuf du, dv, dw;
+    GH_CHECK(slice_uvw(ctx, n, u, v, nullptr, uv_stride, du, dv, dw));
+    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
+    GH_CHECK(conv_grid_dev(ctx, lam, N, Q, gh, gw, kv, n, du.as<double>(), dv.as<double>(), vis, grid));
+    return st.finish();
 }
 
-// w_cache_imaging, src/Gridding.hs:399-449 (wstep default 2000, :412)
-int gridhip_w_cache_imaging(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_t npixFF, int64_t npixKern,
-                            double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
-                            int64_t uv_stride, const double *vis, double *grid)
+// w_cache_imaging, src/Gridding.hs:399-449 (wstep default 2000, :412): uvw in wavelengths, the N x N grid overwritten
+static int w_cache_imaging_any(gridhip_ctx *ctx, bool dev, int64_t wstep, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                               double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
+                               int64_t uv_stride, const double *vis, double *grid)
 {
     if (!ctx) return GRIDHIP_EINVAL;
     ImagingFn fn{2, wstep, qpx, npixFF, npixKern, npixKern, nullptr, theta, lam};
@@ -445,37 +410,70 @@ int gridhip_w_cache_imaging(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_
     GH_CHECK(imaging_fn_check(ctx, fn, &N));
     if (n < 0 || uv_stride < 1 || !grid || (n > 0 && (!u || !v || !w || !vis))) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf du, dv, dw, dvis, dg;
-    GH_CHECK(stage3(ctx, n, u, v, w, uv_stride, vis, du, dv, dw, dvis));
-    GH_CHECK(dg.alloc(ctx, (size_t)N * N * 16));
-    GH_CHECK_HIP(ctx, hipMemsetAsync(dg.p, 0, (size_t)N * N * 16, ctx->stream));
+    const size_t span = span_bytes(n, uv_stride);
+    Staged st(ctx, dev);
+    u = st.in(u, span), v = st.in(v, span), w = st.in(w, span), vis = st.in(vis, (size_t)n * 16);
+    grid = st.out(grid, (size_t)N * N * 16);
+    GH_CHECK(st.status());
+    DevBuf du, dv, dw;
+    if (uv_stride != 1) {  // the (n, 3) matrix: slice its columns
+        GH_CHECK(slice_uvw(ctx, n, u, v, w, uv_stride, du, dv, dw));
+        u = du.as<double>(), v = dv.as<double>(), w = dw.as<double>();
+    }
+    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
     WCache cache;
-    GH_CHECK(w_cache_grid_dev(ctx, cache, theta, lam, fn.wstep, qpx, npixFF, npixKern, N, n, du.as<double>(), dv.as<double>(),
-                              dw.as<double>(), dvis.as<double>(), dg.as<double>()));
-    GH_CHECK(d2h(ctx, grid, dg.p, (size_t)N * N * 16));
-    return sync(ctx);
+    GH_CHECK(w_cache_grid_dev(ctx, cache, theta, lam, fn.wstep, qpx, npixFF, npixKern, N, n, u, v, w, vis, grid));
+    return st.finish();
+}
+
+int gridhip_w_cache_imaging(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                            double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
+                            int64_t uv_stride, const double *vis, double *grid)
+{
+    return w_cache_imaging_any(ctx, false, wstep, qpx, npixFF, npixKern, theta, lam, n, u, v, w, uv_stride, vis, grid);
+}
+
+int gridhip_w_cache_imaging_dev(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                                double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
+                                int64_t uv_stride, const double *vis, double *grid)
+{
+    return w_cache_imaging_any(ctx, true, wstep, qpx, npixFF, npixKern, theta, lam, n, u, v, w, uv_stride, vis, grid);
 }
 
 // aw_imaging / aw_imagingOld, src/Gridding.hs:452-506: p = uvw/lam, wbin = findClosest wbins w,
-// index = (wbin, a1, a2), then convgrid4 / convgrid3 (same grid).  wvals are the W plane w-values.
+// index = (wbin, a1, a2), then convgrid4 / convgrid3 (same grid).  wvals are the W plane w-values.  The N x N grid is
+// overwritten.  The device-resident form is asynchronous: nothing is read back.
+static int aw_imaging_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, double *grid)
+{
+    if (!ctx) return GRIDHIP_EINVAL;
+    int64_t N = 0;
+    GH_CHECK(aw_check(ctx, a, &N));
+    if (!grid) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
+    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    Staged st(ctx, dev);
+    const AwArgs d = stage_aw(st, a);
+    grid = st.out(grid, (size_t)N * N * 16);
+    GH_CHECK(st.status());
+    GH_CHECK(aw_imaging_to(ctx, N, d, grid));
+    return st.finish();
+}
+
 int gridhip_aw_imaging(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
                        const double *wkerns, const double *wvals, const double *akerns, int64_t n, const double *u,
                        const double *v, const double *w, int64_t uv_stride, const int64_t *a1, const int64_t *a2,
                        const double *vis, double *grid)
 {
-    if (!ctx) return GRIDHIP_EINVAL;
     const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
-    int64_t N = 0;
-    GH_CHECK(aw_check(ctx, a, &N));
-    if (!grid) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    AwStage s;
-    GH_CHECK(aw_stage(ctx, false, a, s));
-    DevBuf dg;
-    GH_CHECK(dg.alloc(ctx, (size_t)N * N * 16));
-    GH_CHECK(aw_imaging_to(ctx, N, s.d, dg.as<double>()));
-    GH_CHECK(d2h(ctx, grid, dg.p, (size_t)N * N * 16));
-    return sync(ctx);
+    return aw_imaging_any(ctx, false, a, grid);
+}
+
+int gridhip_aw_imaging_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
+                           const double *wkerns, const double *wvals, const double *akerns, int64_t n, const double *u,
+                           const double *v, const double *w, int64_t uv_stride, const int64_t *a1, const int64_t *a2,
+                           const double *vis, double *grid)
+{
+    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
+    return aw_imaging_any(ctx, true, a, grid);
 }
 
 // do_imaging, src/Gridding.hs:509-549, with the ImagingFunction fn (imaging.h).
@@ -488,18 +486,14 @@ static int do_imaging_any(gridhip_ctx *ctx, bool dev, ImagingFn fn, int64_t n, c
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     int64_t N = 0;
     GH_CHECK(imaging_fn_check(ctx, fn, &N));
-    DevBuf dk;
-    const double *k = fn.kv;
-    if (fn.kind == 1 && !dev) {
-        GH_CHECK(dk.upload(ctx, fn.kv, (size_t)fn.Q * fn.Q * fn.gh * fn.gw * 16));
-        k = dk.as<double>();
-    }
+    Staged st(ctx, dev);
+    if (fn.kind == 1) fn.kv = st.in(fn.kv, (size_t)fn.Q * fn.Q * fn.gh * fn.gw * 16);  // (no other kind reads it)
     WCache cache;  // w_cache: built by the image pass, reused by the PSF pass
-    return do_imaging_impl(ctx, N, fn.lam, n, u, v, w, uv_stride, vis, image, psf, pmax, dev,
+    return do_imaging_impl(ctx, st, N, fn.lam, n, u, v, w, uv_stride, vis, image, psf, pmax,
                            [&](const double *uu, const double *vv, const double *ww, const double *vs, double *g) {
                                if (fn.kind == 0) return simple_grid_dev(ctx, fn.lam, N, n, uu, vv, vs, g);
                                if (fn.kind == 1)
-                                   return conv_grid_dev(ctx, fn.lam, N, fn.Q, fn.gh, fn.gw, k, n, uu, vv, vs, g);
+                                   return conv_grid_dev(ctx, fn.lam, N, fn.Q, fn.gh, fn.gw, fn.kv, n, uu, vv, vs, g);
                                return w_cache_grid_dev(ctx, cache, fn.theta, fn.lam, fn.wstep, fn.Q, fn.npixFF, fn.gh, N, n,
                                                        uu, vv, ww, vs, g);
                            });
@@ -521,44 +515,6 @@ int gridhip_do_imaging_dev(gridhip_ctx *ctx, int kind, int64_t wstep, int64_t Q,
 {
     return do_imaging_any(ctx, true, {kind, wstep, Q, npixFF, gh, gw, kv, theta, lam}, n, u, v, w, uv_stride, vis, image,
                           psf, pmax);
-}
-
-// w_cache_imaging with device-resident uvw (wavelengths), vis and N x N grid (overwritten)
-int gridhip_w_cache_imaging_dev(gridhip_ctx *ctx, int64_t wstep, int64_t qpx, int64_t npixFF, int64_t npixKern,
-                                double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
-                                int64_t uv_stride, const double *vis, double *grid)
-{
-    if (!ctx) return GRIDHIP_EINVAL;
-    ImagingFn fn{2, wstep, qpx, npixFF, npixKern, npixKern, nullptr, theta, lam};
-    int64_t N = 0;
-    GH_CHECK(imaging_fn_check(ctx, fn, &N));
-    if (n < 0 || uv_stride < 1 || !grid || (n > 0 && (!u || !v || !w || !vis))) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf du, dv, dw;
-    const double *pu = u, *pv = v, *pw = w;
-    if (uv_stride != 1) {  // the (n, 3) matrix: slice its columns
-        GH_CHECK(slice_uvw(ctx, n, u, v, w, uv_stride, du, dv, dw));
-        pu = du.as<double>(), pv = dv.as<double>(), pw = dw.as<double>();
-    }
-    GH_CHECK_HIP(ctx, hipMemsetAsync(grid, 0, (size_t)N * N * 16, ctx->stream));
-    WCache cache;
-    return w_cache_grid_dev(ctx, cache, theta, lam, fn.wstep, qpx, npixFF, npixKern, N, n, pu, pv, pw, vis, grid);
-}
-
-// aw_imaging with device-resident arguments: the front end's one kernel (p = uvw / lam, findClosest w-bins), then the
-// aw gridder into the N x N grid (overwritten).  Asynchronous: nothing is read back.
-int gridhip_aw_imaging_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,
-                           const double *wkerns, const double *wvals, const double *akerns, int64_t n, const double *u,
-                           const double *v, const double *w, int64_t uv_stride, const int64_t *a1, const int64_t *a2,
-                           const double *vis, double *grid)
-{
-    if (!ctx) return GRIDHIP_EINVAL;
-    const AwArgs a{theta, lam, W, Q, S, A, wkerns, wvals, akerns, n, u, v, w, uv_stride, a1, a2, vis};
-    int64_t N = 0;
-    GH_CHECK(aw_check(ctx, a, &N));
-    if (!grid) return fail(ctx, GRIDHIP_EINVAL, "bad argument");
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    return aw_imaging_to(ctx, N, a, grid);
 }
 
 int gridhip_do_imaging_aw(gridhip_ctx *ctx, double theta, int64_t lam, int64_t W, int64_t Q, int64_t S, int64_t A,

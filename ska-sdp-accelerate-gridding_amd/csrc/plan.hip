@@ -5,8 +5,6 @@
 // (image and PSF, src/Gridding.hs:538,541) and imaging major cycles alternate degrid / grid over
 // the same baselines many times; a plan keeps the tile-ordered records resident in HBM so each
 // further pass costs the tile kernel only (17 ms instead of 21 ms on the 10^8-visibility case).
-#include <utility>
-
 #include "common.h"
 #include "imaging.h"
 
@@ -25,25 +23,6 @@ struct gridhip_plan {
 };
 
 using namespace gridhip;
-
-namespace {
-// the launchers read the binned data from the context's scratch slots: lend them the plan's
-struct Lend {
-    gridhip_plan *p;
-    explicit Lend(gridhip_plan *pl) : p(pl)
-    {
-        if (p->borrowed) return;
-        std::swap(p->ctx->recs, p->recs);
-        std::swap(p->ctx->tables, p->tables);
-    }
-    ~Lend()
-    {
-        if (p->borrowed) return;
-        std::swap(p->ctx->recs, p->recs);
-        std::swap(p->ctx->tables, p->tables);
-    }
-};
-}  // namespace
 
 static int plan_create(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64_t W, int64_t Q, int64_t gh, int64_t gw,
                        const double *u, const double *v, int64_t uv_stride, const int64_t *wbin, gridhip_plan **out,
@@ -98,7 +77,7 @@ static int plan_create(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t n, int64
         return rc;
     }
     {
-        Lend lend(p);
+        LendScratch lend(ctx, p->recs, p->tables, !p->borrowed);
         rc = ws_reserve(ctx, ctx->tables, tables_bytes(p->p.g));
         if (rc == GRIDHIP_OK) rc = ws_reserve(ctx, ctx->recs, (size_t)(p->p.nrec > 0 ? p->p.nrec : 1) * sizeof(RecWord));
         if (rc == GRIDHIP_OK) rc = launch_bin(ctx, p->p.g, p->p.nrec, u, v, uv_stride, wbin);
@@ -147,11 +126,8 @@ int gridhip_plan_grid_dev(gridhip_plan *p, const double *gcf, const double *vis,
     if (p->n == 0) return GRIDHIP_OK;
     const double *tk = gcf;
     GH_CHECK(tile_kernels(ctx, p->p, gcf, &tk));
-    Lend lend(p);
-    const Prep &q = p->p;
-    if (q.sorted)
-        return launch_tile_grid_sorted(ctx, q.g, q.block, q.lds_sorted, q.nkeys, q.batch, q.nrec, tk, vis, grid, false);
-    return launch_tile_grid(ctx, q.g, q.block, q.lds, q.nrec, tk, vis, grid);
+    LendScratch lend(ctx, p->recs, p->tables, !p->borrowed);
+    return tile_pass(ctx, p->p, p->p.g, p->p.nrec, tk, vis, grid, false);
 }
 
 // vis_out[k] = gather(kernels x G) for every baseline of the plan (degrid2 semantics)
@@ -165,12 +141,8 @@ int gridhip_plan_degrid_dev(gridhip_plan *p, const double *gcf, const double *gr
     if (!p->all_binned && !p->caller_clears) GH_CHECK_HIP(ctx, hipMemsetAsync(vis_out, 0, (size_t)p->n * 16, ctx->stream));
     const double *tk = gcf;
     GH_CHECK(tile_kernels(ctx, p->p, gcf, &tk));
-    Lend lend(p);
-    const Prep &q = p->p;
-    if (q.sorted)
-        return launch_tile_grid_sorted(ctx, q.g, q.block, q.lds_sorted, q.nkeys, q.batch, q.nrec, tk, vis_out,
-                                       const_cast<double *>(grid), true);
-    return launch_tile_degrid(ctx, q.g, q.block, q.lds, q.nrec, tk, grid, vis_out);
+    LendScratch lend(ctx, p->recs, p->tables, !p->borrowed);
+    return tile_pass(ctx, p->p, p->p.g, p->p.nrec, tk, vis_out, grid, true);
 }
 
 }  // extern "C"

@@ -190,25 +190,16 @@ int predict_any(gridhip_ctx *ctx, bool dev, PredictArgs a)
     const int64_t n = a.n;
     // nothing is dropped until a gather says otherwise (the simple gather counts nothing, as `grid` does not)
     GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
-    if (n == 0) return dev ? GRIDHIP_OK : sync(ctx);
-    const size_t cells = (size_t)N * N;
-    const size_t span = (size_t)(n - 1) * a.stride + 1;
-    // the inputs on the device
-    DevBuf sm, su, sv, sw, skv, ssub, sout;
-    const double *model = a.model, *u = a.u, *v = a.v, *w = a.w, *kv = fn.kv, *vis_sub = a.vis_sub;
-    double *out = a.vis_out;
-    if (!dev) {
-        GH_CHECK(sm.upload(ctx, a.model, cells * 8));
-        GH_CHECK(su.upload(ctx, a.u, span * 8));
-        GH_CHECK(sv.upload(ctx, a.v, span * 8));
-        if (fn.kind == 2) GH_CHECK(sw.upload(ctx, a.w, span * 8));
-        if (fn.kind == 1) GH_CHECK(skv.upload(ctx, fn.kv, (size_t)fn.Q * fn.Q * fn.gh * fn.gw * 16));
-        if (a.vis_sub) GH_CHECK(ssub.upload(ctx, a.vis_sub, (size_t)n * 16));
-        GH_CHECK(sout.alloc(ctx, (size_t)n * 16));
-        model = sm.as<double>(), u = su.as<double>(), v = sv.as<double>(), w = sw.as<double>(), kv = skv.as<double>();
-        vis_sub = a.vis_sub ? ssub.as<double>() : nullptr;
-        out = sout.as<double>();
-    }
+    Staged st(ctx, dev);
+    if (n == 0) return st.finish();
+    const size_t cells = (size_t)N * N, span = span_bytes(n, a.stride);
+    // the arguments on the device (w and kv: for the kind that reads them)
+    const double *model = st.in(a.model, cells * 8), *u = st.in(a.u, span), *v = st.in(a.v, span);
+    const double *w = fn.kind == 2 ? st.in(a.w, span) : nullptr;
+    const double *kv = fn.kind == 1 ? st.in(fn.kv, (size_t)fn.Q * fn.Q * fn.gh * fn.gw * 16) : nullptr;
+    const double *vis_sub = st.in(a.vis_sub, (size_t)n * 16);
+    double *out = st.out(a.vis_out, (size_t)n * 16);
+    GH_CHECK(st.status());
     // front end: the imaging function's coordinates (p = uvw / lam; w_cache: the w-bins and its kernel table)
     DevBuf pu, pv, pw;
     WCache wc;
@@ -246,9 +237,7 @@ int predict_any(gridhip_ctx *ctx, bool dev, PredictArgs a)
         }
     }
     GH_CHECK(predict_tail(ctx, n, pred, vis_sub, out));
-    if (dev) return GRIDHIP_OK;
-    GH_CHECK(d2h(ctx, a.vis_out, out, (size_t)n * 16));
-    return sync(ctx);
+    return st.finish();
 }
 
 int predict_aw_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, const double *model, const double *vis_sub,
@@ -261,21 +250,12 @@ int predict_aw_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, const double *mo
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t n = a.n;
     GH_CHECK_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(int32_t), ctx->stream));
-    if (n == 0) return dev ? GRIDHIP_OK : sync(ctx);
-    const size_t cells = (size_t)N * N;
-    AwStage s;
-    GH_CHECK(aw_stage(ctx, dev, a, s));
-    const AwArgs &d = s.d;
-    DevBuf sm, ssub, sout;
-    double *out = vis_out;
-    if (!dev) {
-        GH_CHECK(sm.upload(ctx, model, cells * 8));
-        if (vis_sub) GH_CHECK(ssub.upload(ctx, vis_sub, (size_t)n * 16));
-        GH_CHECK(sout.alloc(ctx, (size_t)n * 16));
-        model = sm.as<double>();
-        vis_sub = vis_sub ? ssub.as<double>() : nullptr;
-        out = sout.as<double>();
-    }
+    Staged st(ctx, dev);
+    if (n == 0) return st.finish();
+    const AwArgs d = stage_aw(st, a);
+    model = st.in(model, (size_t)N * N * 8), vis_sub = st.in(vis_sub, (size_t)n * 16);
+    vis_out = st.out(vis_out, (size_t)n * 16);
+    GH_CHECK(st.status());
     AwFront fr;
     GH_CHECK(aw_front(ctx, N, d, 1.0, false, 0, false, fr));  // p = uvw / lam, findClosest w-bins; no mirror
     DevBuf f, t, pred, cwk, cak;
@@ -293,10 +273,8 @@ int predict_aw_any(gridhip_ctx *ctx, bool dev, const AwArgs &a, const double *mo
         GH_CHECK(gridhip_awdegrid_dev(ctx, N, N, f.as<double>(), n, d.W, d.Q, d.S, d.A, wk, ak, fr.pu.as<double>(),
                                       fr.pv.as<double>(), 1, fr.wb.as<int64_t>(), d.a1, d.a2, pred.as<double>()));
     }
-    GH_CHECK(predict_tail(ctx, n, pred, vis_sub, out));
-    if (dev) return GRIDHIP_OK;
-    GH_CHECK(d2h(ctx, vis_out, out, (size_t)n * 16));
-    return sync(ctx);
+    GH_CHECK(predict_tail(ctx, n, pred, vis_sub, vis_out));
+    return st.finish();
 }
 
 }  // namespace

@@ -80,6 +80,60 @@ def test_aw_imaging(ctx, oracle):
     assert rel(got, ref) < TOL
 
 
+@pytest.mark.parametrize("layout", ["columns", "matrix"])
+@pytest.mark.parametrize("n", [0, 1, 257])
+def test_host_and_device_forms_at_the_staging_edges(ctx, oracle, n, layout):
+    """convgrid4 (gridhip_awgrid) and aw_imaging, each in its host-pointer and its device-pointer form on the same
+    inputs, against the oracle, where a staging path can go wrong: no visibility, one, and an odd few; the baselines as
+    contiguous columns and as columns of the (n, 3) matrix, whose spans overlap; a grid that already holds values (the
+    gridder accumulates, the imaging function overwrites).  n = 0 also with every per-visibility array null, as both
+    forms allow it - the gather (gridhip_awdegrid) included.  Shapes: the smallest of test_awgrid_matches_oracle, and
+    test_aw_imaging's."""
+    import torch
+    from gridhip._marshal import HOST, device
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    forms = [("host", lambda a: a.copy(), lambda a: a), ("dev", t, lambda a: a.cpu().numpy())]
+    rng = np.random.default_rng(200 + n)
+    N, W, Q, S, A = 64, 2, 2, 4, 5
+    wk = rng.normal(size=(W, Q, Q, S, S)) + 1j * rng.normal(size=(W, Q, Q, S, S))
+    ak = rng.normal(size=(A, S, S)) + 1j * rng.normal(size=(A, S, S))
+    u, v = rng.uniform(-0.55, 0.55, n), rng.uniform(-0.55, 0.55, n)
+    wb, a1, a2 = rng.integers(0, W, n), rng.integers(0, A, n), rng.integers(0, A, n)
+    vis = rng.normal(size=n) + 1j * rng.normal(size=n)
+    G0 = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+    ref = oracle.awgrid(wk, ak, G0.copy(), u, v, wb, a1, a2, vis)
+    for name, to, back in forms:
+        p = to(np.stack([u, v, u + v], axis=1)) if layout == "matrix" else (to(u), to(v), None)
+        got = back(ctx.convgrid4(to(wk), to(ak), to(G0), p, (to(wb), to(a1), to(a2)), to(vis)))
+        assert rel(got, ref) < TOL, name
+        assert ctx.get_option("errors") == 0
+    if n == 0 and layout == "columns":
+        for be, (name, to, back) in zip((HOST, device()), forms):
+            g, k, a = to(G0), to(wk), to(ak)
+            ctx._call(be, "awgrid", N, N, g, 0, W, Q, S, A, k, a, None, None, 1, None, None, None, None)
+            ctx._call(be, "awdegrid", N, N, g, 0, W, Q, S, A, k, a, None, None, 1, None, None, None, None)
+            assert np.array_equal(back(g), G0), name
+    theta, lam = 0.05, 1280  # N = 64
+    W, Q, S, A = 5, 2, 15, 4
+    wk = rng.normal(size=(W, Q, Q, S, S)) + 1j * rng.normal(size=(W, Q, Q, S, S))
+    ak = rng.normal(size=(A, S, S)) + 1j * rng.normal(size=(A, S, S))
+    wvals = np.sort(rng.uniform(-400, 400, W))
+    u, v, w = rng.uniform(-600, 600, n), rng.uniform(-600, 600, n), rng.uniform(-500, 500, n)
+    a1, a2 = rng.integers(0, A, n), rng.integers(0, A, n)
+    wb = np.array([oracle.find_closest(wvals, x) for x in w], dtype=np.int64)
+    ref = oracle.awgrid(wk, ak, np.zeros((64, 64), dtype=np.complex128), u / lam, v / lam, wb, a1, a2, vis)
+    for name, to, back in forms:
+        p = to(np.stack([u, v, w], axis=1)) if layout == "matrix" else (to(u), to(v), to(w))
+        got = back(ctx.aw_imaging(theta, lam, to(wk), to(wvals), to(ak), p, (to(a1), to(a2), None, None), to(vis)))
+        assert rel(got, ref) < TOL, name
+    if n == 0 and layout == "columns":
+        for be, (name, to, back) in zip((HOST, device()), forms):
+            g = to(G0)
+            ctx._call(be, "aw_imaging", theta, lam, W, Q, S, A, to(wk), to(wvals), to(ak), 0, None, None, None, 1, None,
+                      None, None, g)
+            assert not back(g).any(), name
+
+
 def _aw_case(seed, N, W, Q, S, A, nb, dumps, drift=0.02):
     """baseline-structured stream: nb baselines x `dumps` consecutive samples drifting by `drift` cells each"""
     rng = np.random.default_rng(seed)

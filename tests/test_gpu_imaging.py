@@ -159,6 +159,56 @@ def test_do_imaging_at_the_drivers_size_host_and_resident(ctx, kind):
     assert ctx.get_option("errors") == 0
 
 
+@pytest.mark.parametrize("layout", ["columns", "matrix"])
+@pytest.mark.parametrize("n", [0, 1, 257])
+def test_do_imaging_conv_host_and_resident_at_the_staging_edges(ctx, n, layout):
+    """do_imaging with conv_imaging - the kind the driver-sized test above leaves out - in its host and its resident form
+    on the same inputs, against the numpy oracle at test_do_imaging's size, where a staging path can go wrong: no
+    visibility, one, and an odd few; uvw as contiguous columns and as the (n, 3) matrix, whose column spans overlap; psf
+    and image each once null (a null output stays unwritten, the other is unchanged by it).  n = 0: the PSF is all zero
+    and its maximum 0, so there is no oracle image (0 / 0): no atomic takes part, and the forms must agree on pmax = 0
+    and on every cell, also with every per-visibility array null."""
+    import ctypes as C
+    import torch
+    from gridhip._marshal import HOST, device, imaging_function
+    theta, lam, N = 0.05, 2560, 128
+    u, v, w, vis = _vis(40 + n, n, 1100, 500)
+    rng = np.random.default_rng(10)
+    kv = rng.normal(size=(2, 2, 7, 7)) + 1j * rng.normal(size=(2, 2, 7, 7))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    forms = [("host", HOST, lambda a: a.copy(), lambda a: a), ("dev", device(), t, lambda a: a.cpu().numpy())]
+    empty = None  # n = 0: what the first form gave
+    if n > 0:
+        fn = lambda th, la, uu, vv, ww, vs: P.convgrid(kv, np.zeros((N, N), complex), uu / la, vv / la, vs)
+        rimg, rpsf, rpmax = P.do_imaging(theta, lam, u, v, w, vis, fn)
+    for name, be, to, back in forms:
+        uvw = to(np.stack([u, v, w], axis=1)) if layout == "matrix" else (to(u), to(v), to(w))
+        img, psf, pmax = ctx.do_imaging(theta, lam, uvw, None, None, None, 1.0e8, to(vis), ("conv", to(kv)))
+        img, psf = back(img), back(psf)
+        def check(gi, gp, gm, what):
+            if n == 0:
+                assert gm == 0.0, what
+                for got, want in ((gi, empty[0]), (gp, empty[1])):
+                    assert got is None or np.array_equal(got, want, equal_nan=True), what
+            else:
+                assert abs(gm - rpmax) / abs(rpmax) < TOL, what
+                assert (gp is None or rel(gp, rpsf) < TOL) and (gi is None or rel(gi, rimg) < TOL), what
+        empty = empty or (img, psf)
+        check(img, psf, pmax, name)
+        if layout == "matrix":
+            continue
+        # the C entry point itself, for what the binding never passes: a null image, a null psf, null baselines
+        cu, cv, cw, cvis = (None,) * 4 if n == 0 else (to(u), to(v), to(w), to(vis))
+        head = imaging_function(be, ("conv", to(kv)))
+        for skip in ("image", "psf"):
+            oi, op, pm = to(np.full((N, N), 7.0)), to(np.full((N, N), 7.0)), C.c_double()
+            ctx._call(be, "do_imaging", *head, theta, lam, n, cu, cv, cw, 1, cvis, None if skip == "image" else oi,
+                      None if skip == "psf" else op, C.byref(pm))
+            assert (back(oi if skip == "image" else op) == 7.0).all(), (name, skip)
+            check(None if skip == "image" else back(oi), None if skip == "psf" else back(op), pm.value, (name, skip))
+    assert ctx.get_option("errors") == 0
+
+
 def test_w_cache_imaging_resident(ctx):
     import torch
     theta, lam = 0.05, 2560

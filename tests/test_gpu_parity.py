@@ -611,6 +611,47 @@ def test_device_path_with_torch_tensors(ctx, oracle):
     assert rel(d.cpu().numpy(), oracle.degrid2(gcf, ref, u, v, wb)) < 1e-9
 
 
+@pytest.mark.parametrize("layout", ["columns", "matrix"])
+@pytest.mark.parametrize("n", [0, 1, 257])
+def test_host_and_device_forms_at_the_staging_edges(ctx, oracle, n, layout):
+    """grid, convgrid2 and degrid2, each in its host-pointer and its device-pointer form on the same inputs, against the
+    oracle, where a staging path can go wrong: no visibility, one, and an odd few; u and v as contiguous columns and as
+    columns of the (n, 3) matrix, whose spans overlap; wbin given and (a one-plane call) null; a grid that already holds
+    values.  n = 0 also with every per-visibility array null, as both forms allow it.  Grid and support: SHAPES'
+    smallest grid."""
+    import torch
+    from gridhip._marshal import HOST, device
+    N, M, W, Q, gh, gw = 33, 47, 2, 4, 2, 4
+    gcf, u, v, wb, vis = case(90 + n, N, M, W, Q, gh, gw, n)
+    rng = np.random.default_rng(91)
+    G0 = rng.normal(size=(N, M)) + 1j * rng.normal(size=(N, M))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    forms = [("host", lambda a: a.copy(), lambda a: a), ("dev", t, lambda a: a.cpu().numpy())]
+    for planes, bins in ((W, wb), (1, None)):
+        k, zb = gcf[:planes], (wb if bins is not None else np.zeros(n, np.int64))
+        ref = oracle.convgrid2(k, G0.copy(), u, v, zb, vis)
+        dref = oracle.degrid2(k, G0, u, v, zb)
+        for name, to, back in forms:
+            p = to(np.stack([u, v, u + v], axis=1)) if layout == "matrix" else (to(u), to(v), None)
+            b = None if bins is None else to(bins)
+            got = back(ctx.convgrid2(to(k), to(G0), p, b, to(vis)))
+            d = back(ctx.degrid2(to(k), to(G0), p, b))
+            assert rel(got, ref) < TOL, (name, planes)
+            assert d.shape == (n,) and (n == 0 or rel(d, dref) < TOL), (name, planes)
+            assert ctx.get_option("errors") == 0
+    ref = oracle.grid(G0.copy(), u, v, vis)
+    for name, to, back in forms:
+        p = to(np.stack([u, v, u + v], axis=1)) if layout == "matrix" else (to(u), to(v), None)
+        assert rel(back(ctx.grid(to(G0), p, to(vis))), ref) < TOL, name
+    if n == 0 and layout == "columns":
+        for be, (name, to, back) in zip((HOST, device()), forms):
+            g, k = to(G0), to(gcf)
+            ctx._call(be, "grid", N, M, g, 0, None, None, 1, None)
+            ctx._call(be, "convgrid2", N, M, g, 0, W, Q, gh, gw, k, None, None, 1, None, None)
+            ctx._call(be, "degrid2", N, M, g, 0, W, Q, gh, gw, k, None, None, 1, None, None)
+            assert np.array_equal(back(g), G0), name
+
+
 def test_device_path_is_ordered_with_the_callers_stream(ctx):
     """Regression: torch's current stream is HIP's null stream (pointer 0).  The device-pointer calls
     must be enqueued THERE, behind the kernels that are still producing their inputs; a private
