@@ -47,6 +47,8 @@ module GridHip
   , imagerWeightStatsIO
   , GainSolve(..), gaincalIO, applyGainsIO, imagerSelfcalIO
   , ddcalIO, ddSubtractIO, imagerPeelIO
+  -- * polarisation: 2x2 Jones matrices per antenna, their application, correlations <-> Stokes (absent from the reference)
+  , JonesMode(..), jonescalIO, applyJonesIO, stokesIO
   , FlagOptions(..), flagResidualsIO
   , dftPredictIO, componentsFromImageIO
   , findSourcesIO
@@ -431,6 +433,27 @@ foreign import ccall unsafe "gridhip_dd_subtract_dev"
 -- int gridhip_imager_peel_dev(imager, model, vis, A, T, D, a1, a2, slot, wt, mode, refant, warm, niter, tol, model_vis, gains, vis_cal, wt_cal, stats)
 foreign import ccall unsafe "gridhip_imager_peel_dev"
   c_imager_peel_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_jonescal(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+foreign import ccall unsafe "gridhip_jonescal"
+  c_jonescal :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_jonescal_dev(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+foreign import ccall unsafe "gridhip_jonescal_dev"
+  c_jonescal_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> Int64 -> CInt -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int64_t gridhip_jonescal_lds_antennas()
+foreign import ccall unsafe "gridhip_jonescal_lds_antennas"
+  c_jonescal_lds_antennas :: IO Int64
+-- int gridhip_apply_jones(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_jones"
+  c_apply_jones :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_jones_dev(ctx, n, A, T, a1, a2, slot, gains, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_jones_dev"
+  c_apply_jones_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_stokes(ctx, n, basis, which, inverse, vis, stokes)
+foreign import ccall unsafe "gridhip_stokes"
+  c_stokes :: Ptr Ctx -> Int64 -> CInt -> CInt -> CInt -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_stokes_dev(ctx, n, basis, which, inverse, vis, stokes)
+foreign import ccall unsafe "gridhip_stokes_dev"
+  c_stokes_dev :: Ptr Ctx -> Int64 -> CInt -> CInt -> CInt -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_flag_residuals(ctx, n, G, group, vis, model_vis, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats, stats)
 foreign import ccall unsafe "gridhip_flag_residuals"
   c_flag_residuals :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
@@ -1488,6 +1511,65 @@ ddSubtractIO h@(GridHip c) gains models directions ant1 ant2 slot vis = do
     withVis $ \vs -> withForeignPtr out $ \po ->
       c_dd_subtract c (fi n) (fi nant) (fi nslots) (fi nd) a1 a2 sl g ms (fi dirs) vs po >>= check h
   return (A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr out))
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Polarisation (include/gridhip.h, "polarisation"): a sample is four correlations, an [n][2][2] array; the gains are
+-- [nslots][nant][2][2] Jones matrices.
+
+-- | what a Jones solve solves for: a full 2x2 matrix per antenna, one gain per feed, or one phase per feed
+data JonesMode = JonesFull | JonesDiagonal | JonesPhase
+
+jonesModeCode :: JonesMode -> CInt
+jonesModeCode JonesFull = 0
+jonesModeCode JonesDiagonal = 1
+jonesModeCode JonesPhase = 2
+
+-- | jonescalIO h mode solve nant nslots ant1 ant2 slot wt vis model: the [nslots][nant][2][2] Jones matrices of
+-- vis ~ G_p model G_q^H starting from the identity, and the 8 stats - the host form, synchronous.  gainPhaseOnly of
+-- `solve` is not looked at: the mode says it.
+jonescalIO :: GridHip -> JonesMode -> GainSolve -> Int -> Int -> A.Vector Antenna -> A.Vector Antenna
+           -> Maybe (A.Vector Antenna) -> Maybe (A.Vector F) -> A.Array A.DIM3 Visibility -> A.Array A.DIM3 Visibility
+           -> IO (A.Array A.DIM4 Visibility, [F])
+jonescalIO h@(GridHip c) jmode solve nant nslots ant1 ant2 slot wt vis model = do
+  let A.Z A.:. n = A.arrayShape ant1
+      (_, ref, niter, tol) = solveCodes solve
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s k) slot
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+  out <- mallocForeignPtrArray (8 * nslots * nant) :: IO (ForeignPtr CDouble)
+  st <- withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 -> withSlot $ \sl -> withWt $ \ps -> withCplx vis $ \vs ->
+          withCplx model $ \ms -> withForeignPtr out $ \po -> allocaArray 8 $ \pst -> do
+            c_jonescal c (fi n) (fi nant) (fi nslots) a1 a2 sl vs ms ps (jonesModeCode jmode) ref 0 niter tol po pst
+              >>= check h
+            map realToFrac <$> peekArray 8 pst
+  return (A.fromForeignPtrs (A.Z A.:. nslots A.:. nant A.:. 2 A.:. 2) (castForeignPtr out), st)
+
+-- | applyJonesIO h inverse gains ant1 ant2 slot wt vis: (the samples, the weights) after the Jones matrices - True: data
+-- corrected, G_p^-1 vis G_q^-H with weights |det G_p| |det G_q| wt and weight 0 where there is no usable matrix; False:
+-- a model corrupted, G_p vis G_q^H - the host form, synchronous
+applyJonesIO :: GridHip -> Bool -> A.Array A.DIM4 Visibility -> A.Vector Antenna -> A.Vector Antenna
+             -> Maybe (A.Vector Antenna) -> Maybe (A.Vector F) -> A.Array A.DIM3 Visibility
+             -> IO (A.Array A.DIM3 Visibility, A.Vector F)
+applyJonesIO h@(GridHip c) inverse gains ant1 ant2 slot wt vis = do
+  let A.Z A.:. n = A.arrayShape ant1
+      A.Z A.:. nslots A.:. nant A.:. _ A.:. _ = A.arrayShape gains
+      withSlot k = maybe (k nullPtr) (\s -> withI64 s k) slot
+      withWt k = maybe (k nullPtr) (\s -> withF s k) wt
+  out <- mallocForeignPtrArray (8 * n) :: IO (ForeignPtr CDouble)
+  wout <- mallocForeignPtrArray n :: IO (ForeignPtr CDouble)
+  withI64 ant1 $ \a1 -> withI64 ant2 $ \a2 -> withSlot $ \sl -> withWt $ \ps -> withCplx gains $ \g ->
+    withCplx vis $ \vs -> withForeignPtr out $ \po -> withForeignPtr wout $ \pw ->
+      c_apply_jones c (fi n) (fi nant) (fi nslots) a1 a2 sl g (if inverse then 1 else 0) vs ps po pw >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. n A.:. 2 A.:. 2) (castForeignPtr out), A.fromForeignPtrs (A.Z A.:. n) (castForeignPtr wout))
+
+-- | stokesIO h circular vis: the [4][n] block of the Stokes rows I, Q, U, V of the [n][2][2] samples (circular: the
+-- basis is RR, RL, LR, LL, else XX, XY, YX, YY) - the host form, synchronous.  Each row is a scalar stream for an imager.
+stokesIO :: GridHip -> Bool -> A.Array A.DIM3 Visibility -> IO (A.Matrix Visibility)
+stokesIO h@(GridHip c) circular vis = do
+  let A.Z A.:. n A.:. _ A.:. _ = A.arrayShape vis
+  out <- mallocForeignPtrArray (8 * n) :: IO (ForeignPtr CDouble)
+  withCplx vis $ \vs -> withForeignPtr out $ \po ->
+    c_stokes c (fi n) (if circular then 1 else 0) 15 0 vs po >>= check h
+  return (A.fromForeignPtrs (A.Z A.:. 4 A.:. n) (castForeignPtr out))
 
 -- | imagerPeelIO im solve nant nslots ant1 ant2 slot wt model vis models: one peel step (gridhip_imager_peel_dev:
 -- predict into row 0 of models, the direction-dependent solve, the subtraction of the directions 1 .. D - 1 and the

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 270 /* 0.2.7 */
+#define GRIDHIP_VERSION 280 /* 0.2.8 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1026,7 +1026,8 @@ int gridhip_imager_mfdeconvolve_dev(gridhip_imager *imager, const double *vis, d
 
 /* ---- gain calibration: per-antenna gains by StEFCal, their application, and a selfcal step, on the device ----------------
  * The reference has no calibration: the semantics are defined here.  Scalar, single-polarisation, direction-independent
- * antenna gains (StEFCal: Salvini & Wijnholds 2014) with solution intervals.  Inputs: n visibilities V_k (vis) and model
+ * antenna gains (StEFCal: Salvini & Wijnholds 2014; 2x2 Jones matrices: "polarisation" below) with solution intervals.
+ * Inputs: n visibilities V_k (vis) and model
  * visibilities M_k (model_vis), complex as interleaved doubles; the antenna pairs p_k = a1[k], q_k = a2[k], each in
  * [0, A); the solution interval t_k = slot[k] in [0, T), or slot == NULL with T == 1; data weights s_k (wt: n doubles, or
  * NULL for all ones).  The measurement equation is V_k ~ g[t,p] M_k conj(g[t,q]); gains is [T][A] complex.
@@ -1206,6 +1207,116 @@ int gridhip_imager_peel_dev(gridhip_imager *imager, const double *model, const d
                             const int64_t *a1, const int64_t *a2, const int64_t *slot, const double *wt, int mode,
                             int64_t refant, int warm, int64_t niter, double tol, double *model_vis, double *gains,
                             double *vis_cal, double *wt_cal, double *stats);
+
+/* ---- polarisation: 2x2 Jones matrices per antenna by the matrix StEFCal, their application, correlations <-> Stokes --------
+ * The reference has no calibration: the semantics are defined here, on top of "gain calibration" above.  A sample is four
+ * correlations: vis and model_vis are [n][2][2] complex, row-major - XX, XY, YX, YY (or RR, RL, LR, LL) as interleaved
+ * doubles, 64 B per sample; gains is [T][A][2][2] complex, a Jones matrix G[t,a] per (interval, antenna).  The measurement
+ * equation is V_k ~ G[t,p] M_k G[t,q]^H.  n, A, T, a1, a2, slot, wt (ONE weight per sample, shared by its four
+ * correlations), refant, warm, niter, tol and stats are gridhip_gaincal's, and so are the classes FLAGGED, DROPPED and AUTO:
+ * a flagged sample contributes exactly nothing even when any of its eight numbers, or of the model's, is NaN or Inf
+ * (selected out, not multiplied by zero).  There are no per-correlation flags: a sample with one bad correlation is flagged
+ * by its weight.
+ * PRODUCTS.  Every 2x2 product is C[i][j] = X[i][0] Y[0][j] + X[i][1] Y[1][j]: two complex products, each (a c - b d) +
+ * (a d + b c) i with every product and every sum rounded (no fused multiply-add), then added.  X^H is exact (transpose,
+ * the imaginary signs flipped).  |X|_F^2 = ((|x00|^2 + |x01|^2) + |x10|^2) + |x11|^2, |x|^2 = re re + im im.
+ *     start     G = I everywhere, or the caller's gains when warm != 0; in modes 1 and 2 the off-diagonal entries of the
+ *               start are replaced by +0.0
+ *     iteration i = 0, 1, ... with the current G, for every used k with s = s_k, p, q, t:
+ *               toward p:  Z = M_k G[t,q]^H;    sZ = s Z entry by entry;  num[t,p] += V_k (sZ)^H;    den[t,p] += Z (sZ)^H
+ *               toward q:  Z = M_k^H G[t,p]^H;  sZ = s Z;                 num[t,q] += V_k^H (sZ)^H;  den[t,q] += Z (sZ)^H
+ *               den is Hermitian: d00 and d11 (the real parts of its diagonal) and d01 (complex) are kept, 4 doubles
+ *               beside the 8 of num.
+ *               mode 0 (full Jones): (t, a) is SOLVABLE in this iteration iff d00 > 0, d11 > 0 and e > 1e-12 * d11 with
+ *               e = d11 - |d01|^2 / d00, the second pivot of the LDL^H of den without pivoting (a NaN fails).  Then
+ *               G' = num den^-1 by that LDL^H: with c = d01 / d00, for each row (n0, n1) of num the row of G' is
+ *               x1 = (n1 - n0 c) / e,  x0 = n0 / d00 - x1 conj(c).  Else G' = G, the very bits, and none of the rules
+ *               below touches it (UNSOLVED in this iteration).
+ *               mode 1 (diagonal): solvable iff d00 > 0 and d11 > 0.  G'00 = num00 / d00, G'11 = num11 / d11, the
+ *               off-diagonals are +0.0: the same sums with only their diagonals used - the per-feed StEFCal over all
+ *               four correlations.
+ *               mode 2 (diagonal, phase only): mode 1, then each diagonal entry is divided by its modulus where that is
+ *               > 0, else it is G's entry (gridhip_gaincal's rule).
+ *               on odd i: G' <- (G' + G) / 2 entry by entry
+ *               rel = sqrt(sum |G' - G|_F^2 / sum |G'|_F^2) over all (t, a);  then G <- G';  stop when tol > 0 and
+ *               rel <= tol
+ *     after the loop (t, a) is UNSOLVED when it was never solvable: its gain is exactly the start's, and it is counted.
+ *               If refant >= 0, every entry of every solved G[t,a] of an interval is multiplied by the one scalar
+ *               conj(r) / |r| with r = G[t,refant][0][0] (the off-diagonals of modes 1 and 2 stay +0.0), and
+ *               G[t,refant][0][0] itself becomes (|r|, 0).  An interval whose reference antenna is unsolved, or whose r
+ *               is zero or not finite, is left unrotated.  Only a common phase is taken out: it is the only gauge
+ *               freedom that holds for an arbitrary polarised model (G -> G U needs U M_k U^H = M_k for every k).
+ *     stats     8 doubles in gridhip_gaincal's layout; chi^2 = sum s_k |V_k - (G_p M_k) G_q^H|_F^2 over the used k, at the
+ *               final gains and at G = I (|V_k - M_k|_F^2); "unsolved" counts the (t, a) that were never solvable.
+ * With G = g I and M_k = m_k I the iteration is gridhip_gaincal's on the scalar stream, up to the order of the products;
+ * mode 2 is then its phase-only mode.
+ * All arguments are checked before anything is touched.  GRIDHIP_EINVAL: every refusal of gridhip_gaincal, with mode in
+ * 0..2 and gains, vis and model_vis at their sizes here in the overlap test (gains overlapping an input is refused).
+ * A * T above 2^21 is GRIDHIP_EUNSUPPORTED.  n = 0 is valid.
+ * gridhip_jonescal is synchronous and stages host arrays through the context's pool.  gridhip_jonescal_dev takes device
+ * pointers and enqueues kernels only on the context's stream - no memset node, no copy node; it allocates nothing after
+ * the first call of a shape (the scratch - 16 B per visibility, 100 B per (t, a) - comes from the context's pool), never
+ * synchronises and reads nothing back: niter iterations are enqueued unconditionally and a launch that finds the state
+ * stopped returns at its first instruction, so a solve can be captured into a graph as one linear chain.
+ * A solve is: one pass that classifies the samples and leaves the packed 8-byte key and the weight per visibility; per
+ * iteration a kernel that streams those 16 B and the caller's V and M (144 B per visibility, where gaincal streams 32 B:
+ * no product of V and M can be formed once per solve, the gain stands between them) - a work-group takes a contiguous
+ * range of whole chunks of 4096 visibilities, keeps the gains (8 doubles) and the sums (12 doubles) of one interval in
+ * LDS, 160 bytes per antenna, adds with LDS fp64 atomics (24 per visibility) and flushes to a global [T][A][12] table when
+ * the interval changes - and a one-work-group kernel that forms G', rel and the stop test and zeroes the table; then the
+ * rotation, and one more pass for chi^2.
+ * LDS BUDGET.  The LDS path serves A <= gridhip_jonescal_lds_antennas() = 512, 80 KiB of the 160 KiB a gfx950 CU has: the
+ * limit of gridhip_gaincal, so that an array either solver keeps in LDS the other does too.  A CU holds 1024 threads of the
+ * kernel whatever the table takes: as many work-groups as tables (and a word each) fit, each the larger for it - four of
+ * 256 threads up to A = 255, two of 512 up to A = 511, one of 1024 at A = 512.  More antennas add to the global table
+ * directly.  gridhip_jonescal_lds_antennas is a pure host function.
+ * DETERMINISM.  As gridhip_gaincal: the sums over the visibilities meet in fp64 atomics, so gains are reproducible to the
+ * order of those sums (1e-10 of the largest |G| entry) - NOT bit for bit.  Given the gains, rel, chi^2 and the counts are
+ * added in a fixed order. */
+int gridhip_jonescal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                     const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                     int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats);
+int gridhip_jonescal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                         const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
+                         int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats);
+int64_t gridhip_jonescal_lds_antennas(void);
+/* APPLY takes gains [T][A][2][2], vis_in [n][2][2], a1, a2, slot and optionally wt_in (NULL: ones) and wt_out (NULL: not
+ * written); the arguments are gridhip_apply_gains' with the layouts above.
+ *     inverse 1 (correct data)     vis_out = (G_p^-1 vis_in) (G_q^-1)^H with G^-1 = adj(G) / det G: det = g00 g11 - g01 g10,
+ *               every entry of adj(G) = [[g11, -g01], [-g10, g00]] times conj(det), divided by |det|^2.
+ *               wt_out = (wt_in sqrt(|det G_p|^2)) sqrt(|det G_q|^2), which is gridhip_apply_gains' wt |g_p|^2 |g_q|^2 for
+ *               G = g I; for a general Jones matrix it is the scalar approximation of a noise covariance that is no
+ *               longer diagonal.  A sample whose p, q or t is out of range, or that touches a gain whose |det|^2, as fp64
+ *               computes it, is zero or not finite (singular, underflowing or overflowing), gets vis_out = vis_in and
+ *               wt_out = +0.0.
+ *     inverse 0 (corrupt a model)  vis_out = (G_p vis_in) G_q^H, weights copied; out of range: vis_out = vis_in.
+ *     Autocorrelations and flagged samples are applied like any other.  In place (vis_out == vis_in, wt_out == wt_in) is
+ *     allowed; any other overlap of an output with an input or with the other output is refused.  The refusals are
+ *     gridhip_apply_gains'. */
+int gridhip_apply_jones(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                        const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
+                        double *vis_out, double *wt_out);
+int gridhip_apply_jones_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
+                            const int64_t *slot, const double *gains, int inverse, const double *vis_in,
+                            const double *wt_in, double *vis_out, double *wt_out);
+/* STOKES is the bridge to everything that holds one scalar stream.  vis is [n][2][2] complex, stokes is [4][n] complex -
+ * the rows I, Q, U, V, each a contiguous stream that goes into an imager, gridhip_weights, gridhip_flag_residuals,
+ * gridhip_average or gridhip_gaincal as it is.  basis 0 is linear (XX, XY, YX, YY), 1 circular (RR, RL, LR, LL); which is
+ * a bit mask 1..15 over I (1), Q (2), U (4), V (8).  inverse 0 reads vis and writes the selected rows of stokes; the others
+ * are not touched.  With a, b, c, d the correlations 00, 01, 10, 11, real and imaginary parts separately, each sum rounded
+ * once and the halving exact:
+ *     linear    I = (a + d) / 2,  Q = (a - d) / 2,  U = (b + c) / 2,  V = (b - c) / (2i)
+ *     circular  I = (a + d) / 2,  V = (a - d) / 2,  Q = (b + c) / 2,  U = (b - c) / (2i)
+ *     (x + yi) / (2i) = (y / 2) - (x / 2) i:  re = (im b - im c) / 2,  im = (re c - re b) / 2
+ * inverse 1 reads all four rows (which must be 15) and writes vis:
+ *     linear    a = I + Q,  d = I - Q,  b = U + iV,  c = U - iV
+ *     circular  a = I + V,  d = I - V,  b = Q + iU,  c = Q - iU
+ *     x + i y = (re x - im y) + (im x + re y) i,  x - i y = (re x + im y) + (im x - re y) i
+ * This is how four per-Stokes predictions become the model_vis of gridhip_jonescal.  No weights are read or written: the
+ * one weight per sample serves all four streams.  GRIDHIP_EINVAL: a NULL context; n < 0; which outside 1..15; basis or
+ * inverse outside 0..1; inverse with which != 15; a NULL vis or stokes with n > 0; vis overlapping the [4][n] block. */
+int gridhip_stokes(gridhip_ctx *ctx, int64_t n, int basis, int which, int inverse, double *vis, double *stokes);
+int gridhip_stokes_dev(gridhip_ctx *ctx, int64_t n, int basis, int which, int inverse, double *vis, double *stokes);
 
 /* ---- residual flagging: robust per-group clipping of visibility residuals, on the device -----------------------------------
  * The reference has no flagging: the semantics are defined here.  Every other step treats a visibility whose weight is not

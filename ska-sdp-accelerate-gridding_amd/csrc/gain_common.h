@@ -1,6 +1,6 @@
-// What the two gain solvers (gaincal.hip, ddcal.hip) share: the packed key of a visibility, the state block of a solve
-// that stops on the device, the fixed-order sum of a work-group, rounded complex products, the classes of a visibility,
-// and the two one-work-group kernels that open a solve's state and write its 8 statistics.
+// What the gain solvers (gaincal.hip, ddcal.hip, jonescal.hip) share: the packed key of a visibility, the state block of a
+// solve that stops on the device, the fixed-order sum of a work-group, rounded complex products, the classes of a
+// visibility, the two one-work-group kernels that open a solve's state and write its 8 statistics, and the shape rule.
 #pragma once
 #include "common.h"
 #include "imaging.h"
@@ -98,6 +98,17 @@ __global__ void __launch_bounds__(256)
     stats[5] = st->flagged;
     stats[6] = st->dropped;
     stats[7] = (double)st->unsolved;
+}
+
+// the rules the solves and the applies of gaincal.hip and jonescal.hip share: the sizes, the limit on the table
+inline int shape_check(gridhip_ctx *ctx, const char *who, int64_t n, int64_t A, int64_t T, const int64_t *a1,
+                       const int64_t *a2, const int64_t *slot)
+{
+    if (n < 0 || A < 2 || T < 1 || (!slot && T != 1) || (n > 0 && (!a1 || !a2)))
+        return fail(ctx, GRIDHIP_EINVAL, "%s: n >= 0, A >= 2, T >= 1, a slot array unless T == 1, a1 and a2", who);
+    if (A > GC_MAX_TABLE || T > GC_MAX_TABLE || A * T > GC_MAX_TABLE)
+        return fail(ctx, GRIDHIP_EUNSUPPORTED, "%s: A * T above %lld", who, (long long)GC_MAX_TABLE);
+    return GRIDHIP_OK;
 }
 
 }  // namespace

@@ -322,17 +322,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// the rules gaincal and apply_gains share: the sizes, the limit on the table
-int shape_check(gridhip_ctx *ctx, const char *who, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
-                const int64_t *slot)
-{
-    if (n < 0 || A < 2 || T < 1 || (!slot && T != 1) || (n > 0 && (!a1 || !a2)))
-        return fail(ctx, GRIDHIP_EINVAL, "%s: n >= 0, A >= 2, T >= 1, a slot array unless T == 1, a1 and a2", who);
-    if (A > GC_MAX_TABLE || T > GC_MAX_TABLE || A * T > GC_MAX_TABLE)
-        return fail(ctx, GRIDHIP_EUNSUPPORTED, "%s: A * T above %lld", who, (long long)GC_MAX_TABLE);
-    return GRIDHIP_OK;
-}
-
 }  // namespace
 
 int gaincal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,

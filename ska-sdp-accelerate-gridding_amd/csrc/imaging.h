@@ -2,7 +2,7 @@
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
 // msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
-// sources.hip, average.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
+// sources.hip, average.hip, jonescal.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -41,6 +41,7 @@ struct ImagingState {
     bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
     bool flag_lds_raised = false;     // and flag_hist_kernel's LDS path its 64 KB (flag.hip)
     unsigned int ddcal_lds_raised = 0;  // and ddcal_iter_kernel<D> its DD_LDS_BUDGET: bit D (ddcal.hip)
+    bool jonescal_lds_raised = false;   // and jones_iter_kernel its 80 KB (jonescal.hip)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
 };
@@ -516,6 +517,11 @@ int ddcal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, cons
 int dd_subtract_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs, const double *vis_in,
                     double *vis_out);
+
+// ---- polarisation (jonescal.hip) -----------------------------------------------------------------------------------------
+// the most antennas whose Jones matrices and sums of one interval the iteration kernel keeps in LDS, 160 bytes each
+// (gridhip_jonescal_lds_antennas, include/gridhip.h); the chunk, the table limit and the key are gaincal's
+constexpr int JC_LDS_A = 512;
 
 // ---- residual flagging (flag.hip) ------------------------------------------------------------------------------------------
 // the most groups of one call (the bin table is 1 KB per group); the most groups whose bins a work-group of the histogram

@@ -18,6 +18,7 @@
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
 //   gaincal, apply_gains: per-antenna gains by StEFCal and their application (absent from the reference)
+//   jonescal, apply_jones, stokes: 2x2 Jones matrices per antenna, their application, correlations <-> Stokes (likewise)
 //   ddcal, dd_subtract: direction-dependent gains of D directions at once and the subtraction of directions
 //   flag_residuals: robust per-group clipping of visibility residuals (absent from the reference)
 //   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
@@ -550,6 +551,68 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         std::vector<Visibility> out((size_t)n);
         check(gridhip_dd_subtract(ctx_, n, A, T, D, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(gains),
                                   cd(models), dirs, vis.empty() ? nullptr : cd(vis), cd(out)));
+        return out;
+    }
+
+    // ---- polarisation (gridhip_jonescal, gridhip_apply_jones, gridhip_stokes; include/gridhip.h, "polarisation") ----
+    // (Host forms; the device-pointer forms gridhip_jonescal_dev, gridhip_apply_jones_dev, gridhip_stokes_dev and the pure
+    // gridhip_jonescal_lds_antennas are the C header's.)  A sample is four correlations, XX, XY, YX, YY one after the other:
+    // vis and model hold 4 n values, gains 4 A T.
+    enum class JonesMode { Full = 0, Diagonal = 1, Phase = 2 };
+    // The [T][A][2][2] Jones matrices of vis ~ G[slot, a1] model G[slot, a2]^H by the matrix StEFCal, starting from the
+    // identity (or, warm, from `gains`).  data: one weight per sample.  The other arguments are gaincal's.
+    std::vector<Visibility> jonescal(const std::vector<Visibility> &vis, const std::vector<Visibility> &model,
+                                     const std::vector<Int> &a1, const std::vector<Int> &a2, Int A,
+                                     const std::vector<Int> &slot = {}, Int T = 1, const std::vector<F> &data = {},
+                                     JonesMode mode = JonesMode::Full, Int refant = 0, Int niter = 50, F tol = 1e-8,
+                                     GainStats *stats = nullptr, const std::vector<Visibility> *warm = nullptr)
+    {
+        const Int n = (Int)a1.size();
+        if ((Int)vis.size() != 4 * n || (Int)model.size() != 4 * n || (Int)a2.size() != n ||
+            (!slot.empty() && (Int)slot.size() != n) || (!data.empty() && (Int)data.size() != n) || A < 2 || T < 1 ||
+            (warm && (Int)warm->size() != 4 * A * T))
+            throw Error(GRIDHIP_EINVAL, "jonescal: four values per sample, A >= 2, T >= 1, gains of T x A x 2 x 2");
+        std::vector<Visibility> g = warm ? *warm : std::vector<Visibility>((size_t)(4 * A * T));
+        F st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_jonescal(ctx_, n, A, T, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(vis), cd(model),
+                               data.empty() ? nullptr : data.data(), (int)mode, refant, warm ? 1 : 0, niter, tol, cd(g), st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+        return g;
+    }
+    // vis after the [T][A][2][2] Jones matrices: inverse - data corrected, G_p^-1 vis G_q^-H, *wt_out = data |det G_p| |det G_q|
+    // and 0 where there is no usable matrix; else a model corrupted, G_p vis G_q^H, weights copied
+    std::vector<Visibility> apply_jones(const std::vector<Visibility> &gains, Int A, Int T, const std::vector<Visibility> &vis,
+                                        const std::vector<Int> &a1, const std::vector<Int> &a2,
+                                        const std::vector<Int> &slot = {}, bool inverse = true,
+                                        const std::vector<F> &data = {}, std::vector<F> *wt_out = nullptr)
+    {
+        const Int n = (Int)a1.size();
+        if ((Int)vis.size() != 4 * n || (Int)a2.size() != n || (!slot.empty() && (Int)slot.size() != n) ||
+            (!data.empty() && (Int)data.size() != n) || A < 2 || T < 1 || (Int)gains.size() != 4 * A * T)
+            throw Error(GRIDHIP_EINVAL, "apply_jones: four values per sample, gains of T x A x 2 x 2");
+        std::vector<Visibility> out((size_t)(4 * n));
+        if (wt_out) wt_out->assign((size_t)n, 0);
+        check(gridhip_apply_jones(ctx_, n, A, T, a1.data(), a2.data(), slot.empty() ? nullptr : slot.data(), cd(gains),
+                                  inverse ? 1 : 0, cd(vis), data.empty() ? nullptr : data.data(), cd(out),
+                                  wt_out ? wt_out->data() : nullptr));
+        return out;
+    }
+    // The [4][n] block of the Stokes rows I, Q, U, V of the four-correlation stream vis (4 n values); circular: the basis
+    // is RR, RL, LR, LL.  which: the bit mask of the rows to write (I 1, Q 2, U 4, V 8); the others stay zero.
+    std::vector<Visibility> stokes(const std::vector<Visibility> &vis, bool circular = false, int which = 15)
+    {
+        if (vis.size() % 4) throw Error(GRIDHIP_EINVAL, "stokes: four values per sample");
+        std::vector<Visibility> v = vis, out(vis.size());
+        check(gridhip_stokes(ctx_, (Int)(vis.size() / 4), circular ? 1 : 0, which, 0, cd(v), cd(out)));
+        return out;
+    }
+    // The four-correlation stream (4 n values) of the [4][n] block of Stokes rows: how four per-Stokes predictions become
+    // the model of jonescal
+    std::vector<Visibility> stokes_inverse(const std::vector<Visibility> &iquv, bool circular = false)
+    {
+        if (iquv.size() % 4) throw Error(GRIDHIP_EINVAL, "stokes_inverse: four rows of n values");
+        std::vector<Visibility> s = iquv, out(iquv.size());
+        check(gridhip_stokes(ctx_, (Int)(iquv.size() / 4), circular ? 1 : 0, 15, 1, cd(out), cd(s)));
         return out;
     }
 

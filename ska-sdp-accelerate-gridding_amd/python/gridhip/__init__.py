@@ -27,13 +27,14 @@ from ._marshal import (HOST, Handle, aw_kernels, aw_tables, backend, baselines, 
                        auto_args, image_of, imaging_function, in_place, is_torch, mask_of, scale_list)
 from ._marshal import gain_stream, result_array, solve_args, stream_array
 from ._marshal import direction_mask, model_rows
+from ._marshal import jones_array, stokes_args
 from ._marshal import flag_outputs, flag_scalars, flag_stream
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
 from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import group_ids, rotation as _rotation
 from ._marshal import weighting as _weighting
 
-__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas",
+__all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups"]
 
 
@@ -628,6 +629,55 @@ class Context(Handle):
         weights_out = result_array(be, weights_out, be.f64, (n,), "weights_out", vis)
         self._call(be, "apply_gains", n, A, T, a1, a2, slot, gains, int(bool(inverse)), vis, wt, out, weights_out)
         return out, weights_out
+
+    def jonescal(self, vis, model_vis, a1, a2, nant, *, slot=None, nslots=1, weights=None, mode="full", refant=0, niter=50,
+                 tol=1e-8, gains=None):
+        """Jones matrices of the four-correlation stream `vis` (n, 2, 2) against `model_vis` (n, 2, 2) by the matrix
+        StEFCal (gridhip_jonescal[_dev]; include/gridhip.h, "polarisation"): vis ~ G[slot, a1] model_vis G[slot, a2]^H.
+        mode: "full" (a 2x2 matrix per antenna), "diagonal" (one gain per feed, solved over all four correlations) or
+        "phase" (diagonal, |g| = 1).  weights: one per sample, shared by its four correlations.  refant: the antenna
+        whose [0][0] entry is made real and non-negative in every interval - only a common phase is taken out (None:
+        nothing).  gains: an (nslots, nant, 2, 2) complex128 array in the ABI's form to start from, updated in place, or
+        None to start from the identity.  Everything else is Context.gaincal's.  Returns (gains (nslots, nant, 2, 2),
+        stats), stats the 8 values of Context.gaincal."""
+        be = backend(vis)
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, nant, slot, nslots, weights, jones=True)
+        model_vis = jones_array(be, model_vis, n, "model_vis")
+        mode, refant, warm, niter, tol, gains = solve_args(be, mode, refant, niter, tol, gains, A, T, vis, "jones")
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "jonescal", n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats)
+        return gains, stats
+
+    def apply_jones(self, gains, vis, a1, a2, *, slot=None, weights=None, inverse=True, out=None, weights_out=None):
+        """Apply the (nslots, nant, 2, 2) Jones matrices to a four-correlation stream (n, 2, 2)
+        (gridhip_apply_jones[_dev]).  inverse=True corrects data: G[a1]^-1 vis G[a2]^-H and weights |det G[a1]|
+        |det G[a2]| times `weights` (None: ones); a sample whose indices are out of range or that touches a matrix whose
+        |det|^2 is zero or not finite keeps its value and gets the weight +0.0.  inverse=False corrupts a model:
+        G[a1] vis G[a2]^H, weights copied.  out and weights_out: the arrays to write (new ones when None); they may be
+        `vis` and `weights` themselves.  Returns (vis_out, weights_out)."""
+        be = backend(vis)
+        if not hasattr(gains, "shape") or len(gains.shape) != 4 or tuple(gains.shape[2:]) != (2, 2):
+            raise ValueError("gains must be of shape (nslots, nant, 2, 2)")
+        T, A = int(gains.shape[0]), int(gains.shape[1])
+        n, A, T, a1, a2, slot, vis, wt = gain_stream(be, vis, a1, a2, A, slot, T, weights, jones=True)
+        gains = jones_array(be, gains.reshape(T * A, 2, 2), T * A, "gains")
+        out = result_array(be, out, be.c128, (n, 2, 2), "out", vis)
+        weights_out = result_array(be, weights_out, be.f64, (n,), "weights_out", vis)
+        self._call(be, "apply_jones", n, A, T, a1, a2, slot, gains, int(bool(inverse)), vis, wt, out, weights_out)
+        return out, weights_out
+
+    def stokes(self, vis, basis="linear", which="IQUV", inverse=False, out=None):
+        """Correlations <-> Stokes parameters (gridhip_stokes[_dev]).  Forward: `vis` (n, 2, 2) -> the (4, n) block of
+        the rows I, Q, U, V, of which those named in `which` are written - each row is a contiguous stream for
+        Context.imager, weights, flag_residuals, average or gaincal; out: the block to write into (its other rows are
+        not touched), or None for a new one of zeros.  inverse=True: `vis` is the (4, n) block, all four rows, and the
+        result the (n, 2, 2) stream - how four per-Stokes predictions become the model_vis of Context.jonescal.
+        basis: "linear" (XX, XY, YX, YY) or "circular" (RR, RL, LR, LL).  The one weight per sample serves all four
+        streams."""
+        be = backend(vis)
+        args, out = stokes_args(be, vis, basis, which, inverse, out)
+        self._call(be, "stokes", *args)
+        return out
 
     def flag_residuals(self, vis, model_vis=None, group=None, G=None, weights=None, nsigma=5.0, amax=0.0, min_count=8,
                        niter=3, out=None):
@@ -1306,6 +1356,12 @@ def ddcal_lds_antennas(D):
     """The most antennas whose gains and sums of one interval Context.ddcal's iteration kernel keeps in LDS for D
     directions (gridhip_ddcal_lds_antennas): more antennas add to global memory directly.  0 for D outside 1..8."""
     return int(_lib.load().gridhip_ddcal_lds_antennas(int(D)))
+
+
+def jonescal_lds_antennas():
+    """The most antennas whose Jones matrices and sums of one interval Context.jonescal's iteration kernel keeps in LDS
+    (gridhip_jonescal_lds_antennas): more antennas add to global memory directly."""
+    return int(_lib.load().gridhip_jonescal_lds_antennas())
 
 
 def flag_groups(a1, a2, slot=None, by="baseline"):

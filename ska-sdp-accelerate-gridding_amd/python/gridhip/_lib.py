@@ -55,6 +55,7 @@ _WEIGHTING = [ci, C.c_double, C.c_double, vp]  # mode, robust, taper_sigma, wt_i
 _GAINCAL = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]
 _APPLY_GAINS = [vp, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
 _DDCAL = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp]  # gaincal's, D after T
+_STOKES = [vp, i64, ci, ci, ci, vp, vp]  # n, basis, which, inverse, vis, stokes
 _DD_SUBTRACT = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp]
 _FLAG_ARGS = [C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]  # nsigma, amax, min_count, niter, then the four outputs
 _FLAG = [vp, i64, i64, vp, vp, vp, vp, *_FLAG_ARGS]
@@ -198,6 +199,13 @@ SIGNATURES = {
     "gridhip_dd_subtract_dev": (ci, _DD_SUBTRACT),
     "gridhip_imager_peel_dev": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, ci, i64, ci, i64, C.c_double, vp, vp, vp, vp,
                                      vp]),
+    "gridhip_jonescal": (ci, _GAINCAL),
+    "gridhip_jonescal_dev": (ci, _GAINCAL),
+    "gridhip_jonescal_lds_antennas": (i64, []),
+    "gridhip_apply_jones": (ci, _APPLY_GAINS),
+    "gridhip_apply_jones_dev": (ci, _APPLY_GAINS),
+    "gridhip_stokes": (ci, _STOKES),
+    "gridhip_stokes_dev": (ci, _STOKES),
     "gridhip_flag_residuals": (ci, _FLAG),
     "gridhip_flag_residuals_dev": (ci, _FLAG),
     "gridhip_imager_flag_dev": (ci, [vp, vp, vp, i64, vp, vp, *_FLAG_ARGS]),

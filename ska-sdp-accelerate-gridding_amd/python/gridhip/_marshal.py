@@ -365,10 +365,25 @@ def result_array(be, x, dt, shape, what, like):
     return x
 
 
-def gain_stream(be, vis, a1, a2, nant, slot, nslots, weights):
+def jones_array(be, x, n, what):
+    """a four-correlation stream or a table of Jones matrices as the ABI takes it: (n, 2, 2) complex values (n < 0: any
+    number of them), converted to contiguous complex128 where they must be"""
+    if x is None or (be is not backend(x) and be is not HOST):
+        raise ValueError(f"{what} must be a {be.array}")
+    if be is HOST:
+        x = np.asarray(x)
+    shape = tuple(int(v) for v in x.shape)
+    if len(shape) != 3 or shape[1:] != (2, 2) or (n >= 0 and shape[0] != n):
+        raise ValueError(f"{what} must be of shape ({'n' if n < 0 else n}, 2, 2): XX, XY, YX, YY per sample, not {shape}")
+    return be.cv(x, be.c128)
+
+
+def gain_stream(be, vis, a1, a2, nant, slot, nslots, weights, jones=False):
     """n, A, T, a1, a2, slot, vis, wt as gridhip_gaincal, gridhip_apply_gains and gridhip_imager_selfcal_dev take the
-    visibility stream: slot None goes as NULL and needs nslots == 1."""
-    vis = stream_array(be, vis, be.c128, -1, "vis")  # (its length is the stream's: any one-dimensional array)
+    visibility stream: slot None goes as NULL and needs nslots == 1.  jones: vis is (n, 2, 2), the four correlations of
+    every sample (gridhip_jonescal, gridhip_apply_jones)."""
+    # (its length is the stream's: any one-dimensional array)
+    vis = jones_array(be, vis, -1, "vis") if jones else stream_array(be, vis, be.c128, -1, "vis")
     n, A, T = int(vis.shape[0]), int(nant), int(nslots)
     if A < 2 or T < 1:
         raise ValueError("nant must be >= 2 and nslots >= 1")
@@ -379,11 +394,17 @@ def gain_stream(be, vis, a1, a2, nant, slot, nslots, weights):
     return n, A, T, a1, a2, slot, vis, stream_array(be, weights, be.f64, n, "weights")
 
 
+JONES_MODES = {"full": 0, "diagonal": 1, "phase": 2}  # gridhip_jonescal's mode
+
+
 def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like, D=None):
     """mode, refant, warm, niter, tol, gains as the solving entry points take them: refant None is -1 (no rotation); gains
     None starts from 1 in a new [T][A] array ([D][T][A] with D, the direction-dependent solves), a given one - in the
-    ABI's form: it is updated in place - is the warm start."""
+    ABI's form: it is updated in place - is the warm start.  D == "jones": phase_only is gridhip_jonescal's mode by name
+    and the gains are [T][A][2][2]."""
     import math
+    if D == "jones" and phase_only not in JONES_MODES:
+        raise ValueError(f"mode must be one of {sorted(JONES_MODES)}, not {phase_only!r}")
     refant = -1 if refant is None else int(refant)
     niter, tol = int(niter), float(tol)
     if refant >= A:
@@ -391,8 +412,40 @@ def solve_args(be, phase_only, refant, niter, tol, gains, A, T, like, D=None):
     if niter < 0 or not (tol >= 0.0 and math.isfinite(tol)):
         raise ValueError("niter must be >= 0 and tol finite and >= 0")
     warm = int(gains is not None)
-    gains = result_array(be, gains, be.c128, (T, A) if D is None else (D, T, A), "gains", like)
-    return int(bool(phase_only)), refant, warm, niter, tol, gains
+    shape = (T, A) if D is None else (T, A, 2, 2) if D == "jones" else (D, T, A)
+    gains = result_array(be, gains, be.c128, shape, "gains", like)
+    return JONES_MODES[phase_only] if D == "jones" else int(bool(phase_only)), refant, warm, niter, tol, gains
+
+
+STOKES_BITS = {"I": 1, "Q": 2, "U": 4, "V": 8}
+STOKES_BASES = {"linear": 0, "circular": 1}
+
+
+def stokes_args(be, vis, basis, which, inverse, out):
+    """n, basis, which, inverse, vis, stokes as gridhip_stokes takes them.  Forward: vis (n, 2, 2) is read and `out`, the
+    (4, n) block whose selected rows are written, is the caller's own or a new one of zeros.  Inverse: vis is the (4, n)
+    block, all four rows, and `out` the (n, 2, 2) stream to write.  -> (the arguments, the array the caller gets back)"""
+    if basis not in STOKES_BASES:
+        raise ValueError(f"basis must be one of {sorted(STOKES_BASES)}, not {basis!r}")
+    letters = str(which).upper()
+    if not letters or any(c not in STOKES_BITS for c in letters) or len(set(letters)) != len(letters):
+        raise ValueError(f"which must name some of I, Q, U, V once each, not {which!r}")
+    mask = sum(STOKES_BITS[c] for c in letters)
+    if inverse:
+        if mask != 15:
+            raise ValueError("the inverse form reads all four rows: which must be 'IQUV'")
+        if vis is None or (be is not backend(vis) and be is not HOST):
+            raise ValueError(f"vis must be a {be.array}")
+        block = be.cv(np.asarray(vis) if be is HOST else vis, be.c128)
+        if len(block.shape) != 2 or int(block.shape[0]) != 4:
+            raise ValueError(f"the Stokes block must be of shape (4, n), not {tuple(block.shape)}")
+        n = int(block.shape[1])
+        out = result_array(be, out, be.c128, (n, 2, 2), "out", block)
+        return (n, STOKES_BASES[basis], mask, 1, out, block), out
+    vis = jones_array(be, vis, -1, "vis")
+    n = int(vis.shape[0])
+    out = be.zeros((4, n), be.c128, vis) if out is None else result_array(be, out, be.c128, (4, n), "out", vis)
+    return (n, STOKES_BASES[basis], mask, 0, vis, out), out
 
 
 DD_MAX_DIRECTIONS = 8  # the most directions of gridhip_ddcal
