@@ -496,6 +496,18 @@ foreign import ccall unsafe "gridhip_average"
 -- int gridhip_average_dev(ctx, n, G, group, R, u, v, w, uv_stride, x, vis, wt, u_out, v_out, w_out, out_stride, x_out, vis_out, wt_out, count_out, stats)
 foreign import ccall unsafe "gridhip_average_dev"
   c_average_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_mosaic(ctx, F, Ns, theta_s, facets, weights, R, kind, inner, outer, normalize, wmin, blank, Nd, theta_d, out, wsum, stats)
+foreign import ccall unsafe "gridhip_mosaic"
+  c_mosaic :: Ptr Ctx -> Int64 -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> CInt -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_mosaic_dev(ctx, F, Ns, theta_s, facets, weights, R, kind, inner, outer, normalize, wmin, blank, Nd, theta_d, out, wsum, stats)
+foreign import ccall unsafe "gridhip_mosaic_dev"
+  c_mosaic_dev :: Ptr Ctx -> Int64 -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> CInt -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_reproject(ctx, Ns, theta_s, image, R, kind, inner, outer, blank, Nd, theta_d, out)
+foreign import ccall unsafe "gridhip_reproject"
+  c_reproject :: Ptr Ctx -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_reproject_dev(ctx, Ns, theta_s, image, R, kind, inner, outer, blank, Nd, theta_d, out)
+foreign import ccall unsafe "gridhip_reproject_dev"
+  c_reproject_dev :: Ptr Ctx -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 280 /* 0.2.8 */
+#define GRIDHIP_VERSION 290 /* 0.2.9 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -135,6 +135,8 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               100 + t: widen the record's kernel-slice field until its fields take t <= 64 bits
  *   "dft_slices"  gridhip_dft_predict: the slices S the component list is cut into; 0 = auto (a function of n and C
  *               alone), 1..64 = that many (values above 64 count as 64)
+ *   "mosaic_cull"  gridhip_mosaic: 0 = every tile walks the facets its cull keeps, 1 = every tile walks all valid facets
+ *               (the same bits: kept for comparison runs)
  *   ("dbg", the ablation / profiling switch of tuning runs, exists only in the tuning build of the library,
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
@@ -1641,6 +1643,77 @@ int gridhip_average_dev(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *g
                         const double *v, const double *w, int64_t uv_stride, const double *x, const double *vis,
                         const double *wt, double *u_out, double *v_out, double *w_out, int64_t out_stride, double *x_out,
                         double *vis_out, double *wt_out, int64_t *count_out, double *stats);
+
+/* ---- reprojection and mosaicking: images on other tangent planes brought onto one plane and combined, on the device --------
+ * The reference has neither: the semantics are defined here.  gridhip_phase_shift makes a stream about any centre, so that any
+ * patch of the sky - a facet - is imaged about its own centre; gridhip_mosaic brings F such images back onto ONE tangent plane,
+ * and gridhip_reproject, its F = 1 case, also takes a model on the full plane to a facet's plane for gridhip_imager_predict_dev.
+ *     facets    F contiguous Ns x Ns real fp64 images, row-major [f][y][x], all with the field of view theta_s.  Cell (x, y)
+ *               lies at l = theta (x - N/2) / N, m = theta (y - N/2) / N (N/2 the integer half): gridhip_dft_predict's
+ *               convention.
+ *     weights   NULL, or F x Ns x Ns fp64 laid out the same way: a primary-beam power, an inverse variance.
+ *     R         F x 9 doubles, row-major: R_f is the rotation from the DESTINATION frame to facet f's frame - exactly what
+ *               gridhip_phase_shift was given to make that facet.  HOST memory in the host form; DEVICE memory in the _dev
+ *               form, so that a call can be captured with any F: a prologue kernel of every call judges it on the device.
+ *               A facet whose R_f is not finite, has R22 <= 0 or has an entry of |R R^T - I| above 1e-9 (phase_shift's rule)
+ *               contributes nothing and is counted: it is not an error.
+ *     out       Nd x Nd, field of view theta_d.  wsum (may be NULL): Nd x Nd, the weight sum of every cell.
+ *     kind      0 nearest cell, 1 bilinear, 3 Keys' cubic convolution (a = -1/2).
+ *     inner, outer   the feather window in facet cells, measured from the facet's centre cell Ns/2 on either axis.
+ * THE RULE FOR ONE DESTINATION CELL (x, y).  Every product and sum is rounded, contraction is off, sums go left to right.
+ *     1. l = theta_d (x - Nd/2) / Nd, m likewise, r2 = l l + m m.  If not r2 < 1 the cell lies BEYOND THE HORIZON: it is
+ *        blank and no facet is looked at.  Otherwise n = sqrt(1 - r2).
+ *     2. For f = 0 .. F-1 in ascending order, over the valid facets only:
+ *            l' = (R00 l + R01 m) + R02 n,  m' = (R10 l + R11 m) + R12 n,  n' = (R20 l + R21 m) + R22 n.
+ *        If not n' > 0 the facet does not cover the cell.
+ *     3. fx = (l' * Ns) / theta_s + (double)(Ns/2), fy likewise from m'.
+ *     4. WINDOW.  dx = |fx - Ns/2|, dy likewise.  s(d) = 1 if d <= inner; else 0 if d >= outer; else with
+ *            t = (outer - d) / (outer - inner),   s(d) = (t t) (3 - 2 t).
+ *        w = s(dx) s(dy).  If w == 0 the facet does not cover the cell.
+ *     5. SAMPLE v.
+ *            kind 0   the cell (floor(0.5 + fx), floor(0.5 + fy)): the gridders' tie rule.
+ *            kind 1   i = floor(fx), t = fx - i; a row is a (1 - t) + b t; the two rows are combined the same way in y.
+ *            kind 3   taps i-1 .. i+2 with the coefficients in Horner form
+ *                         c0 = ((-0.5 t + 1) t - 0.5) t      c1 = ((1.5 t - 2.5) t) t + 1
+ *                         c2 = ((-1.5 t + 2) t + 0.5) t      c3 = ((0.5 t - 0.5) t) t
+ *                     a row is ((c0 a + c1 b) + c2 c) + c3 d; the four rows are combined the same way in y.
+ *        ALL TAPS of the footprint must lie inside the facet, otherwise the facet does not cover the cell (Ns < 4 never
+ *        covers anything with kind 3, Ns < 2 nothing with kind 1).  If any tap is not finite the sample is LEFT OUT and
+ *        counted.
+ *     6. With a weight image: q = its bilinear sample at (fx, fy), which needs the bilinear footprint inside the facet; if
+ *        q is not finite or not > 0 the facet does not cover the cell; otherwise w = w q.
+ *     7. num = num + w v, den = den + w.  A facet that does not cover a cell CONTRIBUTES NOTHING - not 0 * v: a NaN under a
+ *        zero weight or outside the window never reaches the output.
+ *     8. Where den > wmin: out = num / den if normalize, else num; wsum = den.  Otherwise out = blank and wsum = +0.0.
+ *     stats     optional, 8 doubles { destination cells covered, cells blank, facets used, facets refused, facet samples
+ *               left out because a tap was not finite, the largest number of facets covering one cell, 0, 0 }.
+ * gridhip_reproject is gridhip_mosaic with F = 1, no weight image, normalize = 1, wmin = 0 and neither wsum nor stats: the
+ * same body.  The way back from the full plane to facet f is R_f^T.
+ * Refused before anything is touched, GRIDHIP_EINVAL: a NULL context, facets, R or out; F < 1, Ns < 1 or Nd < 1; a theta
+ * that is not finite or not > 0; kind outside {0, 1, 3}; inner < 0, outer < inner or either not finite; wmin negative or
+ * NaN; any output overlapping an input or another output.  F above 4096 and Ns or Nd above 32768 are GRIDHIP_EUNSUPPORTED.
+ * The host forms are synchronous and stage through the context's pool.  The _dev forms take device pointers and enqueue
+ * kernels only on the context's stream - no memset node, no copy node; the scratch (256 B and 80 B per facet) comes from the
+ * context's pool, so nothing is allocated after the first call of a shape; they never synchronise and read nothing back, so
+ * they can be captured into a graph.  A call is 2 launches, 3 with stats: the prologue that judges every R_f; one thread per
+ * destination cell in 16 x 16 tiles, each tile first culling the facets into a list in LDS, in ascending order - the
+ * accumulation order, so the cull changes no bit (option "mosaic_cull") - by a bound that holds on the sphere: the tile's
+ * box in (l, m, n), on which R is linear (mosaic.hip); the stats.
+ * DETERMINISM.  every cell's sums belong to one thread: no floating-point atomic, no order that depends on scheduling; the
+ * counts use integer atomics.  fp64 multiply, add, divide, sqrt and floor are correctly rounded, so the bits are the same
+ * for the host and _dev forms, for every run, and for a numpy restatement of the rule (tests/mosaic_ref.py).
+ * OUT OF SCOPE.  flux conservation for Jy-per-pixel models (a pixel's solid angle changes between planes: a component list
+ * through gridhip_components_from_image is the exact route); Lanczos or sinc kernels; primary-beam models. */
+int gridhip_mosaic(gridhip_ctx *ctx, int64_t F, int64_t Ns, double theta_s, const double *facets, const double *weights,
+                   const double *R, int kind, double inner, double outer, int normalize, double wmin, double blank, int64_t Nd,
+                   double theta_d, double *out, double *wsum, double *stats);
+int gridhip_mosaic_dev(gridhip_ctx *ctx, int64_t F, int64_t Ns, double theta_s, const double *facets, const double *weights,
+                       const double *R, int kind, double inner, double outer, int normalize, double wmin, double blank,
+                       int64_t Nd, double theta_d, double *out, double *wsum, double *stats);
+int gridhip_reproject(gridhip_ctx *ctx, int64_t Ns, double theta_s, const double *image, const double *R, int kind,
+                      double inner, double outer, double blank, int64_t Nd, double theta_d, double *out);
+int gridhip_reproject_dev(gridhip_ctx *ctx, int64_t Ns, double theta_s, const double *image, const double *R, int kind,
+                          double inner, double outer, double blank, int64_t Nd, double theta_d, double *out);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -516,6 +516,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "bin_reuse")) return &ctx->opt.bin_reuse;
     if (!strcmp(key, "noise_bits")) return &ctx->img->noise_bits;  // image_stats' digit: 8, or anything else for 13
     if (!strcmp(key, "dft_slices")) return &ctx->img->dft_slices;  // dft_predict's component slices: 0 = auto, 1..64
+    if (!strcmp(key, "mosaic_cull")) return &ctx->img->mosaic_cull;  // mosaic's per-tile cull: 0 = on, 1 = every valid facet
     return nullptr;
 }
 

@@ -2,7 +2,7 @@
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
 // msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
-// sources.hip, average.hip, jonescal.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
+// sources.hip, average.hip, jonescal.hip, mosaic.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -44,6 +44,7 @@ struct ImagingState {
     bool jonescal_lds_raised = false;   // and jones_iter_kernel its 80 KB (jonescal.hip)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
+    int64_t mosaic_cull = 0;          // option "mosaic_cull": 1 = every tile of gridhip_mosaic walks all valid facets (the same bits)
 };
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled
@@ -598,5 +599,18 @@ int sources_run(gridhip_ctx *ctx, int64_t N, double theta, const double *image, 
                 double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac, int64_t min_cells,
                 const double *beam, int correct, int64_t max_c, double *comps, double *info, int64_t *count, double *stats,
                 void *am_scratch, void *scratch);
+
+// ---- reprojection and mosaicking (mosaic.hip) ------------------------------------------------------------------------------
+// gridhip_mosaic's argument rules (GRIDHIP_EINVAL, then GRIDHIP_EUNSUPPORTED); nothing is read
+int mosaic_check(gridhip_ctx *ctx, int64_t F, int64_t Ns, double theta_s, const double *facets, const double *weights,
+                 const double *R, int kind, double inner, double outer, double wmin, int64_t Nd, double theta_d,
+                 const double *out, const double *wsum, const double *stats);
+// the counter block and 80 B per facet (R_f and its verdict)
+size_t mosaic_scratch_bytes(int64_t F);
+// gridhip_mosaic_dev on checked arguments: kernels only, on ctx->stream; scratch: mosaic_scratch_bytes(F).  R is device
+// memory: the prologue kernel judges it
+int mosaic_run(gridhip_ctx *ctx, int64_t F, int64_t Ns, double theta_s, const double *facets, const double *weights,
+               const double *R, int kind, double inner, double outer, int normalize, double wmin, double blank, int64_t Nd,
+               double theta_d, double *out, double *wsum, double *stats, void *scratch);
 
 }  // namespace gridhip

@@ -23,6 +23,7 @@
 //   flag_residuals: robust per-group clipping of visibility residuals (absent from the reference)
 //   dft_predict, components_from_image: the exact visibilities of a component list (absent from the reference)
 //   find_sources: a map as a list of Gaussian components - islands, moments, the beam deconvolved (absent from the reference)
+//   mosaic, reproject: images on other tangent planes brought onto one plane and combined (absent from the reference)
 //   (phase shift and averaging, gridhip_phase_shift / gridhip_average, have no mirror here: the C ABI and the Python binding carry them)
 //   aw_gridding                                     src/ImageDataset.hs:29-86 (after the HDF5 reads)
 //   mirror_uvw, doweight, make_grid_hermitian, ifft, w_kernel, findClosest
@@ -721,6 +722,42 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         if (info) info->resize(rows * GRIDHIP_SRC_DOUBLES);
         if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
         return comps;
+    }
+
+    // ---- reprojection and mosaicking (gridhip_mosaic, gridhip_reproject; include/gridhip.h, "reprojection and mosaicking") ----
+    // F facets of Ns x Ns cells (facets: F * Ns * Ns doubles, [f][y][x]; field of view theta_s) onto the Nd x Nd plane of
+    // field of view theta_d.  R: 9 doubles per facet, the rotation from the destination frame to the facet's frame - what
+    // phase_shift was given; kind 0 nearest, 1 bilinear, 3 cubic; inner, outer: the feather window in facet cells; weights
+    // empty: none.  A facet whose R is no rotation with R22 > 0 is counted in stats and left out.
+    struct MosaicStats {
+        F covered, blank, used, refused, left_out, most, r6, r7;
+    };
+    Matrix<F> mosaic(Int F_, Int Ns, F theta_s, const std::vector<F> &facets, const std::vector<F> &R, Int Nd, F theta_d,
+                     int kind, F inner, F outer, const std::vector<F> &weights = {}, bool normalize = true, F wmin = 0,
+                     F blank = 0, Matrix<F> *wsum = nullptr, MosaicStats *stats = nullptr)
+    {
+        if (F_ < 1 || Ns < 1 || Nd < 1 || (Int)facets.size() != F_ * Ns * Ns || (Int)R.size() != F_ * 9 ||
+            (!weights.empty() && weights.size() != facets.size()))
+            throw Error(GRIDHIP_EINVAL, "mosaic: F x Ns x Ns facets, 9 doubles of R per facet, weights of the facets' shape");
+        Matrix<F> out(Nd, Nd);
+        if (wsum) *wsum = Matrix<F>(Nd, Nd);
+        F st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(gridhip_mosaic(ctx_, F_, Ns, theta_s, facets.data(), weights.empty() ? nullptr : weights.data(), R.data(), kind,
+                             inner, outer, normalize ? 1 : 0, wmin, blank, Nd, theta_d, out.data.data(),
+                             wsum ? wsum->data.data() : nullptr, st));
+        if (stats) *stats = {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+        return out;
+    }
+    // the one-facet case: no weights, normalised; the way back from the full plane to a facet takes R^T
+    Matrix<F> reproject(const Matrix<F> &image, F theta_s, const std::vector<F> &R, Int Nd, F theta_d, int kind, F inner,
+                        F outer, F blank = 0)
+    {
+        if (image.h != image.w || image.h < 1 || Nd < 1 || R.size() != 9)
+            throw Error(GRIDHIP_EINVAL, "reproject: a square image and the 9 doubles of one rotation");
+        Matrix<F> out(Nd, Nd);
+        check(gridhip_reproject(ctx_, image.h, theta_s, image.data.data(), R.data(), kind, inner, outer, blank, Nd, theta_d,
+                                out.data.data()));
+        return out;
     }
 
     // ---- helpers ----

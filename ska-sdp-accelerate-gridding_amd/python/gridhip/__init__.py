@@ -33,9 +33,10 @@ from ._marshal import COMP_DOUBLES, component_count, component_list, model_plane
 from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import group_ids, rotation as _rotation
 from ._marshal import weighting as _weighting
+from ._marshal import mosaic_args
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
-           "rotation_to", "rotation_radec", "average_groups"]
+           "rotation_to", "rotation_radec", "average_groups", "facet_grid"]
 
 
 class Context(Handle):
@@ -781,6 +782,42 @@ class Context(Handle):
                    vis_g, wt_g, cnt, st8)
         return (uvw_g, vis_g, wt_g, x_g) + ((cnt,) if counts else ()) + ((st8,) if stats else ())
 
+    def mosaic(self, facets, theta_src, R, theta_dst, N_dst, kind="cubic", weights=None, window=None, normalize=True,
+               wmin=0.0, blank=float("nan"), wsum=False, stats=False, out=None):
+        """F images on F tangent planes brought onto one plane and combined (gridhip_mosaic[_dev]; include/gridhip.h,
+        "reprojection and mosaicking").  facets: (F, Ns, Ns) float64, all with the field of view theta_src; R: one
+        rotation per facet, (F, 3, 3) or (F, 9), from the destination frame to the facet's frame - what phase_shift was
+        given to make that facet (facet_grid returns them).  The result is N_dst x N_dst with the field of view theta_dst.
+        kind: "nearest", "bilinear" or "cubic" (Keys, a = -1/2).  weights: None, or an array of the facets' shape (a
+        primary-beam power, an inverse variance); a sample whose weight is not finite or not > 0 is left out.  window:
+        (inner, outer) in facet cells from the facet's centre - 1 inside inner, 0 from outer on, a smoothstep between, per
+        axis - or None for inner = outer = Ns / 2: every cell whose footprint lies inside the facet takes part (for
+        "nearest", up to half a cell short of that on the low side of an even Ns).  normalize: out = num / den, else num;
+        a cell with den <= wmin or beyond the horizon gets `blank`.  A host R is checked here (ValueError); a cuda R is
+        judged on the device, where a facet with a bad R is counted and left out.  Returns out, then with wsum=True the
+        weight sum of every cell and with stats=True the 8 values [cells covered, cells blank, facets used, facets
+        refused, samples left out for a tap that is not finite, most facets on one cell, 0, 0].  numpy in gives numpy
+        out; cuda tensors take the device form on torch's stream: nothing is read back, and the call can be captured.
+        The same bits on every run."""
+        be = backend(facets)
+        args = mosaic_args(be, facets, theta_src, R, theta_dst, N_dst, kind, weights, window, normalize, wmin, blank, wsum,
+                           stats, out)
+        self._call(be, "mosaic", *args)
+        res = (args[14],) + ((args[15],) if wsum else ()) + ((args[16],) if stats else ())
+        return res if len(res) > 1 else res[0]
+
+    def reproject(self, image, theta_src, R, theta_dst, N_dst, kind="cubic", window=None, blank=float("nan"), out=None):
+        """One Ns x Ns image on the tangent plane R away from the destination's, resampled onto the destination plane
+        (gridhip_reproject[_dev]): mosaic with one facet, no weights, normalize=True.  R: the 3 x 3 rotation from the
+        destination frame to the image's frame.  A model on the full plane becomes facet f's model with R_f.T:
+        reproject(model, theta, R_f.T, theta_f, N_f), which Imager.predict takes."""
+        be = backend(image)
+        if len(getattr(image, "shape", ())) != 2:
+            raise ValueError("image must be one Ns x Ns image")
+        a = mosaic_args(be, image, theta_src, R, theta_dst, N_dst, kind, None, window, True, 0.0, blank, False, False, out)
+        self._call(be, "reproject", a[1], a[2], a[3], a[5], a[6], a[7], a[8], a[11], a[12], a[13], a[14])
+        return a[14]
+
     def components_from_image(self, theta, lam, model, max_components, out=None):
         """The non-zero cells of a model image as a component list (gridhip_components_from_image[_dev]): model is N x N,
         N = image_size(theta, lam), or (T, N, N) Taylor-term planes as mfclean leaves them; every cell where some term is
@@ -1403,6 +1440,29 @@ def rotation_to(l0, m0):
     n0 = math.sqrt(1.0 - r2)
     k = 1.0 / (1.0 + n0)
     return np.array([[1.0 - k * l0 * l0, -k * l0 * m0, -l0], [-k * l0 * m0, 1.0 - k * m0 * m0, -m0], [l0, m0, n0]])
+
+
+def facet_grid(theta, nf, overlap=0.0, N=1):
+    """nf x nf facets that tile the field of view `theta`: returns (centres, R, theta_f, window).  centres: (F, 2), the
+    (l0, m0) of facet f = j * nf + i at l0 = theta ((i + 1/2) / nf - 1/2), m0 likewise from j; R: (F, 9), rotation_to of
+    every centre - what Context.phase_shift takes to make the facet and Context.mosaic to bring it back; theta_f =
+    (theta / nf) (1 + overlap), the field of view of every facet; window: (inner, outer) in cells of an N x N facet (N = 1:
+    as fractions of the facet's side, to be multiplied by its size) for Context.mosaic.  Neighbouring centres lie
+    D = N / (1 + overlap) cells apart and inner + outer = D, so that along a seam the smoothsteps of the two facets sum to 1:
+    the feathered facets tile the field without a gap.  The feather takes the inner half of the overlap, outer =
+    D / 2 + (N - D) / 4, and leaves the outer half, (N - D) / 4 cells at every edge, to the taps of the interpolation:
+    "cubic" needs 2 cells there (overlap = 0 is a hard window that reaches the facet's edge, which only "nearest"
+    fills).  Plumbing: numpy only."""
+    import numpy as np
+    theta, nf, overlap, N = float(theta), int(nf), float(overlap), float(N)
+    if not (theta > 0.0 and nf >= 1 and overlap >= 0.0 and N > 0.0):
+        raise ValueError("facet_grid needs theta > 0, nf >= 1, overlap >= 0 and N > 0")
+    c = theta * ((np.arange(nf) + 0.5) / nf - 0.5)
+    centres = np.array([(c[i], c[j]) for j in range(nf) for i in range(nf)], dtype=np.float64).reshape(nf * nf, 2)
+    R = np.array([rotation_to(l0, m0).ravel() for l0, m0 in centres]).reshape(nf * nf, 9)
+    D = N / (1.0 + overlap)
+    outer = D / 2 + (N - D) / 4
+    return centres, R, (theta / nf) * (1.0 + overlap), (D - outer, outer)
 
 
 def rotation_radec(ra0, dec0, ra1, dec1):

@@ -68,6 +68,11 @@ _FIND_SOURCES = [vp, C.c_double, i64, vp, *_FIND_SOURCES_ARGS]
 # R is the host's in both forms (9 doubles, read at the call)
 _PHASE_SHIFT = [vp, i64, _HOST_F64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
 _AVERAGE = [vp, i64, i64, vp, _HOST_F64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+# F, Ns, theta_s, facets, weights, R, kind, inner, outer, normalize, wmin, blank, Nd, theta_d, out, wsum, stats; R is an
+# array of the form's own kind (host memory in the host form, device memory in the _dev form)
+_MOSAIC = [vp, i64, i64, C.c_double, vp, vp, vp, ci, C.c_double, C.c_double, ci, C.c_double, C.c_double, i64, C.c_double,
+           vp, vp, vp]
+_REPROJECT = [vp, i64, C.c_double, vp, vp, ci, C.c_double, C.c_double, C.c_double, i64, C.c_double, vp]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -220,6 +225,10 @@ SIGNATURES = {
     "gridhip_phase_shift_dev": (ci, _PHASE_SHIFT),
     "gridhip_average": (ci, _AVERAGE),
     "gridhip_average_dev": (ci, _AVERAGE),
+    "gridhip_mosaic": (ci, _MOSAIC),
+    "gridhip_mosaic_dev": (ci, _MOSAIC),
+    "gridhip_reproject": (ci, _REPROJECT),
+    "gridhip_reproject_dev": (ci, _REPROJECT),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

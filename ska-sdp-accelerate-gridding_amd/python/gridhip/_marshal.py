@@ -577,6 +577,76 @@ def rotation(R):
     return R.ctypes.data_as(C.POINTER(C.c_double)), R
 
 
+MOSAIC_KINDS = {"nearest": 0, "bilinear": 1, "cubic": 3}  # gridhip_mosaic's kind
+
+
+def facet_rotations(be, R, F, like):
+    """R as gridhip_mosaic takes it: (F, 9) float64 of `be`'s own kind.  A host array - (F, 3, 3), (F, 9), or one 3 x 3
+    rotation when F == 1 - is checked here by the library's rule (finite, R22 > 0, orthonormal to 1e-9) and, for cuda
+    facets, uploaded; a cuda tensor is left to the rule on the device, where a bad facet is counted and left out."""
+    if is_torch(R) and R.is_cuda:
+        if be is HOST:
+            raise ValueError("R must be a host array when the facets are numpy arrays")
+        R = be.cv(R, be.f64)
+        if R.numel() != 9 * F:
+            raise ValueError(f"R must hold one 3 x 3 rotation per facet ({F}), not {tuple(R.shape)}")
+        return R.reshape(F, 9)
+    if is_torch(R):
+        R = R.detach().numpy()
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if R.size != 9 * F or R.shape[-1] not in (3, 9):
+        raise ValueError(f"R must hold one 3 x 3 rotation per facet ({F}), not {R.shape}")
+    R = R.reshape(F, 9)
+    M = R.reshape(F, 3, 3)
+    with np.errstate(invalid="ignore"):
+        bad = ~np.isfinite(R).all(axis=1) | ~(R[:, 8] > 0.0)
+        bad |= ~(np.abs(M @ M.transpose(0, 2, 1) - np.eye(3)) <= 1e-9).all(axis=(1, 2))
+    if bad.any():
+        raise ValueError(f"R of facet {int(np.flatnonzero(bad)[0])} is not a rotation with R22 > 0 (finite, |R R^T - I| <= 1e-9)")
+    return R if be is HOST else be.torch.from_numpy(R).to(getattr(like, "device", like))
+
+
+def mosaic_args(be, facets, theta_src, R, theta_dst, N_dst, kind, weights, window, normalize, wmin, blank, wsum, stats, out):
+    """F, Ns, theta_s, facets, weights, R, kind, inner, outer, normalize, wmin, blank, Nd, theta_d, out, wsum, stats as
+    gridhip_mosaic[_dev] takes them (include/gridhip.h, "reprojection and mosaicking").  facets: (F, Ns, Ns) or one
+    (Ns, Ns) image; window: (inner, outer) in facet cells, None for inner = outer = Ns / 2."""
+    import math
+    given = shape = tuple(getattr(facets, "shape", ()))
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1] != shape[2] or min(shape) < 1:
+        raise ValueError(f"facets must be (F, Ns, Ns) square images, not {shape}")
+    F, Ns, Nd = shape[0], shape[1], int(N_dst)
+    if Nd < 1:
+        raise ValueError("N_dst must be >= 1")
+    if be is HOST:
+        facets = np.asarray(facets)
+    if (facets.dtype.kind == "c") if be is HOST else facets.dtype.is_complex:
+        raise ValueError(f"facets must be real, not {facets.dtype}")
+    facets = be.cv(facets, be.f64)
+    if weights is not None:
+        if be is not backend(weights) or tuple(weights.shape) != given:
+            raise ValueError(f"weights must be a {be.array} of the facets' shape {given}, or None")
+        weights = be.cv(weights, be.f64)
+    if kind not in MOSAIC_KINDS:
+        raise ValueError(f"kind must be one of {sorted(MOSAIC_KINDS)}, not {kind!r}")
+    theta_s, theta_d = float(theta_src), float(theta_dst)
+    if not (math.isfinite(theta_s) and theta_s > 0.0 and math.isfinite(theta_d) and theta_d > 0.0):
+        raise ValueError("theta_src and theta_dst must be finite and > 0")
+    inner, outer = (Ns / 2, Ns / 2) if window is None else (float(window[0]), float(window[1]))
+    if not (math.isfinite(inner) and math.isfinite(outer) and 0.0 <= inner <= outer):
+        raise ValueError("window must be (inner, outer) in cells with 0 <= inner <= outer")
+    wmin = float(wmin)
+    if not wmin >= 0.0:
+        raise ValueError("wmin must be >= 0")
+    R = facet_rotations(be, R, F, facets)
+    out = result_array(be, out, be.f64, (Nd, Nd), "out", facets)
+    ws = be.empty((Nd, Nd), be.f64, facets) if wsum else None
+    st8 = be.empty(8, be.f64, facets) if stats else None
+    return (F, Ns, theta_s, facets, weights, R, MOSAIC_KINDS[kind], inner, outer, int(bool(normalize)), wmin, float(blank), Nd,
+            theta_d, out, ws, st8)
+
+
 SRC_DOUBLES = 16  # GRIDHIP_SRC_DOUBLES: { label, ncells, yp, xp, peak, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1, flags }
 
 
