@@ -30,16 +30,18 @@
 // against the array all the same and violations are counted (option "errors").
 //
 // Reuse.  Everything the gridder takes from (u, v, wbin) is in the pre-records, and in real use the coordinates stay
-// the same from call to call while the values change (image then PSF, degrid then grid, every major cycle).  A plain
-// convgrid2 / degrid2 call whose key - geometry, n, stride, the three pointers, the pre-pass options, the scratch
+// the same from call to call while the values change (image then PSF, degrid then grid, every major cycle).  The
+// counting sweep of a plain convgrid2 / degrid2 call therefore also leaves one 128-bit digest per 128 consecutive
+// pre-records (bin_digest.h; 0.125 B per visibility in the block bin_digest - the pre-records themselves need not
+// outlive their call).  A call whose key - geometry, n, stride, the three pointers, the pre-pass options, the scratch
 // blocks and the generation of the tables (gridhip_ctx::bin_gen: every pre-pass and every other writer of the records
-// counts there) - equals the one the pre-records in recs_raw were written under first runs
+// counts there) - equals the one those digests were written under first runs
 //   clear       : every pre-pass's first kernel, captured or not, one-level or two-level, stamps its generation into
 //                 d_scalars[SC_GEN]; before it does, it arms the device word `match` to 1 only if the stamp it finds
 //                 is the kept generation.  A replay of a graph captured earlier never enters the library, but it
 //                 stamps its capture-time generation, which no kept state carries: the call after it runs in full
-//   bin_verify  : one read-only sweep that derives every pre-record again and compares it with the kept one; a
-//                 work-group that meets a difference clears `match`
+//   bin_verify  : one read-only sweep (24 B per visibility) that derives every pre-record again and compares the
+//                 digests of what it derived with the kept ones; a wave that meets a difference clears `match`
 // and then enqueues the usual kernels, each of which returns at once while `match` is 1: the records, bin_start and
 // work_start in the context are then the ones a fresh pre-pass would write.  The host never waits for the verdict; the
 // last kernel copies it into a mapped host word that the NEXT call reads, unsynchronised, to stop verifying a stream
@@ -51,6 +53,7 @@
 #include <stddef.h>
 #include <string.h>
 
+#include "bin_digest.h"
 #include "tile_common.h"
 
 namespace gridhip {
@@ -187,6 +190,26 @@ __device__ __forceinline__ void vis_bin_pair(const Geom &g, const double *__rest
 // `match` of the kernels below: null, or the verify sweep's verdict - 1: the kept records stand, return at once
 __device__ __forceinline__ bool records_stand(const int32_t *match) { return match && *match == 1; }
 
+// ---- digests of the pre-records (bin_digest.h) ---------------------------------------------------
+// Wrapping sum of a digest over the wave; every lane gets the total.  All 64 lanes take part, so the loops that call
+// it run wave-uniform: a lane without an element brings zero.
+__device__ __forceinline__ Digest wave_sum(Digest d)
+{
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        d.a += __shfl_xor(d.a, off, 64);
+        d.b += __shfl_xor(d.b, off, 64);
+    }
+    return d;
+}
+// The counting sweep's forms whose waves cover half a group per step add their halves into a cleared block.
+__global__ void __launch_bounds__(256) digest_clear_kernel(Digest *__restrict__ dig, int64_t ngroups, const int32_t *match)
+{
+    if (records_stand(match)) return;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ngroups; i += (int64_t)gridDim.x * blockDim.x)
+        dig[i] = Digest{0, 0};
+}
+
 // ---- records between the two scatter levels -------------------------------------------------------
 // FMT 8: the final 8-byte word with, in the bits above its fields (from bit ob + kb + 14), the bin's index inside its
 // coarse bin (bin & (2^shift - 1)); which coarse bin follows from where the record lies in the coarse-ordered array.
@@ -244,12 +267,15 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
                                                          int32_t *__restrict__ block_hist,
                                                          int32_t *__restrict__ scalars, int bin_lo, int bin_hi,
                                                          PreFmt pf, unsigned long long *__restrict__ pre,
-                                                         double2 *__restrict__ zero_out, const int32_t *match)
+                                                         double2 *__restrict__ zero_out, const int32_t *match,
+                                                         Digest *__restrict__ dig)
 {
     if (records_stand(match)) return;
     // LDS_HIST: this launch handles the bins [bin_lo, bin_hi) only (a window that fits in LDS); grids
     // with more bins than that are covered by several launches.  pre != null: the first window's launch leaves
     // the pre-record of every visibility, the others (pf.bin_bits < 0) count from those.
+    // dig != null (with pre, first window): it also leaves the digest of every group of 128 pre-records, which is
+    // what a later call's verify sweep compares with (bin_digest.h).
     extern __shared__ int32_t hist[];
     const int nwin = bin_hi - bin_lo;
     if (LDS_HIST) {
@@ -275,24 +301,43 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
     // and the work-groups take the stream grid-stride instead of one contiguous slice each.  The wider accesses alone
     // measured nothing; the grid-stride order took the sweep from 0.70 to 0.62 ms (256 x 4 concurrent streams become
     // four narrow windows: HBM page locality).  The same order in the coarse scatter measured no difference.
+    // A wave's 128 visibilities of one trip are one digest group (the work-group is a whole number of waves), so the
+    // group's digest is one wave reduction; for that the loop runs wave-uniform, a lane past the end idling through.
+    const int lane = threadIdx.x & 63;
     if (V2 && !from_pre) {
         hi = n;
-        for (int64_t k0 = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); k0 < hi; k0 += 2 * (int64_t)gridDim.x * blockDim.x) {
+        const int64_t kstep = 2 * (int64_t)gridDim.x * blockDim.x;
+        int64_t k0 = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+        uint64_t salt = digest_salt((uint64_t)k0);
+        const uint64_t dsalt = digest_salt((uint64_t)kstep);
+        for (; k0 - 2 * lane < hi; k0 += kstep, salt += dsalt) {
             const bool two = k0 + 1 < hi;
-            BinOut b0, b1;
-            vis_bin_pair(g, u, v, wbin, k0, two, &b0, &b1);
-            if (pre) {
-                if (two)
-                    *reinterpret_cast<ulonglong2 *>(pre + k0) = make_ulonglong2(pre_pack(rf, b0), pre_pack(rf, b1));
-                else
-                    pre[k0] = pre_pack(rf, b0);
+            Digest d{0, 0};
+            if (k0 < hi) {
+                BinOut b0, b1;
+                vis_bin_pair(g, u, v, wbin, k0, two, &b0, &b1);
+                if (pre) {
+                    const unsigned long long p0 = pre_pack(rf, b0), p1 = pre_pack(rf, b1);
+                    if (two)
+                        *reinterpret_cast<ulonglong2 *>(pre + k0) = make_ulonglong2(p0, p1);
+                    else
+                        pre[k0] = p0;
+                    if (dig) {
+                        d = digest_salted(p0, salt);
+                        if (two) digest_add(d, digest_salted(p1, salt + DIGEST_SALT));
+                    }
+                }
+                if (zero_out) {
+                    if (b0.bin < 0) zero_out[k0] = make_double2(0.0, 0.0);
+                    if (two && b1.bin < 0) zero_out[k0 + 1] = make_double2(0.0, 0.0);
+                }
+                tally(b0);
+                tally(b1);
             }
-            if (zero_out) {
-                if (b0.bin < 0) zero_out[k0] = make_double2(0.0, 0.0);
-                if (two && b1.bin < 0) zero_out[k0 + 1] = make_double2(0.0, 0.0);
+            if (dig) {
+                d = wave_sum(d);
+                if (lane == 0) dig[(uint64_t)k0 / DIGEST_GROUP] = d;
             }
-            tally(b0);
-            tally(b1);
         }
     } else {
     // UN visibilities per thread and trip: their loads are in flight together (one work-group per CU has
@@ -304,7 +349,10 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
         hi = n;
     }
     const int64_t kstep = block_hist ? (int64_t)UN * blockDim.x : (int64_t)gridDim.x * UN * blockDim.x;
-    for (int64_t k0 = lo + threadIdx.x; k0 < hi; k0 += kstep) {
+    // (dig: a wave's 64 elements of one step are half a group - `lo` is a multiple of the work-group's size - and the
+    // halves meet in the block, which digest_clear_kernel has cleared; wave-uniform trips as above)
+    const bool digests = dig && pre && !from_pre;
+    for (int64_t k0 = lo + threadIdx.x; k0 - (digests ? lane : 0) < hi; k0 += kstep) {
         BinOut b[UN];
         if (from_pre) {
             unsigned long long p[UN];
@@ -331,11 +379,23 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
             for (int q = 0; q < UN; ++q) {
                 const int64_t e = k0 + (int64_t)q * blockDim.x;
                 b[q] = vis_bin(g, pu[q], pv[q], wb[q], kk[q], part[q]);
+                Digest d{0, 0};
                 if (e >= hi)
                     b[q].bin = -1;
                 else {
-                    if (pre) pre[e] = pre_pack(rf, b[q]);
+                    if (pre) {
+                        const unsigned long long p = pre_pack(rf, b[q]);
+                        pre[e] = p;
+                        if (digests) d = digest_elem(p, (uint64_t)e);
+                    }
                     if (zero_out && b[q].bin < 0) zero_out[kk[q]] = make_double2(0.0, 0.0);
+                }
+                if (digests) {
+                    d = wave_sum(d);
+                    if (lane == 0 && e < hi) {
+                        atomicAdd(reinterpret_cast<unsigned long long *>(&dig[(uint64_t)e / DIGEST_GROUP].a), (unsigned long long)d.a);
+                        atomicAdd(reinterpret_cast<unsigned long long *>(&dig[(uint64_t)e / DIGEST_GROUP].b), (unsigned long long)d.b);
+                    }
                 }
             }
         }
@@ -358,62 +418,79 @@ __global__ void __launch_bounds__(1024) bin_count_kernel(Geom g, int64_t n, cons
 }
 
 // The verify sweep ("Reuse" at the top): the counting sweep without histogram and without stores - every pre-record
-// derived again (vis_bin, pre_pack: the same code) and compared with the kept one.  Grid-stride like the V2 counting
-// sweep; every POLL trips a wave that met a difference clears `flags[0]` (one lane's store) and leaves, and the
-// others leave once they see it cleared.  What the skipped counting sweep would have done besides is done here: the
-// dropped visibilities are counted (flags[1]; the last pre-pass kernel makes it the call's count if the records
-// stand) and a degrid's zero predictions for them are written (rare stores, outside the common path).
+// derived again (vis_bin, pre_pack: the same code), its digest contribution added up, and the sums compared with the
+// digests the counting sweep kept (bin_digest.h): 24 B of stream per visibility and 16 B per 128 of them, where reading
+// the kept pre-records themselves took 8 B more per visibility.  A wave takes one whole group per trip (both forms:
+// the groups are dealt to the waves grid-stride, as the V2 counting sweep's are) and runs wave-uniform.  It keeps the
+// sum of its groups since the last poll and takes the kept digests of the POLL groups ahead from it, one per lane of
+// its first POLL lanes: sums of digests are digests, so one wave reduction per POLL trips gives the verdict on all of
+// them.  A wave whose sum is not zero clears `flags[0]` (one lane's store) and leaves, and the others leave once they
+// see it cleared.  What the skipped counting sweep would have done besides is done here: the dropped visibilities are
+// counted (flags[1]; the last pre-pass kernel makes it the call's count if the records stand) and a degrid's zero
+// predictions for them are written (rare stores, outside the common path).
 template <bool V2>
 __global__ void __launch_bounds__(1024) bin_verify_kernel(Geom g, int64_t n, const double *__restrict__ u,
                                                           const double *__restrict__ v, int64_t stride,
                                                           const int64_t *__restrict__ wbin, PreFmt pf,
-                                                          const unsigned long long *__restrict__ pre,
+                                                          const Digest *__restrict__ dig,
                                                           double2 *__restrict__ zero_out, int32_t *flags)
 {
     constexpr int POLL = 8;
-    bool diff = false;
+    const int lane = threadIdx.x & 63;
+    // this wave's first group, and the waves of the launch (work-groups are whole numbers of waves)
+    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    Digest acc{0, 0}, kept{0, 0};  // derived since the last poll (this lane's share); kept digest of one group of the window
     int dropped = 0, trip = 0;
-    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, tstep = (int64_t)gridDim.x * blockDim.x;
     // (the clear kernel disarms the verdict itself when the device's stamp is not the kept generation)
     if (__hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
     // true: this wave is done (a difference, here or elsewhere)
     auto settled = [&]() {
-        if (__ballot(diff)) {
-            if ((threadIdx.x & 63) == 0) __hip_atomic_store(flags, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        acc.a -= kept.a;
+        acc.b -= kept.b;
+        const Digest t = wave_sum(acc);
+        if (t.a | t.b) {
+            if (lane == 0) __hip_atomic_store(flags, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return true;
         }
+        acc = kept = Digest{0, 0};
         return __hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
     };
-    if (V2) {
-        for (int64_t k0 = 2 * t0; k0 < n; k0 += 2 * tstep) {
-            const bool two = k0 + 1 < n;
-            ulonglong2 kept;
-            if (two)
-                kept = *reinterpret_cast<const ulonglong2 *>(pre + k0);
-            else
-                kept = make_ulonglong2(pre[k0], ~0ull);
-            BinOut b0, b1;
-            vis_bin_pair(g, u, v, wbin, k0, two, &b0, &b1);
-            diff |= pre_pack(pf, b0) != kept.x || pre_pack(pf, b1) != kept.y;
-            dropped += (b0.bin == -2) + (b1.bin == -2);
-            if (zero_out) {
-                if (b0.bin < 0) zero_out[k0] = make_double2(0.0, 0.0);
-                if (two && b1.bin < 0) zero_out[k0 + 1] = make_double2(0.0, 0.0);
+    uint64_t salt = digest_salt((uint64_t)(w0 * DIGEST_GROUP + 2 * lane));  // (V2)
+    const uint64_t dsalt = digest_salt((uint64_t)(nw * DIGEST_GROUP));
+    for (int64_t grp = w0; grp * DIGEST_GROUP < n; grp += nw, salt += dsalt) {
+        if (trip % POLL == 0 && lane < POLL) {
+            const int64_t gl = grp + lane * nw;
+            if (gl * DIGEST_GROUP < n) kept = dig[gl];
+        }
+        if (V2) {
+            const int64_t k0 = grp * DIGEST_GROUP + 2 * lane;
+            if (k0 < n) {
+                const bool two = k0 + 1 < n;
+                BinOut b0, b1;
+                vis_bin_pair(g, u, v, wbin, k0, two, &b0, &b1);
+                digest_add(acc, digest_salted(pre_pack(pf, b0), salt));
+                if (two) digest_add(acc, digest_salted(pre_pack(pf, b1), salt + DIGEST_SALT));
+                dropped += (b0.bin == -2) + (b1.bin == -2);
+                if (zero_out) {
+                    if (b0.bin < 0) zero_out[k0] = make_double2(0.0, 0.0);
+                    if (two && b1.bin < 0) zero_out[k0 + 1] = make_double2(0.0, 0.0);
+                }
             }
-            if (++trip % POLL == 0 && settled()) return;
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int64_t e = grp * DIGEST_GROUP + h * 64 + lane;
+                if (e >= n) continue;
+                int64_t k;
+                int part;
+                elem_of(g, e, &k, &part);
+                const BinOut b = vis_bin(g, u[k * stride], v[k * stride], wbin ? wbin[k] : 0, k, part);
+                digest_add(acc, digest_elem(pre_pack(pf, b), (uint64_t)e));
+                dropped += b.bin == -2;
+                if (zero_out && b.bin < 0) zero_out[k] = make_double2(0.0, 0.0);
+            }
         }
-    } else {
-        for (int64_t e = t0; e < n; e += tstep) {
-            int64_t k;
-            int part;
-            elem_of(g, e, &k, &part);
-            const unsigned long long kept = pre[e];
-            const BinOut b = vis_bin(g, u[k * stride], v[k * stride], wbin ? wbin[k] : 0, k, part);
-            diff |= pre_pack(pf, b) != kept;
-            dropped += b.bin == -2;
-            if (zero_out && b.bin < 0) zero_out[k] = make_double2(0.0, 0.0);
-            if (++trip % POLL == 0 && settled()) return;
-        }
+        if (++trip % POLL == 0 && settled()) return;
     }
     if (settled()) return;
     if (dropped) atomicAdd(&flags[1], dropped);
@@ -1055,7 +1132,8 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             GH_CHECK(ws_reserve(ctx, ctx->recs_raw, (size_t)(n > 0 ? n : 1) * sizeof(unsigned long long)));
             pre = (unsigned long long *)ctx->recs_raw.ptr;
         }
-        // ---- reuse (see the top): verify when the pre-records in recs_raw were written by the previous pre-pass of this
+        const int64_t ndig = (n + DIGEST_GROUP - 1) / DIGEST_GROUP;
+        // ---- reuse (see the top): verify when the digests in bin_digest were written by the previous pre-pass of this
         // context under an equal key.  Not while the stream is captured (or its state cannot be told): nothing runs
         // then, so a captured call neither verifies nor leaves state behind.  What its replays write later the host
         // does not see; the stamp the clear kernel leaves on the device is there for them.
@@ -1070,6 +1148,7 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
         }
         if (may_reuse && use_pre && n > 0 && ctx->opt.fault_inject == 0 && capturing == hipStreamCaptureStatusNone) {
             keeps = true;
+            GH_CHECK(ws_reserve(ctx, ctx->bin_digest, (size_t)(ndig > 0 ? ndig : 1) * sizeof(Digest)));
             key.g = g;
             key.n = n;
             key.stride = uv_stride;
@@ -1083,7 +1162,7 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             key.opt[4] = ctx->opt.fault_inject;
             key.recs = ctx->recs.ptr;
             key.tables = ctx->tables.ptr;
-            key.pre = pre;
+            key.dig = ctx->bin_digest.ptr;
             key.gen = gen_in + 1;
             constexpr size_t geom_bytes = offsetof(Geom, sPx) + sizeof(int32_t);  // (no padding before the last field)
             const bool same = keep.valid && keep.key.gen == gen_in && !memcmp(&keep.key.g, &key.g, geom_bytes) &&
@@ -1109,41 +1188,53 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
         launch_clear(ctx, t.bin_count, g.nbins, t.scalars, 3, (int32_t *)ctx->blockhist.ptr, ncoarse, match, t.scalars + SC_GEN,
                      gen_in + 1, gen_in);
         if (verify) {
-            const bool v2 = uv_stride == 1 && g.P == 1 && (((uintptr_t)u | (uintptr_t)v | (uintptr_t)wbin | (uintptr_t)pre) & 15) == 0;
-            // no LDS and 72 registers: three work-groups of 512 threads share a CU (24 waves against the counting sweep's 16)
-            // (measured on the headline case: 0.545 ms; 1 or 2 x 1024 threads 0.54, 4 x 512 0.61, 6 x 256 0.58, 8 x 256 0.65)
+            const bool v2 = uv_stride == 1 && g.P == 1 && (((uintptr_t)u | (uintptr_t)v | (uintptr_t)wbin) & 15) == 0;
+            // no LDS and 78 registers: three work-groups of 512 threads share a CU (24 waves against the counting sweep's 16;
+            // 80 registers is the most that leaves room for them).  Measured on the headline case: 0.44 ms; two groups per
+            // trip, their loads in flight together, take 122 registers, i.e. 16 waves: 0.49 ms; 83 registers, i.e. two of
+            // the three work-groups resident: 0.47 ms.  (The sweep that also read the pre-records: 0.545 ms; 1 or 2 x 1024
+            // threads 0.54, 4 x 512 0.61, 6 x 256 0.58, 8 x 256 0.65.)
             const int vthreads = 512, vper = 3;
             int64_t vneed = (n + 16383) / 16384;
             const int vblocks = (int)(vneed < ctx->num_cu * vper ? vneed : ctx->num_cu * vper);
             if (v2)
                 hipLaunchKernelGGL(bin_verify_kernel<true>, dim3(vblocks), dim3(vthreads), 0, ctx->stream, g, n, u, v, uv_stride, wbin,
-                                   PreFmt{bb}, (const unsigned long long *)pre, zero_out, match);
+                                   PreFmt{bb}, (const Digest *)ctx->bin_digest.ptr, zero_out, match);
             else
                 hipLaunchKernelGGL(bin_verify_kernel<false>, dim3(vblocks), dim3(vthreads), 0, ctx->stream, g, n, u, v, uv_stride, wbin,
-                                   PreFmt{bb}, (const unsigned long long *)pre, zero_out, match);
+                                   PreFmt{bb}, (const Digest *)ctx->bin_digest.ptr, zero_out, match);
             ++keep.verified;
             keep.pending = true;
             *(volatile int32_t *)keep.host_flag = 1;  // (until this sweep's verdict arrives: assume the best)
+        }
+        // a call that keeps state leaves the digests of its pre-records with it (the first window's launch)
+        Digest *const dig = keeps ? (Digest *)ctx->bin_digest.ptr : nullptr;
+        const bool count_v2 = pre && uv_stride == 1 && g.P == 1 && ctx->opt.count_unroll != 1 &&
+                              (((uintptr_t)u | (uintptr_t)v | (uintptr_t)wbin | (uintptr_t)pre) & 15) == 0;
+        if (dig && !count_v2) {  // (the forms that add half groups into the block)
+            const int64_t dblocks = (ndig + 255) / 256;
+            hipLaunchKernelGGL(digest_clear_kernel, dim3((int)(dblocks < ctx->num_cu * 8 ? dblocks : ctx->num_cu * 8)), dim3(256), 0,
+                               ctx->stream, dig, ndig, match);
         }
         for (int wdw = 0; wdw < windows; ++wdw) {
             const int b_lo = wdw * win, b_hi = b_lo + win < g.nbins ? b_lo + win : g.nbins;
             // four visibilities per thread and trip when the bins take several windows: the windows after the first
             // read nothing but 8-byte pre-records and gain from more loads in flight (8192^2, three windows: 2.8 -> 2.6 ms;
             // one window, 4096^2: no difference).  Option count_unroll: 4 = always, 1 = never.
-            const bool v2 = wdw == 0 && pre && uv_stride == 1 && g.P == 1 && ctx->opt.count_unroll != 1 &&
-                            (((uintptr_t)u | (uintptr_t)v | (uintptr_t)wbin | (uintptr_t)pre) & 15) == 0;
+            const bool v2 = wdw == 0 && count_v2;
+            Digest *const wdig = wdw == 0 ? dig : nullptr;
             if (v2)
                 hipLaunchKernelGGL((bin_count_kernel<true, 1, true>), dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u, v,
                                    uv_stride, wbin, t.bin_count, (int32_t *)nullptr, t.scalars, b_lo, b_hi,
-                                   PreFmt{bb}, pre, zero_out, match);
+                                   PreFmt{bb}, pre, zero_out, match, wdig);
             else if (ctx->opt.count_unroll == 4 || (ctx->opt.count_unroll == 0 && windows > 1))
                 hipLaunchKernelGGL((bin_count_kernel<true, 4>), dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u, v,
                                    uv_stride, wbin, t.bin_count, (int32_t *)nullptr, t.scalars, b_lo, b_hi,
-                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out, match);
+                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out, match, wdig);
             else
                 hipLaunchKernelGGL((bin_count_kernel<true, 1>), dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u, v,
                                    uv_stride, wbin, t.bin_count, (int32_t *)nullptr, t.scalars, b_lo, b_hi,
-                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out, match);
+                                   PreFmt{wdw == 0 ? bb : -bb}, pre, zero_out, match, wdig);
         }
         hipLaunchKernelGGL(bin_scan_kernel<1024>, dim3(SCAN_SEGS + g.ngroups), dim3(1024), 0, ctx->stream, g, t.bin_count, t.bin_start,
                            t.work_start, t.cursor, match);
@@ -1167,7 +1258,7 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             GH_CHECK(GH_TWO(false, 16));
 #undef GH_TWO
         GH_CHECK_HIP(ctx, hipGetLastError());
-        if (keeps) {  // whichever way the verdict goes, recs_raw now holds this call's pre-records
+        if (keeps) {  // whichever way the verdict goes, bin_digest now holds the digests of this call's pre-records
             keep.key = key;
             keep.valid = true;
         }
@@ -1183,12 +1274,12 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             const int b_lo = wdw * win, b_hi = b_lo + win < g.nbins ? b_lo + win : g.nbins;
             hipLaunchKernelGGL(bin_count_kernel<true>, dim3(blocks), dim3(threads), hist_bytes, ctx->stream, g, n, u,
                                v, uv_stride, wbin, t.bin_count, block_hist, t.scalars, b_lo, b_hi, PreFmt{0},
-                               (unsigned long long *)nullptr, zero_out, (const int32_t *)nullptr);
+                               (unsigned long long *)nullptr, zero_out, (const int32_t *)nullptr, (Digest *)nullptr);
         }
     } else {
         hipLaunchKernelGGL(bin_count_kernel<false>, dim3(blocks), dim3(threads), 0, ctx->stream, g, n, u, v,
                            uv_stride, wbin, t.bin_count, block_hist, t.scalars, 0, g.nbins, PreFmt{0},
-                           (unsigned long long *)nullptr, zero_out, (const int32_t *)nullptr);
+                           (unsigned long long *)nullptr, zero_out, (const int32_t *)nullptr, (Digest *)nullptr);
     }
     hipLaunchKernelGGL(bin_scan_kernel<1024>, dim3(SCAN_SEGS + g.ngroups), dim3(1024), 0, ctx->stream, g, t.bin_count, t.bin_start,
                        t.work_start, t.cursor, (const int32_t *)nullptr);

@@ -121,13 +121,14 @@ struct Workspace {
 };
 
 // What the last two-level pre-pass of a plain gridding call (convgrid2 / degrid2) left behind, so that the next call
-// over the same coordinates can keep its records (bin.hip, "Reuse").  The pre-records themselves stay in recs_raw.
+// over the same coordinates can keep its records (bin.hip, "Reuse").  What the next call compares with is one digest per
+// 128 pre-records, in bin_digest; the pre-records themselves (recs_raw) are the pre-pass's own from call to call.
 struct BinKey {
     Geom g;                  // compared up to its last named field
     int64_t n, stride;
     const void *u, *v, *wbin;
     int64_t opt[5];          // prepass, coarse_shift, scatter_chunk, count_unroll, fault_inject
-    const void *recs, *tables, *pre;  // the scratch blocks the state lives in (a re-allocation moves them)
+    const void *recs, *tables, *dig;  // the scratch blocks the state lives in (a re-allocation moves them)
     uint64_t gen;            // gridhip_ctx::bin_gen when the state was written
 };
 struct BinKeep {
@@ -161,6 +162,7 @@ struct gridhip_ctx {
     gridhip::Workspace tables;  // bin_count / bin_start / work_start / cursors / scalars
     gridhip::Workspace sorted;  // sorted-list scratch of the tap-reusing tile kernel (tile_sorted.hip)
     gridhip::Workspace recs_raw;   // 8-byte pre-records the counting sweep leaves for the scatter (bin.hip)
+    gridhip::Workspace bin_digest; // Digest[n / 128] of those pre-records, kept for the next call's verify sweep (bin_digest.h)
     gridhip::Workspace recs_tmp;   // coarse-binned records between the two scatter levels of the pre-pass (bin.hip)
     gridhip::Workspace blockhist;  // [pre-pass work-groups][nbins] histograms -> first slots
     gridhip::Workspace ktab;       // kernel table cut into zero-padded square parts (sub-footprints, api.hip)
