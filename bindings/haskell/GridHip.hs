@@ -75,6 +75,7 @@ data Ctx
 data Plan
 data AwPlan
 data Imager
+data WStack
 data Comm
 newtype GridHip = GridHip (Ptr Ctx)
 newtype Node    = Node (Ptr Comm)
@@ -508,6 +509,33 @@ foreign import ccall unsafe "gridhip_reproject"
 -- int gridhip_reproject_dev(ctx, Ns, theta_s, image, R, kind, inner, outer, blank, Nd, theta_d, out)
 foreign import ccall unsafe "gridhip_reproject_dev"
   c_reproject_dev :: Ptr Ctx -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_wstack_create_dev(ctx, wstep, M, qpx, npixFF, npixKern, theta, lam, n, u, v, w, uv_stride, ws)
+foreign import ccall unsafe "gridhip_wstack_create_dev"
+  c_wstack_create_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr (Ptr WStack) -> IO CInt
+-- int gridhip_wstack_image_dev(ws, vis, image)
+foreign import ccall unsafe "gridhip_wstack_image_dev"
+  c_wstack_image_dev :: Ptr WStack -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_wstack_predict_dev(ws, model, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_wstack_predict_dev"
+  c_wstack_predict_dev :: Ptr WStack -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_wstack_info(ws, layers, occupied, pmin, dropped)
+foreign import ccall unsafe "gridhip_wstack_info"
+  c_wstack_info :: Ptr WStack -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> IO CInt
+-- int gridhip_wstack_destroy(ws)
+foreign import ccall unsafe "gridhip_wstack_destroy"
+  c_wstack_destroy :: Ptr WStack -> IO CInt
+-- int gridhip_do_imaging_wstack(ctx, wstep, M, qpx, npixFF, npixKern, theta, lam, n, u, v, w, uv_stride, vis, image, psf, pmax)
+foreign import ccall unsafe "gridhip_do_imaging_wstack"
+  c_do_imaging_wstack :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_do_imaging_wstack_dev(ctx, wstep, M, qpx, npixFF, npixKern, theta, lam, n, u, v, w, uv_stride, vis, image, psf, pmax)
+foreign import ccall unsafe "gridhip_do_imaging_wstack_dev"
+  c_do_imaging_wstack_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_predict_wstack(ctx, wstep, M, qpx, npixFF, npixKern, theta, lam, model, n, u, v, w, uv_stride, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_predict_wstack"
+  c_predict_wstack :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_predict_wstack_dev(ctx, wstep, M, qpx, npixFF, npixKern, theta, lam, model, n, u, v, w, uv_stride, vis_sub, vis_out)
+foreign import ccall unsafe "gridhip_predict_wstack_dev"
+  c_predict_wstack_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt

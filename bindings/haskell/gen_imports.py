@@ -23,6 +23,8 @@ TYPES = [
     (r"^gridhip_aw_plan \*$", "Ptr AwPlan"),
     (r"^gridhip_imager \*\*$", "Ptr (Ptr Imager)"),
     (r"^gridhip_imager \*$", "Ptr Imager"),
+    (r"^gridhip_wstack \*\*$", "Ptr (Ptr WStack)"),
+    (r"^gridhip_wstack \*$", "Ptr WStack"),
     (r"^gridhip_comm \*\*$", "Ptr (Ptr Comm)"),
     (r"^(const )?gridhip_comm \*$", "Ptr Comm"),
     (r"^double \*const \*$", "Ptr (Ptr CDouble)"),

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 290 /* 0.2.9 */
+#define GRIDHIP_VERSION 300 /* 0.3.0 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1714,6 +1714,74 @@ int gridhip_reproject(gridhip_ctx *ctx, int64_t Ns, double theta_s, const double
                       double inner, double outer, double blank, int64_t Nd, double theta_d, double *out);
 int gridhip_reproject_dev(gridhip_ctx *ctx, int64_t Ns, double theta_s, const double *image, const double *R, int kind,
                           double inner, double outer, double blank, int64_t Nd, double theta_d, double *out);
+
+/* ---- w-stacking: layered grids, image-plane w-screens, a stacked prediction -----------------------------------------------
+ * The third way to correct the w-term, beside w-projection (w_cache_imaging: one kernel per w-plane of the whole stream,
+ * whose support grows with |w| theta^2) and facets (phase_shift, then mosaic).  The w range is cut into layers of M planes
+ * of `wstep`; a layer is gridded on its own with w-projection kernels of the RESIDUAL w only, transformed to the image
+ * plane, multiplied there by the exact w-screen of the layer's centre, and the layers are summed.  The kernel table has M
+ * planes, whatever the stream's w range, and carries at most M wstep / 2 of |w|.  (Citations: oracle/gridref_np.py;
+ * tests/wstack_ref.py is the numpy restatement of this section.)
+ * INPUTS.  (theta, lam), N = gridhip_image_size(theta, lam); wstep >= 1; M >= 1 planes per layer; the w-kernel shape
+ * (qpx, npixFF, npixKern) under the w-kernel shape rule (at gridhip_w_kernel); a stream u, v, w in wavelengths (uv_stride as
+ * everywhere).
+ * PLANES AND LAYERS.  p_k = round(w_k / wstep) (libm round, half away from zero: acc_round, the plane of gridhip_wbins);
+ * pmin, pmax over the visibilities with a finite w; L = (pmax - pmin) div M + 1 layers; layer_k = (p_k - pmin) div M; the
+ * centre plane of layer l is pc_l = pmin + l M + M div 2; the residual bin r_k = p_k - pc_l + M div 2 lies in [0, M).  A
+ * visibility with a non-finite w has no layer: it grids nothing and predicts exactly 0 (vis_sub[k] in the residual form),
+ * and is counted by gridhip_last_dropped (and by gridhip_wstack_info) together with what the layers' gridder drops.
+ * L > 4096, M > 65536, n >= 2^31 - 256 or |p| > 2^52 is GRIDHIP_EUNSUPPORTED.  n = 0 (or no finite w) gives L = 0, a zero
+ * image and no error.
+ * KERNEL TABLE.  One for all layers: K[r] = conj(w_kernel(theta, (r - M div 2) wstep, npixFF, npixKern, qpx)), r in [0, M).
+ * SCREEN.  c_i = (i - N div 2) / N theta; ph[y, x] = 1 - sqrt(1 - c_x^2 - c_y^2); S_l[y, x] = exp(-2 pi i pc_l wstep
+ * ph[y, x]), and 0 where c_x^2 + c_y^2 >= 1.  The minus sign is the one that makes S_l conj(far field of K) the far field of
+ * conj(w_kernel(w)); with a plus the error against a direct Fourier sum triples (tests/test_wstack_host.py).
+ * IMAGE.  G_l = convgrid2(K, 0, u / lam, v / lam, r, vis) over the visibilities of layer l; D = sum_l S_l x ifft_c(G_l);
+ * gridhip_wstack_image_dev writes image = Re(D), N x N doubles, overwritten.  An empty layer contributes nothing and costs
+ * nothing: no clear, no transform.
+ * PREDICT.  The exact adjoint: for k in layer l, pred_k = degrid2(conj(K), fft_c(conj(S_l) x model), u / lam, v / lam, r)_k,
+ * written at the visibility's own index; vis_out = pred, or vis_sub - pred; vis_out == vis_sub is allowed.  For any vis
+ * and any real model   sum(model * image(vis)) == N^-2 Re(vdot(vis, predict(model))).
+ * THE HANDLE.  A gridhip_wstack behaves like a gridhip_plan: it binds the stream as given (no mirror, no weights), owns
+ * everything it needs (the layer-ordered coordinates, one gridhip_plan per occupied layer, the two kernel tables, two
+ * N x N grids, its transform), its inputs may be freed once creation returns, and it belongs to its context (same
+ * device, same stream, not thread-safe; destroy it before the context).  gridhip_wstack_create_dev synchronises: it reads
+ * the plane range and the layers' sizes back, as kind 2 reads its w-bins' range.  After creation, image and predict
+ * enqueue kernels and hipFFT executions only - no memset or copy node, nothing read back - and allocate nothing after
+ * their first call, so a pass can be captured into a graph.  All arguments are checked before anything is touched
+ * (GRIDHIP_EINVAL); a refused creation leaves *ws NULL, a refused pass its outputs as they were.  The order of the
+ * visibilities inside a layer's slice is the order the partition's atomic adds arrive in, and the gridder adds with
+ * floating-point atomics: an image agrees from run to run to rounding, not to the bit; a prediction is bit-reproducible.
+ * gridhip_wstack_info: the layers L, how many of them hold a visibility, pmin, and the dropped visibilities (any may be
+ * NULL).
+ * DO_IMAGING WITH A STACK.  mirror_uvw; doweight on the mirrored u, v, as every kind; ONE stack on the mirrored stream;
+ * image = 2 Re D(wt vis1), psf = 2 Re D(wt); both divided by pmax = max(psf).  DIFFERENCE FROM KINDS 0 TO 2: those
+ * return Re(ifft_c(make_grid_hermitian(G))), which equals 2 Re(ifft_c(G)) except for what the gridder put on row 0 or
+ * column 0 of an even-N grid - make_grid_hermitian leaves those cells without their mirror image, 2 Re doubles them like
+ * every other cell.  A stack cannot apply make_grid_hermitian (its layers' mirror images lie in the layers of -w), so it
+ * takes 2 Re throughout.  gridhip_predict_wstack is the stack's predict on the stream as given (no mirror), as
+ * gridhip_predict.  Both make a stack for the call and destroy it; the host forms are synchronous, the _dev forms take
+ * device pointers (pmax stays a host pointer) and synchronise too. */
+typedef struct gridhip_wstack gridhip_wstack;
+int gridhip_wstack_create_dev(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                              double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
+                              int64_t uv_stride, gridhip_wstack **ws);
+int gridhip_wstack_image_dev(gridhip_wstack *ws, const double *vis, double *image);
+int gridhip_wstack_predict_dev(gridhip_wstack *ws, const double *model, const double *vis_sub, double *vis_out);
+int gridhip_wstack_info(gridhip_wstack *ws, int64_t *layers, int64_t *occupied, int64_t *pmin, int64_t *dropped);
+int gridhip_wstack_destroy(gridhip_wstack *ws);
+int gridhip_do_imaging_wstack(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                              double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
+                              int64_t uv_stride, const double *vis, double *image, double *psf, double *pmax);
+int gridhip_do_imaging_wstack_dev(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                                  double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,
+                                  int64_t uv_stride, const double *vis, double *image, double *psf, double *pmax);
+int gridhip_predict_wstack(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                           double theta, int64_t lam, const double *model, int64_t n, const double *u, const double *v,
+                           const double *w, int64_t uv_stride, const double *vis_sub, double *vis_out);
+int gridhip_predict_wstack_dev(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
+                               double theta, int64_t lam, const double *model, int64_t n, const double *u, const double *v,
+                               const double *w, int64_t uv_stride, const double *vis_sub, double *vis_out);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -2,7 +2,7 @@
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
 // msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
-// sources.hip, average.hip, jonescal.hip, mosaic.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
+// sources.hip, average.hip, jonescal.hip, mosaic.hip, wstack.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -276,6 +276,10 @@ struct WCache {
 // u, v, w: n contiguous doubles each (wavelengths); synchronises (the w-bin rule reads min / max back)
 int w_cache_prepare(gridhip_ctx *ctx, WCache &c, double theta, int64_t lam, int64_t wstep, int64_t Q, int64_t npixFF,
                     int64_t S, int64_t n, const double *u, const double *v, const double *w);
+
+// a[k] = 1 + 0i; out[k] = a[k] * b[k] (out may be b): do_imaging's weights and wt * vis1 (src/Gridding.hs:534-538)
+int launch_fill_ones(gridhip_ctx *ctx, int64_t n, double2 *a);
+int launch_cmul(gridhip_ctx *ctx, int64_t n, const double2 *a, const double2 *b, double2 *out);
 
 // the arguments of the aw entry points (aw_imaging_dev, do_imaging_aw, aw_gridding, predict_aw)
 struct AwArgs {
@@ -612,5 +616,29 @@ size_t mosaic_scratch_bytes(int64_t F);
 int mosaic_run(gridhip_ctx *ctx, int64_t F, int64_t Ns, double theta_s, const double *facets, const double *weights,
                const double *R, int kind, double inner, double outer, int normalize, double wmin, double blank, int64_t Nd,
                double theta_d, double *out, double *wsum, double *stats, void *scratch);
+
+// ---- w-stacking (wstack.hip) ------------------------------------------------------------------------------------------------
+// the most layers of a stack (the per-layer histogram of the partition is kept in LDS: 2 x 16 KB) and the most planes of a
+// layer (w_cache_imaging's limit of one kernel table)
+constexpr int64_t WS_MAX_LAYERS = 4096;
+constexpr int64_t WS_MAX_PLANES = 65536;
+// The arguments a stack is made from, and their rules (GRIDHIP_EINVAL; n or M beyond the limits: GRIDHIP_EUNSUPPORTED).
+// Nothing is read.  *N: the image size.
+struct WStackArgs {
+    int64_t wstep, M, Q, npixFF, S;
+    double theta;
+    int64_t lam, n;
+    const double *u, *v, *w;
+    int64_t stride;
+};
+int wstack_check(gridhip_ctx *ctx, const WStackArgs &a, int64_t *N);
+// gridhip_wstack_create_dev on checked arguments (synchronises: the plane range and the layer counts come back).  own_fft:
+// the stack keeps a transform of its own (a handle outlives the context's four cached sizes); false: the passes take the
+// context's cached one
+int wstack_create(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, gridhip_wstack **out, bool own_fft = true);
+// The two passes on device pointers: kernels and transforms only, on the stack's context's stream.
+// image = factor * Re(D(vis)), overwritten (factor 1: gridhip_wstack_image_dev; 2: do_imaging, see include/gridhip.h)
+int wstack_image_run(gridhip_wstack *ws, const double *vis, double *image, double factor);
+int wstack_predict_run(gridhip_wstack *ws, const double *model, const double *vis_sub, double *vis_out);
 
 }  // namespace gridhip

@@ -86,6 +86,21 @@ __global__ void fill_ones_kernel(int64_t n, double2 *__restrict__ a)
         a[k] = make_double2(1.0, 0.0);
 }
 
+// what do_imaging's weighting needs beside launch_doweight: a = 1 + 0i, and out = a * b (both on ctx->stream)
+int launch_fill_ones(gridhip_ctx *ctx, int64_t n, double2 *a)
+{
+    if (n > 0) hipLaunchKernelGGL(fill_ones_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, a);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int launch_cmul(gridhip_ctx *ctx, int64_t n, const double2 *a, const double2 *b, double2 *out)
+{
+    if (n > 0) hipLaunchKernelGGL(cmul_real_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, a, b, out);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
 // mirror + weights + the two gridding passes + hermitian + iFFT + normalise, all on the device.
 // `imgfn` grids (u1, v1, w1, vis) -> zeroed N x N grid.  st: the call's staging, which may hold arguments of the
 // caller's already (conv_imaging's kv); the array arguments here are the caller's own, taken through it.

@@ -34,6 +34,7 @@ from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import group_ids, rotation as _rotation
 from ._marshal import weighting as _weighting
 from ._marshal import mosaic_args
+from ._marshal import wstack_options
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid"]
@@ -316,7 +317,8 @@ class Context(Handle):
 
     def do_imaging(self, theta, lam, uvw, a1, a2, t, f, vis, imgfn):
         """:509-549 -> (image, psf, pmax).  imgfn = ("simple",) | ("conv", kv) | ("w_cache", kernops) |
-        ("aw", wkernels, wbins, akernels); a1, a2 feed the antenna indices of "aw" (not swapped by the mirror), t, f
+        ("aw", wkernels, wbins, akernels) | ("wstack", dict(wstep=, planes=, qpx=, npixFF=, npixKern=)) - w-stacking, whose
+        image is 2 Re D instead of the Hermitian fill (include/gridhip.h, "w-stacking"); a1, a2 feed the antenna indices of "aw" (not swapped by the mirror), t, f
         (src) are accepted for signature parity and unused by these imaging functions.
         torch cuda tensors (uvw, vis, and kv / the aw tables and antennas) take the device-resident form
         (gridhip_do_imaging_dev / gridhip_do_imaging_aw_dev): nothing crosses PCIe, image and psf come back as cuda
@@ -327,6 +329,8 @@ class Context(Handle):
         if imgfn[0] == "aw":
             tables, a1, a2 = aw_tables(be, imgfn[1], imgfn[2], imgfn[3], a1, a2)
             self._call(be, "do_imaging_aw", *tl, *tables, *stream, a1, a2, vis, img, psf, C.byref(pmax))
+        elif imgfn[0] == "wstack":
+            self._call(be, "do_imaging_wstack", *wstack_options(imgfn[1]), *tl, *stream, vis, img, psf, C.byref(pmax))
         else:
             self._call(be, "do_imaging", *imaging_function(be, imgfn), *tl, *stream, vis, img, psf, C.byref(pmax))
         return img, psf, pmax.value
@@ -346,7 +350,7 @@ class Context(Handle):
         """Visibilities of a real N x N model image (gridhip_predict[_aw][_dev]): the adjoint of the imaging function
         `imgfn` applied to fft_c(model), or vis_sub minus that (the residual) when vis_sub is given.  imgfn takes
         do_imaging's tuples: ("simple",) | ("conv", kv) | ("w_cache", kernops) | ("aw", wkernels, wbins, akernels), the
-        last with the antenna indices a1, a2.  uvw (wavelengths, not mirrored) as the imaging function takes it.
+        last with the antenna indices a1, a2, | ("wstack", kernops with planes=).  uvw (wavelengths, not mirrored) as the imaging function takes it.
         numpy in gives numpy out; torch cuda tensors take the device form on torch's stream and return a cuda tensor.
         out: the array to write (may be vis_sub itself: an in-place residual); a new one when None."""
         be = backend(model)
@@ -365,6 +369,8 @@ class Context(Handle):
         if imgfn[0] == "aw":
             tables, a1, a2 = aw_tables(be, imgfn[1], imgfn[2], imgfn[3], a1, a2)
             self._call(be, "predict_aw", *tl, *tables, model, n, u, v, w, st, a1, a2, sub, out)
+        elif imgfn[0] == "wstack":
+            self._call(be, "predict_wstack", *wstack_options(imgfn[1]), *tl, model, n, u, v, w, st, sub, out)
         else:
             self._call(be, "predict", *imaging_function(be, imgfn), *tl, model, n, u, v, w, st, sub, out)
         return out
@@ -889,6 +895,20 @@ class Context(Handle):
         return Imager(self, h, n, self.image_size(theta, lam), u.device)
 
 
+    def wstack(self, theta, lam, uvw, kernops):
+        """Bind the stream `uvw` (torch cuda tensors, wavelengths, taken as given: no mirror, no weights) for w-stacking
+        (gridhip_wstack; include/gridhip.h, "w-stacking"): kernops = dict(wstep=, planes=, qpx=, npixFF=, npixKern=), planes
+        the w-planes per layer.  The stream is cut into layers, each binned once, and the table of the residual
+        w-kernels is built here.  Returns a WStack whose image() / predict() are one asynchronous, capturable pass each;
+        uvw may be freed or changed afterwards."""
+        be = device()
+        opts = wstack_options(kernops)
+        u, v, w, st = baselines(be, uvw, 3)
+        n, h = int(u.shape[0]), C.c_void_p()
+        self._call(be, "wstack_create", *opts, float(theta), int(lam), n, u, v, w, st, C.byref(h))
+        return WStack(self, h, n, self.image_size(theta, lam), u.device)
+
+
 class _Bound(Handle):
     """A handle a context made for n device-resident baselines (a plan, an imager): it runs on the context's device
     and stream, reports through the context and takes contiguous cuda tensors only."""
@@ -959,6 +979,53 @@ class AwPlan(_Bound):
         self._chk(a)
         out = self._vis(out, a)
         self._call(device(), "aw_plan_degrid", a, out)
+        return out
+
+
+class WStack(_Bound):
+    """A stream bound for w-stacking (gridhip_wstack): image() is Re(sum_l S_l ifft_c(G_l)) of the visibilities, predict()
+    its exact adjoint; both take contiguous cuda tensors and run on torch's current stream."""
+    _destroy, _what = "gridhip_wstack_destroy", "wstack"
+
+    def __init__(self, ctx, handle, n, N, device):
+        super().__init__(ctx, handle, n)
+        self.N, self.device = N, device
+
+    def _info(self, i):
+        self._open()
+        out = [C.c_int64() for _ in range(4)]
+        self._check(self._lib.gridhip_wstack_info(self._h, *(C.byref(x) for x in out)))
+        return out[i].value
+
+    layers = property(lambda self: self._info(0), doc="the layers L of the stream's w range")
+    occupied = property(lambda self: self._info(1), doc="the layers that hold a visibility")
+    pmin = property(lambda self: self._info(2), doc="the lowest w-plane, round(w / wstep), of the stream")
+    dropped = property(lambda self: self._info(3), doc="visibilities without a finite w, or dropped by the gridder")
+
+    def image(self, vis, out=None):
+        """Re(D) of the visibilities `vis` (cuda complex128, length n) -> N x N cuda float64 (out, or a new tensor)"""
+        self._open()
+        be = device()
+        Imager._ok(vis, be.c128, (self.n,), "vis")
+        if out is None:
+            out = be.empty((self.N, self.N), be.f64, self.device)
+        else:
+            Imager._ok(out, be.f64, (self.N, self.N), "out")
+        self._call(be, "wstack_image", vis, out)
+        return out
+
+    def predict(self, model, vis_sub=None, out=None):
+        """The stack's prediction of the N x N cuda float64 `model`, or vis_sub minus it; out may be vis_sub."""
+        self._open()
+        be = device()
+        Imager._ok(model, be.f64, (self.N, self.N), "model")
+        if vis_sub is not None:
+            Imager._ok(vis_sub, be.c128, (self.n,), "vis_sub")
+        if out is None:
+            out = self._vis(None, self.device)
+        else:
+            Imager._ok(out, be.c128, (self.n,), "out")
+        self._call(be, "wstack_predict", model, vis_sub, out)
         return out
 
 

@@ -73,6 +73,9 @@ _AVERAGE = [vp, i64, i64, vp, _HOST_F64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp
 _MOSAIC = [vp, i64, i64, C.c_double, vp, vp, vp, ci, C.c_double, C.c_double, ci, C.c_double, C.c_double, i64, C.c_double,
            vp, vp, vp]
 _REPROJECT = [vp, i64, C.c_double, vp, vp, ci, C.c_double, C.c_double, C.c_double, i64, C.c_double, vp]
+# wstep, M, qpx, npixFF, npixKern, theta, lam (the stack's shape), then the stream n, u, v, w, uv_stride
+_WSTACK = [vp, i64, i64, i64, i64, i64, C.c_double, i64]
+_WSTACK_STREAM = [i64, vp, vp, vp, i64]
 _PREDICT_AW = [vp, C.c_double, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 SIGNATURES = {
     "gridhip_version": (ci, []),
@@ -229,6 +232,15 @@ SIGNATURES = {
     "gridhip_mosaic_dev": (ci, _MOSAIC),
     "gridhip_reproject": (ci, _REPROJECT),
     "gridhip_reproject_dev": (ci, _REPROJECT),
+    "gridhip_wstack_create_dev": (ci, _WSTACK + _WSTACK_STREAM + [C.POINTER(vp)]),
+    "gridhip_wstack_image_dev": (ci, [vp, vp, vp]),
+    "gridhip_wstack_predict_dev": (ci, [vp, vp, vp, vp]),
+    "gridhip_wstack_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    "gridhip_wstack_destroy": (ci, [vp]),
+    "gridhip_do_imaging_wstack": (ci, _WSTACK + _WSTACK_STREAM + [vp, vp, vp, C.POINTER(C.c_double)]),
+    "gridhip_do_imaging_wstack_dev": (ci, _WSTACK + _WSTACK_STREAM + [vp, vp, vp, C.POINTER(C.c_double)]),
+    "gridhip_predict_wstack": (ci, _WSTACK + [vp] + _WSTACK_STREAM + [vp, vp]),
+    "gridhip_predict_wstack_dev": (ci, _WSTACK + [vp] + _WSTACK_STREAM + [vp, vp]),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

@@ -131,6 +131,19 @@ def imaging_function(be, imgfn):
     raise ValueError("unknown imaging function")
 
 
+def wstack_options(ko):
+    """dict(wstep=, planes=, qpx=, npixFF=, npixKern=) -> (wstep, M, qpx, npixFF, npixKern), the leading arguments of the
+    w-stacking entry points (include/gridhip.h, "w-stacking"); no wstep, or 0: 2000, as for "w_cache".  What the library
+    would refuse is refused here, before any call: wstep or planes below 1, a shape outside the w-kernel shape rule."""
+    wstep, M = int(ko.get("wstep") or 2000), int(ko["planes"])
+    Q, ff, S = int(ko["qpx"]), int(ko["npixFF"]), int(ko["npixKern"])
+    if wstep < 1 or M < 1:
+        raise ValueError(f"wstack: wstep ({wstep}) and planes ({M}) must be >= 1")
+    if not (ff > 0 and S > 0 and Q > 0 and S <= ff and (ff * Q) // 2 - Q * (S // 2) >= Q - 1):
+        raise ValueError(f"wstack: npixFF={ff}, npixKern={S}, qpx={Q} is outside the w-kernel shape rule")
+    return wstep, M, Q, ff, S
+
+
 def aw_tables(be, wkernels, wbins, akernels, a1, a2):
     """-> (W, Q, S, A, wkerns, wvals, akerns), a1, a2 as gridhip_aw_imaging and every entry point with its layout take them"""
     wk, wv, ak = be.cv(wkernels, be.c128), be.cv(wbins, be.f64), be.cv(akernels, be.c128)
