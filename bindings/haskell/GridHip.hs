@@ -40,6 +40,8 @@ module GridHip
   , AutomaskOptions(..), automaskIO, imagerDeconvolveAutomaskIO
   -- * wide-band imaging: Taylor-term major cycles and the multi-term CLEAN (absent from the reference)
   , mfcleanIO, imagerSetSpectralIO, imagerMfsCycleIO, imagerMfDeconvolveIO
+  -- * joint deconvolution: P images of one sky - Stokes planes, channels - cleaned at shared positions (absent from the reference)
+  , JointMetric(..), jcleanIO
   -- * the restoring beam fitted to a PSF, and model * beam + residual (absent from the reference)
   , fitBeamIO, restoreIO, imagerBeamIO, imagerRestoreIO
   -- * imaging weights: natural, uniform, Briggs, taper and data weights, alone or as what an imager is created with
@@ -536,6 +538,12 @@ foreign import ccall unsafe "gridhip_predict_wstack"
 -- int gridhip_predict_wstack_dev(ctx, wstep, M, qpx, npixFF, npixKern, theta, lam, model, n, u, v, w, uv_stride, vis_sub, vis_out)
 foreign import ccall unsafe "gridhip_predict_wstack_dev"
   c_predict_wstack_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_jclean(ctx, N, P, Q, psfs, residuals, models, weights, metric, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_jclean"
+  c_jclean :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_jclean_dev(ctx, N, P, Q, psfs, residuals, models, weights, metric, gain, threshold, niter, border, patch, mask, nsigma, noise, peak_frac, stats)
+foreign import ccall unsafe "gridhip_jclean_dev"
+  c_jclean_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CInt -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> Ptr CDouble -> CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_comm_create(ndev, dev_ids, comm)
 foreign import ccall safe "gridhip_comm_create"
   c_comm_create :: CInt -> Ptr CInt -> Ptr (Ptr Comm) -> IO CInt
@@ -1231,6 +1239,36 @@ imagerMsDeconvolveIO (ImagerH h@(GridHip c) p n n') (CleanOptions g t ni b pa) s
                 msStatsRows rows ps
   let sh = A.Z A.:. n' A.:. n'
   return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr img), st)
+
+-- ---------------------------------------------------------------------------------------------------------
+-- Joint deconvolution (include/gridhip.h, "joint deconvolution"): P images of one sky, as [P][N][N] arrays.
+
+-- | the statistic the joint search maximises: the weighted sum of the planes, or of their squares
+data JointMetric = JointSum | JointSumSq deriving (Eq, Show)
+
+-- | jcleanIO h opts auto sigma metric weights images psfs models: the joint CLEAN of the P residual images with one PSF
+-- ([1][N][N]) or one per plane ([P][N][N]); weights Nothing is 1 for every plane; mask, nsigma, sigma and peak_frac as for
+-- cleanAutoIO.  (models + the components found, the residuals, the 16 stats [iterations, s at the final peak, its flat
+-- index, L, reason, first s, 0, 0, flux_0 .. flux_7]) - the host form, synchronous
+jcleanIO :: GridHip -> CleanOptions -> AutoOptions -> F -> JointMetric -> Maybe [F] -> A.Array A.DIM3 F
+         -> A.Array A.DIM3 F -> A.Array A.DIM3 F -> IO (A.Array A.DIM3 F, A.Array A.DIM3 F, [F])
+jcleanIO h@(GridHip c) (CleanOptions g t ni b pa) (AutoOptions mask ns pf) sigma metric weights images psfs models = do
+  let A.Z A.:. np A.:. n' A.:. _ = A.arrayShape images
+      A.Z A.:. nq A.:. _ A.:. _ = A.arrayShape psfs
+      copyOf m = do o <- mallocForeignPtrArray (np * n' * n') :: IO (ForeignPtr CDouble)
+                    withF m $ \s -> withForeignPtr o $ \d -> copyArray d s (np * n' * n')
+                    return o
+      withWeights Nothing k = k nullPtr
+      withWeights (Just w) k = withArray (map realToFrac w) k
+  res <- copyOf images
+  mdl <- copyOf models
+  st <- withF psfs $ \pp -> withForeignPtr res $ \pr -> withForeignPtr mdl $ \pm -> withMask mask $ \pk ->
+          withWeights weights $ \pw -> with (realToFrac sigma :: CDouble) $ \pn -> allocaArray 16 $ \ps -> do
+            c_jclean c (fi n') (fi np) (fi nq) pp pr pm pw (if metric == JointSum then 0 else 1) (realToFrac g)
+              (realToFrac t) (fi ni) (fi b) (fi pa) pk (realToFrac ns) pn (realToFrac pf) ps >>= check h
+            map realToFrac <$> peekArray 16 ps
+  let sh = A.Z A.:. np A.:. n' A.:. n'
+  return (A.fromForeignPtrs sh (castForeignPtr mdl), A.fromForeignPtrs sh (castForeignPtr res), st)
 
 -- ---------------------------------------------------------------------------------------------------------
 -- Wide-band imaging (include/gridhip.h, "wide-band imaging"): T Taylor terms of the sky, as [T][N][N] arrays.

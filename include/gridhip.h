@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 300 /* 0.3.0 */
+#define GRIDHIP_VERSION 310 /* 0.3.1 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -1782,6 +1782,61 @@ int gridhip_predict_wstack(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t q
 int gridhip_predict_wstack_dev(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
                                double theta, int64_t lam, const double *model, int64_t n, const double *u, const double *v,
                                const double *w, int64_t uv_stride, const double *vis_sub, double *vis_out);
+
+/* ---- joint deconvolution: P images of one sky cleaned together, on the device --------------------------------------------
+ * Several images of the same sky - the Stokes planes of one stream, the channels of a cube - cleaned one by one put their
+ * components at different cells and chase each plane's own noise peaks.  Here the search runs on ONE combined statistic and
+ * every component is taken at one cell in all planes, each plane with its own peak value and PSF.  The reference has none
+ * of this: the semantics are defined here.  All images are real N x N, laid out as gridhip_clean's, c = N / 2.
+ *     P in 1 .. 8 planes;  residuals[P][N][N] is updated in place;  models[P][N][N] is accumulated into, never zeroed
+ *     psfs[Q][N][N], Q in {1, P}: Q == 1 is one PSF for all planes (Stokes planes of one stream), Q == P a PSF per plane
+ *         (channels); plane p uses psfs[Q == P ? p : 0]
+ *     weights: a HOST array of P doubles for every form, read at call time as gridhip_msclean's scales are; NULL: all 1.0.
+ *         Each is finite and >= 0 and at least one is > 0.  A plane of weight 0 does not steer the search and is still
+ *         cleaned at every position found: {1, 0, 0, 0} cleans Q, U, V where I peaks.
+ *     metric 0 ("sum"):    s = w_0 * R_0 + w_1 * R_1 + ...
+ *     metric 1 ("sumsq"):  s = w_0 * (R_0 * R_0) + w_1 * (R_1 * R_1) + ...
+ *         p ascending from the first term, every product rounded, then added; no fused multiply-add
+ *     mask, nsigma, noise (ONE double, sigma, where the images are), peak_frac: as for gridhip_clean_auto
+ * With d = metric + 1 (x^1 = x, x^2 = x * x rounded once):
+ *     first pick: s1 = s at the first peak (NaN when nothing can be selected)
+ *         L = max(threshold^d, (nsigma * sigma)^d, (peak_frac^d) * |s1|)      every product rounded once; a term whose
+ *             factor is 0 is left out (noise is then not read), and s1's term when s1 does not exist; nsigma > 0 with a
+ *             NaN sigma: the call stops at once and touches nothing but stats (reason 3)
+ *     repeat at most niter times:
+ *         k = the flat index of the largest |s| over border <= y, x < N - border with mask[k] != 0; ties go to the lowest
+ *             flat index; a NaN s is never selected (so a NaN in any plane, under any weight, excludes the cell)
+ *         nothing selectable: stop, reason 2
+ *         |s[k]| <= L: stop, reason 1                 (before anything is subtracted and before the niter test)
+ *         for every p:  f_p = gain * R_p[k] (rounded once);  models[p][k] += f_p;  flux_p += f_p   (one fused multiply-add
+ *                       each, as gridhip_clean's);  R_p -= f_p * psf_q(p) over gridhip_clean's update region and patch
+ *                       rule, the product rounded, then subtracted
+ *     stats (GRIDHIP_JCLEAN_STATS = 16 doubles) = { iterations, s at the final k*, k*, L, reason, s1, 0, 0,
+ *                       flux_0 .. flux_7 }, k* the peak of the final residuals under the same rule (NaN at -1 when none);
+ *                       reason 0: niter components taken; unused flux slots are 0
+ * The sumsq stop level is therefore in image units: the polarised intensity sqrt(Q^2 + U^2 + ...) <= T is tested as
+ * s <= T * T; no square root is taken anywhere.  No atomics: a call is deterministic bit for bit, and the host and _dev
+ * forms give the same bits.  IDENTITY: with P = 1, metric 0 and weights NULL, residuals, models and iterations, final
+ * peak, index, flux, T, reason and first peak have the bits of gridhip_clean_auto for the same mask, nsigma, noise and
+ * peak_frac.
+ * Arguments, checked before anything is touched: gridhip_clean_auto's rules for N, gain, threshold, niter, border, patch,
+ * nsigma, peak_frac, noise, NULL pointers and the limit on N; GRIDHIP_EINVAL for P outside 1 .. 8, Q not in {1, P}, a
+ * metric other than 0 or 1, a bad weight, or any overlap among the Q + 2P planes and the mask.
+ * The shape is gridhip_mfclean's: tiles of 16 x 128 cells and a table of one (score, index) entry per tile; an iteration
+ * is a tile kernel over the overlapped tiles - it reads P residuals and Q PSFs and writes P residuals, (2P + Q) * 8 B
+ * per cell - and a one-work-group kernel that reduces the table, tests the stop rule and reads the P cells at k.
+ * gridhip_jclean is synchronous and stages host arrays through the context's pool.  The _dev form enqueues kernels only
+ * on the context's stream (2 + 2 * niter launches; no memset or copy node), allocates nothing after the first call of a
+ * shape, never synchronises and reads nothing back: it can be captured into a graph.  Scratch (256 B + 16 B per tile)
+ * comes from the context's pool; the state block stops later launches at their first instruction. */
+#define GRIDHIP_JCLEAN_STATS 16
+int gridhip_jclean(gridhip_ctx *ctx, int64_t N, int64_t P, int64_t Q, const double *psfs, double *residuals, double *models,
+                   const double *weights, int metric, double gain, double threshold, int64_t niter, int64_t border,
+                   int64_t patch, const uint8_t *mask, double nsigma, const double *noise, double peak_frac, double *stats);
+int gridhip_jclean_dev(gridhip_ctx *ctx, int64_t N, int64_t P, int64_t Q, const double *psfs, double *residuals,
+                       double *models, const double *weights, int metric, double gain, double threshold, int64_t niter,
+                       int64_t border, int64_t patch, const uint8_t *mask, double nsigma, const double *noise,
+                       double peak_frac, double *stats);
 
 /* ---- multi-GPU: visibility-sharded gridding + one RCCL fp64 sum all-reduce of the partial grids ------
  * Gridding is linear in the visibility set, so the path shards by visibility with no data-path exchange; the

@@ -1,6 +1,6 @@
-// What the three CLEANs (clean.hip, msclean.hip, mfclean.hip) share and nothing else includes: the tile, a tile's table
-// entry, the search rule and its reductions, the stop level of the _auto forms, the one walk over a tile that all three
-// tile kernels are, and on the host the tile grids and the launch loop of a call.
+// What the four CLEANs (clean.hip, msclean.hip, mfclean.hip, jclean.hip) share and nothing else includes: the tile, a
+// tile's table entry, the search rule and its reductions, the stop level of the _auto forms, the one walk over a tile
+// that all four tile kernels are, and on the host the tile grids and the launch loop of a call.
 #pragma once
 #include <type_traits>
 
@@ -86,7 +86,7 @@ __device__ __forceinline__ double stop_level(double threshold, double nsigma, co
     return T;
 }
 
-// One tile per work-group of 256: the body of clean_tile_kernel, ms_tile_kernel and mf_tile_kernel.  SUB = false: grid
+// One tile per work-group of 256: the body of clean_tile_kernel, ms_tile_kernel, mf_tile_kernel and j_tile_kernel.  SUB = false: grid
 // (ntx, nty), the tile's entry from the residual as it is.  SUB = true: the grid covers the most tiles the update
 // region can overlap, counted from the region's first tile; work-groups past its last tile leave.  The update region is
 // the cells whose PSF index lies in the grid when the PSF's centre is put on the component at flat index k, cut to the
@@ -98,11 +98,13 @@ __device__ __forceinline__ double stop_level(double threshold, double nsigma, co
 // its two cells by two 8-byte accesses.  The PSF is read at a shifted offset: 16 bytes at once where that address
 // happens to be aligned (the same for a whole wave), two loads if not.  The tile's best (score, index) goes to
 // table[ty * ntx + tx].
-// The policy p, by value, says what differs between the three:
+// The policy p, by value, says what differs between them:
 //     T, NP             residual planes and PSF planes
 //     res, psf, cells   plane 0 of each and the stride from one plane to the next
 //     product(t, q, p)  the q-th of the T rounded products that plane t of a cell loses, from the cell's PSF values
 //                       p[NP]; the walk subtracts them one after the other, q ascending, where the cell is in the region
+//                       (a product that is the constant +0.0 for some (t, q) costs nothing: both loops are unrolled and
+//                       x - (+0.0) is x for every x - the joint CLEAN's planes, which do not mix, rely on it)
 //     score(r)          what the search maximises in magnitude, from r[T]
 //     searched(a)       whether the cell at flat index a may be selected (the mask; the subtraction does not ask)
 // (contraction is off here whatever the caller's setting; the pragma is lexical, so the policy's methods set their own)

@@ -1,7 +1,7 @@
 // libgridhip internal declarations of the layer around the gridder: the host-pointer forms' staging, the transform, the
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
-// msclean.hip, mfclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
+// msclean.hip, mfclean.hip, jclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
 // sources.hip, average.hip, jonescal.hip, mosaic.hip, wstack.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
@@ -305,7 +305,7 @@ struct AwFront {
 int aw_front(gridhip_ctx *ctx, int64_t N, const AwArgs &d, double fc, bool mirror, int weigh, bool want_wt, AwFront &f);
 
 // ---- deconvolution (clean.hip) -------------------------------------------------------------------------------------------
-// (what the three CLEANs share on the device and in their launchers - the tile, the table entry, the search rule, the
+// (what the four CLEANs share on the device and in their launchers - the tile, the table entry, the search rule, the
 // walk over a tile - is in clean_walk.h, which only they include; here are the host declarations)
 // the largest N clean's tile grid holds (65535 rows of 16-row tiles); the restore takes the same limit
 constexpr int64_t CLEAN_MAX_N = 16 * 65535;
@@ -359,6 +359,21 @@ size_t mfclean_scratch_bytes(int64_t N);
 // gridhip_mfclean_dev on checked arguments: kernels only, on ctx->stream; scratch: mfclean_scratch_bytes(N)
 int mfclean_run(gridhip_ctx *ctx, int64_t N, int64_t T, const double *psfs, double *residuals, double *models,
                 double gain, double threshold, int64_t niter, int64_t border, int64_t patch, double *stats, void *scratch);
+
+// ---- joint CLEAN (jclean.hip) -------------------------------------------------------------------------------------------------
+constexpr int JC_MAX_PLANES = 8;
+// gridhip_jclean's argument rules: P, Q, metric and the weights, then clean's and clean_auto's, then no overlap among the
+// Q + 2P planes and the mask (GRIDHIP_EINVAL; clean's GRIDHIP_EUNSUPPORTED limit on N)
+int jclean_check(gridhip_ctx *ctx, int64_t N, int64_t P, int64_t Q, const double *psfs, const double *residuals,
+                 const double *models, const double *weights, int metric, double gain, double threshold, int64_t niter,
+                 int64_t border, int64_t patch, const uint8_t *mask, double nsigma, const double *noise, double peak_frac);
+// the state block and the tile table of an N x N joint clean, the same for every P
+size_t jclean_scratch_bytes(int64_t N);
+// gridhip_jclean_dev on checked arguments: kernels only, on ctx->stream; weights is the host's; scratch: jclean_scratch_bytes(N)
+int jclean_run(gridhip_ctx *ctx, int64_t N, int64_t P, int64_t Q, const double *psfs, double *residuals, double *models,
+               const double *weights, int metric, double gain, double threshold, int64_t niter, int64_t border,
+               int64_t patch, const uint8_t *mask, double nsigma, const double *noise, double peak_frac, double *stats,
+               void *scratch);
 
 // ---- robust image statistics (noise.hip) -----------------------------------------------------------------------------------
 // gridhip_image_stats' argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED)

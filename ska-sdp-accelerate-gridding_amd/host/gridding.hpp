@@ -14,6 +14,7 @@
 //   clean: Hogbom CLEAN, the minor cycle between do_imaging and predict (absent from the reference)
 //   msclean: multi-scale CLEAN, clean with components of several scales (absent from the reference)
 //   mfclean: multi-term CLEAN, the minor cycle of wide-band imaging over T Taylor terms (absent from the reference)
+//   jclean: joint CLEAN of P images of one sky - Stokes planes, channels - at shared positions (absent from the reference)
 //   automask: the clean mask from the map itself - two levels, pruned, grown, accumulated (absent from the reference)
 //   fit_beam / restore: the restoring beam of a PSF, and model * beam + residual (absent from the reference)
 //   weights: natural, uniform and Briggs imaging weights with a taper and data weights (absent from the reference)
@@ -343,6 +344,35 @@ class Backend {  // plays the role of the (run, runN) pair of `Runners`, src/Gri
         check(gridhip_mfclean(ctx_, N, T, psfs.data(), images.data(), models.data(), gain, threshold, niter, border, patch,
                               st));
         return {st[0], st[1], st[2], {st[3], st[4], st[5], st[6]}, st[7]};
+    }
+
+    // ---- joint CLEAN (gridhip_jclean; include/gridhip.h, "joint deconvolution") ----
+    // P images of one sky, 1 <= P <= 8, as a stack of N x N planes, searched on one statistic - metric 0: the weighted
+    // sum of the planes, 1: of their squares - and cleaned at shared positions: images [P][N][N] become the residuals
+    // and models [P][N][N] are accumulated into, both in place; psfs holds one PSF for all planes or one per plane.  An
+    // empty weights is 1 for every plane; an empty mask is none; sigma is the noise the nsigma term multiplies.
+    // reason: 0 niter components taken, 1 the stop level, 2 nothing selectable, 3 no usable sigma.
+    struct JCleanStats {
+        F iterations, peak, index, level, reason, first_peak;
+        F flux[8];
+    };
+    JCleanStats jclean(Int N, Int P, std::vector<F> &images, const std::vector<F> &psfs, std::vector<F> &models,
+                       int metric = 1, const std::vector<F> &weights = {}, F gain = 0.1, F threshold = 0.0, Int niter = 100,
+                       Int border = 0, Int patch = 0, const std::vector<uint8_t> &mask = {}, F nsigma = 0.0, F sigma = 0.0,
+                       F peak_frac = 0.0)
+    {
+        if (N < 1 || P < 1 || P > 8 || (Int)images.size() != P * N * N || (Int)models.size() != P * N * N ||
+            ((Int)psfs.size() != N * N && (Int)psfs.size() != P * N * N) ||
+            (!weights.empty() && (Int)weights.size() != P) || (!mask.empty() && (Int)mask.size() != N * N))
+            throw Error(GRIDHIP_EINVAL, "jclean: images and models must be P x N x N, psfs N x N or P x N x N, P in 1 .. 8, "
+                                        "one weight per plane, the mask N x N bytes");
+        F st[GRIDHIP_JCLEAN_STATS] = {0};
+        check(gridhip_jclean(ctx_, N, P, (Int)psfs.size() / (N * N), psfs.data(), images.data(), models.data(),
+                             weights.empty() ? nullptr : weights.data(), metric, gain, threshold, niter, border, patch,
+                             mask.empty() ? nullptr : mask.data(), nsigma, &sigma, peak_frac, st));
+        JCleanStats out = {st[0], st[1], st[2], st[3], st[4], st[5], {}};
+        for (int p = 0; p < 8; ++p) out.flux[p] = st[8 + p];
+        return out;
     }
 
     // ---- image statistics, masks and noise-based stop levels (gridhip_image_stats, gridhip_clean_auto,

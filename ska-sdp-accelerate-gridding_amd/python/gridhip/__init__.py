@@ -35,9 +35,10 @@ from ._marshal import group_ids, rotation as _rotation
 from ._marshal import weighting as _weighting
 from ._marshal import mosaic_args
 from ._marshal import wstack_options
+from ._marshal import JOINT_MAX_PLANES, joint_search, psf_planes
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
-           "rotation_to", "rotation_radec", "average_groups", "facet_grid"]
+           "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve"]
 
 
 class Context(Handle):
@@ -501,6 +502,38 @@ class Context(Handle):
         models = in_place(be, models, shape, "models", images)
         stats = be.empty(8, be.f64, images)
         self._call(be, "mfclean", N, T, psfs, images, models, *clean_scalars(gain, threshold, niter, border, patch), stats)
+        return models, images, stats
+
+    def jclean(self, images, psfs, metric="sumsq", weights=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0,
+               models=None, mask=None, nsigma=0.0, noise=None, peak_frac=0.0):
+        """Joint CLEAN of the P images `images` ([P, N, N] float64, 1 <= P <= 8) of one sky - Stokes planes, channels -
+        (gridhip_jclean[_dev]; include/gridhip.h, "joint deconvolution"): the search runs on one statistic, metric "sum":
+        s = sum_p w_p R_p, or "sumsq": s = sum_p w_p R_p^2, and every component is taken at one cell in all planes, plane
+        p losing gain * R_p[k] times its PSF.  `psfs` is [N, N] or [1, N, N] - one PSF for all planes - or [P, N, N], one
+        per plane.  `weights`: P host numbers, finite and >= 0 (a plane of weight 0 does not steer the search and is
+        still cleaned); None is 1 / P each for "sum" - the mean image, so that thresholds stay in image units - and 1
+        each for "sumsq".  The loop stops at |s| <= L = max(threshold^d, (nsigma * sigma)^d, peak_frac^d * |first s|),
+        d = 1 for "sum" and 2 for "sumsq": the levels are given in image units.  border, patch, mask, nsigma, noise and
+        peak_frac as for clean.  `images` is UPDATED IN PLACE and returned as the residuals; `models` ([P, N, N], zeros
+        when None) is accumulated into.  Returns (models, residuals, stats); stats = [iterations, s at the final peak,
+        its flat index, L, reason, first s, 0, 0, flux_0 .. flux_7] with clean's reasons.  numpy arrays take the
+        synchronous host form; torch cuda tensors the asynchronous one on torch's stream, with stats a cuda tensor.  As
+        for clean, a numeric `noise` with cuda tensors is a host-to-device copy and cannot be captured: pass a device
+        element such as image_stats(...)[3:4]."""
+        be = backend(images)
+        shape = tuple(getattr(images, "shape", ()))
+        if len(shape) != 3 or shape[1] != shape[2] or not 1 <= shape[0] <= JOINT_MAX_PLANES:
+            raise ValueError(f"images must be P x N x N with P in 1 .. {JOINT_MAX_PLANES}")
+        P, N = shape[0], shape[1]
+        images = in_place(be, images, shape, "images")
+        Q, psfs = psf_planes(be, psfs, P, N)
+        search, keep = joint_search(metric, weights, P)
+        models = in_place(be, models, shape, "models", images)
+        auto = auto_args(be, mask, nsigma, noise, peak_frac, (N, N), images) or (None, 0.0, None, 0.0)
+        stats = be.empty(16, be.f64, images)
+        self._call(be, "jclean", N, P, Q, psfs, images, models, *search,
+                   *clean_scalars(gain, threshold, niter, border, patch), *auto, stats)
+        del keep
         return models, images, stats
 
     def fit_beam(self, psf, window=8, cut=0.5):
@@ -1596,6 +1629,59 @@ def average_groups(a1, a2, time, ntime=1, chan=None, nchan=1, uvw=None, bda=None
     block = torch.div(chan, nchan, rounding_mode="floor")
     keys, group = torch.unique(torch.stack((lo, hi, window, block), dim=1), dim=0, sorted=True, return_inverse=True)
     return group.to(torch.int64), int(keys.shape[0]), keys[:, 0].contiguous(), keys[:, 1].contiguous()
+
+
+def joint_deconvolve(imagers, vis, nmajor, metric="sumsq", weights=None, noise_plane=None, **clean_kw):
+    """The joint major cycle over P imagers of one N and one context - one per Stokes parameter, or one per channel - a
+    composition DEFINED BY THE CALLS IT REPLACES (include/gridhip.h, "joint deconvolution"):
+        repeat nmajor times:
+            images[p] = imagers[p].cycle(vis[p], model=models[p], out=images[p])     for every p
+            noise = ctx.image_stats(images[noise_plane], border=border)[3:4]          when nsigma > 0
+            ctx.jclean(images, psfs, metric, weights, models=models, noise=noise, **clean_kw)
+        images[p] = imagers[p].cycle(vis[p], model=models[p], out=images[p])         for every p
+    `vis` holds one stream per imager ([P, n], or a sequence of P tensors).  psfs is the stack of the imagers' PSFs,
+    built by the first call and kept; where every entry of `imagers` is the same object - the Stokes streams of one set
+    of baselines - it is that imager's one PSF.  noise_plane: the plane whose robust sigma the nsigma term multiplies
+    (None: the last one, Stokes V of an I, Q, U, V set).  clean_kw: jclean's gain, threshold, niter, border, patch,
+    models, mask, nsigma and peak_frac.  Returns (models, images, stats[nmajor, 16]): the models accumulated into, the
+    closing residual images and jclean's stats of every major cycle.  Everything is enqueued on torch's stream and
+    nothing is read back; after a first call the loop can be captured into a graph."""
+    imagers = list(imagers)
+    P, nmajor = len(imagers), int(nmajor)
+    if not 1 <= P <= JOINT_MAX_PLANES or nmajor < 0:
+        raise ValueError(f"joint_deconvolve takes 1 .. {JOINT_MAX_PLANES} imagers and nmajor >= 0")
+    first = imagers[0]
+    ctx, N, dev = first.ctx, first.N, first.device
+    if any(im.ctx is not ctx or im.N != N for im in imagers):
+        raise ValueError("the imagers must share one context and one image size")
+    if len(vis) != P:
+        raise ValueError(f"vis must hold one stream per imager ({P})")
+    unknown = set(clean_kw) - {"gain", "threshold", "niter", "border", "patch", "models", "mask", "nsigma", "peak_frac"}
+    if unknown:
+        raise ValueError(f"joint_deconvolve has no option {sorted(unknown)}")
+    kw = dict(clean_kw)
+    be = device()
+    models = in_place(be, kw.pop("models", None), (P, N, N), "models", dev)
+    nsigma, border = float(kw.get("nsigma", 0.0)), int(kw.get("border", 0))
+    plane = P - 1 if noise_plane is None else int(noise_plane)
+    if not 0 <= plane < P:
+        raise ValueError(f"noise_plane must be in 0 .. {P - 1}")
+    cached = getattr(first, "_joint_psfs", None)
+    if cached is None or len(cached[0]) != P or any(a is not b for a, b in zip(cached[0], imagers)):
+        shared = all(im is first for im in imagers)
+        psfs = first.psf.reshape(1, N, N) if shared else be.torch.stack([im.psf for im in imagers])
+        cached = first._joint_psfs = (tuple(imagers), psfs)
+    psfs = cached[1]
+    images = be.empty((P, N, N), be.f64, dev)
+    stats = be.empty((nmajor, 16), be.f64, dev)
+    for i in range(nmajor):
+        for p, im in enumerate(imagers):
+            im.cycle(vis[p], model=models[p], out=images[p])
+        noise = ctx.image_stats(images[plane], border=border)[3:4] if nsigma > 0.0 else None
+        stats[i].copy_(ctx.jclean(images, psfs, metric, weights, models=models, noise=noise, **kw)[2])
+    for p, im in enumerate(imagers):
+        im.cycle(vis[p], model=models[p], out=images[p])
+    return models, images, stats
 
 
 def default_context(device=0):

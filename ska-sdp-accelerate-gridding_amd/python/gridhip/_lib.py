@@ -40,6 +40,8 @@ _MSCLEAN = [vp, i64, vp, vp, vp, i64, _HOST_F64, _HOST_F64, C.c_double, C.c_doub
 _AUTO = [vp, C.c_double, vp, C.c_double]  # mask, nsigma, noise, peak_frac (the _auto forms, before stats)
 _CLEAN_AUTO = _CLEAN[:-1] + _AUTO + [vp]
 _MSCLEAN_AUTO = _MSCLEAN[:-1] + _AUTO + [vp]
+# N, P, Q, psfs, residuals, models, weights (the host's in both forms), metric, then clean's scalars, _AUTO and stats
+_JCLEAN = [vp, i64, i64, i64, vp, vp, vp, _HOST_F64, ci, C.c_double, C.c_double, i64, i64, i64, *_AUTO, vp]
 _IMAGE_STATS = [vp, i64, vp, vp, i64, vp]
 # border, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, grow (automask, after image and mask)
 _AUTOMASK_ARGS = [i64, ci, C.c_double, C.c_double, C.c_double, C.c_double, vp, C.c_double, i64, i64]
@@ -241,6 +243,8 @@ SIGNATURES = {
     "gridhip_do_imaging_wstack_dev": (ci, _WSTACK + _WSTACK_STREAM + [vp, vp, vp, C.POINTER(C.c_double)]),
     "gridhip_predict_wstack": (ci, _WSTACK + [vp] + _WSTACK_STREAM + [vp, vp]),
     "gridhip_predict_wstack_dev": (ci, _WSTACK + [vp] + _WSTACK_STREAM + [vp, vp]),
+    "gridhip_jclean": (ci, _JCLEAN),
+    "gridhip_jclean_dev": (ci, _JCLEAN),
     "gridhip_comm_create": (ci, [ci, C.POINTER(ci), C.POINTER(vp)]),
     "gridhip_comm_unique_id": (ci, [vp]),
     "gridhip_comm_create_rank": (ci, [vp, ci, ci, vp, C.POINTER(vp)]),

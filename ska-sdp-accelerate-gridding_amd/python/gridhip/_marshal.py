@@ -287,6 +287,41 @@ def scale_list(scales, bias):
     return (int(sc.size), sc.ctypes.data_as(f64p), bs.ctypes.data_as(f64p)), (sc, bs)
 
 
+JOINT_METRICS = {"sum": 0, "sumsq": 1}  # gridhip_jclean's metric
+JOINT_MAX_PLANES = 8
+
+
+def joint_search(metric, weights, P):
+    """weights, metric as gridhip_jclean takes them: the metric by name and P host float64 weights whichever back end the
+    images come from, passed by address - the caller keeps the returned array alive for the call.  weights=None: 1 / P
+    each for "sum" (the mean image, so that thresholds stay in image units), 1 each for "sumsq".  What the library would
+    refuse is refused here: a weight that is not finite and >= 0, or none above 0."""
+    if metric not in JOINT_METRICS:
+        raise ValueError(f"metric must be one of {sorted(JOINT_METRICS)}, not {metric!r}")
+    if weights is None:
+        w = np.full(P, 1.0 / P if metric == "sum" else 1.0, dtype=np.float64)
+    else:
+        if is_torch(weights):
+            weights = weights.detach().cpu().numpy()
+        w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+    if w.size != P:
+        raise ValueError(f"weights must hold one value per plane ({P}), not {w.size}")
+    if not (np.isfinite(w).all() and (w >= 0.0).all() and (w > 0.0).any()):
+        raise ValueError("weights must be finite and >= 0, at least one of them > 0")
+    return (w.ctypes.data_as(C.POINTER(C.c_double)), JOINT_METRICS[metric]), w
+
+
+def psf_planes(be, psfs, P, N):
+    """Q, psfs as gridhip_jclean takes the PSFs: (N, N) or (1, N, N) - one PSF for all planes - or (P, N, N), one per
+    plane, float64"""
+    shape = tuple(getattr(psfs, "shape", ()))
+    if shape == (N, N):
+        shape = (1, N, N)
+    if len(shape) != 3 or shape[1:] != (N, N) or shape[0] not in (1, P):
+        raise ValueError(f"psfs must be {(N, N)}, {(1, N, N)} or {(P, N, N)}: one PSF, or one per plane, not {shape}")
+    return shape[0], be.cv(psfs, be.f64)
+
+
 def image_of(be, x, shape, what):
     """An N x N float64 image an entry point only reads (restore's model and residual), converted where it must be"""
     x = be.cv(x, be.f64)
