@@ -466,6 +466,15 @@ foreign import ccall unsafe "gridhip_flag_residuals_dev"
 -- int gridhip_imager_flag_dev(imager, model, vis, G, group, wt_in, nsigma, amax, min_count, niter, wt_out, flags_out, group_stats, stats)
 foreign import ccall unsafe "gridhip_imager_flag_dev"
   c_imager_flag_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_sumthreshold(ctx, B, T, F, order, vis, model_vis, wt_in, K, levels, eta_f, eta_t, min_count, niter, wt_out, flags_out, baseline_stats, stats)
+foreign import ccall unsafe "gridhip_sumthreshold"
+  c_sumthreshold :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_sumthreshold_dev(ctx, B, T, F, order, vis, model_vis, wt_in, K, levels, eta_f, eta_t, min_count, niter, wt_out, flags_out, baseline_stats, stats)
+foreign import ccall unsafe "gridhip_sumthreshold_dev"
+  c_sumthreshold_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_sumthreshold_tile(tile_t, tile_f)
+foreign import ccall unsafe "gridhip_sumthreshold_tile"
+  c_sumthreshold_tile :: Ptr Int64 -> Ptr Int64 -> IO CInt
 -- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
 foreign import ccall unsafe "gridhip_dft_predict"
   c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt

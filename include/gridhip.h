@@ -1393,6 +1393,86 @@ int gridhip_imager_flag_dev(gridhip_imager *imager, const double *model, const d
                             const int64_t *group, const double *wt_in, double nsigma, double amax, int64_t min_count,
                             int64_t niter, double *wt_out, uint8_t *flags_out, double *group_stats, double *stats);
 
+/* ---- time-frequency flagging: SumThreshold and the scale-invariant rank operator over a baseline's waterfall ----------------
+ * The reference has no flagging: the semantics are defined here.  gridhip_flag_residuals looks at every sample on its own;
+ * interference that lifts every channel of a few time steps, or one channel for a whole scan, by about one sigma shows
+ * only in sums along time or frequency.  This is SumThreshold (Offringa et al. 2010) followed by the SIR operator (Offringa
+ * et al. 2012), which extends the flags over samples that are mostly surrounded by flags.
+ * DATA.  A dense cube of B baselines x T time steps x F channels, n = B T F samples.  order 0: [B][T][F]; order 1:
+ *     [T][B][F], the order of a measurement set; F is innermost in both and nothing is copied or transposed for either.
+ *     vis: interleaved complex doubles; model_vis: the same shape, or NULL for zero; wt_in: n doubles s_k, or NULL for all
+ *     ones.  A cell of the cube that holds no measurement carries the weight 0.
+ * CLASSES.  The FIRST class that applies sets the code of a sample in flags_out (n bytes, may be NULL):
+ *     1            FLAGGED ON INPUT  s_k is not > 0 (zero, negative, NaN)
+ *     3            NOT FINITE        a_k is NaN or Inf
+ *     16 + 8 r + k flagged by SumThreshold in round r, stage k
+ *     8            added by the SIR operator
+ *     0            KEPT
+ *     a_k is the amplitude of vis - model_vis exactly as gridhip_flag_residuals defines it: each component one rounded
+ *     subtraction, a_k = sqrt(re * re + im * im) with both products rounded, the sum rounded, no fused multiply-add and a
+ *     correctly rounded square root.
+ * ROUNDS r = 0 .. niter - 1, 0 <= niter <= 4, over the PARTICIPANTS, the samples of class 0.  For every baseline b:
+ *     n_b the number of its participants; med_b and MAD_b the lower medians of gridhip_flag_residuals (the element of rank
+ *     (n_b - 1) / 2 of a_k, and of |a_k - med_b|); sigma_b = 1.4826 * MAD_b.  If n_b < min_count or sigma_b == 0 the
+ *     baseline is not thresholded in this round.  Otherwise e_k = a_k - med_b, one rounded subtraction, and for the STAGES
+ *     k = 0 .. K - 1, 1 <= K <= 7, chi_k(b) = levels[k] * sigma_b, one rounded product, with the window length M = 2^k.
+ *     levels: K finite positive doubles, in host memory in both forms (they are read while the call is checked).
+ * A STAGE works from the participants as the previous stage left them; both directions use the same set.  Along a row of
+ *     length L (L = F along frequency, L = T along time) a direction with M > L does nothing.  Otherwise x_i = e_i for a
+ *     participant and +0.0 otherwise, c_i = 1 for a participant and 0 otherwise, and the window sums are the doubling tree
+ *         S^(1)_j = x_j,   S^(2m)_j = S^(m)_j + S^(m)_{j+m}, each addition rounded once,
+ *     C_j likewise (exact), both for the starts j = 0 .. L - M only.  Window j is HIT when C_j > 0 and
+ *     S_j > chi_k * (double)C_j, the product rounded once; sample i is hit when any window j in [max(0, i - M + 1),
+ *     min(i, L - M)] is hit.  A participant that is hit in either direction gets the code 16 + 8 r + k and is no
+ *     participant from the next stage on.  Only positive excess is tested: interference adds power.
+ *     A round in which no stage flags anything ends the loop.
+ * SIR runs after the rounds, also with niter = 0: along frequency with eta_f, then along time with eta_t on the result; a
+ *     direction whose eta == 0 is skipped.  q = rint(eta * 2^20) (the product is exact).  Per row the int64 weights are
+ *     w = q for the codes 3, 8 and >= 16, q - 2^20 for code 0, and 0 for code 1 - a missing cell neither attracts nor repels
+ *     flags.  P_0 = 0, P_{j+1} = P_j + w_j; a sample x of code 0 gets the code 8 when
+ *         max_{j > x} P_j - min_{i <= x} P_i >= 0,
+ *     that is when some interval around it holds a fraction of at least (1 - eta) of flagged samples.  Integer arithmetic.
+ * OUTPUTS.  wt_out (n doubles; may be wt_in itself) holds s_k (1 without weights) for code 0 and exactly +0.0 otherwise;
+ *     vis is never written.  baseline_stats ([B][4] doubles, may be NULL) holds { n_b, med_b, MAD_b, chi_0(b) } as the last
+ *     round that ran saw them; a baseline that was not thresholded gives chi_0 = +Inf, an empty one { 0, NaN, NaN, +Inf },
+ *     and with niter = 0 every baseline has that form with its count.  stats (8 doubles, may be NULL): { rounds run (the
+ *     one that flagged nothing included), participants at the start, flagged by SumThreshold, not finite, added by SIR, 0,
+ *     flagged on input, kept }.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL context; B, T or F < 1; order not 0 or 1; a
+ * NULL vis or wt_out; K outside 1..7 or a NULL levels; a level not finite or <= 0; eta_f or eta_t not in [0, 1);
+ * min_count < 1; niter outside 0..4; any output overlapping an input or another output, other than wt_out == wt_in.
+ * GRIDHIP_EUNSUPPORTED: B above 2^18, T or F above 2^20 (1048576), n above 2^32 - 1.
+ * gridhip_sumthreshold is synchronous and stages host arrays through the context's pool.  The _dev form takes device
+ * pointers (levels stays a host array) and enqueues kernels only on the context's stream - no memset node, no copy node;
+ * it allocates nothing after the first call of a shape (the scratch - 13 B per sample, 16 B more when a SIR direction runs,
+ * 1 KB of bins and 40 B of state per baseline - comes from the context's pool), never synchronises, reads nothing back
+ * and can be captured into a graph.  The stop test lives on the device as in gridhip_flag_residuals: all rounds are
+ * enqueued, the stages of a round count what they flag, and every launch of the next round reads that count first and
+ * returns at once when it is zero.  The launch count, 3 + niter (32 + K) + 2 per SIR direction (2 more for niter = 0),
+ * depends on (niter, K, eta) and on nothing in the data.
+ * A call is: the front pass and, per round, the select of gridhip_flag_residuals (one copy of each serves both); per stage
+ * one launch in which a work-group owns a tile of tile_t x tile_f samples of one baseline (gridhip_sumthreshold_tile),
+ * stages x and c of the tile and a halo of M - 1 either side along the direction in LDS, builds the tree and the sliding
+ * OR of the hits there by the same doubling, for both directions, and writes the codes of its own tile only, in place;
+ * per SIR direction a forward scan with a running minimum and a backward running maximum, one wave per row; and a pass
+ * that writes wt_out.
+ * DETERMINISM.  Every output is an order statistic, a count, an integer sum or a fixed tree of rounded additions:
+ * integer atomics only, no floating-point atomic.  The bits are the same for the host and _dev forms, for two runs, for
+ * both orders of the same cube, and for a numpy restatement (S = S[..., :-m] + S[..., m:] is the tree).
+ * NOT HERE: the smooth background fit of the full AOFlagger strategy (model_vis, for instance an imager's prediction, is
+ * how a caller removes structure); several correlations in one call (call per Stokes plane and combine the weights); an
+ * imager form; two-sided thresholds; windows above 64; several devices. */
+int gridhip_sumthreshold(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int order, const double *vis,
+                         const double *model_vis, const double *wt_in, int64_t K, const double *levels, double eta_f,
+                         double eta_t, int64_t min_count, int64_t niter, double *wt_out, uint8_t *flags_out,
+                         double *baseline_stats, double *stats);
+int gridhip_sumthreshold_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int order, const double *vis,
+                             const double *model_vis, const double *wt_in, int64_t K, const double *levels, double eta_f,
+                             double eta_t, int64_t min_count, int64_t niter, double *wt_out, uint8_t *flags_out,
+                             double *baseline_stats, double *stats);
+/* the stage kernel's tile, so that a caller (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
+int gridhip_sumthreshold_tile(int64_t *tile_t, int64_t *tile_f);
+
 /* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
  * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image
  * and a degridder; this one evaluates the measurement equation itself,

@@ -24,6 +24,9 @@
 // The stop test lives on the device (clean.hip's scheme): round r counts what it clips in its own counter, every launch
 // of round r + 1 reads that counter first and returns when it is zero - the zero counter IS the stop flag, and a round
 // that never ran leaves its counter zero for the rounds after it.
+// The front pass (flag_front) and the select of a round (flag_select) also serve time-frequency flagging (sumthreshold.hip),
+// through imaging.h: its groups are the baselines of a dense cube, found from the sample's index, and its threshold is
+// nsigma * sigma_g without the median.
 // Determinism: counts, key comparisons and one rounded expression per output (contraction off); no floating-point atomic
 // and no sum of doubles anywhere in this file.  The result is the same bits on every run and the bits a host sort gives.
 #include "common.h"
@@ -36,25 +39,8 @@ namespace {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-constexpr u32 FLAG_DEAD = 0xffffffffu;  // the group code of a visibility that takes part in nothing
-constexpr u32 FLAG_LEFT = 0xfffffffeu;  // and of one that is left alone
 constexpr u64 EXP_MASK = 0x7ff0000000000000ULL;
 static_assert(FLAG_MAX_GROUPS < (int64_t)FLAG_LEFT, "a group code holds every group and the two reserved values");
-
-struct FlagState {  // 256 bytes at the head of the scratch block
-    u32 clipped[FLAG_MAX_ROUNDS];  // per round; the counter of round r is the stop flag of round r + 1
-    u32 cls[5];                    // participants at the start of round 0, then the visibilities of the classes 1 to 4
-    u32 pad[43];
-};
-static_assert(sizeof(FlagState) == 256, "the state block");
-
-struct FlagGroup {  // one row of the per-group state table
-    u64 prefix;     // the digits of the wanted key chosen so far (the lower bits zero)
-    double med, mad, T;
-    u32 rank;  // the wanted rank among the participants whose higher digits equal the prefix
-    u32 n;     // the participants of the group in this round
-};
-static_assert(sizeof(FlagGroup) == 40, "the per-group state");
 
 struct FlagLayout {
     size_t state, groups, bins, keys, codes, total;
@@ -76,16 +62,6 @@ FlagLayout layout(int64_t n, int64_t G)
     return l;
 }
 
-// has round r been stopped?  (round 0 always runs)
-__device__ __forceinline__ bool stopped(const FlagState *st, int r) { return r > 0 && st->clipped[r - 1] == 0; }
-
-// the sum of x over the work-group's waves goes to *dst with one integer atomic per wave
-__device__ __forceinline__ void wave_count(u32 x, u32 *dst)
-{
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
-    if ((threadIdx.x & 63) == 0 && x) atomicAdd(dst, x);
-}
-
 // words: the 32-bit words of the bin table (a multiple of 4).  The two slots behind the n codes are dead (layout).
 __global__ void __launch_bounds__(256)
     flag_init_kernel(int64_t words, int64_t n, FlagState *st, u32 *__restrict__ bins, u64 *__restrict__ keys,
@@ -99,8 +75,9 @@ __global__ void __launch_bounds__(256)
 }
 
 // The classes 1 to 4 (the first that applies), the key and the group code of every visibility; flags may be null.
+// cube_div > 0: the group is (k / cube_div) % G, the baseline of a dense cube (imaging.h), and `group` is not read.
 __global__ void __launch_bounds__(256)
-    flag_front_kernel(int64_t n, int64_t G, const int64_t *__restrict__ group, const double2 *__restrict__ vis,
+    flag_front_kernel(int64_t n, int64_t G, const int64_t *__restrict__ group, int64_t cube_div, const double2 *__restrict__ vis,
                       const double2 *__restrict__ mod, const double *__restrict__ wt, double amax, u64 *__restrict__ keys,
                       u32 *__restrict__ codes, uint8_t *__restrict__ flags, FlagState *st)
 {
@@ -109,7 +86,7 @@ __global__ void __launch_bounds__(256)
     u32 c[5] = {0u, 0u, 0u, 0u, 0u};
     for (int64_t k = k0; k < n; k += step) {
         const double s = wt ? wt[k] : 1.0;
-        const int64_t g = group ? group[k] : 0;
+        const int64_t g = cube_div > 0 ? (int64_t)(((u64)k / (u64)cube_div) % (u64)G) : group ? group[k] : 0;
         int cl = 0;
         u64 key = 0ull;
         if (!(s > 0.0)) {
@@ -135,7 +112,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
         for (int j = 0; j < 5; ++j) c[j] += (u32)(cl == j);
     }
-    for (int j = 0; j < 5; ++j) wave_count(c[j], &st->cls[j]);
+    for (int j = 0; j < 5; ++j) flag_wave_count(c[j], &st->cls[j]);
 }
 
 // One digit (the 8 bits from `shift` up) of the key of every participant whose bits above the digit equal its group's
@@ -148,7 +125,7 @@ __global__ void __launch_bounds__(256)
 {
 #pragma clang fp contract(off)
     extern __shared__ u32 lbins[];
-    if (stopped(st, round)) return;
+    if (flag_stopped(st, round)) return;
     const int hi = shift + 8, nb = G * 256;
     if (LDS) {
         for (int i = threadIdx.x; i < nb; i += 256) lbins[i] = 0u;
@@ -189,13 +166,14 @@ __global__ void __launch_bounds__(256)
 // first: the first pass of a round - n_g is the sum of all bins and the wanted rank (n_g - 1) / 2; a group that is empty
 // gets { 0, NaN, NaN, +Inf } and is skipped by every later pick of the round (nothing is ever added to its bins).
 // last: 1 - the prefix is the median: into the state, and the second selection starts from an empty prefix and the same
-// rank; 2 - the prefix is the MAD: T_g and the group's stats row; 3 (niter = 0, with first) - the count alone.
+// rank; 2 - the prefix is the MAD: T_g (sigma_only: nsigma * sigma_g without the median, sumthreshold.hip's chi_0) and
+// the group's stats row; 3 (niter = 0, with first) - the count alone.
 __global__ void __launch_bounds__(256)
-    flag_pick_kernel(int64_t G, int shift, int first, int last, int round, double nsigma, int64_t min_count, FlagGroup *gs,
+    flag_pick_kernel(int64_t G, int shift, int first, int last, int round, double nsigma, int sigma_only, int64_t min_count, FlagGroup *gs,
                      u32 *bins, const FlagState *st, double *__restrict__ group_stats)
 {
 #pragma clang fp contract(off)
-    if (stopped(st, round)) return;
+    if (flag_stopped(st, round)) return;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= G) return;
     const int lane = threadIdx.x & 63;
@@ -249,7 +227,7 @@ __global__ void __launch_bounds__(256)
         const double med = s->med, mad = __builtin_bit_cast(double, prefix);
         const double sigma = 1.4826 * mad;
         const double ns = nsigma * sigma;
-        const double T = ((int64_t)n < min_count || sigma == 0.0) ? inf : med + ns;
+        const double T = ((int64_t)n < min_count || sigma == 0.0) ? inf : sigma_only ? ns : med + ns;
         s->mad = mad;
         s->T = T;
         if (group_stats) {
@@ -265,7 +243,7 @@ __global__ void __launch_bounds__(256)
     flag_clip_kernel(int64_t pairs, int round, const u64 *__restrict__ keys, u32 *codes, const FlagGroup *__restrict__ gs,
                      FlagState *st, uint8_t *__restrict__ flags)
 {
-    if (stopped(st, round)) return;
+    if (flag_stopped(st, round)) return;
     const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(keys);
     const uint2 *c2 = reinterpret_cast<const uint2 *>(codes);  // (a slot is read and then written by the same lane)
     const int64_t T = (int64_t)gridDim.x * 256;
@@ -283,7 +261,7 @@ __global__ void __launch_bounds__(256)
             count += 1u;
         }
     }
-    wave_count(count, &st->clipped[round]);
+    flag_wave_count(count, &st->clipped[round]);
 }
 
 // wt_out = the data weight (1 without data weights) where the visibility is kept or left alone, else +0.0.  wt_out may be
@@ -352,17 +330,34 @@ int flag_check(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, con
 
 size_t flag_scratch_bytes(int64_t n, int64_t G) { return layout(n, G).total; }
 
-int flag_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis, const double *model_vis,
-             const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter, double *wt_out,
-             uint8_t *flags_out, double *group_stats, double *stats, void *scratch)
+FlagScratch flag_scratch_parts(void *scratch, int64_t n, int64_t G)
 {
     const FlagLayout l = layout(n, G);
     char *base = reinterpret_cast<char *>(scratch);
-    FlagState *st = reinterpret_cast<FlagState *>(base + l.state);
-    FlagGroup *gs = reinterpret_cast<FlagGroup *>(base + l.groups);
-    u32 *bins = reinterpret_cast<u32 *>(base + l.bins);
-    u64 *keys = reinterpret_cast<u64 *>(base + l.keys);
-    u32 *codes = reinterpret_cast<u32 *>(base + l.codes);
+    FlagScratch s;
+    s.st = reinterpret_cast<FlagState *>(base + l.state);
+    s.gs = reinterpret_cast<FlagGroup *>(base + l.groups);
+    s.bins = reinterpret_cast<u32 *>(base + l.bins);
+    s.keys = reinterpret_cast<u64 *>(base + l.keys);
+    s.codes = reinterpret_cast<u32 *>(base + l.codes);
+    return s;
+}
+
+int flag_front(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, int64_t cube_div, const double *vis,
+               const double *model_vis, const double *wt_in, double amax, uint8_t *flags_out, const FlagScratch &s)
+{
+    const int64_t words = G * 256;
+    hipLaunchKernelGGL(flag_init_kernel, grid_for(ctx, words / 4), dim3(256), 0, ctx->stream, words, n, s.st, s.bins, s.keys,
+                       s.codes);
+    hipLaunchKernelGGL(flag_front_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, G, group, cube_div,
+                       (const double2 *)vis, (const double2 *)model_vis, wt_in, amax, s.keys, s.codes, flags_out, s.st);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int flag_select(gridhip_ctx *ctx, int64_t n, int64_t G, int round, double level, bool sigma_only, int64_t min_count,
+                double *group_stats, const FlagScratch &s)
+{
     const bool lds = G <= FLAG_LDS_GROUPS;
     const size_t lds_bytes = lds ? (size_t)G * 1024 : 0;
     if (!ctx->img->flag_lds_raised) {  // (64 KB of dynamic LDS at G = 64: the functions are told so once)
@@ -372,40 +367,53 @@ int flag_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const
                                               hipFuncAttributeMaxDynamicSharedMemorySize, FLAG_LDS_GROUPS * 1024));
         ctx->img->flag_lds_raised = true;
     }
-    const int64_t words = G * 256, pairs = (n + 1) / 2;
-    const dim3 sgrid = grid_for(ctx, n), pgrid = grid_for(ctx, pairs), kgrid((unsigned)((G + 3) / 4));
+    const int64_t pairs = (n + 1) / 2;
+    const dim3 pgrid = grid_for(ctx, pairs), kgrid((unsigned)((G + 3) / 4));
     // the LDS path zeroes and walks its table in every work-group: fewer, longer-lived work-groups the larger the table
     int64_t hwg = (pairs + 1023) / 1024, most = (int64_t)ctx->num_cu * (lds_bytes <= 16384 ? 4 : 2);
     if (hwg < 1) hwg = 1;
     if (hwg > most) hwg = most;
     const dim3 hgrid = lds ? dim3((unsigned)hwg) : pgrid;
-    hipLaunchKernelGGL(flag_init_kernel, grid_for(ctx, words / 4), dim3(256), 0, ctx->stream, words, n, st, bins, keys, codes);
-    hipLaunchKernelGGL(flag_front_kernel, sgrid, dim3(256), 0, ctx->stream, n, G, group, (const double2 *)vis,
-                       (const double2 *)model_vis, wt_in, amax, keys, codes, flags_out, st);
-    const auto hist = [&](bool mad, int shift, int round) {
+    const auto hist = [&](bool mad, int shift, int r) {
         if (lds)
-            launch_hist<true>(ctx, hgrid, lds_bytes, mad, pairs, (int)G, shift, round, keys, codes, gs, st, bins);
+            launch_hist<true>(ctx, hgrid, lds_bytes, mad, pairs, (int)G, shift, r, s.keys, s.codes, s.gs, s.st, s.bins);
         else
-            launch_hist<false>(ctx, hgrid, 0, mad, pairs, (int)G, shift, round, keys, codes, gs, st, bins);
+            launch_hist<false>(ctx, hgrid, 0, mad, pairs, (int)G, shift, r, s.keys, s.codes, s.gs, s.st, s.bins);
     };
-    if (niter == 0) {  // the groups' counts alone
+    const int so = sigma_only ? 1 : 0;
+    if (round < 0) {  // the groups' counts alone
         hist(false, 56, 0);
-        hipLaunchKernelGGL(flag_pick_kernel, kgrid, dim3(256), 0, ctx->stream, G, 56, 1, 3, 0, nsigma, min_count, gs, bins,
-                           (const FlagState *)st, group_stats);
-    }
-    for (int r = 0; r < (int)niter; ++r) {
+        hipLaunchKernelGGL(flag_pick_kernel, kgrid, dim3(256), 0, ctx->stream, G, 56, 1, 3, 0, level, so, min_count, s.gs,
+                           s.bins, (const FlagState *)s.st, group_stats);
+    } else {
         for (int sel = 0; sel < 2; ++sel)
             for (int p = 0; p < 8; ++p) {
                 const int shift = 56 - 8 * p;
-                hist(sel == 1, shift, r);
+                hist(sel == 1, shift, round);
                 hipLaunchKernelGGL(flag_pick_kernel, kgrid, dim3(256), 0, ctx->stream, G, shift, (int)(sel == 0 && p == 0),
-                                   p == 7 ? sel + 1 : 0, r, nsigma, min_count, gs, bins, (const FlagState *)st, group_stats);
+                                   p == 7 ? sel + 1 : 0, round, level, so, min_count, s.gs, s.bins, (const FlagState *)s.st,
+                                   group_stats);
             }
-        hipLaunchKernelGGL(flag_clip_kernel, pgrid, dim3(256), 0, ctx->stream, pairs, r, (const u64 *)keys, codes,
-                           (const FlagGroup *)gs, st, flags_out);
     }
-    hipLaunchKernelGGL(flag_final_kernel, sgrid, dim3(256), 0, ctx->stream, n, (int)niter, (const u32 *)codes, wt_in, wt_out,
-                       (const FlagState *)st, stats);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int flag_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis, const double *model_vis,
+             const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter, double *wt_out,
+             uint8_t *flags_out, double *group_stats, double *stats, void *scratch)
+{
+    const FlagScratch s = flag_scratch_parts(scratch, n, G);
+    const int64_t pairs = (n + 1) / 2;
+    GH_CHECK(flag_front(ctx, n, G, group, 0, vis, model_vis, wt_in, amax, flags_out, s));
+    if (niter == 0) GH_CHECK(flag_select(ctx, n, G, -1, nsigma, false, min_count, group_stats, s));
+    for (int r = 0; r < (int)niter; ++r) {
+        GH_CHECK(flag_select(ctx, n, G, r, nsigma, false, min_count, group_stats, s));
+        hipLaunchKernelGGL(flag_clip_kernel, grid_for(ctx, pairs), dim3(256), 0, ctx->stream, pairs, r, (const u64 *)s.keys,
+                           s.codes, (const FlagGroup *)s.gs, s.st, flags_out);
+    }
+    hipLaunchKernelGGL(flag_final_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, (int)niter, (const u32 *)s.codes,
+                       wt_in, wt_out, (const FlagState *)s.st, stats);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }

@@ -2,7 +2,7 @@
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
 // msclean.hip, mfclean.hip, jclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
-// sources.hip, average.hip, jonescal.hip, mosaic.hip, wstack.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
+// sumthreshold.hip, sources.hip, average.hip, jonescal.hip, mosaic.hip, wstack.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -559,6 +559,54 @@ size_t flag_scratch_bytes(int64_t n, int64_t G);
 int flag_run(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, const double *vis, const double *model_vis,
              const double *wt_in, double nsigma, double amax, int64_t min_count, int64_t niter, double *wt_out,
              uint8_t *flags_out, double *group_stats, double *stats, void *scratch);
+// What time-frequency flagging (sumthreshold.hip) shares with the clip: the front pass and the select, one copy of each.
+constexpr unsigned int FLAG_DEAD = 0xffffffffu;  // the group code of a visibility that takes part in nothing
+constexpr unsigned int FLAG_LEFT = 0xfffffffeu;  // and of one that is left alone
+struct FlagState {  // 256 bytes at the head of the scratch block
+    unsigned int clipped[FLAG_MAX_ROUNDS];  // per round; the counter of round r is the stop flag of round r + 1
+    unsigned int cls[5];  // participants at the start of round 0, then the visibilities of the classes 1 to 4
+    unsigned int sir;     // samples added by the SIR operator (sumthreshold.hip)
+    unsigned int pad[42];
+};
+static_assert(sizeof(FlagState) == 256, "the state block");
+struct FlagGroup {  // one row of the per-group state table
+    unsigned long long prefix;  // the digits of the wanted key chosen so far (the lower bits zero)
+    double med, mad, T;
+    unsigned int rank;  // the wanted rank among the participants whose higher digits equal the prefix
+    unsigned int n;     // the participants of the group in this round
+};
+static_assert(sizeof(FlagGroup) == 40, "the per-group state");
+struct FlagScratch {  // the parts of a block of flag_scratch_bytes(n, G)
+    FlagState *st;
+    FlagGroup *gs;
+    unsigned int *bins;
+    unsigned long long *keys;  // the bits of a_k
+    unsigned int *codes;       // the group of a participant, FLAG_DEAD or FLAG_LEFT
+};
+FlagScratch flag_scratch_parts(void *scratch, int64_t n, int64_t G);
+// has round r been stopped?  (round 0 always runs)
+__device__ __forceinline__ bool flag_stopped(const FlagState *st, int r) { return r > 0 && st->clipped[r - 1] == 0; }
+// the sum of x over the work-group's waves goes to *dst with one integer atomic per wave
+__device__ __forceinline__ void flag_wave_count(unsigned int x, unsigned int *dst)
+{
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
+    if ((threadIdx.x & 63) == 0 && x) atomicAdd(dst, x);
+}
+// flag_init_kernel and flag_front_kernel.  cube_div > 0: the n samples are a dense cube and the group of sample k is
+// (k / cube_div) % G - the baseline of [B][T][F] (cube_div = T F) or of [T][B][F] (cube_div = F); group is not read.
+int flag_front(gridhip_ctx *ctx, int64_t n, int64_t G, const int64_t *group, int64_t cube_div, const double *vis,
+               const double *model_vis, const double *wt_in, double amax, uint8_t *flags_out, const FlagScratch &s);
+// The select of round `round`, 32 launches: n_g, med_g and MAD_g of every group into s.gs, and with sigma_g = 1.4826 MAD_g
+// T_g = med_g + level * sigma_g, or level * sigma_g alone (sigma_only), or +Inf for a group below min_count or of ties;
+// group_stats as gridhip_flag_residuals defines it.  round < 0: the groups' counts alone, 2 launches.
+int flag_select(gridhip_ctx *ctx, int64_t n, int64_t G, int round, double level, bool sigma_only, int64_t min_count,
+                double *group_stats, const FlagScratch &s);
+
+// ---- time-frequency flagging (sumthreshold.hip) ---------------------------------------------------------------------------
+// the stage kernel's tile, the most stages (windows up to 64) and rounds, the longest row
+constexpr int ST_TILE_T = 32, ST_TILE_F = 32;
+constexpr int ST_MAX_STAGES = 7, ST_MAX_ROUNDS = 4;
+constexpr int64_t ST_MAX_ROW = (int64_t)1 << 20;
 
 // ---- direct-Fourier prediction of a component list (dft.hip) ---------------------------------------------------------------
 // gridhip_dft_predict's and gridhip_components_from_image's argument rules (GRIDHIP_EINVAL, GRIDHIP_EUNSUPPORTED); *N: the

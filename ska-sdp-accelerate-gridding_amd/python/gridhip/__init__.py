@@ -29,6 +29,7 @@ from ._marshal import gain_stream, result_array, solve_args, stream_array
 from ._marshal import direction_mask, model_rows
 from ._marshal import jones_array, stokes_args
 from ._marshal import flag_outputs, flag_scalars, flag_stream
+from ._marshal import cube_arrays, sumthreshold_scalars
 from ._marshal import COMP_DOUBLES, component_count, component_list, model_planes
 from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import group_ids, rotation as _rotation
@@ -38,7 +39,8 @@ from ._marshal import wstack_options
 from ._marshal import JOINT_MAX_PLANES, joint_search, psf_planes
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
-           "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve"]
+           "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
+           "waterfall_layout"]
 
 
 class Context(Handle):
@@ -740,6 +742,31 @@ class Context(Handle):
         out, flags, gstats, stats = flag_outputs(be, n, G, out, vis)
         self._call(be, "flag_residuals", n, G, group, vis, model_vis, wt, *scalars, out, flags, gstats, stats)
         return out, flags, gstats, stats
+
+    def sumthreshold(self, vis, model_vis=None, weights=None, order="btf", levels=None, nsigma=6.0, rho=1.5, nlevels=7,
+                     eta=(0.2, 0.2), min_count=8, niter=2, out=None):
+        """Time-frequency flagging of a cube of residuals vis - model_vis (gridhip_sumthreshold[_dev]; include/gridhip.h,
+        "time-frequency flagging"): SumThreshold with the windows 1, 2, 4, ... along frequency and time against
+        levels[k] * sigma_b, sigma_b from the lower median and the MAD of every baseline, in up to niter rounds, then the
+        SIR operator along frequency with eta[0] and along time with eta[1] (0: skipped).  vis is three-dimensional:
+        [B][T][F] for order "btf", [T][B][F] for "tbf"; model_vis and weights have its shape (None: zero; ones - a weight
+        that is not > 0 flags its sample on input, and a cell that holds no measurement carries 0).  levels None: the
+        ladder nsigma / rho^k, k < nlevels.  Returns (weights, flags, baseline_stats, stats): the weights with +0.0 where
+        a sample is flagged (out: the array to write, which may be `weights` itself) and the code of every sample (uint8:
+        0 kept, 1 flagged on input, 3 not finite, 8 added by SIR, 16 + 8 r + k by stage k of round r), both shaped as vis;
+        (B, 4) rows [n, median, MAD, chi_0] of the last round that ran; and the 8 values [rounds, participants, flagged by
+        SumThreshold, not finite, added by SIR, 0, flagged on input, kept].  numpy arrays take the synchronous host form;
+        torch cuda tensors the asynchronous device form on torch's current stream, which reads nothing back."""
+        be = backend(vis)
+        cube, shape = cube_arrays(be, vis, model_vis, weights, order)
+        K, levels, *scalars = sumthreshold_scalars(levels, nsigma, rho, nlevels, eta, min_count, niter)
+        n, B = shape[0] * shape[1] * shape[2], cube[0]
+        given = out  # (written in place and returned as it is)
+        out, flags, bstats, stats = flag_outputs(be, n, B, None if out is None else result_array(
+            be, out, be.f64, shape, "out", vis).reshape(n), cube[4])
+        self._call(be, "sumthreshold", *cube, K, levels.ctypes.data_as(C.POINTER(C.c_double)), *scalars, out, flags, bstats,
+                   stats)
+        return out.reshape(shape) if given is None else given, flags.reshape(shape), bstats, stats
 
     def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
         """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
@@ -1525,6 +1552,47 @@ def flag_groups(a1, a2, slot=None, by="baseline"):
     cols = {"baseline": (lo, hi), "slot": (slot,), "baseline_slot": (lo, hi, slot)}[by]
     _, group = torch.unique(torch.stack(cols, dim=1), dim=0, sorted=True, return_inverse=True)
     return group.to(torch.int64), int(group.max()) + 1
+
+
+def sumthreshold_tile():
+    """(tile_t, tile_f): the tile of time steps x channels that a work-group of Context.sumthreshold's stage kernel owns
+    (gridhip_sumthreshold_tile)."""
+    tt, tf = C.c_int64(), C.c_int64()
+    rc = _lib.load().gridhip_sumthreshold_tile(C.byref(tt), C.byref(tf))
+    if rc != 0:
+        raise GridHipError(rc, "gridhip_sumthreshold_tile")
+    return tt.value, tf.value
+
+
+def waterfall_layout(a1, a2, time, ntime, chan, nchan, order="btf"):
+    """Where every sample of a flat visibility stream lies in the cube Context.sumthreshold takes, from its antenna pair,
+    its integer time index in [0, ntime) and its integer channel in [0, nchan).  Returns (index, B, pairs): index (int64)
+    is the cell of every sample in the flattened cube - [B][ntime][nchan] for order "btf", [ntime][B][nchan] for "tbf" -
+    so that cube.view(-1)[index] = stream fills the cube and weights.view(-1)[index] is the way back; B is the number of
+    baselines, the unordered antenna pairs numbered in sorted order as in flag_groups; pairs (B, 2) holds their antennas.
+    A cube of weights starts from zeros: the cells nobody fills keep the weight 0 and are flagged on input.  torch
+    tensors (any device) or anything numpy converts; plumbing - torch operations only, no kernel of the library - and B
+    is read back: one synchronisation where the tensors are on a device."""
+    import torch
+    if order not in ("btf", "tbf"):
+        raise ValueError(f'order must be "btf" or "tbf", not {order!r}')
+    a1, a2, time, chan = (torch.as_tensor(x).to(torch.int64).reshape(-1) for x in (a1, a2, time, chan))
+    dev = a1.device
+    a2, time, chan = a2.to(dev), time.to(dev), chan.to(dev)
+    ntime, nchan = int(ntime), int(nchan)
+    if not (a1.shape == a2.shape == time.shape == chan.shape):
+        raise ValueError("a1, a2, time and chan must hold one value per visibility each")
+    if ntime < 1 or nchan < 1:
+        raise ValueError("ntime and nchan must be >= 1")
+    if a1.numel() == 0:
+        return torch.zeros_like(a1), 1, torch.zeros((1, 2), dtype=torch.int64, device=dev)
+    if bool(((time < 0) | (time >= ntime) | (chan < 0) | (chan >= nchan)).any()):
+        raise ValueError("time must lie in [0, ntime) and chan in [0, nchan)")
+    lo, hi = torch.minimum(a1, a2), torch.maximum(a1, a2)
+    pairs, b = torch.unique(torch.stack((lo, hi), dim=1), dim=0, sorted=True, return_inverse=True)
+    B = int(pairs.shape[0])
+    index = ((b * ntime + time) if order == "btf" else (time * B + b)) * nchan + chan
+    return index.to(torch.int64), B, pairs.contiguous()
 
 
 def rotation_to(l0, m0):

@@ -61,6 +61,8 @@ _STOKES = [vp, i64, ci, ci, ci, vp, vp]  # n, basis, which, inverse, vis, stokes
 _DD_SUBTRACT = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp]
 _FLAG_ARGS = [C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]  # nsigma, amax, min_count, niter, then the four outputs
 _FLAG = [vp, i64, i64, vp, vp, vp, vp, *_FLAG_ARGS]
+# ctx, B, T, F, order, vis, model_vis, wt_in, K, levels (a host array in both forms), eta_f, eta_t, min_count, niter, outputs
+_SUMTHRESHOLD = [vp, i64, i64, i64, ci, vp, vp, vp, i64, C.POINTER(C.c_double), C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 # border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats
@@ -219,6 +221,9 @@ SIGNATURES = {
     "gridhip_flag_residuals": (ci, _FLAG),
     "gridhip_flag_residuals_dev": (ci, _FLAG),
     "gridhip_imager_flag_dev": (ci, [vp, vp, vp, i64, vp, vp, *_FLAG_ARGS]),
+    "gridhip_sumthreshold": (ci, _SUMTHRESHOLD),
+    "gridhip_sumthreshold_dev": (ci, _SUMTHRESHOLD),
+    "gridhip_sumthreshold_tile": (ci, [C.POINTER(i64), C.POINTER(i64)]),
     "gridhip_dft_predict": (ci, _DFT_PREDICT),
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),

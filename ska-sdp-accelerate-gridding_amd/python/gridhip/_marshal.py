@@ -570,6 +570,59 @@ def flag_outputs(be, n, G, out, like):
             be.empty((8,), be.f64, like))
 
 
+ST_MAX_STAGES, ST_MAX_ROUNDS = 7, 4  # the most stages (windows up to 64) and rounds of gridhip_sumthreshold
+
+
+def cube_arrays(be, vis, model_vis, weights, order):
+    """B, T, F, order, vis, model_vis, wt_in as gridhip_sumthreshold takes a cube: vis is three-dimensional, [B][T][F] for
+    order "btf" and [T][B][F] for "tbf"; model_vis and weights have its shape or are None.  -> those and vis' shape"""
+    if order not in ("btf", "tbf"):
+        raise ValueError(f'order must be "btf" or "tbf", not {order!r}')
+    if be is HOST:
+        vis = np.asarray(vis)
+    shape = tuple(int(v) for v in vis.shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"vis must be a cube of three non-empty axes, not of shape {shape}")
+    n = shape[0] * shape[1] * shape[2]
+
+    def flat(x, dt, what):
+        if x is None:
+            return None
+        if be is HOST:
+            x = np.asarray(x)
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{what} must have the shape of vis, {shape}, not {tuple(x.shape)}")
+        return stream_array(be, x.reshape(n), dt, n, what)
+    (B, T), F = (shape[:2] if order == "btf" else shape[1::-1]), shape[2]
+    return (B, T, F, 0 if order == "btf" else 1, flat(vis, be.c128, "vis"), flat(model_vis, be.c128, "model_vis"),
+            flat(weights, be.f64, "weights")), shape
+
+
+def sumthreshold_scalars(levels, nsigma, rho, nlevels, eta, min_count, niter):
+    """K, levels, eta_f, eta_t, min_count, niter as gridhip_sumthreshold takes them; levels None: the ladder
+    nsigma / rho^k, k = 0 .. nlevels - 1.  levels is a host array of float64 in both forms and goes by address."""
+    import math
+    if levels is None:
+        nsigma, rho, nlevels = float(nsigma), float(rho), int(nlevels)
+        if not (math.isfinite(nsigma) and nsigma > 0.0 and math.isfinite(rho) and rho > 0.0):
+            raise ValueError("nsigma and rho must be finite and > 0")
+        if not 1 <= nlevels <= ST_MAX_STAGES:
+            raise ValueError(f"nlevels must be in 1 .. {ST_MAX_STAGES}")
+        levels = [nsigma / rho ** k for k in range(nlevels)]
+    levels = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).reshape(-1))
+    if not 1 <= len(levels) <= ST_MAX_STAGES:
+        raise ValueError(f"levels must hold 1 .. {ST_MAX_STAGES} thresholds (windows 1, 2, 4, ...)")
+    if not (np.isfinite(levels).all() and (levels > 0.0).all()):
+        raise ValueError("every level must be finite and > 0")
+    eta_f, eta_t = (float(e) for e in eta)
+    if not (0.0 <= eta_f < 1.0 and 0.0 <= eta_t < 1.0):
+        raise ValueError("eta must be a pair (eta_f, eta_t) in [0, 1)")
+    min_count, niter = int(min_count), int(niter)
+    if min_count < 1 or not 0 <= niter <= ST_MAX_ROUNDS:
+        raise ValueError(f"min_count must be >= 1 and niter in 0 .. {ST_MAX_ROUNDS}")
+    return len(levels), levels, eta_f, eta_t, min_count, niter
+
+
 COMP_DOUBLES = 10  # GRIDHIP_COMP_DOUBLES: { l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0 }
 
 
