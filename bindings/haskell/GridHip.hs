@@ -475,6 +475,27 @@ foreign import ccall unsafe "gridhip_sumthreshold_dev"
 -- int gridhip_sumthreshold_tile(tile_t, tile_f)
 foreign import ccall unsafe "gridhip_sumthreshold_tile"
   c_sumthreshold_tile :: Ptr Int64 -> Ptr Int64 -> IO CInt
+-- int gridhip_rm_tables(ctx, C, J, lam2, weights, phi0, dphi, fwhm, tables)
+foreign import ccall unsafe "gridhip_rm_tables"
+  c_rm_tables :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_rm_tables_dev(ctx, C, J, lam2, weights, phi0, dphi, fwhm, tables)
+foreign import ccall unsafe "gridhip_rm_tables_dev"
+  c_rm_tables_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_rmsynth(ctx, M, C, J, tables, Q, U, cube, stats)
+foreign import ccall unsafe "gridhip_rmsynth"
+  c_rmsynth :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_rmsynth_dev(ctx, M, C, J, tables, Q, U, cube, stats)
+foreign import ccall unsafe "gridhip_rmsynth_dev"
+  c_rmsynth_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_rmclean(ctx, M, J, tables, cube, model, gain, threshold, niter, nsigma, noise, restore, maps, stats)
+foreign import ccall unsafe "gridhip_rmclean"
+  c_rmclean :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_rmclean_dev(ctx, M, J, tables, cube, model, gain, threshold, niter, nsigma, noise, restore, maps, stats)
+foreign import ccall unsafe "gridhip_rmclean_dev"
+  c_rmclean_dev :: Ptr Ctx -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> Ptr CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_rm_tile(out)
+foreign import ccall unsafe "gridhip_rm_tile"
+  c_rm_tile :: Ptr Int64 -> IO CInt
 -- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
 foreign import ccall unsafe "gridhip_dft_predict"
   c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt

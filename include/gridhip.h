@@ -137,6 +137,8 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               alone), 1..64 = that many (values above 64 count as 64)
  *   "mosaic_cull"  gridhip_mosaic: 0 = every tile walks the facets its cull keeps, 1 = every tile walks all valid facets
  *               (the same bits: kept for comparison runs)
+ *   "rm_stage"  gridhip_rmclean: 0 = every wave reads and writes its line of sight directly, 1 = a work-group moves its
+ *               lines of sight through LDS, consecutive threads along m (the same bits: kept for comparison runs)
  *   ("dbg", the ablation / profiling switch of tuning runs, exists only in the tuning build of the library,
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
@@ -1472,6 +1474,113 @@ int gridhip_sumthreshold_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, 
                              double *baseline_stats, double *stats);
 /* the stage kernel's tile, so that a caller (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
 int gridhip_sumthreshold_tile(int64_t *tile_t, int64_t *tile_f);
+
+/* ---- rotation-measure synthesis: the Faraday dispersion function of every line of sight, and RM-CLEAN ----------------------
+ * The reference has no polarisation: the semantics are defined here.  After jonescal -> apply_jones -> stokes -> one imager
+ * per Stokes plane -> jclean a caller holds Q and U images per channel.  RM synthesis (Brentjens & de Bruyn 2005) turns the
+ * complex polarisation P(lambda^2) = Q + iU of a line of sight into the Faraday dispersion function
+ *     F(phi_j) = K sum_c w_c P_c exp(-2 i phi_j (lambda_c^2 - lambda_0^2)),
+ * and RM-CLEAN (Heald et al. 2009) deconvolves it with the RM spread function (RMSF), a Hogbom loop along phi.
+ * All arrays are doubles; complex arrays are interleaved (re, im).  "Rounded" means one IEEE operation, never contracted
+ * into a fused multiply-add, so that numpy reproduces the bits (tests/rm_ref.py restates every rule below).
+ * A LINE OF SIGHT (LOS) is one of M flat cells; M is any count, not only N^2: a caller may hand over an image in row
+ * slabs and so bound the cube's memory (at N = 2400, J = 400 a whole cube is 36 GB).
+ *
+ * gridhip_rm_tables(C, J, lam2[C], weights[C] or NULL (all 1), phi0, dphi, fwhm, tables) makes the table the other two
+ * read, GRIDHIP_RM_TABLE_DOUBLES(C, J) doubles in four parts:
+ *   head[16] = { valid, C, J, phi0, dphi, lam0^2, K, sum w, fwhm, 0 ... }.  sum w and sum w lam2 are plain sums, c ascending
+ *       from 0, every product rounded, by one thread; K = 1 / sum w; lam0^2 = (sum w lam2) / sum w.  valid = 1 when every
+ *       lam2[c] is finite, every w_c finite and >= 0, sum w finite and > 0 and sum w lam2 finite - judged on the device, by
+ *       the prologue kernel; otherwise valid = 0, lam0^2 = K = sum w = 0 and E, R and G are all zeros.
+ *       Below a_c = lam2[c] - lam0^2 and kw_c = K * w_c.
+ *   E[C][J] complex, j fastest: phi_j = phi0 + j * dphi (the product rounded, then added); t = (phi_j * a_c) * INV_PI with
+ *       INV_PI = 0.3183098861837907; r = t - rint(t), exact; (sn, cs) = sincospi(2 r); E = (kw_c * cs, -(kw_c * sn)): the
+ *       phasor kw_c exp(-2 i phi_j a_c) with the weight folded in, the phase reduced as the direct-Fourier prediction does.
+ *   R[2J - 1] complex, the RMSF at the lags lag_k = (k - (J - 1)) * dphi: R_k = sum_c kw_c exp(-2 i lag_k a_c), every term
+ *       formed by the recipe of E with lag_k for phi_j, added with c ascending from (0, 0).  R[J - 1] = (sum kw_c, 0).
+ *   G[2J - 1] real, the restoring function: x = lag_k / fwhm, G_k = exp(-(2.772588722239781 * (x * x))) (4 ln 2).
+ *   One thread per entry; the only sum is the RMSF's, over at most 1024 channels: a create-once step.
+ *   GRIDHIP_EINVAL: C outside 1..1024, J outside 1..512; phi0, dphi or fwhm not finite; dphi or fwhm not > 0; a NULL lam2
+ *   or tables; arrays that overlap.
+ *
+ * gridhip_rmsynth(M, C, J, tables, Q[C][M], U[C][M], cube[J][M] complex, stats[8]): per output element, c ascending from
+ *   acc = (0, 0):   acc.re = acc.re + (E.re * q - E.im * u),   acc.im = acc.im + (E.re * u + E.im * q),
+ *   every product rounded and the bracket rounded.  A LOS with a non-finite Q or U in any channel gets NaN in all 2J values
+ *   and is counted in stats[0].  stats = { bad LOS, 0, 0, 0, 0, 0, 0, invalid }: when the table's head has valid = 0, or its
+ *   C or J differ from the arguments, stats = { 0, ..., 0, 1 } and the cube is left as it is (in the host form too).
+ *   GRIDHIP_EINVAL: M < 1, C or J out of range, a NULL pointer, a cube that is not 16-byte aligned, arrays that overlap.
+ *   GRIDHIP_EUNSUPPORTED: more than 2^31 - 1 tiles of 64 LOS x 64 depths (M above 1.7 x 10^10 at J = 512).
+ *   The kernel is a register-tiled product in plain fp64 vector arithmetic (no matrix instruction: v_mfma_f64 fixes its own
+ *   summation order and fuses): a work-group owns rm_tile()[0] LOS x rm_tile()[1] depths, stages rm_tile()[2] channels of E,
+ *   Q and U at a time in LDS and reads Q and U as the two real cubes they are.  Every output element belongs to one lane,
+ *   which adds its channels in order.
+ *
+ * gridhip_rmclean(M, J, tables, cube[J][M], model[J][M] or NULL, gain, threshold, niter, nsigma, noise (ONE double, or NULL
+ *   when nsigma == 0), restore, maps[7][M], stats[8]).  The stop level is L = max(threshold, nsigma * sigma) as
+ *   gridhip_clean_auto forms it: L = threshold, and when nsigma > 0, sigma = *noise and L = nsigma * sigma where that is
+ *   larger (noise is not read when nsigma == 0); L2 = L * L, rounded once.  nsigma > 0 with a NaN sigma gives stats =
+ *   { 0, 0, 0, 0, 0, 0, 1, 0 } and touches nothing else; a table whose head has valid = 0, a C outside 1..1024 or another J
+ *   gives stats = { 0, ..., 0, 1 } and touches nothing else (the NaN sigma is reported first).
+ *   Per LOS, repeat:
+ *     1. p_j = re * re + im * im, each product rounded;
+ *     2. k = the depth of the largest p, ties to the lowest j, a NaN never selected (no depth left: p_k = -1, k = -1);
+ *     3. p_k <= L2: stop, reason 1 - before anything is subtracted and before the niter test;
+ *     4. niter components taken: stop, reason 0;
+ *     5. f = (gain * re_k, gain * im_k); model_k += f (the model is accumulated into, never zeroed);
+ *     6. for every j, r = R[j - k + J - 1]:  re_j -= (f.re * r.re - f.im * r.im),  im_j -= (f.re * r.im + f.im * r.re),
+ *        every product and every bracket rounded.
+ *   A LOS with any non-finite value in the cube is left untouched (cube and model): reason 3, 0 iterations, j* = -1 and
+ *   NaN in the other maps.  restore = 1 (model must not be NULL), after the loop:
+ *     cube_j = residual_j + sum_k model_k * G[j - k + J - 1], k ascending over the depths whose model value is not exactly
+ *     (0, 0), each product rounded and added in that order, starting from the residual; model is the whole accumulated
+ *     model, what earlier calls left in it included.
+ *   maps[.][m] = { iterations, reason, j*, p*, phi_fit, Re F_j*, Im F_j* }: j* and p* by rule 2 on the cube as the call
+ *   leaves it (all four are NaN and j* = -1 when no depth can be selected); phi_fit = phi_j* = phi0 + j* * dphi, and if
+ *   0 < j* < J - 1 and d = (p_- - p*) + (p_+ - p*) < 0 then off = (0.5 * (p_- - p_+)) / d and phi_fit = phi_j* + off * dphi,
+ *   every step rounded (p_-, p_+: the neighbours of j*).
+ *   stats = { bad LOS, sum of iterations, LOS stopped by niter, LOS stopped at the level, 0, L, NaN sigma, invalid table }:
+ *   counts are integer sums and so free of order.
+ *   GRIDHIP_EINVAL: M < 1, J out of range, gain or threshold not finite, niter < 0, nsigma not finite or < 0, nsigma > 0
+ *   with a NULL noise, restore not 0 or 1, restore = 1 with a NULL model, a NULL tables, cube, maps or stats, a cube or
+ *   model that is not 16-byte aligned, arrays that overlap.  GRIDHIP_EUNSUPPORTED: M above 2^40.
+ *   The kernel: one wave per LOS, four consecutive LOS per work-group; depth j in register j / 64 of lane j % 64 (at most 8
+ *   complex residuals and 8 model values per lane, all in registers); R and G staged once per work-group in LDS (24 KB);
+ *   the arg-max a wave reduction over (p, j) pairs; in the subtraction consecutive lanes read consecutive entries of R; the
+ *   restore broadcasts model_k from its lane and skips zeros for the whole wave at once.  The loop's length differs
+ *   between waves, never within one.  No floating-point atomic; one integer atomic per wave and counter for the stats.
+ *
+ * FORMS.  The host forms are synchronous and stage through the context's pool (gridhip_rmclean reads the table's C from
+ * its head in host memory to know its size).  The _dev forms take device pointers for EVERY array - lam2, weights and noise
+ * too, so nothing needs a copy node - enqueue kernels only on the context's stream (2, 3 and 3 launches), allocate nothing
+ * after the first call (64 bytes of counters from the pool), read nothing back, never synchronise and can be captured into a
+ * graph.  Both forms run the same kernels and give the same bits, as do two runs, and as does the numpy restatement
+ * given the library's table (the table itself agrees within the rounding of sincospi and exp).
+ * NOT HERE: per-LOS channel weights or blanked channels (a LOS with a NaN is dropped whole); a fused synthesis and clean
+ * that never writes the cube; per-LOS thresholds; multi-scale RM-CLEAN; QU-fitting; derotated angle maps (the caller takes
+ * 0.5 atan2(Im, Re) - phi_fit lam0^2); matrix instructions; several devices. */
+#define GRIDHIP_RM_MAX_CHANNELS 1024
+#define GRIDHIP_RM_MAX_DEPTHS 512
+#define GRIDHIP_RM_HEAD 16
+#define GRIDHIP_RM_MAPS 7
+#define GRIDHIP_RM_STATS 8
+#define GRIDHIP_RM_TABLE_DOUBLES(C, J) (16 + 2 * (C) * (J) + 3 * (2 * (J) - 1))
+int gridhip_rm_tables(gridhip_ctx *ctx, int64_t C, int64_t J, const double *lam2, const double *weights, double phi0,
+                      double dphi, double fwhm, double *tables);
+int gridhip_rm_tables_dev(gridhip_ctx *ctx, int64_t C, int64_t J, const double *lam2, const double *weights, double phi0,
+                          double dphi, double fwhm, double *tables);
+int gridhip_rmsynth(gridhip_ctx *ctx, int64_t M, int64_t C, int64_t J, const double *tables, const double *Q,
+                    const double *U, double *cube, double *stats);
+int gridhip_rmsynth_dev(gridhip_ctx *ctx, int64_t M, int64_t C, int64_t J, const double *tables, const double *Q,
+                        const double *U, double *cube, double *stats);
+int gridhip_rmclean(gridhip_ctx *ctx, int64_t M, int64_t J, const double *tables, double *cube, double *model, double gain,
+                    double threshold, int64_t niter, double nsigma, const double *noise, int restore, double *maps,
+                    double *stats);
+int gridhip_rmclean_dev(gridhip_ctx *ctx, int64_t M, int64_t J, const double *tables, double *cube, double *model,
+                        double gain, double threshold, int64_t niter, double nsigma, const double *noise, int restore,
+                        double *maps, double *stats);
+/* out[3] = { LOS per work-group, depths per work-group, channels of a chunk } of the synthesis kernel, so that a caller
+ * (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
+int gridhip_rm_tile(int64_t *out);
 
 /* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
  * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image

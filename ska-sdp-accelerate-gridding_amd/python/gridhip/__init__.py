@@ -37,10 +37,11 @@ from ._marshal import weighting as _weighting
 from ._marshal import mosaic_args
 from ._marshal import wstack_options
 from ._marshal import JOINT_MAX_PLANES, joint_search, psf_planes
+from ._marshal import RM_MAPS, rm_clean_scalars, rm_cube, rm_images, rm_table_args, rm_table_doubles, rm_table_of
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
-           "waterfall_layout"]
+           "waterfall_layout", "rm_tile", "faraday_grid"]
 
 
 class Context(Handle):
@@ -767,6 +768,62 @@ class Context(Handle):
         self._call(be, "sumthreshold", *cube, K, levels.ctypes.data_as(C.POINTER(C.c_double)), *scalars, out, flags, bstats,
                    stats)
         return out.reshape(shape) if given is None else given, flags.reshape(shape), bstats, stats
+
+    def rm_tables(self, lam2, phi, weights=None, fwhm=None):
+        """The table RM synthesis and RM-CLEAN read (gridhip_rm_tables[_dev]; include/gridhip.h, "rotation-measure
+        synthesis"): lam2 - the C <= 1024 squared wavelengths of the channels - weights (C values, finite and >= 0; None:
+        ones) and the Faraday depths phi = (phi0, dphi, J), phi_j = phi0 + j dphi, J <= 512 (gridhip.faraday_grid proposes
+        them).  fwhm: the width of the restoring Gaussian; None: 2 sqrt(3) / (max lam2 - min lam2).  Returns one float64
+        array of 16 + 2 C J + 3 (2 J - 1) values: the head [valid, C, J, phi0, dphi, lam0^2, K, sum w, fwhm, 0 ...], the
+        phasors E[C][J] with the weights folded in, the RMSF R[2J - 1] and the restoring function G[2J - 1].  lam2 and the
+        weights are judged on the device: a value that is not finite, a negative weight or no weight above 0 gives
+        valid = 0, which rmsynth and rmclean report in stats[7].  A numpy lam2 takes the synchronous host form; a torch
+        cuda tensor the asynchronous one on torch's stream (fwhm=None reads lam2's range back, once)."""
+        be = backend(lam2)
+        C_, J, lam2, weights, phi0, dphi, fwhm = rm_table_args(be, lam2, phi, weights, fwhm)
+        tables = be.empty(rm_table_doubles(C_, J), be.f64, lam2)
+        self._call(be, "rm_tables", C_, J, lam2, weights, phi0, dphi, fwhm, tables)
+        return tables
+
+    def rmsynth(self, q, u, tables, out=None):
+        """RM synthesis (gridhip_rmsynth[_dev]): q and u, real [C, ...] arrays of one shape - the Q and U images of the C
+        channels, [C, N, N], or any block of lines of sight such as a slab of rows - give the Faraday dispersion function
+        F(phi_j) = sum_c E[c][j] (q_c + i u_c) of every line of sight as a complex128 cube [J, ...], J the table's.
+        Returns (cube, stats): stats = [bad, 0, 0, 0, 0, 0, 0, invalid] - a line of sight with a non-finite q or u in any
+        channel is NaN at every depth and counted in `bad`; invalid = 1: the table is not valid or not of q's C, and the
+        cube was not written.  out: the cube to write.  The same bits on every run and as numpy's unfused products summed
+        over the channels in order.  numpy in gives numpy out; torch cuda tensors take the device form on torch's stream."""
+        be = backend(q)
+        M, C_, q, u, rest = rm_images(be, q, u)
+        tables, C_, J = rm_table_of(be, tables, C_=C_)
+        cube = result_array(be, out, be.c128, (J,) + rest, "out", q)
+        stats = be.empty(8, be.f64, q)
+        self._call(be, "rmsynth", M, C_, J, tables, q, u, cube, stats)
+        return cube, stats
+
+    def rmclean(self, cube, tables, gain=0.1, threshold=0.0, niter=100, nsigma=0.0, noise=None, restore=False, model=None):
+        """RM-CLEAN of every line of sight of `cube` ([J, ...] complex128 as rmsynth returns it; gridhip_rmclean[_dev]): a
+        Hogbom loop along the Faraday depth with the table's RMSF - take the depth of the largest |F|^2 (ties to the lowest
+        depth), stop when |F| <= L = max(threshold, nsigma * noise) or after niter components, else add gain * F there to
+        the model and subtract it times the shifted RMSF.  noise: sigma as a number or one float64 element (a number with
+        cuda tensors is uploaded by this call and cannot be captured).  `cube` is UPDATED IN PLACE and returned: the
+        residual, or with restore=True the residual plus the whole model convolved with the table's Gaussian.  `model`
+        ([J, ...] complex128, zeros when None) is accumulated into.  Returns (model, cube, maps, stats): maps [7, ...] =
+        [iterations, reason (0 niter, 1 level, 3 non-finite: left untouched), j*, |F|^2 there, phi fitted by a parabola
+        through the three powers around j*, Re F, Im F at j*] of the cube as it is returned; stats = [bad, iterations,
+        stopped by niter, stopped at the level, 0, L, NaN noise, invalid table] - either of the last two set: nothing else
+        was touched.  Every line of sight is cleaned by one wave, on its own; the same bits on every run."""
+        be = backend(cube)
+        M, J, rest = rm_cube(be, cube)
+        tables, _, J = rm_table_of(be, tables, J=J)
+        scalars = rm_clean_scalars(be, gain, threshold, niter, nsigma, noise, restore, cube)
+        if model is None:
+            model = be.zeros((J,) + rest, be.c128, cube)
+        elif not (be is backend(model) and be.ok(model, be.c128) and tuple(model.shape) == tuple(cube.shape)):
+            raise ValueError(f"model must be {be.form} of the cube's shape (it is accumulated into)")
+        maps, stats = be.empty((RM_MAPS,) + rest, be.f64, cube), be.empty(8, be.f64, cube)
+        self._call(be, "rmclean", M, J, tables, cube, model, *scalars, maps, stats)
+        return model, cube, maps, stats
 
     def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
         """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
@@ -1593,6 +1650,42 @@ def waterfall_layout(a1, a2, time, ntime, chan, nchan, order="btf"):
     B = int(pairs.shape[0])
     index = ((b * ntime + time) if order == "btf" else (time * B + b)) * nchan + chan
     return index.to(torch.int64), B, pairs.contiguous()
+
+
+def rm_tile():
+    """(LOS per work-group, depths per work-group, channels of a chunk) of Context.rmsynth's kernel (gridhip_rm_tile)."""
+    out = (C.c_int64 * 3)()
+    rc = _lib.load().gridhip_rm_tile(out)
+    if rc != 0:
+        raise GridHipError(rc, "gridhip_rm_tile")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def faraday_grid(lam2, oversample=4, phi_max=None):
+    """The Faraday depths a set of channels supports (Brentjens & de Bruyn 2005, eqs. 61-63), from their squared
+    wavelengths lam2 (at least two different ones): returns (phi0, dphi, J, fwhm, max_scale, phi_limit) with
+    fwhm = 2 sqrt(3) / (max lam2 - min lam2), the width of the RMSF; dphi = fwhm / oversample; phi_limit =
+    sqrt(3) / max |delta lam2| over neighbours of the sorted channels, the depth at which the widest channel gap loses
+    half its sensitivity; max_scale = pi / min lam2, the widest structure in depth that is seen; J = 2 floor(phi_max /
+    dphi) + 1 depths (phi_max None: phi_limit), at most 511; phi0 = -(J - 1) / 2 * dphi, so that depth 0 is on the grid.
+    Pure host code: Context.rm_tables takes phi = (phi0, dphi, J) and fwhm."""
+    import math
+    import numpy as np
+    lam2 = np.sort(np.asarray(lam2, dtype=np.float64).reshape(-1))
+    if lam2.size < 2 or not np.isfinite(lam2).all() or not lam2[0] > 0.0 or not lam2[-1] > lam2[0]:
+        raise ValueError("lam2 must hold at least two different finite squared wavelengths > 0")
+    oversample = float(oversample)
+    if not (math.isfinite(oversample) and oversample > 0.0):
+        raise ValueError("oversample must be finite and > 0")
+    fwhm = 2.0 * math.sqrt(3.0) / float(lam2[-1] - lam2[0])
+    dphi = fwhm / oversample
+    phi_limit = math.sqrt(3.0) / float(np.max(np.abs(np.diff(lam2))))
+    max_scale = math.pi / float(lam2[0])
+    phi_max = phi_limit if phi_max is None else float(phi_max)
+    if not (math.isfinite(phi_max) and phi_max >= 0.0):
+        raise ValueError("phi_max must be finite and >= 0")
+    J = min(2 * int(math.floor(phi_max / dphi)) + 1, 511)
+    return -(J - 1) / 2 * dphi, dphi, J, fwhm, max_scale, phi_limit
 
 
 def rotation_to(l0, m0):

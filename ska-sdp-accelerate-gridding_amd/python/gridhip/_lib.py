@@ -63,6 +63,11 @@ _FLAG_ARGS = [C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]  # nsigma, amax,
 _FLAG = [vp, i64, i64, vp, vp, vp, vp, *_FLAG_ARGS]
 # ctx, B, T, F, order, vis, model_vis, wt_in, K, levels (a host array in both forms), eta_f, eta_t, min_count, niter, outputs
 _SUMTHRESHOLD = [vp, i64, i64, i64, ci, vp, vp, vp, i64, C.POINTER(C.c_double), C.c_double, C.c_double, i64, i64, vp, vp, vp, vp]
+# every array is of the form's own kind (lam2, weights and noise too): C, J, lam2, weights, phi0, dphi, fwhm, tables
+_RM_TABLES = [vp, i64, i64, vp, vp, C.c_double, C.c_double, C.c_double, vp]
+_RMSYNTH = [vp, i64, i64, i64, vp, vp, vp, vp, vp]  # M, C, J, tables, Q, U, cube, stats
+# M, J, tables, cube, model, gain, threshold, niter, nsigma, noise, restore, maps, stats
+_RMCLEAN = [vp, i64, i64, vp, vp, vp, C.c_double, C.c_double, i64, C.c_double, vp, ci, vp, vp]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 # border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats
@@ -224,6 +229,13 @@ SIGNATURES = {
     "gridhip_sumthreshold": (ci, _SUMTHRESHOLD),
     "gridhip_sumthreshold_dev": (ci, _SUMTHRESHOLD),
     "gridhip_sumthreshold_tile": (ci, [C.POINTER(i64), C.POINTER(i64)]),
+    "gridhip_rm_tables": (ci, _RM_TABLES),
+    "gridhip_rm_tables_dev": (ci, _RM_TABLES),
+    "gridhip_rmsynth": (ci, _RMSYNTH),
+    "gridhip_rmsynth_dev": (ci, _RMSYNTH),
+    "gridhip_rmclean": (ci, _RMCLEAN),
+    "gridhip_rmclean_dev": (ci, _RMCLEAN),
+    "gridhip_rm_tile": (ci, [C.POINTER(i64)]),
     "gridhip_dft_predict": (ci, _DFT_PREDICT),
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),

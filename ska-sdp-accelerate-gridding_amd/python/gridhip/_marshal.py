@@ -623,6 +623,115 @@ def sumthreshold_scalars(levels, nsigma, rho, nlevels, eta, min_count, niter):
     return len(levels), levels, eta_f, eta_t, min_count, niter
 
 
+RM_MAX_CHANNELS, RM_MAX_DEPTHS, RM_HEAD, RM_MAPS = 1024, 512, 16, 7  # GRIDHIP_RM_* of include/gridhip.h
+
+
+def rm_table_doubles(C, J):
+    """GRIDHIP_RM_TABLE_DOUBLES(C, J): head, E[C][J] complex, R[2J - 1] complex, G[2J - 1]"""
+    return RM_HEAD + 2 * C * J + 3 * (2 * J - 1)
+
+
+def rm_table_args(be, lam2, phi, weights, fwhm):
+    """C, J, lam2, weights, phi0, dphi, fwhm as gridhip_rm_tables takes them: lam2 and weights are one-dimensional arrays
+    of `be`'s own kind (weights None: all ones), phi = (phi0, dphi, J).  fwhm None: 2 sqrt(3) / (max lam2 - min lam2),
+    which for a cuda lam2 is read back (one synchronisation: the table is made once)."""
+    import math
+    if lam2 is None or (be is not backend(lam2) and be is not HOST):
+        raise ValueError(f"lam2 must be a {be.array}")
+    lam2 = stream_array(be, lam2, be.f64, -1, "lam2")
+    C_ = int(lam2.shape[0])
+    weights = stream_array(be, weights, be.f64, C_, "weights")
+    try:
+        phi0, dphi, J = phi
+        phi0, dphi, J = float(phi0), float(dphi), int(J)
+    except (TypeError, ValueError):
+        raise ValueError("phi must be (phi0, dphi, J)") from None
+    if not 1 <= C_ <= RM_MAX_CHANNELS:
+        raise ValueError(f"lam2 must hold 1 .. {RM_MAX_CHANNELS} channels, not {C_}")
+    if not 1 <= J <= RM_MAX_DEPTHS:
+        raise ValueError(f"J must be in 1 .. {RM_MAX_DEPTHS}, not {J}")
+    if not (math.isfinite(phi0) and math.isfinite(dphi) and dphi > 0.0):
+        raise ValueError("phi0 and dphi must be finite and dphi > 0")
+    if fwhm is None:
+        span = float(lam2.max() - lam2.min())
+        if not (math.isfinite(span) and span > 0.0):
+            raise ValueError("fwhm=None needs two different finite lam2 (pass fwhm)")
+        fwhm = 2.0 * math.sqrt(3.0) / span
+    fwhm = float(fwhm)
+    if not (math.isfinite(fwhm) and fwhm > 0.0):
+        raise ValueError("fwhm must be finite and > 0")
+    return C_, J, lam2, weights, phi0, dphi, fwhm
+
+
+def rm_table_of(be, tables, C_=None, J=None):
+    """tables, C, J: a table of gridhip_rm_tables as the other two entry points take it - one-dimensional float64 of `be`'s
+    own kind, in the ABI's form - and its shape, from its length and the one of C and J that the caller's arrays fix."""
+    if tables is None or be is not backend(tables) or not be.ok(tables, be.f64) or len(tables.shape) != 1:
+        raise ValueError(f"tables must be a one-dimensional float64 {be.array} (Context.rm_tables)")
+    n = int(tables.shape[0]) - (RM_HEAD - 3)
+    if C_ is not None:
+        J = n // (2 * C_ + 6)
+    else:
+        C_ = (n // J - 6) // 2
+    if not (1 <= C_ <= RM_MAX_CHANNELS and 1 <= J <= RM_MAX_DEPTHS and rm_table_doubles(C_, J) == int(tables.shape[0])):
+        raise ValueError(f"tables of {int(tables.shape[0])} values do not belong to these arrays")
+    return tables, C_, J
+
+
+def rm_images(be, q, u):
+    """M, C, q, u, the shape of a LOS block: q and u are [C, ...] real arrays of one shape, converted where they must be"""
+    if q is None or u is None or be is not backend(u) or not hasattr(q, "shape") or not hasattr(u, "shape"):
+        raise ValueError(f"q and u must be {be.array}s of one kind")
+    shape = tuple(int(v) for v in q.shape)
+    if len(shape) < 2 or min(shape) < 1 or tuple(int(v) for v in u.shape) != shape:
+        raise ValueError(f"q and u must be of one shape [C, ...] with at least one line of sight, not {shape} and {tuple(u.shape)}")
+    for x in (q, u):
+        if (x.dtype.kind == "c") if be is HOST else x.dtype.is_complex:
+            raise ValueError("q and u must be real")
+    if not 1 <= shape[0] <= RM_MAX_CHANNELS:
+        raise ValueError(f"q and u must hold 1 .. {RM_MAX_CHANNELS} channels, not {shape[0]}")
+    M = 1
+    for v in shape[1:]:
+        M *= v
+    return M, shape[0], be.cv(q, be.f64), be.cv(u, be.f64), shape[1:]
+
+
+def rm_cube(be, cube):
+    """M, J, the shape of a LOS block: the [J, ...] complex128 cube RM-CLEAN updates in place, in the ABI's form"""
+    shape = tuple(int(v) for v in getattr(cube, "shape", ()))
+    if not (hasattr(cube, "dtype") and be.ok(cube, be.c128)) or len(shape) < 2 or min(shape) < 1:
+        raise ValueError(f"cube must be {be.form} of shape [J, ...] (it is updated in place)")
+    if not 1 <= shape[0] <= RM_MAX_DEPTHS:
+        raise ValueError(f"cube must hold 1 .. {RM_MAX_DEPTHS} depths, not {shape[0]}")
+    M = 1
+    for v in shape[1:]:
+        M *= v
+    return M, shape[0], shape[1:]
+
+
+def rm_clean_scalars(be, gain, threshold, niter, nsigma, noise, restore, like):
+    """gain, threshold, niter, nsigma, noise, restore as gridhip_rmclean takes them.  noise: sigma as a number, or one
+    float64 element of `be`'s own kind; a NUMBER with device arrays is uploaded by this call and cannot be captured."""
+    import math
+    gain, threshold, niter, nsigma = float(gain), float(threshold), int(niter), float(nsigma)
+    if not (math.isfinite(gain) and math.isfinite(threshold)):
+        raise ValueError("gain and threshold must be finite")
+    if niter < 0:
+        raise ValueError("niter must be >= 0")
+    if not (math.isfinite(nsigma) and nsigma >= 0.0):
+        raise ValueError("nsigma must be finite and >= 0")
+    if noise is None:
+        if nsigma > 0.0:
+            raise ValueError("nsigma > 0 needs noise (sigma: a number or one float64 element)")
+    elif isinstance(noise, (int, float)):
+        noise = np.array([noise], dtype=np.float64)
+        if be is not HOST:
+            noise = be.torch.from_numpy(noise).to(getattr(like, "device", like))
+    elif be is not backend(noise) or not be.ok(noise, be.f64) or int(np.prod(tuple(noise.shape))) != 1:
+        raise ValueError(f"noise must be a number or a {be.array} of one float64 element")
+    return gain, threshold, niter, nsigma, noise, int(bool(restore))
+
+
 COMP_DOUBLES = 10  # GRIDHIP_COMP_DOUBLES: { l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0 }
 
 
