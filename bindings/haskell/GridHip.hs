@@ -496,6 +496,15 @@ foreign import ccall unsafe "gridhip_rmclean_dev"
 -- int gridhip_rm_tile(out)
 foreign import ccall unsafe "gridhip_rm_tile"
   c_rm_tile :: Ptr Int64 -> IO CInt
+-- int gridhip_contsub(ctx, R, C, layout, ncomp, degree, mode, x, chan_mask, data, wt, nsigma, niter, out, coeffs, rowinfo, codes, stats)
+foreign import ccall unsafe "gridhip_contsub"
+  c_contsub :: Ptr Ctx -> Int64 -> Int64 -> CInt -> CInt -> CInt -> CInt -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> IO CInt
+-- int gridhip_contsub_dev(ctx, R, C, layout, ncomp, degree, mode, x, chan_mask, data, wt, nsigma, niter, out, coeffs, rowinfo, codes, stats)
+foreign import ccall unsafe "gridhip_contsub_dev"
+  c_contsub_dev :: Ptr Ctx -> Int64 -> Int64 -> CInt -> CInt -> CInt -> CInt -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> Ptr CDouble -> CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Word8 -> Ptr CDouble -> IO CInt
+-- int gridhip_contsub_tile(out)
+foreign import ccall unsafe "gridhip_contsub_tile"
+  c_contsub_tile :: Ptr Int64 -> IO CInt
 -- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
 foreign import ccall unsafe "gridhip_dft_predict"
   c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt

@@ -1582,6 +1582,92 @@ int gridhip_rmclean_dev(gridhip_ctx *ctx, int64_t M, int64_t J, const double *ta
  * (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
 int gridhip_rm_tile(int64_t *out);
 
+/* ---- continuum subtraction: a smooth function of frequency fitted to every spectrum, subtracted, and kept ------------------
+ * The reference has no such step: the semantics are defined here.  Between continuum and line work lies one operation:
+ * fit a polynomial along frequency to the line-free channels of every spectrum, subtract it, keep the fit as the continuum
+ * (CASA's uvcontsub / imcontsub, Miriad's uvlin).  In model mode it is also the smooth background fit that
+ * gridhip_sumthreshold leaves to its caller: the result is a model_vis.
+ * "Rounded" means one IEEE operation, never contracted into a fused multiply-add, so that numpy reproduces the bits
+ * (tests/contsub_ref.py restates every rule below).
+ * DATA.  R rows (spectra) of C channels, n = R C samples; ncomp 1: real values (images), 2: interleaved complex values
+ *     (visibilities).  layout 0: [R][C], the channel innermost - both orders of a gridhip_sumthreshold cube, R = B T;
+ *     layout 1: [C][R], the channel outermost - the [C, N, N] cube of gridhip_rmsynth, R = N N.  Nothing is transposed or
+ *     copied for either.  wt: NULL for all ones, or one double per sample in the data's layout (not interleaved: one per
+ *     complex sample).  x: C doubles, the channel coordinate, for instance (nu - mid) / half.  chan_mask: NULL for all
+ *     channels, or C bytes; a byte that is not 0 marks a line-free channel that may enter the fit.
+ * BASIS.  Chebyshev polynomials by the rounded recurrence T_0 = 1, T_1 = x, T_{p+1} = (2 * x) * T_p - T_{p-1}, every
+ *     product and difference rounded once, for p up to 2 * degree.  The EFFECTIVE channel mask is chan_mask[c] != 0 &&
+ *     isfinite(x[c]); a channel whose x is not finite has NaN in `out`, in every row and in both modes: the continuum has
+ *     no value there.
+ * CLASSES.  The FIRST class that applies sets the code of a sample in `codes` (n bytes in the data's layout, may be NULL):
+ *     1       FLAGGED ON INPUT  the weight is not finite or not > 0
+ *     3       NOT FINITE        a component of the value is NaN or Inf
+ *     2       MASKED            the channel is outside the effective channel mask
+ *     16 + i  CLIPPED in round i
+ *     0       USED in the final fit
+ *     The PARTICIPANTS are the samples of class 0 at that moment.
+ * FIT of a row.  The channels are walked in ascending order, one accumulator chain per sum, all from +0.0 - no tree, no
+ *     floating-point atomic.  For a participant with weight w (1.0 without weights) and value v:
+ *         mu_p = mu_p + w * T_p[c]                                          p = 0 .. 2D
+ *         g = w * T_k[c];  b_k.re = b_k.re + g * v.re;  b_k.im likewise     k = 0 .. D
+ *     every product and sum rounded once.  The normal matrix follows from the moments by the product identity
+ *     T_j T_k = (T_{j+k} + T_{|j-k|}) / 2:   A_jk = 0.5 * (mu_{j+k} + mu_{|j-k|}),   2D + 1 accumulators instead of
+ *     (D + 1)(D + 2) / 2.  The solve is LDL^T without pivoting, k = 0 .. D:
+ *         t = A_kk;  t = t - (L_kp * L_kp) * d_p  for p = 0 .. k - 1 in this order, each operation rounded.
+ *     The pivot is GOOD when A_kk > 0 and t > 1e-12 * A_kk; then d_k = t and for i > k
+ *         s = A_ik;  s = s - (L_ip * L_kp) * d_p  for p = 0 .. k - 1;  L_ik = s / d_k.
+ *     At the first pivot that is not good the row's degree becomes k - 1 and the factorisation stops: the leading block of
+ *     an LDL^T is the factorisation of the lower-degree problem, so the fit falls back instead of failing.  Degree -1: no
+ *     usable sample; the continuum of the row is +0.0.  Forward: z_k = b_k;  z_k = z_k - L_kp * z_p, p ascending.  Back,
+ *     over the row's degree only, k descending: a_k = z_k / d_k;  a_k = a_k - L_ik * a_i for i = k + 1 .. degree
+ *     ascending; a_k = +0.0 above the degree.  The continuum at channel c:  acc = a_0;  acc = acc + a_k * T_k[c], k = 1 .. D
+ *     ascending, for both components.
+ * CLIP ROUNDS i = 0 .. niter - 1, 0 <= niter <= 4; none when nsigma == 0.  After a fit, over the participants, r = v -
+ *     continuum (one rounded subtraction per component), q_c = w * (r.re * r.re + r.im * r.im) (real data: w * (r * r)),
+ *     Q their sum in channel order from +0.0, qbar = Q / (double)n_used.  A participant with q_c > (nsigma * nsigma) * qbar
+ *     gets the code 16 + i (the square is rounded once, on the host; then one rounded product per row), and the row is
+ *     fitted again from the participants that remain.  A row in which a round clips nothing, or whose degree is -1, is
+ *     finished.  Every row is independent: there is no global stop test.
+ * OUTPUTS.  out has the data's shape and may be `data` itself.  mode 0: v - continuum, one rounded subtraction per component;
+ *     mode 1: the continuum itself - at every channel of every row, masked, flagged and clipped ones included.  coeffs (may
+ *     be NULL): [R][D+1][ncomp] for layout 0, [D+1][R][ncomp] for layout 1 - coefficient images, plane 0 the continuum
+ *     image at x = 0 (for degree 2 and 3: a_0 - a_2).  rowinfo (may be NULL): [R][4] for layout 0, [4][R] for layout 1: { degree used,
+ *     samples in the final fit, samples clipped, final qbar }; the final qbar is that of the closing pass, which forms
+ *     the residuals anyway, and NaN for a row without a sample.  stats (8 doubles, may be NULL): { rows, rows at full
+ *     degree, rows at reduced degree, rows without a fit, samples used, samples clipped, samples not finite, samples
+ *     flagged on input }, from integer atomics.
+ * All arguments are checked before anything is touched, GRIDHIP_EINVAL: a NULL context, data, x or out; R or C < 1; layout
+ * or mode not 0 or 1; ncomp not 1 or 2; degree outside 0..3; nsigma negative or not finite; niter outside 0..4; any output
+ * overlapping an input or another output, other than out == data.  GRIDHIP_EUNSUPPORTED: C above 4096, R above 2^31 - 1.
+ * FORMS.  gridhip_contsub is synchronous and stages host arrays through the context's pool.  In the _dev form every array,
+ * x and chan_mask too, lives on the device; it enqueues three launches on the context's stream - a prologue that writes
+ * the table of T_p[c] and the effective mask to scratch, the main kernel, the stats - no memset node, no copy node; it
+ * allocates nothing after the first call of a shape (64 B per channel and 64 B of counters from the context's pool; n
+ * bytes more only when there are clip rounds and codes is NULL), reads nothing back, never synchronises and can be
+ * captured into a graph: a linear chain.  In the main kernel a lane owns a row through all passes - moments, solve, per
+ * round the residual sum, then clip and moments, then the closing subtraction - so out == data holds by construction: a
+ * row's data is written only in its closing pass.  Layout 1 is read straight from global memory, consecutive lanes at
+ * consecutive addresses; for layout 0 a work-group owns `rows` rows and streams chunks of `chunk` channels through LDS,
+ * loaded along the channel and walked per lane at a padded pitch (gridhip_contsub_tile reports the two).
+ * DETERMINISM.  Every floating-point result belongs to one lane and one fixed order: the same bits for the host and _dev
+ * forms, for two runs, for a replayed graph, for the two layouts of the same cube, and for the numpy restatement.
+ * NOT HERE: median or other robust estimators; fits along time; splines; per-row channel masks other than through wt (a
+ * zero weight is the per-row mask); an imager form; several devices; a uv-plane fit for sources far from the phase
+ * centre, where the continuum is not smooth in frequency per baseline (gridhip_phase_shift to the source first). */
+#define GRIDHIP_CONTSUB_MAX_CHANNELS 4096
+#define GRIDHIP_CONTSUB_MAX_DEGREE 3
+#define GRIDHIP_CONTSUB_ROWINFO 4
+#define GRIDHIP_CONTSUB_STATS 8
+int gridhip_contsub(gridhip_ctx *ctx, int64_t R, int64_t C, int layout, int ncomp, int degree, int mode, const double *x,
+                    const uint8_t *chan_mask, const double *data, const double *wt, double nsigma, int64_t niter, double *out,
+                    double *coeffs, double *rowinfo, uint8_t *codes, double *stats);
+int gridhip_contsub_dev(gridhip_ctx *ctx, int64_t R, int64_t C, int layout, int ncomp, int degree, int mode, const double *x,
+                        const uint8_t *chan_mask, const double *data, const double *wt, double nsigma, int64_t niter,
+                        double *out, double *coeffs, double *rowinfo, uint8_t *codes, double *stats);
+/* out[2] = { rows per work-group, channels per staged chunk } of the layout-0 kernel, so that a caller (a test) can stand
+ * either side of its edges; GRIDHIP_EINVAL for a NULL */
+int gridhip_contsub_tile(int64_t *out);
+
 /* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
  * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image
  * and a degridder; this one evaluates the measurement equation itself,

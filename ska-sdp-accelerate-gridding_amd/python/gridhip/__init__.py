@@ -38,10 +38,11 @@ from ._marshal import mosaic_args
 from ._marshal import wstack_options
 from ._marshal import JOINT_MAX_PLANES, joint_search, psf_planes
 from ._marshal import RM_MAPS, rm_clean_scalars, rm_cube, rm_images, rm_table_args, rm_table_doubles, rm_table_of
+from ._marshal import contsub_args
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
-           "waterfall_layout", "rm_tile", "faraday_grid"]
+           "waterfall_layout", "rm_tile", "faraday_grid", "contsub_tile", "channel_coordinate"]
 
 
 class Context(Handle):
@@ -824,6 +825,30 @@ class Context(Handle):
         maps, stats = be.empty((RM_MAPS,) + rest, be.f64, cube), be.empty(8, be.f64, cube)
         self._call(be, "rmclean", M, J, tables, cube, model, *scalars, maps, stats)
         return model, cube, maps, stats
+
+    def contsub(self, data, x, mask=None, weights=None, degree=1, axis=-1, mode="subtract", nsigma=0.0, niter=0, out=None,
+                coeffs=True, info=True, codes=False):
+        """Continuum subtraction (gridhip_contsub[_dev]; include/gridhip.h, "continuum subtraction"): per spectrum a
+        Chebyshev polynomial of `degree` <= 3 in the channel coordinate x (C values; gridhip.channel_coordinate), fitted by
+        weighted least squares to the samples that `mask` (C values, non-zero: a line-free channel; None: all) and
+        `weights` (data's shape; a weight that is not finite and > 0 drops its sample: the per-row mask) let in, with up to
+        niter <= 4 rounds that drop the samples whose weighted squared residual exceeds nsigma^2 times the row's mean and
+        fit again.  data: [..., C] for axis=-1 - a sumthreshold cube in either order - or [C, ...] for axis=0 - an image
+        cube; complex128 or float64, in the ABI's form: nothing is converted, transposed or copied.  mode "subtract": out =
+        data - continuum; "model": out = the continuum, at every channel of every spectrum.  out: the array to write,
+        which may be data itself; a new one when None.  Returns (out, coeffs, info, codes, stats): coeffs [..., D+1] or
+        [D+1, ...] of data's dtype (for axis=0 coefficient images; a row that fell back has +0.0 above its degree); info
+        [..., 4] or [4, ...] = [degree used (-1: no usable sample, continuum 0), samples in the final fit, samples clipped,
+        final mean weighted squared residual]; codes (uint8, data's shape: 0 used, 1 flagged on input, 3 not finite, 2
+        masked, 16 + i clipped in round i); stats = [rows, at full degree, at reduced degree, without a fit, samples used,
+        clipped, not finite, flagged on input].  coeffs, info, codes False: that output is not made (None comes back).  A
+        channel whose x is not finite is NaN in out.  The same bits on every run, for both axes of the same cube and as
+        tests/contsub_ref.py.  numpy in gives numpy out; torch cuda tensors take the device form on torch's stream: three
+        launches, nothing read back."""
+        be = backend(data)
+        args = contsub_args(be, data, x, mask, weights, degree, axis, mode, nsigma, niter, out, coeffs, info, codes)
+        self._call(be, "contsub", *args)
+        return args[12:]
 
     def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
         """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
@@ -1659,6 +1684,29 @@ def rm_tile():
     if rc != 0:
         raise GridHipError(rc, "gridhip_rm_tile")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def contsub_tile():
+    """(rows per work-group, channels per staged chunk) of Context.contsub's kernel for axis=-1 (gridhip_contsub_tile)."""
+    out = (C.c_int64 * 2)()
+    rc = _lib.load().gridhip_contsub_tile(out)
+    if rc != 0:
+        raise GridHipError(rc, "gridhip_contsub_tile")
+    return int(out[0]), int(out[1])
+
+
+def channel_coordinate(freq):
+    """The channel coordinate Context.contsub fits in: x = (f - mid) / half with mid = 0.5 * (fmin + fmax) and half =
+    0.5 * (fmax - fmin), so that the band maps onto [-1, 1], where the Chebyshev basis is well conditioned; all zeros for one
+    channel or equal frequencies.  Pure host code: a float64 ndarray."""
+    import numpy as np
+    f = np.asarray(freq, dtype=np.float64).reshape(-1)
+    if f.size == 0:
+        raise ValueError("freq must hold at least one channel")
+    mid, half = 0.5 * (f.min() + f.max()), 0.5 * (f.max() - f.min())
+    if not half > 0.0:
+        return np.zeros_like(f)
+    return (f - mid) / half
 
 
 def faraday_grid(lam2, oversample=4, phi_max=None):

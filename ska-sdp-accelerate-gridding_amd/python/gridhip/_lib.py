@@ -68,6 +68,8 @@ _RM_TABLES = [vp, i64, i64, vp, vp, C.c_double, C.c_double, C.c_double, vp]
 _RMSYNTH = [vp, i64, i64, i64, vp, vp, vp, vp, vp]  # M, C, J, tables, Q, U, cube, stats
 # M, J, tables, cube, model, gain, threshold, niter, nsigma, noise, restore, maps, stats
 _RMCLEAN = [vp, i64, i64, vp, vp, vp, C.c_double, C.c_double, i64, C.c_double, vp, ci, vp, vp]
+# ctx, R, C, layout, ncomp, degree, mode, x, chan_mask, data, wt, nsigma, niter, out, coeffs, rowinfo, codes, stats
+_CONTSUB = [vp, i64, i64, ci, ci, ci, ci, vp, vp, vp, vp, C.c_double, i64, vp, vp, vp, vp, vp]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 # border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats
@@ -236,6 +238,9 @@ SIGNATURES = {
     "gridhip_rmclean": (ci, _RMCLEAN),
     "gridhip_rmclean_dev": (ci, _RMCLEAN),
     "gridhip_rm_tile": (ci, [C.POINTER(i64)]),
+    "gridhip_contsub": (ci, _CONTSUB),
+    "gridhip_contsub_dev": (ci, _CONTSUB),
+    "gridhip_contsub_tile": (ci, [C.POINTER(i64)]),
     "gridhip_dft_predict": (ci, _DFT_PREDICT),
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),

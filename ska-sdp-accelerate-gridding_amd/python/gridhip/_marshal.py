@@ -732,6 +732,62 @@ def rm_clean_scalars(be, gain, threshold, niter, nsigma, noise, restore, like):
     return gain, threshold, niter, nsigma, noise, int(bool(restore))
 
 
+CONTSUB_MAX_CHANNELS, CONTSUB_MAX_DEGREE, CONTSUB_ROWINFO, CONTSUB_MAX_ROUNDS = 4096, 3, 4, 4  # GRIDHIP_CONTSUB_*
+
+
+def contsub_args(be, data, x, mask, weights, degree, axis, mode, nsigma, niter, out, coeffs, info, codes):
+    """R, C, layout, ncomp, degree, mode, x, chan_mask, data, wt, nsigma, niter, out, coeffs, rowinfo, codes, stats as
+    gridhip_contsub takes them.  data: [..., C] for axis -1 (layout 0) or [C, ...] for axis 0 (layout 1), complex128 (ncomp
+    2) or float64 (ncomp 1), in the ABI's form as it is - a cube is never converted or copied; weights (float64) and out
+    (data's dtype; it may be data itself) have its shape and form.  x: C real values; mask: C values of dtype bool or uint8,
+    or None.  coeffs, info, codes: whether the call makes that output (coeffs [..., D+1] or [D+1, ...] of data's dtype, info
+    [..., 4] or [4, ...], codes uint8 of data's shape)."""
+    import math
+    if axis not in (-1, 0):
+        raise ValueError(f"axis must be -1 ([..., C]) or 0 ([C, ...]), not {axis!r}")
+    if mode not in ("subtract", "model"):
+        raise ValueError(f'mode must be "subtract" or "model", not {mode!r}')
+    shape = tuple(int(v) for v in getattr(data, "shape", ()))
+    if not hasattr(data, "dtype") or be is not backend(data) or len(shape) < 1 or min(shape) < 1:
+        raise ValueError(f"data must be a non-empty {be.array} of dtype complex128 or float64")
+    dt = be.c128 if be.ok(data, be.c128) else be.f64
+    if not be.ok(data, dt):
+        raise ValueError(f"data must be a {be.array} of dtype complex128 or float64, not converted: {data.dtype}")
+    C_, rest = (shape[-1], shape[:-1]) if axis == -1 else (shape[0], shape[1:])
+    R = 1
+    for v in rest:
+        R *= v
+    degree, niter, nsigma = int(degree), int(niter), float(nsigma)
+    if not 1 <= C_ <= CONTSUB_MAX_CHANNELS:
+        raise ValueError(f"data must hold 1 .. {CONTSUB_MAX_CHANNELS} channels along axis {axis}, not {C_}")
+    if not 0 <= degree <= CONTSUB_MAX_DEGREE or not 0 <= niter <= CONTSUB_MAX_ROUNDS:
+        raise ValueError(f"degree must be in 0 .. {CONTSUB_MAX_DEGREE} and niter in 0 .. {CONTSUB_MAX_ROUNDS}")
+    if not (math.isfinite(nsigma) and nsigma >= 0.0):
+        raise ValueError("nsigma must be finite and >= 0")
+    if x is None:
+        raise ValueError("x must hold one coordinate per channel (gridhip.channel_coordinate)")
+    if be is HOST and (is_torch(x) or is_torch(mask) or is_torch(weights) or is_torch(out)):
+        raise ValueError("numpy data takes numpy arguments throughout")
+    x = stream_array(be, x, be.f64, C_, "x")
+    if be is HOST and mask is not None:
+        mask = np.asarray(mask)
+    mask = mask_of(be, mask, (C_,))
+    if weights is not None and not (be is backend(weights) and be.ok(weights, be.f64) and tuple(weights.shape) == shape):
+        raise ValueError(f"weights must be a float64 {be.array} of data's shape {shape}")
+    if out is not None and not (be is backend(out) and be.ok(out, dt) and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a {be.array} of data's shape and dtype (it is written in place; it may be data)")
+    if out is None:
+        out = be.empty(shape, dt, data)
+    u8 = np.uint8 if be is HOST else be.torch.uint8
+    lead = (lambda k: rest + (k,)) if axis == -1 else (lambda k: (k,) + rest)
+    coeffs = be.empty(lead(degree + 1), dt, data) if coeffs else None
+    info = be.empty(lead(CONTSUB_ROWINFO), be.f64, data) if info else None
+    codes = be.empty(shape, u8, data) if codes else None
+    stats = be.empty(8, be.f64, data)
+    return (R, C_, 0 if axis == -1 else 1, 2 if dt is be.c128 else 1, degree, 0 if mode == "subtract" else 1, x, mask, data,
+            weights, nsigma, niter, out, coeffs, info, codes, stats)
+
+
 COMP_DOUBLES = 10  # GRIDHIP_COMP_DOUBLES: { l, m, f0, f1, f2, f3, bmaj, bmin, bpa, 0 }
 
 
