@@ -505,6 +505,39 @@ foreign import ccall unsafe "gridhip_contsub_dev"
 -- int gridhip_contsub_tile(out)
 foreign import ccall unsafe "gridhip_contsub_tile"
   c_contsub_tile :: Ptr Int64 -> IO CInt
+-- int gridhip_fringe_tables(ctx, F, T, tint, freq, time, tau0, dtau, Nd, r0, drate, Nr, tables)
+foreign import ccall unsafe "gridhip_fringe_tables"
+  c_fringe_tables :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_fringe_tables_dev(ctx, F, T, tint, freq, time, tau0, dtau, Nd, r0, drate, Nr, tables)
+foreign import ccall unsafe "gridhip_fringe_tables_dev"
+  c_fringe_tables_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_fringe_search(ctx, B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, k0, k1, peaks, stats)
+foreign import ccall unsafe "gridhip_fringe_search"
+  c_fringe_search :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fringe_search_dev(ctx, B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, k0, k1, peaks, stats)
+foreign import ccall unsafe "gridhip_fringe_search_dev"
+  c_fringe_search_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fringe_solve(ctx, B, I, A, a1, a2, peaks, min_count, min_coh2, refant, niter, tol, sol, info, stats)
+foreign import ccall unsafe "gridhip_fringe_solve"
+  c_fringe_solve :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fringe_solve_dev(ctx, B, I, A, a1, a2, peaks, min_count, min_coh2, refant, niter, tol, sol, info, stats)
+foreign import ccall unsafe "gridhip_fringe_solve_dev"
+  c_fringe_solve_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fringefit(ctx, B, T, F, A, I, Nd, Nr, tables, vis, model_vis, wt, a1, a2, rounds, wj, wk, min_count, min_coh2, refant, niter, tol, warm, sol, peaks, info, stats)
+foreign import ccall unsafe "gridhip_fringefit"
+  c_fringefit :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fringefit_dev(ctx, B, T, F, A, I, Nd, Nr, tables, vis, model_vis, wt, a1, a2, rounds, wj, wk, min_count, min_coh2, refant, niter, tol, warm, sol, peaks, info, stats)
+foreign import ccall unsafe "gridhip_fringefit_dev"
+  c_fringefit_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_fringe(ctx, B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_fringe"
+  c_apply_fringe :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_fringe_dev(ctx, B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_fringe_dev"
+  c_apply_fringe_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_fringe_tile(out)
+foreign import ccall unsafe "gridhip_fringe_tile"
+  c_fringe_tile :: Ptr Int64 -> IO CInt
 -- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
 foreign import ccall unsafe "gridhip_dft_predict"
   c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt

@@ -1668,6 +1668,184 @@ int gridhip_contsub_dev(gridhip_ctx *ctx, int64_t R, int64_t C, int layout, int 
  * either side of its edges; GRIDHIP_EINVAL for a NULL */
 int gridhip_contsub_tile(int64_t *out);
 
+/* ---- delay and rate calibration: a fringe search per baseline, an antenna-based fit, and the apply step -------------------
+ * The reference has no calibration: the semantics are defined here.  gridhip_gaincal, gridhip_ddcal and gridhip_jonescal
+ * solve one complex number per antenna and solution interval; the term before them in every reduction is a per-antenna
+ * delay and phase rate (fringe fitting: Schwab & Cotton 1983), whose phase slope across the band or the interval wipes out
+ * the averages that gridhip_average, the gain solvers and the gridders form.
+ * All arrays are doubles; complex values are interleaved (re, im).  "Rounded" means one IEEE operation, never contracted
+ * into a fused multiply-add, as in the RM section (tests/fringe_ref.py restates every rule below).
+ * DATA.  The cube is [B][T][F], the order "btf" of gridhip_sumthreshold (gridhip.waterfall_layout builds it and returns
+ *     the pairs): vis and the optional model_vis complex, the optional wt one double per sample.  a1[B], a2[B]: the int64
+ *     antenna pair (p, q) of a baseline, each in [0, A).  freq[F] in Hz and time[T] in seconds; neither needs to be uniform.
+ *     tint: the time steps of a solution interval, 0 meaning T; I = ceil(T / tint) intervals, the last may be short.
+ * MODEL.  V[b,t,f] ~ M[b,t,f] exp(i (psi_p - psi_q)),  psi_a(t,f) = arg g[i,a] + 2 pi tau[i,a] (nu_f - nu0) + 2 pi r[i,a]
+ *     (t - tref_i), with nu0 = freq[0] + 0.5 * (freq[F-1] - freq[0]) and tref_i formed the same way from the first and the
+ *     last time of interval i.  A solution `sol` is [I][A][4] = { tau, r, Re g, Im g } with |g| = 1: phasors, not angles -
+ *     no atan2 enters it.
+ * PHASOR RECIPE.  ph(a, b) = exp(2 pi i a b): the turns x = a * b (rounded), r = x - rint(x) (exact), (sn, cs) =
+ *     sincospi(2 r), ph = (cs, sn) - the reduction of the RM table's E.  Complex products: x conj(c) = (x.re c.re + x.im c.im,
+ *     x.im c.re - x.re c.im) and x c = (x.re c.re - x.im c.im, x.re c.im + x.im c.re), four rounded products and two rounded
+ *     sums each; acc + e x as gridhip_rmsynth adds it: acc.re = acc.re + (e.re x.re - e.im x.im), acc.im = acc.im + (e.re x.im
+ *     + e.im x.re), every product and the bracket rounded.
+ *
+ * gridhip_fringe_tables(F, T, tint, freq, time, tau0, dtau, Nd, r0, drate, Nr, tables) makes the table the others read,
+ * GRIDHIP_FRINGE_TABLE_DOUBLES(F, T, Nd, Nr) doubles:
+ *   head[16] = { valid, F, T, tint (after the 0 -> T rule), I, Nd, Nr, tau0, dtau, r0, drate, nu0, 0 ... }
+ *   Ef[F][Nd] complex, j fastest: conj ph(tau_j, a_f), tau_j = tau0 + j * dtau (the product rounded, then added), a_f =
+ *       freq[f] - nu0: exp(-2 pi i tau_j (nu_f - nu0)) = (cs, -sn)
+ *   Et[T][Nr] complex, k fastest: conj ph(r_k, dt_t), r_k = r0 + k * drate, dt_t = time[t] - tref_i(t)
+ *   tref[T]: the I reference times, then zeros;  a[F] = a_f;  dt[T] = dt_t (what the derotation and the apply step read)
+ *   valid is judged on the device (one work-group scans freq and time): every freq and time, tau0, dtau, r0, drate and nu0 finite, dtau > 0 and drate > 0;
+ *   otherwise valid = 0 and everything behind the head is zeros.  One thread per entry.
+ *   GRIDHIP_EINVAL: F outside 1..1024, Nd outside 1..4096, Nr outside 1..1024, T < 1, tint < 0 or above 256 after the
+ *   0 -> T rule, a NULL pointer, arrays that overlap.  GRIDHIP_EUNSUPPORTED: T above 2^20.
+ *
+ * gridhip_fringe_search(B, T, F, A, I, tables, vis, model_vis or NULL, wt or NULL, a1, a2, sol or NULL, j0, j1, k0, k1,
+ * peaks[B][I][12], stats[8]) - the hot path.  I is the table's number of intervals, by which the caller has sized peaks and
+ *   sol: the call cannot read it from a table on the device, and refuses a table whose head says otherwise.  Per sample, s = wt (1 without), X = (s re V, s im V) conj(M) by
+ *   gridhip_gaincal's rounded formula; without a model X = (s re V, s im V).
+ *     FLAGGED   a sample whose s is not > 0: selected out, it contributes exactly nothing even when it is NaN
+ *     BAD       a (baseline, interval) with an unflagged sample whose X' is not finite
+ *   With sol the sample is derotated, X' = ((X conj(d_b)) conj(Df[f])) conj(Dt[t]) in this order, with d_b = g_p conj(g_q)
+ *   (the x conj(c) rule), Df[f] = ph(tau_p - tau_q, a_f) and Dt[t] = ph(r_p - r_q, dt_t), made once per (baseline,
+ *   interval); without sol X' = X, no product.  Then for j in [j0, j1) and k in [k0, k1):
+ *     1. Y[t][j] = sum_f Ef[f][j] X'[t][f], f ascending from (0, 0) by the acc + e x rule (flagged samples add (0, 0));
+ *     2. S[j][k] = sum_t Et[t][k] Y[t][j], t ascending over the interval, the same rule;
+ *     3. P = re * re + im * im.
+ *   The peak (j*, k*) is the largest P, ties to the lowest j, then the lowest k; a NaN is never selected.  Refinement is
+ *   gridhip_rmclean's parabola rule on each axis separately: tau_b = tau_j*, and if j0 < j* < j1 - 1 and d = (P_- - P*) +
+ *   (P_+ - P*) < 0 then tau_b = tau_j* + ((0.5 * (P_- - P_+)) / d) * dtau (P_-, P_+ at j* -+ 1 and k*); r_b likewise along k.
+ *   Energy: e_t = sum_f (re * re + im * im) of the unflagged X', f ascending; N = sum_t e_t, t ascending; n_used the number
+ *   of unflagged samples.  coh2 = P* / ((double)n_used * N), 0 when N is not > 0;  z = (Re S* / sqrt(P*), Im S* / sqrt(P*)),
+ *   (1, 0) when P* is not > 0.
+ *   peaks row = { j*, k*, P*, tau_b, r_b, Re z, Im z, coh2, n_used, N, code, 0 };  code, the first that applies:
+ *     3  p == q or an antenna out of range     1  empty: no unflagged sample     2  BAD     0  ok
+ *   A row whose code is not 0 is { -1, -1, 0, 0, 0, 1, 0, 0, n_used, 0, code, 0 }.  An all-zero baseline is ok: the tie
+ *   goes to (j0, k0), coh2 = 0.
+ *   stats = { flagged samples, BAD, empty, refused (code 3), ok rows, 0, 0, invalid }: when the table's head has valid = 0,
+ *   its F, T or I differ from the arguments, or the cells do not lie in its grid, stats = { 0, ..., 0, 1 } and peaks is left as
+ *   it is (in the host form too).
+ *   GRIDHIP_EINVAL: B, T < 1, F outside 1..1024, A < 2, I outside 1..T, cells not 0 <= j0 < j1 <= 4096, 0 <= k0 < k1 <= 1024, a NULL
+ *   tables, vis, a1, a2, peaks or stats, a vis or model_vis that is not 16-byte aligned, an output overlapping an input or
+ *   the other output.  GRIDHIP_EUNSUPPORTED: B above 2^24, T above 2^20, A above 1024, B T above 2^31 - 1.
+ *   The kernels.  A work-group owns a baseline and fringe_tile()[0] delays and walks the intervals: X' and Ef stream through
+ *   LDS in chunks of fringe_tile()[1] channels, Y[t][j] is accumulated in registers, one output element per lane-slot,
+ *   channels in order; Y is parked in LDS and S formed against Et, fringe_tile()[2] rates per lane-pass, t in order, with a
+ *   running (P, j, k) maximum per lane, reduced by the tie rule into one candidate per tile.  A second kernel, one wave per
+ *   (baseline, interval), takes the best tile in ascending order, recomputes the five values the parabolas need by the same
+ *   two ordered sums - so the bits do not depend on the tile borders - and forms the energy and the row.  No matrix
+ *   instruction (gridhip_rmsynth's argument); 53 KB of LDS per work-group; integer atomics only, for the stats.
+ *
+ * gridhip_fringe_solve(B, I, A, a1, a2, peaks, min_count, min_coh2, refant, niter, tol, sol, info[I][A], stats[8]).
+ *   The baseline weight w_b = coh2 when code == 0, n_used >= min_count, coh2 >= min_coh2, coh2 > 0, the row's tau_b, r_b, z
+ *   and coh2 are finite and the pair is in range with p != q; else 0 and the baseline is not USED.  Per interval three
+ *   antenna-based problems are solved together from x_tau = x_r = 0, h = (1, 0); sweep it = 0, 1, ..., for every antenna a
+ *   that a used baseline touches, b ascending over the used baselines that touch it, all sums from +0.0:
+ *       wz = (w_b * Re z_b, w_b * Im z_b);  den = den + w_b
+ *       p_b = a:  nt = nt + w_b * (tau_b + x_tau[q]);  nr likewise;  num = num + wz h[q]        (the acc + e x rule)
+ *       q_b = a:  nt = nt + w_b * (x_tau[p] - tau_b);  nr likewise;  num = num + conj(wz) h[p]  (num.re + (wz.re h.re +
+ *                 wz.im h.im), num.im + (wz.re h.im - wz.im h.re))
+ *       x_tau' = nt / den;  x_r' = nr / den;  m = num.re * num.re + num.im * num.im;  h' = (num.re / sqrt(m), num.im /
+ *       sqrt(m)) when m > 0 and finite, else h
+ *       on odd it: x' <- 0.5 * (x' + x) for both, and h' <- the sum 0.5 * (h' + h) per component, divided by its sqrt(re * re +
+ *       im * im) when that is > 0 and finite, else h
+ *   (Jacobi: every antenna reads the values of the sweep before.)  An antenna no used baseline touches keeps its values and
+ *   is UNSOLVED.  Stop after the sweep in which c_tau <= tol * s_tau, c_r <= tol * s_r and c_h <= tol, with c = the largest
+ *   |x' - x| and s = the largest |x'| over the antennas of the interval, c_h the largest sqrt(dre * dre + dim * dim).
+ *   Then, if refant >= 0 and it is solved: x_tau and x_r of every solved antenna minus refant's, h <- h conj(h_refant), and
+ *   h_refant = (1, 0); an interval whose refant is unsolved stays unreferenced and is counted.  Then sol is accumulated
+ *   into, for the solved antennas only: tau += x_tau, r += x_r, g <- g h (the x c rule) divided by its sqrt(re * re + im * im)
+ *   when that is > 0 and finite.  info[i][a] = the used baselines that touch a; 0: unsolved.
+ *   stats = { sweeps (the most of any interval), used baselines, unsolved antennas, unreferenced intervals, rms_tau, rms_r,
+ *   0, 0 }: rms = sqrt(sum w y^2 / sum w) over the used baselines with y = tau_b or r_b (0 without any) - a thread adds
+ *   ceil(B / 256) consecutive baselines from +0.0, w * (y * y), then the 256 runs are added in order, then the intervals.
+ *   No floating-point atomic: the same bits on every run.  One work-group per interval; a thread owns an antenna.  The
+ *   baselines pass through LDS twice, 256 at a time - once to count, once to fill - which leaves every antenna a list of
+ *   its used baselines in ascending order (96 B of pooled scratch per baseline and interval); a sweep reads only those.
+ *   Measured on a numpy prototype: 50 sweeps reach 1e-16 on a full array of 8 or 32 antennas; a pure
+ *   chain of 32 antennas does not converge in 200 - Jacobi needs a well-connected array.
+ *   GRIDHIP_EINVAL: B or I < 1, A < 2, min_count or min_coh2 negative or not finite, refant >= A (negative: none), niter
+ *   outside 0..100000, tol negative or not finite, a NULL pointer, arrays that overlap.  GRIDHIP_EUNSUPPORTED: A above 1024,
+ *   B above 2^24, I above 2^20.
+ *
+ * gridhip_fringefit(B, T, F, A, I, Nd, Nr, tables, vis, model_vis, wt, a1, a2, rounds, wj, wk, min_count, min_coh2, refant,
+ * niter, tol, warm, sol, peaks, info, stats) is the driver; I, Nd and Nr are the table's (it cannot read them from the
+ *   device).  warm = 0: sol starts as { 0, 0, 1, 0 }.  Round 0 searches the whole grid, derotating by sol when warm; the
+ *   rounds 1 .. rounds - 1 (rounds in 1..4) derotate by the current sol and search only the cells within (wj, wk) of the grid's
+ *   zero, jz = rint(-tau0 / dtau) and kz = rint(-r0 / drate) clamped into the grid: [jz - wj, jz + wj] x [kz - wk, kz + wk],
+ *   cut at the grid's edges.  Every search is followed by gridhip_fringe_solve, which accumulates into sol.  It returns sol,
+ *   the last round's peaks (residual delays and rates against sol BEFORE that round's solve) and info, and stats = { sweeps
+ *   of the last solve, flagged samples, BAD, empty, unsolved antennas, rms_tau / dtau, rms_r / drate (the last round's, in
+ *   cells), invalid }; invalid = 1 (a head that does not fit F, T, I, Nd, Nr): nothing else is meaningful, and no solve ran.
+ *   A fixed number of launches (6 per round, 1 or 2 more), nothing read back, the stop test on the device: the _dev form
+ *   can be captured.  GRIDHIP_EINVAL / EUNSUPPORTED: those of the search and the solve; I outside 1..T, Nd, Nr out of range,
+ *   rounds outside 1..4, wj outside 0..4096, wk outside 0..1024, warm not 0 or 1.
+ *
+ * gridhip_apply_fringe(B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in or NULL, vis_out, wt_out or NULL) reads only
+ *   the head, a[F] and dt[T] of a table (any Nd, Nr).  D = d_b, Df[f], Dt[t] as in the search.  inverse 1 (correct data):
+ *   vis_out = ((vis_in conj(d_b)) conj(Df[f])) conj(Dt[t]); inverse 0 (corrupt a model): vis_out = ((vis_in d_b) Df[f])
+ *   Dt[t].  Weights are copied (ones without wt_in).  A sample that touches an antenna whose sol row is not finite, or an
+ *   antenna out of range, keeps its value and gets the weight +0.0 (gridhip_apply_gains' rule).  In place (vis_out ==
+ *   vis_in, wt_out == wt_in) is allowed; any other overlap is refused.  A head that does not fit F, T and I: nothing is
+ *   written.  GRIDHIP_EINVAL: the cube's limits as above, I outside 1..T, a NULL tables, sol, a1, a2, vis_in or vis_out, inverse not 0 or 1,
+ *   a cube that is not 16-byte aligned, overlap.
+ *
+ * FORMS.  The host forms are synchronous, stage through the context's pool and read the table's head in host memory to know
+ * the table's size.  The _dev forms take device pointers for EVERY array, enqueue kernels only on the context's stream, read
+ * nothing back, never synchronise and can be captured.  Every call that sizes an array by I takes I from its caller and the
+ * kernels compare it with the table's head.  Both forms run the same kernels and give the same bits, as do two runs and the
+ * numpy restatement given the library's table.
+ * NOT HERE: the order "tbf"; dispersive (TEC) delays; rates that scale with frequency; multi-band delays; a global
+ * least-squares polish over all samples; an imager form; several devices. */
+#define GRIDHIP_FRINGE_MAX_CHANNELS 1024
+#define GRIDHIP_FRINGE_MAX_DELAYS 4096
+#define GRIDHIP_FRINGE_MAX_TINT 256
+#define GRIDHIP_FRINGE_MAX_RATES 1024
+#define GRIDHIP_FRINGE_MAX_ANTENNAS 1024
+#define GRIDHIP_FRINGE_MAX_ITER 100000
+#define GRIDHIP_FRINGE_MAX_ROUNDS 4
+#define GRIDHIP_FRINGE_HEAD 16
+#define GRIDHIP_FRINGE_PEAK 12
+#define GRIDHIP_FRINGE_STATS 8
+#define GRIDHIP_FRINGE_TABLE_DOUBLES(F, T, Nd, Nr) (16 + 2 * (F) * (Nd) + 2 * (T) * (Nr) + 2 * (T) + (F))
+int gridhip_fringe_tables(gridhip_ctx *ctx, int64_t F, int64_t T, int64_t tint, const double *freq, const double *time,
+                          double tau0, double dtau, int64_t Nd, double r0, double drate, int64_t Nr, double *tables);
+int gridhip_fringe_tables_dev(gridhip_ctx *ctx, int64_t F, int64_t T, int64_t tint, const double *freq, const double *time,
+                              double tau0, double dtau, int64_t Nd, double r0, double drate, int64_t Nr, double *tables);
+int gridhip_fringe_search(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                          const double *vis, const double *model_vis, const double *wt, const int64_t *a1, const int64_t *a2,
+                          const double *sol, int64_t j0, int64_t j1, int64_t k0, int64_t k1, double *peaks, double *stats);
+int gridhip_fringe_search_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                              const double *vis, const double *model_vis, const double *wt, const int64_t *a1,
+                              const int64_t *a2, const double *sol, int64_t j0, int64_t j1, int64_t k0, int64_t k1,
+                              double *peaks, double *stats);
+int gridhip_fringe_solve(gridhip_ctx *ctx, int64_t B, int64_t I, int64_t A, const int64_t *a1, const int64_t *a2,
+                         const double *peaks, double min_count, double min_coh2, int64_t refant, int64_t niter, double tol,
+                         double *sol, double *info, double *stats);
+int gridhip_fringe_solve_dev(gridhip_ctx *ctx, int64_t B, int64_t I, int64_t A, const int64_t *a1, const int64_t *a2,
+                             const double *peaks, double min_count, double min_coh2, int64_t refant, int64_t niter,
+                             double tol, double *sol, double *info, double *stats);
+int gridhip_fringefit(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, int64_t Nd, int64_t Nr,
+                      const double *tables, const double *vis, const double *model_vis, const double *wt, const int64_t *a1,
+                      const int64_t *a2, int64_t rounds, int64_t wj, int64_t wk, double min_count, double min_coh2,
+                      int64_t refant, int64_t niter, double tol, int warm, double *sol, double *peaks, double *info,
+                      double *stats);
+int gridhip_fringefit_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, int64_t Nd, int64_t Nr,
+                          const double *tables, const double *vis, const double *model_vis, const double *wt,
+                          const int64_t *a1, const int64_t *a2, int64_t rounds, int64_t wj, int64_t wk, double min_count,
+                          double min_coh2, int64_t refant, int64_t niter, double tol, int warm, double *sol, double *peaks,
+                          double *info, double *stats);
+int gridhip_apply_fringe(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                         const double *sol, const int64_t *a1, const int64_t *a2, int inverse, const double *vis_in,
+                         const double *wt_in, double *vis_out, double *wt_out);
+int gridhip_apply_fringe_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                             const double *sol, const int64_t *a1, const int64_t *a2, int inverse, const double *vis_in,
+                             const double *wt_in, double *vis_out, double *wt_out);
+/* out[3] = { delays per work-group, channels per staged chunk, rates per lane-pass } of the search kernel, so that a caller
+ * (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
+int gridhip_fringe_tile(int64_t *out);
+
 /* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
  * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image
  * and a degridder; this one evaluates the measurement equation itself,

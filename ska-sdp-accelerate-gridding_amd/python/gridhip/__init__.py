@@ -39,10 +39,13 @@ from ._marshal import wstack_options
 from ._marshal import JOINT_MAX_PLANES, joint_search, psf_planes
 from ._marshal import RM_MAPS, rm_clean_scalars, rm_cube, rm_images, rm_table_args, rm_table_doubles, rm_table_of
 from ._marshal import contsub_args
+from ._marshal import FRINGE_MAX_DELAYS, FRINGE_MAX_RATES, FRINGE_PEAK, fringe_cube, fringe_intervals, fringe_sol
+from ._marshal import fringe_solve_scalars, fringe_table_args, fringe_table_doubles, fringe_table_of
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
-           "waterfall_layout", "rm_tile", "faraday_grid", "contsub_tile", "channel_coordinate"]
+           "waterfall_layout", "rm_tile", "faraday_grid", "contsub_tile", "channel_coordinate",
+           "fringe_tile", "fringe_grid"]
 
 
 class Context(Handle):
@@ -849,6 +852,125 @@ class Context(Handle):
         args = contsub_args(be, data, x, mask, weights, degree, axis, mode, nsigma, niter, out, coeffs, info, codes)
         self._call(be, "contsub", *args)
         return args[12:]
+
+    def fringe_tables(self, freq, time, tint, delays, rates):
+        """The table the fringe search and the apply step read (gridhip_fringe_tables[_dev]; include/gridhip.h, "delay and
+        rate calibration"): freq (F <= 1024 channels, Hz) and time (T steps, seconds), neither necessarily uniform; tint
+        time steps per solution interval (0: all T; at most 256); delays = (tau0, dtau, Nd <= 4096) and rates = (r0, drate,
+        Nr <= 1024), the cells tau_j = tau0 + j dtau and r_k = r0 + k drate (gridhip.fringe_grid proposes them).  Returns one
+        float64 array: the head [valid, F, T, tint, I, Nd, Nr, tau0, dtau, r0, drate, nu0, 0 ...], the phasors Ef[F][Nd] and
+        Et[T][Nr], the reference times, nu_f - nu0 and t - tref.  freq and time are judged on the device: a value that is
+        not finite, or a step that is not > 0, gives valid = 0, which every reader reports.  numpy in gives numpy out; torch
+        cuda tensors take the device form on torch's stream."""
+        be = backend(freq)
+        args = fringe_table_args(be, freq, time, tint, delays, rates)
+        tables = be.empty(fringe_table_doubles(args[0], args[1], args[7], args[10]), be.f64, args[3])
+        self._call(be, "fringe_tables", *args, tables)
+        return tables
+
+    def fringe_search(self, vis, tables, a1, a2, nant, tint, delays, rates, model_vis=None, weights=None, sol=None, cells=None,
+                      peaks=None):
+        """The fringe search (gridhip_fringe_search[_dev]): per baseline of the [B, T, F] cube `vis` and solution interval,
+        the delay and rate cell at which sum_t Et[t][k] sum_f Ef[f][j] X'[t][f] has the largest power, X' = weights * vis *
+        conj(model_vis), derotated by `sol` ([I, nant, 4] = tau, r, Re g, Im g) where one is given.  a1, a2: the B antenna
+        pairs; tint, delays = (tau0, dtau, Nd) and rates = (r0, drate, Nr): what the table was made with; cells = (j0, j1, k0,
+        k1): the half-open ranges of delay and rate cells to search (None: the whole grid).  Returns (peaks [B, I, 12], stats): a row is [j*, k*,
+        P*, tau_b, r_b, Re z, Im z, coh2, n_used, N, code, 0] with the peak refined by a parabola per axis where it is
+        interior to the ranges, z the unit phasor of the peak, coh2 = P* / (n_used N) in [0, 1] and code 0 ok, 1 no
+        unflagged sample, 2 a non-finite unflagged sample, 3 p == q or an antenna out of range; stats = [flagged samples,
+        bad, empty, refused, ok rows, 0, 0, invalid] - invalid = 1: the table does not belong to this cube, was made with another
+        tint, or the cells do not lie in its grid, and peaks was not written.  A sample whose weight is not > 0 contributes exactly nothing.  The same
+        bits on every run and as tests/fringe_ref.py given the table."""
+        be = backend(vis)
+        B, T, F, A, vis, model_vis, wt, a1, a2 = fringe_cube(be, vis, model_vis, weights, a1, a2, nant)
+        tables, I = fringe_table_of(be, tables, F, T, tint)
+        Nd, Nr = int(delays[2]), int(rates[2])
+        if int(tables.shape[0]) != fringe_table_doubles(F, T, Nd, Nr):
+            raise ValueError(f"tables of {int(tables.shape[0])} values do not belong to this cube and these axes")
+        try:
+            j0, j1, k0, k1 = (0, Nd, 0, Nr) if cells is None else (int(v) for v in cells)
+        except (TypeError, ValueError):
+            raise ValueError("cells must be (j0, j1, k0, k1)") from None
+        if not (0 <= j0 < j1 <= Nd and 0 <= k0 < k1 <= Nr):
+            raise ValueError("cells must be half-open ranges 0 <= j0 < j1 and 0 <= k0 < k1 inside the grid")
+        sol = fringe_sol(be, sol, I, A, vis)
+        peaks = result_array(be, peaks, be.f64, (B, I, FRINGE_PEAK), "peaks", vis)
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "fringe_search", B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, k0, k1, peaks, stats)
+        return peaks, stats
+
+    def fringe_solve(self, peaks, a1, a2, nant, sol=None, min_count=0, min_coh2=0.0, refant=0, niter=50, tol=0.0):
+        """The antenna-based fit of the baseline values of a fringe search (gridhip_fringe_solve[_dev]): per interval,
+        Jacobi sweeps on the weighted least squares of tau_p - tau_q = tau_b and r_p - r_q = r_b and a phase-only StEFCal
+        on the peak phasors, all weighted by coh2 of the baselines with code 0, n_used >= min_count and coh2 >= min_coh2;
+        then referenced to `refant` (None: not) and ACCUMULATED into `sol` ([I, nant, 4]; None: a new one of tau = r = 0,
+        g = 1), which is returned: (sol, info [I, nant] - the used baselines per antenna, 0: unsolved and untouched -
+        stats = [sweeps, used baselines, unsolved antennas, unreferenced intervals, rms tau_b, rms r_b, 0, 0]).  The sweeps
+        stop when the largest change of each of the three is at or below tol (relative to the largest value for delays
+        and rates).  No floating-point atomic: the same bits on every run and as tests/fringe_ref.py."""
+        be = backend(peaks)
+        shape = tuple(int(v) for v in getattr(peaks, "shape", ()))
+        if not (hasattr(peaks, "dtype") and be.ok(peaks, be.f64)) or len(shape) != 3 or shape[2] != FRINGE_PEAK or min(shape) < 1:
+            raise ValueError(f"peaks must be a float64 {be.array} of shape [B, I, {FRINGE_PEAK}] (Context.fringe_search)")
+        B, I, A = shape[0], shape[1], int(nant)
+        if A < 2:
+            raise ValueError("nant must be >= 2")
+        a1, a2 = stream_array(be, a1, be.i64, B, "a1"), stream_array(be, a2, be.i64, B, "a2")
+        scalars = fringe_solve_scalars(min_count, min_coh2, refant, niter, tol, A)
+        if sol is None:
+            sol = be.zeros((I, A, 4), be.f64, peaks)
+            sol[:, :, 2] = 1.0
+        sol = fringe_sol(be, sol, I, A, peaks)
+        info, stats = be.empty((I, A), be.f64, peaks), be.empty(8, be.f64, peaks)
+        self._call(be, "fringe_solve", B, I, A, a1, a2, peaks, *scalars, sol, info, stats)
+        return sol, info, stats
+
+    def fringefit(self, vis, tables, a1, a2, nant, tint, delays, rates, model_vis=None, weights=None, sol=None, rounds=3,
+                  window=(2, 2), min_count=0, min_coh2=0.0, refant=0, niter=50, tol=0.0):
+        """Delay and rate calibration (gridhip_fringefit[_dev]): `rounds` (1 .. 4) times a fringe search followed by the
+        antenna-based fit.  Round 0 searches the whole grid - delays = (tau0, dtau, Nd), rates = (r0, drate, Nr) and tint
+        as given to Context.fringe_tables - against `sol` where one is given (a warm start, updated in place) or zero; the
+        later rounds derotate by the current solution and search only the cells within window = (wj, wk) of the grid's
+        zero, so that the parabola refines a residual of a fraction of a cell.  Everything else is Context.fringe_search's
+        and Context.fringe_solve's.  Returns (sol [I, nant, 4] = tau, r, Re g, Im g per interval and antenna, peaks of the
+        last round, info, stats = [sweeps of the last solve, flagged samples, bad, empty, unsolved antennas, weighted rms
+        of the last round's tau_b and r_b in cells, invalid]).  Correct data with Context.apply_fringe(sol, ...).  A fixed
+        number of launches, nothing read back: with cuda tensors the call can be captured into a graph."""
+        be = backend(vis)
+        B, T, F, A, vis, model_vis, wt, a1, a2 = fringe_cube(be, vis, model_vis, weights, a1, a2, nant)
+        tables, I = fringe_table_of(be, tables, F, T, tint)
+        Nd, Nr = int(delays[2]), int(rates[2])
+        if int(tables.shape[0]) != fringe_table_doubles(F, T, Nd, Nr):
+            raise ValueError(f"tables of {int(tables.shape[0])} values do not belong to this cube and these axes")
+        rounds, (wj, wk) = int(rounds), (int(v) for v in window)
+        if not 1 <= rounds <= 4 or not (0 <= wj <= FRINGE_MAX_DELAYS and 0 <= wk <= FRINGE_MAX_RATES):
+            raise ValueError("rounds must be in 1 .. 4 and window a pair of cell counts >= 0")
+        scalars = fringe_solve_scalars(min_count, min_coh2, refant, niter, tol, A)
+        warm = int(sol is not None)
+        sol = fringe_sol(be, sol, I, A, vis) if warm else be.empty((I, A, 4), be.f64, vis)
+        peaks, info = be.empty((B, I, FRINGE_PEAK), be.f64, vis), be.empty((I, A), be.f64, vis)
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "fringefit", B, T, F, A, I, Nd, Nr, tables, vis, model_vis, wt, a1, a2, rounds, wj, wk, *scalars,
+                   warm, sol, peaks, info, stats)
+        return sol, peaks, info, stats
+
+    def apply_fringe(self, sol, tables, vis, a1, a2, tint, *, inverse=True, weights=None, out=None, weights_out=None):
+        """Apply a delay and rate solution to a [B, T, F] cube (gridhip_apply_fringe[_dev]).  inverse=True corrects data:
+        vis conj(D) with D = g_p conj(g_q) exp(2 pi i ((tau_p - tau_q)(nu_f - nu0) + (r_p - r_q)(t - tref_i))); inverse=False
+        corrupts a model: vis D.  Weights are copied (ones without `weights`); a sample that touches an antenna whose row
+        of `sol` is not finite, or an antenna out of range, keeps its value and gets the weight +0.0.  out, weights_out:
+        the arrays to write, which may be vis and weights themselves.  Returns (out, weights_out); a table made with another tint
+        than the one given here leaves both unwritten (a numpy table is refused with ValueError).  Only the head and the
+        two coordinate vectors of the table are read: a table of any search axes over the same freq, time and tint."""
+        be = backend(vis)
+        nant = int(sol.shape[1]) if hasattr(sol, "shape") and len(sol.shape) == 3 else 0
+        B, T, F, A, vis, _, wt, a1, a2 = fringe_cube(be, vis, None, weights, a1, a2, nant)
+        tables, I = fringe_table_of(be, tables, F, T, tint)
+        sol = fringe_sol(be, sol, I, A, vis)
+        out = result_array(be, out, be.c128, (B, T, F), "out", vis)
+        weights_out = result_array(be, weights_out, be.f64, (B, T, F), "weights_out", vis)
+        self._call(be, "apply_fringe", B, T, F, A, I, tables, sol, a1, a2, int(bool(inverse)), vis, wt, out, weights_out)
+        return out, weights_out
 
     def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
         """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
@@ -1693,6 +1815,40 @@ def contsub_tile():
     if rc != 0:
         raise GridHipError(rc, "gridhip_contsub_tile")
     return int(out[0]), int(out[1])
+
+
+def fringe_tile():
+    """(delays per work-group, channels per staged chunk, rates per lane-pass) of Context.fringe_search's kernel
+    (gridhip_fringe_tile)."""
+    out = (C.c_int64 * 3)()
+    rc = _lib.load().gridhip_fringe_tile(out)
+    if rc != 0:
+        raise GridHipError(rc, "gridhip_fringe_tile")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def fringe_grid(freq, time, tint, pad=4):
+    """The delay and rate cells a band and a solution interval support: returns (tau0, dtau, Nd), (r0, drate, Nr), both
+    centred on 0 (cell N // 2 is zero).  dtau = 1 / (pad * F * median channel step) with Nd = pad * F cells, so that the
+    axis spans the unambiguous range 1 / step at `pad` cells per resolution element; the rate axis is built the same way
+    from the tint time steps of an interval (0: all) and the median time step.  Pure host code: Context.fringe_tables
+    takes the two triples."""
+    import numpy as np
+    freq, time = np.asarray(freq, dtype=np.float64).reshape(-1), np.asarray(time, dtype=np.float64).reshape(-1)
+    F, T, pad = freq.size, time.size, int(pad)
+    if F < 1 or T < 1 or pad < 1:
+        raise ValueError("freq and time must hold at least one value each and pad must be >= 1")
+    tint, _ = fringe_intervals(T, tint)
+    df = float(np.median(np.abs(np.diff(freq)))) if F > 1 else 1.0
+    dt = float(np.median(np.abs(np.diff(time)))) if T > 1 else 1.0
+    if not (np.isfinite(df) and df > 0.0 and np.isfinite(dt) and dt > 0.0):
+        raise ValueError("the median channel step and time step must be finite and > 0")
+    Nd, Nr = pad * F, pad * tint
+    if Nd > FRINGE_MAX_DELAYS or Nr > FRINGE_MAX_RATES:
+        raise ValueError(f"pad * F = {Nd} delays (at most {FRINGE_MAX_DELAYS}) or pad * tint = {Nr} rates (at most "
+                         f"{FRINGE_MAX_RATES}): lower pad")
+    dtau, drate = 1.0 / (pad * F * df), 1.0 / (pad * tint * dt)
+    return (-(Nd // 2) * dtau, dtau, Nd), (-(Nr // 2) * drate, drate, Nr)
 
 
 def channel_coordinate(freq):

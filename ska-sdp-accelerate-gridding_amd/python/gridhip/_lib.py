@@ -70,6 +70,17 @@ _RMSYNTH = [vp, i64, i64, i64, vp, vp, vp, vp, vp]  # M, C, J, tables, Q, U, cub
 _RMCLEAN = [vp, i64, i64, vp, vp, vp, C.c_double, C.c_double, i64, C.c_double, vp, ci, vp, vp]
 # ctx, R, C, layout, ncomp, degree, mode, x, chan_mask, data, wt, nsigma, niter, out, coeffs, rowinfo, codes, stats
 _CONTSUB = [vp, i64, i64, ci, ci, ci, ci, vp, vp, vp, vp, C.c_double, i64, vp, vp, vp, vp, vp]
+# F, T, tint, freq, time, tau0, dtau, Nd, r0, drate, Nr, tables
+_FRINGE_TABLES = [vp, i64, i64, i64, vp, vp, C.c_double, C.c_double, i64, C.c_double, C.c_double, i64, vp]
+# B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, k0, k1, peaks, stats
+_FRINGE_SEARCH = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]
+# B, I, A, a1, a2, peaks, min_count, min_coh2, refant, niter, tol, sol, info, stats
+_FRINGE_SOLVE = [vp, i64, i64, i64, vp, vp, vp, C.c_double, C.c_double, i64, i64, C.c_double, vp, vp, vp]
+# B, T, F, A, I, Nd, Nr, tables, vis, model_vis, wt, a1, a2, rounds, wj, wk, then the solve's scalars, warm, sol, peaks, info, stats
+_FRINGEFIT = [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_double, C.c_double, i64, i64,
+              C.c_double, ci, vp, vp, vp, vp]
+# B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in, vis_out, wt_out
+_APPLY_FRINGE = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 # border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats
@@ -241,6 +252,17 @@ SIGNATURES = {
     "gridhip_contsub": (ci, _CONTSUB),
     "gridhip_contsub_dev": (ci, _CONTSUB),
     "gridhip_contsub_tile": (ci, [C.POINTER(i64)]),
+    "gridhip_fringe_tables": (ci, _FRINGE_TABLES),
+    "gridhip_fringe_tables_dev": (ci, _FRINGE_TABLES),
+    "gridhip_fringe_search": (ci, _FRINGE_SEARCH),
+    "gridhip_fringe_search_dev": (ci, _FRINGE_SEARCH),
+    "gridhip_fringe_solve": (ci, _FRINGE_SOLVE),
+    "gridhip_fringe_solve_dev": (ci, _FRINGE_SOLVE),
+    "gridhip_fringefit": (ci, _FRINGEFIT),
+    "gridhip_fringefit_dev": (ci, _FRINGEFIT),
+    "gridhip_apply_fringe": (ci, _APPLY_FRINGE),
+    "gridhip_apply_fringe_dev": (ci, _APPLY_FRINGE),
+    "gridhip_fringe_tile": (ci, [C.POINTER(i64)]),
     "gridhip_dft_predict": (ci, _DFT_PREDICT),
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),

@@ -732,6 +732,107 @@ def rm_clean_scalars(be, gain, threshold, niter, nsigma, noise, restore, like):
     return gain, threshold, niter, nsigma, noise, int(bool(restore))
 
 
+FRINGE_HEAD, FRINGE_PEAK = 16, 12  # GRIDHIP_FRINGE_* of include/gridhip.h
+FRINGE_MAX_CHANNELS, FRINGE_MAX_DELAYS, FRINGE_MAX_TINT, FRINGE_MAX_RATES = 1024, 4096, 256, 1024
+
+
+def fringe_table_doubles(F, T, Nd, Nr):
+    """GRIDHIP_FRINGE_TABLE_DOUBLES(F, T, Nd, Nr): head, Ef[F][Nd] and Et[T][Nr] complex, tref[T], a[F], dt[T]"""
+    return FRINGE_HEAD + 2 * F * Nd + 2 * T * Nr + 2 * T + F
+
+
+def fringe_intervals(T, tint):
+    """tint after the 0 -> T rule, and I = ceil(T / tint)"""
+    tint = int(tint)
+    tint = T if tint == 0 else tint
+    if not 1 <= tint <= FRINGE_MAX_TINT:
+        raise ValueError(f"tint must be in 1 .. {FRINGE_MAX_TINT} (0: all {T} time steps), not {tint}")
+    return tint, (T + tint - 1) // tint
+
+
+def fringe_axis(axis, most, what):
+    """(x0, dx, N) of a search axis"""
+    import math
+    try:
+        x0, dx, N = axis
+        x0, dx, N = float(x0), float(dx), int(N)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be (first, step, count)") from None
+    if not 1 <= N <= most:
+        raise ValueError(f"{what} must hold 1 .. {most} cells, not {N}")
+    if not (math.isfinite(x0) and math.isfinite(dx) and dx > 0.0):
+        raise ValueError(f"{what} must start at a finite value with a finite step > 0")
+    return x0, dx, N
+
+
+def fringe_table_args(be, freq, time, tint, delays, rates):
+    """F, T, tint, freq, time, tau0, dtau, Nd, r0, drate, Nr as gridhip_fringe_tables takes them"""
+    if freq is None or time is None or be is not backend(time):
+        raise ValueError(f"freq and time must be {be.array}s of one kind")
+    freq, time = stream_array(be, freq, be.f64, -1, "freq"), stream_array(be, time, be.f64, -1, "time")
+    F, T = int(freq.shape[0]), int(time.shape[0])
+    if not 1 <= F <= FRINGE_MAX_CHANNELS or T < 1:
+        raise ValueError(f"freq must hold 1 .. {FRINGE_MAX_CHANNELS} channels and time at least one step")
+    tint, _ = fringe_intervals(T, tint)
+    return (F, T, tint, freq, time, *fringe_axis(delays, FRINGE_MAX_DELAYS, "delays"),
+            *fringe_axis(rates, FRINGE_MAX_RATES, "rates"))
+
+
+def fringe_cube(be, vis, model_vis, weights, a1, a2, nant):
+    """B, T, F, A, vis, model_vis, wt, a1, a2: the [B, T, F] cube of a fringe call and its antenna pairs"""
+    if vis is None or not hasattr(vis, "shape") or len(vis.shape) != 3 or min(int(v) for v in vis.shape) < 1:
+        raise ValueError("vis must be a [B, T, F] cube (gridhip.waterfall_layout, order \"btf\")")
+    shape = tuple(int(v) for v in vis.shape)
+    B, T, F = shape
+    A = int(nant)
+    if A < 2 or not 1 <= F <= FRINGE_MAX_CHANNELS:
+        raise ValueError(f"nant must be >= 2 and the cube must hold 1 .. {FRINGE_MAX_CHANNELS} channels")
+    for x, what in ((model_vis, "model_vis"), (weights, "weights")):
+        if x is not None and (be is not backend(x) or tuple(int(v) for v in x.shape) != shape):
+            raise ValueError(f"{what} must be a {be.array} of vis' shape {shape}")
+    if weights is not None and ((weights.dtype.kind == "c") if be is HOST else weights.dtype.is_complex):
+        raise ValueError("weights must be real")
+    return (B, T, F, A, be.cv(vis, be.c128), be.cv(model_vis, be.c128), be.cv(weights, be.f64),
+            _integers(be, a1, B, "a1"), _integers(be, a2, B, "a2"))
+
+
+def fringe_table_of(be, tables, F, T, tint):
+    """tables, I of a table that belongs to a cube of T time steps and F channels: tint is what Context.fringe_tables was
+    given, and I = ceil(T / tint) is what the caller's peaks and sol are sized by.  The library compares I with the table's
+    head and refuses another (stats[7] = 1, nothing written); a numpy table's head is compared here as well, so that the
+    mistake raises."""
+    if tables is None or be is not backend(tables) or not be.ok(tables, be.f64) or len(tables.shape) != 1 or \
+            int(tables.shape[0]) < FRINGE_HEAD:
+        raise ValueError(f"tables must be a one-dimensional float64 {be.array} (Context.fringe_tables)")
+    tint, I = fringe_intervals(T, tint)
+    if be is HOST and tables[0] == 1.0 and (tables[1], tables[2]) == (F, T) and (tables[3], tables[4]) != (tint, I):
+        raise ValueError(f"tables were made with tint = {int(tables[3])} ({int(tables[4])} intervals), not {tint} ({I})")
+    return tables, I
+
+
+def fringe_sol(be, sol, I, A, like, what="sol"):
+    """a solution [I][A][4] in the ABI's form, or None"""
+    if sol is None:
+        return None
+    if not (be is backend(sol) and be.ok(sol, be.f64) and tuple(int(v) for v in sol.shape) == (I, A, 4)):
+        raise ValueError(f"{what} must be a float64 {be.array} of shape ({I}, {A}, 4): tau, r, Re g, Im g")
+    return sol
+
+
+def fringe_solve_scalars(min_count, min_coh2, refant, niter, tol, A):
+    """min_count, min_coh2, refant, niter, tol as gridhip_fringe_solve takes them (refant None: -1)"""
+    import math
+    min_count, min_coh2, niter, tol = float(min_count), float(min_coh2), int(niter), float(tol)
+    refant = -1 if refant is None else int(refant)
+    if refant >= A:
+        raise ValueError(f"refant must be below nant ({A}), or None")
+    if not (math.isfinite(min_count) and min_count >= 0.0 and math.isfinite(min_coh2) and min_coh2 >= 0.0):
+        raise ValueError("min_count and min_coh2 must be finite and >= 0")
+    if not 0 <= niter <= 100000 or not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError("niter must be in 0 .. 100000 and tol finite and >= 0")
+    return min_count, min_coh2, refant, niter, tol
+
+
 CONTSUB_MAX_CHANNELS, CONTSUB_MAX_DEGREE, CONTSUB_ROWINFO, CONTSUB_MAX_ROUNDS = 4096, 3, 4, 4  # GRIDHIP_CONTSUB_*
 
 
