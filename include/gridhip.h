@@ -103,6 +103,13 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               calls do not try); 1 = never.  A call made while the stream is being captured into a graph neither
  *               verifies nor leaves anything to reuse, and a replay of such a graph marks the device so that the
  *               next call after it runs its pre-pass in full
+ *   "list_reuse" 0 = auto: such a call over the two-level pre-pass also keeps the tap-reusing tile kernel's per-work-item
+ *               lists of records sorted by kernel slice (in the block that held the pre-records, 8 B per record), and the
+ *               next one whose records stand - same work-item shape, no other pre-pass in between, the verify sweep's
+ *               verdict read on the device - walks them instead of sorting again (convgrid2 and degrid2 share them, as
+ *               they share the records); 1 = never: every call sorts into the per-work-group scratch.  Calls cut into
+ *               parts, the one-level pre-pass, the aw forms, plans, imagers and captured calls always do; "bin_reuse" = 1
+ *               implies it
  *   "aw_cache"  aw gridders: 1 (default) = build each distinct (a1, a2, wbin, yf, xf) kernel once per call and let
  *               the visibilities that share it reuse it; 0 = one kernel per visibility (as the reference evaluates)
  *   "aw_batch"  aw gridders, degridders and plans: visibilities per batch of the kernel table.  0 (default) = 2^20 with
@@ -143,6 +150,8 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
  * "prepass_reused" = those of them that kept their records (counted on the device: reading it synchronises the stream);
+ * "lists_reused" = tile launches so far that were told the previous call's sorted lists are in place ("list_reuse"; the
+ * kernel still sorts afresh if the verify sweep then finds the records changed);
  * "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last convgrid / convgrid2 / degrid2
  * call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
  * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or

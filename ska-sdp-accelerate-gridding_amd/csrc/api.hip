@@ -60,6 +60,12 @@ template <typename One>
 int in_parts(gridhip_ctx *ctx, int64_t n, int64_t part, One one)
 {
     if (part < 0) return fail(ctx, GRIDHIP_EUNSUPPORTED, "kernel table with too many slices");
+    // (the parts share the record array one after the other: none of them keeps its sorted lists)
+    struct Hold {
+        gridhip_ctx *c;
+        explicit Hold(gridhip_ctx *c_) : c(c_) { ++c->list_hold; }
+        ~Hold() { --c->list_hold; }
+    } hold(ctx);
     for (int64_t lo = 0; lo < n; lo += part) GH_CHECK(one(lo, part < n - lo ? part : n - lo));
     return GRIDHIP_OK;
 }
@@ -188,11 +194,11 @@ int tile_kernels(gridhip_ctx *ctx, const Prep &p, const double *gcf, const doubl
 
 // (gridding reads vis and writes grid, degridding the other way round: the const of the one it writes is cast away here)
 int tile_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t nrec, const double *table, const double *vis,
-              const double *grid, bool degrid)
+              const double *grid, bool degrid, bool may_keep)
 {
     if (p.sorted)  // the sorted kernel's degrid mode reads `grid` and writes the vis array
         return launch_tile_grid_sorted(ctx, g, p.block, p.lds_sorted, p.nkeys, p.batch, nrec, table, vis,
-                                       const_cast<double *>(grid), degrid);
+                                       const_cast<double *>(grid), degrid, may_keep);
     if (degrid) return launch_tile_degrid(ctx, g, p.block, p.lds, nrec, table, grid, const_cast<double *>(vis));
     return launch_tile_grid(ctx, g, p.block, p.lds, nrec, table, vis, const_cast<double *>(grid));
 }
@@ -246,7 +252,7 @@ int gridhip_convgrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid,
     GH_CHECK(tile_kernels(ctx, p, gcf, &tk));
     GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, nullptr, true));
     mark(ctx, 1);
-    if (n > 0) GH_CHECK(tile_pass(ctx, p, p.g, p.nrec, tk, vis, grid, false));
+    if (n > 0) GH_CHECK(tile_pass(ctx, p, p.g, p.nrec, tk, vis, grid, false, true));
     mark(ctx, 2);
     return GRIDHIP_OK;
 }
@@ -285,7 +291,7 @@ int gridhip_degrid2_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, const double *g
     GH_CHECK(tile_kernels(ctx, p, gcf, &tk));
     GH_CHECK(launch_bin(ctx, p.g, p.nrec, u, v, uv_stride, wbin, parts ? nullptr : reinterpret_cast<double2 *>(vis_out), true));
     mark(ctx, 1);
-    if (n > 0) GH_CHECK(tile_pass(ctx, p, p.g, p.nrec, tk, vis_out, grid, true));
+    if (n > 0) GH_CHECK(tile_pass(ctx, p, p.g, p.nrec, tk, vis_out, grid, true, true));
     mark(ctx, 2);
     return GRIDHIP_OK;
 }

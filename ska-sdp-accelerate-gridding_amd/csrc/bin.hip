@@ -1178,6 +1178,7 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
             keep.pending = false;
         }
         keep.valid = false;
+        keep.verifying = verify;
         if (verify && !keep.host_flag) {
             GH_CHECK_HIP(ctx, hipHostMalloc((void **)&keep.host_flag, 64, hipHostMallocMapped));
             GH_CHECK_HIP(ctx, hipHostGetDevicePointer((void **)&keep.host_flag_dev, keep.host_flag, 0));
@@ -1266,6 +1267,7 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
     }
 
     ctx->keep.valid = false;
+    ctx->keep.verifying = false;
     launch_clear(ctx, t.bin_count, g.nbins, t.scalars, 3, nullptr, 0, nullptr, t.scalars + SC_GEN, gen_in + 1);
     if (lds_hist) {
         GH_CHECK(ws_reserve(ctx, ctx->blockhist, (size_t)blocks * g.nbins * sizeof(int32_t)));

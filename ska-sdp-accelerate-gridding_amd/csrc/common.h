@@ -112,7 +112,7 @@ __host__ __device__ __forceinline__ RecWord rec_pack(const Geom &g, int32_t lxy,
 }
 
 struct Options {
-    int64_t tile = 0, block = 0, chunk = 0, wgroups = 0, variant = 0, sort = 0, dbg = 0, prepass = 0, fault_inject = 0, aw_cache = 1, aw_batch = 0, tile_x = 0, tile_y = 0, coarse_shift = 0, scatter_chunk = 0, count_unroll = 0, rec_bits = 0, wtable = 0, reserve_cus = 0, subfoot = 0, bigtile = 0, yield_cus = 0, bin_reuse = 0;
+    int64_t tile = 0, block = 0, chunk = 0, wgroups = 0, variant = 0, sort = 0, dbg = 0, prepass = 0, fault_inject = 0, aw_cache = 1, aw_batch = 0, tile_x = 0, tile_y = 0, coarse_shift = 0, scatter_chunk = 0, count_unroll = 0, rec_bits = 0, wtable = 0, reserve_cus = 0, subfoot = 0, bigtile = 0, yield_cus = 0, bin_reuse = 0, list_reuse = 0;
 };
 
 struct Workspace {
@@ -139,6 +139,16 @@ struct BinKeep {
     int32_t *host_flag = nullptr;  // mapped host word: 1 = the last verifying pre-pass kept its records, 0 = it did not
     int32_t *host_flag_dev = nullptr;
     int64_t verified = 0;    // calls that ran the verify sweep (read-only option "prepass_verified")
+    bool verifying = false;  // the last launch_bin enqueued a verify sweep: its verdict is the one in SC_MATCH
+};
+// What the last tile launch that KEPT its sorted lists (tile_sorted.hip, "Kept lists") ran under: the next launch may
+// tell the kernel to trust them only if all of this is equal and the pre-pass generation is the next one.
+struct ListKeep {
+    bool valid = false;
+    uint64_t gen = 0;        // gridhip_ctx::bin_gen at that launch
+    int64_t nrec = 0;
+    int32_t nkeys = 0, batch = 0, ngroups = 0, ntiles = 0, Tx = 0, Ty = 0, ldw = 0, Q = 0, W = 0, P = 0;
+    const void *list = nullptr, *staged = nullptr;
 };
 // slots of d_scalars the reuse uses: the verify sweep's verdict (1 = every pre-record equal), its count of dropped
 // visibilities, the calls that kept their records so far (read-only option "prepass_reused"), and - two words - the
@@ -161,7 +171,9 @@ struct gridhip_ctx {
     gridhip::Workspace recs;    // RecWord[n]
     gridhip::Workspace tables;  // bin_count / bin_start / work_start / cursors / scalars
     gridhip::Workspace sorted;  // sorted-list scratch of the tap-reusing tile kernel (tile_sorted.hip)
-    gridhip::Workspace recs_raw;   // 8-byte pre-records the counting sweep leaves for the scatter (bin.hip)
+    gridhip::Workspace recs_raw;   // 8-byte pre-records the counting sweep leaves for the scatter (bin.hip); after the
+                                   // scatter, the sorted lists a plain call's tile kernel keeps (tile_sorted.hip)
+    gridhip::Workspace list_staged;  // int32 per work item: entries of its kept sorted list
     gridhip::Workspace bin_digest; // Digest[n / 128] of those pre-records, kept for the next call's verify sweep (bin_digest.h)
     gridhip::Workspace recs_tmp;   // coarse-binned records between the two scatter levels of the pre-pass (bin.hip)
     gridhip::Workspace blockhist;  // [pre-pass work-groups][nbins] histograms -> first slots
@@ -174,6 +186,9 @@ struct gridhip_ctx {
     // good as the generation it was written under
     uint64_t bin_gen = 0;
     gridhip::BinKeep keep;
+    gridhip::ListKeep lists;
+    int list_hold = 0;          // > 0: inside a call cut into parts (api.hip): no lists are kept
+    int64_t lists_reused = 0;   // tile launches told to trust the kept lists (read-only option "lists_reused")
     int num_cu = 256;
     int max_lds = 160 * 1024;
     bool timing = false;
@@ -301,8 +316,9 @@ int launch_bin(gridhip_ctx *ctx, const Geom &g, int64_t n, const double *u, cons
 int launch_tile_grid(gridhip_ctx *ctx, const Geom &g, int block, size_t lds_bytes, int64_t n,
                      const double *gcf, const double *vis, double *grid);
 bool sorted_plan(const gridhip_ctx *ctx, const Geom &g, int block, int *nkeys, int *maxchunk, size_t *lds_bytes);
+// may_keep: a plain convgrid2 / degrid2 call, whose sorted lists may outlive it ("Kept lists" in tile_sorted.hip)
 int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g, int block, size_t lds_bytes, int nkeys, int maxchunk,
-                            int64_t n, const double *gcf, const double *vis, double *grid, bool degrid);
+                            int64_t n, const double *gcf, const double *vis, double *grid, bool degrid, bool may_keep = false);
 int launch_tile_degrid(gridhip_ctx *ctx, const Geom &g, int block, size_t lds_bytes, int64_t n,
                        const double *gcf, const double *grid, double *vis_out);
 int launch_direct_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n,
@@ -327,7 +343,7 @@ int tile_kernels(gridhip_ctx *ctx, const Prep &p, const double *gcf, const doubl
 // vis x kernels onto grid; degridding reads grid and writes the predictions to vis.  p says which kernel (the
 // tap-reusing one, or the general one of the direction) and its launch shape; g is p.g, or a batch's copy of it (aw).
 int tile_pass(gridhip_ctx *ctx, const Prep &p, const Geom &g, int64_t nrec, const double *table, const double *vis,
-              const double *grid, bool degrid);
+              const double *grid, bool degrid, bool may_keep = false);
 int launch_simple_grid(gridhip_ctx *ctx, int64_t H, int64_t Wd, double *grid, int64_t n,
                        const double *u, const double *v, int64_t uv_stride, const double *vis);
 

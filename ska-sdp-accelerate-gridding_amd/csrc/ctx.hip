@@ -426,7 +426,7 @@ int gridhip_destroy(gridhip_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     fft_release(ctx);
-    Workspace *all[] = {&ctx->recs, &ctx->tables, &ctx->blockhist, &ctx->sorted, &ctx->recs_tmp, &ctx->recs_raw, &ctx->bin_digest, &ctx->ktab, &ctx->aw};
+    Workspace *all[] = {&ctx->recs, &ctx->tables, &ctx->blockhist, &ctx->sorted, &ctx->recs_tmp, &ctx->recs_raw, &ctx->list_staged, &ctx->bin_digest, &ctx->ktab, &ctx->aw};
     for (Workspace *w : all)
         if (w->ptr) (void)hipFree(w->ptr);
     for (auto &b : ctx->img->pool_free) (void)hipFree(b.first);
@@ -514,6 +514,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "bigtile")) return &ctx->opt.bigtile;
     if (!strcmp(key, "yield_cus")) return &ctx->opt.yield_cus;
     if (!strcmp(key, "bin_reuse")) return &ctx->opt.bin_reuse;
+    if (!strcmp(key, "list_reuse")) return &ctx->opt.list_reuse;
     if (!strcmp(key, "noise_bits")) return &ctx->img->noise_bits;  // image_stats' digit: 8, or anything else for 13
     if (!strcmp(key, "dft_slices")) return &ctx->img->dft_slices;  // dft_predict's component slices: 0 = auto, 1..64
     if (!strcmp(key, "mosaic_cull")) return &ctx->img->mosaic_cull;  // mosaic's per-tile cull: 0 = on, 1 = every valid facet
@@ -569,6 +570,12 @@ int gridhip_get_option(gridhip_ctx *ctx, const char *key, int64_t *value)
         GH_CHECK_HIP(ctx, hipMemcpyAsync(&h, ctx->d_scalars + SC_REUSED, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
         GH_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         *value = h;
+        return GRIDHIP_OK;
+    }
+    if (!strcmp(key, "lists_reused")) {
+        // read-only: tile launches so far that were told to trust the previous call's sorted lists (tile_sorted.hip,
+        // "Kept lists"; the kernel still sorts when the verify sweep's verdict goes against the records)
+        *value = ctx->lists_reused;
         return GRIDHIP_OK;
     }
     if (!strcmp(key, "last_path")) {

@@ -11,7 +11,8 @@
 //
 // Where things live (65 x 89 tiles, 15x15): LDS holds the tile (2 x 65.1 KB, resident for the whole
 // work item, flushed once) and the sort's histogram (4.1 KB).  The sorted list itself - 8 bytes per
-// record: (slice key | cell offset, orig) - goes to a per-work-group scratch in global memory: it is
+// record: (slice key | cell offset, orig) - goes to a per-work-group scratch in global memory (or, where the next call
+// may walk it again, to the record's own position in a per-call array: "Kept lists" below): it is
 // written once and read once, coalesced, by the same CU, and the walkers gather each record's visibility
 // value from the caller's array a block of 64 records ahead of its use.  That keeps LDS reads out of the
 // accumulate loop altogether: an LDS read returns only after the wave's outstanding ds_add_f64s, so every
@@ -54,7 +55,20 @@ __device__ const int cut15[3][16] = {{0, 106, 211, 317, 422, 500, 578, 655, 733,
 
 struct SortedItem {
     int32_t valid, tile, grp, staged;
+    int32_t v_lo;  // the item's first record: where its list starts in the per-call list array ("Kept lists")
 };
+
+// Kept lists.  A plain convgrid2 / degrid2 call over the two-level pre-pass (launch argument keep_list != null) does not
+// sort into the per-work-group scratch: a work item covers records [v_lo, v_hi) of the tile-ordered record array, and
+// its sorted list goes to entries [v_lo, v_lo + staged) of ONE array of 8-byte entries per call - the block that held
+// the counting sweep's pre-records (recs_raw), which nothing reads once the scatter has run and which every full
+// pre-pass rewrites, i.e. exactly when the lists die - and `staged` to keep_staged[grp * istride + item].  The next
+// such call under the same geometry and the next pre-pass generation (the host's share: lists_valid) whose verify sweep
+// finds every record unchanged (the device's share: the verdict word SC_MATCH) walks those lists again: its prepare()
+// fetches the item, reads `staged` and returns.  A verdict of 0 means the scatter has just rewritten records and
+// pre-records: the kernel sorts, and what it writes are the lists of the new generation.
+// What the walkers read from a kept list has been in memory since an earlier launch, so both fields that become
+// addresses are brought into range where they are loaded (load_list), as load_rec does for the records.
 
 // AW (aw gridders, awgrid.hip): a record's kslice is the index of its de-duplicated (a1, a2, wbin, yf, xf) kernel in a
 // table built for this call - arbitrary 31-bit numbers, far more of them than a histogram holds.  The counting sort
@@ -76,7 +90,10 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
                                                                 double *__restrict__ grid, int nkeys, int batch,
                                                                 int32_t *__restrict__ scalars,
                                                                 double2 *__restrict__ sorted_vals,
-                                                                uint2 *__restrict__ sorted_mo)
+                                                                uint2 *__restrict__ sorted_mo,
+                                                                uint2 *__restrict__ keep_list,
+                                                                int32_t *__restrict__ keep_staged, int istride,
+                                                                int lists_valid)
 {
     extern __shared__ double lds[];
     constexpr int S2 = S * S;
@@ -131,6 +148,11 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
     // gathers the values and stages them next to the list (16 bytes more per record, written and read back).
     constexpr bool STAGE_VALS = !DEGRID && AW;
     constexpr bool STAGE_ORIG = DEGRID && AW;  // (the aw gather: orig travels next to the list)
+    // kept lists (never the aw forms): `keeping` = this launch's lists go to / come from the per-call array; `kept` = they
+    // are there already (uniform: one kernel argument and one word the pre-pass wrote before this launch)
+    const bool keeping = !AW && keep_list != nullptr;
+    const bool kept = keeping && lists_valid && __builtin_amdgcn_readfirstlane(scalars[SC_MATCH]) == 1;
+    const int maxcell = (g.Ty - 1) * g.ldw + g.Tx - 1;  // largest cell offset of a footprint origin
     const bool solo = nw == 1;
     const bool is_sorter = wave == nw - 1;
     // the sorter is the youngest wave of its SIMD, i.e. last at the arbiter, and its work is a chain of latencies:
@@ -168,13 +190,13 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
     int items_left = ((int)blockIdx.x >= g.npersist) ? g.budget : 0x7fffffff;
     auto prepare = [&](int slot) {
         WorkItem w;
-        int grp = 0;
+        int grp = 0, item = 0;
         bool have = false;
         if (items_left <= 0) turn = g.ngroups;
         --items_left;
         while (turn < g.ngroups) {
             grp = (blockIdx.x + turn) % g.ngroups;
-            int item = 0;
+            item = 0;
             if (lane == 0) item = atomicAdd(&queue[grp], 1);
             item = __builtin_amdgcn_readfirstlane(item);
             if (find_work_at(g, bin_start, work_start, grp, item, &w)) {
@@ -195,6 +217,21 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
         int32_t *sorig = sorig_wg + (size_t)slot * batch;
         const int b_lo = w.v_lo;
         const int cnt = min(batch, w.v_hi - b_lo);  // a work item never holds more than `batch` records
+        // (find_work_at ends a queue at item nrec / chunk + ntiles: istride is one more than that)
+        int32_t *my_staged = keeping ? keep_staged + ((size_t)grp * istride + min(item, istride - 1)) : nullptr;
+        if (kept) {  // the list of this item is where the previous launch left it
+            if (lane == 0) {
+                SortedItem d;
+                d.valid = 1;
+                d.tile = w.tile;
+                d.grp = grp;
+                d.staged = min(max(*my_staged, 0), max(cnt, 0));
+                d.v_lo = b_lo;
+                desc[slot] = d;
+            }
+            return;
+        }
+        if (keeping) smo = keep_list + b_lo;  // entries [v_lo, v_lo + cnt): inside the item's own records' range
         // counting sort by kernel slice, one wave: LDS operations of a wave execute in program order; the
         // fences keep the compiler from reordering them across the phases
         for (int i = lane; i <= nkeys; i += 64) hist[i] = 0;
@@ -263,7 +300,7 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
                 // run_rank, as the pre-pass does - gained 0.7 - 1 % on streams of long tracks and cost the random stream
                 // 0.7 %: the extra instructions sit on the sorter's critical path)
                 const int pos = atomicAdd(&hist[key], 1);
-                if ((unsigned)pos < (unsigned)batch) {
+                if ((unsigned)pos < (unsigned)cnt) {
                     // meta = slice key | the footprint origin's cell offset in the tile (< 8192: sorted_plan)
                     smo[pos] = make_uint2(((uint32_t)key << 16) | (uint32_t)((rec[q].lxy >> 16) * g.ldw + (rec[q].lxy & 0xffff)),
                                           (uint32_t)(AW ? rec[q].kslice : rec[q].orig));
@@ -283,8 +320,10 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
             d.valid = 1;
             d.tile = w.tile;
             d.grp = grp;
-            d.staged = hist[nkeys - 1];
+            d.staged = min(hist[nkeys - 1], max(cnt, 0));
+            d.v_lo = b_lo;
             desc[slot] = d;
+            if (keeping) *my_staged = d.staged;
         }
         GH_STAMP(3)  // scatter + value gather
     };
@@ -307,9 +346,9 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
     // The piece is taken in blocks of 64 records: two coalesced loads bring a block into registers, one
     // record per lane; runs of equal slice are found with a ballot and every per-record quantity is
     // broadcast with v_readlane, so the accumulate loop issues nothing but arithmetic and ds_add_f64.
-    auto walk = [&](int slot, int staged, int first_slice) {
+    auto walk = [&](int slot, int staged, int first_slice, int v_lo) {
         const double2 *svals = svals_wg + (size_t)slot * batch;
-        const uint2 *smo = smo_wg + (size_t)slot * batch;
+        const uint2 *smo = keeping ? keep_list + v_lo : smo_wg + (size_t)slot * batch;
         const int32_t *sorig = sorig_wg + (size_t)slot * batch;
         // With 15 walkers the pieces are weighted: the SIMD arbiter favours its oldest wave, so with equal pieces
         // walkers 0..3 finish at 0.55 of the walk and the last three run on for the rest with the LDS unit half idle.
@@ -326,10 +365,16 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
         auto load_list = [&](int b0, uint2 &mo, double2 &v, int32_t &o) {
             const int idx = max(min(b0 + lane, seg_hi - 1), seg_lo);  // past the end: the piece's last record
             mo = smo[idx];
+            if (keeping) {  // (uniform) cell offset and orig of a kept entry: in range before either becomes an address
+                const uint32_t cell = min(mo.x & 0xffffu, (uint32_t)maxcell), o_ = min(mo.y, (uint32_t)(g.nvis - 1));
+                if (cell != (mo.x & 0xffffu) || o_ != mo.y) atomicAdd(&scalars[2], 1);  // (never, unless the array was overwritten)
+                mo.x = (mo.x & 0xffff0000u) | cell;
+                mo.y = o_;
+            }
             if (STAGE_VALS) v = svals[idx];
             if (STAGE_ORIG) o = sorig[idx];
         };
-        auto load_value = [&](const uint2 &mo, double2 &v) {  // (mo.y = orig, brought below nvis by the sorter)
+        auto load_value = [&](const uint2 &mo, double2 &v) {  // (mo.y = orig, below nvis: load_rec in the sorter, load_list)
             if (!DEGRID && !STAGE_VALS) v = (ABL & 8) ? make_double2(1.0, 2.0) : load_nt(vis + mo.y);
         };
         // first step of part `part` in the slice's step list, and how many steps it has
@@ -674,7 +719,7 @@ __global__ void __launch_bounds__(1024, 4) tile_grid_sorted_kernel(Geom g, const
         if (is_sorter && !solo) prepare(cur ^ 1);
         if (is_walker) {
             if ((ABL & 16) && wave == 0 && lane == 0) pt = clock64();
-            walk(cur, d.staged, first_slice);
+            walk(cur, d.staged, first_slice, d.v_lo);
             if ((ABL & 16) && wave == 0) GH_STAMP(4)  // wave 0's own accumulate walk
         }
         if (solo) prepare(cur ^ 1);
@@ -749,7 +794,7 @@ bool sorted_plan(const gridhip_ctx *ctx, const Geom &g, int block, int *nkeys, i
 }
 
 int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_t lds_bytes, int nkeys, int batch,
-                            int64_t n, const double *gcf, const double *vis, double *grid, bool degrid)
+                            int64_t n, const double *gcf, const double *vis, double *grid, bool degrid, bool may_keep)
 {
     Geom g = g_in;
     Tables t = tables_of(ctx, g);
@@ -786,8 +831,46 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
         }
     }
     const dim3 gr(nblk), bl(block);
+    // Kept lists (at the kernel): a plain call whose launch_bin has just left reusable state - the two-level pre-pass
+    // with pre-records, not captured, the context's own record array - and is the last writer (generation) sorts into
+    // the pre-records' block, one entry per record, instead of the scratch.  Not where no later call could trust them:
+    // "list_reuse" = 1, and "bin_reuse" = 1 (no verify sweep, so never a verdict).
+    const BinKeep &bk = ctx->keep;
+    const bool keeping = may_keep && !g.per_vis && ctx->list_hold == 0 && ctx->opt.list_reuse != 1 && ctx->opt.bin_reuse != 1 && bk.valid &&
+                         bk.key.gen == ctx->bin_gen && bk.key.recs == ctx->recs.ptr && bk.key.n == n && n > 0 &&
+                         ctx->recs_raw.bytes >= (size_t)n * sizeof(uint2);
+    const int istride = g.nrec / g.chunk + g.ntiles + 1;  // items a w-group's queue can hold (find_work_at)
+    uint2 *klist = nullptr;
+    int32_t *kstaged = nullptr;
+    int lists_valid = 0;
+    const ListKeep was = ctx->lists;
+    ListKeep now;
+    ctx->lists.valid = false;  // (until this launch is enqueued: `done` below)
+    if (keeping) {
+        GH_CHECK(ws_reserve(ctx, ctx->list_staged, (size_t)g.ngroups * istride * sizeof(int32_t)));
+        klist = (uint2 *)ctx->recs_raw.ptr;
+        kstaged = (int32_t *)ctx->list_staged.ptr;
+        now.valid = true;
+        now.gen = ctx->bin_gen;
+        now.nrec = n;
+        now.nkeys = nkeys, now.batch = batch, now.ngroups = g.ngroups, now.ntiles = g.ntiles;
+        now.Tx = g.Tx, now.Ty = g.Ty, now.ldw = g.ldw, now.Q = g.Q, now.W = g.W, now.P = g.P;
+        now.list = klist, now.staged = kstaged;
+        // the lists are the previous launch's, and this call's pre-pass is verifying the records they were sorted from:
+        // the verdict is on the device, the kernel combines the two
+        lists_valid = bk.verifying && was.valid && was.gen + 1 == now.gen && was.nrec == now.nrec && was.nkeys == now.nkeys &&
+                      was.batch == now.batch && was.ngroups == now.ngroups && was.ntiles == now.ntiles && was.Tx == now.Tx &&
+                      was.Ty == now.Ty && was.ldw == now.ldw && was.Q == now.Q && was.W == now.W && was.P == now.P &&
+                      was.list == now.list && was.staged == now.staged;
+        if (lists_valid) ++ctx->lists_reused;
+    }
+    auto done = [&]() {
+        ctx->lists = now;
+        return GRIDHIP_OK;
+    };
     // two sorted lists (current item, next item) per resident work-group: 8 B (meta, orig) per record, and for the aw
-    // gridders, whose sorter stages the values (gridding) or each record's orig (degrid), 16 B more
+    // gridders, whose sorter stages the values (gridding) or each record's orig (degrid), 16 B more (reserved in keeping
+    // mode as well: a later captured call runs in scratch mode and must not have to grow it)
     const size_t nlist = (size_t)nblk * 2 * batch, nvals = g.per_vis ? nlist : 0;
     GH_CHECK(ws_reserve(ctx, ctx->sorted, nvals * 16 + nlist * 8));
     double2 *svals = (double2 *)ctx->sorted.ptr;  // (not dereferenced when nothing is staged)
@@ -798,7 +881,7 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
         GH_CHECK(raise_lds(ctx, tile_grid_sorted_kernel<S_, D_, 0, false, B_>));                                 \
         hipLaunchKernelGGL((tile_grid_sorted_kernel<S_, D_, 0, false, B_>), gr, bl, lds_bytes, ctx->stream, g, recs, \
                            t.bin_start, t.work_start, (const double2 *)gcf, (double2 *)vis, grid, nkeys, batch, \
-                           t.scalars, svals, smo);                                                               \
+                           t.scalars, svals, smo, klist, kstaged, istride, lists_valid);                         \
     } while (0)
 #define GH_LAUNCH(S_, D_)                \
     do {                                 \
@@ -812,7 +895,7 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
         GH_CHECK(raise_lds(ctx, tile_grid_sorted_kernel<S_, D_, 0, true>));                                      \
         hipLaunchKernelGGL((tile_grid_sorted_kernel<S_, D_, 0, true>), gr, bl, lds_bytes, ctx->stream, g, recs,  \
                            t.bin_start, t.work_start, (const double2 *)gcf, (double2 *)vis, grid, nkeys, batch, \
-                           t.scalars, svals, smo);                                                               \
+                           t.scalars, svals, smo, klist, kstaged, istride, lists_valid);                         \
     } while (0)
 #define GH_LAUNCH_AW(S_)                 \
     do {                                 \
@@ -843,18 +926,18 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
         GH_CHECK(raise_lds(ctx, tile_grid_sorted_kernel<15, false, A_, false, true>));                           \
         hipLaunchKernelGGL((tile_grid_sorted_kernel<15, false, A_, false, true>), gr, bl, lds_bytes, ctx->stream, g, recs, \
                            t.bin_start, t.work_start, (const double2 *)gcf, (double2 *)vis, grid, nkeys, batch, \
-                           t.scalars, svals, smo);                                                               \
+                           t.scalars, svals, smo, klist, kstaged, istride, lists_valid);                         \
         GH_CHECK_HIP(ctx, hipGetLastError());                                                                    \
-        return GRIDHIP_OK;                                                                                       \
+        return done();                                                                                           \
     }
 #define GH_ABL(A_)                                                                                               \
     if (g.gh == 15 && !degrid && g.imoff == 0 && g.dbg == A_) {                                                  \
         GH_CHECK(raise_lds(ctx, tile_grid_sorted_kernel<15, false, A_>));                                        \
         hipLaunchKernelGGL((tile_grid_sorted_kernel<15, false, A_>), gr, bl, lds_bytes, ctx->stream, g, recs,    \
                            t.bin_start, t.work_start, (const double2 *)gcf, (double2 *)vis, grid, nkeys, batch, \
-                           t.scalars, svals, smo);                                                               \
+                           t.scalars, svals, smo, klist, kstaged, istride, lists_valid);                         \
         GH_CHECK_HIP(ctx, hipGetLastError());                                                                    \
-        return GRIDHIP_OK;                                                                                       \
+        return done();                                                                                           \
     }
 #ifdef GRIDHIP_TUNING  // ablation / phase-profile instantiations: tuning builds only (make tuning)
     GH_ABL(1) GH_ABL(2) GH_ABL(3) GH_ABL(4) GH_ABL(5) GH_ABL(7) GH_ABL(8) GH_ABL(15) GH_ABL(16) GH_ABL_BT(16)
@@ -875,7 +958,7 @@ int launch_tile_grid_sorted(gridhip_ctx *ctx, const Geom &g_in, int block, size_
 #undef GH_LAUNCH_AW
 #undef GH_LAUNCH_AW_
     GH_CHECK_HIP(ctx, hipGetLastError());
-    return GRIDHIP_OK;
+    return done();
 }
 
 }  // namespace gridhip
