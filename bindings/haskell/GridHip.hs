@@ -538,6 +538,33 @@ foreign import ccall unsafe "gridhip_apply_fringe_dev"
 -- int gridhip_fringe_tile(out)
 foreign import ccall unsafe "gridhip_fringe_tile"
   c_fringe_tile :: Ptr Int64 -> IO CInt
+-- int gridhip_tec_tables(ctx, F, T, tint, freq, tau0, dtau, Nd, tec0, dtec, Nm, tables)
+foreign import ccall unsafe "gridhip_tec_tables"
+  c_tec_tables :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_tec_tables_dev(ctx, F, T, tint, freq, tau0, dtau, Nd, tec0, dtec, Nm, tables)
+foreign import ccall unsafe "gridhip_tec_tables_dev"
+  c_tec_tables_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> CDouble -> CDouble -> Int64 -> Ptr CDouble -> IO CInt
+-- int gridhip_tec_search(ctx, B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, m0, m1, peaks, stats)
+foreign import ccall unsafe "gridhip_tec_search"
+  c_tec_search :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_tec_search_dev(ctx, B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, m0, m1, peaks, stats)
+foreign import ccall unsafe "gridhip_tec_search_dev"
+  c_tec_search_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_tecfit(ctx, B, T, F, A, I, Nd, Nm, tables, vis, model_vis, wt, a1, a2, rounds, wj, wm, min_count, min_coh2, refant, niter, tol, warm, sol, peaks, info, stats)
+foreign import ccall unsafe "gridhip_tecfit"
+  c_tecfit :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_tecfit_dev(ctx, B, T, F, A, I, Nd, Nm, tables, vis, model_vis, wt, a1, a2, rounds, wj, wm, min_count, min_coh2, refant, niter, tol, warm, sol, peaks, info, stats)
+foreign import ccall unsafe "gridhip_tecfit_dev"
+  c_tecfit_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Int64 -> Int64 -> Int64 -> CDouble -> CDouble -> Int64 -> Int64 -> CDouble -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_tec(ctx, B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_tec"
+  c_apply_tec :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_apply_tec_dev(ctx, B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in, vis_out, wt_out)
+foreign import ccall unsafe "gridhip_apply_tec_dev"
+  c_apply_tec_dev :: Ptr Ctx -> Int64 -> Int64 -> Int64 -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_tec_tile(out)
+foreign import ccall unsafe "gridhip_tec_tile"
+  c_tec_tile :: Ptr Int64 -> IO CInt
 -- int gridhip_dft_predict(ctx, C, comps, count, T, n, u, v, w, uv_stride, x, vis_sub, vis_out, stats)
 foreign import ccall unsafe "gridhip_dft_predict"
   c_dft_predict :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Int64 -> CInt -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt

@@ -1805,8 +1805,9 @@ int gridhip_contsub_tile(int64_t *out);
  * nothing back, never synchronise and can be captured.  Every call that sizes an array by I takes I from its caller and the
  * kernels compare it with the table's head.  Both forms run the same kernels and give the same bits, as do two runs and the
  * numpy restatement given the library's table.
- * NOT HERE: the order "tbf"; dispersive (TEC) delays; rates that scale with frequency; multi-band delays; a global
- * least-squares polish over all samples; an imager form; several devices. */
+ * NOT HERE: the order "tbf"; rates that scale with frequency; multi-band delays; a global least-squares polish over all
+ * samples; an imager form; several devices.  Dispersive (TEC) delays: the next section, "dispersive delay (TEC)
+ * calibration". */
 #define GRIDHIP_FRINGE_MAX_CHANNELS 1024
 #define GRIDHIP_FRINGE_MAX_DELAYS 4096
 #define GRIDHIP_FRINGE_MAX_TINT 256
@@ -1854,6 +1855,127 @@ int gridhip_apply_fringe_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, 
 /* out[3] = { delays per work-group, channels per staged chunk, rates per lane-pass } of the search kernel, so that a caller
  * (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
 int gridhip_fringe_tile(int64_t *out);
+
+/* ---- dispersive delay (TEC) calibration: a delay-TEC search per baseline, the fringe section's antenna fit, the apply step --
+ * The reference has no calibration: the semantics are defined here.  Below about 350 MHz the ionosphere puts a phase of
+ * -2 pi kappa dTEC / nu on every antenna, dTEC the differential total electron content in TEC units (1e16 electrons / m^2)
+ * and kappa = GRIDHIP_TEC_KAPPA = e^2 1e16 / (8 pi^2 eps0 m_e c) = 1.3445365934456e9 turns Hz per TEC unit (CODATA 2018;
+ * 2 pi kappa = 8.448e9 rad Hz).  That phase curves across the band: the linear delay of the section before cannot absorb it.
+ * This section inherits from "delay and rate calibration", by name: DATA, the PHASOR RECIPE with the x conj(c), x c and
+ * acc + e x rules, FLAGGED and BAD, the row of peaks, and the FORMS paragraph (tests/tec_ref.py restates every rule below).
+ * MODEL, per solution interval i:  psi_a(f) = arg g[i,a] + 2 pi tau[i,a] a_f + 2 pi tec[i,a] c_f, with
+ *     a_f = freq[f] - nu0, nu0 as in the fringe section;
+ *     z_f = -(kappa * (1 / freq[f] - 1 / nu0)), every operation rounded: the dispersive coordinate, 0 at nu0;
+ *     s   = (sum_f a_f * z_f) / (sum_f a_f * a_f), the products rounded, both sums f ascending from +0.0; s = 0 when the
+ *           denominator is not > 0;
+ *     c_f = z_f - s * a_f (the product rounded): z with its linear part taken out, sum_f a_f c_f = 0 to rounding.
+ *   THE TEC AXIS IS THE ORTHOGONALISED ONE.  Along the raw z_f the delay and TEC axes are almost collinear and the per-axis
+ *   parabola with windowed later rounds stalls on the ridge; along c_f it converges by a factor of about
+ *   12 per round.  The delay this section reports is therefore the EFFECTIVE delay tau_eff = tau_clock + s * tec, and the
+ *   table carries s so that a caller can separate the clock: tau_clock = tau - s * tec (gridhip.tec_clock).
+ *   A solution `sol` is [I][A][4] = { tau, tec, Re g, Im g } with |g| = 1.  There is no time axis: a step only selects its
+ *   interval.
+ *
+ * gridhip_tec_tables(F, T, tint, freq, tau0, dtau, Nd, tec0, dtec, Nm, tables) makes the table the others read,
+ * GRIDHIP_TEC_TABLE_DOUBLES(F, Nd, Nm) doubles.  It takes no time array.
+ *   head[16] = { valid, F, T, tint (after the 0 -> T rule), I, Nd, Nm, tau0, dtau, tec0, dtec, nu0, s, kappa, 0, 0 }
+ *   Ef[F][Nd] complex, j fastest: conj ph(tau_j, a_f), tau_j = tau0 + j * dtau, as in the fringe table
+ *   Em[F][Nm] complex, m fastest: conj ph(tec_m, c_f), tec_m = tec0 + m * dtec (the product rounded, then added)
+ *   a[F] = a_f;  c[F] = c_f (what the derotation and the apply step read)
+ *   valid is judged on the device by one work-group: every freq finite and > 0, tau0, dtau, tec0, dtec, nu0 and s finite,
+ *   dtau > 0 and dtec > 0; otherwise valid = 0, nu0 = s = 0 and everything behind the head is zeros.
+ *   GRIDHIP_EINVAL: F outside 1..1024, Nd outside 1..4096, Nm outside 1..1024, T < 1, tint outside 0..T (0: T; there is no
+ *   cap of 256 - time is summed before the search), a NULL pointer, arrays that overlap.  GRIDHIP_EUNSUPPORTED: T above 2^20.
+ *
+ * gridhip_tec_search(B, T, F, A, I, tables, vis, model_vis or NULL, wt or NULL, a1, a2, sol or NULL, j0, j1, m0, m1,
+ * peaks[B][I][12], stats[8]) - the hot path.  I is the table's, as in the fringe search.
+ *   1. Per sample X as in the fringe search.  With sol: d_b = g_p conj(g_q) (the x conj(c) rule) and Dfm[f] = ph(tau_p -
+ *      tau_q, a_f) ph(tec_p - tec_q, c_f) (the x c rule, the delay phasor first), made once per (baseline, interval);
+ *      X' = (X conj(d_b)) conj(Dfm[f]).  Without sol X' = X, no product.
+ *   2. Xbar[f] = sum_t X'[t][f], t ascending over the interval from (0, 0), plain rounded sums per component; a flagged
+ *      sample adds (0, 0).
+ *   3. S[j][m] = sum_f Ef[f][j] (Em[f][m] Xbar[f]) for j in [j0, j1), m in [m0, m1): the inner product by the x c rule with
+ *      x = Em and c = Xbar, then the acc + e x rule with e = Ef, f ascending from (0, 0).  P = re * re + im * im.
+ *   4. The peak (j*, m*) is the largest P, ties to the lowest j, then the lowest m; a NaN is never selected.  The fringe
+ *      section's parabola per axis where the peak is interior: tau_b along j at m*, tec_b along m at j*.
+ *   5. Energy N (of the unflagged X' per sample: e_t = sum_f, then N = sum_t), n_used, coh2 = P* / (n_used N), z, the codes
+ *      and stats are exactly the fringe search's.
+ *   peaks row = { j*, m*, P*, tau_b, tec_b, Re z, Im z, coh2, n_used, N, code, 0 }; a row whose code is not 0 is the fringe
+ *   search's.  An all-zero baseline is ok: the tie goes to (j0, m0), coh2 = 0.  stats[7] = 1 and peaks left as it is when
+ *   the head has valid = 0, its F, T or I differ from the arguments, or the cells do not lie in its grid.
+ *   GRIDHIP_EINVAL: B, T < 1, F outside 1..1024, A < 2, I outside 1..T, cells not 0 <= j0 < j1 <= 4096, 0 <= m0 < m1 <= 1024,
+ *   a NULL tables, vis, a1, a2, peaks or stats, a vis or model_vis that is not 16-byte aligned, an output overlapping an
+ *   input or the other output.  GRIDHIP_EUNSUPPORTED: B above 2^24, T above 2^20, A above 1024, B T above 2^31 - 1, more
+ *   than 2^31 - 1 tiles.
+ *   The kernels.  A work-group owns one (baseline, interval) and a tile of tec_tile()[0] delays x tec_tile()[1] TEC cells.
+ *   It forms Xbar once in LDS (16 KB), the sample rows read coalesced along f and derotated on the way, and stages Ef and
+ *   Em through LDS in chunks of tec_tile()[2] channels (a tile of fewer delays stages as many more channels at a time as
+ *   its narrower rows leave room for, up to 32: the sums and their order are the same).  A lane keeps two delays x the tile's TEC cells (1, 2, 4 or 8: a
+ *   grid of three TEC cells does not pay for eight) in registers, so one Em Xbar product feeds both delays and one Ef entry
+ *   every TEC cell; each accumulator adds its channels in order, unfused.  One candidate per tile.  A second kernel, one wave
+ *   per (baseline, interval), takes the best candidate, recomputes the five powers the parabolas need by the same ordered
+ *   sums - the bits do not depend on the tile borders - and forms the energy and the row.  No matrix instruction
+ *   (gridhip_rmsynth's argument); 52 KB of LDS per work-group; integer atomics only, for the stats.
+ *
+ * THE ANTENNA FIT IS gridhip_fringe_solve, UNCHANGED.  The delay and TEC values sit in the slots of the row the fringe solve
+ *   reads as delay and rate, and it treats the two identically, as linear differences tau_p - tau_q and tec_p - tec_q: there
+ *   is no second solver.  Its stats name rms_r what is rms_tec here.
+ *
+ * gridhip_tecfit(B, T, F, A, I, Nd, Nm, tables, vis, model_vis, wt, a1, a2, rounds, wj, wm, min_count, min_coh2, refant,
+ * niter, tol, warm, sol, peaks, info, stats) is the driver: gridhip_fringefit's argument list and stats with Nm for Nr, wm
+ *   for wk, and rms_tec / dtec in place of the rate entry.  Round 0 searches the whole grid (derotating by sol when warm);
+ *   the rounds 1 .. rounds - 1 (rounds in 1..4) derotate by the current sol and search the cells within (wj, wm) of the grid's
+ *   zero, jz = rint(-tau0 / dtau) and mz = rint(-tec0 / dtec) clamped into the grid.  Every search is followed by
+ *   gridhip_fringe_solve's kernels, which accumulate into sol.  stats = { sweeps of the last solve, flagged samples, BAD,
+ *   empty, unsolved antennas, rms_tau / dtau, rms_tec / dtec, invalid }.  A fixed number of launches (6 per round, 1 or 2
+ *   more), nothing read back: the _dev form can be captured.  GRIDHIP_EINVAL / EUNSUPPORTED: those of the search and the
+ *   solve; I outside 1..T, Nd, Nm out of range, rounds outside 1..4, wj outside 0..4096, wm outside 0..1024, warm not 0 or 1.
+ *
+ * gridhip_apply_tec(B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in or NULL, vis_out, wt_out or NULL) follows
+ *   gridhip_apply_fringe's rules - the weight copy, +0.0 for a non-finite row or an antenna out of range, in place allowed,
+ *   a head that does not fit F, T and I leaves the outputs unwritten - and reads only the head, a[F] and c[F] of a table
+ *   (any Nd, Nm).  The phasor is D = d_b Dfm[f]: inverse 1, vis_out = (vis_in conj(d_b)) conj(Dfm[f]); inverse 0,
+ *   vis_out = (vis_in d_b) Dfm[f].  GRIDHIP_EINVAL / EUNSUPPORTED: those of gridhip_apply_fringe.
+ *
+ * NOT HERE: a joint rate axis (run gridhip_fringefit for the rates first); the order "tbf"; higher-order ionospheric terms;
+ * Faraday rotation; a direction-dependent TEC screen; an imager form; several devices. */
+#define GRIDHIP_TEC_KAPPA 1.3445365934456e9
+#define GRIDHIP_TEC_MAX_CHANNELS 1024
+#define GRIDHIP_TEC_MAX_DELAYS 4096
+#define GRIDHIP_TEC_MAX_CELLS 1024
+#define GRIDHIP_TEC_MAX_ROUNDS 4
+#define GRIDHIP_TEC_HEAD 16
+#define GRIDHIP_TEC_PEAK 12
+#define GRIDHIP_TEC_STATS 8
+#define GRIDHIP_TEC_TABLE_DOUBLES(F, Nd, Nm) (16 + 2 * (F) * (Nd) + 2 * (F) * (Nm) + 2 * (F))
+int gridhip_tec_tables(gridhip_ctx *ctx, int64_t F, int64_t T, int64_t tint, const double *freq, double tau0, double dtau,
+                       int64_t Nd, double tec0, double dtec, int64_t Nm, double *tables);
+int gridhip_tec_tables_dev(gridhip_ctx *ctx, int64_t F, int64_t T, int64_t tint, const double *freq, double tau0, double dtau,
+                           int64_t Nd, double tec0, double dtec, int64_t Nm, double *tables);
+int gridhip_tec_search(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                       const double *vis, const double *model_vis, const double *wt, const int64_t *a1, const int64_t *a2,
+                       const double *sol, int64_t j0, int64_t j1, int64_t m0, int64_t m1, double *peaks, double *stats);
+int gridhip_tec_search_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                           const double *vis, const double *model_vis, const double *wt, const int64_t *a1, const int64_t *a2,
+                           const double *sol, int64_t j0, int64_t j1, int64_t m0, int64_t m1, double *peaks, double *stats);
+int gridhip_tecfit(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, int64_t Nd, int64_t Nm,
+                   const double *tables, const double *vis, const double *model_vis, const double *wt, const int64_t *a1,
+                   const int64_t *a2, int64_t rounds, int64_t wj, int64_t wm, double min_count, double min_coh2, int64_t refant,
+                   int64_t niter, double tol, int warm, double *sol, double *peaks, double *info, double *stats);
+int gridhip_tecfit_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, int64_t Nd, int64_t Nm,
+                       const double *tables, const double *vis, const double *model_vis, const double *wt, const int64_t *a1,
+                       const int64_t *a2, int64_t rounds, int64_t wj, int64_t wm, double min_count, double min_coh2,
+                       int64_t refant, int64_t niter, double tol, int warm, double *sol, double *peaks, double *info,
+                       double *stats);
+int gridhip_apply_tec(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                      const double *sol, const int64_t *a1, const int64_t *a2, int inverse, const double *vis_in,
+                      const double *wt_in, double *vis_out, double *wt_out);
+int gridhip_apply_tec_dev(gridhip_ctx *ctx, int64_t B, int64_t T, int64_t F, int64_t A, int64_t I, const double *tables,
+                          const double *sol, const int64_t *a1, const int64_t *a2, int inverse, const double *vis_in,
+                          const double *wt_in, double *vis_out, double *wt_out);
+/* out[3] = { delays per work-group tile, TEC cells per tile, channels per staged chunk } of the search kernel, so that a
+ * caller (a test) can stand either side of its edges; GRIDHIP_EINVAL for a NULL */
+int gridhip_tec_tile(int64_t *out);
 
 /* ---- direct-Fourier prediction of a sky-model component list, and a model image as such a list ----------------------------
  * The reference has no such function: the semantics are defined here.  Every other prediction goes through a model image

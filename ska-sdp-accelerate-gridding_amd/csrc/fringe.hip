@@ -27,6 +27,7 @@
 // in chunks of 256, once to count and once to fill, which leaves every antenna the list of its used baselines in ascending
 // order in scratch; a Jacobi sweep reads only an antenna's own list, in that order: no floating-point atomic.
 #include "common.h"
+#include "fringe_solve.h"
 #include "imaging.h"
 
 #pragma clang fp contract(off)
@@ -472,25 +473,7 @@ __global__ void fr_search_stats_kernel(FrSearch a, double *__restrict__ stats)
     }
 }
 
-// one end of a used baseline as its antenna sees it: side 0, the antenna is p and `other` is q; side 1 the reverse
-struct FrEdge {
-    double w, tau, r, zr, zi;
-    int other, side;
-};
-
-struct FrSolve {
-    int B, I, A;
-    const int64_t *a1, *a2;
-    const double *peaks;
-    double min_count, min_coh2;
-    int refant, niter;
-    double tol;
-    double *sol, *info;
-    double *w;     // [I][B]: the baseline weights
-    double *part;  // [I][8]: what an interval adds to the stats
-    FrEdge *edges;  // [I][2 B]: the antennas' lists of their used baselines
-    const double *gate;  // the driver: the stats of the search before; [7] set: that search did not run, nor does the solve
-};
+// (FrEdge and FrSolve: fringe_solve.h)
 
 // a chunk of FR_THREADS baselines of interval i into LDS: the pair, the weight (0 beyond B) and, with `rows`, the values
 __device__ __forceinline__ void fr_solve_chunk(const FrSolve &a, int i, int c0, const double *w, bool rows, int *cp, int *cq,
@@ -1026,6 +1009,20 @@ int fr_apply_any(gridhip_ctx *ctx, bool dev, int64_t B, int64_t T, int64_t F, in
 }
 
 }  // namespace
+
+// what fringe_solve.h declares: the solve as another driver (tec.hip) enqueues it
+bool fringe_solve_args_ok(int64_t B, int64_t I, int64_t A, double min_count, double min_coh2, int64_t refant, int64_t niter,
+                          double tol)
+{
+    return fr_solve_args_ok(B, I, A, min_count, min_coh2, refant, niter, tol);
+}
+
+void fringe_solve_enqueue(gridhip_ctx *ctx, const FrSolve &a, double *stats) { fr_solve_launch(ctx, a, stats); }
+
+void fringe_init_sol_enqueue(gridhip_ctx *ctx, int64_t n, double *sol)
+{
+    hipLaunchKernelGGL(fr_init_sol_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, sol);
+}
 
 }  // namespace gridhip
 

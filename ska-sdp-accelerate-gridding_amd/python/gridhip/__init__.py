@@ -41,11 +41,12 @@ from ._marshal import RM_MAPS, rm_clean_scalars, rm_cube, rm_images, rm_table_ar
 from ._marshal import contsub_args
 from ._marshal import FRINGE_MAX_DELAYS, FRINGE_MAX_RATES, FRINGE_PEAK, fringe_cube, fringe_intervals, fringe_sol
 from ._marshal import fringe_solve_scalars, fringe_table_args, fringe_table_doubles, fringe_table_of
+from ._marshal import TEC_HEAD, TEC_KAPPA, TEC_MAX_CELLS, TEC_MAX_DELAYS, TEC_PEAK, tec_table_args, tec_table_doubles, tec_table_of
 
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
            "waterfall_layout", "rm_tile", "faraday_grid", "contsub_tile", "channel_coordinate",
-           "fringe_tile", "fringe_grid"]
+           "fringe_tile", "fringe_grid", "tec_tile", "tec_grid", "tec_clock", "tec_coordinates", "TEC_KAPPA"]
 
 
 class Context(Handle):
@@ -972,6 +973,91 @@ class Context(Handle):
         self._call(be, "apply_fringe", B, T, F, A, I, tables, sol, a1, a2, int(bool(inverse)), vis, wt, out, weights_out)
         return out, weights_out
 
+    def tec_tables(self, freq, ntime, tint, delays, tecs):
+        """The table the delay-TEC search and its apply step read (gridhip_tec_tables[_dev]; include/gridhip.h, "dispersive
+        delay (TEC) calibration"): freq (F <= 1024 channels, Hz, every one > 0), ntime = T time steps of the cube and tint
+        of them per solution interval (0: all; no other cap), delays = (tau0, dtau, Nd <= 4096) and tecs = (tec0, dtec,
+        Nm <= 1024) in TEC units (gridhip.tec_grid proposes both).  Returns one float64 array: the head [valid, F, T, tint, I,
+        Nd, Nm, tau0, dtau, tec0, dtec, nu0, s, kappa, 0, 0], the phasors Ef[F][Nd] and Em[F][Nm], a_f = nu_f - nu0 and the
+        orthogonalised dispersive coordinate c_f = z_f - s a_f.  freq is judged on the device: valid = 0 is what every
+        reader reports.  numpy in gives numpy out; torch cuda tensors take the device form on torch's stream."""
+        be = backend(freq)
+        args = tec_table_args(be, freq, ntime, tint, delays, tecs)
+        tables = be.empty(tec_table_doubles(args[0], args[6], args[9]), be.f64, args[3])
+        self._call(be, "tec_tables", *args, tables)
+        return tables
+
+    def tec_search(self, vis, tables, a1, a2, nant, tint, delays, tecs, model_vis=None, weights=None, sol=None, cells=None,
+                   peaks=None):
+        """The delay-TEC search (gridhip_tec_search[_dev]): per baseline of the [B, T, F] cube `vis` and solution interval,
+        the delay and TEC cell at which sum_f Ef[f][j] Em[f][m] Xbar[f] has the largest power, Xbar the sum over the
+        interval of X' = weights * vis * conj(model_vis), derotated by `sol` ([I, nant, 4] = tau, tec, Re g, Im g) where
+        one is given.  Arguments, cells = (j0, j1, m0, m1), the returned (peaks [B, I, 12], stats), the codes and the
+        refusals are Context.fringe_search's, with the TEC axis for the rate axis: a row is [j*, m*, P*, tau_b, tec_b,
+        Re z, Im z, coh2, n_used, N, code, 0].  The delay is the effective one, tau_clock + s tec (gridhip.tec_clock).  The
+        same bits on every run and as tests/tec_ref.py given the table."""
+        be = backend(vis)
+        B, T, F, A, vis, model_vis, wt, a1, a2 = fringe_cube(be, vis, model_vis, weights, a1, a2, nant)
+        tables, I = tec_table_of(be, tables, F, T, tint)
+        Nd, Nm = int(delays[2]), int(tecs[2])
+        if int(tables.shape[0]) != tec_table_doubles(F, Nd, Nm):
+            raise ValueError(f"tables of {int(tables.shape[0])} values do not belong to this cube and these axes")
+        try:
+            j0, j1, m0, m1 = (0, Nd, 0, Nm) if cells is None else (int(v) for v in cells)
+        except (TypeError, ValueError):
+            raise ValueError("cells must be (j0, j1, m0, m1)") from None
+        if not (0 <= j0 < j1 <= Nd and 0 <= m0 < m1 <= Nm):
+            raise ValueError("cells must be half-open ranges 0 <= j0 < j1 and 0 <= m0 < m1 inside the grid")
+        sol = fringe_sol(be, sol, I, A, vis)
+        peaks = result_array(be, peaks, be.f64, (B, I, TEC_PEAK), "peaks", vis)
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "tec_search", B, T, F, A, I, tables, vis, model_vis, wt, a1, a2, sol, j0, j1, m0, m1, peaks, stats)
+        return peaks, stats
+
+    def tecfit(self, vis, tables, a1, a2, nant, tint, delays, tecs, model_vis=None, weights=None, sol=None, rounds=3,
+               window=(2, 2), min_count=0, min_coh2=0.0, refant=0, niter=50, tol=0.0):
+        """Dispersive delay calibration (gridhip_tecfit[_dev]): `rounds` (1 .. 4) times a delay-TEC search followed by the
+        antenna-based fit of Context.fringe_solve, which serves as it is.  Round 0 searches the whole grid - delays, tecs
+        and tint as given to Context.tec_tables - against `sol` where one is given (a warm start, updated in place) or
+        zero; the later rounds derotate by the current solution and search only the cells within window = (wj, wm) of the
+        grid's zero.  Returns (sol [I, nant, 4] = tau_eff, tec, Re g, Im g per interval and antenna, peaks of the last
+        round, info, stats = [sweeps of the last solve, flagged samples, bad, empty, unsolved antennas, weighted rms of the
+        last round's tau_b and tec_b in cells, invalid]).  Correct data with Context.apply_tec(sol, ...).  A fixed number
+        of launches, nothing read back: with cuda tensors the call can be captured into a graph."""
+        be = backend(vis)
+        B, T, F, A, vis, model_vis, wt, a1, a2 = fringe_cube(be, vis, model_vis, weights, a1, a2, nant)
+        tables, I = tec_table_of(be, tables, F, T, tint)
+        Nd, Nm = int(delays[2]), int(tecs[2])
+        if int(tables.shape[0]) != tec_table_doubles(F, Nd, Nm):
+            raise ValueError(f"tables of {int(tables.shape[0])} values do not belong to this cube and these axes")
+        rounds, (wj, wm) = int(rounds), (int(v) for v in window)
+        if not 1 <= rounds <= 4 or not (0 <= wj <= TEC_MAX_DELAYS and 0 <= wm <= TEC_MAX_CELLS):
+            raise ValueError("rounds must be in 1 .. 4 and window a pair of cell counts >= 0")
+        scalars = fringe_solve_scalars(min_count, min_coh2, refant, niter, tol, A)
+        warm = int(sol is not None)
+        sol = fringe_sol(be, sol, I, A, vis) if warm else be.empty((I, A, 4), be.f64, vis)
+        peaks, info = be.empty((B, I, TEC_PEAK), be.f64, vis), be.empty((I, A), be.f64, vis)
+        stats = be.empty(8, be.f64, vis)
+        self._call(be, "tecfit", B, T, F, A, I, Nd, Nm, tables, vis, model_vis, wt, a1, a2, rounds, wj, wm, *scalars, warm, sol,
+                   peaks, info, stats)
+        return sol, peaks, info, stats
+
+    def apply_tec(self, sol, tables, vis, a1, a2, tint, *, inverse=True, weights=None, out=None, weights_out=None):
+        """Apply a delay and TEC solution to a [B, T, F] cube (gridhip_apply_tec[_dev]).  inverse=True corrects data: vis
+        conj(D) with D = g_p conj(g_q) exp(2 pi i ((tau_p - tau_q) a_f + (tec_p - tec_q) c_f)); inverse=False corrupts a
+        model: vis D.  Weights, non-finite rows, out and weights_out, in place and a table of another tint: as
+        Context.apply_fringe.  Only the head, a_f and c_f of the table are read: a table of any search axes over the same
+        freq, ntime and tint."""
+        be = backend(vis)
+        nant = int(sol.shape[1]) if hasattr(sol, "shape") and len(sol.shape) == 3 else 0
+        B, T, F, A, vis, _, wt, a1, a2 = fringe_cube(be, vis, None, weights, a1, a2, nant)
+        tables, I = tec_table_of(be, tables, F, T, tint)
+        sol = fringe_sol(be, sol, I, A, vis)
+        out = result_array(be, out, be.c128, (B, T, F), "out", vis)
+        weights_out = result_array(be, weights_out, be.f64, (B, T, F), "weights_out", vis)
+        self._call(be, "apply_tec", B, T, F, A, I, tables, sol, a1, a2, int(bool(inverse)), vis, wt, out, weights_out)
+        return out, weights_out
+
     def dft_predict(self, uvw, comps, x=None, count=None, vis_sub=None, out=None, terms=1, stats=False):
         """The exact visibilities of a component list (gridhip_dft_predict[_dev]; include/gridhip.h, "direct-Fourier
         prediction"): sum_c S_c(x) E_c(u, v) exp(-2 pi i (u l_c + v m_c + w (n_c - 1))), or vis_sub minus that.  uvw
@@ -1849,6 +1935,65 @@ def fringe_grid(freq, time, tint, pad=4):
                          f"{FRINGE_MAX_RATES}): lower pad")
     dtau, drate = 1.0 / (pad * F * df), 1.0 / (pad * tint * dt)
     return (-(Nd // 2) * dtau, dtau, Nd), (-(Nr // 2) * drate, drate, Nr)
+
+
+def tec_tile():
+    """(delays per work-group tile, TEC cells per tile, channels per staged chunk) of Context.tec_search's kernel
+    (gridhip_tec_tile)."""
+    out = (C.c_int64 * 3)()
+    rc = _lib.load().gridhip_tec_tile(out)
+    if rc != 0:
+        raise GridHipError(rc, "gridhip_tec_tile")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def tec_coordinates(freq):
+    """(a_f, c_f, s, nu0) of include/gridhip.h, "dispersive delay (TEC) calibration", in plain numpy: a_f = nu_f - nu0, the
+    orthogonalised dispersive coordinate c_f = z_f - s a_f with z_f = -kappa (1 / nu_f - 1 / nu0), and the slope s that was
+    taken out.  Host code for choosing a grid; the table's own values are made on the device."""
+    import numpy as np
+    freq = np.asarray(freq, dtype=np.float64).reshape(-1)
+    if freq.size < 1 or not (np.isfinite(freq).all() and (freq > 0.0).all()):
+        raise ValueError("freq must hold at least one channel, every one finite and > 0")
+    nu0 = freq[0] + 0.5 * (freq[-1] - freq[0])
+    a, z = freq - nu0, -(TEC_KAPPA * (1.0 / freq - 1.0 / nu0))
+    den = float((a * a).sum())
+    s = float((a * z).sum()) / den if den > 0.0 else 0.0
+    return a, z - s * a, s, nu0
+
+
+def tec_grid(freq, tec_max, pad=4):
+    """The delay and TEC cells a band supports: returns (tau0, dtau, Nd), (tec0, dtec, Nm), both centred on 0.  The delay
+    axis is gridhip.fringe_grid's: Nd = pad * F cells of 1 / (pad * F * median channel step).  dtec = 1 / (pad * (max c_f -
+    min c_f)) TEC units - `pad` cells per resolution element of the orthogonalised dispersive coordinate - and Nm = 2 *
+    ceil(tec_max / dtec) + 1 cells, enough for |tec| <= tec_max.  Pure host code: Context.tec_tables takes the two triples."""
+    import math
+    import numpy as np
+    freq, pad, tec_max = np.asarray(freq, dtype=np.float64).reshape(-1), int(pad), float(tec_max)
+    F = freq.size
+    _, c, _, _ = tec_coordinates(freq)
+    if pad < 1 or not (math.isfinite(tec_max) and tec_max >= 0.0):
+        raise ValueError("pad must be >= 1 and tec_max finite and >= 0")
+    df = float(np.median(np.abs(np.diff(freq)))) if F > 1 else 1.0
+    span = float(c.max() - c.min())
+    if not (np.isfinite(df) and df > 0.0 and np.isfinite(span) and span > 0.0):
+        raise ValueError("the band must hold at least three distinct channels: it has no dispersive curvature otherwise")
+    Nd, dtau, dtec = pad * F, 1.0 / (pad * F * df), 1.0 / (pad * span)
+    Nm = 2 * int(math.ceil(tec_max / dtec)) + 1
+    if Nd > TEC_MAX_DELAYS or Nm > TEC_MAX_CELLS:
+        raise ValueError(f"pad * F = {Nd} delays (at most {TEC_MAX_DELAYS}) or {Nm} TEC cells (at most {TEC_MAX_CELLS}): "
+                         f"lower pad or tec_max")
+    return (-(Nd // 2) * dtau, dtau, Nd), (-(Nm // 2) * dtec, dtec, Nm)
+
+
+def tec_clock(sol, tables):
+    """The non-dispersive (clock) delays of a delay-TEC solution: tau_clock = tau_eff - s * tec, [I, nant], with s from the
+    head of the table.  Host code: numpy in and out (copy a cuda solution and at least the table's head to the host first)."""
+    import numpy as np
+    sol, head = np.asarray(sol, dtype=np.float64), np.asarray(tables[:TEC_HEAD], dtype=np.float64)
+    if sol.ndim != 3 or sol.shape[2] != 4 or head.shape != (TEC_HEAD,) or head[0] != 1.0:
+        raise ValueError("sol must be [I, nant, 4] and tables a valid table of Context.tec_tables")
+    return sol[:, :, 0] - head[12] * sol[:, :, 1]
 
 
 def channel_coordinate(freq):

@@ -81,6 +81,8 @@ _FRINGEFIT = [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64
               C.c_double, ci, vp, vp, vp, vp]
 # B, T, F, A, I, tables, sol, a1, a2, inverse, vis_in, wt_in, vis_out, wt_out
 _APPLY_FRINGE = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+# F, T, tint, freq, tau0, dtau, Nd, tec0, dtec, Nm, tables (the search, the driver and the apply step: the fringe lists)
+_TEC_TABLES = [vp, i64, i64, i64, vp, C.c_double, C.c_double, i64, C.c_double, C.c_double, i64, vp]
 _DFT_PREDICT = [vp, i64, vp, vp, ci, i64, vp, vp, vp, i64, vp, vp, vp, vp]
 _COMPONENTS = [vp, C.c_double, i64, ci, vp, i64, vp, vp]
 # border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise, peak_frac, min_cells, beam, correct, max_c, comps, info, count, stats
@@ -263,6 +265,15 @@ SIGNATURES = {
     "gridhip_apply_fringe": (ci, _APPLY_FRINGE),
     "gridhip_apply_fringe_dev": (ci, _APPLY_FRINGE),
     "gridhip_fringe_tile": (ci, [C.POINTER(i64)]),
+    "gridhip_tec_tables": (ci, _TEC_TABLES),
+    "gridhip_tec_tables_dev": (ci, _TEC_TABLES),
+    "gridhip_tec_search": (ci, _FRINGE_SEARCH),
+    "gridhip_tec_search_dev": (ci, _FRINGE_SEARCH),
+    "gridhip_tecfit": (ci, _FRINGEFIT),
+    "gridhip_tecfit_dev": (ci, _FRINGEFIT),
+    "gridhip_apply_tec": (ci, _APPLY_FRINGE),
+    "gridhip_apply_tec_dev": (ci, _APPLY_FRINGE),
+    "gridhip_tec_tile": (ci, [C.POINTER(i64)]),
     "gridhip_dft_predict": (ci, _DFT_PREDICT),
     "gridhip_dft_predict_dev": (ci, _DFT_PREDICT),
     "gridhip_components_from_image": (ci, _COMPONENTS),

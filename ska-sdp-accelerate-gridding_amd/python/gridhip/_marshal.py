@@ -833,6 +833,47 @@ def fringe_solve_scalars(min_count, min_coh2, refant, niter, tol, A):
     return min_count, min_coh2, refant, niter, tol
 
 
+TEC_KAPPA = 1.3445365934456e9  # GRIDHIP_TEC_KAPPA: turns Hz per TEC unit
+TEC_HEAD, TEC_PEAK, TEC_MAX_CHANNELS, TEC_MAX_DELAYS, TEC_MAX_CELLS = 16, 12, 1024, 4096, 1024  # GRIDHIP_TEC_*
+
+
+def tec_table_doubles(F, Nd, Nm):
+    """GRIDHIP_TEC_TABLE_DOUBLES(F, Nd, Nm): head, Ef[F][Nd] and Em[F][Nm] complex, a[F], c[F]"""
+    return TEC_HEAD + 2 * F * Nd + 2 * F * Nm + 2 * F
+
+
+def tec_intervals(T, tint):
+    """tint after the 0 -> T rule, and I = ceil(T / tint); no cap but T: time is summed before the search"""
+    tint = int(tint)
+    tint = T if tint == 0 else tint
+    if not 1 <= tint <= T:
+        raise ValueError(f"tint must be in 1 .. {T} (0: all {T} time steps), not {tint}")
+    return tint, (T + tint - 1) // tint
+
+
+def tec_table_args(be, freq, ntime, tint, delays, tecs):
+    """F, T, tint, freq, tau0, dtau, Nd, tec0, dtec, Nm as gridhip_tec_tables takes them"""
+    if freq is None:
+        raise ValueError(f"freq must be a {be.array}")
+    freq = stream_array(be, freq, be.f64, -1, "freq")
+    F, T = int(freq.shape[0]), int(ntime)
+    if not 1 <= F <= TEC_MAX_CHANNELS or T < 1:
+        raise ValueError(f"freq must hold 1 .. {TEC_MAX_CHANNELS} channels and ntime must be at least 1")
+    tint, _ = tec_intervals(T, tint)
+    return (F, T, tint, freq, *fringe_axis(delays, TEC_MAX_DELAYS, "delays"), *fringe_axis(tecs, TEC_MAX_CELLS, "tecs"))
+
+
+def tec_table_of(be, tables, F, T, tint):
+    """tables, I of a TEC table that belongs to a cube of T time steps and F channels (fringe_table_of's rules)"""
+    if tables is None or be is not backend(tables) or not be.ok(tables, be.f64) or len(tables.shape) != 1 or \
+            int(tables.shape[0]) < TEC_HEAD:
+        raise ValueError(f"tables must be a one-dimensional float64 {be.array} (Context.tec_tables)")
+    tint, I = tec_intervals(T, tint)
+    if be is HOST and tables[0] == 1.0 and (tables[1], tables[2]) == (F, T) and (tables[3], tables[4]) != (tint, I):
+        raise ValueError(f"tables were made with tint = {int(tables[3])} ({int(tables[4])} intervals), not {tint} ({I})")
+    return tables, I
+
+
 CONTSUB_MAX_CHANNELS, CONTSUB_MAX_DEGREE, CONTSUB_ROWINFO, CONTSUB_MAX_ROUNDS = 4096, 3, 4, 4  # GRIDHIP_CONTSUB_*
 
 
