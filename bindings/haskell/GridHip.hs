@@ -349,6 +349,15 @@ foreign import ccall unsafe "gridhip_imager_deconvolve_automask_dev"
 -- int gridhip_imager_msdeconvolve_automask_dev(imager, vis, model, image, nmajor, S, scales, bias, gain, threshold, niter, border, patch, mask, nsigma, peak_frac_clean, absolute, thr_hi, thr_lo, nsigma_hi, nsigma_lo, peak_frac, min_cells, grow, stats, istats, astats)
 foreign import ccall unsafe "gridhip_imager_msdeconvolve_automask_dev"
   c_imager_msdeconvolve_automask_dev :: Ptr Imager -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Int64 -> Ptr Word8 -> CDouble -> CDouble -> CInt -> CDouble -> CDouble -> CDouble -> CDouble -> CDouble -> Int64 -> Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int64_t gridhip_noise_map_nodes(N, border, step)
+foreign import ccall unsafe "gridhip_noise_map_nodes"
+  c_noise_map_nodes :: Int64 -> Int64 -> Int64 -> IO Int64
+-- int gridhip_noise_map(ctx, N, image, mask, exclude, border, step, half, kappa, nclip, min_count, mode, nodes, background, rms, out, stats)
+foreign import ccall unsafe "gridhip_noise_map"
+  c_noise_map :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Word8 -> CInt -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+-- int gridhip_noise_map_dev(ctx, N, image, mask, exclude, border, step, half, kappa, nclip, min_count, mode, nodes, background, rms, out, stats)
+foreign import ccall unsafe "gridhip_noise_map_dev"
+  c_noise_map_dev :: Ptr Ctx -> Int64 -> Ptr CDouble -> Ptr Word8 -> CInt -> Int64 -> Int64 -> Int64 -> CDouble -> Int64 -> Int64 -> CInt -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 -- int gridhip_fit_beam(ctx, N, psf, window, cut, beam)
 foreign import ccall unsafe "gridhip_fit_beam"
   c_fit_beam :: Ptr Ctx -> Int64 -> Ptr CDouble -> Int64 -> CDouble -> Ptr CDouble -> IO CInt

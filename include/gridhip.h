@@ -146,6 +146,11 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               (the same bits: kept for comparison runs)
  *   "rm_stage"  gridhip_rmclean: 0 = every wave reads and writes its line of sight directly, 1 = a work-group moves its
  *               lines of sight through LDS, consecutive threads along m (the same bits: kept for comparison runs)
+ *   "noisemap_hist"  gridhip_noise_map: how the node kernel builds the 256-counter histogram of a pass.  0 (default) =
+ *               every lane adds to one copy; else bits: 1 = skip the digits that the window's smallest and largest key
+ *               share, 2 = one copy of the counters per wave, 4 = lanes of a wave with the same digit add once (up to
+ *               four digits per step).  The same bits each way, and each slower than 0 where measured: kept for
+ *               comparison runs
  *   ("dbg", the ablation / profiling switch of tuning runs, exists only in the tuning build of the library,
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
@@ -828,6 +833,65 @@ int gridhip_imager_msdeconvolve_automask_dev(gridhip_imager *imager, const doubl
                                              double thr_hi, double thr_lo, double nsigma_hi, double nsigma_lo,
                                              double peak_frac, int64_t min_cells, int64_t grow, double *stats,
                                              double *istats, double *astats);
+
+/* ---- local background and noise maps: a windowed median and MAD on a mesh, interpolated onto the image, on the device ------
+ * The reference has none of this: the semantics are defined here.  gridhip_image_stats gives one sigma for a whole map;
+ * the noise of a primary-beam-corrected image or a mosaic rises toward its edge, and it is several times higher around a
+ * bright source.  This gives a sigma per cell.  image is a real N x N image, row-major, k = y * N + x; mask is N x N bytes,
+ * or NULL for none.  A cell TAKES PART when
+ *     border <= y, x < N - border,   image[k] is finite,   and   mask == NULL,  or  exclude == 0 and mask[k] != 0
+ *     (gridhip_image_stats' rule),  or  exclude == 1 and mask[k] == 0  (the sources of a clean mask stay out of their own
+ *     noise estimate).
+ * MESH.  M = N - 2 * border, G = max(1, M / step) in integer division (gridhip_noise_map_nodes returns it).  Node i has
+ * the centre c_i = border + min(i * step + step / 2, M - 1); node (i, j) owns the window |y - c_i| <= half, |x - c_j| <=
+ * half, clipped to the border region.
+ * NODE STATISTIC.  V is the window's cells that take part, ordered by gridhip_image_stats' 64-bit key.  For rounds r = 0, 1 ..
+ *     1  med = the lower median of V (rank (n - 1) / 2)
+ *     2  d_k = |v_k - med|, the difference rounded once
+ *     3  MAD = the lower median of the d_k
+ *     4  if r == nclip, or V is empty: stop
+ *     5  L = kappa * (1.4826 * MAD), both products rounded once
+ *     6  the cells with d_k > L leave V
+ *     7  if none left: stop; else r += 1
+ * With n_used the size of the final V and `rounds` the final r (the rounds that dropped a cell):
+ *     nodes[4][G][G] = { background, rms, n_used, rounds }
+ *     background = med if n_used >= min_count, else NaN;   rms = 1.4826 * MAD if n_used >= min_count and MAD > 0, else NaN
+ * so a constant patch has a background and no rms.
+ * MAPS, for a cell inside the border region.  i = the largest node with c_i <= y, or 0 when y < c_0; i1 = min(i + 1, G - 1);
+ * fy = 0 when i1 == i or y < c_i, else (double)(y - c_i) / (double)(c_i1 - c_i); j, j1, fx the same from x.
+ *     lerp(a, b, f) = a + f * (b - a) when both are finite - difference, product and sum each rounded, nothing fused -
+ *                     a when only a is finite, b when only b is, NaN when neither is
+ *     value = lerp(lerp(t[i][j], t[i][j1], fx), lerp(t[i1][j], t[i1][j1], fx), fy)
+ * for t the background table and for t the rms table.  A cell outside the border region is NaN in both maps and in out.
+ * out, by mode: 0 nothing; 1 image - background; 2 (image - background) / rms, a subtraction and then an IEEE division.  A
+ * non-finite image cell propagates as the arithmetic gives it.
+ * stats is 8 doubles { G, nodes with a background, nodes with an rms, the smallest rms of a node, the largest (both under
+ * the key order; NaN when no node has one), the cells of out inside the region that are not finite (0 for mode 0), the
+ * largest `rounds` of a node, 0 }.
+ * Everything is an order statistic, a count or a fixed sequence of rounded operations: the same bits for the host and _dev
+ * forms, for two runs, for a replayed graph, and for a restatement with a sort on the host.
+ * Arguments, checked before anything is touched.  GRIDHIP_EINVAL: N < 1; border < 0 or 2 * border >= N; step < 1; half < 1;
+ * kappa not finite or <= 0; nclip outside 0 .. 8; min_count < 1; exclude not 0 or 1; mode not 0, 1 or 2; a NULL image or
+ * stats; a NULL out with mode != 0; any of nodes, background, rms, out and stats overlapping image, mask or each other -
+ * but out may be image itself.  nodes, background, rms and (mode 0) out may each be NULL.  Then GRIDHIP_EUNSUPPORTED:
+ * half > 64, or N > 1048560.  gridhip_noise_map_nodes returns GRIDHIP_EINVAL for the first three rules.
+ * The node kernel is one work-group per node: the window's keys go into LDS once - (2 half + 1)^2 x 8 B, 133,128 B at
+ * half = 64, which fits the 160 KB a work-group may take on gfx950 and not 64 KB - and every select of every round is a
+ * radix select with 8-bit digits out of that copy, the MAD's over d_k recomputed from the keys; a cell that leaves V is
+ * overwritten by a key no finite value has.  The histograms use 32-bit integer LDS atomics (context option
+ * "noisemap_hist" chooses how, the same bits each way); there is no floating-point atomic and no sum of doubles.  A second
+ * kernel writes the maps and out in one pass, a third the stats.
+ * gridhip_noise_map is synchronous and stages host arrays through the context's pool.  The _dev form enqueues these three
+ * kernels on the context's stream, whatever the image holds - no memset or copy node - allocates nothing after the first
+ * call of a shape, reads nothing back and never synchronises: it can be captured.  Scratch (64 B, and the node table when
+ * nodes is NULL) comes from the context's pool; stats is on the device. */
+int64_t gridhip_noise_map_nodes(int64_t N, int64_t border, int64_t step);
+int gridhip_noise_map(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int exclude, int64_t border,
+                      int64_t step, int64_t half, double kappa, int64_t nclip, int64_t min_count, int mode, double *nodes,
+                      double *background, double *rms, double *out, double *stats);
+int gridhip_noise_map_dev(gridhip_ctx *ctx, int64_t N, const double *image, const uint8_t *mask, int exclude,
+                          int64_t border, int64_t step, int64_t half, double kappa, int64_t nclip, int64_t min_count,
+                          int mode, double *nodes, double *background, double *rms, double *out, double *stats);
 
 /* ---- restoring beam and restore: from clean's model and residual to a map, on the device -----------------------------
  * The reference stops at the dirty image: the semantics are defined here.  All images are real N x N, row-major [y][x];

@@ -519,6 +519,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "dft_slices")) return &ctx->img->dft_slices;  // dft_predict's component slices: 0 = auto, 1..64
     if (!strcmp(key, "mosaic_cull")) return &ctx->img->mosaic_cull;  // mosaic's per-tile cull: 0 = on, 1 = every valid facet
     if (!strcmp(key, "rm_stage")) return &ctx->img->rm_stage;  // rmclean's cube access: 0 = direct, 1 = through LDS
+    if (!strcmp(key, "noisemap_hist")) return &ctx->img->noisemap_hist;  // noise_map's histogram: 0 = default, else bits
     return nullptr;
 }
 

@@ -2,7 +2,7 @@
 // streaming image operations, the imaging functions, prediction, imagers, deconvolution and the restore (api.hip, comm.hip,
 // awgrid.hip's entry points, ctx.hip's pool, fft.hip, image_ops.hip, imaging.hip, predict.hip, imager.hip, clean.hip,
 // msclean.hip, mfclean.hip, jclean.hip, noise.hip, automask.hip, restore.hip, weights.hip, gaincal.hip, ddcal.hip, dft.hip, flag.hip,
-// sumthreshold.hip, sources.hip, average.hip, jonescal.hip, mosaic.hip, wstack.hip, rm.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
+// sumthreshold.hip, sources.hip, average.hip, jonescal.hip, mosaic.hip, wstack.hip, rm.hip, noisemap.hip).  The byte-range rules of the argument checks are in argrules.h, which this file includes.
 // The pre-pass and the tile kernels (bin.hip, tile_*.hip, tile_common.h, simple.hip) see none of this: what they are
 // compiled from is common.h alone, so that a change here leaves their source fingerprint (bench.py) as it is.
 #pragma once
@@ -46,6 +46,8 @@ struct ImagingState {
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
     int64_t mosaic_cull = 0;          // option "mosaic_cull": 1 = every tile of gridhip_mosaic walks all valid facets (the same bits)
     int64_t rm_stage = 0;             // option "rm_stage": 1 = gridhip_rmclean reads and writes the cube through LDS (the same bits)
+    int64_t noisemap_hist = 0;        // option "noisemap_hist": how noise_map's node kernel builds a histogram (noisemap.hip)
+    bool noisemap_lds_raised = false; // nm_node_kernel has been allowed its 146 KB of dynamic LDS (noisemap.hip)
 };
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled

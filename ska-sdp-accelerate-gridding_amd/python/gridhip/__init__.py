@@ -400,6 +400,62 @@ class Context(Handle):
         self._call(be, "image_stats", shape[0], image, mask, int(border), stats)
         return stats
 
+    def noise_map(self, image, mask=None, exclude=False, border=0, step=16, half=None, kappa=3.0, nclip=3, min_count=16,
+                  mode=None, maps=True, out=None):
+        """Local background and noise maps of the N x N float64 `image` (gridhip_noise_map[_dev]; include/gridhip.h,
+        "local background and noise maps"): the lower median and 1.4826 MAD of the (2 half + 1)^2 window around every
+        node of a mesh `step` cells apart, clipped at `kappa` sigma for up to `nclip` rounds, interpolated onto the
+        image.  half=None means min(64, 2 * step).  `mask` (bool or uint8, N x N) names the cells that take part, or with
+        exclude=True the cells that do not - a clean mask then keeps its sources out of their own noise estimate.
+        mode: None, "subtract" (out = image - background) or "snr" (out = (image - background) / rms); `out` is the
+        array to write, which may be `image` itself, a new one when None.  maps=False leaves the two maps out.
+        Returns (background, rms, out, nodes, stats): nodes is [4, G, G] = background, rms, cells used, clip rounds per
+        node, NaN where a node has fewer than `min_count` cells (and for the rms of a constant patch);
+        stats = [G, nodes with a background, nodes with an rms, smallest and largest node rms, non-finite cells of out,
+        most rounds, 0].  ctx.image_stats(nodes[1]) gives one typical sigma (it skips the NaNs).  numpy in gives numpy
+        out; torch cuda tensors take the asynchronous device form, which reads nothing back and can be captured."""
+        be = backend(image)
+        shape = tuple(getattr(image, "shape", ()))
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError("image must be N x N")
+        modes = {None: 0, "subtract": 1, "snr": 2}
+        if mode not in modes:
+            raise ValueError('mode must be None, "subtract" or "snr"')
+        step = int(step)
+        half = min(64, 2 * step) if half is None else int(half)
+        G = int(self._lib.gridhip_noise_map_nodes(shape[0], int(border), step))
+        if G < 0:
+            raise GridHipError(G, "noise_map: N, border or step out of range")
+        if out is not None and out is image:
+            out = image = in_place(be, image, shape, "image")
+        else:
+            image = image_of(be, image, shape, "image")
+            if mode is None:
+                out = None
+            elif out is None:
+                out = be.empty(shape, be.f64, image)
+            else:
+                out = in_place(be, out, shape, "out")
+        mask = mask_of(be, mask, shape)
+        bg, rms = (be.empty(shape, be.f64, image), be.empty(shape, be.f64, image)) if maps else (None, None)
+        nodes, stats = be.empty((4, G, G), be.f64, image), be.empty(8, be.f64, image)
+        self._call(be, "noise_map", shape[0], image, mask, int(bool(exclude)), int(border), step, half, float(kappa),
+                   int(nclip), int(min_count), modes[mode], nodes, bg, rms, out, stats)
+        return bg, rms, out, nodes, stats
+
+    def automask_local(self, image, mask=None, border=0, step=16, half=None, kappa=3.0, nclip=3, min_count=16,
+                       nsigma=(5, 2.5), min_cells=1, grow=0, absolute=False):
+        """automask against the LOCAL noise: noise_map(mode="snr") - with `mask` given, over the cells outside it
+        (exclude=True) - and then automask on the S/N image with the fixed levels thr=nsigma, so that nsigma[0] means
+        that many local sigma everywhere in the map.  `mask` is updated in place as automask does.  Returns
+        (mask, automask's stats, the S/N image, noise_map's stats)."""
+        _, _, snr, _, nstats = self.noise_map(image, mask=mask, exclude=mask is not None, border=border, step=step,
+                                              half=half, kappa=kappa, nclip=nclip, min_count=min_count, mode="snr",
+                                              maps=False)
+        mask, astats = self.automask(snr, mask=mask, border=border, absolute=absolute, thr=nsigma, nsigma=(0, 0),
+                                     min_cells=min_cells, grow=grow)
+        return mask, astats, snr, nstats
+
     def automask(self, image, mask=None, noise=None, border=0, absolute=False, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0,
                  min_cells=1, grow=0):
         """The clean mask of the N x N float64 `image` (gridhip_automask[_dev]; include/gridhip.h, "auto-masking"): the
@@ -1474,6 +1530,19 @@ class Imager(_Bound):
         self._call(be, "imager_automask", image, m8, int(border), *args, stats)
         return mask, stats
 
+    def automask_local(self, image, mask=None, border=0, step=16, half=None, kappa=3.0, nclip=3, min_count=16,
+                       nsigma=(5, 2.5), min_cells=1, grow=0, absolute=False):
+        """Context.automask_local of an N x N cuda float64 image: the context's noise_map(mode="snr"), then this imager's
+        automask on the S/N image.  Returns (mask, automask's stats, the S/N image, noise_map's stats)."""
+        self._open()
+        self._ok(image, device().f64, (self.N, self.N), "image")
+        _, _, snr, _, nstats = self._ctx.noise_map(image, mask=mask, exclude=mask is not None, border=border, step=step,
+                                                   half=half, kappa=kappa, nclip=nclip, min_count=min_count, mode="snr",
+                                                   maps=False)
+        mask, astats = self.automask(snr, mask=mask, border=border, absolute=absolute, thr=nsigma, nsigma=(0, 0),
+                                     min_cells=min_cells, grow=grow)
+        return mask, astats, snr, nstats
+
     def find_sources(self, image, beam=None, noise=None, border=0, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0, min_cells=1,
                      correct=True, max_sources=1024, out=None, info=True):
         """Context.find_sources of an N x N cuda float64 map with the imager's theta, lam and its own scratch
@@ -1892,6 +1961,17 @@ def rm_tile():
     if rc != 0:
         raise GridHipError(rc, "gridhip_rm_tile")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def noise_grid(N, border=0, step=16):
+    """The node centres of Context.noise_map's mesh for an N x N image (gridhip_noise_map_nodes): G int64 cell indices,
+    the same along y and x."""
+    import numpy as np
+    G = int(_lib.load().gridhip_noise_map_nodes(int(N), int(border), int(step)))
+    if G < 0:
+        raise GridHipError(G, "gridhip_noise_map_nodes")
+    M = int(N) - 2 * int(border)
+    return int(border) + np.minimum(np.arange(G, dtype=np.int64) * int(step) + int(step) // 2, M - 1)
 
 
 def contsub_tile():

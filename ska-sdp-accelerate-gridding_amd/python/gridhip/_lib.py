@@ -50,6 +50,8 @@ _AUTOMASK = [vp, i64, vp, vp, *_AUTOMASK_ARGS, vp]
 # (no border, no noise), then stats, istats, astats
 _AUTOMASK_LOOP = [vp, C.c_double, C.c_double, ci, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i64, i64,
                   vp, vp, vp]
+# N, image, mask, exclude, border, step, half, kappa, nclip, min_count, mode, nodes, background, rms, out, stats
+_NOISE_MAP = [vp, i64, vp, vp, ci, i64, i64, i64, C.c_double, i64, i64, ci, vp, vp, vp, vp, vp]
 _FIT_BEAM = [vp, i64, vp, i64, C.c_double, vp]
 _RESTORE = [vp, i64, vp, vp, vp, i64, vp]
 _WEIGHTS = [vp, C.c_double, i64, i64, vp, vp, i64, vp, ci, C.c_double, C.c_double, vp, vp]
@@ -199,6 +201,9 @@ SIGNATURES = {
                                                     *_AUTOMASK_LOOP]),
     "gridhip_imager_msdeconvolve_automask_dev": (ci, [vp, vp, vp, vp, i64, i64, _HOST_F64, _HOST_F64, C.c_double,
                                                       C.c_double, i64, i64, i64, *_AUTOMASK_LOOP]),
+    "gridhip_noise_map_nodes": (i64, [i64, i64, i64]),
+    "gridhip_noise_map": (ci, _NOISE_MAP),
+    "gridhip_noise_map_dev": (ci, _NOISE_MAP),
     "gridhip_fit_beam": (ci, _FIT_BEAM),
     "gridhip_fit_beam_dev": (ci, _FIT_BEAM),
     "gridhip_restore": (ci, _RESTORE),
