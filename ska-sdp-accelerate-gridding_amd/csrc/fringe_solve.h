@@ -1,6 +1,6 @@
-// The antenna fit of gridhip_fringe_solve as a driver enqueues it.  fringe.hip defines the kernels and these functions;
-// tec.hip reaches the same solve through them (include/gridhip.h, "dispersive delay (TEC) calibration": the fit is
-// gridhip_fringe_solve, unchanged).
+// The antenna fit of gridhip_fringe_solve (fringe_solve.hip) as a driver enqueues it: the fit drivers of fringe.hip and
+// tec.hip run the same solve between their searches (delay_common.h, "the fit driver"; include/gridhip.h, "dispersive
+// delay (TEC) calibration": the fit is gridhip_fringe_solve, unchanged).
 #pragma once
 #include "common.h"
 
@@ -27,11 +27,11 @@ struct FrSolve {
 };
 
 // the scalar rules of gridhip_fringe_solve
-bool fringe_solve_args_ok(int64_t B, int64_t I, int64_t A, double min_count, double min_coh2, int64_t refant, int64_t niter,
-                          double tol);
+bool fr_solve_args_ok(int64_t B, int64_t I, int64_t A, double min_count, double min_coh2, int64_t refant, int64_t niter,
+                      double tol);
 // the two launches of a solve on the context's stream; stats: 8 doubles on the device
-void fringe_solve_enqueue(gridhip_ctx *ctx, const FrSolve &a, double *stats);
+void fr_solve_launch(gridhip_ctx *ctx, const FrSolve &a, double *stats);
 // sol[n][4] = { 0, 0, 1, 0 }
-void fringe_init_sol_enqueue(gridhip_ctx *ctx, int64_t n, double *sol);
+void fr_init_sol_launch(gridhip_ctx *ctx, int64_t n, double *sol);
 
 }  // namespace gridhip

@@ -208,6 +208,26 @@ def test_peak_across_a_tile_border(ctx, tile, which):
     assert same(got[0], want) and same(got[1], wstats)
 
 
+def test_an_exact_tie_across_tiles(ctx, tile):
+    """all-zero visibilities under unit weights: every cell's power is 0, so the reduction within a tile and the refinement's
+    choice among the four tiles are decided by the tie rule alone - the lowest delay, then the lowest TEC cell - on the
+    whole grid and on a window that starts one cell in on both axes"""
+    tj, tm, _ = tile
+    F, T, A = 3, 2, 2
+    Nd, Nm = tj + 1, tm + 1
+    freq = tc.band(F)
+    delays, tecs = grid_axes(freq, Nd, Nm)
+    a1, a2 = np.array([0], dtype=np.int64), np.array([1], dtype=np.int64)
+    vis, wt = np.zeros((1, T, F), dtype=np.complex128), np.ones((1, T, F))
+    tab = ctx.tec_tables(freq, T, 0, delays, tecs)
+    for cells, peak in ((None, (0, 0)), ((1, Nd, 1, Nm), (1, 1))):
+        want, wstats = tr.search(tab, vis, a1, a2, A, wt=wt, cells=cells)
+        got = ctx.tec_search(vis, tab, a1, a2, A, 0, delays, tecs, weights=wt, cells=cells)
+        assert same(got[0], want) and same(got[1], wstats)
+        row = got[0][0, 0]
+        assert (row[0], row[1]) == peak and row[7] == 0 and row[10] == 0, "the peak, coh^2 and the class"
+
+
 def test_search_classes(ctx):
     c = search_case(5, 6, 4, seed=3, A=6, T=4, tint=0)
     vis, wt, a1, a2 = c["vis"].copy(), np.ones(c["vis"].shape), c["a1"].copy(), c["a2"].copy()
