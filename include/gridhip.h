@@ -151,12 +151,20 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               share, 2 = one copy of the counters per wave, 4 = lanes of a wave with the same digit add once (up to
  *               four digits per step).  The same bits each way, and each slower than 0 where measured: kept for
  *               comparison runs
+ *   "scratch_fill"  TEST HOOK: 0 (default) = off; 1..255 = every block of device memory the library takes for itself - a
+ *               pooled block each time it is handed out (scratch and the host-pointer forms' staging alike), a gridder
+ *               workspace when it grows, the blocks a plan, stack or imager owns - is first filled with this byte, in
+ *               stream order, so that a kernel that reads scratch it never wrote, or a host form that returns an output
+ *               it filled only in part, shows.  Values above 255 are refused.  Set it before the context's first call.
+ *               Each fill is a memset node: not for calls captured into a graph.  Memory from gridhip_malloc is the
+ *               caller's and is left alone
  *   ("dbg", the ablation / profiling switch of tuning runs, exists only in the tuning build of the library,
  *   `make -C csrc tuning` -> lib/libgridhip_tuning.so; the shipped library rejects the key)
  * Read-only (gridhip_get_option): "prepass_verified" = calls so far that ran the verify sweep of "bin_reuse",
  * "prepass_reused" = those of them that kept their records (counted on the device: reading it synchronises the stream);
  * "lists_reused" = tile launches so far that were told the previous call's sorted lists are in place ("list_reuse"; the
  * kernel still sorts afresh if the verify sweep then finds the records changed);
+ * "scratch_filled" = blocks filled so far on this context by the test hook "scratch_fill";
  * "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last convgrid / convgrid2 / degrid2
  * call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
  * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or

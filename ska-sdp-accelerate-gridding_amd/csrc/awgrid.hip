@@ -897,6 +897,7 @@ int gridhip_aw_plan_create_dev(gridhip_ctx *ctx, int64_t H, int64_t Wd, int64_t 
             }
             b.nkern = nk < 0 ? 0 : nk > m ? m : nk;
             GH_CHECK_HIP(ctx, hipMalloc((void **)&b.table, (size_t)(b.nkern > 0 ? b.nkern : 1) * S2 * 16));
+            GH_CHECK(scratch_prefill(ctx, b.table, (size_t)(b.nkern > 0 ? b.nkern : 1) * S2 * 16));
             GH_CHECK(aw_build(ctx, c, m, wkerns, b.table, b.nkern));
             ++ctx->aw_tables_built;
             Geom g = c.p.g;

@@ -20,6 +20,15 @@ int fail(gridhip_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
+int scratch_prefill(gridhip_ctx *ctx, void *p, size_t bytes)
+{
+    const int64_t fill = ctx->img->scratch_fill;
+    if (fill == 0 || !p || bytes == 0) return GRIDHIP_OK;
+    GH_CHECK_HIP(ctx, hipMemsetAsync(p, (int)fill, bytes, ctx->stream));
+    ++ctx->img->scratch_filled;
+    return GRIDHIP_OK;
+}
+
 int ws_reserve(gridhip_ctx *ctx, Workspace &ws, size_t bytes)
 {
     if (bytes <= ws.bytes) return GRIDHIP_OK;
@@ -31,7 +40,7 @@ int ws_reserve(gridhip_ctx *ctx, Workspace &ws, size_t bytes)
     size_t want = bytes + bytes / 8 + 4096;  // head-room so nearby sizes do not reallocate
     GH_CHECK_HIP(ctx, hipMalloc(&ws.ptr, want));
     ws.bytes = want;
-    return GRIDHIP_OK;
+    return scratch_prefill(ctx, ws.ptr, want);
 }
 
 int DevBuf::alloc(gridhip_ctx *ctx, size_t bytes)
@@ -48,7 +57,7 @@ int DevBuf::alloc(gridhip_ctx *ctx, size_t bytes)
         p = pool[best].first;
         cap = pool[best].second;
         pool.erase(pool.begin() + best);
-        return GRIDHIP_OK;
+        return scratch_prefill(ctx, p, cap);
     }
     hipError_t e = hipMalloc(&p, bytes);
     if (e == hipErrorOutOfMemory && !pool.empty()) {  // give the pooled blocks back and try once more
@@ -64,7 +73,7 @@ int DevBuf::alloc(gridhip_ctx *ctx, size_t bytes)
                     hipGetErrorString(e));
     }
     cap = bytes;
-    return GRIDHIP_OK;
+    return scratch_prefill(ctx, p, cap);
 }
 
 int DevBuf::upload(gridhip_ctx *ctx, const void *host, size_t bytes)
@@ -520,6 +529,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "mosaic_cull")) return &ctx->img->mosaic_cull;  // mosaic's per-tile cull: 0 = on, 1 = every valid facet
     if (!strcmp(key, "rm_stage")) return &ctx->img->rm_stage;  // rmclean's cube access: 0 = direct, 1 = through LDS
     if (!strcmp(key, "noisemap_hist")) return &ctx->img->noisemap_hist;  // noise_map's histogram: 0 = default, else bits
+    if (!strcmp(key, "scratch_fill")) return &ctx->img->scratch_fill;  // TEST HOOK: the byte every block is filled with first
     return nullptr;
 }
 
@@ -530,6 +540,7 @@ int gridhip_set_option(gridhip_ctx *ctx, const char *key, int64_t value)
     if (!s) return fail(ctx, GRIDHIP_EINVAL, "unknown option '%s'", key);
     // ("aw_batch" keeps a negative value as given: the aw entry points refuse it, before they touch anything)
     if (value < 0 && s != &ctx->opt.aw_batch) return fail(ctx, GRIDHIP_EINVAL, "option '%s' must be >= 0", key);
+    if (s == &ctx->img->scratch_fill && value > 255) return fail(ctx, GRIDHIP_EINVAL, "option 'scratch_fill' is a byte: 0..255");
     *s = value;
     return GRIDHIP_OK;
 }
@@ -577,6 +588,11 @@ int gridhip_get_option(gridhip_ctx *ctx, const char *key, int64_t *value)
         // read-only: tile launches so far that were told to trust the previous call's sorted lists (tile_sorted.hip,
         // "Kept lists"; the kernel still sorts when the verify sweep's verdict goes against the records)
         *value = ctx->lists_reused;
+        return GRIDHIP_OK;
+    }
+    if (!strcmp(key, "scratch_filled")) {
+        // read-only: the blocks option "scratch_fill" has filled so far on this context
+        *value = ctx->img->scratch_filled;
         return GRIDHIP_OK;
     }
     if (!strcmp(key, "last_path")) {

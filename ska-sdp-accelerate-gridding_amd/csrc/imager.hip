@@ -230,7 +230,7 @@ int own(gridhip_imager *im, T **p, size_t bytes)
     if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return fail(im->ctx, GRIDHIP_ENOMEM, "imager: %zu bytes", bytes);
     im->owned.push_back(q);
     *p = (T *)q;
-    return GRIDHIP_OK;
+    return scratch_prefill(im->ctx, q, bytes ? bytes : 16);
 }
 
 // n complex numbers (2 n doubles) of zeros

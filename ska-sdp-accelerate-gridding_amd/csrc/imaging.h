@@ -48,7 +48,14 @@ struct ImagingState {
     int64_t rm_stage = 0;             // option "rm_stage": 1 = gridhip_rmclean reads and writes the cube through LDS (the same bits)
     int64_t noisemap_hist = 0;        // option "noisemap_hist": how noise_map's node kernel builds a histogram (noisemap.hip)
     bool noisemap_lds_raised = false; // nm_node_kernel has been allowed its 146 KB of dynamic LDS (noisemap.hip)
+    int64_t scratch_fill = 0;         // option "scratch_fill" (TEST HOOK): 1..255 = the byte every block is filled with first
+    int64_t scratch_filled = 0;       // read-only "scratch_filled": the blocks filled so far (scratch_prefill, ctx.hip)
 };
+
+// TEST HOOK (option "scratch_fill"): a block the library is about to use - a pooled one handed out, a workspace that
+// grew, a handle's own - is filled with the option's byte, in stream order before whatever the call enqueues next.  Off
+// (0): one comparison.  A memset node: not for captured calls.
+int scratch_prefill(gridhip_ctx *ctx, void *p, size_t bytes);
 
 // Device block of one call, drawn from and returned to the context's pool (ImagingState::pool_free): the smallest pooled
 // block of at least the size asked for and at most twice it, else a new one.  Nothing is freed before gridhip_destroy,

@@ -179,6 +179,7 @@ int w_cache_prepare(gridhip_ctx *ctx, WCache &c, double theta, int64_t lam, int6
                 return fail(ctx, GRIDHIP_ENOMEM, "w-kernel table: %zu bytes", bytes);
             }
             k.bytes = bytes;
+            GH_CHECK(scratch_prefill(ctx, k.ptr, bytes));
         }
         GH_CHECK(build_w_planes(ctx, theta, wstep, wmin, c.nplanes, npixFF, S, Q, (double2 *)k.ptr, true));  // (:441)
         GH_CHECK(sync(ctx));

@@ -404,6 +404,7 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
         ws->base = nullptr;
         return fail(ctx, GRIDHIP_ENOMEM, "w-stacking: %zu bytes", total);
     }
+    GH_CHECK(scratch_prefill(ctx, ws->base, total));
     char *b = (char *)ws->base;
     ws->pu = (double *)(b + at[0]), ws->pv = (double *)(b + at[1]), ws->rbin = (int64_t *)(b + at[2]);
     ws->src = (int32_t *)(b + at[3]), ws->lay = (double2 *)(b + at[4]);
