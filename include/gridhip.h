@@ -151,6 +151,11 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               share, 2 = one copy of the counters per wave, 4 = lanes of a wave with the same digit add once (up to
  *               four digits per step).  The same bits each way, and each slower than 0 where measured: kept for
  *               comparison runs
+ *   "wstack_middle"  gridhip_imager_cycle_dev of an imager of kind 4 (w-stacking): 0 (default) = the pass over the
+ *               visibilities between the prediction and the gridding runs once, in the layer order of the mirrored
+ *               stack; 1 = it runs in stream order between the stacks' two permuting passes (three passes over the
+ *               visibilities instead of one).  The same vis_res bit for bit and images equal to the atomics' tolerance;
+ *               0 is the faster where measured, 1 is kept for comparison runs.  Read per call.
  *   "scratch_fill"  TEST HOOK: 0 (default) = off; 1..255 = every block of device memory the library takes for itself - a
  *               pooled block each time it is handed out (scratch and the host-pointer forms' staging alike), a gridder
  *               workspace when it grows, the blocks a plan, stack or imager owns - is first filled with this byte, in
@@ -510,7 +515,26 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
  * with spectral terms (see "wide-band imaging") 8 B + 16 B more per visibility, 2T - 1 images and mfclean's scratch
  * (all released at destroy).
  * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
- * and 1).  n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
+ * and 1).
+ * kind 4 w-stacking (see "w-stacking"): wstep = the w step, Q = qpx, npixFF, gh = npixKern, gw = M (the planes per layer),
+ * kv ignored.  The two calls it replaces are gridhip_do_imaging_wstack_dev and gridhip_predict_wstack_dev, so its image
+ * is 2 Re D(wt vis1) / pmax, not the Hermitian fill of kinds 0 to 2 ("DO_IMAGING WITH A STACK" explains the difference),
+ * and its prediction is the stack's on the un-mirrored stream.  A visibility whose w is not finite grids nothing,
+ * predicts exactly 0 and leaves vis_res[k] = vis[k]; n > 0 without any finite w gives what that call gives (a division by
+ * pmax = 0).  Checked at creation by the stack's rules: wstep < 1, M < 1, the w-kernel shape rule or w == NULL with n > 0
+ * are GRIDHIP_EINVAL, more than 4096 layers on either stream, M > 65536, |w / wstep| > 2^52 or n >= 2^31 - 256
+ * GRIDHIP_EUNSUPPORTED.  gridhip_do_imaging* and gridhip_predict* keep refusing kind 4 (they have their _wstack forms),
+ * and kind 3 is refused here (aw has its own creation calls).  The imager holds a stack on each stream - the un-mirrored
+ * one for the predict passes only, the mirrored one for the image passes only: v < 0 negates w, so plane ranges, pmin and
+ * layer bounds differ - which share ONE kernel table K, one conj(K) and the imager's hipFFT plan, and have one N x N
+ * complex grid each.  gridhip_last_dropped after creation reports the mirrored stack's total.  A cycle is: per layer of
+ * the un-mirrored stack head kernel + forward FFT + gather; ONE pass over the visibilities in the mirrored stack's layer
+ * order (option "wstack_middle"); per layer of the mirrored stack scatter + inverse FFT + screen; one division by the
+ * stored pmax.  predict, selfcal, peel, flag and the wide-band calls take the stream-order passes.  Memory of this kind:
+ * per visibility 8 B (the weight) + 16 B (the prediction in stream order) + two 16 B layer-ordered blocks + three 4 B
+ * indices (each stack's and their composition) + 2 x 24 B of layer-ordered coordinates and bins, and the layers'
+ * records; per N^2 cell 2 x 16 B (the two grids) + 8 B (psf); 2 x M Q^2 S^2 x 16 B of tables and one hipFFT plan.
+ * n = 0 is a valid imager whose image is zero.  cycle with NULL vis or image (n > 0) is GRIDHIP_EINVAL and
  * touches nothing.  An imager belongs to its context (same device, same stream, not thread-safe) and must be destroyed
  * before it; any other call on the context between two imager calls - do_imaging or predict of another shape, another
  * imager, a rebuild of the w-kernel cache - leaves its results unchanged. */
@@ -2417,7 +2441,8 @@ int gridhip_reproject_dev(gridhip_ctx *ctx, int64_t Ns, double theta_s, const do
  * every other cell.  A stack cannot apply make_grid_hermitian (its layers' mirror images lie in the layers of -w), so it
  * takes 2 Re throughout.  gridhip_predict_wstack is the stack's predict on the stream as given (no mirror), as
  * gridhip_predict.  Both make a stack for the call and destroy it; the host forms are synchronous, the _dev forms take
- * device pointers (pmax stays a host pointer) and synchronise too. */
+ * device pointers (pmax stays a host pointer) and synchronise too.  A major-cycle loop does not call them per cycle: an
+ * imager of kind 4 ("imagers") binds both streams once and is defined by these two calls. */
 typedef struct gridhip_wstack gridhip_wstack;
 int gridhip_wstack_create_dev(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
                               double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,

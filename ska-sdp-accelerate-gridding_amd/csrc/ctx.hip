@@ -529,6 +529,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "mosaic_cull")) return &ctx->img->mosaic_cull;  // mosaic's per-tile cull: 0 = on, 1 = every valid facet
     if (!strcmp(key, "rm_stage")) return &ctx->img->rm_stage;  // rmclean's cube access: 0 = direct, 1 = through LDS
     if (!strcmp(key, "noisemap_hist")) return &ctx->img->noisemap_hist;  // noise_map's histogram: 0 = default, else bits
+    if (!strcmp(key, "wstack_middle")) return &ctx->img->wstack_middle;  // a stack imager's cycle middle: 0 = default, 1 = the other
     if (!strcmp(key, "scratch_fill")) return &ctx->img->scratch_fill;  // TEST HOOK: the byte every block is filled with first
     return nullptr;
 }

@@ -11,6 +11,11 @@
 // with no pre-pass, no table build, no histogram, no PSF pass, no allocation, no synchronisation and no memset node.
 // The gather and the scatter are the tile kernels of the plans (plan.hip, awgrid.hip), which lend their records to the
 // launchers; the simple kind has no records and keeps its two coordinate sets instead.
+// The w-stacking kind (include/gridhip.h, "imagers") holds two half stacks (wstack.hip) in place of the two plans: the
+// un-mirrored one runs predict passes only, the mirrored one image passes only, and they share one kernel table, its
+// conjugate and the imager's transform.  Its image is gridhip_do_imaging_wstack's: per layer a scatter, an inverse
+// transform and the w-screen, 2 Re of the sum divided by pmax - no Hermitian fill.  Its cycle has a middle pass of its own
+// in the mirrored stack's layer order (ws_middle_kernel) besides the generic one in stream order.
 // Wide-band imaging ("wide-band imaging" in the header) adds to an imager x = (nu - nu_0) / nu_0 per visibility, the
 // 2T - 1 spectral PSFs - each the image of a plain cycle of (x^s, 0) - and a residual-visibility block: an mfs_cycle is one
 // transform and gather per model term accumulated into that block, then per term one pass over it (times x^t, conjugate
@@ -174,7 +179,7 @@ using namespace gridhip;
 
 struct gridhip_imager {
     gridhip_ctx *ctx = nullptr;
-    int kind = 0;  // 0 simple, 1 conv, 2 w_cache, 3 aw
+    int kind = 0;  // 0 simple, 1 conv, 2 w_cache, 3 aw, 4 w-stacking
     int64_t N = 0, n = 0;
     std::vector<void *> owned;  // every device block below
     double *sw = nullptr;       // [n] weight, negative where the baseline is mirrored
@@ -193,6 +198,11 @@ struct gridhip_imager {
     double2 *ktab_g = nullptr, *ktab_s = nullptr;
     // aw: the same as aw plans, which hold their batches' kernel tables themselves
     gridhip_aw_plan *aw_gather = nullptr, *aw_scatter = nullptr;
+    // w-stacking: the half stack of the un-mirrored stream (predict passes) and of the mirrored one (image passes); they
+    // borrow ktab_s = K, ktab_g = conj(K) and fft.  ws_back[j'] = the place in the gather's layer order of the visibility
+    // the scatter keeps at j' (the layer-order middle pass)
+    gridhip_wstack *ws_gather = nullptr, *ws_scatter = nullptr;
+    int32_t *ws_back = nullptr;
     bool clear_pred = false;  // the gather does not write every prediction: they start from zero
     void *clean_scratch = nullptr;  // clean's state block and tile table (clean.hip), made by the first clean
     // msclean's scratch (msclean.hip), made by the first msclean and grown by one that needs more; it keeps the taps and
@@ -223,6 +233,10 @@ struct gridhip_imager {
 
 namespace {
 
+// Which middle pass a w-stacking imager's cycle takes when the option "wstack_middle" is 0: the one that measured faster
+// ("W-stacking: the imager kind").  true: the layer-order pass (ws_middle_kernel); the option's 1 is the other.
+constexpr bool WS_MIDDLE_LAYERED = true;
+
 template <typename T>
 int own(gridhip_imager *im, T **p, size_t bytes)
 {
@@ -245,6 +259,7 @@ int zero(gridhip_ctx *ctx, int64_t n, double2 *a)
 int gather(gridhip_imager *im, const double *model)
 {
     gridhip_ctx *ctx = im->ctx;
+    if (im->kind == 4) return wstack_predict_run(im->ws_gather, model, nullptr, (double *)im->pred);  // (its own transforms)
     GH_CHECK(model_transform_to(ctx, im->N, model, im->f, im->t, im->fft));
     if (im->clear_pred) GH_CHECK(zero(ctx, im->n, im->pred));
     switch (im->kind) {
@@ -271,6 +286,27 @@ int scatter(gridhip_imager *im)
             return gridhip_plan_grid_dev(im->scatter, (const double *)im->ktab_s, (const double *)im->pred,
                                          (double *)im->g);
     }
+}
+
+// The image of the values in pred on the mirrored baselines: scatter and the imaging tail, or (w-stacking) the mirrored
+// stack's image pass times 2.  maxbits: the image's maximum goes there; divbits: the image is divided by the maximum kept
+// there (one of the two is null).
+int image_pass(gridhip_imager *im, double *out, unsigned long long *maxbits, const unsigned long long *divbits,
+               bool layered = false)
+{
+    gridhip_ctx *ctx = im->ctx;
+    if (im->kind != 4) {
+        GH_CHECK(scatter(im));
+        return image_tail(ctx, im->N, im->g, im->f, out, maxbits, divbits, im->fft);
+    }
+    // (layered: the middle pass has left the values in the stack's layer order already)
+    if (layered)
+        GH_CHECK(wstack_image_layers(im->ws_scatter, out, 2.0));
+    else
+        GH_CHECK(wstack_image_run(im->ws_scatter, (const double *)im->pred, out, 2.0));
+    if (maxbits) GH_CHECK(wstack_image_max(ctx, im->N * im->N, out, maxbits));
+    if (divbits) GH_CHECK(launch_divide(ctx, im->N * im->N, out, divbits));  // (as normalise divides)
+    return GRIDHIP_OK;
 }
 
 struct Kernels {  // conv, w_cache: the imaging function; aw: its Q, the tables and the antennas; the weighting
@@ -306,9 +342,11 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
     }
     GH_CHECK(own(im, &im->sw, (size_t)n * 8));
     GH_CHECK(own(im, &im->pred, (size_t)n * 16));
-    GH_CHECK(own(im, &im->g, cells * 16));
-    GH_CHECK(own(im, &im->f, cells * 16));
-    if (N % 2 != 0) GH_CHECK(own(im, &im->t, cells * 16));
+    if (im->kind != 4) {  // (the stacks have the one grid each that their passes use)
+        GH_CHECK(own(im, &im->g, cells * 16));
+        GH_CHECK(own(im, &im->f, cells * 16));
+        if (N % 2 != 0) GH_CHECK(own(im, &im->t, cells * 16));
+    }
     GH_CHECK(fft_plan_own(ctx, N, &im->fft));
 
     // ---- front end: both coordinate sets, the mirror flags, the weights
@@ -323,8 +361,8 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
         }
     }
     for (int i = 0; i < 2; ++i) {
-        if (im->kind == 2) GH_CHECK(tw[i].alloc(ctx, (size_t)n * 8));
-        if (im->kind >= 2) GH_CHECK(tb[i].alloc(ctx, (size_t)n * 8));
+        if (im->kind == 2 || im->kind == 4) GH_CHECK(tw[i].alloc(ctx, (size_t)n * 8));
+        if (im->kind == 2 || im->kind == 3) GH_CHECK(tb[i].alloc(ctx, (size_t)n * 8));
     }
     GH_CHECK(cell.alloc(ctx, (size_t)n * 8));
     hipLaunchKernelGGL(imager_front_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, u, v,
@@ -366,6 +404,21 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
                                          &im->gather));
         GH_CHECK(gridhip_plan_create_dev(ctx, N, N, n, np[1], fn.Q, fn.gh, fn.gh, p[2], p[3], 1, tb[1].as<int64_t>(),
                                          &im->scatter));
+    } else if (im->kind == 4) {
+        // one table K of the residual planes and its conjugate for both stacks; a stack on each stream, the gather's
+        // first.  The stacks divide by lam themselves: p is u / lam already, and a division by 1 is exact.
+        const size_t tab = (size_t)fn.gw * fn.Q * fn.Q * fn.gh * fn.gh;
+        GH_CHECK(own(im, &im->ktab_g, tab * 16));
+        GH_CHECK(own(im, &im->ktab_s, tab * 16));
+        WStackArgs a{fn.wstep, fn.gw, fn.Q, fn.npixFF, fn.gh, fn.theta, 1, n, p[0], p[1], tw[0].as<double>(), 1};
+        GH_CHECK(wstack_tables(ctx, a, im->ktab_s, im->ktab_g));
+        WsLend lend{1, im->fft, im->ktab_s, im->ktab_g};
+        GH_CHECK(wstack_create(ctx, a, N, &im->ws_gather, false, &lend));
+        a.u = p[2], a.v = p[3], a.w = tw[1].as<double>();
+        lend.half = 2;
+        GH_CHECK(wstack_create(ctx, a, N, &im->ws_scatter, false, &lend));
+        GH_CHECK(own(im, &im->ws_back, (size_t)wstack_count(im->ws_scatter) * 4));
+        GH_CHECK(wstack_compose(im->ws_gather, im->ws_scatter, im->ws_back));
     } else {
         // the gather's kernels are conj(aw_kernel_fn2(conj wk, conj ak)) (predict_aw); the aw plans keep what they build
         const size_t wel = (size_t)k.W * fn.Q * fn.Q * k.S * k.S, ael = (size_t)k.A * k.S * k.S;
@@ -385,22 +438,32 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
     if (im->aw_gather) im->clear_pred = aw_plan_caller_clears(im->aw_gather);
     const int64_t tables = ctx->aw_tables_built;
 
+    // (w-stacking: the gather of an empty model, see below, comes first - its model is the PSF's block while that is
+    // still free, and gridhip_last_dropped is left with the mirrored stack's total, which the image pass reports)
+    if (im->kind == 4) {
+        hipLaunchKernelGGL(imager_zero_kernel, grid_for(ctx, (int64_t)cells / 2 + 1), dim3(256), 0, ctx->stream,
+                           (int64_t)cells, im->psf);
+        GH_CHECK_HIP(ctx, hipGetLastError());
+        GH_CHECK(gather(im, im->psf));
+    }
     // ---- the PSF (src/Gridding.hs:541-548) and its maximum
     hipLaunchKernelGGL(imager_wt_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, im->sw, im->pred);
     GH_CHECK_HIP(ctx, hipGetLastError());
-    GH_CHECK(scatter(im));
-    GH_CHECK(image_tail(ctx, N, im->g, im->f, im->psf, im->pmaxbits, nullptr, im->fft));
+    GH_CHECK(image_pass(im, im->psf, im->pmaxbits, nullptr));
     GH_CHECK(launch_divide(ctx, (int64_t)cells, im->psf, im->pmaxbits));
     // one gather of an empty grid: a support the gather cannot hold is refused here, not in the first cycle, and the
     // launchers' scratch has its size before a cycle is captured
-    GH_CHECK(zero(ctx, (int64_t)cells, im->f));
-    if (im->clear_pred) GH_CHECK(zero(ctx, n, im->pred));
-    if (im->kind == 0)
-        GH_CHECK(launch_simple_degrid(ctx, N, N, im->f, n, im->pu, im->pv, 1, 1.0, im->pred));
-    else if (im->kind == 3)
-        GH_CHECK(gridhip_aw_plan_degrid_dev(im->aw_gather, (const double *)im->f, (double *)im->pred));
-    else
-        GH_CHECK(gridhip_plan_degrid_dev(im->gather, (const double *)im->ktab_g, (const double *)im->f, (double *)im->pred));
+    if (im->kind != 4) {  // (w-stacking: done above)
+        GH_CHECK(zero(ctx, (int64_t)cells, im->f));
+        if (im->clear_pred) GH_CHECK(zero(ctx, n, im->pred));
+        if (im->kind == 0)
+            GH_CHECK(launch_simple_degrid(ctx, N, N, im->f, n, im->pu, im->pv, 1, 1.0, im->pred));
+        else if (im->kind == 3)
+            GH_CHECK(gridhip_aw_plan_degrid_dev(im->aw_gather, (const double *)im->f, (double *)im->pred));
+        else
+            GH_CHECK(gridhip_plan_degrid_dev(im->gather, (const double *)im->ktab_g, (const double *)im->f,
+                                             (double *)im->pred));
+    }
     ctx->aw_tables_built = tables;  // (the passes above reset it: it reports the creation)
     unsigned long long mb = 0;
     GH_CHECK(d2h(ctx, &mb, im->pmaxbits, 8));
@@ -445,7 +508,10 @@ int gridhip_imager_create_weighted_dev(gridhip_ctx *ctx, int kind, int64_t wstep
     k.fn = {kind, wstep, Q, npixFF, gh, kind == 2 ? gh : gw, kv, theta, lam};
     k.mode = mode, k.robust = robust, k.sigma = taper_sigma, k.wt_in = wt_in;
     int64_t N = 0;
-    GH_CHECK(imaging_fn_check(ctx, k.fn, &N));
+    if (kind == 4)  // w-stacking: gw = the planes per layer, and the stack's own rules and limits
+        GH_CHECK(wstack_check(ctx, WStackArgs{wstep, gw, Q, npixFF, gh, theta, lam, n, u, v, w, uv_stride}, &N));
+    else
+        GH_CHECK(imaging_fn_check(ctx, k.fn, &N));
     GH_CHECK(weights_mode_check(ctx, mode, robust, taper_sigma));
     if (!imager || n < 0 || uv_stride < 1 || (n > 0 && (!u || !v || (kind == 2 && !w))))
         return fail(ctx, GRIDHIP_EINVAL, "bad argument");
@@ -528,6 +594,16 @@ int gridhip_imager_cycle_dev(gridhip_imager *im, const double *model, const doub
         return GRIDHIP_OK;
     }
     mark(ctx, 0);
+    // w-stacking: the middle pass in the mirrored stack's layer order, between the layers' gathers and the layers' scatters
+    // - or (option "wstack_middle" = 1) the generic one below, in stream order between the stacks' two permuting passes
+    if (im->kind == 4 && (ctx->img->wstack_middle != 0) != WS_MIDDLE_LAYERED) {
+        if (model) GH_CHECK(wstack_predict_layers(im->ws_gather, model));
+        GH_CHECK(wstack_middle_run(model ? im->ws_gather : nullptr, im->ws_scatter, im->ws_back, vis, im->sw, vis_res));
+        mark(ctx, 1);
+        GH_CHECK(image_pass(im, image, nullptr, im->pmaxbits, true));
+        mark(ctx, 2);
+        return GRIDHIP_OK;
+    }
     if (model) GH_CHECK(gather(im, model));
     if (model)
         hipLaunchKernelGGL(imager_middle_kernel<true>, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, (const double2 *)vis,
@@ -537,8 +613,7 @@ int gridhip_imager_cycle_dev(gridhip_imager *im, const double *model, const doub
                            im->pred, im->sw, (double2 *)vis_res);
     GH_CHECK_HIP(ctx, hipGetLastError());
     mark(ctx, 1);
-    GH_CHECK(scatter(im));
-    GH_CHECK(image_tail(ctx, im->N, im->g, im->f, image, nullptr, im->pmaxbits, im->fft));
+    GH_CHECK(image_pass(im, image, nullptr, im->pmaxbits));
     mark(ctx, 2);
     return GRIDHIP_OK;
 }
@@ -799,8 +874,7 @@ int gridhip_imager_mfs_cycle_dev(gridhip_imager *im, const double *models, const
                            (const double *)im->sp_x, (const double *)im->sw, (int)t, im->pred,
                            t == 0 ? (double2 *)vis_res : (double2 *)nullptr);
         GH_CHECK_HIP(ctx, hipGetLastError());
-        GH_CHECK(scatter(im));
-        GH_CHECK(image_tail(ctx, im->N, im->g, im->f, images + t * cells, nullptr, im->pmaxbits, im->fft));
+        GH_CHECK(image_pass(im, images + t * cells, nullptr, im->pmaxbits));
     }
     mark(ctx, 2);
     return GRIDHIP_OK;
@@ -952,6 +1026,8 @@ int gridhip_imager_destroy(gridhip_imager *im)
     gridhip_plan_destroy(im->scatter);
     gridhip_aw_plan_destroy(im->aw_gather);
     gridhip_aw_plan_destroy(im->aw_scatter);
+    wstack_release(im->ws_gather);  // (before the transform and the tables they borrow)
+    wstack_release(im->ws_scatter);
     fft_plan_drop(im->fft);
     for (void *p : im->owned)
         if (p) (void)hipFree(p);

@@ -47,7 +47,8 @@ struct ImagingState {
     int64_t mosaic_cull = 0;          // option "mosaic_cull": 1 = every tile of gridhip_mosaic walks all valid facets (the same bits)
     int64_t rm_stage = 0;             // option "rm_stage": 1 = gridhip_rmclean reads and writes the cube through LDS (the same bits)
     int64_t noisemap_hist = 0;        // option "noisemap_hist": how noise_map's node kernel builds a histogram (noisemap.hip)
-    bool noisemap_lds_raised = false; // nm_node_kernel has been allowed its 146 KB of dynamic LDS (noisemap.hip)
+    int64_t wstack_middle = 0;        // option "wstack_middle": 1 = a stack imager's cycle takes the other middle pass (imager.hip)
+    bool noisemap_lds_raised = false;// nm_node_kernel has been allowed its 146 KB of dynamic LDS (noisemap.hip)
     int64_t scratch_fill = 0;         // option "scratch_fill" (TEST HOOK): 1..255 = the byte every block is filled with first
     int64_t scratch_filled = 0;       // read-only "scratch_filled": the blocks filled so far (scratch_prefill, ctx.hip)
 };
@@ -708,10 +709,37 @@ int wstack_check(gridhip_ctx *ctx, const WStackArgs &a, int64_t *N);
 // gridhip_wstack_create_dev on checked arguments (synchronises: the plane range and the layer counts come back).  own_fft:
 // the stack keeps a transform of its own (a handle outlives the context's four cached sizes); false: the passes take the
 // context's cached one
-int wstack_create(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, gridhip_wstack **out, bool own_fft = true);
+// What an imager lends the two stacks it holds (imager.hip, the w-stacking kind), and the half of a stack each of them is:
+// 1 = the predict passes only (no scatter grid), 2 = the image passes only (no gather grid).  A lent stack builds no
+// table and makes no transform: K, conj(K) and the transform are the lender's, which outlives the stack.
+struct WsLend {
+    int half;
+    void *fft;
+    double2 *ktab, *ktab_g;
+};
+int wstack_create(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, gridhip_wstack **out, bool own_fft = true,
+                  const WsLend *lend = nullptr);
+// ktab = K[M][Q][Q][S][S], the table of the residual planes, and ktab_g = conj(K) (asynchronous)
+int wstack_tables(gridhip_ctx *ctx, const WStackArgs &a, double2 *ktab, double2 *ktab_g);
+void wstack_release(gridhip_wstack *ws);  // gridhip_wstack_destroy's
 // The two passes on device pointers: kernels and transforms only, on the stack's context's stream.
 // image = factor * Re(D(vis)), overwritten (factor 1: gridhip_wstack_image_dev; 2: do_imaging, see include/gridhip.h)
 int wstack_image_run(gridhip_wstack *ws, const double *vis, double *image, double factor);
 int wstack_predict_run(gridhip_wstack *ws, const double *model, const double *vis_sub, double *vis_out);
+// The passes without their permuting ends, for a caller that works in layer order itself: the predictions of `model` left
+// in the stack's layer-ordered block; the image of what that block holds.
+int wstack_predict_layers(gridhip_wstack *ws, const double *model);
+int wstack_image_layers(gridhip_wstack *ws, double *image, double factor);
+// the visibilities that have a layer
+int64_t wstack_count(const gridhip_wstack *ws);
+// back[j'] = j where `from` keeps at j the visibility that `to` keeps at j' (wstack_count(to) entries; the two stacks are
+// of one stream's visibilities, as an imager's un-mirrored and mirrored ones are)
+int wstack_compose(gridhip_wstack *from, gridhip_wstack *to, int32_t *back);
+// An imager's cycle middle in the layer order of `to` (ws_middle_kernel, wstack.hip): to's block = the weighted, mirrored
+// residual of vis and from's block (from = NULL: of vis alone); vis_res (or NULL, or vis) gets the residual in stream order.
+int wstack_middle_run(gridhip_wstack *from, gridhip_wstack *to, const int32_t *back, const double *vis, const double *sw,
+                      double *vis_res);
+// *maxbits = the maximum of x[0 .. cells) in ordered bits (do_imaging's pmax)
+int wstack_image_max(gridhip_ctx *ctx, int64_t cells, const double *x, unsigned long long *maxbits);
 
 }  // namespace gridhip

@@ -42,6 +42,7 @@ struct gridhip_wstack {
     double2 *ktab = nullptr, *ktab_g = nullptr;  // K (the scatter's) and conj(K) (the gather's)
     double2 *grid = nullptr, *fgrid = nullptr;   // the scatter's grid (zero between passes) and the gather's
     void *fft = nullptr;                   // the handle's own transform; null: the context's cached one (the one-call forms)
+    bool lent = false;                     // an imager's half stack: fft, ktab and ktab_g are the imager's (WsLend, imaging.h)
 };
 
 namespace gridhip {
@@ -307,6 +308,50 @@ __global__ void __launch_bounds__(256) ws_unpermute_kernel(int64_t m, const int3
     }
 }
 
+// inv[src[j]] = j: the place in a stack's layer order of every visibility that has a layer
+__global__ void __launch_bounds__(256) ws_invert_kernel(int64_t m, const int32_t *__restrict__ src, int32_t *__restrict__ inv)
+{
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x)
+        inv[src[j]] = (int32_t)j;
+}
+
+// back[j'] = inv[src[j']]: where the other stack keeps the visibility that this one keeps at j'
+__global__ void __launch_bounds__(256) ws_compose_kernel(int64_t m, const int32_t *__restrict__ src,
+                                                         const int32_t *__restrict__ inv, int32_t *__restrict__ back)
+{
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x)
+        back[j] = inv[src[j]];
+}
+
+// An imager's cycle middle (imager_middle_kernel, imager.hip) in the layer order of the mirrored stack, between the layers'
+// gathers of the un-mirrored stack and the layers' scatters of the mirrored one: for the visibility k = src[j],
+// r = vis[k] - layp[back[j]] (SUB) or vis[k]; vis_res[k] = r when asked; conj where sw[k] carries the sign, times |sw[k]|,
+// into lay[j].  The expressions and their rounding are imager_middle_kernel's, so that vis_res has the same bits either way.
+// vis_res may be vis: element k is read and written by the one lane that holds j.  A visibility without a layer is not
+// visited (the launcher fills vis_res first).
+template <bool SUB>
+__global__ void __launch_bounds__(256)
+    ws_middle_kernel(int64_t m, const int32_t *__restrict__ src, const int32_t *__restrict__ back, const double2 *vis,
+                     const double2 *__restrict__ layp, const double *__restrict__ sw, double2 *__restrict__ lay,
+                     double2 *vis_res, int32_t dropped, int32_t *__restrict__ dropped_out)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *dropped_out = dropped;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = src[j];
+        double2 r = vis[k];
+        if (SUB) {
+            const double2 p = layp[back[j]];
+            r = make_double2(r.x - p.x, r.y - p.y);
+        }
+        if (vis_res) vis_res[k] = r;
+        const double s = sw[k];
+        const double a = fabs(s);
+        if (signbit(s)) r.y = -r.y;
+        lay[j] = a == 0.0 ? make_double2(0.0, 0.0) : make_double2(a * r.x, a * r.y);  // (selected out: vis may be NaN)
+    }
+}
+
 // the maximum of x[0 .. cells) into *maxbits (ordered bits, initialised by the launcher): do_imaging's pmax
 __global__ void __launch_bounds__(256) ws_max_kernel(int64_t cells, const double *__restrict__ x,
                                                      unsigned long long *__restrict__ maxbits)
@@ -331,7 +376,7 @@ void wstack_free(gridhip_wstack *ws)
     for (WsLayer &l : ws->layers) gridhip_plan_destroy(l.plan);  // (synchronises the device)
     (void)hipSetDevice(ws->ctx->device);
     (void)hipDeviceSynchronize();
-    fft_plan_drop(ws->fft);
+    if (!ws->lent) fft_plan_drop(ws->fft);
     if (ws->base) (void)hipFree(ws->base);
     delete ws;
 }
@@ -359,7 +404,13 @@ static int wstack_fft(gridhip_wstack *ws, void **plan)
     return fft_plan_for(ws->ctx, ws->N, plan);
 }
 
-static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool own_fft, gridhip_wstack *ws)
+int wstack_tables(gridhip_ctx *ctx, const WStackArgs &a, double2 *ktab, double2 *ktab_g)
+{
+    GH_CHECK(build_w_planes(ctx, a.theta, a.wstep, -(a.M / 2) * a.wstep, a.M, a.npixFF, a.S, a.Q, ktab, true));
+    return launch_conj_copy(ctx, a.M * a.Q * a.Q * a.S * a.S, ktab, ktab_g);
+}
+
+static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool own_fft, const WsLend *lend, gridhip_wstack *ws)
 {
     const int64_t n = a.n;
     ws->ctx = ctx, ws->theta = a.theta, ws->N = N, ws->n = n, ws->wstep = a.wstep, ws->M = a.M;
@@ -393,8 +444,11 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
     const int L = (int)ws->L;
     // ---- the stack's own memory, one block
     const size_t cells = (size_t)N * N, tab = (size_t)a.M * a.Q * a.Q * a.S * a.S;
+    // (an imager's half stack: the tables are the imager's, and of the two grids it has the one its passes use)
+    const bool own_tab = !lend, own_grid = !lend || lend->half == 2, own_fgrid = !lend || lend->half == 1;
     const size_t sizes[] = {(size_t)nfinite * 8, (size_t)nfinite * 8, (size_t)nfinite * 8, (size_t)nfinite * 4,
-                            (size_t)nfinite * 16, tab * 16, tab * 16, cells * 16, cells * 16};
+                            (size_t)nfinite * 16, own_tab ? tab * 16 : 0, own_tab ? tab * 16 : 0, own_grid ? cells * 16 : 0,
+                            own_fgrid ? cells * 16 : 0};
     size_t total = 0, at[9];
     for (int i = 0; i < 9; ++i) {
         at[i] = total;
@@ -409,13 +463,15 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
     ws->pu = (double *)(b + at[0]), ws->pv = (double *)(b + at[1]), ws->rbin = (int64_t *)(b + at[2]);
     ws->src = (int32_t *)(b + at[3]), ws->lay = (double2 *)(b + at[4]);
     ws->ktab = (double2 *)(b + at[5]), ws->ktab_g = (double2 *)(b + at[6]);
-    ws->grid = (double2 *)(b + at[7]), ws->fgrid = (double2 *)(b + at[8]);
-    hipLaunchKernelGGL(ws_zero_kernel, grid_for(ctx, (int64_t)cells), dim3(256), 0, ctx->stream, (int64_t)cells * 2,
-                       (double *)ws->grid);
+    ws->grid = own_grid ? (double2 *)(b + at[7]) : nullptr, ws->fgrid = own_fgrid ? (double2 *)(b + at[8]) : nullptr;
+    if (lend) ws->lent = true, ws->fft = lend->fft, ws->ktab = lend->ktab, ws->ktab_g = lend->ktab_g;
+    if (own_grid)
+        hipLaunchKernelGGL(ws_zero_kernel, grid_for(ctx, (int64_t)cells), dim3(256), 0, ctx->stream, (int64_t)cells * 2,
+                           (double *)ws->grid);
     GH_CHECK_HIP(ctx, hipGetLastError());
     // (making a hipFFT plan loads its kernels: about 16 ms at N = 2048, as much again to drop it - a handle pays it once,
     // the one-call forms take the context's cached plan, as kind 2 does)
-    if (own_fft) GH_CHECK(fft_plan_own(ctx, N, &ws->fft));
+    if (own_fft && !lend) GH_CHECK(fft_plan_own(ctx, N, &ws->fft));
     if (L == 0) return GRIDHIP_OK;
     // ---- the layer partition: count, scan, scatter; the slices' bounds back to the host
     DevBuf dtab;  // count[L], offs[L + 1], cursor[L]
@@ -434,8 +490,7 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
     std::vector<int32_t> hoffs((size_t)L + 1);
     GH_CHECK(d2h(ctx, hoffs.data(), offs, hoffs.size() * 4));
     // ---- the kernel table of the residual planes, and its conjugate for the gather
-    GH_CHECK(build_w_planes(ctx, a.theta, a.wstep, -(a.M / 2) * a.wstep, a.M, a.npixFF, a.S, a.Q, ws->ktab, true));
-    GH_CHECK(launch_conj_copy(ctx, (int64_t)tab, ws->ktab, ws->ktab_g));
+    if (own_tab) GH_CHECK(wstack_tables(ctx, a, ws->ktab, ws->ktab_g));
     GH_CHECK(sync(ctx));
     if (hoffs[L] != nfinite) return fail(ctx, GRIDHIP_EHIP, "w-stacking: the partition lost visibilities");
     // ---- one plan per occupied layer over its slice
@@ -456,14 +511,14 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
     return GRIDHIP_OK;
 }
 
-int wstack_create(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, gridhip_wstack **out, bool own_fft)
+int wstack_create(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, gridhip_wstack **out, bool own_fft, const WsLend *lend)
 {
     *out = nullptr;
     GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     gridhip_wstack *ws = new (std::nothrow) gridhip_wstack();
     if (!ws) return GRIDHIP_ENOMEM;
     ws->ctx = ctx;
-    int rc = wstack_build(ctx, a, N, own_fft, ws);
+    int rc = wstack_build(ctx, a, N, own_fft, lend, ws);
     if (rc == GRIDHIP_OK) {
         // gridhip_last_dropped reports the whole stack, not its last layer's plan
         const int32_t d = (int32_t)ws->dropped;
@@ -480,7 +535,21 @@ int wstack_create(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, gridhip_wsta
     return GRIDHIP_OK;
 }
 
+int64_t wstack_count(const gridhip_wstack *ws) { return ws->layers.empty() ? 0 : ws->layers.back().off + ws->layers.back().cnt; }
+
 int wstack_image_run(gridhip_wstack *ws, const double *vis, double *image, double factor)
+{
+    gridhip_ctx *ctx = ws->ctx;
+    const int64_t m = wstack_count(ws);
+    if (m > 0) {
+        hipLaunchKernelGGL(ws_gather_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, ws->src, (const double2 *)vis,
+                           ws->lay, (int32_t)ws->dropped, ctx->d_scalars);
+        GH_CHECK_HIP(ctx, hipGetLastError());
+    }
+    return wstack_image_layers(ws, image, factor);
+}
+
+int wstack_image_layers(gridhip_wstack *ws, double *image, double factor)
 {
     gridhip_ctx *ctx = ws->ctx;
     const int64_t N = ws->N, cells = N * N;
@@ -492,10 +561,6 @@ int wstack_image_run(gridhip_wstack *ws, const double *vis, double *image, doubl
     if (ws->grid_dirty)
         hipLaunchKernelGGL(ws_zero_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, cells * 2, (double *)ws->grid);
     ws->grid_dirty = true;
-    const int64_t m = ws->layers.back().off + ws->layers.back().cnt;
-    hipLaunchKernelGGL(ws_gather_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, ws->src, (const double2 *)vis, ws->lay,
-                       (int32_t)ws->dropped, ctx->d_scalars);
-    GH_CHECK_HIP(ctx, hipGetLastError());
     void *fft = nullptr;
     GH_CHECK(wstack_fft(ws, &fft));
     const double scale = factor / ((double)N * (double)N);
@@ -520,14 +585,26 @@ int wstack_image_run(gridhip_wstack *ws, const double *vis, double *image, doubl
 int wstack_predict_run(gridhip_wstack *ws, const double *model, const double *vis_sub, double *vis_out)
 {
     gridhip_ctx *ctx = ws->ctx;
-    const int64_t N = ws->N, cells = N * N, n = ws->n;
+    const int64_t n = ws->n;
     if (n == 0) return GRIDHIP_OK;
     const double2 *sub = (const double2 *)vis_sub;
     double2 *out = (double2 *)vis_out;
     // a visibility without a layer: 0, or vis_sub[k] (in place: it is there already)
-    const int64_t m = ws->layers.empty() ? 0 : ws->layers.back().off + ws->layers.back().cnt;
+    const int64_t m = wstack_count(ws);
     if (m < n && sub != out) hipLaunchKernelGGL(ws_fill_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, sub, out);
     GH_CHECK_HIP(ctx, hipGetLastError());
+    if (m == 0) return GRIDHIP_OK;
+    GH_CHECK(wstack_predict_layers(ws, model));
+    hipLaunchKernelGGL(ws_unpermute_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, ws->src, ws->lay, sub, out,
+                       (int32_t)ws->dropped, ctx->d_scalars);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int wstack_predict_layers(gridhip_wstack *ws, const double *model)
+{
+    gridhip_ctx *ctx = ws->ctx;
+    const int64_t N = ws->N, cells = N * N, m = wstack_count(ws);
     if (m == 0) return GRIDHIP_OK;
     if (ws->clear_pred)
         hipLaunchKernelGGL(ws_zero_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m * 2, (double *)ws->lay);
@@ -541,11 +618,55 @@ int wstack_predict_run(gridhip_wstack *ws, const double *model, const double *vi
         GH_CHECK(gridhip_plan_degrid_dev(l.plan, (const double *)ws->ktab_g, (const double *)ws->fgrid,
                                          (double *)(ws->lay + l.off)));
     }
-    hipLaunchKernelGGL(ws_unpermute_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, ws->src, ws->lay, sub, out,
-                       (int32_t)ws->dropped, ctx->d_scalars);
+    return GRIDHIP_OK;
+}
+
+int wstack_compose(gridhip_wstack *from, gridhip_wstack *to, int32_t *back)
+{
+    gridhip_ctx *ctx = to->ctx;
+    const int64_t m = wstack_count(to);
+    if (wstack_count(from) != m || from->n != to->n)
+        return fail(ctx, GRIDHIP_EHIP, "w-stacking: the two streams of an imager differ in their finite w");
+    if (m == 0) return GRIDHIP_OK;
+    DevBuf inv;  // (every entry that is read has been written: the two stacks hold the same visibilities)
+    GH_CHECK(inv.alloc(ctx, (size_t)to->n * 4));
+    hipLaunchKernelGGL(ws_invert_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, from->src, inv.as<int32_t>());
+    hipLaunchKernelGGL(ws_compose_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, to->src, inv.as<int32_t>(), back);
     GH_CHECK_HIP(ctx, hipGetLastError());
     return GRIDHIP_OK;
 }
+
+int wstack_middle_run(gridhip_wstack *from, gridhip_wstack *to, const int32_t *back, const double *vis, const double *sw,
+                      double *vis_res)
+{
+    gridhip_ctx *ctx = to->ctx;
+    const int64_t n = to->n, m = wstack_count(to);
+    const double2 *v = (const double2 *)vis;
+    double2 *res = (double2 *)vis_res;
+    // a visibility without a layer is not visited: its residual is vis[k] (in place: it is there already)
+    if (m < n && res && res != v) hipLaunchKernelGGL(ws_fill_kernel, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, v, res);
+    if (m > 0) {
+        if (from)
+            hipLaunchKernelGGL(ws_middle_kernel<true>, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, to->src, back, v,
+                               (const double2 *)from->lay, sw, to->lay, res, (int32_t)to->dropped, ctx->d_scalars);
+        else
+            hipLaunchKernelGGL(ws_middle_kernel<false>, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, to->src, back, v,
+                               (const double2 *)nullptr, sw, to->lay, res, (int32_t)to->dropped, ctx->d_scalars);
+    }
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+int wstack_image_max(gridhip_ctx *ctx, int64_t cells, const double *x, unsigned long long *maxbits)
+{
+    static const unsigned long long neg_inf_bits = ordered_bits(-INFINITY);  // (static: the source of an async copy)
+    GH_CHECK(h2d(ctx, maxbits, &neg_inf_bits, 8));
+    hipLaunchKernelGGL(ws_max_kernel, dim3((unsigned)ctx->num_cu * 4), dim3(256), 0, ctx->stream, cells, x, maxbits);
+    GH_CHECK_HIP(ctx, hipGetLastError());
+    return GRIDHIP_OK;
+}
+
+void wstack_release(gridhip_wstack *ws) { wstack_free(ws); }
 
 namespace {
 

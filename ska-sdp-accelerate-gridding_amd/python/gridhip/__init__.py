@@ -1281,6 +1281,9 @@ class Context(Handle):
         (gridhip_imager): mirror, weights, w-bins, kernel tables, both binnings and the PSF are made here.  Returns an
         Imager whose cycle(vis, model) is do_imaging(predict(model, vis_sub=vis))'s image in one asynchronous call.  Every
         argument may be freed or changed afterwards.
+        imgfn ("wstack", dict(wstep=, planes=, qpx=, npixFF=, npixKern=)) gives an imager that owns a stack on each of the
+        two streams: its psf, pmax and cycle are do_imaging's and its predict is predict's with that tuple (2 Re of the
+        layers' sum over pmax, no Hermitian fill), and every other method works as for the other kinds.
         weighting "natural" | "uniform" | "briggs", robust, taper and weights (n cuda float64 data weights in the order of
         vis, or None) are Context.weights' (gridhip_imager_create[_aw]_weighted_dev): the density is taken on the mirrored
         baselines, a visibility whose data weight is not > 0 contributes nothing to any image even where its vis is NaN,
@@ -1437,7 +1440,9 @@ class WStack(_Bound):
 
 class Imager(_Bound):
     """The baselines of a major cycle bound once (gridhip_imager): cycle() is predict + do_imaging without anything that
-    depends on the baselines alone; psf and pmax were computed at creation."""
+    depends on the baselines alone; psf and pmax were computed at creation.  An imager made with ("wstack", kernops)
+    runs every pass on layered grids (do_imaging's and predict's "wstack" forms are the two calls it replaces); the
+    context option "wstack_middle" selects between the two ways its cycle passes from the prediction to the gridding."""
     _destroy, _what = "gridhip_imager_destroy", "imager"
 
     def __init__(self, ctx, handle, n, N, device):

@@ -117,7 +117,10 @@ def baselines(be, p, k):
 def imaging_function(be, imgfn):
     """("simple",) | ("conv", kv) | ("w_cache", kernops) -> (kind, wstep, Q, npixFF, gh, gw, kv), the leading arguments
     of gridhip_do_imaging, gridhip_predict and gridhip_imager_create_dev.  kernops = dict(wstep=, qpx=, npixFF=,
-    npixKern=) as KernelOptions (src/Gridding.hs:30-38); no wstep, or 0: 2000."""
+    npixKern=) as KernelOptions (src/Gridding.hs:30-38); no wstep, or 0: 2000.
+    ("wstack", kernops with planes=) -> (4, wstep, qpx, npixFF, npixKern, planes, None) by wstack_options' rules: the
+    kind gridhip_imager_create_dev takes for an imager that owns a stack (gridhip_do_imaging and gridhip_predict refuse
+    it: they have their _wstack forms)."""
     if imgfn[0] == "simple":
         return 0, 0, 0, 0, 0, 0, None
     if imgfn[0] == "conv":
@@ -128,6 +131,9 @@ def imaging_function(be, imgfn):
         ko = imgfn[1]
         side = int(ko["npixKern"])
         return 2, int(ko.get("wstep") or 2000), int(ko["qpx"]), int(ko["npixFF"]), side, side, None
+    if imgfn[0] == "wstack":
+        wstep, M, Q, ff, S = wstack_options(imgfn[1])
+        return 4, wstep, Q, ff, S, M, None
     raise ValueError("unknown imaging function")
 
 
