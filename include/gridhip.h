@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GRIDHIP_VERSION 310 /* 0.3.1 */
+#define GRIDHIP_VERSION 320 /* 0.3.2 */
 
 #define GRIDHIP_OK 0
 #define GRIDHIP_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -170,6 +170,8 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  * "lists_reused" = tile launches so far that were told the previous call's sorted lists are in place ("list_reuse"; the
  * kernel still sorts afresh if the verify sweep then finds the records changed);
  * "scratch_filled" = blocks filled so far on this context by the test hook "scratch_fill";
+ * "idg_chunk", "idg_split" = the visibilities the image-domain gridder ("w-stacking", IMAGE-DOMAIN LAYERS) stages in LDS at
+ * a time, and the size above which a tile's visibilities are cut into several work items;
  * "last_wgroups", "last_tile_x", "last_tile_y", "last_bigtile" = the geometry the last convgrid / convgrid2 / degrid2
  * call chose (w-groups, the LDS tile's interior, whether the tile uses all of the LDS);
  * "aw_tables_built" = kernel tables (one per batch of visibilities) the last aw gridding / degridding / imaging call or
@@ -517,11 +519,13 @@ int gridhip_predict_aw_dev(gridhip_ctx *ctx, double theta, int64_t lam, int64_t 
  * kind 0 simple, 1 conv, 2 w_cache: gridhip_do_imaging's / gridhip_predict's argument layout (w may be NULL for kinds 0
  * and 1).
  * kind 4 w-stacking (see "w-stacking"): wstep = the w step, Q = qpx, npixFF, gh = npixKern, gw = M (the planes per layer),
- * kv ignored.  The two calls it replaces are gridhip_do_imaging_wstack_dev and gridhip_predict_wstack_dev, so its image
+ * kv ignored; Q == 0: image-domain layers, npixFF the margin and gh the subgrid ("w-stacking", IMAGE-DOMAIN LAYERS: no
+ * tables, and the image and the PSF are 0 outside the trusted region).  The two calls it replaces are gridhip_do_imaging_wstack_dev and gridhip_predict_wstack_dev, so its image
  * is 2 Re D(wt vis1) / pmax, not the Hermitian fill of kinds 0 to 2 ("DO_IMAGING WITH A STACK" explains the difference),
  * and its prediction is the stack's on the un-mirrored stream.  A visibility whose w is not finite grids nothing,
  * predicts exactly 0 and leaves vis_res[k] = vis[k]; n > 0 without any finite w gives what that call gives (a division by
- * pmax = 0).  Checked at creation by the stack's rules: wstep < 1, M < 1, the w-kernel shape rule or w == NULL with n > 0
+ * pmax = 0).  Checked at creation by the stack's rules: wstep < 1, M < 1, the w-kernel shape rule (Q == 0: the subgrid and
+ * margin rule) or w == NULL with n > 0
  * are GRIDHIP_EINVAL, more than 4096 layers on either stream, M > 65536, |w / wstep| > 2^52 or n >= 2^31 - 256
  * GRIDHIP_EUNSUPPORTED.  gridhip_do_imaging* and gridhip_predict* keep refusing kind 4 (they have their _wstack forms),
  * and kind 3 is refused here (aw has its own creation calls).  The imager holds a stack on each stream - the un-mirrored
@@ -2403,7 +2407,7 @@ int gridhip_reproject_dev(gridhip_ctx *ctx, int64_t Ns, double theta_s, const do
  * planes, whatever the stream's w range, and carries at most M wstep / 2 of |w|.  (Citations: oracle/gridref_np.py;
  * tests/wstack_ref.py is the numpy restatement of this section.)
  * INPUTS.  (theta, lam), N = gridhip_image_size(theta, lam); wstep >= 1; M >= 1 planes per layer; the w-kernel shape
- * (qpx, npixFF, npixKern) under the w-kernel shape rule (at gridhip_w_kernel); a stream u, v, w in wavelengths (uv_stride as
+ * (qpx, npixFF, npixKern) under the w-kernel shape rule (at gridhip_w_kernel) - or qpx == 0, IMAGE-DOMAIN LAYERS below; a stream u, v, w in wavelengths (uv_stride as
  * everywhere).
  * PLANES AND LAYERS.  p_k = round(w_k / wstep) (libm round, half away from zero: acc_round, the plane of gridhip_wbins);
  * pmin, pmax over the visibilities with a finite w; L = (pmax - pmin) div M + 1 layers; layer_k = (p_k - pmin) div M; the
@@ -2442,7 +2446,41 @@ int gridhip_reproject_dev(gridhip_ctx *ctx, int64_t Ns, double theta_s, const do
  * takes 2 Re throughout.  gridhip_predict_wstack is the stack's predict on the stream as given (no mirror), as
  * gridhip_predict.  Both make a stack for the call and destroy it; the host forms are synchronous, the _dev forms take
  * device pointers (pmax stays a host pointer) and synchronise too.  A major-cycle loop does not call them per cycle: an
- * imager of kind 4 ("imagers") binds both streams once and is defined by these two calls. */
+ * imager of kind 4 ("imagers") binds both streams once and is defined by these two calls.
+ * IMAGE-DOMAIN LAYERS.  qpx == 0 in any of the entry points below (and Q == 0 in an imager of kind 4) selects another
+ * way to form a layer's grid G_l: image-domain gridding (van der Tol, Veenboer & Offringa 2018).  npixKern is then the
+ * subgrid size Sg, one of 16, 24, 32, and npixFF the margin K, even, 4 <= K <= Sg / 2; anything else is GRIDHIP_EINVAL,
+ * checked with the other arguments before anything is touched.  Planes, layers, pmin, L, pc_l, the screens S_l, D = sum_l S_l
+ * x ifft_c(G_l), a non-finite w, 2 Re in do_imaging and the limits are as above; the residual bin r is not used and there
+ * is no kernel table.  e(p) = exp(2 pi i p); a phase p in turns is reduced, r = p - rint(p), and evaluated by
+ * sincospi(2 r).  (tests/idg_ref.py is the numpy restatement of this paragraph.)
+ *   Cells and tiles.  T = Sg - K.  x_k = N (u_k / lam) + N div 2 (the product rounded, then the sum), y_k likewise.  A
+ *   visibility outside 0 <= x < N, 0 <= y < N (NaN included) is dropped: it grids nothing, predicts exactly 0 (vis_sub[k]
+ *   in the residual form) and is counted with the visibilities without a finite w.  Tile tx = floor(x / T), ty likewise;
+ *   subgrid origin ox = tx T - K / 2, centre cell cx = ox + Sg / 2; a_k = x_k - cx in [-T / 2, T / 2), b_k likewise;
+ *   dw_k = w_k - pc_l wstep, the exact residual w.
+ *   Subgrid image.  f_i = (i - Sg / 2) / Sg, l_i = f_i theta, ph[j][i] = 1 - sqrt(1 - l_i^2 - l_j^2);
+ *   P[j][i] = sum_k vis_k e(a_k f_i + b_k f_j - dw_k ph[j][i]) over the visibilities of the tile, and 0 where
+ *   l_i^2 + l_j^2 >= 1.
+ *   Taper.  beta = 1.15 K, t(f) = exp(beta (sqrt(1 - 4 f^2) - 1)), Pt = P t(f_i) t(f_j).
+ *   To the grid.  Gs[q][p] = Sg^-2 sum_{j,i} Pt[j][i] e(-((p - Sg / 2) f_i + (q - Sg / 2) f_j)), added to G_l at cell
+ *   (oy + q, ox + p); cells outside the grid are skipped, not wrapped, and the visibility is kept.
+ *   Correction and trusted region.  c(x) = 1 / t((x - N div 2) / N) where 8 |x - N div 2| <= 3 N, else 0; C[y][x] = c(y)
+ *   c(x); image = Re(C x D).  Outside the inner three quarters the image and the PSF are exactly 0, so pmax and every CLEAN
+ *   peak search see only cells the taper can be divided out of (C reaches 2.6e5 in the corner at K = 16).
+ *   Predict, the exact adjoint.  F_l = fft_c(conj(S_l) x C x model) (the model is read inside the trusted region only); the
+ *   Sg x Sg patch of F_l at (oy, ox), 0 outside the grid; p[j][i] = t(f_i) t(f_j) Sg^-2 sum_{q,p'} patch[q][p'] e(+((p' - Sg
+ *   / 2) f_i + (q - Sg / 2) f_j)), 0 where l_i^2 + l_j^2 >= 1; pred_k = sum_{j,i} p[j][i] e(-(a_k f_i + b_k f_j - dw_k
+ *   ph[j][i])), j outer and i inner in one thread: a prediction is bit-reproducible from run to run, an image agrees to
+ *   rounding (the subgrids are added with floating-point atomics).  The adjoint identity above holds.
+ *   The handle binds a partition by (layer, tile) - a, b, dw and the stream index of every kept visibility - and a list of
+ *   work items, one per occupied tile of a layer, a tile of more than "idg_split" visibilities cut into several (the map is
+ *   linear); no gridhip_plan and no table.  The gridder stages a work item's visibilities through LDS "idg_chunk" at a time
+ *   (both read-only options).  L x ceil(N / T)^2 above 2^26 is GRIDHIP_EUNSUPPORTED.  Accuracy against a direct Fourier
+ *   sum, and cost against the w-projection layers: DESIGN.md, section 9.
+ *   An imager of kind 4 with Q == 0: 0 <= x < N is not symmetric under the mirror (x = 0 against x = N; an odd N), so
+ *   its two stacks may keep different visibilities; it then takes the stream-order middle pass in every cycle, whatever
+ *   "wstack_middle" says, and vis_res and the image are still those of the two calls it replaces. */
 typedef struct gridhip_wstack gridhip_wstack;
 int gridhip_wstack_create_dev(gridhip_ctx *ctx, int64_t wstep, int64_t M, int64_t qpx, int64_t npixFF, int64_t npixKern,
                               double theta, int64_t lam, int64_t n, const double *u, const double *v, const double *w,

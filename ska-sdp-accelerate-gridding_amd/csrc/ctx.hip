@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "imaging.h"
+#include "idg.h"
 
 namespace gridhip {
 
@@ -589,6 +590,11 @@ int gridhip_get_option(gridhip_ctx *ctx, const char *key, int64_t *value)
         // read-only: tile launches so far that were told to trust the previous call's sorted lists (tile_sorted.hip,
         // "Kept lists"; the kernel still sorts when the verify sweep's verdict goes against the records)
         *value = ctx->lists_reused;
+        return GRIDHIP_OK;
+    }
+    if (!strcmp(key, "idg_chunk") || !strcmp(key, "idg_split")) {
+        // read-only: the image-domain gridder's LDS chunk and the tile size above which a tile is cut (idg.h)
+        *value = key[4] == 'c' ? IDG_CHUNK : IDG_SPLIT;
         return GRIDHIP_OK;
     }
     if (!strcmp(key, "scratch_filled")) {

@@ -418,7 +418,9 @@ int make(gridhip_imager *im, const Kernels &k, double lam, const double *u, cons
         lend.half = 2;
         GH_CHECK(wstack_create(ctx, a, N, &im->ws_scatter, false, &lend));
         GH_CHECK(own(im, &im->ws_back, (size_t)wstack_count(im->ws_scatter) * 4));
-        GH_CHECK(wstack_compose(im->ws_gather, im->ws_scatter, im->ws_back));
+        bool same = true;
+        GH_CHECK(wstack_compose(im->ws_gather, im->ws_scatter, im->ws_back, &same));
+        if (!same) im->ws_back = nullptr;  // (image-domain layers only: every cycle takes the stream-order middle)
     } else {
         // the gather's kernels are conj(aw_kernel_fn2(conj wk, conj ak)) (predict_aw); the aw plans keep what they build
         const size_t wel = (size_t)k.W * fn.Q * fn.Q * k.S * k.S, ael = (size_t)k.A * k.S * k.S;
@@ -596,7 +598,7 @@ int gridhip_imager_cycle_dev(gridhip_imager *im, const double *model, const doub
     mark(ctx, 0);
     // w-stacking: the middle pass in the mirrored stack's layer order, between the layers' gathers and the layers' scatters
     // - or (option "wstack_middle" = 1) the generic one below, in stream order between the stacks' two permuting passes
-    if (im->kind == 4 && (ctx->img->wstack_middle != 0) != WS_MIDDLE_LAYERED) {
+    if (im->kind == 4 && im->ws_back && (ctx->img->wstack_middle != 0) != WS_MIDDLE_LAYERED) {
         if (model) GH_CHECK(wstack_predict_layers(im->ws_gather, model));
         GH_CHECK(wstack_middle_run(model ? im->ws_gather : nullptr, im->ws_scatter, im->ws_back, vis, im->sw, vis_res));
         mark(ctx, 1);

@@ -733,8 +733,10 @@ int wstack_image_layers(gridhip_wstack *ws, double *image, double factor);
 // the visibilities that have a layer
 int64_t wstack_count(const gridhip_wstack *ws);
 // back[j'] = j where `from` keeps at j the visibility that `to` keeps at j' (wstack_count(to) entries; the two stacks are
-// of one stream's visibilities, as an imager's un-mirrored and mirrored ones are)
-int wstack_compose(gridhip_wstack *from, gridhip_wstack *to, int32_t *back);
+// of one stream's visibilities, as an imager's un-mirrored and mirrored ones are).  *same: the two stacks keep the same
+// visibilities - always, but for image-domain layers, which drop what lies off the grid of their own stream: then false,
+// `back` is not to be used and the caller takes the passes in stream order.  Synchronises for image-domain layers.
+int wstack_compose(gridhip_wstack *from, gridhip_wstack *to, int32_t *back, bool *same);
 // An imager's cycle middle in the layer order of `to` (ws_middle_kernel, wstack.hip): to's block = the weighted, mirrored
 // residual of vis and from's block (from = NULL: of vis alone); vis_res (or NULL, or vis) gets the residual in stream order.
 int wstack_middle_run(gridhip_wstack *from, gridhip_wstack *to, const int32_t *back, const double *vis, const double *sw,

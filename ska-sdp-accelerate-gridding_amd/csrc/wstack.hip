@@ -14,6 +14,7 @@
 // cell anyway and the shift's share is added to it in turns, reduced exactly in integers.
 #include "common.h"
 #include "imaging.h"
+#include "idg.h"
 
 namespace gridhip {
 
@@ -21,6 +22,7 @@ struct WsLayer {
     int64_t pc = 0;             // the centre plane pc_l
     int64_t off = 0, cnt = 0;   // its slice of the layer-ordered arrays
     gridhip_plan *plan = nullptr;
+    int64_t ioff = 0, icnt = 0;  // image-domain layers: its slice of the work items (no plan)
 };
 
 }  // namespace gridhip
@@ -37,6 +39,10 @@ struct gridhip_wstack {
     void *base = nullptr;
     double *pu = nullptr, *pv = nullptr;   // u / lam, v / lam in layer order
     int64_t *rbin = nullptr;               // the residual bins r
+    // image-domain layers (qpx == 0; idg.hip): Sg != 0, pu / pv / rbin hold a, b and the exact residual w (a double) in
+    // (layer, tile) order, there is no table and no plan
+    int Sg = 0, K = 0;
+    gridhip::IdgItem *items = nullptr;     // the work items, a block of their own
     int32_t *src = nullptr;                // the visibility's index in the stream
     double2 *lay = nullptr;                // n values in layer order: the gathered vis of a grid pass, the predictions
     double2 *ktab = nullptr, *ktab_g = nullptr;  // K (the scatter's) and conj(K) (the gather's)
@@ -51,9 +57,7 @@ namespace {
 
 constexpr int WS_ITEMS = 8;  // visibilities per thread and chunk of the scatter pass
 
-// the plane of a finite w: libm round, as the w-bin rule (wround_kernel, image_ops.hip)
-__device__ __forceinline__ double plane_of(double w, double wstep) { return round(w / wstep); }
-__device__ __forceinline__ bool finite_w(double w) { return fabs(w) < __builtin_inf(); }
+// (plane_of, finite_w and layer_of, the plane and layer rules, are in idg.h: the image-domain partition shares them)
 
 // minimum and maximum plane over the finite w (ordered bits: imaging.h) and how many there are
 __global__ void __launch_bounds__(256) ws_range_kernel(int64_t n, const double *__restrict__ w, int64_t stride, double wstep,
@@ -92,21 +96,10 @@ __global__ void __launch_bounds__(256) ws_range_kernel(int64_t n, const double *
     }
 }
 
-// tab[0 .. L] = 0 (the counts and the scan's total), before the counting pass
-__global__ void __launch_bounds__(256) ws_zero_i32_kernel(int64_t n, int32_t *__restrict__ a)
+// a[0 .. n) = value: tab[0 .. L] = 0 (the counts and the scan's total) before the counting pass; -1 in wstack_compose
+__global__ void __launch_bounds__(256) ws_fill_i32_kernel(int64_t n, int32_t *__restrict__ a, int32_t value)
 {
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) a[k] = 0;
-}
-
-// The layer of visibility k, or -1 without a finite w; *r: its residual bin.  pmin and M are exact in doubles (the host
-// has checked |plane| <= 2^52), and (p - pmin) / M is below L <= 4096.
-__device__ __forceinline__ int layer_of(double w, double wstep, double pmin, int64_t M, int64_t *r)
-{
-    if (!finite_w(w)) return -1;
-    const int64_t d = (int64_t)(plane_of(w, wstep) - pmin);
-    const int64_t l = d / M;
-    *r = d - l * M;
-    return (int)l;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) a[k] = value;
 }
 
 // the counting pass: a histogram of the layers per work-group in LDS, added to count[L] at the end
@@ -234,9 +227,11 @@ __device__ __forceinline__ void turns_sincos(double a, int64_t q, int64_t N, dou
 // transformed cell (the output roll is the index), times the input roll's phase and the screen S_l = exp(-2 pi i wc ph),
 // its real part times `scale` added to the image (stored by the first layer), and a zero written back, so that the grid
 // is clear for the next layer.  Every cell of h is read and cleared by exactly one thread.
-template <bool FIRST>
+// IDG (image-domain layers, margin K): the cell times the correction C[y][x] = c(y) c(x), and exactly 0 outside the
+// trusted region; the w-projection stack's instantiations are as they were.
+template <bool FIRST, bool IDG>
 __global__ void __launch_bounds__(256) ws_screen_kernel(int64_t N, double theta, double wc, double2 *__restrict__ h,
-                                                        double *__restrict__ image, double scale)
+                                                        double *__restrict__ image, double scale, int K)
 {
     const int64_t cells = N * N, s = N / 2, m = (N + 1) / 2;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (int64_t)gridDim.x * blockDim.x) {
@@ -253,15 +248,21 @@ __global__ void __launch_bounds__(256) ws_screen_kernel(int64_t N, double theta,
             const int64_t q = (s * (ky + kx)) % N;
             turns_sincos(-(wc * ph), q == 0 ? 0 : N - q, N, &sn, &cs);
             val = scale * (z.x * cs - z.y * sn);
+            if (IDG) {
+                const double corr = idg_correction(y, N, K) * idg_correction(x, N, K);
+                val = corr == 0.0 ? 0.0 : val * corr;
+            }
         }
         image[c] = FIRST ? val : image[c] + val;
     }
 }
 
 // The head of one layer of a predict pass: f = X' of the file's head, X = conj(S_l) x model = model exp(+2 pi i wc ph), in
-// the forward transform's input order, so that the transform's output is fft_c(X) as it lies.
+// the forward transform's input order, so that the transform's output is fft_c(X) as it lies.  IDG: X = conj(S_l) x C x
+// model, and a cell outside the trusted region is not read.
+template <bool IDG>
 __global__ void __launch_bounds__(256) ws_head_kernel(int64_t N, double theta, double wc, const double *__restrict__ model,
-                                                      double2 *__restrict__ f)
+                                                      double2 *__restrict__ f, int K)
 {
     const int64_t cells = N * N, s = N / 2, m = (N + 1) / 2;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (int64_t)gridDim.x * blockDim.x) {
@@ -275,8 +276,16 @@ __global__ void __launch_bounds__(256) ws_head_kernel(int64_t N, double theta, d
             // turns: +wc ph - m (jy + jx) / N
             const int64_t q = (m * (jy + jx)) % N;
             turns_sincos(wc * ph, q == 0 ? 0 : N - q, N, &sn, &cs);
-            const double a = model[y * N + x];
-            out = make_double2(a * cs, a * sn);
+            if (IDG) {
+                const double corr = idg_correction(y, N, K) * idg_correction(x, N, K);
+                if (corr != 0.0) {
+                    const double a = corr * model[y * N + x];
+                    out = make_double2(a * cs, a * sn);
+                }
+            } else {
+                const double a = model[y * N + x];
+                out = make_double2(a * cs, a * sn);
+            }
         }
         f[c] = out;
     }
@@ -315,12 +324,17 @@ __global__ void __launch_bounds__(256) ws_invert_kernel(int64_t m, const int32_t
         inv[src[j]] = (int32_t)j;
 }
 
-// back[j'] = inv[src[j']]: where the other stack keeps the visibility that this one keeps at j'
+// back[j'] = inv[src[j']]: where the other stack keeps the visibility that this one keeps at j'; *miss (when given) is
+// set where the other stack does not keep it (inv = -1)
 __global__ void __launch_bounds__(256) ws_compose_kernel(int64_t m, const int32_t *__restrict__ src,
-                                                         const int32_t *__restrict__ inv, int32_t *__restrict__ back)
+                                                         const int32_t *__restrict__ inv, int32_t *__restrict__ back,
+                                                         int32_t *__restrict__ miss)
 {
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x)
-        back[j] = inv[src[j]];
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t i = inv[src[j]];
+        back[j] = i;
+        if (miss && i < 0) *miss = 1;
+    }
 }
 
 // An imager's cycle middle (imager_middle_kernel, imager.hip) in the layer order of the mirrored stack, between the layers'
@@ -378,6 +392,7 @@ void wstack_free(gridhip_wstack *ws)
     (void)hipDeviceSynchronize();
     if (!ws->lent) fft_plan_drop(ws->fft);
     if (ws->base) (void)hipFree(ws->base);
+    if (ws->items) (void)hipFree(ws->items);
     delete ws;
 }
 
@@ -386,9 +401,11 @@ void wstack_free(gridhip_wstack *ws)
 int wstack_check(gridhip_ctx *ctx, const WStackArgs &a, int64_t *N)
 {
     *N = gridhip_image_size(a.theta, a.lam);
-    if (*N <= 0 || a.wstep < 1 || a.M < 1 || !w_kernel_shape_ok(a.npixFF, a.S, a.Q) || a.n < 0 || a.stride < 1 ||
+    // (qpx == 0: image-domain layers, npixKern the subgrid and npixFF the margin)
+    const bool shape_ok = a.Q == 0 ? idg_shape_ok(a.S, a.npixFF) : w_kernel_shape_ok(a.npixFF, a.S, a.Q);
+    if (*N <= 0 || a.wstep < 1 || a.M < 1 || !shape_ok || a.n < 0 || a.stride < 1 ||
         (a.n > 0 && (!a.u || !a.v || !a.w)))
-        return fail(ctx, GRIDHIP_EINVAL, "w-stacking: bad argument (wstep, planes >= 1, the w-kernel shape rule, image size %lld)",
+        return fail(ctx, GRIDHIP_EINVAL, "w-stacking: bad argument (wstep, planes >= 1, the w-kernel shape rule or, with qpx 0, subgrid 16 / 24 / 32 and an even margin in [4, subgrid / 2], image size %lld)",
                     (long long)*N);
     if (a.n > (int64_t)0x7fffff00) return fail(ctx, GRIDHIP_EUNSUPPORTED, "n must be < 2^31 per stack");
     if (a.M > WS_MAX_PLANES) return fail(ctx, GRIDHIP_EUNSUPPORTED, "%lld planes per layer (at most 65536)", (long long)a.M);
@@ -406,6 +423,7 @@ static int wstack_fft(gridhip_wstack *ws, void **plan)
 
 int wstack_tables(gridhip_ctx *ctx, const WStackArgs &a, double2 *ktab, double2 *ktab_g)
 {
+    if (a.Q == 0) return GRIDHIP_OK;  // image-domain layers have no table
     GH_CHECK(build_w_planes(ctx, a.theta, a.wstep, -(a.M / 2) * a.wstep, a.M, a.npixFF, a.S, a.Q, ktab, true));
     return launch_conj_copy(ctx, a.M * a.Q * a.Q * a.S * a.S, ktab, ktab_g);
 }
@@ -414,6 +432,8 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
 {
     const int64_t n = a.n;
     ws->ctx = ctx, ws->theta = a.theta, ws->N = N, ws->n = n, ws->wstep = a.wstep, ws->M = a.M;
+    const bool idg = a.Q == 0;
+    if (idg) ws->Sg = (int)a.S, ws->K = (int)a.npixFF;
     // ---- the plane range of the finite w, back to the host (as the w-bin rule of w_cache_imaging reads its own back)
     unsigned long long range[3] = {~0ULL, 0ULL, 0ULL};
     if (n > 0) {
@@ -473,11 +493,27 @@ static int wstack_build(gridhip_ctx *ctx, const WStackArgs &a, int64_t N, bool o
     // the one-call forms take the context's cached plan, as kind 2 does)
     if (own_fft && !lend) GH_CHECK(fft_plan_own(ctx, N, &ws->fft));
     if (L == 0) return GRIDHIP_OK;
+    if (idg) {
+        // ---- image-domain layers: the partition by (layer, tile), a, b and the exact residual w in place of pu, pv and r
+        std::vector<IdgSlice> slices;
+        GH_CHECK(idg_partition(ctx, a, N, pmin, L, nfinite, ws->pu, ws->pv, (double *)ws->rbin, ws->src, &slices, &ws->items));
+        int64_t kept = 0;
+        for (int l = 0; l < L; ++l) {
+            kept += slices[l].cnt;
+            if (slices[l].cnt <= 0) continue;
+            WsLayer lay;
+            lay.pc = ws->pmin + (int64_t)l * a.M + a.M / 2;
+            lay.off = slices[l].off, lay.cnt = slices[l].cnt, lay.ioff = slices[l].ioff, lay.icnt = slices[l].icnt;
+            ws->layers.push_back(lay);
+        }
+        ws->dropped = n - kept;  // (outside the grid, or NaN in u or v: with those without a finite w)
+        return GRIDHIP_OK;
+    }
     // ---- the layer partition: count, scan, scatter; the slices' bounds back to the host
     DevBuf dtab;  // count[L], offs[L + 1], cursor[L]
     GH_CHECK(dtab.alloc(ctx, (size_t)(3 * L + 1) * 4));
     int32_t *count = dtab.as<int32_t>(), *offs = count + L, *cursor = offs + L + 1;
-    hipLaunchKernelGGL(ws_zero_i32_kernel, dim3(1), dim3(256), 0, ctx->stream, (int64_t)(3 * L + 1), count);
+    hipLaunchKernelGGL(ws_fill_i32_kernel, dim3(1), dim3(256), 0, ctx->stream, (int64_t)(3 * L + 1), count, 0);
     unsigned gc = grid_for(ctx, n).x;  // (every work-group ends with up to L global adds: few, long ones)
     if (gc > (unsigned)ctx->num_cu * 4) gc = (unsigned)ctx->num_cu * 4;
     hipLaunchKernelGGL(ws_count_kernel, dim3(gc), dim3(256), (size_t)L * 4, ctx->stream, n, a.w, a.stride, (double)a.wstep,
@@ -566,15 +602,18 @@ int wstack_image_layers(gridhip_wstack *ws, double *image, double factor)
     const double scale = factor / ((double)N * (double)N);
     bool first = true;
     for (const WsLayer &l : ws->layers) {
-        GH_CHECK(gridhip_plan_grid_dev(l.plan, (const double *)ws->ktab, (const double *)(ws->lay + l.off), (double *)ws->grid));
+        if (ws->Sg)
+            GH_CHECK(idg_grid(ctx, ws->Sg, ws->K, N, ws->theta, ws->items + l.ioff, l.icnt, ws->pu, ws->pv,
+                              (const double *)ws->rbin, ws->lay, ws->grid));
+        else
+            GH_CHECK(gridhip_plan_grid_dev(l.plan, (const double *)ws->ktab, (const double *)(ws->lay + l.off),
+                                           (double *)ws->grid));
         GH_CHECK(fft_exec(ctx, fft, ws->grid, true));
         const double wc = (double)l.pc * (double)ws->wstep;
-        if (first)
-            hipLaunchKernelGGL(ws_screen_kernel<true>, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, ws->theta, wc, ws->grid,
-                               image, scale);
-        else
-            hipLaunchKernelGGL(ws_screen_kernel<false>, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, ws->theta, wc,
-                               ws->grid, image, scale);
+        auto screen = ws->Sg ? (first ? ws_screen_kernel<true, true> : ws_screen_kernel<false, true>)
+                             : (first ? ws_screen_kernel<true, false> : ws_screen_kernel<false, false>);
+        hipLaunchKernelGGL(screen, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, ws->theta, wc, ws->grid, image, scale,
+                           ws->K);
         GH_CHECK_HIP(ctx, hipGetLastError());
         first = false;
     }
@@ -611,28 +650,52 @@ int wstack_predict_layers(gridhip_wstack *ws, const double *model)
     void *fft = nullptr;
     GH_CHECK(wstack_fft(ws, &fft));
     for (const WsLayer &l : ws->layers) {
-        hipLaunchKernelGGL(ws_head_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, N, ws->theta,
-                           (double)l.pc * (double)ws->wstep, model, ws->fgrid);
+        hipLaunchKernelGGL(ws->Sg ? ws_head_kernel<true> : ws_head_kernel<false>, grid_for(ctx, cells), dim3(256), 0, ctx->stream,
+                           N, ws->theta, (double)l.pc * (double)ws->wstep, model, ws->fgrid, ws->K);
         GH_CHECK_HIP(ctx, hipGetLastError());
         GH_CHECK(fft_exec(ctx, fft, ws->fgrid, false));
-        GH_CHECK(gridhip_plan_degrid_dev(l.plan, (const double *)ws->ktab_g, (const double *)ws->fgrid,
-                                         (double *)(ws->lay + l.off)));
+        if (ws->Sg)
+            GH_CHECK(idg_degrid(ctx, ws->Sg, ws->K, N, ws->theta, ws->items + l.ioff, l.icnt, l.cnt, ws->pu, ws->pv,
+                                (const double *)ws->rbin, ws->fgrid, ws->lay));
+        else
+            GH_CHECK(gridhip_plan_degrid_dev(l.plan, (const double *)ws->ktab_g, (const double *)ws->fgrid,
+                                             (double *)(ws->lay + l.off)));
     }
     return GRIDHIP_OK;
 }
 
-int wstack_compose(gridhip_wstack *from, gridhip_wstack *to, int32_t *back)
+int wstack_compose(gridhip_wstack *from, gridhip_wstack *to, int32_t *back, bool *same)
 {
     gridhip_ctx *ctx = to->ctx;
     const int64_t m = wstack_count(to);
-    if (wstack_count(from) != m || from->n != to->n)
-        return fail(ctx, GRIDHIP_EHIP, "w-stacking: the two streams of an imager differ in their finite w");
+    *same = true;
+    // Image-domain layers drop a visibility that lies off the grid, and 0 <= x < N is not symmetric under the mirror (x = 0
+    // against x = N; an odd N): the two stacks may keep different visibilities, which is found here and is no error.
+    const bool idg = to->Sg != 0;
+    if (wstack_count(from) != m || from->n != to->n) {
+        if (!idg) return fail(ctx, GRIDHIP_EHIP, "w-stacking: the two streams of an imager differ in their finite w");
+        *same = false;
+        return GRIDHIP_OK;
+    }
     if (m == 0) return GRIDHIP_OK;
-    DevBuf inv;  // (every entry that is read has been written: the two stacks hold the same visibilities)
-    GH_CHECK(inv.alloc(ctx, (size_t)to->n * 4));
+    // (w-projection: every entry that is read has been written, the two stacks hold the same visibilities; image-domain
+    // layers: inv starts at -1, and its last entry is set when `to` keeps a visibility that `from` does not)
+    DevBuf inv;
+    GH_CHECK(inv.alloc(ctx, (size_t)(to->n + 1) * 4));
+    int32_t *miss = idg ? inv.as<int32_t>() + to->n : nullptr;
+    if (idg) {
+        hipLaunchKernelGGL(ws_fill_i32_kernel, grid_for(ctx, to->n), dim3(256), 0, ctx->stream, to->n, inv.as<int32_t>(), -1);
+        hipLaunchKernelGGL(ws_fill_i32_kernel, dim3(1), dim3(256), 0, ctx->stream, (int64_t)1, miss, 0);
+    }
     hipLaunchKernelGGL(ws_invert_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, from->src, inv.as<int32_t>());
-    hipLaunchKernelGGL(ws_compose_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, to->src, inv.as<int32_t>(), back);
+    hipLaunchKernelGGL(ws_compose_kernel, grid_for(ctx, m), dim3(256), 0, ctx->stream, m, to->src, inv.as<int32_t>(), back, miss);
     GH_CHECK_HIP(ctx, hipGetLastError());
+    if (idg) {
+        int32_t h = 0;
+        GH_CHECK(d2h(ctx, &h, miss, 4));
+        GH_CHECK(sync(ctx));
+        *same = h == 0;
+    }
     return GRIDHIP_OK;
 }
 

@@ -35,7 +35,7 @@ from ._marshal import automask_args, mask_in_place, source_args
 from ._marshal import group_ids, rotation as _rotation
 from ._marshal import weighting as _weighting
 from ._marshal import mosaic_args
-from ._marshal import wstack_options
+from ._marshal import idg_options, idg_trusted, stack_options, wstack_options
 from ._marshal import JOINT_MAX_PLANES, joint_search, psf_planes
 from ._marshal import RM_MAPS, rm_clean_scalars, rm_cube, rm_images, rm_table_args, rm_table_doubles, rm_table_of
 from ._marshal import contsub_args
@@ -46,7 +46,7 @@ from ._marshal import TEC_HEAD, TEC_KAPPA, TEC_MAX_CELLS, TEC_MAX_DELAYS, TEC_PE
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
            "waterfall_layout", "rm_tile", "faraday_grid", "contsub_tile", "channel_coordinate",
-           "fringe_tile", "fringe_grid", "tec_tile", "tec_grid", "tec_clock", "tec_coordinates", "TEC_KAPPA"]
+           "fringe_tile", "fringe_grid", "tec_tile", "tec_grid", "tec_clock", "tec_coordinates", "TEC_KAPPA", "idg_trusted"]
 
 
 class Context(Handle):
@@ -327,7 +327,10 @@ class Context(Handle):
     def do_imaging(self, theta, lam, uvw, a1, a2, t, f, vis, imgfn):
         """:509-549 -> (image, psf, pmax).  imgfn = ("simple",) | ("conv", kv) | ("w_cache", kernops) |
         ("aw", wkernels, wbins, akernels) | ("wstack", dict(wstep=, planes=, qpx=, npixFF=, npixKern=)) - w-stacking, whose
-        image is 2 Re D instead of the Hermitian fill (include/gridhip.h, "w-stacking"); a1, a2 feed the antenna indices of "aw" (not swapped by the mirror), t, f
+        image is 2 Re D instead of the Hermitian fill (include/gridhip.h, "w-stacking") | ("idg", dict(wstep=, planes=,
+        subgrid=, margin=)) - the same stack with image-domain layers: every visibility with its exact w on subgrids of
+        `subgrid` (16, 24, 32) cells with a margin of `margin` (even, 4 .. subgrid / 2), no kernel table; image and psf are
+        exactly 0 outside the trusted region [idg_trusted(N), idg_trusted(N)]; a1, a2 feed the antenna indices of "aw" (not swapped by the mirror), t, f
         (src) are accepted for signature parity and unused by these imaging functions.
         torch cuda tensors (uvw, vis, and kv / the aw tables and antennas) take the device-resident form
         (gridhip_do_imaging_dev / gridhip_do_imaging_aw_dev): nothing crosses PCIe, image and psf come back as cuda
@@ -338,8 +341,8 @@ class Context(Handle):
         if imgfn[0] == "aw":
             tables, a1, a2 = aw_tables(be, imgfn[1], imgfn[2], imgfn[3], a1, a2)
             self._call(be, "do_imaging_aw", *tl, *tables, *stream, a1, a2, vis, img, psf, C.byref(pmax))
-        elif imgfn[0] == "wstack":
-            self._call(be, "do_imaging_wstack", *wstack_options(imgfn[1]), *tl, *stream, vis, img, psf, C.byref(pmax))
+        elif imgfn[0] in ("wstack", "idg"):
+            self._call(be, "do_imaging_wstack", *stack_options(imgfn), *tl, *stream, vis, img, psf, C.byref(pmax))
         else:
             self._call(be, "do_imaging", *imaging_function(be, imgfn), *tl, *stream, vis, img, psf, C.byref(pmax))
         return img, psf, pmax.value
@@ -359,7 +362,8 @@ class Context(Handle):
         """Visibilities of a real N x N model image (gridhip_predict[_aw][_dev]): the adjoint of the imaging function
         `imgfn` applied to fft_c(model), or vis_sub minus that (the residual) when vis_sub is given.  imgfn takes
         do_imaging's tuples: ("simple",) | ("conv", kv) | ("w_cache", kernops) | ("aw", wkernels, wbins, akernels), the
-        last with the antenna indices a1, a2, | ("wstack", kernops with planes=).  uvw (wavelengths, not mirrored) as the imaging function takes it.
+        last with the antenna indices a1, a2, | ("wstack", kernops with planes=) | ("idg", dict(wstep=, planes=, subgrid=,
+        margin=)), which reads the model inside the trusted region only.  uvw (wavelengths, not mirrored) as the imaging function takes it.
         numpy in gives numpy out; torch cuda tensors take the device form on torch's stream and return a cuda tensor.
         out: the array to write (may be vis_sub itself: an in-place residual); a new one when None."""
         be = backend(model)
@@ -378,8 +382,8 @@ class Context(Handle):
         if imgfn[0] == "aw":
             tables, a1, a2 = aw_tables(be, imgfn[1], imgfn[2], imgfn[3], a1, a2)
             self._call(be, "predict_aw", *tl, *tables, model, n, u, v, w, st, a1, a2, sub, out)
-        elif imgfn[0] == "wstack":
-            self._call(be, "predict_wstack", *wstack_options(imgfn[1]), *tl, model, n, u, v, w, st, sub, out)
+        elif imgfn[0] in ("wstack", "idg"):
+            self._call(be, "predict_wstack", *stack_options(imgfn), *tl, model, n, u, v, w, st, sub, out)
         else:
             self._call(be, "predict", *imaging_function(be, imgfn), *tl, model, n, u, v, w, st, sub, out)
         return out
@@ -1284,6 +1288,8 @@ class Context(Handle):
         imgfn ("wstack", dict(wstep=, planes=, qpx=, npixFF=, npixKern=)) gives an imager that owns a stack on each of the
         two streams: its psf, pmax and cycle are do_imaging's and its predict is predict's with that tuple (2 Re of the
         layers' sum over pmax, no Hermitian fill), and every other method works as for the other kinds.
+        imgfn ("idg", dict(wstep=, planes=, subgrid=, margin=)) gives the same imager with image-domain layers; it needs every
+        visibility it keeps on the grid of both streams (u and -u: the library refuses a stream that is not).
         weighting "natural" | "uniform" | "briggs", robust, taper and weights (n cuda float64 data weights in the order of
         vis, or None) are Context.weights' (gridhip_imager_create[_aw]_weighted_dev): the density is taken on the mirrored
         baselines, a visibility whose data weight is not > 0 contributes nothing to any image even where its vis is NaN,
@@ -1308,10 +1314,11 @@ class Context(Handle):
         """Bind the stream `uvw` (torch cuda tensors, wavelengths, taken as given: no mirror, no weights) for w-stacking
         (gridhip_wstack; include/gridhip.h, "w-stacking"): kernops = dict(wstep=, planes=, qpx=, npixFF=, npixKern=), planes
         the w-planes per layer.  The stream is cut into layers, each binned once, and the table of the residual
-        w-kernels is built here.  Returns a WStack whose image() / predict() are one asynchronous, capturable pass each;
+        w-kernels is built here.  kernops may also be a whole tuple ("wstack", kernops) or ("idg", dict(wstep=, planes=,
+        subgrid=, margin=)); the latter makes a stack of image-domain layers: a partition by (layer, tile), no table.  Returns a WStack whose image() / predict() are one asynchronous, capturable pass each;
         uvw may be freed or changed afterwards."""
         be = device()
-        opts = wstack_options(kernops)
+        opts = stack_options(kernops) if isinstance(kernops, tuple) else wstack_options(kernops)
         u, v, w, st = baselines(be, uvw, 3)
         n, h = int(u.shape[0]), C.c_void_p()
         self._call(be, "wstack_create", *opts, float(theta), int(lam), n, u, v, w, st, C.byref(h))

@@ -120,7 +120,9 @@ def imaging_function(be, imgfn):
     npixKern=) as KernelOptions (src/Gridding.hs:30-38); no wstep, or 0: 2000.
     ("wstack", kernops with planes=) -> (4, wstep, qpx, npixFF, npixKern, planes, None) by wstack_options' rules: the
     kind gridhip_imager_create_dev takes for an imager that owns a stack (gridhip_do_imaging and gridhip_predict refuse
-    it: they have their _wstack forms)."""
+    it: they have their _wstack forms).
+    ("idg", dict(wstep=, planes=, subgrid=, margin=)) -> (4, wstep, 0, margin, subgrid, planes, None) by idg_options' rules:
+    the same kind with image-domain layers, which qpx = 0 selects."""
     if imgfn[0] == "simple":
         return 0, 0, 0, 0, 0, 0, None
     if imgfn[0] == "conv":
@@ -131,8 +133,8 @@ def imaging_function(be, imgfn):
         ko = imgfn[1]
         side = int(ko["npixKern"])
         return 2, int(ko.get("wstep") or 2000), int(ko["qpx"]), int(ko["npixFF"]), side, side, None
-    if imgfn[0] == "wstack":
-        wstep, M, Q, ff, S = wstack_options(imgfn[1])
+    if imgfn[0] in ("wstack", "idg"):
+        wstep, M, Q, ff, S = stack_options(imgfn)
         return 4, wstep, Q, ff, S, M, None
     raise ValueError("unknown imaging function")
 
@@ -148,6 +150,41 @@ def wstack_options(ko):
     if not (ff > 0 and S > 0 and Q > 0 and S <= ff and (ff * Q) // 2 - Q * (S // 2) >= Q - 1):
         raise ValueError(f"wstack: npixFF={ff}, npixKern={S}, qpx={Q} is outside the w-kernel shape rule")
     return wstep, M, Q, ff, S
+
+
+IDG_SUBGRIDS = (16, 24, 32)
+
+
+def idg_options(ko):
+    """dict(wstep=, planes=, subgrid=, margin=) -> (wstep, M, 0, margin, subgrid), the leading arguments of the w-stacking
+    entry points for image-domain layers (include/gridhip.h, "w-stacking", IMAGE-DOMAIN LAYERS): qpx = 0 selects them, npixFF
+    carries the margin and npixKern the subgrid; no wstep, or 0: 2000.  What the library would refuse is refused here, before
+    any call: wstep or planes below 1, a subgrid other than 16, 24 or 32, a margin that is odd or outside [4, subgrid / 2]."""
+    wstep, M = int(ko.get("wstep") or 2000), int(ko["planes"])
+    Sg, K = int(ko["subgrid"]), int(ko["margin"])
+    if wstep < 1 or M < 1:
+        raise ValueError(f"idg: wstep ({wstep}) and planes ({M}) must be >= 1")
+    if Sg not in IDG_SUBGRIDS:
+        raise ValueError(f"idg: subgrid ({Sg}) must be one of {IDG_SUBGRIDS}")
+    if K % 2 or not 4 <= K <= Sg // 2:
+        raise ValueError(f"idg: margin ({K}) must be even and in [4, subgrid / 2 = {Sg // 2}]")
+    return wstep, M, 0, K, Sg
+
+
+def stack_options(imgfn):
+    """("wstack", kernops) | ("idg", options) -> the five leading arguments of the w-stacking entry points"""
+    if imgfn[0] == "idg":
+        return idg_options(imgfn[1])
+    if imgfn[0] == "wstack":
+        return wstack_options(imgfn[1])
+    raise ValueError("a stack is made from (\"wstack\", kernops) or (\"idg\", options)")
+
+
+def idg_trusted(N):
+    """The slice of the cells of either axis of an N x N image that image-domain layers fill (8 |x - N div 2| <= 3 N, the
+    inner three quarters): image[idg_trusted(N), idg_trusted(N)] is the trusted region, every other cell is exactly 0."""
+    N = int(N)
+    return slice(N // 2 - (3 * N) // 8, N // 2 + (3 * N) // 8 + 1)
 
 
 def aw_tables(be, wkernels, wbins, akernels, a1, a2):
