@@ -48,16 +48,17 @@ def make_w(rng, n, M, L, partial=False):
 _cases = {}
 
 
-def case(N, msq, L, seed=11, span=0.4, partial=False):
-    """a stream, a model, the restatement's plan and its outputs, computed once per (shape, kernel, layers)"""
-    key = (N, msq, L, seed, span, partial)
+def case(N, msq, L, seed=11, span=0.4, partial=False, n=NVIS):
+    """a stream of n visibilities, a model, the restatement's plan and its outputs, computed once per (shape, kernel,
+    layers, n)"""
+    key = (N, msq, L, seed, span, partial, n)
     if key not in _cases:
         theta, lam = SHAPES[N]
         M, S, Q = msq
         rng = np.random.default_rng(seed)
-        u, v = rng.uniform(-span * lam, span * lam, NVIS), rng.uniform(-span * lam, span * lam, NVIS)
-        w = make_w(rng, NVIS, M, L, partial)
-        vis = rng.normal(size=NVIS) + 1j * rng.normal(size=NVIS)
+        u, v = rng.uniform(-span * lam, span * lam, n), rng.uniform(-span * lam, span * lam, n)
+        w = make_w(rng, n, M, L, partial)
+        vis = rng.normal(size=n) + 1j * rng.normal(size=n)
         model = rng.normal(size=(N, N))
         ref = W.Stack(theta, lam, u, v, w, WSTEP, M, Q, NPIXFF, S)
         _cases[key] = dict(theta=theta, lam=lam, N=N, u=u, v=v, w=w, vis=vis, model=model, ref=ref, opts=opts(M, S, Q),

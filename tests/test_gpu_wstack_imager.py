@@ -55,9 +55,9 @@ def restatement(c, key, M, S, Q):
 
 
 # ---- 1: against the calls it replaces, and against the restatement -------------------------------------------------------------
-def against_the_calls(ctx, N, msq, L):
+def against_the_calls(ctx, N, msq, L, n=NVIS):
     import torch
-    c = case(N, msq, L)
+    c = case(N, msq, L, n=n)
     assert (c["v"] < 0).any() and (c["v"] >= 0).any() and (c["u"] < 0).any()
     im = make(ctx, c)
     dvis, dmodel = to_dev(c["vis"]), to_dev(c["model"])
@@ -81,7 +81,7 @@ def against_the_calls(ctx, N, msq, L):
     e["cycle twice"] = rel(host(im.cycle(dvis, dmodel)), r_img2)
     e["cycle(None) twice"] = rel(host(im.cycle(dvis)), r_img)
     # the restatement
-    ref, n_img, n_img2 = restatement(c, (N, msq, L), *msq)
+    ref, n_img, n_img2 = restatement(c, (N, msq, L, n), *msq)
     e["psf vs numpy"], e["pmax vs numpy"] = rel(host(im.psf), ref.psf), abs(im.pmax - ref.pmax) / ref.pmax
     e["cycle(None) vs numpy"] = rel(host(im.cycle(dvis)), n_img)
     e["cycle(model) vs numpy"] = rel(host(im.cycle(dvis, dmodel)), n_img2)
