@@ -2,7 +2,7 @@
 // interval, antenna) by the multi-direction StEFCal, and the subtraction of corrupted directions from a visibility stream.
 // The scheme is gaincal.hip's - the stop condition lives in the state block, niter iterations are enqueued unconditionally
 // and a launch whose state is stopped returns at its first instruction - with a D x D normal matrix per (t, a) in place
-// of one ratio.
+// of one ratio, and what is the same in words is gain_common.h's: the interval walk, the driver, the entry point.
 //
 //     ddcal_init_kernel      the [T][A][D^2 + 2 D] table and the solved flags start from zero, the gains from 1
 //     ddcal_prepare_kernel   one pass over V, M, s, a1, a2, slot: s V (16 B), s (8 B) and the packed 8-byte key per
@@ -20,7 +20,7 @@
 //               ddcal_solve_kernel<D>  one work-group: thread i takes the cells i, i + 512, ...: LDL^H in direction
 //                                      order, the pivot rule, the phase-only and averaging rules, rel in a fixed order,
 //                                      the stop test; zeroes the table for the next iteration }
-//     ddcal_finish_kernel    one work-group: the rotation per direction and interval, the number of unsolved (t, a)
+//     gc_finish_kernel       (gain_common.h) one work-group: the rotation per direction and interval, the unsolved (t, a)
 //     ddcal_chi_kernel       one pass with the final gains: chi^2 against the full sum over the directions
 //     gaincal_stats_kernel   (gain_common.h) the 8 doubles
 //     dd_subtract_kernel     vis_out = vis_in - the corrupted models of the chosen directions, one pass
@@ -33,9 +33,6 @@
 namespace gridhip {
 
 namespace {
-
-constexpr int DD_CU_THREADS = 1024;  // threads of ddcal_iter_kernel a CU holds (launch bound 1024: 128 VGPRs a lane)
-constexpr int64_t DD_CU_LDS = 160 * 1024;
 
 __host__ __device__ constexpr int dd_sums(int D) { return D * D + 2 * D; }  // doubles of H's upper triangle and b
 
@@ -79,15 +76,11 @@ __global__ void __launch_bounds__(256)
             }
             x = make_double2(s * v.x, s * v.y);
             chi0 += s * norm2(r);
-            kk = GC_USED | (unsigned long long)p | (unsigned long long)q << 21 | (unsigned long long)t << 42;
+            kk = gc_pack(p, q, t);
         }
         sV[k] = x, S[k] = c == 0 ? s : 0.0, key[k] = kk;
     }
-    const double r[GC_PARTS] = {chi0, (double)used, (double)flagged, (double)dropped};
-    for (int j = 0; j < GC_PARTS; ++j) {
-        const double x = block_sum(r[j], lds);
-        if (threadIdx.x == 0) parts[(int64_t)blockIdx.x * GC_PARTS + j] = x;
-    }
+    gc_prepare_tail(chi0, used, flagged, dropped, parts, lds);
 }
 
 // One side of one visibility into the sums of its antenna: row = { H[d,d] (D), H[d,e] d < e row by row (re, im), b[d] (re,
@@ -135,93 +128,48 @@ __device__ __forceinline__ void dd_visibility(int64_t n, int64_t k, const double
     dd_add<D>(rq, z, s, make_double2(sv.x, -sv.y));
 }
 
-// One iteration's sums, A <= gridhip_ddcal_lds_antennas(D).  Work-group b takes the visibilities [b * per, (b + 1) * per),
-// per a whole number of chunks, in steps of 4 blockDim.x: thread i holds the keys of base + i + blockDim.x j.  lg [A][D],
-// acc [A][D^2 + 2 D]: the gains and the sums of interval tcur.  The interval logic is gaincal_iter_kernel's.
+// What gc_walk needs of this module: lg [A][D] from the caller's [D][T][A], acc [A][D^2 + 2 D].  D > 3: one visibility at a
+// time - unrolled, the loads of all four are hoisted together and the lane spills.  DdSolve<D> below adds the driver's part.
+template <int D>
+struct DdMod {
+    static constexpr int NS = dd_sums(D), NG = D, GSTEP = 1, UNROLL = D > 3 ? 1 : 4;
+    struct In {
+        int64_t n;
+        const double2 *sV;
+        const double *S;
+        const double2 *M;
+    };
+    using Held = GcNoHeld;
+    static __device__ __forceinline__ void load_gains(double2 *lg, const double2 *__restrict__ g, long long tn, int A, int64_t T)
+    {
+        for (int a = threadIdx.x, nt = blockDim.x; a < D * A; a += nt) lg[a] = g[((int64_t)(a % D) * T + tn) * A + a / D];
+    }
+    static __device__ __forceinline__ void add(const In &in, const Held &, int, int64_t k, const double2 *gp,
+                                               const double2 *gq, int64_t gstride, double *rp, double *rq)
+    {
+        dd_visibility<D>(in.n, k, in.sV, in.S, in.M, gp, gq, gstride, rp, rq);
+    }
+};
+
+// One iteration's sums, A <= gridhip_ddcal_lds_antennas(D): gc_walk with dynamic LDS, (D^2 + 4 D) * 8 bytes per antenna
 template <int D>
 __global__ void __launch_bounds__(1024)
     ddcal_iter_kernel(int64_t n, int A, int64_t T, int64_t per, const double2 *__restrict__ sV, const double *__restrict__ S,
                       const unsigned long long *__restrict__ key, const double2 *__restrict__ M,
                       const double2 *__restrict__ g, double *table, const GcState *st)
 {
-    if (st->stopped) return;
-    constexpr int NS = dd_sums(D), DD_UNROLL = D > 3 ? 1 : 4;
     extern __shared__ double2 dd_lds[];
-    __shared__ unsigned int tsel;
-    double2 *lg = dd_lds;
-    double *acc = reinterpret_cast<double *>(dd_lds + (size_t)D * A);
-    const int nt = blockDim.x;
-    for (int a = threadIdx.x; a < NS * A; a += nt) acc[a] = 0.0;
-    const int64_t k0 = (int64_t)blockIdx.x * per, k1 = k0 + per < n ? k0 + per : n;
-    long long tcur = -1;
-    for (int64_t base = k0; base < k1; base += 4 * nt) {
-        unsigned long long kk[4];
-        unsigned int pend = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t k = base + threadIdx.x + (int64_t)nt * j;
-            kk[j] = k < k1 ? key[k] : 0ull;
-            if (kk[j] & GC_USED) pend |= 1u << j;
-        }
-        for (;;) {
-            // (D > 3: one visibility at a time - unrolled, the loads of all four are hoisted together and the lane spills)
-#pragma unroll DD_UNROLL
-            for (int j = 0; j < 4; ++j) {
-                const unsigned long long kj = j == 0 ? kk[0] : j == 1 ? kk[1] : j == 2 ? kk[2] : kk[3];
-                if (!(pend >> j & 1u) || (long long)(kj >> 42 & GC_FIELD) != tcur) continue;
-                const int p = (int)(kj & GC_FIELD), q = (int)(kj >> 21 & GC_FIELD);
-                dd_visibility<D>(n, base + threadIdx.x + (int64_t)nt * j, sV, S, M, lg + p * D, lg + q * D, 1, acc + p * NS,
-                                 acc + q * NS);
-                pend &= ~(1u << j);
-            }
-            if (!__syncthreads_or(pend != 0)) break;  // (a barrier: every add into tcur's sums is done)
-            if (threadIdx.x == 0) tsel = 0xffffffffu;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (pend >> j & 1u) atomicMin(&tsel, (unsigned int)(kk[j] >> 42 & GC_FIELD));
-            __syncthreads();
-            const long long tn = tsel;
-            if (tcur >= 0) {
-                double *rows = table + (size_t)tcur * A * NS;
-                for (int a = threadIdx.x; a < NS * A; a += nt) {
-                    const double v = acc[a];
-                    if (v != 0.0) atomicAdd(&rows[a], v);
-                    acc[a] = 0.0;
-                }
-            }
-            for (int a = threadIdx.x; a < D * A; a += nt) lg[a] = g[((int64_t)(a % D) * T + tn) * A + a / D];
-            __syncthreads();
-            tcur = tn;
-        }
-    }
-    __syncthreads();
-    if (tcur >= 0) {
-        double *rows = table + (size_t)tcur * A * NS;
-        for (int a = threadIdx.x; a < NS * A; a += nt) {
-            const double v = acc[a];
-            if (v != 0.0) atomicAdd(&rows[a], v);
-        }
-    }
+    gc_walk<DdMod<D>>(typename DdMod<D>::In{n, sV, S, M}, n, A, T, per, key, g, table, st, dd_lds,
+                      reinterpret_cast<double *>(dd_lds + (size_t)D * A));
 }
 
-// the same sums for any A: gains from global memory, fp64 atomics straight to the table
 template <int D>
 __global__ void __launch_bounds__(256)
     ddcal_iter_global_kernel(int64_t n, int64_t A, int64_t T, const double2 *__restrict__ sV, const double *__restrict__ S,
                              const unsigned long long *__restrict__ key, const double2 *__restrict__ M,
                              const double2 *__restrict__ g, double *table, const GcState *st)
 {
-    if (st->stopped) return;
-    constexpr int NS = dd_sums(D);
-    const int64_t k0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t k = k0; k < n; k += step) {
-        const unsigned long long kk = key[k];
-        if (!(kk & GC_USED)) continue;
-        const int64_t t = (int64_t)(kk >> 42 & GC_FIELD), p = t * A + (int64_t)(kk & GC_FIELD),
-                      q = t * A + (int64_t)(kk >> 21 & GC_FIELD);
-        dd_visibility<D>(n, k, sV, S, M, g + p, g + q, T * A, table + p * NS, table + q * NS);
-    }
+    gc_walk_global<DdMod<D>>(typename DdMod<D>::In{n, sV, S, M}, n, A, T, key, g, table, st);
 }
 
 // One work-group of 512 threads: thread i takes the cells i, i + 512, ... in order.  H = L diag(dj) L^H with L unit lower
@@ -318,50 +266,7 @@ __global__ void __launch_bounds__(512)
             s2 += norm2(gn);
         }
     }
-    d2 = block_sum(d2, lds);
-    s2 = block_sum(s2, lds);
-    if (threadIdx.x != 0) return;
-    const double rel = sqrt(d2 / s2);
-    st->rel = rel;
-    st->iters += 1;
-    if (tol > 0.0 && rel <= tol) st->stopped = 1;
-}
-
-// One work-group of 1024 threads.  rot[d,t] as gaincal_finish_kernel's rot[t], from g[d,t,refant]; the gains of a
-// direction and interval are read (rot) before any is written: a barrier lies between.
-__global__ void __launch_bounds__(1024)
-    ddcal_finish_kernel(int64_t A, int64_t T, int D, int64_t refant, const unsigned int *__restrict__ ever, double2 *g,
-                        double2 *__restrict__ rot, GcState *st)
-{
-#pragma clang fp contract(off)
-    __shared__ double lds[16];
-    const int64_t cells = A * T;
-    if (refant >= 0) {
-        for (int64_t i = threadIdx.x; i < D * T; i += 1024) {
-            const int64_t t = i % T;
-            const double2 r = g[i * A + refant];
-            const double a = sqrt(norm2(r));
-            rot[i] = (ever[t * A + refant] && a > 0.0 && a - a == 0.0) ? make_double2(r.x / a, -r.y / a)
-                                                                      : make_double2(1.0, 0.0);
-        }
-        __syncthreads();
-    }
-    double un = 0.0;
-    for (int64_t i = threadIdx.x; i < D * cells; i += 1024) {
-        const int64_t d = i / cells, e = i - d * cells;
-        if (!ever[e]) {  // unsolved: counted once, and its gains stay the bits they started from
-            un += d == 0 ? 1.0 : 0.0;
-            continue;
-        }
-        if (refant < 0) continue;
-        const int64_t t = e / A;
-        const double2 r = rot[d * T + t];
-        if (r.x == 1.0 && r.y == 0.0) continue;
-        const double2 go = g[i];
-        g[i] = e - t * A == refant ? make_double2(sqrt(norm2(go)), 0.0) : cmul(go, r);
-    }
-    un = block_sum(un, lds);
-    if (threadIdx.x == 0) st->unsolved = (long long)un;
+    gc_close_iteration(d2, s2, tol, st, lds);
 }
 
 // the corrupted model of direction d at visibility k, every product rounded
@@ -418,50 +323,65 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// the rules the solve and the subtraction share: the sizes, the limit on the table
-int dd_shape_check(gridhip_ctx *ctx, const char *who, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1,
-                   const int64_t *a2, const int64_t *slot)
-{
-    if (n < 0 || A < 2 || T < 1 || D < 1 || D > DD_MAX_D || (!slot && T != 1) || (n > 0 && (!a1 || !a2)))
-        return fail(ctx, GRIDHIP_EINVAL, "%s: n >= 0, A >= 2, T >= 1, D in 1..%d, a slot array unless T == 1, a1 and a2", who,
-                    DD_MAX_D);
-    if (A > GC_MAX_TABLE || T > GC_MAX_TABLE || A * T > GC_MAX_TABLE || D * A * T > GC_MAX_TABLE)
-        return fail(ctx, GRIDHIP_EUNSUPPORTED, "%s: D * A * T above %lld", who, (long long)GC_MAX_TABLE);
-    return GRIDHIP_OK;
-}
-
+// what gc_solve_run needs of this module: its launches; every plane of the gains [D][T][A] takes its own rotation
 template <int D>
-int dd_iterate(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const double2 *sV, const double *S,
-               const unsigned long long *key, const double2 *M, double2 *g, double *table, unsigned int *ever, GcState *st,
-               int mode, int64_t niter, double tol)
-{
-    const int64_t cells = A * T;
-    const bool lds = A <= gridhip_ddcal_lds_antennas(D);
-    const size_t bytes = (size_t)A * (dd_sums(D) + 2 * D) * 8;
-    // a CU holds DD_CU_THREADS threads of the kernel: as many work-groups as tables fit, each the larger for it
-    const int fit = lds ? (int)(DD_CU_LDS / (int64_t)(bytes + 64)) : 0;
-    const int block = fit >= 4 ? 256 : fit >= 2 ? 512 : 1024, resident = DD_CU_THREADS / block;
-    if (lds && n > 0 && !(ctx->img->ddcal_lds_raised >> D & 1u)) {  // (more than 64 KB of LDS only once the function is told so)
-        GH_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ddcal_iter_kernel<D>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)DD_LDS_BUDGET));
-        ctx->img->ddcal_lds_raised |= 1u << D;
+struct DdSolve : DdMod<D> {
+    static constexpr int BLOCK = 0, RESIDENT = 0, RAISE_BIT = D;
+    static constexpr int64_t LDS_MOST = DD_LDS_BUDGET;
+    static constexpr bool PAIR = true;  // s V
+    static const void *walker() { return reinterpret_cast<const void *>(ddcal_iter_kernel<D>); }
+    static int64_t lds_antennas() { return gridhip_ddcal_lds_antennas(D); }
+    static GcPlanes planes(const GcCall &c) { return {D, c.A * c.T, 1, true, 0u}; }
+    static void init(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(ddcal_init_kernel, grid_for(ctx, c.A * c.T * dd_sums(D)), dim3(256), 0, ctx->stream, c.A * c.T, D,
+                           c.warm, w.table, w.ever, w.g);
     }
-    // the iteration kernel's ranges: whole chunks, and no more work-groups than are resident at once
-    const int64_t nchunks = (n + GC_CHUNK - 1) / GC_CHUNK, most = (int64_t)ctx->num_cu * resident;
-    const int64_t cpw = nchunks > most ? (nchunks + most - 1) / most : 1;
-    const int64_t igrid = nchunks > 0 ? (nchunks + cpw - 1) / cpw : 0;
-    for (int64_t i = 0; i < niter; ++i) {
-        if (n > 0 && lds)
-            hipLaunchKernelGGL(ddcal_iter_kernel<D>, dim3((unsigned)igrid), dim3(block), bytes, ctx->stream, n, (int)A, T,
-                               cpw * GC_CHUNK, sV, S, key, M, (const double2 *)g, table, (const GcState *)st);
-        else if (n > 0)
-            hipLaunchKernelGGL(ddcal_iter_global_kernel<D>, grid_for(ctx, n), dim3(256), 0, ctx->stream, n, A, T, sV, S, key,
-                               M, (const double2 *)g, table, (const GcState *)st);
-        hipLaunchKernelGGL(ddcal_solve_kernel<D>, dim3(1), dim3(512), 0, ctx->stream, cells, mode, tol, table, ever, g, st);
+    static void prepare(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(ddcal_prepare_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, c.T, D, c.a1, c.a2, c.slot,
+                           (const double2 *)c.vis, (const double2 *)c.model_vis, c.wt, w.pair, w.real, w.key, w.parts);
     }
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    return GRIDHIP_OK;
-}
+    static void iter(gridhip_ctx *ctx, const GcCall &c, const GcWork &w, bool lds, dim3 grid, dim3 block, size_t bytes,
+                     int64_t per)
+    {
+        const double2 *M = (const double2 *)c.model_vis;
+        if (lds)
+            hipLaunchKernelGGL(ddcal_iter_kernel<D>, grid, block, bytes, ctx->stream, c.n, (int)c.A, c.T, per,
+                               (const double2 *)w.pair, (const double *)w.real, (const unsigned long long *)w.key, M,
+                               (const double2 *)w.g, w.table, (const GcState *)w.st);
+        else
+            hipLaunchKernelGGL(ddcal_iter_global_kernel<D>, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, c.T,
+                               (const double2 *)w.pair, (const double *)w.real, (const unsigned long long *)w.key, M,
+                               (const double2 *)w.g, w.table, (const GcState *)w.st);
+    }
+    static void update(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(ddcal_solve_kernel<D>, dim3(1), dim3(512), 0, ctx->stream, c.A * c.T, c.mode, c.tol, w.table,
+                           w.ever, w.g, w.st);
+    }
+    static void final(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(ddcal_chi_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, c.T, D, c.a1, c.a2, c.slot,
+                           (const double2 *)w.g, (const double2 *)c.vis, (const double2 *)c.model_vis, c.wt, w.parts);
+    }
+};
+
+// what gc_solve_any needs: the rules, and the driver of the call's D
+struct DdAny {
+    static GcRules rules(const GcCall &c) { return {"ddcal", 1, true, 16, 16 * (size_t)c.D, (size_t)c.D * c.A * c.T * 16}; }
+    static int run(gridhip_ctx *ctx, const GcCall &c)
+    {
+#define DD_CASE(d) \
+    case d:        \
+        return gc_solve_run<DdSolve<d>>(ctx, c);
+        switch (c.D) {
+            DD_CASE(1) DD_CASE(2) DD_CASE(3) DD_CASE(4) DD_CASE(5) DD_CASE(6) DD_CASE(7) DD_CASE(8)
+        }
+#undef DD_CASE
+        return GRIDHIP_EINVAL;  // (ddcal_check lets no other D through)
+    }
+};
 
 }  // namespace
 
@@ -469,15 +389,8 @@ int ddcal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, co
                 const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
                 int64_t niter, double tol, const double *gains)
 {
-    if (n < 0 || A < 2 || T < 1 || D < 1 || D > DD_MAX_D || (!slot && T != 1) ||
-        (n > 0 && (!a1 || !a2 || !vis || !model_vis)) || !gains || niter < 0 || !(tol >= 0.0) || mode < 0 || mode > 1 ||
-        refant >= A)
-        return fail(ctx, GRIDHIP_EINVAL, "ddcal: bad argument");
-    GH_CHECK(dd_shape_check(ctx, "ddcal", n, A, T, D, a1, a2, slot));
-    const size_t gb = (size_t)D * A * T * 16, n8 = (size_t)n * 8;
-    if (overlaps_any({gains, gb}, {{a1, n8}, {a2, n8}, {slot, n8}, {vis, 2 * n8}, {model_vis, 2 * n8 * D}, {wt, n8}}))
-        return fail(ctx, GRIDHIP_EINVAL, "ddcal: gains must not overlap an input");
-    return GRIDHIP_OK;
+    const GcCall c = {n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, 0, niter, tol, const_cast<double *>(gains)};
+    return gc_solve_check(ctx, DdAny::rules(c), c);
 }
 
 int dd_subtract_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
@@ -487,7 +400,7 @@ int dd_subtract_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t
     if (n < 0 || A < 2 || T < 1 || D < 1 || D > DD_MAX_D || (!slot && T != 1) ||
         (n > 0 && (!a1 || !a2 || !model_vis || !vis_out)) || !gains || dirs < 0 || (dirs >> D) != 0)
         return fail(ctx, GRIDHIP_EINVAL, "dd_subtract: bad argument");
-    GH_CHECK(dd_shape_check(ctx, "dd_subtract", n, A, T, D, a1, a2, slot));
+    GH_CHECK(shape_check(ctx, "dd_subtract", n, A, T, a1, a2, slot, &D));
     const size_t gb = (size_t)D * A * T * 16, n8 = (size_t)n * 8;
     if (overlaps_any({vis_out, 2 * n8}, {{gains, gb}, {a1, n8}, {a2, n8}, {slot, n8}, {model_vis, 2 * n8 * D}}))
         return fail(ctx, GRIDHIP_EINVAL, "dd_subtract: vis_out overlaps gains, model_vis, a1, a2 or slot");
@@ -524,50 +437,7 @@ int ddcal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, cons
               const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
               int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    const int64_t cells = A * T;
-    const dim3 sgrid = grid_for(ctx, n);  // the prepare pass and the chi^2 pass: one row of partial sums per work-group
-    DevBuf small, table, ever, sV, S, key;
-    GH_CHECK(small.alloc(ctx, ((size_t)GC_HEAD + (size_t)GC_PARTS * ctx->num_cu * 16 + 2 * (size_t)D * T) * 8));
-    GH_CHECK(table.alloc(ctx, (size_t)cells * dd_sums((int)D) * 8));
-    GH_CHECK(ever.alloc(ctx, (size_t)cells * 4));
-    if (n > 0) {
-        GH_CHECK(sV.alloc(ctx, (size_t)n * 16));
-        GH_CHECK(S.alloc(ctx, (size_t)n * 8));
-        GH_CHECK(key.alloc(ctx, (size_t)n * 8));
-    }
-    GcState *st = small.as<GcState>();
-    double *parts = small.as<double>() + GC_HEAD;
-    double2 *rot = reinterpret_cast<double2 *>(parts + (size_t)GC_PARTS * ctx->num_cu * 16);
-    double2 *g = (double2 *)gains;
-    const double2 *M = (const double2 *)model_vis;
-    hipLaunchKernelGGL(ddcal_init_kernel, grid_for(ctx, cells * dd_sums((int)D)), dim3(256), 0, ctx->stream, cells, (int)D,
-                       warm, table.as<double>(), ever.as<unsigned int>(), g);
-    if (n > 0)
-        hipLaunchKernelGGL(ddcal_prepare_kernel, sgrid, dim3(256), 0, ctx->stream, n, A, T, (int)D, a1, a2, slot,
-                           (const double2 *)vis, M, wt, sV.as<double2>(), S.as<double>(), key.as<unsigned long long>(),
-                           parts);
-    hipLaunchKernelGGL(gaincal_begin_kernel, dim3(1), dim3(256), 0, ctx->stream, n > 0 ? (int)sgrid.x : 0,
-                       (const double *)parts, st);
-    GH_CHECK_HIP(ctx, hipGetLastError());
-#define DD_CASE(d)                                                                                                         \
-    case d:                                                                                                                \
-        GH_CHECK(dd_iterate<d>(ctx, n, A, T, sV.as<double2>(), S.as<double>(), key.as<unsigned long long>(), M, g,         \
-                               table.as<double>(), ever.as<unsigned int>(), st, mode, niter, tol));                        \
-        break;
-    switch (D) {
-        DD_CASE(1) DD_CASE(2) DD_CASE(3) DD_CASE(4) DD_CASE(5) DD_CASE(6) DD_CASE(7) DD_CASE(8)
-    }
-#undef DD_CASE
-    hipLaunchKernelGGL(ddcal_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, A, T, (int)D, refant,
-                       (const unsigned int *)ever.as<unsigned int>(), g, rot, st);
-    if (n > 0)
-        hipLaunchKernelGGL(ddcal_chi_kernel, sgrid, dim3(256), 0, ctx->stream, n, A, T, (int)D, a1, a2, slot,
-                           (const double2 *)g, (const double2 *)vis, M, wt, parts);
-    if (stats)
-        hipLaunchKernelGGL(gaincal_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, n > 0 ? (int)sgrid.x : 0,
-                           (const double *)parts, (const GcState *)st, stats);
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    return GRIDHIP_OK;
+    return DdAny::run(ctx, {n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats});
 }
 
 }  // namespace gridhip
@@ -575,24 +445,6 @@ int ddcal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, cons
 using namespace gridhip;
 
 namespace {
-
-int ddcal_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
-              const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
-              int warm, int64_t niter, double tol, double *gains, double *stats)
-{
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(ddcal_check(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8, gb = (size_t)D * A * T * 16;
-    Staged st(ctx, dev);
-    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), vis = st.in(vis, 2 * n8);
-    model_vis = st.in(model_vis, 2 * n8 * D), wt = st.in(wt, n8);
-    gains = warm ? st.inout(gains, gains, gb) : st.out(gains, gb);  // (a cold start reads no gains)
-    stats = st.out(stats, 64);
-    GH_CHECK(st.status());
-    GH_CHECK(ddcal_run(ctx, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats));
-    return st.finish();
-}
 
 int dd_subtract_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1,
                     const int64_t *a2, const int64_t *slot, const double *gains, const double *model_vis, int64_t dirs,
@@ -624,14 +476,16 @@ int gridhip_ddcal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t
                       const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                       int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    return ddcal_any(ctx, true, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return gc_solve_any<DdAny>(ctx, true, {n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol,
+                                           gains, stats});
 }
 
 int gridhip_ddcal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1, const int64_t *a2,
                   const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                   int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    return ddcal_any(ctx, false, n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return gc_solve_any<DdAny>(ctx, false, {n, A, T, D, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol,
+                                            gains, stats});
 }
 
 int gridhip_dd_subtract_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, int64_t D, const int64_t *a1,

@@ -8,7 +8,8 @@
 //                             visibility, and the sums that do not depend on the gains (chi^2 at g = 1, used, flagged,
 //                             dropped) - one row of partial sums per work-group, no atomics
 //     gaincal_begin_kernel    one work-group adds the rows in a fixed order and starts the state block (gain_common.h,
-//                             with everything else ddcal.hip shares: the key, the state block, the classes, the products)
+//                             with everything else ddcal.hip and jonescal.hip share: the key, the state block, the classes,
+//                             the products, the interval walk gc_walk, the driver gc_solve_run and the entry gc_solve_any)
 //     niter x { gaincal_iter_kernel    streams key, X, Y (32 B per visibility).  A work-group takes a contiguous range of
 //                                      whole chunks of GC_CHUNK visibilities, keeps the gains and a (num.re, num.im, den)
 //                                      accumulator of ONE interval in LDS (A <= GC_LDS_A: 16 A + 24 A bytes, 20 KB at
@@ -19,7 +20,7 @@
 //                                      A > GC_LDS_A: gaincal_iter_global_kernel adds to the global table directly.
 //               gaincal_update_kernel  one work-group: g' from the table, the phase-only and averaging rules, rel in a
 //                                      fixed order, the stop test; zeroes the table for the next iteration }
-//     gaincal_finish_kernel   one work-group: the reference-antenna rotation and the number of unsolved (t, a)
+//     gc_finish_kernel        (gain_common.h) one work-group: the reference-antenna rotation and the number of unsolved (t, a)
 //     gaincal_stream_kernel   one pass over the visibilities with the final gains: chi^2 (partial rows), and - selfcal -
 //                             the corrected visibilities and weights in the same pass; alone it is gridhip_apply_gains
 //     gaincal_stats_kernel    one work-group adds the chi^2 rows in a fixed order and writes the 8 doubles (gain_common.h)
@@ -34,11 +35,11 @@ namespace gridhip {
 
 namespace {
 
-// work-groups of gaincal_iter_kernel resident on a CU: the kernel takes 82 VGPRs, which the hardware allocates as 88, so a
+// work-groups of gaincal_iter_kernel resident on a CU: the kernel takes 84 VGPRs, which the hardware allocates as 88, so a
 // SIMD holds 512 / 88 = 5 waves and a CU five work-groups of four waves (LDS, 20.3 KB each, would allow seven)
 constexpr int GC_RESIDENT = 5;
-constexpr int GC_STEP = 1024;  // visibilities a work-group takes between two barriers: 4 per thread
-static_assert(GC_CHUNK % GC_STEP == 0, "a chunk is whole steps");
+constexpr int GC_BLOCK = 256;  // its work-group: a step of the walk is 4 visibilities per thread
+static_assert(GC_CHUNK % (4 * GC_BLOCK) == 0, "a chunk is whole steps");
 
 // cells: T * A.  The table (3 doubles per cell) and the flags (one 32-bit word per cell) are zeroed; warm: the gains stay
 __global__ void __launch_bounds__(256)
@@ -78,113 +79,62 @@ __global__ void __launch_bounds__(256)
             y = s * norm2(m);
             const double2 r = make_double2(v.x - m.x, v.y - m.y);
             chi0 += s * norm2(r);
-            kk = GC_USED | (unsigned long long)p | (unsigned long long)q << 21 | (unsigned long long)t << 42;
+            kk = gc_pack(p, q, t);
         }
         X[k] = x, Y[k] = y, key[k] = kk;
     }
-    const double r[GC_PARTS] = {chi0, (double)used, (double)flagged, (double)dropped};
-    for (int j = 0; j < GC_PARTS; ++j) {
-        const double x = block_sum(r[j], lds);
-        if (threadIdx.x == 0) parts[(int64_t)blockIdx.x * GC_PARTS + j] = x;
-    }
+    gc_prepare_tail(chi0, used, flagged, dropped, parts, lds);
 }
 
-// One iteration's sums, A <= GC_LDS_A.  Work-group b takes the visibilities [b * per, (b + 1) * per), per a whole number
-// of chunks, in steps of GC_STEP: thread i holds the visibilities base + i + 256 j.  lg, acc: the gains and the sums of
-// interval tcur.  A step whose used visibilities all lie in tcur costs one barrier; otherwise the work-group agrees on the
-// lowest interval still pending, flushes, loads that interval's gains and goes on until nothing is pending.
-__global__ void __launch_bounds__(256)
+// What gc_walk needs of this module.  A lane loads X and Y of its four visibilities (32 B each) at the start of a step,
+// before the interval loop; the add is the two sides' (num.re, num.im, den).  GcSolve below adds the driver's part.
+struct GcMod {
+    static constexpr int NS = 3, NG = 1, GSTEP = 1, UNROLL = 4;
+    struct In {
+        const double2 *X;
+        const double *Y;
+    };
+    struct Held {
+        double2 x[4];
+        double y[4];
+        __device__ __forceinline__ void load(const In &in, int j, int64_t k, bool there)
+        {
+            x[j] = there ? in.X[k] : make_double2(0.0, 0.0);
+            y[j] = there ? in.Y[k] : 0.0;
+        }
+    };
+    static __device__ __forceinline__ void load_gains(double2 *lg, const double2 *__restrict__ g, long long tn, int A, int64_t)
+    {
+        gc_copy_gains(lg, g, tn, A);
+    }
+    static __device__ __forceinline__ void add(const In &, const Held &h, int j, int64_t, const double2 *gp,
+                                               const double2 *gq, int64_t, double *rp, double *rq)
+    {
+        const double2 x = h.x[j], a = *gp, b = *gq;
+        const double y = h.y[j];
+        const double2 np = cmul(x, b), nq = cmul(make_double2(x.x, -x.y), a);
+        atomicAdd(&rp[0], np.x), atomicAdd(&rp[1], np.y), atomicAdd(&rp[2], y * norm2(b));
+        atomicAdd(&rq[0], nq.x), atomicAdd(&rq[1], nq.y), atomicAdd(&rq[2], y * norm2(a));
+    }
+};
+
+// One iteration's sums, A <= GC_LDS_A: gc_walk with static LDS, 16 A + 24 A bytes
+__global__ void __launch_bounds__(GC_BLOCK)
     gaincal_iter_kernel(int64_t n, int A, int64_t per, const double2 *__restrict__ X, const double *__restrict__ Y,
                         const unsigned long long *__restrict__ key, const double2 *__restrict__ g, double *table,
                         const GcState *st)
 {
-    if (st->stopped) return;
     __shared__ double2 lg[GC_LDS_A];
     __shared__ double acc[3 * GC_LDS_A];
-    __shared__ unsigned int tsel;
-    for (int a = threadIdx.x; a < 3 * A; a += 256) acc[a] = 0.0;
-    const int64_t k0 = (int64_t)blockIdx.x * per, k1 = k0 + per < n ? k0 + per : n;
-    long long tcur = -1;
-    for (int64_t base = k0; base < k1; base += GC_STEP) {
-        unsigned long long kk[4];
-        double2 x[4];
-        double y[4];
-        unsigned int pend = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t k = base + threadIdx.x + 256 * j;
-            kk[j] = 0ull, x[j] = make_double2(0.0, 0.0), y[j] = 0.0;
-            if (k < k1) {
-                kk[j] = key[k];
-                x[j] = X[k];
-                y[j] = Y[k];
-            }
-            if (kk[j] & GC_USED) pend |= 1u << j;
-        }
-        for (;;) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (!(pend >> j & 1u) || (long long)(kk[j] >> 42 & GC_FIELD) != tcur) continue;
-                const int p = (int)(kk[j] & GC_FIELD), q = (int)(kk[j] >> 21 & GC_FIELD);
-                const double2 gp = lg[p], gq = lg[q];
-                const double2 np = cmul(x[j], gq), nq = cmul(make_double2(x[j].x, -x[j].y), gp);
-                atomicAdd(&acc[3 * p], np.x), atomicAdd(&acc[3 * p + 1], np.y), atomicAdd(&acc[3 * p + 2], y[j] * norm2(gq));
-                atomicAdd(&acc[3 * q], nq.x), atomicAdd(&acc[3 * q + 1], nq.y), atomicAdd(&acc[3 * q + 2], y[j] * norm2(gp));
-                pend &= ~(1u << j);
-            }
-            if (!__syncthreads_or(pend != 0)) break;  // (a barrier: every add into tcur's sums is done)
-            if (threadIdx.x == 0) tsel = 0xffffffffu;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (pend >> j & 1u) atomicMin(&tsel, (unsigned int)(kk[j] >> 42 & GC_FIELD));
-            __syncthreads();
-            const long long tn = tsel;
-            for (int a = threadIdx.x; a < A; a += 256) {
-                if (tcur >= 0) {
-                    double *row = table + 3 * (tcur * A + a);
-                    for (int c = 0; c < 3; ++c) {
-                        const double v = acc[3 * a + c];
-                        if (v != 0.0) atomicAdd(&row[c], v);
-                        acc[3 * a + c] = 0.0;
-                    }
-                }
-                lg[a] = g[tn * A + a];
-            }
-            __syncthreads();
-            tcur = tn;
-        }
-    }
-    __syncthreads();
-    if (tcur >= 0)
-        for (int a = threadIdx.x; a < A; a += 256) {
-            double *row = table + 3 * (tcur * A + a);
-            for (int c = 0; c < 3; ++c) {
-                const double v = acc[3 * a + c];
-                if (v != 0.0) atomicAdd(&row[c], v);
-            }
-        }
+    gc_walk<GcMod>(GcMod::In{X, Y}, n, A, 1, per, key, g, table, st, lg, acc);
 }
 
-// the same sums for any A: gains from global memory, fp64 atomics straight to the table
 __global__ void __launch_bounds__(256)
     gaincal_iter_global_kernel(int64_t n, int64_t A, const double2 *__restrict__ X, const double *__restrict__ Y,
                                const unsigned long long *__restrict__ key, const double2 *__restrict__ g, double *table,
                                const GcState *st)
 {
-    if (st->stopped) return;
-    const int64_t k0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t k = k0; k < n; k += step) {
-        const unsigned long long kk = key[k];
-        if (!(kk & GC_USED)) continue;
-        const int64_t t = (int64_t)(kk >> 42 & GC_FIELD), p = t * A + (int64_t)(kk & GC_FIELD),
-                      q = t * A + (int64_t)(kk >> 21 & GC_FIELD);
-        const double2 x = X[k], gp = g[p], gq = g[q];
-        const double y = Y[k];
-        const double2 np = cmul(x, gq), nq = cmul(make_double2(x.x, -x.y), gp);
-        atomicAdd(&table[3 * p], np.x), atomicAdd(&table[3 * p + 1], np.y), atomicAdd(&table[3 * p + 2], y * norm2(gq));
-        atomicAdd(&table[3 * q], nq.x), atomicAdd(&table[3 * q + 1], nq.y), atomicAdd(&table[3 * q + 2], y * norm2(gp));
-    }
+    gc_walk_global<GcMod>(GcMod::In{X, Y}, n, A, 1, key, g, table, st);
 }
 
 // One work-group of 1024 threads: thread i takes the cells i, i + 1024, ... in order.  The phase-only rule applies where
@@ -216,48 +166,7 @@ __global__ void __launch_bounds__(1024)
         d2 += norm2(make_double2(gn.x - go.x, gn.y - go.y));
         s2 += norm2(gn);
     }
-    d2 = block_sum(d2, lds);
-    s2 = block_sum(s2, lds);
-    if (threadIdx.x != 0) return;
-    const double rel = sqrt(d2 / s2);
-    st->rel = rel;
-    st->iters += 1;
-    if (tol > 0.0 && rel <= tol) st->stopped = 1;
-}
-
-// One work-group of 1024 threads.  rot[t] = conj(g[t, refant]) / |g[t, refant]| where the reference antenna was solved and
-// its gain is finite and not zero, else 1: every solved gain of the interval is multiplied by it (an unsolved one stays
-// exactly what it started from), the reference antenna's own becomes (|g|, 0).  The gains of an interval are read (rot) before any is written: a barrier lies between.
-__global__ void __launch_bounds__(1024)
-    gaincal_finish_kernel(int64_t A, int64_t T, int64_t refant, const unsigned int *__restrict__ ever, double2 *g,
-                          double2 *__restrict__ rot, GcState *st)
-{
-#pragma clang fp contract(off)
-    __shared__ double lds[16];
-    if (refant >= 0) {
-        for (int64_t t = threadIdx.x; t < T; t += 1024) {
-            const double2 r = g[t * A + refant];
-            const double a = sqrt(norm2(r));
-            rot[t] = (ever[t * A + refant] && a > 0.0 && a - a == 0.0) ? make_double2(r.x / a, -r.y / a)
-                                                                      : make_double2(1.0, 0.0);
-        }
-        __syncthreads();
-    }
-    double un = 0.0;
-    for (int64_t e = threadIdx.x; e < A * T; e += 1024) {
-        if (!ever[e]) {  // unsolved: counted, and the gain stays the bits it started from
-            un += 1.0;
-            continue;
-        }
-        if (refant < 0) continue;
-        const int64_t t = e / A;
-        const double2 r = rot[t];
-        if (r.x == 1.0 && r.y == 0.0) continue;
-        const double2 go = g[e];
-        g[e] = e - t * A == refant ? make_double2(sqrt(norm2(go)), 0.0) : cmul(go, r);
-    }
-    un = block_sum(un, lds);
-    if (threadIdx.x == 0) st->unsolved = (long long)un;
+    gc_close_iteration(d2, s2, tol, st, lds);
 }
 
 // What gridhip_apply_gains does with one visibility (include/gridhip.h): returns the output weight
@@ -322,20 +231,59 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// what gc_solve_run and gc_solve_any need of this module: a fixed work-group of GC_BLOCK with static LDS, its launches
+struct GcSolve : GcMod {
+    static constexpr int BLOCK = GC_BLOCK, RESIDENT = GC_RESIDENT, LDS_MOST = 0, RAISE_BIT = 0;
+    static constexpr bool PAIR = true;  // X
+    static const void *walker() { return nullptr; }
+    static int64_t lds_antennas() { return GC_LDS_A; }
+    static GcPlanes planes(const GcCall &c) { return {1, c.A * c.T, 1, true, 0u}; }
+    static GcRules rules(const GcCall &c) { return {"gaincal", 1, false, 16, 16, (size_t)c.A * c.T * 16}; }
+    static int run(gridhip_ctx *ctx, const GcCall &c) { return gc_solve_run<GcSolve>(ctx, c); }
+    static void init(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(gaincal_init_kernel, grid_for(ctx, c.A * c.T), dim3(256), 0, ctx->stream, c.A * c.T, c.warm,
+                           w.table, w.ever, w.g);
+    }
+    static void prepare(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(gaincal_prepare_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, c.T, c.a1, c.a2, c.slot,
+                           (const double2 *)c.vis, (const double2 *)c.model_vis, c.wt, w.pair, w.real, w.key, w.parts);
+    }
+    static void iter(gridhip_ctx *ctx, const GcCall &c, const GcWork &w, bool lds, dim3 grid, dim3 block, size_t,
+                     int64_t per)
+    {
+        if (lds)
+            hipLaunchKernelGGL(gaincal_iter_kernel, grid, block, 0, ctx->stream, c.n, (int)c.A, per, (const double2 *)w.pair,
+                               (const double *)w.real, (const unsigned long long *)w.key, (const double2 *)w.g, w.table,
+                               (const GcState *)w.st);
+        else
+            hipLaunchKernelGGL(gaincal_iter_global_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A,
+                               (const double2 *)w.pair, (const double *)w.real, (const unsigned long long *)w.key,
+                               (const double2 *)w.g, w.table, (const GcState *)w.st);
+    }
+    static void update(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(gaincal_update_kernel, dim3(1), dim3(1024), 0, ctx->stream, c.A * c.T, c.mode, c.tol, w.table,
+                           w.ever, w.g, w.st);
+    }
+    static void final(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)  // a selfcal: the corrected stream in the same pass
+    {
+        const auto pass = c.vis_cal ? gaincal_stream_kernel<true, true> : gaincal_stream_kernel<true, false>;
+        hipLaunchKernelGGL(pass, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, c.T, c.a1, c.a2, c.slot, (const double2 *)w.g,
+                           (const double2 *)c.vis, (const double2 *)c.model_vis, c.wt, 1, (double2 *)c.vis_cal,
+                           c.vis_cal ? c.wt_cal : nullptr, w.parts);
+    }
+};
+
 }  // namespace
 
 int gaincal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                   const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                   int64_t refant, int64_t niter, double tol, const double *gains)
 {
-    if (n < 0 || A < 2 || T < 1 || (!slot && T != 1) || (n > 0 && (!a1 || !a2 || !vis || !model_vis)) || !gains ||
-        niter < 0 || !(tol >= 0.0) || mode < 0 || mode > 1 || refant >= A)
-        return fail(ctx, GRIDHIP_EINVAL, "gaincal: bad argument");
-    GH_CHECK(shape_check(ctx, "gaincal", n, A, T, a1, a2, slot));
-    const size_t gb = (size_t)A * T * 16, n8 = (size_t)n * 8;
-    if (overlaps_any({gains, gb}, {{a1, n8}, {a2, n8}, {slot, n8}, {vis, 2 * n8}, {model_vis, 2 * n8}, {wt, n8}}))
-        return fail(ctx, GRIDHIP_EINVAL, "gaincal: gains must not overlap an input");
-    return GRIDHIP_OK;
+    const GcCall c = {n, A, T, 1, a1, a2, slot, vis, model_vis, wt, mode, refant, 0, niter, tol, const_cast<double *>(gains)};
+    return gc_solve_check(ctx, GcSolve::rules(c), c);
 }
 
 int apply_gains_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
@@ -376,65 +324,8 @@ int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t
                 const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
                 int warm, int64_t niter, double tol, double *gains, double *stats, double *vis_cal, double *wt_cal)
 {
-    const int64_t cells = A * T;
-    const dim3 sgrid = grid_for(ctx, n);  // the prepare pass and the final pass: one row of partial sums per work-group
-    DevBuf small, table, ever, X, Y, key;
-    GH_CHECK(small.alloc(ctx, ((size_t)GC_HEAD + (size_t)GC_PARTS * ctx->num_cu * 16 + 2 * (size_t)T) * 8));
-    GH_CHECK(table.alloc(ctx, (size_t)cells * 24));
-    GH_CHECK(ever.alloc(ctx, (size_t)cells * 4));
-    if (n > 0) {
-        GH_CHECK(X.alloc(ctx, (size_t)n * 16));
-        GH_CHECK(Y.alloc(ctx, (size_t)n * 8));
-        GH_CHECK(key.alloc(ctx, (size_t)n * 8));
-    }
-    GcState *st = small.as<GcState>();
-    double *parts = small.as<double>() + GC_HEAD;
-    double2 *rot = reinterpret_cast<double2 *>(parts + (size_t)GC_PARTS * ctx->num_cu * 16);
-    double2 *g = (double2 *)gains;
-    hipLaunchKernelGGL(gaincal_init_kernel, grid_for(ctx, cells), dim3(256), 0, ctx->stream, cells, warm, table.as<double>(),
-                       ever.as<unsigned int>(), g);
-    if (n > 0)
-        hipLaunchKernelGGL(gaincal_prepare_kernel, sgrid, dim3(256), 0, ctx->stream, n, A, T, a1, a2, slot,
-                           (const double2 *)vis, (const double2 *)model_vis, wt, X.as<double2>(), Y.as<double>(),
-                           key.as<unsigned long long>(), parts);
-    hipLaunchKernelGGL(gaincal_begin_kernel, dim3(1), dim3(256), 0, ctx->stream, n > 0 ? (int)sgrid.x : 0,
-                       (const double *)parts, st);
-    // the iteration kernel's ranges: whole chunks, GC_RESIDENT work-groups per CU at the most, so that every work-group
-    // of the launch is resident at once and none waits for another to retire
-    const int64_t nchunks = (n + GC_CHUNK - 1) / GC_CHUNK, most = (int64_t)ctx->num_cu * GC_RESIDENT;
-    const int64_t cpw = nchunks > most ? (nchunks + most - 1) / most : 1;
-    const int64_t igrid = nchunks > 0 ? (nchunks + cpw - 1) / cpw : 0;
-    for (int64_t i = 0; i < niter; ++i) {
-        if (n > 0 && A <= GC_LDS_A)
-            hipLaunchKernelGGL(gaincal_iter_kernel, dim3((unsigned)igrid), dim3(256), 0, ctx->stream, n, (int)A,
-                               cpw * GC_CHUNK, (const double2 *)X.as<double2>(), (const double *)Y.as<double>(),
-                               (const unsigned long long *)key.as<unsigned long long>(), (const double2 *)g,
-                               table.as<double>(), (const GcState *)st);
-        else if (n > 0)
-            hipLaunchKernelGGL(gaincal_iter_global_kernel, sgrid, dim3(256), 0, ctx->stream, n, A,
-                               (const double2 *)X.as<double2>(), (const double *)Y.as<double>(),
-                               (const unsigned long long *)key.as<unsigned long long>(), (const double2 *)g,
-                               table.as<double>(), (const GcState *)st);
-        hipLaunchKernelGGL(gaincal_update_kernel, dim3(1), dim3(1024), 0, ctx->stream, cells, mode, tol, table.as<double>(),
-                           ever.as<unsigned int>(), g, st);
-    }
-    hipLaunchKernelGGL(gaincal_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, A, T, refant,
-                       (const unsigned int *)ever.as<unsigned int>(), g, rot, st);
-    if (n > 0) {
-        if (vis_cal)
-            hipLaunchKernelGGL((gaincal_stream_kernel<true, true>), sgrid, dim3(256), 0, ctx->stream, n, A, T, a1, a2, slot,
-                               (const double2 *)g, (const double2 *)vis, (const double2 *)model_vis, wt, 1,
-                               (double2 *)vis_cal, wt_cal, parts);
-        else
-            hipLaunchKernelGGL((gaincal_stream_kernel<true, false>), sgrid, dim3(256), 0, ctx->stream, n, A, T, a1, a2, slot,
-                               (const double2 *)g, (const double2 *)vis, (const double2 *)model_vis, wt, 1,
-                               (double2 *)nullptr, (double *)nullptr, parts);
-    }
-    if (stats)
-        hipLaunchKernelGGL(gaincal_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, n > 0 ? (int)sgrid.x : 0,
-                           (const double *)parts, (const GcState *)st, stats);
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    return GRIDHIP_OK;
+    return GcSolve::run(ctx, {n, A, T, 1, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats,
+                              vis_cal, wt_cal});
 }
 
 }  // namespace gridhip
@@ -442,25 +333,6 @@ int gaincal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t
 using namespace gridhip;
 
 namespace {
-
-int gaincal_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
-                const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
-                int warm, int64_t niter, double tol, double *gains, double *stats)
-{
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(gaincal_check(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8, gb = (size_t)A * T * 16;
-    Staged st(ctx, dev);
-    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), vis = st.in(vis, 2 * n8);
-    model_vis = st.in(model_vis, 2 * n8), wt = st.in(wt, n8);
-    gains = warm ? st.inout(gains, gains, gb) : st.out(gains, gb);  // (a cold start reads no gains)
-    stats = st.out(stats, 64);
-    GH_CHECK(st.status());
-    GH_CHECK(gaincal_run(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats, nullptr,
-                         nullptr));
-    return st.finish();
-}
 
 int apply_gains_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
@@ -488,14 +360,16 @@ int gridhip_gaincal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const
                         const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                         int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    return gaincal_any(ctx, true, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return gc_solve_any<GcSolve>(ctx, true, {n, A, T, 1, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol,
+                                             gains, stats});
 }
 
 int gridhip_gaincal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                     const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                     int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    return gaincal_any(ctx, false, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return gc_solve_any<GcSolve>(ctx, false, {n, A, T, 1, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol,
+                                              gains, stats});
 }
 
 int gridhip_apply_gains_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,

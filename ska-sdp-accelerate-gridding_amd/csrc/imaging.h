@@ -40,8 +40,7 @@ struct ImagingState {
     bool restore_lds_raised = false;  // restore_kernel has been allowed its dynamic LDS on this device (restore.hip)
     bool msconv_lds_raised = false;   // and ms_conv_kernel its own (msclean.hip)
     bool flag_lds_raised = false;     // and flag_hist_kernel's LDS path its 64 KB (flag.hip)
-    unsigned int ddcal_lds_raised = 0;  // and ddcal_iter_kernel<D> its DD_LDS_BUDGET: bit D (ddcal.hip)
-    bool jonescal_lds_raised = false;   // and jones_iter_kernel its 80 KB (jonescal.hip)
+    unsigned int gain_lds_raised = 0;  // and ddcal_iter_kernel<D> its DD_LDS_BUDGET (bit D), jones_iter_kernel its 80 KB (bit 0)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
     int64_t mosaic_cull = 0;          // option "mosaic_cull": 1 = every tile of gridhip_mosaic walks all valid facets (the same bits)

@@ -15,14 +15,14 @@
 //                                    visibilities, keeps the gains (8 doubles) and the sums (12 doubles) of ONE interval's
 //                                    antennas in dynamic LDS, 160 A bytes, adds with LDS fp64 atomics (24 per visibility)
 //                                    and flushes to the global table when the interval changes and at the end of its
-//                                    range.  The interval logic is gaincal_iter_kernel's.  A CU holds 1024 threads of it
+//                                    range.  The interval logic is gc_walk (gain_common.h).  A CU holds 1024 threads of it
 //                                    whatever the table takes: four work-groups of 256 threads while four tables (and
 //                                    a word each) fit, A <= 255, two of 512 up to A = 511, one of 1024 at A = JC_LDS_A
 //                                    = 512, exactly 80 KB.
 //                                    A > JC_LDS_A: jones_iter_global_kernel adds to the global table directly.
 //               jones_update_kernel  one work-group: G' from the table (the LDL^H of the 2x2 den, or its diagonal), the
 //                                    phase-only and averaging rules, rel in a fixed order, the stop test; zeroes the table }
-//     jones_finish_kernel    one work-group: the common phase of the reference antenna and the number of unsolved (t, a)
+//     gc_finish_kernel       (gain_common.h) one work-group: the common phase of the reference antenna, the unsolved (t, a)
 //     jones_chi_kernel       one pass with the final gains: chi^2 as partial rows
 //     gaincal_stats_kernel   (gain_common.h) the 8 doubles
 //     jones_apply_kernel     gridhip_apply_jones;  stokes_kernel  gridhip_stokes - one visibility per lane, no scratch
@@ -36,9 +36,6 @@ namespace gridhip {
 namespace {
 
 constexpr int JC_SUMS = 12;           // num (4 complex), d00, d11, d01 (complex)
-constexpr int JC_CU_THREADS = 1024;   // threads of jones_iter_kernel a CU holds (launch bound 1024: 128 VGPRs a lane)
-constexpr int64_t JC_CU_LDS = 160 * 1024;
-constexpr int64_t JC_LDS_BYTES = (int64_t)JC_LDS_A * (8 + JC_SUMS) * 8;  // the most dynamic LDS of a launch
 
 struct J2 {  // a 2x2 complex matrix, row-major: 00, 01, 10, 11
     double2 e[4];
@@ -118,15 +115,11 @@ __global__ void __launch_bounds__(256)
         unsigned long long kk = 0ull;
         if (c == 0) {
             chi0 += s * jnorm2(jsub(jload(vis + 4 * k), jload(mod + 4 * k)));
-            kk = GC_USED | (unsigned long long)p | (unsigned long long)q << 21 | (unsigned long long)t << 42;
+            kk = gc_pack(p, q, t);
         }
         S[k] = c == 0 ? s : 0.0, key[k] = kk;
     }
-    const double r[GC_PARTS] = {chi0, (double)used, (double)flagged, (double)dropped};
-    for (int j = 0; j < GC_PARTS; ++j) {
-        const double x = block_sum(r[j], lds);
-        if (threadIdx.x == 0) parts[(int64_t)blockIdx.x * GC_PARTS + j] = x;
-    }
+    gc_prepare_tail(chi0, used, flagged, dropped, parts, lds);
 }
 
 // One side of one visibility into the 12 sums of its antenna: Z = Mx Gh, sZ = s Z, num += Y (sZ)^H, den += Z (sZ)^H, of
@@ -157,89 +150,43 @@ __device__ __forceinline__ void jones_visibility(int64_t k, double s, const doub
     jones_add(rq, jherm(V), jherm(M), jherm(jload(gp)), s);
 }
 
-// One iteration's sums, A <= JC_LDS_A.  Work-group b takes the visibilities [b * per, (b + 1) * per), per a whole number
-// of chunks, in steps of 4 blockDim.x: thread i holds the keys of base + i + blockDim.x j.  lg [A][4] complex, acc [A][12]:
-// the gains and the sums of interval tcur.  The interval logic is gaincal_iter_kernel's.  One visibility at a time: unrolled,
-// the 16 doubles of V and M of all four would be held at once.
+// What gc_walk needs of this module: lg [A][4] complex, acc [A][12].  One visibility at a time: unrolled, the 16 doubles of
+// V and M of all four would be held at once.  JcSolve below adds the driver's part.
+struct JcMod {
+    static constexpr int NS = JC_SUMS, NG = 4, GSTEP = 4, UNROLL = 1;
+    struct In {
+        const double *S;
+        const double2 *vis, *mod;
+    };
+    using Held = GcNoHeld;
+    static __device__ __forceinline__ void load_gains(double2 *lg, const double2 *__restrict__ g, long long tn, int A, int64_t)
+    {
+        gc_copy_gains(lg, g, tn, 4 * A);
+    }
+    static __device__ __forceinline__ void add(const In &in, const Held &, int, int64_t k, const double2 *gp,
+                                               const double2 *gq, int64_t, double *rp, double *rq)
+    {
+        jones_visibility(k, in.S[k], in.vis, in.mod, gp, gq, rp, rq);
+    }
+};
+
+// One iteration's sums, A <= JC_LDS_A: gc_walk with dynamic LDS, 160 bytes per antenna
 __global__ void __launch_bounds__(1024)
     jones_iter_kernel(int64_t n, int A, int64_t per, const double *__restrict__ S, const unsigned long long *__restrict__ key,
                       const double2 *__restrict__ vis, const double2 *__restrict__ mod, const double2 *__restrict__ g,
                       double *table, const GcState *st)
 {
-    if (st->stopped) return;
     extern __shared__ double2 jc_lds[];
-    __shared__ unsigned int tsel;
-    double2 *lg = jc_lds;
-    double *acc = reinterpret_cast<double *>(jc_lds + (size_t)4 * A);
-    const int nt = blockDim.x;
-    for (int a = threadIdx.x; a < JC_SUMS * A; a += nt) acc[a] = 0.0;
-    const int64_t k0 = (int64_t)blockIdx.x * per, k1 = k0 + per < n ? k0 + per : n;
-    long long tcur = -1;
-    for (int64_t base = k0; base < k1; base += 4 * nt) {
-        unsigned long long kk[4];
-        unsigned int pend = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t k = base + threadIdx.x + (int64_t)nt * j;
-            kk[j] = k < k1 ? key[k] : 0ull;
-            if (kk[j] & GC_USED) pend |= 1u << j;
-        }
-        for (;;) {
-#pragma unroll 1
-            for (int j = 0; j < 4; ++j) {
-                const unsigned long long kj = j == 0 ? kk[0] : j == 1 ? kk[1] : j == 2 ? kk[2] : kk[3];
-                if (!(pend >> j & 1u) || (long long)(kj >> 42 & GC_FIELD) != tcur) continue;
-                const int p = (int)(kj & GC_FIELD), q = (int)(kj >> 21 & GC_FIELD);
-                const int64_t k = base + threadIdx.x + (int64_t)nt * j;
-                jones_visibility(k, S[k], vis, mod, lg + 4 * p, lg + 4 * q, acc + JC_SUMS * p, acc + JC_SUMS * q);
-                pend &= ~(1u << j);
-            }
-            if (!__syncthreads_or(pend != 0)) break;  // (a barrier: every add into tcur's sums is done)
-            if (threadIdx.x == 0) tsel = 0xffffffffu;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (pend >> j & 1u) atomicMin(&tsel, (unsigned int)(kk[j] >> 42 & GC_FIELD));
-            __syncthreads();
-            const long long tn = tsel;
-            if (tcur >= 0) {
-                double *rows = table + (size_t)tcur * A * JC_SUMS;
-                for (int a = threadIdx.x; a < JC_SUMS * A; a += nt) {
-                    const double v = acc[a];
-                    if (v != 0.0) atomicAdd(&rows[a], v);
-                    acc[a] = 0.0;
-                }
-            }
-            for (int a = threadIdx.x; a < 4 * A; a += nt) lg[a] = g[tn * 4 * A + a];
-            __syncthreads();
-            tcur = tn;
-        }
-    }
-    __syncthreads();
-    if (tcur >= 0) {
-        double *rows = table + (size_t)tcur * A * JC_SUMS;
-        for (int a = threadIdx.x; a < JC_SUMS * A; a += nt) {
-            const double v = acc[a];
-            if (v != 0.0) atomicAdd(&rows[a], v);
-        }
-    }
+    gc_walk<JcMod>(JcMod::In{S, vis, mod}, n, A, 1, per, key, g, table, st, jc_lds,
+                   reinterpret_cast<double *>(jc_lds + (size_t)4 * A));
 }
 
-// the same sums for any A: gains from global memory, fp64 atomics straight to the table
 __global__ void __launch_bounds__(256)
     jones_iter_global_kernel(int64_t n, int64_t A, const double *__restrict__ S, const unsigned long long *__restrict__ key,
                              const double2 *__restrict__ vis, const double2 *__restrict__ mod,
                              const double2 *__restrict__ g, double *table, const GcState *st)
 {
-    if (st->stopped) return;
-    const int64_t k0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t k = k0; k < n; k += step) {
-        const unsigned long long kk = key[k];
-        if (!(kk & GC_USED)) continue;
-        const int64_t t = (int64_t)(kk >> 42 & GC_FIELD), p = t * A + (int64_t)(kk & GC_FIELD),
-                      q = t * A + (int64_t)(kk >> 21 & GC_FIELD);
-        jones_visibility(k, S[k], vis, mod, g + 4 * p, g + 4 * q, table + JC_SUMS * p, table + JC_SUMS * q);
-    }
+    gc_walk_global<JcMod>(JcMod::In{S, vis, mod}, n, A, 1, key, g, table, st);
 }
 
 // One work-group of 1024 threads: thread i takes the cells i, i + 1024, ... in order.  An unsolved cell keeps the bits of
@@ -297,52 +244,7 @@ __global__ void __launch_bounds__(1024)
         d2 += jnorm2(jsub(gn, go));
         s2 += jnorm2(gn);
     }
-    d2 = block_sum(d2, lds);
-    s2 = block_sum(s2, lds);
-    if (threadIdx.x != 0) return;
-    const double rel = sqrt(d2 / s2);
-    st->rel = rel;
-    st->iters += 1;
-    if (tol > 0.0 && rel <= tol) st->stopped = 1;
-}
-
-// One work-group of 1024 threads.  rot[t] = conj(r) / |r| with r = G[t, refant][0][0] where the reference antenna was solved
-// and r is finite and not zero, else 1: every entry of every solved gain of the interval is multiplied by it (the
-// off-diagonals of the diagonal modes stay +0.0), and G[t, refant][0][0] itself becomes (|r|, 0).  The gains of an interval
-// are read (rot) before any is written: a barrier lies between.
-__global__ void __launch_bounds__(1024)
-    jones_finish_kernel(int64_t A, int64_t T, int mode, int64_t refant, const unsigned int *__restrict__ ever, double2 *g,
-                        double2 *__restrict__ rot, GcState *st)
-{
-#pragma clang fp contract(off)
-    __shared__ double lds[16];
-    if (refant >= 0) {
-        for (int64_t t = threadIdx.x; t < T; t += 1024) {
-            const double2 r = g[4 * (t * A + refant)];
-            const double a = sqrt(norm2(r));
-            rot[t] = (ever[t * A + refant] && a > 0.0 && a - a == 0.0) ? make_double2(r.x / a, -r.y / a)
-                                                                      : make_double2(1.0, 0.0);
-        }
-        __syncthreads();
-    }
-    double un = 0.0;
-    for (int64_t e = threadIdx.x; e < A * T; e += 1024) {
-        if (!ever[e]) {  // unsolved: counted, and the gain stays the bits it started from
-            un += 1.0;
-            continue;
-        }
-        if (refant < 0) continue;
-        const int64_t t = e / A;
-        const double2 r = rot[t];
-        if (r.x == 1.0 && r.y == 0.0) continue;
-        for (int i = 0; i < 4; ++i) {
-            if (mode != 0 && (i == 1 || i == 2)) continue;
-            const double2 go = g[4 * e + i];
-            g[4 * e + i] = (i == 0 && e - t * A == refant) ? make_double2(sqrt(norm2(go)), 0.0) : cmul(go, r);
-        }
-    }
-    un = block_sum(un, lds);
-    if (threadIdx.x == 0) st->unsolved = (long long)un;
+    gc_close_iteration(d2, s2, tol, st, lds);
 }
 
 // chi^2 over the used visibilities with the final gains, one partial sum per work-group: s |V - (G_p M) G_q^H|_F^2
@@ -446,19 +348,50 @@ __global__ void __launch_bounds__(256) stokes_kernel(int64_t n, int basis, int i
     }
 }
 
-int jonescal_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
-                   const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
-                   int64_t refant, int64_t niter, double tol, const double *gains)
-{
-    if (n < 0 || A < 2 || T < 1 || (!slot && T != 1) || (n > 0 && (!a1 || !a2 || !vis || !model_vis)) || !gains ||
-        niter < 0 || !(tol >= 0.0) || mode < 0 || mode > 2 || refant >= A)
-        return fail(ctx, GRIDHIP_EINVAL, "jonescal: bad argument");
-    GH_CHECK(shape_check(ctx, "jonescal", n, A, T, a1, a2, slot));
-    const size_t gb = (size_t)A * T * 64, n8 = (size_t)n * 8;
-    if (overlaps_any({gains, gb}, {{a1, n8}, {a2, n8}, {slot, n8}, {vis, 8 * n8}, {model_vis, 8 * n8}, {wt, n8}}))
-        return fail(ctx, GRIDHIP_EINVAL, "jonescal: gains must not overlap an input");
-    return GRIDHIP_OK;
-}
+// what gc_solve_run and gc_solve_any need of this module: its launches; the four entries of a gain [T][A][2][2] are planes
+// a cell apart, all rotated by the phase of [0][0], the off-diagonals left +0.0 in the diagonal modes
+struct JcSolve : JcMod {
+    static constexpr int BLOCK = 0, RESIDENT = 0, RAISE_BIT = 0;
+    static constexpr int64_t LDS_MOST = (int64_t)JC_LDS_A * (8 + JC_SUMS) * 8;
+    static constexpr bool PAIR = false;
+    static const void *walker() { return reinterpret_cast<const void *>(jones_iter_kernel); }
+    static int64_t lds_antennas() { return JC_LDS_A; }
+    static GcPlanes planes(const GcCall &c) { return {4, 1, 4, false, c.mode != 0 ? 6u : 0u}; }
+    static GcRules rules(const GcCall &c) { return {"jonescal", 2, false, 64, 64, (size_t)c.A * c.T * 64}; }
+    static int run(gridhip_ctx *ctx, const GcCall &c) { return gc_solve_run<JcSolve>(ctx, c); }
+    static void init(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(jones_init_kernel, grid_for(ctx, c.A * c.T * JC_SUMS), dim3(256), 0, ctx->stream, c.A * c.T, c.warm,
+                           c.mode, w.table, w.ever, w.g);
+    }
+    static void prepare(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(jones_prepare_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, c.T, c.a1, c.a2, c.slot,
+                           (const double2 *)c.vis, (const double2 *)c.model_vis, c.wt, w.real, w.key, w.parts);
+    }
+    static void iter(gridhip_ctx *ctx, const GcCall &c, const GcWork &w, bool lds, dim3 grid, dim3 block, size_t bytes,
+                     int64_t per)
+    {
+        const double2 *V = (const double2 *)c.vis, *M = (const double2 *)c.model_vis;
+        if (lds)
+            hipLaunchKernelGGL(jones_iter_kernel, grid, block, bytes, ctx->stream, c.n, (int)c.A, per, (const double *)w.real,
+                               (const unsigned long long *)w.key, V, M, (const double2 *)w.g, w.table, (const GcState *)w.st);
+        else
+            hipLaunchKernelGGL(jones_iter_global_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, (const double *)w.real,
+                               (const unsigned long long *)w.key, V, M, (const double2 *)w.g, w.table, (const GcState *)w.st);
+    }
+    static void update(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(jones_update_kernel, dim3(1), dim3(1024), 0, ctx->stream, c.A * c.T, c.mode, c.tol, w.table, w.ever,
+                           w.g, w.st);
+    }
+    static void final(gridhip_ctx *ctx, const GcCall &c, const GcWork &w)
+    {
+        hipLaunchKernelGGL(jones_chi_kernel, w.sgrid, dim3(256), 0, ctx->stream, c.n, c.A, (const double *)w.real,
+                           (const unsigned long long *)w.key, (const double2 *)w.g, (const double2 *)c.vis,
+                           (const double2 *)c.model_vis, w.parts);
+    }
+};
 
 int apply_jones_check(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                       const int64_t *slot, const double *gains, int inverse, const double *vis_in, const double *wt_in,
@@ -490,89 +423,6 @@ int stokes_check(gridhip_ctx *ctx, int64_t n, int basis, int which, int inverse,
     if (overlap(vis, (size_t)n * 64, stokes, (size_t)n * 64))
         return fail(ctx, GRIDHIP_EINVAL, "stokes: vis overlaps the Stokes block");
     return GRIDHIP_OK;
-}
-
-int jonescal_run(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
-                 const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
-                 int warm, int64_t niter, double tol, double *gains, double *stats)
-{
-    const int64_t cells = A * T;
-    const dim3 sgrid = grid_for(ctx, n);  // the prepare pass and the chi^2 pass: one row of partial sums per work-group
-    DevBuf small, table, ever, S, key;
-    GH_CHECK(small.alloc(ctx, ((size_t)GC_HEAD + (size_t)GC_PARTS * ctx->num_cu * 16 + 2 * (size_t)T) * 8));
-    GH_CHECK(table.alloc(ctx, (size_t)cells * JC_SUMS * 8));
-    GH_CHECK(ever.alloc(ctx, (size_t)cells * 4));
-    if (n > 0) {
-        GH_CHECK(S.alloc(ctx, (size_t)n * 8));
-        GH_CHECK(key.alloc(ctx, (size_t)n * 8));
-    }
-    GcState *st = small.as<GcState>();
-    double *parts = small.as<double>() + GC_HEAD;
-    double2 *rot = reinterpret_cast<double2 *>(parts + (size_t)GC_PARTS * ctx->num_cu * 16);
-    double2 *g = (double2 *)gains;
-    const double2 *V = (const double2 *)vis, *M = (const double2 *)model_vis;
-    const double *s = S.as<double>();
-    const unsigned long long *kk = key.as<unsigned long long>();
-    hipLaunchKernelGGL(jones_init_kernel, grid_for(ctx, cells * JC_SUMS), dim3(256), 0, ctx->stream, cells, warm, mode,
-                       table.as<double>(), ever.as<unsigned int>(), g);
-    if (n > 0)
-        hipLaunchKernelGGL(jones_prepare_kernel, sgrid, dim3(256), 0, ctx->stream, n, A, T, a1, a2, slot, V, M, wt,
-                           S.as<double>(), key.as<unsigned long long>(), parts);
-    hipLaunchKernelGGL(gaincal_begin_kernel, dim3(1), dim3(256), 0, ctx->stream, n > 0 ? (int)sgrid.x : 0,
-                       (const double *)parts, st);
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    const bool lds = A <= JC_LDS_A;
-    const size_t bytes = (size_t)A * (8 + JC_SUMS) * 8;
-    // a CU holds JC_CU_THREADS threads of the kernel: as many work-groups as tables fit, each the larger for it
-    const int fit = lds ? (int)(JC_CU_LDS / (int64_t)(bytes + 64)) : 0;
-    const int block = fit >= 4 ? 256 : fit >= 2 ? 512 : 1024, resident = JC_CU_THREADS / block;
-    // (more than 64 KB of LDS only once the function is told so)
-    if (lds && n > 0 && niter > 0 && !ctx->img->jonescal_lds_raised) {
-        GH_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(jones_iter_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)JC_LDS_BYTES));
-        ctx->img->jonescal_lds_raised = true;
-    }
-    // the iteration kernel's ranges: whole chunks, and no more work-groups than are resident at once
-    const int64_t nchunks = (n + GC_CHUNK - 1) / GC_CHUNK, most = (int64_t)ctx->num_cu * resident;
-    const int64_t cpw = nchunks > most ? (nchunks + most - 1) / most : 1;
-    const int64_t igrid = nchunks > 0 ? (nchunks + cpw - 1) / cpw : 0;
-    for (int64_t i = 0; i < niter; ++i) {
-        if (n > 0 && lds)
-            hipLaunchKernelGGL(jones_iter_kernel, dim3((unsigned)igrid), dim3(block), bytes, ctx->stream, n, (int)A,
-                               cpw * GC_CHUNK, s, kk, V, M, (const double2 *)g, table.as<double>(), (const GcState *)st);
-        else if (n > 0)
-            hipLaunchKernelGGL(jones_iter_global_kernel, sgrid, dim3(256), 0, ctx->stream, n, A, s, kk, V, M,
-                               (const double2 *)g, table.as<double>(), (const GcState *)st);
-        hipLaunchKernelGGL(jones_update_kernel, dim3(1), dim3(1024), 0, ctx->stream, cells, mode, tol, table.as<double>(),
-                           ever.as<unsigned int>(), g, st);
-    }
-    hipLaunchKernelGGL(jones_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, A, T, mode, refant,
-                       (const unsigned int *)ever.as<unsigned int>(), g, rot, st);
-    if (n > 0)
-        hipLaunchKernelGGL(jones_chi_kernel, sgrid, dim3(256), 0, ctx->stream, n, A, s, kk, (const double2 *)g, V, M, parts);
-    if (stats)
-        hipLaunchKernelGGL(gaincal_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, n > 0 ? (int)sgrid.x : 0,
-                           (const double *)parts, (const GcState *)st, stats);
-    GH_CHECK_HIP(ctx, hipGetLastError());
-    return GRIDHIP_OK;
-}
-
-int jonescal_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
-                 const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode, int64_t refant,
-                 int warm, int64_t niter, double tol, double *gains, double *stats)
-{
-    if (!ctx) return GRIDHIP_EINVAL;
-    GH_CHECK(jonescal_check(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, niter, tol, gains));
-    GH_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n8 = (size_t)n * 8, gb = (size_t)A * T * 64;
-    Staged st(ctx, dev);
-    a1 = st.in(a1, n8), a2 = st.in(a2, n8), slot = st.in(slot, n8), vis = st.in(vis, 8 * n8);
-    model_vis = st.in(model_vis, 8 * n8), wt = st.in(wt, n8);
-    gains = warm ? st.inout(gains, gains, gb) : st.out(gains, gb);  // (a cold start reads no gains)
-    stats = st.out(stats, 64);
-    GH_CHECK(st.status());
-    GH_CHECK(jonescal_run(ctx, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats));
-    return st.finish();
 }
 
 int apply_jones_any(gridhip_ctx *ctx, bool dev, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
@@ -634,14 +484,16 @@ int gridhip_jonescal_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, cons
                          const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                          int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    return jonescal_any(ctx, true, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return gc_solve_any<JcSolve>(ctx, true, {n, A, T, 1, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol,
+                                             gains, stats});
 }
 
 int gridhip_jonescal(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,
                      const int64_t *slot, const double *vis, const double *model_vis, const double *wt, int mode,
                      int64_t refant, int warm, int64_t niter, double tol, double *gains, double *stats)
 {
-    return jonescal_any(ctx, false, n, A, T, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol, gains, stats);
+    return gc_solve_any<JcSolve>(ctx, false, {n, A, T, 1, a1, a2, slot, vis, model_vis, wt, mode, refant, warm, niter, tol,
+                                              gains, stats});
 }
 
 int gridhip_apply_jones_dev(gridhip_ctx *ctx, int64_t n, int64_t A, int64_t T, const int64_t *a1, const int64_t *a2,

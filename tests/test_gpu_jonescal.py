@@ -99,6 +99,26 @@ def test_every_baseline_three_intervals(ctx, mode):
          refant=3)
 
 
+def test_a_diagonal_solve_of_diagonal_data_is_gaincal_on_each_correlation(ctx):
+    """Without off-diagonals the sums of [0][0] and [1][1] are gaincal's of the xx and the yy stream, so the two modules'
+    walk, update and finish meet here.  No reference antenna: jonescal would rotate both diagonals by the phase of [0][0],
+    gaincal each stream by its own."""
+    rng = np.random.default_rng(5)
+    a1, a2, sl, V, M, _ = polarised(rng, 7, 3, noise=0.05)
+    V, M, w = V.copy(), M.copy(), rng.uniform(0.5, 2, len(a1))
+    V[:, 0, 1] = V[:, 1, 0] = M[:, 0, 1] = M[:, 1, 0] = 0
+    G, st = solve(ctx, V, M, a1, a2, 7, slot=sl, T=3, wt=w, mode=1, refant=-1, niter=9)
+    assert G.shape == (3, 7, 2, 2) and np.all(G[..., 0, 1] == 0) and np.all(G[..., 1, 0] == 0)
+    for i, name in ((0, "xx"), (1, "yy")):
+        g, sg = ctx.gaincal(dev(np.ascontiguousarray(V[:, i, i])), dev(np.ascontiguousarray(M[:, i, i])), dev(a1), dev(a2), 7,
+                            slot=dev(sl), nslots=3, weights=dev(w), refant=None, niter=9, tol=0.0)
+        g, sg = host(g), host(sg)
+        eg = np.abs(G[..., i, i] - g).max() / np.abs(g).max()
+        print(f"{name}: gains {eg:.2e}  ints {st[[0, 4, 5, 6, 7]]} / {sg[[0, 4, 5, 6, 7]]}")
+        assert g.shape == (3, 7) and eg <= TOL, name
+        assert np.array_equal(st[[0, 4, 5, 6, 7]], sg[[0, 4, 5, 6, 7]]), name
+
+
 def test_no_visibilities_and_no_iterations(ctx):
     e = np.zeros(0)
     (g, st), _ = both(ctx, "n=0", np.zeros((0, 2, 2), c128), np.zeros((0, 2, 2), c128), e.astype(i64), e.astype(i64), 3, niter=3)
