@@ -142,6 +142,10 @@ int gridhip_synchronize(gridhip_ctx *ctx);
  *               100 + t: widen the record's kernel-slice field until its fields take t <= 64 bits
  *   "dft_slices"  gridhip_dft_predict: the slices S the component list is cut into; 0 = auto (a function of n and C
  *               alone), 1..64 = that many (values above 64 count as 64)
+ *   "sources_deblend"  gridhip_find_sources and its _dev and imager forms: 0 (default) = an island is one row; r in 1..32 =
+ *               an island is split into one row per peak, with window radius r cells ("source finding", DEBLENDING).  Read
+ *               when a call is enqueued.  A value above 32 is kept as given: the three entry points then return
+ *               GRIDHIP_EINVAL before they touch anything
  *   "mosaic_cull"  gridhip_mosaic: 0 = every tile walks the facets its cull keeps, 1 = every tile walks all valid facets
  *               (the same bits: kept for comparison runs)
  *   "rm_stage"  gridhip_rmclean: 0 = every wave reads and writes its line of sight directly, 1 = a work-group moves its
@@ -2163,7 +2167,7 @@ int gridhip_components_from_image_dev(gridhip_ctx *ctx, double theta, int64_t la
  * that hold a cell of a component of H = { v > T_hi } with at least min_cells cells.  An island's label is its smallest
  * cell index; the islands are listed in ascending label order, so the list is a function of the image alone.  Since the
  * levels are >= 0 every cell of an island is > 0 and all weights below are positive.  An island with several peaks (a
- * blend) is ONE component: nothing here splits islands.
+ * blend) is ONE component unless the option "sources_deblend" is set: see DEBLENDING.
  * PER ISLAND, over its cells I(y, x):
  *     exact     ncells; the bounding box y0, y1, x0, x1; the peak P_i and its cell (yp, xp) - the maximum under
  *               image_stats' key order, the smallest cell index among equals; edge = the box touches row or column `border`
@@ -2198,12 +2202,37 @@ int gridhip_components_from_image_dev(gridhip_ctx *ctx, double theta, int64_t la
  *        r <- pi / 2 - r if |y| > |x|; r <- pi - r if x < 0; the sign of y.  Within 1e-15 relative of the true value.
  *     5  l = theta (cx - N/2) / N, m = theta (cy - N/2) / N with the integer N/2, the product before the quotient, as for
  *        gridhip_components_from_image.
+ * DEBLENDING.  The option "sources_deblend" = r, 1 <= r <= 32, read when a call is enqueued (0, the default: everything
+ * above, bit for bit; above 32: GRIDHIP_EINVAL from all three forms), splits an island into one component per peak.  Islands,
+ * levels, min_cells, border and the noise rule are unchanged.  Within an island the cells are ordered by value, and among
+ * equal values the smaller cell index ranks higher - image_stats' key order (all values are finite and > 0, so comparing
+ * values is comparing keys).
+ *     1  up-pointer: for every cell k of K, up[k] is the highest-ranked cell among k and those of its 8 neighbours that lie
+ *        in K and carry k's island label.  Neighbours outside the image, outside K or in another island do not count.
+ *     2  summits: a cell with up[k] == k looks at the cells of its own island within Chebyshev distance r, the window
+ *        clipped at the image; W(k) is the highest-ranked of them, k included.  W(k) != k: up[k] = W(k), the basin climbs on
+ *        to a strictly higher cell (which need not be a peak itself).  W(k) == k and image[k] > T_hi: k is a PEAK.  W(k) ==
+ *        k and image[k] <= T_hi: k is a faint summit and up[k] is the island's brightest cell, the highest in the order -
+ *        always above T_hi and always a peak, so every island keeps at least one row.
+ *     3  basins: sub[k] is the fixed point of following up from k; every step goes to a strictly higher cell, so there is
+ *        no cycle.  The component of a peak p is { k in K : sub[k] == p }; the components of an island partition its cells.
+ *     4  rows: one per peak, in ascending order of the peak's cell index, each measured exactly as an island is, by PER
+ *        ISLAND and the steps 1 to 5 over its own cells: ncells, box, peak, the six sums about the peak, `correct` with the
+ *        row's own P_i, beam, shape, l and m.  `correct` assumes a cut at an isophote; a basin is cut by a watershed line
+ *        where it meets another, and for such a row the correction is approximate.  info[.][0] stays the ISLAND's label, its
+ *        smallest cell index, so the rows of one island share it; (yp, xp) is the peak; flag bit 3 (value 8) is set on every
+ *        row whose island has more than one row; count, stats[3] and stats[4] count components.  An island with one peak
+ *        gives the same comps row and the same info[1:16] bits as with the option off; only the order of the rows can differ.
+ *     Only integer comparisons decide anything, so sub is an exact function of the image, and every statement about
+ *     determinism in this section holds as it stands: the three forms, two runs and a replayed graph give the same bits.
  * OUTPUTS
  *     comps   [max_c][GRIDHIP_COMP_DOUBLES] rows { l, m, F, 0, 0, 0, bmaj, bmin, bpa, 0 }
  *     info    [max_c][GRIDHIP_SRC_DOUBLES = 16] rows { label, ncells, yp, xp, P_i, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1,
- *             flags }, or NULL.  flags: bit 0 a point, bit 1 edge, bit 2 the beam is unusable
- *     count   one int64 (on the device for the _dev and imager forms): the islands found, even above max_c.  Only the
- *             first max_c rows are written; the rows after the last one written are left as they were
+ *             flags }, or NULL.  flags: bit 0 a point, bit 1 edge, bit 2 the beam is unusable, bit 3 one of several rows of
+ *             its island (DEBLENDING)
+ *     count   one int64 (on the device for the _dev and imager forms): the islands found (with DEBLENDING: the components),
+ *             even above max_c.  Only the first max_c rows are written; the rows after the last one written are left as they
+ *             were
  *     stats   8 doubles { T_hi, T_lo, P, islands found, rows written, of them points, the sum of F over the rows written
  *             (added in row order by one thread), reason }.  reason 2 and 3 as for auto-masking: count is 0, the counts
  *             are 0 and no row is written
@@ -2214,13 +2243,22 @@ int gridhip_components_from_image_dev(gridhip_ctx *ctx, double theta, int64_t la
  * enqueue kernels only on the context's stream - 17 launches whatever the image holds (12 with max_c = 0), no memset or
  * copy node - allocate nothing after the first call of a shape, read nothing back and never synchronise: image ->
  * image_stats -> find_sources -> dft_predict can be captured into one graph.  Scratch is auto-masking's (9 bytes per cell)
- * and 12 B per 1024 cells and 20 B per row; the imager form keeps its own.
+ * and 12 B per 1024 cells and 20 B per row; the imager form keeps its own.  With DEBLENDING: 23 launches whatever the image
+ * holds (18 with max_c = 0) - 17 and 12 as before with the option at 0 - and 16 B per cell more (the islands' largest value,
+ * 8 B, reused for their peak counts; its cell, 4 B; sub, 4 B; up lies in the plane the labelling leaves free), drawn from the
+ * context's pool for the length of the call by all three forms, and only when the option is not 0.  A captured graph keeps
+ * the address of that pooled block (as it does of the scratch of gridhip_find_sources_dev): replay it on the context's stream
+ * only, between calls of the same context and not concurrently with them, and not after the context has met an
+ * out-of-memory condition, which frees pooled blocks.
  * The labelling is auto-masking's own kernels.  Then: the roots of the islands are compacted in order (per-segment counts,
  * an exclusive scan, a scatter - components_from_image's pattern), which numbers the rows; one flat pass takes the boxes by
  * 32-bit integer atomicMin / atomicMax per row; one work-group of 256 threads per row walks the row's box in row-major
  * order, thread t the cells t, t + 256, ..., keeping the cells that carry the island's label - first for the peak, then for
  * the count and the six sums - each reduced by a wave shuffle tree and a fixed tree over the four waves; one thread derives
- * the fields and writes both rows. */
+ * the fields and writes both rows.  DEBLENDING is a relabelling in front of that: each island's largest value by a 64-bit
+ * integer atomicMax of its bits and then the smallest cell that holds it by a 32-bit atomicMin; up per cell; a wave per summit
+ * scans the window; every cell follows up to its fixed point (the cost of a cell is the length of its ascent); and the same
+ * compaction, box and measuring kernels run on sub, where a root is a peak. */
 #define GRIDHIP_SRC_DOUBLES 16
 int gridhip_find_sources(gridhip_ctx *ctx, double theta, int64_t lam, const double *image, int64_t border, double thr_hi,
                          double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,

@@ -527,6 +527,7 @@ static int64_t *opt_slot(gridhip_ctx *ctx, const char *key)
     if (!strcmp(key, "list_reuse")) return &ctx->opt.list_reuse;
     if (!strcmp(key, "noise_bits")) return &ctx->img->noise_bits;  // image_stats' digit: 8, or anything else for 13
     if (!strcmp(key, "dft_slices")) return &ctx->img->dft_slices;  // dft_predict's component slices: 0 = auto, 1..64
+    if (!strcmp(key, "sources_deblend")) return &ctx->img->sources_deblend;  // find_sources' deblending window: 0 = off, 1..32
     if (!strcmp(key, "mosaic_cull")) return &ctx->img->mosaic_cull;  // mosaic's per-tile cull: 0 = on, 1 = every valid facet
     if (!strcmp(key, "rm_stage")) return &ctx->img->rm_stage;  // rmclean's cube access: 0 = direct, 1 = through LDS
     if (!strcmp(key, "noisemap_hist")) return &ctx->img->noisemap_hist;  // noise_map's histogram: 0 = default, else bits

@@ -43,6 +43,7 @@ struct ImagingState {
     unsigned int gain_lds_raised = 0;  // and ddcal_iter_kernel<D> its DD_LDS_BUDGET (bit D), jones_iter_kernel its 80 KB (bit 0)
     int64_t noise_bits = 0;           // option "noise_bits": the digit of image_stats' radix select, 8 or (else) 13 bits
     int64_t dft_slices = 0;           // option "dft_slices": the component slices of dft_predict, 0 = by (n, C), 1..64 forced
+    int64_t sources_deblend = 0;      // option "sources_deblend": find_sources splits islands at window radius 1..32, 0 = not
     int64_t mosaic_cull = 0;          // option "mosaic_cull": 1 = every tile of gridhip_mosaic walks all valid facets (the same bits)
     int64_t rm_stage = 0;             // option "rm_stage": 1 = gridhip_rmclean reads and writes the cube through LDS (the same bits)
     int64_t noisemap_hist = 0;        // option "noisemap_hist": how noise_map's node kernel builds a histogram (noisemap.hip)
@@ -663,7 +664,9 @@ int segment_scan(gridhip_ctx *ctx, int64_t nseg, const unsigned int *segcount, i
 
 // ---- source finding (sources.hip) ---------------------------------------------------------------------------------------------
 constexpr int64_t SRC_MAX_N = 46340;  // automask's limit: labels are 32-bit cell indices
-// gridhip_find_sources' argument rules (GRIDHIP_EINVAL, then GRIDHIP_EUNSUPPORTED); nothing is read; *N: the image size
+constexpr int64_t SRC_MAX_DEBLEND = 32;  // the largest window radius of the option "sources_deblend"
+// gridhip_find_sources' argument rules (GRIDHIP_EINVAL, then GRIDHIP_EUNSUPPORTED) and the option's; nothing is read; *N:
+// the image size
 int sources_check(gridhip_ctx *ctx, double theta, int64_t lam, const double *image, int64_t border, double thr_hi,
                   double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac,
                   int64_t min_cells, const double *beam, int correct, int64_t max_c, const double *comps, const double *info,
@@ -671,7 +674,8 @@ int sources_check(gridhip_ctx *ctx, double theta, int64_t lam, const double *ima
 // the segment counts and offsets of the compaction, and a root and a box per row that can be written
 size_t sources_scratch_bytes(int64_t N, int64_t max_c);
 // gridhip_find_sources_dev on checked arguments: kernels only, on ctx->stream; am_scratch: automask_scratch_bytes(N),
-// scratch: sources_scratch_bytes(N, max_c)
+// scratch: sources_scratch_bytes(N, max_c).  With the option "sources_deblend" set it takes 16 B per cell more from the
+// context's pool for the length of the call
 int sources_run(gridhip_ctx *ctx, int64_t N, double theta, const double *image, int64_t border, double thr_hi,
                 double thr_lo, double nsigma_hi, double nsigma_lo, const double *noise, double peak_frac, int64_t min_cells,
                 const double *beam, int correct, int64_t max_c, double *comps, double *info, int64_t *count, double *stats,

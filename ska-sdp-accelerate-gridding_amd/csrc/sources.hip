@@ -26,6 +26,10 @@
 // DETERMINISM.  A thread's partial sum runs over its cells in walk order, the trees are fixed, and which cells a thread
 // takes depends on the box alone: the sums are a function of the image.  There is no floating-point atomic anywhere.
 // An island whose box is huge is walked by one work-group - see DESIGN.md §9 for what that costs.
+// DEBLENDING (the option "sources_deblend" = r > 0) puts six launches in front of src_count_kernel that turn the labels
+// into `sub`, the peak each cell of K climbs to (below, "deblending"); the kernels above then run on sub as they are, on
+// roots that are peaks, and src_measure_kernel takes the island's label and its peak count for the info row.  With the
+// option at 0 none of it is launched and no scratch is drawn for it.
 #include "common.h"
 #include "imaging.h"
 
@@ -190,12 +194,195 @@ __device__ __forceinline__ double atan2_series(double y, double x)
     return y < 0.0 ? 0.0 - r : r;
 }
 
-// One work-group per row (a work-group strides over the rows when there are more rows than work-groups).
+// ---- deblending (the header's DEBLENDING): sub[k], the peak whose basin the cell k of K lies in ---------------------------------
+// Six launches in front of src_count_kernel, which then runs on `sub` in place of the labels: a root is a peak.
+//     deb_init_kernel     bmax[.] = 0, bidx[.] = INT_MAX
+//     deb_max_kernel      bmax[label] = the largest value of the island: 64-bit atomicMax of the bits (all values are > 0)
+//     deb_idx_kernel      bidx[label] = the smallest index among the cells that hold it: 32-bit atomicMin
+//     deb_up_kernel       up[k] = the highest of k and its 8 neighbours with k's label; the peak counts zeroed
+//     deb_summit_kernel   a cell with up[k] == k: the wave scans its window and the cell climbs on, is a peak (counted at
+//                         its island), or - a faint summit - hangs below the island's brightest cell
+//     deb_chase_kernel    sub[k] = the fixed point of up from k; -1 outside K
+// A cell with k's label lies in K as k does (K is whole components of L), so comparing labels is the whole test.
+// Only keys are compared and only integers are combined by atomics: sub is a function of the image.
+struct DebLayout {
+    size_t bmax, bidx, sub, total;
+};
+
+DebLayout deb_layout(int64_t N)
+{
+    DebLayout l;
+    const size_t cells = (size_t)N * N;
+    l.bmax = 0;  // (u64 per cell; after deb_idx_kernel its first 4 B per cell are the peak counts)
+    l.bidx = (cells * 8 + 255) & ~(size_t)255;
+    l.sub = l.bidx + ((cells * 4 + 255) & ~(size_t)255);
+    l.total = l.sub + ((cells * 4 + 255) & ~(size_t)255);
+    return l;
+}
+
+__device__ __forceinline__ u64 max_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void __launch_bounds__(256) deb_init_kernel(int64_t cells, const AmState *st, u64 *__restrict__ bmax, int *__restrict__ bidx)
+{
+    if (st->reason != 0) return;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < cells; k += (int64_t)gridDim.x * 256) {
+        bmax[k] = 0;
+        bidx[k] = 0x7fffffff;
+    }
+}
+
+// A wave whose 64 cells all belong to one island reduces by shuffles and sends one lane, as src_box_kernel does; a value
+// the slot already holds is not sent (the slot only rises, so a stale read can only cost an atomic, never lose one).
+__global__ void __launch_bounds__(256)
+    deb_max_kernel(int64_t cells, const AmState *st, const double *__restrict__ image, const int *__restrict__ label,
+                   const uint8_t *__restrict__ kbyte, u64 *bmax)
+{
+    if (st->reason != 0) return;
+    const int64_t step = (int64_t)gridDim.x * 256;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < cells; base += step) {  // (uniform over the work-group)
+        const int64_t k = base + threadIdx.x;
+        int L = -1;
+        u64 key = 0;
+        if (k < cells && kbyte[k] != 0) L = label[k], key = __builtin_bit_cast(u64, image[k]);
+        const int first = __shfl(L, 0);
+        if (__all(L == first)) {
+            if (first < 0) continue;
+            for (int off = 32; off > 0; off >>= 1) {
+                const u64 o = __shfl_down(key, off);
+                key = o > key ? o : key;
+            }
+            if ((threadIdx.x & 63) == 0 && key > max_load(bmax + first)) atomicMax(bmax + first, key);
+        } else if (L >= 0 && key > max_load(bmax + L)) {
+            atomicMax(bmax + L, key);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+    deb_idx_kernel(int64_t cells, const AmState *st, const double *__restrict__ image, const int *__restrict__ label,
+                   const uint8_t *__restrict__ kbyte, const u64 *__restrict__ bmax, int *bidx)
+{
+    if (st->reason != 0) return;
+    const int64_t step = (int64_t)gridDim.x * 256;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < cells; base += step) {  // (uniform over the work-group)
+        const int64_t k = base + threadIdx.x;
+        int L = -1, cand = 0x7fffffff;
+        if (k < cells && kbyte[k] != 0) {
+            L = label[k];
+            if (__builtin_bit_cast(u64, image[k]) == bmax[L]) cand = (int)k;
+        }
+        const int first = __shfl(L, 0);
+        if (__all(L == first)) {
+            if (first < 0) continue;
+            for (int off = 32; off > 0; off >>= 1) {
+                const int o = __shfl_down(cand, off);
+                cand = o < cand ? o : cand;
+            }
+            if ((threadIdx.x & 63) == 0 && cand < box_load(bidx + first)) atomicMin(bidx + first, cand);
+        } else if (L >= 0 && cand < box_load(bidx + L)) {
+            atomicMin(bidx + L, cand);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+    deb_up_kernel(int64_t N, const AmState *st, const double *__restrict__ image, const int *__restrict__ label,
+                  const uint8_t *__restrict__ kbyte, int *__restrict__ up, int *__restrict__ npk)
+{
+    if (st->reason != 0) return;
+    const int64_t cells = N * N;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < cells; k += (int64_t)gridDim.x * 256) {
+        npk[k] = 0;
+        if (kbyte[k] == 0) continue;
+        const int L = label[k];
+        const int64_t y = k / N, x = k - y * N;
+        u64 bkey = ordered_bits(image[k]);
+        int bk = (int)k;
+        for (int64_t ey = (y > 0 ? y - 1 : 0); ey <= (y < N - 1 ? y + 1 : N - 1); ++ey)
+            for (int64_t ex = (x > 0 ? x - 1 : 0); ex <= (x < N - 1 ? x + 1 : N - 1); ++ex) {
+                const int64_t e = ey * N + ex;
+                if (label[e] == L) better(ordered_bits(image[e]), (int)e, bkey, bk);
+            }
+        up[k] = bk;
+    }
+}
+
+// The summits of a wave's 64 cells are taken one after the other; the wave's lanes share the window's cells.
+__global__ void __launch_bounds__(256)
+    deb_summit_kernel(int64_t N, int r, const AmState *st, const double *__restrict__ image, const int *__restrict__ label,
+                      const uint8_t *__restrict__ kbyte, const int *__restrict__ bidx, int *up, int *npk)
+{
+    if (st->reason != 0) return;
+    const int64_t cells = N * N, step = (int64_t)gridDim.x * 256;
+    const int lane = threadIdx.x & 63;
+    const double T_hi = st->T_hi;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < cells; base += step) {  // (uniform over the work-group)
+        const int64_t k = base + threadIdx.x;
+        u64 todo = __ballot(k < cells && kbyte[k] != 0 && up[k] == (int)k);  // (up[k] is written by k's own lane alone)
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int ks = __shfl((int)k, src), L = label[ks];
+            const int ys = (int)(ks / N), xs = (int)(ks - (int64_t)ys * N);
+            const int y0 = ys - r > 0 ? ys - r : 0, y1 = ys + r < N - 1 ? ys + r : (int)N - 1;
+            const int x0 = xs - r > 0 ? xs - r : 0, x1 = xs + r < N - 1 ? xs + r : (int)N - 1;
+            const int w = x1 - x0 + 1, n = w * (y1 - y0 + 1);  // at most 65 x 65
+            u64 bkey = 0;
+            int bk = -1;
+            for (int i = lane; i < n; i += 64) {
+                const int64_t e = (int64_t)(y0 + i / w) * N + x0 + i % w;
+                if (label[e] == L) better(ordered_bits(image[e]), (int)e, bkey, bk);
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                const u64 okey = __shfl_down(bkey, o);
+                const int ok = __shfl_down(bk, o);
+                better(okey, ok, bkey, bk);
+            }
+            bk = __shfl(bk, 0);  // W(ks): never -1, the window holds ks
+            if (lane == src) {
+                if (bk >= 0 && bk != ks)
+                    up[ks] = bk;
+                else if (image[ks] > T_hi)
+                    atomicAdd(npk + L, 1);
+                else
+                    up[ks] = bidx[L];
+            }
+        }
+    }
+}
+
+// An ascent ends because every step goes to a strictly higher cell.  The fixed point found is stored over up[k] as well, so
+// that an ascent that starts later through k is shorter: a reader finds the old pointer or the new one, both lead to the same
+// fixed point, and a fixed point's own pointer is never written.  These loads are relaxed agent-scope atomics for that.
+__global__ void __launch_bounds__(256)
+    deb_chase_kernel(int64_t cells, const AmState *st, const uint8_t *__restrict__ kbyte, int *up, int *__restrict__ sub)
+{
+    if (st->reason != 0) return;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < cells; k += (int64_t)gridDim.x * 256) {
+        if (kbyte[k] == 0) {
+            sub[k] = -1;
+            continue;
+        }
+        int x = (int)k;
+        int hops = 0;
+        for (;; ++hops) {
+            const int p = box_load(up + x);
+            if (p == x || p < 0 || p >= cells) break;  // (p outside the image cannot be: it would end the loop, never extend it)
+            x = p;
+        }
+        if (hops > 1) __hip_atomic_store(up + k, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sub[k] = x;
+    }
+}
+
+// One work-group per row (a work-group strides over the rows when there are more rows than work-groups).  With deblending
+// `label` is sub, a root is a peak, island[root] is its island's label and npk[that] the island's peaks; else both are NULL.
 __global__ void __launch_bounds__(256)
     src_measure_kernel(int64_t N, double theta, int64_t border, const AmState *st, const double *__restrict__ image,
                        const int *__restrict__ label, const int *__restrict__ roots, const int *__restrict__ boxes,
                        const int64_t *__restrict__ count, int64_t max_c, const double *__restrict__ beam, int correct,
-                       double *__restrict__ comps, double *__restrict__ info)
+                       const int *__restrict__ island, const int *__restrict__ npk, double *__restrict__ comps,
+                       double *__restrict__ info)
 {
 #pragma clang fp contract(off)
     __shared__ u64 pk_key[4];
@@ -305,6 +492,8 @@ __global__ void __launch_bounds__(256)
             }
         }
         if (y0 <= border || x0 <= border || y1 >= N - 1 - border || x1 >= N - 1 - border) flags |= 2;
+        const int isl = island ? island[root] : root;
+        if (npk && npk[isl] > 1) flags |= 8;
         // 5  the position
         const double half = (double)(N / 2);
         double *o = comps + row * GRIDHIP_COMP_DOUBLES;
@@ -316,7 +505,7 @@ __global__ void __launch_bounds__(256)
         o[9] = 0.0;
         if (info) {
             double *q = info + row * SRC_INFO;
-            q[0] = (double)root, q[1] = n, q[2] = (double)yp, q[3] = (double)xp, q[4] = Pi;
+            q[0] = (double)isl, q[1] = n, q[2] = (double)yp, q[3] = (double)xp, q[4] = Pi;
             q[5] = S, q[6] = Sx, q[7] = Sy, q[8] = Sxx, q[9] = Sxy, q[10] = Syy;
             q[11] = (double)y0, q[12] = (double)y1, q[13] = (double)x0, q[14] = (double)x1;
             q[15] = (double)flags;
@@ -353,6 +542,8 @@ int sources_check(gridhip_ctx *ctx, double theta, int64_t lam, const double *ima
                   const int64_t *count, const double *stats, int64_t *N)
 {
     *N = gridhip_image_size(theta, lam);
+    if (ctx->img->sources_deblend > SRC_MAX_DEBLEND)
+        return fail(ctx, GRIDHIP_EINVAL, "find_sources: option 'sources_deblend' above %d", (int)SRC_MAX_DEBLEND);
     if (!count || !stats || max_c < 0 || (max_c > 0 && !comps) || (correct != 0 && correct != 1))
         return fail(ctx, GRIDHIP_EINVAL, "find_sources: max_c >= 0, comps, count, stats, correct in {0, 1}");
     GH_CHECK(automask_levels_check(ctx, "find_sources", *N, image, border, thr_hi, thr_lo, nsigma_hi, nsigma_lo, noise,
@@ -384,19 +575,37 @@ int sources_run(gridhip_ctx *ctx, int64_t N, double theta, const double *image, 
     int *roots = reinterpret_cast<int *>(base + l.roots), *boxes = reinterpret_cast<int *>(base + l.boxes);
     const int64_t cells = N * N;
     const AmState *st = p.state;
-    const dim3 seggrid = grid_for(ctx, l.nseg, 1);
+    const dim3 seggrid = grid_for(ctx, l.nseg, 1), flat = grid_for(ctx, cells);
+    const uint8_t *kbyte = p.kbyte;
     hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(src_count_kernel, seggrid, dim3(256), 0, s, cells, st, (const int *)p.label, (const uint8_t *)p.kbyte,
-                       l.nseg, segcount);
+    // what the kernels below take for labels: the islands', or with deblending the basins'
+    const int *lab = p.label, *island = nullptr, *npk = nullptr;
+    DevBuf deb;  // (handed back to the pool at the return: what is enqueued later on this stream runs after these kernels)
+    const int r = (int)ctx->img->sources_deblend;
+    if (r > 0) {
+        const DebLayout d = deb_layout(N);
+        GH_CHECK(deb.alloc(ctx, d.total));
+        char *db = deb.as<char>();
+        u64 *bmax = reinterpret_cast<u64 *>(db + d.bmax);
+        int *bidx = reinterpret_cast<int *>(db + d.bidx), *sub = reinterpret_cast<int *>(db + d.sub);
+        int *peaks = reinterpret_cast<int *>(bmax), *up = p.spare;
+        hipLaunchKernelGGL(deb_init_kernel, flat, dim3(256), 0, s, cells, st, bmax, bidx);
+        hipLaunchKernelGGL(deb_max_kernel, flat, dim3(256), 0, s, cells, st, image, lab, kbyte, bmax);
+        hipLaunchKernelGGL(deb_idx_kernel, flat, dim3(256), 0, s, cells, st, image, lab, kbyte, (const u64 *)bmax, bidx);
+        hipLaunchKernelGGL(deb_up_kernel, flat, dim3(256), 0, s, N, st, image, lab, kbyte, up, peaks);
+        hipLaunchKernelGGL(deb_summit_kernel, flat, dim3(256), 0, s, N, r, st, image, lab, kbyte, (const int *)bidx, up, peaks);
+        hipLaunchKernelGGL(deb_chase_kernel, flat, dim3(256), 0, s, cells, st, kbyte, up, sub);
+        island = lab, npk = peaks, lab = sub;
+    }
+    hipLaunchKernelGGL(src_count_kernel, seggrid, dim3(256), 0, s, cells, st, lab, kbyte, l.nseg, segcount);
     GH_CHECK(segment_scan(ctx, l.nseg, segcount, offs, count));
     if (max_c > 0) {
-        hipLaunchKernelGGL(src_scatter_kernel, seggrid, dim3(256), 0, s, N, st, (const int *)p.label,
-                           (const uint8_t *)p.kbyte, l.nseg, (const int64_t *)offs, max_c, p.spare, roots, boxes);
-        hipLaunchKernelGGL(src_box_kernel, grid_for(ctx, cells), dim3(256), 0, s, N, st, (const int *)p.label,
-                           (const uint8_t *)p.kbyte, (const int *)p.spare, max_c, boxes);
-        hipLaunchKernelGGL(src_measure_kernel, grid_for(ctx, max_c, 1), dim3(256), 0, s, N, theta, border, st, image,
-                           (const int *)p.label, (const int *)roots, (const int *)boxes, (const int64_t *)count, max_c, beam,
-                           correct, comps, info);
+        hipLaunchKernelGGL(src_scatter_kernel, seggrid, dim3(256), 0, s, N, st, lab, kbyte, l.nseg, (const int64_t *)offs, max_c,
+                           p.spare, roots, boxes);
+        hipLaunchKernelGGL(src_box_kernel, flat, dim3(256), 0, s, N, st, lab, kbyte, (const int *)p.spare, max_c, boxes);
+        hipLaunchKernelGGL(src_measure_kernel, grid_for(ctx, max_c, 1), dim3(256), 0, s, N, theta, border, st, image, lab,
+                           (const int *)roots, (const int *)boxes, (const int64_t *)count, max_c, beam, correct, island, npk,
+                           comps, info);
     }
     hipLaunchKernelGGL(src_stats_kernel, dim3(1), dim3(1), 0, s, st, (const int64_t *)count, max_c, (const double *)comps,
                        stats);

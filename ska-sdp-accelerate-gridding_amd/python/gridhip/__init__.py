@@ -46,7 +46,25 @@ from ._marshal import TEC_HEAD, TEC_KAPPA, TEC_MAX_CELLS, TEC_MAX_DELAYS, TEC_PE
 __all__ = ["Context", "default_context", "grid", "convgrid", "convgrid2", "degrid2", "GridHipError", "components", "flag_groups", "ddcal_lds_antennas", "jonescal_lds_antennas",
            "rotation_to", "rotation_radec", "average_groups", "facet_grid", "joint_deconvolve", "sumthreshold_tile",
            "waterfall_layout", "rm_tile", "faraday_grid", "contsub_tile", "channel_coordinate",
-           "fringe_tile", "fringe_grid", "tec_tile", "tec_grid", "tec_clock", "tec_coordinates", "TEC_KAPPA", "idg_trusted"]
+           "fringe_tile", "fringe_grid", "tec_tile", "tec_grid", "tec_clock", "tec_coordinates", "TEC_KAPPA", "idg_trusted",
+           "SOURCE_BLENDED"]
+
+SOURCE_BLENDED = 8  # flag bit 3 of a find_sources info row: the row's island was split into several rows (deblend > 0)
+
+
+def _deblended(ctx, deblend, call):
+    """call() with the option "sources_deblend" at `deblend`, put back afterwards; 0 leaves the option alone"""
+    deblend = int(deblend)
+    if deblend < 0:
+        raise ValueError("deblend must be >= 0")
+    if deblend == 0:
+        return call()
+    before = ctx.get_option("sources_deblend")
+    ctx.set_option("sources_deblend", deblend)
+    try:
+        return call()
+    finally:
+        ctx.set_option("sources_deblend", before)
 
 
 class Context(Handle):
@@ -1256,7 +1274,7 @@ class Context(Handle):
         return out, (int(count[0]) if be is HOST else count)
 
     def find_sources(self, theta, lam, image, beam=None, noise=None, border=0, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0,
-                     min_cells=1, correct=True, max_sources=1024, out=None, info=True):
+                     min_cells=1, correct=True, max_sources=1024, out=None, info=True, deblend=0):
         """A catalogue of the N x N float64 map `image`, N = image_size(theta, lam) (gridhip_find_sources[_dev];
         include/gridhip.h, "source finding"): the islands of automask's levels - above T_lo = max(thr[1], nsigma[1] * sigma,
         peak_frac * peak) around at least `min_cells` connected cells above T_hi, no growing - each measured by its moments
@@ -1268,14 +1286,19 @@ class Context(Handle):
         (out: the array to write; a new one of zeros when None); count the islands found - an int for numpy, one int64 cuda
         element for torch tensors, which dft_predict takes as `count`; info (None with info=False) the (max_sources, 16) rows
         [label, ncells, yp, xp, peak, S, Sx, Sy, Sxx, Sxy, Syy, y0, y1, x0, x1, flags (1 point, 2 at the edge, 4 beam
-        unusable)]; stats = [T_hi, T_lo, peak, islands found, rows written, of them points, their summed flux, reason].
+        unusable, 8 = SOURCE_BLENDED)]; stats = [T_hi, T_lo, peak, islands found, rows written, of them points, their
+        summed flux, reason].
+        deblend = r in 1 .. 32 sets the option "sources_deblend" for this call and puts it back afterwards (0 leaves the
+        option as it is): an island with several peaks - local maxima above T_hi that no higher cell of the island lies
+        within r cells of - becomes one row per peak, in ascending order of the peaks' cells, each measured over the cells
+        that climb to it; the rows of one island share its label and carry flag 8, and count and the stats count rows.
         numpy arrays take the synchronous host form; torch cuda tensors the asynchronous one: nothing is read back, and
         with `noise` a device element the call can be captured."""
         be = backend(image)
         N = self.image_size(theta, lam)
         image = image_of(be, image, (N, N), "image")
         args = source_args(be, thr, nsigma, noise, peak_frac, min_cells, beam, correct, max_sources, out, info, image)
-        self._call(be, "find_sources", float(theta), int(lam), image, int(border), *args)
+        _deblended(self, deblend, lambda: self._call(be, "find_sources", float(theta), int(lam), image, int(border), *args))
         comps, table, count, stats = args[-4:]
         return comps, (int(count[0]) if be is HOST else count), table, stats
 
@@ -1556,15 +1579,16 @@ class Imager(_Bound):
         return mask, astats, snr, nstats
 
     def find_sources(self, image, beam=None, noise=None, border=0, thr=(0, 0), nsigma=(5, 2.5), peak_frac=0, min_cells=1,
-                     correct=True, max_sources=1024, out=None, info=True):
+                     correct=True, max_sources=1024, out=None, info=True, deblend=0):
         """Context.find_sources of an N x N cuda float64 map with the imager's theta, lam and its own scratch
-        (gridhip_imager_find_sources_dev): asynchronous, and capturable after a first call with as many rows.  Returns
-        (comps, count, info, stats)."""
+        (gridhip_imager_find_sources_dev): asynchronous, and capturable after a first call with as many rows.  deblend:
+        the context's option "sources_deblend" for this call, as for Context.find_sources.  Returns (comps, count, info,
+        stats)."""
         self._open()
         be, NN = device(), (self.N, self.N)
         self._ok(image, be.f64, NN, "image")
         args = source_args(be, thr, nsigma, noise, peak_frac, min_cells, beam, correct, max_sources, out, info, self.device)
-        self._call(be, "imager_find_sources", image, int(border), *args)
+        _deblended(self._ctx, deblend, lambda: self._call(be, "imager_find_sources", image, int(border), *args))
         return args[-4], args[-2], args[-3], args[-1]
 
     def clean(self, image, model=None, gain=0.1, threshold=0.0, niter=100, border=0, patch=0, mask=None, nsigma=0.0,

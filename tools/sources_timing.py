@@ -24,6 +24,7 @@ THETA, LAM = 0.08, 30000  # image_size = 2400
 STEPS = [("noise", 300), ("islands", 300), ("all_set", 300)]
 ROWS = 4096
 FWHM = 3.0  # the beam, in cells
+DEBLEND = [0, 2, 8]  # the window radii of the option "sources_deblend" that are timed; 0 = off
 
 
 def step(name, reps):
@@ -57,8 +58,21 @@ def step(name, reps):
     row["automask_graph"] = timed(torch, graph.replay, mask.zero_, reps)
     row["find_sources_over_automask_graph"] = row["find_sources_graph"]["median_ms"] / row["automask_graph"]["median_ms"]
     row["find_sources_over_automask_eager"] = row["find_sources_eager"]["median_ms"] / row["automask_eager"]["median_ms"]
+    rows = [row]
+    for r in DEBLEND:  # the same call with the option "sources_deblend" at r (0: the figures above, taken again)
+        split = lambda: ctx.find_sources(THETA, LAM, img, beam, deblend=r, **src)  # noqa: E731
+        d = {"what": "find_sources_deblend", "image": name, "N": N, "device": row["device"], "rows": ROWS, "deblend": r}
+        d["eager"] = timed(torch, split, lambda: None, reps)
+        # (the option is read when a call is enqueued, and `deblend` puts it back itself: the capture records the six launches)
+        graph, (_, count, info, st) = graphed(torch, split)
+        d["graph"] = timed(torch, graph.replay, lambda: None, reps)
+        d["stats"] = st.cpu().tolist()
+        written = int(d["stats"][4])
+        d["blended_rows"] = int((info[:written, 15].to(torch.int64) & 8).ne(0).sum().item())
+        d["graph_over_off"] = d["graph"]["median_ms"] / row["find_sources_graph"]["median_ms"]
+        rows.append(d)
     ctx.close()
-    return [row]
+    return rows
 
 
 def main():
